@@ -77,6 +77,9 @@ PRIME_TO = 12          # untimed batches a workload has seen before its timed st
 # 7.71 7.63 7.66 7.67 7.68 / 7.72 7.64 7.64 7.64 7.66; the later workloads of the same process never showed one)
 PRIME_PROCESS_TO = int(os.environ.get("FEM_BENCH_PRIME", "100"))
 _batches_seen = [0]    # by this process, any workload
+DUMP_STRANDS = 1 << 16  # --dump-outputs: (read, strand) pairs of the last timed step's result written, a fixed seeded sample
+DUMP_SEED = 1234
+DUMP_BYTES = 64 << 20   # ... and all files together at most this large
 
 WORKLOADS = {
     "c2": dict(seed=2, seq_lens=[5_000_000], L=100, e=3,
@@ -154,8 +157,38 @@ class Rank:
         self.dist = self.world > 1 or os.environ.get("FEM_BENCH_FORCE_DIST") == "1"
 
 
-def run_workload(key, dev, data, rk, steps, warmup, batch, torch, dist, red_dev, threads, reps=1, compare_forms=False):
-    """Pipeline measurement + resident-kernel replay of one workload on this rank's device.  `data` = (text, off, lens)."""
+def dump_outputs(res, out_dir):
+    """--dump-outputs: what the last timed step handed its caller (fem_batch_result or fem_batch_packed), regrouped in
+    (read, strand) order, for a fixed seeded sample of the batch's strands, as float64 .npy files:
+        stats       the batch's five counters (reads, mapped reads, pre-filter, candidates, mappings)
+        strand      the sampled strand indices, ascending (read = strand // 2, reverse strand = strand % 2)
+        cand_count  candidates of each sampled strand
+        cand, ed, end  those candidates one after the other: sequence << 32 | offset, edit distance (255: none within e),
+                       end offset (0 where ed is 255, as the oracle has it: the library leaves it undefined there)
+    Whole strands are kept in ascending order until DUMP_BYTES would be exceeded."""
+    import numpy as np
+    off, cand, ed, end = res.per_strand()
+    off = off.astype(np.int64)
+    n2 = len(off) - 1
+    rng = np.random.default_rng(DUMP_SEED)
+    strands = np.sort(rng.choice(n2, size=min(n2, DUMP_STRANDS), replace=False))
+    cnt = off[strands + 1] - off[strands]
+    fit = np.searchsorted(np.cumsum(2 + 3 * cnt), (DUMP_BYTES - 4096) // 8, side="right")  # (the five counters, six headers)
+    strands, cnt = strands[:fit], cnt[:fit]
+    first = np.zeros(len(cnt), dtype=np.int64)
+    first[1:] = np.cumsum(cnt)[:-1]
+    sel = np.arange(int(cnt.sum()), dtype=np.int64) + np.repeat(off[strands] - first, cnt)
+    ed_s = ed[sel]
+    end_s = np.where(ed_s != 0xFF, end[sel], 0)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in (("stats", res.stats), ("strand", strands), ("cand_count", cnt), ("cand", cand[sel]), ("ed", ed_s), ("end", end_s)):
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
+    return {"dir": out_dir, "strands": int(len(strands)), "of_strands": n2, "candidates": int(len(sel)), "sample_seed": DUMP_SEED}
+
+
+def run_workload(key, dev, data, rk, steps, warmup, batch, torch, dist, red_dev, threads, reps=1, compare_forms=False, dump_dir=None):
+    """Pipeline measurement + resident-kernel replay of one workload on this rank's device.  `data` = (text, off, lens).
+    dump_dir: write the last timed step's result there (dump_outputs)."""
     import numpy as np
     from fem_amd import host
     w = WORKLOADS[key]
@@ -190,6 +223,7 @@ def run_workload(key, dev, data, rk, steps, warmup, batch, torch, dist, red_dev,
     seen = [[] for _ in range(N_SLOTS)]  # the five counters of every batch retired, per slot
     keep = {}                            # slot -> True: keep a copy of that slot's next full result (the self-check)
     kept = {}
+    last_res = [None]                    # the latest full result retired (views of the slot's pinned buffers)
 
     def submit(i):
         s = i % N_SLOTS
@@ -221,6 +255,7 @@ def run_workload(key, dev, data, rk, steps, warmup, batch, torch, dist, red_dev,
             # slot (include/fem_hip.h) — packed on the device and sent home behind the batch's kernels
             r = dev.fetch_packed(slot=sl, copy=False)
             host_s[1] += time.perf_counter() - t_in
+            last_res[0] = r
             d2h_bytes[0] = r.d2h_bytes
             seen[sl].append(r.stats.copy())
             if keep.pop(sl, False):
@@ -229,6 +264,7 @@ def run_workload(key, dev, data, rk, steps, warmup, batch, torch, dist, red_dev,
             return r.stats
         r = dev.fetch(slot=sl, copy=False)  # waits; the per-candidate outcome is (or comes) in pinned host memory
         host_s[1] += time.perf_counter() - t_in
+        last_res[0] = r
         d2h_bytes[0] = 16 * r.n_reads + 11 * r.n_candidates
         seen[sl].append(r.stats.copy())
         if keep.pop(sl, False):
@@ -307,6 +343,8 @@ def run_workload(key, dev, data, rk, steps, warmup, batch, torch, dist, red_dev,
             job, last_stats = job_r, last_r
             d2h_timed = d2h_bytes[0]  # (of the timed steps' form; the comparison forms below fetch the plain arrays)
     dev.set_timing(False)
+    # the last timed step was retired last, and its slot has not been staged or mapped since: its views are still its result
+    dumped = dump_outputs(last_res[0], dump_dir) if dump_dir else None
     # `value` is the MEDIAN of the timed repetitions (each exactly `steps` steps between fences; all of them in spread.values).
     # Until round 5's last day it was the first one; since then the GPU boxes show one stall of 20-50 ms every half second or so
     # (a host call or a wait that returns late: kernel times unchanged, no cgroup throttling, the previous day's library shows
@@ -483,7 +521,7 @@ def run_workload(key, dev, data, rk, steps, warmup, batch, torch, dist, red_dev,
         "fetch_form": "fem_dev_fetch_packed" if packed_fetch else "fem_dev_fetch",
         "stage_reads_mreads": None if stage_reads_rate is None else round(stage_reads_rate, 3),
         "zero_copy_ascii_mreads": None if zero_copy is None else round(zero_copy, 3), "zero_copy_h2d_bytes_per_step": int(h2d_zero_copy),
-        "priming_steps": priming, "pipeline_check": pipe_check,
+        "priming_steps": priming, "pipeline_check": pipe_check, "dumped_outputs": dumped,
         "distinct_reads": "%d distinct reads per GPU (%d slots x %d), each slot's batch mapped again every %d steps"
                           % (N_SLOTS * batch, N_SLOTS, batch, N_SLOTS),
         # what this rank's host thread does per step: the staging call (2-bit packing of the batch on the library's threads,
@@ -734,6 +772,8 @@ def main():
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-compare", action="store_true", help="skip the stage_reads / zero-copy comparison forms (N = 1 runs them by default)")
     ap.add_argument("--no-e2e", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the headline workload's result of its last timed step (a fixed "
+                                                          "seeded sample of its strands) to DIR/<name>.npy, float64, at most 64 MB")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0 or args.batch < 1:
         sys.exit("bench.py: --steps >= 1, --warmup >= 0, --batch >= 1")
@@ -842,7 +882,8 @@ def main():
             return
         res = run_workload(key, dev, (text, off, lens), rk, steps, warmup, args.batch, torch, dist, red_dev, gen_threads,
                            reps=1 if "repeats" in w else args.reps,
-                           compare_forms=None if args.no_compare or "repeats" in w else ("all" if rk.world == 1 else "stage_reads"))
+                           compare_forms=None if args.no_compare or "repeats" in w else ("all" if rk.world == 1 else "stage_reads"),
+                           dump_dir=args.dump_outputs if key == args.workload and rk.rank == 0 else None)
         res["index_entries"] = n_occ
         results[key] = res
         log("rank %d %s: pipeline %.1f Mreads/s, kernels only %.1f, %s" % (rk.rank, key, res["value"], res["kernel_only_mreads"], res["kernel_ms_per_launch"]))

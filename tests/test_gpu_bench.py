@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -87,3 +88,26 @@ def test_headline_workload_is_c3_with_two_seed_kernels():
     assert d["roofline"]["algorithmic_bytes_per_launch"] == 8 * c[2]
     assert d["roofline"]["implementation_bytes_per_launch"] == 4 * c[2] + (8 * 6 * 5 + 8) * 100000
     assert c[1] > 0.97 * c[0]  # 98.4 % of the reads map on the 3 Gbp reference
+
+
+def test_dump_outputs_are_the_last_steps_result_and_repeat(tmp_path):
+    # --dump-outputs writes the last timed step's result (a fixed sample of its strands).  3 and 7 steps both end on slot 2,
+    # i.e. on the same batch, so two runs of different lengths must write the same arrays
+    runs = []
+    for steps in (3, 7):
+        out = tmp_path / ("s%d" % steps)
+        d = _run(["--workload", "c2", "--reps", "1", "--steps", str(steps), "--warmup", "1", "--batch", "100000", "--extra", "none",
+                  "--no-cpu", "--no-e2e", "--no-compare", "--dump-outputs", str(out)])
+        assert d["steps"] == steps and d["ms_per_step"] > 0 and d["config"]["counters"]["reads"] == steps * 100000
+        files = {f.name[:-4]: f for f in out.iterdir()}
+        assert set(files) == {"stats", "strand", "cand_count", "cand", "ed", "end"}
+        assert sum(f.stat().st_size for f in files.values()) <= 64 << 20
+        arr = {k: np.load(str(f)) for k, f in files.items()}
+        assert all(a.dtype in (np.float32, np.float64) for a in arr.values())
+        assert list(arr["stats"]) == d["config"]["counters_last_step_per_gpu"]
+        assert len(arr["strand"]) == len(arr["cand_count"]) == 1 << 16 and np.all(np.diff(arr["strand"]) > 0)
+        assert arr["cand_count"].sum() == len(arr["cand"]) == len(arr["ed"]) == len(arr["end"]) > 0
+        assert np.all((arr["ed"] <= 3) | (arr["ed"] == 255)) and np.any(arr["ed"] <= 3)
+        runs.append(arr)
+    for k in runs[0]:
+        assert np.array_equal(runs[0][k], runs[1][k]), k

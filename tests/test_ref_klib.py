@@ -1,5 +1,5 @@
 """libfemhost's sequence readers and the mapping sort against THE REFERENCE'S OWN klib code: oracle/_ref/libfemref_klib.so
-is the reference's src/kseq.h and src/ksort.h, compiled from where they lie under /root/reference behind the harness
+is the reference's src/kseq.h and src/ksort.h, compiled from where they lie in the reference's tree behind the harness
 oracle/ref_klib.c (`make -C oracle ref`; everything else of the reference needs htslib and cannot be built here).
 
   * records: kseq_read as src/sequence_batch.c:47-66 drives it (zero-length records skipped, any return below -1 fatal)
@@ -7,10 +7,14 @@ oracle/ref_klib.c (`make -C oracle ref`; everything else of the reference needs 
   * order of a read's mappings: radix_sort_mapping (src/align.c:53-57) vs the oracle's restatement, which the host tail
     and the device ordering kernel are compared with elsewhere (tests/test_host.py, tests/test_gpu_tail.py)
 
-Without the library (a checkout that never saw /root/reference) the committed vectors under tests/golden/klib_*.npz,
-made from it by tests/golden/make_klib_golden.py, stand in."""
+Without the library (a checkout that never saw the reference's sources) what it returned stands in:
+tests/golden/klib_records.npz holds, for every input these tests give it (keyed by a hash of the input), SHA-1
+fingerprints of what they compare: the loader's view of a file's records, the sort's permutation.  The vectors of
+tests/golden/klib_kseq.npz and klib_sort.npz are compared in full.  All are made by tests/golden/make_klib_golden.py."""
 import gzip
+import hashlib
 import os
+import struct
 
 import numpy as np
 import pytest
@@ -20,7 +24,86 @@ from oracle import fem_oracle as fo
 from oracle import ref_klib
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-needs_ref = pytest.mark.skipif(not ref_klib.available(), reason="oracle/_ref/libfemref_klib.so not built (no /root/reference here)")
+RECORDS = os.path.join(GOLDEN, "klib_records.npz")
+_stored = {}
+
+
+def input_key(kind, data):
+    return hashlib.sha1(kind + b"\0" + data).digest()[:8]
+
+
+def file_key(path):
+    data = open(path, "rb").read()
+    return input_key(b"gz", gzip.decompress(data)) if data[:2] == b"\x1f\x8b" else input_key(b"raw", data)
+
+
+def fingerprint(fields):
+    """SHA-1 (first 16 bytes) of a sequence of byte strings, each with its length; None is told apart from b""."""
+    h = hashlib.sha1()
+    for f in fields:
+        h.update(struct.pack("<q", -1 if f is None else len(f)))
+        h.update(f or b"")
+    return h.digest()[:16]
+
+
+def view_fingerprints(records):
+    """(names and sequences, qualities) of (name, sequence, quality) records: what same_records compares."""
+    return (fingerprint([x for r in records for x in (r[0], r[1])]), fingerprint([r[2] for r in records]))
+
+
+class StoredView:
+    """The loader's view of kseq_read's records (loader_view) of a file, as klib_records.npz holds it: how many records,
+    whether all have qualities, and the fingerprints of view_fingerprints."""
+
+    def __init__(self, n, all_qual, names_seqs, quals):
+        self.n, self.all_qual, self.names_seqs, self.quals = n, all_qual, names_seqs, quals
+
+    def __len__(self):
+        return self.n
+
+    @classmethod
+    def of(cls, view):
+        ns, q = view_fingerprints([(r[0], r[2], r[3]) for r in view])
+        all_qual = all(r[3] is not None for r in view)
+        return cls(len(view), all_qual, ns, q if all_qual and view else bytes(16))  # (qualities compared only then)
+
+
+def stored():
+    """{"kseq": {key: (StoredView, last_rc)}, "sort": {key: fingerprint of perm}} (format: make_klib_golden.py)."""
+    if not _stored:
+        g = np.load(RECORDS)
+        _stored["kseq"] = {k.tobytes(): (StoredView(int(n), bool(aq), ns.tobytes(), q.tobytes()), int(rc))
+                           for k, n, aq, ns, q, rc in zip(g["kseq_key"], g["n_records"], g["all_qual"], g["names_seqs"],
+                                                          g["quals"], g["last_rc"])}
+        _stored["sort"] = {k.tobytes(): f.tobytes() for k, f in zip(g["sort_key"], g["perm"])}
+    return _stored
+
+
+def perm_fingerprint(perm):
+    return fingerprint([np.ascontiguousarray(perm, dtype="<u4").tobytes()])
+
+
+def ref_view(path):
+    """(loader's view of the reference's kseq_read records, fatal): live from oracle/_ref where it is built, else what it
+    returned for the same input (a StoredView)."""
+    if ref_klib.available():
+        return loader_view(*ref_klib.kseq_records(path))
+    got = stored()["kseq"].get(file_key(path))
+    assert got is not None, "no stored kseq result for %s: tests/golden/make_klib_golden.py makes them" % path
+    return got[0], got[1] != -1
+
+
+def same_sort(keys, got_k, got_perm):
+    """The oracle's sort of `keys` against the reference's radix_sort_mapping, live or by its stored permutation."""
+    if ref_klib.available():
+        want_k, want_perm = ref_klib.radix_sort(keys)
+        assert np.array_equal(want_k, got_k)
+        assert np.array_equal(want_perm, got_perm), "order among equal keys"
+        return
+    want = stored()["sort"].get(input_key(b"sort", np.ascontiguousarray(keys, dtype=np.uint64).tobytes()))
+    assert want is not None, "no stored radix sort result for these %d keys" % len(keys)
+    assert np.array_equal(keys[got_perm.astype(np.int64)], got_k)
+    assert perm_fingerprint(got_perm) == want, "order among equal keys"
 
 
 def loader_view(records, last_rc):
@@ -48,13 +131,20 @@ def ours_planned(path, approx, threads):
     return out, False
 
 
-def same_records(ref, mine):
-    all_qual = all(r[3] is not None for r in ref)
+def same_records(ref, mine, quals=True):
+    # (a batch keeps its qualities only if every record has them, fem_host.cc finish_seqset: they are compared then only)
     assert len(ref) == len(mine)
+    if isinstance(ref, StoredView):
+        names_seqs, q = view_fingerprints(mine)
+        assert names_seqs == ref.names_seqs
+        if quals and ref.all_qual and ref.n:
+            assert q == ref.quals
+        return
+    all_qual = all(r[3] is not None for r in ref)
     for (name, _comment, seq, qual), (n2, s2, q2) in zip(ref, mine):
         assert name == n2 and seq == s2
-        if all_qual and ref:
-            assert qual == q2  # (a batch keeps its qualities only if every record has them, fem_host.cc finish_seqset)
+        if quals and all_qual and ref:
+            assert qual == q2
 
 
 HAND_MADE = {
@@ -81,7 +171,6 @@ HAND_MADE = {
 }
 
 
-@needs_ref
 @pytest.mark.parametrize("name", sorted(HAND_MADE))
 def test_readers_follow_kseq_on_hand_made_files(tmp_path, name):
     data = HAND_MADE[name]
@@ -89,7 +178,7 @@ def test_readers_follow_kseq_on_hand_made_files(tmp_path, name):
         p = str(tmp_path / (name + (".fq.gz" if gz else ".fq")))
         with (gzip.open(p, "wb") if gz else open(p, "wb")) as f:
             f.write(data)
-        ref, fatal = loader_view(*ref_klib.kseq_records(p))
+        ref, fatal = ref_view(p)
         mine, failed = ours_sequential(p)
         assert failed == fatal, name
         if not fatal:
@@ -138,7 +227,6 @@ def _random_file(rng):
     return bytes(data)
 
 
-@needs_ref
 def test_readers_follow_kseq_on_random_damaged_files(tmp_path):
     rng = np.random.default_rng(2024)
     n_fatal = n_ok = 0
@@ -147,7 +235,7 @@ def test_readers_follow_kseq_on_random_damaged_files(tmp_path):
         p = str(tmp_path / ("f%d.fq" % case))
         with open(p, "wb") as f:
             f.write(data)
-        ref, fatal = loader_view(*ref_klib.kseq_records(p))
+        ref, fatal = ref_view(p)
         mine, failed = ours_sequential(p)
         assert failed == fatal, (case, data)
         if not fatal:
@@ -181,14 +269,11 @@ def _oracle_sort(keys):
     return k, perm
 
 
-@needs_ref
 def test_mapping_order_follows_the_reference_radix_sort():
     n_tied = 0
     for keys in _sort_cases():
-        want_k, want_perm = ref_klib.radix_sort(keys)
         got_k, got_perm = _oracle_sort(keys)
-        assert np.array_equal(want_k, got_k)
-        assert np.array_equal(want_perm, got_perm), "order among equal keys"
+        same_sort(keys, got_k, got_perm)
         n_tied += len(keys) - len(np.unique(keys))
     assert n_tied > 5000
 
@@ -243,7 +328,6 @@ def _random_fasta(rng):
     return data[:-1] if rng.random() < 0.2 and data.endswith(b"\n") else data
 
 
-@needs_ref
 def test_parallel_fasta_reader_follows_kseq(tmp_path, monkeypatch):
     # fem_seqfile_read on a plain FASTA file is read_fasta_parallel (fem_host.cc) when the file is regular enough, the
     # sequential reader otherwise: either way kseq's records.  Small pieces so that every body is cut many times.
@@ -255,12 +339,11 @@ def test_parallel_fasta_reader_follows_kseq(tmp_path, monkeypatch):
         p = str(tmp_path / ("r%d.fa" % case))
         with open(p, "wb") as f:
             f.write(data)
-        ref, fatal = loader_view(*ref_klib.kseq_records(p))
+        ref, fatal = ref_view(p)
         mine, failed = ours_sequential(p)
         assert failed == fatal, (case, data)
         if not fatal:
             assert len(ref) == len(mine), (case, data)
-            for (name, _c, seq, _q), (n2, s2, _q2) in zip(ref, mine):
-                assert name == n2 and seq == s2, (case, data)
+            same_records(ref, mine, quals=False)
             n_multi += len(ref) > 1
     assert n_multi > 300
