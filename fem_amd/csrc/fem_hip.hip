@@ -41,7 +41,7 @@ constexpr uint32_t kMaxReadLen = 1024;
 constexpr size_t kFrontPad = 16;  // kernels fetch a reverse-strand chunk from up to 15 bytes in front of a read
 constexpr uint32_t kXcapSmall = 512, kFcap = 128, kCcap = 128;
 
-constexpr int kTimedKernels = 10;  // fem_dev_kernel_time ids: 0 seed (join), 1 verify, 2 generic seed, 3-5 tail, 6 pack_results_kernel (round 5; the count kernel of rounds 1-2 before), 7 SAM text, 8 seed selection
+constexpr int kTimedKernels = 10;  // fem_dev_kernel_time ids: 0 seed (join), 1 verify, 2 generic seed, 3-5 tail, 6 pack_results_kernel (round 5; the count kernel of rounds 1-2 before), 7 SAM text, 8 seed selection, 9 pairing
 struct TimedLaunch {
   int kernel;
   hipEvent_t start, stop;
@@ -151,6 +151,15 @@ struct Slot {
   uint32_t n_cand = 0;
   std::vector<TimedLaunch> pending;
   femt::Tail *tail = nullptr;  // device mapping tail (fem_dev_fetch_records), created on first use
+  // pair mode (fem_dev_set_pairs): the batches are read pairs, read i and read n_reads / 2 + i
+  bool paired = false;
+  int32_t min_insert = 0, max_insert = 0;
+  uint64_t n_proper = 0;  // of the slot's last paired SAM text
+  // fem_dev_fetch_pairs: the records in output order (host copies, valid until the slot's next fetch_pairs)
+  std::vector<uint16_t> pr_flag;
+  std::vector<uint32_t> pr_tid, pr_pos0, pr_cigar_off, pr_cigar, pr_md_off;
+  std::vector<uint8_t> pr_nm;
+  std::vector<char> pr_md;
 };
 
 // ctr[4] | arena_ctr[2] | stats[4] | pack cursor[2]
@@ -2277,9 +2286,11 @@ static int fetch_sam(fem_dev *h, int slot, fem_batch_sam *out, bool wait) {
   femt::TailOutput t{};
   double ms[3] = {0, 0, 0}, ms_text = 0;
   std::string err;
+  if (s.paired && (s.n_reads & 1)) return fail(h, FEM_ERR_INVALID, "a batch of read pairs holds an even number of reads");
   hipStream_t os = out_stream_of(h, s);
   rc = s.tail->run(in, os, h->n_cu, h->tiny_buffers, &t, &err, h->timing ? ms : nullptr, false);
   if (rc) return fail(h, rc, err);
+  if (s.paired && (rc = s.tail->pair(s.min_insert, s.max_insert, os, &err))) return fail(h, rc, err);
   const double ms_run = since(t_in);
   femt::SamInput names{};
   names.quals = s.host_quals ? nullptr : s.d_quals, names.names = s.d_names, names.name_off = s.d_name_off;
@@ -2287,8 +2298,9 @@ static int fetch_sam(fem_dev *h, int slot, fem_batch_sam *out, bool wait) {
   names.ref_names = h->d_ref_names, names.ref_name_off = h->d_ref_name_off;
   femt::SamOutput text{};
   HIP_TRY(h, hipStreamWaitEvent(os, s.ev_text_staged, 0));  // qualities and names came on the slot's text stream
-  rc = s.tail->sam(in, names, os, h->n_cu, &text, &err, h->timing ? &ms_text : nullptr, wait, &h->text_gate);
+  rc = s.tail->sam(in, names, os, h->n_cu, &text, &err, h->timing ? &ms_text : nullptr, wait, &h->text_gate, s.paired);
   if (rc) return fail(h, rc, err);
+  s.n_proper = s.paired ? s.tail->n_proper() : 0;  // (sam() has waited for the stream once, after sizing the text)
   if (!s.ev_text_order) HIP_TRY(h, hipEventCreateWithFlags(&s.ev_text_order, hipEventDisableTiming));
   HIP_TRY(h, hipEventRecord(s.ev_text_order, os));
   s.have_text_order = true;
@@ -2297,10 +2309,76 @@ static int fetch_sam(fem_dev *h, int slot, fem_batch_sam *out, bool wait) {
     FEM_LOCK(h);
     for (int i = 0; i < 3; ++i) h->t_ms[3 + i] += ms[i], h->t_n[3 + i] += 1;
     if (wait) h->t_ms[7] += ms_text, h->t_n[7] += 1;  // (without the wait no elapsed time is read: nothing to count)
+    if (s.paired) h->t_ms[9] += s.tail->pair_ms(), h->t_n[9] += 1;
   }
   s.qual_at = text.qual_at;
   out->text = text.text, out->len = text.len, out->n_asserted = text.n_asserted;
   out->n_reads = t.n_reads, out->n_records = t.n_records;
+  memcpy(out->stats, s.stats, sizeof s.stats);
+  return FEM_OK;
+}
+
+int fem_dev_set_pairs(fem_dev *h, int slot, const fem_pair_params *pp) {
+  int rc = check_slot(h, slot);
+  if (rc) return rc;
+  FEM_LOCK(h);
+  Slot &s = h->slot[slot];
+  if (!pp) {
+    s.paired = false;
+    return FEM_OK;
+  }
+  if (pp->min_insert < 0 || pp->max_insert < pp->min_insert || pp->max_insert > (1 << 30))
+    return fail(h, FEM_ERR_INVALID, "insert size range out of bounds (0 <= min_insert <= max_insert <= 2^30)");
+  s.paired = true, s.min_insert = pp->min_insert, s.max_insert = pp->max_insert;
+  return FEM_OK;
+}
+
+int fem_dev_pair_count(fem_dev *h, int slot, uint64_t *n_proper) {
+  int rc = check_slot(h, slot);
+  if (rc) return rc;
+  if (!n_proper) return fail(h, FEM_ERR_INVALID, "null output pointer");
+  FEM_LOCK(h);
+  Slot &s = h->slot[slot];
+  if (!s.paired) return fail(h, FEM_ERR_STATE, "the slot is not in pair mode (fem_dev_set_pairs)");
+  *n_proper = s.n_proper;
+  return FEM_OK;
+}
+
+// The records of fem_dev_fetch_records, paired on the device (pair_kernel) and put in output order here on the host: an
+// inspection path (tests, tools); FEM map takes the text (fem_dev_fetch_sam).
+int fem_dev_fetch_pairs(fem_dev *h, int slot, fem_batch_pairs *out) {
+  int rc = check_slot(h, slot);
+  if (rc) return rc;
+  if (!out) return fail(h, FEM_ERR_INVALID, "null result");
+  if (!h->slot[slot].paired) return fail(h, FEM_ERR_STATE, "the slot is not in pair mode (fem_dev_set_pairs)");
+  if ((rc = fem_dev_sync(h, slot))) return rc;
+  Slot &s = h->slot[slot];
+  if (s.n_reads & 1) return fail(h, FEM_ERR_INVALID, "a batch of read pairs holds an even number of reads");
+  fem_batch_records rec{};
+  if ((rc = fem_dev_fetch_records(h, slot, &rec))) return rc;
+  std::string err;
+  femt::PairOutput po{};
+  if ((rc = s.tail->pair(s.min_insert, s.max_insert, s.stream, &err))) return fail(h, rc, err);
+  if ((rc = s.tail->pair_fetch(s.stream, &po, &err))) return fail(h, rc, err);
+  const uint64_t nr = po.n_records;
+  s.pr_flag.assign(po.flag, po.flag + nr);
+  s.pr_tid.resize(nr), s.pr_pos0.resize(nr), s.pr_nm.resize(nr), s.pr_cigar_off.resize(nr + 1), s.pr_md_off.resize(nr + 1);
+  s.pr_cigar.clear(), s.pr_md.clear();
+  s.pr_cigar_off[0] = 0, s.pr_md_off[0] = 0;
+  for (uint64_t k = 0; k < nr; ++k) {
+    const uint32_t r = po.perm[k];
+    s.pr_tid[k] = rec.tid[r], s.pr_pos0[k] = rec.pos0[r], s.pr_nm[k] = rec.nm[r];
+    s.pr_cigar.insert(s.pr_cigar.end(), rec.cigar + rec.cigar_off[r], rec.cigar + rec.cigar_off[r + 1]);
+    s.pr_md.insert(s.pr_md.end(), rec.md + rec.md_off[r], rec.md + rec.md_off[r + 1]);
+    s.pr_cigar_off[k + 1] = (uint32_t)s.pr_cigar.size(), s.pr_md_off[k + 1] = (uint32_t)s.pr_md.size();
+  }
+  s.n_proper = po.n_proper;
+  out->n_pairs = po.n_pairs, out->n_records = nr;
+  out->rec_begin = po.pair_begin, out->flag = s.pr_flag.data(), out->tid = s.pr_tid.data(), out->pos0 = s.pr_pos0.data();
+  out->nm = s.pr_nm.data(), out->cigar_off = s.pr_cigar_off.data(), out->cigar = s.pr_cigar.data();
+  out->md_off = s.pr_md_off.data(), out->md = s.pr_md.data();
+  out->mate_tid = po.mate_tid, out->mate_pos0 = po.mate_pos0, out->tlen = po.tlen;
+  out->n_proper = po.n_proper;
   memcpy(out->stats, s.stats, sizeof s.stats);
   return FEM_OK;
 }

@@ -1021,6 +1021,122 @@ int fem_seqfile_plan(fem_seqfile *f, uint64_t approx_bytes, int n_threads, fem_b
   return pl->rc;  // -2 / -3: "Didn't reach the end of sequence file"; the records read so far are still in the plan
 }
 
+// A plan of exactly the next n_records records (fewer at the end of the input): the second file of read pairs, cut where the
+// first one was.  The records are found by one walk over the window (plain files through their mapping, gzip / BGZF windows
+// grown until they hold them), then counted by the threads as fem_seqfile_plan counts its ranges; anything the fast parser
+// declines goes to the sequential reader, which stops after n_records.
+int fem_seqfile_plan_count(fem_seqfile *f, uint64_t n_records, int n_threads, fem_batch_plan **plan_out, fem_batch_shape *shape) {
+  if (!f || !plan_out || !shape) return -1;
+  if (n_threads < 1) n_threads = 1;
+  *plan_out = nullptr;
+  memset(shape, 0, sizeof *shape);
+  fem_batch_plan *pl = new (std::nothrow) fem_batch_plan();
+  if (!pl) return -4;
+  if (n_records == 0) {  // (an empty held batch)
+    shape->has_qual = 1;
+    *plan_out = pl;
+    return 0;
+  }
+  const size_t pos0 = f->in->tell();
+  f->threads = n_threads;
+  uint64_t approx = std::max<uint64_t>(n_records * 256u, 1u << 16);
+  FastView fv;
+  while (fast_view(f, approx, &fv)) {
+    const char *m = fv.m;
+    const size_t len = fv.len;
+    size_t lo = fv.lo;
+    while (lo < len && m[lo] != '@' && m[lo] != '>') ++lo;
+    if (lo >= len && fv.whole) {
+      fast_view_consumed(f, len);
+      pl->fast = true, pl->m = m, pl->end = len, pl->cut.assign(2, len), pl->count.assign(1, RangeCount());
+      shape->has_qual = 1;
+      *plan_out = pl;
+      return 0;
+    }
+    const size_t lim = fv.whole ? len : last_fastq_record(m, lo, len);  // (the record that straddles the window's end waits)
+    bool bad = false;
+    size_t hi = lo;
+    if (lo < len && m[lo] == '@' && next_fastq_record(m, len, lo) == lo) {
+      uint64_t n = 0;
+      FqRec r;
+      while (n < n_records && next_fq(m, hi, lim, r, bad))
+        if (r.len) ++n;
+      if (!bad && n < n_records && !fv.whole) {  // the window is too small: grow it
+        approx *= 2;
+        continue;
+      }
+    } else if (lo < len && m[lo] == '>') {
+      bad = true;
+    } else if (!fv.whole) {
+      approx *= 2;
+      continue;
+    } else {
+      bad = true;
+    }
+    if (!bad && hi > lo) {
+      const size_t span = hi - lo;
+      const int nt = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_threads, span / (1u << 18) + 1));
+      pl->cut.assign((size_t)nt + 1, hi);
+      pl->cut[0] = lo;
+      for (int t = 1; t < nt; ++t) pl->cut[(size_t)t] = std::min(hi, next_fastq_record(m, len, lo + span * (size_t)t / (size_t)nt));
+      for (int t = 1; t <= nt; ++t) pl->cut[(size_t)t] = std::max(pl->cut[(size_t)t], pl->cut[(size_t)t - 1]);
+      pl->count.assign((size_t)nt, RangeCount());
+      planner_pool().run(nt, [&](int t) {
+        RangeCount c;
+        size_t p = pl->cut[(size_t)t];
+        const size_t h = pl->cut[(size_t)t + 1];
+        FqRec r;
+        bool b = false;
+        while (next_fq(m, p, h, r, b)) {
+          if (r.len == 0) continue;
+          ++c.n, c.bases += r.len, c.names += r.name_len;
+          c.max_len = std::max<uint32_t>(c.max_len, (uint32_t)std::min<size_t>(r.len, 0xFFFFFFFFu));
+          c.min_len = std::min<uint32_t>(c.min_len, (uint32_t)std::min<size_t>(r.len, 0xFFFFFFFFu));
+        }
+        c.ok = !b;
+        pl->count[(size_t)t] = c;
+      });
+      bool ok = true;
+      for (const RangeCount &c : pl->count) ok = ok && c.ok;
+      if (ok) {
+        uint32_t min_len = 0xFFFFFFFFu;
+        for (const RangeCount &c : pl->count) {
+          shape->n_reads += c.n, shape->n_bases += c.bases, shape->n_name_bytes += c.names;
+          shape->max_len = std::max(shape->max_len, c.max_len);
+          min_len = std::min(min_len, c.min_len);
+        }
+        shape->min_len = shape->n_reads ? min_len : 0;
+        shape->has_qual = 1;
+        pl->fast = true, pl->m = m, pl->end = hi;
+        fast_view_consumed(f, hi);
+        *plan_out = pl;
+        return 0;
+      }
+    }
+    f->fast_ok = false;  // FASTA, multi-line FASTQ or malformed input: the exact sequential reader takes over
+    fast_view_abandon(f, pos0);
+    pl->cut.clear(), pl->count.clear();
+    break;
+  }
+  pl->rc = fem_seqfile_read(f, n_records, &pl->held);
+  if (pl->rc != 0 && pl->rc != -2 && pl->rc != -3) {
+    int rc = pl->rc;
+    fem_batch_plan_free(pl);
+    return rc;
+  }
+  shape->n_reads = pl->held.n;
+  shape->n_bases = pl->held.n ? pl->held.off[pl->held.n] : 0;
+  shape->n_name_bytes = pl->held.n ? pl->held.name_off[pl->held.n] : 0;
+  shape->min_len = pl->held.n ? 0xFFFFFFFFu : 0u;
+  for (uint64_t i = 0; i < pl->held.n; ++i) {
+    const uint32_t l = (uint32_t)std::min<uint64_t>(pl->held.off[i + 1] - pl->held.off[i], 0xFFFFFFFFu);
+    shape->max_len = std::max(shape->max_len, l), shape->min_len = std::min(shape->min_len, l);
+  }
+  shape->has_qual = pl->held.quals != nullptr || pl->held.n == 0;
+  *plan_out = pl;
+  return pl->rc;
+}
+
 int fem_seqfile_fill(fem_seqfile *f, fem_batch_plan *pl, int n_threads, char *bases, uint64_t *off, char *quals, char *names,
                      uint64_t *name_off) {
   if (!f || !pl || !bases || !off || !names || !name_off) return -1;

@@ -59,6 +59,9 @@ typedef struct {
   uint32_t min_len; /* == max_len: reads of one length (fem_dev_commit_stage_uniform) */
 } fem_batch_shape;
 int fem_seqfile_plan(fem_seqfile *f, uint64_t approx_bytes, int n_threads, fem_batch_plan **plan, fem_batch_shape *shape);
+/* plan_count: the same for exactly the next n_records records (fewer at the end of the input, 0 after it; zero-length records
+ * are skipped and not counted, as everywhere): the second file of read pairs, cut where the first one was. */
+int fem_seqfile_plan_count(fem_seqfile *f, uint64_t n_records, int n_threads, fem_batch_plan **plan, fem_batch_shape *shape);
 int fem_seqfile_fill(fem_seqfile *f, fem_batch_plan *plan, int n_threads, char *bases, uint64_t *off, char *quals,
                      char *names, uint64_t *name_off);
 /* fill with the bases written at TWO BITS PER BASE, the form fem_dev_commit_stage_packed (include/fem_hip.h) takes: `codes`

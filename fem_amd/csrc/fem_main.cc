@@ -4,7 +4,8 @@
 //
 // New, optional: `--gpus N` (map) spreads read batches over N GPUs of this node (whichever GPU has a free slot takes the
 // next batch; record order in the SAM file follows completion, parity is modulo record order); `--batch N` sets reads
-// per batch.
+// per batch.  `--read2 STR` maps read pairs (record i of --read1 and of --read2 are the two mates of pair i), with -I / -X the
+// accepted insert size: the pairing and the paired SAM text on the device (fem_dev_set_pairs).
 #include <errno.h>
 #include <fcntl.h>
 #include <getopt.h>
@@ -68,6 +69,9 @@ void usage_map() {
   fprintf(stderr, "        --ref    STR  Input reference file\n");
   fprintf(stderr, "        --index  STR  Input index file\n");
   fprintf(stderr, "        --read1  STR  Input read1 file\n");
+  fprintf(stderr, "        --read2  STR  Input read2 file: map read pairs (record i of both files is pair i)\n");
+  fprintf(stderr, "        -I, --minins INT  minimum insert size of a proper pair [0]\n");
+  fprintf(stderr, "        -X, --maxins INT  maximum insert size of a proper pair [500]\n");
   fprintf(stderr, "        -o       STR  Output SAM file \n\n");
 }
 
@@ -240,6 +244,7 @@ struct BatchBuf {  // everything about the batch that sits in one (GPU, slot) pa
   fem_batch_shape shape{};
   uint64_t want_reads = 0, want_bases = 0;  // set by the reader when the staging buffers are too small
   fem_batch_records rec{};                  // device tail's records (default path)
+  uint64_t n_proper = 0;                    // paired: proper pairs of the batch
   fem_batch_result res{};                   // per-candidate outcome (FEM_HOST_TAIL=1)
   double t_submit = 0;
   double t_slot = 0, t_filled = 0, t_submitted = 0, t_retired = 0, t_text = 0;  // FEM_STAGE_TIMES=2: the batch's way through the stages
@@ -263,7 +268,8 @@ int map_main(int argc, char **argv) {
   // that a recycled buffer's pages are already there (page faults were a visible share of the host time).
   mallopt(M_MMAP_MAX, 0);
   mallopt(M_TRIM_THRESHOLD, -1);
-  char *ref_path = nullptr, *index_path = nullptr, *read_path = nullptr, *out_path = nullptr;
+  char *ref_path = nullptr, *index_path = nullptr, *read_path = nullptr, *read2_path = nullptr, *out_path = nullptr;
+  long long min_insert = 0, max_insert = 500;
   fem_params params{12, 3, 2, 1};  // src/FEM_map.c:67-70: k and step are fixed, whatever the index header says
   int n_threads = 1, n_gpus = 1;
   // reads per batch: 250 k fills the pipeline soonest on small inputs; a batch costs three host round trips on its way through
@@ -271,17 +277,21 @@ int map_main(int argc, char **argv) {
   // 71 -> 81; round 4) — chosen by the size of the read file unless --batch says otherwise
   uint64_t batch_reads = 250000;
   bool batch_given = false;
-  const char *short_opt = "ha:f:e:t:o:r:i:b:";
+  const char *short_opt = "ha:f:e:t:o:r:i:b:I:X:";
   static struct option long_opt[] = {{"help", no_argument, nullptr, 'h'},       {"ref", required_argument, nullptr, 'r'},
                                      {"index", required_argument, nullptr, 'i'}, {"read1", required_argument, nullptr, 'b'},
                                      {"gpus", required_argument, nullptr, 'G'},  {"batch", required_argument, nullptr, 'B'},
-                                     {nullptr, 0, nullptr, 0}};
+                                     {"read2", required_argument, nullptr, 'c'}, {"minins", required_argument, nullptr, 'I'},
+                                     {"maxins", required_argument, nullptr, 'X'}, {nullptr, 0, nullptr, 0}};
   int c, oi = 0;
   while ((c = getopt_long(argc, argv, short_opt, long_opt, &oi)) >= 0) {
     switch (c) {
       case 'r': ref_path = optarg; break;
       case 'i': index_path = optarg; break;
       case 'b': read_path = optarg; break;
+      case 'c': read2_path = optarg; break;
+      case 'I': min_insert = strtoll(optarg, nullptr, 10); break;
+      case 'X': max_insert = strtoll(optarg, nullptr, 10); break;
       case 'e': params.e = atoi(optarg); break;
       case 't': n_threads = atoi(optarg); break;
       case 'a': params.a = atoi(optarg); break;
@@ -305,6 +315,7 @@ int map_main(int argc, char **argv) {
   if (params.e < 0 || params.e > 7) bad = "Wrong error threshold.";
   else if (n_threads <= 0) bad = "Wrong number of threads.";
   else if (params.a < 0 || params.a > 2) bad = "Wrong number of additional q-grams.";
+  else if (min_insert < 0 || max_insert < min_insert || max_insert > (1ll << 30)) bad = "Wrong insert size range.";
   else if (!ref_path) bad = "Reference file path is required.";
   else if (!index_path) bad = "Index file path is required.";
   else if (!read_path) bad = "Read file path is required.";
@@ -350,6 +361,13 @@ int map_main(int argc, char **argv) {
   // option, not the default.  FEM_HOST_TAIL=1: ordering, traceback and text by the host threads from the per-candidate outcome.
   const char *hf = getenv("FEM_HOST_FORMAT"), *spl = getenv("FEM_SPLICE");
   const bool device_text = !host_tail && !(hf && hf[0] == '1');
+  // Read pairs: paired and rendered on the device only (fem_dev_set_pairs), the reads staged as characters.
+  const bool paired = read2_path != nullptr;
+  if (paired && !device_text) {
+    fprintf(stderr, "%s is not supported with --read2: the paired SAM text is made on the device only.\n",
+            host_tail ? "FEM_HOST_TAIL=1" : "FEM_HOST_FORMAT=1");
+    exit(EXIT_FAILURE);
+  }
   // ... with the qualities kept on the host (fem_dev_commit_names_stage: the device leaves their field open and the batch's
   // retiring thread fills it in): they are 228 of the 473 bytes per read on the link otherwise — and 0.027 core-µs per read on
   // the host then, next to the parser's 0.078.  With 16 cores per GPU the two forms are within +7 / -16 % of each other from box
@@ -362,7 +380,7 @@ int map_main(int argc, char **argv) {
   // base — the parser writes that form straight into the pinned staging (fem_seqfile_fill_packed ->
   // fem_dev_commit_stage_packed: no host work per base beyond the parse itself) (FEM_PACK_BASES=0: always as characters).
   const char *pk = getenv("FEM_PACK_BASES");
-  const bool pack_bases = !host_tail && !(pk && pk[0] == '0');
+  const bool pack_bases = !host_tail && !paired && !(pk && pk[0] == '0');
   if (!batch_given) {
     struct stat st;
     if (stat(read_path, &st) == 0 && st.st_size >= (off_t)(1ll << 30)) batch_reads = 1000000;  // (plain FASTQ of >= ~4 M reads)
@@ -412,6 +430,10 @@ int map_main(int argc, char **argv) {
           if (!rc && device_text) rc = fem_dev_acquire_text_stage(devs[(size_t)g], sl, reads_cap0, bases_cap0, names_cap0, &pq, &pn, &pno);
           if (!rc && device_text) rc = fem_dev_reserve_text(devs[(size_t)g], sl, reads_cap0, bases_cap0, names_cap0, batch_bytes + batch_bytes / 4);
           if (!rc && device_text && res_reads) rc = fem_dev_reserve_batch(devs[(size_t)g], sl, res_reads, res_reads + res_reads / 8, res_len, &params);
+          if (!rc && paired) {
+            const fem_pair_params pp{(int32_t)min_insert, (int32_t)max_insert};
+            rc = fem_dev_set_pairs(devs[(size_t)g], sl, &pp);
+          }
         }
         up_rc[(size_t)g] = rc;
       });
@@ -498,7 +520,7 @@ int map_main(int argc, char **argv) {
   Channel<WriteItem> write_q;
   std::vector<TextOut> texts(3);
   for (TextOut &t : texts) text_free_q.push(&t);
-  std::vector<uint64_t> per_gpu((size_t)n_gpus * 5, 0);
+  std::vector<uint64_t> per_gpu((size_t)n_gpus * 5, 0), per_gpu_proper((size_t)n_gpus, 0);
 
   // ---- writer (src/output_queue.c:60-91) ----
   std::thread writer([&] {
@@ -642,6 +664,7 @@ int map_main(int argc, char **argv) {
         int rc = host_tail     ? fem_dev_map_batch_wait(h, b->slot, &b->res)
                  : device_text ? fem_dev_fetch_sam_nowait(h, b->slot, &b->sam)  // (the writer waits for the text itself)
                                : fem_dev_fetch_records(h, b->slot, &b->rec);
+        if (!rc && paired) rc = fem_dev_pair_count(h, b->slot, &b->n_proper);
         const double waited = real_time() - t0;
         b->t_retired = t0 + waited;
         double placing = 0;
@@ -677,6 +700,7 @@ int map_main(int argc, char **argv) {
           }
           const uint64_t *st = host_tail ? b->res.stats : device_text ? b->sam.stats : b->rec.stats;
           for (int i = 0; i < 5; ++i) per_gpu[(size_t)g * 5 + (size_t)i] += st[i];
+          if (paired) per_gpu_proper[(size_t)g] += b->n_proper;
           if (device_text) {
             n_asserted += b->sam.n_asserted;
             write_q.push(WriteItem{nullptr, b});
@@ -745,12 +769,14 @@ int map_main(int argc, char **argv) {
     });
 
   // ---- reader (src/input_queue.c:53-79): this thread ----
-  fem_seqfile *read_file = nullptr;
+  fem_seqfile *read_file = nullptr, *read2_file = nullptr;
   {
     fem_seqfile *f = read_file = fem_seqfile_open(read_path);
-    if (!f) {
+    fem_seqfile *f2 = read2_file = paired ? fem_seqfile_open(read2_path) : nullptr;
+    if (!f || (paired && !f2)) {
       fprintf(stderr, "Cannot find sequence file!");  // the reference exits here (src/sequence_batch.c:33-35)
       exit_code = EXIT_FAILURE;
+      f = nullptr;
     }
     // The planner: cuts the next batch out of the input (one pass over it: where the records end, how many, how long) on a
     // thread of its own, ahead of the batch being filled where the file allows it (plain FASTQ through a mapping: a plan's records
@@ -761,11 +787,15 @@ int map_main(int argc, char **argv) {
       fem_batch_plan *plan = nullptr;
       fem_batch_shape shape{};
       int rc = 0;
+      fem_batch_plan *plan2 = nullptr;  // paired: as many records of --read2 (one, to see that it ends, behind the end of --read1)
+      fem_batch_shape shape2{};
+      int rc2 = 0;
     };
     Channel<Planned> planned_q;
     Channel<int> plan_tokens;  // a plan is made per token: one while nothing may run ahead, two where it may
     std::atomic<bool> plan_stop{false};
-    const bool ahead = f && fem_seqfile_plan_ahead_ok(f) && !(getenv("FEM_PLAN_AHEAD") && getenv("FEM_PLAN_AHEAD")[0] == '0');
+    const bool ahead = f && fem_seqfile_plan_ahead_ok(f) && (!paired || fem_seqfile_plan_ahead_ok(f2)) &&
+                       !(getenv("FEM_PLAN_AHEAD") && getenv("FEM_PLAN_AHEAD")[0] == '0');
     plan_tokens.push(1);
     if (ahead) plan_tokens.push(1);
     std::thread planner([&] {
@@ -774,13 +804,51 @@ int map_main(int argc, char **argv) {
         if (plan_stop) break;
         Planned pl;
         const double t_p = real_time();
-        pl.rc = fem_seqfile_plan(f, batch_bytes, rd_threads, &pl.plan, &pl.shape);
+        pl.rc = fem_seqfile_plan(f, paired ? batch_bytes / 2 : batch_bytes, rd_threads, &pl.plan, &pl.shape);
+        if (paired && pl.plan && pl.rc == 0)  // the mates: cut by count where the first file was cut by bytes
+          pl.rc2 = fem_seqfile_plan_count(f2, std::max<uint64_t>(pl.shape.n_reads, 1), rd_threads, &pl.plan2, &pl.shape2);
         busy_plan += real_time() - t_p;
         const bool last = !pl.plan || pl.rc != 0 || pl.shape.n_reads == 0;
         planned_q.push(pl);
         if (last) break;
       }
     });
+    // A batch of read pairs in the slot's staging: mate 1's records, then mate 2's behind them (offsets and name offsets running
+    // on), a trailing /1 or /2 taken off every name, the two names of each pair compared.  0 = filled, 2 = the names differ
+    // (reported here), anything else = the reader failed.  Frees both plans.
+    auto fill_pair = [&](fem_seqfile *fa, fem_batch_plan *pa, fem_seqfile *fb, fem_batch_plan *pb, const fem_batch_shape &sa,
+                         BatchBuf *b) -> int {
+      int frc = fem_seqfile_fill(fa, pa, rd_threads, b->bases, b->off, b->q_stage, b->n_stage, b->no_stage);
+      const uint64_t n1 = sa.n_reads, nb1 = sa.n_bases, nn1 = sa.n_name_bytes;
+      if (frc) {
+        fem_batch_plan_free(pb);
+        return frc;
+      }
+      frc = fem_seqfile_fill(fb, pb, rd_threads, b->bases + nb1, b->off + n1, b->q_stage + nb1, b->n_stage + nn1, b->no_stage + n1);
+      if (frc) return frc;
+      const uint64_t n = b->shape.n_reads;
+      uint64_t *off = b->off, *no = b->no_stage;
+      char *nm = b->n_stage;
+      for (uint64_t r = n1; r <= n; ++r) off[r] += nb1, no[r] += nn1;
+      uint64_t w = 0, from = no[0];
+      for (uint64_t r = 0; r < n; ++r) {
+        const uint64_t to = no[r + 1];
+        uint64_t len = to - from;
+        if (len >= 2 && nm[from + len - 2] == '/' && (nm[from + len - 1] == '1' || nm[from + len - 1] == '2')) len -= 2;
+        if (w != from) memmove(nm + w, nm + from, len);
+        no[r] = w, w += len, from = to;
+      }
+      no[n] = w;
+      b->shape.n_name_bytes = w;
+      for (uint64_t i = 0; i < n1; ++i) {
+        const uint64_t l1 = no[i + 1] - no[i], l2 = no[n1 + i + 1] - no[n1 + i];
+        if (l1 != l2 || memcmp(nm + no[i], nm + no[n1 + i], l1) != 0) {
+          fprintf(stderr, "Read names differ in the two read files: %.*s %.*s\n", (int)l1, nm + no[i], (int)l2, nm + no[n1 + i]);
+          return 2;
+        }
+      }
+      return 0;
+    };
     bool planner_done = false;  // the planner has handed over its last plan (end of input or failure)
     while (f && !exit_code) {
       const double t_pop = real_time();
@@ -797,6 +865,20 @@ int map_main(int argc, char **argv) {
       int rc = pd.rc;
       if (!plan || rc != 0 || pd.shape.n_reads == 0) planner_done = true;
       bool ok = plan != nullptr;
+      if (paired && ok && rc == 0) {
+        if (!pd.plan2 || pd.rc2 != 0) {
+          rc = pd.rc2 ? pd.rc2 : -1;
+        } else if (pd.shape2.n_reads != pd.shape.n_reads) {
+          fprintf(stderr, "The two read files hold different numbers of reads.\n");
+          exit_code = EXIT_FAILURE;
+          ok = false;
+        } else if (pd.shape.n_reads > 0) {  // one batch of both mates: mate 1's reads, then mate 2's
+          const fem_batch_shape &s2 = pd.shape2;
+          b->shape.n_reads += s2.n_reads, b->shape.n_bases += s2.n_bases, b->shape.n_name_bytes += s2.n_name_bytes;
+          b->shape.max_len = std::max(b->shape.max_len, s2.max_len), b->shape.min_len = std::min(b->shape.min_len, s2.min_len);
+          b->shape.has_qual = b->shape.has_qual && s2.has_qual;
+        }
+      }
       if (rc != 0) {  // the reference exits on a truncated file (src/sequence_batch.c:63-66): nothing of this batch is mapped
         fprintf(stderr, "Didn't reach the end of sequence file, which might be corrupted!");
         exit_code = EXIT_FAILURE;
@@ -826,6 +908,7 @@ int map_main(int argc, char **argv) {
       }
       if (!ok || b->shape.n_reads == 0) {
         fem_batch_plan_free(plan);
+        fem_batch_plan_free(pd.plan2);
         busy_read += real_time() - t0;
         break;  // end of input (or failure)
       }
@@ -853,9 +936,17 @@ int map_main(int argc, char **argv) {
           b->packed = rc == 0;
         }
       }
-      if (rc == 1)
+      if (rc == 1 && paired) {
+        rc = fill_pair(f, plan, f2, pd.plan2, pd.shape, b);
+        pd.plan2 = nullptr;
+        if (rc == 2) {
+          exit_code = EXIT_FAILURE;
+          break;
+        }
+      } else if (rc == 1) {
         rc = device_text ? fem_seqfile_fill(f, plan, rd_threads, b->bases, b->off, b->q_stage, b->n_stage, b->no_stage)
                          : fem_seqfile_fill(f, plan, rd_threads, b->bases, b->off, b->quals.p, b->names.p, (uint64_t *)b->name_off.p);
+      }
       busy_read += real_time() - t0;
       plan_tokens.push(1);  // (this batch's plan is consumed: the planner may cut the next but one)
       if (rc) {
@@ -873,7 +964,7 @@ int map_main(int argc, char **argv) {
     planner.join();
     {
       Planned pd;
-      while (!planner_done && planned_q.try_pop_for(pd, 0.0)) fem_batch_plan_free(pd.plan);
+      while (!planner_done && planned_q.try_pop_for(pd, 0.0)) fem_batch_plan_free(pd.plan), fem_batch_plan_free(pd.plan2);
     }
     // (the file stays open until the mapping phase is over: unmapping 4 GB of faulted-in pages takes 0.08 s, which the GPUs
     // would otherwise spend waiting for their stop message)
@@ -922,6 +1013,7 @@ int map_main(int argc, char **argv) {
   const double t_mapping = real_time() - t_start;  // (the reference's timer stops after the counter reduction, src/FEM_map.c:219)
   for (TextOut &t : texts) free(t.buf);
   if (read_file) fem_seqfile_close(read_file);
+  if (read2_file) fem_seqfile_close(read2_file);
   for (fem_dev *h : devs) fem_dev_close(h);
   if (exit_code) return exit_code;
   fprintf(stderr, "The number of read: %lu\n", (unsigned long)totals[0]);
@@ -929,6 +1021,11 @@ int map_main(int argc, char **argv) {
   fprintf(stderr, "The number of candidate before additional q-gram filter: %lu\n", (unsigned long)totals[2]);
   fprintf(stderr, "The number of candidate: %lu\n", (unsigned long)totals[3]);
   fprintf(stderr, "The number of mapping: %lu\n", (unsigned long)totals[4]);
+  if (paired) {  // (not part of the all-reduce of the five: summed here, per GPU)
+    uint64_t n_proper = 0;
+    for (uint64_t x : per_gpu_proper) n_proper += x;
+    fprintf(stderr, "The number of proper pairs: %lu\n", (unsigned long)n_proper);
+  }
   fprintf(stderr, "Time: %fs\n", t_mapping);
   return 0;
 }

@@ -1151,6 +1151,11 @@ struct SamParams {
   uint32_t *asserted;
   unsigned long long *qual_at;  // qual_hole: n_reads entries, set for the reads that have a record
   uint32_t qual_hole;           // the QUAL field of a primary record is sized but not written (quals == nullptr)
+  // pair mode (the kernels' kPair instances): line k renders record perm[k] with FLAG pflag[k] and these mate columns
+  const uint32_t *perm;
+  const uint16_t *pflag;
+  const uint32_t *mtid, *mpos0;  // 0xFFFFFFFF: the other mate has no record
+  const int32_t *tlen;
 };
 
 __device__ __forceinline__ uint32_t dec_digits(uint32_t v) {
@@ -1166,6 +1171,17 @@ __device__ __forceinline__ uint8_t *put_dec(uint8_t *w, uint32_t v) {
   return w + n;
 }
 
+// RNEXT, PNEXT and TLEN of line j in pair mode, without the tabs around them (single-end: "*\t0\t0", 5 characters)
+__device__ __forceinline__ uint32_t mate_cols_len(const SamParams &p, uint32_t j, uint32_t tid) {
+  const uint32_t mt = p.mtid[j];
+  if (mt == 0xFFFFFFFFu) return 5u;
+  const uint32_t rnext = mt == tid ? 1u : p.ref_name_off[mt + 1] - p.ref_name_off[mt];
+  const int32_t tl = p.tlen[j];
+  const uint32_t tl_len = tl < 0 ? 1u + dec_digits((uint32_t)-tl) : dec_digits((uint32_t)tl);
+  return rnext + 1u + dec_digits(p.mpos0[j] + 1u) + 1u + tl_len;
+}
+
+template <bool kPair>
 __global__ void __launch_bounds__(256) sam_len_kernel(SamParams p) {
   const uint32_t stride = gridDim.x * blockDim.x;
   for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j <= p.n_records; j += stride) {
@@ -1173,21 +1189,23 @@ __global__ void __launch_bounds__(256) sam_len_kernel(SamParams p) {
       p.line_len[j] = 0;
       continue;
     }
-    const uint32_t r = p.s_read[j];
-    const bool primary = p.rec_begin[r] == j;
+    const uint32_t rec = kPair ? p.perm[j] : j;  // (pair mode: j is the line, rec the record it renders)
+    const uint32_t r = p.s_read[rec];
+    const uint16_t flag = kPair ? p.pflag[j] : p.flag[j];
+    const bool primary = kPair ? !(flag & 256u) : p.rec_begin[r] == j;
     const uint32_t L = (uint32_t)(p.read_off[r + 1] - p.read_off[r]);
     const uint32_t name_len = (uint32_t)(p.name_off[r + 1] - p.name_off[r]);
-    const uint32_t t = p.tid[j], rname_len = p.ref_name_off[t + 1] - p.ref_name_off[t];
-    const uint16_t flag = p.flag[j];
+    const uint32_t t = p.tid[rec], rname_len = p.ref_name_off[t + 1] - p.ref_name_off[t];
     if (flag & 0x8000u) atomicAdd(p.asserted, 1u);
     uint32_t cig = 0;
-    const uint32_t c0 = p.cigar_off[j], c1 = p.cigar_off[j + 1];
+    const uint32_t c0 = p.cigar_off[rec], c1 = p.cigar_off[rec + 1];
     for (uint32_t c = c0; c < c1; ++c) cig += dec_digits(p.cigar[c] >> 4) + 1u;
     if (c1 == c0) cig = 1;  // '*'
-    const uint32_t md_len = p.md_off[j + 1] - p.md_off[j];
+    const uint32_t md_len = p.md_off[rec + 1] - p.md_off[rec];
     const uint32_t seq_qual = primary && L > 0 ? L + 1u + (p.quals || p.qual_hole ? L : 1u) : 3u;
-    p.line_len[j] = (unsigned long long)name_len + 1u + dec_digits(flag & 0x7FFFu) + 1u + rname_len + 1u + dec_digits(p.pos0[j] + 1u) + 5u + cig +
-                    7u + seq_qual + 6u + dec_digits(p.nm[j]) + 6u + md_len + 1u;
+    const uint32_t mate = kPair ? mate_cols_len(p, j, t) : 5u;
+    p.line_len[j] = (unsigned long long)name_len + 1u + dec_digits(flag & 0x7FFFu) + 1u + rname_len + 1u + dec_digits(p.pos0[rec] + 1u) + 5u + cig +
+                    2u + mate + seq_qual + 6u + dec_digits(p.nm[rec]) + 6u + md_len + 1u;
   }
 }
 
@@ -1196,6 +1214,8 @@ __global__ void __launch_bounds__(256) sam_len_kernel(SamParams p) {
 // records), where each field of its line starts, and the short fields (numbers, separators, tags), written by the lane itself.
 // Then the wave goes through its records two at a time, the long fields (QNAME, RNAME, SEQ, QUAL, MD) a byte per lane, every
 // load of a pair requested before the first store; what a lane knows of record i reaches the others by v_readlane.
+// kPair: j counts lines, each rendering record perm[j] with the pair's FLAG and mate columns (the lane writes those itself).
+template <bool kPair>
 __global__ void __launch_bounds__(256) sam_write_kernel(SamParams p) {
   __shared__ uint8_t lut[256];
   lut[threadIdx.x] = kSamSeqLut[threadIdx.x];
@@ -1207,13 +1227,14 @@ __global__ void __launch_bounds__(256) sam_write_kernel(SamParams p) {
   const bool mine = ln < n_here;
   const uint32_t j = j0 + (mine ? ln : n_here - 1u);  // (lanes behind the last record repeat its loads and write nothing)
   // level 1
-  const uint32_t r = p.s_read[j];
-  const uint32_t t = p.tid[j];
-  const uint32_t flag = p.flag[j] & 0x7FFFu, pos1 = p.pos0[j] + 1u, nm = p.nm[j];
-  const uint32_t c0 = p.cigar_off[j], c1 = p.cigar_off[j + 1], m0 = p.md_off[j], md_len = p.md_off[j + 1] - m0;
+  const uint32_t rec = kPair ? p.perm[j] : j;
+  const uint32_t r = p.s_read[rec];
+  const uint32_t t = p.tid[rec];
+  const uint32_t flag = (kPair ? p.pflag[j] : p.flag[rec]) & 0x7FFFu, pos1 = p.pos0[rec] + 1u, nm = p.nm[rec];
+  const uint32_t c0 = p.cigar_off[rec], c1 = p.cigar_off[rec + 1], m0 = p.md_off[rec], md_len = p.md_off[rec + 1] - m0;
   const unsigned long long at = p.line_off[j];
   // level 2
-  const bool primary = p.rec_begin[r] == j;
+  const bool primary = kPair ? !(flag & 256u) : p.rec_begin[r] == j;
   const uint64_t ro = p.read_off[r];
   const uint32_t L = (uint32_t)(p.read_off[r + 1] - ro);
   const uint64_t no = p.name_off[r];
@@ -1239,7 +1260,7 @@ __global__ void __launch_bounds__(256) sam_write_kernel(SamParams p) {
   const uint32_t o_rname = o_flag + dec_digits(flag) + 1u;
   const uint32_t o_pos = o_rname + rname_len + 1u;
   const uint32_t o_cig = o_pos + dec_digits(pos1) + 5u;
-  const uint32_t o_seq = o_cig + cig + 7u;
+  const uint32_t o_seq = o_cig + cig + 2u + (kPair ? mate_cols_len(p, j, t) : 5u);
   const uint32_t o_nm = o_seq + (seq ? L + 1u + (p.quals || p.qual_hole ? L : 1u) : 3u) + 6u;
   const uint32_t o_md = o_nm + dec_digits(nm) + 6u;
   if (mine) {  // the short fields of the lane's own record
@@ -1262,7 +1283,29 @@ __global__ void __launch_bounds__(256) sam_write_kernel(SamParams p) {
         *q++ = (uint8_t)"MIDNSHP=XB"[op & 0xFu];
       }
     }
-    q[0] = '\t', q[1] = '*', q[2] = '\t', q[3] = '0', q[4] = '\t', q[5] = '0', q[6] = '\t';
+    if (!kPair) {
+      q[0] = '\t', q[1] = '*', q[2] = '\t', q[3] = '0', q[4] = '\t', q[5] = '0', q[6] = '\t';
+    } else {  // RNEXT PNEXT TLEN
+      const uint32_t mt = p.mtid[j];
+      *q++ = '\t';
+      if (mt == 0xFFFFFFFFu) {
+        q[0] = '*', q[1] = '\t', q[2] = '0', q[3] = '\t', q[4] = '0', q[5] = '\t';
+      } else {
+        if (mt == t) {
+          *q++ = '=';
+        } else {  // the other mate on another sequence (rare: its name a byte at a time)
+          const uint32_t n0 = p.ref_name_off[mt], n1 = p.ref_name_off[mt + 1];
+          for (uint32_t k = n0; k < n1; ++k) *q++ = p.ref_names[k];
+        }
+        *q++ = '\t';
+        q = put_dec(q, p.mpos0[j] + 1u);
+        *q++ = '\t';
+        const int32_t tl = p.tlen[j];
+        if (tl < 0) *q++ = '-';
+        q = put_dec(q, tl < 0 ? (uint32_t)-tl : (uint32_t)tl);
+        *q = '\t';
+      }
+    }
     uint8_t *w_seq = w + o_seq;
     if (seq) {
       w_seq[L] = '\t';
@@ -1349,6 +1392,161 @@ __global__ void __launch_bounds__(256) sam_write_kernel(SamParams p) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Pair mode: the records of read i (mate 1, list A) and of read n_pairs + i (mate 2, list B) of a batch of 2 n_pairs reads.
+// A combination (a, b) is concordant when neither carries 0x8000, both lie on one sequence on opposite strands, the forward one
+// f starts at or before the reverse one r, and I <= end0(r) - pos0(f) <= X (end0 = pos0 + the M and D lengths of the CIGAR).
+// The chosen one has the least nm(a) + nm(b), ties to the smaller a, then the smaller b.  Output lines: mate 1's, then
+// mate 2's, the chosen record first in each, the others in their order.
+// One lane per pair; a pair with more than kPairAlone combinations is taken by its whole wave after the lanes' own pairs.
+// ---------------------------------------------------------------------------------------------------------
+constexpr uint64_t kPairAlone = 32;
+constexpr uint64_t kNoKey = ~0ull;
+
+struct PairParams {
+  uint32_t n_pairs;
+  int64_t min_insert, max_insert;
+  const uint32_t *rec_begin;  // 2 n_pairs + 1
+  const uint16_t *flag;
+  const uint32_t *tid, *pos0;
+  const uint8_t *nm;
+  const uint32_t *cigar_off, *cigar;
+  uint32_t *perm;             // per line
+  uint16_t *pflag;
+  uint32_t *mtid, *mpos0;
+  int32_t *tlen;
+  uint32_t *pair_begin;       // 2 n_pairs + 1
+  uint32_t *n_proper;
+};
+
+struct MateRec {
+  uint32_t tid, pos0, flag, nm;
+  uint64_t end0;
+};
+
+__device__ __forceinline__ MateRec mate_rec(const PairParams &p, uint32_t r) {
+  MateRec m;
+  m.tid = p.tid[r], m.pos0 = p.pos0[r], m.flag = p.flag[r], m.nm = p.nm[r];
+  uint64_t span = 0;
+  for (uint32_t c = p.cigar_off[r], c1 = p.cigar_off[r + 1]; c < c1; ++c) {
+    const uint32_t op = p.cigar[c];
+    if ((op & 0xFu) == kOpM || (op & 0xFu) == kOpD) span += op >> 4;
+  }
+  m.end0 = (uint64_t)m.pos0 + span;
+  return m;
+}
+
+// the insert of a concordant combination, -1 otherwise (an insert is never negative: pos0(f) <= pos0(r) <= end0(r))
+__device__ __forceinline__ int64_t concordant(const PairParams &p, const MateRec &a, const MateRec &b) {
+  if (((a.flag | b.flag) & 0x8000u) || a.tid != b.tid || !((a.flag ^ b.flag) & 16u)) return -1;
+  const MateRec &f = (a.flag & 16u) ? b : a, &r = (a.flag & 16u) ? a : b;
+  if (f.pos0 > r.pos0) return -1;
+  const int64_t ins = (int64_t)(r.end0 - f.pos0);
+  return ins >= p.min_insert && ins <= p.max_insert ? ins : -1;
+}
+
+// lines [first, na + nb) of a pair, every step-th one
+__device__ void write_pair(const PairParams &p, uint32_t a0, uint32_t na, uint32_t b0, uint32_t nb, uint32_t ob, bool proper, uint32_t ca,
+                           uint32_t cb, int64_t insert, uint32_t first, uint32_t step) {
+  for (uint32_t u = first; u < na + nb; u += step) {
+    const bool m2 = u >= na;
+    const uint32_t t = m2 ? u - na : u, c = m2 ? cb : ca;
+    const uint32_t idx = proper ? (t == 0 ? c : t - 1u + (t - 1u >= c ? 1u : 0u)) : t;
+    const uint32_t rec = (m2 ? b0 : a0) + idx;
+    const bool has_other = m2 ? na > 0 : nb > 0;
+    const uint32_t other = m2 ? a0 + (proper ? ca : 0u) : b0 + (proper ? cb : 0u);
+    const uint32_t fl = p.flag[rec];
+    uint32_t nf = (fl & 0x8010u) | 1u | (m2 ? 0x80u : 0x40u) | (t ? 256u : 0u) | (proper && t == 0 ? 2u : 0u);
+    uint32_t mt = 0xFFFFFFFFu, mp = 0xFFFFFFFFu;
+    if (!has_other) {
+      nf |= 8u;
+    } else {
+      if (p.flag[other] & 16u) nf |= 0x20u;
+      mt = p.tid[other], mp = p.pos0[other];
+    }
+    const uint32_t k = ob + u;
+    p.perm[k] = rec, p.pflag[k] = (uint16_t)nf, p.mtid[k] = mt, p.mpos0[k] = mp;
+    p.tlen[k] = proper && t == 0 ? (int32_t)((fl & 16u) ? -insert : insert) : 0;
+  }
+}
+
+__device__ __forceinline__ uint32_t wave_bcast(uint32_t v, uint32_t lane) {
+  return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)lane);
+}
+
+__global__ void __launch_bounds__(256) pair_kernel(PairParams p) {
+  const uint32_t ln = threadIdx.x & 63u;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = i < p.n_pairs;
+  uint32_t a0 = 0, na = 0, b0 = 0, nb = 0, ob = 0;
+  if (live) {
+    const uint32_t mid = p.rec_begin[p.n_pairs];
+    a0 = p.rec_begin[i], na = p.rec_begin[i + 1] - a0;
+    b0 = p.rec_begin[p.n_pairs + i], nb = p.rec_begin[p.n_pairs + i + 1] - b0;
+    ob = a0 + b0 - mid;  // the lines of the pairs in front: their mate 1 records and their mate 2 records
+    p.pair_begin[2u * i] = ob, p.pair_begin[2u * i + 1u] = ob + na;
+    if (i + 1u == p.n_pairs) p.pair_begin[2u * i + 2u] = ob + na + nb;
+  }
+  const bool big = live && (uint64_t)na * nb > kPairAlone;
+  bool proper_here = false;
+  if (live && !big) {  // the lane alone: a ascending, b ascending, only a smaller sum replaces (the tie rule)
+    uint32_t best = 0xFFFFFFFFu, ca = 0, cb = 0;
+    int64_t ins = -1;
+    for (uint32_t a = 0; a < na; ++a) {
+      const MateRec ra = mate_rec(p, a0 + a);
+      if (ra.flag & 0x8000u) continue;
+      for (uint32_t b = 0; b < nb; ++b) {
+        const MateRec rb = mate_rec(p, b0 + b);
+        const int64_t x = concordant(p, ra, rb);
+        if (x >= 0 && ra.nm + rb.nm < best) best = ra.nm + rb.nm, ca = a, cb = b, ins = x;
+      }
+    }
+    proper_here = best != 0xFFFFFFFFu;
+    write_pair(p, a0, na, b0, nb, ob, proper_here, ca, cb, ins, 0u, 1u);
+  }
+  // pairs with many combinations (repeats): the wave, one pair after the other; the lanes stride over the longer list, each
+  // walks the shorter one; the least (nm sum, a, b) in two steps: (nm sum << 32 | a), then b among the lanes that hold it
+  uint64_t todo = __ballot(big);
+  while (todo) {
+    const uint32_t src = (uint32_t)__builtin_ctzll(todo);
+    todo &= todo - 1u;
+    const uint32_t A0 = wave_bcast(a0, src), NA = wave_bcast(na, src), B0 = wave_bcast(b0, src), NB = wave_bcast(nb, src);
+    const uint32_t OB = wave_bcast(ob, src);
+    const bool lanes_on_a = NA >= NB;
+    const uint32_t n_long = lanes_on_a ? NA : NB, n_short = lanes_on_a ? NB : NA;
+    uint64_t key = kNoKey;
+    uint32_t key_b = 0xFFFFFFFFu;
+    for (uint32_t u = ln; u < n_long; u += 64u) {
+      const MateRec ru = mate_rec(p, (lanes_on_a ? A0 : B0) + u);
+      if (ru.flag & 0x8000u) continue;
+      for (uint32_t v = 0; v < n_short; ++v) {
+        const MateRec rv = mate_rec(p, (lanes_on_a ? B0 : A0) + v);
+        if (concordant(p, ru, rv) < 0) continue;
+        const uint32_t a = lanes_on_a ? u : v, b = lanes_on_a ? v : u;
+        const uint64_t k = (uint64_t)(ru.nm + rv.nm) << 32 | a;
+        if (k < key || (k == key && b < key_b)) key = k, key_b = b;
+      }
+    }
+    uint64_t kmin = key;
+    for (int d = 32; d > 0; d >>= 1) {
+      const uint64_t o = (uint64_t)__shfl_xor((unsigned long long)kmin, d);
+      kmin = o < kmin ? o : kmin;
+    }
+    uint32_t bmin = key == kmin ? key_b : 0xFFFFFFFFu;
+    for (int d = 32; d > 0; d >>= 1) {
+      const uint32_t o = (uint32_t)__shfl_xor(bmin, d);
+      bmin = o < bmin ? o : bmin;
+    }
+    const bool proper = kmin != kNoKey;
+    const uint32_t ca = proper ? (uint32_t)kmin : 0u, cb = proper ? bmin : 0u;
+    const int64_t ins = proper ? concordant(p, mate_rec(p, A0 + ca), mate_rec(p, B0 + cb)) : -1;
+    write_pair(p, A0, NA, B0, NB, OB, proper, ca, cb, ins, ln, 64u);
+    if (ln == src) proper_here = proper;
+  }
+  const uint64_t proper_lanes = __ballot(proper_here);
+  if (ln == 0 && proper_lanes) atomicAdd(p.n_proper, (uint32_t)__builtin_popcountll(proper_lanes));
+}
+
 }  // namespace
 
 struct Tail::Impl {
@@ -1356,11 +1554,20 @@ struct Tail::Impl {
       flag, tid, pos0, nm, cigar_off, md_off, cigar, md, scan_tmp;
   DevBuf line_len, line_off, text, qual_at;
   PinBuf h_ctl, h_rec_begin, h_flag, h_tid, h_pos0, h_nm, h_cigar_off, h_md_off, h_cigar, h_md, h_text, h_qual_at;
+  // pair mode (pair()): per line, the pairs' line ranges, the proper-pair counter; their host copies (pair_fetch())
+  DevBuf perm, pflag, mtid, mpos0, tlen, pair_begin, pair_ctl;
+  PinBuf h_perm, h_pflag, h_mtid, h_mpos0, h_tlen, h_pair_begin, h_pair_ctl;
   uint32_t last_n = 0, last_nr = 0;  // what the last run() left on the device
+  bool paired = false;               // pair() has run on it
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t ev_pair[2] = {nullptr, nullptr};
   hipEvent_t ev_text = nullptr;  // the SAM text has arrived in h_text
   ~Impl() {
     if (ev_text) (void)hipEventDestroy(ev_text);
+    for (hipEvent_t e : ev_pair)
+      if (e) (void)hipEventDestroy(e);
+    for (DevBuf *b : {&perm, &pflag, &mtid, &mpos0, &tlen, &pair_begin, &pair_ctl}) b->release();
+    for (PinBuf *b : {&h_perm, &h_pflag, &h_mtid, &h_mpos0, &h_tlen, &h_pair_begin, &h_pair_ctl}) b->release();
     for (DevBuf *b : {&rec_begin, &queue, &ctl, &u_cand, &u_misc, &s_cand, &s_misc, &s_read, &t_ops, &t_md, &o_ops, &o_md, &ovf, &rec_list,
                       &src_slot, &n_ops, &n_md, &flag, &tid, &pos0, &nm, &cigar_off, &md_off, &cigar, &md, &scan_tmp, &line_len, &line_off, &text, &qual_at})
       b->release();
@@ -1449,8 +1656,9 @@ int Tail::warm(hipStream_t stream, std::string *err) {
                            (const void *)trace_fast_kernel<uint8_t, NoPlane>, (const void *)trace_fast_kernel<uint16_t, NoPlane>,
                            (const void *)trace_fast_kernel<uint16_t, uint8_t>, (const void *)trace_fast_kernel<uint32_t, NoPlane>,
                            (const void *)trace_fast_kernel<uint32_t, uint8_t>, (const void *)trace_fast_kernel<uint32_t, uint16_t>,
-                           (const void *)trace_kernel, (const void *)compact_kernel, (const void *)sam_len_kernel,
-                           (const void *)sam_write_kernel};
+                           (const void *)trace_kernel, (const void *)compact_kernel, (const void *)sam_len_kernel<false>,
+                           (const void *)sam_write_kernel<false>, (const void *)sam_len_kernel<true>,
+                           (const void *)sam_write_kernel<true>, (const void *)pair_kernel};
   for (const void *k : kernels) TAIL_TRY(hipFuncGetAttributes(&a, k));
   if (!m.scan_tmp.p || !m.rec_begin.p || !m.n_ops.p || !m.line_len.p) return FEM_OK;  // (nothing reserved: the scans load with the first batch)
   size_t tmp = m.scan_tmp.cap;
@@ -1614,7 +1822,7 @@ int Tail::run(const TailInput &in, hipStream_t stream, int n_cu, bool tiny, Tail
   TAIL_TRY(hipEventRecord(m.ev[3], stream));
   TAIL_TRY(hipMemcpyAsync(h_ctl + 4, m.cigar_off.as<uint32_t>() + nr, 4, hipMemcpyDeviceToHost, stream));
   TAIL_TRY(hipMemcpyAsync(h_ctl + 5, m.md_off.as<uint32_t>() + nr, 4, hipMemcpyDeviceToHost, stream));
-  m.last_n = n, m.last_nr = nr;
+  m.last_n = n, m.last_nr = nr, m.paired = false;
   if (!copy_records) {  // the caller renders them on the device (sam())
     TAIL_TRY(hipMemcpyAsync(h_ctl, m.ctl.p, 16, hipMemcpyDeviceToHost, stream));
     TAIL_TRY(hipStreamSynchronize(stream));
@@ -1691,9 +1899,13 @@ int Tail::wait_text() {
 }
 
 int Tail::sam(const TailInput &in, const SamInput &names, hipStream_t stream, int n_cu, SamOutput *out, std::string *err, double *ms,
-              bool wait, TextGate *gate) {
+              bool wait, TextGate *gate, bool paired) {
   if (!impl_ || !out) return FEM_ERR_STATE;
   Impl &m = *impl_;
+  if (paired && !m.paired) {
+    if (err) *err = "the records were not paired (Tail::pair)";
+    return FEM_ERR_STATE;
+  }
   const uint32_t nr = m.last_nr;
   const size_t r1 = (size_t)nr + 1;
   for (hipEvent_t &e : m.ev)
@@ -1721,9 +1933,15 @@ int Tail::sam(const TailInput &in, const SamInput &names, hipStream_t stream, in
   }
   p.line_len = m.line_len.as<unsigned long long>(), p.line_off = m.line_off.as<unsigned long long>();
   p.asserted = m.ctl.as<uint32_t>() + 2;  // (ctl[2] is zero after a successful run())
+  if (paired) {
+    p.perm = m.perm.as<uint32_t>(), p.pflag = m.pflag.as<uint16_t>(), p.mtid = m.mtid.as<uint32_t>(), p.mpos0 = m.mpos0.as<uint32_t>();
+    p.tlen = m.tlen.as<int32_t>();
+  }
   unsigned long long *h_total = (unsigned long long *)(m.h_ctl.as<uint32_t>() + 6);
   TAIL_TRY(hipEventRecord(m.ev[0], stream));
-  hipLaunchKernelGGL(sam_len_kernel, dim3(std::max<uint32_t>(1u, std::min<uint32_t>((nr + 256u) / 256u, (uint32_t)n_cu * 16u))), dim3(256), 0, stream, p);
+  const dim3 len_grid(std::max<uint32_t>(1u, std::min<uint32_t>((nr + 256u) / 256u, (uint32_t)n_cu * 16u)));
+  if (paired) hipLaunchKernelGGL(sam_len_kernel<true>, len_grid, dim3(256), 0, stream, p);
+  else hipLaunchKernelGGL(sam_len_kernel<false>, len_grid, dim3(256), 0, stream, p);
   TAIL_TRY(hipGetLastError());
   TAIL_TRY(rocprim::exclusive_scan(m.scan_tmp.p, m.scan_tmp.cap, m.line_len.as<unsigned long long>(), m.line_off.as<unsigned long long>(), 0ull,
                                    r1, rocprim::plus<unsigned long long>(), stream));
@@ -1736,7 +1954,8 @@ int Tail::sam(const TailInput &in, const SamInput &names, hipStream_t stream, in
   if (nr) {
     p.text = m.text.as<uint8_t>();
     const uint32_t blocks = (nr + 255u) / 256u;  // a wave per 64 records
-    hipLaunchKernelGGL(sam_write_kernel, dim3(blocks), dim3(256), 0, stream, p);
+    if (paired) hipLaunchKernelGGL(sam_write_kernel<true>, dim3(blocks), dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL(sam_write_kernel<false>, dim3(blocks), dim3(256), 0, stream, p);
     TAIL_TRY(hipGetLastError());
   }
   TAIL_TRY(hipEventRecord(m.ev[1], stream));
@@ -1762,6 +1981,79 @@ int Tail::sam(const TailInput &in, const SamInput &names, hipStream_t stream, in
   }
   out->text = m.h_text.as<char>(), out->len = total, out->n_asserted = m.h_ctl.as<uint32_t>()[2];
   out->qual_at = hole ? m.h_qual_at.as<uint64_t>() : nullptr;
+  return FEM_OK;
+}
+
+int Tail::pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::string *err) {
+  if (!impl_) return FEM_ERR_STATE;
+  Impl &m = *impl_;
+  const uint32_t n = m.last_n, nr = m.last_nr, np = n / 2u;
+  if (n & 1u) {
+    if (err) *err = "a paired batch holds an even number of reads";
+    return FEM_ERR_INVALID;
+  }
+  const size_t lines = std::max<size_t>(nr, 1);
+  TAIL_TRY(m.perm.need(lines * 4));
+  TAIL_TRY(m.pflag.need(lines * 2));
+  TAIL_TRY(m.mtid.need(lines * 4));
+  TAIL_TRY(m.mpos0.need(lines * 4));
+  TAIL_TRY(m.tlen.need(lines * 4));
+  TAIL_TRY(m.pair_begin.need(((size_t)n + 1) * 4));
+  TAIL_TRY(m.pair_ctl.need(16));
+  TAIL_TRY(m.h_pair_ctl.need(16));
+  for (hipEvent_t &e : m.ev_pair)
+    if (!e) TAIL_TRY(hipEventCreate(&e));
+  TAIL_TRY(hipEventRecord(m.ev_pair[0], stream));
+  TAIL_TRY(hipMemsetAsync(m.pair_ctl.p, 0, 16, stream));
+  if (np) {
+    PairParams q{};
+    q.n_pairs = np, q.min_insert = min_insert, q.max_insert = max_insert;
+    q.rec_begin = m.rec_begin.as<uint32_t>(), q.flag = m.flag.as<uint16_t>(), q.tid = m.tid.as<uint32_t>(), q.pos0 = m.pos0.as<uint32_t>();
+    q.nm = m.nm.as<uint8_t>(), q.cigar_off = m.cigar_off.as<uint32_t>(), q.cigar = m.cigar.as<uint32_t>();
+    q.perm = m.perm.as<uint32_t>(), q.pflag = m.pflag.as<uint16_t>(), q.mtid = m.mtid.as<uint32_t>(), q.mpos0 = m.mpos0.as<uint32_t>();
+    q.tlen = m.tlen.as<int32_t>(), q.pair_begin = m.pair_begin.as<uint32_t>(), q.n_proper = m.pair_ctl.as<uint32_t>();
+    hipLaunchKernelGGL(pair_kernel, dim3((np + 255u) / 256u), dim3(256), 0, stream, q);
+    TAIL_TRY(hipGetLastError());
+  } else {
+    TAIL_TRY(hipMemsetAsync(m.pair_begin.p, 0, 4, stream));
+  }
+  TAIL_TRY(hipEventRecord(m.ev_pair[1], stream));
+  TAIL_TRY(hipMemcpyAsync(m.h_pair_ctl.p, m.pair_ctl.p, 4, hipMemcpyDeviceToHost, stream));
+  m.paired = true;
+  return FEM_OK;
+}
+
+uint64_t Tail::n_proper() const { return impl_ && impl_->paired && impl_->h_pair_ctl.p ? impl_->h_pair_ctl.as<uint32_t>()[0] : 0; }
+
+float Tail::pair_ms() const {
+  float t = 0.f;
+  if (!impl_ || !impl_->paired || hipEventElapsedTime(&t, impl_->ev_pair[0], impl_->ev_pair[1]) != hipSuccess) return 0.f;
+  return t;
+}
+
+int Tail::pair_fetch(hipStream_t stream, PairOutput *out, std::string *err) {
+  if (!impl_ || !impl_->paired || !out) return FEM_ERR_STATE;
+  Impl &m = *impl_;
+  const uint32_t n = m.last_n, nr = m.last_nr;
+  const size_t lines = std::max<size_t>(nr, 1);
+  TAIL_TRY(m.h_perm.need(lines * 4));
+  TAIL_TRY(m.h_pflag.need(lines * 2));
+  TAIL_TRY(m.h_mtid.need(lines * 4));
+  TAIL_TRY(m.h_mpos0.need(lines * 4));
+  TAIL_TRY(m.h_tlen.need(lines * 4));
+  TAIL_TRY(m.h_pair_begin.need(((size_t)n + 1) * 4));
+  if (nr) {
+    TAIL_TRY(hipMemcpyAsync(m.h_perm.p, m.perm.p, (size_t)nr * 4, hipMemcpyDeviceToHost, stream));
+    TAIL_TRY(hipMemcpyAsync(m.h_pflag.p, m.pflag.p, (size_t)nr * 2, hipMemcpyDeviceToHost, stream));
+    TAIL_TRY(hipMemcpyAsync(m.h_mtid.p, m.mtid.p, (size_t)nr * 4, hipMemcpyDeviceToHost, stream));
+    TAIL_TRY(hipMemcpyAsync(m.h_mpos0.p, m.mpos0.p, (size_t)nr * 4, hipMemcpyDeviceToHost, stream));
+    TAIL_TRY(hipMemcpyAsync(m.h_tlen.p, m.tlen.p, (size_t)nr * 4, hipMemcpyDeviceToHost, stream));
+  }
+  TAIL_TRY(hipMemcpyAsync(m.h_pair_begin.p, m.pair_begin.p, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost, stream));
+  TAIL_TRY(hipStreamSynchronize(stream));
+  out->n_pairs = n / 2u, out->n_records = nr, out->n_proper = m.h_pair_ctl.as<uint32_t>()[0];
+  out->pair_begin = m.h_pair_begin.as<uint32_t>(), out->perm = m.h_perm.as<uint32_t>(), out->flag = m.h_pflag.as<uint16_t>();
+  out->mate_tid = m.h_mtid.as<uint32_t>(), out->mate_pos0 = m.h_mpos0.as<uint32_t>(), out->tlen = m.h_tlen.as<int32_t>();
   return FEM_OK;
 }
 

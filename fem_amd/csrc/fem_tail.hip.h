@@ -68,6 +68,16 @@ struct SamOutput {  // pinned host memory owned by the Tail object, valid until 
   const uint64_t *qual_at;  // qual_hole: per READ, where in `text` its QUAL field starts (~0: the read has no record); else nullptr
 };
 
+// ---- pair mode: the reads of the last run() are n / 2 read pairs, read i and read n / 2 + i the two mates of pair i ----
+struct PairOutput {  // pinned host memory owned by the Tail object, valid until its next pair_fetch()
+  uint64_t n_pairs, n_records, n_proper;
+  const uint32_t *pair_begin;  // 2 * n_pairs + 1: mate m of pair i has output lines [pair_begin[2i+m], pair_begin[2i+m+1])
+  const uint32_t *perm;        // n_records: line k renders record perm[k] (record numbers of run()'s output)
+  const uint16_t *flag;        // per line: the SAM flag as written, 0x8000 kept
+  const uint32_t *mate_tid, *mate_pos0;  // per line: the other mate's primary (0xFFFFFFFF: the other mate has no record)
+  const int32_t *tlen;         // per line
+};
+
 // One text on its way home at a time (per GPU).  Two device-to-host copies queued in the copy engines take both of them, and
 // the next batch's reads wait for their copy in until every queued text is home (scratch/sdma_probe.hip: a 30 MB copy in
 // behind ONE 300 MB copy out is done after 0.6 ms, behind four after all four, 22 ms); FEM map's device then alternated
@@ -99,8 +109,16 @@ class Tail {
   // The records of the last run() as SAM lines, in record order.  ms (optional) receives the device time.
   // wait = false: returns once the copy of the text to the host has been queued; wait_text() (which may be called from
   // another thread) returns when it has arrived.
+  // paired = true: the lines in the order of the last pair() with its mate columns (the records of both stay on the device).
   int sam(const TailInput &in, const SamInput &names, hipStream_t stream, int n_cu, SamOutput *out, std::string *err, double *ms,
-          bool wait = true, TextGate *gate = nullptr);
+          bool wait = true, TextGate *gate = nullptr, bool paired = false);
+  // Pairs the records of the last run() (pair_kernel): output order, FLAG, mate columns and TLEN of every line, the proper-pair
+  // count.  Asynchronous on `stream`; n_proper() is valid once the stream has been synchronised (sam() does).
+  int pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::string *err);
+  uint64_t n_proper() const;
+  float pair_ms() const;  // device time of the last pair(), once its stream has been synchronised (timing: 0 otherwise)
+  // The arrays of the last pair() to the host (waits for `stream`).
+  int pair_fetch(hipStream_t stream, PairOutput *out, std::string *err);
   int wait_text();
 
  private:

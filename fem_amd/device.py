@@ -19,6 +19,7 @@ ABI_SYMBOLS = [
     "fem_dev_h2d_bandwidth",
     "fem_device_numa", "fem_bind_thread_near_device",
     "fem_dev_allreduce_stats",
+    "fem_dev_set_pairs", "fem_dev_fetch_pairs", "fem_dev_pair_count",
 ]
 
 
@@ -56,6 +57,17 @@ class _BatchRecords(C.Structure):
 class _BatchSam(C.Structure):
     _fields_ = [("text", C.c_void_p), ("len", C.c_uint64), ("n_reads", C.c_uint64), ("n_records", C.c_uint64),
                 ("n_asserted", C.c_uint64), ("stats", C.c_uint64 * 5)]
+
+
+class _PairParams(C.Structure):
+    _fields_ = [("min_insert", C.c_int32), ("max_insert", C.c_int32)]
+
+
+class _BatchPairs(C.Structure):
+    _fields_ = [("n_pairs", C.c_uint64), ("n_records", C.c_uint64), ("rec_begin", C.c_void_p), ("flag", C.c_void_p),
+                ("tid", C.c_void_p), ("pos0", C.c_void_p), ("nm", C.c_void_p), ("cigar_off", C.c_void_p),
+                ("cigar", C.c_void_p), ("md_off", C.c_void_p), ("md", C.c_void_p), ("mate_tid", C.c_void_p),
+                ("mate_pos0", C.c_void_p), ("tlen", C.c_void_p), ("n_proper", C.c_uint64), ("stats", C.c_uint64 * 5)]
 
 
 def hip_library_path():
@@ -121,6 +133,10 @@ def load_hip():
     L.fem_dev_fetch_sam_nowait.argtypes = [vp, C.c_int, C.POINTER(_BatchSam)]
     L.fem_dev_sam_wait.argtypes = [vp, C.c_int]
     L.fem_dev_stage_info.argtypes = [vp, C.c_int, C.POINTER(u64), C.POINTER(C.c_int32)]
+    if hasattr(L, "fem_dev_set_pairs"):
+        L.fem_dev_set_pairs.argtypes = [vp, C.c_int, C.POINTER(_PairParams)]
+        L.fem_dev_fetch_pairs.argtypes = [vp, C.c_int, C.POINTER(_BatchPairs)]
+        L.fem_dev_pair_count.argtypes = [vp, C.c_int, C.POINTER(u64)]
     L.fem_device_numa.argtypes = [C.c_int, C.POINTER(C.c_int32), C.c_char_p, u64]
     L.fem_bind_thread_near_device.argtypes = [C.c_int]
     _HIP = L
@@ -270,6 +286,28 @@ class BatchRecords:
         self.cigar = _copy(r.cigar, int(self.cigar_off[-1]) if nr + 1 else 0, np.uint32)
         self.md_off = _copy(r.md_off, nr + 1, np.uint32)
         self.md = _copy(r.md, int(self.md_off[-1]) if nr + 1 else 0, np.uint8)
+        self.stats = np.array(list(r.stats), dtype=np.uint64)
+
+
+class BatchPairs:
+    """Host copy of fem_batch_pairs: the batch's records in paired output order, with the mate columns.  rec_begin[2 i + m]:
+    first record of mate m of pair i."""
+
+    def __init__(self, r):
+        n_pairs, nr = int(r.n_pairs), int(r.n_records)
+        self.n_pairs, self.n_records, self.n_proper = n_pairs, nr, int(r.n_proper)
+        self.rec_begin = _copy(r.rec_begin, 2 * n_pairs + 1, np.uint32)
+        self.flag = _copy(r.flag, nr, np.uint16)
+        self.tid = _copy(r.tid, nr, np.uint32)
+        self.pos0 = _copy(r.pos0, nr, np.uint32)
+        self.nm = _copy(r.nm, nr, np.uint8)
+        self.cigar_off = _copy(r.cigar_off, nr + 1, np.uint32)
+        self.cigar = _copy(r.cigar, int(self.cigar_off[-1]), np.uint32)
+        self.md_off = _copy(r.md_off, nr + 1, np.uint32)
+        self.md = _copy(r.md, int(self.md_off[-1]), np.uint8)
+        self.mate_tid = _copy(r.mate_tid, nr, np.uint32)
+        self.mate_pos0 = _copy(r.mate_pos0, nr, np.uint32)
+        self.tlen = _copy(r.tlen, nr, np.int32)
         self.stats = np.array(list(r.stats), dtype=np.uint64)
 
 
@@ -460,6 +498,26 @@ class Device:
                 raise FemError("fem_sam_fill_quals failed (%d)" % rc)
         text = C.string_at(r.text, r.len) if r.len else b""
         return text, int(r.n_records), int(r.n_asserted), np.array(list(r.stats), dtype=np.uint64)
+
+    def set_pairs(self, min_insert=0, max_insert=500, slot=0):
+        """fem_dev_set_pairs: the slot's batches are read pairs (read i and read n/2 + i); min_insert=None: single-end again."""
+        if min_insert is None:
+            self._check(self._L.fem_dev_set_pairs(self._h, slot, None))
+        else:
+            pp = _PairParams(int(min_insert), int(max_insert))
+            self._check(self._L.fem_dev_set_pairs(self._h, slot, C.byref(pp)))
+
+    def fetch_pairs(self, slot=0):
+        """fem_dev_fetch_pairs: the records paired on the device, in output order (BatchPairs)."""
+        r = _BatchPairs()
+        self._check(self._L.fem_dev_fetch_pairs(self._h, slot, C.byref(r)))
+        return BatchPairs(r)
+
+    def pair_count(self, slot=0):
+        """fem_dev_pair_count: proper pairs of the slot's last paired text."""
+        n = C.c_uint64()
+        self._check(self._L.fem_dev_pair_count(self._h, slot, C.byref(n)))
+        return int(n.value)
 
     def map_batch(self, bases, offsets, e=3, a=1, k=12, step=3, slot=0):
         b, keep = self._batch(bases, offsets)

@@ -63,6 +63,7 @@ def lib():
         L.fem_seqset_free.argtypes = [C.POINTER(SeqSet)]
         L.fem_seqfile_read_bytes.argtypes = [vp, u64, C.c_int, C.POINTER(SeqSet)]
         L.fem_seqfile_plan.argtypes = [vp, u64, C.c_int, C.POINTER(vp), C.POINTER(BatchShape)]
+        L.fem_seqfile_plan_count.argtypes = [vp, u64, C.c_int, C.POINTER(vp), C.POINTER(BatchShape)]
         L.fem_seqfile_fill.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp]
         L.fem_seqfile_fill_packed.argtypes = [vp, vp, C.c_int, C.c_uint32, vp, u64, C.POINTER(u64), vp, vp, vp]
         L.fem_seqfile_fill_packed_refs.argtypes = [vp, vp, C.c_int, C.c_uint32, vp, u64, C.POINTER(u64), vp]
@@ -363,6 +364,37 @@ def read_planned_batches(path, approx_bytes, threads=4, alloc=None, packed=False
                     continue
                 if rc != 1:
                     raise ValueError("fem_seqfile_fill_packed failed (%d)" % rc)
+            rc = L.fem_seqfile_fill(f, plan, threads, bases.ctypes.data, off.ctypes.data,
+                                    quals.ctypes.data if quals is not None else None, names.ctypes.data, name_off.ctypes.data)
+            if rc != 0:
+                raise ValueError("fem_seqfile_fill failed (%d)" % rc)
+            out.append(PlannedBatch(shape, bases, off, quals, names, name_off))
+    finally:
+        L.fem_seqfile_close(f)
+    return out
+
+
+def read_counted_batches(path, counts, threads=4):
+    """Batches of exactly counts[i] records (fewer at the end of the input) through fem_seqfile_plan_count + fem_seqfile_fill:
+    how FEM map cuts the second file of read pairs.  One PlannedBatch per entry of counts."""
+    L = lib()
+    f = L.fem_seqfile_open(path.encode())
+    if not f:
+        raise FileNotFoundError(path)
+    out = []
+    try:
+        for want in counts:
+            plan, shape = C.c_void_p(), BatchShape()
+            rc = L.fem_seqfile_plan_count(f, int(want), threads, C.byref(plan), C.byref(shape))
+            if rc != 0:
+                if plan:
+                    L.fem_batch_plan_free(plan)
+                raise ValueError("malformed sequence file %s (rc=%d)" % (path, rc))
+            n, nb = int(shape.n_reads), int(shape.n_bases)
+            bases, off = np.zeros(nb + 64, np.uint8), np.zeros(n + 1, np.uint64)
+            quals = np.zeros(nb + 1, np.uint8) if shape.has_qual else None
+            names = np.zeros(int(shape.n_name_bytes) + 1, np.uint8)
+            name_off = np.zeros(n + 1, np.uint64)
             rc = L.fem_seqfile_fill(f, plan, threads, bases.ctypes.data, off.ctypes.data,
                                     quals.ctypes.data if quals is not None else None, names.ctypes.data, name_off.ctypes.data)
             if rc != 0:

@@ -268,6 +268,44 @@ int fem_dev_fetch_sam(fem_dev *h, int slot, fem_batch_sam *out);
 int fem_dev_fetch_sam_nowait(fem_dev *h, int slot, fem_batch_sam *out);
 int fem_dev_sam_wait(fem_dev *h, int slot);
 
+/* ---- read pairs (new: the reference maps single-end reads only) ----
+ * fem_dev_set_pairs: the slot's batches are read pairs from now on: read i and read n_reads/2 + i are the two mates of pair i
+ *   (mate 1's reads first, then mate 2's, in the same order).  NULL: single-end again.  FEM_ERR_INVALID for min_insert < 0,
+ *   max_insert < min_insert, max_insert > 2^30.
+ * In pair mode fem_dev_fetch_sam / fem_dev_fetch_sam_nowait render the paired text: pairs in batch order, mate 1's lines then
+ *   mate 2's, the chosen combination's records first (below), FLAG with 0x1 0x2 0x8 0x20 0x40 0x80, RNEXT PNEXT TLEN filled.
+ *   The qualities may stay on the host as in single-end mode (fem_dev_commit_names_stage -> fem_dev_sam_quals: qual_at per read,
+ *   numbered as staged).  fem_dev_fetch, fem_dev_fetch_packed, fem_dev_fetch_records and fem_dev_fetch_stats keep their
+ *   single-end meaning over the n_reads reads.  An odd n_reads is FEM_ERR_INVALID at fetch time.
+ * Pairing: the records of each mate as single-end mode makes them, lists A and B.  (a, b) is concordant when neither carries
+ *   0x8000, both lie on one sequence on opposite strands, the forward one f starts at or before the reverse one r, and
+ *   min_insert <= end0(r) - pos0(f) <= max_insert (end0 = pos0 + the M and D lengths of the CIGAR: the insert).  The chosen
+ *   combination has the least nm(a) + nm(b), ties to the smaller index in A, then in B; a pair with one is a proper pair.
+ * A paired batch's call order: fem_dev_acquire_stage + fem_dev_acquire_text_stage, the parser fills mate 1's reads then mate
+ *   2's (offsets and name offsets running on), fem_dev_commit_stage*, fem_dev_map_staged, fem_dev_commit_text_stage (or
+ *   _names_stage), fem_dev_fetch_sam[_nowait] (+ fem_dev_sam_wait), fem_dev_pair_count. */
+typedef struct {
+  int32_t min_insert, max_insert;
+} fem_pair_params;
+int fem_dev_set_pairs(fem_dev *h, int slot, const fem_pair_params *pp);
+/* The records of the slot's batch in paired output order.  Same lifetime as fem_batch_records.  FEM_ERR_STATE without pair mode. */
+typedef struct {
+  uint64_t n_pairs, n_records;
+  const uint32_t *rec_begin; /* 2*n_pairs+1: mate m (0, 1) of pair i has records [rec_begin[2i+m], rec_begin[2i+m+1]), primary first */
+  const uint16_t *flag;      /* the full SAM flag as written (0x8000 kept as in fem_batch_records) */
+  const uint32_t *tid, *pos0;
+  const uint8_t *nm;
+  const uint32_t *cigar_off, *cigar, *md_off;
+  const char *md;
+  const uint32_t *mate_tid, *mate_pos0; /* 0xFFFFFFFF: the other mate has no record */
+  const int32_t *tlen;
+  uint64_t n_proper;
+  uint64_t stats[5];
+} fem_batch_pairs;
+int fem_dev_fetch_pairs(fem_dev *h, int slot, fem_batch_pairs *out);
+/* Proper pairs of the slot's last paired SAM text (valid once fem_dev_fetch_sam[_nowait] has returned) or fem_dev_fetch_pairs. */
+int fem_dev_pair_count(fem_dev *h, int slot, uint64_t *n_proper);
+
 /* Name of the seed + filter kernel fem_dev_map_staged would launch first for these parameters on the resident
  * index ("seed_join_kernel" — behind its "seed_select_kernel"; "seed_join_banked_kernel" where the reference's sequences
  * need more than one 32-bit coordinate space —, "seed_fast_kernel<hash>", "seed_fast_kernel<lean>" or
@@ -291,7 +329,8 @@ int fem_dev_index_info(const fem_dev *h, char *buf, uint64_t cap);
  * 6 = unused, always 0 (the count kernel of rounds 1-2; the counters come out of kernel 1 now); of fem_dev_fetch_sam:
  * 7 = the SAM text kernels;
  * 8 = seed selection kernel of the dense-index path (it runs beside the previous batch's kernel 0: its event time is
- * what it takes there, not what it would take alone). */
+ * what it takes there, not what it would take alone);
+ * 9 = the pairing kernel of a paired fem_dev_fetch_sam (fem_dev_set_pairs). */
 int fem_dev_set_timing(fem_dev *h, int on);
 int fem_dev_reset_timing(fem_dev *h);
 int fem_dev_kernel_time(fem_dev *h, int kernel, double *ms_total, uint64_t *launches);
