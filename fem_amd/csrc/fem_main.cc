@@ -422,14 +422,16 @@ int map_main(int argc, char **argv) {
         // the slots' pinned staging (and, for the device's SAM text, its buffers): pinning host memory takes ~0.25 ms per
         // MB, 35 ms per slot here, and belongs to the setup rather than to the first batches
         int32_t ns = 4;
-        if (!rc) (void)fem_dev_limits(devs[(size_t)g], nullptr, &ns);
+        uint32_t max_read_len = 0;
+        if (!rc) (void)fem_dev_limits(devs[(size_t)g], &max_read_len, &ns);
         for (int sl = 0; !rc && sl < ns; ++sl) {
           char *pb = nullptr, *pq = nullptr, *pn = nullptr;
           uint64_t *po = nullptr, *pno = nullptr;
           rc = fem_dev_acquire_stage(devs[(size_t)g], sl, reads_cap0, bases_cap0, &pb, &po);
           if (!rc && device_text) rc = fem_dev_acquire_text_stage(devs[(size_t)g], sl, reads_cap0, bases_cap0, names_cap0, &pq, &pn, &pno);
           if (!rc && device_text) rc = fem_dev_reserve_text(devs[(size_t)g], sl, reads_cap0, bases_cap0, names_cap0, batch_bytes + batch_bytes / 4);
-          if (!rc && device_text && res_reads) rc = fem_dev_reserve_batch(devs[(size_t)g], sl, res_reads, res_reads + res_reads / 8, res_len, &params);
+          // (a read over the device's limit among the first records: no reservation, the staging of its batch names the read)
+          if (!rc && device_text && res_reads && res_len <= max_read_len) rc = fem_dev_reserve_batch(devs[(size_t)g], sl, res_reads, res_reads + res_reads / 8, res_len, &params);
           if (!rc && paired) {
             const fem_pair_params pp{(int32_t)min_insert, (int32_t)max_insert};
             rc = fem_dev_set_pairs(devs[(size_t)g], sl, &pp);
@@ -500,7 +502,7 @@ int map_main(int argc, char **argv) {
   // FEM_STAGE_TIMES=1: busy seconds of each pipeline stage on stderr at the end
   const char *st_env = getenv("FEM_STAGE_TIMES");
   const bool stage_times = st_env && (st_env[0] == '1' || st_env[0] == '2');
-  const bool batch_times = st_env && st_env[0] == '2';  // ... =2: and every batch's way through them
+  const bool batch_times = st_env && st_env[0] == '2';  // ... =2: and every batch's way through them, and the form its bases took
   double busy_read = 0, busy_text = 0, busy_write = 0, busy_plan = 0;
   std::mutex stat_mu;  // (busy_text: the batches' retiring threads add to it)
   double wait_slot = 0, wait_records = 0, wait_text_buf = 0;  // reader waiting for a free slot, formatter for records / a text buffer
@@ -539,10 +541,11 @@ int map_main(int argc, char **argv) {
         busy_write += real_time() - t_w;
         fprintf(stderr, "Mapped read batch in %fs.\n", real_time() - it.b->t_submit);
         if (batch_times)
-          fprintf(stderr, "[FEM] batch %lu gpu %d slot %d (ms): slot %.2f filled %.2f submit %.2f..%.2f retired %.2f text home %.2f written %.2f\n",
+          fprintf(stderr, "[FEM] batch %lu gpu %d slot %d (ms): slot %.2f filled %.2f submit %.2f..%.2f retired %.2f text home %.2f written %.2f; "
+                          "bases sent as %s\n",
                   (unsigned long)it.b->seq, it.b->gpu, it.b->slot, 1e3 * (it.b->t_slot - t_start), 1e3 * (it.b->t_filled - t_start),
                   1e3 * (it.b->t_submit - t_start), 1e3 * (it.b->t_submitted - t_start), 1e3 * (it.b->t_retired - t_start),
-                  1e3 * (it.b->t_text - t_start), 1e3 * (real_time() - t_start));
+                  1e3 * (it.b->t_text - t_start), 1e3 * (real_time() - t_start), it.b->packed ? "2-bit codes" : "characters");
         free_q.push(it.b);  // written: the slot's buffers may be refilled
         continue;
       }

@@ -74,6 +74,83 @@ def test_myers32_equals_banded_dp(e):
     assert n_checked > 200
 
 
+def _end_edits(rng, read, at_start, at_end):
+    """A substitution or an insertion right at the read's first (at_start) and / or last (at_end) bases; same length."""
+    r = bytearray(read)
+    L = len(r)
+    for where, on in ((0, at_start), (L - 1, at_end)):
+        if not on:
+            continue
+        if rng.random() < 0.6:
+            r[where] = util.ACGT[(util.ACGT.tolist().index(r[where]) + 1 + int(rng.integers(0, 3))) % 4] if r[where] in b"ACGT" else 65
+        elif where == 0:
+            r = bytearray(bytes(util.ACGT[rng.integers(0, 4, 1)]) + bytes(r[:-1]))
+        else:
+            r = bytearray(bytes(r[:-2]) + bytes(util.ACGT[rng.integers(0, 4, 1)]) + bytes(r[-1:]))
+    return bytes(r)
+
+
+LONG_LENGTHS = (257, 300, 301, 443, 515, 700, 1000, 1023, 1024)
+
+
+@pytest.mark.parametrize("e", [0, 1, 3, 5, 7])
+def test_myers32_equals_banded_dp_on_long_reads(e):
+    # reads of 257..1024 bases (the device path's whole range: kMaxReadLen), edits at both ends of the read
+    rng = np.random.default_rng(2100 + e)
+    n_checked = n_acc = 0
+    for trial in range(45):
+        L = LONG_LENGTHS[trial % len(LONG_LENGTHS)] if trial < 2 * len(LONG_LENGTHS) else int(rng.integers(301, 1025))
+        ref = util.rand_seq(rng, L + 4 * e + 8)
+        shift = int(rng.integers(0, 2 * e + 1))
+        read = util.mutate(rng, ref[shift:shift + L + e], int(rng.integers(0, e + 1)))[:L]
+        if len(read) < L:
+            read = read + util.rand_seq(rng, L - len(read))
+        read = _end_edits(rng, read, trial % 3 != 1, trial % 3 != 2)
+        if trial % 7 == 0:
+            read = bytearray(read)
+            read[int(rng.integers(0, L))] = 78
+            read = bytes(read)
+        assert len(read) == L
+        ed, end = fo.banded_ed32(e, ref, read)
+        m_ed, m_end = banded_dp(e, ref, read)
+        if m_end is None:
+            assert ed == e + 1
+        else:
+            assert (ed, end) == (m_ed, m_end), (e, trial, L)
+            n_acc += ed <= e
+        n_checked += 1
+    assert n_checked == 45 and (n_acc > 10 or e == 0)
+
+
+@pytest.mark.parametrize("e", [1, 3, 7])
+def test_myers16x8_agrees_with_myers32_on_long_reads(e):
+    rng = np.random.default_rng(2200 + e)
+    n_acc = 0
+    for trial in range(24):
+        L = (1023, 1024, 257, 301, 515, 700, 1000, 443)[trial % 8] if trial < 16 else int(rng.integers(257, 1025))
+        base = util.rand_seq(rng, L + 4 * e + 8)
+        read = util.mutate(rng, base[e:e + L + e], int(rng.integers(0, e)) if e > 1 else 0)[:L]
+        if len(read) < L:
+            read = read + util.rand_seq(rng, L - len(read))
+        read = _end_edits(rng, read, trial % 2 == 0, trial % 4 < 2)
+        pats = []
+        for lane in range(8):
+            if lane < 5:
+                p = util.mutate(rng, base, int(rng.integers(0, 3)))
+                p = (p + util.rand_seq(rng, 16))[:L + 4 * e + 8]
+            else:
+                p = util.rand_seq(rng, L + 4 * e + 8)
+            pats.append(p)
+        ed16, end16 = fo.banded_ed16x8(e, pats, read)
+        for lane in range(8):
+            ed32, end32 = fo.banded_ed32(e, pats[lane], read)
+            assert (ed16[lane] <= e) == (ed32 <= e), (e, trial, L, lane)
+            if ed32 <= e:
+                assert (int(ed16[lane]), int(end16[lane])) == (ed32, end32), (e, trial, L, lane)
+                n_acc += 1
+    assert n_acc > 30
+
+
 @pytest.mark.parametrize("e", [1, 3, 7])
 def test_myers16x8_agrees_with_myers32_on_accepts(e):
     rng = np.random.default_rng(7 + e)
@@ -195,6 +272,28 @@ def test_seeding_equals_closed_form(e, a, L):
         assert n_nonempty == 0
 
 
+@pytest.mark.parametrize("e,a,L", [(3, 1, 300), (3, 1, 450), (3, 1, 520), (3, 1, 1024),
+                                   (7, 2, 300), (7, 2, 450), (7, 2, 520), (7, 2, 1024)])
+def test_seeding_equals_closed_form_on_long_reads(e, a, L):
+    # the DP widths of the device's selection kernel on both sides of 32, 64 and 128 columns (R = 4 and R = 10), and
+    # reads of the device path's greatest length; repeat units longer than the read, so that whole reads recur
+    rng = np.random.default_rng(3000 + 10 * e + a + L)
+    seqs = util.repeat_rich_reference(rng, n_seq=2, unit_len=L + 60, n_units=3, copies=12, spacer=120)
+    assert min(len(s) for s in seqs) > 12 * L
+    ref = fo.Reference(seqs)
+    idx = fo.OracleIndex(ref)
+    reads = util.make_reads(rng, seqs, 24, L, e, n_rate=0.002)
+    n_nonempty = 0
+    for r in reads:
+        for strand in (r, fo.revcomp(r)):
+            got, pre = fo.seed_candidates(ref, idx, strand, e=e, a=a)
+            want, wpre = closed_form_candidates(ref, idx, strand, e, a)
+            assert pre == wpre
+            assert list(map(int, got)) == want
+            n_nonempty += bool(want)
+    assert n_nonempty >= 8, n_nonempty
+
+
 # ---------------------------------------------------------------- traceback re-scoring
 def rescore(pattern, text, start, cigar, md):
     """Walk CIGAR over both strings; return (#edits, read bases consumed, MD rebuilt from first principles)."""
@@ -257,6 +356,35 @@ def test_traceback_cigar_has_exactly_ed_edits(e):
             assert rp - 1 > end and edits <= ed and "D" not in cigar.split("M")[-1]
         n += 1
     assert n > 250 and n_exact > 0.9 * n
+
+
+@pytest.mark.parametrize("e", [1, 3, 7])
+def test_traceback_cigar_has_exactly_ed_edits_on_long_reads(e):
+    rng = np.random.default_rng(4400 + e)
+    n = n_exact = 0
+    for trial in range(60):
+        L = (1024, 1023, 257, 301, 515, 700, 1000)[trial % 7] if trial < 21 else int(rng.integers(257, 1025))
+        ref = util.rand_seq(rng, L + 4 * e + 8)
+        read = util.mutate(rng, ref[e:e + L + e], int(rng.integers(0, e + 1)))[:L]
+        if len(read) < L:
+            continue
+        if trial % 4 == 0:
+            read = _end_edits(rng, read, trial % 8 == 0, trial % 8 == 4)
+        ed, end = fo.banded_ed32(e, ref, read)
+        if ed > e:
+            continue
+        start, cigar, md = fo.align(e, ref, read, ed, end)
+        assert start >= 0, (L, ed, end)
+        edits, used, md_model, rp = rescore(ref, read, start, cigar, md)
+        assert used == L
+        assert md == md_model
+        if rp - 1 == end:
+            assert edits == ed, (cigar, md, ed)
+            n_exact += 1
+        else:
+            assert rp - 1 > end and edits <= ed and "D" not in cigar.split("M")[-1]
+        n += 1
+    assert n > 40 and n_exact > 0.85 * n
 
 
 # ---------------------------------------------------------------- sort: klib radix with ties

@@ -236,6 +236,49 @@ def test_model_walk_equals_the_oracle_traceback(e):
     assert n > 500 and n_indel > 60 and n_diagonal > 150, (n, n_indel, n_folded, n_diagonal)
 
 
+@pytest.mark.parametrize("e", [1, 3, 5, 7])
+def test_model_walk_equals_the_oracle_traceback_on_long_reads(e):
+    # reads of 257..1024 bases (the device path's whole range), edits at the first and last bases every few trials
+    rng = np.random.default_rng(5900 + e)
+    n = n_indel = n_ends = 0
+    for trial in range(80):
+        L = (1024, 1023, 257, 301, 515, 700, 1000, 443)[trial % 8] if trial < 24 else int(rng.integers(257, 1025))
+        ref = util.rand_seq(rng, L + 4 * e + 8)
+        shift = int(rng.integers(0, 2 * e + 1))
+        read = util.mutate(rng, ref[shift:shift + L + e], int(rng.integers(0, e + 1)))[:L]
+        if len(read) < L:
+            continue
+        if trial % 3 == 0:
+            r = bytearray(read)
+            for at in ((0,), (L - 1,), (0, L - 1))[trial % 9 // 3]:
+                r[at] = util.ACGT[(util.ACGT.tolist().index(r[at]) + 1) % 4] if r[at] in b"ACGT" else 65
+            read = bytes(r)
+        if trial % 11 == 0:
+            r = bytearray(read)
+            r[int(rng.integers(0, L))] = 78
+            read = bytes(r)
+        ed, end = fo.banded_ed32(e, ref, read)
+        if ed > e:
+            continue
+        o_start, o_cigar, o_md = fo.align(e, ref, read, ed, end)
+        try:
+            m_start, m_cig, m_md = model_align(e, ref, read, ed, end)
+        except Asserted:
+            assert o_start < 0, (e, trial, L, ed, end, o_start, o_cigar)
+            continue
+        assert o_start >= 0 and (o_start, o_cigar, o_md) == (m_start, cigar_str(m_cig), m_md), (e, trial, L, ed, end)
+        cost, rp, tp = path_cost(ref, read, m_start, m_cig)
+        assert tp == L
+        if rp - 1 == end:
+            assert cost == ed
+        else:
+            assert rp - 1 > end and cost <= ed
+        n += 1
+        n_indel += any(op != "M" for op, _ in m_cig)
+        n_ends += trial % 3 == 0
+    assert n > 50 and n_indel >= 4 and n_ends >= 6, (n, n_indel, n_ends)
+
+
 def test_model_walk_equals_the_oracle_on_the_repeat_fixture_records():
     # every record of the committed repeat-rich fixture (tests/golden/repeat_rich.npz: 14 045 records, 387 of its reads
     # with indels, N runs in the reference), rebuilt from the accepted candidates by the model: the same multiset of
