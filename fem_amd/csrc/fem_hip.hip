@@ -41,7 +41,7 @@ constexpr uint32_t kMaxReadLen = 1024;
 constexpr size_t kFrontPad = 16;  // kernels fetch a reverse-strand chunk from up to 15 bytes in front of a read
 constexpr uint32_t kXcapSmall = 512, kFcap = 128, kCcap = 128;
 
-constexpr int kTimedKernels = 10;  // fem_dev_kernel_time ids: 0 seed (join), 1 verify, 2 generic seed, 3-5 tail, 6 pack_results_kernel (round 5; the count kernel of rounds 1-2 before), 7 SAM text, 8 seed selection, 9 pairing
+constexpr int kTimedKernels = 11;  // fem_dev_kernel_time ids: 0 seed (join), 1 verify, 2 generic seed, 3-5 tail, 6 pack_results_kernel (round 5; the count kernel of rounds 1-2 before), 7 SAM text, 8 seed selection, 9 pairing, 10 mate rescue
 struct TimedLaunch {
   int kernel;
   hipEvent_t start, stop;
@@ -155,6 +155,10 @@ struct Slot {
   bool paired = false;
   int32_t min_insert = 0, max_insert = 0;
   uint64_t n_proper = 0;  // of the slot's last paired SAM text
+  // mate rescue (fem_dev_set_rescue): at rescue_edits edits
+  bool rescue = false;
+  int32_t rescue_edits = 0;
+  uint64_t n_rescued = 0;  // of the slot's last paired SAM text (or fetch_pairs)
   // fem_dev_fetch_pairs: the records in output order (host copies, valid until the slot's next fetch_pairs)
   std::vector<uint16_t> pr_flag;
   std::vector<uint32_t> pr_tid, pr_pos0, pr_cigar_off, pr_cigar, pr_md_off;
@@ -1572,6 +1576,8 @@ int fem_dev_upload_reference(fem_dev *h, uint32_t n_seq, const char *const *seq,
   HIP_TRY(h, hipMalloc((void **)&h->d_seq_len, n_seq * sizeof(uint32_t)));
   for (uint32_t i = 0; i < n_seq; ++i)
     if (seq_len[i]) HIP_TRY(h, hipMemcpy(h->d_ref_raw + h->seq_off[i], seq[i], seq_len[i], hipMemcpyHostToDevice));
+  // (the slack zeroed, as the oracle pads its concatenation: a traceback whose 'S' fold walks past the last sequence reads it)
+  HIP_TRY(h, hipMemset(h->d_ref_raw + total, 0, 128));
   HIP_TRY(h, hipMemcpy(h->d_seq_off, h->seq_off.data(), n_seq * sizeof(uint64_t), hipMemcpyHostToDevice));
   HIP_TRY(h, hipMemcpy(h->d_seq_len, h->seq_len.data(), n_seq * sizeof(uint32_t), hipMemcpyHostToDevice));
   HIP_TRY(h, hipMemset(h->d_ref_raw + total, 'N', 128));
@@ -2262,6 +2268,17 @@ int fem_dev_sam_wait(fem_dev *h, int slot) {
   return s.tail->wait_text();  // (touches nothing but the slot's event: safe next to the thread that drives the handle)
 }
 
+// What mate rescue needs of the slot's batch and the reference (fetch time: the insert window's width is checked here).
+static int rescue_input(fem_dev *h, const Slot &s, femt::RescueInput *ri) {
+  if (!s.rescue) return FEM_OK;
+  if ((int64_t)s.max_insert - s.min_insert > 65536)
+    return fail(h, FEM_ERR_UNSUPPORTED, "mate rescue searches insert windows of at most 65536 (max_insert - min_insert)");
+  ri->max_edits = s.rescue_edits;
+  ri->bases = s.bases(), ri->read_off = s.d_off, ri->max_len = s.max_len;
+  ri->ref_raw = h->d_ref_raw, ri->ref_bytes = h->ref_bytes + 64, ri->seq_off = h->d_seq_off, ri->seq_len = h->d_seq_len;
+  return FEM_OK;
+}
+
 static int fetch_sam(fem_dev *h, int slot, fem_batch_sam *out, bool wait) {
   static const bool trace_host = testing_switch("FEM_FETCH_TIMES");  // host time of the call's three stretches, on stderr
   const auto t_in = std::chrono::steady_clock::now();
@@ -2290,7 +2307,11 @@ static int fetch_sam(fem_dev *h, int slot, fem_batch_sam *out, bool wait) {
   hipStream_t os = out_stream_of(h, s);
   rc = s.tail->run(in, os, h->n_cu, h->tiny_buffers, &t, &err, h->timing ? ms : nullptr, false);
   if (rc) return fail(h, rc, err);
-  if (s.paired && (rc = s.tail->pair(s.min_insert, s.max_insert, os, &err))) return fail(h, rc, err);
+  if (s.paired) {
+    femt::RescueInput ri{};
+    if ((rc = rescue_input(h, s, &ri))) return rc;
+    if ((rc = s.tail->pair(s.min_insert, s.max_insert, os, &err, s.rescue ? &ri : nullptr))) return fail(h, rc, err);
+  }
   const double ms_run = since(t_in);
   femt::SamInput names{};
   names.quals = s.host_quals ? nullptr : s.d_quals, names.names = s.d_names, names.name_off = s.d_name_off;
@@ -2301,6 +2322,7 @@ static int fetch_sam(fem_dev *h, int slot, fem_batch_sam *out, bool wait) {
   rc = s.tail->sam(in, names, os, h->n_cu, &text, &err, h->timing ? &ms_text : nullptr, wait, &h->text_gate, s.paired);
   if (rc) return fail(h, rc, err);
   s.n_proper = s.paired ? s.tail->n_proper() : 0;  // (sam() has waited for the stream once, after sizing the text)
+  s.n_rescued = s.paired ? s.tail->n_rescued() : 0;
   if (!s.ev_text_order) HIP_TRY(h, hipEventCreateWithFlags(&s.ev_text_order, hipEventDisableTiming));
   HIP_TRY(h, hipEventRecord(s.ev_text_order, os));
   s.have_text_order = true;
@@ -2310,6 +2332,7 @@ static int fetch_sam(fem_dev *h, int slot, fem_batch_sam *out, bool wait) {
     for (int i = 0; i < 3; ++i) h->t_ms[3 + i] += ms[i], h->t_n[3 + i] += 1;
     if (wait) h->t_ms[7] += ms_text, h->t_n[7] += 1;  // (without the wait no elapsed time is read: nothing to count)
     if (s.paired) h->t_ms[9] += s.tail->pair_ms(), h->t_n[9] += 1;
+    if (s.paired && s.rescue) h->t_ms[10] += s.tail->rescue_ms(), h->t_n[10] += 1;
   }
   s.qual_at = text.qual_at;
   out->text = text.text, out->len = text.len, out->n_asserted = text.n_asserted;
@@ -2344,6 +2367,31 @@ int fem_dev_pair_count(fem_dev *h, int slot, uint64_t *n_proper) {
   return FEM_OK;
 }
 
+int fem_dev_set_rescue(fem_dev *h, int slot, const fem_rescue_params *rp) {
+  int rc = check_slot(h, slot);
+  if (rc) return rc;
+  FEM_LOCK(h);
+  Slot &s = h->slot[slot];
+  if (!rp) {
+    s.rescue = false;
+    return FEM_OK;
+  }
+  if (rp->max_edits < 0 || rp->max_edits > 15) return fail(h, FEM_ERR_INVALID, "rescue edit bound out of range (0 <= max_edits <= 15)");
+  s.rescue = true, s.rescue_edits = rp->max_edits;
+  return FEM_OK;
+}
+
+int fem_dev_rescue_count(fem_dev *h, int slot, uint64_t *n_rescued) {
+  int rc = check_slot(h, slot);
+  if (rc) return rc;
+  if (!n_rescued) return fail(h, FEM_ERR_INVALID, "null output pointer");
+  FEM_LOCK(h);
+  Slot &s = h->slot[slot];
+  if (!s.paired) return fail(h, FEM_ERR_STATE, "the slot is not in pair mode (fem_dev_set_pairs)");
+  *n_rescued = s.n_rescued;
+  return FEM_OK;
+}
+
 // The records of fem_dev_fetch_records, paired on the device (pair_kernel) and put in output order here on the host: an
 // inspection path (tests, tools); FEM map takes the text (fem_dev_fetch_sam).
 int fem_dev_fetch_pairs(fem_dev *h, int slot, fem_batch_pairs *out) {
@@ -2354,11 +2402,13 @@ int fem_dev_fetch_pairs(fem_dev *h, int slot, fem_batch_pairs *out) {
   if ((rc = fem_dev_sync(h, slot))) return rc;
   Slot &s = h->slot[slot];
   if (s.n_reads & 1) return fail(h, FEM_ERR_INVALID, "a batch of read pairs holds an even number of reads");
+  femt::RescueInput ri{};
+  if ((rc = rescue_input(h, s, &ri))) return rc;
   fem_batch_records rec{};
   if ((rc = fem_dev_fetch_records(h, slot, &rec))) return rc;
   std::string err;
   femt::PairOutput po{};
-  if ((rc = s.tail->pair(s.min_insert, s.max_insert, s.stream, &err))) return fail(h, rc, err);
+  if ((rc = s.tail->pair(s.min_insert, s.max_insert, s.stream, &err, s.rescue ? &ri : nullptr))) return fail(h, rc, err);
   if ((rc = s.tail->pair_fetch(s.stream, &po, &err))) return fail(h, rc, err);
   const uint64_t nr = po.n_records;
   s.pr_flag.assign(po.flag, po.flag + nr);
@@ -2367,12 +2417,19 @@ int fem_dev_fetch_pairs(fem_dev *h, int slot, fem_batch_pairs *out) {
   s.pr_cigar_off[0] = 0, s.pr_md_off[0] = 0;
   for (uint64_t k = 0; k < nr; ++k) {
     const uint32_t r = po.perm[k];
-    s.pr_tid[k] = rec.tid[r], s.pr_pos0[k] = rec.pos0[r], s.pr_nm[k] = rec.nm[r];
-    s.pr_cigar.insert(s.pr_cigar.end(), rec.cigar + rec.cigar_off[r], rec.cigar + rec.cigar_off[r + 1]);
-    s.pr_md.insert(s.pr_md.end(), rec.md + rec.md_off[r], rec.md + rec.md_off[r + 1]);
+    if (r < po.first_rescued) {
+      s.pr_tid[k] = rec.tid[r], s.pr_pos0[k] = rec.pos0[r], s.pr_nm[k] = rec.nm[r];
+      s.pr_cigar.insert(s.pr_cigar.end(), rec.cigar + rec.cigar_off[r], rec.cigar + rec.cigar_off[r + 1]);
+      s.pr_md.insert(s.pr_md.end(), rec.md + rec.md_off[r], rec.md + rec.md_off[r + 1]);
+    } else {  // a rescued mate's record
+      const uint32_t q = r - po.first_rescued, c0 = po.r_cigar_off[0], m0 = po.r_md_off[0];
+      s.pr_tid[k] = po.r_tid[q], s.pr_pos0[k] = po.r_pos0[q], s.pr_nm[k] = po.r_nm[q];
+      s.pr_cigar.insert(s.pr_cigar.end(), po.r_cigar + (po.r_cigar_off[q] - c0), po.r_cigar + (po.r_cigar_off[q + 1] - c0));
+      s.pr_md.insert(s.pr_md.end(), po.r_md + (po.r_md_off[q] - m0), po.r_md + (po.r_md_off[q + 1] - m0));
+    }
     s.pr_cigar_off[k + 1] = (uint32_t)s.pr_cigar.size(), s.pr_md_off[k + 1] = (uint32_t)s.pr_md.size();
   }
-  s.n_proper = po.n_proper;
+  s.n_proper = po.n_proper, s.n_rescued = po.n_rescued;
   out->n_pairs = po.n_pairs, out->n_records = nr;
   out->rec_begin = po.pair_begin, out->flag = s.pr_flag.data(), out->tid = s.pr_tid.data(), out->pos0 = s.pr_pos0.data();
   out->nm = s.pr_nm.data(), out->cigar_off = s.pr_cigar_off.data(), out->cigar = s.pr_cigar.data();

@@ -5,7 +5,8 @@
 // New, optional: `--gpus N` (map) spreads read batches over N GPUs of this node (whichever GPU has a free slot takes the
 // next batch; record order in the SAM file follows completion, parity is modulo record order); `--batch N` sets reads
 // per batch.  `--read2 STR` maps read pairs (record i of --read1 and of --read2 are the two mates of pair i), with -I / -X the
-// accepted insert size: the pairing and the paired SAM text on the device (fem_dev_set_pairs).
+// accepted insert size: the pairing and the paired SAM text on the device (fem_dev_set_pairs); `--rescue INT` adds mate rescue
+// at INT edits (fem_dev_set_rescue).
 #include <errno.h>
 #include <fcntl.h>
 #include <getopt.h>
@@ -72,6 +73,7 @@ void usage_map() {
   fprintf(stderr, "        --read2  STR  Input read2 file: map read pairs (record i of both files is pair i)\n");
   fprintf(stderr, "        -I, --minins INT  minimum insert size of a proper pair [0]\n");
   fprintf(stderr, "        -X, --maxins INT  maximum insert size of a proper pair [500]\n");
+  fprintf(stderr, "        --rescue INT  with --read2: search a mate without records in its mate's insert window at INT (0-15) edits\n");
   fprintf(stderr, "        -o       STR  Output SAM file \n\n");
 }
 
@@ -245,6 +247,7 @@ struct BatchBuf {  // everything about the batch that sits in one (GPU, slot) pa
   uint64_t want_reads = 0, want_bases = 0;  // set by the reader when the staging buffers are too small
   fem_batch_records rec{};                  // device tail's records (default path)
   uint64_t n_proper = 0;                    // paired: proper pairs of the batch
+  uint64_t n_rescued = 0;                   // --rescue: rescued mates of the batch
   fem_batch_result res{};                   // per-candidate outcome (FEM_HOST_TAIL=1)
   double t_submit = 0;
   double t_slot = 0, t_filled = 0, t_submitted = 0, t_retired = 0, t_text = 0;  // FEM_STAGE_TIMES=2: the batch's way through the stages
@@ -270,6 +273,8 @@ int map_main(int argc, char **argv) {
   mallopt(M_TRIM_THRESHOLD, -1);
   char *ref_path = nullptr, *index_path = nullptr, *read_path = nullptr, *read2_path = nullptr, *out_path = nullptr;
   long long min_insert = 0, max_insert = 500;
+  long long rescue_edits = 0;  // --rescue (mate rescue at this many edits, fem_dev_set_rescue)
+  bool rescue_given = false;
   fem_params params{12, 3, 2, 1};  // src/FEM_map.c:67-70: k and step are fixed, whatever the index header says
   int n_threads = 1, n_gpus = 1;
   // reads per batch: 250 k fills the pipeline soonest on small inputs; a batch costs three host round trips on its way through
@@ -282,7 +287,8 @@ int map_main(int argc, char **argv) {
                                      {"index", required_argument, nullptr, 'i'}, {"read1", required_argument, nullptr, 'b'},
                                      {"gpus", required_argument, nullptr, 'G'},  {"batch", required_argument, nullptr, 'B'},
                                      {"read2", required_argument, nullptr, 'c'}, {"minins", required_argument, nullptr, 'I'},
-                                     {"maxins", required_argument, nullptr, 'X'}, {nullptr, 0, nullptr, 0}};
+                                     {"maxins", required_argument, nullptr, 'X'}, {"rescue", required_argument, nullptr, 'R'},
+                                     {nullptr, 0, nullptr, 0}};
   int c, oi = 0;
   while ((c = getopt_long(argc, argv, short_opt, long_opt, &oi)) >= 0) {
     switch (c) {
@@ -292,6 +298,13 @@ int map_main(int argc, char **argv) {
       case 'c': read2_path = optarg; break;
       case 'I': min_insert = strtoll(optarg, nullptr, 10); break;
       case 'X': max_insert = strtoll(optarg, nullptr, 10); break;
+      case 'R': {
+        char *end = nullptr;
+        rescue_edits = strtoll(optarg, &end, 10);
+        if (!end || end == optarg || *end) rescue_edits = -1;  // (not a number: refused below)
+        rescue_given = true;
+        break;
+      }
       case 'e': params.e = atoi(optarg); break;
       case 't': n_threads = atoi(optarg); break;
       case 'a': params.a = atoi(optarg); break;
@@ -316,6 +329,9 @@ int map_main(int argc, char **argv) {
   else if (n_threads <= 0) bad = "Wrong number of threads.";
   else if (params.a < 0 || params.a > 2) bad = "Wrong number of additional q-grams.";
   else if (min_insert < 0 || max_insert < min_insert || max_insert > (1ll << 30)) bad = "Wrong insert size range.";
+  else if (rescue_given && !read2_path) bad = "--rescue needs read pairs (--read2).";
+  else if (rescue_given && (rescue_edits < 0 || rescue_edits > 15)) bad = "Wrong rescue error threshold (0-15).";
+  else if (rescue_given && max_insert - min_insert > 65536) bad = "--rescue searches insert size ranges of at most 65536.";
   else if (!ref_path) bad = "Reference file path is required.";
   else if (!index_path) bad = "Index file path is required.";
   else if (!read_path) bad = "Read file path is required.";
@@ -435,6 +451,10 @@ int map_main(int argc, char **argv) {
           if (!rc && paired) {
             const fem_pair_params pp{(int32_t)min_insert, (int32_t)max_insert};
             rc = fem_dev_set_pairs(devs[(size_t)g], sl, &pp);
+            if (!rc && rescue_given) {
+              const fem_rescue_params rp{(int32_t)rescue_edits};
+              rc = fem_dev_set_rescue(devs[(size_t)g], sl, &rp);
+            }
           }
         }
         up_rc[(size_t)g] = rc;
@@ -522,7 +542,8 @@ int map_main(int argc, char **argv) {
   Channel<WriteItem> write_q;
   std::vector<TextOut> texts(3);
   for (TextOut &t : texts) text_free_q.push(&t);
-  std::vector<uint64_t> per_gpu((size_t)n_gpus * 5, 0), per_gpu_proper((size_t)n_gpus, 0);
+  std::vector<uint64_t> per_gpu((size_t)n_gpus * 5, 0), per_gpu_proper((size_t)n_gpus, 0),
+      per_gpu_rescued((size_t)n_gpus, 0);
 
   // ---- writer (src/output_queue.c:60-91) ----
   std::thread writer([&] {
@@ -668,6 +689,7 @@ int map_main(int argc, char **argv) {
                  : device_text ? fem_dev_fetch_sam_nowait(h, b->slot, &b->sam)  // (the writer waits for the text itself)
                                : fem_dev_fetch_records(h, b->slot, &b->rec);
         if (!rc && paired) rc = fem_dev_pair_count(h, b->slot, &b->n_proper);
+        if (!rc && rescue_given) rc = fem_dev_rescue_count(h, b->slot, &b->n_rescued);
         const double waited = real_time() - t0;
         b->t_retired = t0 + waited;
         double placing = 0;
@@ -703,7 +725,7 @@ int map_main(int argc, char **argv) {
           }
           const uint64_t *st = host_tail ? b->res.stats : device_text ? b->sam.stats : b->rec.stats;
           for (int i = 0; i < 5; ++i) per_gpu[(size_t)g * 5 + (size_t)i] += st[i];
-          if (paired) per_gpu_proper[(size_t)g] += b->n_proper;
+          if (paired) per_gpu_proper[(size_t)g] += b->n_proper, per_gpu_rescued[(size_t)g] += b->n_rescued;
           if (device_text) {
             n_asserted += b->sam.n_asserted;
             write_q.push(WriteItem{nullptr, b});
@@ -1028,6 +1050,11 @@ int map_main(int argc, char **argv) {
     uint64_t n_proper = 0;
     for (uint64_t x : per_gpu_proper) n_proper += x;
     fprintf(stderr, "The number of proper pairs: %lu\n", (unsigned long)n_proper);
+    if (rescue_given) {
+      uint64_t n_rescued = 0;
+      for (uint64_t x : per_gpu_rescued) n_rescued += x;
+      fprintf(stderr, "The number of rescued mates: %lu\n", (unsigned long)n_rescued);
+    }
   }
   fprintf(stderr, "Time: %fs\n", t_mapping);
   return 0;

@@ -1073,6 +1073,14 @@ struct PairPlus {  // component-wise sum of (run count, MD length) pairs
   }
 };
 
+struct TriplePlus {  // component-wise sum of (kept, runs, MD length) triples (mate rescue)
+  __host__ __device__ rocprim::tuple<uint32_t, uint32_t, uint32_t> operator()(const rocprim::tuple<uint32_t, uint32_t, uint32_t> &a,
+                                                                             const rocprim::tuple<uint32_t, uint32_t, uint32_t> &b) const {
+    return rocprim::make_tuple(rocprim::get<0>(a) + rocprim::get<0>(b), rocprim::get<1>(a) + rocprim::get<1>(b),
+                               rocprim::get<2>(a) + rocprim::get<2>(b));
+  }
+};
+
 // ---- host-side buffer helpers ----
 struct DevBuf {
   void *p = nullptr;
@@ -1092,6 +1100,23 @@ struct DevBuf {
   }
   template <typename T>
   T *as() const { return (T *)p; }
+  // need() that keeps the first `used` bytes (waits for `stream` when it has to move them)
+  hipError_t grow(size_t bytes, size_t used, hipStream_t stream) {
+    if (bytes <= cap && p) return hipSuccess;
+    const size_t want = std::max<size_t>(bytes + bytes / 4, 256);
+    void *q = nullptr;
+    hipError_t e = hipMalloc(&q, want);
+    if (e != hipSuccess) return e;
+    if (p && used) e = hipMemcpyAsync(q, p, used, hipMemcpyDeviceToDevice, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) {
+      (void)hipFree(q);
+      return e;
+    }
+    if (p) (void)hipFree(p);
+    p = q, cap = want;
+    return hipSuccess;
+  }
 };
 struct PinBuf {
   void *p = nullptr;
@@ -1417,6 +1442,10 @@ struct PairParams {
   int32_t *tlen;
   uint32_t *pair_begin;       // 2 n_pairs + 1
   uint32_t *n_proper;
+  // mate rescue (nullptr: off): exclusive scan of the kept rescued records over the pairs (n_pairs + 1); pair i's one, if it
+  // has one, is record resc_first + resc_before[i] and becomes the only record of its mate that had none
+  const uint32_t *resc_before;
+  uint32_t resc_first;
 };
 
 struct MateRec {
@@ -1484,6 +1513,14 @@ __global__ void __launch_bounds__(256) pair_kernel(PairParams p) {
     a0 = p.rec_begin[i], na = p.rec_begin[i + 1] - a0;
     b0 = p.rec_begin[p.n_pairs + i], nb = p.rec_begin[p.n_pairs + i + 1] - b0;
     ob = a0 + b0 - mid;  // the lines of the pairs in front: their mate 1 records and their mate 2 records
+    if (p.resc_before) {  // ... and their rescued mates
+      const uint32_t before = p.resc_before[i], kept = p.resc_before[i + 1] - before;
+      ob += before;
+      if (kept) {
+        if (na == 0) a0 = p.resc_first + before, na = 1;
+        else b0 = p.resc_first + before, nb = 1;
+      }
+    }
     p.pair_begin[2u * i] = ob, p.pair_begin[2u * i + 1u] = ob + na;
     if (i + 1u == p.n_pairs) p.pair_begin[2u * i + 2u] = ob + na + nb;
   }
@@ -1547,6 +1584,295 @@ __global__ void __launch_bounds__(256) pair_kernel(PairParams p) {
   if (ln == 0 && proper_lanes) atomicAdd(p.n_proper, (uint32_t)__builtin_popcountll(proper_lanes));
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Mate rescue (include/fem_hip.h).  A pair where exactly one mate (B) has no record: its other mate's first
+// kRescueAnchors records without 0x8000 are the anchors, and B's pos0 is searched in each anchor's insert window at E edits:
+// tiles c = lo + j (2E + 1), each the banded Myers of fo_banded_ed32 over ref[c, c + L + 2E) (first strict minimum, the same
+// 32-bit word and character codes); the least (nm(anchor) + ed, anchor, pos0) is traced (trace_record at E) and kept if it is
+// concordant with its anchor.  Four kernels, then an exclusive scan of the kept records, then pair_kernel:
+//   rescue_jobs_kernel   lane per pair: candidates and one job per (candidate, anchor)
+//   rescue_search_kernel wave per job, lane per tile: the mate's codes staged in LDS once per wave, a 64-bit atomicMin per job
+//   rescue_trace_kernel  lane per candidate: the traceback, the concordance check
+//   rescue_append_kernel lane per candidate: the kept records behind run()'s (record arrays, CIGAR / MD, s_read)
+// ---------------------------------------------------------------------------------------------------------
+constexpr uint32_t kRescueAnchors = 8;
+constexpr uint32_t kResWaves = 4;  // waves per block of the search kernel
+constexpr uint32_t kRescRec = 5;   // words per candidate in RescueParams::c_rec
+
+struct RescueParams {
+  uint32_t n_pairs, n_records;  // run()'s records; the rescued ones are numbered from n_records on
+  int32_t E;
+  int64_t min_insert, max_insert;
+  const uint32_t *rec_begin;  // 2 n_pairs + 1
+  uint16_t *flag;
+  uint32_t *tid, *pos0;
+  uint8_t *nm;
+  uint32_t *cigar_off, *cigar, *md_off, *s_read;
+  uint8_t *md;
+  const uint8_t *bases;
+  const uint64_t *read_off;
+  const uint8_t *ref_raw;
+  uint64_t ref_bytes;
+  const uint64_t *seq_off;
+  const uint32_t *seq_len;
+  uint32_t *ctl;                 // [0] candidates, [1] jobs, [2] overflow queue length, [3] overflow staging too small (never)
+  uint32_t *cand_pair;           // per candidate: its pair
+  uint32_t *jobs;                // candidate << 3 | anchor index
+  unsigned long long *best;      // per candidate: (nm(a) + ed) << 35 | a << 32 | pos0, ~0 = no hit
+  uint32_t lanes, text_words, pat_words, max_len;  // LDS plan of the trace kernel
+  uint32_t ops_cap, md_cap;
+  uint32_t *t_ops;               // first pass, per candidate: ops_cap runs, md_cap MD characters
+  uint8_t *t_md;
+  uint32_t o_ops_cap, o_md_cap;  // overflow pass, per queued candidate: room for the longest walk (trace_kernel's staging)
+  uint32_t *o_ops;
+  uint8_t *o_md;
+  uint32_t *ovf_queue;           // candidates whose CIGAR or MD outgrew the first pass's staging
+  uint32_t overflow_pass;        // rescue_trace_kernel: 0 = every candidate, 1 = the queued ones
+  uint32_t *c_rec;               // per candidate (kRescRec words): tid, pos0, flag | nm << 16, n_ops | n_md << 16, staging
+  uint32_t *kept, *k_ops, *k_md; // per pair (n_pairs + 1): the kept record's 1, runs, MD characters (0 0 0 otherwise)
+  const uint32_t *s_kept, *s_ops, *s_md;  // their exclusive scans
+  uint32_t cig_total, md_total;  // run()'s CIGAR runs and MD characters
+};
+
+// pair i's candidate view: the anchors' mate (A) and the mate without records (B)
+struct RescuePair {
+  uint32_t a0, na, b_read;
+};
+__device__ __forceinline__ RescuePair rescue_pair(const RescueParams &p, uint32_t i) {
+  const uint32_t a0 = p.rec_begin[i], na = p.rec_begin[i + 1] - a0;
+  const uint32_t b0 = p.rec_begin[p.n_pairs + i], nb = p.rec_begin[p.n_pairs + i + 1] - b0;
+  RescuePair r;
+  if (na) r.a0 = a0, r.na = na, r.b_read = p.n_pairs + i;
+  else r.a0 = b0, r.na = nb, r.b_read = i;
+  return r;
+}
+
+// an anchor's window of B's pos0 ([lo, hi], empty when lo > hi) and the strand B is searched on
+struct RescueWindow {
+  int64_t lo, hi;
+  uint32_t tid, rc;  // rc: B reverse-complemented (the anchor is forward)
+};
+__device__ __forceinline__ RescueWindow rescue_window(const RescueParams &p, const MateRec &an, int64_t L) {
+  RescueWindow w;
+  w.tid = an.tid;
+  const int64_t pa = an.pos0, ea = (int64_t)an.end0;
+  if (!(an.flag & 16u)) {
+    w.rc = 1u, w.lo = pa + p.min_insert - L > pa ? pa + p.min_insert - L : pa, w.hi = pa + p.max_insert - L;
+  } else {
+    w.rc = 0u, w.lo = ea - p.max_insert > 0 ? ea - p.max_insert : 0, w.hi = ea - p.min_insert < pa ? ea - p.min_insert : pa;
+  }
+  return w;
+}
+
+__device__ __forceinline__ MateRec rescue_rec(const RescueParams &p, uint32_t r) {
+  PairParams q{};
+  q.tid = p.tid, q.pos0 = p.pos0, q.flag = p.flag, q.nm = p.nm, q.cigar_off = p.cigar_off, q.cigar = p.cigar;
+  return mate_rec(q, r);
+}
+
+// character j of B as searched: the read itself, or fo_revcomp's reverse complement (ACGT complemented in upper case, anything else N)
+__device__ __forceinline__ uint32_t rescue_char(const uint8_t *fwd, int64_t L, int64_t j, uint32_t rc) {
+  if (!rc) return fwd[j];
+  const uint32_t c = base_code(fwd[L - 1 - j]);
+  return c < 4u ? (uint32_t)"TGCA"[c] : (uint32_t)'N';
+}
+
+__global__ void __launch_bounds__(256) rescue_jobs_kernel(RescueParams p) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= p.n_pairs) return;
+  const uint32_t na = p.rec_begin[i + 1] - p.rec_begin[i], nb = p.rec_begin[p.n_pairs + i + 1] - p.rec_begin[p.n_pairs + i];
+  if ((na == 0) == (nb == 0)) return;
+  const RescuePair rp = rescue_pair(p, i);
+  const uint32_t n_look = rp.na < kRescueAnchors ? rp.na : kRescueAnchors;
+  uint32_t anchors = 0;  // bit a: record a of A is an anchor
+  for (uint32_t a = 0; a < n_look; ++a)
+    if (!(p.flag[rp.a0 + a] & kFlagBroken)) anchors |= 1u << a;
+  if (!anchors) return;
+  const uint32_t k = atomicAdd(&p.ctl[0], 1u);
+  p.cand_pair[k] = i, p.best[k] = ~0ull;
+  uint32_t j = atomicAdd(&p.ctl[1], (uint32_t)__builtin_popcount(anchors));
+  for (; anchors; anchors &= anchors - 1u) p.jobs[j++] = k << 3 | (uint32_t)__builtin_ctz(anchors);
+}
+
+// fo_banded_ed32 (E, pat[0 .. L + 2E), text codes tc[0 .. L)): the same operations on the same 32-bit words, the read's code
+// mask built from three bit planes of the window (Peq[code] of the reference = the band's bits whose three code bits all agree)
+__device__ __forceinline__ int rescue_myers(const uint8_t *pat, const uint8_t *tc, int L, int E, int *end_out) {
+  uint32_t B0 = 0, B1 = 0, B2 = 0;
+  for (int j = 0; j < 2 * E; ++j) {
+    const uint32_t pc = base_code(pat[j]);
+    B0 |= (pc & 1u) << j, B1 |= ((pc >> 1) & 1u) << j, B2 |= ((pc >> 2) & 1u) << j;
+  }
+  const int sh = 2 * E;
+  const uint32_t band = (2u << sh) - 1u;
+  uint32_t vp = 0, vn = 0;
+  int score = 0;
+  for (int i0 = 0; i0 < L; i0 += 16) {
+    const uint4 w = load_u128_unaligned(pat + sh + i0);  // (up to 15 bytes past the window: inside the reference's slack)
+    const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const int i = i0 + u;
+      if (i >= L) break;
+      const uint32_t pc = base_code((ws[u >> 2] >> (8 * (u & 3))) & 0xFFu), t = tc[i];
+      B0 |= (pc & 1u) << sh, B1 |= ((pc >> 1) & 1u) << sh, B2 |= ((pc >> 2) & 1u) << sh;
+      const uint32_t m0 = 0u - (t & 1u), m1 = 0u - ((t >> 1) & 1u), m2 = 0u - ((t >> 2) & 1u);
+      uint32_t x = (~((B0 ^ m0) | (B1 ^ m1) | (B2 ^ m2)) & band) | vn;
+      const uint32_t d0 = ((vp + (x & vp)) ^ vp) | x;
+      const uint32_t hn = vp & d0;
+      const uint32_t hp = vn | ~(vp | d0);
+      x = d0 >> 1;
+      vn = x & hp;
+      vp = hn | ~(x | hp);
+      score += 1 - (int)(d0 & 1u);
+      if (score > 3 * E) return E + 1;
+      B0 >>= 1, B1 >>= 1, B2 >>= 1;
+    }
+  }
+  int best = score, end = L - 1;
+  for (int j = 0; j < 2 * E; ++j) {
+    score += (int)((vp >> j) & 1u) - (int)((vn >> j) & 1u);
+    if (score < best) best = score, end = L + j;  // first strict minimum
+  }
+  *end_out = end;
+  return best;
+}
+
+__global__ void __launch_bounds__(256) rescue_search_kernel(RescueParams p) {
+  __shared__ uint8_t codes[kResWaves][1024];  // the mate's character codes (reads are <= 1024 bases on the device)
+  const uint32_t ln = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  uint8_t *tc = codes[wv];
+  const uint32_t n_jobs = p.ctl[1];
+  const int E = p.E;
+  const int64_t W = 2 * E + 1;
+  for (uint32_t job = blockIdx.x * kResWaves + wv; job < n_jobs; job += gridDim.x * kResWaves) {
+    const uint32_t k = p.jobs[job] >> 3, a = p.jobs[job] & 7u;
+    const RescuePair rp = rescue_pair(p, p.cand_pair[k]);
+    const MateRec an = rescue_rec(p, rp.a0 + a);
+    const uint64_t off = p.read_off[rp.b_read];
+    const int64_t L = (int64_t)(p.read_off[rp.b_read + 1] - off);
+    const RescueWindow w = rescue_window(p, an, L);
+    if (w.lo > w.hi || L == 0) continue;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // (the previous job's reads of tc are done)
+    __builtin_amdgcn_wave_barrier();
+    for (int64_t j = ln; j < L; j += 64) tc[j] = (uint8_t)base_code(rescue_char(p.bases + off, L, j, w.rc));
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const int64_t slen = p.seq_len[w.tid];
+    const uint8_t *seq = p.ref_raw + p.seq_off[w.tid];
+    const int64_t n_tiles = (w.hi - w.lo) / W + 1;
+    unsigned long long key = ~0ull;
+    for (int64_t t = ln; t < n_tiles; t += 64) {
+      const int64_t c = w.lo + t * W;
+      if (c + L + 2 * E > slen) continue;
+      int end = 0;
+      const int ed = rescue_myers(seq + c, tc, (int)L, E, &end);
+      const int64_t pos = c + end - L + 1;
+      if (ed <= E && pos <= w.hi) {
+        const unsigned long long h = (unsigned long long)ed << 32 | (uint64_t)pos;
+        key = h < key ? h : key;
+      }
+    }
+    for (int d = 32; d > 0; d >>= 1) {
+      const unsigned long long o = (unsigned long long)__shfl_xor(key, d);
+      key = o < key ? o : key;
+    }
+    if (ln == 0 && key != ~0ull)
+      atomicMin(&p.best[k], (unsigned long long)(an.nm + (uint32_t)(key >> 32)) << 35 | (unsigned long long)a << 32 | (uint32_t)key);
+  }
+}
+
+// One lane per candidate, the general traceback's LDS layout (trace_kernel) sized for E.  The first pass stages a record's
+// CIGAR and MD in room for a walk of E errors on canonical characters; one that outgrows it (lower-case or IUPAC characters on
+// either side: the walk and MD compare characters, so every column can be an MD character) is queued and traced again by the
+// overflow pass, whose staging holds the longest walk (as trace_kernel's).
+__global__ void __launch_bounds__(64) rescue_trace_kernel(RescueParams p) {
+  extern __shared__ uint32_t lds[];
+  const uint32_t nl = p.lanes, ln = threadIdx.x;
+  uint32_t *text_w = lds;
+  uint32_t *pat_w = text_w + p.text_words * nl;
+  uint32_t *d0_w = pat_w + p.pat_words * nl;
+  uint32_t *hp_w = d0_w + p.max_len * nl;
+  const bool ovf = p.overflow_pass != 0;
+  const uint32_t n_items = ovf ? p.ctl[2] : p.ctl[0];
+  const int E = p.E;
+  for (uint32_t base = blockIdx.x * nl; base < n_items; base += gridDim.x * nl) {
+    const uint32_t item = base + ln;
+    if (ln >= nl || item >= n_items) continue;
+    const uint32_t k = ovf ? p.ovf_queue[item] : item;
+    const unsigned long long best = p.best[k];
+    if (best == ~0ull) continue;
+    const uint32_t i = p.cand_pair[k], a = (uint32_t)(best >> 32) & 7u, pos = (uint32_t)best;
+    const RescuePair rp = rescue_pair(p, i);
+    const MateRec an = rescue_rec(p, rp.a0 + a);
+    const int ed = (int)(best >> 35) - (int)an.nm;
+    const uint64_t off = p.read_off[rp.b_read];
+    const int L = (int)(p.read_off[rp.b_read + 1] - off);
+    const RescueWindow w = rescue_window(p, an, L);
+    const int64_t W = 2 * E + 1;
+    const int64_t c = w.lo + ((int64_t)pos - w.lo) / W * W;  // the tile the hit came from (tiles are disjoint in pos0)
+    const int end = (int)((int64_t)pos - c) + L - 1;
+    for (int j = 0; j < L; j += 4) {
+      uint32_t word = 0;
+      for (int u = 0; u < 4 && j + u < L; ++u) word |= rescue_char(p.bases + off, L, j + u, w.rc) << (8 * u);
+      text_w[(uint32_t)(j / 4) * nl + ln] = word;
+    }
+    const uint64_t pat_abs = p.seq_off[w.tid] + (uint64_t)c;
+    const uint8_t *pattern = p.ref_raw + pat_abs;
+    for (int j = 0; j < L + 2 * E; j += 16) {  // (inside the sequence, and the reference buffer has 64 bytes of slack behind it)
+      const uint4 q = load_u128_unaligned(pattern + j);
+      const uint32_t ws[4] = {q.x, q.y, q.z, q.w};
+      for (int u = 0; u < 4; ++u)
+        if ((uint32_t)(j / 4 + u) < p.pat_words) pat_w[(uint32_t)(j / 4 + u) * nl + ln] = ws[u];
+    }
+    LaneView v{text_w, pat_w, d0_w, hp_w, nl, ln};
+    Staging st;
+    if (ovf) st.ops = p.o_ops + (size_t)item * p.o_ops_cap, st.md = p.o_md + (size_t)item * p.o_md_cap, st.ops_cap = p.o_ops_cap, st.md_cap = p.o_md_cap;
+    else st.ops = p.t_ops + (size_t)k * p.ops_cap, st.md = p.t_md + (size_t)k * p.md_cap, st.ops_cap = p.ops_cap, st.md_cap = p.md_cap;
+    const int start = trace_record(v, pattern, -(int64_t)pat_abs, (int64_t)p.ref_bytes - 1 - (int64_t)pat_abs, L, E, ed, end, st);
+    if (st.overflow) {
+      if (ovf) atomicAdd(&p.ctl[3], 1u);  // cannot happen: this staging holds the longest possible walk
+      else p.ovf_queue[atomicAdd(&p.ctl[2], 1u)] = k;
+      continue;
+    }
+    if (start < 0) continue;
+    MateRec rs;
+    rs.tid = w.tid, rs.pos0 = (uint32_t)(c + start), rs.flag = w.rc ? 16u : 0u, rs.nm = (uint32_t)ed;
+    uint64_t span = 0;
+    for (uint32_t u = 0; u < st.n_ops; ++u)
+      if ((st.ops[u] & 0xFu) == kOpM || (st.ops[u] & 0xFu) == kOpD) span += st.ops[u] >> 4;
+    rs.end0 = (uint64_t)rs.pos0 + span;
+    PairParams q{};
+    q.min_insert = p.min_insert, q.max_insert = p.max_insert;
+    if (concordant(q, an, rs) < 0) continue;
+    uint32_t *cr = p.c_rec + (size_t)k * kRescRec;
+    cr[0] = rs.tid, cr[1] = rs.pos0, cr[2] = rs.flag | rs.nm << 16, cr[3] = st.n_ops | st.n_md << 16, cr[4] = ovf ? item + 1u : 0u;
+    p.kept[i] = 1u, p.k_ops[i] = st.n_ops, p.k_md[i] = st.n_md;
+  }
+}
+
+__global__ void __launch_bounds__(256) rescue_append_kernel(RescueParams p) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k == 0) {  // the offsets' end behind the last rescued record
+    const uint32_t n_kept = p.s_kept[p.n_pairs];
+    p.cigar_off[p.n_records + n_kept] = p.cig_total + p.s_ops[p.n_pairs];
+    p.md_off[p.n_records + n_kept] = p.md_total + p.s_md[p.n_pairs];
+  }
+  if (k >= p.ctl[0]) return;
+  const uint32_t i = p.cand_pair[k];
+  if (!p.kept[i]) return;
+  const uint32_t rec = p.n_records + p.s_kept[i];
+  const uint32_t *cr = p.c_rec + (size_t)k * kRescRec;
+  p.tid[rec] = cr[0], p.pos0[rec] = cr[1], p.flag[rec] = (uint16_t)(cr[2] & 0xFFFFu), p.nm[rec] = (uint8_t)(cr[2] >> 16);
+  p.s_read[rec] = rescue_pair(p, i).b_read;
+  const uint32_t co = p.cig_total + p.s_ops[i], mo = p.md_total + p.s_md[i];
+  p.cigar_off[rec] = co, p.md_off[rec] = mo;
+  const uint32_t *ops = cr[4] ? p.o_ops + (size_t)(cr[4] - 1u) * p.o_ops_cap : p.t_ops + (size_t)k * p.ops_cap;
+  const uint8_t *md = cr[4] ? p.o_md + (size_t)(cr[4] - 1u) * p.o_md_cap : p.t_md + (size_t)k * p.md_cap;
+  for (uint32_t u = 0; u < (cr[3] & 0xFFFFu); ++u) p.cigar[co + u] = ops[u];
+  for (uint32_t u = 0; u < (cr[3] >> 16); ++u) p.md[mo + u] = md[u];
+}
+
 }  // namespace
 
 struct Tail::Impl {
@@ -1557,15 +1883,26 @@ struct Tail::Impl {
   // pair mode (pair()): per line, the pairs' line ranges, the proper-pair counter; their host copies (pair_fetch())
   DevBuf perm, pflag, mtid, mpos0, tlen, pair_begin, pair_ctl;
   PinBuf h_perm, h_pflag, h_mtid, h_mpos0, h_tlen, h_pair_begin, h_pair_ctl;
+  // mate rescue (pair() with a RescueInput): candidates, jobs, best hits, the tracebacks' staging, the kept flags and their scans
+  DevBuf r_ctl, r_cand, r_jobs, r_best, r_ops, r_md, r_rec, r_ovf, r_o_ops, r_o_md, r_kept, r_scan, r_scan_tmp;
+  PinBuf h_r_ctl, h_r_flag, h_r_tid, h_r_pos0, h_r_nm, h_r_cigar_off, h_r_cigar, h_r_md_off, h_r_md;
   uint32_t last_n = 0, last_nr = 0;  // what the last run() left on the device
   bool paired = false;               // pair() has run on it
+  uint32_t n_resc = 0;               // rescued records the last pair() appended behind run()'s (records last_nr ..)
+  bool resc_timed = false;           // ... and its rescue kernels ran between ev_resc[0] and ev_resc[1]
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   hipEvent_t ev_pair[2] = {nullptr, nullptr};
+  hipEvent_t ev_resc[2] = {nullptr, nullptr};
   hipEvent_t ev_text = nullptr;  // the SAM text has arrived in h_text
   ~Impl() {
     if (ev_text) (void)hipEventDestroy(ev_text);
     for (hipEvent_t e : ev_pair)
       if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ev_resc)
+      if (e) (void)hipEventDestroy(e);
+    for (DevBuf *b : {&r_ctl, &r_cand, &r_jobs, &r_best, &r_ops, &r_md, &r_rec, &r_ovf, &r_o_ops, &r_o_md, &r_kept, &r_scan, &r_scan_tmp})
+      b->release();
+    for (PinBuf *b : {&h_r_ctl, &h_r_flag, &h_r_tid, &h_r_pos0, &h_r_nm, &h_r_cigar_off, &h_r_cigar, &h_r_md_off, &h_r_md}) b->release();
     for (DevBuf *b : {&perm, &pflag, &mtid, &mpos0, &tlen, &pair_begin, &pair_ctl}) b->release();
     for (PinBuf *b : {&h_perm, &h_pflag, &h_mtid, &h_mpos0, &h_tlen, &h_pair_begin, &h_pair_ctl}) b->release();
     for (DevBuf *b : {&rec_begin, &queue, &ctl, &u_cand, &u_misc, &s_cand, &s_misc, &s_read, &t_ops, &t_md, &o_ops, &o_md, &ovf, &rec_list,
@@ -1658,7 +1995,8 @@ int Tail::warm(hipStream_t stream, std::string *err) {
                            (const void *)trace_fast_kernel<uint32_t, uint8_t>, (const void *)trace_fast_kernel<uint32_t, uint16_t>,
                            (const void *)trace_kernel, (const void *)compact_kernel, (const void *)sam_len_kernel<false>,
                            (const void *)sam_write_kernel<false>, (const void *)sam_len_kernel<true>,
-                           (const void *)sam_write_kernel<true>, (const void *)pair_kernel};
+                           (const void *)sam_write_kernel<true>, (const void *)pair_kernel, (const void *)rescue_jobs_kernel,
+                           (const void *)rescue_search_kernel, (const void *)rescue_trace_kernel, (const void *)rescue_append_kernel};
   for (const void *k : kernels) TAIL_TRY(hipFuncGetAttributes(&a, k));
   if (!m.scan_tmp.p || !m.rec_begin.p || !m.n_ops.p || !m.line_len.p) return FEM_OK;  // (nothing reserved: the scans load with the first batch)
   size_t tmp = m.scan_tmp.cap;
@@ -1822,7 +2160,7 @@ int Tail::run(const TailInput &in, hipStream_t stream, int n_cu, bool tiny, Tail
   TAIL_TRY(hipEventRecord(m.ev[3], stream));
   TAIL_TRY(hipMemcpyAsync(h_ctl + 4, m.cigar_off.as<uint32_t>() + nr, 4, hipMemcpyDeviceToHost, stream));
   TAIL_TRY(hipMemcpyAsync(h_ctl + 5, m.md_off.as<uint32_t>() + nr, 4, hipMemcpyDeviceToHost, stream));
-  m.last_n = n, m.last_nr = nr, m.paired = false;
+  m.last_n = n, m.last_nr = nr, m.paired = false, m.n_resc = 0, m.resc_timed = false;
   if (!copy_records) {  // the caller renders them on the device (sam())
     TAIL_TRY(hipMemcpyAsync(h_ctl, m.ctl.p, 16, hipMemcpyDeviceToHost, stream));
     TAIL_TRY(hipStreamSynchronize(stream));
@@ -1906,7 +2244,7 @@ int Tail::sam(const TailInput &in, const SamInput &names, hipStream_t stream, in
     if (err) *err = "the records were not paired (Tail::pair)";
     return FEM_ERR_STATE;
   }
-  const uint32_t nr = m.last_nr;
+  const uint32_t nr = m.last_nr + (paired ? m.n_resc : 0u);  // (paired: lines, the rescued records' included)
   const size_t r1 = (size_t)nr + 1;
   for (hipEvent_t &e : m.ev)
     if (!e) TAIL_TRY(hipEventCreate(&e));
@@ -1984,7 +2322,7 @@ int Tail::sam(const TailInput &in, const SamInput &names, hipStream_t stream, in
   return FEM_OK;
 }
 
-int Tail::pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::string *err) {
+int Tail::pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::string *err, const RescueInput *rescue) {
   if (!impl_) return FEM_ERR_STATE;
   Impl &m = *impl_;
   const uint32_t n = m.last_n, nr = m.last_nr, np = n / 2u;
@@ -1992,7 +2330,125 @@ int Tail::pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::
     if (err) *err = "a paired batch holds an even number of reads";
     return FEM_ERR_INVALID;
   }
-  const size_t lines = std::max<size_t>(nr, 1);
+  m.n_resc = 0, m.resc_timed = false;
+  const uint32_t *resc_before = nullptr;
+  if (rescue && np) {  // ---- mate rescue: the kept records behind run()'s, resc_before their exclusive scan over the pairs ----
+    const int32_t E = rescue->max_edits;
+    for (hipEvent_t &e : m.ev_resc)
+      if (!e) TAIL_TRY(hipEventCreate(&e));
+    TAIL_TRY(m.r_ctl.need(16));
+    TAIL_TRY(m.h_r_ctl.need(16));
+    TAIL_TRY(m.r_cand.need((size_t)np * 4));
+    TAIL_TRY(m.r_best.need((size_t)np * 8));
+    TAIL_TRY(m.r_jobs.need((size_t)np * kRescueAnchors * 4));
+    const uint32_t *h_tot = m.h_ctl.as<uint32_t>();  // run() left its CIGAR and MD totals in h_ctl[4], h_ctl[5]
+    RescueParams r{};
+    r.n_pairs = np, r.n_records = nr, r.E = E, r.min_insert = min_insert, r.max_insert = max_insert;
+    r.bases = rescue->bases, r.read_off = rescue->read_off, r.ref_raw = rescue->ref_raw, r.ref_bytes = rescue->ref_bytes;
+    r.seq_off = rescue->seq_off, r.seq_len = rescue->seq_len;
+    r.ctl = m.r_ctl.as<uint32_t>(), r.cand_pair = m.r_cand.as<uint32_t>(), r.jobs = m.r_jobs.as<uint32_t>();
+    r.best = m.r_best.as<unsigned long long>();
+    r.cig_total = h_tot[4], r.md_total = h_tot[5];
+    auto bind_records = [&]() {
+      r.rec_begin = m.rec_begin.as<uint32_t>(), r.flag = m.flag.as<uint16_t>(), r.tid = m.tid.as<uint32_t>(), r.pos0 = m.pos0.as<uint32_t>();
+      r.nm = m.nm.as<uint8_t>(), r.cigar_off = m.cigar_off.as<uint32_t>(), r.cigar = m.cigar.as<uint32_t>();
+      r.md_off = m.md_off.as<uint32_t>(), r.md = m.md.as<uint8_t>(), r.s_read = m.s_read.as<uint32_t>();
+    };
+    bind_records();
+    TAIL_TRY(hipEventRecord(m.ev_resc[0], stream));
+    TAIL_TRY(hipMemsetAsync(m.r_ctl.p, 0, 16, stream));
+    hipLaunchKernelGGL(rescue_jobs_kernel, dim3((np + 255u) / 256u), dim3(256), 0, stream, r);
+    TAIL_TRY(hipGetLastError());
+    uint32_t *h_rc = m.h_r_ctl.as<uint32_t>();
+    TAIL_TRY(hipMemcpyAsync(h_rc, m.r_ctl.p, 8, hipMemcpyDeviceToHost, stream));
+    TAIL_TRY(hipStreamSynchronize(stream));
+    const uint32_t n_cand = h_rc[0], n_jobs = h_rc[1];
+    if (n_cand) {
+      // first pass: the staging of a walk of E errors on canonical characters (<= 2E + 2 runs; MD <= 2E + 1 numbers of <= 4
+      // digits and 3E characters); overflow pass: the longest walk, as trace_kernel's (every column an MD character)
+      r.max_len = std::max<uint32_t>(rescue->max_len, 1);
+      r.ops_cap = 2u * (uint32_t)E + 8u, r.md_cap = 8u * (uint32_t)E + 64u;
+      r.o_ops_cap = 2u * r.max_len + 2u * (uint32_t)E + 8u, r.o_md_cap = 8u * r.max_len + 128u;
+      const size_t rec_cap = (size_t)nr + n_cand + 1;
+      TAIL_TRY(m.flag.grow(rec_cap * 2, (size_t)nr * 2, stream));
+      TAIL_TRY(m.tid.grow(rec_cap * 4, (size_t)nr * 4, stream));
+      TAIL_TRY(m.pos0.grow(rec_cap * 4, (size_t)nr * 4, stream));
+      TAIL_TRY(m.nm.grow(rec_cap, nr, stream));
+      TAIL_TRY(m.s_read.grow(rec_cap * 4, (size_t)nr * 4, stream));
+      TAIL_TRY(m.cigar_off.grow(rec_cap * 4, ((size_t)nr + 1) * 4, stream));
+      TAIL_TRY(m.md_off.grow(rec_cap * 4, ((size_t)nr + 1) * 4, stream));
+      bind_records();
+      TAIL_TRY(m.r_ops.need((size_t)n_cand * r.ops_cap * 4));
+      TAIL_TRY(m.r_md.need((size_t)n_cand * r.md_cap));
+      TAIL_TRY(m.r_rec.need((size_t)n_cand * kRescRec * 4));
+      TAIL_TRY(m.r_ovf.need((size_t)n_cand * 4));
+      r.ovf_queue = m.r_ovf.as<uint32_t>();
+      const size_t p1 = (size_t)np + 1;
+      TAIL_TRY(m.r_kept.need(p1 * 12));
+      TAIL_TRY(m.r_scan.need(p1 * 12));
+      r.t_ops = m.r_ops.as<uint32_t>(), r.t_md = m.r_md.as<uint8_t>(), r.c_rec = m.r_rec.as<uint32_t>();
+      r.kept = m.r_kept.as<uint32_t>(), r.k_ops = r.kept + p1, r.k_md = r.kept + 2 * p1;
+      r.s_kept = m.r_scan.as<uint32_t>(), r.s_ops = r.s_kept + p1, r.s_md = r.s_kept + 2 * p1;
+      TAIL_TRY(hipMemsetAsync(m.r_kept.p, 0, p1 * 12, stream));
+      if (n_jobs) {
+        const uint32_t blocks = std::min<uint32_t>((n_jobs + kResWaves - 1u) / kResWaves, 16384u);
+        hipLaunchKernelGGL(rescue_search_kernel, dim3(blocks), dim3(64 * kResWaves), 0, stream, r);
+        TAIL_TRY(hipGetLastError());
+      }
+      // the trace kernel's LDS plan (trace_kernel's, at E)
+      r.text_words = (r.max_len + 3) / 4 + 4, r.pat_words = (r.max_len + 2 * (uint32_t)E + 3) / 4 + 4;
+      const uint32_t words_per_lane = r.text_words + r.pat_words + 2 * r.max_len;
+      r.lanes = std::min<uint32_t>(64, (64u * 1024u / 4u) / words_per_lane);
+      if (r.lanes == 0) {
+        if (err) *err = "read too long for the device traceback";
+        return FEM_ERR_UNSUPPORTED;
+      }
+      const uint32_t t_blocks = std::min<uint32_t>((n_cand + r.lanes - 1u) / r.lanes, 16384u);
+      r.overflow_pass = 0;
+      hipLaunchKernelGGL(rescue_trace_kernel, dim3(t_blocks), dim3(64), r.lanes * words_per_lane * 4u, stream, r);
+      TAIL_TRY(hipGetLastError());
+      TAIL_TRY(hipMemcpyAsync(h_rc + 2, m.r_ctl.as<uint32_t>() + 2, 4, hipMemcpyDeviceToHost, stream));
+      TAIL_TRY(hipStreamSynchronize(stream));
+      const uint32_t n_ovf = h_rc[2];
+      if (n_ovf) {  // the records that outgrew the first staging, again with room for the longest walk
+        TAIL_TRY(m.r_o_ops.need((size_t)n_ovf * r.o_ops_cap * 4));
+        TAIL_TRY(m.r_o_md.need((size_t)n_ovf * r.o_md_cap));
+        r.o_ops = m.r_o_ops.as<uint32_t>(), r.o_md = m.r_o_md.as<uint8_t>(), r.overflow_pass = 1;
+        const uint32_t o_blocks = std::min<uint32_t>((n_ovf + r.lanes - 1u) / r.lanes, 16384u);
+        hipLaunchKernelGGL(rescue_trace_kernel, dim3(o_blocks), dim3(64), r.lanes * words_per_lane * 4u, stream, r);
+        TAIL_TRY(hipGetLastError());
+      }
+      // the kept records' CIGAR runs and MD characters fit what their stagings can hold
+      TAIL_TRY(m.cigar.grow(((size_t)r.cig_total + (size_t)n_cand * r.ops_cap + (size_t)n_ovf * r.o_ops_cap) * 4,
+                            (size_t)r.cig_total * 4, stream));
+      TAIL_TRY(m.md.grow((size_t)r.md_total + (size_t)n_cand * r.md_cap + (size_t)n_ovf * r.o_md_cap, r.md_total, stream));
+      bind_records();
+      {
+        auto lens = rocprim::make_zip_iterator(rocprim::make_tuple(r.kept, r.k_ops, r.k_md));
+        auto offs = rocprim::make_zip_iterator(rocprim::make_tuple(m.r_scan.as<uint32_t>(), m.r_scan.as<uint32_t>() + p1,
+                                                                   m.r_scan.as<uint32_t>() + 2 * p1));
+        size_t tmp = 0;
+        TAIL_TRY(rocprim::exclusive_scan(nullptr, tmp, lens, offs, rocprim::make_tuple(0u, 0u, 0u), p1, TriplePlus(), stream));
+        TAIL_TRY(m.r_scan_tmp.need(std::max<size_t>(tmp, 16)));
+        tmp = m.r_scan_tmp.cap;
+        TAIL_TRY(rocprim::exclusive_scan(m.r_scan_tmp.p, tmp, lens, offs, rocprim::make_tuple(0u, 0u, 0u), p1, TriplePlus(), stream));
+      }
+      hipLaunchKernelGGL(rescue_append_kernel, dim3((n_cand + 255u) / 256u), dim3(256), 0, stream, r);
+      TAIL_TRY(hipGetLastError());
+      TAIL_TRY(hipMemcpyAsync(h_rc, m.r_scan.as<uint32_t>() + np, 4, hipMemcpyDeviceToHost, stream));
+      TAIL_TRY(hipMemcpyAsync(h_rc + 3, m.r_ctl.as<uint32_t>() + 3, 4, hipMemcpyDeviceToHost, stream));
+      TAIL_TRY(hipStreamSynchronize(stream));
+      if (h_rc[3] != 0) {
+        if (err) *err = "mate rescue: a traceback outgrew its staging (internal error)";
+        return FEM_ERR_HIP;
+      }
+      m.n_resc = h_rc[0];
+      if (m.n_resc) resc_before = m.r_scan.as<uint32_t>();
+    }
+    TAIL_TRY(hipEventRecord(m.ev_resc[1], stream));
+    m.resc_timed = true;
+  }
+  const size_t lines = std::max<size_t>((size_t)nr + m.n_resc, 1);
   TAIL_TRY(m.perm.need(lines * 4));
   TAIL_TRY(m.pflag.need(lines * 2));
   TAIL_TRY(m.mtid.need(lines * 4));
@@ -2012,6 +2468,7 @@ int Tail::pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::
     q.nm = m.nm.as<uint8_t>(), q.cigar_off = m.cigar_off.as<uint32_t>(), q.cigar = m.cigar.as<uint32_t>();
     q.perm = m.perm.as<uint32_t>(), q.pflag = m.pflag.as<uint16_t>(), q.mtid = m.mtid.as<uint32_t>(), q.mpos0 = m.mpos0.as<uint32_t>();
     q.tlen = m.tlen.as<int32_t>(), q.pair_begin = m.pair_begin.as<uint32_t>(), q.n_proper = m.pair_ctl.as<uint32_t>();
+    q.resc_before = resc_before, q.resc_first = nr;
     hipLaunchKernelGGL(pair_kernel, dim3((np + 255u) / 256u), dim3(256), 0, stream, q);
     TAIL_TRY(hipGetLastError());
   } else {
@@ -2021,6 +2478,14 @@ int Tail::pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::
   TAIL_TRY(hipMemcpyAsync(m.h_pair_ctl.p, m.pair_ctl.p, 4, hipMemcpyDeviceToHost, stream));
   m.paired = true;
   return FEM_OK;
+}
+
+uint64_t Tail::n_rescued() const { return impl_ && impl_->paired ? impl_->n_resc : 0; }
+
+float Tail::rescue_ms() const {
+  float t = 0.f;
+  if (!impl_ || !impl_->paired || !impl_->resc_timed || hipEventElapsedTime(&t, impl_->ev_resc[0], impl_->ev_resc[1]) != hipSuccess) return 0.f;
+  return t;
 }
 
 uint64_t Tail::n_proper() const { return impl_ && impl_->paired && impl_->h_pair_ctl.p ? impl_->h_pair_ctl.as<uint32_t>()[0] : 0; }
@@ -2034,7 +2499,7 @@ float Tail::pair_ms() const {
 int Tail::pair_fetch(hipStream_t stream, PairOutput *out, std::string *err) {
   if (!impl_ || !impl_->paired || !out) return FEM_ERR_STATE;
   Impl &m = *impl_;
-  const uint32_t n = m.last_n, nr = m.last_nr;
+  const uint32_t n = m.last_n, nr = m.last_nr + m.n_resc;  // (lines)
   const size_t lines = std::max<size_t>(nr, 1);
   TAIL_TRY(m.h_perm.need(lines * 4));
   TAIL_TRY(m.h_pflag.need(lines * 2));
@@ -2050,10 +2515,37 @@ int Tail::pair_fetch(hipStream_t stream, PairOutput *out, std::string *err) {
     TAIL_TRY(hipMemcpyAsync(m.h_tlen.p, m.tlen.p, (size_t)nr * 4, hipMemcpyDeviceToHost, stream));
   }
   TAIL_TRY(hipMemcpyAsync(m.h_pair_begin.p, m.pair_begin.p, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost, stream));
+  // the rescued records (records last_nr .. last_nr + n_resc - 1), their offsets as they stand (from run()'s totals on)
+  const uint32_t k = m.n_resc, first = m.last_nr;
+  TAIL_TRY(m.h_r_flag.need(std::max<size_t>(k, 1) * 2));
+  TAIL_TRY(m.h_r_tid.need(std::max<size_t>(k, 1) * 4));
+  TAIL_TRY(m.h_r_pos0.need(std::max<size_t>(k, 1) * 4));
+  TAIL_TRY(m.h_r_nm.need(std::max<size_t>(k, 1)));
+  TAIL_TRY(m.h_r_cigar_off.need(((size_t)k + 1) * 4));
+  TAIL_TRY(m.h_r_md_off.need(((size_t)k + 1) * 4));
+  if (k) {
+    TAIL_TRY(hipMemcpyAsync(m.h_r_flag.p, m.flag.as<uint16_t>() + first, (size_t)k * 2, hipMemcpyDeviceToHost, stream));
+    TAIL_TRY(hipMemcpyAsync(m.h_r_tid.p, m.tid.as<uint32_t>() + first, (size_t)k * 4, hipMemcpyDeviceToHost, stream));
+    TAIL_TRY(hipMemcpyAsync(m.h_r_pos0.p, m.pos0.as<uint32_t>() + first, (size_t)k * 4, hipMemcpyDeviceToHost, stream));
+    TAIL_TRY(hipMemcpyAsync(m.h_r_nm.p, m.nm.as<uint8_t>() + first, k, hipMemcpyDeviceToHost, stream));
+    TAIL_TRY(hipMemcpyAsync(m.h_r_cigar_off.p, m.cigar_off.as<uint32_t>() + first, ((size_t)k + 1) * 4, hipMemcpyDeviceToHost, stream));
+    TAIL_TRY(hipMemcpyAsync(m.h_r_md_off.p, m.md_off.as<uint32_t>() + first, ((size_t)k + 1) * 4, hipMemcpyDeviceToHost, stream));
+  }
   TAIL_TRY(hipStreamSynchronize(stream));
+  const uint32_t *co = m.h_r_cigar_off.as<uint32_t>(), *mo = m.h_r_md_off.as<uint32_t>();
+  const size_t n_cig = k ? co[k] - co[0] : 0, n_md = k ? mo[k] - mo[0] : 0;
+  TAIL_TRY(m.h_r_cigar.need(std::max<size_t>(n_cig, 1) * 4));
+  TAIL_TRY(m.h_r_md.need(std::max<size_t>(n_md, 1)));
+  if (n_cig) TAIL_TRY(hipMemcpyAsync(m.h_r_cigar.p, m.cigar.as<uint32_t>() + co[0], n_cig * 4, hipMemcpyDeviceToHost, stream));
+  if (n_md) TAIL_TRY(hipMemcpyAsync(m.h_r_md.p, m.md.as<uint8_t>() + mo[0], n_md, hipMemcpyDeviceToHost, stream));
+  if (n_cig || n_md) TAIL_TRY(hipStreamSynchronize(stream));
   out->n_pairs = n / 2u, out->n_records = nr, out->n_proper = m.h_pair_ctl.as<uint32_t>()[0];
   out->pair_begin = m.h_pair_begin.as<uint32_t>(), out->perm = m.h_perm.as<uint32_t>(), out->flag = m.h_pflag.as<uint16_t>();
   out->mate_tid = m.h_mtid.as<uint32_t>(), out->mate_pos0 = m.h_mpos0.as<uint32_t>(), out->tlen = m.h_tlen.as<int32_t>();
+  out->first_rescued = first, out->n_rescued = k;
+  out->r_flag = m.h_r_flag.as<uint16_t>(), out->r_tid = m.h_r_tid.as<uint32_t>(), out->r_pos0 = m.h_r_pos0.as<uint32_t>();
+  out->r_nm = m.h_r_nm.as<uint8_t>(), out->r_cigar_off = co, out->r_cigar = m.h_r_cigar.as<uint32_t>();
+  out->r_md_off = mo, out->r_md = m.h_r_md.as<char>();
   return FEM_OK;
 }
 

@@ -76,6 +76,27 @@ struct PairOutput {  // pinned host memory owned by the Tail object, valid until
   const uint16_t *flag;        // per line: the SAM flag as written, 0x8000 kept
   const uint32_t *mate_tid, *mate_pos0;  // per line: the other mate's primary (0xFFFFFFFF: the other mate has no record)
   const int32_t *tlen;         // per line
+  // mate rescue (RescueInput): records first_rescued .. first_rescued + n_rescued - 1 are not run()'s but the rescued mates'
+  uint32_t first_rescued;
+  uint64_t n_rescued;
+  const uint16_t *r_flag;
+  const uint32_t *r_tid, *r_pos0;
+  const uint8_t *r_nm;
+  const uint32_t *r_cigar_off, *r_cigar;  // r_cigar_off: n_rescued + 1, from r_cigar_off[0] (not 0) on
+  const uint32_t *r_md_off;               // n_rescued + 1, from r_md_off[0] on
+  const char *r_md;
+};
+
+// Mate rescue (fem_dev_set_rescue): what pair() needs besides the records to search the mapped mate's insert window.
+struct RescueInput {  // device pointers unless noted
+  int32_t max_edits;           // E, 0 .. 15
+  const uint8_t *bases;        // the batch's read characters (both stagings leave them on the device)
+  const uint64_t *read_off;
+  uint32_t max_len;            // host: longest read of the batch
+  const uint8_t *ref_raw;
+  uint64_t ref_bytes;          // host: bytes in ref_raw, its slack included
+  const uint64_t *seq_off;
+  const uint32_t *seq_len;
 };
 
 // One text on its way home at a time (per GPU).  Two device-to-host copies queued in the copy engines take both of them, and
@@ -114,9 +135,13 @@ class Tail {
           bool wait = true, TextGate *gate = nullptr, bool paired = false);
   // Pairs the records of the last run() (pair_kernel): output order, FLAG, mate columns and TLEN of every line, the proper-pair
   // count.  Asynchronous on `stream`; n_proper() is valid once the stream has been synchronised (sam() does).
-  int pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::string *err);
+  // rescue (optional): mate rescue first (the rescue kernels), the kept rescued records appended behind run()'s; pair() then
+  // waits for the stream twice (the candidate count, the kept count).
+  int pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::string *err, const RescueInput *rescue = nullptr);
   uint64_t n_proper() const;
+  uint64_t n_rescued() const;  // kept rescued records of the last pair() (0 without rescue)
   float pair_ms() const;  // device time of the last pair(), once its stream has been synchronised (timing: 0 otherwise)
+  float rescue_ms() const;  // ... and of its rescue kernels
   // The arrays of the last pair() to the host (waits for `stream`).
   int pair_fetch(hipStream_t stream, PairOutput *out, std::string *err);
   int wait_text();

@@ -20,6 +20,7 @@ ABI_SYMBOLS = [
     "fem_device_numa", "fem_bind_thread_near_device",
     "fem_dev_allreduce_stats",
     "fem_dev_set_pairs", "fem_dev_fetch_pairs", "fem_dev_pair_count",
+    "fem_dev_set_rescue", "fem_dev_rescue_count",
 ]
 
 
@@ -61,6 +62,10 @@ class _BatchSam(C.Structure):
 
 class _PairParams(C.Structure):
     _fields_ = [("min_insert", C.c_int32), ("max_insert", C.c_int32)]
+
+
+class _RescueParams(C.Structure):
+    _fields_ = [("max_edits", C.c_int32)]
 
 
 class _BatchPairs(C.Structure):
@@ -137,6 +142,9 @@ def load_hip():
         L.fem_dev_set_pairs.argtypes = [vp, C.c_int, C.POINTER(_PairParams)]
         L.fem_dev_fetch_pairs.argtypes = [vp, C.c_int, C.POINTER(_BatchPairs)]
         L.fem_dev_pair_count.argtypes = [vp, C.c_int, C.POINTER(u64)]
+    if hasattr(L, "fem_dev_set_rescue"):
+        L.fem_dev_set_rescue.argtypes = [vp, C.c_int, C.POINTER(_RescueParams)]
+        L.fem_dev_rescue_count.argtypes = [vp, C.c_int, C.POINTER(u64)]
     L.fem_device_numa.argtypes = [C.c_int, C.POINTER(C.c_int32), C.c_char_p, u64]
     L.fem_bind_thread_near_device.argtypes = [C.c_int]
     _HIP = L
@@ -517,6 +525,20 @@ class Device:
         """fem_dev_pair_count: proper pairs of the slot's last paired text."""
         n = C.c_uint64()
         self._check(self._L.fem_dev_pair_count(self._h, slot, C.byref(n)))
+        return int(n.value)
+
+    def set_rescue(self, max_edits=None, slot=0):
+        """fem_dev_set_rescue: rescue the mate without records of a read pair at max_edits (0..15) edits; None: off."""
+        if max_edits is None:
+            self._check(self._L.fem_dev_set_rescue(self._h, slot, None))
+        else:
+            rp = _RescueParams(int(max_edits))
+            self._check(self._L.fem_dev_set_rescue(self._h, slot, C.byref(rp)))
+
+    def rescue_count(self, slot=0):
+        """fem_dev_rescue_count: rescued mates of the slot's last paired text (or fetch_pairs)."""
+        n = C.c_uint64()
+        self._check(self._L.fem_dev_rescue_count(self._h, slot, C.byref(n)))
         return int(n.value)
 
     def map_batch(self, bases, offsets, e=3, a=1, k=12, step=3, slot=0):

@@ -306,6 +306,32 @@ int fem_dev_fetch_pairs(fem_dev *h, int slot, fem_batch_pairs *out);
 /* Proper pairs of the slot's last paired SAM text (valid once fem_dev_fetch_sam[_nowait] has returned) or fem_dev_fetch_pairs. */
 int fem_dev_pair_count(fem_dev *h, int slot, uint64_t *n_proper);
 
+/* ---- mate rescue (new; opt-in: with it off every paired output stays byte for byte what it is without it) ----
+ * fem_dev_set_rescue: the slot's read pairs are rescued at max_edits = E edits (0 <= E <= 15, else FEM_ERR_INVALID); NULL: off.
+ *   It takes effect with pair mode (fem_dev_set_pairs); fetch time refuses max_insert - min_insert > 65536 (FEM_ERR_UNSUPPORTED).
+ * Rule.  A pair is a candidate when exactly one mate, B (length L), has no record.  The anchors are those of the other mate's
+ *   first FEM_RESCUE_ANCHORS records that do not carry 0x8000.  Per anchor a (sequence tid, pa = pos0, ea = end0, signed
+ *   arithmetic), the window of B's pos0 is
+ *     anchor forward: B reverse-complemented, lo = max(pa, pa + I - L), hi = pa + X - L;
+ *     anchor reverse: B forward,             lo = max(0, ea - X),         hi = min(pa, ea - I);      none when lo > hi
+ *   (I, X = min_insert, max_insert).  Tiles c_j = lo + j (2E + 1) <= hi, skipped where c_j + L + 2E exceeds the sequence; tile c
+ *   runs the banded Myers of the mapping (fo_banded_ed32: one 32-bit word, first strict minimum) at E over ref[c, c + L + 2E)
+ *   and hits when ed <= E and pos0 = c + end - L + 1 <= hi.  Each anchor keeps its least (ed, pos0); the pair takes the least
+ *   (nm(a) + ed, a); that hit is traced at E (the traceback of the mapping) into a record: FLAG 16 if B was reverse-complemented
+ *   else 0, the anchor's tid, pos0 = c + start, NM = ed, CIGAR and MD.  It is kept only if start >= 0 and it is concordant with
+ *   its anchor (the pairing rule above, the real CIGAR span); a kept record is B's only record, otherwise the pair stays as it
+ *   is (no fall-back to another anchor).
+ * Pairing then runs unchanged on the extended lists (the rescued pair is a proper one, counted by fem_dev_pair_count), and
+ *   fem_batch_pairs holds the rescued records like any other.  fem_dev_fetch_records and the stats keep their single-end meaning.
+ * fem_dev_rescue_count: kept rescued records of the slot's last paired text or fem_dev_fetch_pairs (valid when
+ *   fem_dev_pair_count is); 0 with rescue off. */
+#define FEM_RESCUE_ANCHORS 8
+typedef struct {
+  int32_t max_edits;
+} fem_rescue_params;
+int fem_dev_set_rescue(fem_dev *h, int slot, const fem_rescue_params *rp);
+int fem_dev_rescue_count(fem_dev *h, int slot, uint64_t *n_rescued);
+
 /* Name of the seed + filter kernel fem_dev_map_staged would launch first for these parameters on the resident
  * index ("seed_join_kernel" — behind its "seed_select_kernel"; "seed_join_banked_kernel" where the reference's sequences
  * need more than one 32-bit coordinate space —, "seed_fast_kernel<hash>", "seed_fast_kernel<lean>" or
@@ -330,7 +356,8 @@ int fem_dev_index_info(const fem_dev *h, char *buf, uint64_t cap);
  * 7 = the SAM text kernels;
  * 8 = seed selection kernel of the dense-index path (it runs beside the previous batch's kernel 0: its event time is
  * what it takes there, not what it would take alone);
- * 9 = the pairing kernel of a paired fem_dev_fetch_sam (fem_dev_set_pairs). */
+ * 9 = the pairing kernel of a paired fem_dev_fetch_sam (fem_dev_set_pairs);
+ * 10 = the mate rescue kernels in front of it (fem_dev_set_rescue; their host waits included). */
 int fem_dev_set_timing(fem_dev *h, int on);
 int fem_dev_reset_timing(fem_dev *h);
 int fem_dev_kernel_time(fem_dev *h, int kernel, double *ms_total, uint64_t *launches);
