@@ -30,6 +30,7 @@
 #include "fem_seed_fast.hip.h"
 #include "fem_seed_join.hip.h"
 #include "fem_tail.hip.h"
+#include "fem_bgzf.hip.h"
 
 namespace {
 
@@ -41,7 +42,7 @@ constexpr uint32_t kMaxReadLen = 1024;
 constexpr size_t kFrontPad = 16;  // kernels fetch a reverse-strand chunk from up to 15 bytes in front of a read
 constexpr uint32_t kXcapSmall = 512, kFcap = 128, kCcap = 128;
 
-constexpr int kTimedKernels = 11;  // fem_dev_kernel_time ids: 0 seed (join), 1 verify, 2 generic seed, 3-5 tail, 6 pack_results_kernel (round 5; the count kernel of rounds 1-2 before), 7 SAM text, 8 seed selection, 9 pairing, 10 mate rescue
+constexpr int kTimedKernels = 13;  // fem_dev_kernel_time ids: 0 seed (join), 1 verify, 2 generic seed, 3-5 tail, 6 pack_results_kernel (round 5; the count kernel of rounds 1-2 before), 7 SAM text, 8 seed selection, 9 pairing, 10 mate rescue, 11 BAM records, 12 BGZF
 struct TimedLaunch {
   int kernel;
   hipEvent_t start, stop;
@@ -241,6 +242,11 @@ struct fem_dev {
   // the slots share (the kernels' chaining events, the event pool, the timing sums, the error string) is touched under this
   // lock; a thread waiting for the device does not hold it.
   femt::TextGate text_gate;  // one SAM text on its way to the host at a time (fem_tail.hip.h)
+  // fem_dev_bgzf_compress: its compressor, input buffer and stream
+  femz::Bgzf *bgzf = nullptr;
+  uint8_t *d_zin = nullptr;
+  size_t d_zin_cap = 0;
+  hipStream_t z_stream = nullptr;
   std::recursive_mutex mu;
   int device = 0;
   StagePool *stage_pool = nullptr;  // host threads of fem_dev_stage_reads
@@ -1479,6 +1485,10 @@ int fem_dev_close(fem_dev *h) {
     delete s.tail;
     s.tail = nullptr;
   }
+  delete h->bgzf;
+  h->bgzf = nullptr;
+  if (h->d_zin) (void)hipFree(h->d_zin);
+  if (h->z_stream) (void)hipStreamDestroy(h->z_stream);
   if (h->d_ref_names) (void)hipFree(h->d_ref_names);
   if (h->d_ref_name_off) (void)hipFree(h->d_ref_name_off);
   for (hipEvent_t e : h->event_pool) (void)hipEventDestroy(e);
@@ -2338,6 +2348,99 @@ static int fetch_sam(fem_dev *h, int slot, fem_batch_sam *out, bool wait) {
   out->text = text.text, out->len = text.len, out->n_asserted = text.n_asserted;
   out->n_reads = t.n_reads, out->n_records = t.n_records;
   memcpy(out->stats, s.stats, sizeof s.stats);
+  return FEM_OK;
+}
+
+// ---- BAM output: the SAM lines as BAM records, BGZF-compressed on the device ----
+static int fetch_bam(fem_dev *h, int slot, int level, fem_batch_bam *out, bool wait) {
+  if (level < 0 || level > 1) return fail(h, FEM_ERR_INVALID, "BAM compression level must be 0 or 1");
+  int rc = fem_dev_sync(h, slot);
+  if (rc) return rc;
+  if (!out) return fail(h, FEM_ERR_INVALID, "null result");
+  Slot &s = h->slot[slot];
+  if (!s.text_staged) return fail(h, FEM_ERR_STATE, "qualities and names of this batch were not committed (fem_dev_commit_text_stage)");
+  if (s.host_quals) return fail(h, FEM_ERR_STATE, "BAM records need the qualities on the device (fem_dev_commit_text_stage, not _names_stage)");
+  if (!h->d_ref_names) return fail(h, FEM_ERR_STATE, "reference names must be uploaded first (fem_dev_upload_reference_names)");
+  s.prefetch_results = false;
+  if (!s.tail) s.tail = new (std::nothrow) femt::Tail();
+  if (!s.tail) return fail(h, FEM_ERR_NOMEM, "out of host memory");
+  femt::TailInput in{};
+  in.bases = s.bases(), in.read_off = s.d_off, in.n_reads = (uint32_t)s.n_reads, in.max_len = s.max_len;
+  in.ref_raw = h->d_ref_raw, in.ref_bytes = h->ref_bytes + 64, in.seq_off = h->d_seq_off;
+  in.planes = h->d_planes;
+  if (s.sent_packed) in.packed = s.d_packed, in.packed_bpr = s.packed_bpr, in.exc_bits = s.d_exc_bits;
+  in.cand = s.d_cand, in.ed = s.d_ed, in.end = s.d_end, in.cand_begin = s.d_begin, in.cand_count = s.d_count;
+  in.n_map = s.d_nmap, in.e = s.params.e, in.n_records = s.stats[4];
+  femt::TailOutput t{};
+  double ms[3] = {0, 0, 0}, ms_bam[2] = {0, 0};
+  std::string err;
+  if (s.paired && (s.n_reads & 1)) return fail(h, FEM_ERR_INVALID, "a batch of read pairs holds an even number of reads");
+  hipStream_t os = out_stream_of(h, s);
+  rc = s.tail->run(in, os, h->n_cu, h->tiny_buffers, &t, &err, h->timing ? ms : nullptr, false);
+  if (rc) return fail(h, rc, err);
+  if (s.paired) {
+    femt::RescueInput ri{};
+    if ((rc = rescue_input(h, s, &ri))) return rc;
+    if ((rc = s.tail->pair(s.min_insert, s.max_insert, os, &err, s.rescue ? &ri : nullptr))) return fail(h, rc, err);
+  }
+  femt::SamInput names{};
+  names.quals = s.d_quals, names.names = s.d_names, names.name_off = s.d_name_off;
+  names.ref_names = h->d_ref_names, names.ref_name_off = h->d_ref_name_off;
+  femt::BamOutput bam{};
+  HIP_TRY(h, hipStreamWaitEvent(os, s.ev_text_staged, 0));  // qualities and names came on the slot's text stream
+  rc = s.tail->bam(in, names, level, os, h->n_cu, &bam, &err, h->timing ? ms_bam : nullptr, wait, &h->text_gate, s.paired);
+  if (rc) return fail(h, rc, err);
+  s.n_proper = s.paired ? s.tail->n_proper() : 0;
+  s.n_rescued = s.paired ? s.tail->n_rescued() : 0;
+  if (!s.ev_text_order) HIP_TRY(h, hipEventCreateWithFlags(&s.ev_text_order, hipEventDisableTiming));
+  HIP_TRY(h, hipEventRecord(s.ev_text_order, os));
+  s.have_text_order = true;
+  if (h->timing) {
+    FEM_LOCK(h);
+    for (int i = 0; i < 3; ++i) h->t_ms[3 + i] += ms[i], h->t_n[3 + i] += 1;
+    h->t_ms[11] += ms_bam[0], h->t_n[11] += 1;
+    h->t_ms[12] += ms_bam[1], h->t_n[12] += 1;
+    if (s.paired) h->t_ms[9] += s.tail->pair_ms(), h->t_n[9] += 1;
+    if (s.paired && s.rescue) h->t_ms[10] += s.tail->rescue_ms(), h->t_n[10] += 1;
+  }
+  s.qual_at = nullptr;
+  out->data = bam.data, out->len = bam.len, out->raw_len = bam.raw_len, out->n_blocks = bam.n_blocks;
+  out->n_records = t.n_records, out->n_asserted = bam.n_asserted;
+  memcpy(out->stats, s.stats, sizeof s.stats);
+  return FEM_OK;
+}
+int fem_dev_fetch_bam(fem_dev *h, int slot, int level, fem_batch_bam *out) { return fetch_bam(h, slot, level, out, true); }
+int fem_dev_fetch_bam_nowait(fem_dev *h, int slot, int level, fem_batch_bam *out) { return fetch_bam(h, slot, level, out, false); }
+int fem_dev_bam_wait(fem_dev *h, int slot) { return fem_dev_sam_wait(h, slot); }
+
+int fem_dev_bgzf_compress(fem_dev *h, const void *in, uint64_t n, int level, void *out, uint64_t out_cap, uint64_t *out_len) {
+  if (!h) return FEM_ERR_INVALID;
+  FEM_LOCK(h);
+  if (!out_len || (n && (!in || !out))) return fail(h, FEM_ERR_INVALID, "null argument");
+  if (level < 0 || level > 1) return fail(h, FEM_ERR_INVALID, "BGZF compression level must be 0 or 1");
+  *out_len = 0;
+  if (!n) return FEM_OK;
+  HIP_TRY(h, hipSetDevice(h->device));
+  if (!h->bgzf) h->bgzf = new (std::nothrow) femz::Bgzf();
+  if (!h->bgzf) return fail(h, FEM_ERR_NOMEM, "out of host memory");
+  if (!h->z_stream) HIP_TRY(h, hipStreamCreateWithFlags(&h->z_stream, hipStreamNonBlocking));
+  if (h->d_zin_cap < n) {
+    if (h->d_zin) (void)hipFree(h->d_zin);
+    h->d_zin = nullptr, h->d_zin_cap = 0;
+    HIP_TRY(h, hipMalloc((void **)&h->d_zin, (size_t)n));
+    h->d_zin_cap = (size_t)n;
+  }
+  HIP_TRY(h, hipMemcpyAsync(h->d_zin, in, (size_t)n, hipMemcpyHostToDevice, h->z_stream));
+  std::vector<uint64_t> starts;
+  femz::bgzf_cut(nullptr, 0, n, &starts);
+  uint64_t len = 0;
+  std::string err;
+  int rc = h->bgzf->compress(h->d_zin, n, starts, level, h->z_stream, &len, &err);
+  if (rc) return fail(h, rc, err);
+  if (len > out_cap) return fail(h, FEM_ERR_INVALID, "output buffer too small for the BGZF members");
+  HIP_TRY(h, hipMemcpyAsync(out, h->bgzf->out(), (size_t)len, hipMemcpyDeviceToHost, h->z_stream));
+  HIP_TRY(h, hipStreamSynchronize(h->z_stream));
+  *out_len = len;
   return FEM_OK;
 }
 

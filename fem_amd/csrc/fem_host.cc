@@ -1919,6 +1919,38 @@ int fem_sam_header(const fem_tail_ref *ref, char **text, uint64_t *text_len) {
   return 0;
 }
 
+// BAM header (SAM/BAM specification 4.2): "BAM\1", l_text and the text fem_sam_header writes, n_ref, then per sequence l_name,
+// its name with a NUL, l_ref.  pos and l_ref are int32: a sequence of 2^31 bases or more cannot be written (-5).
+int fem_bam_header(const fem_tail_ref *ref, uint8_t **raw, uint64_t *len) {
+  if (!ref || !raw || !len) return -1;
+  for (uint32_t i = 0; i < ref->n_seq; ++i)
+    if (ref->len[i] >= (1u << 31)) return -5;
+  char *text = nullptr;
+  uint64_t text_len = 0;
+  int rc = fem_sam_header(ref, &text, &text_len);
+  if (rc) return rc;
+  std::string s("BAM\1", 4);
+  auto i32 = [&](uint32_t v) {
+    for (int k = 0; k < 4; ++k) s.push_back((char)(v >> (8 * k)));
+  };
+  i32((uint32_t)text_len);
+  s.append(text, text_len);
+  free(text);
+  i32(ref->n_seq);
+  for (uint32_t i = 0; i < ref->n_seq; ++i) {
+    const uint64_t nl = ref->name_off[i + 1] - ref->name_off[i];
+    i32((uint32_t)(nl + 1));
+    s.append(ref->names + ref->name_off[i], nl);
+    s.push_back('\0');
+    i32(ref->len[i]);
+  }
+  *raw = (uint8_t *)malloc(s.size() + 1);
+  if (!*raw) return -4;
+  memcpy(*raw, s.data(), s.size());
+  *len = s.size();
+  return 0;
+}
+
 int fem_tail_sam(int32_t e, const fem_tail_ref *ref, const fem_seqset *reads, const fem_tail_input *in, int n_threads,
                  char **text, uint64_t *text_len) {
   if (!ref || !reads || !in || !text || !text_len) return -1;

@@ -177,6 +177,9 @@ int fem_records_sam_refs(const fem_tail_ref *ref, const fem_read_refs *reads, co
                          uint64_t *cap, fem_text_part *parts, uint64_t *n_asserted);
 /* "@SQ\tSN:%s\tLN:%d\n" per sequence (src/output_queue.c:104-108). *text is malloc'd. */
 int fem_sam_header(const fem_tail_ref *ref, char **text, uint64_t *text_len);
+/* The BAM header, uncompressed: "BAM\1", l_text, the text of fem_sam_header, n_ref, then each sequence's l_name, name + NUL
+ * and l_ref (SAM/BAM specification 4.2).  malloc'ed (free()).  -5: a sequence of 2^31 bases or more (l_ref is an int32). */
+int fem_bam_header(const fem_tail_ref *ref, uint8_t **raw, uint64_t *len);
 /* The other half of fem_dev_commit_names_stage / fem_dev_sam_quals (include/fem_hip.h): copies read r's quality string
  * (quals + off[r], off[r + 1] - off[r] characters; off == NULL: reads of one length, quals + r * read_len) to text + qual_at[r]
  * for every read with qual_at[r] != UINT64_MAX, on up to n_threads threads (they sleep between calls).  Returns 0, or -1 on a

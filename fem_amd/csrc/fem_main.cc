@@ -74,6 +74,7 @@ void usage_map() {
   fprintf(stderr, "        -I, --minins INT  minimum insert size of a proper pair [0]\n");
   fprintf(stderr, "        -X, --maxins INT  maximum insert size of a proper pair [500]\n");
   fprintf(stderr, "        --rescue INT  with --read2: search a mate without records in its mate's insert window at INT (0-15) edits\n");
+  fprintf(stderr, "        --bam[=INT]   write BAM instead of SAM: BGZF level 1 (default) or 0 (uncompressed)\n");
   fprintf(stderr, "        -o       STR  Output SAM file \n\n");
 }
 
@@ -275,6 +276,7 @@ int map_main(int argc, char **argv) {
   long long min_insert = 0, max_insert = 500;
   long long rescue_edits = 0;  // --rescue (mate rescue at this many edits, fem_dev_set_rescue)
   bool rescue_given = false;
+  int bam_level = -1;  // --bam[=LEVEL]: BAM records and BGZF members made on the device (fem_dev_fetch_bam); -1: SAM
   fem_params params{12, 3, 2, 1};  // src/FEM_map.c:67-70: k and step are fixed, whatever the index header says
   int n_threads = 1, n_gpus = 1;
   // reads per batch: 250 k fills the pipeline soonest on small inputs; a batch costs three host round trips on its way through
@@ -288,7 +290,7 @@ int map_main(int argc, char **argv) {
                                      {"gpus", required_argument, nullptr, 'G'},  {"batch", required_argument, nullptr, 'B'},
                                      {"read2", required_argument, nullptr, 'c'}, {"minins", required_argument, nullptr, 'I'},
                                      {"maxins", required_argument, nullptr, 'X'}, {"rescue", required_argument, nullptr, 'R'},
-                                     {nullptr, 0, nullptr, 0}};
+                                     {"bam", optional_argument, nullptr, 'Z'},  {nullptr, 0, nullptr, 0}};
   int c, oi = 0;
   while ((c = getopt_long(argc, argv, short_opt, long_opt, &oi)) >= 0) {
     switch (c) {
@@ -305,6 +307,9 @@ int map_main(int argc, char **argv) {
         rescue_given = true;
         break;
       }
+      case 'Z':
+        bam_level = !optarg ? 1 : strcmp(optarg, "0") == 0 ? 0 : strcmp(optarg, "1") == 0 ? 1 : -2;  // (-2: refused below)
+        break;
       case 'e': params.e = atoi(optarg); break;
       case 't': n_threads = atoi(optarg); break;
       case 'a': params.a = atoi(optarg); break;
@@ -332,6 +337,7 @@ int map_main(int argc, char **argv) {
   else if (rescue_given && !read2_path) bad = "--rescue needs read pairs (--read2).";
   else if (rescue_given && (rescue_edits < 0 || rescue_edits > 15)) bad = "Wrong rescue error threshold (0-15).";
   else if (rescue_given && max_insert - min_insert > 65536) bad = "--rescue searches insert size ranges of at most 65536.";
+  else if (bam_level == -2) bad = "Wrong BAM compression level (0-1).";
   else if (!ref_path) bad = "Reference file path is required.";
   else if (!index_path) bad = "Index file path is required.";
   else if (!read_path) bad = "Read file path is required.";
@@ -342,6 +348,14 @@ int map_main(int argc, char **argv) {
     fprintf(stderr, "%s\n", bad);
     usage_map();
     exit(EXIT_FAILURE);
+  }
+  const bool bam = bam_level >= 0;
+  for (const char *v : {"FEM_HOST_TAIL", "FEM_HOST_FORMAT", "FEM_HOST_QUALS"}) {  // (BAM records are made on the device, from its qualities)
+    const char *x = getenv(v);
+    if (bam && x && x[0] == '1') {
+      fprintf(stderr, "--bam is not supported with %s=1: BAM records are made on the device, with the qualities there.\n", v);
+      exit(EXIT_FAILURE);
+    }
   }
 
   // Host placement: with one GPU the whole process (parser, formatter, staging buffers) moves next to it, before any
@@ -390,7 +404,7 @@ int map_main(int argc, char **argv) {
   // to box (the run is bound by the link in one and by the cores in the other); from 24 threads on the qualities stay on the
   // host.  FEM_HOST_QUALS=1 / FEM_DEVICE_QUALS=1 decide it by hand.
   const char *dq = getenv("FEM_DEVICE_QUALS"), *hq = getenv("FEM_HOST_QUALS");
-  const bool host_quals = device_text && !(dq && dq[0] == '1') && ((hq && hq[0] == '1') || n_threads >= 24);
+  const bool host_quals = device_text && !bam && !(dq && dq[0] == '1') && ((hq && hq[0] == '1') || n_threads >= 24);
   const bool splice = !host_tail && !device_text && !(spl && spl[0] == '0');
   // With the text on the device the link is what bounds the run: batches of equal-length reads then cross it at two bits per
   // base — the parser writes that form straight into the pinned staging (fem_seqfile_fill_packed ->
@@ -485,7 +499,27 @@ int map_main(int argc, char **argv) {
     }
     return true;
   };
-  {
+  if (bam) {  // the BAM header, through the device's compressor
+    uint8_t *raw = nullptr;
+    uint64_t rl = 0, zl = 0;
+    int rc = fem_bam_header(&ref.view, &raw, &rl);
+    if (rc == -5) {
+      fprintf(stderr, "A reference sequence of 2^31 bases or more cannot be written as BAM.\n");
+      exit(EXIT_FAILURE);
+    }
+    if (rc) {
+      fprintf(stderr, "BAM header failed (%d)\n", rc);
+      exit(EXIT_FAILURE);
+    }
+    std::vector<uint8_t> z((size_t)(rl / 65280 + 1) * 65536);
+    rc = fem_dev_bgzf_compress(devs[0], raw, rl, bam_level, z.data(), z.size(), &zl);
+    free(raw);
+    if (rc) return dev_fail(devs[0], "BAM header", rc);
+    if (!write_all((const char *)z.data(), zl)) {
+      fprintf(stderr, "[FEM] write error on %s\n", out_path);
+      exit_code = EXIT_FAILURE;
+    }
+  } else {
     char *hdr = nullptr;
     uint64_t hl = 0;
     fem_sam_header(&ref.view, &hdr, &hl);
@@ -683,9 +717,19 @@ int map_main(int argc, char **argv) {
         }
       };
       Channel<BatchBuf *> retire_q;
+      // BAM: the batch's BGZF members take the text's place (the writer waits for them with fem_dev_sam_wait as for a text)
+      auto fetch_bam = [&](fem_dev *hd, BatchBuf *b) -> int {
+        fem_batch_bam z{};
+        const int rc = fem_dev_fetch_bam_nowait(hd, b->slot, bam_level, &z);
+        if (rc) return rc;
+        b->sam.text = (const char *)z.data, b->sam.len = z.len, b->sam.n_records = z.n_records, b->sam.n_asserted = z.n_asserted;
+        memcpy(b->sam.stats, z.stats, sizeof z.stats);
+        return FEM_OK;
+      };
       auto retire = [&](BatchBuf *b) {
         double t0 = real_time();
         int rc = host_tail     ? fem_dev_map_batch_wait(h, b->slot, &b->res)
+                 : bam         ? fetch_bam(h, b)
                  : device_text ? fem_dev_fetch_sam_nowait(h, b->slot, &b->sam)  // (the writer waits for the text itself)
                                : fem_dev_fetch_records(h, b->slot, &b->rec);
         if (!rc && paired) rc = fem_dev_pair_count(h, b->slot, &b->n_proper);
@@ -1019,6 +1063,10 @@ int map_main(int argc, char **argv) {
     fprintf(stderr, "[FEM] timeline (s after the mapping phase began): first staging slot %.3f, first batch parsed %.3f, input read %.3f, "
                     "devices done %.3f, output written %.3f\n", t_first_slot - t_start, t_first_filled - t_start, t_reader_done - t_start,
             t_workers_done - t_start, real_time() - t_start);
+  }
+  if (bam) {  // the BGZF end-of-file marker (SAM/BAM specification 4.1.2)
+    static const unsigned char eof[28] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 66, 67, 2, 0, 27, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (!write_all((const char *)eof, sizeof eof) && !exit_code.exchange(EXIT_FAILURE)) fprintf(stderr, "[FEM] write error on %s\n", out_path);
   }
   if (close(out_fd) != 0 && !exit_code.exchange(EXIT_FAILURE)) fprintf(stderr, "[FEM] write error on %s\n", out_path);
   if (n_asserted)

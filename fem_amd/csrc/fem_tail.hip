@@ -1,6 +1,7 @@
 // fem_tail.hip — device mapping tail: kernels + the host-side driver behind fem_dev_fetch_records.
 // See fem_tail.hip.h for what is computed and the reference lines it follows.
 #include "fem_tail.hip.h"
+#include "fem_bgzf.hip.h"
 #include "fem_planes.hip.h"
 
 #include <cstring>  // before rocprim: its headers use memcpy unqualified
@@ -1418,6 +1419,117 @@ __global__ void __launch_bounds__(256) sam_write_kernel(SamParams p) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// BAM records (SAM/BAM specification §4.2): the same lines as the SAM kernels, field for field.  refID pos = tid pos0,
+// l_read_name = name + NUL, MAPQ 255, bin = reg2bin(pos0, end0) (end0 = pos0 + the M/D/N/=/X lengths, pos0 + 1 for none),
+// the device's CIGAR words as they are, FLAG & 0x7FFF, l_seq = L where SAM prints SEQ else 0, mate columns -1 -1 0 (single-end)
+// or pair_kernel's, SEQ in 4-bit codes (the SAM round trip's letters), QUAL - 33 (0xFF where SAM prints *), NM:C, MD:Z.
+// ---------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t bam_reg2bin(uint32_t beg, uint32_t end) {  // spec §5.3, end exclusive
+  --end;
+  if (beg >> 14 == end >> 14) return ((1u << 15) - 1u) / 7u + (beg >> 14);
+  if (beg >> 17 == end >> 17) return ((1u << 12) - 1u) / 7u + (beg >> 17);
+  if (beg >> 20 == end >> 20) return ((1u << 9) - 1u) / 7u + (beg >> 20);
+  if (beg >> 23 == end >> 23) return ((1u << 6) - 1u) / 7u + (beg >> 23);
+  if (beg >> 26 == end >> 26) return ((1u << 3) - 1u) / 7u + (beg >> 26);
+  return 0;
+}
+
+// Record sizes (block_size + 4); a read name over 254 characters in the batch sets *bad_name (l_read_name is a uint8).
+template <bool kPair>
+__global__ void __launch_bounds__(256) bam_len_kernel(SamParams p, uint32_t n_reads, uint32_t *bad_name) {
+  const uint32_t stride = gridDim.x * blockDim.x;
+  for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < n_reads; r += stride)
+    if (p.name_off[r + 1] - p.name_off[r] > 254u) atomicOr(bad_name, 1u);
+  for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j <= p.n_records; j += stride) {
+    if (j == p.n_records) {
+      p.line_len[j] = 0;
+      continue;
+    }
+    const uint32_t rec = kPair ? p.perm[j] : j;
+    const uint32_t r = p.s_read[rec];
+    const uint16_t flag = kPair ? p.pflag[j] : p.flag[j];
+    const bool primary = kPair ? !(flag & 256u) : p.rec_begin[r] == j;
+    const uint32_t L = (uint32_t)(p.read_off[r + 1] - p.read_off[r]);
+    const uint32_t name_len = (uint32_t)(p.name_off[r + 1] - p.name_off[r]);
+    if (flag & 0x8000u) atomicAdd(p.asserted, 1u);
+    const uint32_t n_ops = p.cigar_off[rec + 1] - p.cigar_off[rec], md_len = p.md_off[rec + 1] - p.md_off[rec];
+    const uint32_t ls = primary ? L : 0u;
+    p.line_len[j] = 36ull + name_len + 1u + 4u * n_ops + (ls + 1u) / 2u + ls + 4u + 4u + md_len;
+  }
+}
+
+// One wave per record, a byte (or CIGAR word) per lane.
+template <bool kPair>
+__global__ void __launch_bounds__(256) bam_write_kernel(SamParams p) {
+  __shared__ uint8_t code4[256];  // read character -> 4-bit code of the letter the SAM text prints
+  {
+    const uint8_t ch = kSamSeqLut[threadIdx.x];
+    const char *abc = "=ACMGRSVTWYHKDBN";
+    uint8_t c = 15;
+    for (uint8_t k = 0; k < 16; ++k)
+      if ((uint8_t)abc[k] == ch) c = k;
+    code4[threadIdx.x] = c;
+  }
+  __syncthreads();
+  const uint32_t ln = threadIdx.x & 63u;
+  const uint32_t j = blockIdx.x * 4u + (threadIdx.x >> 6);
+  if (j >= p.n_records) return;
+  const uint32_t rec = kPair ? p.perm[j] : j;
+  const uint32_t r = p.s_read[rec];
+  const uint32_t fl = kPair ? p.pflag[j] : p.flag[rec];
+  const bool primary = kPair ? !(fl & 256u) : p.rec_begin[r] == j;
+  const uint64_t ro = p.read_off[r];
+  const uint32_t L = (uint32_t)(p.read_off[r + 1] - ro), ls = primary ? L : 0u;
+  const uint64_t no = p.name_off[r];
+  const uint32_t name_len = (uint32_t)(p.name_off[r + 1] - no);
+  const uint32_t c0 = p.cigar_off[rec], n_ops = p.cigar_off[rec + 1] - c0;
+  const uint32_t m0 = p.md_off[rec], md_len = p.md_off[rec + 1] - m0;
+  const uint32_t tid = p.tid[rec], pos0 = p.pos0[rec], nm = p.nm[rec];
+  uint32_t span = 0;
+  for (uint32_t c = ln; c < n_ops; c += 64u) {
+    const uint32_t op = p.cigar[c0 + c], o = op & 0xFu;
+    if (o == 0u || o == 2u || o == 3u || o == 7u || o == 8u) span += op >> 4;
+  }
+  for (uint32_t o = 32; o; o >>= 1) span += __shfl_xor(span, o);
+  const uint32_t bin = bam_reg2bin(pos0, pos0 + (span ? span : 1u));
+  uint32_t ntid = 0xFFFFFFFFu, npos = 0xFFFFFFFFu, tlen = 0;
+  if (kPair && p.mtid[j] != 0xFFFFFFFFu) ntid = p.mtid[j], npos = p.mpos0[j], tlen = (uint32_t)p.tlen[j];
+  const uint64_t at = p.line_off[j];
+  const uint32_t size = (uint32_t)(p.line_off[j + 1] - at);
+  uint8_t *w = p.text + at;
+  if (ln < 36u) {
+    const uint32_t q = ln >> 2;
+    const uint32_t v = q == 0 ? size - 4u : q == 1 ? tid : q == 2 ? pos0 : q == 3 ? (name_len + 1u) | 255u << 8 | bin << 16
+                     : q == 4 ? n_ops | (fl & 0x7FFFu) << 16 : q == 5 ? ls : q == 6 ? ntid : q == 7 ? npos : tlen;
+    w[ln] = (uint8_t)(v >> (8u * (ln & 3u)));
+  }
+  uint8_t *x = w + 36;
+  const uint8_t *name = p.names + no;
+  for (uint32_t k = ln; k <= name_len; k += 64u) x[k] = k < name_len ? name[k] : 0;
+  x += name_len + 1u;
+  for (uint32_t c = ln; c < n_ops; c += 64u) {
+    const uint32_t op = p.cigar[c0 + c];
+    uint8_t *y = x + 4u * c;
+    y[0] = (uint8_t)op, y[1] = (uint8_t)(op >> 8), y[2] = (uint8_t)(op >> 16), y[3] = (uint8_t)(op >> 24);
+  }
+  x += 4u * n_ops;
+  const uint8_t *bases = p.bases + ro;
+  const uint32_t sb = (ls + 1u) / 2u;
+  for (uint32_t k = ln; k < sb; k += 64u) {
+    const uint32_t hi = code4[bases[2u * k]], lo = 2u * k + 1u < ls ? code4[bases[2u * k + 1u]] : 0u;
+    x[k] = (uint8_t)(hi << 4 | lo);
+  }
+  x += sb;
+  const uint8_t *quals = p.quals ? p.quals + ro : nullptr;
+  for (uint32_t k = ln; k < ls; k += 64u) x[k] = quals ? (uint8_t)(quals[k] - 33u) : (uint8_t)0xFF;
+  x += ls;
+  if (ln == 0) x[0] = 'N', x[1] = 'M', x[2] = 'C', x[3] = (uint8_t)nm, x[4] = 'M', x[5] = 'D', x[6] = 'Z';
+  x += 7;
+  const uint8_t *md = p.md + m0;
+  for (uint32_t k = ln; k <= md_len; k += 64u) x[k] = k < md_len ? md[k] : 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // Pair mode: the records of read i (mate 1, list A) and of read n_pairs + i (mate 2, list B) of a batch of 2 n_pairs reads.
 // A combination (a, b) is concordant when neither carries 0x8000, both lie on one sequence on opposite strands, the forward one
 // f starts at or before the reverse one r, and I <= end0(r) - pos0(f) <= X (end0 = pos0 + the M and D lengths of the CIGAR).
@@ -1886,6 +1998,11 @@ struct Tail::Impl {
   // mate rescue (pair() with a RescueInput): candidates, jobs, best hits, the tracebacks' staging, the kept flags and their scans
   DevBuf r_ctl, r_cand, r_jobs, r_best, r_ops, r_md, r_rec, r_ovf, r_o_ops, r_o_md, r_kept, r_scan, r_scan_tmp;
   PinBuf h_r_ctl, h_r_flag, h_r_tid, h_r_pos0, h_r_nm, h_r_cigar_off, h_r_cigar, h_r_md_off, h_r_md;
+  // BAM (bam()): the name check, the record offsets home (the member cuts), the compressor
+  DevBuf bam_ctl;
+  PinBuf h_line_off;
+  femz::Bgzf bgzf;
+  std::vector<uint64_t> cuts;
   uint32_t last_n = 0, last_nr = 0;  // what the last run() left on the device
   bool paired = false;               // pair() has run on it
   uint32_t n_resc = 0;               // rescued records the last pair() appended behind run()'s (records last_nr ..)
@@ -1906,9 +2023,9 @@ struct Tail::Impl {
     for (DevBuf *b : {&perm, &pflag, &mtid, &mpos0, &tlen, &pair_begin, &pair_ctl}) b->release();
     for (PinBuf *b : {&h_perm, &h_pflag, &h_mtid, &h_mpos0, &h_tlen, &h_pair_begin, &h_pair_ctl}) b->release();
     for (DevBuf *b : {&rec_begin, &queue, &ctl, &u_cand, &u_misc, &s_cand, &s_misc, &s_read, &t_ops, &t_md, &o_ops, &o_md, &ovf, &rec_list,
-                      &src_slot, &n_ops, &n_md, &flag, &tid, &pos0, &nm, &cigar_off, &md_off, &cigar, &md, &scan_tmp, &line_len, &line_off, &text, &qual_at})
+                      &src_slot, &n_ops, &n_md, &flag, &tid, &pos0, &nm, &cigar_off, &md_off, &cigar, &md, &scan_tmp, &line_len, &line_off, &text, &qual_at, &bam_ctl})
       b->release();
-    for (PinBuf *b : {&h_ctl, &h_rec_begin, &h_flag, &h_tid, &h_pos0, &h_nm, &h_cigar_off, &h_md_off, &h_cigar, &h_md, &h_text, &h_qual_at})
+    for (PinBuf *b : {&h_ctl, &h_rec_begin, &h_flag, &h_tid, &h_pos0, &h_nm, &h_cigar_off, &h_md_off, &h_cigar, &h_md, &h_text, &h_qual_at, &h_line_off})
       b->release();
     for (hipEvent_t e : ev)
       if (e) (void)hipEventDestroy(e);
@@ -2319,6 +2436,98 @@ int Tail::sam(const TailInput &in, const SamInput &names, hipStream_t stream, in
   }
   out->text = m.h_text.as<char>(), out->len = total, out->n_asserted = m.h_ctl.as<uint32_t>()[2];
   out->qual_at = hole ? m.h_qual_at.as<uint64_t>() : nullptr;
+  return FEM_OK;
+}
+
+int Tail::bam(const TailInput &in, const SamInput &names, int level, hipStream_t stream, int n_cu, BamOutput *out, std::string *err,
+              double *ms, bool wait, TextGate *gate, bool paired) {
+  if (!impl_ || !out) return FEM_ERR_STATE;
+  Impl &m = *impl_;
+  if (paired && !m.paired) {
+    if (err) *err = "the records were not paired (Tail::pair)";
+    return FEM_ERR_STATE;
+  }
+  if (!names.quals || names.qual_hole) {
+    if (err) *err = "BAM records need the qualities on the device";
+    return FEM_ERR_STATE;
+  }
+  const uint32_t nr = m.last_nr + (paired ? m.n_resc : 0u);
+  const size_t r1 = (size_t)nr + 1;
+  for (hipEvent_t &e : m.ev)
+    if (!e) TAIL_TRY(hipEventCreate(&e));
+  TAIL_TRY(m.line_len.need(r1 * 8));
+  TAIL_TRY(m.line_off.need(r1 * 8));
+  TAIL_TRY(m.h_line_off.need(r1 * 8));
+  TAIL_TRY(m.h_ctl.need(32));
+  TAIL_TRY(m.bam_ctl.need(16));
+  size_t tmp = 0;
+  TAIL_TRY(rocprim::exclusive_scan(nullptr, tmp, m.line_len.as<unsigned long long>(), m.line_off.as<unsigned long long>(), 0ull, r1,
+                                   rocprim::plus<unsigned long long>(), stream));
+  TAIL_TRY(m.scan_tmp.need(std::max<size_t>(tmp, 16)));
+  SamParams p{};
+  p.n_records = nr, p.rec_begin = m.rec_begin.as<uint32_t>(), p.s_read = m.s_read.as<uint32_t>();
+  p.flag = m.flag.as<uint16_t>(), p.tid = m.tid.as<uint32_t>(), p.pos0 = m.pos0.as<uint32_t>(), p.nm = m.nm.as<uint8_t>();
+  p.cigar_off = m.cigar_off.as<uint32_t>(), p.cigar = m.cigar.as<uint32_t>(), p.md_off = m.md_off.as<uint32_t>(), p.md = m.md.as<uint8_t>();
+  p.bases = in.bases, p.read_off = in.read_off;
+  p.quals = names.quals, p.names = names.names, p.name_off = names.name_off, p.ref_names = names.ref_names, p.ref_name_off = names.ref_name_off;
+  p.line_len = m.line_len.as<unsigned long long>(), p.line_off = m.line_off.as<unsigned long long>();
+  p.asserted = m.ctl.as<uint32_t>() + 2;  // (ctl[2] is zero after a successful run())
+  if (paired) {
+    p.perm = m.perm.as<uint32_t>(), p.pflag = m.pflag.as<uint16_t>(), p.mtid = m.mtid.as<uint32_t>(), p.mpos0 = m.mpos0.as<uint32_t>();
+    p.tlen = m.tlen.as<int32_t>();
+  }
+  uint32_t *bad_name = m.bam_ctl.as<uint32_t>();
+  TAIL_TRY(hipMemsetAsync(bad_name, 0, 4, stream));
+  TAIL_TRY(hipEventRecord(m.ev[0], stream));
+  const dim3 len_grid(std::max<uint32_t>(1u, std::min<uint32_t>((nr + 256u) / 256u, (uint32_t)n_cu * 16u)));
+  if (paired) hipLaunchKernelGGL(bam_len_kernel<true>, len_grid, dim3(256), 0, stream, p, m.last_n, bad_name);
+  else hipLaunchKernelGGL(bam_len_kernel<false>, len_grid, dim3(256), 0, stream, p, m.last_n, bad_name);
+  TAIL_TRY(hipGetLastError());
+  TAIL_TRY(rocprim::exclusive_scan(m.scan_tmp.p, m.scan_tmp.cap, m.line_len.as<unsigned long long>(), m.line_off.as<unsigned long long>(), 0ull,
+                                   r1, rocprim::plus<unsigned long long>(), stream));
+  // the record offsets come home with the total: the member cuts are made here
+  TAIL_TRY(hipMemcpyAsync(m.h_line_off.p, m.line_off.p, r1 * 8, hipMemcpyDeviceToHost, stream));
+  TAIL_TRY(hipMemcpyAsync(m.h_ctl.as<uint32_t>() + 2, m.ctl.as<uint32_t>() + 2, 4, hipMemcpyDeviceToHost, stream));
+  TAIL_TRY(hipMemcpyAsync(m.h_ctl.as<uint32_t>() + 3, bad_name, 4, hipMemcpyDeviceToHost, stream));
+  TAIL_TRY(hipStreamSynchronize(stream));
+  if (m.h_ctl.as<uint32_t>()[3]) {
+    if (err) *err = "the batch holds a read name over 254 characters: not writable as BAM (l_read_name is one byte)";
+    return FEM_ERR_UNSUPPORTED;
+  }
+  const uint64_t total = m.h_line_off.as<uint64_t>()[nr];
+  TAIL_TRY(m.text.need(std::max<size_t>((size_t)total, 16)));
+  if (nr) {
+    p.text = m.text.as<uint8_t>();
+    hipLaunchKernelGGL(paired ? bam_write_kernel<true> : bam_write_kernel<false>, dim3((nr + 3u) / 4u), dim3(256), 0, stream, p);
+    TAIL_TRY(hipGetLastError());
+  }
+  TAIL_TRY(hipEventRecord(m.ev[1], stream));
+  femz::bgzf_cut(m.h_line_off.as<uint64_t>(), nr, total, &m.cuts);
+  uint64_t len = 0;
+  float ms_z = 0.f;
+  int rc = m.bgzf.compress(m.text.as<uint8_t>(), total, m.cuts, level, stream, &len, err, ms ? &ms_z : nullptr);
+  if (rc) return rc;
+  TAIL_TRY(m.h_text.need(std::max<size_t>((size_t)len, 1u << 20)));
+  if (!m.ev_text) TAIL_TRY(hipEventCreateWithFlags(&m.ev_text, hipEventDisableTiming));
+  {
+    std::unique_lock<std::mutex> turn;
+    if (gate) {
+      turn = std::unique_lock<std::mutex>(gate->mu);
+      if (gate->last && gate->last != m.ev_text) TAIL_TRY(hipEventSynchronize(gate->last));
+    }
+    if (len) TAIL_TRY(hipMemcpyAsync(m.h_text.p, m.bgzf.out(), (size_t)len, hipMemcpyDeviceToHost, stream));
+    TAIL_TRY(hipEventRecord(m.ev_text, stream));
+    if (gate) gate->last = m.ev_text;
+  }
+  if (wait) TAIL_TRY(hipStreamSynchronize(stream));
+  if (ms) {  // (compress() has waited for the stream: both spans are over)
+    float t = 0.f;
+    if (hipEventElapsedTime(&t, m.ev[0], m.ev[1]) == hipSuccess) ms[0] += t;
+    ms[1] += ms_z;
+  }
+  out->data = m.h_text.as<uint8_t>(), out->len = len, out->raw_len = total;
+  out->n_blocks = m.cuts.empty() ? 0 : m.cuts.size() - 1;
+  out->n_asserted = m.h_ctl.as<uint32_t>()[2];
   return FEM_OK;
 }
 

@@ -68,6 +68,13 @@ struct SamOutput {  // pinned host memory owned by the Tail object, valid until 
   const uint64_t *qual_at;  // qual_hole: per READ, where in `text` its QUAL field starts (~0: the read has no record); else nullptr
 };
 
+// ---- BAM on the device: the same lines as BAM records, BGZF-compressed (fem_bgzf.hip) ----
+struct BamOutput {  // pinned host memory owned by the Tail object (the SAM text's), valid until its next sam() / bam()
+  const uint8_t *data;  // whole BGZF members: no header, no EOF block
+  uint64_t len, raw_len, n_blocks;
+  uint64_t n_asserted;
+};
+
 // ---- pair mode: the reads of the last run() are n / 2 read pairs, read i and read n / 2 + i the two mates of pair i ----
 struct PairOutput {  // pinned host memory owned by the Tail object, valid until its next pair_fetch()
   uint64_t n_pairs, n_records, n_proper;
@@ -133,6 +140,11 @@ class Tail {
   // paired = true: the lines in the order of the last pair() with its mate columns (the records of both stay on the device).
   int sam(const TailInput &in, const SamInput &names, hipStream_t stream, int n_cu, SamOutput *out, std::string *err, double *ms,
           bool wait = true, TextGate *gate = nullptr, bool paired = false);
+  // The same lines as BAM records (names.quals must be set: no qual_hole), compressed at `level` (0 or 1) into BGZF members.
+  // ms (optional): ms[0] += the record kernels' device time, ms[1] += the BGZF kernels'.  wait, gate, paired: as sam().
+  // FEM_ERR_UNSUPPORTED for a read name over 254 characters.
+  int bam(const TailInput &in, const SamInput &names, int level, hipStream_t stream, int n_cu, BamOutput *out, std::string *err,
+          double *ms, bool wait = true, TextGate *gate = nullptr, bool paired = false);
   // Pairs the records of the last run() (pair_kernel): output order, FLAG, mate columns and TLEN of every line, the proper-pair
   // count.  Asynchronous on `stream`; n_proper() is valid once the stream has been synchronised (sam() does).
   // rescue (optional): mate rescue first (the rescue kernels), the kept rescued records appended behind run()'s; pair() then

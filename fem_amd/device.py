@@ -21,6 +21,7 @@ ABI_SYMBOLS = [
     "fem_dev_allreduce_stats",
     "fem_dev_set_pairs", "fem_dev_fetch_pairs", "fem_dev_pair_count",
     "fem_dev_set_rescue", "fem_dev_rescue_count",
+    "fem_dev_fetch_bam", "fem_dev_fetch_bam_nowait", "fem_dev_bam_wait", "fem_dev_bgzf_compress",
 ]
 
 
@@ -58,6 +59,11 @@ class _BatchRecords(C.Structure):
 class _BatchSam(C.Structure):
     _fields_ = [("text", C.c_void_p), ("len", C.c_uint64), ("n_reads", C.c_uint64), ("n_records", C.c_uint64),
                 ("n_asserted", C.c_uint64), ("stats", C.c_uint64 * 5)]
+
+
+class _BatchBam(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("len", C.c_uint64), ("raw_len", C.c_uint64), ("n_blocks", C.c_uint64),
+                ("n_records", C.c_uint64), ("n_asserted", C.c_uint64), ("stats", C.c_uint64 * 5)]
 
 
 class _PairParams(C.Structure):
@@ -145,6 +151,11 @@ def load_hip():
     if hasattr(L, "fem_dev_set_rescue"):
         L.fem_dev_set_rescue.argtypes = [vp, C.c_int, C.POINTER(_RescueParams)]
         L.fem_dev_rescue_count.argtypes = [vp, C.c_int, C.POINTER(u64)]
+    if hasattr(L, "fem_dev_fetch_bam"):
+        L.fem_dev_fetch_bam.argtypes = [vp, C.c_int, C.c_int, C.POINTER(_BatchBam)]
+        L.fem_dev_fetch_bam_nowait.argtypes = [vp, C.c_int, C.c_int, C.POINTER(_BatchBam)]
+        L.fem_dev_bam_wait.argtypes = [vp, C.c_int]
+        L.fem_dev_bgzf_compress.argtypes = [vp, vp, u64, C.c_int, vp, u64, C.POINTER(u64)]
     L.fem_device_numa.argtypes = [C.c_int, C.POINTER(C.c_int32), C.c_char_p, u64]
     L.fem_bind_thread_near_device.argtypes = [C.c_int]
     _HIP = L
@@ -506,6 +517,28 @@ class Device:
                 raise FemError("fem_sam_fill_quals failed (%d)" % rc)
         text = C.string_at(r.text, r.len) if r.len else b""
         return text, int(r.n_records), int(r.n_asserted), np.array(list(r.stats), dtype=np.uint64)
+
+    def fetch_bam(self, slot=0, level=1, nowait=False):
+        """(BGZF members of the slot's batch as BAM records (bytes), raw_len, n_blocks, n_records, n_asserted, stats) — the
+        lines of fetch_sam, encoded and compressed on the device.  nowait: through fem_dev_fetch_bam_nowait + fem_dev_bam_wait."""
+        r = _BatchBam()
+        if nowait:
+            self._check(self._L.fem_dev_fetch_bam_nowait(self._h, slot, int(level), C.byref(r)))
+            self._check(self._L.fem_dev_bam_wait(self._h, slot))
+        else:
+            self._check(self._L.fem_dev_fetch_bam(self._h, slot, int(level), C.byref(r)))
+        data = C.string_at(r.data, r.len) if r.len else b""
+        return (data, int(r.raw_len), int(r.n_blocks), int(r.n_records), int(r.n_asserted),
+                np.array(list(r.stats), dtype=np.uint64))
+
+    def bgzf_compress(self, data, level=1):
+        """fem_dev_bgzf_compress: BGZF members (bytes, no EOF block) of `data`, compressed on the device."""
+        raw = bytes(data)
+        cap = 65536 * (len(raw) // 65280 + 1)
+        out = C.create_string_buffer(cap)
+        n = C.c_uint64()
+        self._check(self._L.fem_dev_bgzf_compress(self._h, raw, len(raw), int(level), out, cap, C.byref(n)))
+        return out.raw[:n.value]
 
     def set_pairs(self, min_insert=0, max_insert=500, slot=0):
         """fem_dev_set_pairs: the slot's batches are read pairs (read i and read n/2 + i); min_insert=None: single-end again."""

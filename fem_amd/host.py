@@ -81,6 +81,7 @@ def lib():
         L.fem_tail_sam.argtypes = [i32, C.POINTER(TailRef), C.POINTER(SeqSet), C.POINTER(TailInput), C.c_int,
                                    C.POINTER(vp), C.POINTER(u64)]
         L.fem_sam_header.argtypes = [C.POINTER(TailRef), C.POINTER(vp), C.POINTER(u64)]
+        L.fem_bam_header.argtypes = [C.POINTER(TailRef), C.POINTER(vp), C.POINTER(u64)]
         L.fem_sam_fill_quals.argtypes = [vp, u64, vp, u64, vp, vp, C.c_uint32, C.c_int]
         L.fem_synth_reference.argtypes = [u64, C.c_uint32, vp, vp, vp, C.c_int]
         L.fem_synth_reads.argtypes = [u64, vp, vp, vp, C.c_uint32, u64, u64, C.c_uint32, i32, vp, C.c_int]
@@ -523,6 +524,19 @@ def sam_header(ref):
     s = _copy(p.value, n.value, np.uint8).tobytes().decode()
     lib().free(p)
     return s
+
+
+def bam_header(ref):
+    """fem_bam_header: the uncompressed BAM header (bytes) of a TailReference; ValueError for a sequence of 2^31 bases or more."""
+    p, n = C.c_void_p(), C.c_uint64()
+    rc = lib().fem_bam_header(C.byref(ref.c), C.byref(p), C.byref(n))
+    if rc == -5:
+        raise ValueError("a reference sequence of 2^31 bases or more cannot be written as BAM")
+    if rc:
+        raise RuntimeError("fem_bam_header failed (%d)" % rc)
+    raw = C.string_at(p.value, n.value)
+    lib().free(p)
+    return raw
 
 
 def tail_sam(e, ref, names, read_bases, read_off, quals, cand_begin, cand_count, cand, ed, end, threads=1):

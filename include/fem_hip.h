@@ -268,6 +268,31 @@ int fem_dev_fetch_sam(fem_dev *h, int slot, fem_batch_sam *out);
 int fem_dev_fetch_sam_nowait(fem_dev *h, int slot, fem_batch_sam *out);
 int fem_dev_sam_wait(fem_dev *h, int slot);
 
+/* ---- BAM output (new: the reference writes SAM only) ----
+ * fem_dev_fetch_bam: the lines fem_dev_fetch_sam would render, as BAM records (SAM/BAM specification 4.2), compressed on the
+ *   device into BGZF members (4.1) of whole records, each cut greedily at 65280 input bytes.  data holds the members only: no
+ *   BAM header (fem_bam_header of libfemhost, compressed with fem_dev_bgzf_compress), no EOF block.  raw_len = bytes of the
+ *   uncompressed records, n_blocks = members.  level 1: deflate with dynamic Huffman codes, a member stored where that is not
+ *   larger; level 0: stored members.  n_records, n_asserted and stats are fem_dev_fetch_sam's.  Lifetime, threads, pair mode
+ *   and rescue as fem_dev_fetch_sam / _nowait / fem_dev_sam_wait (the data shares the text's pinned memory).
+ *   Encoding: refID pos = the record's tid pos0; l_read_name = name + 1; MAPQ 255; bin = reg2bin(pos0, end0) with end0 = pos0 +
+ *   the M/D/N/=/X lengths (pos0 + 1 for none); CIGAR as the device's words; FLAG & 0x7FFF (0x8000 still counted in n_asserted);
+ *   l_seq = L where the text prints SEQ, else 0; next_refID next_pos tlen = -1 -1 0, or the pair's mate columns; SEQ in 4-bit
+ *   codes of the letters the text prints; QUAL - 33; aux NM:C then MD:Z.
+ *   FEM_ERR_STATE after fem_dev_commit_names_stage (the qualities must be on the device); FEM_ERR_UNSUPPORTED for a read name
+ *   over 254 characters; FEM_ERR_INVALID for a level other than 0 or 1.
+ * fem_dev_bgzf_compress: any n bytes into BGZF members cut every 65280 bytes (n = 0: nothing, *out_len = 0); FEM_ERR_INVALID
+ *   when they do not fit in out_cap (65536 bytes per started 65280 always do). */
+typedef struct {
+  const uint8_t *data;
+  uint64_t len, raw_len, n_blocks, n_records, n_asserted;
+  uint64_t stats[5];
+} fem_batch_bam;
+int fem_dev_fetch_bam(fem_dev *h, int slot, int level, fem_batch_bam *out);
+int fem_dev_fetch_bam_nowait(fem_dev *h, int slot, int level, fem_batch_bam *out);
+int fem_dev_bam_wait(fem_dev *h, int slot);
+int fem_dev_bgzf_compress(fem_dev *h, const void *in, uint64_t n, int level, void *out, uint64_t out_cap, uint64_t *out_len);
+
 /* ---- read pairs (new: the reference maps single-end reads only) ----
  * fem_dev_set_pairs: the slot's batches are read pairs from now on: read i and read n_reads/2 + i are the two mates of pair i
  *   (mate 1's reads first, then mate 2's, in the same order).  NULL: single-end again.  FEM_ERR_INVALID for min_insert < 0,
@@ -357,7 +382,8 @@ int fem_dev_index_info(const fem_dev *h, char *buf, uint64_t cap);
  * 8 = seed selection kernel of the dense-index path (it runs beside the previous batch's kernel 0: its event time is
  * what it takes there, not what it would take alone);
  * 9 = the pairing kernel of a paired fem_dev_fetch_sam (fem_dev_set_pairs);
- * 10 = the mate rescue kernels in front of it (fem_dev_set_rescue; their host waits included). */
+ * 10 = the mate rescue kernels in front of it (fem_dev_set_rescue; their host waits included);
+ * of fem_dev_fetch_bam: 11 = the BAM record kernels, 12 = the BGZF kernels. */
 int fem_dev_set_timing(fem_dev *h, int on);
 int fem_dev_reset_timing(fem_dev *h);
 int fem_dev_kernel_time(fem_dev *h, int kernel, double *ms_total, uint64_t *launches);
