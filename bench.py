@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py — mapped Mreads/s of the FEM hot path (seeding + candidate filter + banded Myers) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does what the headline needs and nothing else: it sets up the headline workload (reference, device index, the
+slots' batches), primes and warms up the pipeline, times the K steps, writes --dump-outputs and prints the line.  `--full`
+adds everything below that is measured or checked beside the headline: the comparison forms, the pipeline's self-check
+against the oracle, the resident-kernel replays (`kernel_only_mreads`, `kernel_ms_alone`, `roofline_by_kernel`), the
+device bandwidths, the other workloads, the CPU baselines and the end-to-end CLI runs.
 
 N > 1: bench.py starts its N ranks itself (children made before anything touches the GPU), or runs as one rank when
 it is already under torch.distributed.run (RANK / WORLD_SIZE in the environment).  One rank per GPU.
@@ -13,15 +19,15 @@ One step = one batch of `--batch` (2.5 M) synthetic reads through the DEVICE PIP
 with four batches in flight on four slots and a different batch in every slot (fresh H2D and D2H every step).  No host
 work per base happens inside a step, so N ranks need no host cores to speak of.  The same pipeline fed by
 fem_dev_map_batch_submit (a caller-owned batch of characters, packed by the library's host threads) and by the zero-copy
-character form are measured next to it at N = 1 (`stage_reads_mreads`, `zero_copy_ascii_mreads`).
-After the timed steps the pipeline checks itself (`config.pipeline_check`): every repeat of a slot's batch gave the same
-five counters, and — at N = 1, where the oracle's index exists — one slot's candidates / edit distances / end offsets of
-a 100 k-read prefix, fetched out of the running four-deep pipeline, equal the oracle's.
+character form are measured next to it at N = 1 (`stage_reads_mreads`, `zero_copy_ascii_mreads`; --full).
+After the timed steps of a --full run the pipeline checks itself (`config.pipeline_check`): every repeat of a slot's batch
+gave the same five counters, and — at N = 1, where the oracle's index exists — one slot's candidates / edit distances /
+end offsets of a 100 k-read prefix, fetched out of the running four-deep pipeline, equal the oracle's.
 `value`, `ms_per_step` and `roofline` all come from the SAME workload, the headline one: C3 (100 bp, e=3, 3 Gbp
 reference: the HBM-resident configuration SURVEY.md 8d calls bandwidth-relevant; 20 steps x 2.5 M = BASELINE's 50 M
 reads).  `value` is the MEDIAN of `--reps` (3) timed runs of exactly K steps each, `ms_per_step` and the kernel times are
 that run's; `spread` has all of them (`value_is_repetition`: which one).  C2 (5 Mbp: the index is cache-resident, the pipeline host- and link-balanced) and C5 (150 bp,
-e=7) are measured next to it at N = 1 (`pipeline_by_workload`, `roofline_by_workload`).
+e=7) are measured next to it at N = 1 with --full (`pipeline_by_workload`, `roofline_by_workload`).
 
 `roofline` is the dominant kernel of the headline workload — seed_join_kernel — with ITS algorithmic bytes (8 P: the
 occurrence entries of the selected seeds) over ITS mean launch time inside the timed pipeline (HIP events on its stream;
@@ -33,8 +39,8 @@ as in the pipeline, one batch's selection runs beside the previous batch's join)
 
 Workloads (BASELINE.json `configs`):
     c3   24 x 125 Mbp reference, 100 bp, e=3       the headline: `value`, all N
-    c2   5 Mbp reference, 100 bp reads, e=3        N = 1 runs it too
-    c5   same reference as c3, 150 bp, e=7         N = 1 runs it too (20 steps x 2.5 M = BASELINE's 50 M)
+    c2   5 Mbp reference, 100 bp reads, e=3        N = 1 --full runs it too
+    c5   same reference as c3, 150 bp, e=7         N = 1 --full runs it too (20 steps x 2.5 M = BASELINE's 50 M)
 Rank 0 prints ONE JSON line.
 """
 import argparse
@@ -186,9 +192,11 @@ def dump_outputs(res, out_dir):
     return {"dir": out_dir, "strands": int(len(strands)), "of_strands": n2, "candidates": int(len(sel)), "sample_seed": DUMP_SEED}
 
 
-def run_workload(key, dev, data, rk, steps, warmup, batch, torch, dist, red_dev, threads, reps=1, compare_forms=False, dump_dir=None):
-    """Pipeline measurement + resident-kernel replay of one workload on this rank's device.  `data` = (text, off, lens).
-    dump_dir: write the last timed step's result there (dump_outputs)."""
+def run_workload(key, dev, data, rk, steps, warmup, batch, torch, dist, red_dev, threads, reps=1, compare_forms=False, dump_dir=None,
+                 full=False):
+    """Pipeline measurement of one workload on this rank's device.  `data` = (text, off, lens).
+    dump_dir: write the last timed step's result there (dump_outputs).  full: then the pipeline's self-check, the comparison
+    forms (compare_forms) and the resident-kernel replays."""
     import numpy as np
     from fem_amd import host
     w = WORKLOADS[key]
@@ -353,22 +361,23 @@ def run_workload(key, dev, data, rk, steps, warmup, batch, torch, dist, red_dev,
     elapsed, kt = runs[mid]
     host_first = host_reps[mid]
 
-    # ---- the pipeline checks itself (untimed): the same four-deep pipeline once more round the slots, with a copy of slot
-    #      0's full result taken out of it; every repeat of a slot's batch, timed steps included, must have given the same
-    #      five counters ----
-    keep[0] = True
-    pipeline(2 * N_SLOTS)
-    repeats_identical = all(all(np.array_equal(x, sl[0]) for x in sl) for sl in seen if sl)
-    n_repeats = [len(sl) for sl in seen]
-    pipe_check = {"repeats_identical": bool(repeats_identical), "batches_retired_per_slot": n_repeats,
-                  "what": "every retired batch of a slot (priming, warm-up, timed steps, this check) gave the same five counters"}
-    if rk.dist:  # every rank's verdict
-        ok_t = torch.tensor([1 if repeats_identical else 0], dtype=torch.int64, device=red_dev)
-        dist.all_reduce(ok_t, op=dist.ReduceOp.MIN)
-        pipe_check["repeats_identical"] = bool(ok_t.item())
-    pipe_check["_kept"] = kept.get(0)
-    pipe_check["_first_read"] = lo
-    pipe_check["_slot0_stats"] = seen[0][0] if seen[0] else None
+    if full:
+        # ---- the pipeline checks itself (untimed): the same four-deep pipeline once more round the slots, with a copy of slot
+        #      0's full result taken out of it; every repeat of a slot's batch, timed steps included, must have given the same
+        #      five counters ----
+        keep[0] = True
+        pipeline(2 * N_SLOTS)
+        repeats_identical = all(all(np.array_equal(x, sl[0]) for x in sl) for sl in seen if sl)
+        n_repeats = [len(sl) for sl in seen]
+        pipe_check = {"repeats_identical": bool(repeats_identical), "batches_retired_per_slot": n_repeats,
+                      "what": "every retired batch of a slot (priming, warm-up, timed steps, this check) gave the same five counters"}
+        if rk.dist:  # every rank's verdict
+            ok_t = torch.tensor([1 if repeats_identical else 0], dtype=torch.int64, device=red_dev)
+            dist.all_reduce(ok_t, op=dist.ReduceOp.MIN)
+            pipe_check["repeats_identical"] = bool(ok_t.item())
+        pipe_check["_kept"] = kept.get(0)
+        pipe_check["_first_read"] = lo
+        pipe_check["_slot0_stats"] = seen[0][0] if seen[0] else None
 
     stage_reads_rate = zero_copy = None
     h2d_zero_copy = 0
@@ -409,29 +418,30 @@ def run_workload(key, dev, data, rk, steps, warmup, batch, torch, dist, red_dev,
         h2d_zero_copy = dev.stage_info(0)[0]
     batches.clear()
 
-    # the kernels alone on batches already resident in HBM (every slot as staged by the pipeline steps above), the four
-    # slots in rotation: as in the pipeline, a batch's seed selection runs beside the previous batch's join
-    form[0] = "resident"
-    n_rep = max(8, min(steps, 12))
-    pipeline(N_SLOTS)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    pipeline(n_rep)
-    torch.cuda.synchronize()
-    kernel_only = batch * n_rep / (time.perf_counter() - t1) / 1e6
-    # ... and one batch at a time (nothing beside anything): every kernel's time when it has the chip to itself
-    dev.set_timing(True)
-    dev.reset_timing()
-    for _ in range(3):
-        dev.map_staged(e=e, a=a, k=k, step=step, slot=0)
-        dev.fetch_stats(slot=0)
-    torch.cuda.synchronize()
-    alone = {name: dev.kernel_time(kid) for name, kid in KERNEL_IDS.items()}
-    dev.set_timing(False)
-    # (the comparison forms and the resident replay mapped the same four batches again: their counters count too)
-    local_ok = all(all(np.array_equal(x, sl[0]) for x in sl) for sl in seen if sl)
-    pipe_check["repeats_identical"] = bool(pipe_check["repeats_identical"] and local_ok)
-    pipe_check["batches_retired_per_slot"] = [len(sl) for sl in seen]
+    if full:
+        # the kernels alone on batches already resident in HBM (every slot as staged by the pipeline steps above), the four
+        # slots in rotation: as in the pipeline, a batch's seed selection runs beside the previous batch's join
+        form[0] = "resident"
+        n_rep = max(8, min(steps, 12))
+        pipeline(N_SLOTS)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        pipeline(n_rep)
+        torch.cuda.synchronize()
+        kernel_only = batch * n_rep / (time.perf_counter() - t1) / 1e6
+        # ... and one batch at a time (nothing beside anything): every kernel's time when it has the chip to itself
+        dev.set_timing(True)
+        dev.reset_timing()
+        for _ in range(3):
+            dev.map_staged(e=e, a=a, k=k, step=step, slot=0)
+            dev.fetch_stats(slot=0)
+        torch.cuda.synchronize()
+        alone = {name: dev.kernel_time(kid) for name, kid in KERNEL_IDS.items()}
+        dev.set_timing(False)
+        # (the comparison forms and the resident replay mapped the same four batches again: their counters count too)
+        local_ok = all(all(np.array_equal(x, sl[0]) for x in sl) for sl in seen if sl)
+        pipe_check["repeats_identical"] = bool(pipe_check["repeats_identical"] and local_ok)
+        pipe_check["batches_retired_per_slot"] = [len(sl) for sl in seen]
 
     seed_name = dev.seed_kernel(e=e, a=a, k=k, step=step)
 
@@ -443,7 +453,6 @@ def run_workload(key, dev, data, rk, steps, warmup, batch, torch, dist, red_dev,
         return out
 
     per_launch = {n_: (v[0], v[1] / steps) for n_, v in per_launch_of(kt).items()}
-    alone_ms = {n_: v[0] for n_, v in per_launch_of(alone).items()}
     # algorithmic bytes: B = N*L + 16*(L-k+1)*N + 8*P + (L+2e)*C + 16*M, from the path's own counters
     N, P, Cn, M = batch, int(last_stats[2]), int(last_stats[3]), int(last_stats[4])
     S = L - k + 1
@@ -475,10 +484,6 @@ def run_workload(key, dev, data, rk, steps, warmup, batch, torch, dist, red_dev,
         impl = 4 * P + 8 * 6 * R * N + 8 * N
         roof["implementation_bytes_per_launch"] = int(impl / max(dom_launches, 1.0))
         roof["implementation_gbs"] = round(impl / max(dom_launches, 1.0) / (dom_ms * 1e-3) / 1e9, 2) if dom_ms > 0 else 0.0
-    by_kernel = {dominant: roof}
-    for n_ in per_launch:
-        if n_ in bytes_of and n_ != dominant and n_ in alone_ms and n_ != "seed_filter_kernel":
-            by_kernel[n_] = roof_of(n_, alone_ms[n_], bytes_of[n_], "launch duration with the chip to itself (resident replay, one batch at a time)")
     ms_step = elapsed * 1e3 / steps
     step_roof = roof_of("whole step: every kernel of one batch", ms_step * rk.world, (seed_bytes + verify_bytes) * rk.world,
                         "driver-visible ms_per_step (copies, gaps, fill and drain included)")
@@ -511,17 +516,17 @@ def run_workload(key, dev, data, rk, steps, warmup, batch, torch, dist, red_dev,
             log("could not read %s: %s" % (tpath, ex))
     values = [rk.world * batch * steps / r[0] / 1e6 for r in runs]
     value = values[mid]
-    return {
+    res = {
         "workload": w["name"], "value": round(value, 3), "ms_per_step": round(ms_step, 3), "steps": steps,
         "spread": {"reps": len(values), "min": round(min(values), 3), "median": round(sorted(values)[len(values) // 2], 3),
                    "max": round(max(values), 3), "values": [round(v, 3) for v in values], "value_is_repetition": mid},
         "reads_per_step_per_gpu": batch, "read_len": L, "e": e, "a": a, "k": k, "step": step,
-        "kernel_only_mreads": round(kernel_only, 3), "seed_kernel": seed_name, "index_tables": dev.index_info(),
+        "seed_kernel": seed_name, "index_tables": dev.index_info(),
         "h2d_bytes_per_step": int(h2d_bytes), "h2d_packed": bool(sent_packed), "d2h_bytes_per_step": d2h_timed,
         "fetch_form": "fem_dev_fetch_packed" if packed_fetch else "fem_dev_fetch",
         "stage_reads_mreads": None if stage_reads_rate is None else round(stage_reads_rate, 3),
         "zero_copy_ascii_mreads": None if zero_copy is None else round(zero_copy, 3), "zero_copy_h2d_bytes_per_step": int(h2d_zero_copy),
-        "priming_steps": priming, "pipeline_check": pipe_check, "dumped_outputs": dumped,
+        "priming_steps": priming, "dumped_outputs": dumped,
         "distinct_reads": "%d distinct reads per GPU (%d slots x %d), each slot's batch mapped again every %d steps"
                           % (N_SLOTS * batch, N_SLOTS, batch, N_SLOTS),
         # what this rank's host thread does per step: the staging call (2-bit packing of the batch on the library's threads,
@@ -538,9 +543,17 @@ def run_workload(key, dev, data, rk, steps, warmup, batch, torch, dist, red_dev,
         "algorithmic_bytes_per_step_per_gpu": seed_bytes + verify_bytes,
         "kernel_ms_per_launch": {n_: round(v[0], 4) for n_, v in per_launch.items()},
         "kernel_launches_per_step": {n_: round(v[1], 2) for n_, v in per_launch.items()},
-        "kernel_ms_alone": {n_: round(v, 4) for n_, v in alone_ms.items()},
-        "roofline": roof, "roofline_step": step_roof, "roofline_by_kernel": by_kernel,
+        "roofline": roof, "roofline_step": step_roof,
     }
+    if full:
+        alone_ms = {n_: v[0] for n_, v in per_launch_of(alone).items()}
+        by_kernel = {dominant: roof}
+        for n_ in per_launch:
+            if n_ in bytes_of and n_ != dominant and n_ in alone_ms and n_ != "seed_filter_kernel":
+                by_kernel[n_] = roof_of(n_, alone_ms[n_], bytes_of[n_], "launch duration with the chip to itself (resident replay, one batch at a time)")
+        res.update(kernel_only_mreads=round(kernel_only, 3), pipeline_check=pipe_check,
+                   kernel_ms_alone={n_: round(v, 4) for n_, v in alone_ms.items()}, roofline_by_kernel=by_kernel)
+    return res
 
 
 def profile_replay(key, dev, data, n, batch, torch, threads):
@@ -757,6 +770,11 @@ def main():
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS), help="the workload `value` is measured on")
     ap.add_argument("--reps", type=int, default=3, help="timed runs of exactly --steps steps each (value = their median; spread = all)")
     ap.add_argument("--batch", type=int, default=2_500_000, help="reads per step and GPU")
+    ap.add_argument("--full", action="store_true", help="measure and check everything beside the headline as well: the comparison "
+                                                        "forms, the pipeline's self-check, the resident-kernel replays, the device "
+                                                        "bandwidths, the --extra workloads, the CPU baselines, the end-to-end CLI runs "
+                                                        "(--extra, --extra-steps, --cpu-sample*, --e2e-reads*, --no-cpu, --no-compare "
+                                                        "and --no-e2e choose among them)")
     ap.add_argument("--extra", default="auto", help="comma list of further workloads measured on rank 0 when N = 1 "
                                                     "(auto = c5,c3r,c2 next to c3; none)")
     ap.add_argument("--extra-steps", type=int, default=20)
@@ -777,6 +795,11 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0 or args.batch < 1:
         sys.exit("bench.py: --steps >= 1, --warmup >= 0, --batch >= 1")
+    if not args.full:
+        if args.extra not in ("auto", "none"):
+            sys.exit("bench.py: --extra workloads are measured by --full runs")
+        # a plain run measures the headline alone: set-up, warm-up, the timed steps, --dump-outputs and the line
+        args.extra, args.no_cpu, args.no_compare, args.no_e2e = "none", True, True, True
     if "RANK" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args))
     if args.profile_replay > 0:
@@ -870,7 +893,7 @@ def main():
             data_cache[ref_key] = (text, off, lens, n_occ)
             log("rank %d %s: reference %d bp in %d sequences, index %d entries built on device in %.1fs"
                 % (rk.rank, key, int(lens.astype(np.uint64).sum()), len(lens), n_occ, time.time() - t0))
-            if not bw:
+            if args.full and not bw:
                 bw = {"device_copy_gbs": round(dev.copy_bandwidth(1 << 30, 10), 1), "pinned_h2d_gbs": round(dev.h2d_bandwidth(1 << 28, 8), 1)}
         text, off, lens, n_occ = data_cache[ref_key]
         steps, warmup = (args.steps, args.warmup) if key == args.workload else (args.extra_steps, N_SLOTS + 1)  # (every slot warm)
@@ -883,10 +906,11 @@ def main():
         res = run_workload(key, dev, (text, off, lens), rk, steps, warmup, args.batch, torch, dist, red_dev, gen_threads,
                            reps=1 if "repeats" in w else args.reps,
                            compare_forms=None if args.no_compare or "repeats" in w else ("all" if rk.world == 1 else "stage_reads"),
-                           dump_dir=args.dump_outputs if key == args.workload and rk.rank == 0 else None)
+                           dump_dir=args.dump_outputs if key == args.workload and rk.rank == 0 else None, full=args.full)
         res["index_entries"] = n_occ
         results[key] = res
-        log("rank %d %s: pipeline %.1f Mreads/s, kernels only %.1f, %s" % (rk.rank, key, res["value"], res["kernel_only_mreads"], res["kernel_ms_per_launch"]))
+        log("rank %d %s: pipeline %.1f Mreads/s%s, %s" % (rk.rank, key, res["value"], ", kernels only %.1f" % res["kernel_only_mreads"]
+                                                         if args.full else "", res["kernel_ms_per_launch"]))
 
     cpu_c3_now()
     if rk.rank != 0:
@@ -901,7 +925,7 @@ def main():
         "value": head["value"], "unit": "Mreads/s", "n_gpus": rk.world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": head["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         # (round 4 changed what `value` is fed by — see config.value_is; the round-3 form, the library packing the caller's
-        #  characters on host threads, is pipeline_by_workload.*.stage_reads_mreads, measured at every N)
+        #  characters on host threads, is pipeline_by_workload.*.stage_reads_mreads, measured at every N by --full runs)
         "value_form": "packed_commit", "value_stage_reads_form": head.get("stage_reads_mreads"),
         "dtype": "u32/u64 integer + 32-bit Myers bit-vectors", "data": "synthetic", "spread": head["spread"],
         "config": dict({k_: v_ for k_, v_ in head.items() if k_ not in ("value", "ms_per_step", "steps", "roofline", "roofline_step",
@@ -910,18 +934,21 @@ def main():
                                 "writes it) -> fem_dev_commit_stage_packed (H2D, expansion) -> kernels -> D2H of fem_batch_result, %d batches "
                                 "in flight, a different batch per slot, fresh H2D and D2H every step; no host work per base; the median of %d timed "
                                 "runs of exactly %d steps each (spread.values)" % (DEPTH, max(1, args.reps), args.steps),
-                       parallelism="reads sharded x%d, index replicated" % rk.world, bandwidths=bw),
+                       parallelism="reads sharded x%d, index replicated" % rk.world),
         "roofline": dict(head["roofline"], workload=args.workload),
         "roofline_step": dict(head["roofline_step"], workload=args.workload),
-        "roofline_by_kernel": head["roofline_by_kernel"],
-        "roofline_by_workload": {k_: {"dominant_kernel": v_["roofline"], "step": v_["roofline_step"]} for k_, v_ in results.items()},
-        "pipeline_by_workload": {k_: {x: v_[x] for x in ("value", "ms_per_step", "steps", "kernel_only_mreads", "seed_kernel", "index_tables",
-                                                           "reads_per_step_per_gpu", "kernel_ms_per_launch", "kernel_ms_alone", "counters_last_step_per_gpu",
-                                                           "algorithmic_bytes_per_step_per_gpu", "h2d_bytes_per_step", "h2d_packed", "d2h_bytes_per_step", "fetch_form",
-                                                           "stage_reads_mreads", "zero_copy_ascii_mreads", "zero_copy_h2d_bytes_per_step", "priming_steps",
-                                                           "host_ms_per_step", "spread", "pipeline_check")}
-                                 for k_, v_ in results.items()},
     }
+    if args.full:
+        out["config"]["bandwidths"] = bw
+        out.update({
+            "roofline_by_kernel": head["roofline_by_kernel"],
+            "roofline_by_workload": {k_: {"dominant_kernel": v_["roofline"], "step": v_["roofline_step"]} for k_, v_ in results.items()},
+            "pipeline_by_workload": {k_: {x: v_[x] for x in ("value", "ms_per_step", "steps", "kernel_only_mreads", "seed_kernel", "index_tables",
+                                                               "reads_per_step_per_gpu", "kernel_ms_per_launch", "kernel_ms_alone", "counters_last_step_per_gpu",
+                                                               "algorithmic_bytes_per_step_per_gpu", "h2d_bytes_per_step", "h2d_packed", "d2h_bytes_per_step", "fetch_form",
+                                                               "stage_reads_mreads", "zero_copy_ascii_mreads", "zero_copy_h2d_bytes_per_step", "priming_steps",
+                                                               "host_ms_per_step", "spread", "pipeline_check")}
+                                     for k_, v_ in results.items()}})
     if cpu_c3[0] is not None:
         out["cpu_baseline"] = cpu_c3[0]
     c2_data = None
@@ -947,11 +974,12 @@ def main():
             out["e2e_cli"] = e2e_cli(WORKLOADS["c2"], c2_data, args.e2e_reads, threads)
         except Exception as ex:
             out["e2e_cli"] = {"error": repr(ex)}
-    for v_ in results.values():
-        for k_ in [k_ for k_ in v_["pipeline_check"] if k_.startswith("_")]:
-            del v_["pipeline_check"][k_]
-    pc = head["pipeline_check"]
-    out["counters_match_pipeline"] = bool(pc["repeats_identical"] and (pc.get("prefix_vs_oracle") or {"equal_to_oracle": True})["equal_to_oracle"])
+    if args.full:
+        for v_ in results.values():
+            for k_ in [k_ for k_ in v_["pipeline_check"] if k_.startswith("_")]:
+                del v_["pipeline_check"][k_]
+        pc = head["pipeline_check"]
+        out["counters_match_pipeline"] = bool(pc["repeats_identical"] and (pc.get("prefix_vs_oracle") or {"equal_to_oracle": True})["equal_to_oracle"])
     if e2e_c3[0] is not None:
         out["e2e_cli_c3"] = e2e_c3[0]
     out["config"]["counter_reduction"] = ("torch.distributed all_reduce, backend %s, %d rank(s)" % (backend, rk.world)) if rk.dist else "single process: none"

@@ -22,8 +22,8 @@ def _run(args, env=None):
 
 
 def test_single_gpu_line_has_the_contract_fields():
-    d = _run(["--workload", "c2", "--steps", "3", "--warmup", "2", "--batch", "200000", "--extra", "none", "--cpu-sample", "50000", "--e2e-reads", "100000",
-              "--reps", "2"])
+    d = _run(["--full", "--workload", "c2", "--steps", "3", "--warmup", "2", "--batch", "200000", "--extra", "none", "--cpu-sample", "50000",
+              "--e2e-reads", "100000", "--reps", "2"])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "roofline_step", "spread", "cpu_baseline"):
         assert key in d, key
@@ -53,9 +53,27 @@ def test_single_gpu_line_has_the_contract_fields():
     assert c["host_ms_per_step"]["stage_call"] >= 0 and "stage_reads_form" in c["host_ms_per_step"]
 
 
+def test_plain_line_measures_the_headline_alone():
+    # without --full: set-up, warm-up, the timed steps and the line; nothing that takes a run of its own or checks beside them
+    d = _run(["--workload", "c2", "--steps", "3", "--warmup", "2", "--batch", "200000", "--reps", "2"])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "spread", "roofline", "roofline_step"):
+        assert key in d, key
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["unit"] == "Mreads/s" and d["value"] > 0
+    assert abs(d["value"] - 200000 * 3 / (d["ms_per_step"] * 3e-3) / 1e6) < 0.01 * d["value"]
+    assert d["roofline"]["workload"] == "c2" and d["roofline"]["avg_launch_ms"] <= d["ms_per_step"]
+    c = d["config"]
+    assert c["counters"]["reads"] == 3 * 200000 and c["priming_steps"] == 100 - 2 and c["h2d_packed"] is True
+    for key in ("cpu_baseline", "cpu_baseline_c2", "e2e_cli", "e2e_cli_c3", "roofline_by_kernel", "roofline_by_workload",
+                "pipeline_by_workload", "counters_match_pipeline"):
+        assert key not in d, key
+    for key in ("kernel_only_mreads", "kernel_ms_alone", "pipeline_check", "bandwidths"):
+        assert key not in c, key
+    assert c["stage_reads_mreads"] is None and c["zero_copy_ascii_mreads"] is None
+
+
 def test_two_ranks_start_by_themselves_and_reduce_their_counters():
-    one = _run(["--workload", "c2", "--reps", "1", "--steps", "2", "--warmup", "1", "--batch", "100000", "--extra", "none", "--no-cpu", "--no-e2e"])
-    two = _run(["--workload", "c2", "--reps", "1", "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "100000", "--extra", "none", "--no-cpu", "--no-e2e"],
+    one = _run(["--full", "--workload", "c2", "--reps", "1", "--steps", "2", "--warmup", "1", "--batch", "100000", "--extra", "none", "--no-cpu", "--no-e2e"])
+    two = _run(["--full", "--workload", "c2", "--reps", "1", "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "100000", "--extra", "none", "--no-cpu", "--no-e2e"],
                env={"FEM_BENCH_ONE_GPU": "1", "FEM_BENCH_BACKEND": "gloo"})
     assert two["n_gpus"] == 2 and two["scaling"] == "weak"
     assert two["counters_match_pipeline"] is True and one["counters_match_pipeline"] is True
@@ -79,7 +97,7 @@ def test_one_rank_reduces_its_counters_over_rccl():
 def test_headline_workload_is_c3_with_two_seed_kernels():
     # the default line at a toy batch: C3's 3 Gbp reference, seed_select_kernel + seed_join_kernel, one workload behind
     # value / ms_per_step / roofline
-    d = _run(["--steps", "3", "--warmup", "2", "--batch", "100000", "--extra", "none", "--no-cpu", "--no-e2e", "--reps", "1"])
+    d = _run(["--full", "--steps", "3", "--warmup", "2", "--batch", "100000", "--extra", "none", "--no-cpu", "--no-e2e", "--reps", "1"])
     assert d["roofline"]["workload"] == "c3" and d["roofline"]["kernel"] == "seed_join_kernel" and d["config"]["seed_kernel"] == "seed_join_kernel"
     assert set(d["roofline_by_kernel"]) >= {"seed_join_kernel", "seed_select_kernel"}
     assert d["roofline"]["avg_launch_ms"] <= d["ms_per_step"]
