@@ -2063,36 +2063,6 @@ int fem_dev_fetch_packed(fem_dev *h, int slot, fem_batch_packed *out) {
   return FEM_OK;
 }
 
-int fem_dev_fetch_records(fem_dev *h, int slot, fem_batch_records *out) {
-  int rc = fem_dev_sync(h, slot);
-  if (rc) return rc;
-  if (!out) return fail(h, FEM_ERR_INVALID, "null result");
-  Slot &s = h->slot[slot];
-  s.prefetch_results = false;  // this caller takes records, not the per-candidate arrays
-  if (!s.tail) s.tail = new (std::nothrow) femt::Tail();
-  if (!s.tail) return fail(h, FEM_ERR_NOMEM, "out of host memory");
-  femt::TailInput in{};
-  in.bases = s.bases(), in.read_off = s.d_off, in.n_reads = (uint32_t)s.n_reads, in.max_len = s.max_len;
-  in.ref_raw = h->d_ref_raw, in.ref_bytes = h->ref_bytes + 64, in.seq_off = h->d_seq_off;
-  in.planes = h->d_planes;
-  if (s.sent_packed) in.packed = s.d_packed, in.packed_bpr = s.packed_bpr, in.exc_bits = s.d_exc_bits;
-  in.cand = s.d_cand, in.ed = s.d_ed, in.end = s.d_end, in.cand_begin = s.d_begin, in.cand_count = s.d_count;
-  in.n_map = s.d_nmap, in.e = s.params.e, in.n_records = s.stats[4];
-  femt::TailOutput t{};
-  double ms[3] = {0, 0, 0};
-  std::string err;
-  if (s.out_stream) HIP_TRY(h, hipStreamSynchronize(s.out_stream));  // (a SAM text of this slot still being made reads the tail's arrays)
-  rc = s.tail->run(in, s.stream, h->n_cu, h->tiny_buffers, &t, &err, h->timing ? ms : nullptr);
-  if (rc) return fail(h, rc, err);
-  if (h->timing)
-    for (int i = 0; i < 3; ++i) h->t_ms[3 + i] += ms[i], h->t_n[3 + i] += 1;
-  out->n_reads = t.n_reads, out->n_records = t.n_records;
-  out->rec_begin = t.rec_begin, out->flag = t.flag, out->tid = t.tid, out->pos0 = t.pos0, out->nm = t.nm;
-  out->cigar_off = t.cigar_off, out->cigar = t.cigar, out->md_off = t.md_off, out->md = t.md;
-  memcpy(out->stats, s.stats, sizeof s.stats);
-  return FEM_OK;
-}
-
 int fem_dev_upload_reference_names(fem_dev *h, uint32_t n_seq, const char *names, const uint64_t *name_off) {
   if (!h || !names || !name_off || n_seq == 0) return FEM_ERR_INVALID;
   if (h->n_seq && n_seq != h->n_seq) return fail(h, FEM_ERR_INVALID, "as many names as reference sequences, please");
@@ -2289,20 +2259,8 @@ static int rescue_input(fem_dev *h, const Slot &s, femt::RescueInput *ri) {
   return FEM_OK;
 }
 
-static int fetch_sam(fem_dev *h, int slot, fem_batch_sam *out, bool wait) {
-  static const bool trace_host = testing_switch("FEM_FETCH_TIMES");  // host time of the call's three stretches, on stderr
-  const auto t_in = std::chrono::steady_clock::now();
-  auto since = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
-  int rc = fem_dev_sync(h, slot);
-  if (rc) return rc;
-  const double ms_sync = since(t_in);
-  if (!out) return fail(h, FEM_ERR_INVALID, "null result");
-  Slot &s = h->slot[slot];
-  if (!s.text_staged) return fail(h, FEM_ERR_STATE, "qualities and names of this batch were not committed (fem_dev_commit_text_stage)");
-  if (!h->d_ref_names) return fail(h, FEM_ERR_STATE, "reference names must be uploaded first (fem_dev_upload_reference_names)");
-  s.prefetch_results = false;
-  if (!s.tail) s.tail = new (std::nothrow) femt::Tail();
-  if (!s.tail) return fail(h, FEM_ERR_NOMEM, "out of host memory");
+// What the device tail reads of the slot's batch and of the index.
+static femt::TailInput tail_input(const fem_dev *h, const Slot &s) {
   femt::TailInput in{};
   in.bases = s.bases(), in.read_off = s.d_off, in.n_reads = (uint32_t)s.n_reads, in.max_len = s.max_len;
   in.ref_raw = h->d_ref_raw, in.ref_bytes = h->ref_bytes + 64, in.seq_off = h->d_seq_off;
@@ -2310,43 +2268,109 @@ static int fetch_sam(fem_dev *h, int slot, fem_batch_sam *out, bool wait) {
   if (s.sent_packed) in.packed = s.d_packed, in.packed_bpr = s.packed_bpr, in.exc_bits = s.d_exc_bits;
   in.cand = s.d_cand, in.ed = s.d_ed, in.end = s.d_end, in.cand_begin = s.d_begin, in.cand_count = s.d_count;
   in.n_map = s.d_nmap, in.e = s.params.e, in.n_records = s.stats[4];
-  femt::TailOutput t{};
-  double ms[3] = {0, 0, 0}, ms_text = 0;
+  return in;
+}
+
+// What the front of a fetch leaves for the rest of it: the records were made on `stream` (a text goes there), ms = kernel
+// times 3-5; host time from t_in to the mapping synced and to the records made.
+struct TailFront {
+  femt::TailInput in;
+  femt::TailOutput t;
+  hipStream_t stream;
+  double ms[3], ms_sync, ms_run;
+  std::chrono::steady_clock::time_point t_in;
+};
+
+// The front of every way a batch's records leave the device (fem_dev_fetch_records, fetch_sam, fetch_bam): waits for the
+// slot's mapping, checks it (`out`: the caller's result), makes the records.  copy_records: on the slot's stream, copied home.
+// Else a text follows (device_quals: its qualities on the device): records on out_stream_of, a paired slot's paired.
+static int tail_records(fem_dev *h, int slot, const void *out, bool copy_records, bool device_quals, TailFront *f) {
+  f->t_in = std::chrono::steady_clock::now();
+  auto since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - f->t_in).count(); };
+  int rc = fem_dev_sync(h, slot);
+  if (rc) return rc;
+  f->ms_sync = since();
+  if (!out) return fail(h, FEM_ERR_INVALID, "null result");
+  Slot &s = h->slot[slot];
+  const bool text = !copy_records, paired = text && s.paired;
+  if (text && !s.text_staged) return fail(h, FEM_ERR_STATE, "qualities and names of this batch were not committed (fem_dev_commit_text_stage)");
+  if (device_quals && s.host_quals) return fail(h, FEM_ERR_STATE, "BAM records need the qualities on the device (fem_dev_commit_text_stage, not _names_stage)");
+  if (text && !h->d_ref_names) return fail(h, FEM_ERR_STATE, "reference names must be uploaded first (fem_dev_upload_reference_names)");
+  s.prefetch_results = false;  // this caller takes records, not the per-candidate arrays
+  if (!s.tail) s.tail = new (std::nothrow) femt::Tail();
+  if (!s.tail) return fail(h, FEM_ERR_NOMEM, "out of host memory");
+  f->in = tail_input(h, s);
+  if (paired && (s.n_reads & 1)) return fail(h, FEM_ERR_INVALID, "a batch of read pairs holds an even number of reads");
+  if (copy_records && s.out_stream) HIP_TRY(h, hipStreamSynchronize(s.out_stream));  // (a SAM text of this slot still being made reads the tail's arrays)
+  f->stream = copy_records ? s.stream : out_stream_of(h, s);
   std::string err;
-  if (s.paired && (s.n_reads & 1)) return fail(h, FEM_ERR_INVALID, "a batch of read pairs holds an even number of reads");
-  hipStream_t os = out_stream_of(h, s);
-  rc = s.tail->run(in, os, h->n_cu, h->tiny_buffers, &t, &err, h->timing ? ms : nullptr, false);
-  if (rc) return fail(h, rc, err);
-  if (s.paired) {
+  if ((rc = s.tail->run(f->in, f->stream, h->n_cu, h->tiny_buffers, &f->t, &err, h->timing ? f->ms : nullptr, copy_records))) return fail(h, rc, err);
+  if (paired) {
     femt::RescueInput ri{};
     if ((rc = rescue_input(h, s, &ri))) return rc;
-    if ((rc = s.tail->pair(s.min_insert, s.max_insert, os, &err, s.rescue ? &ri : nullptr))) return fail(h, rc, err);
+    if ((rc = s.tail->pair(s.min_insert, s.max_insert, f->stream, &err, s.rescue ? &ri : nullptr))) return fail(h, rc, err);
   }
-  const double ms_run = since(t_in);
-  femt::SamInput names{};
-  names.quals = s.host_quals ? nullptr : s.d_quals, names.names = s.d_names, names.name_off = s.d_name_off;
-  names.qual_hole = s.host_quals;
-  names.ref_names = h->d_ref_names, names.ref_name_off = h->d_ref_name_off;
-  femt::SamOutput text{};
-  HIP_TRY(h, hipStreamWaitEvent(os, s.ev_text_staged, 0));  // qualities and names came on the slot's text stream
-  rc = s.tail->sam(in, names, os, h->n_cu, &text, &err, h->timing ? &ms_text : nullptr, wait, &h->text_gate, s.paired);
-  if (rc) return fail(h, rc, err);
-  s.n_proper = s.paired ? s.tail->n_proper() : 0;  // (sam() has waited for the stream once, after sizing the text)
+  if (text) HIP_TRY(h, hipStreamWaitEvent(f->stream, s.ev_text_staged, 0));  // qualities and names came on the slot's text stream
+  f->ms_run = since();
+  if (copy_records && h->timing) {
+    FEM_LOCK(h);  // (FEM map retires each slot's batches from a thread of its own)
+    for (int i = 0; i < 3; ++i) h->t_ms[3 + i] += f->ms[i], h->t_n[3 + i] += 1;
+  }
+  return FEM_OK;
+}
+
+// The names (and qualities, unless the caller keeps them: qual_hole) the slot's text is rendered with.
+static femt::SamInput sam_input(const fem_dev *h, const Slot &s) {
+  return {s.host_quals ? nullptr : s.d_quals, s.d_names, s.d_name_off, h->d_ref_names, h->d_ref_name_off, s.host_quals};
+}
+
+// What follows a text's sam() / bam() (tag: the caller, for FEM_FETCH_TIMES): the pair counts, the event the slot's next text
+// stage waits for (commit_text), the kernel times: 3-5, n_ms of the text's own from id `id` on, 9 and 10 when paired.
+static int text_done(fem_dev *h, int slot, const TailFront &f, const char *tag, int id, const double *ms, int n_ms) {
+  Slot &s = h->slot[slot];
+  s.n_proper = s.paired ? s.tail->n_proper() : 0;  // (sam() and bam() have waited for the stream once, after sizing the text)
   s.n_rescued = s.paired ? s.tail->n_rescued() : 0;
   if (!s.ev_text_order) HIP_TRY(h, hipEventCreateWithFlags(&s.ev_text_order, hipEventDisableTiming));
-  HIP_TRY(h, hipEventRecord(s.ev_text_order, os));
+  HIP_TRY(h, hipEventRecord(s.ev_text_order, f.stream));
   s.have_text_order = true;
-  if (trace_host) fprintf(stderr, "[fetch_sam] slot %d: mapping synced after %.2f ms, records %.2f, text sized and queued %.2f\n", slot, ms_sync, ms_run, since(t_in));
+  static const bool trace_host = testing_switch("FEM_FETCH_TIMES");  // host time of the call's three stretches, on stderr
+  if (trace_host) fprintf(stderr, "[%s] slot %d: mapping synced after %.2f ms, records %.2f, text sized and queued %.2f\n", tag, slot, f.ms_sync,
+                          f.ms_run, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - f.t_in).count());
   if (h->timing) {
     FEM_LOCK(h);
-    for (int i = 0; i < 3; ++i) h->t_ms[3 + i] += ms[i], h->t_n[3 + i] += 1;
-    if (wait) h->t_ms[7] += ms_text, h->t_n[7] += 1;  // (without the wait no elapsed time is read: nothing to count)
+    for (int i = 0; i < 3; ++i) h->t_ms[3 + i] += f.ms[i], h->t_n[3 + i] += 1;
+    for (int i = 0; i < n_ms; ++i) h->t_ms[id + i] += ms[i], h->t_n[id + i] += 1;
     if (s.paired) h->t_ms[9] += s.tail->pair_ms(), h->t_n[9] += 1;
     if (s.paired && s.rescue) h->t_ms[10] += s.tail->rescue_ms(), h->t_n[10] += 1;
   }
+  return FEM_OK;
+}
+
+int fem_dev_fetch_records(fem_dev *h, int slot, fem_batch_records *out) {
+  TailFront f{};
+  int rc = tail_records(h, slot, out, true, false, &f);
+  if (rc) return rc;
+  out->n_reads = f.t.n_reads, out->n_records = f.t.n_records;
+  out->rec_begin = f.t.rec_begin, out->flag = f.t.flag, out->tid = f.t.tid, out->pos0 = f.t.pos0, out->nm = f.t.nm;
+  out->cigar_off = f.t.cigar_off, out->cigar = f.t.cigar, out->md_off = f.t.md_off, out->md = f.t.md;
+  memcpy(out->stats, h->slot[slot].stats, sizeof out->stats);
+  return FEM_OK;
+}
+
+static int fetch_sam(fem_dev *h, int slot, fem_batch_sam *out, bool wait) {
+  TailFront f{};
+  int rc = tail_records(h, slot, out, false, false, &f);
+  if (rc) return rc;
+  Slot &s = h->slot[slot];
+  femt::SamOutput text{};
+  double ms_text = 0;
+  std::string err;
+  rc = s.tail->sam(f.in, sam_input(h, s), f.stream, h->n_cu, &text, &err, h->timing ? &ms_text : nullptr, wait, &h->text_gate, s.paired);
+  if (rc) return fail(h, rc, err);
+  if ((rc = text_done(h, slot, f, "fetch_sam", 7, &ms_text, wait ? 1 : 0))) return rc;  // (without the wait no elapsed time is read: nothing to count)
   s.qual_at = text.qual_at;
   out->text = text.text, out->len = text.len, out->n_asserted = text.n_asserted;
-  out->n_reads = t.n_reads, out->n_records = t.n_records;
+  out->n_reads = f.t.n_reads, out->n_records = f.t.n_records;
   memcpy(out->stats, s.stats, sizeof s.stats);
   return FEM_OK;
 }
@@ -2354,58 +2378,19 @@ static int fetch_sam(fem_dev *h, int slot, fem_batch_sam *out, bool wait) {
 // ---- BAM output: the SAM lines as BAM records, BGZF-compressed on the device ----
 static int fetch_bam(fem_dev *h, int slot, int level, fem_batch_bam *out, bool wait) {
   if (level < 0 || level > 1) return fail(h, FEM_ERR_INVALID, "BAM compression level must be 0 or 1");
-  int rc = fem_dev_sync(h, slot);
+  TailFront f{};
+  int rc = tail_records(h, slot, out, false, true, &f);
   if (rc) return rc;
-  if (!out) return fail(h, FEM_ERR_INVALID, "null result");
   Slot &s = h->slot[slot];
-  if (!s.text_staged) return fail(h, FEM_ERR_STATE, "qualities and names of this batch were not committed (fem_dev_commit_text_stage)");
-  if (s.host_quals) return fail(h, FEM_ERR_STATE, "BAM records need the qualities on the device (fem_dev_commit_text_stage, not _names_stage)");
-  if (!h->d_ref_names) return fail(h, FEM_ERR_STATE, "reference names must be uploaded first (fem_dev_upload_reference_names)");
-  s.prefetch_results = false;
-  if (!s.tail) s.tail = new (std::nothrow) femt::Tail();
-  if (!s.tail) return fail(h, FEM_ERR_NOMEM, "out of host memory");
-  femt::TailInput in{};
-  in.bases = s.bases(), in.read_off = s.d_off, in.n_reads = (uint32_t)s.n_reads, in.max_len = s.max_len;
-  in.ref_raw = h->d_ref_raw, in.ref_bytes = h->ref_bytes + 64, in.seq_off = h->d_seq_off;
-  in.planes = h->d_planes;
-  if (s.sent_packed) in.packed = s.d_packed, in.packed_bpr = s.packed_bpr, in.exc_bits = s.d_exc_bits;
-  in.cand = s.d_cand, in.ed = s.d_ed, in.end = s.d_end, in.cand_begin = s.d_begin, in.cand_count = s.d_count;
-  in.n_map = s.d_nmap, in.e = s.params.e, in.n_records = s.stats[4];
-  femt::TailOutput t{};
-  double ms[3] = {0, 0, 0}, ms_bam[2] = {0, 0};
-  std::string err;
-  if (s.paired && (s.n_reads & 1)) return fail(h, FEM_ERR_INVALID, "a batch of read pairs holds an even number of reads");
-  hipStream_t os = out_stream_of(h, s);
-  rc = s.tail->run(in, os, h->n_cu, h->tiny_buffers, &t, &err, h->timing ? ms : nullptr, false);
-  if (rc) return fail(h, rc, err);
-  if (s.paired) {
-    femt::RescueInput ri{};
-    if ((rc = rescue_input(h, s, &ri))) return rc;
-    if ((rc = s.tail->pair(s.min_insert, s.max_insert, os, &err, s.rescue ? &ri : nullptr))) return fail(h, rc, err);
-  }
-  femt::SamInput names{};
-  names.quals = s.d_quals, names.names = s.d_names, names.name_off = s.d_name_off;
-  names.ref_names = h->d_ref_names, names.ref_name_off = h->d_ref_name_off;
   femt::BamOutput bam{};
-  HIP_TRY(h, hipStreamWaitEvent(os, s.ev_text_staged, 0));  // qualities and names came on the slot's text stream
-  rc = s.tail->bam(in, names, level, os, h->n_cu, &bam, &err, h->timing ? ms_bam : nullptr, wait, &h->text_gate, s.paired);
+  double ms_bam[2] = {0, 0};
+  std::string err;
+  rc = s.tail->bam(f.in, sam_input(h, s), level, f.stream, h->n_cu, &bam, &err, h->timing ? ms_bam : nullptr, wait, &h->text_gate, s.paired);
   if (rc) return fail(h, rc, err);
-  s.n_proper = s.paired ? s.tail->n_proper() : 0;
-  s.n_rescued = s.paired ? s.tail->n_rescued() : 0;
-  if (!s.ev_text_order) HIP_TRY(h, hipEventCreateWithFlags(&s.ev_text_order, hipEventDisableTiming));
-  HIP_TRY(h, hipEventRecord(s.ev_text_order, os));
-  s.have_text_order = true;
-  if (h->timing) {
-    FEM_LOCK(h);
-    for (int i = 0; i < 3; ++i) h->t_ms[3 + i] += ms[i], h->t_n[3 + i] += 1;
-    h->t_ms[11] += ms_bam[0], h->t_n[11] += 1;
-    h->t_ms[12] += ms_bam[1], h->t_n[12] += 1;
-    if (s.paired) h->t_ms[9] += s.tail->pair_ms(), h->t_n[9] += 1;
-    if (s.paired && s.rescue) h->t_ms[10] += s.tail->rescue_ms(), h->t_n[10] += 1;
-  }
+  if ((rc = text_done(h, slot, f, "fetch_bam", 11, ms_bam, 2))) return rc;
   s.qual_at = nullptr;
   out->data = bam.data, out->len = bam.len, out->raw_len = bam.raw_len, out->n_blocks = bam.n_blocks;
-  out->n_records = t.n_records, out->n_asserted = bam.n_asserted;
+  out->n_records = f.t.n_records, out->n_asserted = bam.n_asserted;
   memcpy(out->stats, s.stats, sizeof s.stats);
   return FEM_OK;
 }

@@ -1082,26 +1082,30 @@ struct TriplePlus {  // component-wise sum of (kept, runs, MD length) triples (m
   }
 };
 
-// ---- host-side buffer helpers ----
+// ---- host-side buffer helpers: device memory (DevBuf) or pinned host memory (PinBuf), freed with the object ----
 struct DevBuf {
   void *p = nullptr;
   size_t cap = 0;
+  bool pinned = false;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  ~DevBuf() { release(); }
   hipError_t need(size_t bytes) {
     if (bytes <= cap && p) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr, cap = 0;
+    release();
     const size_t want = std::max<size_t>(bytes + bytes / 4, 256);
-    hipError_t e = hipMalloc(&p, want);
+    hipError_t e = pinned ? hipHostMalloc(&p, want, hipHostMallocDefault) : hipMalloc(&p, want);
     if (e == hipSuccess) cap = want;
     return e;
   }
   void release() {
-    if (p) (void)hipFree(p);
+    if (p) (void)(pinned ? hipHostFree(p) : hipFree(p));
     p = nullptr, cap = 0;
   }
   template <typename T>
   T *as() const { return (T *)p; }
-  // need() that keeps the first `used` bytes (waits for `stream` when it has to move them)
+  // need() that keeps the first `used` bytes (waits for `stream` when it has to move them; device memory only)
   hipError_t grow(size_t bytes, size_t used, hipStream_t stream) {
     if (bytes <= cap && p) return hipSuccess;
     const size_t want = std::max<size_t>(bytes + bytes / 4, 256);
@@ -1114,29 +1118,13 @@ struct DevBuf {
       (void)hipFree(q);
       return e;
     }
-    if (p) (void)hipFree(p);
+    release();
     p = q, cap = want;
     return hipSuccess;
   }
 };
-struct PinBuf {
-  void *p = nullptr;
-  size_t cap = 0;
-  hipError_t need(size_t bytes) {
-    if (bytes <= cap && p) return hipSuccess;
-    if (p) (void)hipHostFree(p);
-    p = nullptr, cap = 0;
-    const size_t want = std::max<size_t>(bytes + bytes / 4, 256);
-    hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipHostFree(p);
-    p = nullptr, cap = 0;
-  }
-  template <typename T>
-  T *as() const { return (T *)p; }
+struct PinBuf : DevBuf {
+  PinBuf() { pinned = true; }
 };
 
 
@@ -1207,6 +1195,20 @@ __device__ __forceinline__ uint32_t mate_cols_len(const SamParams &p, uint32_t j
   return rnext + 1u + dec_digits(p.mpos0[j] + 1u) + 1u + tl_len;
 }
 
+// What every line kernel first reads of line j: the record it renders (pair mode: perm[j]; else j itself), that record's
+// read, the FLAG as written (0x8000 kept), whether the line is the read's primary one (SEQ, QUAL), the read's and its name's length.
+struct LineHead {
+  uint32_t rec, r, flag;
+  bool primary;
+  uint32_t L, name_len;
+};
+template <bool kPair>
+__device__ __forceinline__ LineHead line_head(const SamParams &p, uint32_t j) {
+  const uint32_t rec = kPair ? p.perm[j] : j, r = p.s_read[rec], flag = kPair ? p.pflag[j] : p.flag[rec];
+  return {rec, r, flag, kPair ? !(flag & 256u) : p.rec_begin[r] == j, (uint32_t)(p.read_off[r + 1] - p.read_off[r]),
+          (uint32_t)(p.name_off[r + 1] - p.name_off[r])};
+}
+
 template <bool kPair>
 __global__ void __launch_bounds__(256) sam_len_kernel(SamParams p) {
   const uint32_t stride = gridDim.x * blockDim.x;
@@ -1215,12 +1217,7 @@ __global__ void __launch_bounds__(256) sam_len_kernel(SamParams p) {
       p.line_len[j] = 0;
       continue;
     }
-    const uint32_t rec = kPair ? p.perm[j] : j;  // (pair mode: j is the line, rec the record it renders)
-    const uint32_t r = p.s_read[rec];
-    const uint16_t flag = kPair ? p.pflag[j] : p.flag[j];
-    const bool primary = kPair ? !(flag & 256u) : p.rec_begin[r] == j;
-    const uint32_t L = (uint32_t)(p.read_off[r + 1] - p.read_off[r]);
-    const uint32_t name_len = (uint32_t)(p.name_off[r + 1] - p.name_off[r]);
+    const auto [rec, r, flag, primary, L, name_len] = line_head<kPair>(p, j);
     const uint32_t t = p.tid[rec], rname_len = p.ref_name_off[t + 1] - p.ref_name_off[t];
     if (flag & 0x8000u) atomicAdd(p.asserted, 1u);
     uint32_t cig = 0;
@@ -1445,12 +1442,7 @@ __global__ void __launch_bounds__(256) bam_len_kernel(SamParams p, uint32_t n_re
       p.line_len[j] = 0;
       continue;
     }
-    const uint32_t rec = kPair ? p.perm[j] : j;
-    const uint32_t r = p.s_read[rec];
-    const uint16_t flag = kPair ? p.pflag[j] : p.flag[j];
-    const bool primary = kPair ? !(flag & 256u) : p.rec_begin[r] == j;
-    const uint32_t L = (uint32_t)(p.read_off[r + 1] - p.read_off[r]);
-    const uint32_t name_len = (uint32_t)(p.name_off[r + 1] - p.name_off[r]);
+    const auto [rec, r, flag, primary, L, name_len] = line_head<kPair>(p, j);
     if (flag & 0x8000u) atomicAdd(p.asserted, 1u);
     const uint32_t n_ops = p.cigar_off[rec + 1] - p.cigar_off[rec], md_len = p.md_off[rec + 1] - p.md_off[rec];
     const uint32_t ls = primary ? L : 0u;
@@ -1474,14 +1466,9 @@ __global__ void __launch_bounds__(256) bam_write_kernel(SamParams p) {
   const uint32_t ln = threadIdx.x & 63u;
   const uint32_t j = blockIdx.x * 4u + (threadIdx.x >> 6);
   if (j >= p.n_records) return;
-  const uint32_t rec = kPair ? p.perm[j] : j;
-  const uint32_t r = p.s_read[rec];
-  const uint32_t fl = kPair ? p.pflag[j] : p.flag[rec];
-  const bool primary = kPair ? !(fl & 256u) : p.rec_begin[r] == j;
-  const uint64_t ro = p.read_off[r];
-  const uint32_t L = (uint32_t)(p.read_off[r + 1] - ro), ls = primary ? L : 0u;
-  const uint64_t no = p.name_off[r];
-  const uint32_t name_len = (uint32_t)(p.name_off[r + 1] - no);
+  const auto [rec, r, fl, primary, L, name_len] = line_head<kPair>(p, j);
+  const uint64_t ro = p.read_off[r], no = p.name_off[r];
+  const uint32_t ls = primary ? L : 0u;
   const uint32_t c0 = p.cigar_off[rec], n_ops = p.cigar_off[rec + 1] - c0;
   const uint32_t m0 = p.md_off[rec], md_len = p.md_off[rec + 1] - m0;
   const uint32_t tid = p.tid[rec], pos0 = p.pos0[rec], nm = p.nm[rec];
@@ -1987,6 +1974,15 @@ __global__ void __launch_bounds__(256) rescue_append_kernel(RescueParams p) {
 
 }  // namespace
 
+#define TAIL_TRY(expr)                                                             \
+  do {                                                                             \
+    hipError_t e_ = (expr);                                                        \
+    if (e_ != hipSuccess) {                                                        \
+      if (err) *err = std::string(#expr) + ": " + hipGetErrorString(e_);           \
+      return e_ == hipErrorOutOfMemory ? FEM_ERR_NOMEM : FEM_ERR_HIP;              \
+    }                                                                              \
+  } while (0)
+
 struct Tail::Impl {
   DevBuf rec_begin, queue, ctl, u_cand, u_misc, s_cand, s_misc, s_read, t_ops, t_md, o_ops, o_md, ovf, rec_list, src_slot, n_ops, n_md,
       flag, tid, pos0, nm, cigar_off, md_off, cigar, md, scan_tmp;
@@ -2011,37 +2007,83 @@ struct Tail::Impl {
   hipEvent_t ev_pair[2] = {nullptr, nullptr};
   hipEvent_t ev_resc[2] = {nullptr, nullptr};
   hipEvent_t ev_text = nullptr;  // the SAM text has arrived in h_text
-  ~Impl() {
-    if (ev_text) (void)hipEventDestroy(ev_text);
-    for (hipEvent_t e : ev_pair)
+  ~Impl() {  // (the buffers free themselves)
+    for (hipEvent_t e : {ev[0], ev[1], ev[2], ev[3], ev_pair[0], ev_pair[1], ev_resc[0], ev_resc[1], ev_text})
       if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ev_resc)
-      if (e) (void)hipEventDestroy(e);
-    for (DevBuf *b : {&r_ctl, &r_cand, &r_jobs, &r_best, &r_ops, &r_md, &r_rec, &r_ovf, &r_o_ops, &r_o_md, &r_kept, &r_scan, &r_scan_tmp})
-      b->release();
-    for (PinBuf *b : {&h_r_ctl, &h_r_flag, &h_r_tid, &h_r_pos0, &h_r_nm, &h_r_cigar_off, &h_r_cigar, &h_r_md_off, &h_r_md}) b->release();
-    for (DevBuf *b : {&perm, &pflag, &mtid, &mpos0, &tlen, &pair_begin, &pair_ctl}) b->release();
-    for (PinBuf *b : {&h_perm, &h_pflag, &h_mtid, &h_mpos0, &h_tlen, &h_pair_begin, &h_pair_ctl}) b->release();
-    for (DevBuf *b : {&rec_begin, &queue, &ctl, &u_cand, &u_misc, &s_cand, &s_misc, &s_read, &t_ops, &t_md, &o_ops, &o_md, &ovf, &rec_list,
-                      &src_slot, &n_ops, &n_md, &flag, &tid, &pos0, &nm, &cigar_off, &md_off, &cigar, &md, &scan_tmp, &line_len, &line_off, &text, &qual_at, &bam_ctl})
-      b->release();
-    for (PinBuf *b : {&h_ctl, &h_rec_begin, &h_flag, &h_tid, &h_pos0, &h_nm, &h_cigar_off, &h_md_off, &h_cigar, &h_md, &h_text, &h_qual_at, &h_line_off})
-      b->release();
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
+  }
+  // sam() and bam(): the lines of run()'s records, or of pair()'s (rescued records included).  Fills *p (all but the text and
+  // qual_at); from ev[0] on, each line's length (bad_name: as BAM, a name over 254 characters setting it; else as SAM), their
+  // scan into line_off, the count of asserted records to h_ctl[2].
+  int lines(const TailInput &in, const SamInput &names, bool pair_order, uint32_t *bad_name, hipStream_t stream, int n_cu, SamParams *p,
+              std::string *err) {
+    if (pair_order && !paired) {
+      if (err) *err = "the records were not paired (Tail::pair)";
+      return FEM_ERR_STATE;
+    }
+    const uint32_t nr = last_nr + (pair_order ? n_resc : 0u);
+    const size_t r1 = (size_t)nr + 1;
+    for (hipEvent_t &e : ev)
+      if (!e) TAIL_TRY(hipEventCreate(&e));
+    TAIL_TRY(line_len.need(r1 * 8));
+    TAIL_TRY(line_off.need(r1 * 8));
+    TAIL_TRY(h_ctl.need(32));
+    size_t tmp = 0;
+    TAIL_TRY(rocprim::exclusive_scan(nullptr, tmp, line_len.as<unsigned long long>(), line_off.as<unsigned long long>(), 0ull, r1,
+                                     rocprim::plus<unsigned long long>(), stream));
+    TAIL_TRY(scan_tmp.need(std::max<size_t>(tmp, 16)));
+    p->n_records = nr, p->rec_begin = rec_begin.as<uint32_t>(), p->s_read = s_read.as<uint32_t>();
+    p->flag = flag.as<uint16_t>(), p->tid = tid.as<uint32_t>(), p->pos0 = pos0.as<uint32_t>(), p->nm = nm.as<uint8_t>();
+    p->cigar_off = cigar_off.as<uint32_t>(), p->cigar = cigar.as<uint32_t>(), p->md_off = md_off.as<uint32_t>(), p->md = md.as<uint8_t>();
+    p->bases = in.bases, p->read_off = in.read_off;
+    p->quals = names.quals, p->names = names.names, p->name_off = names.name_off, p->ref_names = names.ref_names, p->ref_name_off = names.ref_name_off;
+    p->line_len = line_len.as<unsigned long long>(), p->line_off = line_off.as<unsigned long long>();
+    p->asserted = ctl.as<uint32_t>() + 2;  // (ctl[2] is zero after a successful run())
+    if (pair_order) {
+      p->perm = perm.as<uint32_t>(), p->pflag = pflag.as<uint16_t>(), p->mtid = mtid.as<uint32_t>(), p->mpos0 = mpos0.as<uint32_t>();
+      p->tlen = tlen.as<int32_t>();
+    }
+    if (bad_name) TAIL_TRY(hipMemsetAsync(bad_name, 0, 4, stream));
+    TAIL_TRY(hipEventRecord(ev[0], stream));
+    const dim3 len_grid(std::max<uint32_t>(1u, std::min<uint32_t>((nr + 256u) / 256u, (uint32_t)n_cu * 16u)));
+    if (bad_name)
+      hipLaunchKernelGGL(pair_order ? bam_len_kernel<true> : bam_len_kernel<false>, len_grid, dim3(256), 0, stream, *p, last_n, bad_name);
+    else
+      hipLaunchKernelGGL(pair_order ? sam_len_kernel<true> : sam_len_kernel<false>, len_grid, dim3(256), 0, stream, *p);
+    TAIL_TRY(hipGetLastError());
+    TAIL_TRY(rocprim::exclusive_scan(scan_tmp.p, scan_tmp.cap, line_len.as<unsigned long long>(), line_off.as<unsigned long long>(), 0ull,
+                                     r1, rocprim::plus<unsigned long long>(), stream));
+    TAIL_TRY(hipMemcpyAsync(h_ctl.as<uint32_t>() + 2, ctl.as<uint32_t>() + 2, 4, hipMemcpyDeviceToHost, stream));
+    return FEM_OK;
+  }
+
+  // A text's way home after ev[1]: `bytes` from src into h_text (and bytes2 from src2 into dst2: SAM's qual_at) behind the text
+  // that took the gate before (TextGate), ev_text its arrival; wait: until then.  ms += ev[0]..ev[1] (the stream has passed ev[1]).
+  int send_home(const void *src, size_t bytes, void *dst2, const void *src2, size_t bytes2, hipStream_t stream, bool wait, TextGate *gate,
+                  double *ms, std::string *err) {
+    if (!ev_text) TAIL_TRY(hipEventCreateWithFlags(&ev_text, hipEventDisableTiming));
+    static const bool no_gate = getenv("FEM_TESTING") && getenv("FEM_TEXT_NO_GATE");  // (A/B)
+    if (no_gate) gate = nullptr;
+    {
+      std::unique_lock<std::mutex> turn;
+      if (gate) {
+        turn = std::unique_lock<std::mutex>(gate->mu);
+        if (gate->last && gate->last != ev_text) TAIL_TRY(hipEventSynchronize(gate->last));  // (this slot's own last text is home: its stream is in order)
+      }
+      // (by the copy engine.  The shader cores' stores into the pinned buffer — no engine to queue in — bring a text home in 7-9.5
+      //  ms where the engine takes 5.4, and FEM map from 130 to 117 Mreads/s.)
+      if (bytes) TAIL_TRY(hipMemcpyAsync(h_text.p, src, bytes, hipMemcpyDeviceToHost, stream));
+      if (bytes2) TAIL_TRY(hipMemcpyAsync(dst2, src2, bytes2, hipMemcpyDeviceToHost, stream));
+      TAIL_TRY(hipEventRecord(ev_text, stream));
+      if (gate) gate->last = ev_text;
+    }
+    if (wait) TAIL_TRY(hipStreamSynchronize(stream));
+    float t = 0.f;
+    if (ms && hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess) *ms += t;
+    return FEM_OK;
   }
 };
 
 Tail::~Tail() { delete impl_; }
-
-#define TAIL_TRY(expr)                                                             \
-  do {                                                                             \
-    hipError_t e_ = (expr);                                                        \
-    if (e_ != hipSuccess) {                                                        \
-      if (err) *err = std::string(#expr) + ": " + hipGetErrorString(e_);           \
-      return e_ == hipErrorOutOfMemory ? FEM_ERR_NOMEM : FEM_ERR_HIP;              \
-    }                                                                              \
-  } while (0)
 
 // Everything run() and sam() allocate for a batch of n reads with nr records (device arrays sized by the records, the scans'
 // scratch).  run() calls it with the batch's own numbers; a caller that knows what is coming (fem_dev_reserve_batch) calls it
@@ -2148,8 +2190,6 @@ int Tail::run(const TailInput &in, hipStream_t stream, int n_cu, bool tiny, Tail
     return FEM_ERR_UNSUPPORTED;
   }
   const uint32_t n = in.n_reads, nr = (uint32_t)in.n_records;
-  for (hipEvent_t &e : m.ev)
-    if (!e) TAIL_TRY(hipEventCreate(&e));
 
   // ---- LDS plan of the traceback kernel: lanes = records one 64-thread block walks at a time ----
   const uint32_t max_len = std::max<uint32_t>(in.max_len, 1);
@@ -2278,67 +2318,51 @@ int Tail::run(const TailInput &in, hipStream_t stream, int n_cu, bool tiny, Tail
   TAIL_TRY(hipMemcpyAsync(h_ctl + 4, m.cigar_off.as<uint32_t>() + nr, 4, hipMemcpyDeviceToHost, stream));
   TAIL_TRY(hipMemcpyAsync(h_ctl + 5, m.md_off.as<uint32_t>() + nr, 4, hipMemcpyDeviceToHost, stream));
   m.last_n = n, m.last_nr = nr, m.paired = false, m.n_resc = 0, m.resc_timed = false;
-  if (!copy_records) {  // the caller renders them on the device (sam())
-    TAIL_TRY(hipMemcpyAsync(h_ctl, m.ctl.p, 16, hipMemcpyDeviceToHost, stream));
+  if (copy_records) {  // ---- copy back (else the caller renders the records on the device: sam(), bam()) ----
     TAIL_TRY(hipStreamSynchronize(stream));
-    if (h_ctl[2] != 0) {
-      if (err) *err = "device traceback: a record outgrew the overflow staging (internal error)";
-      return FEM_ERR_HIP;
+    const uint32_t n_cigar = h_ctl[4], n_md = h_ctl[5];
+    TAIL_TRY(m.h_rec_begin.need(((size_t)n + 1) * 4));
+    TAIL_TRY(m.h_flag.need(r1 * 2));
+    TAIL_TRY(m.h_tid.need(r1 * 4));
+    TAIL_TRY(m.h_pos0.need(r1 * 4));
+    TAIL_TRY(m.h_nm.need(r1));
+    TAIL_TRY(m.h_cigar_off.need(r1 * 4));
+    TAIL_TRY(m.h_md_off.need(r1 * 4));
+    TAIL_TRY(m.h_cigar.need(std::max<size_t>(n_cigar, 1) * 4));
+    TAIL_TRY(m.h_md.need(std::max<size_t>(n_md, 1)));
+    TAIL_TRY(hipMemcpyAsync(m.h_rec_begin.p, m.rec_begin.p, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost, stream));
+    TAIL_TRY(hipMemcpyAsync(m.h_cigar_off.p, m.cigar_off.p, r1 * 4, hipMemcpyDeviceToHost, stream));
+    TAIL_TRY(hipMemcpyAsync(m.h_md_off.p, m.md_off.p, r1 * 4, hipMemcpyDeviceToHost, stream));
+    if (nr) {
+      TAIL_TRY(hipMemcpyAsync(m.h_flag.p, m.flag.p, (size_t)nr * 2, hipMemcpyDeviceToHost, stream));
+      TAIL_TRY(hipMemcpyAsync(m.h_tid.p, m.tid.p, (size_t)nr * 4, hipMemcpyDeviceToHost, stream));
+      TAIL_TRY(hipMemcpyAsync(m.h_pos0.p, m.pos0.p, (size_t)nr * 4, hipMemcpyDeviceToHost, stream));
+      TAIL_TRY(hipMemcpyAsync(m.h_nm.p, m.nm.p, (size_t)nr, hipMemcpyDeviceToHost, stream));
     }
-    if (ms) {
-      for (int i = 0; i < 3; ++i) {
-        float t = 0.f;
-        if (hipEventElapsedTime(&t, m.ev[i], m.ev[i + 1]) == hipSuccess) ms[i] += t;
-      }
-    }
-    memset(out, 0, sizeof *out);
-    out->n_reads = n, out->n_records = nr;
-    return FEM_OK;
+    if (n_cigar) TAIL_TRY(hipMemcpyAsync(m.h_cigar.p, m.cigar.p, (size_t)n_cigar * 4, hipMemcpyDeviceToHost, stream));
+    if (n_md) TAIL_TRY(hipMemcpyAsync(m.h_md.p, m.md.p, (size_t)n_md, hipMemcpyDeviceToHost, stream));
   }
-  // ---- copy back ----
-  TAIL_TRY(hipStreamSynchronize(stream));
-  const uint32_t n_cigar = h_ctl[4], n_md = h_ctl[5];
-  TAIL_TRY(m.h_rec_begin.need(((size_t)n + 1) * 4));
-  TAIL_TRY(m.h_flag.need(r1 * 2));
-  TAIL_TRY(m.h_tid.need(r1 * 4));
-  TAIL_TRY(m.h_pos0.need(r1 * 4));
-  TAIL_TRY(m.h_nm.need(r1));
-  TAIL_TRY(m.h_cigar_off.need(r1 * 4));
-  TAIL_TRY(m.h_md_off.need(r1 * 4));
-  TAIL_TRY(m.h_cigar.need(std::max<size_t>(n_cigar, 1) * 4));
-  TAIL_TRY(m.h_md.need(std::max<size_t>(n_md, 1)));
-  TAIL_TRY(hipMemcpyAsync(m.h_rec_begin.p, m.rec_begin.p, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost, stream));
-  TAIL_TRY(hipMemcpyAsync(m.h_cigar_off.p, m.cigar_off.p, r1 * 4, hipMemcpyDeviceToHost, stream));
-  TAIL_TRY(hipMemcpyAsync(m.h_md_off.p, m.md_off.p, r1 * 4, hipMemcpyDeviceToHost, stream));
-  if (nr) {
-    TAIL_TRY(hipMemcpyAsync(m.h_flag.p, m.flag.p, (size_t)nr * 2, hipMemcpyDeviceToHost, stream));
-    TAIL_TRY(hipMemcpyAsync(m.h_tid.p, m.tid.p, (size_t)nr * 4, hipMemcpyDeviceToHost, stream));
-    TAIL_TRY(hipMemcpyAsync(m.h_pos0.p, m.pos0.p, (size_t)nr * 4, hipMemcpyDeviceToHost, stream));
-    TAIL_TRY(hipMemcpyAsync(m.h_nm.p, m.nm.p, (size_t)nr, hipMemcpyDeviceToHost, stream));
-  }
-  if (n_cigar) TAIL_TRY(hipMemcpyAsync(m.h_cigar.p, m.cigar.p, (size_t)n_cigar * 4, hipMemcpyDeviceToHost, stream));
-  if (n_md) TAIL_TRY(hipMemcpyAsync(m.h_md.p, m.md.p, (size_t)n_md, hipMemcpyDeviceToHost, stream));
   TAIL_TRY(hipMemcpyAsync(h_ctl, m.ctl.p, 16, hipMemcpyDeviceToHost, stream));
   TAIL_TRY(hipStreamSynchronize(stream));
   if (h_ctl[2] != 0) {
     if (err) *err = "device traceback: a record outgrew the overflow staging (internal error)";
     return FEM_ERR_HIP;
   }
-  if (ms) {
-    for (int i = 0; i < 3; ++i) {
-      float t = 0.f;
-      if (hipEventElapsedTime(&t, m.ev[i], m.ev[i + 1]) == hipSuccess) ms[i] += t;
-    }
+  for (int i = 0; ms && i < 3; ++i) {
+    float t = 0.f;
+    if (hipEventElapsedTime(&t, m.ev[i], m.ev[i + 1]) == hipSuccess) ms[i] += t;
   }
+  *out = TailOutput{};
   out->n_reads = n, out->n_records = nr;
-  out->rec_begin = m.h_rec_begin.as<uint32_t>();
-  out->flag = m.h_flag.as<uint16_t>(), out->tid = m.h_tid.as<uint32_t>(), out->pos0 = m.h_pos0.as<uint32_t>();
-  out->nm = m.h_nm.as<uint8_t>();
-  out->cigar_off = m.h_cigar_off.as<uint32_t>(), out->cigar = m.h_cigar.as<uint32_t>();
-  out->md_off = m.h_md_off.as<uint32_t>(), out->md = m.h_md.as<char>();
+  if (copy_records) {
+    out->rec_begin = m.h_rec_begin.as<uint32_t>();
+    out->flag = m.h_flag.as<uint16_t>(), out->tid = m.h_tid.as<uint32_t>(), out->pos0 = m.h_pos0.as<uint32_t>();
+    out->nm = m.h_nm.as<uint8_t>();
+    out->cigar_off = m.h_cigar_off.as<uint32_t>(), out->cigar = m.h_cigar.as<uint32_t>();
+    out->md_off = m.h_md_off.as<uint32_t>(), out->md = m.h_md.as<char>();
+  }
   return FEM_OK;
 }
-
 
 int Tail::reserve_text(uint64_t bytes, std::string *err) {
   if (!impl_) impl_ = new (std::nothrow) Impl();
@@ -2357,27 +2381,7 @@ int Tail::sam(const TailInput &in, const SamInput &names, hipStream_t stream, in
               bool wait, TextGate *gate, bool paired) {
   if (!impl_ || !out) return FEM_ERR_STATE;
   Impl &m = *impl_;
-  if (paired && !m.paired) {
-    if (err) *err = "the records were not paired (Tail::pair)";
-    return FEM_ERR_STATE;
-  }
-  const uint32_t nr = m.last_nr + (paired ? m.n_resc : 0u);  // (paired: lines, the rescued records' included)
-  const size_t r1 = (size_t)nr + 1;
-  for (hipEvent_t &e : m.ev)
-    if (!e) TAIL_TRY(hipEventCreate(&e));
-  TAIL_TRY(m.line_len.need(r1 * 8));
-  TAIL_TRY(m.line_off.need(r1 * 8));
-  TAIL_TRY(m.h_ctl.need(32));
-  size_t tmp = 0;
-  TAIL_TRY(rocprim::exclusive_scan(nullptr, tmp, m.line_len.as<unsigned long long>(), m.line_off.as<unsigned long long>(), 0ull, r1,
-                                   rocprim::plus<unsigned long long>(), stream));
-  TAIL_TRY(m.scan_tmp.need(std::max<size_t>(tmp, 16)));
   SamParams p{};
-  p.n_records = nr, p.rec_begin = m.rec_begin.as<uint32_t>(), p.s_read = m.s_read.as<uint32_t>();
-  p.flag = m.flag.as<uint16_t>(), p.tid = m.tid.as<uint32_t>(), p.pos0 = m.pos0.as<uint32_t>(), p.nm = m.nm.as<uint8_t>();
-  p.cigar_off = m.cigar_off.as<uint32_t>(), p.cigar = m.cigar.as<uint32_t>(), p.md_off = m.md_off.as<uint32_t>(), p.md = m.md.as<uint8_t>();
-  p.bases = in.bases, p.read_off = in.read_off;
-  p.quals = names.quals, p.names = names.names, p.name_off = names.name_off, p.ref_names = names.ref_names, p.ref_name_off = names.ref_name_off;
   const bool hole = names.qual_hole && !names.quals;
   const size_t n_reads1 = (size_t)m.last_n + 1;
   if (hole) {  // where each read's QUAL field starts (all ones: the read has no record)
@@ -2386,22 +2390,11 @@ int Tail::sam(const TailInput &in, const SamInput &names, hipStream_t stream, in
     TAIL_TRY(hipMemsetAsync(m.qual_at.p, 0xFF, n_reads1 * 8, stream));
     p.qual_at = m.qual_at.as<unsigned long long>(), p.qual_hole = 1u;
   }
-  p.line_len = m.line_len.as<unsigned long long>(), p.line_off = m.line_off.as<unsigned long long>();
-  p.asserted = m.ctl.as<uint32_t>() + 2;  // (ctl[2] is zero after a successful run())
-  if (paired) {
-    p.perm = m.perm.as<uint32_t>(), p.pflag = m.pflag.as<uint16_t>(), p.mtid = m.mtid.as<uint32_t>(), p.mpos0 = m.mpos0.as<uint32_t>();
-    p.tlen = m.tlen.as<int32_t>();
-  }
+  int rc = m.lines(in, names, paired, nullptr, stream, n_cu, &p, err);
+  if (rc) return rc;
+  const uint32_t nr = p.n_records;
   unsigned long long *h_total = (unsigned long long *)(m.h_ctl.as<uint32_t>() + 6);
-  TAIL_TRY(hipEventRecord(m.ev[0], stream));
-  const dim3 len_grid(std::max<uint32_t>(1u, std::min<uint32_t>((nr + 256u) / 256u, (uint32_t)n_cu * 16u)));
-  if (paired) hipLaunchKernelGGL(sam_len_kernel<true>, len_grid, dim3(256), 0, stream, p);
-  else hipLaunchKernelGGL(sam_len_kernel<false>, len_grid, dim3(256), 0, stream, p);
-  TAIL_TRY(hipGetLastError());
-  TAIL_TRY(rocprim::exclusive_scan(m.scan_tmp.p, m.scan_tmp.cap, m.line_len.as<unsigned long long>(), m.line_off.as<unsigned long long>(), 0ull,
-                                   r1, rocprim::plus<unsigned long long>(), stream));
   TAIL_TRY(hipMemcpyAsync(h_total, m.line_off.as<unsigned long long>() + nr, 8, hipMemcpyDeviceToHost, stream));
-  TAIL_TRY(hipMemcpyAsync(m.h_ctl.as<uint32_t>() + 2, m.ctl.as<uint32_t>() + 2, 4, hipMemcpyDeviceToHost, stream));
   TAIL_TRY(hipStreamSynchronize(stream));
   const uint64_t total = *h_total;
   TAIL_TRY(m.text.need(std::max<size_t>((size_t)total, 16)));
@@ -2409,31 +2402,12 @@ int Tail::sam(const TailInput &in, const SamInput &names, hipStream_t stream, in
   if (nr) {
     p.text = m.text.as<uint8_t>();
     const uint32_t blocks = (nr + 255u) / 256u;  // a wave per 64 records
-    if (paired) hipLaunchKernelGGL(sam_write_kernel<true>, dim3(blocks), dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL(sam_write_kernel<false>, dim3(blocks), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL(paired ? sam_write_kernel<true> : sam_write_kernel<false>, dim3(blocks), dim3(256), 0, stream, p);
     TAIL_TRY(hipGetLastError());
   }
   TAIL_TRY(hipEventRecord(m.ev[1], stream));
-  if (!m.ev_text) TAIL_TRY(hipEventCreateWithFlags(&m.ev_text, hipEventDisableTiming));
-  static const bool no_gate = getenv("FEM_TESTING") && getenv("FEM_TEXT_NO_GATE");  // (A/B)
-  {
-    std::unique_lock<std::mutex> turn;
-    if (gate && !no_gate) {
-      turn = std::unique_lock<std::mutex>(gate->mu);
-      if (gate->last && gate->last != m.ev_text) TAIL_TRY(hipEventSynchronize(gate->last));  // (this slot's own last text is home: its stream is in order)
-    }
-    // (by the copy engine.  The shader cores' stores into the pinned buffer — no engine to queue in — bring a text home in 7-9.5
-    //  ms where the engine takes 5.4, and FEM map from 130 to 117 Mreads/s.)
-    if (total) TAIL_TRY(hipMemcpyAsync(m.h_text.p, m.text.p, (size_t)total, hipMemcpyDeviceToHost, stream));
-    if (hole) TAIL_TRY(hipMemcpyAsync(m.h_qual_at.p, m.qual_at.p, n_reads1 * 8, hipMemcpyDeviceToHost, stream));
-    TAIL_TRY(hipEventRecord(m.ev_text, stream));
-    if (gate) gate->last = m.ev_text;
-  }
-  if (wait) TAIL_TRY(hipStreamSynchronize(stream));
-  if (ms && wait) {
-    float t = 0.f;
-    if (hipEventElapsedTime(&t, m.ev[0], m.ev[1]) == hipSuccess) *ms += t;
-  }
+  rc = m.send_home(m.text.p, (size_t)total, m.h_qual_at.p, m.qual_at.p, hole ? n_reads1 * 8 : 0, stream, wait, gate, wait ? ms : nullptr, err);
+  if (rc) return rc;
   out->text = m.h_text.as<char>(), out->len = total, out->n_asserted = m.h_ctl.as<uint32_t>()[2];
   out->qual_at = hole ? m.h_qual_at.as<uint64_t>() : nullptr;
   return FEM_OK;
@@ -2443,51 +2417,19 @@ int Tail::bam(const TailInput &in, const SamInput &names, int level, hipStream_t
               double *ms, bool wait, TextGate *gate, bool paired) {
   if (!impl_ || !out) return FEM_ERR_STATE;
   Impl &m = *impl_;
-  if (paired && !m.paired) {
-    if (err) *err = "the records were not paired (Tail::pair)";
-    return FEM_ERR_STATE;
-  }
   if (!names.quals || names.qual_hole) {
     if (err) *err = "BAM records need the qualities on the device";
     return FEM_ERR_STATE;
   }
-  const uint32_t nr = m.last_nr + (paired ? m.n_resc : 0u);
-  const size_t r1 = (size_t)nr + 1;
-  for (hipEvent_t &e : m.ev)
-    if (!e) TAIL_TRY(hipEventCreate(&e));
-  TAIL_TRY(m.line_len.need(r1 * 8));
-  TAIL_TRY(m.line_off.need(r1 * 8));
-  TAIL_TRY(m.h_line_off.need(r1 * 8));
-  TAIL_TRY(m.h_ctl.need(32));
   TAIL_TRY(m.bam_ctl.need(16));
-  size_t tmp = 0;
-  TAIL_TRY(rocprim::exclusive_scan(nullptr, tmp, m.line_len.as<unsigned long long>(), m.line_off.as<unsigned long long>(), 0ull, r1,
-                                   rocprim::plus<unsigned long long>(), stream));
-  TAIL_TRY(m.scan_tmp.need(std::max<size_t>(tmp, 16)));
   SamParams p{};
-  p.n_records = nr, p.rec_begin = m.rec_begin.as<uint32_t>(), p.s_read = m.s_read.as<uint32_t>();
-  p.flag = m.flag.as<uint16_t>(), p.tid = m.tid.as<uint32_t>(), p.pos0 = m.pos0.as<uint32_t>(), p.nm = m.nm.as<uint8_t>();
-  p.cigar_off = m.cigar_off.as<uint32_t>(), p.cigar = m.cigar.as<uint32_t>(), p.md_off = m.md_off.as<uint32_t>(), p.md = m.md.as<uint8_t>();
-  p.bases = in.bases, p.read_off = in.read_off;
-  p.quals = names.quals, p.names = names.names, p.name_off = names.name_off, p.ref_names = names.ref_names, p.ref_name_off = names.ref_name_off;
-  p.line_len = m.line_len.as<unsigned long long>(), p.line_off = m.line_off.as<unsigned long long>();
-  p.asserted = m.ctl.as<uint32_t>() + 2;  // (ctl[2] is zero after a successful run())
-  if (paired) {
-    p.perm = m.perm.as<uint32_t>(), p.pflag = m.pflag.as<uint16_t>(), p.mtid = m.mtid.as<uint32_t>(), p.mpos0 = m.mpos0.as<uint32_t>();
-    p.tlen = m.tlen.as<int32_t>();
-  }
   uint32_t *bad_name = m.bam_ctl.as<uint32_t>();
-  TAIL_TRY(hipMemsetAsync(bad_name, 0, 4, stream));
-  TAIL_TRY(hipEventRecord(m.ev[0], stream));
-  const dim3 len_grid(std::max<uint32_t>(1u, std::min<uint32_t>((nr + 256u) / 256u, (uint32_t)n_cu * 16u)));
-  if (paired) hipLaunchKernelGGL(bam_len_kernel<true>, len_grid, dim3(256), 0, stream, p, m.last_n, bad_name);
-  else hipLaunchKernelGGL(bam_len_kernel<false>, len_grid, dim3(256), 0, stream, p, m.last_n, bad_name);
-  TAIL_TRY(hipGetLastError());
-  TAIL_TRY(rocprim::exclusive_scan(m.scan_tmp.p, m.scan_tmp.cap, m.line_len.as<unsigned long long>(), m.line_off.as<unsigned long long>(), 0ull,
-                                   r1, rocprim::plus<unsigned long long>(), stream));
+  int rc = m.lines(in, names, paired, bad_name, stream, n_cu, &p, err);
+  if (rc) return rc;
+  const uint32_t nr = p.n_records;
   // the record offsets come home with the total: the member cuts are made here
-  TAIL_TRY(hipMemcpyAsync(m.h_line_off.p, m.line_off.p, r1 * 8, hipMemcpyDeviceToHost, stream));
-  TAIL_TRY(hipMemcpyAsync(m.h_ctl.as<uint32_t>() + 2, m.ctl.as<uint32_t>() + 2, 4, hipMemcpyDeviceToHost, stream));
+  TAIL_TRY(m.h_line_off.need(((size_t)nr + 1) * 8));
+  TAIL_TRY(hipMemcpyAsync(m.h_line_off.p, m.line_off.p, ((size_t)nr + 1) * 8, hipMemcpyDeviceToHost, stream));
   TAIL_TRY(hipMemcpyAsync(m.h_ctl.as<uint32_t>() + 3, bad_name, 4, hipMemcpyDeviceToHost, stream));
   TAIL_TRY(hipStreamSynchronize(stream));
   if (m.h_ctl.as<uint32_t>()[3]) {
@@ -2505,26 +2447,11 @@ int Tail::bam(const TailInput &in, const SamInput &names, int level, hipStream_t
   femz::bgzf_cut(m.h_line_off.as<uint64_t>(), nr, total, &m.cuts);
   uint64_t len = 0;
   float ms_z = 0.f;
-  int rc = m.bgzf.compress(m.text.as<uint8_t>(), total, m.cuts, level, stream, &len, err, ms ? &ms_z : nullptr);
-  if (rc) return rc;
+  if ((rc = m.bgzf.compress(m.text.as<uint8_t>(), total, m.cuts, level, stream, &len, err, ms ? &ms_z : nullptr))) return rc;
   TAIL_TRY(m.h_text.need(std::max<size_t>((size_t)len, 1u << 20)));
-  if (!m.ev_text) TAIL_TRY(hipEventCreateWithFlags(&m.ev_text, hipEventDisableTiming));
-  {
-    std::unique_lock<std::mutex> turn;
-    if (gate) {
-      turn = std::unique_lock<std::mutex>(gate->mu);
-      if (gate->last && gate->last != m.ev_text) TAIL_TRY(hipEventSynchronize(gate->last));
-    }
-    if (len) TAIL_TRY(hipMemcpyAsync(m.h_text.p, m.bgzf.out(), (size_t)len, hipMemcpyDeviceToHost, stream));
-    TAIL_TRY(hipEventRecord(m.ev_text, stream));
-    if (gate) gate->last = m.ev_text;
-  }
-  if (wait) TAIL_TRY(hipStreamSynchronize(stream));
-  if (ms) {  // (compress() has waited for the stream: both spans are over)
-    float t = 0.f;
-    if (hipEventElapsedTime(&t, m.ev[0], m.ev[1]) == hipSuccess) ms[0] += t;
-    ms[1] += ms_z;
-  }
+  // (compress() has waited for the stream: both spans are over)
+  if ((rc = m.send_home(m.bgzf.out(), (size_t)len, nullptr, nullptr, 0, stream, wait, gate, ms, err))) return rc;
+  if (ms) ms[1] += ms_z;
   out->data = m.h_text.as<uint8_t>(), out->len = len, out->raw_len = total;
   out->n_blocks = m.cuts.empty() ? 0 : m.cuts.size() - 1;
   out->n_asserted = m.h_ctl.as<uint32_t>()[2];

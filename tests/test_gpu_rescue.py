@@ -261,3 +261,39 @@ def test_cli_rescue_equals_the_model(tmp_path, gz):
     assert r.returncode == 0, r.stderr
     assert out0.read_text(encoding="latin-1") == header + pm.sam_lines(want, n, ["s0", "s1"], r1 + r2, base + base, q1 + q2, 0, 500)
     assert "rescued" not in r.stderr
+
+
+def test_fetch_timing_counts():
+    """With timing on, every fetch advances the launch counts of exactly its kernel-time ids (include/fem_hip.h), by one
+    each: fetch_records 3-5; fetch_sam 3-5 and 7 when it waits; fetch_bam 3-5, 11 and 12; a text of read pairs also 9, and
+    10 with mate rescue."""
+    rng, dev, ref, idx, seqs, names = _setup(28, False)
+    try:
+        n, e = 150, 2
+        r1, r2 = make_rescue_pairs(rng, seqs, n, 100, 100, e, 8, 500)
+        reads = r1 + r2
+        batch = fo.ReadBatch(reads)
+        q = np.full(len(batch.bases), ord("I"), np.uint8)
+        dev.set_pairs(0, 500, slot=1)
+        dev.set_rescue(8, slot=1)
+        dev.set_pairs(0, 500, slot=2)
+        dev.set_timing(True)
+
+        def advanced(fetch):
+            before = [dev.kernel_time(k)[1] for k in range(13)]
+            fetch()
+            after = [dev.kernel_time(k)[1] for k in range(13)]
+            return {k: after[k] - before[k] for k in range(13) if after[k] != before[k]}
+
+        for slot, paired, rescue in ((0, False, False), (1, True, True), (2, True, False)):
+            dev.stage_reads(batch.bases, batch.off, slot=slot)
+            dev.stage_text(q, ["r%d" % i for i in range(2 * n)], slot=slot)
+            dev.map_staged(e=e, slot=slot)
+            dev.sync(slot)
+            text_ids = {3, 4, 5} | ({9} if paired else set()) | ({10} if rescue else set())
+            assert advanced(lambda: dev.fetch_records(slot=slot)) == dict.fromkeys({3, 4, 5}, 1)
+            assert advanced(lambda: dev.fetch_sam(slot=slot)) == dict.fromkeys(text_ids | {7}, 1)
+            assert advanced(lambda: dev.fetch_sam(slot=slot, nowait=True)) == dict.fromkeys(text_ids, 1)
+            assert advanced(lambda: dev.fetch_bam(slot=slot)) == dict.fromkeys(text_ids | {11, 12}, 1)
+    finally:
+        dev.close()

@@ -29,7 +29,7 @@ try:
         m = re.search(r"Time: ([0-9.]+)s", r.stderr)
         print("==== %s %d reads [%s]: rc %d Time %s -> %.1f Mreads/s (wall %.2f)" % (key, n_reads, spec, r.returncode, m.group(1) if m else None, n_reads / float(m.group(1)) / 1e6 if m else 0, time.perf_counter() - t0))
         for l in r.stderr.split("\n"):
-            if l.startswith("[FEM]") or l.startswith("TL") or l.startswith("[fetch_sam]") or l.startswith("[tail]"):
+            if l.startswith("[FEM]") or l.startswith("TL") or l.startswith("[fetch_") or l.startswith("[tail]"):
                 print(l)
 finally:
     shutil.rmtree(d, ignore_errors=True)
