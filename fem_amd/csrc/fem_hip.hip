@@ -42,7 +42,7 @@ constexpr uint32_t kMaxReadLen = 1024;
 constexpr size_t kFrontPad = 16;  // kernels fetch a reverse-strand chunk from up to 15 bytes in front of a read
 constexpr uint32_t kXcapSmall = 512, kFcap = 128, kCcap = 128;
 
-constexpr int kTimedKernels = 13;  // fem_dev_kernel_time ids: 0 seed (join), 1 verify, 2 generic seed, 3-5 tail, 6 pack_results_kernel (round 5; the count kernel of rounds 1-2 before), 7 SAM text, 8 seed selection, 9 pairing, 10 mate rescue, 11 BAM records, 12 BGZF
+constexpr int kTimedKernels = 14;  // fem_dev_kernel_time ids: 0 seed (join), 1 verify, 2 generic seed, 3-5 tail, 6 pack_results_kernel (round 5; the count kernel of rounds 1-2 before), 7 SAM text, 8 seed selection, 9 pairing, 10 mate rescue, 11 BAM records, 12 BGZF, 13 MAPQ
 struct TimedLaunch {
   int kernel;
   hipEvent_t start, stop;
@@ -160,6 +160,7 @@ struct Slot {
   bool rescue = false;
   int32_t rescue_edits = 0;
   uint64_t n_rescued = 0;  // of the slot's last paired SAM text (or fetch_pairs)
+  bool mapq = false;  // fem_dev_set_mapq: MAPQ from the hit strata in the slot's SAM text and BAM records
   // fem_dev_fetch_pairs: the records in output order (host copies, valid until the slot's next fetch_pairs)
   std::vector<uint16_t> pr_flag;
   std::vector<uint32_t> pr_tid, pr_pos0, pr_cigar_off, pr_cigar, pr_md_off;
@@ -2308,7 +2309,7 @@ static int tail_records(fem_dev *h, int slot, const void *out, bool copy_records
   if (paired) {
     femt::RescueInput ri{};
     if ((rc = rescue_input(h, s, &ri))) return rc;
-    if ((rc = s.tail->pair(s.min_insert, s.max_insert, f->stream, &err, s.rescue ? &ri : nullptr))) return fail(h, rc, err);
+    if ((rc = s.tail->pair(s.min_insert, s.max_insert, f->stream, &err, s.rescue ? &ri : nullptr, s.mapq))) return fail(h, rc, err);
   }
   if (text) HIP_TRY(h, hipStreamWaitEvent(f->stream, s.ev_text_staged, 0));  // qualities and names came on the slot's text stream
   f->ms_run = since();
@@ -2321,11 +2322,11 @@ static int tail_records(fem_dev *h, int slot, const void *out, bool copy_records
 
 // The names (and qualities, unless the caller keeps them: qual_hole) the slot's text is rendered with.
 static femt::SamInput sam_input(const fem_dev *h, const Slot &s) {
-  return {s.host_quals ? nullptr : s.d_quals, s.d_names, s.d_name_off, h->d_ref_names, h->d_ref_name_off, s.host_quals};
+  return {s.host_quals ? nullptr : s.d_quals, s.d_names, s.d_name_off, h->d_ref_names, h->d_ref_name_off, s.host_quals, s.mapq};
 }
 
 // What follows a text's sam() / bam() (tag: the caller, for FEM_FETCH_TIMES): the pair counts, the event the slot's next text
-// stage waits for (commit_text), the kernel times: 3-5, n_ms of the text's own from id `id` on, 9 and 10 when paired.
+// stage waits for (commit_text), the kernel times: 3-5, n_ms of the text's own from id `id` on, 9 and 10 when paired, 13 with MAPQ.
 static int text_done(fem_dev *h, int slot, const TailFront &f, const char *tag, int id, const double *ms, int n_ms) {
   Slot &s = h->slot[slot];
   s.n_proper = s.paired ? s.tail->n_proper() : 0;  // (sam() and bam() have waited for the stream once, after sizing the text)
@@ -2342,6 +2343,7 @@ static int text_done(fem_dev *h, int slot, const TailFront &f, const char *tag, 
     for (int i = 0; i < n_ms; ++i) h->t_ms[id + i] += ms[i], h->t_n[id + i] += 1;
     if (s.paired) h->t_ms[9] += s.tail->pair_ms(), h->t_n[9] += 1;
     if (s.paired && s.rescue) h->t_ms[10] += s.tail->rescue_ms(), h->t_n[10] += 1;
+    if (s.mapq) h->t_ms[13] += s.tail->mapq_ms(), h->t_n[13] += 1;  // (its events precede the text's sizing, which sam() and bam() wait for)
   }
   return FEM_OK;
 }
@@ -2466,6 +2468,14 @@ int fem_dev_set_rescue(fem_dev *h, int slot, const fem_rescue_params *rp) {
   }
   if (rp->max_edits < 0 || rp->max_edits > 15) return fail(h, FEM_ERR_INVALID, "rescue edit bound out of range (0 <= max_edits <= 15)");
   s.rescue = true, s.rescue_edits = rp->max_edits;
+  return FEM_OK;
+}
+
+int fem_dev_set_mapq(fem_dev *h, int slot, int on) {
+  int rc = check_slot(h, slot);
+  if (rc) return rc;
+  FEM_LOCK(h);
+  h->slot[slot].mapq = on != 0;
   return FEM_OK;
 }
 

@@ -6,7 +6,7 @@
 // next batch; record order in the SAM file follows completion, parity is modulo record order); `--batch N` sets reads
 // per batch.  `--read2 STR` maps read pairs (record i of --read1 and of --read2 are the two mates of pair i), with -I / -X the
 // accepted insert size: the pairing and the paired SAM text on the device (fem_dev_set_pairs); `--rescue INT` adds mate rescue
-// at INT edits (fem_dev_set_rescue).
+// at INT edits (fem_dev_set_rescue).  `--mapq` writes mapping qualities made on the device (fem_dev_set_mapq) instead of 255.
 #include <errno.h>
 #include <fcntl.h>
 #include <getopt.h>
@@ -75,6 +75,7 @@ void usage_map() {
   fprintf(stderr, "        -X, --maxins INT  maximum insert size of a proper pair [500]\n");
   fprintf(stderr, "        --rescue INT  with --read2: search a mate without records in its mate's insert window at INT (0-15) edits\n");
   fprintf(stderr, "        --bam[=INT]   write BAM instead of SAM: BGZF level 1 (default) or 0 (uncompressed)\n");
+  fprintf(stderr, "        --mapq        write mapping qualities (0-60) from the hits' edit distances instead of 255\n");
   fprintf(stderr, "        -o       STR  Output SAM file \n\n");
 }
 
@@ -277,6 +278,7 @@ int map_main(int argc, char **argv) {
   long long rescue_edits = 0;  // --rescue (mate rescue at this many edits, fem_dev_set_rescue)
   bool rescue_given = false;
   int bam_level = -1;  // --bam[=LEVEL]: BAM records and BGZF members made on the device (fem_dev_fetch_bam); -1: SAM
+  bool mapq = false;   // --mapq: MAPQ from the hit strata, made on the device (fem_dev_set_mapq); else 255 as the reference
   fem_params params{12, 3, 2, 1};  // src/FEM_map.c:67-70: k and step are fixed, whatever the index header says
   int n_threads = 1, n_gpus = 1;
   // reads per batch: 250 k fills the pipeline soonest on small inputs; a batch costs three host round trips on its way through
@@ -290,7 +292,8 @@ int map_main(int argc, char **argv) {
                                      {"gpus", required_argument, nullptr, 'G'},  {"batch", required_argument, nullptr, 'B'},
                                      {"read2", required_argument, nullptr, 'c'}, {"minins", required_argument, nullptr, 'I'},
                                      {"maxins", required_argument, nullptr, 'X'}, {"rescue", required_argument, nullptr, 'R'},
-                                     {"bam", optional_argument, nullptr, 'Z'},  {nullptr, 0, nullptr, 0}};
+                                     {"bam", optional_argument, nullptr, 'Z'},  {"mapq", no_argument, nullptr, 'Q'},
+                                     {nullptr, 0, nullptr, 0}};
   int c, oi = 0;
   while ((c = getopt_long(argc, argv, short_opt, long_opt, &oi)) >= 0) {
     switch (c) {
@@ -310,6 +313,7 @@ int map_main(int argc, char **argv) {
       case 'Z':
         bam_level = !optarg ? 1 : strcmp(optarg, "0") == 0 ? 0 : strcmp(optarg, "1") == 0 ? 1 : -2;  // (-2: refused below)
         break;
+      case 'Q': mapq = true; break;
       case 'e': params.e = atoi(optarg); break;
       case 't': n_threads = atoi(optarg); break;
       case 'a': params.a = atoi(optarg); break;
@@ -354,6 +358,13 @@ int map_main(int argc, char **argv) {
     const char *x = getenv(v);
     if (bam && x && x[0] == '1') {
       fprintf(stderr, "--bam is not supported with %s=1: BAM records are made on the device, with the qualities there.\n", v);
+      exit(EXIT_FAILURE);
+    }
+  }
+  for (const char *v : {"FEM_HOST_TAIL", "FEM_HOST_FORMAT"}) {  // (the host formatter has no MAPQ path)
+    const char *x = getenv(v);
+    if (mapq && x && x[0] == '1') {
+      fprintf(stderr, "--mapq is not supported with %s=1: mapping qualities are made on the device, with its SAM text or BAM.\n", v);
       exit(EXIT_FAILURE);
     }
   }
@@ -462,6 +473,7 @@ int map_main(int argc, char **argv) {
           if (!rc && device_text) rc = fem_dev_reserve_text(devs[(size_t)g], sl, reads_cap0, bases_cap0, names_cap0, batch_bytes + batch_bytes / 4);
           // (a read over the device's limit among the first records: no reservation, the staging of its batch names the read)
           if (!rc && device_text && res_reads && res_len <= max_read_len) rc = fem_dev_reserve_batch(devs[(size_t)g], sl, res_reads, res_reads + res_reads / 8, res_len, &params);
+          if (!rc && mapq) rc = fem_dev_set_mapq(devs[(size_t)g], sl, 1);
           if (!rc && paired) {
             const fem_pair_params pp{(int32_t)min_insert, (int32_t)max_insert};
             rc = fem_dev_set_pairs(devs[(size_t)g], sl, &pp);

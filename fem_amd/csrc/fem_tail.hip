@@ -1170,6 +1170,8 @@ struct SamParams {
   const uint16_t *pflag;
   const uint32_t *mtid, *mpos0;  // 0xFFFFFFFF: the other mate has no record
   const int32_t *tlen;
+  // MAPQ (fem_dev_set_mapq; nullptr: 255 on every line): single-end per read, its primary line's (the others 0); kPair per line
+  const uint8_t *mapq;
 };
 
 __device__ __forceinline__ uint32_t dec_digits(uint32_t v) {
@@ -1209,6 +1211,13 @@ __device__ __forceinline__ LineHead line_head(const SamParams &p, uint32_t j) {
           (uint32_t)(p.name_off[r + 1] - p.name_off[r])};
 }
 
+// The MAPQ line j prints (r: its read)
+template <bool kPair>
+__device__ __forceinline__ uint32_t line_mapq(const SamParams &p, uint32_t j, uint32_t r, bool primary) {
+  if (!p.mapq) return 255u;
+  return kPair ? p.mapq[j] : primary ? p.mapq[r] : 0u;
+}
+
 template <bool kPair>
 __global__ void __launch_bounds__(256) sam_len_kernel(SamParams p) {
   const uint32_t stride = gridDim.x * blockDim.x;
@@ -1227,8 +1236,9 @@ __global__ void __launch_bounds__(256) sam_len_kernel(SamParams p) {
     const uint32_t md_len = p.md_off[rec + 1] - p.md_off[rec];
     const uint32_t seq_qual = primary && L > 0 ? L + 1u + (p.quals || p.qual_hole ? L : 1u) : 3u;
     const uint32_t mate = kPair ? mate_cols_len(p, j, t) : 5u;
-    p.line_len[j] = (unsigned long long)name_len + 1u + dec_digits(flag & 0x7FFFu) + 1u + rname_len + 1u + dec_digits(p.pos0[rec] + 1u) + 5u + cig +
-                    2u + mate + seq_qual + 6u + dec_digits(p.nm[rec]) + 6u + md_len + 1u;
+    const uint32_t mq = line_mapq<kPair>(p, j, r, primary);
+    p.line_len[j] = (unsigned long long)name_len + 1u + dec_digits(flag & 0x7FFFu) + 1u + rname_len + 1u + dec_digits(p.pos0[rec] + 1u) + 2u +
+                    dec_digits(mq) + cig + 2u + mate + seq_qual + 6u + dec_digits(p.nm[rec]) + 6u + md_len + 1u;
   }
 }
 
@@ -1269,6 +1279,7 @@ __global__ void __launch_bounds__(256) sam_write_kernel(SamParams p) {
   if (n_ops > 1) op_b = p.cigar[c0 + 1];
   if (n_ops > 2) op_c = p.cigar[c0 + 2];
   const bool seq = primary && L > 0;
+  const uint32_t mq = line_mapq<kPair>(p, j, r, primary);
   uint32_t cig = 0;
   if (n_ops <= 3u) {
     if (n_ops > 0) cig += dec_digits(op_a >> 4) + 1u;
@@ -1282,7 +1293,7 @@ __global__ void __launch_bounds__(256) sam_write_kernel(SamParams p) {
   const uint32_t o_flag = name_len + 1u;
   const uint32_t o_rname = o_flag + dec_digits(flag) + 1u;
   const uint32_t o_pos = o_rname + rname_len + 1u;
-  const uint32_t o_cig = o_pos + dec_digits(pos1) + 5u;
+  const uint32_t o_cig = o_pos + dec_digits(pos1) + 2u + dec_digits(mq);
   const uint32_t o_seq = o_cig + cig + 2u + (kPair ? mate_cols_len(p, j, t) : 5u);
   const uint32_t o_nm = o_seq + (seq ? L + 1u + (p.quals || p.qual_hole ? L : 1u) : 3u) + 6u;
   const uint32_t o_md = o_nm + dec_digits(nm) + 6u;
@@ -1292,7 +1303,8 @@ __global__ void __launch_bounds__(256) sam_write_kernel(SamParams p) {
     put_dec(w + o_flag, flag)[0] = '\t';
     w[o_rname + rname_len] = '\t';
     uint8_t *q = put_dec(w + o_pos, pos1);
-    q[0] = '\t', q[1] = '2', q[2] = '5', q[3] = '5', q[4] = '\t';
+    q[0] = '\t';
+    put_dec(q + 1, mq)[0] = '\t';
     q = w + o_cig;
     if (n_ops == 0) *q++ = '*';
     if (n_ops <= 3u) {
@@ -1417,7 +1429,7 @@ __global__ void __launch_bounds__(256) sam_write_kernel(SamParams p) {
 
 // ---------------------------------------------------------------------------------------------------------
 // BAM records (SAM/BAM specification §4.2): the same lines as the SAM kernels, field for field.  refID pos = tid pos0,
-// l_read_name = name + NUL, MAPQ 255, bin = reg2bin(pos0, end0) (end0 = pos0 + the M/D/N/=/X lengths, pos0 + 1 for none),
+// l_read_name = name + NUL, MAPQ 255 (or line_mapq's), bin = reg2bin(pos0, end0) (end0 = pos0 + the M/D/N/=/X lengths, pos0 + 1 for none),
 // the device's CIGAR words as they are, FLAG & 0x7FFF, l_seq = L where SAM prints SEQ else 0, mate columns -1 -1 0 (single-end)
 // or pair_kernel's, SEQ in 4-bit codes (the SAM round trip's letters), QUAL - 33 (0xFF where SAM prints *), NM:C, MD:Z.
 // ---------------------------------------------------------------------------------------------------------
@@ -1471,7 +1483,7 @@ __global__ void __launch_bounds__(256) bam_write_kernel(SamParams p) {
   const uint32_t ls = primary ? L : 0u;
   const uint32_t c0 = p.cigar_off[rec], n_ops = p.cigar_off[rec + 1] - c0;
   const uint32_t m0 = p.md_off[rec], md_len = p.md_off[rec + 1] - m0;
-  const uint32_t tid = p.tid[rec], pos0 = p.pos0[rec], nm = p.nm[rec];
+  const uint32_t tid = p.tid[rec], pos0 = p.pos0[rec], nm = p.nm[rec], mq = line_mapq<kPair>(p, j, r, primary);
   uint32_t span = 0;
   for (uint32_t c = ln; c < n_ops; c += 64u) {
     const uint32_t op = p.cigar[c0 + c], o = op & 0xFu;
@@ -1486,7 +1498,7 @@ __global__ void __launch_bounds__(256) bam_write_kernel(SamParams p) {
   uint8_t *w = p.text + at;
   if (ln < 36u) {
     const uint32_t q = ln >> 2;
-    const uint32_t v = q == 0 ? size - 4u : q == 1 ? tid : q == 2 ? pos0 : q == 3 ? (name_len + 1u) | 255u << 8 | bin << 16
+    const uint32_t v = q == 0 ? size - 4u : q == 1 ? tid : q == 2 ? pos0 : q == 3 ? (name_len + 1u) | mq << 8 | bin << 16
                      : q == 4 ? n_ops | (fl & 0x7FFFu) << 16 : q == 5 ? ls : q == 6 ? ntid : q == 7 ? npos : tlen;
     w[ln] = (uint8_t)(v >> (8u * (ln & 3u)));
   }
@@ -1545,7 +1557,63 @@ struct PairParams {
   // has one, is record resc_first + resc_before[i] and becomes the only record of its mate that had none
   const uint32_t *resc_before;
   uint32_t resc_first;
+  // MAPQ (pair_kernel<true>): per line, 0 on every line but a mate's primary one, which gets kPairProper | qp for a proper pair
+  // (| kPairOwn when the chosen record may keep its single-end MAPQ: not rescued, NM = d1 of its mate); mapq_kernel finishes it
+  uint8_t *lmq;
 };
+constexpr uint32_t kPairOwn = 0x80u, kPairProper = 0x40u;
+
+// Q(g, c) = min(60, max(0, 20 g - 3 floor(log2 c))) (include/fem_hip.h, fem_dev_set_mapq), c >= 1
+__device__ __forceinline__ uint32_t mapq_q(int32_t gap, uint64_t c) {
+  const int32_t q = 20 * gap - 3 * (63 - __builtin_clzll(c));
+  return q < 0 ? 0u : q > 60 ? 60u : (uint32_t)q;
+}
+
+// The two least distinct values seen and how often each was (the hit strata of a read or of a pair's concordant sums)
+constexpr uint32_t kNoStratum = 0xFFFFFFFFu;
+struct Strata {
+  uint32_t s1 = kNoStratum, s2 = kNoStratum;
+  uint64_t c1 = 0, c2 = 0;
+  __device__ __forceinline__ void add(uint32_t s) {
+    if (s < s1) s2 = s1, c2 = c1, s1 = s, c1 = 1;
+    else if (s == s1) ++c1;
+    else if (s < s2) s2 = s, c2 = 1;
+    else if (s == s2) ++c2;
+  }
+};
+
+__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
+  for (int d = 32; d > 0; d >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, d);
+  return v;
+}
+__device__ __forceinline__ uint32_t wave_min32(uint32_t v) {
+  for (int d = 32; d > 0; d >>= 1) {
+    const uint32_t o = (uint32_t)__shfl_xor(v, d);
+    v = o < v ? o : v;
+  }
+  return v;
+}
+
+// The wave's strata from each lane's (lanes whose least value is above the wave's least hold their own least as the second)
+__device__ __forceinline__ Strata wave_strata(const Strata &x) {
+  Strata w;
+  w.s1 = wave_min32(x.s1);
+  w.c1 = wave_sum64(x.s1 == w.s1 ? x.c1 : 0u);
+  w.s2 = wave_min32(x.s1 == w.s1 ? x.s2 : x.s1);
+  w.c2 = wave_sum64(w.s2 == kNoStratum ? 0u : x.s1 == w.s2 ? x.c1 : x.s2 == w.s2 ? x.c2 : 0u);
+  return w;
+}
+
+// qp of a proper pair from the strata of its concordant sums
+__device__ __forceinline__ uint32_t pair_qp(const Strata &w) {
+  return w.c1 >= 2u ? 0u : w.s2 == kNoStratum ? 60u : mapq_q((int32_t)(w.s2 - w.s1), w.c2);
+}
+
+// The byte pair_kernel<true> leaves on a mate's primary line: chosen record x of a list that starts at x0 (rescued: from a window)
+__device__ __forceinline__ uint32_t pair_mq_byte(const PairParams &p, bool proper, uint32_t qp, uint32_t x0, uint32_t x, bool rescued) {
+  if (!proper) return 0u;
+  return kPairProper | qp | (!rescued && p.nm[x0 + x] == p.nm[x0] ? kPairOwn : 0u);
+}
 
 struct MateRec {
   uint32_t tid, pos0, flag, nm;
@@ -1573,9 +1641,10 @@ __device__ __forceinline__ int64_t concordant(const PairParams &p, const MateRec
   return ins >= p.min_insert && ins <= p.max_insert ? ins : -1;
 }
 
-// lines [first, na + nb) of a pair, every step-th one
+// lines [first, na + nb) of a pair, every step-th one (kMapq: mq_a, mq_b the bytes of the mates' primary lines)
+template <bool kMapq>
 __device__ void write_pair(const PairParams &p, uint32_t a0, uint32_t na, uint32_t b0, uint32_t nb, uint32_t ob, bool proper, uint32_t ca,
-                           uint32_t cb, int64_t insert, uint32_t first, uint32_t step) {
+                           uint32_t cb, int64_t insert, uint32_t first, uint32_t step, uint32_t mq_a = 0, uint32_t mq_b = 0) {
   for (uint32_t u = first; u < na + nb; u += step) {
     const bool m2 = u >= na;
     const uint32_t t = m2 ? u - na : u, c = m2 ? cb : ca;
@@ -1595,6 +1664,7 @@ __device__ void write_pair(const PairParams &p, uint32_t a0, uint32_t na, uint32
     const uint32_t k = ob + u;
     p.perm[k] = rec, p.pflag[k] = (uint16_t)nf, p.mtid[k] = mt, p.mpos0[k] = mp;
     p.tlen[k] = proper && t == 0 ? (int32_t)((fl & 16u) ? -insert : insert) : 0;
+    if (kMapq) p.lmq[k] = (uint8_t)(t ? 0u : m2 ? mq_b : mq_a);
   }
 }
 
@@ -1602,11 +1672,14 @@ __device__ __forceinline__ uint32_t wave_bcast(uint32_t v, uint32_t lane) {
   return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)lane);
 }
 
+// kMapq: also the strata of the concordant sums (cp1 at s1, the least sum s2 above it and cp2 at s2) and each line's MAPQ byte.
+template <bool kMapq>
 __global__ void __launch_bounds__(256) pair_kernel(PairParams p) {
   const uint32_t ln = threadIdx.x & 63u;
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   const bool live = i < p.n_pairs;
   uint32_t a0 = 0, na = 0, b0 = 0, nb = 0, ob = 0;
+  uint32_t resc = 0;  // kMapq: 1 = list A is a rescued record, 2 = list B
   if (live) {
     const uint32_t mid = p.rec_begin[p.n_pairs];
     a0 = p.rec_begin[i], na = p.rec_begin[i + 1] - a0;
@@ -1616,8 +1689,8 @@ __global__ void __launch_bounds__(256) pair_kernel(PairParams p) {
       const uint32_t before = p.resc_before[i], kept = p.resc_before[i + 1] - before;
       ob += before;
       if (kept) {
-        if (na == 0) a0 = p.resc_first + before, na = 1;
-        else b0 = p.resc_first + before, nb = 1;
+        if (na == 0) a0 = p.resc_first + before, na = 1, resc = 1;
+        else b0 = p.resc_first + before, nb = 1, resc = 2;
       }
     }
     p.pair_begin[2u * i] = ob, p.pair_begin[2u * i + 1u] = ob + na;
@@ -1628,6 +1701,7 @@ __global__ void __launch_bounds__(256) pair_kernel(PairParams p) {
   if (live && !big) {  // the lane alone: a ascending, b ascending, only a smaller sum replaces (the tie rule)
     uint32_t best = 0xFFFFFFFFu, ca = 0, cb = 0;
     int64_t ins = -1;
+    Strata st;
     for (uint32_t a = 0; a < na; ++a) {
       const MateRec ra = mate_rec(p, a0 + a);
       if (ra.flag & 0x8000u) continue;
@@ -1635,23 +1709,32 @@ __global__ void __launch_bounds__(256) pair_kernel(PairParams p) {
         const MateRec rb = mate_rec(p, b0 + b);
         const int64_t x = concordant(p, ra, rb);
         if (x >= 0 && ra.nm + rb.nm < best) best = ra.nm + rb.nm, ca = a, cb = b, ins = x;
+        if (kMapq && x >= 0) st.add(ra.nm + rb.nm);
       }
     }
     proper_here = best != 0xFFFFFFFFu;
-    write_pair(p, a0, na, b0, nb, ob, proper_here, ca, cb, ins, 0u, 1u);
+    if (kMapq) {
+      const uint32_t qp = pair_qp(st);
+      write_pair<true>(p, a0, na, b0, nb, ob, proper_here, ca, cb, ins, 0u, 1u, pair_mq_byte(p, proper_here, qp, a0, ca, resc == 1),
+                       pair_mq_byte(p, proper_here, qp, b0, cb, resc == 2));
+    } else {
+      write_pair<false>(p, a0, na, b0, nb, ob, proper_here, ca, cb, ins, 0u, 1u);
+    }
   }
   // pairs with many combinations (repeats): the wave, one pair after the other; the lanes stride over the longer list, each
-  // walks the shorter one; the least (nm sum, a, b) in two steps: (nm sum << 32 | a), then b among the lanes that hold it
+  // walks the shorter one; the least (nm sum, a, b) in two steps: (nm sum << 32 | a), then b among the lanes that hold it;
+  // kMapq: each lane's strata, then the wave's (wave_strata: a sum for cp1, a minimum for s2, a sum for cp2)
   uint64_t todo = __ballot(big);
   while (todo) {
     const uint32_t src = (uint32_t)__builtin_ctzll(todo);
     todo &= todo - 1u;
     const uint32_t A0 = wave_bcast(a0, src), NA = wave_bcast(na, src), B0 = wave_bcast(b0, src), NB = wave_bcast(nb, src);
-    const uint32_t OB = wave_bcast(ob, src);
+    const uint32_t OB = wave_bcast(ob, src), RESC = kMapq ? wave_bcast(resc, src) : 0u;
     const bool lanes_on_a = NA >= NB;
     const uint32_t n_long = lanes_on_a ? NA : NB, n_short = lanes_on_a ? NB : NA;
     uint64_t key = kNoKey;
     uint32_t key_b = 0xFFFFFFFFu;
+    Strata st;
     for (uint32_t u = ln; u < n_long; u += 64u) {
       const MateRec ru = mate_rec(p, (lanes_on_a ? A0 : B0) + u);
       if (ru.flag & 0x8000u) continue;
@@ -1661,6 +1744,7 @@ __global__ void __launch_bounds__(256) pair_kernel(PairParams p) {
         const uint32_t a = lanes_on_a ? u : v, b = lanes_on_a ? v : u;
         const uint64_t k = (uint64_t)(ru.nm + rv.nm) << 32 | a;
         if (k < key || (k == key && b < key_b)) key = k, key_b = b;
+        if (kMapq) st.add(ru.nm + rv.nm);
       }
     }
     uint64_t kmin = key;
@@ -1676,11 +1760,97 @@ __global__ void __launch_bounds__(256) pair_kernel(PairParams p) {
     const bool proper = kmin != kNoKey;
     const uint32_t ca = proper ? (uint32_t)kmin : 0u, cb = proper ? bmin : 0u;
     const int64_t ins = proper ? concordant(p, mate_rec(p, A0 + ca), mate_rec(p, B0 + cb)) : -1;
-    write_pair(p, A0, NA, B0, NB, OB, proper, ca, cb, ins, ln, 64u);
+    if (kMapq) {
+      const uint32_t qp = pair_qp(wave_strata(st));
+      write_pair<true>(p, A0, NA, B0, NB, OB, proper, ca, cb, ins, ln, 64u, pair_mq_byte(p, proper, qp, A0, ca, RESC == 1),
+                       pair_mq_byte(p, proper, qp, B0, cb, RESC == 2));
+    } else {
+      write_pair<false>(p, A0, NA, B0, NB, OB, proper, ca, cb, ins, ln, 64u);
+    }
     if (ln == src) proper_here = proper;
   }
   const uint64_t proper_lanes = __ballot(proper_here);
   if (ln == 0 && proper_lanes) atomicAdd(p.n_proper, (uint32_t)__builtin_popcountll(proper_lanes));
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// MAPQ (fem_dev_set_mapq).  One lane per read: q_se from its records' NM (d1 the first record's, c1 records
+// at d1; d2 the least NM above d1 and c2 records at it, or e + 1 and 1 where there is none): 0 when c1 >= 2, else
+// Q(d2 - d1, c2).  A read with more than kMapqAlone records is taken by its whole wave after the lanes' own reads (repeats:
+// thousands of records).  Single-end: q_se per read, which the text kernels print on the read's primary line.  Pair mode: the
+// byte pair_kernel<true> left on each mate's primary line becomes its MAPQ: q_se without a proper pair, else
+// max(q_x, min(qp, q_x + 40)) with q_x = q_se where the chosen record keeps it (kPairOwn), else 0.
+// ---------------------------------------------------------------------------------------------------------
+constexpr uint32_t kMapqAlone = 32;
+
+struct MapqParams {
+  uint32_t n_reads;
+  int32_t e;
+  const uint32_t *rec_begin;   // n_reads + 1 (run()'s records)
+  const uint8_t *nm;
+  uint8_t *q_read;             // single-end: per read
+  const uint32_t *pair_begin;  // pair mode (else nullptr): n_reads + 1; mate m of pair i has lines [pair_begin[2i+m], pair_begin[2i+m+1])
+  uint8_t *lmq;                // pair mode: pair_kernel<true>'s bytes, per line
+};
+
+__device__ __forceinline__ uint32_t single_q(uint64_t c1, uint32_t d1, uint32_t d2, uint64_t c2, int32_t e) {
+  if (c1 >= 2u) return 0u;
+  if (d2 == kNoStratum) d2 = (uint32_t)e + 1u, c2 = 1u;
+  return mapq_q((int32_t)d2 - (int32_t)d1, c2);
+}
+
+__global__ void __launch_bounds__(256) mapq_kernel(MapqParams p) {
+  const uint32_t ln = threadIdx.x & 63u;
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = r < p.n_reads;
+  uint32_t r0 = 0, nr = 0;
+  if (live) r0 = p.rec_begin[r], nr = p.rec_begin[r + 1] - r0;
+  const bool big = nr > kMapqAlone;
+  uint32_t q = 0;  // (a read without records: no line; in pair mode a rescued mate, whose q_x is 0)
+  if (live && !big && nr) {
+    const uint32_t d1 = p.nm[r0];
+    uint32_t c1 = 0, d2 = kNoStratum, c2 = 0;
+    for (uint32_t k = r0; k < r0 + nr; ++k) {
+      const uint32_t v = p.nm[k];
+      if (v == d1) ++c1;
+      else if (v > d1 && v < d2) d2 = v, c2 = 1;
+      else if (v > d1 && v == d2) ++c2;
+    }
+    q = single_q(c1, d1, d2, c2, p.e);
+  }
+  uint64_t todo = __ballot(big);
+  while (todo) {
+    const uint32_t src = (uint32_t)__builtin_ctzll(todo);
+    todo &= todo - 1u;
+    const uint32_t R0 = wave_bcast(r0, src), NR = wave_bcast(nr, src), d1 = p.nm[R0];
+    uint32_t c1 = 0, d2 = kNoStratum, c2 = 0;
+    for (uint32_t k = ln; k < NR; k += 64u) {
+      const uint32_t v = p.nm[R0 + k];
+      if (v == d1) ++c1;
+      else if (v > d1 && v < d2) d2 = v, c2 = 1;
+      else if (v > d1 && v == d2) ++c2;
+    }
+    const uint64_t C1 = wave_sum64(c1);
+    const uint32_t D2 = wave_min32(d2);
+    const uint64_t C2 = wave_sum64(d2 == D2 && D2 != kNoStratum ? c2 : 0u);
+    if (ln == src) q = single_q(C1, d1, D2, C2, p.e);
+  }
+  if (!live) return;
+  if (!p.pair_begin) {
+    p.q_read[r] = (uint8_t)q;
+    return;
+  }
+  const uint32_t np = p.n_reads / 2u, m = r >= np ? 1u : 0u, i = r - m * np;
+  const uint32_t k0 = p.pair_begin[2u * i + m], k1 = p.pair_begin[2u * i + m + 1u];
+  if (k1 == k0) return;
+  const uint32_t b = p.lmq[k0];
+  uint32_t out = q;
+  if (b & kPairProper) {
+    const uint32_t qx = (b & kPairOwn) ? q : 0u, qp = b & 0x3Fu;
+    out = qp < qx + 40u ? qp : qx + 40u;
+    out = out > qx ? out : qx;
+  }
+  p.lmq[k0] = (uint8_t)out;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1990,6 +2160,8 @@ struct Tail::Impl {
   PinBuf h_ctl, h_rec_begin, h_flag, h_tid, h_pos0, h_nm, h_cigar_off, h_md_off, h_cigar, h_md, h_text, h_qual_at;
   // pair mode (pair()): per line, the pairs' line ranges, the proper-pair counter; their host copies (pair_fetch())
   DevBuf perm, pflag, mtid, mpos0, tlen, pair_begin, pair_ctl;
+  // MAPQ (SamInput::mapq): per read (single-end), per line (pair(): pair_kernel<true>'s bytes, then the MAPQ)
+  DevBuf q_read, lmq;
   PinBuf h_perm, h_pflag, h_mtid, h_mpos0, h_tlen, h_pair_begin, h_pair_ctl;
   // mate rescue (pair() with a RescueInput): candidates, jobs, best hits, the tracebacks' staging, the kept flags and their scans
   DevBuf r_ctl, r_cand, r_jobs, r_best, r_ops, r_md, r_rec, r_ovf, r_o_ops, r_o_md, r_kept, r_scan, r_scan_tmp;
@@ -2003,17 +2175,20 @@ struct Tail::Impl {
   bool paired = false;               // pair() has run on it
   uint32_t n_resc = 0;               // rescued records the last pair() appended behind run()'s (records last_nr ..)
   bool resc_timed = false;           // ... and its rescue kernels ran between ev_resc[0] and ev_resc[1]
+  bool pair_mapq = false;            // the last pair() left its MAPQ bytes in lmq, not yet made MAPQ by a text
+  bool mapq_timed = false;           // the last text's MAPQ kernel ran between ev_mapq[0] and ev_mapq[1]
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   hipEvent_t ev_pair[2] = {nullptr, nullptr};
   hipEvent_t ev_resc[2] = {nullptr, nullptr};
+  hipEvent_t ev_mapq[2] = {nullptr, nullptr};
   hipEvent_t ev_text = nullptr;  // the SAM text has arrived in h_text
   ~Impl() {  // (the buffers free themselves)
-    for (hipEvent_t e : {ev[0], ev[1], ev[2], ev[3], ev_pair[0], ev_pair[1], ev_resc[0], ev_resc[1], ev_text})
+    for (hipEvent_t e : {ev[0], ev[1], ev[2], ev[3], ev_pair[0], ev_pair[1], ev_resc[0], ev_resc[1], ev_mapq[0], ev_mapq[1], ev_text})
       if (e) (void)hipEventDestroy(e);
   }
   // sam() and bam(): the lines of run()'s records, or of pair()'s (rescued records included).  Fills *p (all but the text and
-  // qual_at); from ev[0] on, each line's length (bad_name: as BAM, a name over 254 characters setting it; else as SAM), their
-  // scan into line_off, the count of asserted records to h_ctl[2].
+  // qual_at); names.mapq: first the MAPQ kernel (between ev_mapq[0] and ev_mapq[1]); from ev[0] on, each line's length (bad_name:
+  // as BAM, a name over 254 characters setting it; else as SAM), their scan into line_off, the count of asserted records to h_ctl[2].
   int lines(const TailInput &in, const SamInput &names, bool pair_order, uint32_t *bad_name, hipStream_t stream, int n_cu, SamParams *p,
               std::string *err) {
     if (pair_order && !paired) {
@@ -2041,6 +2216,33 @@ struct Tail::Impl {
     if (pair_order) {
       p->perm = perm.as<uint32_t>(), p->pflag = pflag.as<uint16_t>(), p->mtid = mtid.as<uint32_t>(), p->mpos0 = mpos0.as<uint32_t>();
       p->tlen = tlen.as<int32_t>();
+    }
+    mapq_timed = false;
+    if (names.mapq) {
+      if (pair_order && !pair_mapq) {
+        if (err) *err = "the records were paired without MAPQ (Tail::pair)";
+        return FEM_ERR_STATE;
+      }
+      for (hipEvent_t &e : ev_mapq)
+        if (!e) TAIL_TRY(hipEventCreate(&e));
+      MapqParams q{};
+      q.n_reads = last_n, q.e = in.e, q.rec_begin = rec_begin.as<uint32_t>(), q.nm = nm.as<uint8_t>();
+      if (pair_order) {
+        q.pair_begin = pair_begin.as<uint32_t>(), q.lmq = lmq.as<uint8_t>();
+        p->mapq = lmq.as<uint8_t>();
+        pair_mapq = false;  // (made MAPQ in place: once)
+      } else {
+        TAIL_TRY(q_read.need(std::max<size_t>(last_n, 1)));
+        q.q_read = q_read.as<uint8_t>();
+        p->mapq = q_read.as<uint8_t>();
+      }
+      TAIL_TRY(hipEventRecord(ev_mapq[0], stream));
+      if (last_n) {
+        hipLaunchKernelGGL(mapq_kernel, dim3((last_n + 255u) / 256u), dim3(256), 0, stream, q);
+        TAIL_TRY(hipGetLastError());
+      }
+      TAIL_TRY(hipEventRecord(ev_mapq[1], stream));
+      mapq_timed = true;
     }
     if (bad_name) TAIL_TRY(hipMemsetAsync(bad_name, 0, 4, stream));
     TAIL_TRY(hipEventRecord(ev[0], stream));
@@ -2154,7 +2356,8 @@ int Tail::warm(hipStream_t stream, std::string *err) {
                            (const void *)trace_fast_kernel<uint32_t, uint8_t>, (const void *)trace_fast_kernel<uint32_t, uint16_t>,
                            (const void *)trace_kernel, (const void *)compact_kernel, (const void *)sam_len_kernel<false>,
                            (const void *)sam_write_kernel<false>, (const void *)sam_len_kernel<true>,
-                           (const void *)sam_write_kernel<true>, (const void *)pair_kernel, (const void *)rescue_jobs_kernel,
+                           (const void *)sam_write_kernel<true>, (const void *)pair_kernel<false>, (const void *)pair_kernel<true>,
+                           (const void *)mapq_kernel, (const void *)rescue_jobs_kernel,
                            (const void *)rescue_search_kernel, (const void *)rescue_trace_kernel, (const void *)rescue_append_kernel};
   for (const void *k : kernels) TAIL_TRY(hipFuncGetAttributes(&a, k));
   if (!m.scan_tmp.p || !m.rec_begin.p || !m.n_ops.p || !m.line_len.p) return FEM_OK;  // (nothing reserved: the scans load with the first batch)
@@ -2317,7 +2520,7 @@ int Tail::run(const TailInput &in, hipStream_t stream, int n_cu, bool tiny, Tail
   TAIL_TRY(hipEventRecord(m.ev[3], stream));
   TAIL_TRY(hipMemcpyAsync(h_ctl + 4, m.cigar_off.as<uint32_t>() + nr, 4, hipMemcpyDeviceToHost, stream));
   TAIL_TRY(hipMemcpyAsync(h_ctl + 5, m.md_off.as<uint32_t>() + nr, 4, hipMemcpyDeviceToHost, stream));
-  m.last_n = n, m.last_nr = nr, m.paired = false, m.n_resc = 0, m.resc_timed = false;
+  m.last_n = n, m.last_nr = nr, m.paired = false, m.n_resc = 0, m.resc_timed = false, m.pair_mapq = false;
   if (copy_records) {  // ---- copy back (else the caller renders the records on the device: sam(), bam()) ----
     TAIL_TRY(hipStreamSynchronize(stream));
     const uint32_t n_cigar = h_ctl[4], n_md = h_ctl[5];
@@ -2458,7 +2661,7 @@ int Tail::bam(const TailInput &in, const SamInput &names, int level, hipStream_t
   return FEM_OK;
 }
 
-int Tail::pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::string *err, const RescueInput *rescue) {
+int Tail::pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::string *err, const RescueInput *rescue, bool mapq) {
   if (!impl_) return FEM_ERR_STATE;
   Impl &m = *impl_;
   const uint32_t n = m.last_n, nr = m.last_nr, np = n / 2u;
@@ -2466,7 +2669,7 @@ int Tail::pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::
     if (err) *err = "a paired batch holds an even number of reads";
     return FEM_ERR_INVALID;
   }
-  m.n_resc = 0, m.resc_timed = false;
+  m.n_resc = 0, m.resc_timed = false, m.pair_mapq = false;
   const uint32_t *resc_before = nullptr;
   if (rescue && np) {  // ---- mate rescue: the kept records behind run()'s, resc_before their exclusive scan over the pairs ----
     const int32_t E = rescue->max_edits;
@@ -2590,6 +2793,7 @@ int Tail::pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::
   TAIL_TRY(m.mtid.need(lines * 4));
   TAIL_TRY(m.mpos0.need(lines * 4));
   TAIL_TRY(m.tlen.need(lines * 4));
+  if (mapq) TAIL_TRY(m.lmq.need(lines));
   TAIL_TRY(m.pair_begin.need(((size_t)n + 1) * 4));
   TAIL_TRY(m.pair_ctl.need(16));
   TAIL_TRY(m.h_pair_ctl.need(16));
@@ -2605,14 +2809,15 @@ int Tail::pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::
     q.perm = m.perm.as<uint32_t>(), q.pflag = m.pflag.as<uint16_t>(), q.mtid = m.mtid.as<uint32_t>(), q.mpos0 = m.mpos0.as<uint32_t>();
     q.tlen = m.tlen.as<int32_t>(), q.pair_begin = m.pair_begin.as<uint32_t>(), q.n_proper = m.pair_ctl.as<uint32_t>();
     q.resc_before = resc_before, q.resc_first = nr;
-    hipLaunchKernelGGL(pair_kernel, dim3((np + 255u) / 256u), dim3(256), 0, stream, q);
+    q.lmq = mapq ? m.lmq.as<uint8_t>() : nullptr;
+    hipLaunchKernelGGL(mapq ? pair_kernel<true> : pair_kernel<false>, dim3((np + 255u) / 256u), dim3(256), 0, stream, q);
     TAIL_TRY(hipGetLastError());
   } else {
     TAIL_TRY(hipMemsetAsync(m.pair_begin.p, 0, 4, stream));
   }
   TAIL_TRY(hipEventRecord(m.ev_pair[1], stream));
   TAIL_TRY(hipMemcpyAsync(m.h_pair_ctl.p, m.pair_ctl.p, 4, hipMemcpyDeviceToHost, stream));
-  m.paired = true;
+  m.paired = true, m.pair_mapq = mapq;
   return FEM_OK;
 }
 
@@ -2621,6 +2826,12 @@ uint64_t Tail::n_rescued() const { return impl_ && impl_->paired ? impl_->n_resc
 float Tail::rescue_ms() const {
   float t = 0.f;
   if (!impl_ || !impl_->paired || !impl_->resc_timed || hipEventElapsedTime(&t, impl_->ev_resc[0], impl_->ev_resc[1]) != hipSuccess) return 0.f;
+  return t;
+}
+
+float Tail::mapq_ms() const {
+  float t = 0.f;
+  if (!impl_ || !impl_->mapq_timed || hipEventElapsedTime(&t, impl_->ev_mapq[0], impl_->ev_mapq[1]) != hipSuccess) return 0.f;
   return t;
 }
 

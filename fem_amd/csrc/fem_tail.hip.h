@@ -60,6 +60,7 @@ struct SamInput {  // device pointers
   const uint8_t *ref_names;      // reference sequence names, concatenated
   const uint32_t *ref_name_off;  // n_seq + 1
   bool qual_hole;                // quals == nullptr and the QUAL field of a primary record is LEFT UNWRITTEN (the caller fills it: SamOutput::qual_at)
+  bool mapq = false;             // MAPQ from the hit strata (mapq_kernel; in pair mode pair() must have been asked for it too); else 255
 };
 struct SamOutput {  // pinned host memory owned by the Tail object, valid until its next sam()
   const char *text;
@@ -149,11 +150,15 @@ class Tail {
   // count.  Asynchronous on `stream`; n_proper() is valid once the stream has been synchronised (sam() does).
   // rescue (optional): mate rescue first (the rescue kernels), the kept rescued records appended behind run()'s; pair() then
   // waits for the stream twice (the candidate count, the kept count).
-  int pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::string *err, const RescueInput *rescue = nullptr);
+  // mapq: pair_kernel also writes each line's pairing byte (qp and whether the chosen record may keep its own MAPQ), which the
+  // next sam() / bam() with SamInput::mapq turns into the MAPQ of the mates' primary lines.
+  int pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::string *err, const RescueInput *rescue = nullptr,
+           bool mapq = false);
   uint64_t n_proper() const;
   uint64_t n_rescued() const;  // kept rescued records of the last pair() (0 without rescue)
   float pair_ms() const;  // device time of the last pair(), once its stream has been synchronised (timing: 0 otherwise)
   float rescue_ms() const;  // ... and of its rescue kernels
+  float mapq_ms() const;  // device time of the last sam() / bam()'s MAPQ kernel (0 without SamInput::mapq)
   // The arrays of the last pair() to the host (waits for `stream`).
   int pair_fetch(hipStream_t stream, PairOutput *out, std::string *err);
   int wait_text();

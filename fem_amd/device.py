@@ -20,7 +20,7 @@ ABI_SYMBOLS = [
     "fem_device_numa", "fem_bind_thread_near_device",
     "fem_dev_allreduce_stats",
     "fem_dev_set_pairs", "fem_dev_fetch_pairs", "fem_dev_pair_count",
-    "fem_dev_set_rescue", "fem_dev_rescue_count",
+    "fem_dev_set_rescue", "fem_dev_rescue_count", "fem_dev_set_mapq",
     "fem_dev_fetch_bam", "fem_dev_fetch_bam_nowait", "fem_dev_bam_wait", "fem_dev_bgzf_compress",
 ]
 
@@ -151,6 +151,8 @@ def load_hip():
     if hasattr(L, "fem_dev_set_rescue"):
         L.fem_dev_set_rescue.argtypes = [vp, C.c_int, C.POINTER(_RescueParams)]
         L.fem_dev_rescue_count.argtypes = [vp, C.c_int, C.POINTER(u64)]
+    if hasattr(L, "fem_dev_set_mapq"):
+        L.fem_dev_set_mapq.argtypes = [vp, C.c_int, C.c_int]
     if hasattr(L, "fem_dev_fetch_bam"):
         L.fem_dev_fetch_bam.argtypes = [vp, C.c_int, C.c_int, C.POINTER(_BatchBam)]
         L.fem_dev_fetch_bam_nowait.argtypes = [vp, C.c_int, C.c_int, C.POINTER(_BatchBam)]
@@ -567,6 +569,10 @@ class Device:
         else:
             rp = _RescueParams(int(max_edits))
             self._check(self._L.fem_dev_set_rescue(self._h, slot, C.byref(rp)))
+
+    def set_mapq(self, on=True, slot=0):
+        """fem_dev_set_mapq: MAPQ from the hit strata in the slot's SAM text and BAM records (False: 255, as the reference)."""
+        self._check(self._L.fem_dev_set_mapq(self._h, slot, 1 if on else 0))
 
     def rescue_count(self, slot=0):
         """fem_dev_rescue_count: rescued mates of the slot's last paired text (or fetch_pairs)."""

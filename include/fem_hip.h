@@ -275,7 +275,7 @@ int fem_dev_sam_wait(fem_dev *h, int slot);
  *   uncompressed records, n_blocks = members.  level 1: deflate with dynamic Huffman codes, a member stored where that is not
  *   larger; level 0: stored members.  n_records, n_asserted and stats are fem_dev_fetch_sam's.  Lifetime, threads, pair mode
  *   and rescue as fem_dev_fetch_sam / _nowait / fem_dev_sam_wait (the data shares the text's pinned memory).
- *   Encoding: refID pos = the record's tid pos0; l_read_name = name + 1; MAPQ 255; bin = reg2bin(pos0, end0) with end0 = pos0 +
+ *   Encoding: refID pos = the record's tid pos0; l_read_name = name + 1; MAPQ 255 (fem_dev_set_mapq: its rule); bin = reg2bin(pos0, end0) with end0 = pos0 +
  *   the M/D/N/=/X lengths (pos0 + 1 for none); CIGAR as the device's words; FLAG & 0x7FFF (0x8000 still counted in n_asserted);
  *   l_seq = L where the text prints SEQ, else 0; next_refID next_pos tlen = -1 -1 0, or the pair's mate columns; SEQ in 4-bit
  *   codes of the letters the text prints; QUAL - 33; aux NM:C then MD:Z.
@@ -357,6 +357,24 @@ typedef struct {
 int fem_dev_set_rescue(fem_dev *h, int slot, const fem_rescue_params *rp);
 int fem_dev_rescue_count(fem_dev *h, int slot, uint64_t *n_rescued);
 
+/* ---- mapping qualities (new; opt-in: the reference prints MAPQ 255, "not available", and so does every output without it) ----
+ * fem_dev_set_mapq: on != 0: the slot's fem_dev_fetch_sam[_nowait] text and fem_dev_fetch_bam[_nowait] records carry MAPQ from
+ *   the hit strata below; 0: 255 again.  fem_batch_records and fem_batch_pairs are unchanged (MAPQ is output text only).
+ * Rule.  Q(g, c) = min(60, max(0, 20 g - 3 floor(log2 c))) for a gap of g >= 1 edits and c >= 1 alternatives (20 per edit of
+ *   gap, 3 = 10 log10 2 per doubling of the alternatives, capped at 60), in integers: floor(log2 c) = 31 - clz(c).
+ *   Single-end value of read r, mapped at -e e, from its records as single-end mapping makes them (NM non-decreasing; every
+ *   record counts, 0x8000 included, none merged by locus): d1 = NM of the first record, c1 = records with NM = d1.  c1 >= 2:
+ *   q_se(r) = 0.  Else d2 = the least NM above d1 and c2 = records with NM = d2, or d2 = e + 1 and c2 = 1 when there is none;
+ *   q_se(r) = Q(d2 - d1, c2).
+ *   Single-end lines: a read's primary line gets q_se(r), every other line 0.
+ *   Pair mode (fem_dev_set_pairs, with or without rescue; a rescued record is its mate's only record).  Not a proper pair:
+ *   each mate's primary line gets q_se(mate), every other line 0.  Proper pair with chosen combination (a, b): s1 = nm(a) +
+ *   nm(b), cp1 = concordant combinations with sum s1, s2 = the least concordant sum above s1, cp2 = how many have it; qp = 0
+ *   if cp1 >= 2, 60 if there is no s2, else Q(s2 - s1, cp2).  For the chosen record x of a mate, q_x = q_se(mate) if x is
+ *   not rescued and nm(x) = d1(mate), else 0; the mate's primary line gets max(q_x, min(qp, q_x + 40)), every 0x100 line 0.
+ *   "Concordant" is the pairing rule above. */
+int fem_dev_set_mapq(fem_dev *h, int slot, int on);
+
 /* Name of the seed + filter kernel fem_dev_map_staged would launch first for these parameters on the resident
  * index ("seed_join_kernel" — behind its "seed_select_kernel"; "seed_join_banked_kernel" where the reference's sequences
  * need more than one 32-bit coordinate space —, "seed_fast_kernel<hash>", "seed_fast_kernel<lean>" or
@@ -383,7 +401,9 @@ int fem_dev_index_info(const fem_dev *h, char *buf, uint64_t cap);
  * what it takes there, not what it would take alone);
  * 9 = the pairing kernel of a paired fem_dev_fetch_sam (fem_dev_set_pairs);
  * 10 = the mate rescue kernels in front of it (fem_dev_set_rescue; their host waits included);
- * of fem_dev_fetch_bam: 11 = the BAM record kernels, 12 = the BGZF kernels. */
+ * of fem_dev_fetch_bam: 11 = the BAM record kernels, 12 = the BGZF kernels;
+ * 13 = the MAPQ kernel of a fem_dev_fetch_sam / fem_dev_fetch_bam with fem_dev_set_mapq on (one entry per call; the
+ * pairing kernel's MAPQ part stays in 9). */
 int fem_dev_set_timing(fem_dev *h, int on);
 int fem_dev_reset_timing(fem_dev *h);
 int fem_dev_kernel_time(fem_dev *h, int kernel, double *ms_total, uint64_t *launches);

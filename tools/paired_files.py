@@ -19,13 +19,8 @@ L, E_HEAVY, HEAVY = 100, 8, 0.05
 ACGT = np.frombuffer(b"ACGT", np.uint8)
 
 
-def main():
-    n, d = int(sys.argv[1]), sys.argv[2]
-    w = bench.WORKLOADS["c3"]
-    os.makedirs(d, exist_ok=True)
-    text, off, lens = host.synth_reference(3, w["seq_lens"], threads=16)
-    fa, ix = os.path.join(d, "ref.fa"), os.path.join(d, "ref.idx")
-    host.write_fasta(fa, text, off, lens)
+def mates(text, off, lens, n):
+    """The n pairs' mates on the reference (text, off, lens of host.synth_reference): two (n, L) uint8 arrays."""
     rng = np.random.default_rng(17)
     lens64 = lens.astype(np.int64)
     seq = rng.choice(len(lens64), size=n, p=lens64 / lens64.sum())
@@ -58,6 +53,17 @@ def main():
         m[i] = np.frombuffer(s, np.uint8)
     swap = rng.random(n) < 0.5
     m1[swap], m2[swap] = m2[swap].copy(), m1[swap].copy()
+    return m1, m2
+
+
+def main():
+    n, d = int(sys.argv[1]), sys.argv[2]
+    w = bench.WORKLOADS["c3"]
+    os.makedirs(d, exist_ok=True)
+    text, off, lens = host.synth_reference(3, w["seq_lens"], threads=16)
+    fa, ix = os.path.join(d, "ref.fa"), os.path.join(d, "ref.idx")
+    host.write_fasta(fa, text, off, lens)
+    m1, m2 = mates(text, off, lens, n)
     for name, m in (("r1.fq", m1), ("r2.fq", m2)):
         bases = np.zeros(n * L + 8, np.uint8)
         bases[:n * L] = m.reshape(-1)
