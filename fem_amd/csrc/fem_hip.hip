@@ -42,7 +42,7 @@ constexpr uint32_t kMaxReadLen = 1024;
 constexpr size_t kFrontPad = 16;  // kernels fetch a reverse-strand chunk from up to 15 bytes in front of a read
 constexpr uint32_t kXcapSmall = 512, kFcap = 128, kCcap = 128;
 
-constexpr int kTimedKernels = 14;  // fem_dev_kernel_time ids: 0 seed (join), 1 verify, 2 generic seed, 3-5 tail, 6 pack_results_kernel (round 5; the count kernel of rounds 1-2 before), 7 SAM text, 8 seed selection, 9 pairing, 10 mate rescue, 11 BAM records, 12 BGZF, 13 MAPQ
+constexpr int kTimedKernels = 15;  // fem_dev_kernel_time ids: 0 seed (join), 1 verify, 2 generic seed, 3-5 tail, 6 pack_results_kernel (round 5; the count kernel of rounds 1-2 before), 7 SAM text, 8 seed selection, 9 pairing, 10 mate rescue, 11 BAM records, 12 BGZF, 13 MAPQ, 14 the line index with unmapped reads
 struct TimedLaunch {
   int kernel;
   hipEvent_t start, stop;
@@ -161,6 +161,8 @@ struct Slot {
   int32_t rescue_edits = 0;
   uint64_t n_rescued = 0;  // of the slot's last paired SAM text (or fetch_pairs)
   bool mapq = false;  // fem_dev_set_mapq: MAPQ from the hit strata in the slot's SAM text and BAM records
+  bool unmapped = false;  // fem_dev_set_unmapped: a line for every read without a mapping in the slot's SAM text and BAM records
+  uint64_t n_unmapped = 0;  // ... and how many the slot's last text or BAM had
   // fem_dev_fetch_pairs: the records in output order (host copies, valid until the slot's next fetch_pairs)
   std::vector<uint16_t> pr_flag;
   std::vector<uint32_t> pr_tid, pr_pos0, pr_cigar_off, pr_cigar, pr_md_off;
@@ -2322,15 +2324,16 @@ static int tail_records(fem_dev *h, int slot, const void *out, bool copy_records
 
 // The names (and qualities, unless the caller keeps them: qual_hole) the slot's text is rendered with.
 static femt::SamInput sam_input(const fem_dev *h, const Slot &s) {
-  return {s.host_quals ? nullptr : s.d_quals, s.d_names, s.d_name_off, h->d_ref_names, h->d_ref_name_off, s.host_quals, s.mapq};
+  return {s.host_quals ? nullptr : s.d_quals, s.d_names, s.d_name_off, h->d_ref_names, h->d_ref_name_off, s.host_quals, s.mapq, s.unmapped};
 }
 
 // What follows a text's sam() / bam() (tag: the caller, for FEM_FETCH_TIMES): the pair counts, the event the slot's next text
-// stage waits for (commit_text), the kernel times: 3-5, n_ms of the text's own from id `id` on, 9 and 10 when paired, 13 with MAPQ.
+// stage waits for (commit_text), the kernel times: 3-5, n_ms of the text's own from id `id` on, 9 and 10 when paired, 13 with MAPQ, 14 with lines for unmapped reads.
 static int text_done(fem_dev *h, int slot, const TailFront &f, const char *tag, int id, const double *ms, int n_ms) {
   Slot &s = h->slot[slot];
   s.n_proper = s.paired ? s.tail->n_proper() : 0;  // (sam() and bam() have waited for the stream once, after sizing the text)
   s.n_rescued = s.paired ? s.tail->n_rescued() : 0;
+  s.n_unmapped = s.tail->n_unmapped();
   if (!s.ev_text_order) HIP_TRY(h, hipEventCreateWithFlags(&s.ev_text_order, hipEventDisableTiming));
   HIP_TRY(h, hipEventRecord(s.ev_text_order, f.stream));
   s.have_text_order = true;
@@ -2344,6 +2347,7 @@ static int text_done(fem_dev *h, int slot, const TailFront &f, const char *tag, 
     if (s.paired) h->t_ms[9] += s.tail->pair_ms(), h->t_n[9] += 1;
     if (s.paired && s.rescue) h->t_ms[10] += s.tail->rescue_ms(), h->t_n[10] += 1;
     if (s.mapq) h->t_ms[13] += s.tail->mapq_ms(), h->t_n[13] += 1;  // (its events precede the text's sizing, which sam() and bam() wait for)
+    if (s.unmapped) h->t_ms[14] += s.tail->unmapped_ms(), h->t_n[14] += 1;  // (as do these)
   }
   return FEM_OK;
 }
@@ -2476,6 +2480,23 @@ int fem_dev_set_mapq(fem_dev *h, int slot, int on) {
   if (rc) return rc;
   FEM_LOCK(h);
   h->slot[slot].mapq = on != 0;
+  return FEM_OK;
+}
+
+int fem_dev_set_unmapped(fem_dev *h, int slot, int on) {
+  int rc = check_slot(h, slot);
+  if (rc) return rc;
+  FEM_LOCK(h);
+  h->slot[slot].unmapped = on != 0;
+  return FEM_OK;
+}
+
+int fem_dev_unmapped_count(fem_dev *h, int slot, uint64_t *n) {
+  int rc = check_slot(h, slot);
+  if (rc) return rc;
+  if (!n) return fail(h, FEM_ERR_INVALID, "null output pointer");
+  FEM_LOCK(h);
+  *n = h->slot[slot].n_unmapped;
   return FEM_OK;
 }
 

@@ -7,6 +7,7 @@
 // per batch.  `--read2 STR` maps read pairs (record i of --read1 and of --read2 are the two mates of pair i), with -I / -X the
 // accepted insert size: the pairing and the paired SAM text on the device (fem_dev_set_pairs); `--rescue INT` adds mate rescue
 // at INT edits (fem_dev_set_rescue).  `--mapq` writes mapping qualities made on the device (fem_dev_set_mapq) instead of 255.
+// `--unmapped` adds a line for every read without a mapping, made on the device (fem_dev_set_unmapped).
 #include <errno.h>
 #include <fcntl.h>
 #include <getopt.h>
@@ -76,6 +77,7 @@ void usage_map() {
   fprintf(stderr, "        --rescue INT  with --read2: search a mate without records in its mate's insert window at INT (0-15) edits\n");
   fprintf(stderr, "        --bam[=INT]   write BAM instead of SAM: BGZF level 1 (default) or 0 (uncompressed)\n");
   fprintf(stderr, "        --mapq        write mapping qualities (0-60) from the hits' edit distances instead of 255\n");
+  fprintf(stderr, "        --unmapped    write a line for every read without a mapping too (FLAG 0x4; a mate placed at its mapped mate)\n");
   fprintf(stderr, "        -o       STR  Output SAM file \n\n");
 }
 
@@ -250,6 +252,7 @@ struct BatchBuf {  // everything about the batch that sits in one (GPU, slot) pa
   fem_batch_records rec{};                  // device tail's records (default path)
   uint64_t n_proper = 0;                    // paired: proper pairs of the batch
   uint64_t n_rescued = 0;                   // --rescue: rescued mates of the batch
+  uint64_t n_unmapped = 0;                  // --unmapped: lines for unmapped reads of the batch
   fem_batch_result res{};                   // per-candidate outcome (FEM_HOST_TAIL=1)
   double t_submit = 0;
   double t_slot = 0, t_filled = 0, t_submitted = 0, t_retired = 0, t_text = 0;  // FEM_STAGE_TIMES=2: the batch's way through the stages
@@ -278,6 +281,7 @@ int map_main(int argc, char **argv) {
   long long rescue_edits = 0;  // --rescue (mate rescue at this many edits, fem_dev_set_rescue)
   bool rescue_given = false;
   int bam_level = -1;  // --bam[=LEVEL]: BAM records and BGZF members made on the device (fem_dev_fetch_bam); -1: SAM
+  bool unmapped = false;  // --unmapped: a line for every read without a mapping, made on the device (fem_dev_set_unmapped)
   bool mapq = false;   // --mapq: MAPQ from the hit strata, made on the device (fem_dev_set_mapq); else 255 as the reference
   fem_params params{12, 3, 2, 1};  // src/FEM_map.c:67-70: k and step are fixed, whatever the index header says
   int n_threads = 1, n_gpus = 1;
@@ -293,6 +297,7 @@ int map_main(int argc, char **argv) {
                                      {"read2", required_argument, nullptr, 'c'}, {"minins", required_argument, nullptr, 'I'},
                                      {"maxins", required_argument, nullptr, 'X'}, {"rescue", required_argument, nullptr, 'R'},
                                      {"bam", optional_argument, nullptr, 'Z'},  {"mapq", no_argument, nullptr, 'Q'},
+                                     {"unmapped", no_argument, nullptr, 'U'},
                                      {nullptr, 0, nullptr, 0}};
   int c, oi = 0;
   while ((c = getopt_long(argc, argv, short_opt, long_opt, &oi)) >= 0) {
@@ -314,6 +319,7 @@ int map_main(int argc, char **argv) {
         bam_level = !optarg ? 1 : strcmp(optarg, "0") == 0 ? 0 : strcmp(optarg, "1") == 0 ? 1 : -2;  // (-2: refused below)
         break;
       case 'Q': mapq = true; break;
+      case 'U': unmapped = true; break;
       case 'e': params.e = atoi(optarg); break;
       case 't': n_threads = atoi(optarg); break;
       case 'a': params.a = atoi(optarg); break;
@@ -365,6 +371,10 @@ int map_main(int argc, char **argv) {
     const char *x = getenv(v);
     if (mapq && x && x[0] == '1') {
       fprintf(stderr, "--mapq is not supported with %s=1: mapping qualities are made on the device, with its SAM text or BAM.\n", v);
+      exit(EXIT_FAILURE);
+    }
+    if (unmapped && x && x[0] == '1') {  // (nor lines for unmapped reads)
+      fprintf(stderr, "--unmapped is not supported with %s=1: the lines of unmapped reads are made on the device, with its SAM text or BAM.\n", v);
       exit(EXIT_FAILURE);
     }
   }
@@ -470,10 +480,13 @@ int map_main(int argc, char **argv) {
           uint64_t *po = nullptr, *pno = nullptr;
           rc = fem_dev_acquire_stage(devs[(size_t)g], sl, reads_cap0, bases_cap0, &pb, &po);
           if (!rc && device_text) rc = fem_dev_acquire_text_stage(devs[(size_t)g], sl, reads_cap0, bases_cap0, names_cap0, &pq, &pn, &pno);
-          if (!rc && device_text) rc = fem_dev_reserve_text(devs[(size_t)g], sl, reads_cap0, bases_cap0, names_cap0, batch_bytes + batch_bytes / 4);
+          if (!rc && device_text) rc = fem_dev_reserve_text(devs[(size_t)g], sl, reads_cap0, bases_cap0, names_cap0,
+                                                                  // (--unmapped: a read of which nothing maps still has a line of its name, bases and qualities)
+                                                                  batch_bytes + batch_bytes / (unmapped ? 2 : 4));
           // (a read over the device's limit among the first records: no reservation, the staging of its batch names the read)
           if (!rc && device_text && res_reads && res_len <= max_read_len) rc = fem_dev_reserve_batch(devs[(size_t)g], sl, res_reads, res_reads + res_reads / 8, res_len, &params);
           if (!rc && mapq) rc = fem_dev_set_mapq(devs[(size_t)g], sl, 1);
+          if (!rc && unmapped) rc = fem_dev_set_unmapped(devs[(size_t)g], sl, 1);
           if (!rc && paired) {
             const fem_pair_params pp{(int32_t)min_insert, (int32_t)max_insert};
             rc = fem_dev_set_pairs(devs[(size_t)g], sl, &pp);
@@ -589,7 +602,7 @@ int map_main(int argc, char **argv) {
   std::vector<TextOut> texts(3);
   for (TextOut &t : texts) text_free_q.push(&t);
   std::vector<uint64_t> per_gpu((size_t)n_gpus * 5, 0), per_gpu_proper((size_t)n_gpus, 0),
-      per_gpu_rescued((size_t)n_gpus, 0);
+      per_gpu_rescued((size_t)n_gpus, 0), per_gpu_unmapped((size_t)n_gpus, 0);
 
   // ---- writer (src/output_queue.c:60-91) ----
   std::thread writer([&] {
@@ -746,6 +759,7 @@ int map_main(int argc, char **argv) {
                                : fem_dev_fetch_records(h, b->slot, &b->rec);
         if (!rc && paired) rc = fem_dev_pair_count(h, b->slot, &b->n_proper);
         if (!rc && rescue_given) rc = fem_dev_rescue_count(h, b->slot, &b->n_rescued);
+        if (!rc && unmapped) rc = fem_dev_unmapped_count(h, b->slot, &b->n_unmapped);
         const double waited = real_time() - t0;
         b->t_retired = t0 + waited;
         double placing = 0;
@@ -782,6 +796,7 @@ int map_main(int argc, char **argv) {
           const uint64_t *st = host_tail ? b->res.stats : device_text ? b->sam.stats : b->rec.stats;
           for (int i = 0; i < 5; ++i) per_gpu[(size_t)g * 5 + (size_t)i] += st[i];
           if (paired) per_gpu_proper[(size_t)g] += b->n_proper, per_gpu_rescued[(size_t)g] += b->n_rescued;
+          per_gpu_unmapped[(size_t)g] += b->n_unmapped;
           if (device_text) {
             n_asserted += b->sam.n_asserted;
             write_q.push(WriteItem{nullptr, b});
@@ -1115,6 +1130,11 @@ int map_main(int argc, char **argv) {
       for (uint64_t x : per_gpu_rescued) n_rescued += x;
       fprintf(stderr, "The number of rescued mates: %lu\n", (unsigned long)n_rescued);
     }
+  }
+  if (unmapped) {
+    uint64_t n_unmapped = 0;
+    for (uint64_t x : per_gpu_unmapped) n_unmapped += x;
+    fprintf(stderr, "The number of unmapped reads: %lu\n", (unsigned long)n_unmapped);
   }
   fprintf(stderr, "Time: %fs\n", t_mapping);
   return 0;

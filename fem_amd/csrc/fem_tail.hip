@@ -1172,6 +1172,12 @@ struct SamParams {
   const int32_t *tlen;
   // MAPQ (fem_dev_set_mapq; nullptr: 255 on every line): single-end per read, its primary line's (the others 0); kPair per line
   const uint8_t *mapq;
+  // lines for unmapped reads (fem_dev_set_unmapped; the kernels' kUnm instances): n_records then counts LINES, and line j
+  // renders usrc[j]: below u_base a record (pair mode: a line of pair_kernel's), else the unmapped read usrc[j] - u_base
+  const uint32_t *usrc;
+  uint32_t u_base, n_reads;
+  const uint32_t *u_lines;      // the length kernels: the line count itself (n_records there bounds it: lines behind it get length 0)
+  const uint32_t *pair_begin;   // pair mode: pair_kernel's (mate m of pair i: its lines [pair_begin[2i+m], pair_begin[2i+m+1]))
 };
 
 __device__ __forceinline__ uint32_t dec_digits(uint32_t v) {
@@ -1187,14 +1193,70 @@ __device__ __forceinline__ uint8_t *put_dec(uint8_t *w, uint32_t v) {
   return w + n;
 }
 
-// RNEXT, PNEXT and TLEN of line j in pair mode, without the tabs around them (single-end: "*\t0\t0", 5 characters)
-__device__ __forceinline__ uint32_t mate_cols_len(const SamParams &p, uint32_t j, uint32_t tid) {
-  const uint32_t mt = p.mtid[j];
-  if (mt == 0xFFFFFFFFu) return 5u;
-  const uint32_t rnext = mt == tid ? 1u : p.ref_name_off[mt + 1] - p.ref_name_off[mt];
-  const int32_t tl = p.tlen[j];
-  const uint32_t tl_len = tl < 0 ? 1u + dec_digits((uint32_t)-tl) : dec_digits((uint32_t)tl);
-  return rnext + 1u + dec_digits(p.mpos0[j] + 1u) + 1u + tl_len;
+// ---- lines for unmapped reads (include/fem_hip.h, fem_dev_set_unmapped) ----
+constexpr uint32_t kNoMate = 0xFFFFFFFFu;
+
+// Pair order: mate m of pair i (read m n/2 + i) is slot 2i + m
+__device__ __forceinline__ uint32_t pair_slot(const SamParams &p, uint32_t r) {
+  const uint32_t np = p.n_reads / 2u, m = r >= np ? 1u : 0u;
+  return 2u * (r - m * np) + m;
+}
+
+// Where the unmapped mate of slot s's mapped read is placed: at that read's first line (no combination was chosen for such a
+// pair, so it is the read's first single-end record, or its rescued one)
+struct Placed {
+  uint32_t t, pos0, rev;
+};
+__device__ __forceinline__ Placed placed_at(const SamParams &p, uint32_t s) {
+  const uint32_t k0 = p.pair_begin[s], rec0 = p.perm[k0];
+  return {p.tid[rec0], p.pos0[rec0], p.pflag[k0] & 16u};
+}
+
+// The line of unmapped read r: FLAG, and (t, pos0) where it is placed (kNoMate, 0xFFFFFFFF: unplaced, which print * and 0)
+struct Unmapped {
+  uint32_t r, flag, t, pos0;
+};
+template <bool kPair>
+__device__ __forceinline__ Unmapped unmapped_line(const SamParams &p, uint32_t r) {
+  Unmapped u{r, 4u, kNoMate, 0xFFFFFFFFu};
+  if (kPair) {
+    const uint32_t s = pair_slot(p, r), o = s ^ 1u;
+    u.flag = 1u | 4u | ((s & 1u) ? 0x80u : 0x40u);
+    if (p.pair_begin[o + 1] == p.pair_begin[o]) {
+      u.flag |= 8u;
+    } else {
+      const Placed a = placed_at(p, o);
+      u.t = a.t, u.pos0 = a.pos0;
+      if (a.rev) u.flag |= 0x20u;
+    }
+  }
+  return u;
+}
+
+// The mate columns of pair_kernel's line k (read r's).  kUnm: a line whose mate has no record names where that mate's line is
+// placed, which is this read's own first line.
+struct MateCols {
+  uint32_t mt, mp;  // mt == kNoMate: "*" and "0"
+  int32_t tl;
+};
+template <bool kUnm>
+__device__ __forceinline__ MateCols mate_cols(const SamParams &p, uint32_t k, uint32_t r) {
+  MateCols m{p.mtid[k], 0u, 0};
+  if (m.mt != kNoMate) {
+    m.mp = p.mpos0[k], m.tl = p.tlen[k];
+  } else if (kUnm) {
+    const Placed a = placed_at(p, pair_slot(p, r));
+    m.mt = a.t, m.mp = a.pos0;
+  }
+  return m;
+}
+
+// RNEXT, PNEXT and TLEN of a line on sequence `tid` in pair mode, without the tabs around them (single-end: "*\t0\t0", 5 characters)
+__device__ __forceinline__ uint32_t mate_cols_len(const SamParams &p, const MateCols &m, uint32_t tid) {
+  if (m.mt == kNoMate) return 5u;
+  const uint32_t rnext = m.mt == tid ? 1u : p.ref_name_off[m.mt + 1] - p.ref_name_off[m.mt];
+  const uint32_t tl_len = m.tl < 0 ? 1u + dec_digits((uint32_t)-m.tl) : dec_digits((uint32_t)m.tl);
+  return rnext + 1u + dec_digits(m.mp + 1u) + 1u + tl_len;
 }
 
 // What every line kernel first reads of line j: the record it renders (pair mode: perm[j]; else j itself), that record's
@@ -1218,13 +1280,33 @@ __device__ __forceinline__ uint32_t line_mapq(const SamParams &p, uint32_t j, ui
   return kPair ? p.mapq[j] : primary ? p.mapq[r] : 0u;
 }
 
-template <bool kPair>
+// SEQ tab QUAL of a line that carries them (a read of length 0: "*\t*")
+__device__ __forceinline__ uint32_t seq_qual_len(const SamParams &p, uint32_t L) {
+  return L > 0 ? L + 1u + (p.quals || p.qual_hole ? L : 1u) : 3u;
+}
+
+// The line of an unmapped read: QNAME FLAG RNAME POS 0 * RNEXT PNEXT 0 SEQ QUAL, no tags
+__device__ __forceinline__ uint32_t unmapped_len(const SamParams &p, const Unmapped &u) {
+  const uint32_t name_len = (uint32_t)(p.name_off[u.r + 1] - p.name_off[u.r]), L = (uint32_t)(p.read_off[u.r + 1] - p.read_off[u.r]);
+  const uint32_t rname = u.t == kNoMate ? 1u : p.ref_name_off[u.t + 1] - p.ref_name_off[u.t], pos = dec_digits(u.pos0 + 1u);
+  return name_len + 1u + dec_digits(u.flag) + 1u + rname + 1u + pos + 5u + (u.t == kNoMate ? 5u : 4u + pos) + 1u + seq_qual_len(p, L) + 1u;
+}
+
+template <bool kPair, bool kUnm = false>
 __global__ void __launch_bounds__(256) sam_len_kernel(SamParams p) {
   const uint32_t stride = gridDim.x * blockDim.x;
-  for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j <= p.n_records; j += stride) {
-    if (j == p.n_records) {
-      p.line_len[j] = 0;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i <= p.n_records; i += stride) {
+    if (i == p.n_records || (kUnm && i >= p.u_lines[0])) {
+      p.line_len[i] = 0;
       continue;
+    }
+    uint32_t j = i;  // the record (pair mode: pair_kernel's line) that line i renders
+    if (kUnm) {
+      j = p.usrc[i];
+      if (j >= p.u_base) {
+        p.line_len[i] = unmapped_len(p, unmapped_line<kPair>(p, j - p.u_base));
+        continue;
+      }
     }
     const auto [rec, r, flag, primary, L, name_len] = line_head<kPair>(p, j);
     const uint32_t t = p.tid[rec], rname_len = p.ref_name_off[t + 1] - p.ref_name_off[t];
@@ -1234,10 +1316,10 @@ __global__ void __launch_bounds__(256) sam_len_kernel(SamParams p) {
     for (uint32_t c = c0; c < c1; ++c) cig += dec_digits(p.cigar[c] >> 4) + 1u;
     if (c1 == c0) cig = 1;  // '*'
     const uint32_t md_len = p.md_off[rec + 1] - p.md_off[rec];
-    const uint32_t seq_qual = primary && L > 0 ? L + 1u + (p.quals || p.qual_hole ? L : 1u) : 3u;
-    const uint32_t mate = kPair ? mate_cols_len(p, j, t) : 5u;
+    const uint32_t seq_qual = primary ? seq_qual_len(p, L) : 3u;
+    const uint32_t mate = kPair ? mate_cols_len(p, mate_cols<kUnm>(p, j, r), t) : 5u;
     const uint32_t mq = line_mapq<kPair>(p, j, r, primary);
-    p.line_len[j] = (unsigned long long)name_len + 1u + dec_digits(flag & 0x7FFFu) + 1u + rname_len + 1u + dec_digits(p.pos0[rec] + 1u) + 2u +
+    p.line_len[i] = (unsigned long long)name_len + 1u + dec_digits(flag & 0x7FFFu) + 1u + rname_len + 1u + dec_digits(p.pos0[rec] + 1u) + 2u +
                     dec_digits(mq) + cig + 2u + mate + seq_qual + 6u + dec_digits(p.nm[rec]) + 6u + md_len + 1u;
   }
 }
@@ -1248,7 +1330,9 @@ __global__ void __launch_bounds__(256) sam_len_kernel(SamParams p) {
 // Then the wave goes through its records two at a time, the long fields (QNAME, RNAME, SEQ, QUAL, MD) a byte per lane, every
 // load of a pair requested before the first store; what a lane knows of record i reaches the others by v_readlane.
 // kPair: j counts lines, each rendering record perm[j] with the pair's FLAG and mate columns (the lane writes those itself).
-template <bool kPair>
+// kUnm: a line may be an unmapped read's, one more shape of line: QNAME, SEQ and QUAL its long fields (a placed one's RNAME too),
+// no CIGAR, no MD, no tags.
+template <bool kPair, bool kUnm = false>
 __global__ void __launch_bounds__(256) sam_write_kernel(SamParams p) {
   __shared__ uint8_t lut[256];
   lut[threadIdx.x] = kSamSeqLut[threadIdx.x];
@@ -1259,27 +1343,41 @@ __global__ void __launch_bounds__(256) sam_write_kernel(SamParams p) {
   const uint32_t n_here = p.n_records - j0 < 64u ? p.n_records - j0 : 64u;
   const bool mine = ln < n_here;
   const uint32_t j = j0 + (mine ? ln : n_here - 1u);  // (lanes behind the last record repeat its loads and write nothing)
-  // level 1
-  const uint32_t rec = kPair ? p.perm[j] : j;
-  const uint32_t r = p.s_read[rec];
-  const uint32_t t = p.tid[rec];
-  const uint32_t flag = (kPair ? p.pflag[j] : p.flag[rec]) & 0x7FFFu, pos1 = p.pos0[rec] + 1u, nm = p.nm[rec];
-  const uint32_t c0 = p.cigar_off[rec], c1 = p.cigar_off[rec + 1], m0 = p.md_off[rec], md_len = p.md_off[rec + 1] - m0;
+  uint32_t src = j;  // the record (pair mode: pair_kernel's line) that line j renders; kUnm: or an unmapped read
+  bool unm = false;
+  if (kUnm) src = p.usrc[j], unm = src >= p.u_base;
   const unsigned long long at = p.line_off[j];
+  // level 1
+  uint32_t r, t, flag, pos1, nm = 0, c0 = 0, c1 = 0, m0 = 0, md_len = 0;
+  Unmapped um{};
+  if (kUnm && unm) {
+    um = unmapped_line<kPair>(p, src - p.u_base);
+    r = um.r, t = um.t, flag = um.flag, pos1 = um.pos0 + 1u;
+  } else {
+    const uint32_t rec = kPair ? p.perm[src] : src;
+    r = p.s_read[rec];
+    t = p.tid[rec];
+    flag = (kPair ? p.pflag[src] : p.flag[rec]) & 0x7FFFu, pos1 = p.pos0[rec] + 1u, nm = p.nm[rec];
+    c0 = p.cigar_off[rec], c1 = p.cigar_off[rec + 1], m0 = p.md_off[rec], md_len = p.md_off[rec + 1] - m0;
+  }
   // level 2
-  const bool primary = kPair ? !(flag & 256u) : p.rec_begin[r] == j;
+  const bool primary = (kUnm && unm) || (kPair ? !(flag & 256u) : p.rec_begin[r] == src);
   const uint64_t ro = p.read_off[r];
   const uint32_t L = (uint32_t)(p.read_off[r + 1] - ro);
   const uint64_t no = p.name_off[r];
   const uint32_t name_len = (uint32_t)(p.name_off[r + 1] - no);
-  const uint32_t rn0 = p.ref_name_off[t], rname_len = p.ref_name_off[t + 1] - rn0;
+  const bool no_t = kUnm && unm && t == kNoMate;  // an unplaced line: RNAME is the lane's own '*'
+  const uint32_t rn0 = no_t ? 0u : p.ref_name_off[t], rname_len = no_t ? 0u : p.ref_name_off[t + 1] - rn0;
   uint32_t op_a = 0, op_b = 0, op_c = 0;  // the first CIGAR operations (most records have one to three)
   const uint32_t n_ops = c1 - c0;
   if (n_ops > 0) op_a = p.cigar[c0];
   if (n_ops > 1) op_b = p.cigar[c0 + 1];
   if (n_ops > 2) op_c = p.cigar[c0 + 2];
   const bool seq = primary && L > 0;
-  const uint32_t mq = line_mapq<kPair>(p, j, r, primary);
+  const uint32_t mq = kUnm && unm ? 0u : line_mapq<kPair>(p, src, r, primary);
+  MateCols mc{kNoMate, 0u, 0};
+  if (kUnm && unm) mc.mt = um.t, mc.mp = um.pos0;
+  else if (kPair) mc = mate_cols<kUnm>(p, src, r);
   uint32_t cig = 0;
   if (n_ops <= 3u) {
     if (n_ops > 0) cig += dec_digits(op_a >> 4) + 1u;
@@ -1292,16 +1390,18 @@ __global__ void __launch_bounds__(256) sam_write_kernel(SamParams p) {
   // where the line's fields start (offsets from its first byte)
   const uint32_t o_flag = name_len + 1u;
   const uint32_t o_rname = o_flag + dec_digits(flag) + 1u;
-  const uint32_t o_pos = o_rname + rname_len + 1u;
+  const uint32_t o_pos = o_rname + (no_t ? 1u : rname_len) + 1u;
   const uint32_t o_cig = o_pos + dec_digits(pos1) + 2u + dec_digits(mq);
-  const uint32_t o_seq = o_cig + cig + 2u + (kPair ? mate_cols_len(p, j, t) : 5u);
-  const uint32_t o_nm = o_seq + (seq ? L + 1u + (p.quals || p.qual_hole ? L : 1u) : 3u) + 6u;
-  const uint32_t o_md = o_nm + dec_digits(nm) + 6u;
+  const uint32_t o_seq = o_cig + cig + 2u + (kPair ? mate_cols_len(p, mc, t) : 5u);
+  const uint32_t o_tags = o_seq + (seq ? L + 1u + (p.quals || p.qual_hole ? L : 1u) : 3u);  // (an unmapped read's line ends here)
+  const uint32_t o_nm = o_tags + 6u;
+  const uint32_t o_md = kUnm && unm ? o_tags : o_nm + dec_digits(nm) + 6u;
   if (mine) {  // the short fields of the lane's own record
     uint8_t *w = p.text + at;
     w[name_len] = '\t';
     put_dec(w + o_flag, flag)[0] = '\t';
-    w[o_rname + rname_len] = '\t';
+    if (no_t) w[o_rname] = '*';
+    w[o_pos - 1u] = '\t';
     uint8_t *q = put_dec(w + o_pos, pos1);
     q[0] = '\t';
     put_dec(q + 1, mq)[0] = '\t';
@@ -1321,21 +1421,21 @@ __global__ void __launch_bounds__(256) sam_write_kernel(SamParams p) {
     if (!kPair) {
       q[0] = '\t', q[1] = '*', q[2] = '\t', q[3] = '0', q[4] = '\t', q[5] = '0', q[6] = '\t';
     } else {  // RNEXT PNEXT TLEN
-      const uint32_t mt = p.mtid[j];
+      const uint32_t mt = mc.mt;
       *q++ = '\t';
-      if (mt == 0xFFFFFFFFu) {
+      if (mt == kNoMate) {
         q[0] = '*', q[1] = '\t', q[2] = '0', q[3] = '\t', q[4] = '0', q[5] = '\t';
       } else {
         if (mt == t) {
           *q++ = '=';
         } else {  // the other mate on another sequence (rare: its name a byte at a time)
           const uint32_t n0 = p.ref_name_off[mt], n1 = p.ref_name_off[mt + 1];
-          for (uint32_t k = n0; k < n1; ++k) *q++ = p.ref_names[k];
+          for (uint32_t c = n0; c < n1; ++c) *q++ = p.ref_names[c];
         }
         *q++ = '\t';
-        q = put_dec(q, p.mpos0[j] + 1u);
+        q = put_dec(q, mc.mp + 1u);
         *q++ = '\t';
-        const int32_t tl = p.tlen[j];
+        const int32_t tl = mc.tl;
         if (tl < 0) *q++ = '-';
         q = put_dec(q, tl < 0 ? (uint32_t)-tl : (uint32_t)tl);
         *q = '\t';
@@ -1349,10 +1449,12 @@ __global__ void __launch_bounds__(256) sam_write_kernel(SamParams p) {
     } else {
       w_seq[0] = '*', w_seq[1] = '\t', w_seq[2] = '*';
     }
-    q = w + o_nm - 6u;
-    q[0] = '\t', q[1] = 'N', q[2] = 'M', q[3] = ':', q[4] = 'i', q[5] = ':';
-    q = put_dec(w + o_nm, nm);
-    q[0] = '\t', q[1] = 'M', q[2] = 'D', q[3] = ':', q[4] = 'Z', q[5] = ':';
+    if (!(kUnm && unm)) {
+      q = w + o_tags;
+      q[0] = '\t', q[1] = 'N', q[2] = 'M', q[3] = ':', q[4] = 'i', q[5] = ':';
+      q = put_dec(w + o_nm, nm);
+      q[0] = '\t', q[1] = 'M', q[2] = 'D', q[3] = ':', q[4] = 'Z', q[5] = ':';
+    }
     w[o_md + md_len] = '\n';
   }
   // ---- the long fields, record by record, all lanes ----
@@ -1444,26 +1546,35 @@ __device__ __forceinline__ uint32_t bam_reg2bin(uint32_t beg, uint32_t end) {  /
 }
 
 // Record sizes (block_size + 4); a read name over 254 characters in the batch sets *bad_name (l_read_name is a uint8).
-template <bool kPair>
+template <bool kPair, bool kUnm = false>
 __global__ void __launch_bounds__(256) bam_len_kernel(SamParams p, uint32_t n_reads, uint32_t *bad_name) {
   const uint32_t stride = gridDim.x * blockDim.x;
   for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < n_reads; r += stride)
     if (p.name_off[r + 1] - p.name_off[r] > 254u) atomicOr(bad_name, 1u);
-  for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j <= p.n_records; j += stride) {
-    if (j == p.n_records) {
-      p.line_len[j] = 0;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i <= p.n_records; i += stride) {
+    if (i == p.n_records || (kUnm && i >= p.u_lines[0])) {
+      p.line_len[i] = 0;
       continue;
+    }
+    uint32_t j = i;  // (as sam_len_kernel)
+    if (kUnm) {
+      j = p.usrc[i];
+      if (j >= p.u_base) {  // an unmapped read: no CIGAR, SEQ and QUAL, no tags
+        const uint32_t r = j - p.u_base, L = (uint32_t)(p.read_off[r + 1] - p.read_off[r]);
+        p.line_len[i] = 36ull + (uint32_t)(p.name_off[r + 1] - p.name_off[r]) + 1u + (L + 1u) / 2u + L;
+        continue;
+      }
     }
     const auto [rec, r, flag, primary, L, name_len] = line_head<kPair>(p, j);
     if (flag & 0x8000u) atomicAdd(p.asserted, 1u);
     const uint32_t n_ops = p.cigar_off[rec + 1] - p.cigar_off[rec], md_len = p.md_off[rec + 1] - p.md_off[rec];
     const uint32_t ls = primary ? L : 0u;
-    p.line_len[j] = 36ull + name_len + 1u + 4u * n_ops + (ls + 1u) / 2u + ls + 4u + 4u + md_len;
+    p.line_len[i] = 36ull + name_len + 1u + 4u * n_ops + (ls + 1u) / 2u + ls + 4u + 4u + md_len;
   }
 }
 
 // One wave per record, a byte (or CIGAR word) per lane.
-template <bool kPair>
+template <bool kPair, bool kUnm = false>
 __global__ void __launch_bounds__(256) bam_write_kernel(SamParams p) {
   __shared__ uint8_t code4[256];  // read character -> 4-bit code of the letter the SAM text prints
   {
@@ -1478,21 +1589,37 @@ __global__ void __launch_bounds__(256) bam_write_kernel(SamParams p) {
   const uint32_t ln = threadIdx.x & 63u;
   const uint32_t j = blockIdx.x * 4u + (threadIdx.x >> 6);
   if (j >= p.n_records) return;
-  const auto [rec, r, fl, primary, L, name_len] = line_head<kPair>(p, j);
-  const uint64_t ro = p.read_off[r], no = p.name_off[r];
-  const uint32_t ls = primary ? L : 0u;
-  const uint32_t c0 = p.cigar_off[rec], n_ops = p.cigar_off[rec + 1] - c0;
-  const uint32_t m0 = p.md_off[rec], md_len = p.md_off[rec + 1] - m0;
-  const uint32_t tid = p.tid[rec], pos0 = p.pos0[rec], nm = p.nm[rec], mq = line_mapq<kPair>(p, j, r, primary);
-  uint32_t span = 0;
-  for (uint32_t c = ln; c < n_ops; c += 64u) {
-    const uint32_t op = p.cigar[c0 + c], o = op & 0xFu;
-    if (o == 0u || o == 2u || o == 3u || o == 7u || o == 8u) span += op >> 4;
-  }
-  for (uint32_t o = 32; o; o >>= 1) span += __shfl_xor(span, o);
-  const uint32_t bin = bam_reg2bin(pos0, pos0 + (span ? span : 1u));
+  uint32_t src = j;  // the record (pair mode: pair_kernel's line) that record j renders; kUnm: or an unmapped read
+  bool unm = false;
+  if (kUnm) src = p.usrc[j], unm = src >= p.u_base;
+  uint32_t r, fl, ls, name_len, c0 = 0, n_ops = 0, m0 = 0, md_len = 0, tid, pos0, nm = 0, mq = 0, bin;
   uint32_t ntid = 0xFFFFFFFFu, npos = 0xFFFFFFFFu, tlen = 0;
-  if (kPair && p.mtid[j] != 0xFFFFFFFFu) ntid = p.mtid[j], npos = p.mpos0[j], tlen = (uint32_t)p.tlen[j];
+  if (kUnm && unm) {  // (spec: an unplaced read has refID pos -1 -1 and the bin of that, 4680)
+    const Unmapped u = unmapped_line<kPair>(p, src - p.u_base);
+    r = u.r, fl = u.flag, tid = ntid = u.t, pos0 = npos = u.pos0;
+    ls = (uint32_t)(p.read_off[r + 1] - p.read_off[r]), name_len = (uint32_t)(p.name_off[r + 1] - p.name_off[r]);
+    bin = u.t == kNoMate ? 4680u : bam_reg2bin(pos0, pos0 + 1u);
+  } else {
+    const LineHead h = line_head<kPair>(p, src);
+    const uint32_t rec = h.rec;
+    r = h.r, fl = h.flag, name_len = h.name_len;
+    ls = h.primary ? h.L : 0u;
+    c0 = p.cigar_off[rec], n_ops = p.cigar_off[rec + 1] - c0;
+    m0 = p.md_off[rec], md_len = p.md_off[rec + 1] - m0;
+    tid = p.tid[rec], pos0 = p.pos0[rec], nm = p.nm[rec], mq = line_mapq<kPair>(p, src, r, h.primary);
+    uint32_t span = 0;
+    for (uint32_t c = ln; c < n_ops; c += 64u) {
+      const uint32_t op = p.cigar[c0 + c], o = op & 0xFu;
+      if (o == 0u || o == 2u || o == 3u || o == 7u || o == 8u) span += op >> 4;
+    }
+    for (uint32_t o = 32; o; o >>= 1) span += __shfl_xor(span, o);
+    bin = bam_reg2bin(pos0, pos0 + (span ? span : 1u));
+    if (kPair) {
+      const MateCols mc = mate_cols<kUnm>(p, src, r);
+      if (mc.mt != kNoMate) ntid = mc.mt, npos = mc.mp, tlen = (uint32_t)mc.tl;
+    }
+  }
+  const uint64_t ro = p.read_off[r], no = p.name_off[r];
   const uint64_t at = p.line_off[j];
   const uint32_t size = (uint32_t)(p.line_off[j + 1] - at);
   uint8_t *w = p.text + at;
@@ -1522,10 +1649,52 @@ __global__ void __launch_bounds__(256) bam_write_kernel(SamParams p) {
   const uint8_t *quals = p.quals ? p.quals + ro : nullptr;
   for (uint32_t k = ln; k < ls; k += 64u) x[k] = quals ? (uint8_t)(quals[k] - 33u) : (uint8_t)0xFF;
   x += ls;
+  if (kUnm && unm) return;  // (no tags)
   if (ln == 0) x[0] = 'N', x[1] = 'M', x[2] = 'C', x[3] = (uint8_t)nm, x[4] = 'M', x[5] = 'D', x[6] = 'Z';
   x += 7;
   const uint8_t *md = p.md + m0;
   for (uint32_t k = ln; k <= md_len; k += 64u) x[k] = k < md_len ? md[k] : 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The line index with lines for unmapped reads (fem_dev_set_unmapped).  A read has max(records, 1) lines.
+// The reads in output order are the slots: read s single-end, mate m of pair i (slot 2i + m) in pair mode, where a slot's
+// lines so far are [begin[s], begin[s + 1]) of the records (rec_begin) or of pair_kernel's lines (pair_begin, rescued mates
+// included).  unmapped_mark_kernel: cnt[s] = 1 where slot s has none; an exclusive scan of cnt (the unmapped reads alone:
+// one rocPRIM scan over the reads, not the lines); unmapped_src_kernel: line k of the lines so far moves behind the
+// unmapped reads in front of its slot, usrc[k + before[s]] = k, and an unmapped slot's line goes where its records
+// would have stood, usrc[begin[s] + before[s]] = n_base + its read.
+// ---------------------------------------------------------------------------------------------------------
+struct UlineParams {
+  uint32_t n_reads, n_base;  // n_base: records (pair mode: pair_kernel's lines)
+  const uint32_t *begin;     // n_reads + 1, by slot
+  const uint32_t *s_read;    // per record
+  uint32_t paired;
+  const uint32_t *perm;      // pair mode: per line of pair_kernel's
+  uint32_t *cnt;             // n_reads + 1 (the last one zero)
+  const uint32_t *before;    // n_reads + 1: the exclusive scan of cnt
+  uint32_t *usrc;            // n_base + before[n_reads]
+  uint32_t *n_lines;         // that number
+};
+
+__global__ void __launch_bounds__(256) unmapped_mark_kernel(UlineParams p) {
+  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s <= p.n_reads) p.cnt[s] = s < p.n_reads && p.begin[s + 1] == p.begin[s] ? 1u : 0u;
+}
+
+__global__ void __launch_bounds__(256) unmapped_src_kernel(UlineParams p) {
+  const uint32_t stride = gridDim.x * blockDim.x, first = blockIdx.x * blockDim.x + threadIdx.x, np = p.n_reads / 2u;
+  if (first == 0) p.n_lines[0] = p.n_base + p.before[p.n_reads];
+  for (uint32_t k = first; k < p.n_base; k += stride) {
+    const uint32_t r = p.s_read[p.paired ? p.perm[k] : k];
+    const uint32_t s = !p.paired ? r : r >= np ? 2u * (r - np) + 1u : 2u * r;
+    p.usrc[k + p.before[s]] = k;
+  }
+  for (uint32_t s = first; s < p.n_reads; s += stride) {
+    if (p.begin[s + 1] != p.begin[s]) continue;
+    const uint32_t r = !p.paired ? s : (s & 1u) * np + (s >> 1);
+    p.usrc[p.begin[s] + p.before[s]] = p.n_base + r;
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2162,6 +2331,8 @@ struct Tail::Impl {
   DevBuf perm, pflag, mtid, mpos0, tlen, pair_begin, pair_ctl;
   // MAPQ (SamInput::mapq): per read (single-end), per line (pair(): pair_kernel<true>'s bytes, then the MAPQ)
   DevBuf q_read, lmq;
+  // lines for unmapped reads (SamInput::unmapped): the marks, their scan, each line's source, the line count
+  DevBuf u_cnt, u_before, usrc, u_ctl;
   PinBuf h_perm, h_pflag, h_mtid, h_mpos0, h_tlen, h_pair_begin, h_pair_ctl;
   // mate rescue (pair() with a RescueInput): candidates, jobs, best hits, the tracebacks' staging, the kept flags and their scans
   DevBuf r_ctl, r_cand, r_jobs, r_best, r_ops, r_md, r_rec, r_ovf, r_o_ops, r_o_md, r_kept, r_scan, r_scan_tmp;
@@ -2177,35 +2348,53 @@ struct Tail::Impl {
   bool resc_timed = false;           // ... and its rescue kernels ran between ev_resc[0] and ev_resc[1]
   bool pair_mapq = false;            // the last pair() left its MAPQ bytes in lmq, not yet made MAPQ by a text
   bool mapq_timed = false;           // the last text's MAPQ kernel ran between ev_mapq[0] and ev_mapq[1]
+  bool unm_timed = false;            // ... and its line index kernels between ev_unm[0] and ev_unm[1]
+  uint32_t n_unm = 0;                // lines for unmapped reads in the last text
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   hipEvent_t ev_pair[2] = {nullptr, nullptr};
   hipEvent_t ev_resc[2] = {nullptr, nullptr};
   hipEvent_t ev_mapq[2] = {nullptr, nullptr};
+  hipEvent_t ev_unm[2] = {nullptr, nullptr};
   hipEvent_t ev_text = nullptr;  // the SAM text has arrived in h_text
   ~Impl() {  // (the buffers free themselves)
-    for (hipEvent_t e : {ev[0], ev[1], ev[2], ev[3], ev_pair[0], ev_pair[1], ev_resc[0], ev_resc[1], ev_mapq[0], ev_mapq[1], ev_text})
+    for (hipEvent_t e : {ev[0], ev[1], ev[2], ev[3], ev_pair[0], ev_pair[1], ev_resc[0], ev_resc[1], ev_mapq[0], ev_mapq[1], ev_unm[0], ev_unm[1], ev_text})
       if (e) (void)hipEventDestroy(e);
   }
   // sam() and bam(): the lines of run()'s records, or of pair()'s (rescued records included).  Fills *p (all but the text and
   // qual_at); names.mapq: first the MAPQ kernel (between ev_mapq[0] and ev_mapq[1]); from ev[0] on, each line's length (bad_name:
   // as BAM, a name over 254 characters setting it; else as SAM), their scan into line_off, the count of asserted records to h_ctl[2].
+  // names.unmapped: the line index first (between ev_unm[0] and ev_unm[1]).  The line count is known on the device alone then:
+  // p->n_records bounds it (records + reads; the lengths behind the last line are zero, so line_off[p->n_records] is the text's
+  // size all the same) and the count comes to h_ctl[8]; counted() puts it into p->n_records once the stream has been waited for.
   int lines(const TailInput &in, const SamInput &names, bool pair_order, uint32_t *bad_name, hipStream_t stream, int n_cu, SamParams *p,
               std::string *err) {
     if (pair_order && !paired) {
       if (err) *err = "the records were not paired (Tail::pair)";
       return FEM_ERR_STATE;
     }
-    const uint32_t nr = last_nr + (pair_order ? n_resc : 0u);
-    const size_t r1 = (size_t)nr + 1;
+    const uint32_t n_base = last_nr + (pair_order ? n_resc : 0u);
+    if (names.unmapped && (uint64_t)n_base + last_n > 0xFFFFFFF0ull) {
+      if (err) *err = "more than 2^32 lines in one batch; split the batch";
+      return FEM_ERR_UNSUPPORTED;
+    }
+    const uint32_t nr = n_base + (names.unmapped ? last_n : 0u);
+    const size_t r1 = (size_t)nr + 1, n1 = (size_t)last_n + 1;
     for (hipEvent_t &e : ev)
       if (!e) TAIL_TRY(hipEventCreate(&e));
     TAIL_TRY(line_len.need(r1 * 8));
     TAIL_TRY(line_off.need(r1 * 8));
-    TAIL_TRY(h_ctl.need(32));
-    size_t tmp = 0;
+    TAIL_TRY(h_ctl.need(48));
+    size_t tmp = 0, tmp_u = 0;
     TAIL_TRY(rocprim::exclusive_scan(nullptr, tmp, line_len.as<unsigned long long>(), line_off.as<unsigned long long>(), 0ull, r1,
                                      rocprim::plus<unsigned long long>(), stream));
-    TAIL_TRY(scan_tmp.need(std::max<size_t>(tmp, 16)));
+    if (names.unmapped) {
+      TAIL_TRY(u_cnt.need(n1 * 4));
+      TAIL_TRY(u_before.need(n1 * 4));
+      TAIL_TRY(usrc.need(std::max<size_t>(nr, 1) * 4));
+      TAIL_TRY(u_ctl.need(16));
+      TAIL_TRY(rocprim::exclusive_scan(nullptr, tmp_u, u_cnt.as<uint32_t>(), u_before.as<uint32_t>(), 0u, n1, rocprim::plus<uint32_t>(), stream));
+    }
+    TAIL_TRY(scan_tmp.need(std::max<size_t>(std::max(tmp, tmp_u), 16)));
     p->n_records = nr, p->rec_begin = rec_begin.as<uint32_t>(), p->s_read = s_read.as<uint32_t>();
     p->flag = flag.as<uint16_t>(), p->tid = tid.as<uint32_t>(), p->pos0 = pos0.as<uint32_t>(), p->nm = nm.as<uint8_t>();
     p->cigar_off = cigar_off.as<uint32_t>(), p->cigar = cigar.as<uint32_t>(), p->md_off = md_off.as<uint32_t>(), p->md = md.as<uint8_t>();
@@ -2216,6 +2405,30 @@ struct Tail::Impl {
     if (pair_order) {
       p->perm = perm.as<uint32_t>(), p->pflag = pflag.as<uint16_t>(), p->mtid = mtid.as<uint32_t>(), p->mpos0 = mpos0.as<uint32_t>();
       p->tlen = tlen.as<int32_t>();
+    }
+    unm_timed = false, n_unm = 0;
+    if (names.unmapped) {
+      for (hipEvent_t &e : ev_unm)
+        if (!e) TAIL_TRY(hipEventCreate(&e));
+      UlineParams u{};
+      u.n_reads = last_n, u.n_base = n_base, u.paired = pair_order ? 1u : 0u;
+      u.begin = pair_order ? pair_begin.as<uint32_t>() : rec_begin.as<uint32_t>();
+      u.s_read = s_read.as<uint32_t>(), u.perm = perm.as<uint32_t>();
+      u.cnt = u_cnt.as<uint32_t>(), u.before = u_before.as<uint32_t>(), u.usrc = usrc.as<uint32_t>(), u.n_lines = u_ctl.as<uint32_t>();
+      TAIL_TRY(hipEventRecord(ev_unm[0], stream));
+      hipLaunchKernelGGL(unmapped_mark_kernel, dim3((last_n + 256u) / 256u), dim3(256), 0, stream, u);
+      TAIL_TRY(hipGetLastError());
+      size_t tmp_bytes = scan_tmp.cap;
+      TAIL_TRY(rocprim::exclusive_scan(scan_tmp.p, tmp_bytes, u_cnt.as<uint32_t>(), u_before.as<uint32_t>(), 0u, n1, rocprim::plus<uint32_t>(), stream));
+      const uint32_t work = std::max(n_base, last_n);
+      hipLaunchKernelGGL(unmapped_src_kernel, dim3(std::max<uint32_t>(1u, std::min<uint32_t>((work + 255u) / 256u, (uint32_t)n_cu * 16u))),
+                         dim3(256), 0, stream, u);
+      TAIL_TRY(hipGetLastError());
+      TAIL_TRY(hipEventRecord(ev_unm[1], stream));
+      TAIL_TRY(hipMemcpyAsync(h_ctl.as<uint32_t>() + 8, u_ctl.p, 4, hipMemcpyDeviceToHost, stream));
+      unm_timed = true;
+      p->usrc = usrc.as<uint32_t>(), p->u_base = n_base, p->n_reads = last_n, p->u_lines = u_ctl.as<uint32_t>();
+      p->pair_begin = pair_begin.as<uint32_t>();
     }
     mapq_timed = false;
     if (names.mapq) {
@@ -2247,15 +2460,27 @@ struct Tail::Impl {
     if (bad_name) TAIL_TRY(hipMemsetAsync(bad_name, 0, 4, stream));
     TAIL_TRY(hipEventRecord(ev[0], stream));
     const dim3 len_grid(std::max<uint32_t>(1u, std::min<uint32_t>((nr + 256u) / 256u, (uint32_t)n_cu * 16u)));
+    const bool um = names.unmapped;
     if (bad_name)
-      hipLaunchKernelGGL(pair_order ? bam_len_kernel<true> : bam_len_kernel<false>, len_grid, dim3(256), 0, stream, *p, last_n, bad_name);
+      hipLaunchKernelGGL(um ? (pair_order ? bam_len_kernel<true, true> : bam_len_kernel<false, true>)
+                            : (pair_order ? bam_len_kernel<true> : bam_len_kernel<false>), len_grid, dim3(256), 0, stream, *p, last_n, bad_name);
     else
-      hipLaunchKernelGGL(pair_order ? sam_len_kernel<true> : sam_len_kernel<false>, len_grid, dim3(256), 0, stream, *p);
+      hipLaunchKernelGGL(um ? (pair_order ? sam_len_kernel<true, true> : sam_len_kernel<false, true>)
+                            : (pair_order ? sam_len_kernel<true> : sam_len_kernel<false>), len_grid, dim3(256), 0, stream, *p);
     TAIL_TRY(hipGetLastError());
     TAIL_TRY(rocprim::exclusive_scan(scan_tmp.p, scan_tmp.cap, line_len.as<unsigned long long>(), line_off.as<unsigned long long>(), 0ull,
                                      r1, rocprim::plus<unsigned long long>(), stream));
     TAIL_TRY(hipMemcpyAsync(h_ctl.as<uint32_t>() + 2, ctl.as<uint32_t>() + 2, 4, hipMemcpyDeviceToHost, stream));
     return FEM_OK;
+  }
+  // after lines() and a wait for its stream: the number of lines (into p->n_records, which bounded it), n_unm
+  uint32_t counted(const SamInput &names, SamParams *p) {
+    if (names.unmapped) {
+      const uint32_t n_lines = std::min(h_ctl.as<uint32_t>()[8], p->n_records);
+      n_unm = n_lines - p->u_base;
+      p->n_records = n_lines;
+    }
+    return p->n_records;
   }
 
   // A text's way home after ev[1]: `bytes` from src into h_text (and bytes2 from src2 into dst2: SAM's qual_at) behind the text
@@ -2300,7 +2525,7 @@ int Tail::reserve(uint32_t n, uint32_t nr, uint32_t max_len_in, int e, bool tiny
   TAIL_TRY(m.rec_begin.need(((size_t)n + 1) * 4));
   TAIL_TRY(m.queue.need(std::max<size_t>(n, 1) * 4));
   TAIL_TRY(m.ctl.need(16));
-  TAIL_TRY(m.h_ctl.need(32));
+  TAIL_TRY(m.h_ctl.need(48));
   const size_t r1 = (size_t)nr + 1;
   TAIL_TRY(m.u_cand.need(r1 * 8));
   TAIL_TRY(m.u_misc.need(r1 * 4));
@@ -2357,7 +2582,10 @@ int Tail::warm(hipStream_t stream, std::string *err) {
                            (const void *)trace_kernel, (const void *)compact_kernel, (const void *)sam_len_kernel<false>,
                            (const void *)sam_write_kernel<false>, (const void *)sam_len_kernel<true>,
                            (const void *)sam_write_kernel<true>, (const void *)pair_kernel<false>, (const void *)pair_kernel<true>,
-                           (const void *)mapq_kernel, (const void *)rescue_jobs_kernel,
+                           (const void *)mapq_kernel, (const void *)unmapped_mark_kernel, (const void *)unmapped_src_kernel,
+                           (const void *)sam_len_kernel<false, true>, (const void *)sam_write_kernel<false, true>,
+                           (const void *)sam_len_kernel<true, true>, (const void *)sam_write_kernel<true, true>,
+                           (const void *)rescue_jobs_kernel,
                            (const void *)rescue_search_kernel, (const void *)rescue_trace_kernel, (const void *)rescue_append_kernel};
   for (const void *k : kernels) TAIL_TRY(hipFuncGetAttributes(&a, k));
   if (!m.scan_tmp.p || !m.rec_begin.p || !m.n_ops.p || !m.line_len.p) return FEM_OK;  // (nothing reserved: the scans load with the first batch)
@@ -2595,17 +2823,18 @@ int Tail::sam(const TailInput &in, const SamInput &names, hipStream_t stream, in
   }
   int rc = m.lines(in, names, paired, nullptr, stream, n_cu, &p, err);
   if (rc) return rc;
-  const uint32_t nr = p.n_records;
   unsigned long long *h_total = (unsigned long long *)(m.h_ctl.as<uint32_t>() + 6);
-  TAIL_TRY(hipMemcpyAsync(h_total, m.line_off.as<unsigned long long>() + nr, 8, hipMemcpyDeviceToHost, stream));
+  TAIL_TRY(hipMemcpyAsync(h_total, m.line_off.as<unsigned long long>() + p.n_records, 8, hipMemcpyDeviceToHost, stream));
   TAIL_TRY(hipStreamSynchronize(stream));
+  const uint32_t nr = m.counted(names, &p);
   const uint64_t total = *h_total;
   TAIL_TRY(m.text.need(std::max<size_t>((size_t)total, 16)));
   TAIL_TRY(m.h_text.need(std::max<size_t>((size_t)total + total / 8, 1u << 20)));
   if (nr) {
     p.text = m.text.as<uint8_t>();
     const uint32_t blocks = (nr + 255u) / 256u;  // a wave per 64 records
-    hipLaunchKernelGGL(paired ? sam_write_kernel<true> : sam_write_kernel<false>, dim3(blocks), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL(names.unmapped ? (paired ? sam_write_kernel<true, true> : sam_write_kernel<false, true>)
+                                      : (paired ? sam_write_kernel<true> : sam_write_kernel<false>), dim3(blocks), dim3(256), 0, stream, p);
     TAIL_TRY(hipGetLastError());
   }
   TAIL_TRY(hipEventRecord(m.ev[1], stream));
@@ -2629,21 +2858,23 @@ int Tail::bam(const TailInput &in, const SamInput &names, int level, hipStream_t
   uint32_t *bad_name = m.bam_ctl.as<uint32_t>();
   int rc = m.lines(in, names, paired, bad_name, stream, n_cu, &p, err);
   if (rc) return rc;
-  const uint32_t nr = p.n_records;
+  const uint32_t n_bound = p.n_records;
   // the record offsets come home with the total: the member cuts are made here
-  TAIL_TRY(m.h_line_off.need(((size_t)nr + 1) * 8));
-  TAIL_TRY(hipMemcpyAsync(m.h_line_off.p, m.line_off.p, ((size_t)nr + 1) * 8, hipMemcpyDeviceToHost, stream));
+  TAIL_TRY(m.h_line_off.need(((size_t)n_bound + 1) * 8));
+  TAIL_TRY(hipMemcpyAsync(m.h_line_off.p, m.line_off.p, ((size_t)n_bound + 1) * 8, hipMemcpyDeviceToHost, stream));
   TAIL_TRY(hipMemcpyAsync(m.h_ctl.as<uint32_t>() + 3, bad_name, 4, hipMemcpyDeviceToHost, stream));
   TAIL_TRY(hipStreamSynchronize(stream));
   if (m.h_ctl.as<uint32_t>()[3]) {
     if (err) *err = "the batch holds a read name over 254 characters: not writable as BAM (l_read_name is one byte)";
     return FEM_ERR_UNSUPPORTED;
   }
+  const uint32_t nr = m.counted(names, &p);
   const uint64_t total = m.h_line_off.as<uint64_t>()[nr];
   TAIL_TRY(m.text.need(std::max<size_t>((size_t)total, 16)));
   if (nr) {
     p.text = m.text.as<uint8_t>();
-    hipLaunchKernelGGL(paired ? bam_write_kernel<true> : bam_write_kernel<false>, dim3((nr + 3u) / 4u), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL(names.unmapped ? (paired ? bam_write_kernel<true, true> : bam_write_kernel<false, true>)
+                                      : (paired ? bam_write_kernel<true> : bam_write_kernel<false>), dim3((nr + 3u) / 4u), dim3(256), 0, stream, p);
     TAIL_TRY(hipGetLastError());
   }
   TAIL_TRY(hipEventRecord(m.ev[1], stream));
@@ -2826,6 +3057,14 @@ uint64_t Tail::n_rescued() const { return impl_ && impl_->paired ? impl_->n_resc
 float Tail::rescue_ms() const {
   float t = 0.f;
   if (!impl_ || !impl_->paired || !impl_->resc_timed || hipEventElapsedTime(&t, impl_->ev_resc[0], impl_->ev_resc[1]) != hipSuccess) return 0.f;
+  return t;
+}
+
+uint64_t Tail::n_unmapped() const { return impl_ ? impl_->n_unm : 0; }
+
+float Tail::unmapped_ms() const {
+  float t = 0.f;
+  if (!impl_ || !impl_->unm_timed || hipEventElapsedTime(&t, impl_->ev_unm[0], impl_->ev_unm[1]) != hipSuccess) return 0.f;
   return t;
 }
 

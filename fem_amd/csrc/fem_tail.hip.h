@@ -61,12 +61,13 @@ struct SamInput {  // device pointers
   const uint32_t *ref_name_off;  // n_seq + 1
   bool qual_hole;                // quals == nullptr and the QUAL field of a primary record is LEFT UNWRITTEN (the caller fills it: SamOutput::qual_at)
   bool mapq = false;             // MAPQ from the hit strata (mapq_kernel; in pair mode pair() must have been asked for it too); else 255
+  bool unmapped = false;         // a line for every read without a record (fem_dev_set_unmapped; the kernels' kUnm instances)
 };
 struct SamOutput {  // pinned host memory owned by the Tail object, valid until its next sam()
   const char *text;
   uint64_t len;
   uint64_t n_asserted;  // records on which the reference would have tripped an assertion (written with CIGAR *)
-  const uint64_t *qual_at;  // qual_hole: per READ, where in `text` its QUAL field starts (~0: the read has no record); else nullptr
+  const uint64_t *qual_at;  // qual_hole: per READ, where in `text` its QUAL field starts (~0: the read has no line, or a line without QUAL); else nullptr
 };
 
 // ---- BAM on the device: the same lines as BAM records, BGZF-compressed (fem_bgzf.hip) ----
@@ -159,6 +160,8 @@ class Tail {
   float pair_ms() const;  // device time of the last pair(), once its stream has been synchronised (timing: 0 otherwise)
   float rescue_ms() const;  // ... and of its rescue kernels
   float mapq_ms() const;  // device time of the last sam() / bam()'s MAPQ kernel (0 without SamInput::mapq)
+  uint64_t n_unmapped() const;  // lines for unmapped reads in the last sam() / bam() (0 without SamInput::unmapped)
+  float unmapped_ms() const;    // ... and the device time of its line index kernels
   // The arrays of the last pair() to the host (waits for `stream`).
   int pair_fetch(hipStream_t stream, PairOutput *out, std::string *err);
   int wait_text();

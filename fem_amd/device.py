@@ -21,6 +21,7 @@ ABI_SYMBOLS = [
     "fem_dev_allreduce_stats",
     "fem_dev_set_pairs", "fem_dev_fetch_pairs", "fem_dev_pair_count",
     "fem_dev_set_rescue", "fem_dev_rescue_count", "fem_dev_set_mapq",
+    "fem_dev_set_unmapped", "fem_dev_unmapped_count",
     "fem_dev_fetch_bam", "fem_dev_fetch_bam_nowait", "fem_dev_bam_wait", "fem_dev_bgzf_compress",
 ]
 
@@ -153,6 +154,9 @@ def load_hip():
         L.fem_dev_rescue_count.argtypes = [vp, C.c_int, C.POINTER(u64)]
     if hasattr(L, "fem_dev_set_mapq"):
         L.fem_dev_set_mapq.argtypes = [vp, C.c_int, C.c_int]
+    if hasattr(L, "fem_dev_set_unmapped"):
+        L.fem_dev_set_unmapped.argtypes = [vp, C.c_int, C.c_int]
+        L.fem_dev_unmapped_count.argtypes = [vp, C.c_int, C.POINTER(u64)]
     if hasattr(L, "fem_dev_fetch_bam"):
         L.fem_dev_fetch_bam.argtypes = [vp, C.c_int, C.c_int, C.POINTER(_BatchBam)]
         L.fem_dev_fetch_bam_nowait.argtypes = [vp, C.c_int, C.c_int, C.POINTER(_BatchBam)]
@@ -573,6 +577,17 @@ class Device:
     def set_mapq(self, on=True, slot=0):
         """fem_dev_set_mapq: MAPQ from the hit strata in the slot's SAM text and BAM records (False: 255, as the reference)."""
         self._check(self._L.fem_dev_set_mapq(self._h, slot, 1 if on else 0))
+
+    def set_unmapped(self, on=True, slot=0):
+        """fem_dev_set_unmapped: a line for every read without a mapping in the slot's SAM text and BAM records (False: none,
+        as the reference)."""
+        self._check(self._L.fem_dev_set_unmapped(self._h, slot, 1 if on else 0))
+
+    def unmapped_count(self, slot=0):
+        """fem_dev_unmapped_count: lines for unmapped reads in the slot's last SAM text or BAM."""
+        n = C.c_uint64()
+        self._check(self._L.fem_dev_unmapped_count(self._h, slot, C.byref(n)))
+        return int(n.value)
 
     def rescue_count(self, slot=0):
         """fem_dev_rescue_count: rescued mates of the slot's last paired text (or fetch_pairs)."""

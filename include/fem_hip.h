@@ -247,7 +247,8 @@ int fem_dev_commit_text_stage(fem_dev *h, int slot, uint64_t n_reads, uint64_t n
  * the device 228 of the 473 bytes per 100-bp read on the link are the qualities going to the device and coming back unchanged;
  * this form sends none up and the SAM text comes back with the QUAL field of every read's first record sized but NOT WRITTEN.
  * fem_dev_sam_quals (once the text is home: after fem_dev_fetch_sam / fem_dev_sam_wait) gives qual_at[n_reads]: where in the
- * text read r's field starts, UINT64_MAX for a read without a record; the caller copies each read's quality string there
+ * text read r's field starts, UINT64_MAX for a read without a record (fem_dev_set_unmapped: such a read has a line, and its
+ * field's start stands here like any other's); the caller copies each read's quality string there
  * (libfemhost's fem_sam_fill_quals does it on several threads) before it uses the text.  Pinned memory of the slot, valid until
  * the slot's next SAM text. */
 int fem_dev_commit_names_stage(fem_dev *h, int slot, uint64_t n_reads, uint64_t n_name_bytes);
@@ -375,6 +376,33 @@ int fem_dev_rescue_count(fem_dev *h, int slot, uint64_t *n_rescued);
  *   "Concordant" is the pairing rule above. */
 int fem_dev_set_mapq(fem_dev *h, int slot, int on);
 
+/* ---- lines for unmapped reads (new; opt-in: the reference drops a read without a mapping, and so does every output without it) ----
+ * fem_dev_set_unmapped: on != 0: the slot's fem_dev_fetch_sam[_nowait] text and fem_dev_fetch_bam[_nowait] records carry one
+ *   line for every unmapped read; 0: none again.  fem_batch_sam / fem_batch_bam keep their layout and n_records keeps meaning
+ *   mapping records: lines = n_records (+ the rescued mates in pair mode) + fem_dev_unmapped_count.  fem_batch_records and
+ *   fem_batch_pairs are unchanged (as with MAPQ, this is output text only; mate_tid there stays 0xFFFFFFFF).
+ * Rule.  A read is unmapped when, after single-end mapping and (pair mode with rescue) after mate rescue, it has no record.
+ *   It gets exactly one line, where its records would have stood: single-end in batch read order between its neighbours'
+ *   lines; in pair mode in the pair's slot (mate 1's lines, then mate 2's).  Mapped reads keep their lines.
+ *   Single-end, and a pair with both mates unmapped, the unplaced line: QNAME as on a mapped line; FLAG 4 (pairs: 0x1 | 0x4 |
+ *   0x8 | 0x40 = 77 for mate 1, 0x1 | 0x4 | 0x8 | 0x80 = 141 for mate 2); RNAME * POS 0; MAPQ 0, with and without
+ *   fem_dev_set_mapq (never 255); CIGAR *; RNEXT * PNEXT 0 TLEN 0; SEQ and QUAL the read as given (forward) through the letter
+ *   table and quality handling of a mapped read's primary line (* and * for a read of length 0; with
+ *   fem_dev_commit_names_stage QUAL is sized, not written, and qual_at[r] says where); no tags: the line ends after QUAL.
+ *   A pair with one mapped mate A and one unmapped mate B, the placed line (the SAM specification's recommended practice).
+ *   a0 = A's first line (no combination was chosen for such a pair: A's first single-end record), on sequence t at pos0 p.
+ *   B's line: FLAG 0x1 | 0x4 | 0x40 or 0x80, | 0x20 when a0 is reverse; RNAME t, POS p + 1; MAPQ 0; CIGAR *; RNEXT =, PNEXT
+ *   p + 1; TLEN 0; SEQ and QUAL forward as given; no tags.  A's lines keep 0x8 and everything else they have without the
+ *   switch, except RNEXT PNEXT (there * 0), which name where B was placed: RNEXT = where the line's own sequence is t, else
+ *   t's name; PNEXT p + 1.  TLEN stays 0; the pair is not proper and not counted as one.  With fem_dev_set_mapq A's lines get
+ *   what they get without the switch, B's line 0.
+ *   BAM records are these lines field for field in the encoding above: refID pos -1 -1 and bin 4680 unplaced; t, p and
+ *   reg2bin(p, p + 1) placed; n_cigar_op 0; l_seq L with the 4-bit SEQ and QUAL - 33; no aux.
+ * fem_dev_unmapped_count: the lines for unmapped reads in the slot's last text or BAM (valid once the fetch has returned);
+ *   0 with the switch off. */
+int fem_dev_set_unmapped(fem_dev *h, int slot, int on);
+int fem_dev_unmapped_count(fem_dev *h, int slot, uint64_t *n);
+
 /* Name of the seed + filter kernel fem_dev_map_staged would launch first for these parameters on the resident
  * index ("seed_join_kernel" — behind its "seed_select_kernel"; "seed_join_banked_kernel" where the reference's sequences
  * need more than one 32-bit coordinate space —, "seed_fast_kernel<hash>", "seed_fast_kernel<lean>" or
@@ -403,7 +431,9 @@ int fem_dev_index_info(const fem_dev *h, char *buf, uint64_t cap);
  * 10 = the mate rescue kernels in front of it (fem_dev_set_rescue; their host waits included);
  * of fem_dev_fetch_bam: 11 = the BAM record kernels, 12 = the BGZF kernels;
  * 13 = the MAPQ kernel of a fem_dev_fetch_sam / fem_dev_fetch_bam with fem_dev_set_mapq on (one entry per call; the
- * pairing kernel's MAPQ part stays in 9). */
+ * pairing kernel's MAPQ part stays in 9);
+ * 14 = the line index kernels of a fem_dev_fetch_sam / fem_dev_fetch_bam with fem_dev_set_unmapped on (one entry per call;
+ * the unmapped reads' lines themselves are written by the text and BAM record kernels: 7 and 11). */
 int fem_dev_set_timing(fem_dev *h, int on);
 int fem_dev_reset_timing(fem_dev *h);
 int fem_dev_kernel_time(fem_dev *h, int kernel, double *ms_total, uint64_t *launches);
