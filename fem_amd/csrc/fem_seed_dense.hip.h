@@ -43,8 +43,9 @@ constexpr uint32_t kDenseVLimit = 0xDFFFF800u; // v < this <=> the lane holds a 
 // kDensePadBase + j * kDensePadStride + pad_shift(h) — above every coordinate (also once a seed's start, < 1 024, is
 // subtracted), below kDenseRemap, consecutive lanes in different LDS banks (2 304 = 9 words of the join's bitmap).  What
 // sent_a of seed_join_kernel was in round 4, but it comes with the load: no clamped lane offset, no compare, no select per
-// chunk.  The join does not ask which lanes hold entries at all: a pad is a value like any other that can pair with no REAL
-// value (they lie 2^28 below), and whatever survives the filter is tested for being a coordinate.  pad_shift — a multiple
+// chunk.  Which lanes hold entries the padded join takes from scalar masks of the runs' lengths (vm, join_read): a flagged pad
+// is masked out of the flagged set.  (The form that did not ask at all — a pad as a value like any other, whatever survives
+// tested for being a coordinate — was tried and dropped.)  pad_shift — a multiple
 // of 36 below the lane stride, by a hash of the bucket — keeps the pads of a unit's runs (different buckets, starts 12 or
 // more apart) out of each other's neighbouring slots but for chance: without it the same lane's pads of two runs sat 12
 // to 24 positions apart and flagged each other in every unit.

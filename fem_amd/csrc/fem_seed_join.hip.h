@@ -62,7 +62,27 @@ constexpr uint32_t join_slots(int R, bool padded = false) { return R >= 7 ? FEM_
 #define FEM_JOIN_BATCH_HI 3
 #endif
 
+// Round 6: TWO bodies for a unit's middle part (lists -> flagged values of the group; fem_seed_join_unit.hip.h, included twice
+// in join_read), picked per unit by a wave-uniform test.  The PLAIN one serves a unit in which no list has a second chunk and the
+// first chunks hold no remapped entry — most units of a dense index: no second-chunk registers, no rare path.  As one
+// instruction stream joined by wave-uniform branches the common unit paid for both (sentinels and copies of five registers it
+// never used, compares on them).  Units of R <= FEM_JOIN_SPLIT_MAX_R are split; above, every unit takes the full body.
+#ifndef FEM_JOIN_SPLIT_MAX_R
+#define FEM_JOIN_SPLIT_MAX_R 10
+#endif
+// Chunks of the FULL body whose LDS steps are issued together at R <= 6 (the plain body: all R).  With a unit's second chunks in
+// registers too, batches of all R chunks made the full body the kernel's register peak (scratch, R = 5: 28 bytes at 5 chunks, 0
+// at 2 or 1); it is the rare body, so the kernel's budget is the plain body's.
+#ifndef FEM_JOIN_BATCH_FULL
+#define FEM_JOIN_BATCH_FULL 2
+#endif
+
 constexpr uint32_t join_bitmap_words(int R, bool padded = false) { return join_slots(R, padded) / 32u + 4u; }  // + the guard word (all ones), 16-byte padded
+
+// lanes of `m` below this one (two v_mbcnt; as popcount(m & ((1 << lane) - 1)) the lane mask held a register pair all along)
+__device__ __forceinline__ uint32_t lanes_below(uint64_t m) {
+  return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
 
 __device__ __forceinline__ void lds_or(uint32_t *w, uint32_t bits) {
   (void)__hip_atomic_fetch_or(w, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
@@ -123,7 +143,6 @@ __device__ bool join_read(const SeedParams &p, uint32_t s_start, uint32_t s_lo, 
   // all-pairs filter: which of four ballots holds lane i's row (i >> 2), and where in it (16 (i & 3))
   const uint64_t q_is1 = __builtin_amdgcn_ballot_w64((ln >> 2) == 1u), q_is2 = __builtin_amdgcn_ballot_w64((ln >> 2) == 2u),
                  q_is3 = __builtin_amdgcn_ballot_w64((ln >> 2) == 3u);
-  const uint32_t sh16 = 16u * (ln & 3u);
   uint32_t nxt[R], nxt_sf[R];  // first chunk of every run of the next unit (raw table entries), its packed scalars
   typedef const __attribute__((address_space(1))) uint8_t *GlobalBytes;  // (an address rebuilt from integers is "flat" to the compiler otherwise)
   auto run_base_of = [&](uint32_t alo, uint32_t ahi, uint32_t lane) -> GlobalBytes {
@@ -139,6 +158,7 @@ __device__ bool join_read(const SeedParams &p, uint32_t s_start, uint32_t s_lo, 
       nxt_sf[t] = (uint32_t)__builtin_amdgcn_readlane((int)sf, (int)(u * R + t));
       base[t] = run_base_of(alo, ahi, u * R + t);
     }
+    if (PADDED) asm volatile("" : "+v"(lane4));  // (opaque in the block of these loads, every time: hoisted out of the unit loop as a 64-bit lane offset it cost a 64-bit vector add per load)
 #pragma unroll
     for (int t = 0; t < R; ++t) {
       const uint32_t last4 = nxt_sf[t] >> 24;
@@ -195,8 +215,10 @@ __device__ bool join_read(const SeedParams &p, uint32_t s_start, uint32_t s_lo, 
   };
   prefetch(0);
   uint32_t cmin = 0xFFFFFFFFu, cmax = 0u;  // per lane: smallest / largest surviving value of this strand it has seen
-  uint64_t pm0 = 0, pm1 = 0, pm2 = 0;      // survivors of the strand's groups (lanes of flg[g])
-  uint32_t nf0 = 0, nf1 = 0, nf2 = 0;
+  // Survivors of the strand's groups (lanes of flg[g]).  The one-candidate test at the strand's end asks only whether there are
+  // any: which groups have some is a scalar bit field; the masks and the groups' numbers of flagged values wait in LDS
+  // (scatter[4 g ..], written by lane 0 — scatter is otherwise used by the general path alone, which fetches them first).
+  uint32_t surv_groups = 0;
   bool any_hi = false;  // a survivor sits in the second flagged value of some lane
 #pragma unroll 1
   for (uint32_t u = 0; u < kUnits; ++u) {
@@ -232,217 +254,20 @@ __device__ bool join_read(const SeedParams &p, uint32_t s_start, uint32_t s_lo, 
       if (kFlagCap > (uint32_t)kWave) flg_g[ln + (uint32_t)kWave] = 0xFFFFFFFFu;
     }
     if (!skip) {
-      const bool long_lists = f_max > (uint32_t)kWave;  // some list has a second chunk (entries 64..127)
-      uint32_t hv[R];
+      // no second chunk, and no remapped entry among the first chunks (a lane behind a list's end holds a pad or the list's last
+      // entry: one compare for the unit) -> the plain body
+      uint32_t first_max = val[0];
 #pragma unroll
-      for (int t = 0; t < R; ++t) hv[t] = kDenseSent;
-      if (long_lists) {
-#pragma unroll
-        for (int t = 0; t < R; ++t) {
-          if (kOptLong && f[t] <= (uint32_t)kWave) continue;  // (wave-uniform: only the runs that have a second chunk)
-          const uint32_t last4 = f[t] > (uint32_t)kWave ? (f[t] - 1u) * 4u : 0u;
-          const uint32_t at4 = lane4 + 4u * (uint32_t)kWave;
-          if (PADDED)
-            hv[t] = *(const __attribute__((address_space(1))) uint32_t *)(run_base(u * R + t) + at4);
-          else
-            hv[t] = *(const __attribute__((address_space(1))) uint32_t *)(run_base(u * R + t) + (at4 < last4 ? at4 : last4));
-        }
-      }
-      bool remap;
-      {
-        uint32_t raw_max = val[0];  // (a lane behind a list's end holds the list's last entry: one compare for the unit)
-#pragma unroll
-        for (int t = 1; t < R; ++t) raw_max = val[t] > raw_max ? val[t] : raw_max;
-        if (long_lists) {
-#pragma unroll
-          for (int t = 0; t < R; ++t) raw_max = hv[t] > raw_max ? hv[t] : raw_max;  // (kDenseSent < kDenseRemap: a run without a second chunk says nothing)
-        }
-        remap = __builtin_amdgcn_ballot_w64(raw_max >= kDenseRemap) != 0;
-      }
-      uint32_t max_u = 0;
-      bool any_u = true;
-      uint64_t vm[R];  // lanes that hold an entry of run t's first chunk (kOptSent): scalar arithmetic on the run's length
-#pragma unroll
-      for (int t = 0; t < R; ++t) vm[t] = 0;
-      if (__builtin_expect(remap, 0)) {
-        // rare: entries within kDenseNear of a sequence start are resolved exactly (pos >= start or dropped); the maximum
-        // of U then comes from a wave reduction (a dropped entry may sit at the end of a run)
-        uint32_t mx = 0, have_u = 0;
-        auto settle = [&](uint32_t &v, bool have, uint32_t start) {
-          const uint32_t raw = v;
-          v = kDenseSent;
-          if (have) {
-            v = raw - start;
-            if (raw >= kDenseRemap) {
-              const uint32_t sq = (raw - kDenseRemap) >> 10, pos = raw & (kDenseNear - 1u);
-              v = pos >= start ? p.goff[seq_base + sq] + pos - start : kDenseSent;
-            }
-          }
-        };
-#pragma unroll 1
-        for (int t = 0; t < R; ++t) {
-          // (rolled, the arrays through selects: this path must stay small)
-          uint32_t a_ = 0, b_ = 0;
-#pragma unroll
-          for (int q = 0; q < R; ++q) a_ = q == t ? val[q] : a_, b_ = q == t ? hv[q] : b_;
-          uint32_t f_t = 0, st_t = 0;
-#pragma unroll
-          for (int q = 0; q < R; ++q) f_t = q == t ? f[q] : f_t, st_t = q == t ? st[q] : st_t;
-          settle(a_, ln < f_t, st_t);
-          settle(b_, long_lists && ln + (uint32_t)kWave < f_t, st_t);
-          if (t < R - 1) {
-            if (a_ < kDenseVLimit) mx = a_ > mx ? a_ : mx, have_u = 1;
-            if (b_ < kDenseVLimit) mx = b_ > mx ? b_ : mx, have_u = 1;
-          }
-          if (kOptSent) a_ = a_ < kDenseVLimit ? a_ : sent_b;  // (a sentinel of the lane's own: no two dropped entries in one slot)
-#pragma unroll
-          for (int q = 0; q < R; ++q) val[q] = q == t ? a_ : val[q], hv[q] = q == t ? b_ : hv[q];
-        }
-        any_u = __builtin_amdgcn_ballot_w64(have_u != 0) != 0;
-        max_u = wave_max_u32(mx);
-        if (kOptSent) {
-#pragma unroll
-          for (int t = 0; t < R; ++t) vm[t] = __builtin_amdgcn_ballot_w64(val[t] < kDenseVLimit);
-        }
+      for (int t = 1; t < R; ++t) first_max = val[t] > first_max ? val[t] : first_max;
+      const bool plain = f_max <= (uint32_t)kWave && __builtin_amdgcn_ballot_w64(first_max >= kDenseRemap) == 0;
+      if (R <= FEM_JOIN_SPLIT_MAX_R && plain) {
+#define FEM_JOIN_UNIT_PLAIN true
+#include "fem_seed_join_unit.hip.h"
+#undef FEM_JOIN_UNIT_PLAIN
       } else {
-        // every entry is real and lists ascend: the maximum of U is the largest last entry of runs 0..R-2
-        if (kOptSent) {
-          // a lane behind the list's end takes a sentinel of its own (sent_a - start: no two in one slot, fem_seed_join.hip.h
-          // top) instead of the list's last entry again; which lanes hold entries stays behind as a scalar mask
-#pragma unroll
-          for (int t = 0; t < R; ++t) {
-            if (PADDED) {
-              vm[t] = __builtin_amdgcn_ballot_w64(ln < f[t]);  // (one v_cmp into a scalar pair; as scalar arithmetic on f it is six instructions)
-              val[t] -= st[t];
-            } else {
-              const bool in = ln < f[t];
-              vm[t] = __builtin_amdgcn_ballot_w64(in);  // (the compare's own result: no instruction)
-              val[t] = (in ? val[t] : sent_a) - st[t];
-            }
-          }
-        } else {
-#pragma unroll
-          for (int t = 0; t < R; ++t) val[t] = PADDED ? val[t] - st[t] : ln < f[t] ? val[t] - st[t] : kDenseSent;  // (pads: sentinels already; the inserts test)
-        }
-        if (long_lists) {
-#pragma unroll
-          for (int t = 0; t < R; ++t) {
-            if (PADDED && (!kOptLong || f[t] > (uint32_t)kWave))
-              hv[t] -= st[t];  // (pads: "no entry" already)
-            else
-              hv[t] = ln + (uint32_t)kWave < f[t] ? hv[t] - st[t] : kDenseSent;
-          }
-#pragma unroll
-          for (int t = 0; t < R - 1; ++t) {
-            const uint32_t l_lo = (uint32_t)__builtin_amdgcn_readlane((int)val[t], (int)((f[t] - 1u) & 63u));
-            const uint32_t l_hi = (uint32_t)__builtin_amdgcn_readlane((int)hv[t], (int)((f[t] - 65u) & 63u));
-            const uint32_t lastv = f[t] > (uint32_t)kWave ? l_hi : l_lo;
-            max_u = f[t] && lastv > max_u ? lastv : max_u;
-          }
-        } else {
-#pragma unroll
-          for (int t = 0; t < R - 1; ++t) {
-            const uint32_t lastv = (uint32_t)__builtin_amdgcn_readlane((int)val[t], (int)((f[t] - 1u) & 63u));
-            max_u = f[t] && lastv > max_u ? lastv : max_u;
-          }
-        }
-      }
-      if (keep_all) any_u = true, max_u = 0xFFFFFFFFu;
-      if (any_u) {
-        // the last run keeps values <= max(U) only (src/filter.c:85); everything dropped becomes a sentinel
-        if (kOptSent) {
-          const bool keep = val[R - 1] <= max_u;
-          vm[R - 1] &= __builtin_amdgcn_ballot_w64(keep);
-          val[R - 1] = keep ? val[R - 1] : sent_b;
-        } else {
-          val[R - 1] = val[R - 1] <= max_u ? val[R - 1] : kDenseSent;
-        }
-        if (long_lists) hv[R - 1] = hv[R - 1] <= max_u ? hv[R - 1] : kDenseSent;
-        // ---- insert, then flag (a neighbouring slot is present: the flagged values are compacted into the group's array).
-        //      In batches of kBatch chunks: all of a batch's atomics back to back, its marks, later all of a batch's window
-        //      reads before the first is used.  At R <= 6 a batch is the whole unit; above, one chunk — what a batch holds
-        //      in registers (at R = 5 batches of 1, 2, 3 or 5 chunks run within 3 % of each other: the kernel is bound by
-        //      instruction issue, not by the LDS round trips) (hit bits, window words) decides whether the kernel fits the 80 registers of six waves per SIMD,
-        //      i.e. whether five of its blocks or four sit on a CU beside seed_select_kernel ----
-        constexpr int kBatch = R <= 6 ? R : FEM_JOIN_BATCH_HI;
-        // `exact`: the lanes without an entry are tested one by one (v < kDenseVLimit).  Otherwise `valid` says which lanes count
-        // and a flagged lane WITHOUT an entry — always above the run's lanes with one: lists ascend, both ends of a run are
-        // cut from the top — stores its sentinel at the place the next flagged value will take, or behind the last one,
-        // where the exact filter reads it as "no value" (it lies above every coordinate).
-        auto flag_chunk = [&](uint32_t v, uint32_t xw, uint64_t valid, bool exact) {
-          if (FEM_JOIN_ABL & 1) {
-            asm volatile("" ::"v"(xw), "v"(v));
-            return;
-          }
-          bool near = xw >= kNearTop;
-          if (exact) near = near && v < kDenseVLimit;
-          const uint64_t m = exact ? __builtin_amdgcn_ballot_w64(near) : __builtin_amdgcn_ballot_w64(near) & valid;
-          if (!exact && m == 0) return;  // (wave-uniform)
-          uint32_t pos = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, n_flag));
-          pos = pos < kFlagCap ? pos : kFlagCap;
-          if (near) flg_g[pos] = v;
-          n_flag += (uint32_t)__popcll(m);
-        };
-        auto insert_all = [&](uint32_t (&vals)[R], bool checked, bool second) {
-#pragma unroll
-          for (int t0 = 0; t0 < R; t0 += kBatch) {
-            uint32_t hit[kBatch];
-#pragma unroll
-            for (int q = 0; q < kBatch; ++q)
-              if (t0 + q < R) {
-                hit[q] = 0;
-                if (second && kOptLong && f[t0 + q] <= (uint32_t)kWave) continue;
-                hit[q] = checked ? insert(vals[t0 + q]) : insert_plain(vals[t0 + q]);
-              }
-            // a slot that took a second value (every true hit does): chunk by chunk, only where some lane saw one
-#pragma unroll
-            for (int q = 0; q < kBatch; ++q)
-              if (t0 + q < R) {
-                if (second && kOptLong && f[t0 + q] <= (uint32_t)kWave) continue;
-                if (kOptHit) {
-                  mark(vals[t0 + q], hit[q]);
-                } else if (__builtin_amdgcn_ballot_w64(hit[q] != 0u)) {
-                  mark(vals[t0 + q], hit[q]);
-                }
-              }
-          }
-        };
-        auto flag_all = [&](uint32_t (&vals)[R], bool second, bool exact) {
-#pragma unroll
-          for (int t0 = 0; t0 < R; t0 += kBatch) {
-            uint32_t x[kBatch];
-#pragma unroll
-            for (int q = 0; q < kBatch; ++q)
-              if (t0 + q < R) {
-                if (second && kOptLong && f[t0 + q] <= (uint32_t)kWave) continue;
-                x[q] = window_top(vals[t0 + q]);
-              }
-#pragma unroll
-            for (int q = 0; q < kBatch; ++q)
-              if (t0 + q < R) {
-                if (second && kOptLong && f[t0 + q] <= (uint32_t)kWave) continue;
-                flag_chunk(vals[t0 + q], x[q], vm[t0 + q], exact);
-              }
-          }
-        };
-        if (FEM_JOIN_ABL & 64) {
-#pragma unroll
-          for (int t = 0; t < R; ++t) asm volatile("" ::"v"(val[t]), "v"(hv[t]));
-        } else {
-        insert_all(val, !kOptSent, false);
-        if (long_lists) insert_all(hv, true, true);
-        wave_sync_lds();
-        if (!kOptSent || __builtin_expect(remap, 0)) flag_all(val, false, true); else flag_all(val, false, false);
-        if (long_lists) flag_all(hv, true, true);  // (second chunks keep the compare against the sentinel: they are the exception)
-        wave_sync_lds();
-        }
-        if (!(FEM_JOIN_ABL & 8)) {  // leave the bitmap clean: every lane clears its 16-byte pieces (the guard word sits behind them)
-          uint4 *b4 = (uint4 *)bitmap;
-#pragma unroll
-          for (uint32_t k = 0; k < kWords / 4u / (uint32_t)kWave; ++k) b4[k * (uint32_t)kWave + ln] = make_uint4(0u, 0u, 0u, 0u);
-        }
-        wave_sync_lds();
-        if (n_flag > kFlagCap) return false;
+#define FEM_JOIN_UNIT_PLAIN false
+#include "fem_seed_join_unit.hip.h"
+#undef FEM_JOIN_UNIT_PLAIN
       }
     }
     if (kSecondProbe && n_flag > kProbeMin) {
@@ -509,6 +334,8 @@ __device__ bool join_read(const SeedParams &p, uint32_t s_start, uint32_t s_lo, 
         const uint32_t *fp = flg_g + (ln >> 4);
         const uint64_t m0 = __builtin_amdgcn_ballot_w64(xj - fp[0] <= e), m1 = __builtin_amdgcn_ballot_w64(xj - fp[4] <= e);
         const uint64_t m2 = __builtin_amdgcn_ballot_w64(xj - fp[8] <= e), m3 = __builtin_amdgcn_ballot_w64(xj - fp[12] <= e);
+        uint32_t sh16;  // 16 (i & 3), made here: as a lane constant it held a register through the whole kernel
+        asm volatile("v_lshlrev_b32 %0, 4, %1" : "=v"(sh16) : "v"(ln & 3u));
         const uint32_t r0 = (uint32_t)(m0 >> sh16), r1 = (uint32_t)(m1 >> sh16), r2 = (uint32_t)(m2 >> sh16), r3 = (uint32_t)(m3 >> sh16);
         uint32_t row = r0;  // (three conditional moves on lane masks that never change: as selects the compiler turns them into branches)
         asm("v_cndmask_b32 %0, %0, %1, %2" : "+v"(row) : "v"(r1), "s"(q_is1));
@@ -549,9 +376,11 @@ __device__ bool join_read(const SeedParams &p, uint32_t s_start, uint32_t s_lo, 
         cmax = pass_hi && fv_hi > cmax ? fv_hi : cmax;
       }
       if (pm != 0) {
-        if (g == 0) pm0 = pm, nf0 = n_flag;
-        else if (g == 1) pm1 = pm, nf1 = n_flag;
-        else pm2 = pm, nf2 = n_flag;
+        surv_groups |= 1u << g;
+        if (ln == 0) {
+          scatter[4u * g] = (uint32_t)pm, scatter[4u * g + 1u] = (uint32_t)(pm >> 32);
+          scatter[4u * g + 2u] = n_flag;
+        }
         cmin = pass && fv < cmin ? fv : cmin;
         cmax = pass && fv > cmax ? fv : cmax;
       }
@@ -559,7 +388,7 @@ __device__ bool join_read(const SeedParams &p, uint32_t s_start, uint32_t s_lo, 
     if (g != (uint32_t)kStep - 1u) continue;
     // ---- the strand's three groups are done: its candidates ----
     uint32_t kept = 0, cv = 0;
-    if ((pm0 | pm1 | pm2) != 0 || any_hi) {
+    if (surv_groups != 0 || any_hi) {
       const uint32_t lo_all = wave_min_u32(cmin), hi_all = wave_max_u32(cmax);
       if (hi_all - lo_all <= e) {  // every survivor within e of the smallest: the greedy merges keep exactly that one
         cv = ln == 0 ? lo_all : 0u;
@@ -568,11 +397,14 @@ __device__ bool join_read(const SeedParams &p, uint32_t s_start, uint32_t s_lo, 
         return false;  // (the general path below takes one survivor per lane)
       } else {
         // general case: per group, survivors sorted into lanes and merged greedily (src/filter.c:45-78)
+        wave_sync_lds();
+        const uint32_t surv = scatter[ln];  // lane 4 g: the group's mask (two words), then its number of flagged values
 #pragma unroll 1
         for (uint32_t gg = 0; gg < (uint32_t)kStep; ++gg) {
-          const uint64_t pm = gg == 0 ? pm0 : gg == 1 ? pm1 : pm2;
-          const uint32_t nfl = gg == 0 ? nf0 : gg == 1 ? nf1 : nf2;
-          if (pm == 0) continue;
+          if (!((surv_groups >> gg) & 1u)) continue;
+          const uint64_t pm = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)surv, (int)(4u * gg)) |
+                              ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)surv, (int)(4u * gg + 1u)) << 32);
+          const uint32_t nfl = (uint32_t)__builtin_amdgcn_readlane((int)surv, (int)(4u * gg + 2u));
           const uint32_t nF = (uint32_t)__popcll(pm);
           const bool mine = (pm >> ln) & 1ull;
           const uint32_t fv = ln < nfl ? flg[gg * kFlgStride + ln] : 0u;
@@ -595,7 +427,7 @@ __device__ bool join_read(const SeedParams &p, uint32_t s_start, uint32_t s_lo, 
     cand_lds[(u >= (uint32_t)kStep ? (uint32_t)kWave : 0u) + ln] = cv;
     if (u >= (uint32_t)kStep) kept1 = kept; else kept0 = kept;
     cmin = 0xFFFFFFFFu, cmax = 0u, any_hi = false;
-    pm0 = pm1 = pm2 = 0, nf0 = nf1 = nf2 = 0;
+    surv_groups = 0;
   }
   return true;
 }
@@ -652,7 +484,7 @@ __device__ __forceinline__ void seed_join_body(const SeedParams &p, uint8_t *sme
     uint32_t pull = 0;
     if (ln == 0) pull = atomicAdd(p.work_cursor, kReadBlock);
     pull = bcast0(pull);
-    if ((uint64_t)p.read_begin + pull >= p.n_reads) break;
+    if (p.read_begin >= p.n_reads || pull >= p.n_reads - p.read_begin) break;  // (32-bit, scalar: an ordered 64-bit compare is a vector instruction on a register pair)
     const uint32_t r0 = p.read_begin + pull;
     const uint32_t n_blk = p.n_reads - r0 < kReadBlock ? p.n_reads - r0 : kReadBlock;
     if (ln < 2u * kReadBlock) blk_entries[ln] = make_uint2(kBlkSkip, 0u);
@@ -660,13 +492,23 @@ __device__ __forceinline__ void seed_join_body(const SeedParams &p, uint8_t *sme
     uint2 hdr = make_uint2(kSelSlow, 0u);
     if (ln < n_blk) hdr = p.sel_hdr[r0 + ln];
     uint2 sel_next = make_uint2(0u, 0u);
-    if (!BANKED && ln < 2u * kSeeds) sel_next = p.sel[(size_t)r0 * (2u * kSeeds) + ln];
+    // (a read's seeds: scalar row address + 32-bit lane offset made on the spot; as p.sel + lane the 64-bit lane address held a
+    //  register pair through the whole kernel)
+    auto sel_of = [&](uint32_t read) -> uint2 {
+      typedef const __attribute__((address_space(1))) uint8_t *GlobalBytes;
+      uint32_t lane8;
+      asm volatile("v_lshlrev_b32 %0, 3, %1" : "=v"(lane8) : "v"(ln));
+      const GlobalBytes row = (GlobalBytes)(uintptr_t)(p.sel + (size_t)read * (2u * kSeeds));
+      const uint64_t w = *(const __attribute__((address_space(1))) uint64_t *)(row + lane8);  // (.x low, .y high: one 8-byte load)
+      return make_uint2((uint32_t)w, (uint32_t)(w >> 32));
+    };
+    if (!BANKED && ln < 2u * kSeeds) sel_next = sel_of(r0);
     for (uint32_t rb = 0; rb < n_blk; ++rb) {
       const uint32_t read = r0 + rb;
       const uint32_t h0 = (uint32_t)__builtin_amdgcn_readlane((int)hdr.x, (int)rb);
       const uint32_t status = h0 & 3u, L = h0 >> 8;
       const uint2 sel = sel_next;
-      if (!BANKED && rb + 1u < n_blk && ln < 2u * kSeeds) sel_next = p.sel[(size_t)(read + 1u) * (2u * kSeeds) + ln];
+      if (!BANKED && rb + 1u < n_blk && ln < 2u * kSeeds) sel_next = sel_of(read + 1u);
       if (status == kSelSlow) continue;  // queued by seed_select_kernel
       if (status == kSelNone) {
         if (ln / 2u == rb) blk_entries[ln] = make_uint2(0u, 0u);
@@ -718,7 +560,7 @@ __device__ __forceinline__ void seed_join_body(const SeedParams &p, uint8_t *sme
               failed = true;
               break;
             }
-            if (ok) stash[strand * kStash + acc[strand] + (uint32_t)__popcll(mo & ((1ull << ln) - 1ull))] = (((uint64_t)sq << 32) | pos) - (uint64_t)p.e;
+            if (ok) stash[strand * kStash + acc[strand] + lanes_below(mo)] = (((uint64_t)sq << 32) | pos) - (uint64_t)p.e;
             acc[strand] += n_ok;
           }
         }
@@ -742,7 +584,7 @@ __device__ __forceinline__ void seed_join_body(const SeedParams &p, uint8_t *sme
               base = bcast0(base);
               chunk.next = base + n_out, chunk.left = kSlotChunk - n_out;
             }
-            if ((unsigned long long)base + n_out > p.cand_cap) {
+            if (n_out > p.cand_cap || base > p.cand_cap - n_out) {
               if (ln == 0) atomicOr(&p.ctr[1], kFlagCandOverflow);
             } else {
               for (uint32_t i = ln; i < n_out; i += (uint32_t)kWave) {
@@ -811,10 +653,10 @@ __device__ __forceinline__ void seed_join_body(const SeedParams &p, uint8_t *sme
             base = bcast0(base);
             chunk.next = base + n_out, chunk.left = kSlotChunk - n_out;
           }
-          if ((unsigned long long)base + n_out > p.cand_cap) {
+          if (n_out > p.cand_cap || base > p.cand_cap - n_out) {
             if (ln == 0) atomicOr(&p.ctr[1], kFlagCandOverflow);
           } else if (ok) {
-            const uint32_t rank = (uint32_t)__popcll(mo & ((1ull << ln) - 1ull)), at = base + rank;
+            const uint32_t rank = lanes_below(mo), at = base + rank;
             p.cand[at] = out;
             p.cand_meta[at] = (read * 2u + strand) | (rank < (n_out & ~7u) ? kMeta16 : 0u);
           }
