@@ -40,6 +40,7 @@ namespace {
 constexpr int kSlots = FEM_SLOTS;
 constexpr uint32_t kMaxReadLen = 1024;
 constexpr size_t kFrontPad = 16;  // kernels fetch a reverse-strand chunk from up to 15 bytes in front of a read
+constexpr size_t kPackedFrontPad = 256;  // ... and verify_kernel_packed up to 16 bytes in front of a read's codes (a multiple of hipMalloc's alignment)
 constexpr uint32_t kXcapSmall = 512, kFcap = 128, kCcap = 128;
 
 constexpr int kTimedKernels = 15;  // fem_dev_kernel_time ids: 0 seed (join), 1 verify, 2 generic seed, 3-5 tail, 6 pack_results_kernel (round 5; the count kernel of rounds 1-2 before), 7 SAM text, 8 seed selection, 9 pairing, 10 mate rescue, 11 BAM records, 12 BGZF, 13 MAPQ, 14 the line index with unmapped reads
@@ -83,7 +84,8 @@ struct Slot {
   hipEvent_t ev_text_staged = nullptr; // ... and have arrived (the SAM text's kernels wait for it)
   hipEvent_t ev_text_order = nullptr;  // the slot's last SAM text has been rendered (its kernels read the same arrays)
   bool have_text_order = false;
-  uint8_t *d_packed = nullptr;            // packed transfer (fem_dev_stage_reads): 2-bit codes + positions of other characters
+  uint8_t *d_packed_alloc = nullptr;      // packed transfer (fem_dev_stage_reads): kPackedFrontPad bytes of padding, 2-bit codes + positions of other characters, 64 bytes of slack
+  uint8_t *packed() const { return d_packed_alloc + kPackedFrontPad; }
   size_t packed_cap = 0;
   uint32_t *d_exc_bits = nullptr;         // ... bit r: read r has such a character (the device tail reads the others' bases from d_packed)
   size_t exc_bits_cap = 0;
@@ -270,6 +272,7 @@ struct fem_dev {
   uint32_t *d_occ32 = nullptr, *d_goff = nullptr, *d_blkseq = nullptr;
   uint32_t list_shift = 0;        // != 0: d_occ32 is the strided table (bucket h at h << list_shift, fem_seed_dense.hip.h); 0: compact
   bool no_strided = false;        // FEM_NO_STRIDED=1: keep the compact 32-bit table (test hook / A-B)
+  bool verify_chars = false;      // FEM_VERIFY_CHARS=1: verify_kernel (characters) on packed batches too (test hook / A-B)
   uint32_t *d_freq11 = nullptr;  // saturated byte frequencies per 11-mer (fem_seed_select.hip.h), 64 MiB
   // banks of sequences, each with 32-bit coordinates of its own (fem_seed_dense.hip.h); 1 = the whole reference in one
   uint32_t n_banks = 1, bank_first[5] = {0, 0, 0, 0, 0};
@@ -291,6 +294,7 @@ struct fem_dev {
   Slot slot[kSlots];
   bool timing = false;
   int verify_blocks_per_cu = 0;  // resident 256-thread blocks of verify_kernel per CU (queried once)
+  int verify_packed_blocks_per_cu = 0;  // ... and of verify_kernel_packed
   double t_ms[kTimedKernels] = {};
   uint64_t t_n[kTimedKernels] = {};
   bool force_generic = false;  // FEM_FORCE_GENERIC=1: skip the fast seed kernel (test hook)
@@ -958,12 +962,19 @@ int launch_batch(fem_dev *h, Slot &s) {
     vp.n_map = s.d_nmap, vp.stats = d_stats;
     HIP_TRY(h, hipMemsetAsync(s.d_nmap, 0, (size_t)s.n_reads * sizeof(uint32_t), s.stream));
     // grid-stride kernel: exactly the blocks that are resident together, or the ones that start late set the makespan
-    if (h->verify_blocks_per_cu == 0) {
+    // A batch that came packed (equal-length reads, codes in d_packed_alloc) is verified straight from its 2-bit codes; every
+    // other one — mixed lengths, FEM_NO_PACK, the zero-copy character forms — from its characters.
+    const bool verify_packed = s.sent_packed && !h->verify_chars;
+    if (verify_packed) vp.packed = s.packed(), vp.exc_bits = s.d_exc_bits, vp.bpr = s.packed_bpr, vp.len = s.max_len;
+    int &v_per_cu = verify_packed ? h->verify_packed_blocks_per_cu : h->verify_blocks_per_cu;
+    if (v_per_cu == 0) {
       int nb = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, femk::verify_kernel, 256, 0) != hipSuccess || nb <= 0) nb = 4;
-      h->verify_blocks_per_cu = nb;
+      const hipError_t qe = verify_packed ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, femk::verify_kernel_packed, 256, 0)
+                                          : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, femk::verify_kernel, 256, 0);
+      if (qe != hipSuccess || nb <= 0) nb = 4;
+      v_per_cu = nb;
     }
-    const uint32_t vgrid = (uint32_t)h->n_cu * (uint32_t)h->verify_blocks_per_cu;
+    const uint32_t vgrid = (uint32_t)h->n_cu * (uint32_t)v_per_cu;
     if (split_dense) {
       // dense index: seed selection for blocks of reads (fem_seed_select.hip.h), then the bitmap join on 32-bit
       // coordinates, a wave per read (fem_seed_dense.hip.h)
@@ -1098,7 +1109,10 @@ int launch_batch(fem_dev *h, Slot &s) {
       rc = timed(2, s.stream, [&] { hipLaunchKernelGGL(femk::seed_filter_kernel, dim3(grid), dim3(64u * wpb), lds_bytes, s.stream, sp); });
       if (rc) return rc;
     }
-    rc = timed(1, s.stream, [&] { hipLaunchKernelGGL(femk::verify_kernel, dim3(vgrid), dim3(256), 0, s.stream, vp); });
+    rc = timed(1, s.stream, [&] {
+      if (verify_packed) hipLaunchKernelGGL(femk::verify_kernel_packed, dim3(vgrid), dim3(256), 0, s.stream, vp);
+      else hipLaunchKernelGGL(femk::verify_kernel, dim3(vgrid), dim3(256), 0, s.stream, vp);
+    });
     if (rc) return rc;
     s.packed_enqueued = false, s.packed_home = 0, s.packed_per_read_home = false;
     // (the packing inside the chain of the batches' kernels, 0.07 ms: beside the next batch's join — three kernels starting at
@@ -1319,7 +1333,7 @@ int enqueue_packed(fem_dev *h, Slot &s, uint64_t n, uint32_t len, uint64_t n_exc
   const uint64_t code_bytes = fempack::code_bytes(n, len), n_bases = n * (uint64_t)len;
   const uint64_t total = code_bytes + n_exc * 5u;
   int rc;
-  if ((rc = dev_realloc(h, &s.d_packed, &s.packed_cap, (size_t)total + 64))) return rc;
+  if ((rc = dev_realloc(h, &s.d_packed_alloc, &s.packed_cap, kPackedFrontPad + (size_t)total + 64))) return rc;
   if ((rc = dev_realloc(h, &s.d_bases_alloc, &s.bases_cap, kFrontPad + (size_t)n_bases + 64))) return rc;
   if ((rc = dev_realloc(h, &s.d_off, &s.off_cap, (size_t)n + 1))) return rc;
   if ((rc = dev_realloc(h, &s.d_exc_bits, &s.exc_bits_cap, (size_t)n / 32 + 2))) return rc;
@@ -1338,22 +1352,22 @@ int enqueue_packed(fem_dev *h, Slot &s, uint64_t n, uint32_t len, uint64_t n_exc
     // (the last part takes the codes' padding and the exceptions along)
     const uint64_t b0 = r0 * bpr, b1 = q + 1 == s.parts ? total : r1 * bpr;
     Span span(h, s, 20, s.stream);
-    if (b1 > b0) HIP_TRY(h, hipMemcpyAsync(s.d_packed + b0, s.h_bases + b0, b1 - b0, hipMemcpyHostToDevice, s.stream));
+    if (b1 > b0) HIP_TRY(h, hipMemcpyAsync(s.packed() + b0, s.h_bases + b0, b1 - b0, hipMemcpyHostToDevice, s.stream));
     // (the link goes to the next batch's copy as soon as this batch's last byte is over — not behind the expansion kernel,
     //  which waits for a free wave slot beside the running kernels: that chained C2's batches at 2.0 ms apiece)
     if (q + 1 == s.parts && (rc = h2d_end(h, s))) return rc;
     if (r1 > r0) {
       const uint32_t grid = (uint32_t)std::min<uint64_t>(((r1 - r0) * bpr + 255) / 256, (uint64_t)h->n_cu * 16u);
-      hipLaunchKernelGGL(femk::unpack_reads_kernel, dim3(grid), dim3(256), 0, s.stream, (const uint8_t *)s.d_packed + b0, r1 - r0, len, bpr,
+      hipLaunchKernelGGL(femk::unpack_reads_kernel, dim3(grid), dim3(256), 0, s.stream, (const uint8_t *)s.packed() + b0, r1 - r0, len, bpr,
                          s.bases() + r0 * len);
     }
     if (s.parts > 1) HIP_TRY(h, hipEventRecord(s.ev_part[q], s.stream));
   }
   if (n_exc) {
     const dim3 g((uint32_t)std::min<uint64_t>((n_exc + 255) / 256, (uint64_t)h->n_cu * 4u));
-    hipLaunchKernelGGL(femk::scatter_chars_kernel, g, dim3(256), 0, s.stream, (const uint32_t *)(s.d_packed + code_bytes),
-                       (const uint8_t *)(s.d_packed + code_bytes + 4u * n_exc), n_exc, s.bases());
-    hipLaunchKernelGGL(femk::mark_exception_reads_kernel, g, dim3(256), 0, s.stream, (const uint32_t *)(s.d_packed + code_bytes), n_exc, len,
+    hipLaunchKernelGGL(femk::scatter_chars_kernel, g, dim3(256), 0, s.stream, (const uint32_t *)(s.packed() + code_bytes),
+                       (const uint8_t *)(s.packed() + code_bytes + 4u * n_exc), n_exc, s.bases());
+    hipLaunchKernelGGL(femk::mark_exception_reads_kernel, g, dim3(256), 0, s.stream, (const uint32_t *)(s.packed() + code_bytes), n_exc, len,
                        s.d_exc_bits);
   }
   s.packed_bpr = bpr;
@@ -1451,6 +1465,7 @@ int fem_dev_open(int device, fem_dev **out) {
     h->force_dense = testing_switch("FEM_FORCE_DENSE");
     h->no_dense = testing_switch("FEM_NO_DENSE");
     h->no_strided = testing_switch("FEM_NO_STRIDED");
+    h->verify_chars = testing_switch("FEM_VERIFY_CHARS");
     h->tiny_buffers = testing_switch("FEM_TEST_TINY_BUFFERS");
     if (const char *bl = getenv("FEM_TEST_BANK_BASES")) h->bank_limit = strtoull(bl, nullptr, 10);
     if (const char *bs = getenv("FEM_TEST_BANK_SEQS")) h->bank_seqs = (uint32_t)strtoul(bs, nullptr, 10);
@@ -1473,7 +1488,7 @@ int fem_dev_close(fem_dev *h) {
     drain_timing(h, s);
     for (void *p : {(void *)s.d_bases_alloc, (void *)s.d_off, (void *)s.d_cand, (void *)s.d_meta, (void *)s.d_ed,
                     (void *)s.d_end, (void *)s.d_begin, (void *)s.d_count, (void *)s.d_nmap, (void *)s.d_ctl,
-                    (void *)s.d_arena, (void *)s.d_slow, (void *)s.d_sel, (void *)s.d_sel_hdr, (void *)s.d_packed, (void *)s.d_exc_bits, (void *)s.d_quals, (void *)s.d_names,
+                    (void *)s.d_arena, (void *)s.d_slow, (void *)s.d_sel, (void *)s.d_sel_hdr, (void *)s.d_packed_alloc, (void *)s.d_exc_bits, (void *)s.d_quals, (void *)s.d_names,
                     (void *)s.d_name_off, (void *)s.d_count8, (void *)s.d_seg, (void *)s.d_pcand, (void *)s.d_ped, (void *)s.d_pend, (void *)s.d_big})
       if (p) (void)hipFree(p);
     for (void *p : {(void *)s.h_ctl, (void *)s.h_begin, (void *)s.h_count, (void *)s.h_cand, (void *)s.h_ed,
@@ -2159,7 +2174,7 @@ int fem_dev_reserve_batch(fem_dev *h, int slot, uint64_t n_reads, uint64_t n_rec
   s.n_reads = n_was;
   if (rc) return rc;
   const uint64_t n_bases = n_reads * (uint64_t)max_len;
-  if ((rc = dev_realloc(h, &s.d_packed, &s.packed_cap, (size_t)fempack::code_bytes(n_reads, max_len) + 64))) return rc;
+  if ((rc = dev_realloc(h, &s.d_packed_alloc, &s.packed_cap, kPackedFrontPad + (size_t)fempack::code_bytes(n_reads, max_len) + 64))) return rc;
   if ((rc = dev_realloc(h, &s.d_bases_alloc, &s.bases_cap, kFrontPad + (size_t)n_bases + 64))) return rc;
   if ((rc = dev_realloc(h, &s.d_off, &s.off_cap, (size_t)n_reads + 1))) return rc;
   if ((rc = dev_realloc(h, &s.d_exc_bits, &s.exc_bits_cap, (size_t)n_reads / 32 + 2))) return rc;
@@ -2268,7 +2283,7 @@ static femt::TailInput tail_input(const fem_dev *h, const Slot &s) {
   in.bases = s.bases(), in.read_off = s.d_off, in.n_reads = (uint32_t)s.n_reads, in.max_len = s.max_len;
   in.ref_raw = h->d_ref_raw, in.ref_bytes = h->ref_bytes + 64, in.seq_off = h->d_seq_off;
   in.planes = h->d_planes;
-  if (s.sent_packed) in.packed = s.d_packed, in.packed_bpr = s.packed_bpr, in.exc_bits = s.d_exc_bits;
+  if (s.sent_packed) in.packed = s.packed(), in.packed_bpr = s.packed_bpr, in.exc_bits = s.d_exc_bits;
   in.cand = s.d_cand, in.ed = s.d_ed, in.end = s.d_end, in.cand_begin = s.d_begin, in.cand_count = s.d_count;
   in.n_map = s.d_nmap, in.e = s.params.e, in.n_records = s.stats[4];
   return in;

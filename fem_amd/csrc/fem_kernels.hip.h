@@ -9,6 +9,8 @@
 //   verify_kernel      : one lane per candidate.  Restates banded_edit_distance /
 //       vectorized_banded_edit_distance (src/align.c:102-277) and the accept test
 //       of verify_candidates (src/align.c:22,40).
+//   verify_kernel_packed : the same for a batch that came packed: the read's codes
+//       straight from its two bits per base (fem_pack.h), no LDS staging.
 //   ref_encode_kernel  : reference characters -> base codes (src/utils.h:72).
 //
 // Integer / bit-parallel work only: nothing here is GEMM shaped, so no MFMA.
@@ -1312,6 +1314,12 @@ struct VerifyParams {
   // with at least one -> stats[2], stats[3]
   uint32_t *n_map;
   unsigned long long *stats;
+  // verify_kernel_packed only: the batch's 2-bit codes (fem_pack.h; read r at packed + r * bpr, at least 16 bytes of padding
+  // in front of read 0 and 64 behind the last), bit r of exc_bits: read r holds a character other than "ACGT" (its codes
+  // are not the whole truth: its lanes take the characters), and the length every read of the batch has
+  const uint8_t *packed;
+  const uint32_t *exc_bits;
+  uint32_t bpr, len;
 };
 
 __device__ __forceinline__ uint4 load_u128_unaligned(const uint8_t *p) {
@@ -1515,6 +1523,216 @@ __global__ void __launch_bounds__(256) verify_kernel(VerifyParams p) {
   // verification itself)
   for (int d = 32; d >= 1; d >>= 1) mappings += __shfl_xor(mappings, d), mapped += __shfl_xor(mapped, d);
   __syncthreads();  // (every wave is through with its staged chunks)
+  if (lane_id() == 0) part[0][threadIdx.x >> 6] = mappings, part[1][threadIdx.x >> 6] = mapped;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const uint32_t a = part[0][0] + part[0][1] + part[0][2] + part[0][3], b = part[1][0] + part[1][1] + part[1][2] + part[1][3];
+    if (a) atomicAdd(&p.stats[2], (unsigned long long)a);
+    if (b) atomicAdd(&p.stats[3], (unsigned long long)b);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// verify_kernel_packed: verify_kernel for a batch that came packed (equal-length reads at two bits per base, fem_pack.h).
+// Same planes, same column, same outcome byte for byte; what differs is the read's side:
+//   * the codes come straight out of the packed words — no characters, no decode4: one 16-byte load holds 64 columns and
+//     waits in registers (no LDS staging), the next stretch's load is issued one stretch ahead as the planes' are.  On the
+//     reverse strand column c is the complement of base L - 1 - c: the 128 bits that hold bases [L - 64 - col, L - col) —
+//     a dword more and a funnel shift where L is no multiple of four — with their sixteen-base words and the fields inside
+//     them in reverse order.  The last, partial stretch reaches up to 16 bytes in front of the read (of read 0: into the
+//     buffer's front padding); nothing of that is consumed;
+//   * a read with anything but upper-case ACGT (its bit in exc_bits) takes its characters from `bases` as verify_kernel
+//     does, sixteen per load, on a path of its own: rare, it only has to be right;
+//   * every read has p.len bases: no gathers from read_off;
+//   * the next candidate's meta and position are requested before the current one's columns are walked, its sequence
+//     offset and exception word behind them.
+// ---------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t reverse_fields2(uint32_t x) {  // the sixteen 2-bit fields in reverse order
+  x = __builtin_bitreverse32(x);
+  return ((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1);
+}
+
+constexpr int kStepsPerTextLoad = 4;  // 16 bytes of codes = 64 columns
+
+// The candidate's columns from the packed codes.  row: the read's first packed byte.  Returns whether it was rejected.
+__device__ __forceinline__ bool verify_walk_packed(const VerifyParams &p, MyersState &m, const uint8_t *row, uint32_t strand, uint64_t pat,
+                                                   int L, int e, uint32_t width, uint32_t wm) {
+  const int n_steps = (L + 15) >> 4;
+  bool rejected = false;
+  // bases [L - 64 - col, L - col) start at bit 2 * (L & 3) of their first byte (col is a multiple of 64); floor division:
+  // the last stretch starts in front of the read
+  const uint32_t sh = strand ? 2u * ((uint32_t)L & 3u) : 0u;
+  auto text_addr = [&](int col) { return strand == 0 ? row + (col >> 2) : row + ((L - 64 - col) >> 2); };
+  auto plane_chunk = [&](int q, int col) { return plane_window(p.planes, q, (pat + (uint32_t)col) >> 3); };
+  uint4 P0 = make_uint4(0, 0, 0, 0), P1 = P0, P2 = P0, P0n = P0, P1n = P0, P2n = P0, T = P0, Tn = P0;
+  uint32_t Tn4 = 0;
+  if (n_steps > 0) {
+    const uint8_t *a = text_addr(0);
+    Tn = load_u128_unaligned(a);
+    if (sh) Tn4 = load_u32_unaligned(a + 16);
+    P0n = plane_chunk(0, 0), P1n = plane_chunk(1, 0), P2n = plane_chunk(2, 0);
+  }
+  const uint32_t pat_bit = (uint32_t)pat & 7u;
+  for (int step = 0; step < n_steps && !rejected; ++step) {
+    const int col = step << 4, sub = step % kStepsPerPlaneLoad;
+    if (step % kStepsPerTextLoad == 0) {
+      T = Tn;
+      const uint32_t t4 = Tn4;
+      if (step + kStepsPerTextLoad < n_steps) {
+        const uint8_t *a = text_addr(col + 16 * kStepsPerTextLoad);
+        Tn = load_u128_unaligned(a);
+        if (sh) Tn4 = load_u32_unaligned(a + 16);
+      }
+      if (strand) {
+        const uint32_t a0 = __builtin_amdgcn_alignbit(T.y, T.x, sh), a1 = __builtin_amdgcn_alignbit(T.z, T.y, sh);
+        const uint32_t a2 = __builtin_amdgcn_alignbit(T.w, T.z, sh), a3 = __builtin_amdgcn_alignbit(t4, T.w, sh);
+        T = make_uint4(~reverse_fields2(a3), ~reverse_fields2(a2), ~reverse_fields2(a1), ~reverse_fields2(a0));
+      }
+    } else {
+      T.x = T.y, T.y = T.z, T.z = T.w;
+    }
+    if (sub == 0) {  // loads of the next stretch are issued one stretch ahead
+      P0 = P0n, P1 = P1n, P2 = P2n;
+      if (step + kStepsPerPlaneLoad < n_steps) {
+        const int nc = col + 16 * kStepsPerPlaneLoad;
+        P0n = plane_chunk(0, nc), P1n = plane_chunk(1, nc), P2n = plane_chunk(2, nc);
+      }
+    } else {
+      window_advance16(P0), window_advance16(P1), window_advance16(P2);
+    }
+    const uint32_t b0 = window_head(P0, pat_bit), b1 = window_head(P1, pat_bit), b2 = window_head(P2, pat_bit);
+    const uint32_t t = T.x;  // text[col .. col + 16), two bits each; none of them is N
+    if (col + 16 <= L) {
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const uint32_t m0 = (uint32_t)__builtin_amdgcn_sbfe((int)t, 2 * q, 1);
+        const uint32_t m1 = (uint32_t)__builtin_amdgcn_sbfe((int)t, 2 * q + 1, 1);
+        myers_column(m, b0, b1, b2, m0, m1, 0u, (uint32_t)q, width, wm);
+      }
+    } else {  // up to fifteen trailing columns
+      for (int q = 0; q < L - col; ++q) {
+        const uint32_t cb = t >> (2 * q);
+        myers_column(m, b0, b1, b2, 0u - (cb & 1u), 0u - ((cb >> 1) & 1u), 0u, (uint32_t)q, width, wm);
+      }
+    }
+    rejected = m.score > 3 * e;  // (once per step: see verify_kernel)
+  }
+  return rejected;
+}
+
+// The same from the read's characters (rd: its first), sixteen per load, as verify_kernel decodes them.
+__device__ __forceinline__ bool verify_walk_chars(const VerifyParams &p, MyersState &m, const uint8_t *rd, uint32_t strand, uint64_t pat,
+                                                  int L, int e, uint32_t width, uint32_t wm) {
+  const int n_steps = (L + 15) >> 4;
+  bool rejected = false;
+  const uint32_t complement = strand ? 0x03030303u : 0u;
+  const uint32_t pat_bit = (uint32_t)pat & 7u;
+  uint4 P0 = make_uint4(0, 0, 0, 0), P1 = P0, P2 = P0;
+  for (int step = 0; step < n_steps && !rejected; ++step) {
+    const int col = step << 4;
+    if (step % kStepsPerPlaneLoad == 0) {
+      const uint64_t at = (pat + (uint32_t)col) >> 3;
+      P0 = plane_window(p.planes, 0, at), P1 = plane_window(p.planes, 1, at), P2 = plane_window(p.planes, 2, at);
+    } else {
+      window_advance16(P0), window_advance16(P1), window_advance16(P2);
+    }
+    // the reverse strand's chunk comes from the far end; the last, partial one may start in front of the read
+    const uint4 r = load_u128_unaligned(strand == 0 ? rd + col : rd + (L - 16 - col));
+    const uint32_t b0 = window_head(P0, pat_bit), b1 = window_head(P1, pat_bit), b2 = window_head(P2, pat_bit);
+    uint32_t cw[4], nw[4];
+    decode4(strand ? __builtin_bswap32(r.w) : r.x, complement, cw[0], nw[0]);
+    decode4(strand ? __builtin_bswap32(r.z) : r.y, complement, cw[1], nw[1]);
+    decode4(strand ? __builtin_bswap32(r.y) : r.z, complement, cw[2], nw[2]);
+    decode4(strand ? __builtin_bswap32(r.x) : r.w, complement, cw[3], nw[3]);
+    const uint64_t clo = ((uint64_t)cw[1] << 32) | cw[0], chi = ((uint64_t)cw[3] << 32) | cw[2];
+    const uint64_t nlo = ((uint64_t)nw[1] << 32) | nw[0], nhi = ((uint64_t)nw[3] << 32) | nw[2];
+    const int n_col = L - col < 16 ? L - col : 16;
+    for (int q = 0; q < n_col; ++q) {
+      const uint32_t cb = (uint32_t)((q < 8 ? clo : chi) >> (8 * (q & 7)));
+      const uint32_t nb = (uint32_t)((q < 8 ? nlo : nhi) >> (8 * (q & 7)));
+      myers_column(m, b0, b1, b2, 0u - (cb & 1u), 0u - ((cb >> 1) & 1u), 0u - (nb & 1u), (uint32_t)q, width, wm);
+    }
+    rejected = m.score > 3 * e;
+  }
+  return rejected;
+}
+
+__global__ void __launch_bounds__(256, 6) verify_kernel_packed(VerifyParams p) {
+  // a scratch buffer overflowed while seeding: slots may be unwritten, the host grows the buffer and re-runs the batch
+  if (p.ctr[1] != 0) return;
+  const uint32_t total = min(p.ctr[0], p.cand_cap);
+  const uint32_t stride = gridDim.x * blockDim.x;
+  const int e = p.e, L = (int)p.len;
+  const uint32_t width = 2u * (uint32_t)e + 1u;
+  __shared__ uint32_t part[2][4];
+  uint32_t mappings = 0, mapped = 0;
+  // one candidate ahead: meta and position first, then (they need those) the sequence's offset and the read's exception word
+  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t meta_n = kInvalidMeta, exc_n = 0;
+  uint64_t c_n = 0, seq_off_n = 0;
+  auto request_second = [&] {
+    if (meta_n != kInvalidMeta) {
+      seq_off_n = p.seq_off[(uint32_t)(c_n >> 32)];
+      exc_n = p.exc_bits[(meta_n & ~kMeta16) >> 6];
+    }
+  };
+  if (i < total) {
+    meta_n = p.cand_meta[i], c_n = p.cand[i];
+    request_second();
+  }
+  while (i < total) {
+    const uint32_t meta = meta_n, exc_word = exc_n;
+    const uint64_t c = c_n, seq_off = seq_off_n;
+    const uint32_t at = i;
+    const uint32_t next = i + stride;
+    i = next > at ? next : total;  // (a wrap past 2^32 ends the lane's range)
+    meta_n = kInvalidMeta;
+    if (i < total) meta_n = p.cand_meta[i], c_n = p.cand[i];
+    if (meta == kInvalidMeta) {
+      p.ed[at] = 0xFF, p.end[at] = 0;
+      request_second();
+      continue;
+    }
+    const uint32_t read = (meta & ~kMeta16) >> 1, strand = meta & 1u;
+    const uint32_t wm = (meta & kMeta16) ? 0xFFFFu : 0xFFFFFFFFu;
+    const uint64_t pat = seq_off + (uint32_t)c;  // base index of pattern[0]
+    MyersState m{0, 0, 0};
+    bool rejected;
+    if ((exc_word >> (read & 31u)) & 1u) {
+      rejected = verify_walk_chars(p, m, p.bases + (uint64_t)read * (uint32_t)L, strand, pat, L, e, width, wm);
+    } else {
+      rejected = verify_walk_packed(p, m, p.packed + (uint64_t)read * p.bpr, strand, pat, L, e, width, wm);
+    }
+    request_second();
+    int score = m.score;
+    int best = score, endp = L - 1;
+    if (!rejected) {
+      for (int j = 0; j < 2 * e; ++j) {  // first strict minimum (src/align.c:135-146)
+        score += (int)((m.VP >> j) & 1u) - (int)((m.VN >> j) & 1u);
+        if (score < best) {
+          best = score;
+          endp = L + j;
+        }
+      }
+    }
+    const bool accepted = !rejected && best <= e;
+    p.ed[at] = accepted ? (uint8_t)best : (uint8_t)0xFF;
+    p.end[at] = accepted ? (int16_t)endp : (int16_t)0;
+    {  // n_map and the two counters as in verify_kernel: one atomic per run of lanes that accepted candidates of one read
+      const uint32_t ln = lane_id();
+      const uint64_t acc = __ballot(accepted);
+      const uint32_t prev_read = __shfl_up(read, 1);
+      const bool joins_prev = accepted && ln > 0u && ((acc >> (ln - 1u)) & 1ull) && prev_read == read;
+      const uint64_t heads = __ballot(accepted && !joins_prev);
+      if (accepted && !joins_prev) {
+        const uint64_t stop = (heads | ~acc) >> ln >> 1;  // the next head, or the next lane that accepted nothing
+        const uint32_t run = stop ? (uint32_t)__builtin_ctzll(stop) + 1u : 64u - ln;
+        mapped += (uint32_t)(atomicAdd(&p.n_map[read], run) == 0u);
+      }
+      if (accepted) ++mappings;
+    }
+  }
+  for (int d = 32; d >= 1; d >>= 1) mappings += __shfl_xor(mappings, d), mapped += __shfl_xor(mapped, d);
   if (lane_id() == 0) part[0][threadIdx.x >> 6] = mappings, part[1][threadIdx.x >> 6] = mapped;
   __syncthreads();
   if (threadIdx.x == 0) {
