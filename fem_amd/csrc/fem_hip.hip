@@ -43,7 +43,7 @@ constexpr size_t kFrontPad = 16;  // kernels fetch a reverse-strand chunk from u
 constexpr size_t kPackedFrontPad = 256;  // ... and verify_kernel_packed up to 16 bytes in front of a read's codes (a multiple of hipMalloc's alignment)
 constexpr uint32_t kXcapSmall = 512, kFcap = 128, kCcap = 128;
 
-constexpr int kTimedKernels = 15;  // fem_dev_kernel_time ids: 0 seed (join), 1 verify, 2 generic seed, 3-5 tail, 6 pack_results_kernel (round 5; the count kernel of rounds 1-2 before), 7 SAM text, 8 seed selection, 9 pairing, 10 mate rescue, 11 BAM records, 12 BGZF, 13 MAPQ, 14 the line index with unmapped reads
+constexpr int kTimedKernels = 16;  // fem_dev_kernel_time ids: 0 seed (join), 1 verify, 2 generic seed, 3-5 tail, 6 pack_results_kernel (round 5; the count kernel of rounds 1-2 before), 7 SAM text, 8 seed selection, 9 pairing, 10 mate rescue, 11 BAM records, 12 BGZF, 13 MAPQ, 14 the line index with unmapped reads, 15 the line filter's line index
 struct TimedLaunch {
   int kernel;
   hipEvent_t start, stop;
@@ -165,6 +165,8 @@ struct Slot {
   bool mapq = false;  // fem_dev_set_mapq: MAPQ from the hit strata in the slot's SAM text and BAM records
   bool unmapped = false;  // fem_dev_set_unmapped: a line for every read without a mapping in the slot's SAM text and BAM records
   uint64_t n_unmapped = 0;  // ... and how many the slot's last text or BAM had
+  int32_t report_strata = -1, report_hits = -1;  // fem_dev_set_report: the line filter of the slot's SAM text and BAM records (-1: off)
+  uint64_t n_filtered = 0;  // ... and how many lines it left out of the slot's last text or BAM
   // fem_dev_fetch_pairs: the records in output order (host copies, valid until the slot's next fetch_pairs)
   std::vector<uint16_t> pr_flag;
   std::vector<uint32_t> pr_tid, pr_pos0, pr_cigar_off, pr_cigar, pr_md_off;
@@ -2339,16 +2341,18 @@ static int tail_records(fem_dev *h, int slot, const void *out, bool copy_records
 
 // The names (and qualities, unless the caller keeps them: qual_hole) the slot's text is rendered with.
 static femt::SamInput sam_input(const fem_dev *h, const Slot &s) {
-  return {s.host_quals ? nullptr : s.d_quals, s.d_names, s.d_name_off, h->d_ref_names, h->d_ref_name_off, s.host_quals, s.mapq, s.unmapped};
+  return {s.host_quals ? nullptr : s.d_quals, s.d_names, s.d_name_off, h->d_ref_names, h->d_ref_name_off, s.host_quals, s.mapq, s.unmapped, s.report_strata, s.report_hits};
 }
 
 // What follows a text's sam() / bam() (tag: the caller, for FEM_FETCH_TIMES): the pair counts, the event the slot's next text
-// stage waits for (commit_text), the kernel times: 3-5, n_ms of the text's own from id `id` on, 9 and 10 when paired, 13 with MAPQ, 14 with lines for unmapped reads.
+// stage waits for (commit_text), the kernel times: 3-5, n_ms of the text's own from id `id` on, 9 and 10 when paired, 13 with MAPQ, 14 with lines for unmapped reads, 15 with the line filter (whose line index is the unmapped reads' too: no 14 then).
 static int text_done(fem_dev *h, int slot, const TailFront &f, const char *tag, int id, const double *ms, int n_ms) {
   Slot &s = h->slot[slot];
   s.n_proper = s.paired ? s.tail->n_proper() : 0;  // (sam() and bam() have waited for the stream once, after sizing the text)
   s.n_rescued = s.paired ? s.tail->n_rescued() : 0;
   s.n_unmapped = s.tail->n_unmapped();
+  s.n_filtered = s.tail->n_filtered();
+  const bool report = s.report_strata >= 0 || s.report_hits >= 1;
   if (!s.ev_text_order) HIP_TRY(h, hipEventCreateWithFlags(&s.ev_text_order, hipEventDisableTiming));
   HIP_TRY(h, hipEventRecord(s.ev_text_order, f.stream));
   s.have_text_order = true;
@@ -2362,7 +2366,8 @@ static int text_done(fem_dev *h, int slot, const TailFront &f, const char *tag, 
     if (s.paired) h->t_ms[9] += s.tail->pair_ms(), h->t_n[9] += 1;
     if (s.paired && s.rescue) h->t_ms[10] += s.tail->rescue_ms(), h->t_n[10] += 1;
     if (s.mapq) h->t_ms[13] += s.tail->mapq_ms(), h->t_n[13] += 1;  // (its events precede the text's sizing, which sam() and bam() wait for)
-    if (s.unmapped) h->t_ms[14] += s.tail->unmapped_ms(), h->t_n[14] += 1;  // (as do these)
+    if (s.unmapped && !report) h->t_ms[14] += s.tail->unmapped_ms(), h->t_n[14] += 1;  // (as do these)
+    if (report) h->t_ms[15] += s.tail->report_ms(), h->t_n[15] += 1;
   }
   return FEM_OK;
 }
@@ -2391,7 +2396,7 @@ static int fetch_sam(fem_dev *h, int slot, fem_batch_sam *out, bool wait) {
   if ((rc = text_done(h, slot, f, "fetch_sam", 7, &ms_text, wait ? 1 : 0))) return rc;  // (without the wait no elapsed time is read: nothing to count)
   s.qual_at = text.qual_at;
   out->text = text.text, out->len = text.len, out->n_asserted = text.n_asserted;
-  out->n_reads = f.t.n_reads, out->n_records = f.t.n_records;
+  out->n_reads = f.t.n_reads, out->n_records = f.t.n_records - s.n_filtered;  // (the filter drops lines of mapping records only)
   memcpy(out->stats, s.stats, sizeof s.stats);
   return FEM_OK;
 }
@@ -2411,7 +2416,7 @@ static int fetch_bam(fem_dev *h, int slot, int level, fem_batch_bam *out, bool w
   if ((rc = text_done(h, slot, f, "fetch_bam", 11, ms_bam, 2))) return rc;
   s.qual_at = nullptr;
   out->data = bam.data, out->len = bam.len, out->raw_len = bam.raw_len, out->n_blocks = bam.n_blocks;
-  out->n_records = f.t.n_records, out->n_asserted = bam.n_asserted;
+  out->n_records = f.t.n_records - s.n_filtered, out->n_asserted = bam.n_asserted;
   memcpy(out->stats, s.stats, sizeof s.stats);
   return FEM_OK;
 }
@@ -2512,6 +2517,30 @@ int fem_dev_unmapped_count(fem_dev *h, int slot, uint64_t *n) {
   if (!n) return fail(h, FEM_ERR_INVALID, "null output pointer");
   FEM_LOCK(h);
   *n = h->slot[slot].n_unmapped;
+  return FEM_OK;
+}
+
+int fem_dev_set_report(fem_dev *h, int slot, const fem_report_params *rp) {
+  int rc = check_slot(h, slot);
+  if (rc) return rc;
+  FEM_LOCK(h);
+  Slot &s = h->slot[slot];
+  if (!rp) {
+    s.report_strata = s.report_hits = -1;
+    return FEM_OK;
+  }
+  if (rp->strata < -1 || rp->strata > 15) return fail(h, FEM_ERR_INVALID, "strata out of range (0 <= strata <= 15, or -1 for off)");
+  if (rp->max_hits < -1 || rp->max_hits == 0) return fail(h, FEM_ERR_INVALID, "hit limit out of range (max_hits >= 1, or -1 for off)");
+  s.report_strata = rp->strata, s.report_hits = rp->max_hits;
+  return FEM_OK;
+}
+
+int fem_dev_filtered_count(fem_dev *h, int slot, uint64_t *n) {
+  int rc = check_slot(h, slot);
+  if (rc) return rc;
+  if (!n) return fail(h, FEM_ERR_INVALID, "null output pointer");
+  FEM_LOCK(h);
+  *n = h->slot[slot].n_filtered;
   return FEM_OK;
 }
 

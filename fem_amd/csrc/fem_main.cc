@@ -8,6 +8,7 @@
 // accepted insert size: the pairing and the paired SAM text on the device (fem_dev_set_pairs); `--rescue INT` adds mate rescue
 // at INT edits (fem_dev_set_rescue).  `--mapq` writes mapping qualities made on the device (fem_dev_set_mapq) instead of 255.
 // `--unmapped` adds a line for every read without a mapping, made on the device (fem_dev_set_unmapped).
+// `--strata INT` / `--max-hits INT` leave out the lines of a read beyond its best strata / its first INT (fem_dev_set_report).
 #include <errno.h>
 #include <fcntl.h>
 #include <getopt.h>
@@ -78,6 +79,8 @@ void usage_map() {
   fprintf(stderr, "        --bam[=INT]   write BAM instead of SAM: BGZF level 1 (default) or 0 (uncompressed)\n");
   fprintf(stderr, "        --mapq        write mapping qualities (0-60) from the hits' edit distances instead of 255\n");
   fprintf(stderr, "        --unmapped    write a line for every read without a mapping too (FLAG 0x4; a mate placed at its mapped mate)\n");
+  fprintf(stderr, "        --strata INT  write only a read's (a mate's) lines within INT (0-15) edits of its best one; the primary line always\n");
+  fprintf(stderr, "        --max-hits INT  write at most INT (>= 1) lines per read (per mate)\n");
   fprintf(stderr, "        -o       STR  Output SAM file \n\n");
 }
 
@@ -253,6 +256,7 @@ struct BatchBuf {  // everything about the batch that sits in one (GPU, slot) pa
   uint64_t n_proper = 0;                    // paired: proper pairs of the batch
   uint64_t n_rescued = 0;                   // --rescue: rescued mates of the batch
   uint64_t n_unmapped = 0;                  // --unmapped: lines for unmapped reads of the batch
+  uint64_t n_filtered = 0;                  // --strata / --max-hits: lines left out of the batch's text
   fem_batch_result res{};                   // per-candidate outcome (FEM_HOST_TAIL=1)
   double t_submit = 0;
   double t_slot = 0, t_filled = 0, t_submitted = 0, t_retired = 0, t_text = 0;  // FEM_STAGE_TIMES=2: the batch's way through the stages
@@ -282,6 +286,8 @@ int map_main(int argc, char **argv) {
   bool rescue_given = false;
   int bam_level = -1;  // --bam[=LEVEL]: BAM records and BGZF members made on the device (fem_dev_fetch_bam); -1: SAM
   bool unmapped = false;  // --unmapped: a line for every read without a mapping, made on the device (fem_dev_set_unmapped)
+  long long strata = -1, max_hits = -1;  // --strata / --max-hits: the line filter, made on the device (fem_dev_set_report); -1: off
+  bool strata_given = false, max_hits_given = false;
   bool mapq = false;   // --mapq: MAPQ from the hit strata, made on the device (fem_dev_set_mapq); else 255 as the reference
   fem_params params{12, 3, 2, 1};  // src/FEM_map.c:67-70: k and step are fixed, whatever the index header says
   int n_threads = 1, n_gpus = 1;
@@ -298,6 +304,7 @@ int map_main(int argc, char **argv) {
                                      {"maxins", required_argument, nullptr, 'X'}, {"rescue", required_argument, nullptr, 'R'},
                                      {"bam", optional_argument, nullptr, 'Z'},  {"mapq", no_argument, nullptr, 'Q'},
                                      {"unmapped", no_argument, nullptr, 'U'},
+                                     {"strata", required_argument, nullptr, 'S'}, {"max-hits", required_argument, nullptr, 'N'},
                                      {nullptr, 0, nullptr, 0}};
   int c, oi = 0;
   while ((c = getopt_long(argc, argv, short_opt, long_opt, &oi)) >= 0) {
@@ -320,6 +327,20 @@ int map_main(int argc, char **argv) {
         break;
       case 'Q': mapq = true; break;
       case 'U': unmapped = true; break;
+      case 'S': {
+        char *end = nullptr;
+        strata = strtoll(optarg, &end, 10);
+        if (!end || end == optarg || *end) strata = -2;  // (not a number: refused below)
+        strata_given = true;
+        break;
+      }
+      case 'N': {
+        char *end = nullptr;
+        max_hits = strtoll(optarg, &end, 10);
+        if (!end || end == optarg || *end) max_hits = -2;  // (not a number: refused below)
+        max_hits_given = true;
+        break;
+      }
       case 'e': params.e = atoi(optarg); break;
       case 't': n_threads = atoi(optarg); break;
       case 'a': params.a = atoi(optarg); break;
@@ -348,6 +369,8 @@ int map_main(int argc, char **argv) {
   else if (rescue_given && (rescue_edits < 0 || rescue_edits > 15)) bad = "Wrong rescue error threshold (0-15).";
   else if (rescue_given && max_insert - min_insert > 65536) bad = "--rescue searches insert size ranges of at most 65536.";
   else if (bam_level == -2) bad = "Wrong BAM compression level (0-1).";
+  else if (strata_given && (strata < 0 || strata > 15)) bad = "Wrong number of strata (0-15).";
+  else if (max_hits_given && (max_hits < 1 || max_hits > 0x7FFFFFFFll)) bad = "Wrong hit limit (>= 1).";
   else if (!ref_path) bad = "Reference file path is required.";
   else if (!index_path) bad = "Index file path is required.";
   else if (!read_path) bad = "Read file path is required.";
@@ -377,7 +400,12 @@ int map_main(int argc, char **argv) {
       fprintf(stderr, "--unmapped is not supported with %s=1: the lines of unmapped reads are made on the device, with its SAM text or BAM.\n", v);
       exit(EXIT_FAILURE);
     }
+    if ((strata_given || max_hits_given) && x && x[0] == '1') {  // (nor a line filter)
+      fprintf(stderr, "--strata and --max-hits are not supported with %s=1: the lines are filtered on the device, with its SAM text or BAM.\n", v);
+      exit(EXIT_FAILURE);
+    }
   }
+  const bool report = strata_given || max_hits_given;
 
   // Host placement: with one GPU the whole process (parser, formatter, staging buffers) moves next to it, before any
   // thread pool exists; with several, each GPU's worker thread does so for itself and the buffers it acquires.
@@ -487,6 +515,10 @@ int map_main(int argc, char **argv) {
           if (!rc && device_text && res_reads && res_len <= max_read_len) rc = fem_dev_reserve_batch(devs[(size_t)g], sl, res_reads, res_reads + res_reads / 8, res_len, &params);
           if (!rc && mapq) rc = fem_dev_set_mapq(devs[(size_t)g], sl, 1);
           if (!rc && unmapped) rc = fem_dev_set_unmapped(devs[(size_t)g], sl, 1);
+          if (!rc && report) {
+            const fem_report_params fp{(int32_t)strata, (int32_t)max_hits};
+            rc = fem_dev_set_report(devs[(size_t)g], sl, &fp);
+          }
           if (!rc && paired) {
             const fem_pair_params pp{(int32_t)min_insert, (int32_t)max_insert};
             rc = fem_dev_set_pairs(devs[(size_t)g], sl, &pp);
@@ -602,7 +634,7 @@ int map_main(int argc, char **argv) {
   std::vector<TextOut> texts(3);
   for (TextOut &t : texts) text_free_q.push(&t);
   std::vector<uint64_t> per_gpu((size_t)n_gpus * 5, 0), per_gpu_proper((size_t)n_gpus, 0),
-      per_gpu_rescued((size_t)n_gpus, 0), per_gpu_unmapped((size_t)n_gpus, 0);
+      per_gpu_rescued((size_t)n_gpus, 0), per_gpu_unmapped((size_t)n_gpus, 0), per_gpu_filtered((size_t)n_gpus, 0);
 
   // ---- writer (src/output_queue.c:60-91) ----
   std::thread writer([&] {
@@ -760,6 +792,7 @@ int map_main(int argc, char **argv) {
         if (!rc && paired) rc = fem_dev_pair_count(h, b->slot, &b->n_proper);
         if (!rc && rescue_given) rc = fem_dev_rescue_count(h, b->slot, &b->n_rescued);
         if (!rc && unmapped) rc = fem_dev_unmapped_count(h, b->slot, &b->n_unmapped);
+        if (!rc && report) rc = fem_dev_filtered_count(h, b->slot, &b->n_filtered);
         const double waited = real_time() - t0;
         b->t_retired = t0 + waited;
         double placing = 0;
@@ -797,6 +830,7 @@ int map_main(int argc, char **argv) {
           for (int i = 0; i < 5; ++i) per_gpu[(size_t)g * 5 + (size_t)i] += st[i];
           if (paired) per_gpu_proper[(size_t)g] += b->n_proper, per_gpu_rescued[(size_t)g] += b->n_rescued;
           per_gpu_unmapped[(size_t)g] += b->n_unmapped;
+          per_gpu_filtered[(size_t)g] += b->n_filtered;
           if (device_text) {
             n_asserted += b->sam.n_asserted;
             write_q.push(WriteItem{nullptr, b});
@@ -1135,6 +1169,11 @@ int map_main(int argc, char **argv) {
     uint64_t n_unmapped = 0;
     for (uint64_t x : per_gpu_unmapped) n_unmapped += x;
     fprintf(stderr, "The number of unmapped reads: %lu\n", (unsigned long)n_unmapped);
+  }
+  if (report) {
+    uint64_t n_filtered = 0;
+    for (uint64_t x : per_gpu_filtered) n_filtered += x;
+    fprintf(stderr, "The number of filtered lines: %lu\n", (unsigned long)n_filtered);
   }
   fprintf(stderr, "Time: %fs\n", t_mapping);
   return 0;

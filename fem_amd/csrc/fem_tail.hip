@@ -1244,7 +1244,7 @@ __device__ __forceinline__ MateCols mate_cols(const SamParams &p, uint32_t k, ui
   MateCols m{p.mtid[k], 0u, 0};
   if (m.mt != kNoMate) {
     m.mp = p.mpos0[k], m.tl = p.tlen[k];
-  } else if (kUnm) {
+  } else if (kUnm && p.pair_begin) {  // (nullptr: the kUnm instances without lines for unmapped reads, the line filter's)
     const Placed a = placed_at(p, pair_slot(p, r));
     m.mt = a.t, m.mp = a.pos0;
   }
@@ -2023,6 +2023,98 @@ __global__ void __launch_bounds__(256) mapq_kernel(MapqParams p) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// The line filter (fem_dev_set_report).  A slot (read s single-end, mate m of pair i = slot 2i + m) has the
+// lines [begin[s], begin[s + 1]) of the records or of pair_kernel's lines; d = the least NM over them (0x8000 records count).
+// Line 0 of the slot stays; line t >= 1 stays iff nm <= d + S (S on) and fewer than N of the slot's lines stay in front of it
+// (N on).  The lines that pass the stratum test are taken in order until N are there, so a line's rank among the passing ones
+// is its place in the slot's output and the slot keeps min(passing, N) lines.
+// report_kernel<false>: cnt[s] = the lines slot s keeps, 1 for a slot without lines when unmapped reads have lines; an
+// exclusive scan of cnt (rocPRIM, n_reads + 1 counts); report_kernel<true>: the same walk again, usrc[before[s] + rank] =
+// the line, or n_base + the slot's read for an unmapped one.  A slot of up to kReportAlone lines is its lane's; a larger one is
+// taken by the whole wave after the lanes' own slots: a wave minimum for d, then 64 lines per step, a ballot of the passing
+// ones and the popcount below the lane for the rank, the passing lines so far carried from step to step.
+// ---------------------------------------------------------------------------------------------------------
+constexpr uint32_t kReportAlone = 32;
+constexpr uint32_t kReportOff = 0xFFFFFFFFu;
+
+struct ReportParams {
+  uint32_t n_reads, n_base;  // n_base: records (pair mode: pair_kernel's lines)
+  const uint32_t *begin;     // n_reads + 1, by slot
+  const uint8_t *nm;         // per record
+  const uint32_t *perm;      // pair mode (else nullptr): per line of pair_kernel's, its record
+  uint32_t strata, max_hits; // kReportOff: off
+  uint32_t unmapped;         // a slot without lines has one (fem_dev_set_unmapped)
+  uint32_t *cnt;             // n_reads + 1 (the last one zero)
+  const uint32_t *before;    // n_reads + 1: the exclusive scan of cnt
+  uint32_t *usrc;            // before[n_reads]
+  uint32_t *n_lines;         // [0] that number, [1] the unmapped slots among them (zeroed before report_kernel<false>)
+};
+
+__device__ __forceinline__ uint32_t report_nm(const ReportParams &p, uint32_t k) { return p.nm[p.perm ? p.perm[k] : k]; }
+
+template <bool kWrite>
+__global__ void __launch_bounds__(256) report_kernel(ReportParams p) {
+  const uint32_t ln = threadIdx.x & 63u;
+  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = s < p.n_reads;
+  uint32_t b0 = 0, c = 0, at = 0;
+  if (live) b0 = p.begin[s], c = p.begin[s + 1] - b0;
+  if (kWrite && live) at = p.before[s];
+  if (kWrite && s == 0) p.n_lines[0] = p.before[p.n_reads];
+  const bool big = c > kReportAlone;
+  uint32_t kept = 0;
+  if (live && !big && c) {
+    uint32_t lim = kReportOff;
+    if (p.strata != kReportOff) {
+      uint32_t d = 255u;
+      for (uint32_t t = 0; t < c; ++t) {
+        const uint32_t v = report_nm(p, b0 + t);
+        d = v < d ? v : d;
+      }
+      lim = d + p.strata;
+    }
+    for (uint32_t t = 0; t < c && kept < p.max_hits; ++t) {
+      if (t && lim != kReportOff && report_nm(p, b0 + t) > lim) continue;
+      if (kWrite) p.usrc[at + kept] = b0 + t;
+      ++kept;
+    }
+  }
+  uint64_t todo = __ballot(big);
+  while (todo) {
+    const uint32_t src = (uint32_t)__builtin_ctzll(todo);
+    todo &= todo - 1u;
+    const uint32_t B0 = wave_bcast(b0, src), C = wave_bcast(c, src), AT = kWrite ? wave_bcast(at, src) : 0u;
+    uint32_t lim = kReportOff;
+    if (p.strata != kReportOff) {
+      uint32_t d = 255u;
+      for (uint32_t t = ln; t < C; t += 64u) {
+        const uint32_t v = report_nm(p, B0 + t);
+        d = v < d ? v : d;
+      }
+      lim = wave_min32(d) + p.strata;
+    }
+    uint32_t passed = 0;  // (the same in every lane)
+    for (uint32_t t0 = 0; t0 < C && passed < p.max_hits; t0 += 64u) {
+      const uint32_t t = t0 + ln;
+      const bool ok = t < C && (t == 0 || lim == kReportOff || report_nm(p, B0 + t) <= lim);
+      const uint64_t oks = __ballot(ok);
+      const uint32_t rank = passed + (uint32_t)__builtin_popcountll(oks & ((1ull << ln) - 1ull));
+      if (kWrite && ok && rank < p.max_hits) p.usrc[AT + rank] = B0 + t;
+      passed += (uint32_t)__builtin_popcountll(oks);
+    }
+    if (ln == src) kept = passed < p.max_hits ? passed : p.max_hits;
+  }
+  const bool unm = live && !c && p.unmapped;
+  if (kWrite) {
+    if (unm) p.usrc[at] = p.n_base + (p.perm ? (s & 1u) * (p.n_reads / 2u) + (s >> 1) : s);
+    return;
+  }
+  if (s <= p.n_reads) p.cnt[s] = unm ? 1u : kept;
+  const uint64_t unms = __ballot(unm);
+  if (ln == 0 && unms) atomicAdd(p.n_lines + 1, (uint32_t)__builtin_popcountll(unms));
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // Mate rescue (include/fem_hip.h).  A pair where exactly one mate (B) has no record: its other mate's first
 // kRescueAnchors records without 0x8000 are the anchors, and B's pos0 is searched in each anchor's insert window at E edits:
 // tiles c = lo + j (2E + 1), each the banded Myers of fo_banded_ed32 over ref[c, c + L + 2E) (first strict minimum, the same
@@ -2332,6 +2424,7 @@ struct Tail::Impl {
   // MAPQ (SamInput::mapq): per read (single-end), per line (pair(): pair_kernel<true>'s bytes, then the MAPQ)
   DevBuf q_read, lmq;
   // lines for unmapped reads (SamInput::unmapped): the marks, their scan, each line's source, the line count
+  // (the line filter, SamInput::strata / max_hits, uses the same four: its counts, their scan, the sources, the line count)
   DevBuf u_cnt, u_before, usrc, u_ctl;
   PinBuf h_perm, h_pflag, h_mtid, h_mpos0, h_tlen, h_pair_begin, h_pair_ctl;
   // mate rescue (pair() with a RescueInput): candidates, jobs, best hits, the tracebacks' staging, the kept flags and their scans
@@ -2350,14 +2443,18 @@ struct Tail::Impl {
   bool mapq_timed = false;           // the last text's MAPQ kernel ran between ev_mapq[0] and ev_mapq[1]
   bool unm_timed = false;            // ... and its line index kernels between ev_unm[0] and ev_unm[1]
   uint32_t n_unm = 0;                // lines for unmapped reads in the last text
+  bool rep_timed = false;            // the last text's filter kernels ran between ev_rep[0] and ev_rep[1]
+  uint32_t n_base_last = 0;          // the lines the last text had before the filter and without the unmapped reads'
+  uint32_t n_filtered = 0;           // lines the filter left out of the last text
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   hipEvent_t ev_pair[2] = {nullptr, nullptr};
   hipEvent_t ev_resc[2] = {nullptr, nullptr};
   hipEvent_t ev_mapq[2] = {nullptr, nullptr};
   hipEvent_t ev_unm[2] = {nullptr, nullptr};
+  hipEvent_t ev_rep[2] = {nullptr, nullptr};
   hipEvent_t ev_text = nullptr;  // the SAM text has arrived in h_text
   ~Impl() {  // (the buffers free themselves)
-    for (hipEvent_t e : {ev[0], ev[1], ev[2], ev[3], ev_pair[0], ev_pair[1], ev_resc[0], ev_resc[1], ev_mapq[0], ev_mapq[1], ev_unm[0], ev_unm[1], ev_text})
+    for (hipEvent_t e : {ev[0], ev[1], ev[2], ev[3], ev_pair[0], ev_pair[1], ev_resc[0], ev_resc[1], ev_mapq[0], ev_mapq[1], ev_unm[0], ev_unm[1], ev_rep[0], ev_rep[1], ev_text})
       if (e) (void)hipEventDestroy(e);
   }
   // sam() and bam(): the lines of run()'s records, or of pair()'s (rescued records included).  Fills *p (all but the text and
@@ -2366,6 +2463,10 @@ struct Tail::Impl {
   // names.unmapped: the line index first (between ev_unm[0] and ev_unm[1]).  The line count is known on the device alone then:
   // p->n_records bounds it (records + reads; the lengths behind the last line are zero, so line_off[p->n_records] is the text's
   // size all the same) and the count comes to h_ctl[8]; counted() puts it into p->n_records once the stream has been waited for.
+  // names.strata / names.max_hits (the line filter): the line index is report_kernel's instead (between ev_rep[0] and ev_rep[1]),
+  // unmapped reads' lines included where names.unmapped asks for them; the count comes home the same way, the unmapped slots'
+  // to h_ctl[9].  The text and BAM kernels are the kUnm instances then, with or without names.unmapped: without it u_base lies
+  // above every source and pair_begin is nullptr (mate_cols), so that no line takes a shape it has not without the filter.
   int lines(const TailInput &in, const SamInput &names, bool pair_order, uint32_t *bad_name, hipStream_t stream, int n_cu, SamParams *p,
               std::string *err) {
     if (pair_order && !paired) {
@@ -2379,6 +2480,7 @@ struct Tail::Impl {
     }
     const uint32_t nr = n_base + (names.unmapped ? last_n : 0u);
     const size_t r1 = (size_t)nr + 1, n1 = (size_t)last_n + 1;
+    const bool report = names.strata >= 0 || names.max_hits >= 1;
     for (hipEvent_t &e : ev)
       if (!e) TAIL_TRY(hipEventCreate(&e));
     TAIL_TRY(line_len.need(r1 * 8));
@@ -2387,7 +2489,7 @@ struct Tail::Impl {
     size_t tmp = 0, tmp_u = 0;
     TAIL_TRY(rocprim::exclusive_scan(nullptr, tmp, line_len.as<unsigned long long>(), line_off.as<unsigned long long>(), 0ull, r1,
                                      rocprim::plus<unsigned long long>(), stream));
-    if (names.unmapped) {
+    if (names.unmapped || report) {
       TAIL_TRY(u_cnt.need(n1 * 4));
       TAIL_TRY(u_before.need(n1 * 4));
       TAIL_TRY(usrc.need(std::max<size_t>(nr, 1) * 4));
@@ -2407,7 +2509,31 @@ struct Tail::Impl {
       p->tlen = tlen.as<int32_t>();
     }
     unm_timed = false, n_unm = 0;
-    if (names.unmapped) {
+    rep_timed = false, n_filtered = 0, n_base_last = n_base;
+    if (report) {
+      for (hipEvent_t &e : ev_rep)
+        if (!e) TAIL_TRY(hipEventCreate(&e));
+      ReportParams f{};
+      f.n_reads = last_n, f.n_base = n_base, f.begin = pair_order ? pair_begin.as<uint32_t>() : rec_begin.as<uint32_t>();
+      f.nm = nm.as<uint8_t>(), f.perm = pair_order ? perm.as<uint32_t>() : nullptr;
+      f.strata = names.strata >= 0 ? (uint32_t)names.strata : kReportOff, f.max_hits = names.max_hits >= 1 ? (uint32_t)names.max_hits : kReportOff;
+      f.unmapped = names.unmapped ? 1u : 0u;
+      f.cnt = u_cnt.as<uint32_t>(), f.before = u_before.as<uint32_t>(), f.usrc = usrc.as<uint32_t>(), f.n_lines = u_ctl.as<uint32_t>();
+      const dim3 grid((last_n + 256u) / 256u);
+      TAIL_TRY(hipEventRecord(ev_rep[0], stream));
+      TAIL_TRY(hipMemsetAsync(u_ctl.p, 0, 8, stream));
+      hipLaunchKernelGGL(report_kernel<false>, grid, dim3(256), 0, stream, f);
+      TAIL_TRY(hipGetLastError());
+      size_t tmp_bytes = scan_tmp.cap;
+      TAIL_TRY(rocprim::exclusive_scan(scan_tmp.p, tmp_bytes, u_cnt.as<uint32_t>(), u_before.as<uint32_t>(), 0u, n1, rocprim::plus<uint32_t>(), stream));
+      hipLaunchKernelGGL(report_kernel<true>, grid, dim3(256), 0, stream, f);
+      TAIL_TRY(hipGetLastError());
+      TAIL_TRY(hipEventRecord(ev_rep[1], stream));
+      TAIL_TRY(hipMemcpyAsync(h_ctl.as<uint32_t>() + 8, u_ctl.p, 8, hipMemcpyDeviceToHost, stream));
+      rep_timed = true;
+      p->usrc = usrc.as<uint32_t>(), p->u_base = names.unmapped ? n_base : kNoMate, p->n_reads = last_n, p->u_lines = u_ctl.as<uint32_t>();
+      p->pair_begin = names.unmapped ? pair_begin.as<uint32_t>() : nullptr;
+    } else if (names.unmapped) {
       for (hipEvent_t &e : ev_unm)
         if (!e) TAIL_TRY(hipEventCreate(&e));
       UlineParams u{};
@@ -2460,7 +2586,7 @@ struct Tail::Impl {
     if (bad_name) TAIL_TRY(hipMemsetAsync(bad_name, 0, 4, stream));
     TAIL_TRY(hipEventRecord(ev[0], stream));
     const dim3 len_grid(std::max<uint32_t>(1u, std::min<uint32_t>((nr + 256u) / 256u, (uint32_t)n_cu * 16u)));
-    const bool um = names.unmapped;
+    const bool um = names.unmapped || report;
     if (bad_name)
       hipLaunchKernelGGL(um ? (pair_order ? bam_len_kernel<true, true> : bam_len_kernel<false, true>)
                             : (pair_order ? bam_len_kernel<true> : bam_len_kernel<false>), len_grid, dim3(256), 0, stream, *p, last_n, bad_name);
@@ -2475,7 +2601,12 @@ struct Tail::Impl {
   }
   // after lines() and a wait for its stream: the number of lines (into p->n_records, which bounded it), n_unm
   uint32_t counted(const SamInput &names, SamParams *p) {
-    if (names.unmapped) {
+    if (rep_timed) {  // (the filter: what it kept, the unmapped reads' lines among them)
+      const uint32_t n_lines = std::min(h_ctl.as<uint32_t>()[8], p->n_records);
+      n_unm = names.unmapped ? std::min(h_ctl.as<uint32_t>()[9], n_lines) : 0u;
+      n_filtered = n_base_last + n_unm - n_lines;
+      p->n_records = n_lines;
+    } else if (names.unmapped) {
       const uint32_t n_lines = std::min(h_ctl.as<uint32_t>()[8], p->n_records);
       n_unm = n_lines - p->u_base;
       p->n_records = n_lines;
@@ -2583,6 +2714,7 @@ int Tail::warm(hipStream_t stream, std::string *err) {
                            (const void *)sam_write_kernel<false>, (const void *)sam_len_kernel<true>,
                            (const void *)sam_write_kernel<true>, (const void *)pair_kernel<false>, (const void *)pair_kernel<true>,
                            (const void *)mapq_kernel, (const void *)unmapped_mark_kernel, (const void *)unmapped_src_kernel,
+                           (const void *)report_kernel<false>, (const void *)report_kernel<true>,
                            (const void *)sam_len_kernel<false, true>, (const void *)sam_write_kernel<false, true>,
                            (const void *)sam_len_kernel<true, true>, (const void *)sam_write_kernel<true, true>,
                            (const void *)rescue_jobs_kernel,
@@ -2833,8 +2965,8 @@ int Tail::sam(const TailInput &in, const SamInput &names, hipStream_t stream, in
   if (nr) {
     p.text = m.text.as<uint8_t>();
     const uint32_t blocks = (nr + 255u) / 256u;  // a wave per 64 records
-    hipLaunchKernelGGL(names.unmapped ? (paired ? sam_write_kernel<true, true> : sam_write_kernel<false, true>)
-                                      : (paired ? sam_write_kernel<true> : sam_write_kernel<false>), dim3(blocks), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL(names.unmapped || m.rep_timed ? (paired ? sam_write_kernel<true, true> : sam_write_kernel<false, true>)
+                                                     : (paired ? sam_write_kernel<true> : sam_write_kernel<false>), dim3(blocks), dim3(256), 0, stream, p);
     TAIL_TRY(hipGetLastError());
   }
   TAIL_TRY(hipEventRecord(m.ev[1], stream));
@@ -2873,8 +3005,8 @@ int Tail::bam(const TailInput &in, const SamInput &names, int level, hipStream_t
   TAIL_TRY(m.text.need(std::max<size_t>((size_t)total, 16)));
   if (nr) {
     p.text = m.text.as<uint8_t>();
-    hipLaunchKernelGGL(names.unmapped ? (paired ? bam_write_kernel<true, true> : bam_write_kernel<false, true>)
-                                      : (paired ? bam_write_kernel<true> : bam_write_kernel<false>), dim3((nr + 3u) / 4u), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL(names.unmapped || m.rep_timed ? (paired ? bam_write_kernel<true, true> : bam_write_kernel<false, true>)
+                                                     : (paired ? bam_write_kernel<true> : bam_write_kernel<false>), dim3((nr + 3u) / 4u), dim3(256), 0, stream, p);
     TAIL_TRY(hipGetLastError());
   }
   TAIL_TRY(hipEventRecord(m.ev[1], stream));
@@ -3065,6 +3197,14 @@ uint64_t Tail::n_unmapped() const { return impl_ ? impl_->n_unm : 0; }
 float Tail::unmapped_ms() const {
   float t = 0.f;
   if (!impl_ || !impl_->unm_timed || hipEventElapsedTime(&t, impl_->ev_unm[0], impl_->ev_unm[1]) != hipSuccess) return 0.f;
+  return t;
+}
+
+uint64_t Tail::n_filtered() const { return impl_ ? impl_->n_filtered : 0; }
+
+float Tail::report_ms() const {
+  float t = 0.f;
+  if (!impl_ || !impl_->rep_timed || hipEventElapsedTime(&t, impl_->ev_rep[0], impl_->ev_rep[1]) != hipSuccess) return 0.f;
   return t;
 }
 

@@ -62,6 +62,8 @@ struct SamInput {  // device pointers
   bool qual_hole;                // quals == nullptr and the QUAL field of a primary record is LEFT UNWRITTEN (the caller fills it: SamOutput::qual_at)
   bool mapq = false;             // MAPQ from the hit strata (mapq_kernel; in pair mode pair() must have been asked for it too); else 255
   bool unmapped = false;         // a line for every read without a record (fem_dev_set_unmapped; the kernels' kUnm instances)
+  int32_t strata = -1;           // the line filter (fem_dev_set_report; report_kernel): a slot's lines within this many edits of its best, -1: off
+  int32_t max_hits = -1;         // ... and at most this many lines per slot (>= 1), -1: off
 };
 struct SamOutput {  // pinned host memory owned by the Tail object, valid until its next sam()
   const char *text;
@@ -162,6 +164,8 @@ class Tail {
   float mapq_ms() const;  // device time of the last sam() / bam()'s MAPQ kernel (0 without SamInput::mapq)
   uint64_t n_unmapped() const;  // lines for unmapped reads in the last sam() / bam() (0 without SamInput::unmapped)
   float unmapped_ms() const;    // ... and the device time of its line index kernels
+  uint64_t n_filtered() const;  // lines the filter left out of the last sam() / bam() (0 without SamInput::strata / max_hits)
+  float report_ms() const;      // ... and the device time of its line index kernels (which are the unmapped reads' too then)
   // The arrays of the last pair() to the host (waits for `stream`).
   int pair_fetch(hipStream_t stream, PairOutput *out, std::string *err);
   int wait_text();

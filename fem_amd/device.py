@@ -22,6 +22,7 @@ ABI_SYMBOLS = [
     "fem_dev_set_pairs", "fem_dev_fetch_pairs", "fem_dev_pair_count",
     "fem_dev_set_rescue", "fem_dev_rescue_count", "fem_dev_set_mapq",
     "fem_dev_set_unmapped", "fem_dev_unmapped_count",
+    "fem_dev_set_report", "fem_dev_filtered_count",
     "fem_dev_fetch_bam", "fem_dev_fetch_bam_nowait", "fem_dev_bam_wait", "fem_dev_bgzf_compress",
 ]
 
@@ -73,6 +74,10 @@ class _PairParams(C.Structure):
 
 class _RescueParams(C.Structure):
     _fields_ = [("max_edits", C.c_int32)]
+
+
+class _ReportParams(C.Structure):
+    _fields_ = [("strata", C.c_int32), ("max_hits", C.c_int32)]
 
 
 class _BatchPairs(C.Structure):
@@ -157,6 +162,9 @@ def load_hip():
     if hasattr(L, "fem_dev_set_unmapped"):
         L.fem_dev_set_unmapped.argtypes = [vp, C.c_int, C.c_int]
         L.fem_dev_unmapped_count.argtypes = [vp, C.c_int, C.POINTER(u64)]
+    if hasattr(L, "fem_dev_set_report"):
+        L.fem_dev_set_report.argtypes = [vp, C.c_int, C.POINTER(_ReportParams)]
+        L.fem_dev_filtered_count.argtypes = [vp, C.c_int, C.POINTER(u64)]
     if hasattr(L, "fem_dev_fetch_bam"):
         L.fem_dev_fetch_bam.argtypes = [vp, C.c_int, C.c_int, C.POINTER(_BatchBam)]
         L.fem_dev_fetch_bam_nowait.argtypes = [vp, C.c_int, C.c_int, C.POINTER(_BatchBam)]
@@ -587,6 +595,24 @@ class Device:
         """fem_dev_unmapped_count: lines for unmapped reads in the slot's last SAM text or BAM."""
         n = C.c_uint64()
         self._check(self._L.fem_dev_unmapped_count(self._h, slot, C.byref(n)))
+        return int(n.value)
+
+    def set_report(self, strata=None, max_hits=None, slot=0):
+        """fem_dev_set_report: the line filter of the slot's SAM text and BAM records: a read's (a mate's) lines within `strata`
+        (0..15) edits of its best one, at most `max_hits` (>= 1) of them; None: that part off, both None: every line again."""
+        if strata is None and max_hits is None:
+            self._check(self._L.fem_dev_set_report(self._h, slot, None))
+            return
+        for v in (strata, max_hits):
+            if v is not None and not -2 ** 31 <= int(v) < 2 ** 31:
+                raise FemError("fem_dev_set_report: parameter out of range")
+        rp = _ReportParams(-1 if strata is None else int(strata), -1 if max_hits is None else int(max_hits))
+        self._check(self._L.fem_dev_set_report(self._h, slot, C.byref(rp)))
+
+    def filtered_count(self, slot=0):
+        """fem_dev_filtered_count: lines the filter left out of the slot's last SAM text or BAM."""
+        n = C.c_uint64()
+        self._check(self._L.fem_dev_filtered_count(self._h, slot, C.byref(n)))
         return int(n.value)
 
     def rescue_count(self, slot=0):

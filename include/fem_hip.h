@@ -403,6 +403,35 @@ int fem_dev_set_mapq(fem_dev *h, int slot, int on);
 int fem_dev_set_unmapped(fem_dev *h, int slot, int on);
 int fem_dev_unmapped_count(fem_dev *h, int slot, uint64_t *n);
 
+/* ---- the line filter: best strata and a hit limit per read (new; opt-in: the reference writes every mapping, and so does every
+ *      output without it) ----
+ * fem_dev_set_report: the slot's fem_dev_fetch_sam[_nowait] text and fem_dev_fetch_bam[_nowait] records leave out the lines the
+ *   rule below drops.  strata S: 0 .. 15, or -1 for off; max_hits N: 1 .. 2^31 - 1, or -1 for off; rp == NULL: both off.  Anything
+ *   else is FEM_ERR_INVALID.  With both off nothing changes.  fem_batch_records, fem_batch_pairs, the stats and
+ *   fem_dev_pair_count / fem_dev_rescue_count / fem_dev_unmapped_count are unchanged (as MAPQ and the unmapped reads' lines, this
+ *   is output text only).  n_records of fem_batch_sam / fem_batch_bam counts the mapping records whose lines are there: lines =
+ *   n_records (+ the rescued mates in pair mode) + fem_dev_unmapped_count, as without the filter.  qual_at of
+ *   fem_dev_sam_quals still points at each read's primary QUAL field (a primary line always stays).
+ * Rule.  The filter acts on LINES, after everything else has been decided: the single-end order, rescue, pairing, MAPQ, the line
+ *   of an unmapped read.  It only removes lines: a line that stays is byte for byte what it is without the filter (FLAG, MAPQ,
+ *   RNEXT / PNEXT / TLEN, NM, MD), the primary line stays the primary line, and the proper-pair, rescued and unmapped counts
+ *   are what they are without it.  The filtered output is the unfiltered output minus some lines, in the same order.
+ *   A slot is a read single-end, or one mate of a pair.  Its lines in output order are l_0 .. l_{c-1}; l_0 is the primary line
+ *   (in a proper pair the chosen record, which need not have the mate's least NM); d = the least NM over ALL of the slot's lines
+ *   (records with 0x8000 count, as for MAPQ).  l_0 is always kept.  A later line l_t (t >= 1) is kept iff
+ *     (S off or nm(l_t) <= d + S)  and  (N off or fewer than N lines of the slot have been kept before it, l_0 included).
+ *   So N = 1 leaves one line per mapped read, and a slot of one line (a rescued mate's record; with fem_dev_set_unmapped an
+ *   unmapped read's line) keeps it.  The placed line of an unmapped mate and its mate's RNEXT / PNEXT name the mapped mate's
+ *   first line, which is l_0 and there.  NM is NOT assumed to be non-decreasing along a slot's lines (in pair mode it is not).
+ * fem_dev_filtered_count: the lines left out of the slot's last text or BAM (valid once the fetch has returned); 0 with the
+ *   filter off. */
+typedef struct {
+  int32_t strata;   /* 0 .. 15, -1: off */
+  int32_t max_hits; /* >= 1, -1: off */
+} fem_report_params;
+int fem_dev_set_report(fem_dev *h, int slot, const fem_report_params *rp);
+int fem_dev_filtered_count(fem_dev *h, int slot, uint64_t *n);
+
 /* Name of the seed + filter kernel fem_dev_map_staged would launch first for these parameters on the resident
  * index ("seed_join_kernel" — behind its "seed_select_kernel"; "seed_join_banked_kernel" where the reference's sequences
  * need more than one 32-bit coordinate space —, "seed_fast_kernel<hash>", "seed_fast_kernel<lean>" or
@@ -433,7 +462,9 @@ int fem_dev_index_info(const fem_dev *h, char *buf, uint64_t cap);
  * 13 = the MAPQ kernel of a fem_dev_fetch_sam / fem_dev_fetch_bam with fem_dev_set_mapq on (one entry per call; the
  * pairing kernel's MAPQ part stays in 9);
  * 14 = the line index kernels of a fem_dev_fetch_sam / fem_dev_fetch_bam with fem_dev_set_unmapped on (one entry per call;
- * the unmapped reads' lines themselves are written by the text and BAM record kernels: 7 and 11). */
+ * the unmapped reads' lines themselves are written by the text and BAM record kernels: 7 and 11; none with a line filter set);
+ * 15 = the line filter's line index kernels of a fem_dev_fetch_sam / fem_dev_fetch_bam with fem_dev_set_report on (one entry
+ * per call; they make the unmapped reads' part of the index too, so 14 has no entry then). */
 int fem_dev_set_timing(fem_dev *h, int on);
 int fem_dev_reset_timing(fem_dev *h);
 int fem_dev_kernel_time(fem_dev *h, int kernel, double *ms_total, uint64_t *launches);
