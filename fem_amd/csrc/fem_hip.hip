@@ -384,7 +384,7 @@ int pinned_realloc(fem_dev *h, T **p, size_t *cap, size_t want) {
 }
 
 bool params_ok(const fem_params *p) {
-  return p && p->k >= 1 && p->k <= 16 && p->step >= 1 && p->step <= 16 && p->e >= 0 && p->e <= 7 && p->a >= 0 &&
+  return p && p->k >= 1 && p->k <= 15 && p->step >= 1 && p->step <= 16 && p->e >= 0 && p->e <= 7 && p->a >= 0 &&
          p->a <= 2;
 }
 
@@ -1545,7 +1545,7 @@ int fem_dev_limits(const fem_dev *h, uint32_t *max_read_len, int32_t *n_slots) {
 int fem_dev_upload_index(fem_dev *h, int32_t k, int32_t step, const uint32_t *lookup, uint64_t n_lookup,
                          const uint64_t *occ, uint64_t n_occ) {
   if (!h || !lookup || (!occ && n_occ)) return FEM_ERR_INVALID;
-  if (k < 1 || k > 16 || step < 1) return fail(h, FEM_ERR_INVALID, "k must be 1..16 and step >= 1");
+  if (k < 1 || k > 15 || step < 1) return fail(h, FEM_ERR_INVALID, "k must be 1..15 and step >= 1");
   if (n_lookup != (1ull << (2 * k)) + 1) return fail(h, FEM_ERR_INVALID, "lookup table must have 4^k + 1 entries");
   if (n_occ > 0xFFFFFFFFull) return fail(h, FEM_ERR_INVALID, "occurrence table larger than its uint32 prefix sums");
   HIP_TRY(h, hipSetDevice(h->device));
@@ -1646,7 +1646,7 @@ int fem_dev_build_index(fem_dev *h, int32_t k, int32_t step, uint32_t *lookup_ou
                         uint64_t *n_occ_out) {
   if (!h) return FEM_ERR_INVALID;
   if (!h->d_ref_raw) return fail(h, FEM_ERR_STATE, "upload the reference before building the index");
-  if (k < 1 || k > 16 || step < 1) return fail(h, FEM_ERR_INVALID, "k must be 1..16 and step >= 1");
+  if (k < 1 || k > 15 || step < 1) return fail(h, FEM_ERR_INVALID, "k must be 1..15 and step >= 1");
   HIP_TRY(h, hipSetDevice(h->device));
   if (h->d_lookup) (void)hipFree(h->d_lookup);
   if (h->d_occ) (void)hipFree(h->d_occ);
@@ -1900,7 +1900,7 @@ int fem_dev_map_staged(fem_dev *h, int slot, const fem_params *p) {
   int rc = check_slot(h, slot);
   if (rc) return rc;
   FEM_LOCK(h);
-  if (!params_ok(p)) return fail(h, FEM_ERR_INVALID, "parameters out of range (k 1..16, step 1..16, e 0..7, a 0..2)");
+  if (!params_ok(p)) return fail(h, FEM_ERR_INVALID, "parameters out of range (k 1..15, step 1..16, e 0..7, a 0..2)");
   if (!h->d_lookup || !h->d_ref_raw || !h->d_planes) return fail(h, FEM_ERR_STATE, "index and reference must be uploaded first");
   if (p->k != h->k) return fail(h, FEM_ERR_INVALID, "k differs from the uploaded index");
   Slot &s = h->slot[slot];
@@ -2162,7 +2162,7 @@ int fem_dev_reserve_batch(fem_dev *h, int slot, uint64_t n_reads, uint64_t n_rec
   int rc = check_slot(h, slot);
   if (rc) return rc;
   FEM_LOCK(h);
-  if (!params_ok(p)) return fail(h, FEM_ERR_INVALID, "parameters out of range (k 1..16, step 1..16, e 0..7, a 0..2)");
+  if (!params_ok(p)) return fail(h, FEM_ERR_INVALID, "parameters out of range (k 1..15, step 1..16, e 0..7, a 0..2)");
   if (!h->d_lookup) return fail(h, FEM_ERR_STATE, "the index must be uploaded first (what a batch needs depends on it)");
   if (n_reads == 0 || n_reads > 0x7FFFFFF0ull || n_records > 0xFFFFFFF0ull || max_len == 0 || max_len > kMaxReadLen)
     return fail(h, FEM_ERR_INVALID, "batch shape out of range");

@@ -1318,7 +1318,7 @@ int fem_index_load(const char *path, int32_t *k, int32_t *step, uint32_t **looku
   int rc = 0;
   size_t n = 0, n_lookup = 0;
   if (fread(k, sizeof(int32_t), 1, f) != 1 || fread(step, sizeof(int32_t), 1, f) != 1) rc = -2;
-  if (rc == 0 && (*k < 1 || *k > 16)) rc = -3;
+  if (rc == 0 && (*k < 1 || *k > 15)) rc = -3;
   if (rc == 0) {
     n_lookup = ((size_t)1 << (2 * *k)) + 1;
     *lookup = (uint32_t *)malloc(n_lookup * sizeof(uint32_t));

@@ -97,7 +97,7 @@ int fem_seqfile_plan_ahead_ok(fem_seqfile *f);
 /* ---------------- index files (src/index.c:100-168) ---------------- */
 /* int32 k | int32 step | uint32 lookup[4^k+1] | size_t n | uint64 occ[n] */
 int fem_index_save(const char *path, int32_t k, int32_t step, const uint32_t *lookup, uint64_t n_occ, const uint64_t *occ);
-/* Allocates *lookup and *occ with malloc. */
+/* Allocates *lookup and *occ with malloc.  -3: the header's k is not 1..15. */
 int fem_index_load(const char *path, int32_t *k, int32_t *step, uint32_t **lookup, uint64_t *n_occ, uint64_t **occ);
 
 /* ---------------- mapping tail ---------------- */

@@ -140,8 +140,8 @@ int index_main(int argc, char **argv) {
   int k = atoi(argv[1]), step = atoi(argv[2]);
   const char *ref_path = argv[3], *out_path = argv[4];
   fprintf(stderr, "k: %d, step size: %d, reference: %s, output: %s\n", k, step, ref_path, out_path);
-  if (k < 1 || k > 16 || step < 1) {
-    fprintf(stderr, "window_size must be 1..16 and step_size >= 1.\n");
+  if (k < 1 || k > 15 || step < 1) {
+    fprintf(stderr, "window_size must be 1..15 and step_size >= 1.\n");
     usage_index();
     exit(EXIT_FAILURE);
   }

@@ -398,10 +398,15 @@ class Device:
         self._check(self._L.fem_dev_build_index(self._h, k, step, None, None, 0, C.byref(n)))
         if not fetch:
             return int(n.value), None, None
+        lookup, occ = self.fetch_index(k, int(n.value))
+        return int(n.value), lookup, occ
+
+    def fetch_index(self, k, n_occ):
+        """fem_dev_fetch_index: (lookup, occ) of the resident index, built or uploaded, whose k and size the caller knows."""
         lookup = np.zeros((1 << (2 * k)) + 1, dtype=np.uint32)
-        occ = np.zeros(max(int(n.value), 1), dtype=np.uint64)
+        occ = np.zeros(max(int(n_occ), 1), dtype=np.uint64)
         self._check(self._L.fem_dev_fetch_index(self._h, lookup.ctypes.data, occ.ctypes.data, len(occ)))
-        return int(n.value), lookup, occ[:n.value]
+        return lookup, occ[:int(n_occ)]
 
     @staticmethod
     def _batch(bases, offsets):

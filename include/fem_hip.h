@@ -41,7 +41,11 @@ enum fem_status {
 };
 
 /* FEMArgs (src/utils.h:63-70) minus threads/seeding_method.  `FEM map` always
- * runs k=12, step=3 (src/FEM_map.c:67-68); 0<=e<=7, 0<=a<=2 (src/FEM_map.c:30,38). */
+ * runs k=12, step=3 (src/FEM_map.c:67-68); 0<=e<=7, 0<=a<=2 (src/FEM_map.c:30,38).
+ * 1<=k<=15, 1<=step<=16.  k = 16 is refused everywhere: the reference's hash mask is
+ * ((uint32_t)1 << 32) - 1 there (src/utils.h:84,104), which is undefined.  k must be
+ * the resident index's; step need not be its step (the seeds are then looked up in
+ * an occurrence table sampled at another step). */
 typedef struct {
   int32_t k;
   int32_t step;
@@ -150,7 +154,7 @@ int fem_dev_limits(const fem_dev *h, uint32_t *max_read_len, int32_t *n_slots);
 /* ---- resident data (replaces load_index / the reference SequenceBatch;
  *      src/index.c:100-131, src/FEM_map.c:135-143) ---- */
 /* lookup: 4^k+1 prefix sums; occ: seq<<32|pos, ascending in each bucket — byte
- * for byte the arrays of the index file (src/index.c:133-168). */
+ * for byte the arrays of the index file (src/index.c:133-168).  1<=k<=15, step>=1. */
 int fem_dev_upload_index(fem_dev *h, int32_t k, int32_t step, const uint32_t *lookup, uint64_t n_lookup,
                          const uint64_t *occ, uint64_t n_occ);
 /* seq[i] points at seq_len[i] raw FASTA characters (any case; non-ACGT = N). */
@@ -158,7 +162,8 @@ int fem_dev_upload_reference(fem_dev *h, uint32_t n_seq, const char *const *seq,
 /* Build the index on the device from the uploaded reference (construct_index,
  * src/index.c:57-98) and keep it resident.  If lookup_out/occ_out are non-NULL
  * the arrays are also copied back (occ_cap entries available); *n_occ_out is
- * always set.  The result is byte-identical to the reference's index arrays. */
+ * always set.  The result is byte-identical to the reference's index arrays.
+ * 1<=k<=15, step>=1; a reference without a sequence of k bases gives an empty index. */
 int fem_dev_build_index(fem_dev *h, int32_t k, int32_t step, uint32_t *lookup_out, uint64_t *occ_out,
                         uint64_t occ_cap, uint64_t *n_occ_out);
 /* Copies the resident index arrays (uploaded or built) to the host: what save_index

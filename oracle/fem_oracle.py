@@ -134,8 +134,15 @@ class ReadBatch:
         return self.bases[int(self.off[i]):int(self.off[i + 1])].tobytes()
 
 
+def _check_k(k):
+    # k = 16: the reference's hash mask, ((uint32_t)1 << 32) - 1 (src/utils.h), is undefined and comes out 0 on x86
+    if not 1 <= k <= 15:
+        raise ValueError("k must be 1..15 (got %d)" % k)
+
+
 class OracleIndex:
     def __init__(self, ref, k=12, step=3, threads=1):
+        _check_k(k)
         L = lib()
         self.k, self.step = k, step
         n = L.fo_index_count(C.byref(ref.c), k, step)
@@ -211,6 +218,7 @@ class MapResult:
 
 def map_reads(ref, index, reads, e=3, a=1, k=12, step=3, threads=1, stages=STAGE_SEED | STAGE_VERIFY | STAGE_ALIGN,
               keep_handle=False):
+    _check_k(k)
     p = Params(k, step, e, a)
     h = lib().fo_map(C.byref(p), C.byref(ref.c), C.byref(index.c), C.byref(reads.c), threads, stages)
     if keep_handle:
@@ -255,6 +263,7 @@ def revcomp(seq):
 
 
 def seed_candidates(ref, index, seq, e=3, a=1, k=12, step=3):
+    _check_k(k)
     p = Params(k, step, e, a)
     cap = 1 << 12
     while True:

@@ -28,6 +28,11 @@ def test_usage_and_argument_errors():
     assert r.returncode == 1 and b"unrecognized command" in r.stderr               # src/FEM.c:37-39
     r = run("index", "12", "3")
     assert r.returncode == 1 and b"Usage: FEM index <window_size> <step_size> <reference> <output>" in r.stderr
+    # k = 16 is refused from the arguments alone: before the reference is read and before a device is opened
+    for k in ("16", "0"):
+        r = run("index", k, "3", "/nonexistent/ref.fa", "/nonexistent/out.idx")
+        assert r.returncode == 1 and b"window_size must be 1..15 and step_size >= 1." in r.stderr
+        assert b"Usage: FEM index" in r.stderr and b"fem_dev_open" not in r.stderr
     r = run("map", "-h")
     assert r.returncode == 0 and b"--read1" in r.stderr                            # src/FEM_map.c:123-125
     r = run("map", "-e", "9", "--ref", "a", "--index", "b", "--read1", "c", "-o", "d")

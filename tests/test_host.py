@@ -228,6 +228,41 @@ def test_index_file_is_byte_compatible(tmp_path):
     assert np.array_equal(lookup, idx.lookup) and np.array_equal(occ, idx.occ[:idx.n_occ])
 
 
+@pytest.mark.parametrize("k,step", [(8, 4), (11, 4), (13, 5)])
+def test_index_file_round_trip_at_other_seed_lengths(tmp_path, k, step):
+    # the header's k sizes the lookup table: 4^k + 1 entries on both sides of the file
+    rng = np.random.default_rng(100 * k + step)
+    ref = fo.Reference([util.rand_seq(rng, 30_000), b"ACGTN" * 7 + util.rand_seq(rng, 999), util.rand_seq(rng, k - 1)])
+    idx = fo.OracleIndex(ref, k, step)
+    assert idx.n_occ > 6000 // step and len(idx.lookup) == 4 ** k + 1
+    a, b = str(tmp_path / "a.idx"), str(tmp_path / "b.idx")
+    idx.save(a)
+    host.index_save(b, k, step, idx.lookup, idx.occ[:idx.n_occ])
+    assert open(a, "rb").read() == open(b, "rb").read()
+    assert os.path.getsize(b) == 8 + 4 * (4 ** k + 1) + 8 + 8 * idx.n_occ
+    for path in (a, b):
+        got_k, got_step, lookup, occ = host.index_load(path)
+        assert (got_k, got_step) == (k, step)
+        assert np.array_equal(lookup, idx.lookup) and np.array_equal(occ, idx.occ[:idx.n_occ])
+
+
+def test_index_load_refuses_a_seed_length_of_16(tmp_path):
+    # k = 16 has no defined meaning (the reference's hash mask is 1 << 32): refused from the header, before the table is read
+    path = tmp_path / "k16.idx"
+    path.write_bytes(np.array([16, 3], np.int32).tobytes() + b"\0" * 64)
+    with pytest.raises(OSError, match=r"fem_index_load failed \(-3\)"):
+        host.index_load(str(path))
+    path.write_bytes(np.array([0, 3], np.int32).tobytes() + b"\0" * 64)
+    with pytest.raises(OSError, match=r"fem_index_load failed \(-3\)"):
+        host.index_load(str(path))
+    rng = np.random.default_rng(1)
+    ref = fo.Reference([util.rand_seq(rng, 500)])
+    for call in (lambda: fo.OracleIndex(ref, 16, 3), lambda: fo.OracleIndex(ref, 0, 3),
+                 lambda: fo.map_reads(ref, fo.OracleIndex(ref, 4, 2), fo.ReadBatch([ref.seq(0)[:100]]), k=16, step=3)):
+        with pytest.raises(ValueError, match="k must be 1..15"):
+            call()
+
+
 def test_synthetic_generator_is_reproducible_and_shardable():
     text, off, lens = host.synth_reference(5, [200_000, 50_000, 70], threads=4)
     text2, _, _ = host.synth_reference(5, [200_000, 50_000, 70], threads=1)

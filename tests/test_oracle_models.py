@@ -294,6 +294,37 @@ def test_seeding_equals_closed_form_on_long_reads(e, a, L):
     assert n_nonempty >= 8, n_nonempty
 
 
+# seed lengths and steps other than 12 / 3: step = 1 (lg = k), step > k (lg = 1), k no multiple of step, step = k, step = 16,
+# the shortest and the longest seeds whose lookup table is built in a second or two
+SEED_SHAPES = [(12, 1), (12, 4), (12, 6), (12, 12), (11, 4), (13, 5), (7, 16), (10, 1), (9, 2), (14, 3), (5, 7), (2, 1),
+               (8, 13)]
+
+
+@pytest.mark.parametrize("e,a,L", [(1, 1, 100), (3, 1, 150), (7, 1, 300), (0, 1, 64), (7, 2, 1024)])
+@pytest.mark.parametrize("k,step", SEED_SHAPES)
+def test_seeding_equals_closed_form_at_other_seed_shapes(k, step, e, a, L):
+    rng = np.random.default_rng(5000 + 1000 * k + 50 * step + 10 * e + a + L)
+    seqs = util.repeat_rich_reference(rng, n_seq=2, unit_len=L + 60, n_units=3, copies=10, spacer=120)
+    ref = fo.Reference(seqs)
+    idx = fo.OracleIndex(ref, k, step)
+    reads = util.make_reads(rng, seqs, 12, L, e, n_rate=0.2 / L)  # (an N in one read of five, whatever the length)
+    n_nonempty = 0
+    for r in reads:
+        for strand in (r, fo.revcomp(r)):
+            got, pre = fo.seed_candidates(ref, idx, strand, e=e, a=a, k=k, step=step)
+            want, wpre = closed_form_candidates(ref, idx, strand, e, a, k, step)
+            assert pre == wpre
+            assert list(map(int, got)) == want
+            n_nonempty += bool(want)
+    print("non-empty strands: %d of %d" % (n_nonempty, 2 * len(reads)))
+    # a read whose edits are all substitutions keeps its seeds in phase with the index over its whole length: of the
+    # e + 1 + a seeds selected in the phase group of its own place at least 1 + a are whole, and that place is a candidate.
+    # An insertion or a deletion moves the rest of the read to another phase group, so nothing is promised then.  With
+    # 0..e edits, 60 % of them substitutions (util.mutate), that is a third of the reads at e = 7 and more below: 4 of 12
+    # expected at the least, half of that as the floor.
+    assert n_nonempty >= 2, n_nonempty
+
+
 # ---------------------------------------------------------------- traceback re-scoring
 def rescore(pattern, text, start, cigar, md):
     """Walk CIGAR over both strings; return (#edits, read bases consumed, MD rebuilt from first principles)."""
