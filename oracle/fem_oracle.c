@@ -1,6 +1,6 @@
 /*
  * fem_oracle.c — CPU restatement of FEM's per-read mapping hot path.
- * TEST INFRASTRUCTURE ONLY; PARITY UNPINNED (see fem_oracle.h).
+ * TEST INFRASTRUCTURE ONLY; pinned against the reference built from its own sources (see fem_oracle.h).
  *
  * Every function names the reference lines it restates.  Where the reference
  * has undefined behaviour the choice made here is marked "UB in reference".

@@ -6,16 +6,30 @@
  * load this library.  The product path (libfemhip.so + libfemhost.so) never
  * links, loads or calls it.
  *
- * PARITY UNPINNED: the reference (haowenz/FEM v0.2) holds no tests, golden
- * vectors or fixtures, and cannot be compiled in this image (every hot-path
- * source includes the un-vendored htslib via src/utils.h:18).  This file is
- * therefore a line-by-line restatement of the reference algorithm, each
- * function citing the reference file:line it follows, cross-checked only by
- * independent brute-force models in tests/ (full-matrix edit distance,
- * closed-form candidate sets, CIGAR re-scoring).  One function is pinned
- * against reference code: fo_sort_mapping_keys equals the reference's own
- * ksort.h instantiation, built from /root/reference behind ref_klib.c
- * (tests/test_ref_klib.py).
+ * PARITY: a line-by-line restatement of the reference algorithm (haowenz/FEM
+ * v0.2), each function citing the reference file:line it follows, and pinned
+ * against the reference BUILT FROM ITS OWN SOURCES: `make -C oracle ref`
+ * compiles them from where they lie against a stand-in for the htslib
+ * declarations and a text-SAM writer (ref_standin/, ref_standin.c; htslib does
+ * no mapping arithmetic) into _ref/FEM_ref and _ref/libfemref_fn.so (ref_fn.c).
+ * tests/test_ref_parity.py compares index files, candidates, (ed, end), CIGAR,
+ * MD, every SAM field and the counters with that build, and with what it gave
+ * as recorded under tests/golden/ref_*.npz.  fo_sort_mapping_keys and the
+ * record reader are pinned by ref_klib.c (tests/test_ref_klib.py).  Beside
+ * that stand the independent brute-force models in tests/ (full-matrix edit
+ * distance, closed-form candidate sets, CIGAR re-scoring).
+ *
+ * NOT pinned: htslib's own text rendering, and the regions where the reference
+ * has no defined answer:
+ *   - lower-case characters: it aborts at src/align.c:367; records carry FLAG
+ *     0x8000 here, and the tests pin that it aborts exactly where this says;
+ *   - reads one seed short of the seed selection's table: defined only for
+ *     g_min - R*lg + 2 >= 2, g_min = (L - k + 1 - (step - 1)) / step,
+ *     R = e + 1 + a, lg = ceil(k / step) (k = 12, step = 3, a = 1: L >= 37 at
+ *     e = 0, 73 at e = 3, 121 at e = 7).  One seed below, the reference reads
+ *     uninitialised Seeds (src/filter.c:5-7, 30-41); no candidates here;
+ *   - construct_index with step > k on several sequences can overrun its seed
+ *     buffer (src/index.c:59); the arrays here are what it would hold.
  */
 #ifndef FEM_ORACLE_H_
 #define FEM_ORACLE_H_

@@ -6,7 +6,7 @@
  *   ksort.h  the radix sort behind radix_sort_mapping, instantiated as src/align.c:53-54 does
  *            (KRADIX_SORT_INIT(mapping, Mapping, MappingSortKey, 8)) on records that carry their key ready-made
  *
- * Everything else of the reference includes htslib (src/utils.h:18), which this image does not have, and is NOT built.
+ * Everything else of the reference includes htslib (src/utils.h:18) and is built against a stand-in for it: ref_fn.c.
  * What this pins: the record rules of the read/reference parser (libfemhost's readers) and the order in which a read's
  * mappings are emitted, ties included (oracle, host tail, device ordering kernel).  Output: oracle/_ref/libfemref_klib.so.
  * Only tests/ and tests/golden/make_klib_golden.py load it.

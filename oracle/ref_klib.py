@@ -1,6 +1,6 @@
 """ctypes binding of oracle/_ref/libfemref_klib.so — the reference's own kseq.h / ksort.h behind oracle/ref_klib.c.
 TEST INFRASTRUCTURE ONLY: loaded by tests/ and tests/golden/make_klib_golden.py, never by the product.
-The library is built by `make -C oracle ref` where /root/reference exists and ships to the GPU box as built."""
+The library is built by `make -C oracle ref` where the reference's sources exist and ships to the GPU box as built."""
 import ctypes as C
 import os
 

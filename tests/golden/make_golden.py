@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Regenerates tests/golden/*.npz.
 
-The reference (haowenz/FEM) cannot be built in this image (htslib is an un-vendored submodule) and ships no golden
-vectors, so these fixtures are produced by the CPU ORACLE (oracle/fem_oracle.c), not by the reference itself: they
-freeze the oracle + the seeded generator so that later changes to either, or to the device path, are caught.
+These fixtures are produced by the CPU ORACLE (oracle/fem_oracle.c), not by the reference (haowenz/FEM): they freeze
+the oracle + the seeded generator so that later changes to either, or to the device path, are caught.  What the reference
+itself computes, recorded from a build of its own sources, is in tests/golden/ref_*.npz (tests/golden/make_ref_golden.py).
 Inputs are not stored: they are a pure function of (seed, sizes) through libfemhost's generator.
 
     python tests/golden/make_golden.py

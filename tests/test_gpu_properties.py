@@ -113,7 +113,7 @@ def test_device_index_equals_uploaded_index_results(dev, c2):
 
 # ---------------------------------------------------------------------------------------------------------
 # Statistical pins against the SURVEY's probe of the UNMODIFIED reference binary.
-# The reference ships no vectors and cannot be built here (PARITY UNPINNED); its probe's generator and
+# The reference ships no vectors (the bit-exact pins are tests/test_ref_parity.py); its probe's generator and
 # seeds are gone, so these are not bit-exact pins.  They compare the device path, on the same input DISTRIBUTION
 # (uniform start, 0..e edits, 60/20/20 % substitution/insertion/deletion at a uniform interior offset
 # of the read, truncated to L), with the counters the real binary printed.  Tolerances = 3 sigma of the probe's

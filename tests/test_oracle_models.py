@@ -1,6 +1,6 @@
-"""The oracle restates reference FEM; the reference has no tests or golden vectors and cannot be built here
-(PARITY UNPINNED, see oracle/fem_oracle.h).  These tests check the restatement against INDEPENDENT models written
-from the algorithm's definition rather than from the reference's code:
+"""The oracle restates reference FEM; tests/test_ref_parity.py pins it against the reference built from its own sources
+(see oracle/fem_oracle.h).  These tests check the restatement against INDEPENDENT models written from the algorithm's
+definition rather than from the reference's code:
 
   * banded Myers  (src/align.c:102-147)   vs  a cell-by-cell banded DP
   * 16-bit x8 form (src/align.c:149-277)  vs  the 32-bit scalar form  (SURVEY.md Appendix B probe)

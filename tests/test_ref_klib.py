@@ -1,6 +1,6 @@
 """libfemhost's sequence readers and the mapping sort against THE REFERENCE'S OWN klib code: oracle/_ref/libfemref_klib.so
 is the reference's src/kseq.h and src/ksort.h, compiled from where they lie in the reference's tree behind the harness
-oracle/ref_klib.c (`make -C oracle ref`; everything else of the reference needs htslib and cannot be built here).
+oracle/ref_klib.c (`make -C oracle ref`; the rest of the reference, built against a stand-in for htslib: tests/test_ref_parity.py).
 
   * records: kseq_read as src/sequence_batch.c:47-66 drives it (zero-length records skipped, any return below -1 fatal)
     vs fem_seqfile_read (sequential), fem_seqfile_read_bytes and fem_seqfile_plan/_fill (multi-threaded), plain and gzip
