@@ -1,6 +1,6 @@
 // fem_hip.hip — host side of libfemhip.so: the C ABI declared in include/fem_hip.h.
 // Owns device memory, streams, pinned result buffers and the launch logic of the
-// kernels in fem_kernels.hip.h.  No CPU fallback: every entry point needs a GPU.
+// kernels in fem_kernels.hip.h and fem_verify.hip.h.  No CPU fallback: every entry point needs a GPU.
 #include "../../include/fem_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -22,11 +22,13 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "fem_index_build.hip.h"
 #include "fem_pack.h"
 #include "fem_kernels.hip.h"
+#include "fem_verify.hip.h"
 #include "fem_seed_fast.hip.h"
 #include "fem_seed_join.hip.h"
 #include "fem_tail.hip.h"
@@ -531,25 +533,24 @@ femk::SeedLayout make_layout_join(const fem_params &p, bool banked, bool padded 
   return l;
 }
 
+typedef void (*SeedKernel)(femk::SeedParams);
+template <size_t... I>
+SeedKernel select_kernel_of(int R, bool banked, std::index_sequence<I...>) {
+  static const SeedKernel k[2][femk::kMaxR] = {{femk::seed_select_kernel<(int)I + 1, false>...}, {femk::seed_select_kernel<(int)I + 1, true>...}};
+  return k[banked][std::min(std::max(R, 1), femk::kMaxR) - 1];
+}
+template <size_t... I>
+SeedKernel fast_kernel_of(int R, bool hash, std::index_sequence<I...>) {
+  static const SeedKernel k[2][femk::kMaxR] = {{femk::seed_fast_kernel<(int)I + 1, false>...}, {femk::seed_fast_kernel<(int)I + 1, true>...}};
+  return k[hash][std::min(std::max(R, 1), femk::kMaxR) - 1];
+}
 // (`banked`: the reference's sequences lie in more than one coordinate space, fem_seed_dense.hip.h)
-template <int R>
-void launch_select_r(bool banked, dim3 grid, dim3 block, uint32_t lds, hipStream_t st, const femk::SeedParams &sp) {
-  if (banked)
-    hipLaunchKernelGGL((femk::seed_select_kernel<R, true>), grid, block, lds, st, sp);
-  else
-    hipLaunchKernelGGL((femk::seed_select_kernel<R>), grid, block, lds, st, sp);
-}
-template <int R>
-int select_blocks_per_cu_r(bool banked, int block, uint32_t lds) {
-  int nb = 0;
-  const hipError_t e = banked ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, femk::seed_select_kernel<R, true>, block, lds)
-                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, femk::seed_select_kernel<R>, block, lds);
-  return e == hipSuccess ? nb : 0;
-}
-typedef void (*JoinKernel)(femk::SeedParams);
+SeedKernel select_kernel(int R, bool banked) { return select_kernel_of(R, banked, std::make_index_sequence<femk::kMaxR>{}); }
+// (`hash`: the hash-join form for long occurrence lists; otherwise the lean one, lists in lanes only)
+SeedKernel fast_kernel(int R, bool hash) { return fast_kernel_of(R, hash, std::make_index_sequence<femk::kMaxR>{}); }
 // which = 0: the compact table, 1: references in banks (compact, cut at bank_lo), 2: the strided table with its pads
-JoinKernel join_kernel(int R, int which) {
-  static const JoinKernel k[3][femk::kMaxR] = {
+SeedKernel join_kernel(int R, int which) {
+  static const SeedKernel k[3][femk::kMaxR] = {
       {femk::seed_join_kernel_r1, femk::seed_join_kernel_r2, femk::seed_join_kernel_r3, femk::seed_join_kernel_r4, femk::seed_join_kernel_r5,
        femk::seed_join_kernel_r6, femk::seed_join_kernel_r7, femk::seed_join_kernel_r8, femk::seed_join_kernel_r9, femk::seed_join_kernel_r10},
       {femk::seed_join_banked_kernel_r1, femk::seed_join_banked_kernel_r2, femk::seed_join_banked_kernel_r3, femk::seed_join_banked_kernel_r4,
@@ -561,26 +562,10 @@ JoinKernel join_kernel(int R, int which) {
   return k[which][std::min(std::max(R, 1), femk::kMaxR) - 1];
 }
 
-#define FEM_DENSE_SWITCH(R, CALL)      \
-  switch (R) {                         \
-    case 1: CALL(1); break;            \
-    case 2: CALL(2); break;            \
-    case 3: CALL(3); break;            \
-    case 4: CALL(4); break;            \
-    case 5: CALL(5); break;            \
-    case 6: CALL(6); break;            \
-    case 7: CALL(7); break;            \
-    case 8: CALL(8); break;            \
-    case 9: CALL(9); break;            \
-    default: CALL(10); break;          \
-  }
-template <int R>
-uint32_t kernel_regs_r(bool join, int which) {
-  hipFuncAttributes a{};
-  const bool banked = which == 1;
-  const void *f = join ? (const void *)join_kernel(R, which)
-                       : banked ? (const void *)femk::seed_select_kernel<R, true> : (const void *)femk::seed_select_kernel<R>;
-  return hipFuncGetAttributes(&a, f) == hipSuccess && a.numRegs > 0 ? (uint32_t)a.numRegs : 128u;
+// blocks of `kernel` one CU holds at a time (registers and LDS both count); 0 = unknown
+int blocks_per_cu(const void *kernel, int block, uint32_t lds) {
+  int nb = 0;
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, block, lds) == hipSuccess ? nb : 0;
 }
 // vector registers per lane of seed_join_kernel<R> / seed_select_kernel<R>
 // (handles of several GPUs launch from their own threads: the cache is atomic; every thread would store the same value)
@@ -589,61 +574,20 @@ uint32_t kernel_regs(int R, bool join, int which = 0) {
   std::atomic<uint32_t> &slot = cache[which][join ? 1 : 0][std::min(std::max(R, 1), femk::kMaxR)];
   uint32_t c = slot.load(std::memory_order_relaxed);
   if (c) return c;
-#define FEM_CALL(r) c = kernel_regs_r<r>(join, which)
-  FEM_DENSE_SWITCH(R, FEM_CALL)
-#undef FEM_CALL
+  hipFuncAttributes a{};
+  const void *f = join ? (const void *)join_kernel(R, which) : (const void *)select_kernel(R, which == 1);
+  c = hipFuncGetAttributes(&a, f) == hipSuccess && a.numRegs > 0 ? (uint32_t)a.numRegs : 128u;
   slot.store(c, std::memory_order_relaxed);
   return c;
 }
-int select_blocks_per_cu(int R, bool banked, int block, uint32_t lds) {
-  int nb = 0;
-#define FEM_CALL(r) nb = select_blocks_per_cu_r<r>(banked, block, lds)
-  FEM_DENSE_SWITCH(R, FEM_CALL)
-#undef FEM_CALL
-  return nb;
-}
 void launch_select(int R, bool banked, dim3 grid, dim3 block, uint32_t lds, hipStream_t st, const femk::SeedParams &sp) {
-#define FEM_CALL(r) launch_select_r<r>(banked, grid, block, lds, st, sp)
-  FEM_DENSE_SWITCH(R, FEM_CALL)
-#undef FEM_CALL
-}
-int join_blocks_per_cu(int R, int which, int block, uint32_t lds) {
-  int nb = 0;
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, join_kernel(R, which), block, lds) == hipSuccess ? nb : 0;
+  hipLaunchKernelGGL(select_kernel(R, banked), grid, block, lds, st, sp);
 }
 void launch_join(int R, int which, dim3 grid, dim3 block, uint32_t lds, hipStream_t st, const femk::SeedParams &sp) {
   hipLaunchKernelGGL(join_kernel(R, which), grid, block, lds, st, sp);
 }
-
-template <int R>
-void launch_fast(bool hash, dim3 grid, dim3 block, uint32_t lds, hipStream_t st, const femk::SeedParams &sp) {
-  if (hash)
-    hipLaunchKernelGGL((femk::seed_fast_kernel<R, true>), grid, block, lds, st, sp);
-  else
-    hipLaunchKernelGGL((femk::seed_fast_kernel<R, false>), grid, block, lds, st, sp);
-}
-
-template <int R>
-int fast_blocks_per_cu_r(bool hash, int block, uint32_t lds) {
-  int nb = 0;
-  hipError_t err = hash ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, femk::seed_fast_kernel<R, true>, block, lds)
-                        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, femk::seed_fast_kernel<R, false>, block, lds);
-  return err == hipSuccess ? nb : 0;
-}
-// blocks of seed_fast_kernel<R, hash> one CU holds at a time (registers and LDS both count); 0 = unknown
-int fast_blocks_per_cu(int R, bool hash, int block, uint32_t lds) {
-  switch (R) {
-    case 1: return fast_blocks_per_cu_r<1>(hash, block, lds);
-    case 2: return fast_blocks_per_cu_r<2>(hash, block, lds);
-    case 3: return fast_blocks_per_cu_r<3>(hash, block, lds);
-    case 4: return fast_blocks_per_cu_r<4>(hash, block, lds);
-    case 5: return fast_blocks_per_cu_r<5>(hash, block, lds);
-    case 6: return fast_blocks_per_cu_r<6>(hash, block, lds);
-    case 7: return fast_blocks_per_cu_r<7>(hash, block, lds);
-    case 8: return fast_blocks_per_cu_r<8>(hash, block, lds);
-    case 9: return fast_blocks_per_cu_r<9>(hash, block, lds);
-    default: return fast_blocks_per_cu_r<10>(hash, block, lds);
-  }
+void launch_fast(int R, bool hash, dim3 grid, dim3 block, uint32_t lds, hipStream_t st, const femk::SeedParams &sp) {
+  hipLaunchKernelGGL(fast_kernel(R, hash), grid, block, lds, st, sp);
 }
 
 hipEvent_t get_event(fem_dev *h) {
@@ -968,13 +912,11 @@ int launch_batch(fem_dev *h, Slot &s) {
     // other one — mixed lengths, FEM_NO_PACK, the zero-copy character forms — from its characters.
     const bool verify_packed = s.sent_packed && !h->verify_chars;
     if (verify_packed) vp.packed = s.packed(), vp.exc_bits = s.d_exc_bits, vp.bpr = s.packed_bpr, vp.len = s.max_len;
+    void (*const verify)(femk::VerifyParams) = verify_packed ? femk::verify_kernel_packed : femk::verify_kernel;
     int &v_per_cu = verify_packed ? h->verify_packed_blocks_per_cu : h->verify_blocks_per_cu;
     if (v_per_cu == 0) {
-      int nb = 0;
-      const hipError_t qe = verify_packed ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, femk::verify_kernel_packed, 256, 0)
-                                          : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, femk::verify_kernel, 256, 0);
-      if (qe != hipSuccess || nb <= 0) nb = 4;
-      v_per_cu = nb;
+      const int nb = blocks_per_cu((const void *)verify, 256, 0);
+      v_per_cu = nb > 0 ? nb : 4;
     }
     const uint32_t vgrid = (uint32_t)h->n_cu * (uint32_t)v_per_cu;
     if (split_dense) {
@@ -1008,14 +950,14 @@ int launch_batch(fem_dev *h, Slot &s) {
       {
         const uint32_t lds_bytes = wpb_s * lay_select.wave_bytes;
         const uint64_t key = ((uint64_t)banked << 48) | ((uint64_t)R << 40) | lds_bytes;
-        if (h->select_occ_key != key) h->select_occ_key = key, h->select_occ_blocks = select_blocks_per_cu(R, banked, (int)(64u * wpb_s), lds_bytes);
+        if (h->select_occ_key != key) h->select_occ_key = key, h->select_occ_blocks = blocks_per_cu((const void *)select_kernel(R, banked), (int)(64u * wpb_s), lds_bytes);
         per_cu_s = h->select_occ_blocks > 0 ? (uint64_t)h->select_occ_blocks : std::max<uint64_t>(1, 160u * 1024u / lds_bytes);
         if (overlap) per_cu_s = 1;  // (3.3 ms per 2.5 M reads of C3 with one block per CU as with five: sectors per second, not waves)
         select_lds = lds_bytes, select_threads = 64u * wpb_s;
       }
       {
         const uint64_t key = ((uint64_t)which << 48) | ((uint64_t)R << 40) | lds_j;
-        if (h->join_occ_key != key) h->join_occ_key = key, h->join_occ_blocks = join_blocks_per_cu(R, which, (int)(64u * wpb_j), lds_j);
+        if (h->join_occ_key != key) h->join_occ_key = key, h->join_occ_blocks = blocks_per_cu((const void *)join_kernel(R, which), (int)(64u * wpb_j), lds_j);
         per_cu_j = h->join_occ_blocks > 0 ? (uint64_t)h->join_occ_blocks : std::max<uint64_t>(1, 160u * 1024u / lds_j);
         if (overlap) {
           // leave one block of the next batch's seed_select_kernel room on every CU: registers (512 per lane and SIMD,
@@ -1078,7 +1020,7 @@ int launch_batch(fem_dev *h, Slot &s) {
         // many waves: the CUs do not all run at the same pace.  Every wave pads its last chunk of candidate slots, so
         // extra waves cost the verify kernel lanes.)  FEM_GRID_MULT overrides the multiple (measurement only).
         const uint64_t key = ((uint64_t)R << 40) | ((uint64_t)hash << 32) | lds_bytes;
-        if (h->fast_occ_key != key) h->fast_occ_key = key, h->fast_occ_blocks = fast_blocks_per_cu((int)R, hash, (int)(64u * wpb), lds_bytes);
+        if (h->fast_occ_key != key) h->fast_occ_key = key, h->fast_occ_blocks = blocks_per_cu((const void *)fast_kernel((int)R, hash), (int)(64u * wpb), lds_bytes);
         static const uint64_t mult = testing_switch("FEM_TESTING") && getenv("FEM_GRID_MULT") ? (uint64_t)std::max(1, atoi(getenv("FEM_GRID_MULT"))) : 1;
         const uint64_t per_cu = h->fast_occ_blocks > 0 ? (uint64_t)h->fast_occ_blocks : std::max<uint64_t>(1, 160u * 1024u / lds_bytes);
         const uint64_t wanted = (s.n_reads + (uint64_t)femk::kReadBlock * wpb - 1) / ((uint64_t)femk::kReadBlock * wpb);
@@ -1088,18 +1030,7 @@ int launch_batch(fem_dev *h, Slot &s) {
         femk::SeedParams q = fp;
         q.read_begin = lo, q.n_reads = hi;
         dim3 g(grid), b(64u * wpb);
-        switch (R) {
-          case 1: launch_fast<1>(hash, g, b, lds_bytes, s.stream, q); break;
-          case 2: launch_fast<2>(hash, g, b, lds_bytes, s.stream, q); break;
-          case 3: launch_fast<3>(hash, g, b, lds_bytes, s.stream, q); break;
-          case 4: launch_fast<4>(hash, g, b, lds_bytes, s.stream, q); break;
-          case 5: launch_fast<5>(hash, g, b, lds_bytes, s.stream, q); break;
-          case 6: launch_fast<6>(hash, g, b, lds_bytes, s.stream, q); break;
-          case 7: launch_fast<7>(hash, g, b, lds_bytes, s.stream, q); break;
-          case 8: launch_fast<8>(hash, g, b, lds_bytes, s.stream, q); break;
-          case 9: launch_fast<9>(hash, g, b, lds_bytes, s.stream, q); break;
-          default: launch_fast<10>(hash, g, b, lds_bytes, s.stream, q); break;
-        }
+        launch_fast((int)R, hash, g, b, lds_bytes, s.stream, q);
       };
       rc = timed(0, s.stream, [&] { launch_range(0, (uint32_t)s.n_reads); });
       if (rc) return rc;
@@ -1111,10 +1042,7 @@ int launch_batch(fem_dev *h, Slot &s) {
       rc = timed(2, s.stream, [&] { hipLaunchKernelGGL(femk::seed_filter_kernel, dim3(grid), dim3(64u * wpb), lds_bytes, s.stream, sp); });
       if (rc) return rc;
     }
-    rc = timed(1, s.stream, [&] {
-      if (verify_packed) hipLaunchKernelGGL(femk::verify_kernel_packed, dim3(vgrid), dim3(256), 0, s.stream, vp);
-      else hipLaunchKernelGGL(femk::verify_kernel, dim3(vgrid), dim3(256), 0, s.stream, vp);
-    });
+    rc = timed(1, s.stream, [&] { hipLaunchKernelGGL(verify, dim3(vgrid), dim3(256), 0, s.stream, vp); });
     if (rc) return rc;
     s.packed_enqueued = false, s.packed_home = 0, s.packed_per_read_home = false;
     // (the packing inside the chain of the batches' kernels, 0.07 ms: beside the next batch's join — three kernels starting at

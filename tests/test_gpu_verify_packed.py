@@ -1,4 +1,4 @@
-"""verify_kernel_packed (fem_amd/csrc/fem_kernels.hip.h): a batch that came packed — equal-length reads at two bits per
+"""verify_kernel_packed (fem_amd/csrc/fem_verify.hip.h): a batch that came packed — equal-length reads at two bits per
 base — is verified straight from its codes; reads with anything but upper-case ACGT take their characters.  Every batch
 here is staged packed (pack_reads -> commit_stage_packed) and compared array for array with the oracle and with a second
 handle on which FEM_VERIFY_CHARS=1 keeps the character kernel (verify_kernel) on the same packed batch.
@@ -304,3 +304,37 @@ def test_dense_and_sparse_index_paths(world, dense):
     _check(world, reads, L, e, want, dense=dense)
     odd, _ = _exceptions(rng, reads, 0.03)
     _check(world, odd, L, e, dense=dense)
+
+
+MIXED_LENGTHS = (31, 32, 33, 63, 64, 65, 95, 96, 97, 129)
+
+
+def test_mixed_lengths_staged_as_characters(world):
+    # one batch of every length around the 16-, 64- and 96-column boundaries, shuffled so that the lanes of a wave walk
+    # different numbers of steps, sent as characters: verify_kernel with its read_off gathers, on the step it shares with the
+    # exception path of verify_kernel_packed
+    e, per_len = 1, 200
+    k, step = _index_of(min(MIXED_LENGTHS), e)
+    rng = np.random.default_rng(4242)
+    reads = [r for L in MIXED_LENGTHS for r in _reads(rng, world.seqs, world.places, per_len, L, e)]
+    reads = [reads[int(j)] for j in rng.permutation(len(reads))]
+    reads, kind = _exceptions(rng, reads, 0.03)
+    assert np.any(kind == 1) and np.any(kind == 2)
+    want = _oracle(world, reads, e, k, step)
+    strand = np.repeat(np.arange(2 * len(reads)) & 1, np.diff(want.cand_off.astype(np.int64)))
+    length = np.repeat(np.repeat([len(r) for r in reads], 2), np.diff(want.cand_off.astype(np.int64)))
+    for L in MIXED_LENGTHS:
+        ok = want.v_ed[length == L] != 255
+        assert np.any(ok & (strand[length == L] == 0)) and np.any(ok & (strand[length == L] == 1)), L
+        assert np.any(~ok), L
+    bases = np.frombuffer(b"".join(reads), np.uint8)
+    off = np.concatenate([[0], np.cumsum([len(r) for r in reads])]).astype(np.uint64)
+    dev = world.dev(k, step, False)
+    dev.stage_reads(bases, off)
+    assert not dev.stage_info()[1]
+    dev.map_staged(e=e, k=k, step=step)
+    got = dev.fetch()
+    off_g, cand, ed, end = got.per_strand()
+    assert np.array_equal(off_g, want.cand_off) and np.array_equal(cand, want.cands)
+    assert np.array_equal(ed, want.v_ed) and np.array_equal(end, want.v_end)
+    assert len(got.stats) == 5 and np.array_equal(got.stats, want.stats)
