@@ -467,15 +467,6 @@ void bgzf_cut(const uint64_t *rec_off, uint64_t n_rec, uint64_t n, std::vector<u
   if (!starts->empty()) starts->push_back(n);
 }
 
-Bgzf::~Bgzf() {
-  for (void *p : {(void *)out_, (void *)slots_, (void *)tokens_, (void *)starts_d_, (void *)sizes_})
-    if (p) (void)hipFree(p);
-  if (h_total_) (void)hipHostFree(h_total_);
-  if (h_starts_) (void)hipHostFree(h_starts_);
-  for (hipEvent_t e : ev_)
-    if (e) (void)hipEventDestroy(e);
-}
-
 #define BGZF_TRY(expr)                                          \
   do {                                                          \
     hipError_t e_ = (expr);                                     \
@@ -484,17 +475,6 @@ Bgzf::~Bgzf() {
       return FEM_ERR_HIP;                                       \
     }                                                           \
   } while (0)
-
-template <typename T>
-static hipError_t grow(T **p, size_t *cap, size_t bytes) {
-  if (*p && *cap >= bytes) return hipSuccess;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr, *cap = 0;
-  const size_t want = std::max<size_t>(bytes + bytes / 4, 256);
-  hipError_t e = hipMalloc((void **)p, want);
-  if (e == hipSuccess) *cap = want;
-  return e;
-}
 
 int Bgzf::compress(const uint8_t *in, uint64_t n, const std::vector<uint64_t> &starts, int level, hipStream_t stream, uint64_t *len,
                    std::string *err, float *ms) {
@@ -505,29 +485,17 @@ int Bgzf::compress(const uint8_t *in, uint64_t n, const std::vector<uint64_t> &s
   *len = 0;
   if (n == 0 || starts.size() < 2) return FEM_OK;
   const uint32_t k = (uint32_t)(starts.size() - 1);
-  if (!h_total_) BGZF_TRY(hipHostMalloc((void **)&h_total_, 8, hipHostMallocDefault));
-  if (starts_cap_ < starts.size()) {  // (member starts up, sizes and offsets on the device)
-    if (h_starts_) (void)hipHostFree(h_starts_);
-    if (starts_d_) (void)hipFree(starts_d_);
-    if (sizes_) (void)hipFree(sizes_);
-    h_starts_ = nullptr, starts_d_ = nullptr, sizes_ = nullptr, starts_cap_ = 0;
+  BGZF_TRY(h_total_.ensure(1));
+  if (!sizes_ || starts_d_.size() < starts.size()) {  // (all three or none: sizes_ comes last)
+    sizes_.release();
     const size_t cap = starts.size() + 1024;
-    BGZF_TRY(hipHostMalloc((void **)&h_starts_, cap * 8, hipHostMallocDefault));
-    BGZF_TRY(hipMalloc((void **)&starts_d_, cap * 8));
-    BGZF_TRY(hipMalloc((void **)&sizes_, 2 * cap * 8));
-    starts_cap_ = cap;
+    BGZF_TRY(femb::alloc_all(cap, h_starts_, starts_d_));
+    BGZF_TRY(sizes_.ensure(2 * cap));
   }
-  size_t c1 = slots_cap_;
-  BGZF_TRY(grow(&slots_, &c1, (size_t)k * kBgzfSlot));
-  slots_cap_ = c1;
-  c1 = tokens_cap_;
-  BGZF_TRY(grow(&tokens_, &c1, (size_t)n * 4 + 64));
-  tokens_cap_ = c1;
-  c1 = out_cap_;
-  BGZF_TRY(grow(&out_, &c1, (size_t)k * kBgzfSlot));
-  out_cap_ = c1;
-  for (hipEvent_t &e : ev_)
-    if (!e) BGZF_TRY(hipEventCreate(&e));
+  BGZF_TRY(slots_.ensure((size_t)k * kBgzfSlot));
+  BGZF_TRY(tokens_.ensure((size_t)n + 16));
+  BGZF_TRY(out_.ensure((size_t)k * kBgzfSlot));
+  for (femb::Event &e : ev_) BGZF_TRY(e.create());
   memcpy(h_starts_, starts.data(), starts.size() * 8);
   BGZF_TRY(hipMemcpyAsync(starts_d_, h_starts_, starts.size() * 8, hipMemcpyHostToDevice, stream));
   unsigned long long *offs = sizes_ + k + 1;

@@ -7,6 +7,8 @@
 #include <string>
 #include <vector>
 
+#include "fem_buf.hip.h"
+
 namespace femz {
 
 constexpr uint32_t kBgzfInput = 65280;  // input bytes per member at most (htslib's BGZF_BLOCK_SIZE)
@@ -19,10 +21,6 @@ void bgzf_cut(const uint64_t *rec_off, uint64_t n_rec, uint64_t n, std::vector<u
 
 class Bgzf {
  public:
-  Bgzf() = default;
-  ~Bgzf();
-  Bgzf(const Bgzf &) = delete;
-  Bgzf &operator=(const Bgzf &) = delete;
   // Compresses the n bytes at device pointer `in` into the members starts[0..k] describes (bgzf_cut) on `stream`, and waits
   // for the stream once (the members' sizes).  The members then lie back to back at out() (device memory, *len bytes),
   // valid until the next call.  level: 0 (stored) or 1.  ms (optional) receives the kernels' device time.
@@ -31,12 +29,11 @@ class Bgzf {
   const uint8_t *out() const { return out_; }
 
  private:
-  uint8_t *out_ = nullptr, *slots_ = nullptr;
-  uint32_t *tokens_ = nullptr;
-  unsigned long long *starts_d_ = nullptr, *sizes_ = nullptr, *h_total_ = nullptr;
-  unsigned long long *h_starts_ = nullptr;
-  size_t out_cap_ = 0, slots_cap_ = 0, tokens_cap_ = 0, starts_cap_ = 0;
-  hipEvent_t ev_[2] = {nullptr, nullptr};
+  femb::Buf<uint8_t, femb::Mem::Device, femb::Grow::Quarter> out_, slots_;
+  femb::Buf<uint32_t, femb::Mem::Device, femb::Grow::Quarter> tokens_;
+  femb::Buf<unsigned long long> starts_d_, sizes_;  // (member starts up; sizes and offsets on the device)
+  femb::PinBuf<unsigned long long> h_starts_, h_total_;
+  femb::Event ev_[2];
 };
 
 }  // namespace femz

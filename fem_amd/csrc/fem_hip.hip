@@ -17,6 +17,7 @@
 #include <cstring>
 #include <condition_variable>
 #include <functional>
+#include <memory>
 #include <atomic>
 #include <chrono>
 #include <mutex>
@@ -25,6 +26,7 @@
 #include <utility>
 #include <vector>
 
+#include "fem_buf.hip.h"
 #include "fem_index_build.hip.h"
 #include "fem_pack.h"
 #include "fem_kernels.hip.h"
@@ -35,6 +37,16 @@
 #include "fem_bgzf.hip.h"
 
 namespace {
+
+using femb::Buf;
+using femb::Event;
+using femb::PinBuf;
+using femb::Stream;
+// A slot's staging buffers grow by half at least, so that batches of slowly rising size do not re-allocate each time
+template <typename T>
+using StageBuf = femb::Buf<T, femb::Mem::Device, femb::Grow::Half>;
+template <typename T>
+using PinStageBuf = femb::Buf<T, femb::Mem::Pinned, femb::Grow::Half>;
 
 #ifndef FEM_SLOTS
 #define FEM_SLOTS 4
@@ -54,43 +66,35 @@ struct TimedLaunch {
 constexpr int kMaxParts = 4;
 
 struct Slot {
-  hipStream_t stream = nullptr;
+  Stream stream;
   // inputs
-  uint8_t *d_bases_alloc = nullptr;  // kFrontPad bytes of padding, then the batch's characters, then 64 bytes of slack
+  StageBuf<uint8_t> d_bases_alloc;  // kFrontPad bytes of padding, then the batch's characters, then 64 bytes of slack
   uint8_t *bases() const { return d_bases_alloc + 16; }
-  size_t bases_cap = 0;
-  uint64_t *d_off = nullptr;
-  size_t off_cap = 0;
+  StageBuf<uint64_t> d_off;
   uint64_t n_reads = 0;
   uint64_t n_bases = 0;
   uint32_t max_len = 0;
   bool staged = false;
   // pinned host staging lent to the parser (fem_dev_acquire_stage)
-  char *h_bases = nullptr;
-  size_t h_bases_cap = 0;
-  uint64_t *h_off = nullptr;
-  size_t h_off_cap = 0;
+  PinStageBuf<char> h_bases;
+  PinStageBuf<uint64_t> h_off;
   uint64_t acq_reads = 0, acq_bases = 0;  // what the last fem_dev_acquire_stage asked for
   // qualities and names for the device SAM text (fem_dev_acquire_text_stage / fem_dev_fetch_sam): pinned staging + copies in HBM
-  char *h_quals = nullptr, *h_names = nullptr;
-  uint64_t *h_name_off = nullptr;
-  size_t h_quals_cap = 0, h_names_cap = 0, h_name_off_cap = 0;
-  uint8_t *d_quals = nullptr, *d_names = nullptr;
-  uint64_t *d_name_off = nullptr;
-  size_t d_quals_cap = 0, d_names_cap = 0, d_name_off_cap = 0;
+  PinStageBuf<char> h_quals, h_names;
+  PinStageBuf<uint64_t> h_name_off;
+  StageBuf<uint8_t> d_quals, d_names;
+  StageBuf<uint64_t> d_name_off;
   bool text_staged = false;
   bool host_quals = false;             // the batch's qualities stayed on the host (fem_dev_commit_names_stage): the text leaves their field open
   const uint64_t *qual_at = nullptr;   // ... and where each read's field starts in the slot's last text (pinned, the tail's)
-  hipStream_t text_stream = nullptr;   // qualities and names go to the device beside the batch's kernels, not in front of them
-  hipStream_t out_stream = nullptr;    // the batch's way out (mapping tail, SAM text, its copy home): HIGH priority, see out_stream_of
-  hipEvent_t ev_text_staged = nullptr; // ... and have arrived (the SAM text's kernels wait for it)
-  hipEvent_t ev_text_order = nullptr;  // the slot's last SAM text has been rendered (its kernels read the same arrays)
+  Stream text_stream;   // qualities and names go to the device beside the batch's kernels, not in front of them
+  Stream out_stream;    // the batch's way out (mapping tail, SAM text, its copy home): HIGH priority, see out_stream_of
+  Event ev_text_staged; // ... and have arrived (the SAM text's kernels wait for it)
+  Event ev_text_order;  // the slot's last SAM text has been rendered (its kernels read the same arrays)
   bool have_text_order = false;
-  uint8_t *d_packed_alloc = nullptr;      // packed transfer (fem_dev_stage_reads): kPackedFrontPad bytes of padding, 2-bit codes + positions of other characters, 64 bytes of slack
+  StageBuf<uint8_t> d_packed_alloc;      // packed transfer (fem_dev_stage_reads): kPackedFrontPad bytes of padding, 2-bit codes + positions of other characters, 64 bytes of slack
   uint8_t *packed() const { return d_packed_alloc + kPackedFrontPad; }
-  size_t packed_cap = 0;
-  uint32_t *d_exc_bits = nullptr;         // ... bit r: read r has such a character (the device tail reads the others' bases from d_packed)
-  size_t exc_bits_cap = 0;
+  StageBuf<uint32_t> d_exc_bits;         // ... bit r: read r has such a character (the device tail reads the others' bases from d_packed)
   uint32_t packed_bpr = 0;
   // fem_dev_fetch callers get the result arrays sent home behind the kernels, without the host waiting for the batch first:
   // the per-read arrays whole, the per-candidate arrays up to what the slot's previous batch needed (the rest at fetch)
@@ -103,47 +107,43 @@ struct Slot {
   // the pipeline.  ev_part[q]: piece q's characters are in HBM; ev_sel[q]: its selection is done.
   int parts = 1;
   uint32_t part_begin[kMaxParts + 1] = {0, 0, 0, 0, 0};
-  hipEvent_t ev_part[kMaxParts] = {nullptr, nullptr, nullptr, nullptr}, ev_sel[kMaxParts] = {nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t ev_zeroed = nullptr;
-  hipEvent_t ev_results = nullptr, ev_home = nullptr;  // the batch's results are final on the device / have arrived on the host
+  Event ev_part[kMaxParts], ev_sel[kMaxParts];
+  Event ev_zeroed;
+  Event ev_results, ev_home;  // the batch's results are final on the device / have arrived on the host
   // outputs on the device
-  uint64_t *d_cand = nullptr;
-  uint32_t *d_meta = nullptr;
-  uint8_t *d_ed = nullptr;
-  int16_t *d_end = nullptr;
-  uint32_t cand_cap = 0;
-  uint32_t *d_begin = nullptr, *d_count = nullptr, *d_nmap = nullptr;
-  size_t per_read_cap = 0;
+  // (arrays that share a capacity are allocated together, femb::alloc_all: all of them hold it or none holds anything)
+  Buf<uint64_t> d_cand;
+  Buf<uint32_t> d_meta;
+  Buf<uint8_t> d_ed;
+  Buf<int16_t> d_end;
+  uint32_t cand_cap = 0;  // published once all four exist
+  Buf<uint32_t> d_begin, d_count, d_nmap;  // 2, 2 and 1 entries per read
   // counters: ctr[4] (u32) | arena_ctr[2] (u64) | stats[4] (u64)
-  uint8_t *d_ctl = nullptr;
-  uint8_t *h_ctl = nullptr;  // pinned mirror
-  uint64_t *d_arena = nullptr;
+  Buf<uint8_t> d_ctl;
+  PinBuf<uint8_t> h_ctl;  // pinned mirror
+  Buf<uint64_t> d_arena;
   uint64_t arena_cap = 0;
-  uint32_t *d_slow = nullptr;  // reads the fast seed kernel leaves to the generic one
+  Buf<uint32_t> d_slow;  // reads the fast seed kernel leaves to the generic one
   uint32_t slow_cap = 0;
   // dense indexes: what seed_select_kernel hands seed_join_kernel (6 R selected seeds + one header per read)
-  uint2 *d_sel = nullptr, *d_sel_hdr = nullptr;
-  size_t sel_cap = 0, sel_hdr_cap = 0;
+  StageBuf<uint2> d_sel, d_sel_hdr;
   // pinned host results
-  uint32_t *h_begin = nullptr, *h_count = nullptr;
-  size_t h_per_read_cap = 0;
-  uint64_t *h_cand = nullptr;
-  uint8_t *h_ed = nullptr;
-  int16_t *h_end = nullptr;
-  size_t h_cand_cap = 0;
+  PinBuf<uint32_t> h_begin, h_count;
+  PinBuf<uint64_t> h_cand;
+  PinBuf<uint8_t> h_ed;
+  PinBuf<int16_t> h_end;
   // the outcome in the form that crosses the link (fem_dev_fetch_packed; pack_results_kernel): on the device, pinned on the host
-  uint8_t *d_count8 = nullptr, *d_ped = nullptr;
-  uint32_t *d_seg = nullptr;
-  uint64_t *d_pcand = nullptr;
-  int16_t *d_pend = nullptr;
-  uint2 *d_big = nullptr;
-  size_t count8_cap = 0, seg_cap = 0, pcand_cap = 0;
-  uint8_t *h_count8 = nullptr, *h_ped = nullptr;
-  uint32_t *h_seg = nullptr;
-  uint64_t *h_pcand = nullptr;
-  int16_t *h_pend = nullptr;
-  uint2 *h_big = nullptr;
-  size_t h_count8_cap = 0, h_seg_cap = 0, h_pcand_cap = 0;
+  StageBuf<uint8_t> d_count8;
+  StageBuf<uint32_t> d_seg;
+  Buf<uint64_t> d_pcand;
+  Buf<uint8_t> d_ped;
+  Buf<int16_t> d_pend;
+  Buf<uint2> d_big;
+  PinBuf<uint8_t> h_count8, h_ped;
+  PinBuf<uint32_t> h_seg;
+  PinBuf<uint64_t> h_pcand;
+  PinBuf<int16_t> h_pend;
+  PinBuf<uint2> h_big;
   bool want_packed = false;    // the slot's last fetch was fem_dev_fetch_packed: launch_batch packs and sends home behind the kernels
   bool packed_enqueued = false;  // pack_results_kernel ran (or is queued) for the slot's current batch
   uint64_t packed_home = 0, last_n_packed = 0;  // packed candidates copied home behind the kernels / of the slot's previous batch
@@ -155,7 +155,7 @@ struct Slot {
   uint64_t stats[5] = {0, 0, 0, 0, 0};
   uint32_t n_cand = 0;
   std::vector<TimedLaunch> pending;
-  femt::Tail *tail = nullptr;  // device mapping tail (fem_dev_fetch_records), created on first use
+  std::unique_ptr<femt::Tail> tail;  // device mapping tail (fem_dev_fetch_records), created on first use
   // pair mode (fem_dev_set_pairs): the batches are read pairs, read i and read n_reads / 2 + i
   bool paired = false;
   int32_t min_insert = 0, max_insert = 0;
@@ -252,46 +252,45 @@ struct fem_dev {
   // lock; a thread waiting for the device does not hold it.
   femt::TextGate text_gate;  // one SAM text on its way to the host at a time (fem_tail.hip.h)
   // fem_dev_bgzf_compress: its compressor, input buffer and stream
-  femz::Bgzf *bgzf = nullptr;
-  uint8_t *d_zin = nullptr;
-  size_t d_zin_cap = 0;
-  hipStream_t z_stream = nullptr;
+  std::unique_ptr<femz::Bgzf> bgzf;
+  Buf<uint8_t> d_zin;
+  Stream z_stream;
   std::recursive_mutex mu;
   int device = 0;
-  StagePool *stage_pool = nullptr;  // host threads of fem_dev_stage_reads
-  uint8_t *d_ref_names = nullptr;   // reference sequence names for the device SAM text
-  uint32_t *d_ref_name_off = nullptr;
+  std::unique_ptr<StagePool> stage_pool;  // host threads of fem_dev_stage_reads
+  Buf<uint8_t> d_ref_names;   // reference sequence names for the device SAM text
+  Buf<uint32_t> d_ref_name_off;
   int n_cu = 256;
   std::string err;
   // index
-  uint32_t *d_lookup = nullptr;
+  Buf<uint32_t> d_lookup;
   uint64_t n_lookup = 0;
-  uint64_t *d_occ = nullptr;
+  Buf<uint64_t> d_occ;
   uint64_t n_occ = 0;
   int32_t k = 0, step = 0;
   uint64_t fast_occ_key = ~0ull;  // seed_fast_kernel residency, cached per (R, form, LDS bytes)
   int fast_occ_blocks = 0;
-  uint32_t *d_summary = nullptr;  // bucket summaries (femk::SeedParams::summary), built for sparse indexes only
+  Buf<uint32_t> d_summary;  // bucket summaries (femk::SeedParams::summary), built for sparse indexes only
   // dense indexes: occurrence table in 32-bit global coordinates + its sequence tables (fem_seed_dense.hip.h)
-  uint32_t *d_occ32 = nullptr, *d_goff = nullptr, *d_blkseq = nullptr;
+  Buf<uint32_t> d_occ32, d_goff, d_blkseq;
   uint32_t list_shift = 0;        // != 0: d_occ32 is the strided table (bucket h at h << list_shift, fem_seed_dense.hip.h); 0: compact
   bool no_strided = false;        // FEM_NO_STRIDED=1: keep the compact 32-bit table (test hook / A-B)
   bool verify_chars = false;      // FEM_VERIFY_CHARS=1: verify_kernel (characters) on packed batches too (test hook / A-B)
-  uint32_t *d_freq11 = nullptr;  // saturated byte frequencies per 11-mer (fem_seed_select.hip.h), 64 MiB
+  Buf<uint32_t> d_freq11;  // saturated byte frequencies per 11-mer (fem_seed_select.hip.h), 64 MiB
   // banks of sequences, each with 32-bit coordinates of its own (fem_seed_dense.hip.h); 1 = the whole reference in one
   uint32_t n_banks = 1, bank_first[5] = {0, 0, 0, 0, 0};
-  uint32_t *d_bank_lo = nullptr;  // [n_banks - 1][n_buckets]: where each further bank's part of a bucket's list starts
+  Buf<uint32_t> d_bank_lo;  // [n_banks - 1][n_buckets]: where each further bank's part of a bucket's list starts
   uint64_t bank_limit = 0;        // FEM_TEST_BANK_BASES: coordinates per bank (tests: banks on small references); 0 = kDenseLimit
   uint32_t bank_seqs = 0;         // FEM_TEST_BANK_SEQS: sequences per bank (tests); 0 = kDenseMaxSeq
   int select_occ_blocks = 0, join_occ_blocks = 0;
   uint64_t select_occ_key = ~0ull, join_occ_key = ~0ull;
   // reference
   // bit q of the codes, one bit per base (verify_kernel's windows); [3]: the uploaded character is not one of "ACGTN"
-  uint8_t *d_planes = nullptr;  // femk::plane_window
-  uint8_t *d_ref_raw = nullptr;  // the characters as uploaded (the traceback and MD compare and print them)
+  Buf<uint8_t> d_planes;  // femk::plane_window
+  Buf<uint8_t> d_ref_raw;  // the characters as uploaded (the traceback and MD compare and print them)
   uint64_t ref_bytes = 0;
-  uint64_t *d_seq_off = nullptr;
-  uint32_t *d_seq_len = nullptr;
+  Buf<uint64_t> d_seq_off;
+  Buf<uint32_t> d_seq_len;
   uint32_t n_seq = 0;
   std::vector<uint64_t> seq_off;
   std::vector<uint32_t> seq_len;
@@ -306,31 +305,31 @@ struct fem_dev {
   bool force_dense = false;    // FEM_FORCE_DENSE=1: build the 32-bit tables and run seed_select_kernel + seed_join_kernel whatever the index density (test hook)
   bool no_dense = false;       // FEM_NO_DENSE=1: never take the dense-index path (measurement / A-B hook)
   bool tiny_buffers = false;   // FEM_TEST_TINY_BUFFERS=1: start every scratch buffer tiny so the grow + re-run paths run (test hook)
-  std::vector<hipEvent_t> event_pool;
+  femb::EventPool event_pool;
   // The slots' streams overlap copies with kernels, but the kernels of different batches run one after the other
   // (each batch's first kernel waits for the previous batch's last): two batches' seed kernels side by side only
   // evict each other's index lines, and per-kernel event times stay those of a kernel that has the chip to itself.
-  hipEvent_t ev_kernels_done = nullptr;
+  Event ev_kernels_done;
   bool have_kernels_done = false;
   // Dense indexes: seed_select_kernel of batch i + 1 runs BESIDE batch i's seed_join_kernel (it is bound by the rate of
   // table sectors the fabric delivers and needs four waves per CU for that; the join is bound by instruction issue):
   // selections are chained among themselves, and a batch's join waits for its own selection and the previous batch's
   // kernels.  FEM_NO_OVERLAP=1: one after the other (measurement hook).
-  hipEvent_t ev_select_done = nullptr;
+  Event ev_select_done;
   bool have_select_done = false;
   bool no_overlap = false;
   // The batches' H2D copies go one after the other (each waits for the previous one's): four batches committed at once —
   // the start of every job — used to share the link, and the first one's kernels started when all four had arrived.
-  hipEvent_t ev_h2d_done = nullptr;
+  Event ev_h2d_done;
   bool have_h2d_done = false;
-  hipStream_t side_stream = nullptr;  // the selections of a batch mapped in parts (beside the joins on the slot's stream)
+  Stream side_stream;  // the selections of a batch mapped in parts (beside the joins on the slot's stream)
   bool no_parts = false;              // FEM_NO_PARTS=1 (measurement hook)
   int max_parts = 2;                  // parts of a batch that meets an idle device (FEM_PARTS, measurement hook): two halves —
                                       // every further launch of the join costs ~0.35 ms of ramp and tail, what a finer first part saves
   // FEM_TIMELINE=1 (with FEM_TESTING=1 and timing on): every timed launch and copy is printed with its start and end in ms since
   // the last fem_dev_reset_timing — the pipeline's fill and drain made visible (ids >= kTimedKernels: 20 H2D + unpack, 21 D2H)
   bool timeline = false, have_epoch = false;
-  hipEvent_t ev_epoch = nullptr;
+  Event ev_epoch;
 };
 
 namespace {
@@ -360,30 +359,6 @@ int fail(fem_dev *h, int rc, const std::string &msg) {
       return fail(h, e_ == hipErrorOutOfMemory ? FEM_ERR_NOMEM : FEM_ERR_HIP,                     \
                   std::string(#expr) + ": " + hipGetErrorString(e_));                             \
   } while (0)
-
-template <typename T>
-int dev_realloc(fem_dev *h, T **p, size_t *cap, size_t want, bool keep = false) {
-  if (want <= *cap && *p) return FEM_OK;
-  size_t n = std::max(want, *cap + *cap / 2);
-  T *q = nullptr;
-  HIP_TRY(h, hipMalloc((void **)&q, std::max<size_t>(n, 1) * sizeof(T)));
-  if (keep && *p && *cap) HIP_TRY(h, hipMemcpy(q, *p, *cap * sizeof(T), hipMemcpyDeviceToDevice));
-  if (*p) (void)hipFree(*p);
-  *p = q;
-  *cap = n;
-  return FEM_OK;
-}
-
-template <typename T>
-int pinned_realloc(fem_dev *h, T **p, size_t *cap, size_t want) {
-  if (want <= *cap && *p) return FEM_OK;
-  size_t n = std::max(want, *cap + *cap / 2);
-  if (*p) (void)hipHostFree(*p);
-  *p = nullptr;
-  HIP_TRY(h, hipHostMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T), hipHostMallocDefault));
-  *cap = n;
-  return FEM_OK;
-}
 
 bool params_ok(const fem_params *p) {
   return p && p->k >= 1 && p->k <= 15 && p->step >= 1 && p->step <= 16 && p->e >= 0 && p->e <= 7 && p->a >= 0 &&
@@ -590,17 +565,6 @@ void launch_fast(int R, bool hash, dim3 grid, dim3 block, uint32_t lds, hipStrea
   hipLaunchKernelGGL(fast_kernel(R, hash), grid, block, lds, st, sp);
 }
 
-hipEvent_t get_event(fem_dev *h) {
-  if (!h->event_pool.empty()) {
-    hipEvent_t e = h->event_pool.back();
-    h->event_pool.pop_back();
-    return e;
-  }
-  hipEvent_t e = nullptr;
-  (void)hipEventCreate(&e);
-  return e;
-}
-
 // (timeline only) events around a copy on `st`
 struct Span {
   fem_dev *h;
@@ -610,7 +574,7 @@ struct Span {
   bool on;
   Span(fem_dev *h_, Slot &s_, int id, hipStream_t st_) : h(h_), s(s_), st(st_), t{id, nullptr, nullptr, false}, on(h_->timing && h_->timeline) {
     if (on) {
-      t.start = get_event(h), t.stop = get_event(h);
+      t.start = h->event_pool.get(), t.stop = h->event_pool.get();
       (void)hipEventRecord(t.start, st);
     }
   }
@@ -634,48 +598,32 @@ void drain_timing(fem_dev *h, Slot &s) {
       if (hipEventElapsedTime(&a, h->ev_epoch, t.start) == hipSuccess && hipEventElapsedTime(&b, h->ev_epoch, t.stop) == hipSuccess)
         fprintf(stderr, "TL slot %d id %2d  %9.3f %9.3f  (%.3f)\n", (int)(&s - h->slot), t.kernel, a, b, b - a);
     }
-    h->event_pool.push_back(t.start);
-    h->event_pool.push_back(t.stop);
+    h->event_pool.put(t.start);
+    h->event_pool.put(t.stop);
   }
   s.pending.clear();
 }
 
 int ensure_outputs(fem_dev *h, Slot &s) {
-  size_t want_reads = (size_t)s.n_reads;
-  if (want_reads > s.per_read_cap || !s.d_begin) {
-    size_t cap = std::max<size_t>(want_reads, 1);
-    if (s.d_begin) (void)hipFree(s.d_begin);
-    if (s.d_count) (void)hipFree(s.d_count);
-    if (s.d_nmap) (void)hipFree(s.d_nmap);
-    s.d_begin = s.d_count = s.d_nmap = nullptr;
-    HIP_TRY(h, hipMalloc((void **)&s.d_begin, cap * 2 * sizeof(uint32_t)));
-    HIP_TRY(h, hipMalloc((void **)&s.d_count, cap * 2 * sizeof(uint32_t)));
-    HIP_TRY(h, hipMalloc((void **)&s.d_nmap, cap * sizeof(uint32_t)));
-    s.per_read_cap = cap;
+  if ((size_t)s.n_reads > s.d_nmap.size() || !s.d_nmap) {  // (d_nmap comes last: where it exists, so do the other two)
+    const size_t cap = std::max<size_t>((size_t)s.n_reads, 1);
+    s.d_nmap.release();
+    HIP_TRY(h, femb::alloc_all(cap * 2, s.d_begin, s.d_count));
+    HIP_TRY(h, s.d_nmap.ensure(cap));
   }
-  if (!s.d_cand || !s.d_meta || !s.d_ed || !s.d_end || s.cand_cap == 0) {
-    for (void *p : {(void *)s.d_cand, (void *)s.d_meta, (void *)s.d_ed, (void *)s.d_end})
-      if (p) (void)hipFree(p);
-    s.d_cand = nullptr, s.d_meta = nullptr, s.d_ed = nullptr, s.d_end = nullptr;
+  if (!s.d_cand || s.cand_cap == 0) {
     uint64_t want = 2 * s.n_reads + (5u << 20);  // ~1 candidate per strand on typical data + chunk padding
     if (h->tiny_buffers) want = 512;
     want = std::min<uint64_t>(want, 0xFFFFFFF0ull);
     s.cand_cap = 0;
-    size_t c0 = 0, c1 = 0, c2 = 0, c3 = 0;
-    int rc;
-    if ((rc = dev_realloc(h, &s.d_cand, &c0, want))) return rc;
-    if ((rc = dev_realloc(h, &s.d_meta, &c1, want))) return rc;
-    if ((rc = dev_realloc(h, &s.d_ed, &c2, want))) return rc;
-    if ((rc = dev_realloc(h, &s.d_end, &c3, want))) return rc;
+    HIP_TRY(h, femb::alloc_all(want, s.d_cand, s.d_meta, s.d_ed, s.d_end));
     s.cand_cap = (uint32_t)want;
   }
-  if (!s.d_ctl) {
-    HIP_TRY(h, hipMalloc((void **)&s.d_ctl, kCtlAlloc));
-    HIP_TRY(h, hipHostMalloc((void **)&s.h_ctl, kCtlBytes, hipHostMallocDefault));
-  }
+  HIP_TRY(h, s.d_ctl.ensure(kCtlAlloc));
+  HIP_TRY(h, s.h_ctl.ensure(kCtlBytes));
   if (!s.d_arena) {
     s.arena_cap = h->tiny_buffers ? 256u : (4u << 20);  // entries (32 MiB); grown on demand
-    HIP_TRY(h, hipMalloc((void **)&s.d_arena, s.arena_cap * sizeof(uint64_t)));
+    HIP_TRY(h, s.d_arena.ensure(s.arena_cap));
   }
   {
     // With long occurrence lists (large references) nearly every read overflows the lanes of the fast kernel
@@ -684,9 +632,8 @@ int ensure_outputs(fem_dev *h, Slot &s) {
     uint64_t want = avg_bucket > 1.0 ? s.n_reads + (1u << 20) : (1u << 18);
     if (h->tiny_buffers) want = s.d_slow ? s.slow_cap : 32;
     if (want > s.slow_cap || !s.d_slow) {
-      if (s.d_slow) (void)hipFree(s.d_slow);
-      s.d_slow = nullptr;
-      HIP_TRY(h, hipMalloc((void **)&s.d_slow, want * sizeof(uint32_t)));
+      s.d_slow.release();
+      HIP_TRY(h, s.d_slow.ensure(want));
       s.slow_cap = (uint32_t)want;
     }
   }
@@ -696,13 +643,7 @@ int ensure_outputs(fem_dev *h, Slot &s) {
 int grow_candidates(fem_dev *h, Slot &s, uint64_t want) {
   if (want > 0xFFFFFFF0ull) return fail(h, FEM_ERR_UNSUPPORTED, "more than 2^32 candidates in one batch; split the batch");
   s.cand_cap = 0;  // published again only once all four arrays exist (ensure_outputs re-allocates otherwise)
-  for (void *p : {(void *)s.d_cand, (void *)s.d_meta, (void *)s.d_ed, (void *)s.d_end})
-    if (p) (void)hipFree(p);
-  s.d_cand = nullptr, s.d_meta = nullptr, s.d_ed = nullptr, s.d_end = nullptr;
-  HIP_TRY(h, hipMalloc((void **)&s.d_cand, want * sizeof(uint64_t)));
-  HIP_TRY(h, hipMalloc((void **)&s.d_meta, want * sizeof(uint32_t)));
-  HIP_TRY(h, hipMalloc((void **)&s.d_ed, want * sizeof(uint8_t)));
-  HIP_TRY(h, hipMalloc((void **)&s.d_end, want * sizeof(int16_t)));
+  HIP_TRY(h, femb::alloc_all(want, s.d_cand, s.d_meta, s.d_ed, s.d_end));
   s.cand_cap = (uint32_t)want;
   return FEM_OK;
 }
@@ -740,58 +681,46 @@ int d2h_end(fem_dev *h, Slot &s, hipStream_t st) {
   return FEM_OK;
 }
 
+// `launch` on `st`, between two events when the handle times its kernels (id: fem_dev_kernel_time; counts = false: a further
+// part of a launch that is counted already)
+template <typename Launch>
+int timed_launch(fem_dev *h, Slot &s, int id, hipStream_t st, bool counts, Launch &&launch) {
+  TimedLaunch t{id, nullptr, nullptr, counts};
+  if (h->timing) {
+    t.start = h->event_pool.get(), t.stop = h->event_pool.get();
+    HIP_TRY(h, hipEventRecord(t.start, st));
+  }
+  launch();
+  HIP_TRY(h, hipGetLastError());
+  if (h->timing) {
+    HIP_TRY(h, hipEventRecord(t.stop, st));
+    s.pending.push_back(t);
+  }
+  return FEM_OK;
+}
+
 // pack_results_kernel behind the slot's verification, and (send_home) the packed arrays' copies behind it: the per-strand
 // bytes and the segment table whole, the per-candidate arrays up to what the slot's previous batch needed (the rest at fetch).
 int enqueue_pack(fem_dev *h, Slot &s, bool kernel, bool send_home) {
   const size_t n2 = (size_t)s.n_reads * 2, n_seg = (n2 + 255) / 256;
   int rc;
-  if ((rc = dev_realloc(h, &s.d_count8, &s.count8_cap, n2 + 16))) return rc;
-  if ((rc = dev_realloc(h, &s.d_seg, &s.seg_cap, n_seg + 4))) return rc;
-  if (s.pcand_cap < s.cand_cap || !s.d_pcand) {
-    for (void *q : {(void *)s.d_pcand, (void *)s.d_ped, (void *)s.d_pend})
-      if (q) (void)hipFree(q);
-    s.d_pcand = nullptr, s.d_ped = nullptr, s.d_pend = nullptr, s.pcand_cap = 0;
-    HIP_TRY(h, hipMalloc((void **)&s.d_pcand, (size_t)s.cand_cap * sizeof(uint64_t)));
-    HIP_TRY(h, hipMalloc((void **)&s.d_ped, (size_t)s.cand_cap * sizeof(uint8_t)));
-    HIP_TRY(h, hipMalloc((void **)&s.d_pend, (size_t)s.cand_cap * sizeof(int16_t)));
-    s.pcand_cap = s.cand_cap;
-  }
-  if (!s.d_big) HIP_TRY(h, hipMalloc((void **)&s.d_big, kBigCap * sizeof(uint2)));
-  if (n2 + 16 > s.h_count8_cap || !s.h_count8) {
-    if (s.h_count8) (void)hipHostFree(s.h_count8);
-    s.h_count8 = nullptr, s.h_count8_cap = 0;
-    if ((rc = pinned_realloc(h, &s.h_count8, &s.h_count8_cap, n2 + 16))) return rc;
-  }
-  if (n_seg + 4 > s.h_seg_cap || !s.h_seg) {
-    if (s.h_seg) (void)hipHostFree(s.h_seg);
-    s.h_seg = nullptr, s.h_seg_cap = 0;
-    if ((rc = pinned_realloc(h, &s.h_seg, &s.h_seg_cap, n_seg + 4))) return rc;
-  }
-  if (!s.h_big) {
-    size_t c = 0;
-    if ((rc = pinned_realloc(h, &s.h_big, &c, (size_t)kBigCap))) return rc;
-  }
+  HIP_TRY(h, s.d_count8.ensure(n2 + 16));
+  HIP_TRY(h, s.d_seg.ensure(n_seg + 4));
+  if (s.d_pcand.size() < s.cand_cap || !s.d_pcand) HIP_TRY(h, femb::alloc_all(s.cand_cap, s.d_pcand, s.d_ped, s.d_pend));
+  HIP_TRY(h, s.d_big.ensure(kBigCap));
+  HIP_TRY(h, s.h_count8.ensure(n2 + 16));
+  HIP_TRY(h, s.h_seg.ensure(n_seg + 4));
+  HIP_TRY(h, s.h_big.ensure(kBigCap));
   if (kernel) {
-  femk::PackParams pp{};
-  pp.cand_begin = s.d_begin, pp.cand_count = s.d_count, pp.cand = s.d_cand, pp.ed = s.d_ed, pp.end = s.d_end;
-  pp.ctr = (const uint32_t *)s.d_ctl, pp.n_strands = (uint32_t)n2;
-  pp.count8 = s.d_count8, pp.seg_begin = s.d_seg, pp.pcand = s.d_pcand, pp.ped = s.d_ped, pp.pend = s.d_pend, pp.pcap = (uint32_t)s.pcand_cap;
-  pp.cursor = (uint32_t *)(s.d_ctl + kCtlPackCursor), pp.big = s.d_big, pp.big_cap = kBigCap;
-  const uint32_t grid = (uint32_t)std::max<size_t>(1, (n_seg + femk::kPackSegs - 1) / femk::kPackSegs);  // (a block per sixteen segments)
-  {
-    TimedLaunch t{6, nullptr, nullptr, true};  // (kernel id 6: pack_results_kernel)
-    if (h->timing) {
-      t.start = get_event(h), t.stop = get_event(h);
-      HIP_TRY(h, hipEventRecord(t.start, s.stream));
-    }
-    hipLaunchKernelGGL(femk::pack_results_kernel, dim3(grid), dim3(256), 0, s.stream, pp);
-    HIP_TRY(h, hipGetLastError());
-    if (h->timing) {
-      HIP_TRY(h, hipEventRecord(t.stop, s.stream));
-      s.pending.push_back(t);
-    }
-  }
-  s.packed_enqueued = true;
+    femk::PackParams pp{};
+    pp.cand_begin = s.d_begin, pp.cand_count = s.d_count, pp.cand = s.d_cand, pp.ed = s.d_ed, pp.end = s.d_end;
+    pp.ctr = (const uint32_t *)s.d_ctl.get(), pp.n_strands = (uint32_t)n2;
+    pp.count8 = s.d_count8, pp.seg_begin = s.d_seg, pp.pcand = s.d_pcand, pp.ped = s.d_ped, pp.pend = s.d_pend, pp.pcap = (uint32_t)s.d_pcand.size();
+    pp.cursor = (uint32_t *)(s.d_ctl + kCtlPackCursor), pp.big = s.d_big, pp.big_cap = kBigCap;
+    const uint32_t grid = (uint32_t)std::max<size_t>(1, (n_seg + femk::kPackSegs - 1) / femk::kPackSegs);  // (a block per sixteen segments)
+    // (kernel id 6: pack_results_kernel)
+    if ((rc = timed_launch(h, s, 6, s.stream, true, [&] { hipLaunchKernelGGL(femk::pack_results_kernel, dim3(grid), dim3(256), 0, s.stream, pp); }))) return rc;
+    s.packed_enqueued = true;
   }
   if (send_home) {
     hipStream_t st = d2h_begin(h, s);
@@ -800,7 +729,7 @@ int enqueue_pack(fem_dev *h, Slot &s, bool kernel, bool send_home) {
       HIP_TRY(h, hipMemcpyAsync(s.h_count8, s.d_count8, n2, hipMemcpyDeviceToHost, st));
       HIP_TRY(h, hipMemcpyAsync(s.h_seg, s.d_seg, n_seg * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
       s.packed_per_read_home = true;
-      const size_t guess = std::min<size_t>({(size_t)(s.last_n_packed + s.last_n_packed / 32 + 1024), s.h_pcand_cap, s.pcand_cap});
+      const size_t guess = std::min<size_t>({(size_t)(s.last_n_packed + s.last_n_packed / 32 + 1024), s.h_pcand.size(), s.d_pcand.size()});
       if (s.last_n_packed && s.h_pcand && guess) {
         HIP_TRY(h, hipMemcpyAsync(s.h_pcand, s.d_pcand, guess * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
         HIP_TRY(h, hipMemcpyAsync(s.h_ped, s.d_ped, guess * sizeof(uint8_t), hipMemcpyDeviceToHost, st));
@@ -816,7 +745,7 @@ int enqueue_pack(fem_dev *h, Slot &s, bool kernel, bool send_home) {
 // Enqueue the two kernels of one batch on the slot's stream (asynchronous).
 int launch_batch(fem_dev *h, Slot &s) {
   const fem_params &p = s.params;
-  uint32_t *d_ctr = (uint32_t *)s.d_ctl;
+  uint32_t *d_ctr = (uint32_t *)s.d_ctl.get();
   unsigned long long *d_arena_ctr = (unsigned long long *)(s.d_ctl + 4 * sizeof(uint32_t));
   unsigned long long *d_stats = (unsigned long long *)(s.d_ctl + 4 * sizeof(uint32_t) + 2 * sizeof(uint64_t));
   // A batch that meets an IDLE device (the start of a job) is mapped in parts on a dense index — see below; its counters are
@@ -879,21 +808,6 @@ int launch_batch(fem_dev *h, Slot &s) {
   };
   if (sp.lay.wave_bytes > 64u * 1024u) return fail(h, FEM_ERR_UNSUPPORTED, "read too long for the device path");
 
-  auto timed = [&](int id, hipStream_t st, auto &&launch, bool counts = true) -> int {
-    TimedLaunch t{id, nullptr, nullptr, counts};
-    if (h->timing) {
-      t.start = get_event(h), t.stop = get_event(h);
-      HIP_TRY(h, hipEventRecord(t.start, st));
-    }
-    launch();
-    HIP_TRY(h, hipGetLastError());
-    if (h->timing) {
-      HIP_TRY(h, hipEventRecord(t.stop, st));
-      s.pending.push_back(t);
-    }
-    return FEM_OK;
-  };
-
   if (s.n_reads) {
     int rc;
     const bool split_dense = use_fast && h->d_occ32 && h->d_freq11;
@@ -925,8 +839,8 @@ int launch_batch(fem_dev *h, Slot &s) {
       const uint32_t max_len = std::max<uint32_t>(s.max_len, (uint32_t)p.k);
       const bool banked = h->n_banks > 1;
       const size_t want_sel = (size_t)s.n_reads * 6u * (size_t)R * h->n_banks;
-      if ((rc = dev_realloc(h, &s.d_sel, &s.sel_cap, want_sel))) return rc;
-      if ((rc = dev_realloc(h, &s.d_sel_hdr, &s.sel_hdr_cap, (size_t)s.n_reads))) return rc;
+      HIP_TRY(h, s.d_sel.ensure(want_sel));
+      HIP_TRY(h, s.d_sel_hdr.ensure((size_t)s.n_reads));
       femk::SeedParams fp = sp;
       fp.occ32 = h->d_occ32, fp.list_shift = h->list_shift, fp.goff = h->d_goff, fp.blkseq = h->d_blkseq;
       fp.freq11 = h->d_freq11, fp.sel = s.d_sel, fp.sel_hdr = s.d_sel_hdr;
@@ -986,7 +900,7 @@ int launch_batch(fem_dev *h, Slot &s) {
           }
           const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((blocks_of_reads + wpb_s - 1) / wpb_s, (uint64_t)h->n_cu * per_cu_s));
           fp.work_cursor = (uint32_t *)(s.d_ctl + kCtlWorkCursor + (size_t)q * kCtlPartStride);
-          rc = timed(8, st_sel, [&] { launch_select(R, banked, dim3(grid), dim3(64u * wpb_s), select_lds, st_sel, fp); }, q == 0);
+          rc = timed_launch(h, s, 8, st_sel, q == 0, [&] { launch_select(R, banked, dim3(grid), dim3(64u * wpb_s), select_lds, st_sel, fp); });
           if (rc) return rc;
           if (parts > 1) {
             HIP_TRY(h, hipEventRecord(s.ev_sel[q], st_sel));
@@ -1002,7 +916,7 @@ int launch_batch(fem_dev *h, Slot &s) {
           fp.lay = lay_join;
           const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((blocks_of_reads + wpb_j - 1) / wpb_j, (uint64_t)h->n_cu * per_cu_j));
           fp.work_cursor = (uint32_t *)(s.d_ctl + kCtlWorkCursor2 + (size_t)q * kCtlPartStride);
-          rc = timed(0, s.stream, [&] { launch_join(R, which, dim3(grid), dim3(64u * wpb_j), lds_j, s.stream, fp); }, q == 0);
+          rc = timed_launch(h, s, 0, s.stream, q == 0, [&] { launch_join(R, which, dim3(grid), dim3(64u * wpb_j), lds_j, s.stream, fp); });
           if (rc) return rc;
         }
       }
@@ -1032,17 +946,17 @@ int launch_batch(fem_dev *h, Slot &s) {
         dim3 g(grid), b(64u * wpb);
         launch_fast((int)R, hash, g, b, lds_bytes, s.stream, q);
       };
-      rc = timed(0, s.stream, [&] { launch_range(0, (uint32_t)s.n_reads); });
+      rc = timed_launch(h, s, 0, s.stream, true, [&] { launch_range(0, (uint32_t)s.n_reads); });
       if (rc) return rc;
       sp.work_queue = s.d_slow;  // the generic kernel finishes what the fast one queued
     }
     {
       uint32_t wpb, lds_bytes, grid;
       shape(sp.lay, &wpb, &lds_bytes, &grid);
-      rc = timed(2, s.stream, [&] { hipLaunchKernelGGL(femk::seed_filter_kernel, dim3(grid), dim3(64u * wpb), lds_bytes, s.stream, sp); });
+      rc = timed_launch(h, s, 2, s.stream, true, [&] { hipLaunchKernelGGL(femk::seed_filter_kernel, dim3(grid), dim3(64u * wpb), lds_bytes, s.stream, sp); });
       if (rc) return rc;
     }
-    rc = timed(1, s.stream, [&] { hipLaunchKernelGGL(verify, dim3(vgrid), dim3(256), 0, s.stream, vp); });
+    rc = timed_launch(h, s, 1, s.stream, true, [&] { hipLaunchKernelGGL(verify, dim3(vgrid), dim3(256), 0, s.stream, vp); });
     if (rc) return rc;
     s.packed_enqueued = false, s.packed_home = 0, s.packed_per_read_home = false;
     // (the packing inside the chain of the batches' kernels, 0.07 ms: beside the next batch's join — three kernels starting at
@@ -1064,12 +978,12 @@ int launch_batch(fem_dev *h, Slot &s) {
     {
       Span span(h, s, 21, st);
       const size_t n2 = (size_t)s.n_reads * 2;
-      if (n2 && s.h_begin && n2 <= s.h_per_read_cap) {
+      if (n2 && s.h_begin && n2 <= s.h_begin.size()) {
         HIP_TRY(h, hipMemcpyAsync(s.h_begin, s.d_begin, n2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         HIP_TRY(h, hipMemcpyAsync(s.h_count, s.d_count, n2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         s.prefetched_reads2 = n2;
       }
-      const size_t guess = std::min<size_t>({(size_t)(s.last_n_cand + s.last_n_cand / 32 + 1024), s.h_cand_cap, (size_t)s.cand_cap});
+      const size_t guess = std::min<size_t>({(size_t)(s.last_n_cand + s.last_n_cand / 32 + 1024), s.h_cand.size(), (size_t)s.cand_cap});
       if (s.last_n_cand && s.h_cand && guess) {
         HIP_TRY(h, hipMemcpyAsync(s.h_cand, s.d_cand, guess * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
         HIP_TRY(h, hipMemcpyAsync(s.h_ed, s.d_ed, guess * sizeof(uint8_t), hipMemcpyDeviceToHost, st));
@@ -1087,14 +1001,13 @@ int launch_batch(fem_dev *h, Slot &s) {
 
 // After the index is resident: for sparse indexes build the bucket summaries the fast seed kernel tests first.
 int refresh_summary(fem_dev *h) {
-  if (h->d_summary) (void)hipFree(h->d_summary);
-  h->d_summary = nullptr;
+  h->d_summary.release();
   const uint64_t n_buckets = h->n_lookup - 1;
   // dense index: nearly every bucket is non-empty, the tests would not pay.  (Fewer than 2^31 entries also keeps bit
   // 31 of a lookup value free: the fast seed kernel tags deferred lookups with it.)
   if (h->n_occ >= n_buckets || h->n_occ >= 0x80000000ull || (n_buckets >> 3) >= (1ull << 22)) return FEM_OK;
   const uint64_t words = n_buckets / femk::kSummaryBuckets + 2;
-  HIP_TRY(h, hipMalloc((void **)&h->d_summary, words * sizeof(uint32_t)));
+  HIP_TRY(h, h->d_summary.ensure(words));
   HIP_TRY(h, hipMemset(h->d_summary, 0, words * sizeof(uint32_t)));
   hipLaunchKernelGGL(femk::bucket_summary_kernel, dim3((uint32_t)h->n_cu * 8u), dim3(256), 0, 0, h->d_lookup, n_buckets, h->d_summary);
   HIP_TRY(h, hipGetLastError());
@@ -1107,10 +1020,11 @@ int refresh_summary(fem_dev *h) {
 // form of seed_fast_kernel runs instead) when the coordinates do not fit 32 bits.
 constexpr double kDenseMinAvgBucket = 4.0;
 int refresh_dense(fem_dev *h) {
-  for (void *p : {(void *)h->d_occ32, (void *)h->d_goff, (void *)h->d_blkseq, (void *)h->d_freq11, (void *)h->d_bank_lo})
-    if (p) (void)hipFree(p);
-  h->d_occ32 = nullptr, h->d_goff = nullptr, h->d_blkseq = nullptr, h->d_freq11 = nullptr, h->d_bank_lo = nullptr;
-  h->n_banks = 1, h->list_shift = 0;
+  auto drop = [&]() {
+    h->d_occ32.release(), h->d_goff.release(), h->d_blkseq.release(), h->d_freq11.release(), h->d_bank_lo.release();
+    h->n_banks = 1, h->list_shift = 0;
+  };
+  drop();
   if (!h->d_occ || !h->d_ref_raw || h->no_dense || h->k != femk::kK || h->step != femk::kStep || h->n_occ == 0) return FEM_OK;
   const uint64_t n_buckets = h->n_lookup - 1;
   if (!h->force_dense && (double)h->n_occ < kDenseMinAvgBucket * (double)n_buckets) return FEM_OK;
@@ -1154,12 +1068,9 @@ int refresh_dense(fem_dev *h) {
     }
   // These tables are optional (4 bytes per occurrence: 4 GB at 3 Gbp): a failed allocation declines the dense form —
   // the 64-bit hash-join form of seed_fast_kernel runs without them — instead of failing the upload.
-  uint32_t *d_bad = nullptr;
+  Buf<uint32_t> d_bad;
   auto decline = [&]() {
-    for (void *q : {(void *)h->d_occ32, (void *)h->d_goff, (void *)h->d_blkseq, (void *)h->d_freq11, (void *)h->d_bank_lo, (void *)d_bad})
-      if (q) (void)hipFree(q);
-    h->d_occ32 = nullptr, h->d_goff = nullptr, h->d_blkseq = nullptr, h->d_freq11 = nullptr, h->d_bank_lo = nullptr;
-    h->n_banks = 1, h->list_shift = 0;
+    drop();
     (void)hipGetLastError();  // (clears the out-of-memory error)
     return FEM_OK;
   };
@@ -1172,25 +1083,21 @@ int refresh_dense(fem_dev *h) {
   const bool strided_pays = h->force_dense || h->n_occ >= (n_buckets << 4);
   if (n_banks == 1 && !h->no_strided && strided_pays) {
     const size_t words = ((size_t)n_buckets + femk::kDensePadBuckets) << femk::kDenseListShift;
-    bool ok = hipMalloc((void **)&h->d_occ32, words * sizeof(uint32_t)) == hipSuccess;
+    bool ok = h->d_occ32.ensure(words) == hipSuccess;
     if (ok) {  // every slot reads "pad" (fem_seed_dense.hip.h) until dense_occ32_strided_kernel writes a bucket's entries over its first ones
-      hipLaunchKernelGGL(femk::dense_pad_kernel, dim3((uint32_t)h->n_cu * 16u), dim3(256), 0, 0, (uint4 *)h->d_occ32, (uint64_t)(words / 4));
+      hipLaunchKernelGGL(femk::dense_pad_kernel, dim3((uint32_t)h->n_cu * 16u), dim3(256), 0, 0, (uint4 *)h->d_occ32.get(), (uint64_t)(words / 4));
       ok = hipGetLastError() == hipSuccess;
     }
     if (ok) {
       list_shift = femk::kDenseListShift;
     } else {
-      if (h->d_occ32) (void)hipFree(h->d_occ32);
-      h->d_occ32 = nullptr;
+      h->d_occ32.release();
       (void)hipGetLastError();
     }
   }
-  if (hipMalloc((void **)&h->d_goff, goff.size() * sizeof(uint32_t)) != hipSuccess ||
-      hipMalloc((void **)&h->d_blkseq, blkseq.size() * sizeof(uint32_t)) != hipSuccess ||
-      (!list_shift && hipMalloc((void **)&h->d_occ32, (h->n_occ + 256) * sizeof(uint32_t)) != hipSuccess) ||
-      hipMalloc((void **)&h->d_freq11, (size_t)femk::kX11 * 4u * sizeof(uint32_t)) != hipSuccess ||
-      (n_banks > 1 && hipMalloc((void **)&h->d_bank_lo, (size_t)(n_banks - 1) * n_buckets * sizeof(uint32_t)) != hipSuccess) ||
-      hipMalloc((void **)&d_bad, sizeof(uint32_t)) != hipSuccess)
+  if (h->d_goff.ensure(goff.size()) != hipSuccess || h->d_blkseq.ensure(blkseq.size()) != hipSuccess ||
+      (!list_shift && h->d_occ32.ensure(h->n_occ + 256) != hipSuccess) || h->d_freq11.ensure((size_t)femk::kX11 * 4u) != hipSuccess ||
+      (n_banks > 1 && h->d_bank_lo.ensure((size_t)(n_banks - 1) * n_buckets) != hipSuccess) || d_bad.ensure(1) != hipSuccess)
     return decline();
   if (hipMemset(d_bad, 0, sizeof(uint32_t)) != hipSuccess ||
       hipMemcpy(h->d_goff, goff.data(), goff.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess ||
@@ -1213,8 +1120,7 @@ int refresh_dense(fem_dev *h) {
     return fail(h, FEM_ERR_HIP, "dense tables: building the 32-bit occurrence table failed");
   }
   if (bad) return decline();  // the index names sequences the reference does not have: leave that to the 64-bit path's checks
-  (void)hipFree(d_bad);
-  d_bad = nullptr;
+  d_bad.release();
   for (uint32_t b = 1; b < n_banks; ++b)  // where bank b's part of every list starts
     hipLaunchKernelGGL(femk::bank_split_kernel, dim3((uint32_t)h->n_cu * 8u), dim3(256), 0, 0, h->d_occ, h->d_lookup, (uint32_t)n_buckets, bank_first[b],
                        h->d_bank_lo + (size_t)(b - 1) * n_buckets);
@@ -1231,7 +1137,7 @@ int refresh_dense(fem_dev *h) {
 struct CommSet {
   std::vector<int> devs;
   std::vector<ncclComm_t> comms;
-  std::vector<uint64_t *> bufs;
+  std::vector<Buf<uint64_t>> bufs;
 };
 std::mutex g_comm_mu;
 CommSet *g_comm = nullptr;
@@ -1239,7 +1145,7 @@ void destroy_comm_set() {  // caller holds g_comm_mu
   if (!g_comm) return;
   for (size_t i = 0; i < g_comm->devs.size(); ++i) {
     (void)hipSetDevice(g_comm->devs[i]);
-    if (g_comm->bufs[i]) (void)hipFree(g_comm->bufs[i]);
+    g_comm->bufs[i].release();
     if (g_comm->comms[i]) ncclCommDestroy(g_comm->comms[i]);
   }
   delete g_comm;
@@ -1263,10 +1169,10 @@ int enqueue_packed(fem_dev *h, Slot &s, uint64_t n, uint32_t len, uint64_t n_exc
   const uint64_t code_bytes = fempack::code_bytes(n, len), n_bases = n * (uint64_t)len;
   const uint64_t total = code_bytes + n_exc * 5u;
   int rc;
-  if ((rc = dev_realloc(h, &s.d_packed_alloc, &s.packed_cap, kPackedFrontPad + (size_t)total + 64))) return rc;
-  if ((rc = dev_realloc(h, &s.d_bases_alloc, &s.bases_cap, kFrontPad + (size_t)n_bases + 64))) return rc;
-  if ((rc = dev_realloc(h, &s.d_off, &s.off_cap, (size_t)n + 1))) return rc;
-  if ((rc = dev_realloc(h, &s.d_exc_bits, &s.exc_bits_cap, (size_t)n / 32 + 2))) return rc;
+  HIP_TRY(h, s.d_packed_alloc.ensure(kPackedFrontPad + (size_t)total + 64));
+  HIP_TRY(h, s.d_bases_alloc.ensure(kFrontPad + (size_t)n_bases + 64));
+  HIP_TRY(h, s.d_off.ensure((size_t)n + 1));
+  HIP_TRY(h, s.d_exc_bits.ensure((size_t)n / 32 + 2));
   // parts: only where nothing is pending on the device (the start of a job), for batches without exceptions (their scatter
   // follows the whole batch) and of some size
   s.parts = 1;
@@ -1359,23 +1265,19 @@ int fem_dev_open(int device, fem_dev **out) {
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess) h->n_cu = prop.multiProcessorCount;
   for (int i = 0; i < kSlots; ++i) {
-    if (hipStreamCreateWithFlags(&h->slot[i].stream, hipStreamNonBlocking) != hipSuccess) {
+    if (h->slot[i].stream.create(hipStreamNonBlocking) != hipSuccess) {
       delete h;
       return FEM_ERR_HIP;
     }
   }
-  bool ok_ev = hipEventCreateWithFlags(&h->ev_kernels_done, hipEventDisableTiming) == hipSuccess &&
-               hipEventCreateWithFlags(&h->ev_select_done, hipEventDisableTiming) == hipSuccess &&
-               hipEventCreateWithFlags(&h->ev_h2d_done, hipEventDisableTiming) == hipSuccess &&
-               hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking) == hipSuccess;
+  bool ok_ev = h->ev_kernels_done.create(hipEventDisableTiming) == hipSuccess && h->ev_select_done.create(hipEventDisableTiming) == hipSuccess &&
+               h->ev_h2d_done.create(hipEventDisableTiming) == hipSuccess && h->side_stream.create(hipStreamNonBlocking) == hipSuccess;
   for (int i = 0; ok_ev && i < kSlots; ++i) {
     Slot &sl = h->slot[i];
-    ok_ev = hipEventCreateWithFlags(&sl.ev_zeroed, hipEventDisableTiming) == hipSuccess &&
-            hipEventCreateWithFlags(&sl.ev_results, hipEventDisableTiming) == hipSuccess &&
-            hipEventCreateWithFlags(&sl.ev_home, hipEventDisableTiming) == hipSuccess;
+    ok_ev = sl.ev_zeroed.create(hipEventDisableTiming) == hipSuccess && sl.ev_results.create(hipEventDisableTiming) == hipSuccess &&
+            sl.ev_home.create(hipEventDisableTiming) == hipSuccess;
     for (int q = 0; ok_ev && q < kMaxParts; ++q)
-      ok_ev = hipEventCreateWithFlags(&sl.ev_part[q], hipEventDisableTiming) == hipSuccess &&
-              hipEventCreateWithFlags(&sl.ev_sel[q], hipEventDisableTiming) == hipSuccess;
+      ok_ev = sl.ev_part[q].create(hipEventDisableTiming) == hipSuccess && sl.ev_sel[q].create(hipEventDisableTiming) == hipSuccess;
   }
   if (!ok_ev) {
     (void)fem_dev_close(h);
@@ -1388,7 +1290,7 @@ int fem_dev_open(int device, fem_dev **out) {
     h->no_parts = testing_switch("FEM_NO_PARTS");
     if (const char *mp = getenv("FEM_PARTS")) h->max_parts = std::min(kMaxParts, std::max(1, atoi(mp)));
     h->timeline = testing_switch("FEM_TIMELINE");
-    if (h->timeline && hipEventCreate(&h->ev_epoch) == hipSuccess && hipEventRecord(h->ev_epoch, h->side_stream) == hipSuccess)
+    if (h->timeline && h->ev_epoch.create() == hipSuccess && hipEventRecord(h->ev_epoch, h->side_stream) == hipSuccess)
       h->timing = true, h->have_epoch = true;  // (a process that never asks for timing, FEM map, is timed from its handle's opening)
     h->force_generic = testing_switch("FEM_FORCE_GENERIC");
     h->force_hash = testing_switch("FEM_FORCE_HASH");
@@ -1412,54 +1314,8 @@ int fem_dev_close(fem_dev *h) {
   }
   (void)hipSetDevice(h->device);
   (void)hipDeviceSynchronize();
-  delete h->stage_pool;
-  h->stage_pool = nullptr;
-  for (auto &s : h->slot) {
-    drain_timing(h, s);
-    for (void *p : {(void *)s.d_bases_alloc, (void *)s.d_off, (void *)s.d_cand, (void *)s.d_meta, (void *)s.d_ed,
-                    (void *)s.d_end, (void *)s.d_begin, (void *)s.d_count, (void *)s.d_nmap, (void *)s.d_ctl,
-                    (void *)s.d_arena, (void *)s.d_slow, (void *)s.d_sel, (void *)s.d_sel_hdr, (void *)s.d_packed_alloc, (void *)s.d_exc_bits, (void *)s.d_quals, (void *)s.d_names,
-                    (void *)s.d_name_off, (void *)s.d_count8, (void *)s.d_seg, (void *)s.d_pcand, (void *)s.d_ped, (void *)s.d_pend, (void *)s.d_big})
-      if (p) (void)hipFree(p);
-    for (void *p : {(void *)s.h_ctl, (void *)s.h_begin, (void *)s.h_count, (void *)s.h_cand, (void *)s.h_ed,
-                    (void *)s.h_end, (void *)s.h_bases, (void *)s.h_off, (void *)s.h_quals, (void *)s.h_names, (void *)s.h_name_off,
-                    (void *)s.h_count8, (void *)s.h_seg, (void *)s.h_pcand, (void *)s.h_ped, (void *)s.h_pend, (void *)s.h_big})
-      if (p) (void)hipHostFree(p);
-    if (s.stream) (void)hipStreamDestroy(s.stream);
-    if (s.text_stream) (void)hipStreamDestroy(s.text_stream);
-    if (s.out_stream) (void)hipStreamDestroy(s.out_stream);
-    if (s.ev_text_staged) (void)hipEventDestroy(s.ev_text_staged);
-    if (s.ev_text_order) (void)hipEventDestroy(s.ev_text_order);
-    delete s.tail;
-    s.tail = nullptr;
-  }
-  delete h->bgzf;
-  h->bgzf = nullptr;
-  if (h->d_zin) (void)hipFree(h->d_zin);
-  if (h->z_stream) (void)hipStreamDestroy(h->z_stream);
-  if (h->d_ref_names) (void)hipFree(h->d_ref_names);
-  if (h->d_ref_name_off) (void)hipFree(h->d_ref_name_off);
-  for (hipEvent_t e : h->event_pool) (void)hipEventDestroy(e);
-  if (h->ev_kernels_done) (void)hipEventDestroy(h->ev_kernels_done);
-  if (h->ev_select_done) (void)hipEventDestroy(h->ev_select_done);
-  if (h->ev_h2d_done) (void)hipEventDestroy(h->ev_h2d_done);
-  if (h->ev_epoch) (void)hipEventDestroy(h->ev_epoch);
-  if (h->side_stream) (void)hipStreamDestroy(h->side_stream);
-  for (int i = 0; i < kSlots; ++i) {
-    Slot &sl = h->slot[i];
-    if (sl.ev_zeroed) (void)hipEventDestroy(sl.ev_zeroed);
-    if (sl.ev_results) (void)hipEventDestroy(sl.ev_results);
-    if (sl.ev_home) (void)hipEventDestroy(sl.ev_home);
-    for (int q = 0; q < kMaxParts; ++q) {
-      if (sl.ev_part[q]) (void)hipEventDestroy(sl.ev_part[q]);
-      if (sl.ev_sel[q]) (void)hipEventDestroy(sl.ev_sel[q]);
-    }
-  }
-  for (void *p : {(void *)h->d_lookup, (void *)h->d_occ, (void *)h->d_ref_raw, (void *)h->d_seq_off,
-                  (void *)h->d_seq_len, (void *)h->d_summary, (void *)h->d_planes, (void *)h->d_occ32, (void *)h->d_goff, (void *)h->d_blkseq,
-                  (void *)h->d_freq11, (void *)h->d_bank_lo})
-    if (p) (void)hipFree(p);
-  delete h;
+  for (auto &s : h->slot) drain_timing(h, s);  // (the timing events go back to the pool)
+  delete h;  // every buffer, event and stream of the handle and its slots frees itself (fem_buf.hip.h)
   return FEM_OK;
 }
 
@@ -1477,11 +1333,9 @@ int fem_dev_upload_index(fem_dev *h, int32_t k, int32_t step, const uint32_t *lo
   if (n_lookup != (1ull << (2 * k)) + 1) return fail(h, FEM_ERR_INVALID, "lookup table must have 4^k + 1 entries");
   if (n_occ > 0xFFFFFFFFull) return fail(h, FEM_ERR_INVALID, "occurrence table larger than its uint32 prefix sums");
   HIP_TRY(h, hipSetDevice(h->device));
-  if (h->d_lookup) (void)hipFree(h->d_lookup);
-  if (h->d_occ) (void)hipFree(h->d_occ);
-  h->d_lookup = nullptr, h->d_occ = nullptr;
-  HIP_TRY(h, hipMalloc((void **)&h->d_lookup, n_lookup * sizeof(uint32_t)));
-  HIP_TRY(h, hipMalloc((void **)&h->d_occ, std::max<uint64_t>(n_occ, 1) * sizeof(uint64_t)));
+  h->d_lookup.release(), h->d_occ.release();
+  HIP_TRY(h, h->d_lookup.ensure(n_lookup));
+  HIP_TRY(h, h->d_occ.ensure(std::max<uint64_t>(n_occ, 1)));
   HIP_TRY(h, hipMemcpy(h->d_lookup, lookup, n_lookup * sizeof(uint32_t), hipMemcpyHostToDevice));
   if (n_occ) HIP_TRY(h, hipMemcpy(h->d_occ, occ, n_occ * sizeof(uint64_t), hipMemcpyHostToDevice));
   h->n_lookup = n_lookup, h->n_occ = n_occ, h->k = k, h->step = step;
@@ -1492,23 +1346,16 @@ int fem_dev_upload_index(fem_dev *h, int32_t k, int32_t step, const uint32_t *lo
 namespace {
 // The reference as base codes 0..4 (what the bit planes and the index build are made from) in a buffer of its own, from the
 // resident characters.  A temporary: nothing on the mapping path reads it, so it is not kept (3 GB at 3 Gbp).
-int make_codes(fem_dev *h, uint8_t **out) {
-  *out = nullptr;
-  uint8_t *codes = nullptr;
+int make_codes(fem_dev *h, Buf<uint8_t> *codes) {
   const uint64_t total = h->ref_bytes;
-  HIP_TRY(h, hipMalloc((void **)&codes, total + 128));
-  hipError_t e = hipMemcpy(codes, h->d_ref_raw, total, hipMemcpyDeviceToDevice);
-  if (e == hipSuccess) e = hipMemset(codes + total, 4, 128);
-  if (e == hipSuccess && total) {
-    hipLaunchKernelGGL(femk::ref_encode_kernel, dim3((uint32_t)h->n_cu * 8u), dim3(256), 0, 0, codes, total);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
+  HIP_TRY(h, codes->ensure(total + 128));
+  HIP_TRY(h, hipMemcpy(*codes, h->d_ref_raw, total, hipMemcpyDeviceToDevice));
+  HIP_TRY(h, hipMemset(*codes + total, 4, 128));
+  if (total) {
+    hipLaunchKernelGGL(femk::ref_encode_kernel, dim3((uint32_t)h->n_cu * 8u), dim3(256), 0, 0, codes->get(), total);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipDeviceSynchronize());
   }
-  if (e != hipSuccess) {
-    (void)hipFree(codes);
-    HIP_TRY(h, e);
-  }
-  *out = codes;
   return FEM_OK;
 }
 }  // namespace
@@ -1523,15 +1370,15 @@ int fem_dev_upload_reference(fem_dev *h, uint32_t n_seq, const char *const *seq,
     h->seq_off[i] = total;
     total += seq_len[i];
   }
-  for (void *p : {(void *)h->d_ref_raw, (void *)h->d_seq_off, (void *)h->d_seq_len, (void *)h->d_planes})
-    if (p) (void)hipFree(p);
-  h->d_ref_raw = nullptr, h->d_seq_off = nullptr, h->d_seq_len = nullptr;
-  h->d_planes = nullptr;
-  h->ref_bytes = 0, h->n_seq = 0;
+  auto drop_reference = [&]() {
+    h->d_ref_raw.release(), h->d_seq_off.release(), h->d_seq_len.release(), h->d_planes.release();
+    h->ref_bytes = 0, h->n_seq = 0;
+  };
+  drop_reference();
   // 64 bytes of slack so that 4-byte window reads at the very end stay inside the allocation
-  HIP_TRY(h, hipMalloc((void **)&h->d_ref_raw, total + 128));
-  HIP_TRY(h, hipMalloc((void **)&h->d_seq_off, n_seq * sizeof(uint64_t)));
-  HIP_TRY(h, hipMalloc((void **)&h->d_seq_len, n_seq * sizeof(uint32_t)));
+  HIP_TRY(h, h->d_ref_raw.ensure(total + 128));
+  HIP_TRY(h, h->d_seq_off.ensure(n_seq));
+  HIP_TRY(h, h->d_seq_len.ensure(n_seq));
   for (uint32_t i = 0; i < n_seq; ++i)
     if (seq_len[i]) HIP_TRY(h, hipMemcpy(h->d_ref_raw + h->seq_off[i], seq[i], seq_len[i], hipMemcpyHostToDevice));
   // (the slack zeroed, as the oracle pads its concatenation: a traceback whose 'S' fold walks past the last sequence reads it)
@@ -1543,27 +1390,20 @@ int fem_dev_upload_reference(fem_dev *h, uint32_t n_seq, const char *const *seq,
   {  // bit planes of the codes, 64 bases of slack (code 4) included; the codes themselves are not kept
     // (a failure from here on must not leave a reference without its planes behind: fem_dev_map_staged and
     //  fem_dev_build_index test d_ref_raw)
-    auto drop_reference = [&]() {
-      for (void *q : {(void *)h->d_ref_raw, (void *)h->d_seq_off, (void *)h->d_seq_len, (void *)h->d_planes})
-        if (q) (void)hipFree(q);
-      h->d_ref_raw = nullptr, h->d_seq_off = nullptr, h->d_seq_len = nullptr, h->d_planes = nullptr;
-      h->ref_bytes = 0, h->n_seq = 0;
-    };
-    uint8_t *codes = nullptr;
+    Buf<uint8_t> codes;
     int rc = make_codes(h, &codes);
     if (rc) {
       drop_reference();
       return rc;
     }
     const uint64_t n_pb = (total + 64 + 7) / 8;
-    hipError_t e = hipMalloc((void **)&h->d_planes, femk::plane_bytes(n_pb));
+    hipError_t e = h->d_planes.ensure(femk::plane_bytes(n_pb));
     if (e == hipSuccess) e = hipMemset(h->d_planes, 0, femk::plane_bytes(n_pb));
     if (e == hipSuccess) {
-      hipLaunchKernelGGL(femk::ref_planes_kernel, dim3((uint32_t)h->n_cu * 8u), dim3(256), 0, 0, codes, h->d_ref_raw, n_pb, h->d_planes);
+      hipLaunchKernelGGL(femk::ref_planes_kernel, dim3((uint32_t)h->n_cu * 8u), dim3(256), 0, 0, codes.get(), h->d_ref_raw.get(), n_pb, h->d_planes.get());
       e = hipGetLastError();
       if (e == hipSuccess) e = hipDeviceSynchronize();
     }
-    (void)hipFree(codes);
     if (e != hipSuccess) drop_reference();
     HIP_TRY(h, e);
   }
@@ -1576,16 +1416,14 @@ int fem_dev_build_index(fem_dev *h, int32_t k, int32_t step, uint32_t *lookup_ou
   if (!h->d_ref_raw) return fail(h, FEM_ERR_STATE, "upload the reference before building the index");
   if (k < 1 || k > 15 || step < 1) return fail(h, FEM_ERR_INVALID, "k must be 1..15 and step >= 1");
   HIP_TRY(h, hipSetDevice(h->device));
-  if (h->d_lookup) (void)hipFree(h->d_lookup);
-  if (h->d_occ) (void)hipFree(h->d_occ);
-  h->d_lookup = nullptr, h->d_occ = nullptr;
+  h->d_lookup.release(), h->d_occ.release();
   uint64_t n_occ = 0;
   std::string err;
-  uint8_t *codes = nullptr;  // (base codes of the reference: made for the build, not kept)
+  Buf<uint8_t> codes;  // (base codes of the reference: made for the build, not kept)
   int rc = make_codes(h, &codes);
   if (rc) return rc;
   rc = femix::build_index(codes, h->seq_off, h->seq_len, k, step, h->n_cu, &h->d_lookup, &h->d_occ, &n_occ, &err);
-  (void)hipFree(codes);
+  codes.release();
   if (rc != FEM_OK) return fail(h, rc, err);
   h->n_lookup = (1ull << (2 * k)) + 1, h->n_occ = n_occ, h->k = k, h->step = step;
   if ((rc = refresh_summary(h))) return rc;
@@ -1623,8 +1461,8 @@ int fem_dev_acquire_stage(fem_dev *h, int slot, uint64_t n_reads_cap, uint64_t n
   HIP_TRY(h, hipStreamSynchronize(s.stream));  // the previous batch's copy out of these buffers is done
   if (s.out_stream) HIP_TRY(h, hipStreamSynchronize(s.out_stream));  // ... and its records and text (they read the slot's device arrays)
   drain_timing(h, s);
-  if ((rc = pinned_realloc(h, &s.h_bases, &s.h_bases_cap, (size_t)n_bases_cap + 64))) return rc;
-  if ((rc = pinned_realloc(h, &s.h_off, &s.h_off_cap, (size_t)n_reads_cap + 1))) return rc;
+  HIP_TRY(h, s.h_bases.ensure((size_t)n_bases_cap + 64));
+  HIP_TRY(h, s.h_off.ensure((size_t)n_reads_cap + 1));
   s.staged = false, s.mapped = false, s.synced = false, s.text_staged = false;
   s.acq_reads = n_reads_cap, s.acq_bases = n_bases_cap;
   *bases = s.h_bases, *offsets = s.h_off;
@@ -1643,8 +1481,8 @@ int fem_dev_commit_stage(fem_dev *h, int slot, uint64_t n_reads, uint32_t max_le
   const uint64_t n_bases = n_reads ? s.h_off[n_reads] : 0;
   if (n_reads && (s.h_off[0] != 0 || n_bases > s.acq_bases)) return fail(h, FEM_ERR_INVALID, "staged offsets must start at 0 and end inside the buffer");
   HIP_TRY(h, hipSetDevice(h->device));
-  if ((rc = dev_realloc(h, &s.d_bases_alloc, &s.bases_cap, kFrontPad + (size_t)n_bases + 64))) return rc;
-  if ((rc = dev_realloc(h, &s.d_off, &s.off_cap, (size_t)n_reads + 1))) return rc;
+  HIP_TRY(h, s.d_bases_alloc.ensure(kFrontPad + (size_t)n_bases + 64));
+  HIP_TRY(h, s.d_off.ensure((size_t)n_reads + 1));
   if ((rc = h2d_begin(h, s))) return rc;
   if (n_bases) HIP_TRY(h, hipMemcpyAsync(s.bases(), s.h_bases, n_bases, hipMemcpyHostToDevice, s.stream));
   if (n_reads) HIP_TRY(h, hipMemcpyAsync(s.d_off, s.h_off, (n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s.stream));
@@ -1667,8 +1505,8 @@ int fem_dev_commit_stage_uniform(fem_dev *h, int slot, uint64_t n_reads, uint32_
   const uint64_t n_bases = n_reads * (uint64_t)read_len;
   if (n_reads > s.acq_reads || n_bases > s.acq_bases) return fail(h, FEM_ERR_INVALID, "more reads than the staging buffers were acquired for");
   HIP_TRY(h, hipSetDevice(h->device));
-  if ((rc = dev_realloc(h, &s.d_bases_alloc, &s.bases_cap, kFrontPad + (size_t)n_bases + 64))) return rc;
-  if ((rc = dev_realloc(h, &s.d_off, &s.off_cap, (size_t)n_reads + 1))) return rc;
+  HIP_TRY(h, s.d_bases_alloc.ensure(kFrontPad + (size_t)n_bases + 64));
+  HIP_TRY(h, s.d_off.ensure((size_t)n_reads + 1));
   if ((rc = h2d_begin(h, s))) return rc;
   if (n_bases) HIP_TRY(h, hipMemcpyAsync(s.bases(), s.h_bases, n_bases, hipMemcpyHostToDevice, s.stream));
   if ((rc = h2d_end(h, s))) return rc;
@@ -1732,7 +1570,7 @@ int fem_dev_stage_reads(fem_dev *h, int slot, const fem_read_batch *reads) {
   if ((rc = fem_dev_acquire_stage(h, slot, n, n_bases, &hb, &ho))) return rc;
   Slot &s = h->slot[slot];
   const unsigned n_thr = stage_threads(n);
-  if (!h->stage_pool) h->stage_pool = new (std::nothrow) StagePool();
+  if (!h->stage_pool) h->stage_pool.reset(new (std::nothrow) StagePool());
   if (!h->stage_pool) return fail(h, FEM_ERR_NOMEM, "out of host memory");
   auto run_threads = [&](unsigned nt, const std::function<void(unsigned)> &work) { h->stage_pool->run(nt, work); };
   // ---- pass 1 (a few host threads): order, longest and shortest read ----
@@ -1850,7 +1688,7 @@ int fem_dev_sync(fem_dev *h, int slot) {
     HIP_TRY(h, hipStreamSynchronize(s.stream));  // (without the handle's lock: other slots' calls go on meanwhile)
     FEM_LOCK(h);
     drain_timing(h, s);
-    const uint32_t *ctr = (const uint32_t *)s.h_ctl;
+    const uint32_t *ctr = (const uint32_t *)s.h_ctl.get();
     const uint64_t *arena_ctr = (const uint64_t *)(s.h_ctl + 4 * sizeof(uint32_t));
     const uint64_t *st = (const uint64_t *)(s.h_ctl + 4 * sizeof(uint32_t) + 2 * sizeof(uint64_t));
     uint32_t flags = ctr[1];
@@ -1874,19 +1712,15 @@ int fem_dev_sync(fem_dev *h, int slot) {
     }
     if (flags & femk::kFlagQueueOverflow) {
       uint64_t want = (uint64_t)ctr[2] + ctr[2] / 8 + 4096;
-      (void)hipFree(s.d_slow);
-      s.d_slow = nullptr;
+      s.d_slow.release();
       s.slow_cap = 0;
-      hipError_t e = hipMalloc((void **)&s.d_slow, want * sizeof(uint32_t));
-      if (e != hipSuccess) return fail(h, FEM_ERR_NOMEM, "slow-read queue does not fit in device memory");
+      if (s.d_slow.ensure(want) != hipSuccess) return fail(h, FEM_ERR_NOMEM, "slow-read queue does not fit in device memory");
       s.slow_cap = (uint32_t)std::min<uint64_t>(want, 0xFFFFFFF0ull);
     }
     if (flags & femk::kFlagArenaOverflow) {
       uint64_t want = arena_ctr[1] + arena_ctr[1] / 8 + 1024;
-      (void)hipFree(s.d_arena);
-      s.d_arena = nullptr;
-      hipError_t e = hipMalloc((void **)&s.d_arena, want * sizeof(uint64_t));
-      if (e != hipSuccess) {
+      s.d_arena.release();
+      if (s.d_arena.ensure(want) != hipSuccess) {
         s.arena_cap = 0;
         return fail(h, FEM_ERR_NOMEM, "scratch arena for oversized seed lists does not fit in device memory; use smaller batches");
       }
@@ -1912,27 +1746,13 @@ int fem_dev_fetch(fem_dev *h, int slot, fem_batch_result *out) {
   Slot &s = h->slot[slot];
   const size_t n2 = (size_t)s.n_reads * 2, nc = s.n_cand;
   bool regrown = false;
-  if (n2 > s.h_per_read_cap || !s.h_begin) {
+  if (n2 > s.h_begin.size() || !s.h_begin) {
     regrown = true;
-    size_t c0 = 0, c1 = 0;
-    if (s.h_begin) (void)hipHostFree(s.h_begin);
-    if (s.h_count) (void)hipHostFree(s.h_count);
-    s.h_begin = s.h_count = nullptr;
-    if ((rc = pinned_realloc(h, &s.h_begin, &c0, std::max<size_t>(n2, 2)))) return rc;
-    if ((rc = pinned_realloc(h, &s.h_count, &c1, std::max<size_t>(n2, 2)))) return rc;
-    s.h_per_read_cap = c0;
+    HIP_TRY(h, femb::alloc_all(std::max<size_t>(n2, 2), s.h_begin, s.h_count));
   }
-  if (nc > s.h_cand_cap || !s.h_cand) {
+  if (nc > s.h_cand.size() || !s.h_cand) {
     regrown = true;
-    size_t c0 = 0, c1 = 0, c2 = 0;
-    for (void *p : {(void *)s.h_cand, (void *)s.h_ed, (void *)s.h_end})
-      if (p) (void)hipHostFree(p);
-    s.h_cand = nullptr, s.h_ed = nullptr, s.h_end = nullptr;
-    size_t want = std::max<size_t>(nc + nc / 4, 1024);
-    if ((rc = pinned_realloc(h, &s.h_cand, &c0, want))) return rc;
-    if ((rc = pinned_realloc(h, &s.h_ed, &c1, want))) return rc;
-    if ((rc = pinned_realloc(h, &s.h_end, &c2, want))) return rc;
-    s.h_cand_cap = c0;
+    HIP_TRY(h, femb::alloc_all(std::max<size_t>(nc + nc / 4, 1024), s.h_cand, s.h_ed, s.h_end));
   }
   // what did not come home behind the kernels already (launch_batch; nothing did if a buffer was regrown just now)
   const bool per_read_home = !regrown && s.prefetched_reads2 == n2;
@@ -1971,17 +1791,9 @@ int fem_dev_fetch_packed(fem_dev *h, int slot, fem_batch_packed *out) {
   if (s.n_big > kBigCap) return fail(h, FEM_ERR_UNSUPPORTED, "more strands with 255 candidates and more than a packed result lists: use fem_dev_fetch");
   const size_t np = s.n_reads ? s.n_packed : 0;
   bool regrown = false;
-  if (np > s.h_pcand_cap || !s.h_pcand) {
+  if (np > s.h_pcand.size() || !s.h_pcand) {
     regrown = true;
-    for (void *q : {(void *)s.h_pcand, (void *)s.h_ped, (void *)s.h_pend})
-      if (q) (void)hipHostFree(q);
-    s.h_pcand = nullptr, s.h_ped = nullptr, s.h_pend = nullptr;
-    size_t c0 = 0, c1 = 0, c2 = 0;
-    const size_t want = std::max<size_t>(np + np / 4, 1024);
-    if ((rc = pinned_realloc(h, &s.h_pcand, &c0, want))) return rc;
-    if ((rc = pinned_realloc(h, &s.h_ped, &c1, want))) return rc;
-    if ((rc = pinned_realloc(h, &s.h_pend, &c2, want))) return rc;
-    s.h_pcand_cap = c0;
+    HIP_TRY(h, femb::alloc_all(std::max<size_t>(np + np / 4, 1024), s.h_pcand, s.h_ped, s.h_pend));
   }
   bool copied = false;
   if (n2 && !s.packed_per_read_home) {
@@ -2006,7 +1818,7 @@ int fem_dev_fetch_packed(fem_dev *h, int slot, fem_batch_packed *out) {
   out->n_candidates = np;
   out->count = s.h_count8, out->seg_begin = s.h_seg;
   out->cand = s.h_pcand, out->ed = s.h_ped, out->end = s.h_pend;
-  out->big = (const uint32_t *)s.h_big, out->n_big = s.n_big;
+  out->big = (const uint32_t *)s.h_big.get(), out->n_big = s.n_big;
   memcpy(out->stats, s.stats, sizeof s.stats);
   return FEM_OK;
 }
@@ -2021,11 +1833,9 @@ int fem_dev_upload_reference_names(fem_dev *h, uint32_t n_seq, const char *names
     if (name_off[i] < name_off[0] || (i && name_off[i] < name_off[i - 1])) return fail(h, FEM_ERR_INVALID, "name offsets must be ascending");
     off[i] = (uint32_t)(name_off[i] - name_off[0]);
   }
-  if (h->d_ref_names) (void)hipFree(h->d_ref_names);
-  if (h->d_ref_name_off) (void)hipFree(h->d_ref_name_off);
-  h->d_ref_names = nullptr, h->d_ref_name_off = nullptr;
-  HIP_TRY(h, hipMalloc((void **)&h->d_ref_names, std::max<size_t>(off[n_seq], 1)));
-  HIP_TRY(h, hipMalloc((void **)&h->d_ref_name_off, (n_seq + 1) * sizeof(uint32_t)));
+  h->d_ref_names.release(), h->d_ref_name_off.release();
+  HIP_TRY(h, h->d_ref_names.ensure(std::max<size_t>(off[n_seq], 1)));
+  HIP_TRY(h, h->d_ref_name_off.ensure(n_seq + 1));
   if (off[n_seq]) HIP_TRY(h, hipMemcpy(h->d_ref_names, names + name_off[0], off[n_seq], hipMemcpyHostToDevice));
   HIP_TRY(h, hipMemcpy(h->d_ref_name_off, off.data(), (n_seq + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
   return FEM_OK;
@@ -2042,9 +1852,9 @@ int fem_dev_acquire_text_stage(fem_dev *h, int slot, uint64_t n_reads_cap, uint6
   HIP_TRY(h, hipStreamSynchronize(s.stream));  // the previous batch's copies out of these buffers are done
   if (s.text_stream) HIP_TRY(h, hipStreamSynchronize(s.text_stream));
   if (s.out_stream) HIP_TRY(h, hipStreamSynchronize(s.out_stream));
-  if ((rc = pinned_realloc(h, &s.h_quals, &s.h_quals_cap, (size_t)n_bases_cap + 64))) return rc;
-  if ((rc = pinned_realloc(h, &s.h_names, &s.h_names_cap, (size_t)n_name_bytes_cap + 64))) return rc;
-  if ((rc = pinned_realloc(h, &s.h_name_off, &s.h_name_off_cap, (size_t)n_reads_cap + 1))) return rc;
+  HIP_TRY(h, s.h_quals.ensure((size_t)n_bases_cap + 64));
+  HIP_TRY(h, s.h_names.ensure((size_t)n_name_bytes_cap + 64));
+  HIP_TRY(h, s.h_name_off.ensure((size_t)n_reads_cap + 1));
   s.text_staged = false;
   *quals = s.h_quals, *names = s.h_names, *name_off = s.h_name_off;
   return FEM_OK;
@@ -2056,12 +1866,12 @@ int fem_dev_reserve_text(fem_dev *h, int slot, uint64_t n_reads, uint64_t n_base
   FEM_LOCK(h);
   Slot &s = h->slot[slot];
   HIP_TRY(h, hipSetDevice(h->device));
-  if ((rc = dev_realloc(h, &s.d_bases_alloc, &s.bases_cap, kFrontPad + (size_t)n_bases + 64))) return rc;
-  if ((rc = dev_realloc(h, &s.d_off, &s.off_cap, (size_t)n_reads + 1))) return rc;
-  if ((rc = dev_realloc(h, &s.d_quals, &s.d_quals_cap, (size_t)n_bases + 64))) return rc;
-  if ((rc = dev_realloc(h, &s.d_names, &s.d_names_cap, (size_t)n_name_bytes + 64))) return rc;
-  if ((rc = dev_realloc(h, &s.d_name_off, &s.d_name_off_cap, (size_t)n_reads + 1))) return rc;
-  if (!s.tail) s.tail = new (std::nothrow) femt::Tail();
+  HIP_TRY(h, s.d_bases_alloc.ensure(kFrontPad + (size_t)n_bases + 64));
+  HIP_TRY(h, s.d_off.ensure((size_t)n_reads + 1));
+  HIP_TRY(h, s.d_quals.ensure((size_t)n_bases + 64));
+  HIP_TRY(h, s.d_names.ensure((size_t)n_name_bytes + 64));
+  HIP_TRY(h, s.d_name_off.ensure((size_t)n_reads + 1));
+  if (!s.tail) s.tail.reset(new (std::nothrow) femt::Tail());
   if (!s.tail) return fail(h, FEM_ERR_NOMEM, "out of host memory");
   std::string err;
   if ((rc = s.tail->reserve_text(text_bytes, &err))) return fail(h, rc, err);
@@ -2078,9 +1888,8 @@ static hipStream_t out_stream_of(fem_dev *h, Slot &s) {
   if (plain) return s.stream;
   if (!s.out_stream) {
     int least = 0, greatest = 0;
-    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess ||
-        hipStreamCreateWithPriority(&s.out_stream, hipStreamNonBlocking, greatest) != hipSuccess)
-      s.out_stream = nullptr;
+    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess || s.out_stream.create(hipStreamNonBlocking, greatest) != hipSuccess)
+      s.out_stream.s = nullptr;
   }
   (void)h;
   return s.out_stream ? s.out_stream : s.stream;
@@ -2104,31 +1913,31 @@ int fem_dev_reserve_batch(fem_dev *h, int slot, uint64_t n_reads, uint64_t n_rec
   s.n_reads = n_was;
   if (rc) return rc;
   const uint64_t n_bases = n_reads * (uint64_t)max_len;
-  if ((rc = dev_realloc(h, &s.d_packed_alloc, &s.packed_cap, kPackedFrontPad + (size_t)fempack::code_bytes(n_reads, max_len) + 64))) return rc;
-  if ((rc = dev_realloc(h, &s.d_bases_alloc, &s.bases_cap, kFrontPad + (size_t)n_bases + 64))) return rc;
-  if ((rc = dev_realloc(h, &s.d_off, &s.off_cap, (size_t)n_reads + 1))) return rc;
-  if ((rc = dev_realloc(h, &s.d_exc_bits, &s.exc_bits_cap, (size_t)n_reads / 32 + 2))) return rc;
+  HIP_TRY(h, s.d_packed_alloc.ensure(kPackedFrontPad + (size_t)fempack::code_bytes(n_reads, max_len) + 64));
+  HIP_TRY(h, s.d_bases_alloc.ensure(kFrontPad + (size_t)n_bases + 64));
+  HIP_TRY(h, s.d_off.ensure((size_t)n_reads + 1));
+  HIP_TRY(h, s.d_exc_bits.ensure((size_t)n_reads / 32 + 2));
   if (h->d_occ32 && h->d_freq11 && p->k == 12 && p->step == 3) {  // dense index: the selection's hand-over to the join
     const size_t R = (size_t)(p->e + 1 + p->a);
-    if ((rc = dev_realloc(h, &s.d_sel, &s.sel_cap, (size_t)n_reads * 6u * R * h->n_banks))) return rc;
-    if ((rc = dev_realloc(h, &s.d_sel_hdr, &s.sel_hdr_cap, (size_t)n_reads))) return rc;
+    HIP_TRY(h, s.d_sel.ensure((size_t)n_reads * 6u * R * h->n_banks));
+    HIP_TRY(h, s.d_sel_hdr.ensure((size_t)n_reads));
   }
   // the mapping tail and the SAM text's bookkeeping
-  if (!s.tail) s.tail = new (std::nothrow) femt::Tail();
+  if (!s.tail) s.tail.reset(new (std::nothrow) femt::Tail());
   if (!s.tail) return fail(h, FEM_ERR_NOMEM, "out of host memory");
   std::string err;
   if ((rc = s.tail->reserve((uint32_t)n_reads, (uint32_t)n_records, max_len, p->e, h->tiny_buffers, &err))) return fail(h, rc, err);
   // first uses: the slot's streams (a stream's queue is made by its first command) and the tail's code object
-  if (!s.text_stream) HIP_TRY(h, hipStreamCreateWithFlags(&s.text_stream, hipStreamNonBlocking));
-  HIP_TRY(h, hipMemsetAsync(s.d_sel_hdr ? (void *)s.d_sel_hdr : (void *)s.d_off, 0, 8, s.text_stream));
+  if (!s.text_stream) HIP_TRY(h, s.text_stream.create(hipStreamNonBlocking));
+  HIP_TRY(h, hipMemsetAsync(s.d_sel_hdr ? (void *)s.d_sel_hdr.get() : (void *)s.d_off.get(), 0, 8, s.text_stream));
   HIP_TRY(h, hipStreamSynchronize(s.text_stream));
   HIP_TRY(h, hipMemsetAsync(s.d_off, 0, 8, h->side_stream));
   HIP_TRY(h, hipStreamSynchronize(h->side_stream));
   // ... and the copy paths a batch takes, in both directions, from and to the buffers it will use
   const size_t probe = 1u << 20;
-  if (s.h_bases && s.h_bases_cap >= probe && s.bases_cap >= kFrontPad + probe)
+  if (s.h_bases && s.h_bases.size() >= probe && s.d_bases_alloc.size() >= kFrontPad + probe)
     HIP_TRY(h, hipMemcpyAsync(s.d_bases_alloc + kFrontPad, s.h_bases, probe, hipMemcpyHostToDevice, s.stream));
-  if (s.h_quals && s.d_quals && s.h_quals_cap >= probe && s.d_quals_cap >= probe)
+  if (s.h_quals && s.d_quals && s.h_quals.size() >= probe && s.d_quals.size() >= probe)
     HIP_TRY(h, hipMemcpyAsync(s.d_quals, s.h_quals, probe, hipMemcpyHostToDevice, s.text_stream));
   HIP_TRY(h, hipMemcpyAsync(s.h_ctl, s.d_ctl, kCtlBytes, hipMemcpyDeviceToHost, s.stream));
   HIP_TRY(h, hipStreamSynchronize(s.text_stream));
@@ -2145,18 +1954,18 @@ static int commit_text(fem_dev *h, int slot, uint64_t n_reads, uint64_t n_name_b
   if (!s.staged) return fail(h, FEM_ERR_STATE, "commit the reads of the batch first");
   if ((with_quals && !s.h_quals) || !s.h_names || !s.h_name_off) return fail(h, FEM_ERR_STATE, "acquire the slot's text staging buffers first");
   if (n_reads != s.n_reads) return fail(h, FEM_ERR_INVALID, "as many names as reads, please");
-  if ((with_quals && s.n_bases + 64 > s.h_quals_cap) || n_name_bytes + 64 > s.h_names_cap || n_reads + 1 > s.h_name_off_cap)
+  if ((with_quals && s.n_bases + 64 > s.h_quals.size()) || n_name_bytes + 64 > s.h_names.size() || n_reads + 1 > s.h_name_off.size())
     return fail(h, FEM_ERR_INVALID, "more qualities or names than the text staging buffers were acquired for");
   if (n_reads && (s.h_name_off[0] != 0 || s.h_name_off[n_reads] != n_name_bytes))
     return fail(h, FEM_ERR_INVALID, "name offsets must start at 0 and end at the number of name bytes");
   HIP_TRY(h, hipSetDevice(h->device));
-  if (with_quals && (rc = dev_realloc(h, &s.d_quals, &s.d_quals_cap, (size_t)s.n_bases + 64))) return rc;
-  if ((rc = dev_realloc(h, &s.d_names, &s.d_names_cap, (size_t)n_name_bytes + 64))) return rc;
-  if ((rc = dev_realloc(h, &s.d_name_off, &s.d_name_off_cap, (size_t)n_reads + 1))) return rc;
+  if (with_quals) HIP_TRY(h, s.d_quals.ensure((size_t)s.n_bases + 64));
+  HIP_TRY(h, s.d_names.ensure((size_t)n_name_bytes + 64));
+  HIP_TRY(h, s.d_name_off.ensure((size_t)n_reads + 1));
   // On a stream of their own: nothing before the SAM text reads them, and on the slot's stream these copies (1.25 times the
   // characters of the reads: 2.5 ms per million 100-bp reads) stood between the batch's reads and its first kernel.
-  if (!s.text_stream) HIP_TRY(h, hipStreamCreateWithFlags(&s.text_stream, hipStreamNonBlocking));
-  if (!s.ev_text_staged) HIP_TRY(h, hipEventCreateWithFlags(&s.ev_text_staged, hipEventDisableTiming));
+  if (!s.text_stream) HIP_TRY(h, s.text_stream.create(hipStreamNonBlocking));
+  HIP_TRY(h, s.ev_text_staged.create(hipEventDisableTiming));
   // (the slot's previous batch may still be rendering its text out of the same arrays)
   if (s.have_text_order) HIP_TRY(h, hipStreamWaitEvent(s.text_stream, s.ev_text_order, 0));
   if (with_quals && s.n_bases) HIP_TRY(h, hipMemcpyAsync(s.d_quals, s.h_quals, s.n_bases, hipMemcpyHostToDevice, s.text_stream));
@@ -2245,7 +2054,7 @@ static int tail_records(fem_dev *h, int slot, const void *out, bool copy_records
   if (device_quals && s.host_quals) return fail(h, FEM_ERR_STATE, "BAM records need the qualities on the device (fem_dev_commit_text_stage, not _names_stage)");
   if (text && !h->d_ref_names) return fail(h, FEM_ERR_STATE, "reference names must be uploaded first (fem_dev_upload_reference_names)");
   s.prefetch_results = false;  // this caller takes records, not the per-candidate arrays
-  if (!s.tail) s.tail = new (std::nothrow) femt::Tail();
+  if (!s.tail) s.tail.reset(new (std::nothrow) femt::Tail());
   if (!s.tail) return fail(h, FEM_ERR_NOMEM, "out of host memory");
   f->in = tail_input(h, s);
   if (paired && (s.n_reads & 1)) return fail(h, FEM_ERR_INVALID, "a batch of read pairs holds an even number of reads");
@@ -2281,7 +2090,7 @@ static int text_done(fem_dev *h, int slot, const TailFront &f, const char *tag, 
   s.n_unmapped = s.tail->n_unmapped();
   s.n_filtered = s.tail->n_filtered();
   const bool report = s.report_strata >= 0 || s.report_hits >= 1;
-  if (!s.ev_text_order) HIP_TRY(h, hipEventCreateWithFlags(&s.ev_text_order, hipEventDisableTiming));
+  HIP_TRY(h, s.ev_text_order.create(hipEventDisableTiming));
   HIP_TRY(h, hipEventRecord(s.ev_text_order, f.stream));
   s.have_text_order = true;
   static const bool trace_host = testing_switch("FEM_FETCH_TIMES");  // host time of the call's three stretches, on stderr
@@ -2360,15 +2169,10 @@ int fem_dev_bgzf_compress(fem_dev *h, const void *in, uint64_t n, int level, voi
   *out_len = 0;
   if (!n) return FEM_OK;
   HIP_TRY(h, hipSetDevice(h->device));
-  if (!h->bgzf) h->bgzf = new (std::nothrow) femz::Bgzf();
+  if (!h->bgzf) h->bgzf.reset(new (std::nothrow) femz::Bgzf());
   if (!h->bgzf) return fail(h, FEM_ERR_NOMEM, "out of host memory");
-  if (!h->z_stream) HIP_TRY(h, hipStreamCreateWithFlags(&h->z_stream, hipStreamNonBlocking));
-  if (h->d_zin_cap < n) {
-    if (h->d_zin) (void)hipFree(h->d_zin);
-    h->d_zin = nullptr, h->d_zin_cap = 0;
-    HIP_TRY(h, hipMalloc((void **)&h->d_zin, (size_t)n));
-    h->d_zin_cap = (size_t)n;
-  }
+  if (!h->z_stream) HIP_TRY(h, h->z_stream.create(hipStreamNonBlocking));
+  HIP_TRY(h, h->d_zin.ensure((size_t)n));
   HIP_TRY(h, hipMemcpyAsync(h->d_zin, in, (size_t)n, hipMemcpyHostToDevice, h->z_stream));
   std::vector<uint64_t> starts;
   femz::bgzf_cut(nullptr, 0, n, &starts);
@@ -2572,15 +2376,11 @@ const char *fem_dev_seed_kernel(const fem_dev *h, const fem_params *p) {
 int fem_dev_set_timing(fem_dev *h, int on) {
   if (!h) return FEM_ERR_INVALID;
   h->timing = on != 0;
-  if (h->timing && h->event_pool.size() < 64) {
+  if (h->timing && h->event_pool.idle.size() < 64) {
     // the events of a few batches in flight, made now: created one by one inside the first timed launches they cost those
     // launches a millisecond each (the pipeline of bench.py was visibly slower over its first steps)
     HIP_TRY(h, hipSetDevice(h->device));
-    while (h->event_pool.size() < 64) {
-      hipEvent_t e = nullptr;
-      HIP_TRY(h, hipEventCreate(&e));
-      h->event_pool.push_back(e);
-    }
+    HIP_TRY(h, h->event_pool.fill(64));
   }
   return FEM_OK;
 }
@@ -2590,7 +2390,7 @@ int fem_dev_reset_timing(fem_dev *h) {
   for (int i = 0; i < kTimedKernels; ++i) h->t_ms[i] = 0, h->t_n[i] = 0;
   if (h->timeline) {
     HIP_TRY(h, hipSetDevice(h->device));
-    if (!h->ev_epoch) HIP_TRY(h, hipEventCreate(&h->ev_epoch));
+    HIP_TRY(h, h->ev_epoch.create());
     HIP_TRY(h, hipEventRecord(h->ev_epoch, h->side_stream));
     h->have_epoch = true;
   }
@@ -2607,14 +2407,11 @@ int fem_dev_kernel_time(fem_dev *h, int kernel, double *ms_total, uint64_t *laun
 int fem_dev_copy_bandwidth(fem_dev *h, uint64_t bytes, int iters, double *gb_per_s) {
   if (!h || !gb_per_s || bytes == 0 || iters <= 0) return FEM_ERR_INVALID;
   HIP_TRY(h, hipSetDevice(h->device));
-  void *a = nullptr, *b = nullptr;
-  HIP_TRY(h, hipMalloc(&a, bytes));
-  if (hipMalloc(&b, bytes) != hipSuccess) {
-    (void)hipFree(a);
-    return fail(h, FEM_ERR_NOMEM, "copy bandwidth probe: out of memory");
-  }
+  Buf<uint8_t> a, b;
+  HIP_TRY(h, a.ensure(bytes));
+  if (b.ensure(bytes) != hipSuccess) return fail(h, FEM_ERR_NOMEM, "copy bandwidth probe: out of memory");
   hipStream_t st = h->slot[0].stream;
-  hipEvent_t e0 = get_event(h), e1 = get_event(h);
+  hipEvent_t e0 = h->event_pool.get(), e1 = h->event_pool.get();
   (void)hipMemsetAsync(a, 1, bytes, st);
   (void)hipMemcpyAsync(b, a, bytes, hipMemcpyDeviceToDevice, st);
   (void)hipEventRecord(e0, st);
@@ -2623,10 +2420,8 @@ int fem_dev_copy_bandwidth(fem_dev *h, uint64_t bytes, int iters, double *gb_per
   hipError_t e = hipStreamSynchronize(st);
   float ms = 0.f;
   (void)hipEventElapsedTime(&ms, e0, e1);
-  h->event_pool.push_back(e0);
-  h->event_pool.push_back(e1);
-  (void)hipFree(a);
-  (void)hipFree(b);
+  h->event_pool.put(e0);
+  h->event_pool.put(e1);
   if (e != hipSuccess) return fail(h, FEM_ERR_HIP, hipGetErrorString(e));
   *gb_per_s = ms > 0 ? (2.0 * (double)bytes * iters) / (ms * 1e6) : 0.0;  // read + write
   return FEM_OK;
@@ -2635,15 +2430,13 @@ int fem_dev_copy_bandwidth(fem_dev *h, uint64_t bytes, int iters, double *gb_per
 int fem_dev_h2d_bandwidth(fem_dev *h, uint64_t bytes, int iters, double *gb_per_s) {
   if (!h || !gb_per_s || bytes == 0 || iters <= 0) return FEM_ERR_INVALID;
   HIP_TRY(h, hipSetDevice(h->device));
-  void *a = nullptr, *b = nullptr;
-  HIP_TRY(h, hipHostMalloc(&a, bytes, hipHostMallocDefault));
-  if (hipMalloc(&b, bytes) != hipSuccess) {
-    (void)hipHostFree(a);
-    return fail(h, FEM_ERR_NOMEM, "h2d bandwidth probe: out of memory");
-  }
+  PinBuf<uint8_t> a;
+  Buf<uint8_t> b;
+  HIP_TRY(h, a.ensure(bytes));
+  if (b.ensure(bytes) != hipSuccess) return fail(h, FEM_ERR_NOMEM, "h2d bandwidth probe: out of memory");
   memset(a, 1, bytes);
   hipStream_t st = h->slot[0].stream;
-  hipEvent_t e0 = get_event(h), e1 = get_event(h);
+  hipEvent_t e0 = h->event_pool.get(), e1 = h->event_pool.get();
   (void)hipMemcpyAsync(b, a, bytes, hipMemcpyHostToDevice, st);
   (void)hipEventRecord(e0, st);
   for (int i = 0; i < iters; ++i) (void)hipMemcpyAsync(b, a, bytes, hipMemcpyHostToDevice, st);
@@ -2651,10 +2444,8 @@ int fem_dev_h2d_bandwidth(fem_dev *h, uint64_t bytes, int iters, double *gb_per_
   hipError_t e = hipStreamSynchronize(st);
   float ms = 0.f;
   (void)hipEventElapsedTime(&ms, e0, e1);
-  h->event_pool.push_back(e0);
-  h->event_pool.push_back(e1);
-  (void)hipHostFree(a);
-  (void)hipFree(b);
+  h->event_pool.put(e0);
+  h->event_pool.put(e1);
   if (e != hipSuccess) return fail(h, FEM_ERR_HIP, hipGetErrorString(e));
   *gb_per_s = ms > 0 ? ((double)bytes * iters) / (ms * 1e6) : 0.0;
   return FEM_OK;
@@ -2671,6 +2462,14 @@ int fem_dbg_stamps(uint64_t *out, int n) {
   return 0;
 }
 #endif
+
+// Bytes of device and pinned host memory the library's buffers hold right now, over all handles of the process (the tests'
+// check that a closed handle has given everything back).
+int fem_dbg_live_bytes(uint64_t *device_bytes, uint64_t *pinned_bytes) {
+  if (device_bytes) *device_bytes = femb::g_live_bytes[(int)femb::Mem::Device].load(std::memory_order_relaxed);
+  if (pinned_bytes) *pinned_bytes = femb::g_live_bytes[(int)femb::Mem::Pinned].load(std::memory_order_relaxed);
+  return FEM_OK;
+}
 
 // ---- host placement ----
 // The pinned staging buffers are what the GPU's copy engines read: they should sit in the memory of the socket the GPU
@@ -2747,14 +2546,14 @@ int fem_dev_allreduce_stats(fem_dev *const *hs, int n, uint64_t *stats) {
     if (!cs) return fail(h0, FEM_ERR_NOMEM, "out of host memory");
     cs->devs = devs;
     cs->comms.assign(n, nullptr);
-    cs->bufs.assign(n, nullptr);
+    cs->bufs.resize(n);
     if (ncclCommInitAll(cs->comms.data(), n, devs.data()) != ncclSuccess) {
       delete cs;
       return fail(h0, FEM_ERR_RCCL, "ncclCommInitAll failed");
     }
     g_comm = cs;
     for (int i = 0; i < n; ++i)
-      if (hipSetDevice(devs[i]) != hipSuccess || hipMalloc((void **)&cs->bufs[i], 5 * sizeof(uint64_t)) != hipSuccess) {
+      if (hipSetDevice(devs[i]) != hipSuccess || cs->bufs[i].ensure(5) != hipSuccess) {
         destroy_comm_set();
         return fail(h0, FEM_ERR_HIP, "allreduce: allocating the counter buffers failed");
       }
@@ -2770,7 +2569,7 @@ int fem_dev_allreduce_stats(fem_dev *const *hs, int n, uint64_t *stats) {
     ncclGroupStart();
     for (int i = 0; i < n; ++i) {
       (void)hipSetDevice(devs[i]);
-      if (ncclAllReduce(cs.bufs[i], cs.bufs[i], 5, ncclUint64, ncclSum, cs.comms[i], hs[i]->slot[0].stream) != ncclSuccess)
+      if (ncclAllReduce(cs.bufs[i].get(), cs.bufs[i].get(), 5, ncclUint64, ncclSum, cs.comms[i], hs[i]->slot[0].stream) != ncclSuccess)
         rc = fail(h0, FEM_ERR_RCCL, "ncclAllReduce failed");
     }
     if (ncclGroupEnd() != ncclSuccess) rc = fail(h0, FEM_ERR_RCCL, "ncclGroupEnd failed");

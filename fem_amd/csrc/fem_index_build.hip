@@ -56,65 +56,56 @@ __global__ void hash_entries_kernel(const uint8_t *ref, SeqTable t, uint64_t n, 
     hipError_t e_ = (expr);                                                     \
     if (e_ != hipSuccess) {                                                     \
       *err = std::string(#expr) + ": " + hipGetErrorString(e_);                 \
-      rc = e_ == hipErrorOutOfMemory ? FEM_ERR_NOMEM : FEM_ERR_HIP;             \
-      goto done;                                                                \
+      return e_ == hipErrorOutOfMemory ? FEM_ERR_NOMEM : FEM_ERR_HIP;           \
     }                                                                           \
   } while (0)
 
 }  // namespace
 
 int build_index(const uint8_t *d_ref, const std::vector<uint64_t> &seq_off, const std::vector<uint32_t> &seq_len, int k,
-                int step, int n_cu, uint32_t **d_lookup_out, uint64_t **d_occ_out, uint64_t *n_occ_out,
+                int step, int n_cu, femb::Buf<uint32_t> *d_lookup_out, femb::Buf<uint64_t> *d_occ_out, uint64_t *n_occ_out,
                 std::string *err) {
-  int rc = FEM_OK;
+  d_lookup_out->release(), d_occ_out->release();
   const uint32_t n_seq = (uint32_t)seq_len.size();
   std::vector<uint64_t> entry_off(n_seq + 1, 0);
   for (uint32_t s = 0; s < n_seq; ++s)  // positions 0, step, 2*step, ... while pos + k - 1 < len (src/index.c:65)
     entry_off[s + 1] = entry_off[s] + (seq_len[s] >= (uint32_t)k ? (uint64_t)(seq_len[s] - k) / step + 1 : 0);
   const uint64_t n = entry_off[n_seq];
   const size_t n_lookup = ((size_t)1 << (2 * k)) + 1;
-  uint64_t *d_entry_off = nullptr, *d_seq_off = nullptr, *d_vals = nullptr, *d_occ = nullptr;
-  uint32_t *d_keys = nullptr, *d_keys2 = nullptr, *d_lookup = nullptr;
-  void *d_tmp = nullptr;
+  femb::Buf<uint64_t> d_entry_off, d_seq_off, d_vals, d_occ;  // (what an early return leaves here is freed with them)
+  femb::Buf<uint32_t> d_keys, d_keys2, d_lookup;
+  femb::Buf<uint8_t> d_tmp;
   size_t tmp_bytes = 0, tmp2 = 0;
   if (n > 0xFFFFFFFFull) {
     *err = "reference yields more than 2^32 index entries (lookup table is uint32)";
     return FEM_ERR_UNSUPPORTED;
   }
-  IX_TRY(hipMalloc((void **)&d_lookup, n_lookup * sizeof(uint32_t)));
+  IX_TRY(d_lookup.ensure(n_lookup));
   IX_TRY(hipMemset(d_lookup, 0, n_lookup * sizeof(uint32_t)));
-  IX_TRY(hipMalloc((void **)&d_occ, (n ? n : 1) * sizeof(uint64_t)));
+  IX_TRY(d_occ.ensure(n ? n : 1));
   if (n) {
-    IX_TRY(hipMalloc((void **)&d_entry_off, (n_seq + 1) * sizeof(uint64_t)));
-    IX_TRY(hipMalloc((void **)&d_seq_off, n_seq * sizeof(uint64_t)));
+    IX_TRY(d_entry_off.ensure(n_seq + 1));
+    IX_TRY(d_seq_off.ensure(n_seq));
     IX_TRY(hipMemcpy(d_entry_off, entry_off.data(), (n_seq + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
     IX_TRY(hipMemcpy(d_seq_off, seq_off.data(), n_seq * sizeof(uint64_t), hipMemcpyHostToDevice));
-    IX_TRY(hipMalloc((void **)&d_keys, n * sizeof(uint32_t)));
-    IX_TRY(hipMalloc((void **)&d_keys2, n * sizeof(uint32_t)));
-    IX_TRY(hipMalloc((void **)&d_vals, n * sizeof(uint64_t)));
+    IX_TRY(d_keys.ensure(n));
+    IX_TRY(d_keys2.ensure(n));
+    IX_TRY(d_vals.ensure(n));
     SeqTable t{d_entry_off, d_seq_off, n_seq};
     hipLaunchKernelGGL(hash_entries_kernel, dim3((uint32_t)n_cu * 8u), dim3(256), 0, 0, d_ref, t, n, k, step, d_keys,
                        d_vals, d_lookup + 1);
     IX_TRY(hipGetLastError());
     // lookup[i] = number of entries with hash < i: inclusive scan over the shifted histogram
-    IX_TRY(rocprim::inclusive_scan(nullptr, tmp_bytes, d_lookup, d_lookup, n_lookup, rocprim::plus<uint32_t>()));
-    IX_TRY(rocprim::radix_sort_pairs(nullptr, tmp2, d_keys, d_keys2, d_vals, d_occ, (size_t)n, 0u, (unsigned)(2 * k)));
+    IX_TRY(rocprim::inclusive_scan(nullptr, tmp_bytes, d_lookup.get(), d_lookup.get(), n_lookup, rocprim::plus<uint32_t>()));
+    IX_TRY(rocprim::radix_sort_pairs(nullptr, tmp2, d_keys.get(), d_keys2.get(), d_vals.get(), d_occ.get(), (size_t)n, 0u, (unsigned)(2 * k)));
     tmp_bytes = tmp_bytes > tmp2 ? tmp_bytes : tmp2;
-    IX_TRY(hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 1));
-    IX_TRY(rocprim::inclusive_scan(d_tmp, tmp_bytes, d_lookup, d_lookup, n_lookup, rocprim::plus<uint32_t>()));
-    IX_TRY(rocprim::radix_sort_pairs(d_tmp, tmp_bytes, d_keys, d_keys2, d_vals, d_occ, (size_t)n, 0u, (unsigned)(2 * k)));
+    IX_TRY(d_tmp.ensure(tmp_bytes ? tmp_bytes : 1));
+    IX_TRY(rocprim::inclusive_scan(d_tmp.get(), tmp_bytes, d_lookup.get(), d_lookup.get(), n_lookup, rocprim::plus<uint32_t>()));
+    IX_TRY(rocprim::radix_sort_pairs(d_tmp.get(), tmp_bytes, d_keys.get(), d_keys2.get(), d_vals.get(), d_occ.get(), (size_t)n, 0u, (unsigned)(2 * k)));
     IX_TRY(hipDeviceSynchronize());
   }
-done:
-  for (void *p : {(void *)d_entry_off, (void *)d_seq_off, (void *)d_vals, (void *)d_keys, (void *)d_keys2, d_tmp})
-    if (p) (void)hipFree(p);
-  if (rc != FEM_OK) {
-    if (d_lookup) (void)hipFree(d_lookup);
-    if (d_occ) (void)hipFree(d_occ);
-    return rc;
-  }
-  *d_lookup_out = d_lookup;
-  *d_occ_out = d_occ;
+  *d_lookup_out = std::move(d_lookup);
+  *d_occ_out = std::move(d_occ);
   *n_occ_out = n;
   return FEM_OK;
 }

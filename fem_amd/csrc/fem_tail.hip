@@ -2,6 +2,7 @@
 // See fem_tail.hip.h for what is computed and the reference lines it follows.
 #include "fem_tail.hip.h"
 #include "fem_bgzf.hip.h"
+#include "fem_buf.hip.h"
 #include "fem_planes.hip.h"
 
 #include <cstring>  // before rocprim: its headers use memcpy unqualified
@@ -1082,50 +1083,11 @@ struct TriplePlus {  // component-wise sum of (kept, runs, MD length) triples (m
   }
 };
 
-// ---- host-side buffer helpers: device memory (DevBuf) or pinned host memory (PinBuf), freed with the object ----
-struct DevBuf {
-  void *p = nullptr;
-  size_t cap = 0;
-  bool pinned = false;
-  DevBuf() = default;
-  DevBuf(const DevBuf &) = delete;
-  DevBuf &operator=(const DevBuf &) = delete;
-  ~DevBuf() { release(); }
-  hipError_t need(size_t bytes) {
-    if (bytes <= cap && p) return hipSuccess;
-    release();
-    const size_t want = std::max<size_t>(bytes + bytes / 4, 256);
-    hipError_t e = pinned ? hipHostMalloc(&p, want, hipHostMallocDefault) : hipMalloc(&p, want);
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  void release() {
-    if (p) (void)(pinned ? hipHostFree(p) : hipFree(p));
-    p = nullptr, cap = 0;
-  }
-  template <typename T>
-  T *as() const { return (T *)p; }
-  // need() that keeps the first `used` bytes (waits for `stream` when it has to move them; device memory only)
-  hipError_t grow(size_t bytes, size_t used, hipStream_t stream) {
-    if (bytes <= cap && p) return hipSuccess;
-    const size_t want = std::max<size_t>(bytes + bytes / 4, 256);
-    void *q = nullptr;
-    hipError_t e = hipMalloc(&q, want);
-    if (e != hipSuccess) return e;
-    if (p && used) e = hipMemcpyAsync(q, p, used, hipMemcpyDeviceToDevice, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) {
-      (void)hipFree(q);
-      return e;
-    }
-    release();
-    p = q, cap = want;
-    return hipSuccess;
-  }
-};
-struct PinBuf : DevBuf {
-  PinBuf() { pinned = true; }
-};
+// The tail's buffers (fem_buf.hip.h): a quarter more than asked for, freed with the object.
+template <typename T>
+using DevBuf = femb::Buf<T, femb::Mem::Device, femb::Grow::Quarter>;
+template <typename T>
+using PinBuf = femb::Buf<T, femb::Mem::Pinned, femb::Grow::Quarter>;
 
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2415,24 +2377,40 @@ __global__ void __launch_bounds__(256) rescue_append_kernel(RescueParams p) {
   } while (0)
 
 struct Tail::Impl {
-  DevBuf rec_begin, queue, ctl, u_cand, u_misc, s_cand, s_misc, s_read, t_ops, t_md, o_ops, o_md, ovf, rec_list, src_slot, n_ops, n_md,
-      flag, tid, pos0, nm, cigar_off, md_off, cigar, md, scan_tmp;
-  DevBuf line_len, line_off, text, qual_at;
-  PinBuf h_ctl, h_rec_begin, h_flag, h_tid, h_pos0, h_nm, h_cigar_off, h_md_off, h_cigar, h_md, h_text, h_qual_at;
+  DevBuf<uint32_t> rec_begin, queue, ctl, u_misc, s_misc, s_read, t_ops, o_ops, ovf, rec_list, src_slot, n_ops, n_md, tid, pos0, cigar_off, md_off, cigar;
+  DevBuf<uint64_t> u_cand, s_cand;
+  DevBuf<uint8_t> t_md, o_md, nm, md, scan_tmp;
+  DevBuf<uint16_t> flag;
+  DevBuf<unsigned long long> line_len, line_off, qual_at;
+  DevBuf<uint8_t> text;
+  PinBuf<uint32_t> h_ctl, h_rec_begin, h_tid, h_pos0, h_cigar_off, h_md_off, h_cigar;
+  PinBuf<uint16_t> h_flag;
+  PinBuf<uint8_t> h_nm;
+  PinBuf<char> h_md, h_text;
+  PinBuf<uint64_t> h_qual_at;
   // pair mode (pair()): per line, the pairs' line ranges, the proper-pair counter; their host copies (pair_fetch())
-  DevBuf perm, pflag, mtid, mpos0, tlen, pair_begin, pair_ctl;
+  DevBuf<uint32_t> perm, mtid, mpos0, pair_begin, pair_ctl;
+  DevBuf<uint16_t> pflag;
+  DevBuf<int32_t> tlen;
   // MAPQ (SamInput::mapq): per read (single-end), per line (pair(): pair_kernel<true>'s bytes, then the MAPQ)
-  DevBuf q_read, lmq;
+  DevBuf<uint8_t> q_read, lmq;
   // lines for unmapped reads (SamInput::unmapped): the marks, their scan, each line's source, the line count
   // (the line filter, SamInput::strata / max_hits, uses the same four: its counts, their scan, the sources, the line count)
-  DevBuf u_cnt, u_before, usrc, u_ctl;
-  PinBuf h_perm, h_pflag, h_mtid, h_mpos0, h_tlen, h_pair_begin, h_pair_ctl;
+  DevBuf<uint32_t> u_cnt, u_before, usrc, u_ctl;
+  PinBuf<uint32_t> h_perm, h_mtid, h_mpos0, h_pair_begin, h_pair_ctl;
+  PinBuf<uint16_t> h_pflag;
+  PinBuf<int32_t> h_tlen;
   // mate rescue (pair() with a RescueInput): candidates, jobs, best hits, the tracebacks' staging, the kept flags and their scans
-  DevBuf r_ctl, r_cand, r_jobs, r_best, r_ops, r_md, r_rec, r_ovf, r_o_ops, r_o_md, r_kept, r_scan, r_scan_tmp;
-  PinBuf h_r_ctl, h_r_flag, h_r_tid, h_r_pos0, h_r_nm, h_r_cigar_off, h_r_cigar, h_r_md_off, h_r_md;
+  DevBuf<uint32_t> r_ctl, r_cand, r_jobs, r_ops, r_rec, r_ovf, r_o_ops, r_kept, r_scan;
+  DevBuf<unsigned long long> r_best;
+  DevBuf<uint8_t> r_md, r_o_md, r_scan_tmp;
+  PinBuf<uint32_t> h_r_ctl, h_r_tid, h_r_pos0, h_r_cigar_off, h_r_cigar, h_r_md_off;
+  PinBuf<uint16_t> h_r_flag;
+  PinBuf<uint8_t> h_r_nm;
+  PinBuf<char> h_r_md;
   // BAM (bam()): the name check, the record offsets home (the member cuts), the compressor
-  DevBuf bam_ctl;
-  PinBuf h_line_off;
+  DevBuf<uint32_t> bam_ctl;
+  PinBuf<uint64_t> h_line_off;
   femz::Bgzf bgzf;
   std::vector<uint64_t> cuts;
   uint32_t last_n = 0, last_nr = 0;  // what the last run() left on the device
@@ -2446,17 +2424,8 @@ struct Tail::Impl {
   bool rep_timed = false;            // the last text's filter kernels ran between ev_rep[0] and ev_rep[1]
   uint32_t n_base_last = 0;          // the lines the last text had before the filter and without the unmapped reads'
   uint32_t n_filtered = 0;           // lines the filter left out of the last text
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t ev_pair[2] = {nullptr, nullptr};
-  hipEvent_t ev_resc[2] = {nullptr, nullptr};
-  hipEvent_t ev_mapq[2] = {nullptr, nullptr};
-  hipEvent_t ev_unm[2] = {nullptr, nullptr};
-  hipEvent_t ev_rep[2] = {nullptr, nullptr};
-  hipEvent_t ev_text = nullptr;  // the SAM text has arrived in h_text
-  ~Impl() {  // (the buffers free themselves)
-    for (hipEvent_t e : {ev[0], ev[1], ev[2], ev[3], ev_pair[0], ev_pair[1], ev_resc[0], ev_resc[1], ev_mapq[0], ev_mapq[1], ev_unm[0], ev_unm[1], ev_rep[0], ev_rep[1], ev_text})
-      if (e) (void)hipEventDestroy(e);
-  }
+  femb::Event ev[4], ev_pair[2], ev_resc[2], ev_mapq[2], ev_unm[2], ev_rep[2];
+  femb::Event ev_text;  // the SAM text has arrived in h_text
   // sam() and bam(): the lines of run()'s records, or of pair()'s (rescued records included).  Fills *p (all but the text and
   // qual_at); names.mapq: first the MAPQ kernel (between ev_mapq[0] and ev_mapq[1]); from ev[0] on, each line's length (bad_name:
   // as BAM, a name over 254 characters setting it; else as SAM), their scan into line_off, the count of asserted records to h_ctl[2].
@@ -2481,80 +2450,77 @@ struct Tail::Impl {
     const uint32_t nr = n_base + (names.unmapped ? last_n : 0u);
     const size_t r1 = (size_t)nr + 1, n1 = (size_t)last_n + 1;
     const bool report = names.strata >= 0 || names.max_hits >= 1;
-    for (hipEvent_t &e : ev)
-      if (!e) TAIL_TRY(hipEventCreate(&e));
-    TAIL_TRY(line_len.need(r1 * 8));
-    TAIL_TRY(line_off.need(r1 * 8));
-    TAIL_TRY(h_ctl.need(48));
+    for (femb::Event &e : ev) TAIL_TRY(e.create());
+    TAIL_TRY(line_len.ensure(r1));
+    TAIL_TRY(line_off.ensure(r1));
+    TAIL_TRY(h_ctl.ensure(12));
     size_t tmp = 0, tmp_u = 0;
-    TAIL_TRY(rocprim::exclusive_scan(nullptr, tmp, line_len.as<unsigned long long>(), line_off.as<unsigned long long>(), 0ull, r1,
+    TAIL_TRY(rocprim::exclusive_scan(nullptr, tmp, line_len.get(), line_off.get(), 0ull, r1,
                                      rocprim::plus<unsigned long long>(), stream));
     if (names.unmapped || report) {
-      TAIL_TRY(u_cnt.need(n1 * 4));
-      TAIL_TRY(u_before.need(n1 * 4));
-      TAIL_TRY(usrc.need(std::max<size_t>(nr, 1) * 4));
-      TAIL_TRY(u_ctl.need(16));
-      TAIL_TRY(rocprim::exclusive_scan(nullptr, tmp_u, u_cnt.as<uint32_t>(), u_before.as<uint32_t>(), 0u, n1, rocprim::plus<uint32_t>(), stream));
+      TAIL_TRY(u_cnt.ensure(n1));
+      TAIL_TRY(u_before.ensure(n1));
+      TAIL_TRY(usrc.ensure(std::max<size_t>(nr, 1)));
+      TAIL_TRY(u_ctl.ensure(4));
+      TAIL_TRY(rocprim::exclusive_scan(nullptr, tmp_u, u_cnt.get(), u_before.get(), 0u, n1, rocprim::plus<uint32_t>(), stream));
     }
-    TAIL_TRY(scan_tmp.need(std::max<size_t>(std::max(tmp, tmp_u), 16)));
-    p->n_records = nr, p->rec_begin = rec_begin.as<uint32_t>(), p->s_read = s_read.as<uint32_t>();
-    p->flag = flag.as<uint16_t>(), p->tid = tid.as<uint32_t>(), p->pos0 = pos0.as<uint32_t>(), p->nm = nm.as<uint8_t>();
-    p->cigar_off = cigar_off.as<uint32_t>(), p->cigar = cigar.as<uint32_t>(), p->md_off = md_off.as<uint32_t>(), p->md = md.as<uint8_t>();
+    TAIL_TRY(scan_tmp.ensure(std::max<size_t>(std::max(tmp, tmp_u), 16)));
+    p->n_records = nr, p->rec_begin = rec_begin, p->s_read = s_read;
+    p->flag = flag, p->tid = tid, p->pos0 = pos0, p->nm = nm;
+    p->cigar_off = cigar_off, p->cigar = cigar, p->md_off = md_off, p->md = md;
     p->bases = in.bases, p->read_off = in.read_off;
     p->quals = names.quals, p->names = names.names, p->name_off = names.name_off, p->ref_names = names.ref_names, p->ref_name_off = names.ref_name_off;
-    p->line_len = line_len.as<unsigned long long>(), p->line_off = line_off.as<unsigned long long>();
-    p->asserted = ctl.as<uint32_t>() + 2;  // (ctl[2] is zero after a successful run())
+    p->line_len = line_len, p->line_off = line_off;
+    p->asserted = ctl + 2;  // (ctl[2] is zero after a successful run())
     if (pair_order) {
-      p->perm = perm.as<uint32_t>(), p->pflag = pflag.as<uint16_t>(), p->mtid = mtid.as<uint32_t>(), p->mpos0 = mpos0.as<uint32_t>();
-      p->tlen = tlen.as<int32_t>();
+      p->perm = perm, p->pflag = pflag, p->mtid = mtid, p->mpos0 = mpos0;
+      p->tlen = tlen;
     }
     unm_timed = false, n_unm = 0;
     rep_timed = false, n_filtered = 0, n_base_last = n_base;
     if (report) {
-      for (hipEvent_t &e : ev_rep)
-        if (!e) TAIL_TRY(hipEventCreate(&e));
+      for (femb::Event &e : ev_rep) TAIL_TRY(e.create());
       ReportParams f{};
-      f.n_reads = last_n, f.n_base = n_base, f.begin = pair_order ? pair_begin.as<uint32_t>() : rec_begin.as<uint32_t>();
-      f.nm = nm.as<uint8_t>(), f.perm = pair_order ? perm.as<uint32_t>() : nullptr;
+      f.n_reads = last_n, f.n_base = n_base, f.begin = pair_order ? pair_begin : rec_begin;
+      f.nm = nm, f.perm = pair_order ? perm : nullptr;
       f.strata = names.strata >= 0 ? (uint32_t)names.strata : kReportOff, f.max_hits = names.max_hits >= 1 ? (uint32_t)names.max_hits : kReportOff;
       f.unmapped = names.unmapped ? 1u : 0u;
-      f.cnt = u_cnt.as<uint32_t>(), f.before = u_before.as<uint32_t>(), f.usrc = usrc.as<uint32_t>(), f.n_lines = u_ctl.as<uint32_t>();
+      f.cnt = u_cnt, f.before = u_before, f.usrc = usrc, f.n_lines = u_ctl;
       const dim3 grid((last_n + 256u) / 256u);
       TAIL_TRY(hipEventRecord(ev_rep[0], stream));
-      TAIL_TRY(hipMemsetAsync(u_ctl.p, 0, 8, stream));
+      TAIL_TRY(hipMemsetAsync(u_ctl, 0, 8, stream));
       hipLaunchKernelGGL(report_kernel<false>, grid, dim3(256), 0, stream, f);
       TAIL_TRY(hipGetLastError());
-      size_t tmp_bytes = scan_tmp.cap;
-      TAIL_TRY(rocprim::exclusive_scan(scan_tmp.p, tmp_bytes, u_cnt.as<uint32_t>(), u_before.as<uint32_t>(), 0u, n1, rocprim::plus<uint32_t>(), stream));
+      size_t tmp_bytes = scan_tmp.bytes();
+      TAIL_TRY(rocprim::exclusive_scan(scan_tmp.get(), tmp_bytes, u_cnt.get(), u_before.get(), 0u, n1, rocprim::plus<uint32_t>(), stream));
       hipLaunchKernelGGL(report_kernel<true>, grid, dim3(256), 0, stream, f);
       TAIL_TRY(hipGetLastError());
       TAIL_TRY(hipEventRecord(ev_rep[1], stream));
-      TAIL_TRY(hipMemcpyAsync(h_ctl.as<uint32_t>() + 8, u_ctl.p, 8, hipMemcpyDeviceToHost, stream));
+      TAIL_TRY(hipMemcpyAsync(h_ctl + 8, u_ctl, 8, hipMemcpyDeviceToHost, stream));
       rep_timed = true;
-      p->usrc = usrc.as<uint32_t>(), p->u_base = names.unmapped ? n_base : kNoMate, p->n_reads = last_n, p->u_lines = u_ctl.as<uint32_t>();
-      p->pair_begin = names.unmapped ? pair_begin.as<uint32_t>() : nullptr;
+      p->usrc = usrc, p->u_base = names.unmapped ? n_base : kNoMate, p->n_reads = last_n, p->u_lines = u_ctl;
+      p->pair_begin = names.unmapped ? pair_begin : nullptr;
     } else if (names.unmapped) {
-      for (hipEvent_t &e : ev_unm)
-        if (!e) TAIL_TRY(hipEventCreate(&e));
+      for (femb::Event &e : ev_unm) TAIL_TRY(e.create());
       UlineParams u{};
       u.n_reads = last_n, u.n_base = n_base, u.paired = pair_order ? 1u : 0u;
-      u.begin = pair_order ? pair_begin.as<uint32_t>() : rec_begin.as<uint32_t>();
-      u.s_read = s_read.as<uint32_t>(), u.perm = perm.as<uint32_t>();
-      u.cnt = u_cnt.as<uint32_t>(), u.before = u_before.as<uint32_t>(), u.usrc = usrc.as<uint32_t>(), u.n_lines = u_ctl.as<uint32_t>();
+      u.begin = pair_order ? pair_begin : rec_begin;
+      u.s_read = s_read, u.perm = perm;
+      u.cnt = u_cnt, u.before = u_before, u.usrc = usrc, u.n_lines = u_ctl;
       TAIL_TRY(hipEventRecord(ev_unm[0], stream));
       hipLaunchKernelGGL(unmapped_mark_kernel, dim3((last_n + 256u) / 256u), dim3(256), 0, stream, u);
       TAIL_TRY(hipGetLastError());
-      size_t tmp_bytes = scan_tmp.cap;
-      TAIL_TRY(rocprim::exclusive_scan(scan_tmp.p, tmp_bytes, u_cnt.as<uint32_t>(), u_before.as<uint32_t>(), 0u, n1, rocprim::plus<uint32_t>(), stream));
+      size_t tmp_bytes = scan_tmp.bytes();
+      TAIL_TRY(rocprim::exclusive_scan(scan_tmp.get(), tmp_bytes, u_cnt.get(), u_before.get(), 0u, n1, rocprim::plus<uint32_t>(), stream));
       const uint32_t work = std::max(n_base, last_n);
       hipLaunchKernelGGL(unmapped_src_kernel, dim3(std::max<uint32_t>(1u, std::min<uint32_t>((work + 255u) / 256u, (uint32_t)n_cu * 16u))),
                          dim3(256), 0, stream, u);
       TAIL_TRY(hipGetLastError());
       TAIL_TRY(hipEventRecord(ev_unm[1], stream));
-      TAIL_TRY(hipMemcpyAsync(h_ctl.as<uint32_t>() + 8, u_ctl.p, 4, hipMemcpyDeviceToHost, stream));
+      TAIL_TRY(hipMemcpyAsync(h_ctl + 8, u_ctl, 4, hipMemcpyDeviceToHost, stream));
       unm_timed = true;
-      p->usrc = usrc.as<uint32_t>(), p->u_base = n_base, p->n_reads = last_n, p->u_lines = u_ctl.as<uint32_t>();
-      p->pair_begin = pair_begin.as<uint32_t>();
+      p->usrc = usrc, p->u_base = n_base, p->n_reads = last_n, p->u_lines = u_ctl;
+      p->pair_begin = pair_begin;
     }
     mapq_timed = false;
     if (names.mapq) {
@@ -2562,18 +2528,17 @@ struct Tail::Impl {
         if (err) *err = "the records were paired without MAPQ (Tail::pair)";
         return FEM_ERR_STATE;
       }
-      for (hipEvent_t &e : ev_mapq)
-        if (!e) TAIL_TRY(hipEventCreate(&e));
+      for (femb::Event &e : ev_mapq) TAIL_TRY(e.create());
       MapqParams q{};
-      q.n_reads = last_n, q.e = in.e, q.rec_begin = rec_begin.as<uint32_t>(), q.nm = nm.as<uint8_t>();
+      q.n_reads = last_n, q.e = in.e, q.rec_begin = rec_begin, q.nm = nm;
       if (pair_order) {
-        q.pair_begin = pair_begin.as<uint32_t>(), q.lmq = lmq.as<uint8_t>();
-        p->mapq = lmq.as<uint8_t>();
+        q.pair_begin = pair_begin, q.lmq = lmq;
+        p->mapq = lmq;
         pair_mapq = false;  // (made MAPQ in place: once)
       } else {
-        TAIL_TRY(q_read.need(std::max<size_t>(last_n, 1)));
-        q.q_read = q_read.as<uint8_t>();
-        p->mapq = q_read.as<uint8_t>();
+        TAIL_TRY(q_read.ensure(std::max<size_t>(last_n, 1)));
+        q.q_read = q_read;
+        p->mapq = q_read;
       }
       TAIL_TRY(hipEventRecord(ev_mapq[0], stream));
       if (last_n) {
@@ -2594,20 +2559,21 @@ struct Tail::Impl {
       hipLaunchKernelGGL(um ? (pair_order ? sam_len_kernel<true, true> : sam_len_kernel<false, true>)
                             : (pair_order ? sam_len_kernel<true> : sam_len_kernel<false>), len_grid, dim3(256), 0, stream, *p);
     TAIL_TRY(hipGetLastError());
-    TAIL_TRY(rocprim::exclusive_scan(scan_tmp.p, scan_tmp.cap, line_len.as<unsigned long long>(), line_off.as<unsigned long long>(), 0ull,
+    size_t tmp_bytes = scan_tmp.bytes();
+    TAIL_TRY(rocprim::exclusive_scan(scan_tmp.get(), tmp_bytes, line_len.get(), line_off.get(), 0ull,
                                      r1, rocprim::plus<unsigned long long>(), stream));
-    TAIL_TRY(hipMemcpyAsync(h_ctl.as<uint32_t>() + 2, ctl.as<uint32_t>() + 2, 4, hipMemcpyDeviceToHost, stream));
+    TAIL_TRY(hipMemcpyAsync(h_ctl + 2, ctl + 2, 4, hipMemcpyDeviceToHost, stream));
     return FEM_OK;
   }
   // after lines() and a wait for its stream: the number of lines (into p->n_records, which bounded it), n_unm
   uint32_t counted(const SamInput &names, SamParams *p) {
     if (rep_timed) {  // (the filter: what it kept, the unmapped reads' lines among them)
-      const uint32_t n_lines = std::min(h_ctl.as<uint32_t>()[8], p->n_records);
-      n_unm = names.unmapped ? std::min(h_ctl.as<uint32_t>()[9], n_lines) : 0u;
+      const uint32_t n_lines = std::min(h_ctl[8], p->n_records);
+      n_unm = names.unmapped ? std::min(h_ctl[9], n_lines) : 0u;
       n_filtered = n_base_last + n_unm - n_lines;
       p->n_records = n_lines;
     } else if (names.unmapped) {
-      const uint32_t n_lines = std::min(h_ctl.as<uint32_t>()[8], p->n_records);
+      const uint32_t n_lines = std::min(h_ctl[8], p->n_records);
       n_unm = n_lines - p->u_base;
       p->n_records = n_lines;
     }
@@ -2618,7 +2584,7 @@ struct Tail::Impl {
   // that took the gate before (TextGate), ev_text its arrival; wait: until then.  ms += ev[0]..ev[1] (the stream has passed ev[1]).
   int send_home(const void *src, size_t bytes, void *dst2, const void *src2, size_t bytes2, hipStream_t stream, bool wait, TextGate *gate,
                   double *ms, std::string *err) {
-    if (!ev_text) TAIL_TRY(hipEventCreateWithFlags(&ev_text, hipEventDisableTiming));
+    TAIL_TRY(ev_text.create(hipEventDisableTiming));
     static const bool no_gate = getenv("FEM_TESTING") && getenv("FEM_TEXT_NO_GATE");  // (A/B)
     if (no_gate) gate = nullptr;
     {
@@ -2629,7 +2595,7 @@ struct Tail::Impl {
       }
       // (by the copy engine.  The shader cores' stores into the pinned buffer — no engine to queue in — bring a text home in 7-9.5
       //  ms where the engine takes 5.4, and FEM map from 130 to 117 Mreads/s.)
-      if (bytes) TAIL_TRY(hipMemcpyAsync(h_text.p, src, bytes, hipMemcpyDeviceToHost, stream));
+      if (bytes) TAIL_TRY(hipMemcpyAsync(h_text, src, bytes, hipMemcpyDeviceToHost, stream));
       if (bytes2) TAIL_TRY(hipMemcpyAsync(dst2, src2, bytes2, hipMemcpyDeviceToHost, stream));
       TAIL_TRY(hipEventRecord(ev_text, stream));
       if (gate) gate->last = ev_text;
@@ -2653,49 +2619,48 @@ int Tail::reserve(uint32_t n, uint32_t nr, uint32_t max_len_in, int e, bool tiny
   const uint32_t fast_ops = std::min<uint32_t>(kOpsCap, 2u * (uint32_t)e + 2u);
   const uint32_t ops_cap = tiny ? 1u : std::max<uint32_t>(8u, fast_ops), md_cap = tiny ? 2u : kMdCap;
   (void)max_len_in;
-  TAIL_TRY(m.rec_begin.need(((size_t)n + 1) * 4));
-  TAIL_TRY(m.queue.need(std::max<size_t>(n, 1) * 4));
-  TAIL_TRY(m.ctl.need(16));
-  TAIL_TRY(m.h_ctl.need(48));
+  TAIL_TRY(m.rec_begin.ensure((size_t)n + 1));
+  TAIL_TRY(m.queue.ensure(std::max<size_t>(n, 1)));
+  TAIL_TRY(m.ctl.ensure(4));
+  TAIL_TRY(m.h_ctl.ensure(12));
   const size_t r1 = (size_t)nr + 1;
-  TAIL_TRY(m.u_cand.need(r1 * 8));
-  TAIL_TRY(m.u_misc.need(r1 * 4));
-  TAIL_TRY(m.s_cand.need(r1 * 8));
-  TAIL_TRY(m.s_misc.need(r1 * 4));
-  TAIL_TRY(m.s_read.need(r1 * 4));
-  TAIL_TRY(m.t_ops.need(r1 * ops_cap * 4));
-  TAIL_TRY(m.t_md.need(r1 * std::max<uint32_t>(md_cap, 12)));  // doubles as the ordering scratch (8 + 4 bytes per hit)
-  TAIL_TRY(m.ovf.need(r1 * 4));
-  TAIL_TRY(m.rec_list.need(r1 * 4));
-  TAIL_TRY(m.src_slot.need(r1 * 4));
-  TAIL_TRY(m.n_ops.need(r1 * 4));
-  TAIL_TRY(m.n_md.need(r1 * 4));
-  TAIL_TRY(m.flag.need(r1 * 2));
-  TAIL_TRY(m.tid.need(r1 * 4));
-  TAIL_TRY(m.pos0.need(r1 * 4));
-  TAIL_TRY(m.nm.need(r1));
-  TAIL_TRY(m.cigar_off.need(r1 * 4));
-  TAIL_TRY(m.md_off.need(r1 * 4));
-  TAIL_TRY(m.cigar.need(std::max<size_t>((size_t)nr * ops_cap, 1) * 4));
-  TAIL_TRY(m.md.need(std::max<size_t>((size_t)nr * md_cap, 1)));
-  TAIL_TRY(m.line_len.need(r1 * 8));
-  TAIL_TRY(m.line_off.need(r1 * 8));
-  TAIL_TRY(m.qual_at.need(((size_t)n + 1) * 8));
-  TAIL_TRY(m.h_qual_at.need(((size_t)n + 1) * 8));
+  TAIL_TRY(m.u_cand.ensure(r1));
+  TAIL_TRY(m.u_misc.ensure(r1));
+  TAIL_TRY(m.s_cand.ensure(r1));
+  TAIL_TRY(m.s_misc.ensure(r1));
+  TAIL_TRY(m.s_read.ensure(r1));
+  TAIL_TRY(m.t_ops.ensure(r1 * ops_cap));
+  TAIL_TRY(m.t_md.ensure(r1 * std::max<uint32_t>(md_cap, 12)));  // doubles as the ordering scratch (8 + 4 bytes per hit)
+  TAIL_TRY(m.ovf.ensure(r1));
+  TAIL_TRY(m.rec_list.ensure(r1));
+  TAIL_TRY(m.src_slot.ensure(r1));
+  TAIL_TRY(m.n_ops.ensure(r1));
+  TAIL_TRY(m.n_md.ensure(r1));
+  TAIL_TRY(m.flag.ensure(r1));
+  TAIL_TRY(m.tid.ensure(r1));
+  TAIL_TRY(m.pos0.ensure(r1));
+  TAIL_TRY(m.nm.ensure(r1));
+  TAIL_TRY(m.cigar_off.ensure(r1));
+  TAIL_TRY(m.md_off.ensure(r1));
+  TAIL_TRY(m.cigar.ensure(std::max<size_t>((size_t)nr * ops_cap, 1)));
+  TAIL_TRY(m.md.ensure(std::max<size_t>((size_t)nr * md_cap, 1)));
+  TAIL_TRY(m.line_len.ensure(r1));
+  TAIL_TRY(m.line_off.ensure(r1));
+  TAIL_TRY(m.qual_at.ensure((size_t)n + 1));
+  TAIL_TRY(m.h_qual_at.ensure((size_t)n + 1));
   size_t tmp_a = 0, tmp_b = 0, tmp_c = 0;
-  TAIL_TRY(rocprim::exclusive_scan(nullptr, tmp_a, (const uint32_t *)nullptr, m.rec_begin.as<uint32_t>(), 0u, (size_t)n,
+  TAIL_TRY(rocprim::exclusive_scan(nullptr, tmp_a, (const uint32_t *)nullptr, m.rec_begin.get(), 0u, (size_t)n,
                                    rocprim::plus<uint32_t>(), (hipStream_t) nullptr));
   {
-    auto lens = rocprim::make_zip_iterator(rocprim::make_tuple(m.n_ops.as<uint32_t>(), m.n_md.as<uint32_t>()));
-    auto offs = rocprim::make_zip_iterator(rocprim::make_tuple(m.cigar_off.as<uint32_t>(), m.md_off.as<uint32_t>()));
+    auto lens = rocprim::make_zip_iterator(rocprim::make_tuple(m.n_ops.get(), m.n_md.get()));
+    auto offs = rocprim::make_zip_iterator(rocprim::make_tuple(m.cigar_off.get(), m.md_off.get()));
     TAIL_TRY(rocprim::exclusive_scan(nullptr, tmp_b, lens, offs, rocprim::make_tuple(0u, 0u), r1, PairPlus(), (hipStream_t) nullptr));
   }
-  TAIL_TRY(rocprim::exclusive_scan(nullptr, tmp_c, m.line_len.as<unsigned long long>(), m.line_off.as<unsigned long long>(), 0ull, r1,
+  TAIL_TRY(rocprim::exclusive_scan(nullptr, tmp_c, m.line_len.get(), m.line_off.get(), 0ull, r1,
                                    rocprim::plus<unsigned long long>(), (hipStream_t) nullptr));
-  TAIL_TRY(m.scan_tmp.need(std::max<size_t>(std::max(tmp_a, std::max(tmp_b, tmp_c)), 16)));
-  for (hipEvent_t &ev : m.ev)
-    if (!ev) TAIL_TRY(hipEventCreate(&ev));
-  if (!m.ev_text) TAIL_TRY(hipEventCreateWithFlags(&m.ev_text, hipEventDisableTiming));
+  TAIL_TRY(m.scan_tmp.ensure(std::max<size_t>(std::max(tmp_a, std::max(tmp_b, tmp_c)), 16)));
+  for (femb::Event &ev : m.ev) TAIL_TRY(ev.create());
+  TAIL_TRY(m.ev_text.create(hipEventDisableTiming));
   return FEM_OK;
 }
 
@@ -2720,25 +2685,25 @@ int Tail::warm(hipStream_t stream, std::string *err) {
                            (const void *)rescue_jobs_kernel,
                            (const void *)rescue_search_kernel, (const void *)rescue_trace_kernel, (const void *)rescue_append_kernel};
   for (const void *k : kernels) TAIL_TRY(hipFuncGetAttributes(&a, k));
-  if (!m.scan_tmp.p || !m.rec_begin.p || !m.n_ops.p || !m.line_len.p) return FEM_OK;  // (nothing reserved: the scans load with the first batch)
-  size_t tmp = m.scan_tmp.cap;
-  TAIL_TRY(hipMemsetAsync(m.n_ops.p, 0, 4, stream));
-  TAIL_TRY(hipMemsetAsync(m.n_md.p, 0, 4, stream));
-  TAIL_TRY(hipMemsetAsync(m.line_len.p, 0, 8, stream));
-  TAIL_TRY(rocprim::exclusive_scan(m.scan_tmp.p, tmp, (const uint32_t *)m.n_ops.as<uint32_t>(), m.rec_begin.as<uint32_t>(), 0u, (size_t)1,
+  if (!m.scan_tmp || !m.rec_begin || !m.n_ops || !m.line_len) return FEM_OK;  // (nothing reserved: the scans load with the first batch)
+  size_t tmp = m.scan_tmp.bytes();
+  TAIL_TRY(hipMemsetAsync(m.n_ops, 0, 4, stream));
+  TAIL_TRY(hipMemsetAsync(m.n_md, 0, 4, stream));
+  TAIL_TRY(hipMemsetAsync(m.line_len, 0, 8, stream));
+  TAIL_TRY(rocprim::exclusive_scan(m.scan_tmp.get(), tmp, (const uint32_t *)m.n_ops.get(), m.rec_begin.get(), 0u, (size_t)1,
                                    rocprim::plus<uint32_t>(), stream));
   {
-    auto lens = rocprim::make_zip_iterator(rocprim::make_tuple(m.n_ops.as<uint32_t>(), m.n_md.as<uint32_t>()));
-    auto offs = rocprim::make_zip_iterator(rocprim::make_tuple(m.cigar_off.as<uint32_t>(), m.md_off.as<uint32_t>()));
-    tmp = m.scan_tmp.cap;
-    TAIL_TRY(rocprim::exclusive_scan(m.scan_tmp.p, tmp, lens, offs, rocprim::make_tuple(0u, 0u), (size_t)1, PairPlus(), stream));
+    auto lens = rocprim::make_zip_iterator(rocprim::make_tuple(m.n_ops.get(), m.n_md.get()));
+    auto offs = rocprim::make_zip_iterator(rocprim::make_tuple(m.cigar_off.get(), m.md_off.get()));
+    tmp = m.scan_tmp.bytes();
+    TAIL_TRY(rocprim::exclusive_scan(m.scan_tmp.get(), tmp, lens, offs, rocprim::make_tuple(0u, 0u), (size_t)1, PairPlus(), stream));
   }
-  tmp = m.scan_tmp.cap;
-  TAIL_TRY(rocprim::exclusive_scan(m.scan_tmp.p, tmp, m.line_len.as<unsigned long long>(), m.line_off.as<unsigned long long>(), 0ull, (size_t)1,
+  tmp = m.scan_tmp.bytes();
+  TAIL_TRY(rocprim::exclusive_scan(m.scan_tmp.get(), tmp, m.line_len.get(), m.line_off.get(), 0ull, (size_t)1,
                                    rocprim::plus<unsigned long long>(), stream));
-  if (m.text.p && m.h_text.p && m.text.cap >= (1u << 20) && m.h_text.cap >= (1u << 20))
-    TAIL_TRY(hipMemcpyAsync(m.h_text.p, m.text.p, 1u << 20, hipMemcpyDeviceToHost, stream));
-  TAIL_TRY(hipMemcpyAsync(m.h_ctl.p, m.ctl.p, 16, hipMemcpyDeviceToHost, stream));
+  if (m.text && m.h_text && m.text.bytes() >= (1u << 20) && m.h_text.bytes() >= (1u << 20))
+    TAIL_TRY(hipMemcpyAsync(m.h_text, m.text, 1u << 20, hipMemcpyDeviceToHost, stream));
+  TAIL_TRY(hipMemcpyAsync(m.h_ctl, m.ctl, 16, hipMemcpyDeviceToHost, stream));
   TAIL_TRY(hipStreamSynchronize(stream));
   return FEM_OK;
 }
@@ -2784,7 +2749,7 @@ int Tail::run(const TailInput &in, hipStream_t stream, int n_cu, bool tiny, Tail
   }
   const double ms_reserved = since_in();
   const size_t r1 = (size_t)nr + 1;
-  size_t tmp_bytes = m.scan_tmp.cap;
+  size_t tmp_bytes = m.scan_tmp.bytes();
 
   Params p{};
   p.bases = in.bases, p.read_off = in.read_off, p.n_reads = n;
@@ -2793,27 +2758,27 @@ int Tail::run(const TailInput &in, hipStream_t stream, int n_cu, bool tiny, Tail
   p.packed = in.packed, p.packed_bpr = in.packed_bpr, p.exc_bits = in.exc_bits;
   p.cand = in.cand, p.ed = in.ed, p.end = in.end, p.cand_begin = in.cand_begin, p.cand_count = in.cand_count;
   p.e = in.e, p.n_records = nr;
-  p.rec_begin = m.rec_begin.as<uint32_t>();
-  p.u_cand = m.u_cand.as<uint64_t>(), p.u_misc = m.u_misc.as<uint32_t>();
-  p.s_cand = m.s_cand.as<uint64_t>(), p.s_misc = m.s_misc.as<uint32_t>(), p.s_read = m.s_read.as<uint32_t>();
-  p.queue = m.queue.as<uint32_t>(), p.ctl = m.ctl.as<uint32_t>();
-  p.g_keys = m.t_md.as<uint64_t>();
-  p.g_idx = (uint32_t *)(m.t_md.as<uint8_t>() + r1 * 8);
+  p.rec_begin = m.rec_begin;
+  p.u_cand = m.u_cand, p.u_misc = m.u_misc;
+  p.s_cand = m.s_cand, p.s_misc = m.s_misc, p.s_read = m.s_read;
+  p.queue = m.queue, p.ctl = m.ctl;
+  p.g_keys = (uint64_t *)m.t_md.get();
+  p.g_idx = (uint32_t *)(m.t_md + r1 * 8);
   p.lanes = lanes, p.text_words = text_words, p.pat_words = pat_words, p.max_len = max_len, p.fast_lanes = fast_lanes, p.fast_ops = fast_ops;
-  p.t_ops = m.t_ops.as<uint32_t>(), p.t_md = m.t_md.as<uint8_t>(), p.ops_cap = ops_cap, p.md_cap = md_cap;
-  p.ovf_queue = nullptr, p.ovf_out = m.ovf.as<uint32_t>(), p.src_slot = m.src_slot.as<uint32_t>();
-  p.rec_list = m.rec_list.as<uint32_t>();
-  p.n_ops = m.n_ops.as<uint32_t>(), p.n_md = m.n_md.as<uint32_t>();
-  p.flag = m.flag.as<uint16_t>(), p.tid = m.tid.as<uint32_t>(), p.pos0 = m.pos0.as<uint32_t>(), p.nm = m.nm.as<uint8_t>();
+  p.t_ops = m.t_ops, p.t_md = m.t_md, p.ops_cap = ops_cap, p.md_cap = md_cap;
+  p.ovf_queue = nullptr, p.ovf_out = m.ovf, p.src_slot = m.src_slot;
+  p.rec_list = m.rec_list;
+  p.n_ops = m.n_ops, p.n_md = m.n_md;
+  p.flag = m.flag, p.tid = m.tid, p.pos0 = m.pos0, p.nm = m.nm;
 
-  uint32_t *h_ctl = m.h_ctl.as<uint32_t>();
+  uint32_t *h_ctl = m.h_ctl;
   TAIL_TRY(hipEventRecord(m.ev[0], stream));
-  TAIL_TRY(hipMemsetAsync(m.ctl.p, 0, 16, stream));
+  TAIL_TRY(hipMemsetAsync(m.ctl, 0, 16, stream));
   if (n) {
-    TAIL_TRY(rocprim::exclusive_scan(m.scan_tmp.p, tmp_bytes, (const uint32_t *)in.n_map, m.rec_begin.as<uint32_t>(), 0u,
+    TAIL_TRY(rocprim::exclusive_scan(m.scan_tmp.get(), tmp_bytes, (const uint32_t *)in.n_map, m.rec_begin.get(), 0u,
                                      (size_t)n, rocprim::plus<uint32_t>(), stream));
   }
-  TAIL_TRY(hipMemsetD32Async((hipDeviceptr_t)(m.rec_begin.as<uint32_t>() + n), (int)nr, 1, stream));
+  TAIL_TRY(hipMemsetD32Async((hipDeviceptr_t)(m.rec_begin + n), (int)nr, 1, stream));
   uint32_t n_overflow = 0;
   if (nr) {
     hipLaunchKernelGGL(gather_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, p);
@@ -2834,7 +2799,7 @@ int Tail::run(const TailInput &in, hipStream_t stream, int n_cu, bool tiny, Tail
       default: hipLaunchKernelGGL((trace_fast_kernel<uint32_t, uint16_t>), dim3(blocks), dim3(64), fast_lds, stream, p); break;
     }
     TAIL_TRY(hipGetLastError());
-    TAIL_TRY(hipMemcpyAsync(h_ctl, m.ctl.p, 16, hipMemcpyDeviceToHost, stream));
+    TAIL_TRY(hipMemcpyAsync(h_ctl, m.ctl, 16, hipMemcpyDeviceToHost, stream));
     const double ms_queued = since_in();
     TAIL_TRY(hipStreamSynchronize(stream));
     if (trace_host) fprintf(stderr, "[tail] allocations %.2f ms, kernels queued %.2f, walked %.2f\n", ms_reserved, ms_queued, since_in());
@@ -2842,11 +2807,11 @@ int Tail::run(const TailInput &in, hipStream_t stream, int n_cu, bool tiny, Tail
     if (getenv("FEM_TESTING") && getenv("FEM_TAIL_DEBUG"))
       fprintf(stderr, "[tail] records %u, queued for ordering %u, walked %u, overflow pass %u, lanes %u/%u\n", nr, h_ctl[0], h_ctl[3], n_overflow, fast_lanes, lanes);
     if (n_overflow) {  // records whose CIGAR or MD outgrew the first staging: once more, with room for any walk
-      TAIL_TRY(m.o_ops.need((size_t)n_overflow * o_ops_cap * 4));
-      TAIL_TRY(m.o_md.need((size_t)n_overflow * o_md_cap));
+      TAIL_TRY(m.o_ops.ensure((size_t)n_overflow * o_ops_cap));
+      TAIL_TRY(m.o_md.ensure((size_t)n_overflow * o_md_cap));
       Params q = p;
-      q.ovf_queue = m.ovf.as<uint32_t>();
-      q.t_ops = m.o_ops.as<uint32_t>(), q.t_md = m.o_md.as<uint8_t>(), q.ops_cap = o_ops_cap, q.md_cap = o_md_cap;
+      q.ovf_queue = m.ovf;
+      q.t_ops = m.o_ops, q.t_md = m.o_md, q.ops_cap = o_ops_cap, q.md_cap = o_md_cap;
       const uint32_t b2 = std::min<uint32_t>((n_overflow + lanes - 1) / lanes, (uint32_t)n_cu * 16u);
       hipLaunchKernelGGL(trace_kernel, dim3(b2), dim3(64), lds_bytes, stream, q);
       TAIL_TRY(hipGetLastError());
@@ -2856,56 +2821,56 @@ int Tail::run(const TailInput &in, hipStream_t stream, int n_cu, bool tiny, Tail
   }
   TAIL_TRY(hipEventRecord(m.ev[2], stream));
   // ---- compaction: offsets by exclusive scans over n_records + 1 lengths (the last one zero) ----
-  TAIL_TRY(hipMemsetAsync(m.n_ops.as<uint32_t>() + nr, 0, 4, stream));
-  TAIL_TRY(hipMemsetAsync(m.n_md.as<uint32_t>() + nr, 0, 4, stream));
+  TAIL_TRY(hipMemsetAsync(m.n_ops + nr, 0, 4, stream));
+  TAIL_TRY(hipMemsetAsync(m.n_md + nr, 0, 4, stream));
   {  // both offsets in one pass: a scan over (runs, MD characters) pairs
-    auto lens = rocprim::make_zip_iterator(rocprim::make_tuple(m.n_ops.as<uint32_t>(), m.n_md.as<uint32_t>()));
-    auto offs = rocprim::make_zip_iterator(rocprim::make_tuple(m.cigar_off.as<uint32_t>(), m.md_off.as<uint32_t>()));
-    TAIL_TRY(rocprim::exclusive_scan(m.scan_tmp.p, tmp_bytes, lens, offs, rocprim::make_tuple(0u, 0u), r1, PairPlus(), stream));
+    auto lens = rocprim::make_zip_iterator(rocprim::make_tuple(m.n_ops.get(), m.n_md.get()));
+    auto offs = rocprim::make_zip_iterator(rocprim::make_tuple(m.cigar_off.get(), m.md_off.get()));
+    TAIL_TRY(rocprim::exclusive_scan(m.scan_tmp.get(), tmp_bytes, lens, offs, rocprim::make_tuple(0u, 0u), r1, PairPlus(), stream));
   }
   // (the compacted arrays are sized by what the stagings can hold, so that no round trip to the host sits between the scan
   // and the kernel that uses it; the totals come back with everything else)
-  TAIL_TRY(m.cigar.need(std::max<size_t>((size_t)nr * ops_cap + (size_t)n_overflow * o_ops_cap, 1) * 4));
-  TAIL_TRY(m.md.need(std::max<size_t>((size_t)nr * md_cap + (size_t)n_overflow * o_md_cap, 1)));
+  TAIL_TRY(m.cigar.ensure(std::max<size_t>((size_t)nr * ops_cap + (size_t)n_overflow * o_ops_cap, 1)));
+  TAIL_TRY(m.md.ensure(std::max<size_t>((size_t)nr * md_cap + (size_t)n_overflow * o_md_cap, 1)));
   if (nr) {
     CompactParams c{};
     c.n_records = nr, c.src_slot = p.src_slot, c.n_ops = p.n_ops, c.n_md = p.n_md;
-    c.cigar_off = m.cigar_off.as<uint32_t>(), c.md_off = m.md_off.as<uint32_t>();
-    c.t_ops = p.t_ops, c.t_md = p.t_md, c.o_ops = m.o_ops.as<uint32_t>(), c.o_md = m.o_md.as<uint8_t>();
+    c.cigar_off = m.cigar_off, c.md_off = m.md_off;
+    c.t_ops = p.t_ops, c.t_md = p.t_md, c.o_ops = m.o_ops, c.o_md = m.o_md;
     c.ops_cap = ops_cap, c.md_cap = md_cap, c.o_ops_cap = o_ops_cap, c.o_md_cap = o_md_cap;
-    c.cigar = m.cigar.as<uint32_t>(), c.md = m.md.as<uint8_t>();
+    c.cigar = m.cigar, c.md = m.md;
     hipLaunchKernelGGL(compact_kernel, dim3((nr + 255u) / 256u), dim3(256), 0, stream, c);
     TAIL_TRY(hipGetLastError());
   }
   TAIL_TRY(hipEventRecord(m.ev[3], stream));
-  TAIL_TRY(hipMemcpyAsync(h_ctl + 4, m.cigar_off.as<uint32_t>() + nr, 4, hipMemcpyDeviceToHost, stream));
-  TAIL_TRY(hipMemcpyAsync(h_ctl + 5, m.md_off.as<uint32_t>() + nr, 4, hipMemcpyDeviceToHost, stream));
+  TAIL_TRY(hipMemcpyAsync(h_ctl + 4, m.cigar_off + nr, 4, hipMemcpyDeviceToHost, stream));
+  TAIL_TRY(hipMemcpyAsync(h_ctl + 5, m.md_off + nr, 4, hipMemcpyDeviceToHost, stream));
   m.last_n = n, m.last_nr = nr, m.paired = false, m.n_resc = 0, m.resc_timed = false, m.pair_mapq = false;
   if (copy_records) {  // ---- copy back (else the caller renders the records on the device: sam(), bam()) ----
     TAIL_TRY(hipStreamSynchronize(stream));
     const uint32_t n_cigar = h_ctl[4], n_md = h_ctl[5];
-    TAIL_TRY(m.h_rec_begin.need(((size_t)n + 1) * 4));
-    TAIL_TRY(m.h_flag.need(r1 * 2));
-    TAIL_TRY(m.h_tid.need(r1 * 4));
-    TAIL_TRY(m.h_pos0.need(r1 * 4));
-    TAIL_TRY(m.h_nm.need(r1));
-    TAIL_TRY(m.h_cigar_off.need(r1 * 4));
-    TAIL_TRY(m.h_md_off.need(r1 * 4));
-    TAIL_TRY(m.h_cigar.need(std::max<size_t>(n_cigar, 1) * 4));
-    TAIL_TRY(m.h_md.need(std::max<size_t>(n_md, 1)));
-    TAIL_TRY(hipMemcpyAsync(m.h_rec_begin.p, m.rec_begin.p, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost, stream));
-    TAIL_TRY(hipMemcpyAsync(m.h_cigar_off.p, m.cigar_off.p, r1 * 4, hipMemcpyDeviceToHost, stream));
-    TAIL_TRY(hipMemcpyAsync(m.h_md_off.p, m.md_off.p, r1 * 4, hipMemcpyDeviceToHost, stream));
+    TAIL_TRY(m.h_rec_begin.ensure((size_t)n + 1));
+    TAIL_TRY(m.h_flag.ensure(r1));
+    TAIL_TRY(m.h_tid.ensure(r1));
+    TAIL_TRY(m.h_pos0.ensure(r1));
+    TAIL_TRY(m.h_nm.ensure(r1));
+    TAIL_TRY(m.h_cigar_off.ensure(r1));
+    TAIL_TRY(m.h_md_off.ensure(r1));
+    TAIL_TRY(m.h_cigar.ensure(std::max<size_t>(n_cigar, 1)));
+    TAIL_TRY(m.h_md.ensure(std::max<size_t>(n_md, 1)));
+    TAIL_TRY(hipMemcpyAsync(m.h_rec_begin, m.rec_begin, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost, stream));
+    TAIL_TRY(hipMemcpyAsync(m.h_cigar_off, m.cigar_off, r1 * 4, hipMemcpyDeviceToHost, stream));
+    TAIL_TRY(hipMemcpyAsync(m.h_md_off, m.md_off, r1 * 4, hipMemcpyDeviceToHost, stream));
     if (nr) {
-      TAIL_TRY(hipMemcpyAsync(m.h_flag.p, m.flag.p, (size_t)nr * 2, hipMemcpyDeviceToHost, stream));
-      TAIL_TRY(hipMemcpyAsync(m.h_tid.p, m.tid.p, (size_t)nr * 4, hipMemcpyDeviceToHost, stream));
-      TAIL_TRY(hipMemcpyAsync(m.h_pos0.p, m.pos0.p, (size_t)nr * 4, hipMemcpyDeviceToHost, stream));
-      TAIL_TRY(hipMemcpyAsync(m.h_nm.p, m.nm.p, (size_t)nr, hipMemcpyDeviceToHost, stream));
+      TAIL_TRY(hipMemcpyAsync(m.h_flag, m.flag, (size_t)nr * 2, hipMemcpyDeviceToHost, stream));
+      TAIL_TRY(hipMemcpyAsync(m.h_tid, m.tid, (size_t)nr * 4, hipMemcpyDeviceToHost, stream));
+      TAIL_TRY(hipMemcpyAsync(m.h_pos0, m.pos0, (size_t)nr * 4, hipMemcpyDeviceToHost, stream));
+      TAIL_TRY(hipMemcpyAsync(m.h_nm, m.nm, (size_t)nr, hipMemcpyDeviceToHost, stream));
     }
-    if (n_cigar) TAIL_TRY(hipMemcpyAsync(m.h_cigar.p, m.cigar.p, (size_t)n_cigar * 4, hipMemcpyDeviceToHost, stream));
-    if (n_md) TAIL_TRY(hipMemcpyAsync(m.h_md.p, m.md.p, (size_t)n_md, hipMemcpyDeviceToHost, stream));
+    if (n_cigar) TAIL_TRY(hipMemcpyAsync(m.h_cigar, m.cigar, (size_t)n_cigar * 4, hipMemcpyDeviceToHost, stream));
+    if (n_md) TAIL_TRY(hipMemcpyAsync(m.h_md, m.md, (size_t)n_md, hipMemcpyDeviceToHost, stream));
   }
-  TAIL_TRY(hipMemcpyAsync(h_ctl, m.ctl.p, 16, hipMemcpyDeviceToHost, stream));
+  TAIL_TRY(hipMemcpyAsync(h_ctl, m.ctl, 16, hipMemcpyDeviceToHost, stream));
   TAIL_TRY(hipStreamSynchronize(stream));
   if (h_ctl[2] != 0) {
     if (err) *err = "device traceback: a record outgrew the overflow staging (internal error)";
@@ -2918,11 +2883,11 @@ int Tail::run(const TailInput &in, hipStream_t stream, int n_cu, bool tiny, Tail
   *out = TailOutput{};
   out->n_reads = n, out->n_records = nr;
   if (copy_records) {
-    out->rec_begin = m.h_rec_begin.as<uint32_t>();
-    out->flag = m.h_flag.as<uint16_t>(), out->tid = m.h_tid.as<uint32_t>(), out->pos0 = m.h_pos0.as<uint32_t>();
-    out->nm = m.h_nm.as<uint8_t>();
-    out->cigar_off = m.h_cigar_off.as<uint32_t>(), out->cigar = m.h_cigar.as<uint32_t>();
-    out->md_off = m.h_md_off.as<uint32_t>(), out->md = m.h_md.as<char>();
+    out->rec_begin = m.h_rec_begin;
+    out->flag = m.h_flag, out->tid = m.h_tid, out->pos0 = m.h_pos0;
+    out->nm = m.h_nm;
+    out->cigar_off = m.h_cigar_off, out->cigar = m.h_cigar;
+    out->md_off = m.h_md_off, out->md = m.h_md;
   }
   return FEM_OK;
 }
@@ -2930,8 +2895,8 @@ int Tail::run(const TailInput &in, hipStream_t stream, int n_cu, bool tiny, Tail
 int Tail::reserve_text(uint64_t bytes, std::string *err) {
   if (!impl_) impl_ = new (std::nothrow) Impl();
   if (!impl_) return FEM_ERR_NOMEM;
-  TAIL_TRY(impl_->text.need((size_t)bytes));
-  TAIL_TRY(impl_->h_text.need((size_t)bytes));
+  TAIL_TRY(impl_->text.ensure((size_t)bytes));
+  TAIL_TRY(impl_->h_text.ensure((size_t)bytes));
   return FEM_OK;
 }
 
@@ -2948,32 +2913,32 @@ int Tail::sam(const TailInput &in, const SamInput &names, hipStream_t stream, in
   const bool hole = names.qual_hole && !names.quals;
   const size_t n_reads1 = (size_t)m.last_n + 1;
   if (hole) {  // where each read's QUAL field starts (all ones: the read has no record)
-    TAIL_TRY(m.qual_at.need(n_reads1 * 8));
-    TAIL_TRY(m.h_qual_at.need(n_reads1 * 8));
-    TAIL_TRY(hipMemsetAsync(m.qual_at.p, 0xFF, n_reads1 * 8, stream));
-    p.qual_at = m.qual_at.as<unsigned long long>(), p.qual_hole = 1u;
+    TAIL_TRY(m.qual_at.ensure(n_reads1));
+    TAIL_TRY(m.h_qual_at.ensure(n_reads1));
+    TAIL_TRY(hipMemsetAsync(m.qual_at, 0xFF, n_reads1 * 8, stream));
+    p.qual_at = m.qual_at, p.qual_hole = 1u;
   }
   int rc = m.lines(in, names, paired, nullptr, stream, n_cu, &p, err);
   if (rc) return rc;
-  unsigned long long *h_total = (unsigned long long *)(m.h_ctl.as<uint32_t>() + 6);
-  TAIL_TRY(hipMemcpyAsync(h_total, m.line_off.as<unsigned long long>() + p.n_records, 8, hipMemcpyDeviceToHost, stream));
+  unsigned long long *h_total = (unsigned long long *)(m.h_ctl + 6);
+  TAIL_TRY(hipMemcpyAsync(h_total, m.line_off + p.n_records, 8, hipMemcpyDeviceToHost, stream));
   TAIL_TRY(hipStreamSynchronize(stream));
   const uint32_t nr = m.counted(names, &p);
   const uint64_t total = *h_total;
-  TAIL_TRY(m.text.need(std::max<size_t>((size_t)total, 16)));
-  TAIL_TRY(m.h_text.need(std::max<size_t>((size_t)total + total / 8, 1u << 20)));
+  TAIL_TRY(m.text.ensure(std::max<size_t>((size_t)total, 16)));
+  TAIL_TRY(m.h_text.ensure(std::max<size_t>((size_t)total + total / 8, 1u << 20)));
   if (nr) {
-    p.text = m.text.as<uint8_t>();
+    p.text = m.text;
     const uint32_t blocks = (nr + 255u) / 256u;  // a wave per 64 records
     hipLaunchKernelGGL(names.unmapped || m.rep_timed ? (paired ? sam_write_kernel<true, true> : sam_write_kernel<false, true>)
                                                      : (paired ? sam_write_kernel<true> : sam_write_kernel<false>), dim3(blocks), dim3(256), 0, stream, p);
     TAIL_TRY(hipGetLastError());
   }
   TAIL_TRY(hipEventRecord(m.ev[1], stream));
-  rc = m.send_home(m.text.p, (size_t)total, m.h_qual_at.p, m.qual_at.p, hole ? n_reads1 * 8 : 0, stream, wait, gate, wait ? ms : nullptr, err);
+  rc = m.send_home(m.text, (size_t)total, m.h_qual_at, m.qual_at, hole ? n_reads1 * 8 : 0, stream, wait, gate, wait ? ms : nullptr, err);
   if (rc) return rc;
-  out->text = m.h_text.as<char>(), out->len = total, out->n_asserted = m.h_ctl.as<uint32_t>()[2];
-  out->qual_at = hole ? m.h_qual_at.as<uint64_t>() : nullptr;
+  out->text = m.h_text, out->len = total, out->n_asserted = m.h_ctl[2];
+  out->qual_at = hole ? m.h_qual_at : nullptr;
   return FEM_OK;
 }
 
@@ -2985,42 +2950,42 @@ int Tail::bam(const TailInput &in, const SamInput &names, int level, hipStream_t
     if (err) *err = "BAM records need the qualities on the device";
     return FEM_ERR_STATE;
   }
-  TAIL_TRY(m.bam_ctl.need(16));
+  TAIL_TRY(m.bam_ctl.ensure(4));
   SamParams p{};
-  uint32_t *bad_name = m.bam_ctl.as<uint32_t>();
+  uint32_t *bad_name = m.bam_ctl;
   int rc = m.lines(in, names, paired, bad_name, stream, n_cu, &p, err);
   if (rc) return rc;
   const uint32_t n_bound = p.n_records;
   // the record offsets come home with the total: the member cuts are made here
-  TAIL_TRY(m.h_line_off.need(((size_t)n_bound + 1) * 8));
-  TAIL_TRY(hipMemcpyAsync(m.h_line_off.p, m.line_off.p, ((size_t)n_bound + 1) * 8, hipMemcpyDeviceToHost, stream));
-  TAIL_TRY(hipMemcpyAsync(m.h_ctl.as<uint32_t>() + 3, bad_name, 4, hipMemcpyDeviceToHost, stream));
+  TAIL_TRY(m.h_line_off.ensure((size_t)n_bound + 1));
+  TAIL_TRY(hipMemcpyAsync(m.h_line_off, m.line_off, ((size_t)n_bound + 1) * 8, hipMemcpyDeviceToHost, stream));
+  TAIL_TRY(hipMemcpyAsync(m.h_ctl + 3, bad_name, 4, hipMemcpyDeviceToHost, stream));
   TAIL_TRY(hipStreamSynchronize(stream));
-  if (m.h_ctl.as<uint32_t>()[3]) {
+  if (m.h_ctl[3]) {
     if (err) *err = "the batch holds a read name over 254 characters: not writable as BAM (l_read_name is one byte)";
     return FEM_ERR_UNSUPPORTED;
   }
   const uint32_t nr = m.counted(names, &p);
-  const uint64_t total = m.h_line_off.as<uint64_t>()[nr];
-  TAIL_TRY(m.text.need(std::max<size_t>((size_t)total, 16)));
+  const uint64_t total = m.h_line_off[nr];
+  TAIL_TRY(m.text.ensure(std::max<size_t>((size_t)total, 16)));
   if (nr) {
-    p.text = m.text.as<uint8_t>();
+    p.text = m.text;
     hipLaunchKernelGGL(names.unmapped || m.rep_timed ? (paired ? bam_write_kernel<true, true> : bam_write_kernel<false, true>)
                                                      : (paired ? bam_write_kernel<true> : bam_write_kernel<false>), dim3((nr + 3u) / 4u), dim3(256), 0, stream, p);
     TAIL_TRY(hipGetLastError());
   }
   TAIL_TRY(hipEventRecord(m.ev[1], stream));
-  femz::bgzf_cut(m.h_line_off.as<uint64_t>(), nr, total, &m.cuts);
+  femz::bgzf_cut(m.h_line_off, nr, total, &m.cuts);
   uint64_t len = 0;
   float ms_z = 0.f;
-  if ((rc = m.bgzf.compress(m.text.as<uint8_t>(), total, m.cuts, level, stream, &len, err, ms ? &ms_z : nullptr))) return rc;
-  TAIL_TRY(m.h_text.need(std::max<size_t>((size_t)len, 1u << 20)));
+  if ((rc = m.bgzf.compress(m.text, total, m.cuts, level, stream, &len, err, ms ? &ms_z : nullptr))) return rc;
+  TAIL_TRY(m.h_text.ensure(std::max<size_t>((size_t)len, 1u << 20)));
   // (compress() has waited for the stream: both spans are over)
   if ((rc = m.send_home(m.bgzf.out(), (size_t)len, nullptr, nullptr, 0, stream, wait, gate, ms, err))) return rc;
   if (ms) ms[1] += ms_z;
-  out->data = m.h_text.as<uint8_t>(), out->len = len, out->raw_len = total;
+  out->data = (uint8_t *)m.h_text.get(), out->len = len, out->raw_len = total;
   out->n_blocks = m.cuts.empty() ? 0 : m.cuts.size() - 1;
-  out->n_asserted = m.h_ctl.as<uint32_t>()[2];
+  out->n_asserted = m.h_ctl[2];
   return FEM_OK;
 }
 
@@ -3036,33 +3001,32 @@ int Tail::pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::
   const uint32_t *resc_before = nullptr;
   if (rescue && np) {  // ---- mate rescue: the kept records behind run()'s, resc_before their exclusive scan over the pairs ----
     const int32_t E = rescue->max_edits;
-    for (hipEvent_t &e : m.ev_resc)
-      if (!e) TAIL_TRY(hipEventCreate(&e));
-    TAIL_TRY(m.r_ctl.need(16));
-    TAIL_TRY(m.h_r_ctl.need(16));
-    TAIL_TRY(m.r_cand.need((size_t)np * 4));
-    TAIL_TRY(m.r_best.need((size_t)np * 8));
-    TAIL_TRY(m.r_jobs.need((size_t)np * kRescueAnchors * 4));
-    const uint32_t *h_tot = m.h_ctl.as<uint32_t>();  // run() left its CIGAR and MD totals in h_ctl[4], h_ctl[5]
+    for (femb::Event &e : m.ev_resc) TAIL_TRY(e.create());
+    TAIL_TRY(m.r_ctl.ensure(4));
+    TAIL_TRY(m.h_r_ctl.ensure(4));
+    TAIL_TRY(m.r_cand.ensure((size_t)np));
+    TAIL_TRY(m.r_best.ensure((size_t)np));
+    TAIL_TRY(m.r_jobs.ensure((size_t)np * kRescueAnchors));
+    const uint32_t *h_tot = m.h_ctl;  // run() left its CIGAR and MD totals in h_ctl[4], h_ctl[5]
     RescueParams r{};
     r.n_pairs = np, r.n_records = nr, r.E = E, r.min_insert = min_insert, r.max_insert = max_insert;
     r.bases = rescue->bases, r.read_off = rescue->read_off, r.ref_raw = rescue->ref_raw, r.ref_bytes = rescue->ref_bytes;
     r.seq_off = rescue->seq_off, r.seq_len = rescue->seq_len;
-    r.ctl = m.r_ctl.as<uint32_t>(), r.cand_pair = m.r_cand.as<uint32_t>(), r.jobs = m.r_jobs.as<uint32_t>();
-    r.best = m.r_best.as<unsigned long long>();
+    r.ctl = m.r_ctl, r.cand_pair = m.r_cand, r.jobs = m.r_jobs;
+    r.best = m.r_best;
     r.cig_total = h_tot[4], r.md_total = h_tot[5];
     auto bind_records = [&]() {
-      r.rec_begin = m.rec_begin.as<uint32_t>(), r.flag = m.flag.as<uint16_t>(), r.tid = m.tid.as<uint32_t>(), r.pos0 = m.pos0.as<uint32_t>();
-      r.nm = m.nm.as<uint8_t>(), r.cigar_off = m.cigar_off.as<uint32_t>(), r.cigar = m.cigar.as<uint32_t>();
-      r.md_off = m.md_off.as<uint32_t>(), r.md = m.md.as<uint8_t>(), r.s_read = m.s_read.as<uint32_t>();
+      r.rec_begin = m.rec_begin, r.flag = m.flag, r.tid = m.tid, r.pos0 = m.pos0;
+      r.nm = m.nm, r.cigar_off = m.cigar_off, r.cigar = m.cigar;
+      r.md_off = m.md_off, r.md = m.md, r.s_read = m.s_read;
     };
     bind_records();
     TAIL_TRY(hipEventRecord(m.ev_resc[0], stream));
-    TAIL_TRY(hipMemsetAsync(m.r_ctl.p, 0, 16, stream));
+    TAIL_TRY(hipMemsetAsync(m.r_ctl, 0, 16, stream));
     hipLaunchKernelGGL(rescue_jobs_kernel, dim3((np + 255u) / 256u), dim3(256), 0, stream, r);
     TAIL_TRY(hipGetLastError());
-    uint32_t *h_rc = m.h_r_ctl.as<uint32_t>();
-    TAIL_TRY(hipMemcpyAsync(h_rc, m.r_ctl.p, 8, hipMemcpyDeviceToHost, stream));
+    uint32_t *h_rc = m.h_r_ctl;
+    TAIL_TRY(hipMemcpyAsync(h_rc, m.r_ctl, 8, hipMemcpyDeviceToHost, stream));
     TAIL_TRY(hipStreamSynchronize(stream));
     const uint32_t n_cand = h_rc[0], n_jobs = h_rc[1];
     if (n_cand) {
@@ -3072,26 +3036,26 @@ int Tail::pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::
       r.ops_cap = 2u * (uint32_t)E + 8u, r.md_cap = 8u * (uint32_t)E + 64u;
       r.o_ops_cap = 2u * r.max_len + 2u * (uint32_t)E + 8u, r.o_md_cap = 8u * r.max_len + 128u;
       const size_t rec_cap = (size_t)nr + n_cand + 1;
-      TAIL_TRY(m.flag.grow(rec_cap * 2, (size_t)nr * 2, stream));
-      TAIL_TRY(m.tid.grow(rec_cap * 4, (size_t)nr * 4, stream));
-      TAIL_TRY(m.pos0.grow(rec_cap * 4, (size_t)nr * 4, stream));
-      TAIL_TRY(m.nm.grow(rec_cap, nr, stream));
-      TAIL_TRY(m.s_read.grow(rec_cap * 4, (size_t)nr * 4, stream));
-      TAIL_TRY(m.cigar_off.grow(rec_cap * 4, ((size_t)nr + 1) * 4, stream));
-      TAIL_TRY(m.md_off.grow(rec_cap * 4, ((size_t)nr + 1) * 4, stream));
+      TAIL_TRY(m.flag.ensure_keep(rec_cap, (size_t)nr, stream));
+      TAIL_TRY(m.tid.ensure_keep(rec_cap, (size_t)nr, stream));
+      TAIL_TRY(m.pos0.ensure_keep(rec_cap, (size_t)nr, stream));
+      TAIL_TRY(m.nm.ensure_keep(rec_cap, nr, stream));
+      TAIL_TRY(m.s_read.ensure_keep(rec_cap, (size_t)nr, stream));
+      TAIL_TRY(m.cigar_off.ensure_keep(rec_cap, (size_t)nr + 1, stream));
+      TAIL_TRY(m.md_off.ensure_keep(rec_cap, (size_t)nr + 1, stream));
       bind_records();
-      TAIL_TRY(m.r_ops.need((size_t)n_cand * r.ops_cap * 4));
-      TAIL_TRY(m.r_md.need((size_t)n_cand * r.md_cap));
-      TAIL_TRY(m.r_rec.need((size_t)n_cand * kRescRec * 4));
-      TAIL_TRY(m.r_ovf.need((size_t)n_cand * 4));
-      r.ovf_queue = m.r_ovf.as<uint32_t>();
+      TAIL_TRY(m.r_ops.ensure((size_t)n_cand * r.ops_cap));
+      TAIL_TRY(m.r_md.ensure((size_t)n_cand * r.md_cap));
+      TAIL_TRY(m.r_rec.ensure((size_t)n_cand * kRescRec));
+      TAIL_TRY(m.r_ovf.ensure((size_t)n_cand));
+      r.ovf_queue = m.r_ovf;
       const size_t p1 = (size_t)np + 1;
-      TAIL_TRY(m.r_kept.need(p1 * 12));
-      TAIL_TRY(m.r_scan.need(p1 * 12));
-      r.t_ops = m.r_ops.as<uint32_t>(), r.t_md = m.r_md.as<uint8_t>(), r.c_rec = m.r_rec.as<uint32_t>();
-      r.kept = m.r_kept.as<uint32_t>(), r.k_ops = r.kept + p1, r.k_md = r.kept + 2 * p1;
-      r.s_kept = m.r_scan.as<uint32_t>(), r.s_ops = r.s_kept + p1, r.s_md = r.s_kept + 2 * p1;
-      TAIL_TRY(hipMemsetAsync(m.r_kept.p, 0, p1 * 12, stream));
+      TAIL_TRY(m.r_kept.ensure(p1 * 3));
+      TAIL_TRY(m.r_scan.ensure(p1 * 3));
+      r.t_ops = m.r_ops, r.t_md = m.r_md, r.c_rec = m.r_rec;
+      r.kept = m.r_kept, r.k_ops = r.kept + p1, r.k_md = r.kept + 2 * p1;
+      r.s_kept = m.r_scan, r.s_ops = r.s_kept + p1, r.s_md = r.s_kept + 2 * p1;
+      TAIL_TRY(hipMemsetAsync(m.r_kept, 0, p1 * 12, stream));
       if (n_jobs) {
         const uint32_t blocks = std::min<uint32_t>((n_jobs + kResWaves - 1u) / kResWaves, 16384u);
         hipLaunchKernelGGL(rescue_search_kernel, dim3(blocks), dim3(64 * kResWaves), 0, stream, r);
@@ -3109,77 +3073,75 @@ int Tail::pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::
       r.overflow_pass = 0;
       hipLaunchKernelGGL(rescue_trace_kernel, dim3(t_blocks), dim3(64), r.lanes * words_per_lane * 4u, stream, r);
       TAIL_TRY(hipGetLastError());
-      TAIL_TRY(hipMemcpyAsync(h_rc + 2, m.r_ctl.as<uint32_t>() + 2, 4, hipMemcpyDeviceToHost, stream));
+      TAIL_TRY(hipMemcpyAsync(h_rc + 2, m.r_ctl + 2, 4, hipMemcpyDeviceToHost, stream));
       TAIL_TRY(hipStreamSynchronize(stream));
       const uint32_t n_ovf = h_rc[2];
       if (n_ovf) {  // the records that outgrew the first staging, again with room for the longest walk
-        TAIL_TRY(m.r_o_ops.need((size_t)n_ovf * r.o_ops_cap * 4));
-        TAIL_TRY(m.r_o_md.need((size_t)n_ovf * r.o_md_cap));
-        r.o_ops = m.r_o_ops.as<uint32_t>(), r.o_md = m.r_o_md.as<uint8_t>(), r.overflow_pass = 1;
+        TAIL_TRY(m.r_o_ops.ensure((size_t)n_ovf * r.o_ops_cap));
+        TAIL_TRY(m.r_o_md.ensure((size_t)n_ovf * r.o_md_cap));
+        r.o_ops = m.r_o_ops, r.o_md = m.r_o_md, r.overflow_pass = 1;
         const uint32_t o_blocks = std::min<uint32_t>((n_ovf + r.lanes - 1u) / r.lanes, 16384u);
         hipLaunchKernelGGL(rescue_trace_kernel, dim3(o_blocks), dim3(64), r.lanes * words_per_lane * 4u, stream, r);
         TAIL_TRY(hipGetLastError());
       }
       // the kept records' CIGAR runs and MD characters fit what their stagings can hold
-      TAIL_TRY(m.cigar.grow(((size_t)r.cig_total + (size_t)n_cand * r.ops_cap + (size_t)n_ovf * r.o_ops_cap) * 4,
-                            (size_t)r.cig_total * 4, stream));
-      TAIL_TRY(m.md.grow((size_t)r.md_total + (size_t)n_cand * r.md_cap + (size_t)n_ovf * r.o_md_cap, r.md_total, stream));
+      TAIL_TRY(m.cigar.ensure_keep((size_t)r.cig_total + (size_t)n_cand * r.ops_cap + (size_t)n_ovf * r.o_ops_cap, (size_t)r.cig_total, stream));
+      TAIL_TRY(m.md.ensure_keep((size_t)r.md_total + (size_t)n_cand * r.md_cap + (size_t)n_ovf * r.o_md_cap, r.md_total, stream));
       bind_records();
       {
         auto lens = rocprim::make_zip_iterator(rocprim::make_tuple(r.kept, r.k_ops, r.k_md));
-        auto offs = rocprim::make_zip_iterator(rocprim::make_tuple(m.r_scan.as<uint32_t>(), m.r_scan.as<uint32_t>() + p1,
-                                                                   m.r_scan.as<uint32_t>() + 2 * p1));
+        auto offs = rocprim::make_zip_iterator(rocprim::make_tuple(m.r_scan.get(), m.r_scan.get() + p1,
+                                                                   m.r_scan + 2 * p1));
         size_t tmp = 0;
         TAIL_TRY(rocprim::exclusive_scan(nullptr, tmp, lens, offs, rocprim::make_tuple(0u, 0u, 0u), p1, TriplePlus(), stream));
-        TAIL_TRY(m.r_scan_tmp.need(std::max<size_t>(tmp, 16)));
-        tmp = m.r_scan_tmp.cap;
-        TAIL_TRY(rocprim::exclusive_scan(m.r_scan_tmp.p, tmp, lens, offs, rocprim::make_tuple(0u, 0u, 0u), p1, TriplePlus(), stream));
+        TAIL_TRY(m.r_scan_tmp.ensure(std::max<size_t>(tmp, 16)));
+        tmp = m.r_scan_tmp.bytes();
+        TAIL_TRY(rocprim::exclusive_scan(m.r_scan_tmp.get(), tmp, lens, offs, rocprim::make_tuple(0u, 0u, 0u), p1, TriplePlus(), stream));
       }
       hipLaunchKernelGGL(rescue_append_kernel, dim3((n_cand + 255u) / 256u), dim3(256), 0, stream, r);
       TAIL_TRY(hipGetLastError());
-      TAIL_TRY(hipMemcpyAsync(h_rc, m.r_scan.as<uint32_t>() + np, 4, hipMemcpyDeviceToHost, stream));
-      TAIL_TRY(hipMemcpyAsync(h_rc + 3, m.r_ctl.as<uint32_t>() + 3, 4, hipMemcpyDeviceToHost, stream));
+      TAIL_TRY(hipMemcpyAsync(h_rc, m.r_scan + np, 4, hipMemcpyDeviceToHost, stream));
+      TAIL_TRY(hipMemcpyAsync(h_rc + 3, m.r_ctl + 3, 4, hipMemcpyDeviceToHost, stream));
       TAIL_TRY(hipStreamSynchronize(stream));
       if (h_rc[3] != 0) {
         if (err) *err = "mate rescue: a traceback outgrew its staging (internal error)";
         return FEM_ERR_HIP;
       }
       m.n_resc = h_rc[0];
-      if (m.n_resc) resc_before = m.r_scan.as<uint32_t>();
+      if (m.n_resc) resc_before = m.r_scan;
     }
     TAIL_TRY(hipEventRecord(m.ev_resc[1], stream));
     m.resc_timed = true;
   }
   const size_t lines = std::max<size_t>((size_t)nr + m.n_resc, 1);
-  TAIL_TRY(m.perm.need(lines * 4));
-  TAIL_TRY(m.pflag.need(lines * 2));
-  TAIL_TRY(m.mtid.need(lines * 4));
-  TAIL_TRY(m.mpos0.need(lines * 4));
-  TAIL_TRY(m.tlen.need(lines * 4));
-  if (mapq) TAIL_TRY(m.lmq.need(lines));
-  TAIL_TRY(m.pair_begin.need(((size_t)n + 1) * 4));
-  TAIL_TRY(m.pair_ctl.need(16));
-  TAIL_TRY(m.h_pair_ctl.need(16));
-  for (hipEvent_t &e : m.ev_pair)
-    if (!e) TAIL_TRY(hipEventCreate(&e));
+  TAIL_TRY(m.perm.ensure(lines));
+  TAIL_TRY(m.pflag.ensure(lines));
+  TAIL_TRY(m.mtid.ensure(lines));
+  TAIL_TRY(m.mpos0.ensure(lines));
+  TAIL_TRY(m.tlen.ensure(lines));
+  if (mapq) TAIL_TRY(m.lmq.ensure(lines));
+  TAIL_TRY(m.pair_begin.ensure((size_t)n + 1));
+  TAIL_TRY(m.pair_ctl.ensure(4));
+  TAIL_TRY(m.h_pair_ctl.ensure(4));
+  for (femb::Event &e : m.ev_pair) TAIL_TRY(e.create());
   TAIL_TRY(hipEventRecord(m.ev_pair[0], stream));
-  TAIL_TRY(hipMemsetAsync(m.pair_ctl.p, 0, 16, stream));
+  TAIL_TRY(hipMemsetAsync(m.pair_ctl, 0, 16, stream));
   if (np) {
     PairParams q{};
     q.n_pairs = np, q.min_insert = min_insert, q.max_insert = max_insert;
-    q.rec_begin = m.rec_begin.as<uint32_t>(), q.flag = m.flag.as<uint16_t>(), q.tid = m.tid.as<uint32_t>(), q.pos0 = m.pos0.as<uint32_t>();
-    q.nm = m.nm.as<uint8_t>(), q.cigar_off = m.cigar_off.as<uint32_t>(), q.cigar = m.cigar.as<uint32_t>();
-    q.perm = m.perm.as<uint32_t>(), q.pflag = m.pflag.as<uint16_t>(), q.mtid = m.mtid.as<uint32_t>(), q.mpos0 = m.mpos0.as<uint32_t>();
-    q.tlen = m.tlen.as<int32_t>(), q.pair_begin = m.pair_begin.as<uint32_t>(), q.n_proper = m.pair_ctl.as<uint32_t>();
+    q.rec_begin = m.rec_begin, q.flag = m.flag, q.tid = m.tid, q.pos0 = m.pos0;
+    q.nm = m.nm, q.cigar_off = m.cigar_off, q.cigar = m.cigar;
+    q.perm = m.perm, q.pflag = m.pflag, q.mtid = m.mtid, q.mpos0 = m.mpos0;
+    q.tlen = m.tlen, q.pair_begin = m.pair_begin, q.n_proper = m.pair_ctl;
     q.resc_before = resc_before, q.resc_first = nr;
-    q.lmq = mapq ? m.lmq.as<uint8_t>() : nullptr;
+    q.lmq = mapq ? m.lmq : nullptr;
     hipLaunchKernelGGL(mapq ? pair_kernel<true> : pair_kernel<false>, dim3((np + 255u) / 256u), dim3(256), 0, stream, q);
     TAIL_TRY(hipGetLastError());
   } else {
-    TAIL_TRY(hipMemsetAsync(m.pair_begin.p, 0, 4, stream));
+    TAIL_TRY(hipMemsetAsync(m.pair_begin, 0, 4, stream));
   }
   TAIL_TRY(hipEventRecord(m.ev_pair[1], stream));
-  TAIL_TRY(hipMemcpyAsync(m.h_pair_ctl.p, m.pair_ctl.p, 4, hipMemcpyDeviceToHost, stream));
+  TAIL_TRY(hipMemcpyAsync(m.h_pair_ctl, m.pair_ctl, 4, hipMemcpyDeviceToHost, stream));
   m.paired = true, m.pair_mapq = mapq;
   return FEM_OK;
 }
@@ -3214,7 +3176,7 @@ float Tail::mapq_ms() const {
   return t;
 }
 
-uint64_t Tail::n_proper() const { return impl_ && impl_->paired && impl_->h_pair_ctl.p ? impl_->h_pair_ctl.as<uint32_t>()[0] : 0; }
+uint64_t Tail::n_proper() const { return impl_ && impl_->paired && impl_->h_pair_ctl ? impl_->h_pair_ctl[0] : 0; }
 
 float Tail::pair_ms() const {
   float t = 0.f;
@@ -3227,51 +3189,51 @@ int Tail::pair_fetch(hipStream_t stream, PairOutput *out, std::string *err) {
   Impl &m = *impl_;
   const uint32_t n = m.last_n, nr = m.last_nr + m.n_resc;  // (lines)
   const size_t lines = std::max<size_t>(nr, 1);
-  TAIL_TRY(m.h_perm.need(lines * 4));
-  TAIL_TRY(m.h_pflag.need(lines * 2));
-  TAIL_TRY(m.h_mtid.need(lines * 4));
-  TAIL_TRY(m.h_mpos0.need(lines * 4));
-  TAIL_TRY(m.h_tlen.need(lines * 4));
-  TAIL_TRY(m.h_pair_begin.need(((size_t)n + 1) * 4));
+  TAIL_TRY(m.h_perm.ensure(lines));
+  TAIL_TRY(m.h_pflag.ensure(lines));
+  TAIL_TRY(m.h_mtid.ensure(lines));
+  TAIL_TRY(m.h_mpos0.ensure(lines));
+  TAIL_TRY(m.h_tlen.ensure(lines));
+  TAIL_TRY(m.h_pair_begin.ensure((size_t)n + 1));
   if (nr) {
-    TAIL_TRY(hipMemcpyAsync(m.h_perm.p, m.perm.p, (size_t)nr * 4, hipMemcpyDeviceToHost, stream));
-    TAIL_TRY(hipMemcpyAsync(m.h_pflag.p, m.pflag.p, (size_t)nr * 2, hipMemcpyDeviceToHost, stream));
-    TAIL_TRY(hipMemcpyAsync(m.h_mtid.p, m.mtid.p, (size_t)nr * 4, hipMemcpyDeviceToHost, stream));
-    TAIL_TRY(hipMemcpyAsync(m.h_mpos0.p, m.mpos0.p, (size_t)nr * 4, hipMemcpyDeviceToHost, stream));
-    TAIL_TRY(hipMemcpyAsync(m.h_tlen.p, m.tlen.p, (size_t)nr * 4, hipMemcpyDeviceToHost, stream));
+    TAIL_TRY(hipMemcpyAsync(m.h_perm, m.perm, (size_t)nr * 4, hipMemcpyDeviceToHost, stream));
+    TAIL_TRY(hipMemcpyAsync(m.h_pflag, m.pflag, (size_t)nr * 2, hipMemcpyDeviceToHost, stream));
+    TAIL_TRY(hipMemcpyAsync(m.h_mtid, m.mtid, (size_t)nr * 4, hipMemcpyDeviceToHost, stream));
+    TAIL_TRY(hipMemcpyAsync(m.h_mpos0, m.mpos0, (size_t)nr * 4, hipMemcpyDeviceToHost, stream));
+    TAIL_TRY(hipMemcpyAsync(m.h_tlen, m.tlen, (size_t)nr * 4, hipMemcpyDeviceToHost, stream));
   }
-  TAIL_TRY(hipMemcpyAsync(m.h_pair_begin.p, m.pair_begin.p, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost, stream));
+  TAIL_TRY(hipMemcpyAsync(m.h_pair_begin, m.pair_begin, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost, stream));
   // the rescued records (records last_nr .. last_nr + n_resc - 1), their offsets as they stand (from run()'s totals on)
   const uint32_t k = m.n_resc, first = m.last_nr;
-  TAIL_TRY(m.h_r_flag.need(std::max<size_t>(k, 1) * 2));
-  TAIL_TRY(m.h_r_tid.need(std::max<size_t>(k, 1) * 4));
-  TAIL_TRY(m.h_r_pos0.need(std::max<size_t>(k, 1) * 4));
-  TAIL_TRY(m.h_r_nm.need(std::max<size_t>(k, 1)));
-  TAIL_TRY(m.h_r_cigar_off.need(((size_t)k + 1) * 4));
-  TAIL_TRY(m.h_r_md_off.need(((size_t)k + 1) * 4));
+  TAIL_TRY(m.h_r_flag.ensure(std::max<size_t>(k, 1)));
+  TAIL_TRY(m.h_r_tid.ensure(std::max<size_t>(k, 1)));
+  TAIL_TRY(m.h_r_pos0.ensure(std::max<size_t>(k, 1)));
+  TAIL_TRY(m.h_r_nm.ensure(std::max<size_t>(k, 1)));
+  TAIL_TRY(m.h_r_cigar_off.ensure((size_t)k + 1));
+  TAIL_TRY(m.h_r_md_off.ensure((size_t)k + 1));
   if (k) {
-    TAIL_TRY(hipMemcpyAsync(m.h_r_flag.p, m.flag.as<uint16_t>() + first, (size_t)k * 2, hipMemcpyDeviceToHost, stream));
-    TAIL_TRY(hipMemcpyAsync(m.h_r_tid.p, m.tid.as<uint32_t>() + first, (size_t)k * 4, hipMemcpyDeviceToHost, stream));
-    TAIL_TRY(hipMemcpyAsync(m.h_r_pos0.p, m.pos0.as<uint32_t>() + first, (size_t)k * 4, hipMemcpyDeviceToHost, stream));
-    TAIL_TRY(hipMemcpyAsync(m.h_r_nm.p, m.nm.as<uint8_t>() + first, k, hipMemcpyDeviceToHost, stream));
-    TAIL_TRY(hipMemcpyAsync(m.h_r_cigar_off.p, m.cigar_off.as<uint32_t>() + first, ((size_t)k + 1) * 4, hipMemcpyDeviceToHost, stream));
-    TAIL_TRY(hipMemcpyAsync(m.h_r_md_off.p, m.md_off.as<uint32_t>() + first, ((size_t)k + 1) * 4, hipMemcpyDeviceToHost, stream));
+    TAIL_TRY(hipMemcpyAsync(m.h_r_flag, m.flag + first, (size_t)k * 2, hipMemcpyDeviceToHost, stream));
+    TAIL_TRY(hipMemcpyAsync(m.h_r_tid, m.tid + first, (size_t)k * 4, hipMemcpyDeviceToHost, stream));
+    TAIL_TRY(hipMemcpyAsync(m.h_r_pos0, m.pos0 + first, (size_t)k * 4, hipMemcpyDeviceToHost, stream));
+    TAIL_TRY(hipMemcpyAsync(m.h_r_nm, m.nm + first, k, hipMemcpyDeviceToHost, stream));
+    TAIL_TRY(hipMemcpyAsync(m.h_r_cigar_off, m.cigar_off + first, ((size_t)k + 1) * 4, hipMemcpyDeviceToHost, stream));
+    TAIL_TRY(hipMemcpyAsync(m.h_r_md_off, m.md_off + first, ((size_t)k + 1) * 4, hipMemcpyDeviceToHost, stream));
   }
   TAIL_TRY(hipStreamSynchronize(stream));
-  const uint32_t *co = m.h_r_cigar_off.as<uint32_t>(), *mo = m.h_r_md_off.as<uint32_t>();
+  const uint32_t *co = m.h_r_cigar_off, *mo = m.h_r_md_off;
   const size_t n_cig = k ? co[k] - co[0] : 0, n_md = k ? mo[k] - mo[0] : 0;
-  TAIL_TRY(m.h_r_cigar.need(std::max<size_t>(n_cig, 1) * 4));
-  TAIL_TRY(m.h_r_md.need(std::max<size_t>(n_md, 1)));
-  if (n_cig) TAIL_TRY(hipMemcpyAsync(m.h_r_cigar.p, m.cigar.as<uint32_t>() + co[0], n_cig * 4, hipMemcpyDeviceToHost, stream));
-  if (n_md) TAIL_TRY(hipMemcpyAsync(m.h_r_md.p, m.md.as<uint8_t>() + mo[0], n_md, hipMemcpyDeviceToHost, stream));
+  TAIL_TRY(m.h_r_cigar.ensure(std::max<size_t>(n_cig, 1)));
+  TAIL_TRY(m.h_r_md.ensure(std::max<size_t>(n_md, 1)));
+  if (n_cig) TAIL_TRY(hipMemcpyAsync(m.h_r_cigar, m.cigar + co[0], n_cig * 4, hipMemcpyDeviceToHost, stream));
+  if (n_md) TAIL_TRY(hipMemcpyAsync(m.h_r_md, m.md + mo[0], n_md, hipMemcpyDeviceToHost, stream));
   if (n_cig || n_md) TAIL_TRY(hipStreamSynchronize(stream));
-  out->n_pairs = n / 2u, out->n_records = nr, out->n_proper = m.h_pair_ctl.as<uint32_t>()[0];
-  out->pair_begin = m.h_pair_begin.as<uint32_t>(), out->perm = m.h_perm.as<uint32_t>(), out->flag = m.h_pflag.as<uint16_t>();
-  out->mate_tid = m.h_mtid.as<uint32_t>(), out->mate_pos0 = m.h_mpos0.as<uint32_t>(), out->tlen = m.h_tlen.as<int32_t>();
+  out->n_pairs = n / 2u, out->n_records = nr, out->n_proper = m.h_pair_ctl[0];
+  out->pair_begin = m.h_pair_begin, out->perm = m.h_perm, out->flag = m.h_pflag;
+  out->mate_tid = m.h_mtid, out->mate_pos0 = m.h_mpos0, out->tlen = m.h_tlen;
   out->first_rescued = first, out->n_rescued = k;
-  out->r_flag = m.h_r_flag.as<uint16_t>(), out->r_tid = m.h_r_tid.as<uint32_t>(), out->r_pos0 = m.h_r_pos0.as<uint32_t>();
-  out->r_nm = m.h_r_nm.as<uint8_t>(), out->r_cigar_off = co, out->r_cigar = m.h_r_cigar.as<uint32_t>();
-  out->r_md_off = mo, out->r_md = m.h_r_md.as<char>();
+  out->r_flag = m.h_r_flag, out->r_tid = m.h_r_tid, out->r_pos0 = m.h_r_pos0;
+  out->r_nm = m.h_r_nm, out->r_cigar_off = co, out->r_cigar = m.h_r_cigar;
+  out->r_md_off = mo, out->r_md = m.h_r_md;
   return FEM_OK;
 }
 

@@ -16,7 +16,7 @@ ABI_SYMBOLS = [
     "fem_dev_fetch_records", "fem_dev_seed_kernel", "fem_dev_index_info",
     "fem_dev_upload_reference_names", "fem_dev_acquire_text_stage", "fem_dev_commit_text_stage", "fem_dev_commit_names_stage", "fem_dev_sam_quals", "fem_dev_reserve_text", "fem_dev_reserve_batch", "fem_set_blocking_waits", "fem_dev_fetch_sam", "fem_dev_fetch_sam_nowait", "fem_dev_sam_wait",
     "fem_dev_set_timing", "fem_dev_reset_timing", "fem_dev_kernel_time", "fem_dev_copy_bandwidth",
-    "fem_dev_h2d_bandwidth",
+    "fem_dev_h2d_bandwidth", "fem_dbg_live_bytes",
     "fem_device_numa", "fem_bind_thread_near_device",
     "fem_dev_allreduce_stats",
     "fem_dev_set_pairs", "fem_dev_fetch_pairs", "fem_dev_pair_count",
@@ -170,6 +170,8 @@ def load_hip():
         L.fem_dev_fetch_bam_nowait.argtypes = [vp, C.c_int, C.c_int, C.POINTER(_BatchBam)]
         L.fem_dev_bam_wait.argtypes = [vp, C.c_int]
         L.fem_dev_bgzf_compress.argtypes = [vp, vp, u64, C.c_int, vp, u64, C.POINTER(u64)]
+    if hasattr(L, "fem_dbg_live_bytes"):
+        L.fem_dbg_live_bytes.argtypes = [C.POINTER(u64), C.POINTER(u64)]
     L.fem_device_numa.argtypes = [C.c_int, C.POINTER(C.c_int32), C.c_char_p, u64]
     L.fem_bind_thread_near_device.argtypes = [C.c_int]
     _HIP = L
@@ -189,6 +191,15 @@ def device_numa(device=0):
 def bind_near_device(device=0):
     """Restricts the calling thread (and the threads it starts later) to the CPUs next to GPU `device`; True if bound."""
     return load_hip().fem_bind_thread_near_device(int(device)) == 0
+
+
+def live_bytes():
+    """fem_dbg_live_bytes: (device bytes, pinned host bytes) the library's buffers hold now, over all handles of the process."""
+    dev, pin = C.c_uint64(), C.c_uint64()
+    rc = load_hip().fem_dbg_live_bytes(C.byref(dev), C.byref(pin))
+    if rc != 0:
+        raise FemError("fem_dbg_live_bytes: %d" % rc)
+    return dev.value, pin.value
 
 
 def packed_layout(n_reads, read_len):

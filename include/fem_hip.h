@@ -477,6 +477,10 @@ int fem_dev_kernel_time(fem_dev *h, int kernel, double *ms_total, uint64_t *laun
 int fem_dev_copy_bandwidth(fem_dev *h, uint64_t bytes, int iters, double *gb_per_s);
 /* Achieved pinned-host-to-device bandwidth in GB/s (what bounds the read stream). */
 int fem_dev_h2d_bandwidth(fem_dev *h, uint64_t bytes, int iters, double *gb_per_s);
+/* Debug: the bytes of device memory and of pinned host memory that the library's buffers hold at this moment, summed
+ * over every handle of the process (either pointer may be null).  Needs no handle; back at its earlier value once a
+ * handle is closed. */
+int fem_dbg_live_bytes(uint64_t *device_bytes, uint64_t *pinned_bytes);
 
 /* ---- host placement (new; the reference leaves its threads to the scheduler, src/FEM_map.c:172-198) ---- */
 /* NUMA node of the host memory GPU `device` is attached to (-1 if the system does not say) and that node's CPUs
