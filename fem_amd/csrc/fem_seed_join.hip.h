@@ -37,10 +37,20 @@ namespace femk {
 //      validity is one scalar AND of masks the loads' compares left behind
 //   4  a second chunk only for the runs that have one (was: for every run of a unit in which some list is long)
 //   8  marks under `if (hit)` alone (the ballot around it cost three scalar instructions per chunk)
+// Round 11, the flag phase and the marks of the common unit (docs/NOTEBOOK.md, round 11):
+//  16  the flagged values of a unit's first chunks are compacted ONCE per unit: a chunk only moves its flagged lanes' values into
+//      one register (`fl`) and ORs their lanes into a scalar mask; the store into the group's array happens when a lane is flagged
+//      a second time and at the unit's end.  (Only in the forms of bit 2; the order within the array becomes lane-major.)
+//  32  with 16: no mask of the lanes that hold an entry per chunk — a lane without one holds a value >= kDenseVLimit (a pad of the
+//      table, sent_a - start, sent_b), so validity is the one compare of the flush
+//  64  the marks of a slot's second value go into the word the insert addressed, as (hit << 1) | (hit >> 1); only a hit in bit 0
+//      or bit 31 writes its one neighbour in the next word
+// C3, join ms per 2.5 M reads: 15: 6.28-6.30, 15+16: 6.25, 15+16+32: 6.07, 15+64: 6.27, all: 6.07-6.11.  At R >= 7 they stay off: 16 and
+// 32 need bit 2, and 64 costs the 80-register kernels scratch (seed_join_kernel_r9 12 -> 20 bytes, padded r10 32 -> 44).
 // At R >= 7 the kernel lives in the 80 registers of six waves per SIMD: 1 and 2 (their lane constants and masks) spill there
 // and cost more than they save (C5, ms per 2.5 M reads: none 14.85, 1: 15.2, 1+2: 15.7, all four 16.1, 1+4+8: 14.8).
 #ifndef FEM_JOIN_OPT
-#define FEM_JOIN_OPT 15
+#define FEM_JOIN_OPT 127
 #endif
 #ifndef FEM_JOIN_OPT_HI
 #define FEM_JOIN_OPT_HI 12
@@ -113,6 +123,7 @@ __device__ bool join_read(const SeedParams &p, uint32_t s_start, uint32_t s_lo, 
   // (PADDED — the strided table with its pads, fem_seed_dense.hip.h: lanes behind a list's end hold a sentinel of their own by
   //  the load itself, so the forms of bit 2 cost nothing: no lane constant, the masks of valid lanes are scalar bit fields)
   constexpr bool kOptPairs = (kOpt & 1) != 0, kOptSent = (kOpt & 2) != 0 || (PADDED && R <= 6), kOptLong = (kOpt & 4) != 0, kOptHit = (kOpt & 8) != 0;
+  constexpr bool kOptOnce = (kOpt & 16) != 0 && kOptSent, kOptNoMask = (kOpt & 32) != 0 && kOptOnce, kOptOwn = (kOpt & 64) != 0;
   constexpr bool kSecondProbe = true;  // weed the chance flags out before the exact filter ...
   constexpr uint32_t kProbeMin = kOptPairs ? 16u : 8u;  // ... when there are more flagged values than this (what the all-pairs filter takes)
   constexpr uint32_t kFlgStride = kFlagCap + 1u;     // the entry behind a group's array takes the overflow writes
@@ -172,11 +183,15 @@ __device__ bool join_read(const SeedParams &p, uint32_t s_start, uint32_t s_lo, 
   // ---- the steps of the join for one chunk.  A lane without an entry holds kDenseSent (>= kDenseVLimit); nothing here
   //      branches on that: such a lane ORs a zero into a word of its own (lane index: no bank conflict), reads some
   //      window and is masked out of the flagged set ----
-  auto insert = [&](uint32_t v) -> uint32_t {  // -> own bit if the slot already held a value, else 0
+  // (the slot's word is handed from an insert to its marks as a pointer INTO LDS: as a plain pointer it went through a select in
+  //  the full body and came out "flat" — flat_atomic_or instead of ds_or_b32)
+  typedef __attribute__((address_space(3))) uint32_t *LdsWord;
+  auto insert = [&](uint32_t v, LdsWord &w) -> uint32_t {  // -> own bit if the slot already held a value, else 0; w: the slot's word
     const bool valid = v < kDenseVLimit;
     const uint32_t bit = valid ? 1u << ((v >> 3) & 31u) : 0u;
     const uint32_t widx = valid ? __builtin_amdgcn_ubfe(v, 8u, kWordBits) : ln;
-    return lds_or_rtn(bitmap + widx, bit) & bit;
+    w = (LdsWord)(bitmap + widx);
+    return lds_or_rtn((uint32_t *)w, bit) & bit;
   };
   // word of the bitmap that holds slot q >> 5 ... as v_bfe + v_lshl_add: left alone the compiler makes shift, and, add of it
   auto word_of = [&](uint32_t x, uint32_t from) -> uint32_t * {
@@ -184,19 +199,31 @@ __device__ bool join_read(const SeedParams &p, uint32_t s_start, uint32_t s_lo, 
     asm("" : "+v"(idx));
     return bitmap + idx;
   };
-  auto insert_plain = [&](uint32_t v) -> uint32_t {  // the same where every lane holds a value or a sentinel of its own
+  auto insert_plain = [&](uint32_t v, LdsWord &w) -> uint32_t {  // the same where every lane holds a value or a sentinel of its own
     const uint32_t bit = 1u << ((v >> 3) & 31u);
-    return lds_or_rtn(word_of(v, 8u), bit) & bit;
+    w = (LdsWord)word_of(v, 8u);
+    return lds_or_rtn((uint32_t *)w, bit) & bit;
   };
-  auto mark = [&](uint32_t v, uint32_t hit) {  // second value of a slot: both neighbours "present"
+  // second value of a slot: both neighbours "present".  `hit` is the lane's own bit in `w`, the word its insert addressed: 30 of the
+  // 32 bit positions have both neighbours in that word (kOptOwn: one OR); bit 0 and bit 31 write the one that lies in the word
+  // before / behind (word_of wraps at the table's ends as before; the guard word is never written)
+  auto mark = [&](uint32_t v, uint32_t hit, LdsWord w) {
     if (FEM_JOIN_ABL & 4) {
       asm volatile("" ::"v"(hit));
       return;
     }
     if (hit) {
-      const uint32_t qm = (v >> 3) - 1u, qp = (v >> 3) + 1u;
-      lds_or(word_of(qm, 5u), 1u << (qm & 31u));
-      lds_or(word_of(qp, 5u), 1u << (qp & 31u));
+      if (kOptOwn) {
+        lds_or((uint32_t *)w, (hit << 1) | (hit >> 1));
+        if (hit & 0x80000001u) {
+          const uint32_t q = (hit >> 31) != 0u ? (v >> 3) + 1u : (v >> 3) - 1u;
+          lds_or(word_of(q, 5u), 1u << (q & 31u));
+        }
+      } else {
+        const uint32_t qm = (v >> 3) - 1u, qp = (v >> 3) + 1u;
+        lds_or(word_of(qm, 5u), 1u << (qm & 31u));
+        lds_or(word_of(qp, 5u), 1u << (qp & 31u));
+      }
     }
   };
   auto window = [&](uint32_t v) -> uint32_t {  // bit 0: slot - 1 present, bit 1: own slot, bit 2: slot + 1
@@ -293,8 +320,9 @@ __device__ bool join_read(const SeedParams &p, uint32_t s_start, uint32_t s_lo, 
         w[0] = 0u, w[1] = 0u;
       };
       const uint32_t k0 = key2(v0), k1 = key2(v1);
-      const uint32_t h0 = insert(have0 ? k0 : kDenseSent), h1 = insert(have1 ? k1 : kDenseSent);
-      if (__builtin_amdgcn_ballot_w64((h0 | h1) != 0u)) mark(k0, h0), mark(k1, h1);
+      LdsWord w0, w1;
+      const uint32_t h0 = insert(have0 ? k0 : kDenseSent, w0), h1 = insert(have1 ? k1 : kDenseSent, w1);
+      if (__builtin_amdgcn_ballot_w64((h0 | h1) != 0u)) mark(k0, h0, w0), mark(k1, h1, w1);
       wave_sync_lds();
       const bool keep0 = have0 && (edge(v0) || (window(k0) & 5u) != 0u);
       const bool keep1 = have1 && (edge(v1) || (window(k1) & 5u) != 0u);

@@ -10,10 +10,10 @@
 // __forceinline__` function taking these names as parameters has NOT been tried.
 //
 // What the text expects from join_read at the place of inclusion:
-//   template parameters / constants  R, BANKED, PADDED, kOptSent, kOptLong, kOptHit, kFlagCap, kWords, kNearTop
+//   template parameters / constants  R, BANKED, PADDED, kOptSent, kOptLong, kOptHit, kOptOnce, kOptNoMask, kFlagCap, kWords, kNearTop
 //   the unit                         u, f[R], st[R], f_max, keep_all, val[R] (first chunks, raw; changed here), flg_g, n_flag (out)
 //   the read / the wave              p, ln, lane4, e, seq_base, sent_a, sent_b, bitmap
-//   helpers                          run_base, insert, insert_plain, mark, window_top
+//   helpers                          run_base, insert, insert_plain, mark, window_top, LdsWord
 // and that `return false` leaves join_read (more flagged values than the group's array takes: the read goes to the generic kernel).
 #ifndef FEM_JOIN_UNIT_PLAIN
 #error "fem_seed_join_unit.hip.h is a part of join_read (fem_seed_join.hip.h): define FEM_JOIN_UNIT_PLAIN true or false and include it there"
@@ -87,7 +87,7 @@
         }
         any_u = __builtin_amdgcn_ballot_w64(have_u != 0) != 0;
         max_u = wave_max_u32(mx);
-        if (kOptSent) {
+        if (kOptSent && !kOptNoMask) {
 #pragma unroll
           for (int t = 0; t < R; ++t) vm[t] = __builtin_amdgcn_ballot_w64(val[t] < kDenseVLimit);
         }
@@ -95,15 +95,16 @@
         // every entry is real and lists ascend: the maximum of U is the largest last entry of runs 0..R-2
         if (kOptSent) {
           // a lane behind the list's end takes a sentinel of its own (sent_a - start: no two in one slot, fem_seed_join.hip.h
-          // top) instead of the list's last entry again; which lanes hold entries stays behind as a scalar mask
+          // top) instead of the list's last entry again; which lanes hold entries stays behind as a scalar mask (kOptNoMask: it
+          // does not — every such lane holds a value >= kDenseVLimit, which the flush of the flagged values tests once)
 #pragma unroll
           for (int t = 0; t < R; ++t) {
             if (PADDED) {
-              vm[t] = __builtin_amdgcn_ballot_w64(ln < f[t]);  // (one v_cmp into a scalar pair; as scalar arithmetic on f it is six instructions)
+              if (!kOptNoMask) vm[t] = __builtin_amdgcn_ballot_w64(ln < f[t]);  // (one v_cmp into a scalar pair; as scalar arithmetic on f it is six instructions)
               val[t] -= st[t];
             } else {
               const bool in = ln < f[t];
-              vm[t] = __builtin_amdgcn_ballot_w64(in);  // (the compare's own result: no instruction)
+              if (!kOptNoMask) vm[t] = __builtin_amdgcn_ballot_w64(in);  // (the compare's own result: no instruction)
               val[t] = (in ? val[t] : sent_a) - st[t];
             }
           }
@@ -139,7 +140,7 @@
         // the last run keeps values <= max(U) only (src/filter.c:85); everything dropped becomes a sentinel
         if (kOptSent) {
           const bool keep = val[R - 1] <= max_u;
-          vm[R - 1] &= __builtin_amdgcn_ballot_w64(keep);
+          if (!kOptNoMask) vm[R - 1] &= __builtin_amdgcn_ballot_w64(keep);
           val[R - 1] = keep ? val[R - 1] : sent_b;
         } else {
           val[R - 1] = val[R - 1] <= max_u ? val[R - 1] : kDenseSent;
@@ -156,9 +157,35 @@
         // and a flagged lane WITHOUT an entry — always above the run's lanes with one: lists ascend, both ends of a run are
         // cut from the top — stores its sentinel at the place the next flagged value will take, or behind the last one,
         // where the exact filter reads it as "no value" (it lies above every coordinate).
+        // kOptOnce, the forms without `exact`: a chunk only gathers — its flagged lanes' values into `fl`, their lanes into `acc` —
+        // and the flagged values are compacted into the group's array by `flush`, when a lane is flagged a second time and once at
+        // the unit's end.  A lane that holds no flagged value since the last flush has fl = 0xFFFFFFFF, a flagged lane without an
+        // entry its sentinel: both >= kDenseVLimit, so the flush's one compare is the validity test (no sentinel is stored: behind
+        // the values the array reads "no value" by join_read's fill).  Within a flush the values lie in lane order.
+        uint32_t fl = 0xFFFFFFFFu;
+        uint64_t acc = 0;
+        auto flush = [&]() {
+          const bool ok = fl < kDenseVLimit;
+          const uint64_t m = __builtin_amdgcn_ballot_w64(ok);
+          uint32_t pos = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, n_flag));
+          pos = pos < kFlagCap ? pos : kFlagCap;
+          if (ok) flg_g[pos] = fl;
+          n_flag += (uint32_t)__popcll(m);
+          fl = 0xFFFFFFFFu;
+          acc = 0;
+        };
         auto flag_chunk = [&](uint32_t v, uint32_t xw, uint64_t valid, bool exact) {
           if (FEM_JOIN_ABL & 1) {
             asm volatile("" ::"v"(xw), "v"(v));
+            return;
+          }
+          if (kOptOnce && !exact) {
+            const bool near_ = xw >= kNearTop;
+            const uint64_t m = __builtin_amdgcn_ballot_w64(near_);
+            if ((kOptNoMask ? m : m & valid) == 0) return;  // (wave-uniform)
+            if ((m & acc) != 0) flush();
+            fl = near_ ? v : fl;
+            acc |= m;
             return;
           }
           bool near = xw >= kNearTop;
@@ -174,12 +201,13 @@
 #pragma unroll
           for (int t0 = 0; t0 < R; t0 += kBatch) {
             uint32_t hit[kBatch];
+            LdsWord hw[kBatch];  // the word each insert addressed: the marks go there (kOptOwn; set wherever hit[q] can be non-zero)
 #pragma unroll
             for (int q = 0; q < kBatch; ++q)
               if (t0 + q < R) {
                 hit[q] = 0;
                 if (second && kOptLong && f[t0 + q] <= (uint32_t)kWave) continue;
-                hit[q] = checked ? insert(vals[t0 + q]) : insert_plain(vals[t0 + q]);
+                hit[q] = checked ? insert(vals[t0 + q], hw[q]) : insert_plain(vals[t0 + q], hw[q]);
               }
             // a slot that took a second value (every true hit does): chunk by chunk, only where some lane saw one
 #pragma unroll
@@ -187,9 +215,9 @@
               if (t0 + q < R) {
                 if (second && kOptLong && f[t0 + q] <= (uint32_t)kWave) continue;
                 if (kOptHit) {
-                  mark(vals[t0 + q], hit[q]);
+                  mark(vals[t0 + q], hit[q], hw[q]);
                 } else if (__builtin_amdgcn_ballot_w64(hit[q] != 0u)) {
-                  mark(vals[t0 + q], hit[q]);
+                  mark(vals[t0 + q], hit[q], hw[q]);
                 }
               }
           }
@@ -211,6 +239,7 @@
                 flag_chunk(vals[t0 + q], x[q], vm[t0 + q], exact);
               }
           }
+          if (kOptOnce && !exact && acc != 0) flush();
         };
         if (FEM_JOIN_ABL & 64) {
 #pragma unroll
