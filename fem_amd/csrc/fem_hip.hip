@@ -55,6 +55,7 @@ constexpr int kSlots = FEM_SLOTS;
 constexpr uint32_t kMaxReadLen = 1024;
 constexpr size_t kFrontPad = 16;  // kernels fetch a reverse-strand chunk from up to 15 bytes in front of a read
 constexpr size_t kPackedFrontPad = 256;  // ... and verify_kernel_packed up to 16 bytes in front of a read's codes (a multiple of hipMalloc's alignment)
+constexpr uint64_t kExpandAllShare = 8;  // a packed batch with more exceptions than one per this many reads is expanded whole at commit
 constexpr uint32_t kXcapSmall = 512, kFcap = 128, kCcap = 128;
 
 constexpr int kTimedKernels = 16;  // fem_dev_kernel_time ids: 0 seed (join), 1 verify, 2 generic seed, 3-5 tail, 6 pack_results_kernel (round 5; the count kernel of rounds 1-2 before), 7 SAM text, 8 seed selection, 9 pairing, 10 mate rescue, 11 BAM records, 12 BGZF, 13 MAPQ, 14 the line index with unmapped reads, 15 the line filter's line index
@@ -102,6 +103,11 @@ struct Slot {
   uint64_t prefetched_reads2 = 0, prefetched_cand = 0, last_n_cand = 0;
   uint64_t h2d_bytes = 0;                 // what the last staging sent over the link
   bool sent_packed = false;
+  // A packed batch's characters (bases(), d_off) are made when something asks for them (ensure_chars); until then only the
+  // reads marked in d_exc_bits have theirs.  select_packed: the slot's last dense mapping read the codes in seed_select_kernel.
+  bool chars_ready = true, offs_ready = true, select_packed = false;  // (offs_ready: d_off alone is filled, see enqueue_packed)
+  uint64_t n_exc = 0;   // exceptions of the packed batch (their positions and bytes lie behind its codes in packed())
+  Event ev_chars;       // the expansion on the slot's stream is done (a tail on another stream waits for it)
   // A batch committed to an IDLE device is sent and mapped in `parts` pieces (reads [part_begin[q], part_begin[q + 1])), so that
   // the join of its first piece starts after a quarter of the copy and a quarter of the selection (launch_batch): the fill of
   // the pipeline.  ev_part[q]: piece q's characters are in HBM; ev_sel[q]: its selection is done.
@@ -275,6 +281,7 @@ struct fem_dev {
   Buf<uint32_t> d_occ32, d_goff, d_blkseq;
   uint32_t list_shift = 0;        // != 0: d_occ32 is the strided table (bucket h at h << list_shift, fem_seed_dense.hip.h); 0: compact
   bool no_strided = false;        // FEM_NO_STRIDED=1: keep the compact 32-bit table (test hook / A-B)
+  bool select_chars = false;      // FEM_SELECT_CHARS=1: packed batches are expanded at commit and selected from characters (test hook / A-B)
   bool verify_chars = false;      // FEM_VERIFY_CHARS=1: verify_kernel (characters) on packed batches too (test hook / A-B)
   Buf<uint32_t> d_freq11;  // saturated byte frequencies per 11-mer (fem_seed_select.hip.h), 64 MiB
   // banks of sequences, each with 32-bit coordinates of its own (fem_seed_dense.hip.h); 1 = the whole reference in one
@@ -459,7 +466,7 @@ femk::SeedLayout make_layout_fast(const fem_params &p, uint32_t max_len, bool ha
 // on `nb` at a time, as many as a budget of 3 KB of 16-bit frequencies holds (a block of four waves then stays within the
 // 16 KB that six blocks of the join leave of a CU's LDS) (the kernel runs beside seed_join_kernel, whose
 // bitmaps want the LDS).
-femk::SeedLayout make_layout_select(const fem_params &p, uint32_t max_len) {
+femk::SeedLayout make_layout_select(const fem_params &p, uint32_t max_len, bool packed) {
   femk::SeedLayout l{};
   const uint32_t R = (uint32_t)(p.e + 1 + p.a);
   l.smax = max_len >= (uint32_t)p.k ? max_len - (uint32_t)p.k + 1u : 1u;
@@ -471,7 +478,9 @@ femk::SeedLayout make_layout_select(const fem_params &p, uint32_t max_len) {
   l.gstride += l.gstride & 1u;
   if (!((l.gstride >> 1) & 1u)) l.gstride += 2u;
   l.nb = std::max<uint32_t>(1u, std::min<uint32_t>(femk::kReadBlock, 3100u / (2u * 2u * l.gstride)));
-  l.strm_words = (l.nb * max_len + 15u) / 16u + 2u;
+  // (a packed batch's reads lie in the stream as they came, each padded to a whole byte = four bases: up to three words more
+  //  per stream where the length is no multiple of four; a batch of characters keeps the layout it had)
+  l.strm_words = (l.nb * (packed ? (max_len + 3u) & ~3u : max_len) + 15u) / 16u + 2u;
   uint32_t o = 0;
   auto take = [&](uint32_t bytes) {
     uint32_t at = o;
@@ -510,17 +519,20 @@ femk::SeedLayout make_layout_join(const fem_params &p, bool banked, bool padded 
 
 typedef void (*SeedKernel)(femk::SeedParams);
 template <size_t... I>
-SeedKernel select_kernel_of(int R, bool banked, std::index_sequence<I...>) {
-  static const SeedKernel k[2][femk::kMaxR] = {{femk::seed_select_kernel<(int)I + 1, false>...}, {femk::seed_select_kernel<(int)I + 1, true>...}};
-  return k[banked][std::min(std::max(R, 1), femk::kMaxR) - 1];
+SeedKernel select_kernel_of(int R, bool banked, bool packed, std::index_sequence<I...>) {
+  static const SeedKernel k[2][2][femk::kMaxR] = {
+      {{femk::seed_select_kernel<(int)I + 1, false, false>...}, {femk::seed_select_kernel<(int)I + 1, true, false>...}},
+      {{femk::seed_select_kernel<(int)I + 1, false, true>...}, {femk::seed_select_kernel<(int)I + 1, true, true>...}}};
+  return k[packed][banked][std::min(std::max(R, 1), femk::kMaxR) - 1];
 }
 template <size_t... I>
 SeedKernel fast_kernel_of(int R, bool hash, std::index_sequence<I...>) {
   static const SeedKernel k[2][femk::kMaxR] = {{femk::seed_fast_kernel<(int)I + 1, false>...}, {femk::seed_fast_kernel<(int)I + 1, true>...}};
   return k[hash][std::min(std::max(R, 1), femk::kMaxR) - 1];
 }
-// (`banked`: the reference's sequences lie in more than one coordinate space, fem_seed_dense.hip.h)
-SeedKernel select_kernel(int R, bool banked) { return select_kernel_of(R, banked, std::make_index_sequence<femk::kMaxR>{}); }
+// (`banked`: the reference's sequences lie in more than one coordinate space, fem_seed_dense.hip.h; `packed`: the batch's
+//  2-bit codes are read, SeedParams::packed, not its characters)
+SeedKernel select_kernel(int R, bool banked, bool packed) { return select_kernel_of(R, banked, packed, std::make_index_sequence<femk::kMaxR>{}); }
 // (`hash`: the hash-join form for long occurrence lists; otherwise the lean one, lists in lanes only)
 SeedKernel fast_kernel(int R, bool hash) { return fast_kernel_of(R, hash, std::make_index_sequence<femk::kMaxR>{}); }
 // which = 0: the compact table, 1: references in banks (compact, cut at bank_lo), 2: the strided table with its pads
@@ -544,19 +556,19 @@ int blocks_per_cu(const void *kernel, int block, uint32_t lds) {
 }
 // vector registers per lane of seed_join_kernel<R> / seed_select_kernel<R>
 // (handles of several GPUs launch from their own threads: the cache is atomic; every thread would store the same value)
-uint32_t kernel_regs(int R, bool join, int which = 0) {
-  static std::atomic<uint32_t> cache[3][2][femk::kMaxR + 1] = {};
-  std::atomic<uint32_t> &slot = cache[which][join ? 1 : 0][std::min(std::max(R, 1), femk::kMaxR)];
+uint32_t kernel_regs(int R, bool join, int which = 0, bool packed = false) {
+  static std::atomic<uint32_t> cache[3][3][femk::kMaxR + 1] = {};
+  std::atomic<uint32_t> &slot = cache[which][join ? 1 : packed ? 2 : 0][std::min(std::max(R, 1), femk::kMaxR)];
   uint32_t c = slot.load(std::memory_order_relaxed);
   if (c) return c;
   hipFuncAttributes a{};
-  const void *f = join ? (const void *)join_kernel(R, which) : (const void *)select_kernel(R, which == 1);
+  const void *f = join ? (const void *)join_kernel(R, which) : (const void *)select_kernel(R, which == 1, packed);
   c = hipFuncGetAttributes(&a, f) == hipSuccess && a.numRegs > 0 ? (uint32_t)a.numRegs : 128u;
   slot.store(c, std::memory_order_relaxed);
   return c;
 }
 void launch_select(int R, bool banked, dim3 grid, dim3 block, uint32_t lds, hipStream_t st, const femk::SeedParams &sp) {
-  hipLaunchKernelGGL(select_kernel(R, banked), grid, block, lds, st, sp);
+  hipLaunchKernelGGL(select_kernel(R, banked, sp.packed != nullptr), grid, block, lds, st, sp);
 }
 void launch_join(int R, int which, dim3 grid, dim3 block, uint32_t lds, hipStream_t st, const femk::SeedParams &sp) {
   hipLaunchKernelGGL(join_kernel(R, which), grid, block, lds, st, sp);
@@ -742,6 +754,8 @@ int enqueue_pack(fem_dev *h, Slot &s, bool kernel, bool send_home) {
   return FEM_OK;
 }
 
+int ensure_chars(fem_dev *h, Slot &s);
+
 // Enqueue the two kernels of one batch on the slot's stream (asynchronous).
 int launch_batch(fem_dev *h, Slot &s) {
   const fem_params &p = s.params;
@@ -771,7 +785,20 @@ int launch_batch(fem_dev *h, Slot &s) {
     HIP_TRY(h, hipMemsetAsync(s.d_ctl, 0, kCtlAlloc, s.stream));
   }
 
+  const int R_all = p.e + 1 + p.a;
+  const bool dense_kernels = !h->force_generic && p.k == femk::kK && p.step == femk::kStep && R_all >= 1 && R_all <= femk::kMaxR && h->d_occ32 && h->d_freq11;
+  // Who reads a whole batch's characters gets them made first (ensure_chars): seed_fast_kernel, the generic kernel over all
+  // reads, verify_kernel.  The dense kernels read a packed batch's codes, and characters of its marked reads only.
+  if (s.n_reads && (!dense_kernels || h->verify_chars)) {
+    int rc = ensure_chars(h, s);
+    if (rc) return rc;
+  }
   femk::SeedParams sp{};
+  s.select_packed = false;
+  if (s.sent_packed && !h->select_chars && dense_kernels) {
+    sp.packed = s.packed(), sp.exc_bits = s.d_exc_bits, sp.bpr = s.packed_bpr, sp.len = s.max_len;
+    s.select_packed = s.n_reads != 0;
+  }
   sp.bases = s.bases();
   sp.read_off = s.d_off;
   sp.n_reads = (uint32_t)s.n_reads;
@@ -851,7 +878,7 @@ int launch_batch(fem_dev *h, Slot &s) {
       // stream as soon as its characters are in HBM, its join on the slot's stream behind its selection — beside the selection
       // of part q + 1.  Any other batch is one part, selection and join on the slot's stream as before.
       uint32_t select_lds = 0, select_threads = 256;
-      fp.lay = make_layout_select(p, max_len);
+      fp.lay = make_layout_select(p, max_len, fp.packed != nullptr);
       if (fp.lay.wave_bytes > 64u * 1024u) return fail(h, FEM_ERR_UNSUPPORTED, "read too long for the device path");
       const femk::SeedLayout lay_select = fp.lay;
       femk::SeedLayout lay_join = make_layout_join(p, banked, !banked && h->list_shift != 0);
@@ -863,8 +890,9 @@ int launch_batch(fem_dev *h, Slot &s) {
       uint64_t per_cu_s, per_cu_j;
       {
         const uint32_t lds_bytes = wpb_s * lay_select.wave_bytes;
-        const uint64_t key = ((uint64_t)banked << 48) | ((uint64_t)R << 40) | lds_bytes;
-        if (h->select_occ_key != key) h->select_occ_key = key, h->select_occ_blocks = blocks_per_cu((const void *)select_kernel(R, banked), (int)(64u * wpb_s), lds_bytes);
+        const uint64_t key = ((uint64_t)(fp.packed != nullptr) << 49) | ((uint64_t)banked << 48) | ((uint64_t)R << 40) | lds_bytes;
+        if (h->select_occ_key != key)
+          h->select_occ_key = key, h->select_occ_blocks = blocks_per_cu((const void *)select_kernel(R, banked, fp.packed != nullptr), (int)(64u * wpb_s), lds_bytes);
         per_cu_s = h->select_occ_blocks > 0 ? (uint64_t)h->select_occ_blocks : std::max<uint64_t>(1, 160u * 1024u / lds_bytes);
         if (overlap) per_cu_s = 1;  // (3.3 ms per 2.5 M reads of C3 with one block per CU as with five: sectors per second, not waves)
         select_lds = lds_bytes, select_threads = 64u * wpb_s;
@@ -876,7 +904,7 @@ int launch_batch(fem_dev *h, Slot &s) {
         if (overlap) {
           // leave one block of the next batch's seed_select_kernel room on every CU: registers (512 per lane and SIMD,
           // handed out in eights), LDS (160 KB) and wave slots (8 per SIMD) of both kernels together
-          const uint32_t vj = (kernel_regs(R, true, which) + 7u) & ~7u, vs = (kernel_regs(R, false, banked ? 1 : 0) + 7u) & ~7u;
+          const uint32_t vj = (kernel_regs(R, true, which) + 7u) & ~7u, vs = (kernel_regs(R, false, banked ? 1 : 0, fp.packed != nullptr) + 7u) & ~7u;
           const uint32_t wj = 64u * wpb_j / 256u ? 64u * wpb_j / 256u : 1u, ws = select_threads / 256u ? select_threads / 256u : 1u;  // waves per SIMD and block
           const uint32_t lj = (lds_j + 511u) & ~511u, ls = (select_lds + 511u) & ~511u;  // (LDS is handed out in pieces of 512 bytes)
           while (per_cu_j > 1 && (per_cu_j * wj * vj + ws * vs > 512u || per_cu_j * lj + ls > 160u * 1024u || per_cu_j * wj + ws > 8u)) --per_cu_j;
@@ -1162,8 +1190,34 @@ int check_slot(fem_dev *h, int slot) {
 // ---- packed read transfer: host side in fem_pack.h (the device side is unpack_reads_kernel) ----
 using fempack::pack_bases;
 
+// The whole batch's characters and offsets in HBM, for whoever reads s.bases() or s.d_off of more than the marked reads
+// (DESIGN.md 5.1 lists them): enqueued on the slot's stream, once per batch.  A batch that came as characters has them.
+int ensure_chars(fem_dev *h, Slot &s) {
+  if (s.chars_ready) return FEM_OK;
+  const uint64_t n = s.n_reads, n_exc = s.n_exc;
+  const uint32_t len = s.max_len, bpr = s.packed_bpr;
+  const uint64_t code_bytes = fempack::code_bytes(n, len);
+  if (!s.offs_ready)
+    hipLaunchKernelGGL(femk::uniform_offsets_kernel, dim3((uint32_t)std::min<uint64_t>((n + 256) / 256, (uint64_t)h->n_cu * 8u)), dim3(256), 0,
+                       s.stream, s.d_off, n, len);
+  if (n) {
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((n * bpr + 255) / 256, (uint64_t)h->n_cu * 16u);
+    hipLaunchKernelGGL(femk::unpack_reads_kernel, dim3(grid), dim3(256), 0, s.stream, (const uint8_t *)s.packed(), n, len, bpr, s.bases());
+  }
+  if (n_exc) {
+    const dim3 g((uint32_t)std::min<uint64_t>((n_exc + 255) / 256, (uint64_t)h->n_cu * 4u));
+    hipLaunchKernelGGL(femk::scatter_chars_kernel, g, dim3(256), 0, s.stream, (const uint32_t *)(s.packed() + code_bytes),
+                       (const uint8_t *)(s.packed() + code_bytes + 4u * n_exc), n_exc, s.bases());
+  }
+  HIP_TRY(h, hipGetLastError());
+  HIP_TRY(h, hipEventRecord(s.ev_chars, s.stream));
+  s.chars_ready = true, s.offs_ready = true;
+  return FEM_OK;
+}
+
 // Device side of a packed batch that sits in the slot's pinned staging (codes | uint32 positions | bytes, fem_pack.h):
-// one copy, then the characters are rebuilt in HBM byte for byte and the offset table is generated there.
+// one copy; the reads marked as holding a character other than "ACGT" get their characters and offsets at once, the
+// rest of the batch when something asks (ensure_chars).
 int enqueue_packed(fem_dev *h, Slot &s, uint64_t n, uint32_t len, uint64_t n_exc) {
   const uint32_t bpr = fempack::bytes_per_read(len);
   const uint64_t code_bytes = fempack::code_bytes(n, len), n_bases = n * (uint64_t)len;
@@ -1180,8 +1234,15 @@ int enqueue_packed(fem_dev *h, Slot &s, uint64_t n, uint32_t len, uint64_t n_exc
     s.parts = (int)std::min<uint64_t>((uint64_t)h->max_parts, n / kPartMinReads);
   for (int q = 0; q <= s.parts; ++q) s.part_begin[q] = q == s.parts ? (uint32_t)n : (uint32_t)((n * q / s.parts) & ~63ull);
   HIP_TRY(h, hipMemsetAsync(s.d_exc_bits, 0, ((size_t)n / 32 + 1) * sizeof(uint32_t), s.stream));
-  hipLaunchKernelGGL(femk::uniform_offsets_kernel, dim3((uint32_t)std::min<uint64_t>((n + 256) / 256, (uint64_t)h->n_cu * 8u)), dim3(256), 0,
-                     s.stream, s.d_off, n, len);
+  // The characters are made here only where the selection is to read them (FEM_SELECT_CHARS) or where more than one read in
+  // kExpandAllShare may be marked: expanding read by read then moves about as much as expanding the batch, less well.
+  const bool at_commit = h->select_chars || n_exc * kExpandAllShare > n;
+  // (a handle without the dense tables will ask for the characters when the batch is mapped: its offset table, which depends on
+  //  nothing the copy brings, is still written here, in front of the copy — behind it it cost C2 6 us per step)
+  const bool offs_at_commit = at_commit || !(h->d_occ32 && h->d_freq11);
+  if (offs_at_commit)
+    hipLaunchKernelGGL(femk::uniform_offsets_kernel, dim3((uint32_t)std::min<uint64_t>((n + 256) / 256, (uint64_t)h->n_cu * 8u)), dim3(256), 0,
+                       s.stream, s.d_off, n, len);
   if ((rc = h2d_begin(h, s))) return rc;
   for (int q = 0; q < s.parts; ++q) {
     const uint64_t r0 = s.part_begin[q], r1 = s.part_begin[q + 1];
@@ -1192,7 +1253,7 @@ int enqueue_packed(fem_dev *h, Slot &s, uint64_t n, uint32_t len, uint64_t n_exc
     // (the link goes to the next batch's copy as soon as this batch's last byte is over — not behind the expansion kernel,
     //  which waits for a free wave slot beside the running kernels: that chained C2's batches at 2.0 ms apiece)
     if (q + 1 == s.parts && (rc = h2d_end(h, s))) return rc;
-    if (r1 > r0) {
+    if (at_commit && r1 > r0) {
       const uint32_t grid = (uint32_t)std::min<uint64_t>(((r1 - r0) * bpr + 255) / 256, (uint64_t)h->n_cu * 16u);
       hipLaunchKernelGGL(femk::unpack_reads_kernel, dim3(grid), dim3(256), 0, s.stream, (const uint8_t *)s.packed() + b0, r1 - r0, len, bpr,
                          s.bases() + r0 * len);
@@ -1201,6 +1262,11 @@ int enqueue_packed(fem_dev *h, Slot &s, uint64_t n, uint32_t len, uint64_t n_exc
   }
   if (n_exc) {
     const dim3 g((uint32_t)std::min<uint64_t>((n_exc + 255) / 256, (uint64_t)h->n_cu * 4u));
+    if (!at_commit) {  // the marked reads alone: their characters and their d_off entries, then the bytes that belong there
+      const dim3 gm((uint32_t)std::min<uint64_t>((n_exc * bpr + 255) / 256, (uint64_t)h->n_cu * 8u));
+      hipLaunchKernelGGL(femk::unpack_marked_reads_kernel, gm, dim3(256), 0, s.stream, (const uint8_t *)s.packed(),
+                         (const uint32_t *)(s.packed() + code_bytes), n_exc, len, bpr, s.bases(), s.d_off.get());
+    }
     hipLaunchKernelGGL(femk::scatter_chars_kernel, g, dim3(256), 0, s.stream, (const uint32_t *)(s.packed() + code_bytes),
                        (const uint8_t *)(s.packed() + code_bytes + 4u * n_exc), n_exc, s.bases());
     hipLaunchKernelGGL(femk::mark_exception_reads_kernel, g, dim3(256), 0, s.stream, (const uint32_t *)(s.packed() + code_bytes), n_exc, len,
@@ -1211,6 +1277,7 @@ int enqueue_packed(fem_dev *h, Slot &s, uint64_t n, uint32_t len, uint64_t n_exc
   s.n_reads = n, s.n_bases = n_bases, s.max_len = len;
   s.staged = true, s.mapped = false, s.synced = false;
   s.h2d_bytes = total, s.sent_packed = true;
+  s.chars_ready = at_commit, s.offs_ready = offs_at_commit, s.n_exc = n_exc;
   return FEM_OK;
 }
 
@@ -1275,7 +1342,7 @@ int fem_dev_open(int device, fem_dev **out) {
   for (int i = 0; ok_ev && i < kSlots; ++i) {
     Slot &sl = h->slot[i];
     ok_ev = sl.ev_zeroed.create(hipEventDisableTiming) == hipSuccess && sl.ev_results.create(hipEventDisableTiming) == hipSuccess &&
-            sl.ev_home.create(hipEventDisableTiming) == hipSuccess;
+            sl.ev_home.create(hipEventDisableTiming) == hipSuccess && sl.ev_chars.create(hipEventDisableTiming) == hipSuccess;
     for (int q = 0; ok_ev && q < kMaxParts; ++q)
       ok_ev = sl.ev_part[q].create(hipEventDisableTiming) == hipSuccess && sl.ev_sel[q].create(hipEventDisableTiming) == hipSuccess;
   }
@@ -1298,6 +1365,7 @@ int fem_dev_open(int device, fem_dev **out) {
     h->no_dense = testing_switch("FEM_NO_DENSE");
     h->no_strided = testing_switch("FEM_NO_STRIDED");
     h->verify_chars = testing_switch("FEM_VERIFY_CHARS");
+    h->select_chars = testing_switch("FEM_SELECT_CHARS");
     h->tiny_buffers = testing_switch("FEM_TEST_TINY_BUFFERS");
     if (const char *bl = getenv("FEM_TEST_BANK_BASES")) h->bank_limit = strtoull(bl, nullptr, 10);
     if (const char *bs = getenv("FEM_TEST_BANK_SEQS")) h->bank_seqs = (uint32_t)strtoul(bs, nullptr, 10);
@@ -1490,7 +1558,7 @@ int fem_dev_commit_stage(fem_dev *h, int slot, uint64_t n_reads, uint32_t max_le
   s.parts = 1;
   s.n_reads = n_reads, s.n_bases = n_bases, s.max_len = max_len;
   s.staged = true, s.mapped = false, s.synced = false;
-  s.h2d_bytes = n_bases + (n_reads ? (n_reads + 1) * sizeof(uint64_t) : 0), s.sent_packed = false, s.staged_by_copy = false;
+  s.h2d_bytes = n_bases + (n_reads ? (n_reads + 1) * sizeof(uint64_t) : 0), s.sent_packed = false, s.chars_ready = true, s.offs_ready = true, s.n_exc = 0, s.staged_by_copy = false;
   return FEM_OK;
 }
 
@@ -1516,7 +1584,7 @@ int fem_dev_commit_stage_uniform(fem_dev *h, int slot, uint64_t n_reads, uint32_
   HIP_TRY(h, hipGetLastError());
   s.n_reads = n_reads, s.n_bases = n_bases, s.max_len = read_len;
   s.staged = true, s.mapped = false, s.synced = false;
-  s.h2d_bytes = n_bases, s.sent_packed = false, s.staged_by_copy = false;
+  s.h2d_bytes = n_bases, s.sent_packed = false, s.chars_ready = true, s.offs_ready = true, s.n_exc = 0, s.staged_by_copy = false;
   return FEM_OK;
 }
 
@@ -1659,6 +1727,14 @@ int fem_dev_stage_info(fem_dev *h, int slot, uint64_t *h2d_bytes, int32_t *packe
   if (rc) return rc;
   if (h2d_bytes) *h2d_bytes = h->slot[slot].h2d_bytes;
   if (packed) *packed = h->slot[slot].sent_packed ? 1 : 0;
+  return FEM_OK;
+}
+
+int fem_dev_stage_front(fem_dev *h, int slot, int32_t *select_packed, int32_t *chars_ready) {
+  int rc = check_slot(h, slot);
+  if (rc) return rc;
+  if (select_packed) *select_packed = h->slot[slot].select_packed ? 1 : 0;
+  if (chars_ready) *chars_ready = h->slot[slot].chars_ready ? 1 : 0;
   return FEM_OK;
 }
 
@@ -2060,6 +2136,9 @@ static int tail_records(fem_dev *h, int slot, const void *out, bool copy_records
   if (paired && (s.n_reads & 1)) return fail(h, FEM_ERR_INVALID, "a batch of read pairs holds an even number of reads");
   if (copy_records && s.out_stream) HIP_TRY(h, hipStreamSynchronize(s.out_stream));  // (a SAM text of this slot still being made reads the tail's arrays)
   f->stream = copy_records ? s.stream : out_stream_of(h, s);
+  // the tail reads characters and offsets of the whole batch (traceback, rescue, SAM and BAM text)
+  if ((rc = ensure_chars(h, s))) return rc;
+  if (s.sent_packed && f->stream != s.stream.s) HIP_TRY(h, hipStreamWaitEvent(f->stream, s.ev_chars, 0));  // (made on the slot's stream)
   std::string err;
   if ((rc = s.tail->run(f->in, f->stream, h->n_cu, h->tiny_buffers, &f->t, &err, h->timing ? f->ms : nullptr, copy_records))) return fail(h, rc, err);
   if (paired) {

@@ -107,6 +107,12 @@ struct SeedParams {
   unsigned long long arena_cap;   // entries
   unsigned long long *arena_ctr;  // [0] cursor, [1] total entries wanted (for the retry)
   SeedLayout lay;
+  // A batch that came packed (fem_pack.h; nullptr: characters only): its 2-bit codes, bpr bytes per read of len bases, and
+  // bit r of exc_bits: read r holds a character other than "ACGT" (its codes are incomplete: `bases` has it whole).
+  // seed_select_kernel and the queue of seed_filter_kernel read these; `bases` and read_off then hold the marked reads only.
+  const uint8_t *packed;
+  const uint32_t *exc_bits;
+  uint32_t bpr, len;
 };
 
 // read offsets of a batch of equal-length reads (fem_dev_commit_stage_uniform): off[i] = i * len, i <= n
@@ -143,6 +149,21 @@ __global__ void unpack_reads_kernel(const uint8_t *packed, uint64_t n_reads, uin
 __global__ void scatter_chars_kernel(const uint32_t *at, const uint8_t *ch, uint64_t n, uint8_t *bases) {
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) bases[at[i]] = ch[i];
+}
+// The reads that the exception positions `at` name, expanded from their codes, and their entries of the offset table: what
+// a packed batch has of characters until the whole of it is asked for.  One thread per entry and packed byte (a read with
+// several entries is written several times, the same bytes); scatter_chars_kernel follows.
+__global__ void unpack_marked_reads_kernel(const uint8_t *packed, const uint32_t *at, uint64_t n_exc, uint32_t len, uint32_t bytes_per_read,
+                                           uint8_t *bases, uint64_t *off) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x, total = n_exc * bytes_per_read;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+    const uint64_t r = at[i / bytes_per_read] / len;
+    const uint32_t kb = (uint32_t)(i % bytes_per_read), k = kb * 4u;
+    const uint32_t b = packed[r * bytes_per_read + kb];
+    uint8_t *o = bases + r * len + k;
+    for (uint32_t q = 0; q < 4u && k + q < len; ++q) o[q] = (uint8_t)((0x54474341u >> (8u * ((b >> (2u * q)) & 3u))) & 0xFFu);
+    if (kb == 0) off[r] = r * (uint64_t)len, off[r + 1] = (r + 1) * (uint64_t)len;
+  }
 }
 
 // bit r of bits[]: read r of a batch of equal-length reads has one of the characters the packed transfer sends separately
@@ -1019,6 +1040,28 @@ __device__ uint32_t select_seeds_dpp(const SeedParams &p, int S, const bool *str
   return pre_mine;
 }
 
+// A read of the batch as seed_filter_kernel sees it: its characters, or — in a batch that came packed, for a read whose
+// bit in exc_bits is clear — "ACGT"[code] from its 2-bit codes (fem_pack.h), with offsets from the batch's one length.
+struct QueuedRead {
+  const uint8_t *chars, *codes;  // codes != nullptr: read them
+  uint32_t len;
+  __device__ __forceinline__ uint32_t at(uint32_t j) const {
+    if (codes) return (0x54474341u /* "ACGT" */ >> (8u * ((codes[j >> 2] >> (2u * (j & 3u))) & 3u))) & 0xFFu;
+    return chars[j];
+  }
+};
+__device__ __forceinline__ QueuedRead queued_read(const SeedParams &p, uint32_t read) {
+  QueuedRead r;
+  if (p.packed) {
+    const bool marked = (p.exc_bits[read >> 5] >> (read & 31u)) & 1u;
+    r.chars = p.bases + (uint64_t)read * p.len, r.codes = marked ? nullptr : p.packed + (uint64_t)read * p.bpr, r.len = p.len;
+  } else {
+    const uint64_t off = p.read_off[read];
+    r.chars = p.bases + off, r.codes = nullptr, r.len = (uint32_t)(p.read_off[read + 1] - off);
+  }
+  return r;
+}
+
 // ---------------------------------------------------------------------------
 // seed + filter kernel: one wave per read, grid-stride over the batch
 // ---------------------------------------------------------------------------
@@ -1057,9 +1100,8 @@ __global__ void __launch_bounds__(256) seed_filter_kernel(SeedParams p) {
     const uint32_t read = p.work_queue ? p.work_queue[item] : item;
     if (read == kInvalidRead) continue;
     STAMP_START(prof);
-    const uint64_t off = p.read_off[read];
-    const uint32_t L = (uint32_t)(p.read_off[read + 1] - off);
-    const uint8_t *seq = p.bases + off;
+    const QueuedRead seq = queued_read(p, read);
+    const uint32_t L = seq.len;
     const int S = (int)L - k + 1;  // num_seeds_in_read
 
     // ---- gates (src/filter.c:161-172) + the (L,e,a) shapes on which the reference DP is undefined ----
@@ -1095,7 +1137,7 @@ __global__ void __launch_bounds__(256) seed_filter_kernel(SeedParams p) {
           for (int q = 0; q < 4; ++q) {
             uint32_t c = 0, isn = 0;
             if (idx + q < L) {
-              uint32_t code = base_code(seq[idx + q]);
+              uint32_t code = base_code(seq.at(idx + q));
               isn = code >> 2;
               c = code & 3u & (isn - 1u);  // N -> A (src/utils.h:92)
               // hash_all_seeds_in_sequence counts ambiguous bases at offsets >= k only (src/utils.h:108-114);

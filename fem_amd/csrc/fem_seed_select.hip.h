@@ -147,6 +147,21 @@ __device__ __forceinline__ int first_set_from(const uint32_t (&m)[W], uint32_t f
   return best;
 }
 
+// The arguments only the packed front end reads, fetched from the kernel's argument segment where a sub-block needs them: taken
+// from `p` they stay in scalar registers across the DP (the compiler does not load an argument twice), and what does not fit
+// there is spilled into lanes — 12 bytes of scratch at R = 8.  (SeedParams is the kernel's one argument: offset 0.)
+struct PackedArgs {
+  const uint8_t *packed, *bases;
+  const uint32_t *exc_bits;
+  uint32_t bpr, len;
+};
+__device__ __forceinline__ PackedArgs packed_args() {
+  typedef const __attribute__((address_space(4))) SeedParams *ArgPtr;
+  ArgPtr a = (ArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(a));  // (opaque: the loads below are not merged with earlier ones)
+  return {a->packed, a->bases, a->exc_bits, a->bpr, a->len};
+}
+
 #ifndef FEM_SELECT_WAVES
 #define FEM_SELECT_WAVES 6
 #endif
@@ -154,7 +169,8 @@ __device__ __forceinline__ int first_set_from(const uint32_t (&m)[W], uint32_t f
 #define FEM_SELECT_UNROLL 2
 #endif
 
-template <int R, bool BANKED = false>
+// PACKED: the batch came as 2-bit codes (SeedParams::packed) and the stream is filled from them; else from its characters.
+template <int R, bool BANKED = false, bool PACKED = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FEM_SELECT_WAVES, 8))) seed_select_kernel(SeedParams p) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const uint32_t ln = lane_id();
@@ -190,26 +206,44 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FEM_SE
     uint32_t pull = 0;
     if (ln == 0) pull = atomicAdd(p.work_cursor, kReadBlock);
     pull = bcast0(pull);
-    if ((uint64_t)p.read_begin + pull >= p.n_reads) break;
+    if constexpr (PACKED) {  // (the same test in 32 bits — read_begin <= n_reads —: the 64-bit form kept n_reads in a lane pair, spilled at R = 8)
+      if (pull >= p.n_reads - p.read_begin) break;
+    } else {
+      if ((uint64_t)p.read_begin + pull >= p.n_reads) break;
+    }
     const uint32_t r0 = p.read_begin + pull;
     const uint32_t n_blk = p.n_reads - r0 < kReadBlock ? p.n_reads - r0 : kReadBlock;
-    wave_sync_lds();
-    if (ln <= n_blk) boff[ln] = p.read_off[r0 + ln];
-    wave_sync_lds();
+    // A batch that came packed (fem_pack.h) is read from its 2-bit codes: every read has `len` bases and `bpr` bytes, so no
+    // offset is loaded.  A sub-block's bits of exc_bits lie in one word (r0 is a multiple of kReadBlock); a set bit = the read
+    // has a character other than "ACGT" and takes its characters from `bases`, as verify_kernel_packed does.
+    constexpr bool from_codes = PACKED;
+    if constexpr (!from_codes) {
+      wave_sync_lds();
+      if (ln <= n_blk) boff[ln] = p.read_off[r0 + ln];
+      wave_sync_lds();
+    }
     for (uint32_t sb = 0; sb < n_blk; sb += nb) {
       const uint32_t cnt = n_blk - sb < nb ? n_blk - sb : nb;
       const uint32_t rd0 = r0 + sb;
-      const uint64_t o_first = boff[sb];
-      const uint64_t blk_off = (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)o_first) |
-                               ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(o_first >> 32)) << 32);
+      uint64_t blk_off = 0;
+      if constexpr (!from_codes) {
+        const uint64_t o_first = boff[sb];
+        blk_off = (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)o_first) |
+                  ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(o_first >> 32)) << 32);
+      }
       // ---- per read (lane i): place in the stream, length, gates (src/filter.c:161-172) and the shapes on which the
       //      reference DP is undefined (src/filter.c:5-7) ----
       uint32_t my_S = 0, my_flag = 0;
       {
         uint32_t L = 0, base = 0;
         if (ln < cnt) {
-          const uint64_t o0 = boff[sb + ln], o1 = boff[sb + ln + 1u];
-          L = (uint32_t)(o1 - o0), base = (uint32_t)(o0 - blk_off);
+          if constexpr (from_codes) {
+            const PackedArgs pk = packed_args();
+            L = pk.len, base = __umul24(ln, 4u * pk.bpr);  // (every read on a byte of the stream: the codes go in as they lie)
+          } else {
+            const uint64_t o0 = boff[sb + ln], o1 = boff[sb + ln + 1u];
+            L = (uint32_t)(o1 - o0), base = (uint32_t)(o0 - blk_off);
+          }
           const int S = (int)L - kK + 1;
           bool shape_ok = S > 0 && R <= S / kStep;
           if (shape_ok) shape_ok = (S - (kStep - 1)) / kStep - R * kLg + 2 >= 2;
@@ -222,10 +256,45 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FEM_SE
         }
         if (ln < kReadBlock) r_base[ln] = base, r_len[ln] = L, r_flag[ln] = my_flag, r_pre[ln] = 0;
       }
-      const uint32_t total_chars = (uint32_t)(boff[sb + cnt] - blk_off);
-      // ---- encode the sub-block: four characters per lane -> one byte of each stream ----
       uint32_t any_n = 0;
-      {
+      if constexpr (from_codes) {
+        const PackedArgs pk = packed_args();
+        // ---- the sub-block's codes, sixteen bases per lane: base j of a packed word sits at bits 2 j (fem_pack.h), the stream
+        //      wants it at bits 31 - 2 j — a bit reversal and a swap inside each pair.  The reads' padding bits (and up to
+        //      three bytes behind the sub-block) come along: bases behind a read's last one are never part of a seed.  The N
+        //      marks are neither written nor read unless a read of the sub-block is marked ----
+        const uint8_t *src = pk.packed + (uint64_t)rd0 * pk.bpr;
+        const uint32_t n_words = (cnt * pk.bpr + 3u) >> 2;
+        for (uint32_t q = ln; q < n_words; q += (uint32_t)kWave) {
+          const uint32_t r = __brev(load_u32_unaligned(src + 4u * q));
+          fw[q] = ((r & 0x55555555u) << 1) | ((r >> 1) & 0x55555555u);
+        }
+        uint32_t marked = (pk.exc_bits[rd0 >> 5] >> (rd0 & 31u)) & ((1u << cnt) - 1u);
+        if (marked != 0u) {
+          // rare: a marked read's bytes of both streams from its characters, as below (the other reads' N marks are zero)
+          for (uint32_t q = ln; q < n_words + 2u; q += (uint32_t)kWave) nw[q] = 0;
+          wave_sync_lds();
+          for (; marked; marked &= marked - 1u) {
+            const uint32_t i = (uint32_t)__builtin_ctz(marked);
+            const uint8_t *rs = pk.bases + (uint64_t)(rd0 + i) * pk.len;
+            const uint32_t byte0 = i * pk.bpr;
+            for (uint32_t q = ln; 4u * q < pk.len; q += (uint32_t)kWave) {
+              uint32_t code, nflag;
+              encode4(load_u32_unaligned(rs + 4u * q), code, nflag);  // may run up to 3 bytes past the read: masked
+              const uint32_t left = pk.len - 4u * q;
+              const uint32_t keep = left >= 4u ? 0xFFFFFFFFu : ((1u << (8u * left)) - 1u);
+              nflag &= keep;
+              code &= keep & ~(nflag * 3u);  // N -> A (src/utils.h:92)
+              const uint32_t k = byte0 + q, byte_addr = (k >> 2) * 4u + (3u - (k & 3u));
+              ((uint8_t *)fw)[byte_addr] = (uint8_t)pack4(code);
+              ((uint8_t *)nw)[byte_addr] = (uint8_t)pack4(nflag * 3u);
+              any_n |= nflag;
+            }
+          }
+        }
+      } else {
+        // ---- encode the sub-block: four characters per lane -> one byte of each stream ----
+        const uint32_t total_chars = (uint32_t)(boff[sb + cnt] - blk_off);
         const uint8_t *src = p.bases + blk_off;
         for (uint32_t q = ln; 4u * q < total_chars; q += (uint32_t)kWave) {
           uint32_t code, nflag;

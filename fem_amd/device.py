@@ -12,7 +12,7 @@ ABI_SYMBOLS = [
     "fem_dev_open", "fem_dev_close", "fem_strerror", "fem_dev_last_error", "fem_dev_limits",
     "fem_dev_upload_index", "fem_dev_upload_reference", "fem_dev_build_index", "fem_dev_fetch_index",
     "fem_dev_map_batch_submit", "fem_dev_map_batch_wait",
-    "fem_dev_stage_reads", "fem_dev_stage_info", "fem_dev_acquire_stage", "fem_dev_commit_stage", "fem_dev_commit_stage_uniform", "fem_dev_packed_layout", "fem_dev_commit_stage_packed", "fem_dev_map_staged", "fem_dev_sync", "fem_dev_fetch_stats", "fem_dev_fetch", "fem_dev_fetch_packed",
+    "fem_dev_stage_reads", "fem_dev_stage_info", "fem_dev_stage_front", "fem_dev_acquire_stage", "fem_dev_commit_stage", "fem_dev_commit_stage_uniform", "fem_dev_packed_layout", "fem_dev_commit_stage_packed", "fem_dev_map_staged", "fem_dev_sync", "fem_dev_fetch_stats", "fem_dev_fetch", "fem_dev_fetch_packed",
     "fem_dev_fetch_records", "fem_dev_seed_kernel", "fem_dev_index_info",
     "fem_dev_upload_reference_names", "fem_dev_acquire_text_stage", "fem_dev_commit_text_stage", "fem_dev_commit_names_stage", "fem_dev_sam_quals", "fem_dev_reserve_text", "fem_dev_reserve_batch", "fem_set_blocking_waits", "fem_dev_fetch_sam", "fem_dev_fetch_sam_nowait", "fem_dev_sam_wait",
     "fem_dev_set_timing", "fem_dev_reset_timing", "fem_dev_kernel_time", "fem_dev_copy_bandwidth",
@@ -150,6 +150,8 @@ def load_hip():
     L.fem_dev_fetch_sam_nowait.argtypes = [vp, C.c_int, C.POINTER(_BatchSam)]
     L.fem_dev_sam_wait.argtypes = [vp, C.c_int]
     L.fem_dev_stage_info.argtypes = [vp, C.c_int, C.POINTER(u64), C.POINTER(C.c_int32)]
+    if hasattr(L, "fem_dev_stage_front"):
+        L.fem_dev_stage_front.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     if hasattr(L, "fem_dev_set_pairs"):
         L.fem_dev_set_pairs.argtypes = [vp, C.c_int, C.POINTER(_PairParams)]
         L.fem_dev_fetch_pairs.argtypes = [vp, C.c_int, C.POINTER(_BatchPairs)]
@@ -434,6 +436,13 @@ class Device:
         nb, pk = C.c_uint64(0), C.c_int32(0)
         self._check(self._L.fem_dev_stage_info(self._h, slot, C.byref(nb), C.byref(pk)))
         return nb.value, bool(pk.value)
+
+    def stage_front(self, slot=0):
+        """(True if the slot's last dense mapping selected its seeds from the 2-bit codes, True if the slot's batch has its
+        characters in device memory)."""
+        sp, cr = C.c_int32(0), C.c_int32(0)
+        self._check(self._L.fem_dev_stage_front(self._h, slot, C.byref(sp), C.byref(cr)))
+        return bool(sp.value), bool(cr.value)
 
     def acquire_stage(self, n_reads_cap, n_bases_cap, slot=0):
         """The slot's pinned staging buffers as numpy views (bases uint8[n_bases_cap + 64], offsets uint64[n_reads_cap + 1]):

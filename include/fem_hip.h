@@ -188,6 +188,11 @@ int fem_dev_stage_reads(fem_dev *h, int slot, const fem_read_batch *reads);
  * packing off.  fem_dev_stage_info: bytes the slot's last staging (either form) sent to the device, and whether they
  * were packed. */
 int fem_dev_stage_info(fem_dev *h, int slot, uint64_t *h2d_bytes, int32_t *packed);
+/* A packed batch is seeded (dense indexes) and verified from its codes; its characters are made on the device when a
+ * consumer asks for them: the sparse seed kernel, the mapping tail (records, SAM, BAM), never for fem_dev_fetch alone.
+ * fem_dev_stage_front: whether the slot's last mapping selected its seeds from the codes, and whether the slot's batch
+ * has its characters in device memory.  FEM_TESTING=1 FEM_SELECT_CHARS=1: characters at commit, selection from them. */
+int fem_dev_stage_front(fem_dev *h, int slot, int32_t *select_packed, int32_t *chars_ready);
 /* Zero-copy form (north_star: "reads streamed in pinned batches"; the reusable SequenceBatch ring of
  * src/input_queue.c:34-51): the library lends the slot's PINNED staging buffers, the FASTQ parser writes the
  * batch straight into them, commit starts the asynchronous H2D copy and returns at once.
