@@ -175,6 +175,8 @@ struct Slot {
   uint64_t n_unmapped = 0;  // ... and how many the slot's last text or BAM had
   int32_t report_strata = -1, report_hits = -1;  // fem_dev_set_report: the line filter of the slot's SAM text and BAM records (-1: off)
   uint64_t n_filtered = 0;  // ... and how many lines it left out of the slot's last text or BAM
+  std::string read_group;  // fem_dev_set_tags: the ID of the RG:Z tag on every line of the slot's SAM text and BAM records (empty: none)
+  bool hit_tags = false;   // ... and NH:i HI:i on every mapped line
   // fem_dev_fetch_pairs: the records in output order (host copies, valid until the slot's next fetch_pairs)
   std::vector<uint16_t> pr_flag;
   std::vector<uint32_t> pr_tid, pr_pos0, pr_cigar_off, pr_cigar, pr_md_off;
@@ -2157,7 +2159,8 @@ static int tail_records(fem_dev *h, int slot, const void *out, bool copy_records
 
 // The names (and qualities, unless the caller keeps them: qual_hole) the slot's text is rendered with.
 static femt::SamInput sam_input(const fem_dev *h, const Slot &s) {
-  return {s.host_quals ? nullptr : s.d_quals, s.d_names, s.d_name_off, h->d_ref_names, h->d_ref_name_off, s.host_quals, s.mapq, s.unmapped, s.report_strata, s.report_hits};
+  return {s.host_quals ? nullptr : s.d_quals, s.d_names, s.d_name_off, h->d_ref_names, h->d_ref_name_off, s.host_quals, s.mapq, s.unmapped, s.report_strata, s.report_hits,
+          s.read_group.empty() ? nullptr : s.read_group.c_str(), (uint32_t)s.read_group.size(), s.hit_tags};
 }
 
 // What follows a text's sam() / bam() (tag: the caller, for FEM_FETCH_TIMES): the pair counts, the event the slot's next text
@@ -2343,6 +2346,27 @@ int fem_dev_set_report(fem_dev *h, int slot, const fem_report_params *rp) {
   if (rp->strata < -1 || rp->strata > 15) return fail(h, FEM_ERR_INVALID, "strata out of range (0 <= strata <= 15, or -1 for off)");
   if (rp->max_hits < -1 || rp->max_hits == 0) return fail(h, FEM_ERR_INVALID, "hit limit out of range (max_hits >= 1, or -1 for off)");
   s.report_strata = rp->strata, s.report_hits = rp->max_hits;
+  return FEM_OK;
+}
+
+int fem_dev_set_tags(fem_dev *h, int slot, const fem_tag_params *tp) {
+  int rc = check_slot(h, slot);
+  if (rc) return rc;
+  FEM_LOCK(h);
+  Slot &s = h->slot[slot];
+  if (!tp) {
+    s.read_group.clear(), s.hit_tags = false;
+    return FEM_OK;
+  }
+  size_t n = 0;
+  if (tp->read_group) {
+    n = strnlen(tp->read_group, 256);
+    if (n < 1 || n > 255) return fail(h, FEM_ERR_INVALID, "read group ID out of range (1 to 255 bytes)");
+    for (size_t i = 0; i < n; ++i)
+      if (tp->read_group[i] < ' ' || tp->read_group[i] > '~') return fail(h, FEM_ERR_INVALID, "read group ID holds a byte outside [ -~]");
+  }
+  s.read_group.assign(tp->read_group ? tp->read_group : "", n);
+  s.hit_tags = tp->hit_tags != 0;
   return FEM_OK;
 }
 

@@ -1902,9 +1902,11 @@ int fem_sam_fill_quals(char *text, uint64_t text_len, const uint64_t *qual_at, u
   return 0;
 }
 
-int fem_sam_header(const fem_tail_ref *ref, char **text, uint64_t *text_len) {
-  if (!ref || !text || !text_len) return -1;
+// The header text: the @SQ lines; hd: "@HD" in front of them, and rg_line / pg_line (whole lines without their newline, or
+// nullptr) behind them in this order.
+static std::string sam_header_text(const fem_tail_ref *ref, bool hd, const char *rg_line, const char *pg_line) {
   std::string s;
+  if (hd) s += "@HD\tVN:1.6\tSO:unsorted\tGO:query\n";
   for (uint32_t i = 0; i < ref->n_seq; ++i) {  // "@SQ\tSN:%s\tLN:%d\n" (src/output_queue.c:107)
     s += "@SQ\tSN:";
     s.append(ref->names + ref->name_off[i], ref->name_off[i + 1] - ref->name_off[i]);
@@ -1912,30 +1914,41 @@ int fem_sam_header(const fem_tail_ref *ref, char **text, uint64_t *text_len) {
     s += std::to_string((int)ref->len[i]);
     s += "\n";
   }
-  *text = (char *)malloc(s.size() + 1);
-  if (!*text) return -4;
-  memcpy(*text, s.data(), s.size());
-  *text_len = s.size();
+  for (const char *line : {rg_line, pg_line})
+    if (line) s += line, s += "\n";
+  return s;
+}
+
+static int copy_out(const std::string &s, void **out, uint64_t *len) {
+  *out = malloc(s.size() + 1);
+  if (!*out) return -4;
+  memcpy(*out, s.data(), s.size());
+  ((char *)*out)[s.size()] = 0;
+  *len = s.size();
   return 0;
+}
+
+int fem_sam_header(const fem_tail_ref *ref, char **text, uint64_t *text_len) {
+  if (!ref || !text || !text_len) return -1;
+  return copy_out(sam_header_text(ref, false, nullptr, nullptr), (void **)text, text_len);
+}
+
+int fem_sam_header_full(const fem_tail_ref *ref, const char *rg_line, const char *pg_line, char **text, uint64_t *text_len) {
+  if (!ref || !text || !text_len) return -1;
+  return copy_out(sam_header_text(ref, true, rg_line, pg_line), (void **)text, text_len);
 }
 
 // BAM header (SAM/BAM specification 4.2): "BAM\1", l_text and the text fem_sam_header writes, n_ref, then per sequence l_name,
 // its name with a NUL, l_ref.  pos and l_ref are int32: a sequence of 2^31 bases or more cannot be written (-5).
-int fem_bam_header(const fem_tail_ref *ref, uint8_t **raw, uint64_t *len) {
-  if (!ref || !raw || !len) return -1;
+static int bam_header_raw(const fem_tail_ref *ref, const std::string &text, uint8_t **raw, uint64_t *len) {
   for (uint32_t i = 0; i < ref->n_seq; ++i)
     if (ref->len[i] >= (1u << 31)) return -5;
-  char *text = nullptr;
-  uint64_t text_len = 0;
-  int rc = fem_sam_header(ref, &text, &text_len);
-  if (rc) return rc;
   std::string s("BAM\1", 4);
   auto i32 = [&](uint32_t v) {
     for (int k = 0; k < 4; ++k) s.push_back((char)(v >> (8 * k)));
   };
-  i32((uint32_t)text_len);
-  s.append(text, text_len);
-  free(text);
+  i32((uint32_t)text.size());
+  s += text;
   i32(ref->n_seq);
   for (uint32_t i = 0; i < ref->n_seq; ++i) {
     const uint64_t nl = ref->name_off[i + 1] - ref->name_off[i];
@@ -1944,11 +1957,65 @@ int fem_bam_header(const fem_tail_ref *ref, uint8_t **raw, uint64_t *len) {
     s.push_back('\0');
     i32(ref->len[i]);
   }
-  *raw = (uint8_t *)malloc(s.size() + 1);
-  if (!*raw) return -4;
-  memcpy(*raw, s.data(), s.size());
-  *len = s.size();
-  return 0;
+  return copy_out(s, (void **)raw, len);
+}
+
+int fem_bam_header(const fem_tail_ref *ref, uint8_t **raw, uint64_t *len) {
+  if (!ref || !raw || !len) return -1;
+  return bam_header_raw(ref, sam_header_text(ref, false, nullptr, nullptr), raw, len);
+}
+
+int fem_bam_header_full(const fem_tail_ref *ref, const char *rg_line, const char *pg_line, uint8_t **raw, uint64_t *len) {
+  if (!ref || !raw || !len) return -1;
+  return bam_header_raw(ref, sam_header_text(ref, true, rg_line, pg_line), raw, len);
+}
+
+int fem_pg_line(int argc, const char *const *argv, const char *version, char **line) {
+  if (argc < 0 || (argc && !argv) || !version || !line) return -1;
+  std::string s = std::string("@PG\tID:FEM\tPN:FEM\tVN:") + version + "\tCL:";
+  for (int i = 0; i < argc; ++i) {
+    if (i) s += ' ';
+    for (const char *c = argv[i]; *c; ++c) {
+      if (*c == '\t') s += "\\t";
+      else s += *c == '\n' ? ' ' : *c;
+    }
+  }
+  uint64_t n = 0;
+  return copy_out(s, (void **)line, &n);
+}
+
+int fem_parse_read_group(const char *arg, char **line, char *id, char *msg, uint64_t msg_cap) {
+  if (!arg || !line || !id) return -1;
+  auto refuse = [&](const std::string &why) {
+    if (msg && msg_cap) snprintf(msg, (size_t)msg_cap, "%s", why.c_str());
+    return -2;
+  };
+  std::string s;
+  for (const char *c = arg; *c; ++c) {
+    if (c[0] == '\\' && c[1] == 't') s += '\t', ++c;
+    else s += *c;
+  }
+  if (s.find('\n') != std::string::npos) return refuse("the read group line contains a newline");
+  if (s.compare(0, 4, "@RG\t") != 0) return refuse("the read group line does not begin with @RG and a tab");
+  std::vector<std::string> tags;
+  std::string found_id;
+  for (size_t at = 4; at <= s.size();) {
+    const size_t end = std::min(s.find('\t', at), s.size());
+    const std::string f = s.substr(at, end - at);
+    bool ok = f.size() >= 4 && isalpha((unsigned char)f[0]) && isalnum((unsigned char)f[1]) && f[2] == ':';
+    for (size_t k = 3; ok && k < f.size(); ++k) ok = f[k] >= ' ' && f[k] <= '~';
+    if (!ok) return refuse("read group field '" + f + "' is not TAG:VALUE ([A-Za-z][A-Za-z0-9]:[ -~]+)");
+    const std::string tag = f.substr(0, 2);
+    if (std::find(tags.begin(), tags.end(), tag) != tags.end()) return refuse("read group tag " + tag + " occurs twice");
+    tags.push_back(tag);
+    if (tag == "ID") found_id = f.substr(3);
+    at = end + 1;
+  }
+  if (found_id.empty()) return refuse("the read group line has no ID");
+  if (found_id.size() > 255) return refuse("the read group ID is longer than 255 bytes");
+  memcpy(id, found_id.c_str(), found_id.size() + 1);
+  uint64_t n = 0;
+  return copy_out(s, (void **)line, &n);
 }
 
 int fem_tail_sam(int32_t e, const fem_tail_ref *ref, const fem_seqset *reads, const fem_tail_input *in, int n_threads,

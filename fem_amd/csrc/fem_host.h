@@ -180,6 +180,20 @@ int fem_sam_header(const fem_tail_ref *ref, char **text, uint64_t *text_len);
 /* The BAM header, uncompressed: "BAM\1", l_text, the text of fem_sam_header, n_ref, then each sequence's l_name, name + NUL
  * and l_ref (SAM/BAM specification 4.2).  malloc'ed (free()).  -5: a sequence of 2^31 bases or more (l_ref is an int32). */
 int fem_bam_header(const fem_tail_ref *ref, uint8_t **raw, uint64_t *len);
+/* The headers of `FEM map --header`: "@HD\tVN:1.6\tSO:unsorted\tGO:query\n" first, the @SQ lines of fem_sam_header, then rg_line
+ * and pg_line, each a whole line without its newline, or NULL for none.  The BAM form carries the same text (l_text, text) and
+ * the n_ref table of fem_bam_header.  malloc'ed (free()); the return values of the forms above. */
+int fem_sam_header_full(const fem_tail_ref *ref, const char *rg_line, const char *pg_line, char **text, uint64_t *text_len);
+int fem_bam_header_full(const fem_tail_ref *ref, const char *rg_line, const char *pg_line, uint8_t **raw, uint64_t *len);
+/* "@PG\tID:FEM\tPN:FEM\tVN:<version>\tCL:<argv joined by single spaces>" (no newline): a tab inside an argument is written as the
+ * two characters \t, a newline as a space.  *line is malloc'ed and NUL-terminated. */
+int fem_pg_line(int argc, const char *const *argv, const char *version, char **line);
+/* The argument of `FEM map --rg`: a whole @RG line as `bwa mem -R` takes it, its fields separated by real tabs or by the two
+ * characters \t (turned into tabs; no other escape is read).  *line: the line (malloc'ed, NUL-terminated, no newline); id: room
+ * for 256 bytes, receives the ID.  -2 with the reason in msg (up to msg_cap bytes, NUL-terminated) when the line contains a
+ * newline, does not begin with "@RG" and a tab, has a field that is not [A-Za-z][A-Za-z0-9]:[ -~]+, names a tag twice, has no
+ * ID, or has an ID over 255 bytes; -1 on a null argument, -4 out of memory. */
+int fem_parse_read_group(const char *arg, char **line, char *id, char *msg, uint64_t msg_cap);
 /* The other half of fem_dev_commit_names_stage / fem_dev_sam_quals (include/fem_hip.h): copies read r's quality string
  * (quals + off[r], off[r + 1] - off[r] characters; off == NULL: reads of one length, quals + r * read_len) to text + qual_at[r]
  * for every read with qual_at[r] != UINT64_MAX, on up to n_threads threads (they sleep between calls).  Returns 0, or -1 on a

@@ -9,6 +9,8 @@
 // at INT edits (fem_dev_set_rescue).  `--mapq` writes mapping qualities made on the device (fem_dev_set_mapq) instead of 255.
 // `--unmapped` adds a line for every read without a mapping, made on the device (fem_dev_set_unmapped).
 // `--strata INT` / `--max-hits INT` leave out the lines of a read beyond its best strata / its first INT (fem_dev_set_report).
+// `--header` puts @HD in front of the @SQ lines and @PG behind them; `--rg LINE` adds the @RG line and RG:Z on every line, `--nh`
+// NH:i and HI:i on every mapped line, both made on the device (fem_dev_set_tags).
 #include <errno.h>
 #include <fcntl.h>
 #include <getopt.h>
@@ -81,8 +83,14 @@ void usage_map() {
   fprintf(stderr, "        --unmapped    write a line for every read without a mapping too (FLAG 0x4; a mate placed at its mapped mate)\n");
   fprintf(stderr, "        --strata INT  write only a read's (a mate's) lines within INT (0-15) edits of its best one; the primary line always\n");
   fprintf(stderr, "        --max-hits INT  write at most INT (>= 1) lines per read (per mate)\n");
+  fprintf(stderr, "        --header      begin the output with @HD (VN:1.6 SO:unsorted GO:query) and end its header with @PG (the command line)\n");
+  fprintf(stderr, "        --rg     STR  a whole @RG line, its fields separated by tabs or \\t ('@RG\\tID:x\\tSM:y'): written into the header\n");
+  fprintf(stderr, "                      (implies --header), and every line gets RG:Z:<ID>\n");
+  fprintf(stderr, "        --nh          write NH:i (the read's, or the mate's, lines in the output) and HI:i (which of them) on every mapped line\n");
   fprintf(stderr, "        -o       STR  Output SAM file \n\n");
 }
+
+std::string g_pg_line;  // the @PG line of `--header`: main() makes it of its argv, before getopt reorders that
 
 struct Reference {
   fem_seqset set{};
@@ -289,6 +297,9 @@ int map_main(int argc, char **argv) {
   long long strata = -1, max_hits = -1;  // --strata / --max-hits: the line filter, made on the device (fem_dev_set_report); -1: off
   bool strata_given = false, max_hits_given = false;
   bool mapq = false;   // --mapq: MAPQ from the hit strata, made on the device (fem_dev_set_mapq); else 255 as the reference
+  bool header = false;  // --header: @HD in front of the @SQ lines, @PG behind them
+  const char *rg_arg = nullptr;  // --rg: the @RG line (implies --header) and RG:Z on every line, made on the device (fem_dev_set_tags)
+  bool hit_tags = false;         // --nh: NH:i and HI:i on every mapped line, made on the device (fem_dev_set_tags)
   fem_params params{12, 3, 2, 1};  // src/FEM_map.c:67-70: k and step are fixed, whatever the index header says
   int n_threads = 1, n_gpus = 1;
   // reads per batch: 250 k fills the pipeline soonest on small inputs; a batch costs three host round trips on its way through
@@ -305,10 +316,15 @@ int map_main(int argc, char **argv) {
                                      {"bam", optional_argument, nullptr, 'Z'},  {"mapq", no_argument, nullptr, 'Q'},
                                      {"unmapped", no_argument, nullptr, 'U'},
                                      {"strata", required_argument, nullptr, 'S'}, {"max-hits", required_argument, nullptr, 'N'},
+                                     {"header", no_argument, nullptr, 'H'},      {"rg", required_argument, nullptr, 'T'},
+                                     {"nh", no_argument, nullptr, 'n'},
                                      {nullptr, 0, nullptr, 0}};
   int c, oi = 0;
   while ((c = getopt_long(argc, argv, short_opt, long_opt, &oi)) >= 0) {
     switch (c) {
+      case 'H': header = true; break;
+      case 'T': rg_arg = optarg, header = true; break;
+      case 'n': hit_tags = true; break;
       case 'r': ref_path = optarg; break;
       case 'i': index_path = optarg; break;
       case 'b': read_path = optarg; break;
@@ -359,6 +375,14 @@ int map_main(int argc, char **argv) {
         exit(EXIT_SUCCESS);
     }
   }
+  char *rg_line = nullptr, rg_id[256] = "";
+  if (rg_arg) {
+    char why[512] = "";
+    if (fem_parse_read_group(rg_arg, &rg_line, rg_id, why, sizeof why) != 0) {
+      fprintf(stderr, "Wrong --rg line: %s.\n", why[0] ? why : "out of memory");
+      exit(EXIT_FAILURE);
+    }
+  }
   // check_args (src/FEM_map.c:29-55)
   const char *bad = nullptr;
   if (params.e < 0 || params.e > 7) bad = "Wrong error threshold.";
@@ -382,6 +406,7 @@ int map_main(int argc, char **argv) {
     usage_map();
     exit(EXIT_FAILURE);
   }
+  const char *pg_line = g_pg_line.empty() ? nullptr : g_pg_line.c_str();  // (no @PG line rather than an empty one)
   const bool bam = bam_level >= 0;
   for (const char *v : {"FEM_HOST_TAIL", "FEM_HOST_FORMAT", "FEM_HOST_QUALS"}) {  // (BAM records are made on the device, from its qualities)
     const char *x = getenv(v);
@@ -398,6 +423,10 @@ int map_main(int argc, char **argv) {
     }
     if (unmapped && x && x[0] == '1') {  // (nor lines for unmapped reads)
       fprintf(stderr, "--unmapped is not supported with %s=1: the lines of unmapped reads are made on the device, with its SAM text or BAM.\n", v);
+      exit(EXIT_FAILURE);
+    }
+    if ((rg_arg || hit_tags) && x && x[0] == '1') {  // (nor tags)
+      fprintf(stderr, "--rg and --nh are not supported with %s=1: the tags are made on the device, with its SAM text or BAM.\n", v);
       exit(EXIT_FAILURE);
     }
     if ((strata_given || max_hits_given) && x && x[0] == '1') {  // (nor a line filter)
@@ -510,7 +539,9 @@ int map_main(int argc, char **argv) {
           if (!rc && device_text) rc = fem_dev_acquire_text_stage(devs[(size_t)g], sl, reads_cap0, bases_cap0, names_cap0, &pq, &pn, &pno);
           if (!rc && device_text) rc = fem_dev_reserve_text(devs[(size_t)g], sl, reads_cap0, bases_cap0, names_cap0,
                                                                   // (--unmapped: a read of which nothing maps still has a line of its name, bases and qualities)
-                                                                  batch_bytes + batch_bytes / (unmapped ? 2 : 4));
+                                                                  // (--rg / --nh: the tags of a line, one line per read at the least)
+                                                                  batch_bytes + batch_bytes / (unmapped ? 2 : 4) +
+                                                                      reads_cap0 * ((rg_arg ? 6 + strlen(rg_id) : 0) + (hit_tags ? 16 : 0)));
           // (a read over the device's limit among the first records: no reservation, the staging of its batch names the read)
           if (!rc && device_text && res_reads && res_len <= max_read_len) rc = fem_dev_reserve_batch(devs[(size_t)g], sl, res_reads, res_reads + res_reads / 8, res_len, &params);
           if (!rc && mapq) rc = fem_dev_set_mapq(devs[(size_t)g], sl, 1);
@@ -518,6 +549,10 @@ int map_main(int argc, char **argv) {
           if (!rc && report) {
             const fem_report_params fp{(int32_t)strata, (int32_t)max_hits};
             rc = fem_dev_set_report(devs[(size_t)g], sl, &fp);
+          }
+          if (!rc && (rg_arg || hit_tags)) {
+            const fem_tag_params tp{rg_arg ? rg_id : nullptr, hit_tags ? 1 : 0};
+            rc = fem_dev_set_tags(devs[(size_t)g], sl, &tp);
           }
           if (!rc && paired) {
             const fem_pair_params pp{(int32_t)min_insert, (int32_t)max_insert};
@@ -559,7 +594,7 @@ int map_main(int argc, char **argv) {
   if (bam) {  // the BAM header, through the device's compressor
     uint8_t *raw = nullptr;
     uint64_t rl = 0, zl = 0;
-    int rc = fem_bam_header(&ref.view, &raw, &rl);
+    int rc = header ? fem_bam_header_full(&ref.view, rg_line, pg_line, &raw, &rl) : fem_bam_header(&ref.view, &raw, &rl);
     if (rc == -5) {
       fprintf(stderr, "A reference sequence of 2^31 bases or more cannot be written as BAM.\n");
       exit(EXIT_FAILURE);
@@ -579,13 +614,15 @@ int map_main(int argc, char **argv) {
   } else {
     char *hdr = nullptr;
     uint64_t hl = 0;
-    fem_sam_header(&ref.view, &hdr, &hl);
+    if (header) fem_sam_header_full(&ref.view, rg_line, pg_line, &hdr, &hl);
+    else fem_sam_header(&ref.view, &hdr, &hl);
     if (!write_all(hdr, hl)) {
       fprintf(stderr, "[FEM] write error on %s\n", out_path);
       exit_code = EXIT_FAILURE;
     }
     free(hdr);
   }
+  free(rg_line);
 
   if (device_text)
     for (fem_dev *h : devs) {
@@ -1192,6 +1229,9 @@ int main(int argc, char *argv[]) {
   if (strcmp(argv[1], "index") == 0) {
     rv = index_main(argc - 1, argv + 1);
   } else if (strcmp(argv[1], "map") == 0) {
+    char *pg = nullptr;
+    if (fem_pg_line(argc, argv, FEM_VERSION, &pg) == 0) g_pg_line = pg;
+    free(pg);
     rv = map_main(argc - 1, argv + 1);
   } else {
     fprintf(stderr, "[%s] unrecognized command '%s'\n", __func__, argv[1]);

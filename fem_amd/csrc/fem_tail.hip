@@ -1140,6 +1140,12 @@ struct SamParams {
   uint32_t u_base, n_reads;
   const uint32_t *u_lines;      // the length kernels: the line count itself (n_records there bounds it: lines behind it get length 0)
   const uint32_t *pair_begin;   // pair mode: pair_kernel's (mate m of pair i: its lines [pair_begin[2i+m], pair_begin[2i+m+1]))
+  // the tags behind MD:Z (fem_dev_set_tags): NH:i HI:i on a mapped line, RG:Z on every line (an unmapped read's: behind QUAL)
+  const uint8_t *rg;            // the read group's ID
+  uint32_t rg_len;              // 0: no RG tag
+  uint32_t hit_tags;            // != 0: NH and HI
+  const uint32_t *hit_begin;    // n_reads + 1, by slot: slot s has the lines [hit_begin[s], hit_begin[s + 1]) ...
+  uint32_t hit_by_line;         // ... of the output (the line filter's scan), else of the records (pair mode: of pair_kernel's lines)
 };
 
 __device__ __forceinline__ uint32_t dec_digits(uint32_t v) {
@@ -1247,11 +1253,33 @@ __device__ __forceinline__ uint32_t seq_qual_len(const SamParams &p, uint32_t L)
   return L > 0 ? L + 1u + (p.quals || p.qual_hole ? L : 1u) : 3u;
 }
 
-// The line of an unmapped read: QNAME FLAG RNAME POS 0 * RNEXT PNEXT 0 SEQ QUAL, no tags
+// NH and HI of a mapped line: the lines its slot has in the output, and its 1-based place among them.  `line`
+// is the line's number in the output, src the record (pair mode: pair_kernel's line) it renders, r its read.  Without the line
+// filter a slot's lines are its records (pair mode: its lines of pair_kernel's) and stay together in their order, whether or not
+// unmapped reads' lines stand between the slots, so both numbers come from that index; with it they come from the scan of
+// report_kernel's counts.
+struct HitTags {
+  uint32_t nh, hi;
+};
+template <bool kPair>
+__device__ __forceinline__ HitTags hit_tags(const SamParams &p, uint32_t line, uint32_t src, uint32_t r) {
+  const uint32_t s = kPair ? pair_slot(p, r) : r, b = p.hit_begin[s];
+  return {p.hit_begin[s + 1] - b, (p.hit_by_line ? line : src) - b + 1u};
+}
+// SAM: "\tNH:i:<n>\tHI:i:<i>" and "\tRG:Z:<ID>"
+__device__ __forceinline__ uint32_t hit_tags_len(const HitTags &h) { return 12u + dec_digits(h.nh) + dec_digits(h.hi); }
+__device__ __forceinline__ uint32_t rg_tag_len(const SamParams &p) { return p.rg_len ? 6u + p.rg_len : 0u; }
+// BAM: NH and HI as type I (7 bytes each, whatever the value), RG as type Z (the ID and a NUL)
+__device__ __forceinline__ uint32_t bam_tags_len(const SamParams &p, bool mapped) {
+  return (mapped && p.hit_tags ? 14u : 0u) + (p.rg_len ? 4u + p.rg_len : 0u);
+}
+
+// The line of an unmapped read: QNAME FLAG RNAME POS 0 * RNEXT PNEXT 0 SEQ QUAL, no tags but RG
 __device__ __forceinline__ uint32_t unmapped_len(const SamParams &p, const Unmapped &u) {
   const uint32_t name_len = (uint32_t)(p.name_off[u.r + 1] - p.name_off[u.r]), L = (uint32_t)(p.read_off[u.r + 1] - p.read_off[u.r]);
   const uint32_t rname = u.t == kNoMate ? 1u : p.ref_name_off[u.t + 1] - p.ref_name_off[u.t], pos = dec_digits(u.pos0 + 1u);
-  return name_len + 1u + dec_digits(u.flag) + 1u + rname + 1u + pos + 5u + (u.t == kNoMate ? 5u : 4u + pos) + 1u + seq_qual_len(p, L) + 1u;
+  return name_len + 1u + dec_digits(u.flag) + 1u + rname + 1u + pos + 5u + (u.t == kNoMate ? 5u : 4u + pos) + 1u + seq_qual_len(p, L) +
+         rg_tag_len(p) + 1u;
 }
 
 template <bool kPair, bool kUnm = false>
@@ -1281,8 +1309,9 @@ __global__ void __launch_bounds__(256) sam_len_kernel(SamParams p) {
     const uint32_t seq_qual = primary ? seq_qual_len(p, L) : 3u;
     const uint32_t mate = kPair ? mate_cols_len(p, mate_cols<kUnm>(p, j, r), t) : 5u;
     const uint32_t mq = line_mapq<kPair>(p, j, r, primary);
+    const uint32_t tags = (p.hit_tags ? hit_tags_len(hit_tags<kPair>(p, i, j, r)) : 0u) + rg_tag_len(p);
     p.line_len[i] = (unsigned long long)name_len + 1u + dec_digits(flag & 0x7FFFu) + 1u + rname_len + 1u + dec_digits(p.pos0[rec] + 1u) + 2u +
-                    dec_digits(mq) + cig + 2u + mate + seq_qual + 6u + dec_digits(p.nm[rec]) + 6u + md_len + 1u;
+                    dec_digits(mq) + cig + 2u + mate + seq_qual + 6u + dec_digits(p.nm[rec]) + 6u + md_len + tags + 1u;
   }
 }
 
@@ -1293,7 +1322,9 @@ __global__ void __launch_bounds__(256) sam_len_kernel(SamParams p) {
 // load of a pair requested before the first store; what a lane knows of record i reaches the others by v_readlane.
 // kPair: j counts lines, each rendering record perm[j] with the pair's FLAG and mate columns (the lane writes those itself).
 // kUnm: a line may be an unmapped read's, one more shape of line: QNAME, SEQ and QUAL its long fields (a placed one's RNAME too),
-// no CIGAR, no MD, no tags.
+// no CIGAR, no MD, no tags but RG.
+// The tags behind MD:Z (p.hit_tags, p.rg_len: the same in every lane): NH and HI are short fields; the ID is a long one, the same
+// bytes on every line, so each lane loads its bytes of it (up to four: 255 characters) once, in front of the records.
 template <bool kPair, bool kUnm = false>
 __global__ void __launch_bounds__(256) sam_write_kernel(SamParams p) {
   __shared__ uint8_t lut[256];
@@ -1358,6 +1389,12 @@ __global__ void __launch_bounds__(256) sam_write_kernel(SamParams p) {
   const uint32_t o_tags = o_seq + (seq ? L + 1u + (p.quals || p.qual_hole ? L : 1u) : 3u);  // (an unmapped read's line ends here)
   const uint32_t o_nm = o_tags + 6u;
   const uint32_t o_md = kUnm && unm ? o_tags : o_nm + dec_digits(nm) + 6u;
+  const bool hits = p.hit_tags && !(kUnm && unm);
+  HitTags ht{};
+  if (hits) ht = hit_tags<kPair>(p, j, src, r);
+  const uint32_t o_hit = o_md + md_len;
+  const uint32_t o_rg = o_hit + (hits ? hit_tags_len(ht) : 0u);
+  const uint32_t o_end = o_rg + rg_tag_len(p);
   if (mine) {  // the short fields of the lane's own record
     uint8_t *w = p.text + at;
     w[name_len] = '\t';
@@ -1417,7 +1454,18 @@ __global__ void __launch_bounds__(256) sam_write_kernel(SamParams p) {
       q = put_dec(w + o_nm, nm);
       q[0] = '\t', q[1] = 'M', q[2] = 'D', q[3] = ':', q[4] = 'Z', q[5] = ':';
     }
-    w[o_md + md_len] = '\n';
+    if (hits) {
+      q = w + o_hit;
+      q[0] = '\t', q[1] = 'N', q[2] = 'H', q[3] = ':', q[4] = 'i', q[5] = ':';
+      q = put_dec(q + 6, ht.nh);
+      q[0] = '\t', q[1] = 'H', q[2] = 'I', q[3] = ':', q[4] = 'i', q[5] = ':';
+      put_dec(q + 6, ht.hi);
+    }
+    if (p.rg_len) {
+      q = w + o_rg;
+      q[0] = '\t', q[1] = 'R', q[2] = 'G', q[3] = ':', q[4] = 'Z', q[5] = ':';
+    }
+    w[o_end] = '\n';
   }
   // ---- the long fields, record by record, all lanes ----
   const uint32_t at_lo = (uint32_t)at, at_hi = (uint32_t)(at >> 32), no_lo = (uint32_t)no, no_hi = (uint32_t)(no >> 32);
@@ -1426,8 +1474,13 @@ __global__ void __launch_bounds__(256) sam_write_kernel(SamParams p) {
   struct Rec {
     uint8_t *w;
     const uint8_t *name, *rname, *md, *bases, *quals;
-    uint32_t name_len, rname_len, md_len, L, o_rname, o_md, o_seq;
+    uint32_t name_len, rname_len, md_len, L, o_rname, o_md, o_seq, o_id;
   };
+  uint8_t id[4] = {0, 0, 0, 0};  // the lane's bytes of the read group's ID
+  if (p.rg_len) {
+    for (uint32_t c = 0; c < 4u; ++c)
+      if (ln + 64u * c < p.rg_len) id[c] = p.rg[ln + 64u * c];
+  }
   auto rl = [](uint32_t v, uint32_t i) -> uint32_t { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)i); };
   auto record = [&](uint32_t i) -> Rec {
     Rec x;
@@ -1438,6 +1491,7 @@ __global__ void __launch_bounds__(256) sam_write_kernel(SamParams p) {
     x.rname = p.ref_names + rl(rn0, i), x.md = p.md + rl(m0, i);
     x.name_len = rl(name_len, i), x.rname_len = rl(rname_len, i), x.md_len = rl(md_len, i), x.L = rl(L_seq, i);
     x.o_rname = rl(o_rname, i), x.o_md = rl(o_md, i), x.o_seq = rl(o_seq, i);
+    x.o_id = p.rg_len ? rl(o_rg, i) + 6u : 0u;
     return x;
   };
   struct Bytes {
@@ -1476,6 +1530,11 @@ __global__ void __launch_bounds__(256) sam_write_kernel(SamParams p) {
     for (uint32_t k = ln + 128u; k < x.L; k += 64u) {
       w_seq[k] = lut[x.bases[k]];
       if (x.quals) w_seq[x.L + 1u + k] = x.quals[k];
+    }
+    if (p.rg_len) {
+      uint8_t *w_id = x.w + x.o_id;
+      for (uint32_t c = 0; c < 4u; ++c)
+        if (ln + 64u * c < p.rg_len) w_id[ln + 64u * c] = id[c];
     }
   };
   uint32_t i = 0;
@@ -1521,9 +1580,9 @@ __global__ void __launch_bounds__(256) bam_len_kernel(SamParams p, uint32_t n_re
     uint32_t j = i;  // (as sam_len_kernel)
     if (kUnm) {
       j = p.usrc[i];
-      if (j >= p.u_base) {  // an unmapped read: no CIGAR, SEQ and QUAL, no tags
+      if (j >= p.u_base) {  // an unmapped read: no CIGAR, SEQ and QUAL, no tags but RG
         const uint32_t r = j - p.u_base, L = (uint32_t)(p.read_off[r + 1] - p.read_off[r]);
-        p.line_len[i] = 36ull + (uint32_t)(p.name_off[r + 1] - p.name_off[r]) + 1u + (L + 1u) / 2u + L;
+        p.line_len[i] = 36ull + (uint32_t)(p.name_off[r + 1] - p.name_off[r]) + 1u + (L + 1u) / 2u + L + bam_tags_len(p, false);
         continue;
       }
     }
@@ -1531,7 +1590,7 @@ __global__ void __launch_bounds__(256) bam_len_kernel(SamParams p, uint32_t n_re
     if (flag & 0x8000u) atomicAdd(p.asserted, 1u);
     const uint32_t n_ops = p.cigar_off[rec + 1] - p.cigar_off[rec], md_len = p.md_off[rec + 1] - p.md_off[rec];
     const uint32_t ls = primary ? L : 0u;
-    p.line_len[i] = 36ull + name_len + 1u + 4u * n_ops + (ls + 1u) / 2u + ls + 4u + 4u + md_len;
+    p.line_len[i] = 36ull + name_len + 1u + 4u * n_ops + (ls + 1u) / 2u + ls + 4u + 4u + md_len + bam_tags_len(p, true);
   }
 }
 
@@ -1611,11 +1670,26 @@ __global__ void __launch_bounds__(256) bam_write_kernel(SamParams p) {
   const uint8_t *quals = p.quals ? p.quals + ro : nullptr;
   for (uint32_t k = ln; k < ls; k += 64u) x[k] = quals ? (uint8_t)(quals[k] - 33u) : (uint8_t)0xFF;
   x += ls;
-  if (kUnm && unm) return;  // (no tags)
-  if (ln == 0) x[0] = 'N', x[1] = 'M', x[2] = 'C', x[3] = (uint8_t)nm, x[4] = 'M', x[5] = 'D', x[6] = 'Z';
-  x += 7;
-  const uint8_t *md = p.md + m0;
-  for (uint32_t k = ln; k <= md_len; k += 64u) x[k] = k < md_len ? md[k] : 0;
+  if (!(kUnm && unm)) {
+    if (ln == 0) x[0] = 'N', x[1] = 'M', x[2] = 'C', x[3] = (uint8_t)nm, x[4] = 'M', x[5] = 'D', x[6] = 'Z';
+    x += 7;
+    const uint8_t *md = p.md + m0;
+    for (uint32_t k = ln; k <= md_len; k += 64u) x[k] = k < md_len ? md[k] : 0;
+    x += md_len + 1u;
+    if (p.hit_tags) {  // NH:I HI:I, lane k byte k of the fourteen
+      const HitTags ht = hit_tags<kPair>(p, j, src, r);
+      if (ln < 14u) {
+        const uint32_t b = ln < 7u ? ln : ln - 7u, v = ln < 7u ? ht.nh : ht.hi;
+        x[ln] = b < 3u ? (uint8_t)(ln < 7u ? "NHI" : "HII")[b] : (uint8_t)(v >> (8u * (b - 3u)));
+      }
+      x += 14;
+    }
+  }
+  if (p.rg_len) {  // (an unmapped read's record has this one alone)
+    if (ln < 3u) x[ln] = (uint8_t)"RGZ"[ln];
+    x += 3;
+    for (uint32_t k = ln; k <= p.rg_len; k += 64u) x[k] = k < p.rg_len ? p.rg[k] : 0;
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2397,6 +2471,10 @@ struct Tail::Impl {
   // lines for unmapped reads (SamInput::unmapped): the marks, their scan, each line's source, the line count
   // (the line filter, SamInput::strata / max_hits, uses the same four: its counts, their scan, the sources, the line count)
   DevBuf<uint32_t> u_cnt, u_before, usrc, u_ctl;
+  // the RG tag (SamInput::read_group): the ID on the device, the pinned copy it came from, and what that holds
+  DevBuf<uint8_t> rg;
+  PinBuf<uint8_t> h_rg;
+  std::string rg_id;
   PinBuf<uint32_t> h_perm, h_mtid, h_mpos0, h_pair_begin, h_pair_ctl;
   PinBuf<uint16_t> h_pflag;
   PinBuf<int32_t> h_tlen;
@@ -2436,6 +2514,8 @@ struct Tail::Impl {
   // unmapped reads' lines included where names.unmapped asks for them; the count comes home the same way, the unmapped slots'
   // to h_ctl[9].  The text and BAM kernels are the kUnm instances then, with or without names.unmapped: without it u_base lies
   // above every source and pair_begin is nullptr (mate_cols), so that no line takes a shape it has not without the filter.
+  // names.read_group / names.hit_tags (the tags behind MD:Z): the ID goes to the device when it is another than the last text's;
+  // NH and HI read the slots' line ranges that are there already (hit_tags(), above): the filter's scan, or the index it began from.
   int lines(const TailInput &in, const SamInput &names, bool pair_order, uint32_t *bad_name, hipStream_t stream, int n_cu, SamParams *p,
               std::string *err) {
     if (pair_order && !paired) {
@@ -2475,6 +2555,22 @@ struct Tail::Impl {
     if (pair_order) {
       p->perm = perm, p->pflag = pflag, p->mtid = mtid, p->mpos0 = mpos0;
       p->tlen = tlen;
+    }
+    p->n_reads = last_n;
+    if (names.read_group && names.rg_len) {
+      if (!rg || rg_id.size() != names.rg_len || memcmp(rg_id.data(), names.read_group, names.rg_len) != 0) {
+        TAIL_TRY(rg.ensure(256));
+        TAIL_TRY(h_rg.ensure(256));
+        TAIL_TRY(hipStreamSynchronize(stream));  // (the ID before may still be on its way out of h_rg, or in a text kernel's hands)
+        memcpy(h_rg.get(), names.read_group, names.rg_len);
+        TAIL_TRY(hipMemcpyAsync(rg, h_rg, names.rg_len, hipMemcpyHostToDevice, stream));
+        rg_id.assign(names.read_group, names.rg_len);
+      }
+      p->rg = rg, p->rg_len = names.rg_len;
+    }
+    if (names.hit_tags) {
+      p->hit_tags = 1u, p->hit_by_line = report ? 1u : 0u;
+      p->hit_begin = report ? u_before : pair_order ? pair_begin : rec_begin;
     }
     unm_timed = false, n_unm = 0;
     rep_timed = false, n_filtered = 0, n_base_last = n_base;

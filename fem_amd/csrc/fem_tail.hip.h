@@ -64,6 +64,9 @@ struct SamInput {  // device pointers
   bool unmapped = false;         // a line for every read without a record (fem_dev_set_unmapped; the kernels' kUnm instances)
   int32_t strata = -1;           // the line filter (fem_dev_set_report; report_kernel): a slot's lines within this many edits of its best, -1: off
   int32_t max_hits = -1;         // ... and at most this many lines per slot (>= 1), -1: off
+  const char *read_group = nullptr;  // HOST: the ID every line's RG:Z tag carries (fem_dev_set_tags), rg_len bytes; nullptr: no RG tag
+  uint32_t rg_len = 0;
+  bool hit_tags = false;         // NH:i and HI:i on every mapped line
 };
 struct SamOutput {  // pinned host memory owned by the Tail object, valid until its next sam()
   const char *text;

@@ -22,7 +22,7 @@ ABI_SYMBOLS = [
     "fem_dev_set_pairs", "fem_dev_fetch_pairs", "fem_dev_pair_count",
     "fem_dev_set_rescue", "fem_dev_rescue_count", "fem_dev_set_mapq",
     "fem_dev_set_unmapped", "fem_dev_unmapped_count",
-    "fem_dev_set_report", "fem_dev_filtered_count",
+    "fem_dev_set_report", "fem_dev_filtered_count", "fem_dev_set_tags",
     "fem_dev_fetch_bam", "fem_dev_fetch_bam_nowait", "fem_dev_bam_wait", "fem_dev_bgzf_compress",
 ]
 
@@ -78,6 +78,10 @@ class _RescueParams(C.Structure):
 
 class _ReportParams(C.Structure):
     _fields_ = [("strata", C.c_int32), ("max_hits", C.c_int32)]
+
+
+class _TagParams(C.Structure):
+    _fields_ = [("read_group", C.c_char_p), ("hit_tags", C.c_int32)]
 
 
 class _BatchPairs(C.Structure):
@@ -167,6 +171,8 @@ def load_hip():
     if hasattr(L, "fem_dev_set_report"):
         L.fem_dev_set_report.argtypes = [vp, C.c_int, C.POINTER(_ReportParams)]
         L.fem_dev_filtered_count.argtypes = [vp, C.c_int, C.POINTER(u64)]
+    if hasattr(L, "fem_dev_set_tags"):
+        L.fem_dev_set_tags.argtypes = [vp, C.c_int, C.POINTER(_TagParams)]
     if hasattr(L, "fem_dev_fetch_bam"):
         L.fem_dev_fetch_bam.argtypes = [vp, C.c_int, C.c_int, C.POINTER(_BatchBam)]
         L.fem_dev_fetch_bam_nowait.argtypes = [vp, C.c_int, C.c_int, C.POINTER(_BatchBam)]
@@ -633,6 +639,16 @@ class Device:
                 raise FemError("fem_dev_set_report: parameter out of range")
         rp = _ReportParams(-1 if strata is None else int(strata), -1 if max_hits is None else int(max_hits))
         self._check(self._L.fem_dev_set_report(self._h, slot, C.byref(rp)))
+
+    def set_tags(self, slot=0, read_group=None, hits=False):
+        """fem_dev_set_tags: RG:Z:<read_group> on every line of the slot's SAM text and BAM records (None: no RG tag), NH:i and
+        HI:i on every mapped line (hits); neither: the lines as they are without tags."""
+        if read_group is None and not hits:
+            self._check(self._L.fem_dev_set_tags(self._h, slot, None))
+            return
+        rg = None if read_group is None else (read_group if isinstance(read_group, bytes) else read_group.encode("latin-1"))
+        tp = _TagParams(rg, 1 if hits else 0)
+        self._check(self._L.fem_dev_set_tags(self._h, slot, C.byref(tp)))
 
     def filtered_count(self, slot=0):
         """fem_dev_filtered_count: lines the filter left out of the slot's last SAM text or BAM."""

@@ -82,6 +82,10 @@ def lib():
                                    C.POINTER(vp), C.POINTER(u64)]
         L.fem_sam_header.argtypes = [C.POINTER(TailRef), C.POINTER(vp), C.POINTER(u64)]
         L.fem_bam_header.argtypes = [C.POINTER(TailRef), C.POINTER(vp), C.POINTER(u64)]
+        L.fem_sam_header_full.argtypes = [C.POINTER(TailRef), C.c_char_p, C.c_char_p, C.POINTER(vp), C.POINTER(u64)]
+        L.fem_bam_header_full.argtypes = [C.POINTER(TailRef), C.c_char_p, C.c_char_p, C.POINTER(vp), C.POINTER(u64)]
+        L.fem_pg_line.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_char_p, C.POINTER(vp)]
+        L.fem_parse_read_group.argtypes = [C.c_char_p, C.POINTER(vp), C.c_char_p, C.c_char_p, u64]
         L.fem_sam_fill_quals.argtypes = [vp, u64, vp, u64, vp, vp, C.c_uint32, C.c_int]
         L.fem_synth_reference.argtypes = [u64, C.c_uint32, vp, vp, vp, C.c_int]
         L.fem_synth_reads.argtypes = [u64, vp, vp, vp, C.c_uint32, u64, u64, C.c_uint32, i32, vp, C.c_int]
@@ -537,6 +541,59 @@ def bam_header(ref):
     raw = C.string_at(p.value, n.value)
     lib().free(p)
     return raw
+
+
+def _line(s):
+    return None if s is None else (s if isinstance(s, bytes) else s.encode("latin-1"))
+
+
+def sam_header_full(ref, rg_line=None, pg_line=None):
+    """fem_sam_header_full: @HD, the @SQ lines, then the @RG and @PG lines given (each without its newline, or None)."""
+    p, n = C.c_void_p(), C.c_uint64()
+    rc = lib().fem_sam_header_full(C.byref(ref.c), _line(rg_line), _line(pg_line), C.byref(p), C.byref(n))
+    if rc:
+        raise RuntimeError("fem_sam_header_full failed (%d)" % rc)
+    s = C.string_at(p.value, n.value).decode("latin-1")
+    lib().free(p)
+    return s
+
+
+def bam_header_full(ref, rg_line=None, pg_line=None):
+    """fem_bam_header_full: the uncompressed BAM header (bytes) with the text of sam_header_full."""
+    p, n = C.c_void_p(), C.c_uint64()
+    rc = lib().fem_bam_header_full(C.byref(ref.c), _line(rg_line), _line(pg_line), C.byref(p), C.byref(n))
+    if rc == -5:
+        raise ValueError("a reference sequence of 2^31 bases or more cannot be written as BAM")
+    if rc:
+        raise RuntimeError("fem_bam_header_full failed (%d)" % rc)
+    raw = C.string_at(p.value, n.value)
+    lib().free(p)
+    return raw
+
+
+def pg_line(argv, version):
+    """fem_pg_line: the @PG line (no newline) of a command line."""
+    args = (C.c_char_p * max(len(argv), 1))(*[_line(a) for a in argv])
+    p = C.c_void_p()
+    rc = lib().fem_pg_line(len(argv), args, _line(version), C.byref(p))
+    if rc:
+        raise RuntimeError("fem_pg_line failed (%d)" % rc)
+    s = C.string_at(p.value).decode("latin-1")
+    lib().free(p)
+    return s
+
+
+def parse_read_group(arg):
+    """fem_parse_read_group: (the @RG line with real tabs, its ID) of a `--rg` argument; ValueError with the reason when refused."""
+    p, ident, msg = C.c_void_p(), C.create_string_buffer(256), C.create_string_buffer(512)
+    rc = lib().fem_parse_read_group(_line(arg), C.byref(p), ident, msg, len(msg))
+    if rc == -2:
+        raise ValueError(msg.value.decode("latin-1"))
+    if rc:
+        raise RuntimeError("fem_parse_read_group failed (%d)" % rc)
+    s = C.string_at(p.value).decode("latin-1")
+    lib().free(p)
+    return s, ident.value.decode("latin-1")
 
 
 def tail_sam(e, ref, names, read_bases, read_off, quals, cand_begin, cand_count, cand, ed, end, threads=1):

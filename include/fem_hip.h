@@ -442,6 +442,32 @@ typedef struct {
 int fem_dev_set_report(fem_dev *h, int slot, const fem_report_params *rp);
 int fem_dev_filtered_count(fem_dev *h, int slot, uint64_t *n);
 
+/* ---- read-group and hit-count tags: RG:Z, NH:i, HI:i (new; opt-in: the reference writes NM and MD alone, and so does every output
+ *      without it) ----
+ * fem_dev_set_tags: the lines of the slot's fem_dev_fetch_sam[_nowait] text and the records of its fem_dev_fetch_bam[_nowait]
+ *   carry further optional fields behind the last one they have.  read_group: the ID, NUL-terminated, 1 .. 255 bytes of [ -~]
+ *   (copied at the call: the caller's string need not live on), or NULL for no RG tag; hit_tags != 0: NH and HI; tp == NULL: all
+ *   off.  An empty or over-long ID, or a byte outside [ -~], is FEM_ERR_INVALID and leaves the slot's setting as it was.  With
+ *   all off nothing changes.  fem_batch_records, fem_batch_pairs, the stats, n_records and every count are unchanged (output
+ *   text only).  The tags stand behind QUAL, so qual_at of fem_dev_sam_quals still points at each read's QUAL field.
+ * Rule.  The tags are added to LINES, after everything else has been decided: the single-end order, rescue, pairing, MAPQ, the
+ *   lines of unmapped reads, the line filter.  Every byte in front of them is what it is without them.
+ *   Field order on a mapped line: NM:i MD:Z NH:i HI:i RG:Z.  The line of an unmapped read (fem_dev_set_unmapped) carries RG:Z
+ *   alone, behind QUAL, and never NH / HI.
+ *   RG:Z:<ID> stands on every line: primary, secondary, 0x8000 record, rescued mate, unmapped read.
+ *   A slot is a read single-end, or one mate of a pair (the slot of fem_dev_set_report).  NH of a mapped line is the number of
+ *   lines of its slot that ARE IN THE OUTPUT: after rescue, pairing and the line filter; lines whose record carries 0x8000
+ *   count, as they do for MAPQ and the filter.  HI is the line's 1-based place among its slot's lines in output order, so the
+ *   primary line has HI 1.  A rescued mate's record has NH 1 HI 1.  With max_hits 1 every mapped line has NH 1: NH states what is
+ *   in the file, not what was found.
+ *   BAM: NH and HI are type I (uint32, seven bytes each whatever the value), RG is type Z (the ID and a NUL); block_size
+ *   includes them; an unmapped read's record has the RG aux alone. */
+typedef struct {
+  const char *read_group; /* the ID, NUL-terminated, 1..255 bytes of [ -~]; NULL: no RG tag */
+  int32_t hit_tags;       /* != 0: NH:i and HI:i on every mapped line */
+} fem_tag_params;
+int fem_dev_set_tags(fem_dev *h, int slot, const fem_tag_params *tp);
+
 /* Name of the seed + filter kernel fem_dev_map_staged would launch first for these parameters on the resident
  * index ("seed_join_kernel" — behind its "seed_select_kernel"; "seed_join_banked_kernel" where the reference's sequences
  * need more than one 32-bit coordinate space —, "seed_fast_kernel<hash>", "seed_fast_kernel<lean>" or
