@@ -58,7 +58,7 @@ constexpr size_t kPackedFrontPad = 256;  // ... and verify_kernel_packed up to 1
 constexpr uint64_t kExpandAllShare = 8;  // a packed batch with more exceptions than one per this many reads is expanded whole at commit
 constexpr uint32_t kXcapSmall = 512, kFcap = 128, kCcap = 128;
 
-constexpr int kTimedKernels = 16;  // fem_dev_kernel_time ids: 0 seed (join), 1 verify, 2 generic seed, 3-5 tail, 6 pack_results_kernel (round 5; the count kernel of rounds 1-2 before), 7 SAM text, 8 seed selection, 9 pairing, 10 mate rescue, 11 BAM records, 12 BGZF, 13 MAPQ, 14 the line index with unmapped reads, 15 the line filter's line index
+constexpr int kTimedKernels = 16;  // fem_dev_kernel_time ids: 0 seed (join), 1 verify, 2 generic seed, 3-5 tail, 6 pack_results_kernel (round 5; the count kernel of rounds 1-2 before), 7 SAM text, 8 seed selection, 9 pairing, 10 mate rescue, 11 BAM records, 12 BGZF, 13 MAPQ, 14 the line index with unmapped reads, 15 the line filter's line index; 3-5, 7, 9-11 and 13-15 are stages of the device tail (kTailStages)
 struct TimedLaunch {
   int kernel;
   hipEvent_t start, stop;
@@ -2106,15 +2106,42 @@ static femt::TailInput tail_input(const fem_dev *h, const Slot &s) {
   return in;
 }
 
-// What the front of a fetch leaves for the rest of it: the records were made on `stream` (a text goes there), ms = kernel
-// times 3-5; host time from t_in to the mapping synced and to the records made.
+// What the front of a fetch leaves for the rest of it: the records were made on `stream` (a text goes there); host time
+// from t_in to the mapping synced and to the records made.
 struct TailFront {
   femt::TailInput in;
   femt::TailOutput t;
   hipStream_t stream;
-  double ms[3], ms_sync, ms_run;
+  double ms_sync, ms_run;
   std::chrono::steady_clock::time_point t_in;
 };
+
+// The fem_dev_kernel_time id of each stage of the device tail, and the slots that count it (nullptr: every fetch, a fetch of
+// records too; the others: texts).  A text's own stage, femt::kText, goes under its fetch's id: 7 SAM, 11 BAM.
+static bool slot_filters(const Slot &s) { return s.report_strata >= 0 || s.report_hits >= 1; }
+struct TailStage {
+  femt::Stage stage;
+  int id;
+  bool (*counted)(const Slot &);
+};
+static const TailStage kTailStages[] = {
+    {femt::kOrder, 3, nullptr}, {femt::kTrace, 4, nullptr}, {femt::kCompact, 5, nullptr},
+    {femt::kPairing, 9, [](const Slot &s) { return s.paired; }},
+    {femt::kRescue, 10, [](const Slot &s) { return s.paired && s.rescue; }},
+    {femt::kMapq, 13, [](const Slot &s) { return s.mapq; }},  // (its events precede the text's sizing, which sam() and bam() wait for)
+    {femt::kUnmappedIndex, 14, [](const Slot &s) { return s.unmapped && !slot_filters(s); }},  // (as do these)
+    {femt::kFilterIndex, 15, slot_filters},  // (whose line index is the unmapped reads' too: no 14 then)
+};
+
+// Timing: counts the stages of the slot's last fetch once each, with their device time where the tail has one.  text_id: the
+// id femt::kText goes under, < 0: none (records; a text that was not waited for: its time cannot be read yet).
+static void count_tail_stages(fem_dev *h, const Slot &s, bool text, int text_id) {
+  FEM_LOCK(h);  // (FEM map retires each slot's batches from a thread of its own)
+  auto count = [&](femt::Stage stage, int id) { h->t_ms[id] += std::max(s.tail->stage_ms(stage), 0.f), h->t_n[id] += 1; };
+  for (const auto &st : kTailStages)
+    if (!st.counted || (text && st.counted(s))) count(st.stage, st.id);
+  if (text_id >= 0) count(femt::kText, text_id);
+}
 
 // The front of every way a batch's records leave the device (fem_dev_fetch_records, fetch_sam, fetch_bam): waits for the
 // slot's mapping, checks it (`out`: the caller's result), makes the records.  copy_records: on the slot's stream, copied home.
@@ -2142,7 +2169,7 @@ static int tail_records(fem_dev *h, int slot, const void *out, bool copy_records
   if ((rc = ensure_chars(h, s))) return rc;
   if (s.sent_packed && f->stream != s.stream.s) HIP_TRY(h, hipStreamWaitEvent(f->stream, s.ev_chars, 0));  // (made on the slot's stream)
   std::string err;
-  if ((rc = s.tail->run(f->in, f->stream, h->n_cu, h->tiny_buffers, &f->t, &err, h->timing ? f->ms : nullptr, copy_records))) return fail(h, rc, err);
+  if ((rc = s.tail->run(f->in, f->stream, h->n_cu, h->tiny_buffers, &f->t, &err, copy_records))) return fail(h, rc, err);
   if (paired) {
     femt::RescueInput ri{};
     if ((rc = rescue_input(h, s, &ri))) return rc;
@@ -2150,10 +2177,7 @@ static int tail_records(fem_dev *h, int slot, const void *out, bool copy_records
   }
   if (text) HIP_TRY(h, hipStreamWaitEvent(f->stream, s.ev_text_staged, 0));  // qualities and names came on the slot's text stream
   f->ms_run = since();
-  if (copy_records && h->timing) {
-    FEM_LOCK(h);  // (FEM map retires each slot's batches from a thread of its own)
-    for (int i = 0; i < 3; ++i) h->t_ms[3 + i] += f->ms[i], h->t_n[3 + i] += 1;
-  }
+  if (copy_records && h->timing) count_tail_stages(h, s, false, -1);
   return FEM_OK;
 }
 
@@ -2164,30 +2188,20 @@ static femt::SamInput sam_input(const fem_dev *h, const Slot &s) {
 }
 
 // What follows a text's sam() / bam() (tag: the caller, for FEM_FETCH_TIMES): the pair counts, the event the slot's next text
-// stage waits for (commit_text), the kernel times: 3-5, n_ms of the text's own from id `id` on, 9 and 10 when paired, 13 with MAPQ, 14 with lines for unmapped reads, 15 with the line filter (whose line index is the unmapped reads' too: no 14 then).
-static int text_done(fem_dev *h, int slot, const TailFront &f, const char *tag, int id, const double *ms, int n_ms) {
+// stage waits for (commit_text), the kernel times (count_tail_stages; text_id: the text's own id, < 0: it was not waited for).
+static int text_done(fem_dev *h, int slot, const TailFront &f, const char *tag, int text_id) {
   Slot &s = h->slot[slot];
   s.n_proper = s.paired ? s.tail->n_proper() : 0;  // (sam() and bam() have waited for the stream once, after sizing the text)
   s.n_rescued = s.paired ? s.tail->n_rescued() : 0;
   s.n_unmapped = s.tail->n_unmapped();
   s.n_filtered = s.tail->n_filtered();
-  const bool report = s.report_strata >= 0 || s.report_hits >= 1;
   HIP_TRY(h, s.ev_text_order.create(hipEventDisableTiming));
   HIP_TRY(h, hipEventRecord(s.ev_text_order, f.stream));
   s.have_text_order = true;
   static const bool trace_host = testing_switch("FEM_FETCH_TIMES");  // host time of the call's three stretches, on stderr
   if (trace_host) fprintf(stderr, "[%s] slot %d: mapping synced after %.2f ms, records %.2f, text sized and queued %.2f\n", tag, slot, f.ms_sync,
                           f.ms_run, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - f.t_in).count());
-  if (h->timing) {
-    FEM_LOCK(h);
-    for (int i = 0; i < 3; ++i) h->t_ms[3 + i] += f.ms[i], h->t_n[3 + i] += 1;
-    for (int i = 0; i < n_ms; ++i) h->t_ms[id + i] += ms[i], h->t_n[id + i] += 1;
-    if (s.paired) h->t_ms[9] += s.tail->pair_ms(), h->t_n[9] += 1;
-    if (s.paired && s.rescue) h->t_ms[10] += s.tail->rescue_ms(), h->t_n[10] += 1;
-    if (s.mapq) h->t_ms[13] += s.tail->mapq_ms(), h->t_n[13] += 1;  // (its events precede the text's sizing, which sam() and bam() wait for)
-    if (s.unmapped && !report) h->t_ms[14] += s.tail->unmapped_ms(), h->t_n[14] += 1;  // (as do these)
-    if (report) h->t_ms[15] += s.tail->report_ms(), h->t_n[15] += 1;
-  }
+  if (h->timing) count_tail_stages(h, s, true, text_id);
   return FEM_OK;
 }
 
@@ -2208,11 +2222,10 @@ static int fetch_sam(fem_dev *h, int slot, fem_batch_sam *out, bool wait) {
   if (rc) return rc;
   Slot &s = h->slot[slot];
   femt::SamOutput text{};
-  double ms_text = 0;
   std::string err;
-  rc = s.tail->sam(f.in, sam_input(h, s), f.stream, h->n_cu, &text, &err, h->timing ? &ms_text : nullptr, wait, &h->text_gate, s.paired);
+  rc = s.tail->sam(f.in, sam_input(h, s), f.stream, h->n_cu, &text, &err, wait, &h->text_gate, s.paired);
   if (rc) return fail(h, rc, err);
-  if ((rc = text_done(h, slot, f, "fetch_sam", 7, &ms_text, wait ? 1 : 0))) return rc;  // (without the wait no elapsed time is read: nothing to count)
+  if ((rc = text_done(h, slot, f, "fetch_sam", wait ? 7 : -1))) return rc;
   s.qual_at = text.qual_at;
   out->text = text.text, out->len = text.len, out->n_asserted = text.n_asserted;
   out->n_reads = f.t.n_reads, out->n_records = f.t.n_records - s.n_filtered;  // (the filter drops lines of mapping records only)
@@ -2228,11 +2241,15 @@ static int fetch_bam(fem_dev *h, int slot, int level, fem_batch_bam *out, bool w
   if (rc) return rc;
   Slot &s = h->slot[slot];
   femt::BamOutput bam{};
-  double ms_bam[2] = {0, 0};
+  float ms_bgzf = 0.f;
   std::string err;
-  rc = s.tail->bam(f.in, sam_input(h, s), level, f.stream, h->n_cu, &bam, &err, h->timing ? ms_bam : nullptr, wait, &h->text_gate, s.paired);
+  rc = s.tail->bam(f.in, sam_input(h, s), level, f.stream, h->n_cu, &bam, &err, h->timing ? &ms_bgzf : nullptr, wait, &h->text_gate, s.paired);
   if (rc) return fail(h, rc, err);
-  if ((rc = text_done(h, slot, f, "fetch_bam", 11, ms_bam, 2))) return rc;
+  if ((rc = text_done(h, slot, f, "fetch_bam", 11))) return rc;  // (bam() has waited for its records' stage: the compressor does)
+  if (h->timing) {
+    FEM_LOCK(h);
+    h->t_ms[12] += ms_bgzf, h->t_n[12] += 1;
+  }
   s.qual_at = nullptr;
   out->data = bam.data, out->len = bam.len, out->raw_len = bam.raw_len, out->n_blocks = bam.n_blocks;
   out->n_records = f.t.n_records - s.n_filtered, out->n_asserted = bam.n_asserted;

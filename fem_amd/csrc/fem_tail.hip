@@ -2450,6 +2450,67 @@ __global__ void __launch_bounds__(256) rescue_append_kernel(RescueParams p) {
     }                                                                              \
   } while (0)
 
+// The <kPair, kUnm> instance of a text or BAM kernel (K: sam_len_kernel, sam_write_kernel, bam_len_kernel, bam_write_kernel)
+#define TEXT_KERNEL(K, pair, um) ((um) ? ((pair) ? K<true, true> : K<false, true>) : ((pair) ? K<true> : K<false>))
+
+// A timed stage: what `stream` does between begin() and end().  A stage that starts where another one ends has no first
+// event of its own (follow()).  ran: it was recorded in the last call.
+struct Span {
+  femb::Event first, last;
+  const femb::Event *from = &first;
+  bool ran = false;
+  hipError_t create() {  // (once: reserve() ahead of the first batch, or the first record())
+    const hipError_t e = first.create();
+    return e != hipSuccess ? e : last.create();
+  }
+  hipError_t record(const femb::Event &ev, hipStream_t stream) {
+    const hipError_t e = create();
+    return e != hipSuccess ? e : hipEventRecord(ev, stream);
+  }
+  hipError_t begin(hipStream_t stream) { return from = &first, record(first, stream); }
+  void follow(const Span &before) { from = &before.last; }
+  hipError_t end(hipStream_t stream) { return ran = true, record(last, stream); }
+  float ms() const {  // < 0: it did not run, or the stream has not passed its end
+    float t = 0.f;
+    return ran && hipEventElapsedTime(&t, *from, last) == hipSuccess ? t : -1.f;
+  }
+};
+
+// The LDS plan of trace_kernel and rescue_trace_kernel for reads of up to max_len characters at e edits: lanes = records one
+// 64-thread block walks at a time.
+struct TracePlan { uint32_t text_words, pat_words, lanes, lds_bytes; };
+static int trace_plan(uint32_t max_len, int e, TracePlan *t, std::string *err) {
+  t->text_words = (max_len + 3) / 4 + 4, t->pat_words = (max_len + 2 * (uint32_t)e + 3) / 4 + 4;
+  const uint32_t words_per_lane = t->text_words + t->pat_words + 2 * max_len;
+  t->lanes = std::min<uint32_t>(64, (64u * 1024u / 4u) / words_per_lane);
+  t->lds_bytes = t->lanes * words_per_lane * 4u;
+  if (t->lanes) return FEM_OK;
+  if (err) *err = "read too long for the device traceback";
+  return FEM_ERR_UNSUPPORTED;
+}
+// ... and a record's room in their overflow staging, the longest possible walk: every step opens a run; the MD of a run
+// never exceeds two characters per column.
+struct OverflowCaps { uint32_t ops, md; };
+static OverflowCaps overflow_caps(uint32_t max_len, int e) { return {2 * max_len + 2 * (uint32_t)e + 8, 8 * max_len + 128}; }
+
+// The scratch bytes rocprim's exclusive scan of n items takes, where that is more than *need.
+template <class In, class Out, class T, class Op>
+static hipError_t scan_need(size_t *need, In in, Out out, T init, size_t n, Op op) {
+  size_t bytes = 0;
+  const hipError_t e = rocprim::exclusive_scan(nullptr, bytes, in, out, init, n, op, (hipStream_t) nullptr);
+  *need = std::max(*need, bytes);
+  return e;
+}
+
+// `count` elements of a device array, from element `first` on, to a pinned buffer of min_cap elements at least: queued on `stream`.
+template <class T, class S>
+static hipError_t copy_home(PinBuf<T> &dst, const DevBuf<S> &src, size_t first, size_t count, size_t min_cap, hipStream_t stream) {
+  static_assert(sizeof(T) == sizeof(S), "the pinned copy has the device array's elements");
+  const hipError_t e = dst.ensure(std::max(count, min_cap));
+  if (e != hipSuccess || !count) return e;
+  return hipMemcpyAsync(dst.get(), src.get() + first, count * sizeof(T), hipMemcpyDeviceToHost, stream);
+}
+
 struct Tail::Impl {
   DevBuf<uint32_t> rec_begin, queue, ctl, u_misc, s_misc, s_read, t_ops, o_ops, ovf, rec_list, src_slot, n_ops, n_md, tid, pos0, cigar_off, md_off, cigar;
   DevBuf<uint64_t> u_cand, s_cand;
@@ -2494,23 +2555,63 @@ struct Tail::Impl {
   uint32_t last_n = 0, last_nr = 0;  // what the last run() left on the device
   bool paired = false;               // pair() has run on it
   uint32_t n_resc = 0;               // rescued records the last pair() appended behind run()'s (records last_nr ..)
-  bool resc_timed = false;           // ... and its rescue kernels ran between ev_resc[0] and ev_resc[1]
   bool pair_mapq = false;            // the last pair() left its MAPQ bytes in lmq, not yet made MAPQ by a text
-  bool mapq_timed = false;           // the last text's MAPQ kernel ran between ev_mapq[0] and ev_mapq[1]
-  bool unm_timed = false;            // ... and its line index kernels between ev_unm[0] and ev_unm[1]
+  bool filtered = false;             // the last text went through the line filter
   uint32_t n_unm = 0;                // lines for unmapped reads in the last text
-  bool rep_timed = false;            // the last text's filter kernels ran between ev_rep[0] and ev_rep[1]
   uint32_t n_base_last = 0;          // the lines the last text had before the filter and without the unmapped reads'
   uint32_t n_filtered = 0;           // lines the filter left out of the last text
-  femb::Event ev[4], ev_pair[2], ev_resc[2], ev_mapq[2], ev_unm[2], ev_rep[2];
-  femb::Event ev_text;  // the SAM text has arrived in h_text
+  Span span[kStages];                // (Tail::stage_ms)
+  femb::Event ev_text;               // the SAM text has arrived in h_text
+
+  void not_run(std::initializer_list<Stage> stages) {
+    for (Stage s : stages) span[s].ran = false;
+  }
+  // rocprim's exclusive scan of n items on `stream`; its scratch is scan_tmp, which reserve() and lines() make large
+  // enough (scan_need), or `tmp`
+  template <class In, class Out, class T, class Op>
+  hipError_t scan(In in, Out out, T init, size_t n, Op op, hipStream_t stream, const DevBuf<uint8_t> *tmp = nullptr) {
+    if (!tmp) tmp = &scan_tmp;
+    size_t bytes = tmp->bytes();
+    return rocprim::exclusive_scan(tmp->get(), bytes, in, out, init, n, op, stream);
+  }
+  // Both offsets of n records in one pass: (runs, MD characters) pairs into (cigar_off, md_off).  need: the scratch it takes only.
+  hipError_t scan_runs_md(size_t n, hipStream_t stream, size_t *need = nullptr) {
+    auto lens = rocprim::make_zip_iterator(rocprim::make_tuple(n_ops.get(), n_md.get()));
+    auto offs = rocprim::make_zip_iterator(rocprim::make_tuple(cigar_off.get(), md_off.get()));
+    const auto zero = rocprim::make_tuple(0u, 0u);
+    return need ? scan_need(need, lens, offs, zero, n, PairPlus()) : scan(lens, offs, zero, n, PairPlus(), stream);
+  }
+  // Mate rescue: (kept, runs, MD characters) of p1 pairs, the three parts of r_kept, into those of r_scan; its scratch is
+  // r_scan_tmp, made large enough here.
+  hipError_t scan_kept(size_t p1, hipStream_t stream) {
+    auto lens = rocprim::make_zip_iterator(rocprim::make_tuple(r_kept.get(), r_kept + p1, r_kept + 2 * p1));
+    auto offs = rocprim::make_zip_iterator(rocprim::make_tuple(r_scan.get(), r_scan + p1, r_scan + 2 * p1));
+    const auto zero = rocprim::make_tuple(0u, 0u, 0u);
+    size_t need = 16;
+    hipError_t e = scan_need(&need, lens, offs, zero, p1, TriplePlus());
+    if (e == hipSuccess) e = r_scan_tmp.ensure(need);
+    return e != hipSuccess ? e : scan(lens, offs, zero, p1, TriplePlus(), stream, &r_scan_tmp);
+  }
+  // The records as pair_kernel reads them ...
+  template <class P>
+  void bind_pairing(P *p) const {
+    p->rec_begin = rec_begin, p->flag = flag, p->tid = tid, p->pos0 = pos0;
+    p->nm = nm, p->cigar_off = cigar_off, p->cigar = cigar;
+  }
+  // ... and whole, as the text and the rescue kernels do (where the arrays are now: again after one of them has grown)
+  template <class P>
+  void bind_records(P *p) const {
+    bind_pairing(p);
+    p->s_read = s_read, p->md_off = md_off, p->md = md;
+  }
+
   // sam() and bam(): the lines of run()'s records, or of pair()'s (rescued records included).  Fills *p (all but the text and
-  // qual_at); names.mapq: first the MAPQ kernel (between ev_mapq[0] and ev_mapq[1]); from ev[0] on, each line's length (bad_name:
-  // as BAM, a name over 254 characters setting it; else as SAM), their scan into line_off, the count of asserted records to h_ctl[2].
-  // names.unmapped: the line index first (between ev_unm[0] and ev_unm[1]).  The line count is known on the device alone then:
+  // qual_at); names.mapq: first the MAPQ kernel (stage kMapq); then stage kText begins: each line's length (bad_name: as BAM, a
+  // name over 254 characters setting it; else as SAM), their scan into line_off, the count of asserted records to h_ctl[2].
+  // names.unmapped: the line index first (stage kUnmappedIndex).  The line count is known on the device alone then:
   // p->n_records bounds it (records + reads; the lengths behind the last line are zero, so line_off[p->n_records] is the text's
   // size all the same) and the count comes to h_ctl[8]; counted() puts it into p->n_records once the stream has been waited for.
-  // names.strata / names.max_hits (the line filter): the line index is report_kernel's instead (between ev_rep[0] and ev_rep[1]),
+  // names.strata / names.max_hits (the line filter): the line index is report_kernel's instead (stage kFilterIndex),
   // unmapped reads' lines included where names.unmapped asks for them; the count comes home the same way, the unmapped slots'
   // to h_ctl[9].  The text and BAM kernels are the kUnm instances then, with or without names.unmapped: without it u_base lies
   // above every source and pair_begin is nullptr (mate_cols), so that no line takes a shape it has not without the filter.
@@ -2530,24 +2631,22 @@ struct Tail::Impl {
     const uint32_t nr = n_base + (names.unmapped ? last_n : 0u);
     const size_t r1 = (size_t)nr + 1, n1 = (size_t)last_n + 1;
     const bool report = names.strata >= 0 || names.max_hits >= 1;
-    for (femb::Event &e : ev) TAIL_TRY(e.create());
+    not_run({kText, kMapq, kUnmappedIndex, kFilterIndex});
     TAIL_TRY(line_len.ensure(r1));
     TAIL_TRY(line_off.ensure(r1));
     TAIL_TRY(h_ctl.ensure(12));
-    size_t tmp = 0, tmp_u = 0;
-    TAIL_TRY(rocprim::exclusive_scan(nullptr, tmp, line_len.get(), line_off.get(), 0ull, r1,
-                                     rocprim::plus<unsigned long long>(), stream));
+    size_t need = 16;
+    TAIL_TRY(scan_need(&need, line_len.get(), line_off.get(), 0ull, r1, rocprim::plus<unsigned long long>()));
     if (names.unmapped || report) {
       TAIL_TRY(u_cnt.ensure(n1));
       TAIL_TRY(u_before.ensure(n1));
       TAIL_TRY(usrc.ensure(std::max<size_t>(nr, 1)));
       TAIL_TRY(u_ctl.ensure(4));
-      TAIL_TRY(rocprim::exclusive_scan(nullptr, tmp_u, u_cnt.get(), u_before.get(), 0u, n1, rocprim::plus<uint32_t>(), stream));
+      TAIL_TRY(scan_need(&need, u_cnt.get(), u_before.get(), 0u, n1, rocprim::plus<uint32_t>()));
     }
-    TAIL_TRY(scan_tmp.ensure(std::max<size_t>(std::max(tmp, tmp_u), 16)));
-    p->n_records = nr, p->rec_begin = rec_begin, p->s_read = s_read;
-    p->flag = flag, p->tid = tid, p->pos0 = pos0, p->nm = nm;
-    p->cigar_off = cigar_off, p->cigar = cigar, p->md_off = md_off, p->md = md;
+    TAIL_TRY(scan_tmp.ensure(need));
+    bind_records(p);
+    p->n_records = nr;
     p->bases = in.bases, p->read_off = in.read_off;
     p->quals = names.quals, p->names = names.names, p->name_off = names.name_off, p->ref_names = names.ref_names, p->ref_name_off = names.ref_name_off;
     p->line_len = line_len, p->line_off = line_off;
@@ -2572,10 +2671,9 @@ struct Tail::Impl {
       p->hit_tags = 1u, p->hit_by_line = report ? 1u : 0u;
       p->hit_begin = report ? u_before : pair_order ? pair_begin : rec_begin;
     }
-    unm_timed = false, n_unm = 0;
-    rep_timed = false, n_filtered = 0, n_base_last = n_base;
+    n_unm = 0;
+    filtered = report, n_filtered = 0, n_base_last = n_base;
     if (report) {
-      for (femb::Event &e : ev_rep) TAIL_TRY(e.create());
       ReportParams f{};
       f.n_reads = last_n, f.n_base = n_base, f.begin = pair_order ? pair_begin : rec_begin;
       f.nm = nm, f.perm = pair_order ? perm : nullptr;
@@ -2583,48 +2681,41 @@ struct Tail::Impl {
       f.unmapped = names.unmapped ? 1u : 0u;
       f.cnt = u_cnt, f.before = u_before, f.usrc = usrc, f.n_lines = u_ctl;
       const dim3 grid((last_n + 256u) / 256u);
-      TAIL_TRY(hipEventRecord(ev_rep[0], stream));
+      TAIL_TRY(span[kFilterIndex].begin(stream));
       TAIL_TRY(hipMemsetAsync(u_ctl, 0, 8, stream));
       hipLaunchKernelGGL(report_kernel<false>, grid, dim3(256), 0, stream, f);
       TAIL_TRY(hipGetLastError());
-      size_t tmp_bytes = scan_tmp.bytes();
-      TAIL_TRY(rocprim::exclusive_scan(scan_tmp.get(), tmp_bytes, u_cnt.get(), u_before.get(), 0u, n1, rocprim::plus<uint32_t>(), stream));
+      TAIL_TRY(scan(u_cnt.get(), u_before.get(), 0u, n1, rocprim::plus<uint32_t>(), stream));
       hipLaunchKernelGGL(report_kernel<true>, grid, dim3(256), 0, stream, f);
       TAIL_TRY(hipGetLastError());
-      TAIL_TRY(hipEventRecord(ev_rep[1], stream));
+      TAIL_TRY(span[kFilterIndex].end(stream));
       TAIL_TRY(hipMemcpyAsync(h_ctl + 8, u_ctl, 8, hipMemcpyDeviceToHost, stream));
-      rep_timed = true;
       p->usrc = usrc, p->u_base = names.unmapped ? n_base : kNoMate, p->n_reads = last_n, p->u_lines = u_ctl;
       p->pair_begin = names.unmapped ? pair_begin : nullptr;
     } else if (names.unmapped) {
-      for (femb::Event &e : ev_unm) TAIL_TRY(e.create());
       UlineParams u{};
       u.n_reads = last_n, u.n_base = n_base, u.paired = pair_order ? 1u : 0u;
       u.begin = pair_order ? pair_begin : rec_begin;
       u.s_read = s_read, u.perm = perm;
       u.cnt = u_cnt, u.before = u_before, u.usrc = usrc, u.n_lines = u_ctl;
-      TAIL_TRY(hipEventRecord(ev_unm[0], stream));
+      TAIL_TRY(span[kUnmappedIndex].begin(stream));
       hipLaunchKernelGGL(unmapped_mark_kernel, dim3((last_n + 256u) / 256u), dim3(256), 0, stream, u);
       TAIL_TRY(hipGetLastError());
-      size_t tmp_bytes = scan_tmp.bytes();
-      TAIL_TRY(rocprim::exclusive_scan(scan_tmp.get(), tmp_bytes, u_cnt.get(), u_before.get(), 0u, n1, rocprim::plus<uint32_t>(), stream));
+      TAIL_TRY(scan(u_cnt.get(), u_before.get(), 0u, n1, rocprim::plus<uint32_t>(), stream));
       const uint32_t work = std::max(n_base, last_n);
       hipLaunchKernelGGL(unmapped_src_kernel, dim3(std::max<uint32_t>(1u, std::min<uint32_t>((work + 255u) / 256u, (uint32_t)n_cu * 16u))),
                          dim3(256), 0, stream, u);
       TAIL_TRY(hipGetLastError());
-      TAIL_TRY(hipEventRecord(ev_unm[1], stream));
+      TAIL_TRY(span[kUnmappedIndex].end(stream));
       TAIL_TRY(hipMemcpyAsync(h_ctl + 8, u_ctl, 4, hipMemcpyDeviceToHost, stream));
-      unm_timed = true;
       p->usrc = usrc, p->u_base = n_base, p->n_reads = last_n, p->u_lines = u_ctl;
       p->pair_begin = pair_begin;
     }
-    mapq_timed = false;
     if (names.mapq) {
       if (pair_order && !pair_mapq) {
         if (err) *err = "the records were paired without MAPQ (Tail::pair)";
         return FEM_ERR_STATE;
       }
-      for (femb::Event &e : ev_mapq) TAIL_TRY(e.create());
       MapqParams q{};
       q.n_reads = last_n, q.e = in.e, q.rec_begin = rec_begin, q.nm = nm;
       if (pair_order) {
@@ -2636,34 +2727,29 @@ struct Tail::Impl {
         q.q_read = q_read;
         p->mapq = q_read;
       }
-      TAIL_TRY(hipEventRecord(ev_mapq[0], stream));
+      TAIL_TRY(span[kMapq].begin(stream));
       if (last_n) {
         hipLaunchKernelGGL(mapq_kernel, dim3((last_n + 255u) / 256u), dim3(256), 0, stream, q);
         TAIL_TRY(hipGetLastError());
       }
-      TAIL_TRY(hipEventRecord(ev_mapq[1], stream));
-      mapq_timed = true;
+      TAIL_TRY(span[kMapq].end(stream));
     }
     if (bad_name) TAIL_TRY(hipMemsetAsync(bad_name, 0, 4, stream));
-    TAIL_TRY(hipEventRecord(ev[0], stream));
+    TAIL_TRY(span[kText].begin(stream));
     const dim3 len_grid(std::max<uint32_t>(1u, std::min<uint32_t>((nr + 256u) / 256u, (uint32_t)n_cu * 16u)));
     const bool um = names.unmapped || report;
     if (bad_name)
-      hipLaunchKernelGGL(um ? (pair_order ? bam_len_kernel<true, true> : bam_len_kernel<false, true>)
-                            : (pair_order ? bam_len_kernel<true> : bam_len_kernel<false>), len_grid, dim3(256), 0, stream, *p, last_n, bad_name);
+      hipLaunchKernelGGL(TEXT_KERNEL(bam_len_kernel, pair_order, um), len_grid, dim3(256), 0, stream, *p, last_n, bad_name);
     else
-      hipLaunchKernelGGL(um ? (pair_order ? sam_len_kernel<true, true> : sam_len_kernel<false, true>)
-                            : (pair_order ? sam_len_kernel<true> : sam_len_kernel<false>), len_grid, dim3(256), 0, stream, *p);
+      hipLaunchKernelGGL(TEXT_KERNEL(sam_len_kernel, pair_order, um), len_grid, dim3(256), 0, stream, *p);
     TAIL_TRY(hipGetLastError());
-    size_t tmp_bytes = scan_tmp.bytes();
-    TAIL_TRY(rocprim::exclusive_scan(scan_tmp.get(), tmp_bytes, line_len.get(), line_off.get(), 0ull,
-                                     r1, rocprim::plus<unsigned long long>(), stream));
+    TAIL_TRY(scan(line_len.get(), line_off.get(), 0ull, r1, rocprim::plus<unsigned long long>(), stream));
     TAIL_TRY(hipMemcpyAsync(h_ctl + 2, ctl + 2, 4, hipMemcpyDeviceToHost, stream));
     return FEM_OK;
   }
   // after lines() and a wait for its stream: the number of lines (into p->n_records, which bounded it), n_unm
   uint32_t counted(const SamInput &names, SamParams *p) {
-    if (rep_timed) {  // (the filter: what it kept, the unmapped reads' lines among them)
+    if (filtered) {  // (what the filter kept, the unmapped reads' lines among them)
       const uint32_t n_lines = std::min(h_ctl[8], p->n_records);
       n_unm = names.unmapped ? std::min(h_ctl[9], n_lines) : 0u;
       n_filtered = n_base_last + n_unm - n_lines;
@@ -2676,10 +2762,10 @@ struct Tail::Impl {
     return p->n_records;
   }
 
-  // A text's way home after ev[1]: `bytes` from src into h_text (and bytes2 from src2 into dst2: SAM's qual_at) behind the text
-  // that took the gate before (TextGate), ev_text its arrival; wait: until then.  ms += ev[0]..ev[1] (the stream has passed ev[1]).
+  // A text's way home after stage kText: `bytes` from src into h_text (and bytes2 from src2 into dst2: SAM's qual_at) behind the
+  // text that took the gate before (TextGate), ev_text its arrival; wait: until then.
   int send_home(const void *src, size_t bytes, void *dst2, const void *src2, size_t bytes2, hipStream_t stream, bool wait, TextGate *gate,
-                  double *ms, std::string *err) {
+                  std::string *err) {
     TAIL_TRY(ev_text.create(hipEventDisableTiming));
     static const bool no_gate = getenv("FEM_TESTING") && getenv("FEM_TEXT_NO_GATE");  // (A/B)
     if (no_gate) gate = nullptr;
@@ -2697,21 +2783,28 @@ struct Tail::Impl {
       if (gate) gate->last = ev_text;
     }
     if (wait) TAIL_TRY(hipStreamSynchronize(stream));
-    float t = 0.f;
-    if (ms && hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess) *ms += t;
     return FEM_OK;
   }
 };
 
-Tail::~Tail() { delete impl_; }
+Tail::Tail() = default;  // (both out of line: Impl is incomplete in the header)
+Tail::~Tail() = default;
+
+int Tail::impl(Impl **m) {
+  if (!impl_) impl_.reset(new (std::nothrow) Impl());
+  *m = impl_.get();
+  return impl_ ? FEM_OK : FEM_ERR_NOMEM;
+}
+
+float Tail::stage_ms(Stage stage) const { return impl_ ? impl_->span[stage].ms() : -1.f; }
 
 // Everything run() and sam() allocate for a batch of n reads with nr records (device arrays sized by the records, the scans'
 // scratch).  run() calls it with the batch's own numbers; a caller that knows what is coming (fem_dev_reserve_batch) calls it
 // during its setup: thirty allocations per slot otherwise fall into the first batches' way home.
 int Tail::reserve(uint32_t n, uint32_t nr, uint32_t max_len_in, int e, bool tiny, std::string *err) {
-  if (!impl_) impl_ = new (std::nothrow) Impl();
-  if (!impl_) return FEM_ERR_NOMEM;
-  Impl &m = *impl_;
+  Impl *mp;
+  if (int rc = impl(&mp)) return rc;
+  Impl &m = *mp;
   const uint32_t fast_ops = std::min<uint32_t>(kOpsCap, 2u * (uint32_t)e + 2u);
   const uint32_t ops_cap = tiny ? 1u : std::max<uint32_t>(8u, fast_ops), md_cap = tiny ? 2u : kMdCap;
   (void)max_len_in;
@@ -2744,18 +2837,12 @@ int Tail::reserve(uint32_t n, uint32_t nr, uint32_t max_len_in, int e, bool tiny
   TAIL_TRY(m.line_off.ensure(r1));
   TAIL_TRY(m.qual_at.ensure((size_t)n + 1));
   TAIL_TRY(m.h_qual_at.ensure((size_t)n + 1));
-  size_t tmp_a = 0, tmp_b = 0, tmp_c = 0;
-  TAIL_TRY(rocprim::exclusive_scan(nullptr, tmp_a, (const uint32_t *)nullptr, m.rec_begin.get(), 0u, (size_t)n,
-                                   rocprim::plus<uint32_t>(), (hipStream_t) nullptr));
-  {
-    auto lens = rocprim::make_zip_iterator(rocprim::make_tuple(m.n_ops.get(), m.n_md.get()));
-    auto offs = rocprim::make_zip_iterator(rocprim::make_tuple(m.cigar_off.get(), m.md_off.get()));
-    TAIL_TRY(rocprim::exclusive_scan(nullptr, tmp_b, lens, offs, rocprim::make_tuple(0u, 0u), r1, PairPlus(), (hipStream_t) nullptr));
-  }
-  TAIL_TRY(rocprim::exclusive_scan(nullptr, tmp_c, m.line_len.get(), m.line_off.get(), 0ull, r1,
-                                   rocprim::plus<unsigned long long>(), (hipStream_t) nullptr));
-  TAIL_TRY(m.scan_tmp.ensure(std::max<size_t>(std::max(tmp_a, std::max(tmp_b, tmp_c)), 16)));
-  for (femb::Event &ev : m.ev) TAIL_TRY(ev.create());
+  size_t need = 16;  // run()'s two scans and the text's
+  TAIL_TRY(scan_need(&need, (const uint32_t *)nullptr, m.rec_begin.get(), 0u, (size_t)n, rocprim::plus<uint32_t>()));
+  TAIL_TRY(m.scan_runs_md(r1, nullptr, &need));
+  TAIL_TRY(scan_need(&need, m.line_len.get(), m.line_off.get(), 0ull, r1, rocprim::plus<unsigned long long>()));
+  TAIL_TRY(m.scan_tmp.ensure(need));
+  for (Span &s : m.span) TAIL_TRY(s.create());
   TAIL_TRY(m.ev_text.create(hipEventDisableTiming));
   return FEM_OK;
 }
@@ -2782,21 +2869,12 @@ int Tail::warm(hipStream_t stream, std::string *err) {
                            (const void *)rescue_search_kernel, (const void *)rescue_trace_kernel, (const void *)rescue_append_kernel};
   for (const void *k : kernels) TAIL_TRY(hipFuncGetAttributes(&a, k));
   if (!m.scan_tmp || !m.rec_begin || !m.n_ops || !m.line_len) return FEM_OK;  // (nothing reserved: the scans load with the first batch)
-  size_t tmp = m.scan_tmp.bytes();
   TAIL_TRY(hipMemsetAsync(m.n_ops, 0, 4, stream));
   TAIL_TRY(hipMemsetAsync(m.n_md, 0, 4, stream));
   TAIL_TRY(hipMemsetAsync(m.line_len, 0, 8, stream));
-  TAIL_TRY(rocprim::exclusive_scan(m.scan_tmp.get(), tmp, (const uint32_t *)m.n_ops.get(), m.rec_begin.get(), 0u, (size_t)1,
-                                   rocprim::plus<uint32_t>(), stream));
-  {
-    auto lens = rocprim::make_zip_iterator(rocprim::make_tuple(m.n_ops.get(), m.n_md.get()));
-    auto offs = rocprim::make_zip_iterator(rocprim::make_tuple(m.cigar_off.get(), m.md_off.get()));
-    tmp = m.scan_tmp.bytes();
-    TAIL_TRY(rocprim::exclusive_scan(m.scan_tmp.get(), tmp, lens, offs, rocprim::make_tuple(0u, 0u), (size_t)1, PairPlus(), stream));
-  }
-  tmp = m.scan_tmp.bytes();
-  TAIL_TRY(rocprim::exclusive_scan(m.scan_tmp.get(), tmp, m.line_len.get(), m.line_off.get(), 0ull, (size_t)1,
-                                   rocprim::plus<unsigned long long>(), stream));
+  TAIL_TRY(m.scan((const uint32_t *)m.n_ops.get(), m.rec_begin.get(), 0u, (size_t)1, rocprim::plus<uint32_t>(), stream));
+  TAIL_TRY(m.scan_runs_md(1, stream));
+  TAIL_TRY(m.scan(m.line_len.get(), m.line_off.get(), 0ull, (size_t)1, rocprim::plus<unsigned long long>(), stream));
   if (m.text && m.h_text && m.text.bytes() >= (1u << 20) && m.h_text.bytes() >= (1u << 20))
     TAIL_TRY(hipMemcpyAsync(m.h_text, m.text, 1u << 20, hipMemcpyDeviceToHost, stream));
   TAIL_TRY(hipMemcpyAsync(m.h_ctl, m.ctl, 16, hipMemcpyDeviceToHost, stream));
@@ -2804,27 +2882,20 @@ int Tail::warm(hipStream_t stream, std::string *err) {
   return FEM_OK;
 }
 
-int Tail::run(const TailInput &in, hipStream_t stream, int n_cu, bool tiny, TailOutput *out, std::string *err, double *ms,
-              bool copy_records) {
-  if (!impl_) impl_ = new (std::nothrow) Impl();
-  if (!impl_) return FEM_ERR_NOMEM;
-  Impl &m = *impl_;
+int Tail::run(const TailInput &in, hipStream_t stream, int n_cu, bool tiny, TailOutput *out, std::string *err, bool copy_records) {
+  Impl *mp;
+  if (int rc = impl(&mp)) return rc;
+  Impl &m = *mp;
   if (in.n_records > 0xFFFFFFF0ull) {
     if (err) *err = "more than 2^32 mappings in one batch; split the batch";
     return FEM_ERR_UNSUPPORTED;
   }
   const uint32_t n = in.n_reads, nr = (uint32_t)in.n_records;
 
-  // ---- LDS plan of the traceback kernel: lanes = records one 64-thread block walks at a time ----
   const uint32_t max_len = std::max<uint32_t>(in.max_len, 1);
-  const uint32_t text_words = (max_len + 3) / 4 + 4, pat_words = (max_len + 2 * (uint32_t)in.e + 3) / 4 + 4;
-  const uint32_t words_per_lane = text_words + pat_words + 2 * max_len;
-  const uint32_t lanes = std::min<uint32_t>(64, (64u * 1024u / 4u) / words_per_lane);
-  if (lanes == 0) {
-    if (err) *err = "read too long for the device traceback";
-    return FEM_ERR_UNSUPPORTED;
-  }
-  const uint32_t lds_bytes = lanes * words_per_lane * 4u;
+  TracePlan plan;
+  if (int rc = trace_plan(max_len, in.e, &plan, err)) return rc;
+  const uint32_t lanes = plan.lanes;
   // first-pass kernel: one packed word per column (two fields of 2e+1 bits) + the run list
   const uint32_t hist_bytes = (2u * (2u * (uint32_t)in.e + 1u) + 7u) / 8u;  // 1, 1, 2, 2, 3, 3, 4, 4 for e = 0..7
   const uint32_t fast_ops = std::min<uint32_t>(kOpsCap, 2u * (uint32_t)in.e + 2u);  // a sane walk opens <= 2 ed + 1 runs
@@ -2833,8 +2904,7 @@ int Tail::run(const TailInput &in, hipStream_t stream, int n_cu, bool tiny, Tail
   const uint32_t fast_lds = ((max_len * hist_bytes * fast_lanes + 3u) & ~3u) + fast_ops * 2u * fast_lanes;
   // (the staging's rows are read and written one record per lane: the shorter the row, the fewer lines a wave touches)
   const uint32_t ops_cap = tiny ? 1u : std::max<uint32_t>(8u, fast_ops), md_cap = tiny ? 2u : kMdCap;
-  // longest possible walk: every step opens a run; the MD of a run never exceeds two characters per column
-  const uint32_t o_ops_cap = 2 * max_len + 2 * (uint32_t)in.e + 8, o_md_cap = 8 * max_len + 128;
+  const OverflowCaps o_cap = overflow_caps(max_len, in.e);
 
   static const bool trace_host = getenv("FEM_TESTING") && getenv("FEM_FETCH_TIMES");
   const auto t_in = std::chrono::steady_clock::now();
@@ -2845,7 +2915,6 @@ int Tail::run(const TailInput &in, hipStream_t stream, int n_cu, bool tiny, Tail
   }
   const double ms_reserved = since_in();
   const size_t r1 = (size_t)nr + 1;
-  size_t tmp_bytes = m.scan_tmp.bytes();
 
   Params p{};
   p.bases = in.bases, p.read_off = in.read_off, p.n_reads = n;
@@ -2860,20 +2929,21 @@ int Tail::run(const TailInput &in, hipStream_t stream, int n_cu, bool tiny, Tail
   p.queue = m.queue, p.ctl = m.ctl;
   p.g_keys = (uint64_t *)m.t_md.get();
   p.g_idx = (uint32_t *)(m.t_md + r1 * 8);
-  p.lanes = lanes, p.text_words = text_words, p.pat_words = pat_words, p.max_len = max_len, p.fast_lanes = fast_lanes, p.fast_ops = fast_ops;
+  p.lanes = lanes, p.text_words = plan.text_words, p.pat_words = plan.pat_words, p.max_len = max_len, p.fast_lanes = fast_lanes, p.fast_ops = fast_ops;
   p.t_ops = m.t_ops, p.t_md = m.t_md, p.ops_cap = ops_cap, p.md_cap = md_cap;
   p.ovf_queue = nullptr, p.ovf_out = m.ovf, p.src_slot = m.src_slot;
   p.rec_list = m.rec_list;
   p.n_ops = m.n_ops, p.n_md = m.n_md;
   p.flag = m.flag, p.tid = m.tid, p.pos0 = m.pos0, p.nm = m.nm;
 
+  // the three stages share four events: the traceback starts where the ordering ends, the compaction where the traceback does
+  Span &ordering = m.span[kOrder], &traceback = m.span[kTrace], &compaction = m.span[kCompact];
+  for (Span &s : m.span) s.ran = false;
+  traceback.follow(ordering), compaction.follow(traceback);
   uint32_t *h_ctl = m.h_ctl;
-  TAIL_TRY(hipEventRecord(m.ev[0], stream));
+  TAIL_TRY(ordering.begin(stream));
   TAIL_TRY(hipMemsetAsync(m.ctl, 0, 16, stream));
-  if (n) {
-    TAIL_TRY(rocprim::exclusive_scan(m.scan_tmp.get(), tmp_bytes, (const uint32_t *)in.n_map, m.rec_begin.get(), 0u,
-                                     (size_t)n, rocprim::plus<uint32_t>(), stream));
-  }
+  if (n) TAIL_TRY(m.scan((const uint32_t *)in.n_map, m.rec_begin.get(), 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
   TAIL_TRY(hipMemsetD32Async((hipDeviceptr_t)(m.rec_begin + n), (int)nr, 1, stream));
   uint32_t n_overflow = 0;
   if (nr) {
@@ -2881,7 +2951,7 @@ int Tail::run(const TailInput &in, hipStream_t stream, int n_cu, bool tiny, Tail
     TAIL_TRY(hipGetLastError());
     hipLaunchKernelGGL(sort_kernel, dim3((uint32_t)n_cu * 4u), dim3(64), 0, stream, p);
     TAIL_TRY(hipGetLastError());
-    TAIL_TRY(hipEventRecord(m.ev[1], stream));
+    TAIL_TRY(ordering.end(stream));
     // zero-edit records first (no recurrence); what they leave goes through the walking kernel
     hipLaunchKernelGGL(trace_ident_kernel, dim3(std::min<uint32_t>((nr + kIdentChunk - 1u) / kIdentChunk, (uint32_t)n_cu * 8u)), dim3(256), 0, stream, p);
     TAIL_TRY(hipGetLastError());
@@ -2903,78 +2973,58 @@ int Tail::run(const TailInput &in, hipStream_t stream, int n_cu, bool tiny, Tail
     if (getenv("FEM_TESTING") && getenv("FEM_TAIL_DEBUG"))
       fprintf(stderr, "[tail] records %u, queued for ordering %u, walked %u, overflow pass %u, lanes %u/%u\n", nr, h_ctl[0], h_ctl[3], n_overflow, fast_lanes, lanes);
     if (n_overflow) {  // records whose CIGAR or MD outgrew the first staging: once more, with room for any walk
-      TAIL_TRY(m.o_ops.ensure((size_t)n_overflow * o_ops_cap));
-      TAIL_TRY(m.o_md.ensure((size_t)n_overflow * o_md_cap));
+      TAIL_TRY(m.o_ops.ensure((size_t)n_overflow * o_cap.ops));
+      TAIL_TRY(m.o_md.ensure((size_t)n_overflow * o_cap.md));
       Params q = p;
       q.ovf_queue = m.ovf;
-      q.t_ops = m.o_ops, q.t_md = m.o_md, q.ops_cap = o_ops_cap, q.md_cap = o_md_cap;
+      q.t_ops = m.o_ops, q.t_md = m.o_md, q.ops_cap = o_cap.ops, q.md_cap = o_cap.md;
       const uint32_t b2 = std::min<uint32_t>((n_overflow + lanes - 1) / lanes, (uint32_t)n_cu * 16u);
-      hipLaunchKernelGGL(trace_kernel, dim3(b2), dim3(64), lds_bytes, stream, q);
+      hipLaunchKernelGGL(trace_kernel, dim3(b2), dim3(64), plan.lds_bytes, stream, q);
       TAIL_TRY(hipGetLastError());
     }
   } else {
-    TAIL_TRY(hipEventRecord(m.ev[1], stream));
+    TAIL_TRY(ordering.end(stream));
   }
-  TAIL_TRY(hipEventRecord(m.ev[2], stream));
+  TAIL_TRY(traceback.end(stream));
   // ---- compaction: offsets by exclusive scans over n_records + 1 lengths (the last one zero) ----
   TAIL_TRY(hipMemsetAsync(m.n_ops + nr, 0, 4, stream));
   TAIL_TRY(hipMemsetAsync(m.n_md + nr, 0, 4, stream));
-  {  // both offsets in one pass: a scan over (runs, MD characters) pairs
-    auto lens = rocprim::make_zip_iterator(rocprim::make_tuple(m.n_ops.get(), m.n_md.get()));
-    auto offs = rocprim::make_zip_iterator(rocprim::make_tuple(m.cigar_off.get(), m.md_off.get()));
-    TAIL_TRY(rocprim::exclusive_scan(m.scan_tmp.get(), tmp_bytes, lens, offs, rocprim::make_tuple(0u, 0u), r1, PairPlus(), stream));
-  }
+  TAIL_TRY(m.scan_runs_md(r1, stream));
   // (the compacted arrays are sized by what the stagings can hold, so that no round trip to the host sits between the scan
   // and the kernel that uses it; the totals come back with everything else)
-  TAIL_TRY(m.cigar.ensure(std::max<size_t>((size_t)nr * ops_cap + (size_t)n_overflow * o_ops_cap, 1)));
-  TAIL_TRY(m.md.ensure(std::max<size_t>((size_t)nr * md_cap + (size_t)n_overflow * o_md_cap, 1)));
+  TAIL_TRY(m.cigar.ensure(std::max<size_t>((size_t)nr * ops_cap + (size_t)n_overflow * o_cap.ops, 1)));
+  TAIL_TRY(m.md.ensure(std::max<size_t>((size_t)nr * md_cap + (size_t)n_overflow * o_cap.md, 1)));
   if (nr) {
     CompactParams c{};
     c.n_records = nr, c.src_slot = p.src_slot, c.n_ops = p.n_ops, c.n_md = p.n_md;
     c.cigar_off = m.cigar_off, c.md_off = m.md_off;
     c.t_ops = p.t_ops, c.t_md = p.t_md, c.o_ops = m.o_ops, c.o_md = m.o_md;
-    c.ops_cap = ops_cap, c.md_cap = md_cap, c.o_ops_cap = o_ops_cap, c.o_md_cap = o_md_cap;
+    c.ops_cap = ops_cap, c.md_cap = md_cap, c.o_ops_cap = o_cap.ops, c.o_md_cap = o_cap.md;
     c.cigar = m.cigar, c.md = m.md;
     hipLaunchKernelGGL(compact_kernel, dim3((nr + 255u) / 256u), dim3(256), 0, stream, c);
     TAIL_TRY(hipGetLastError());
   }
-  TAIL_TRY(hipEventRecord(m.ev[3], stream));
+  TAIL_TRY(compaction.end(stream));
   TAIL_TRY(hipMemcpyAsync(h_ctl + 4, m.cigar_off + nr, 4, hipMemcpyDeviceToHost, stream));
   TAIL_TRY(hipMemcpyAsync(h_ctl + 5, m.md_off + nr, 4, hipMemcpyDeviceToHost, stream));
-  m.last_n = n, m.last_nr = nr, m.paired = false, m.n_resc = 0, m.resc_timed = false, m.pair_mapq = false;
+  m.last_n = n, m.last_nr = nr, m.paired = false, m.n_resc = 0, m.pair_mapq = false;
   if (copy_records) {  // ---- copy back (else the caller renders the records on the device: sam(), bam()) ----
     TAIL_TRY(hipStreamSynchronize(stream));
-    const uint32_t n_cigar = h_ctl[4], n_md = h_ctl[5];
-    TAIL_TRY(m.h_rec_begin.ensure((size_t)n + 1));
-    TAIL_TRY(m.h_flag.ensure(r1));
-    TAIL_TRY(m.h_tid.ensure(r1));
-    TAIL_TRY(m.h_pos0.ensure(r1));
-    TAIL_TRY(m.h_nm.ensure(r1));
-    TAIL_TRY(m.h_cigar_off.ensure(r1));
-    TAIL_TRY(m.h_md_off.ensure(r1));
-    TAIL_TRY(m.h_cigar.ensure(std::max<size_t>(n_cigar, 1)));
-    TAIL_TRY(m.h_md.ensure(std::max<size_t>(n_md, 1)));
-    TAIL_TRY(hipMemcpyAsync(m.h_rec_begin, m.rec_begin, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost, stream));
-    TAIL_TRY(hipMemcpyAsync(m.h_cigar_off, m.cigar_off, r1 * 4, hipMemcpyDeviceToHost, stream));
-    TAIL_TRY(hipMemcpyAsync(m.h_md_off, m.md_off, r1 * 4, hipMemcpyDeviceToHost, stream));
-    if (nr) {
-      TAIL_TRY(hipMemcpyAsync(m.h_flag, m.flag, (size_t)nr * 2, hipMemcpyDeviceToHost, stream));
-      TAIL_TRY(hipMemcpyAsync(m.h_tid, m.tid, (size_t)nr * 4, hipMemcpyDeviceToHost, stream));
-      TAIL_TRY(hipMemcpyAsync(m.h_pos0, m.pos0, (size_t)nr * 4, hipMemcpyDeviceToHost, stream));
-      TAIL_TRY(hipMemcpyAsync(m.h_nm, m.nm, (size_t)nr, hipMemcpyDeviceToHost, stream));
-    }
-    if (n_cigar) TAIL_TRY(hipMemcpyAsync(m.h_cigar, m.cigar, (size_t)n_cigar * 4, hipMemcpyDeviceToHost, stream));
-    if (n_md) TAIL_TRY(hipMemcpyAsync(m.h_md, m.md, (size_t)n_md, hipMemcpyDeviceToHost, stream));
+    TAIL_TRY(copy_home(m.h_rec_begin, m.rec_begin, 0, (size_t)n + 1, 0, stream));
+    TAIL_TRY(copy_home(m.h_cigar_off, m.cigar_off, 0, r1, 0, stream));
+    TAIL_TRY(copy_home(m.h_md_off, m.md_off, 0, r1, 0, stream));
+    TAIL_TRY(copy_home(m.h_flag, m.flag, 0, nr, r1, stream));
+    TAIL_TRY(copy_home(m.h_tid, m.tid, 0, nr, r1, stream));
+    TAIL_TRY(copy_home(m.h_pos0, m.pos0, 0, nr, r1, stream));
+    TAIL_TRY(copy_home(m.h_nm, m.nm, 0, nr, r1, stream));
+    TAIL_TRY(copy_home(m.h_cigar, m.cigar, 0, h_ctl[4], 1, stream));
+    TAIL_TRY(copy_home(m.h_md, m.md, 0, h_ctl[5], 1, stream));
   }
   TAIL_TRY(hipMemcpyAsync(h_ctl, m.ctl, 16, hipMemcpyDeviceToHost, stream));
   TAIL_TRY(hipStreamSynchronize(stream));
   if (h_ctl[2] != 0) {
     if (err) *err = "device traceback: a record outgrew the overflow staging (internal error)";
     return FEM_ERR_HIP;
-  }
-  for (int i = 0; ms && i < 3; ++i) {
-    float t = 0.f;
-    if (hipEventElapsedTime(&t, m.ev[i], m.ev[i + 1]) == hipSuccess) ms[i] += t;
   }
   *out = TailOutput{};
   out->n_reads = n, out->n_records = nr;
@@ -2989,10 +3039,10 @@ int Tail::run(const TailInput &in, hipStream_t stream, int n_cu, bool tiny, Tail
 }
 
 int Tail::reserve_text(uint64_t bytes, std::string *err) {
-  if (!impl_) impl_ = new (std::nothrow) Impl();
-  if (!impl_) return FEM_ERR_NOMEM;
-  TAIL_TRY(impl_->text.ensure((size_t)bytes));
-  TAIL_TRY(impl_->h_text.ensure((size_t)bytes));
+  Impl *m;
+  if (int rc = impl(&m)) return rc;
+  TAIL_TRY(m->text.ensure((size_t)bytes));
+  TAIL_TRY(m->h_text.ensure((size_t)bytes));
   return FEM_OK;
 }
 
@@ -3001,8 +3051,8 @@ int Tail::wait_text() {
   return hipEventSynchronize(impl_->ev_text) == hipSuccess ? FEM_OK : FEM_ERR_HIP;
 }
 
-int Tail::sam(const TailInput &in, const SamInput &names, hipStream_t stream, int n_cu, SamOutput *out, std::string *err, double *ms,
-              bool wait, TextGate *gate, bool paired) {
+int Tail::sam(const TailInput &in, const SamInput &names, hipStream_t stream, int n_cu, SamOutput *out, std::string *err, bool wait,
+              TextGate *gate, bool paired) {
   if (!impl_ || !out) return FEM_ERR_STATE;
   Impl &m = *impl_;
   SamParams p{};
@@ -3026,12 +3076,11 @@ int Tail::sam(const TailInput &in, const SamInput &names, hipStream_t stream, in
   if (nr) {
     p.text = m.text;
     const uint32_t blocks = (nr + 255u) / 256u;  // a wave per 64 records
-    hipLaunchKernelGGL(names.unmapped || m.rep_timed ? (paired ? sam_write_kernel<true, true> : sam_write_kernel<false, true>)
-                                                     : (paired ? sam_write_kernel<true> : sam_write_kernel<false>), dim3(blocks), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL(TEXT_KERNEL(sam_write_kernel, paired, names.unmapped || m.filtered), dim3(blocks), dim3(256), 0, stream, p);
     TAIL_TRY(hipGetLastError());
   }
-  TAIL_TRY(hipEventRecord(m.ev[1], stream));
-  rc = m.send_home(m.text, (size_t)total, m.h_qual_at, m.qual_at, hole ? n_reads1 * 8 : 0, stream, wait, gate, wait ? ms : nullptr, err);
+  TAIL_TRY(m.span[kText].end(stream));
+  rc = m.send_home(m.text, (size_t)total, m.h_qual_at, m.qual_at, hole ? n_reads1 * 8 : 0, stream, wait, gate, err);
   if (rc) return rc;
   out->text = m.h_text, out->len = total, out->n_asserted = m.h_ctl[2];
   out->qual_at = hole ? m.h_qual_at : nullptr;
@@ -3039,7 +3088,7 @@ int Tail::sam(const TailInput &in, const SamInput &names, hipStream_t stream, in
 }
 
 int Tail::bam(const TailInput &in, const SamInput &names, int level, hipStream_t stream, int n_cu, BamOutput *out, std::string *err,
-              double *ms, bool wait, TextGate *gate, bool paired) {
+              float *bgzf_ms, bool wait, TextGate *gate, bool paired) {
   if (!impl_ || !out) return FEM_ERR_STATE;
   Impl &m = *impl_;
   if (!names.quals || names.qual_hole) {
@@ -3053,8 +3102,7 @@ int Tail::bam(const TailInput &in, const SamInput &names, int level, hipStream_t
   if (rc) return rc;
   const uint32_t n_bound = p.n_records;
   // the record offsets come home with the total: the member cuts are made here
-  TAIL_TRY(m.h_line_off.ensure((size_t)n_bound + 1));
-  TAIL_TRY(hipMemcpyAsync(m.h_line_off, m.line_off, ((size_t)n_bound + 1) * 8, hipMemcpyDeviceToHost, stream));
+  TAIL_TRY(copy_home(m.h_line_off, m.line_off, 0, (size_t)n_bound + 1, 0, stream));
   TAIL_TRY(hipMemcpyAsync(m.h_ctl + 3, bad_name, 4, hipMemcpyDeviceToHost, stream));
   TAIL_TRY(hipStreamSynchronize(stream));
   if (m.h_ctl[3]) {
@@ -3066,19 +3114,16 @@ int Tail::bam(const TailInput &in, const SamInput &names, int level, hipStream_t
   TAIL_TRY(m.text.ensure(std::max<size_t>((size_t)total, 16)));
   if (nr) {
     p.text = m.text;
-    hipLaunchKernelGGL(names.unmapped || m.rep_timed ? (paired ? bam_write_kernel<true, true> : bam_write_kernel<false, true>)
-                                                     : (paired ? bam_write_kernel<true> : bam_write_kernel<false>), dim3((nr + 3u) / 4u), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL(TEXT_KERNEL(bam_write_kernel, paired, names.unmapped || m.filtered), dim3((nr + 3u) / 4u), dim3(256), 0, stream, p);
     TAIL_TRY(hipGetLastError());
   }
-  TAIL_TRY(hipEventRecord(m.ev[1], stream));
+  TAIL_TRY(m.span[kText].end(stream));
   femz::bgzf_cut(m.h_line_off, nr, total, &m.cuts);
   uint64_t len = 0;
-  float ms_z = 0.f;
-  if ((rc = m.bgzf.compress(m.text, total, m.cuts, level, stream, &len, err, ms ? &ms_z : nullptr))) return rc;
+  // (compress() waits for the stream: the stage is over when the text sets out)
+  if ((rc = m.bgzf.compress(m.text, total, m.cuts, level, stream, &len, err, bgzf_ms))) return rc;
   TAIL_TRY(m.h_text.ensure(std::max<size_t>((size_t)len, 1u << 20)));
-  // (compress() has waited for the stream: both spans are over)
-  if ((rc = m.send_home(m.bgzf.out(), (size_t)len, nullptr, nullptr, 0, stream, wait, gate, ms, err))) return rc;
-  if (ms) ms[1] += ms_z;
+  if ((rc = m.send_home(m.bgzf.out(), (size_t)len, nullptr, nullptr, 0, stream, wait, gate, err))) return rc;
   out->data = (uint8_t *)m.h_text.get(), out->len = len, out->raw_len = total;
   out->n_blocks = m.cuts.empty() ? 0 : m.cuts.size() - 1;
   out->n_asserted = m.h_ctl[2];
@@ -3093,11 +3138,11 @@ int Tail::pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::
     if (err) *err = "a paired batch holds an even number of reads";
     return FEM_ERR_INVALID;
   }
-  m.n_resc = 0, m.resc_timed = false, m.pair_mapq = false;
+  m.n_resc = 0, m.pair_mapq = false;
+  m.not_run({kRescue, kPairing});
   const uint32_t *resc_before = nullptr;
   if (rescue && np) {  // ---- mate rescue: the kept records behind run()'s, resc_before their exclusive scan over the pairs ----
     const int32_t E = rescue->max_edits;
-    for (femb::Event &e : m.ev_resc) TAIL_TRY(e.create());
     TAIL_TRY(m.r_ctl.ensure(4));
     TAIL_TRY(m.h_r_ctl.ensure(4));
     TAIL_TRY(m.r_cand.ensure((size_t)np));
@@ -3111,13 +3156,8 @@ int Tail::pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::
     r.ctl = m.r_ctl, r.cand_pair = m.r_cand, r.jobs = m.r_jobs;
     r.best = m.r_best;
     r.cig_total = h_tot[4], r.md_total = h_tot[5];
-    auto bind_records = [&]() {
-      r.rec_begin = m.rec_begin, r.flag = m.flag, r.tid = m.tid, r.pos0 = m.pos0;
-      r.nm = m.nm, r.cigar_off = m.cigar_off, r.cigar = m.cigar;
-      r.md_off = m.md_off, r.md = m.md, r.s_read = m.s_read;
-    };
-    bind_records();
-    TAIL_TRY(hipEventRecord(m.ev_resc[0], stream));
+    m.bind_records(&r);
+    TAIL_TRY(m.span[kRescue].begin(stream));
     TAIL_TRY(hipMemsetAsync(m.r_ctl, 0, 16, stream));
     hipLaunchKernelGGL(rescue_jobs_kernel, dim3((np + 255u) / 256u), dim3(256), 0, stream, r);
     TAIL_TRY(hipGetLastError());
@@ -3129,8 +3169,12 @@ int Tail::pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::
       // first pass: the staging of a walk of E errors on canonical characters (<= 2E + 2 runs; MD <= 2E + 1 numbers of <= 4
       // digits and 3E characters); overflow pass: the longest walk, as trace_kernel's (every column an MD character)
       r.max_len = std::max<uint32_t>(rescue->max_len, 1);
+      TracePlan plan;  // (trace_kernel's, at E)
+      if (int rc = trace_plan(r.max_len, E, &plan, err)) return rc;
+      const OverflowCaps o_cap = overflow_caps(r.max_len, E);
+      r.text_words = plan.text_words, r.pat_words = plan.pat_words, r.lanes = plan.lanes;
       r.ops_cap = 2u * (uint32_t)E + 8u, r.md_cap = 8u * (uint32_t)E + 64u;
-      r.o_ops_cap = 2u * r.max_len + 2u * (uint32_t)E + 8u, r.o_md_cap = 8u * r.max_len + 128u;
+      r.o_ops_cap = o_cap.ops, r.o_md_cap = o_cap.md;
       const size_t rec_cap = (size_t)nr + n_cand + 1;
       TAIL_TRY(m.flag.ensure_keep(rec_cap, (size_t)nr, stream));
       TAIL_TRY(m.tid.ensure_keep(rec_cap, (size_t)nr, stream));
@@ -3139,7 +3183,7 @@ int Tail::pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::
       TAIL_TRY(m.s_read.ensure_keep(rec_cap, (size_t)nr, stream));
       TAIL_TRY(m.cigar_off.ensure_keep(rec_cap, (size_t)nr + 1, stream));
       TAIL_TRY(m.md_off.ensure_keep(rec_cap, (size_t)nr + 1, stream));
-      bind_records();
+      m.bind_records(&r);
       TAIL_TRY(m.r_ops.ensure((size_t)n_cand * r.ops_cap));
       TAIL_TRY(m.r_md.ensure((size_t)n_cand * r.md_cap));
       TAIL_TRY(m.r_rec.ensure((size_t)n_cand * kRescRec));
@@ -3157,17 +3201,9 @@ int Tail::pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::
         hipLaunchKernelGGL(rescue_search_kernel, dim3(blocks), dim3(64 * kResWaves), 0, stream, r);
         TAIL_TRY(hipGetLastError());
       }
-      // the trace kernel's LDS plan (trace_kernel's, at E)
-      r.text_words = (r.max_len + 3) / 4 + 4, r.pat_words = (r.max_len + 2 * (uint32_t)E + 3) / 4 + 4;
-      const uint32_t words_per_lane = r.text_words + r.pat_words + 2 * r.max_len;
-      r.lanes = std::min<uint32_t>(64, (64u * 1024u / 4u) / words_per_lane);
-      if (r.lanes == 0) {
-        if (err) *err = "read too long for the device traceback";
-        return FEM_ERR_UNSUPPORTED;
-      }
       const uint32_t t_blocks = std::min<uint32_t>((n_cand + r.lanes - 1u) / r.lanes, 16384u);
       r.overflow_pass = 0;
-      hipLaunchKernelGGL(rescue_trace_kernel, dim3(t_blocks), dim3(64), r.lanes * words_per_lane * 4u, stream, r);
+      hipLaunchKernelGGL(rescue_trace_kernel, dim3(t_blocks), dim3(64), plan.lds_bytes, stream, r);
       TAIL_TRY(hipGetLastError());
       TAIL_TRY(hipMemcpyAsync(h_rc + 2, m.r_ctl + 2, 4, hipMemcpyDeviceToHost, stream));
       TAIL_TRY(hipStreamSynchronize(stream));
@@ -3177,23 +3213,14 @@ int Tail::pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::
         TAIL_TRY(m.r_o_md.ensure((size_t)n_ovf * r.o_md_cap));
         r.o_ops = m.r_o_ops, r.o_md = m.r_o_md, r.overflow_pass = 1;
         const uint32_t o_blocks = std::min<uint32_t>((n_ovf + r.lanes - 1u) / r.lanes, 16384u);
-        hipLaunchKernelGGL(rescue_trace_kernel, dim3(o_blocks), dim3(64), r.lanes * words_per_lane * 4u, stream, r);
+        hipLaunchKernelGGL(rescue_trace_kernel, dim3(o_blocks), dim3(64), plan.lds_bytes, stream, r);
         TAIL_TRY(hipGetLastError());
       }
       // the kept records' CIGAR runs and MD characters fit what their stagings can hold
       TAIL_TRY(m.cigar.ensure_keep((size_t)r.cig_total + (size_t)n_cand * r.ops_cap + (size_t)n_ovf * r.o_ops_cap, (size_t)r.cig_total, stream));
       TAIL_TRY(m.md.ensure_keep((size_t)r.md_total + (size_t)n_cand * r.md_cap + (size_t)n_ovf * r.o_md_cap, r.md_total, stream));
-      bind_records();
-      {
-        auto lens = rocprim::make_zip_iterator(rocprim::make_tuple(r.kept, r.k_ops, r.k_md));
-        auto offs = rocprim::make_zip_iterator(rocprim::make_tuple(m.r_scan.get(), m.r_scan.get() + p1,
-                                                                   m.r_scan + 2 * p1));
-        size_t tmp = 0;
-        TAIL_TRY(rocprim::exclusive_scan(nullptr, tmp, lens, offs, rocprim::make_tuple(0u, 0u, 0u), p1, TriplePlus(), stream));
-        TAIL_TRY(m.r_scan_tmp.ensure(std::max<size_t>(tmp, 16)));
-        tmp = m.r_scan_tmp.bytes();
-        TAIL_TRY(rocprim::exclusive_scan(m.r_scan_tmp.get(), tmp, lens, offs, rocprim::make_tuple(0u, 0u, 0u), p1, TriplePlus(), stream));
-      }
+      m.bind_records(&r);
+      TAIL_TRY(m.scan_kept(p1, stream));
       hipLaunchKernelGGL(rescue_append_kernel, dim3((n_cand + 255u) / 256u), dim3(256), 0, stream, r);
       TAIL_TRY(hipGetLastError());
       TAIL_TRY(hipMemcpyAsync(h_rc, m.r_scan + np, 4, hipMemcpyDeviceToHost, stream));
@@ -3206,8 +3233,7 @@ int Tail::pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::
       m.n_resc = h_rc[0];
       if (m.n_resc) resc_before = m.r_scan;
     }
-    TAIL_TRY(hipEventRecord(m.ev_resc[1], stream));
-    m.resc_timed = true;
+    TAIL_TRY(m.span[kRescue].end(stream));
   }
   const size_t lines = std::max<size_t>((size_t)nr + m.n_resc, 1);
   TAIL_TRY(m.perm.ensure(lines));
@@ -3219,14 +3245,12 @@ int Tail::pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::
   TAIL_TRY(m.pair_begin.ensure((size_t)n + 1));
   TAIL_TRY(m.pair_ctl.ensure(4));
   TAIL_TRY(m.h_pair_ctl.ensure(4));
-  for (femb::Event &e : m.ev_pair) TAIL_TRY(e.create());
-  TAIL_TRY(hipEventRecord(m.ev_pair[0], stream));
+  TAIL_TRY(m.span[kPairing].begin(stream));
   TAIL_TRY(hipMemsetAsync(m.pair_ctl, 0, 16, stream));
   if (np) {
     PairParams q{};
     q.n_pairs = np, q.min_insert = min_insert, q.max_insert = max_insert;
-    q.rec_begin = m.rec_begin, q.flag = m.flag, q.tid = m.tid, q.pos0 = m.pos0;
-    q.nm = m.nm, q.cigar_off = m.cigar_off, q.cigar = m.cigar;
+    m.bind_pairing(&q);
     q.perm = m.perm, q.pflag = m.pflag, q.mtid = m.mtid, q.mpos0 = m.mpos0;
     q.tlen = m.tlen, q.pair_begin = m.pair_begin, q.n_proper = m.pair_ctl;
     q.resc_before = resc_before, q.resc_first = nr;
@@ -3236,92 +3260,41 @@ int Tail::pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::
   } else {
     TAIL_TRY(hipMemsetAsync(m.pair_begin, 0, 4, stream));
   }
-  TAIL_TRY(hipEventRecord(m.ev_pair[1], stream));
+  TAIL_TRY(m.span[kPairing].end(stream));
   TAIL_TRY(hipMemcpyAsync(m.h_pair_ctl, m.pair_ctl, 4, hipMemcpyDeviceToHost, stream));
   m.paired = true, m.pair_mapq = mapq;
   return FEM_OK;
 }
 
 uint64_t Tail::n_rescued() const { return impl_ && impl_->paired ? impl_->n_resc : 0; }
-
-float Tail::rescue_ms() const {
-  float t = 0.f;
-  if (!impl_ || !impl_->paired || !impl_->resc_timed || hipEventElapsedTime(&t, impl_->ev_resc[0], impl_->ev_resc[1]) != hipSuccess) return 0.f;
-  return t;
-}
-
 uint64_t Tail::n_unmapped() const { return impl_ ? impl_->n_unm : 0; }
-
-float Tail::unmapped_ms() const {
-  float t = 0.f;
-  if (!impl_ || !impl_->unm_timed || hipEventElapsedTime(&t, impl_->ev_unm[0], impl_->ev_unm[1]) != hipSuccess) return 0.f;
-  return t;
-}
-
 uint64_t Tail::n_filtered() const { return impl_ ? impl_->n_filtered : 0; }
-
-float Tail::report_ms() const {
-  float t = 0.f;
-  if (!impl_ || !impl_->rep_timed || hipEventElapsedTime(&t, impl_->ev_rep[0], impl_->ev_rep[1]) != hipSuccess) return 0.f;
-  return t;
-}
-
-float Tail::mapq_ms() const {
-  float t = 0.f;
-  if (!impl_ || !impl_->mapq_timed || hipEventElapsedTime(&t, impl_->ev_mapq[0], impl_->ev_mapq[1]) != hipSuccess) return 0.f;
-  return t;
-}
-
 uint64_t Tail::n_proper() const { return impl_ && impl_->paired && impl_->h_pair_ctl ? impl_->h_pair_ctl[0] : 0; }
-
-float Tail::pair_ms() const {
-  float t = 0.f;
-  if (!impl_ || !impl_->paired || hipEventElapsedTime(&t, impl_->ev_pair[0], impl_->ev_pair[1]) != hipSuccess) return 0.f;
-  return t;
-}
 
 int Tail::pair_fetch(hipStream_t stream, PairOutput *out, std::string *err) {
   if (!impl_ || !impl_->paired || !out) return FEM_ERR_STATE;
   Impl &m = *impl_;
   const uint32_t n = m.last_n, nr = m.last_nr + m.n_resc;  // (lines)
-  const size_t lines = std::max<size_t>(nr, 1);
-  TAIL_TRY(m.h_perm.ensure(lines));
-  TAIL_TRY(m.h_pflag.ensure(lines));
-  TAIL_TRY(m.h_mtid.ensure(lines));
-  TAIL_TRY(m.h_mpos0.ensure(lines));
-  TAIL_TRY(m.h_tlen.ensure(lines));
-  TAIL_TRY(m.h_pair_begin.ensure((size_t)n + 1));
-  if (nr) {
-    TAIL_TRY(hipMemcpyAsync(m.h_perm, m.perm, (size_t)nr * 4, hipMemcpyDeviceToHost, stream));
-    TAIL_TRY(hipMemcpyAsync(m.h_pflag, m.pflag, (size_t)nr * 2, hipMemcpyDeviceToHost, stream));
-    TAIL_TRY(hipMemcpyAsync(m.h_mtid, m.mtid, (size_t)nr * 4, hipMemcpyDeviceToHost, stream));
-    TAIL_TRY(hipMemcpyAsync(m.h_mpos0, m.mpos0, (size_t)nr * 4, hipMemcpyDeviceToHost, stream));
-    TAIL_TRY(hipMemcpyAsync(m.h_tlen, m.tlen, (size_t)nr * 4, hipMemcpyDeviceToHost, stream));
-  }
-  TAIL_TRY(hipMemcpyAsync(m.h_pair_begin, m.pair_begin, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost, stream));
+  TAIL_TRY(copy_home(m.h_perm, m.perm, 0, nr, 1, stream));
+  TAIL_TRY(copy_home(m.h_pflag, m.pflag, 0, nr, 1, stream));
+  TAIL_TRY(copy_home(m.h_mtid, m.mtid, 0, nr, 1, stream));
+  TAIL_TRY(copy_home(m.h_mpos0, m.mpos0, 0, nr, 1, stream));
+  TAIL_TRY(copy_home(m.h_tlen, m.tlen, 0, nr, 1, stream));
+  TAIL_TRY(copy_home(m.h_pair_begin, m.pair_begin, 0, (size_t)n + 1, 0, stream));
   // the rescued records (records last_nr .. last_nr + n_resc - 1), their offsets as they stand (from run()'s totals on)
   const uint32_t k = m.n_resc, first = m.last_nr;
-  TAIL_TRY(m.h_r_flag.ensure(std::max<size_t>(k, 1)));
-  TAIL_TRY(m.h_r_tid.ensure(std::max<size_t>(k, 1)));
-  TAIL_TRY(m.h_r_pos0.ensure(std::max<size_t>(k, 1)));
-  TAIL_TRY(m.h_r_nm.ensure(std::max<size_t>(k, 1)));
-  TAIL_TRY(m.h_r_cigar_off.ensure((size_t)k + 1));
-  TAIL_TRY(m.h_r_md_off.ensure((size_t)k + 1));
-  if (k) {
-    TAIL_TRY(hipMemcpyAsync(m.h_r_flag, m.flag + first, (size_t)k * 2, hipMemcpyDeviceToHost, stream));
-    TAIL_TRY(hipMemcpyAsync(m.h_r_tid, m.tid + first, (size_t)k * 4, hipMemcpyDeviceToHost, stream));
-    TAIL_TRY(hipMemcpyAsync(m.h_r_pos0, m.pos0 + first, (size_t)k * 4, hipMemcpyDeviceToHost, stream));
-    TAIL_TRY(hipMemcpyAsync(m.h_r_nm, m.nm + first, k, hipMemcpyDeviceToHost, stream));
-    TAIL_TRY(hipMemcpyAsync(m.h_r_cigar_off, m.cigar_off + first, ((size_t)k + 1) * 4, hipMemcpyDeviceToHost, stream));
-    TAIL_TRY(hipMemcpyAsync(m.h_r_md_off, m.md_off + first, ((size_t)k + 1) * 4, hipMemcpyDeviceToHost, stream));
-  }
+  const size_t k1 = k ? (size_t)k + 1 : 0;
+  TAIL_TRY(copy_home(m.h_r_flag, m.flag, first, k, 1, stream));
+  TAIL_TRY(copy_home(m.h_r_tid, m.tid, first, k, 1, stream));
+  TAIL_TRY(copy_home(m.h_r_pos0, m.pos0, first, k, 1, stream));
+  TAIL_TRY(copy_home(m.h_r_nm, m.nm, first, k, 1, stream));
+  TAIL_TRY(copy_home(m.h_r_cigar_off, m.cigar_off, first, k1, 1, stream));
+  TAIL_TRY(copy_home(m.h_r_md_off, m.md_off, first, k1, 1, stream));
   TAIL_TRY(hipStreamSynchronize(stream));
   const uint32_t *co = m.h_r_cigar_off, *mo = m.h_r_md_off;
   const size_t n_cig = k ? co[k] - co[0] : 0, n_md = k ? mo[k] - mo[0] : 0;
-  TAIL_TRY(m.h_r_cigar.ensure(std::max<size_t>(n_cig, 1)));
-  TAIL_TRY(m.h_r_md.ensure(std::max<size_t>(n_md, 1)));
-  if (n_cig) TAIL_TRY(hipMemcpyAsync(m.h_r_cigar, m.cigar + co[0], n_cig * 4, hipMemcpyDeviceToHost, stream));
-  if (n_md) TAIL_TRY(hipMemcpyAsync(m.h_r_md, m.md + mo[0], n_md, hipMemcpyDeviceToHost, stream));
+  TAIL_TRY(copy_home(m.h_r_cigar, m.cigar, k ? co[0] : 0, n_cig, 1, stream));
+  TAIL_TRY(copy_home(m.h_r_md, m.md, k ? mo[0] : 0, n_md, 1, stream));
   if (n_cig || n_md) TAIL_TRY(hipStreamSynchronize(stream));
   out->n_pairs = n / 2u, out->n_records = nr, out->n_proper = m.h_pair_ctl[0];
   out->pair_begin = m.h_pair_begin, out->perm = m.h_perm, out->flag = m.h_pflag;
@@ -3332,5 +3305,7 @@ int Tail::pair_fetch(hipStream_t stream, PairOutput *out, std::string *err) {
   out->r_md_off = mo, out->r_md = m.h_r_md;
   return FEM_OK;
 }
+
+#undef TEXT_KERNEL
 
 }  // namespace femt

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <memory>
 #include <string>
 
 namespace femt {
@@ -123,17 +124,22 @@ struct TextGate {
   hipEvent_t last = nullptr;  // the latest text's arrival (an event of some slot's Tail; never destroyed before the handle's tails are)
 };
 
+// The timed stages of a batch's way out of the device.  Each runs between two events on its stream, recorded whether or not
+// anybody asks (Tail::stage_ms).  run(): kOrder, kTrace, kCompact.  pair(): kRescue when it rescues, kPairing.  sam() / bam():
+// kMapq with SamInput::mapq; kFilterIndex, the line index with the line filter, or else kUnmappedIndex, the one with
+// SamInput::unmapped alone; kText, the SAM text's or the BAM records' kernels.
+enum Stage { kOrder, kTrace, kCompact, kText, kPairing, kRescue, kMapq, kUnmappedIndex, kFilterIndex, kStages };
+
 class Tail {
  public:
-  Tail() = default;
+  Tail();
   ~Tail();
   Tail(const Tail &) = delete;
   Tail &operator=(const Tail &) = delete;
-  // Runs on `stream` and waits for it.  ms[0..2] (optional) receive the device time of: ordering, traceback, compaction.
+  // Runs on `stream` and waits for it.
   // tiny = test hook: per-record CIGAR/MD staging starts far too small so that the overflow pass runs.
   // copy_records = false: the records stay on the device (for sam()); *out then only carries the counts.
-  int run(const TailInput &in, hipStream_t stream, int n_cu, bool tiny, TailOutput *out, std::string *err, double *ms,
-          bool copy_records = true);
+  int run(const TailInput &in, hipStream_t stream, int n_cu, bool tiny, TailOutput *out, std::string *err, bool copy_records = true);
   // Makes room for `bytes` of SAM text ahead of time (pinning host memory costs ~0.25 ms per MB: better spent before
   // the first batch than inside it).
   int reserve_text(uint64_t bytes, std::string *err);
@@ -141,17 +147,17 @@ class Tail {
   int reserve(uint32_t n_reads, uint32_t n_records, uint32_t max_len, int e, bool tiny, std::string *err);
   // ... and loads the kernels (a code object is loaded by its first launch otherwise) and wakes `stream`.
   int warm(hipStream_t stream, std::string *err);
-  // The records of the last run() as SAM lines, in record order.  ms (optional) receives the device time.
+  // The records of the last run() as SAM lines, in record order.
   // wait = false: returns once the copy of the text to the host has been queued; wait_text() (which may be called from
   // another thread) returns when it has arrived.
   // paired = true: the lines in the order of the last pair() with its mate columns (the records of both stay on the device).
-  int sam(const TailInput &in, const SamInput &names, hipStream_t stream, int n_cu, SamOutput *out, std::string *err, double *ms,
-          bool wait = true, TextGate *gate = nullptr, bool paired = false);
+  int sam(const TailInput &in, const SamInput &names, hipStream_t stream, int n_cu, SamOutput *out, std::string *err, bool wait = true,
+          TextGate *gate = nullptr, bool paired = false);
   // The same lines as BAM records (names.quals must be set: no qual_hole), compressed at `level` (0 or 1) into BGZF members.
-  // ms (optional): ms[0] += the record kernels' device time, ms[1] += the BGZF kernels'.  wait, gate, paired: as sam().
+  // bgzf_ms (optional) receives the BGZF kernels' device time (the record kernels' is stage kText's).  wait, gate, paired: as sam().
   // FEM_ERR_UNSUPPORTED for a read name over 254 characters.
   int bam(const TailInput &in, const SamInput &names, int level, hipStream_t stream, int n_cu, BamOutput *out, std::string *err,
-          double *ms, bool wait = true, TextGate *gate = nullptr, bool paired = false);
+          float *bgzf_ms, bool wait = true, TextGate *gate = nullptr, bool paired = false);
   // Pairs the records of the last run() (pair_kernel): output order, FLAG, mate columns and TLEN of every line, the proper-pair
   // count.  Asynchronous on `stream`; n_proper() is valid once the stream has been synchronised (sam() does).
   // rescue (optional): mate rescue first (the rescue kernels), the kept rescued records appended behind run()'s; pair() then
@@ -161,21 +167,20 @@ class Tail {
   int pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::string *err, const RescueInput *rescue = nullptr,
            bool mapq = false);
   uint64_t n_proper() const;
-  uint64_t n_rescued() const;  // kept rescued records of the last pair() (0 without rescue)
-  float pair_ms() const;  // device time of the last pair(), once its stream has been synchronised (timing: 0 otherwise)
-  float rescue_ms() const;  // ... and of its rescue kernels
-  float mapq_ms() const;  // device time of the last sam() / bam()'s MAPQ kernel (0 without SamInput::mapq)
+  uint64_t n_rescued() const;   // kept rescued records of the last pair() (0 without rescue)
   uint64_t n_unmapped() const;  // lines for unmapped reads in the last sam() / bam() (0 without SamInput::unmapped)
-  float unmapped_ms() const;    // ... and the device time of its line index kernels
   uint64_t n_filtered() const;  // lines the filter left out of the last sam() / bam() (0 without SamInput::strata / max_hits)
-  float report_ms() const;      // ... and the device time of its line index kernels (which are the unmapped reads' too then)
+  // The device time of a stage, in ms.  Negative: the stage was not part of the last run() and of what followed it (pair(),
+  // sam() or bam()), or its stream has not yet passed its end (a text that was not waited for).
+  float stage_ms(Stage stage) const;
   // The arrays of the last pair() to the host (waits for `stream`).
   int pair_fetch(hipStream_t stream, PairOutput *out, std::string *err);
   int wait_text();
 
  private:
   struct Impl;
-  Impl *impl_ = nullptr;
+  std::unique_ptr<Impl> impl_;
+  int impl(Impl **m);  // the state, made on first use; FEM_ERR_NOMEM
 };
 
 }  // namespace femt

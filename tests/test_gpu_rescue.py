@@ -280,10 +280,10 @@ def test_fetch_timing_counts():
         dev.set_timing(True)
 
         def advanced(fetch):
-            before = [dev.kernel_time(k)[1] for k in range(13)]
+            before = [dev.kernel_time(k)[1] for k in range(16)]
             fetch()
-            after = [dev.kernel_time(k)[1] for k in range(13)]
-            return {k: after[k] - before[k] for k in range(13) if after[k] != before[k]}
+            after = [dev.kernel_time(k)[1] for k in range(16)]
+            return {k: after[k] - before[k] for k in range(16) if after[k] != before[k]}
 
         for slot, paired, rescue in ((0, False, False), (1, True, True), (2, True, False)):
             dev.stage_reads(batch.bases, batch.off, slot=slot)
@@ -295,5 +295,39 @@ def test_fetch_timing_counts():
             assert advanced(lambda: dev.fetch_sam(slot=slot)) == dict.fromkeys(text_ids | {7}, 1)
             assert advanced(lambda: dev.fetch_sam(slot=slot, nowait=True)) == dict.fromkeys(text_ids, 1)
             assert advanced(lambda: dev.fetch_bam(slot=slot)) == dict.fromkeys(text_ids | {11, 12}, 1)
+    finally:
+        dev.close()
+
+
+def test_fetch_timing_counts_with_every_stage():
+    """A paired slot with rescue, MAPQ and lines for unmapped reads, over all sixteen ids: with the line filter a waiting
+    fetch_sam counts 3-5, 7, 9, 10, 13 and 15 (the filter's line index is the unmapped reads' too: no 14); without the
+    filter a fetch_bam that does not wait counts 3-5, 9-14."""
+    rng, dev, ref, idx, seqs, names = _setup(28, False)
+    try:
+        n, e = 150, 2
+        r1, r2 = make_rescue_pairs(rng, seqs, n, 100, 100, e, 8, 500)
+        batch = fo.ReadBatch(r1 + r2)
+        q = np.full(len(batch.bases), ord("I"), np.uint8)
+        dev.set_pairs(0, 500, slot=1)
+        dev.set_rescue(8, slot=1)
+        dev.set_mapq(True, slot=1)
+        dev.set_unmapped(True, slot=1)
+        dev.set_timing(True)
+        dev.stage_reads(batch.bases, batch.off, slot=1)
+        dev.stage_text(q, ["r%d" % i for i in range(2 * n)], slot=1)
+        dev.map_staged(e=e, slot=1)
+        dev.sync(1)
+
+        def advanced(fetch):
+            before = [dev.kernel_time(k)[1] for k in range(16)]
+            fetch()
+            after = [dev.kernel_time(k)[1] for k in range(16)]
+            return {k: after[k] - before[k] for k in range(16) if after[k] != before[k]}
+
+        dev.set_report(strata=0, slot=1)
+        assert advanced(lambda: dev.fetch_sam(slot=1)) == dict.fromkeys({3, 4, 5, 7, 9, 10, 13, 15}, 1)
+        dev.set_report(slot=1)
+        assert advanced(lambda: dev.fetch_bam(slot=1, nowait=True)) == dict.fromkeys({3, 4, 5, 9, 10, 11, 12, 13, 14}, 1)
     finally:
         dev.close()
