@@ -170,6 +170,8 @@ struct Slot {
   bool rescue = false;
   int32_t rescue_edits = 0;
   uint64_t n_rescued = 0;  // of the slot's last paired SAM text (or fetch_pairs)
+  bool rescue_discordant = false;      // fem_dev_set_rescue_discordant: pairs whose records do not pair are rescued too
+  uint64_t n_rescued_discordant = 0;   // ... and how many of the rescued records are theirs
   bool mapq = false;  // fem_dev_set_mapq: MAPQ from the hit strata in the slot's SAM text and BAM records
   bool unmapped = false;  // fem_dev_set_unmapped: a line for every read without a mapping in the slot's SAM text and BAM records
   uint64_t n_unmapped = 0;  // ... and how many the slot's last text or BAM had
@@ -2088,7 +2090,7 @@ static int rescue_input(fem_dev *h, const Slot &s, femt::RescueInput *ri) {
   if (!s.rescue) return FEM_OK;
   if ((int64_t)s.max_insert - s.min_insert > 65536)
     return fail(h, FEM_ERR_UNSUPPORTED, "mate rescue searches insert windows of at most 65536 (max_insert - min_insert)");
-  ri->max_edits = s.rescue_edits;
+  ri->max_edits = s.rescue_edits, ri->discordant = s.rescue_discordant;
   ri->bases = s.bases(), ri->read_off = s.d_off, ri->max_len = s.max_len;
   ri->ref_raw = h->d_ref_raw, ri->ref_bytes = h->ref_bytes + 64, ri->seq_off = h->d_seq_off, ri->seq_len = h->d_seq_len;
   return FEM_OK;
@@ -2193,6 +2195,7 @@ static int text_done(fem_dev *h, int slot, const TailFront &f, const char *tag, 
   Slot &s = h->slot[slot];
   s.n_proper = s.paired ? s.tail->n_proper() : 0;  // (sam() and bam() have waited for the stream once, after sizing the text)
   s.n_rescued = s.paired ? s.tail->n_rescued() : 0;
+  s.n_rescued_discordant = s.paired ? s.tail->n_rescued_discordant() : 0;
   s.n_unmapped = s.tail->n_unmapped();
   s.n_filtered = s.tail->n_filtered();
   HIP_TRY(h, s.ev_text_order.create(hipEventDisableTiming));
@@ -2326,6 +2329,25 @@ int fem_dev_set_rescue(fem_dev *h, int slot, const fem_rescue_params *rp) {
   return FEM_OK;
 }
 
+int fem_dev_set_rescue_discordant(fem_dev *h, int slot, int on) {
+  int rc = check_slot(h, slot);
+  if (rc) return rc;
+  FEM_LOCK(h);
+  h->slot[slot].rescue_discordant = on != 0;
+  return FEM_OK;
+}
+
+int fem_dev_rescue_discordant_count(fem_dev *h, int slot, uint64_t *n) {
+  int rc = check_slot(h, slot);
+  if (rc) return rc;
+  if (!n) return fail(h, FEM_ERR_INVALID, "null output pointer");
+  FEM_LOCK(h);
+  Slot &s = h->slot[slot];
+  if (!s.paired) return fail(h, FEM_ERR_STATE, "the slot is not in pair mode (fem_dev_set_pairs)");
+  *n = s.n_rescued_discordant;
+  return FEM_OK;
+}
+
 int fem_dev_set_mapq(fem_dev *h, int slot, int on) {
   int rc = check_slot(h, slot);
   if (rc) return rc;
@@ -2444,7 +2466,7 @@ int fem_dev_fetch_pairs(fem_dev *h, int slot, fem_batch_pairs *out) {
     }
     s.pr_cigar_off[k + 1] = (uint32_t)s.pr_cigar.size(), s.pr_md_off[k + 1] = (uint32_t)s.pr_md.size();
   }
-  s.n_proper = po.n_proper, s.n_rescued = po.n_rescued;
+  s.n_proper = po.n_proper, s.n_rescued = po.n_rescued, s.n_rescued_discordant = s.tail->n_rescued_discordant();
   out->n_pairs = po.n_pairs, out->n_records = nr;
   out->rec_begin = po.pair_begin, out->flag = s.pr_flag.data(), out->tid = s.pr_tid.data(), out->pos0 = s.pr_pos0.data();
   out->nm = s.pr_nm.data(), out->cigar_off = s.pr_cigar_off.data(), out->cigar = s.pr_cigar.data();

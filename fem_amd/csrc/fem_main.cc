@@ -6,7 +6,7 @@
 // next batch; record order in the SAM file follows completion, parity is modulo record order); `--batch N` sets reads
 // per batch.  `--read2 STR` maps read pairs (record i of --read1 and of --read2 are the two mates of pair i), with -I / -X the
 // accepted insert size: the pairing and the paired SAM text on the device (fem_dev_set_pairs); `--rescue INT` adds mate rescue
-// at INT edits (fem_dev_set_rescue).  `--mapq` writes mapping qualities made on the device (fem_dev_set_mapq) instead of 255.
+// at INT edits (fem_dev_set_rescue), `--rescue-discordant` also for pairs whose records do not pair (fem_dev_set_rescue_discordant).  `--mapq` writes mapping qualities made on the device (fem_dev_set_mapq) instead of 255.
 // `--unmapped` adds a line for every read without a mapping, made on the device (fem_dev_set_unmapped).
 // `--strata INT` / `--max-hits INT` leave out the lines of a read beyond its best strata / its first INT (fem_dev_set_report).
 // `--header` puts @HD in front of the @SQ lines and @PG behind them; `--rg LINE` adds the @RG line and RG:Z on every line, `--nh`
@@ -78,6 +78,7 @@ void usage_map() {
   fprintf(stderr, "        -I, --minins INT  minimum insert size of a proper pair [0]\n");
   fprintf(stderr, "        -X, --maxins INT  maximum insert size of a proper pair [500]\n");
   fprintf(stderr, "        --rescue INT  with --read2: search a mate without records in its mate's insert window at INT (0-15) edits\n");
+  fprintf(stderr, "        --rescue-discordant  with --rescue: also search the mates of a pair whose records do not pair\n");
   fprintf(stderr, "        --bam[=INT]   write BAM instead of SAM: BGZF level 1 (default) or 0 (uncompressed)\n");
   fprintf(stderr, "        --mapq        write mapping qualities (0-60) from the hits' edit distances instead of 255\n");
   fprintf(stderr, "        --unmapped    write a line for every read without a mapping too (FLAG 0x4; a mate placed at its mapped mate)\n");
@@ -263,6 +264,7 @@ struct BatchBuf {  // everything about the batch that sits in one (GPU, slot) pa
   fem_batch_records rec{};                  // device tail's records (default path)
   uint64_t n_proper = 0;                    // paired: proper pairs of the batch
   uint64_t n_rescued = 0;                   // --rescue: rescued mates of the batch
+  uint64_t n_rescued_discordant = 0;        // --rescue-discordant: those of pairs whose records did not pair
   uint64_t n_unmapped = 0;                  // --unmapped: lines for unmapped reads of the batch
   uint64_t n_filtered = 0;                  // --strata / --max-hits: lines left out of the batch's text
   fem_batch_result res{};                   // per-candidate outcome (FEM_HOST_TAIL=1)
@@ -292,6 +294,7 @@ int map_main(int argc, char **argv) {
   long long min_insert = 0, max_insert = 500;
   long long rescue_edits = 0;  // --rescue (mate rescue at this many edits, fem_dev_set_rescue)
   bool rescue_given = false;
+  bool rescue_discordant = false;  // --rescue-discordant (fem_dev_set_rescue_discordant)
   int bam_level = -1;  // --bam[=LEVEL]: BAM records and BGZF members made on the device (fem_dev_fetch_bam); -1: SAM
   bool unmapped = false;  // --unmapped: a line for every read without a mapping, made on the device (fem_dev_set_unmapped)
   long long strata = -1, max_hits = -1;  // --strata / --max-hits: the line filter, made on the device (fem_dev_set_report); -1: off
@@ -313,6 +316,7 @@ int map_main(int argc, char **argv) {
                                      {"gpus", required_argument, nullptr, 'G'},  {"batch", required_argument, nullptr, 'B'},
                                      {"read2", required_argument, nullptr, 'c'}, {"minins", required_argument, nullptr, 'I'},
                                      {"maxins", required_argument, nullptr, 'X'}, {"rescue", required_argument, nullptr, 'R'},
+                                     {"rescue-discordant", no_argument, nullptr, 'D'},
                                      {"bam", optional_argument, nullptr, 'Z'},  {"mapq", no_argument, nullptr, 'Q'},
                                      {"unmapped", no_argument, nullptr, 'U'},
                                      {"strata", required_argument, nullptr, 'S'}, {"max-hits", required_argument, nullptr, 'N'},
@@ -341,6 +345,7 @@ int map_main(int argc, char **argv) {
       case 'Z':
         bam_level = !optarg ? 1 : strcmp(optarg, "0") == 0 ? 0 : strcmp(optarg, "1") == 0 ? 1 : -2;  // (-2: refused below)
         break;
+      case 'D': rescue_discordant = true; break;
       case 'Q': mapq = true; break;
       case 'U': unmapped = true; break;
       case 'S': {
@@ -389,6 +394,7 @@ int map_main(int argc, char **argv) {
   else if (n_threads <= 0) bad = "Wrong number of threads.";
   else if (params.a < 0 || params.a > 2) bad = "Wrong number of additional q-grams.";
   else if (min_insert < 0 || max_insert < min_insert || max_insert > (1ll << 30)) bad = "Wrong insert size range.";
+  else if (rescue_discordant && !rescue_given) bad = "--rescue-discordant needs --rescue.";
   else if (rescue_given && !read2_path) bad = "--rescue needs read pairs (--read2).";
   else if (rescue_given && (rescue_edits < 0 || rescue_edits > 15)) bad = "Wrong rescue error threshold (0-15).";
   else if (rescue_given && max_insert - min_insert > 65536) bad = "--rescue searches insert size ranges of at most 65536.";
@@ -560,6 +566,7 @@ int map_main(int argc, char **argv) {
             if (!rc && rescue_given) {
               const fem_rescue_params rp{(int32_t)rescue_edits};
               rc = fem_dev_set_rescue(devs[(size_t)g], sl, &rp);
+              if (!rc && rescue_discordant) rc = fem_dev_set_rescue_discordant(devs[(size_t)g], sl, 1);
             }
           }
         }
@@ -671,7 +678,7 @@ int map_main(int argc, char **argv) {
   std::vector<TextOut> texts(3);
   for (TextOut &t : texts) text_free_q.push(&t);
   std::vector<uint64_t> per_gpu((size_t)n_gpus * 5, 0), per_gpu_proper((size_t)n_gpus, 0),
-      per_gpu_rescued((size_t)n_gpus, 0), per_gpu_unmapped((size_t)n_gpus, 0), per_gpu_filtered((size_t)n_gpus, 0);
+      per_gpu_rescued((size_t)n_gpus, 0), per_gpu_rescued_disc((size_t)n_gpus, 0), per_gpu_unmapped((size_t)n_gpus, 0), per_gpu_filtered((size_t)n_gpus, 0);
 
   // ---- writer (src/output_queue.c:60-91) ----
   std::thread writer([&] {
@@ -828,6 +835,7 @@ int map_main(int argc, char **argv) {
                                : fem_dev_fetch_records(h, b->slot, &b->rec);
         if (!rc && paired) rc = fem_dev_pair_count(h, b->slot, &b->n_proper);
         if (!rc && rescue_given) rc = fem_dev_rescue_count(h, b->slot, &b->n_rescued);
+        if (!rc && rescue_discordant) rc = fem_dev_rescue_discordant_count(h, b->slot, &b->n_rescued_discordant);
         if (!rc && unmapped) rc = fem_dev_unmapped_count(h, b->slot, &b->n_unmapped);
         if (!rc && report) rc = fem_dev_filtered_count(h, b->slot, &b->n_filtered);
         const double waited = real_time() - t0;
@@ -866,6 +874,7 @@ int map_main(int argc, char **argv) {
           const uint64_t *st = host_tail ? b->res.stats : device_text ? b->sam.stats : b->rec.stats;
           for (int i = 0; i < 5; ++i) per_gpu[(size_t)g * 5 + (size_t)i] += st[i];
           if (paired) per_gpu_proper[(size_t)g] += b->n_proper, per_gpu_rescued[(size_t)g] += b->n_rescued;
+          if (paired) per_gpu_rescued_disc[(size_t)g] += b->n_rescued_discordant;
           per_gpu_unmapped[(size_t)g] += b->n_unmapped;
           per_gpu_filtered[(size_t)g] += b->n_filtered;
           if (device_text) {
@@ -1200,6 +1209,11 @@ int map_main(int argc, char **argv) {
       uint64_t n_rescued = 0;
       for (uint64_t x : per_gpu_rescued) n_rescued += x;
       fprintf(stderr, "The number of rescued mates: %lu\n", (unsigned long)n_rescued);
+      if (rescue_discordant) {
+        uint64_t n_disc = 0;
+        for (uint64_t x : per_gpu_rescued_disc) n_disc += x;
+        fprintf(stderr, "The number of rescued discordant pairs: %lu\n", (unsigned long)n_disc);
+      }
     }
   }
   if (unmapped) {

@@ -1759,9 +1759,11 @@ struct PairParams {
   uint32_t *pair_begin;       // 2 n_pairs + 1
   uint32_t *n_proper;
   // mate rescue (nullptr: off): exclusive scan of the kept rescued records over the pairs (n_pairs + 1); pair i's one, if it
-  // has one, is record resc_first + resc_before[i] and becomes the only record of its mate that had none
+  // has one, is record resc_first + resc_before[i]; it belongs to the mate its s_read names and stands in front of that mate's
+  // own records (none where the mate had no record; with fem_dev_set_rescue_discordant it can have some, which pair with nothing)
   const uint32_t *resc_before;
   uint32_t resc_first;
+  const uint32_t *s_read;
   // MAPQ (pair_kernel<true>): per line, 0 on every line but a mate's primary one, which gets kPairProper | qp for a proper pair
   // (| kPairOwn when the chosen record may keep its single-end MAPQ: not rescued, NM = d1 of its mate); mapq_kernel finishes it
   uint8_t *lmq;
@@ -1846,15 +1848,18 @@ __device__ __forceinline__ int64_t concordant(const PairParams &p, const MateRec
   return ins >= p.min_insert && ins <= p.max_insert ? ins : -1;
 }
 
-// lines [first, na + nb) of a pair, every step-th one (kMapq: mq_a, mq_b the bytes of the mates' primary lines)
+// lines [first, na + nb) of a pair, every step-th one (kMapq: mq_a, mq_b the bytes of the mates' primary lines).  na, nb: the
+// mates' lines, their records from a0, b0 on.  resc (1 = mate 1, 2 = mate 2): that mate's list is its rescued record alone
+// (at a0 or b0, the chosen one), which is its first line; its own records, from own0 on, are its other lines.
 template <bool kMapq>
 __device__ void write_pair(const PairParams &p, uint32_t a0, uint32_t na, uint32_t b0, uint32_t nb, uint32_t ob, bool proper, uint32_t ca,
-                           uint32_t cb, int64_t insert, uint32_t first, uint32_t step, uint32_t mq_a = 0, uint32_t mq_b = 0) {
+                           uint32_t cb, int64_t insert, uint32_t first, uint32_t step, uint32_t resc, uint32_t own0, uint32_t mq_a = 0,
+                           uint32_t mq_b = 0) {
   for (uint32_t u = first; u < na + nb; u += step) {
     const bool m2 = u >= na;
     const uint32_t t = m2 ? u - na : u, c = m2 ? cb : ca;
     const uint32_t idx = proper ? (t == 0 ? c : t - 1u + (t - 1u >= c ? 1u : 0u)) : t;
-    const uint32_t rec = (m2 ? b0 : a0) + idx;
+    const uint32_t rec = resc == (m2 ? 2u : 1u) && t ? own0 + t - 1u : (m2 ? b0 : a0) + idx;
     const bool has_other = m2 ? na > 0 : nb > 0;
     const uint32_t other = m2 ? a0 + (proper ? ca : 0u) : b0 + (proper ? cb : 0u);
     const uint32_t fl = p.flag[rec];
@@ -1884,7 +1889,7 @@ __global__ void __launch_bounds__(256) pair_kernel(PairParams p) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   const bool live = i < p.n_pairs;
   uint32_t a0 = 0, na = 0, b0 = 0, nb = 0, ob = 0;
-  uint32_t resc = 0;  // kMapq: 1 = list A is a rescued record, 2 = list B
+  uint32_t resc = 0, own0 = 0, own_n = 0;  // 1 = list A is a rescued record, 2 = list B; that mate's own records (its lines behind it)
   if (live) {
     const uint32_t mid = p.rec_begin[p.n_pairs];
     a0 = p.rec_begin[i], na = p.rec_begin[i + 1] - a0;
@@ -1893,17 +1898,20 @@ __global__ void __launch_bounds__(256) pair_kernel(PairParams p) {
     if (p.resc_before) {  // ... and their rescued mates
       const uint32_t before = p.resc_before[i], kept = p.resc_before[i + 1] - before;
       ob += before;
-      if (kept) {
-        if (na == 0) a0 = p.resc_first + before, na = 1, resc = 1;
-        else b0 = p.resc_first + before, nb = 1, resc = 2;
+      if (kept) {  // the rescued record alone is its mate's list: the mate's own records, if it has any, pair with nothing
+        const uint32_t rrec = p.resc_first + before;
+        if (p.s_read[rrec] < p.n_pairs) own0 = a0, own_n = na, a0 = rrec, na = 1, resc = 1;
+        else own0 = b0, own_n = nb, b0 = rrec, nb = 1, resc = 2;
       }
     }
-    p.pair_begin[2u * i] = ob, p.pair_begin[2u * i + 1u] = ob + na;
-    if (i + 1u == p.n_pairs) p.pair_begin[2u * i + 2u] = ob + na + nb;
+    const uint32_t la = na + (resc == 1u ? own_n : 0u), lb = nb + (resc == 2u ? own_n : 0u);
+    p.pair_begin[2u * i] = ob, p.pair_begin[2u * i + 1u] = ob + la;
+    if (i + 1u == p.n_pairs) p.pair_begin[2u * i + 2u] = ob + la + lb;
   }
   const bool big = live && (uint64_t)na * nb > kPairAlone;
   bool proper_here = false;
   if (live && !big) {  // the lane alone: a ascending, b ascending, only a smaller sum replaces (the tie rule)
+    const uint32_t la = na + (resc == 1u ? own_n : 0u), lb = nb + (resc == 2u ? own_n : 0u);
     uint32_t best = 0xFFFFFFFFu, ca = 0, cb = 0;
     int64_t ins = -1;
     Strata st;
@@ -1920,10 +1928,10 @@ __global__ void __launch_bounds__(256) pair_kernel(PairParams p) {
     proper_here = best != 0xFFFFFFFFu;
     if (kMapq) {
       const uint32_t qp = pair_qp(st);
-      write_pair<true>(p, a0, na, b0, nb, ob, proper_here, ca, cb, ins, 0u, 1u, pair_mq_byte(p, proper_here, qp, a0, ca, resc == 1),
+      write_pair<true>(p, a0, la, b0, lb, ob, proper_here, ca, cb, ins, 0u, 1u, resc, own0, pair_mq_byte(p, proper_here, qp, a0, ca, resc == 1),
                        pair_mq_byte(p, proper_here, qp, b0, cb, resc == 2));
     } else {
-      write_pair<false>(p, a0, na, b0, nb, ob, proper_here, ca, cb, ins, 0u, 1u);
+      write_pair<false>(p, a0, la, b0, lb, ob, proper_here, ca, cb, ins, 0u, 1u, resc, own0);
     }
   }
   // pairs with many combinations (repeats): the wave, one pair after the other; the lanes stride over the longer list, each
@@ -1934,7 +1942,8 @@ __global__ void __launch_bounds__(256) pair_kernel(PairParams p) {
     const uint32_t src = (uint32_t)__builtin_ctzll(todo);
     todo &= todo - 1u;
     const uint32_t A0 = wave_bcast(a0, src), NA = wave_bcast(na, src), B0 = wave_bcast(b0, src), NB = wave_bcast(nb, src);
-    const uint32_t OB = wave_bcast(ob, src), RESC = kMapq ? wave_bcast(resc, src) : 0u;
+    const uint32_t OB = wave_bcast(ob, src), RESC = wave_bcast(resc, src), OWN0 = wave_bcast(own0, src), OWN_N = wave_bcast(own_n, src);
+    const uint32_t LA = NA + (RESC == 1u ? OWN_N : 0u), LB = NB + (RESC == 2u ? OWN_N : 0u);
     const bool lanes_on_a = NA >= NB;
     const uint32_t n_long = lanes_on_a ? NA : NB, n_short = lanes_on_a ? NB : NA;
     uint64_t key = kNoKey;
@@ -1967,15 +1976,60 @@ __global__ void __launch_bounds__(256) pair_kernel(PairParams p) {
     const int64_t ins = proper ? concordant(p, mate_rec(p, A0 + ca), mate_rec(p, B0 + cb)) : -1;
     if (kMapq) {
       const uint32_t qp = pair_qp(wave_strata(st));
-      write_pair<true>(p, A0, NA, B0, NB, OB, proper, ca, cb, ins, ln, 64u, pair_mq_byte(p, proper, qp, A0, ca, RESC == 1),
+      write_pair<true>(p, A0, LA, B0, LB, OB, proper, ca, cb, ins, ln, 64u, RESC, OWN0, pair_mq_byte(p, proper, qp, A0, ca, RESC == 1),
                        pair_mq_byte(p, proper, qp, B0, cb, RESC == 2));
     } else {
-      write_pair<false>(p, A0, NA, B0, NB, OB, proper, ca, cb, ins, ln, 64u);
+      write_pair<false>(p, A0, LA, B0, LB, OB, proper, ca, cb, ins, ln, 64u, RESC, OWN0);
     }
     if (ln == src) proper_here = proper;
   }
   const uint64_t proper_lanes = __ballot(proper_here);
   if (ln == 0 && proper_lanes) atomicAdd(p.n_proper, (uint32_t)__builtin_popcountll(proper_lanes));
+}
+
+// The probe of fem_dev_set_rescue_discordant: disc[i] = 1 for a pair with records on both sides of which no
+// combination is concordant, mate rescue's second kind of candidate, else 0.  The work is divided as pair_kernel's: a pair of
+// up to kPairAlone combinations is its lane's, a larger one its wave's, the lanes striding over the longer list; the walk
+// ends at the first concordant combination (the wave's: a ballot after every step of the stride).
+__global__ void __launch_bounds__(256) pair_probe_kernel(PairParams p, uint8_t *disc) {
+  const uint32_t ln = threadIdx.x & 63u;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = i < p.n_pairs;
+  uint32_t a0 = 0, na = 0, b0 = 0, nb = 0;
+  if (live) {
+    a0 = p.rec_begin[i], na = p.rec_begin[i + 1] - a0;
+    b0 = p.rec_begin[p.n_pairs + i], nb = p.rec_begin[p.n_pairs + i + 1] - b0;
+  }
+  const bool both = na && nb, big = both && (uint64_t)na * nb > kPairAlone;
+  bool found = false;
+  if (both && !big) {
+    for (uint32_t a = 0; a < na && !found; ++a) {
+      const MateRec ra = mate_rec(p, a0 + a);
+      if (ra.flag & 0x8000u) continue;
+      for (uint32_t b = 0; b < nb && !found; ++b) found = concordant(p, ra, mate_rec(p, b0 + b)) >= 0;
+    }
+  }
+  uint64_t todo = __ballot(big);
+  while (todo) {
+    const uint32_t src = (uint32_t)__builtin_ctzll(todo);
+    todo &= todo - 1u;
+    const uint32_t A0 = wave_bcast(a0, src), NA = wave_bcast(na, src), B0 = wave_bcast(b0, src), NB = wave_bcast(nb, src);
+    const bool lanes_on_a = NA >= NB;
+    const uint32_t long0 = lanes_on_a ? A0 : B0, n_long = lanes_on_a ? NA : NB, short0 = lanes_on_a ? B0 : A0, n_short = lanes_on_a ? NB : NA;
+    bool any = false;
+    for (uint32_t u0 = 0; u0 < n_long && !any; u0 += 64u) {
+      const uint32_t u = u0 + ln;
+      bool hit = false;
+      if (u < n_long) {
+        const MateRec ru = mate_rec(p, long0 + u);
+        if (!(ru.flag & 0x8000u))
+          for (uint32_t v = 0; v < n_short && !hit; ++v) hit = concordant(p, ru, mate_rec(p, short0 + v)) >= 0;
+      }
+      any = __ballot(hit) != 0;
+    }
+    if (ln == src) found = any;
+  }
+  if (live) disc[i] = both && !found ? 1u : 0u;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2155,8 +2209,12 @@ __global__ void __launch_bounds__(256) report_kernel(ReportParams p) {
 // kRescueAnchors records without 0x8000 are the anchors, and B's pos0 is searched in each anchor's insert window at E edits:
 // tiles c = lo + j (2E + 1), each the banded Myers of fo_banded_ed32 over ref[c, c + L + 2E) (first strict minimum, the same
 // 32-bit word and character codes); the least (nm(anchor) + ed, anchor, pos0) is traced (trace_record at E) and kept if it is
-// concordant with its anchor.  Four kernels, then an exclusive scan of the kept records, then pair_kernel:
-//   rescue_jobs_kernel   lane per pair: candidates and one job per (candidate, anchor)
+// concordant with its anchor.  With fem_dev_set_rescue_discordant a pair with records on both sides and no concordant
+// combination (pair_probe_kernel's flag) is a candidate too, searched in both directions d (0: B is mate 2, the anchors are
+// mate 1's; 1: the other way round); the least (nm(anchor) + ed, d, anchor, pos0) is traced and a kept record goes behind B's
+// own.  A pair with one empty list has the one direction that its lists give.  Four kernels (five with the probe in front),
+// then an exclusive scan of the kept records, then pair_kernel:
+//   rescue_jobs_kernel   lane per pair: candidates and one job per (candidate, direction, anchor)
 //   rescue_search_kernel wave per job, lane per tile: the mate's codes staged in LDS once per wave, a 64-bit atomicMin per job
 //   rescue_trace_kernel  lane per candidate: the traceback, the concordance check
 //   rescue_append_kernel lane per candidate: the kept records behind run()'s (record arrays, CIGAR / MD, s_read)
@@ -2181,10 +2239,12 @@ struct RescueParams {
   uint64_t ref_bytes;
   const uint64_t *seq_off;
   const uint32_t *seq_len;
-  uint32_t *ctl;                 // [0] candidates, [1] jobs, [2] overflow queue length, [3] overflow staging too small (never)
+  const uint8_t *disc;           // pair_probe_kernel's flag per pair; nullptr: pairs with records on both sides are no candidates
+  uint32_t *ctl;                 // [0] candidates, [1] jobs, [2] overflow queue length, [3] overflow staging too small (never),
+                                 // [4] kept records of pairs with records on both sides
   uint32_t *cand_pair;           // per candidate: its pair
-  uint32_t *jobs;                // candidate << 3 | anchor index
-  unsigned long long *best;      // per candidate: (nm(a) + ed) << 35 | a << 32 | pos0, ~0 = no hit
+  uint32_t *jobs;                // candidate << 4 | direction << 3 | anchor index
+  unsigned long long *best;      // per candidate: (nm(a) + ed) << 36 | d << 35 | a << 32 | pos0, ~0 = no hit
   uint32_t lanes, text_words, pat_words, max_len;  // LDS plan of the trace kernel
   uint32_t ops_cap, md_cap;
   uint32_t *t_ops;               // first pass, per candidate: ops_cap runs, md_cap MD characters
@@ -2200,18 +2260,17 @@ struct RescueParams {
   uint32_t cig_total, md_total;  // run()'s CIGAR runs and MD characters
 };
 
-// pair i's candidate view: the anchors' mate (A) and the mate without records (B)
+// pair i's candidate view in direction d: the anchors' mate (A: mate 1 for d = 0, mate 2 for d = 1) and the searched mate (B)
 struct RescuePair {
   uint32_t a0, na, b_read;
 };
-__device__ __forceinline__ RescuePair rescue_pair(const RescueParams &p, uint32_t i) {
-  const uint32_t a0 = p.rec_begin[i], na = p.rec_begin[i + 1] - a0;
-  const uint32_t b0 = p.rec_begin[p.n_pairs + i], nb = p.rec_begin[p.n_pairs + i + 1] - b0;
+__device__ __forceinline__ RescuePair rescue_pair(const RescueParams &p, uint32_t i, uint32_t d) {
+  const uint32_t a_read = d ? p.n_pairs + i : i;
   RescuePair r;
-  if (na) r.a0 = a0, r.na = na, r.b_read = p.n_pairs + i;
-  else r.a0 = b0, r.na = nb, r.b_read = i;
+  r.a0 = p.rec_begin[a_read], r.na = p.rec_begin[a_read + 1] - r.a0, r.b_read = d ? i : p.n_pairs + i;
   return r;
 }
+constexpr unsigned long long kBestDir = 1ull << 35;  // the direction's bit of RescueParams::best
 
 // an anchor's window of B's pos0 ([lo, hi], empty when lo > hi) and the strand B is searched on
 struct RescueWindow {
@@ -2247,17 +2306,19 @@ __global__ void __launch_bounds__(256) rescue_jobs_kernel(RescueParams p) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= p.n_pairs) return;
   const uint32_t na = p.rec_begin[i + 1] - p.rec_begin[i], nb = p.rec_begin[p.n_pairs + i + 1] - p.rec_begin[p.n_pairs + i];
-  if ((na == 0) == (nb == 0)) return;
-  const RescuePair rp = rescue_pair(p, i);
-  const uint32_t n_look = rp.na < kRescueAnchors ? rp.na : kRescueAnchors;
-  uint32_t anchors = 0;  // bit a: record a of A is an anchor
-  for (uint32_t a = 0; a < n_look; ++a)
-    if (!(p.flag[rp.a0 + a] & kFlagBroken)) anchors |= 1u << a;
+  if ((na == 0) == (nb == 0) && !(na && p.disc && p.disc[i])) return;
+  uint32_t anchors = 0;  // bit d << 3 | a: record a of direction d's A is an anchor
+  for (uint32_t d = 0; d < 2u; ++d) {
+    const RescuePair rp = rescue_pair(p, i, d);
+    const uint32_t n_look = rp.na < kRescueAnchors ? rp.na : kRescueAnchors;
+    for (uint32_t a = 0; a < n_look; ++a)
+      if (!(p.flag[rp.a0 + a] & kFlagBroken)) anchors |= 1u << (d << 3 | a);
+  }
   if (!anchors) return;
   const uint32_t k = atomicAdd(&p.ctl[0], 1u);
   p.cand_pair[k] = i, p.best[k] = ~0ull;
   uint32_t j = atomicAdd(&p.ctl[1], (uint32_t)__builtin_popcount(anchors));
-  for (; anchors; anchors &= anchors - 1u) p.jobs[j++] = k << 3 | (uint32_t)__builtin_ctz(anchors);
+  for (; anchors; anchors &= anchors - 1u) p.jobs[j++] = k << 4 | (uint32_t)__builtin_ctz(anchors);
 }
 
 // fo_banded_ed32 (E, pat[0 .. L + 2E), text codes tc[0 .. L)): the same operations on the same 32-bit words, the read's code
@@ -2311,8 +2372,8 @@ __global__ void __launch_bounds__(256) rescue_search_kernel(RescueParams p) {
   const int E = p.E;
   const int64_t W = 2 * E + 1;
   for (uint32_t job = blockIdx.x * kResWaves + wv; job < n_jobs; job += gridDim.x * kResWaves) {
-    const uint32_t k = p.jobs[job] >> 3, a = p.jobs[job] & 7u;
-    const RescuePair rp = rescue_pair(p, p.cand_pair[k]);
+    const uint32_t k = p.jobs[job] >> 4, d = p.jobs[job] >> 3 & 1u, a = p.jobs[job] & 7u;
+    const RescuePair rp = rescue_pair(p, p.cand_pair[k], d);
     const MateRec an = rescue_rec(p, rp.a0 + a);
     const uint64_t off = p.read_off[rp.b_read];
     const int64_t L = (int64_t)(p.read_off[rp.b_read + 1] - off);
@@ -2344,7 +2405,7 @@ __global__ void __launch_bounds__(256) rescue_search_kernel(RescueParams p) {
       key = o < key ? o : key;
     }
     if (ln == 0 && key != ~0ull)
-      atomicMin(&p.best[k], (unsigned long long)(an.nm + (uint32_t)(key >> 32)) << 35 | (unsigned long long)a << 32 | (uint32_t)key);
+      atomicMin(&p.best[k], (unsigned long long)(an.nm + (uint32_t)(key >> 32)) << 36 | (unsigned long long)(d << 3 | a) << 32 | (uint32_t)key);
   }
 }
 
@@ -2369,9 +2430,9 @@ __global__ void __launch_bounds__(64) rescue_trace_kernel(RescueParams p) {
     const unsigned long long best = p.best[k];
     if (best == ~0ull) continue;
     const uint32_t i = p.cand_pair[k], a = (uint32_t)(best >> 32) & 7u, pos = (uint32_t)best;
-    const RescuePair rp = rescue_pair(p, i);
+    const RescuePair rp = rescue_pair(p, i, best & kBestDir ? 1u : 0u);
     const MateRec an = rescue_rec(p, rp.a0 + a);
-    const int ed = (int)(best >> 35) - (int)an.nm;
+    const int ed = (int)(best >> 36) - (int)an.nm;
     const uint64_t off = p.read_off[rp.b_read];
     const int L = (int)(p.read_off[rp.b_read + 1] - off);
     const RescueWindow w = rescue_window(p, an, L);
@@ -2430,7 +2491,8 @@ __global__ void __launch_bounds__(256) rescue_append_kernel(RescueParams p) {
   const uint32_t rec = p.n_records + p.s_kept[i];
   const uint32_t *cr = p.c_rec + (size_t)k * kRescRec;
   p.tid[rec] = cr[0], p.pos0[rec] = cr[1], p.flag[rec] = (uint16_t)(cr[2] & 0xFFFFu), p.nm[rec] = (uint8_t)(cr[2] >> 16);
-  p.s_read[rec] = rescue_pair(p, i).b_read;
+  p.s_read[rec] = rescue_pair(p, i, p.best[k] & kBestDir ? 1u : 0u).b_read;
+  if (p.disc && p.disc[i]) atomicAdd(&p.ctl[4], 1u);
   const uint32_t co = p.cig_total + p.s_ops[i], mo = p.md_total + p.s_md[i];
   p.cigar_off[rec] = co, p.md_off[rec] = mo;
   const uint32_t *ops = cr[4] ? p.o_ops + (size_t)(cr[4] - 1u) * p.o_ops_cap : p.t_ops + (size_t)k * p.ops_cap;
@@ -2542,7 +2604,7 @@ struct Tail::Impl {
   // mate rescue (pair() with a RescueInput): candidates, jobs, best hits, the tracebacks' staging, the kept flags and their scans
   DevBuf<uint32_t> r_ctl, r_cand, r_jobs, r_ops, r_rec, r_ovf, r_o_ops, r_kept, r_scan;
   DevBuf<unsigned long long> r_best;
-  DevBuf<uint8_t> r_md, r_o_md, r_scan_tmp;
+  DevBuf<uint8_t> r_md, r_o_md, r_scan_tmp, r_disc;
   PinBuf<uint32_t> h_r_ctl, h_r_tid, h_r_pos0, h_r_cigar_off, h_r_cigar, h_r_md_off;
   PinBuf<uint16_t> h_r_flag;
   PinBuf<uint8_t> h_r_nm;
@@ -2555,6 +2617,7 @@ struct Tail::Impl {
   uint32_t last_n = 0, last_nr = 0;  // what the last run() left on the device
   bool paired = false;               // pair() has run on it
   uint32_t n_resc = 0;               // rescued records the last pair() appended behind run()'s (records last_nr ..)
+  uint32_t n_resc_disc = 0;          // ... those of pairs with records on both sides among them (RescueInput::discordant)
   bool pair_mapq = false;            // the last pair() left its MAPQ bytes in lmq, not yet made MAPQ by a text
   bool filtered = false;             // the last text went through the line filter
   uint32_t n_unm = 0;                // lines for unmapped reads in the last text
@@ -2865,7 +2928,7 @@ int Tail::warm(hipStream_t stream, std::string *err) {
                            (const void *)report_kernel<false>, (const void *)report_kernel<true>,
                            (const void *)sam_len_kernel<false, true>, (const void *)sam_write_kernel<false, true>,
                            (const void *)sam_len_kernel<true, true>, (const void *)sam_write_kernel<true, true>,
-                           (const void *)rescue_jobs_kernel,
+                           (const void *)rescue_jobs_kernel, (const void *)pair_probe_kernel,
                            (const void *)rescue_search_kernel, (const void *)rescue_trace_kernel, (const void *)rescue_append_kernel};
   for (const void *k : kernels) TAIL_TRY(hipFuncGetAttributes(&a, k));
   if (!m.scan_tmp || !m.rec_begin || !m.n_ops || !m.line_len) return FEM_OK;  // (nothing reserved: the scans load with the first batch)
@@ -3138,16 +3201,17 @@ int Tail::pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::
     if (err) *err = "a paired batch holds an even number of reads";
     return FEM_ERR_INVALID;
   }
-  m.n_resc = 0, m.pair_mapq = false;
+  m.n_resc = 0, m.n_resc_disc = 0, m.pair_mapq = false;
   m.not_run({kRescue, kPairing});
   const uint32_t *resc_before = nullptr;
   if (rescue && np) {  // ---- mate rescue: the kept records behind run()'s, resc_before their exclusive scan over the pairs ----
     const int32_t E = rescue->max_edits;
-    TAIL_TRY(m.r_ctl.ensure(4));
-    TAIL_TRY(m.h_r_ctl.ensure(4));
+    TAIL_TRY(m.r_ctl.ensure(8));
+    TAIL_TRY(m.h_r_ctl.ensure(8));
     TAIL_TRY(m.r_cand.ensure((size_t)np));
     TAIL_TRY(m.r_best.ensure((size_t)np));
-    TAIL_TRY(m.r_jobs.ensure((size_t)np * kRescueAnchors));
+    TAIL_TRY(m.r_jobs.ensure((size_t)np * kRescueAnchors * (rescue->discordant ? 2u : 1u)));  // (both directions)
+    if (rescue->discordant) TAIL_TRY(m.r_disc.ensure((size_t)np));
     const uint32_t *h_tot = m.h_ctl;  // run() left its CIGAR and MD totals in h_ctl[4], h_ctl[5]
     RescueParams r{};
     r.n_pairs = np, r.n_records = nr, r.E = E, r.min_insert = min_insert, r.max_insert = max_insert;
@@ -3158,7 +3222,15 @@ int Tail::pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::
     r.cig_total = h_tot[4], r.md_total = h_tot[5];
     m.bind_records(&r);
     TAIL_TRY(m.span[kRescue].begin(stream));
-    TAIL_TRY(hipMemsetAsync(m.r_ctl, 0, 16, stream));
+    TAIL_TRY(hipMemsetAsync(m.r_ctl, 0, 32, stream));
+    if (rescue->discordant) {  // the pairs with records on both sides that do not pair are candidates too
+      PairParams q{};
+      q.n_pairs = np, q.min_insert = min_insert, q.max_insert = max_insert;
+      m.bind_pairing(&q);
+      hipLaunchKernelGGL(pair_probe_kernel, dim3((np + 255u) / 256u), dim3(256), 0, stream, q, m.r_disc.get());
+      TAIL_TRY(hipGetLastError());
+      r.disc = m.r_disc;
+    }
     hipLaunchKernelGGL(rescue_jobs_kernel, dim3((np + 255u) / 256u), dim3(256), 0, stream, r);
     TAIL_TRY(hipGetLastError());
     uint32_t *h_rc = m.h_r_ctl;
@@ -3224,13 +3296,13 @@ int Tail::pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::
       hipLaunchKernelGGL(rescue_append_kernel, dim3((n_cand + 255u) / 256u), dim3(256), 0, stream, r);
       TAIL_TRY(hipGetLastError());
       TAIL_TRY(hipMemcpyAsync(h_rc, m.r_scan + np, 4, hipMemcpyDeviceToHost, stream));
-      TAIL_TRY(hipMemcpyAsync(h_rc + 3, m.r_ctl + 3, 4, hipMemcpyDeviceToHost, stream));
+      TAIL_TRY(hipMemcpyAsync(h_rc + 3, m.r_ctl + 3, 8, hipMemcpyDeviceToHost, stream));
       TAIL_TRY(hipStreamSynchronize(stream));
       if (h_rc[3] != 0) {
         if (err) *err = "mate rescue: a traceback outgrew its staging (internal error)";
         return FEM_ERR_HIP;
       }
-      m.n_resc = h_rc[0];
+      m.n_resc = h_rc[0], m.n_resc_disc = h_rc[4];
       if (m.n_resc) resc_before = m.r_scan;
     }
     TAIL_TRY(m.span[kRescue].end(stream));
@@ -3253,7 +3325,7 @@ int Tail::pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::
     m.bind_pairing(&q);
     q.perm = m.perm, q.pflag = m.pflag, q.mtid = m.mtid, q.mpos0 = m.mpos0;
     q.tlen = m.tlen, q.pair_begin = m.pair_begin, q.n_proper = m.pair_ctl;
-    q.resc_before = resc_before, q.resc_first = nr;
+    q.resc_before = resc_before, q.resc_first = nr, q.s_read = m.s_read;
     q.lmq = mapq ? m.lmq : nullptr;
     hipLaunchKernelGGL(mapq ? pair_kernel<true> : pair_kernel<false>, dim3((np + 255u) / 256u), dim3(256), 0, stream, q);
     TAIL_TRY(hipGetLastError());
@@ -3267,6 +3339,7 @@ int Tail::pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::
 }
 
 uint64_t Tail::n_rescued() const { return impl_ && impl_->paired ? impl_->n_resc : 0; }
+uint64_t Tail::n_rescued_discordant() const { return impl_ && impl_->paired ? impl_->n_resc_disc : 0; }
 uint64_t Tail::n_unmapped() const { return impl_ ? impl_->n_unm : 0; }
 uint64_t Tail::n_filtered() const { return impl_ ? impl_->n_filtered : 0; }
 uint64_t Tail::n_proper() const { return impl_ && impl_->paired && impl_->h_pair_ctl ? impl_->h_pair_ctl[0] : 0; }

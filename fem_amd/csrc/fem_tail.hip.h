@@ -112,6 +112,9 @@ struct RescueInput {  // device pointers unless noted
   uint64_t ref_bytes;          // host: bytes in ref_raw, its slack included
   const uint64_t *seq_off;
   const uint32_t *seq_len;
+  // fem_dev_set_rescue_discordant: a pair with records on both sides and no concordant combination is a candidate too,
+  // searched from either mate's anchors (pair_probe_kernel in front of the rescue kernels)
+  bool discordant = false;
 };
 
 // One text on its way home at a time (per GPU).  Two device-to-host copies queued in the copy engines take both of them, and
@@ -161,13 +164,15 @@ class Tail {
   // Pairs the records of the last run() (pair_kernel): output order, FLAG, mate columns and TLEN of every line, the proper-pair
   // count.  Asynchronous on `stream`; n_proper() is valid once the stream has been synchronised (sam() does).
   // rescue (optional): mate rescue first (the rescue kernels), the kept rescued records appended behind run()'s; pair() then
-  // waits for the stream twice (the candidate count, the kept count).
+  // waits for the stream twice (the candidate count, the kept count).  RescueInput::discordant: pair_probe_kernel runs at
+  // their head, inside stage kRescue, and adds no wait.
   // mapq: pair_kernel also writes each line's pairing byte (qp and whether the chosen record may keep its own MAPQ), which the
   // next sam() / bam() with SamInput::mapq turns into the MAPQ of the mates' primary lines.
   int pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::string *err, const RescueInput *rescue = nullptr,
            bool mapq = false);
   uint64_t n_proper() const;
   uint64_t n_rescued() const;   // kept rescued records of the last pair() (0 without rescue)
+  uint64_t n_rescued_discordant() const;  // ... those of pairs with records on both sides (0 without RescueInput::discordant)
   uint64_t n_unmapped() const;  // lines for unmapped reads in the last sam() / bam() (0 without SamInput::unmapped)
   uint64_t n_filtered() const;  // lines the filter left out of the last sam() / bam() (0 without SamInput::strata / max_hits)
   // The device time of a stage, in ms.  Negative: the stage was not part of the last run() and of what followed it (pair(),

@@ -20,7 +20,7 @@ ABI_SYMBOLS = [
     "fem_device_numa", "fem_bind_thread_near_device",
     "fem_dev_allreduce_stats",
     "fem_dev_set_pairs", "fem_dev_fetch_pairs", "fem_dev_pair_count",
-    "fem_dev_set_rescue", "fem_dev_rescue_count", "fem_dev_set_mapq",
+    "fem_dev_set_rescue", "fem_dev_rescue_count", "fem_dev_set_rescue_discordant", "fem_dev_rescue_discordant_count", "fem_dev_set_mapq",
     "fem_dev_set_unmapped", "fem_dev_unmapped_count",
     "fem_dev_set_report", "fem_dev_filtered_count", "fem_dev_set_tags",
     "fem_dev_fetch_bam", "fem_dev_fetch_bam_nowait", "fem_dev_bam_wait", "fem_dev_bgzf_compress",
@@ -163,6 +163,9 @@ def load_hip():
     if hasattr(L, "fem_dev_set_rescue"):
         L.fem_dev_set_rescue.argtypes = [vp, C.c_int, C.POINTER(_RescueParams)]
         L.fem_dev_rescue_count.argtypes = [vp, C.c_int, C.POINTER(u64)]
+    if hasattr(L, "fem_dev_set_rescue_discordant"):
+        L.fem_dev_set_rescue_discordant.argtypes = [vp, C.c_int, C.c_int]
+        L.fem_dev_rescue_discordant_count.argtypes = [vp, C.c_int, C.POINTER(u64)]
     if hasattr(L, "fem_dev_set_mapq"):
         L.fem_dev_set_mapq.argtypes = [vp, C.c_int, C.c_int]
     if hasattr(L, "fem_dev_set_unmapped"):
@@ -613,6 +616,11 @@ class Device:
             rp = _RescueParams(int(max_edits))
             self._check(self._L.fem_dev_set_rescue(self._h, slot, C.byref(rp)))
 
+    def set_rescue_discordant(self, on=True, slot=0):
+        """fem_dev_set_rescue_discordant: with pair mode and set_rescue, also rescue a mate of a pair whose records do not pair
+        (both mates have records, no combination is concordant); False: only the mate without records, as before."""
+        self._check(self._L.fem_dev_set_rescue_discordant(self._h, slot, 1 if on else 0))
+
     def set_mapq(self, on=True, slot=0):
         """fem_dev_set_mapq: MAPQ from the hit strata in the slot's SAM text and BAM records (False: 255, as the reference)."""
         self._check(self._L.fem_dev_set_mapq(self._h, slot, 1 if on else 0))
@@ -660,6 +668,12 @@ class Device:
         """fem_dev_rescue_count: rescued mates of the slot's last paired text (or fetch_pairs)."""
         n = C.c_uint64()
         self._check(self._L.fem_dev_rescue_count(self._h, slot, C.byref(n)))
+        return int(n.value)
+
+    def rescue_discordant_count(self, slot=0):
+        """fem_dev_rescue_discordant_count: the rescued records of pairs whose records did not pair among rescue_count's."""
+        n = C.c_uint64()
+        self._check(self._L.fem_dev_rescue_discordant_count(self._h, slot, C.byref(n)))
         return int(n.value)
 
     def map_batch(self, bases, offsets, e=3, a=1, k=12, step=3, slot=0):

@@ -368,6 +368,29 @@ typedef struct {
 int fem_dev_set_rescue(fem_dev *h, int slot, const fem_rescue_params *rp);
 int fem_dev_rescue_count(fem_dev *h, int slot, uint64_t *n_rescued);
 
+/* ---- mate rescue for pairs whose records do not pair (new; opt-in: with it off, or with rescue off, every output stays byte
+ *      for byte what it is without it) ----
+ * fem_dev_set_rescue_discordant: on != 0: where pair mode and fem_dev_set_rescue are on, a pair is a candidate in two ways.
+ *   Kind 1 (as above): exactly one mate has no record; nothing about it changes.
+ *   Kind 2: both mates have at least one record and no combination (a, b) of their records is concordant (the pairing rule
+ *   above; records with 0x8000 never pair).
+ * Rule for kind 2.  Both directions are searched: d = 0, B is mate 2 and the anchors are mate 1's first FEM_RESCUE_ANCHORS
+ *   records without 0x8000; d = 1, B is mate 1 and the anchors are mate 2's.  Per direction and anchor the rule above applies
+ *   unchanged (window, strand, tiles, the banded Myers at E, the hit test, the least (ed, pos0) per anchor).  The pair takes the
+ *   least (nm(anchor) + ed, d, anchor index); that one hit is traced at E and kept only if start >= 0 and the record is
+ *   concordant with its anchor by its real CIGAR span; there is no fall-back to another anchor or to the other direction.
+ *   A kept record is added to B's list behind B's own records, which all stay.  Pairing then runs by its unchanged rule on the
+ *   lists: B's own records pair with nothing, so the chosen combination is (some a, the rescued record), the a of the least nm
+ *   sum, ties to the smaller a (not necessarily the anchor), and the pair is a proper one.  B's lines are the rescued record
+ *   first (0x2, TLEN, no 0x100), then its own records in their order with 0x100.  For MAPQ the rescued record is "rescued": q_x
+ *   = 0, so B's primary line gets min(qp, 40).
+ *   A rescued hit can lie at the place of one of B's own records whose own traceback span put it just outside [I, X]: no merge
+ *   by locus is done.  No second pass starts from a rescued mate.
+ * fem_dev_rescue_count counts every kept record, of either kind; fem_dev_rescue_discordant_count those of kind 2 (valid when
+ *   fem_dev_rescue_count is; 0 with the switch or rescue off).  fem_dev_fetch_records and the stats keep their single-end meaning. */
+int fem_dev_set_rescue_discordant(fem_dev *h, int slot, int on);
+int fem_dev_rescue_discordant_count(fem_dev *h, int slot, uint64_t *n);
+
 /* ---- mapping qualities (new; opt-in: the reference prints MAPQ 255, "not available", and so does every output without it) ----
  * fem_dev_set_mapq: on != 0: the slot's fem_dev_fetch_sam[_nowait] text and fem_dev_fetch_bam[_nowait] records carry MAPQ from
  *   the hit strata below; 0: 255 again.  fem_batch_records and fem_batch_pairs are unchanged (MAPQ is output text only).
@@ -493,7 +516,8 @@ int fem_dev_index_info(const fem_dev *h, char *buf, uint64_t cap);
  * 8 = seed selection kernel of the dense-index path (it runs beside the previous batch's kernel 0: its event time is
  * what it takes there, not what it would take alone);
  * 9 = the pairing kernel of a paired fem_dev_fetch_sam (fem_dev_set_pairs);
- * 10 = the mate rescue kernels in front of it (fem_dev_set_rescue; their host waits included);
+ * 10 = the mate rescue kernels in front of it (fem_dev_set_rescue; their host waits included; with
+ *   fem_dev_set_rescue_discordant the probe of the pairs whose records do not pair runs at their head, inside this id);
  * of fem_dev_fetch_bam: 11 = the BAM record kernels, 12 = the BGZF kernels;
  * 13 = the MAPQ kernel of a fem_dev_fetch_sam / fem_dev_fetch_bam with fem_dev_set_mapq on (one entry per call; the
  * pairing kernel's MAPQ part stays in 9);
