@@ -162,23 +162,10 @@ struct Slot {
   uint32_t n_cand = 0;
   std::vector<TimedLaunch> pending;
   std::unique_ptr<femt::Tail> tail;  // device mapping tail (fem_dev_fetch_records), created on first use
-  // pair mode (fem_dev_set_pairs): the batches are read pairs, read i and read n_reads / 2 + i
-  bool paired = false;
-  int32_t min_insert = 0, max_insert = 0;
-  uint64_t n_proper = 0;  // of the slot's last paired SAM text
-  // mate rescue (fem_dev_set_rescue): at rescue_edits edits
-  bool rescue = false;
-  int32_t rescue_edits = 0;
-  uint64_t n_rescued = 0;  // of the slot's last paired SAM text (or fetch_pairs)
-  bool rescue_discordant = false;      // fem_dev_set_rescue_discordant: pairs whose records do not pair are rescued too
-  uint64_t n_rescued_discordant = 0;   // ... and how many of the rescued records are theirs
-  bool mapq = false;  // fem_dev_set_mapq: MAPQ from the hit strata in the slot's SAM text and BAM records
-  bool unmapped = false;  // fem_dev_set_unmapped: a line for every read without a mapping in the slot's SAM text and BAM records
-  uint64_t n_unmapped = 0;  // ... and how many the slot's last text or BAM had
-  int32_t report_strata = -1, report_hits = -1;  // fem_dev_set_report: the line filter of the slot's SAM text and BAM records (-1: off)
-  uint64_t n_filtered = 0;  // ... and how many lines it left out of the slot's last text or BAM
-  std::string read_group;  // fem_dev_set_tags: the ID of the RG:Z tag on every line of the slot's SAM text and BAM records (empty: none)
-  bool hit_tags = false;   // ... and NH:i HI:i on every mapped line
+  // what the fem_dev_set_* functions made of the slot's SAM text and BAM records (opt.paired, fem_dev_set_pairs: the batches
+  // are read pairs, read i and read n_reads / 2 + i), and what its last text, BAM or fetch_pairs counted (fem_dev_*_count)
+  femt::LineOptions opt;
+  femt::LineCounts counts;
   // fem_dev_fetch_pairs: the records in output order (host copies, valid until the slot's next fetch_pairs)
   std::vector<uint16_t> pr_flag;
   std::vector<uint32_t> pr_tid, pr_pos0, pr_cigar_off, pr_cigar, pr_md_off;
@@ -1189,6 +1176,14 @@ int check_slot(fem_dev *h, int slot) {
   if (slot < 0 || slot >= kSlots) return fail(h, FEM_ERR_INVALID, "slot out of range");
   return FEM_OK;
 }
+// A setter or getter of one slot's output options and counts: `body` gets the slot, under the handle's lock.
+template <class Body>
+int with_slot(fem_dev *h, int slot, Body body) {
+  int rc = check_slot(h, slot);
+  if (rc) return rc;
+  FEM_LOCK(h);
+  return body(h->slot[slot]);
+}
 
 
 // ---- packed read transfer: host side in fem_pack.h (the device side is unpack_reads_kernel) ----
@@ -2085,15 +2080,16 @@ int fem_dev_sam_wait(fem_dev *h, int slot) {
   return s.tail->wait_text();  // (touches nothing but the slot's event: safe next to the thread that drives the handle)
 }
 
-// What mate rescue needs of the slot's batch and the reference (fetch time: the insert window's width is checked here).
-static int rescue_input(fem_dev *h, const Slot &s, femt::RescueInput *ri) {
-  if (!s.rescue) return FEM_OK;
-  if ((int64_t)s.max_insert - s.min_insert > 65536)
+// Pairs the records the slot's tail has just made, on `stream`, as `opt` (the slot's options, or a copy) says; mate rescue
+// reads the slot's batch and the reference (fetch time: the insert window's width is checked here).
+static int pair_records(fem_dev *h, Slot &s, const femt::LineOptions &opt, hipStream_t stream) {
+  if (s.n_reads & 1) return fail(h, FEM_ERR_INVALID, "a batch of read pairs holds an even number of reads");
+  if (opt.rescues() && (int64_t)opt.max_insert - opt.min_insert > 65536)
     return fail(h, FEM_ERR_UNSUPPORTED, "mate rescue searches insert windows of at most 65536 (max_insert - min_insert)");
-  ri->max_edits = s.rescue_edits, ri->discordant = s.rescue_discordant;
-  ri->bases = s.bases(), ri->read_off = s.d_off, ri->max_len = s.max_len;
-  ri->ref_raw = h->d_ref_raw, ri->ref_bytes = h->ref_bytes + 64, ri->seq_off = h->d_seq_off, ri->seq_len = h->d_seq_len;
-  return FEM_OK;
+  const femt::RescueInput ri{s.bases(), s.d_off, s.max_len, h->d_ref_raw, h->ref_bytes + 64, h->d_seq_off, h->d_seq_len};
+  std::string err;
+  const int rc = s.tail->pair(opt, ri, stream, &err);
+  return rc ? fail(h, rc, err) : FEM_OK;
 }
 
 // What the device tail reads of the slot's batch and of the index.
@@ -2120,19 +2116,18 @@ struct TailFront {
 
 // The fem_dev_kernel_time id of each stage of the device tail, and the slots that count it (nullptr: every fetch, a fetch of
 // records too; the others: texts).  A text's own stage, femt::kText, goes under its fetch's id: 7 SAM, 11 BAM.
-static bool slot_filters(const Slot &s) { return s.report_strata >= 0 || s.report_hits >= 1; }
 struct TailStage {
   femt::Stage stage;
   int id;
-  bool (*counted)(const Slot &);
+  bool (*counted)(const femt::LineOptions &);
 };
 static const TailStage kTailStages[] = {
     {femt::kOrder, 3, nullptr}, {femt::kTrace, 4, nullptr}, {femt::kCompact, 5, nullptr},
-    {femt::kPairing, 9, [](const Slot &s) { return s.paired; }},
-    {femt::kRescue, 10, [](const Slot &s) { return s.paired && s.rescue; }},
-    {femt::kMapq, 13, [](const Slot &s) { return s.mapq; }},  // (its events precede the text's sizing, which sam() and bam() wait for)
-    {femt::kUnmappedIndex, 14, [](const Slot &s) { return s.unmapped && !slot_filters(s); }},  // (as do these)
-    {femt::kFilterIndex, 15, slot_filters},  // (whose line index is the unmapped reads' too: no 14 then)
+    {femt::kPairing, 9, [](const femt::LineOptions &o) { return o.paired; }},
+    {femt::kRescue, 10, [](const femt::LineOptions &o) { return o.rescues(); }},
+    {femt::kMapq, 13, [](const femt::LineOptions &o) { return o.mapq; }},  // (its events precede the text's sizing, which sam() and bam() wait for)
+    {femt::kUnmappedIndex, 14, [](const femt::LineOptions &o) { return o.unmapped && !o.filters(); }},  // (as do these)
+    {femt::kFilterIndex, 15, [](const femt::LineOptions &o) { return o.filters(); }},  // (whose line index is the unmapped reads' too: no 14 then)
 };
 
 // Timing: counts the stages of the slot's last fetch once each, with their device time where the tail has one.  text_id: the
@@ -2141,7 +2136,7 @@ static void count_tail_stages(fem_dev *h, const Slot &s, bool text, int text_id)
   FEM_LOCK(h);  // (FEM map retires each slot's batches from a thread of its own)
   auto count = [&](femt::Stage stage, int id) { h->t_ms[id] += std::max(s.tail->stage_ms(stage), 0.f), h->t_n[id] += 1; };
   for (const auto &st : kTailStages)
-    if (!st.counted || (text && st.counted(s))) count(st.stage, st.id);
+    if (!st.counted || (text && st.counted(s.opt))) count(st.stage, st.id);
   if (text_id >= 0) count(femt::kText, text_id);
 }
 
@@ -2156,7 +2151,7 @@ static int tail_records(fem_dev *h, int slot, const void *out, bool copy_records
   f->ms_sync = since();
   if (!out) return fail(h, FEM_ERR_INVALID, "null result");
   Slot &s = h->slot[slot];
-  const bool text = !copy_records, paired = text && s.paired;
+  const bool text = !copy_records;
   if (text && !s.text_staged) return fail(h, FEM_ERR_STATE, "qualities and names of this batch were not committed (fem_dev_commit_text_stage)");
   if (device_quals && s.host_quals) return fail(h, FEM_ERR_STATE, "BAM records need the qualities on the device (fem_dev_commit_text_stage, not _names_stage)");
   if (text && !h->d_ref_names) return fail(h, FEM_ERR_STATE, "reference names must be uploaded first (fem_dev_upload_reference_names)");
@@ -2164,7 +2159,6 @@ static int tail_records(fem_dev *h, int slot, const void *out, bool copy_records
   if (!s.tail) s.tail.reset(new (std::nothrow) femt::Tail());
   if (!s.tail) return fail(h, FEM_ERR_NOMEM, "out of host memory");
   f->in = tail_input(h, s);
-  if (paired && (s.n_reads & 1)) return fail(h, FEM_ERR_INVALID, "a batch of read pairs holds an even number of reads");
   if (copy_records && s.out_stream) HIP_TRY(h, hipStreamSynchronize(s.out_stream));  // (a SAM text of this slot still being made reads the tail's arrays)
   f->stream = copy_records ? s.stream : out_stream_of(h, s);
   // the tail reads characters and offsets of the whole batch (traceback, rescue, SAM and BAM text)
@@ -2172,11 +2166,7 @@ static int tail_records(fem_dev *h, int slot, const void *out, bool copy_records
   if (s.sent_packed && f->stream != s.stream.s) HIP_TRY(h, hipStreamWaitEvent(f->stream, s.ev_chars, 0));  // (made on the slot's stream)
   std::string err;
   if ((rc = s.tail->run(f->in, f->stream, h->n_cu, h->tiny_buffers, &f->t, &err, copy_records))) return fail(h, rc, err);
-  if (paired) {
-    femt::RescueInput ri{};
-    if ((rc = rescue_input(h, s, &ri))) return rc;
-    if ((rc = s.tail->pair(s.min_insert, s.max_insert, f->stream, &err, s.rescue ? &ri : nullptr, s.mapq))) return fail(h, rc, err);
-  }
+  if (text && s.opt.paired && (rc = pair_records(h, s, s.opt, f->stream))) return rc;
   if (text) HIP_TRY(h, hipStreamWaitEvent(f->stream, s.ev_text_staged, 0));  // qualities and names came on the slot's text stream
   f->ms_run = since();
   if (copy_records && h->timing) count_tail_stages(h, s, false, -1);
@@ -2185,19 +2175,14 @@ static int tail_records(fem_dev *h, int slot, const void *out, bool copy_records
 
 // The names (and qualities, unless the caller keeps them: qual_hole) the slot's text is rendered with.
 static femt::SamInput sam_input(const fem_dev *h, const Slot &s) {
-  return {s.host_quals ? nullptr : s.d_quals, s.d_names, s.d_name_off, h->d_ref_names, h->d_ref_name_off, s.host_quals, s.mapq, s.unmapped, s.report_strata, s.report_hits,
-          s.read_group.empty() ? nullptr : s.read_group.c_str(), (uint32_t)s.read_group.size(), s.hit_tags};
+  return {s.host_quals ? nullptr : s.d_quals, s.d_names, s.d_name_off, h->d_ref_names, h->d_ref_name_off, s.host_quals};
 }
 
-// What follows a text's sam() / bam() (tag: the caller, for FEM_FETCH_TIMES): the pair counts, the event the slot's next text
+// What follows a text's sam() / bam() (tag: the caller, for FEM_FETCH_TIMES): the counts, the event the slot's next text
 // stage waits for (commit_text), the kernel times (count_tail_stages; text_id: the text's own id, < 0: it was not waited for).
 static int text_done(fem_dev *h, int slot, const TailFront &f, const char *tag, int text_id) {
   Slot &s = h->slot[slot];
-  s.n_proper = s.paired ? s.tail->n_proper() : 0;  // (sam() and bam() have waited for the stream once, after sizing the text)
-  s.n_rescued = s.paired ? s.tail->n_rescued() : 0;
-  s.n_rescued_discordant = s.paired ? s.tail->n_rescued_discordant() : 0;
-  s.n_unmapped = s.tail->n_unmapped();
-  s.n_filtered = s.tail->n_filtered();
+  s.counts = s.tail->counts();  // (sam() and bam() have waited for the stream once, after sizing the text)
   HIP_TRY(h, s.ev_text_order.create(hipEventDisableTiming));
   HIP_TRY(h, hipEventRecord(s.ev_text_order, f.stream));
   s.have_text_order = true;
@@ -2226,12 +2211,12 @@ static int fetch_sam(fem_dev *h, int slot, fem_batch_sam *out, bool wait) {
   Slot &s = h->slot[slot];
   femt::SamOutput text{};
   std::string err;
-  rc = s.tail->sam(f.in, sam_input(h, s), f.stream, h->n_cu, &text, &err, wait, &h->text_gate, s.paired);
+  rc = s.tail->sam(f.in, sam_input(h, s), s.opt, f.stream, h->n_cu, &text, &err, wait, &h->text_gate);
   if (rc) return fail(h, rc, err);
   if ((rc = text_done(h, slot, f, "fetch_sam", wait ? 7 : -1))) return rc;
   s.qual_at = text.qual_at;
   out->text = text.text, out->len = text.len, out->n_asserted = text.n_asserted;
-  out->n_reads = f.t.n_reads, out->n_records = f.t.n_records - s.n_filtered;  // (the filter drops lines of mapping records only)
+  out->n_reads = f.t.n_reads, out->n_records = f.t.n_records - s.counts.n_filtered;  // (the filter drops lines of mapping records only)
   memcpy(out->stats, s.stats, sizeof s.stats);
   return FEM_OK;
 }
@@ -2246,7 +2231,7 @@ static int fetch_bam(fem_dev *h, int slot, int level, fem_batch_bam *out, bool w
   femt::BamOutput bam{};
   float ms_bgzf = 0.f;
   std::string err;
-  rc = s.tail->bam(f.in, sam_input(h, s), level, f.stream, h->n_cu, &bam, &err, h->timing ? &ms_bgzf : nullptr, wait, &h->text_gate, s.paired);
+  rc = s.tail->bam(f.in, sam_input(h, s), s.opt, level, f.stream, h->n_cu, &bam, &err, h->timing ? &ms_bgzf : nullptr, wait, &h->text_gate);
   if (rc) return fail(h, rc, err);
   if ((rc = text_done(h, slot, f, "fetch_bam", 11))) return rc;  // (bam() has waited for its records' stage: the compressor does)
   if (h->timing) {
@@ -2255,7 +2240,7 @@ static int fetch_bam(fem_dev *h, int slot, int level, fem_batch_bam *out, bool w
   }
   s.qual_at = nullptr;
   out->data = bam.data, out->len = bam.len, out->raw_len = bam.raw_len, out->n_blocks = bam.n_blocks;
-  out->n_records = f.t.n_records - s.n_filtered, out->n_asserted = bam.n_asserted;
+  out->n_records = f.t.n_records - s.counts.n_filtered, out->n_asserted = bam.n_asserted;
   memcpy(out->stats, s.stats, sizeof s.stats);
   return FEM_OK;
 }
@@ -2289,144 +2274,76 @@ int fem_dev_bgzf_compress(fem_dev *h, const void *in, uint64_t n, int level, voi
   return FEM_OK;
 }
 
-int fem_dev_set_pairs(fem_dev *h, int slot, const fem_pair_params *pp) {
-  int rc = check_slot(h, slot);
-  if (rc) return rc;
-  FEM_LOCK(h);
-  Slot &s = h->slot[slot];
-  if (!pp) {
-    s.paired = false;
-    return FEM_OK;
-  }
-  if (pp->min_insert < 0 || pp->max_insert < pp->min_insert || pp->max_insert > (1 << 30))
-    return fail(h, FEM_ERR_INVALID, "insert size range out of bounds (0 <= min_insert <= max_insert <= 2^30)");
-  s.paired = true, s.min_insert = pp->min_insert, s.max_insert = pp->max_insert;
-  return FEM_OK;
+// One of the slot's counts (fem_dev_*_count); pair_mode: the pair counts are a slot's in pair mode only.
+static int line_count(fem_dev *h, int slot, uint64_t *out, uint64_t femt::LineCounts::*count, bool pair_mode) {
+  return with_slot(h, slot, [&](Slot &s) {
+    if (!out) return fail(h, FEM_ERR_INVALID, "null output pointer");
+    if (pair_mode && !s.opt.paired) return fail(h, FEM_ERR_STATE, "the slot is not in pair mode (fem_dev_set_pairs)");
+    *out = s.counts.*count;
+    return (int)FEM_OK;
+  });
 }
+int fem_dev_pair_count(fem_dev *h, int slot, uint64_t *n) { return line_count(h, slot, n, &femt::LineCounts::n_proper, true); }
+int fem_dev_rescue_count(fem_dev *h, int slot, uint64_t *n) { return line_count(h, slot, n, &femt::LineCounts::n_rescued, true); }
+int fem_dev_rescue_discordant_count(fem_dev *h, int slot, uint64_t *n) {
+  return line_count(h, slot, n, &femt::LineCounts::n_rescued_discordant, true);
+}
+int fem_dev_unmapped_count(fem_dev *h, int slot, uint64_t *n) { return line_count(h, slot, n, &femt::LineCounts::n_unmapped, false); }
+int fem_dev_filtered_count(fem_dev *h, int slot, uint64_t *n) { return line_count(h, slot, n, &femt::LineCounts::n_filtered, false); }
 
-int fem_dev_pair_count(fem_dev *h, int slot, uint64_t *n_proper) {
-  int rc = check_slot(h, slot);
-  if (rc) return rc;
-  if (!n_proper) return fail(h, FEM_ERR_INVALID, "null output pointer");
-  FEM_LOCK(h);
-  Slot &s = h->slot[slot];
-  if (!s.paired) return fail(h, FEM_ERR_STATE, "the slot is not in pair mode (fem_dev_set_pairs)");
-  *n_proper = s.n_proper;
-  return FEM_OK;
+int fem_dev_set_pairs(fem_dev *h, int slot, const fem_pair_params *pp) {
+  return with_slot(h, slot, [&](Slot &s) {
+    if (!pp) return s.opt.paired = false, (int)FEM_OK;
+    if (pp->min_insert < 0 || pp->max_insert < pp->min_insert || pp->max_insert > (1 << 30))
+      return fail(h, FEM_ERR_INVALID, "insert size range out of bounds (0 <= min_insert <= max_insert <= 2^30)");
+    s.opt.paired = true, s.opt.min_insert = pp->min_insert, s.opt.max_insert = pp->max_insert;
+    return (int)FEM_OK;
+  });
 }
 
 int fem_dev_set_rescue(fem_dev *h, int slot, const fem_rescue_params *rp) {
-  int rc = check_slot(h, slot);
-  if (rc) return rc;
-  FEM_LOCK(h);
-  Slot &s = h->slot[slot];
-  if (!rp) {
-    s.rescue = false;
-    return FEM_OK;
-  }
-  if (rp->max_edits < 0 || rp->max_edits > 15) return fail(h, FEM_ERR_INVALID, "rescue edit bound out of range (0 <= max_edits <= 15)");
-  s.rescue = true, s.rescue_edits = rp->max_edits;
-  return FEM_OK;
+  return with_slot(h, slot, [&](Slot &s) {
+    if (!rp) return s.opt.rescue = false, (int)FEM_OK;
+    if (rp->max_edits < 0 || rp->max_edits > 15) return fail(h, FEM_ERR_INVALID, "rescue edit bound out of range (0 <= max_edits <= 15)");
+    s.opt.rescue = true, s.opt.rescue_edits = rp->max_edits;
+    return (int)FEM_OK;
+  });
 }
 
 int fem_dev_set_rescue_discordant(fem_dev *h, int slot, int on) {
-  int rc = check_slot(h, slot);
-  if (rc) return rc;
-  FEM_LOCK(h);
-  h->slot[slot].rescue_discordant = on != 0;
-  return FEM_OK;
+  return with_slot(h, slot, [&](Slot &s) { return s.opt.rescue_discordant = on != 0, (int)FEM_OK; });
 }
-
-int fem_dev_rescue_discordant_count(fem_dev *h, int slot, uint64_t *n) {
-  int rc = check_slot(h, slot);
-  if (rc) return rc;
-  if (!n) return fail(h, FEM_ERR_INVALID, "null output pointer");
-  FEM_LOCK(h);
-  Slot &s = h->slot[slot];
-  if (!s.paired) return fail(h, FEM_ERR_STATE, "the slot is not in pair mode (fem_dev_set_pairs)");
-  *n = s.n_rescued_discordant;
-  return FEM_OK;
-}
-
 int fem_dev_set_mapq(fem_dev *h, int slot, int on) {
-  int rc = check_slot(h, slot);
-  if (rc) return rc;
-  FEM_LOCK(h);
-  h->slot[slot].mapq = on != 0;
-  return FEM_OK;
+  return with_slot(h, slot, [&](Slot &s) { return s.opt.mapq = on != 0, (int)FEM_OK; });
 }
-
 int fem_dev_set_unmapped(fem_dev *h, int slot, int on) {
-  int rc = check_slot(h, slot);
-  if (rc) return rc;
-  FEM_LOCK(h);
-  h->slot[slot].unmapped = on != 0;
-  return FEM_OK;
-}
-
-int fem_dev_unmapped_count(fem_dev *h, int slot, uint64_t *n) {
-  int rc = check_slot(h, slot);
-  if (rc) return rc;
-  if (!n) return fail(h, FEM_ERR_INVALID, "null output pointer");
-  FEM_LOCK(h);
-  *n = h->slot[slot].n_unmapped;
-  return FEM_OK;
+  return with_slot(h, slot, [&](Slot &s) { return s.opt.unmapped = on != 0, (int)FEM_OK; });
 }
 
 int fem_dev_set_report(fem_dev *h, int slot, const fem_report_params *rp) {
-  int rc = check_slot(h, slot);
-  if (rc) return rc;
-  FEM_LOCK(h);
-  Slot &s = h->slot[slot];
-  if (!rp) {
-    s.report_strata = s.report_hits = -1;
-    return FEM_OK;
-  }
-  if (rp->strata < -1 || rp->strata > 15) return fail(h, FEM_ERR_INVALID, "strata out of range (0 <= strata <= 15, or -1 for off)");
-  if (rp->max_hits < -1 || rp->max_hits == 0) return fail(h, FEM_ERR_INVALID, "hit limit out of range (max_hits >= 1, or -1 for off)");
-  s.report_strata = rp->strata, s.report_hits = rp->max_hits;
-  return FEM_OK;
+  return with_slot(h, slot, [&](Slot &s) {
+    if (!rp) return s.opt.strata = s.opt.max_hits = -1, (int)FEM_OK;
+    if (rp->strata < -1 || rp->strata > 15) return fail(h, FEM_ERR_INVALID, "strata out of range (0 <= strata <= 15, or -1 for off)");
+    if (rp->max_hits < -1 || rp->max_hits == 0) return fail(h, FEM_ERR_INVALID, "hit limit out of range (max_hits >= 1, or -1 for off)");
+    s.opt.strata = rp->strata, s.opt.max_hits = rp->max_hits;
+    return (int)FEM_OK;
+  });
 }
 
 int fem_dev_set_tags(fem_dev *h, int slot, const fem_tag_params *tp) {
-  int rc = check_slot(h, slot);
-  if (rc) return rc;
-  FEM_LOCK(h);
-  Slot &s = h->slot[slot];
-  if (!tp) {
-    s.read_group.clear(), s.hit_tags = false;
-    return FEM_OK;
-  }
-  size_t n = 0;
-  if (tp->read_group) {
-    n = strnlen(tp->read_group, 256);
-    if (n < 1 || n > 255) return fail(h, FEM_ERR_INVALID, "read group ID out of range (1 to 255 bytes)");
-    for (size_t i = 0; i < n; ++i)
-      if (tp->read_group[i] < ' ' || tp->read_group[i] > '~') return fail(h, FEM_ERR_INVALID, "read group ID holds a byte outside [ -~]");
-  }
-  s.read_group.assign(tp->read_group ? tp->read_group : "", n);
-  s.hit_tags = tp->hit_tags != 0;
-  return FEM_OK;
-}
-
-int fem_dev_filtered_count(fem_dev *h, int slot, uint64_t *n) {
-  int rc = check_slot(h, slot);
-  if (rc) return rc;
-  if (!n) return fail(h, FEM_ERR_INVALID, "null output pointer");
-  FEM_LOCK(h);
-  *n = h->slot[slot].n_filtered;
-  return FEM_OK;
-}
-
-int fem_dev_rescue_count(fem_dev *h, int slot, uint64_t *n_rescued) {
-  int rc = check_slot(h, slot);
-  if (rc) return rc;
-  if (!n_rescued) return fail(h, FEM_ERR_INVALID, "null output pointer");
-  FEM_LOCK(h);
-  Slot &s = h->slot[slot];
-  if (!s.paired) return fail(h, FEM_ERR_STATE, "the slot is not in pair mode (fem_dev_set_pairs)");
-  *n_rescued = s.n_rescued;
-  return FEM_OK;
+  return with_slot(h, slot, [&](Slot &s) {
+    if (!tp) return s.opt.read_group.clear(), s.opt.hit_tags = false, (int)FEM_OK;
+    size_t n = 0;
+    if (tp->read_group) {
+      n = strnlen(tp->read_group, 256);
+      if (n < 1 || n > 255) return fail(h, FEM_ERR_INVALID, "read group ID out of range (1 to 255 bytes)");
+      for (size_t i = 0; i < n; ++i)
+        if (tp->read_group[i] < ' ' || tp->read_group[i] > '~') return fail(h, FEM_ERR_INVALID, "read group ID holds a byte outside [ -~]");
+    }
+    s.opt.read_group.assign(tp->read_group ? tp->read_group : "", n);
+    s.opt.hit_tags = tp->hit_tags != 0;
+    return (int)FEM_OK;
+  });
 }
 
 // The records of fem_dev_fetch_records, paired on the device (pair_kernel) and put in output order here on the host: an
@@ -2435,17 +2352,17 @@ int fem_dev_fetch_pairs(fem_dev *h, int slot, fem_batch_pairs *out) {
   int rc = check_slot(h, slot);
   if (rc) return rc;
   if (!out) return fail(h, FEM_ERR_INVALID, "null result");
-  if (!h->slot[slot].paired) return fail(h, FEM_ERR_STATE, "the slot is not in pair mode (fem_dev_set_pairs)");
-  if ((rc = fem_dev_sync(h, slot))) return rc;
-  Slot &s = h->slot[slot];
-  if (s.n_reads & 1) return fail(h, FEM_ERR_INVALID, "a batch of read pairs holds an even number of reads");
-  femt::RescueInput ri{};
-  if ((rc = rescue_input(h, s, &ri))) return rc;
+  if (!h->slot[slot].opt.paired) return fail(h, FEM_ERR_STATE, "the slot is not in pair mode (fem_dev_set_pairs)");
   fem_batch_records rec{};
   if ((rc = fem_dev_fetch_records(h, slot, &rec))) return rc;
+  Slot &s = h->slot[slot];
+  // without the MAPQ bytes: the arrays of this path have no MAPQ column, and a later text must not find pair_mapq set by a
+  // pair() that was not its own
+  femt::LineOptions opt = s.opt;
+  opt.mapq = false;
+  if ((rc = pair_records(h, s, opt, s.stream))) return rc;
   std::string err;
   femt::PairOutput po{};
-  if ((rc = s.tail->pair(s.min_insert, s.max_insert, s.stream, &err, s.rescue ? &ri : nullptr))) return fail(h, rc, err);
   if ((rc = s.tail->pair_fetch(s.stream, &po, &err))) return fail(h, rc, err);
   const uint64_t nr = po.n_records;
   s.pr_flag.assign(po.flag, po.flag + nr);
@@ -2466,7 +2383,7 @@ int fem_dev_fetch_pairs(fem_dev *h, int slot, fem_batch_pairs *out) {
     }
     s.pr_cigar_off[k + 1] = (uint32_t)s.pr_cigar.size(), s.pr_md_off[k + 1] = (uint32_t)s.pr_md.size();
   }
-  s.n_proper = po.n_proper, s.n_rescued = po.n_rescued, s.n_rescued_discordant = s.tail->n_rescued_discordant();
+  s.counts = s.tail->counts();  // (pair_fetch() has waited for the stream)
   out->n_pairs = po.n_pairs, out->n_records = nr;
   out->rec_begin = po.pair_begin, out->flag = s.pr_flag.data(), out->tid = s.pr_tid.data(), out->pos0 = s.pr_pos0.data();
   out->nm = s.pr_nm.data(), out->cigar_off = s.pr_cigar_off.data(), out->cigar = s.pr_cigar.data();

@@ -2589,19 +2589,19 @@ struct Tail::Impl {
   DevBuf<uint32_t> perm, mtid, mpos0, pair_begin, pair_ctl;
   DevBuf<uint16_t> pflag;
   DevBuf<int32_t> tlen;
-  // MAPQ (SamInput::mapq): per read (single-end), per line (pair(): pair_kernel<true>'s bytes, then the MAPQ)
+  // MAPQ (LineOptions::mapq): per read (single-end), per line (pair(): pair_kernel<true>'s bytes, then the MAPQ)
   DevBuf<uint8_t> q_read, lmq;
-  // lines for unmapped reads (SamInput::unmapped): the marks, their scan, each line's source, the line count
-  // (the line filter, SamInput::strata / max_hits, uses the same four: its counts, their scan, the sources, the line count)
+  // lines for unmapped reads (LineOptions::unmapped): the marks, their scan, each line's source, the line count
+  // (the line filter, LineOptions::strata / max_hits, uses the same four: its counts, their scan, the sources, the line count)
   DevBuf<uint32_t> u_cnt, u_before, usrc, u_ctl;
-  // the RG tag (SamInput::read_group): the ID on the device, the pinned copy it came from, and what that holds
+  // the RG tag (LineOptions::read_group): the ID on the device, the pinned copy it came from, and what that holds
   DevBuf<uint8_t> rg;
   PinBuf<uint8_t> h_rg;
   std::string rg_id;
   PinBuf<uint32_t> h_perm, h_mtid, h_mpos0, h_pair_begin, h_pair_ctl;
   PinBuf<uint16_t> h_pflag;
   PinBuf<int32_t> h_tlen;
-  // mate rescue (pair() with a RescueInput): candidates, jobs, best hits, the tracebacks' staging, the kept flags and their scans
+  // mate rescue (pair() with LineOptions::rescue): candidates, jobs, best hits, the tracebacks' staging, the kept flags and their scans
   DevBuf<uint32_t> r_ctl, r_cand, r_jobs, r_ops, r_rec, r_ovf, r_o_ops, r_kept, r_scan;
   DevBuf<unsigned long long> r_best;
   DevBuf<uint8_t> r_md, r_o_md, r_scan_tmp, r_disc;
@@ -2617,9 +2617,10 @@ struct Tail::Impl {
   uint32_t last_n = 0, last_nr = 0;  // what the last run() left on the device
   bool paired = false;               // pair() has run on it
   uint32_t n_resc = 0;               // rescued records the last pair() appended behind run()'s (records last_nr ..)
-  uint32_t n_resc_disc = 0;          // ... those of pairs with records on both sides among them (RescueInput::discordant)
+  uint32_t n_resc_disc = 0;          // ... those of pairs with records on both sides among them (LineOptions::rescue_discordant)
   bool pair_mapq = false;            // the last pair() left its MAPQ bytes in lmq, not yet made MAPQ by a text
   bool filtered = false;             // the last text went through the line filter
+  bool um_kernels = false;           // ... its kernels are the kUnm instances (lines for unmapped reads, or the filter's index)
   uint32_t n_unm = 0;                // lines for unmapped reads in the last text
   uint32_t n_base_last = 0;          // the lines the last text had before the filter and without the unmapped reads'
   uint32_t n_filtered = 0;           // lines the filter left out of the last text
@@ -2669,38 +2670,38 @@ struct Tail::Impl {
   }
 
   // sam() and bam(): the lines of run()'s records, or of pair()'s (rescued records included).  Fills *p (all but the text and
-  // qual_at); names.mapq: first the MAPQ kernel (stage kMapq); then stage kText begins: each line's length (bad_name: as BAM, a
+  // qual_at); opt.mapq: first the MAPQ kernel (stage kMapq); then stage kText begins: each line's length (bad_name: as BAM, a
   // name over 254 characters setting it; else as SAM), their scan into line_off, the count of asserted records to h_ctl[2].
-  // names.unmapped: the line index first (stage kUnmappedIndex).  The line count is known on the device alone then:
+  // opt.unmapped: the line index first (stage kUnmappedIndex).  The line count is known on the device alone then:
   // p->n_records bounds it (records + reads; the lengths behind the last line are zero, so line_off[p->n_records] is the text's
   // size all the same) and the count comes to h_ctl[8]; counted() puts it into p->n_records once the stream has been waited for.
-  // names.strata / names.max_hits (the line filter): the line index is report_kernel's instead (stage kFilterIndex),
-  // unmapped reads' lines included where names.unmapped asks for them; the count comes home the same way, the unmapped slots'
-  // to h_ctl[9].  The text and BAM kernels are the kUnm instances then, with or without names.unmapped: without it u_base lies
+  // opt.strata / opt.max_hits (the line filter): the line index is report_kernel's instead (stage kFilterIndex),
+  // unmapped reads' lines included where opt.unmapped asks for them; the count comes home the same way, the unmapped slots'
+  // to h_ctl[9].  The text and BAM kernels are the kUnm instances then, with or without opt.unmapped: without it u_base lies
   // above every source and pair_begin is nullptr (mate_cols), so that no line takes a shape it has not without the filter.
-  // names.read_group / names.hit_tags (the tags behind MD:Z): the ID goes to the device when it is another than the last text's;
+  // opt.read_group / opt.hit_tags (the tags behind MD:Z): the ID goes to the device when it is another than the last text's;
   // NH and HI read the slots' line ranges that are there already (hit_tags(), above): the filter's scan, or the index it began from.
-  int lines(const TailInput &in, const SamInput &names, bool pair_order, uint32_t *bad_name, hipStream_t stream, int n_cu, SamParams *p,
-              std::string *err) {
+  int lines(const TailInput &in, const SamInput &names, const LineOptions &opt, uint32_t *bad_name, hipStream_t stream, int n_cu,
+            SamParams *p, std::string *err) {
+    const bool pair_order = opt.paired, report = opt.filters();
     if (pair_order && !paired) {
       if (err) *err = "the records were not paired (Tail::pair)";
       return FEM_ERR_STATE;
     }
     const uint32_t n_base = last_nr + (pair_order ? n_resc : 0u);
-    if (names.unmapped && (uint64_t)n_base + last_n > 0xFFFFFFF0ull) {
+    if (opt.unmapped && (uint64_t)n_base + last_n > 0xFFFFFFF0ull) {
       if (err) *err = "more than 2^32 lines in one batch; split the batch";
       return FEM_ERR_UNSUPPORTED;
     }
-    const uint32_t nr = n_base + (names.unmapped ? last_n : 0u);
+    const uint32_t nr = n_base + (opt.unmapped ? last_n : 0u);
     const size_t r1 = (size_t)nr + 1, n1 = (size_t)last_n + 1;
-    const bool report = names.strata >= 0 || names.max_hits >= 1;
     not_run({kText, kMapq, kUnmappedIndex, kFilterIndex});
     TAIL_TRY(line_len.ensure(r1));
     TAIL_TRY(line_off.ensure(r1));
     TAIL_TRY(h_ctl.ensure(12));
     size_t need = 16;
     TAIL_TRY(scan_need(&need, line_len.get(), line_off.get(), 0ull, r1, rocprim::plus<unsigned long long>()));
-    if (names.unmapped || report) {
+    if (opt.unmapped || report) {
       TAIL_TRY(u_cnt.ensure(n1));
       TAIL_TRY(u_before.ensure(n1));
       TAIL_TRY(usrc.ensure(std::max<size_t>(nr, 1)));
@@ -2719,29 +2720,30 @@ struct Tail::Impl {
       p->tlen = tlen;
     }
     p->n_reads = last_n;
-    if (names.read_group && names.rg_len) {
-      if (!rg || rg_id.size() != names.rg_len || memcmp(rg_id.data(), names.read_group, names.rg_len) != 0) {
+    if (!opt.read_group.empty()) {
+      const size_t rg_len = opt.read_group.size();
+      if (!rg || rg_id != opt.read_group) {
         TAIL_TRY(rg.ensure(256));
         TAIL_TRY(h_rg.ensure(256));
         TAIL_TRY(hipStreamSynchronize(stream));  // (the ID before may still be on its way out of h_rg, or in a text kernel's hands)
-        memcpy(h_rg.get(), names.read_group, names.rg_len);
-        TAIL_TRY(hipMemcpyAsync(rg, h_rg, names.rg_len, hipMemcpyHostToDevice, stream));
-        rg_id.assign(names.read_group, names.rg_len);
+        memcpy(h_rg.get(), opt.read_group.data(), rg_len);
+        TAIL_TRY(hipMemcpyAsync(rg, h_rg, rg_len, hipMemcpyHostToDevice, stream));
+        rg_id = opt.read_group;
       }
-      p->rg = rg, p->rg_len = names.rg_len;
+      p->rg = rg, p->rg_len = (uint32_t)rg_len;
     }
-    if (names.hit_tags) {
+    if (opt.hit_tags) {
       p->hit_tags = 1u, p->hit_by_line = report ? 1u : 0u;
       p->hit_begin = report ? u_before : pair_order ? pair_begin : rec_begin;
     }
     n_unm = 0;
-    filtered = report, n_filtered = 0, n_base_last = n_base;
+    filtered = report, um_kernels = opt.unmapped || report, n_filtered = 0, n_base_last = n_base;
     if (report) {
       ReportParams f{};
       f.n_reads = last_n, f.n_base = n_base, f.begin = pair_order ? pair_begin : rec_begin;
       f.nm = nm, f.perm = pair_order ? perm : nullptr;
-      f.strata = names.strata >= 0 ? (uint32_t)names.strata : kReportOff, f.max_hits = names.max_hits >= 1 ? (uint32_t)names.max_hits : kReportOff;
-      f.unmapped = names.unmapped ? 1u : 0u;
+      f.strata = opt.strata >= 0 ? (uint32_t)opt.strata : kReportOff, f.max_hits = opt.max_hits >= 1 ? (uint32_t)opt.max_hits : kReportOff;
+      f.unmapped = opt.unmapped ? 1u : 0u;
       f.cnt = u_cnt, f.before = u_before, f.usrc = usrc, f.n_lines = u_ctl;
       const dim3 grid((last_n + 256u) / 256u);
       TAIL_TRY(span[kFilterIndex].begin(stream));
@@ -2753,9 +2755,9 @@ struct Tail::Impl {
       TAIL_TRY(hipGetLastError());
       TAIL_TRY(span[kFilterIndex].end(stream));
       TAIL_TRY(hipMemcpyAsync(h_ctl + 8, u_ctl, 8, hipMemcpyDeviceToHost, stream));
-      p->usrc = usrc, p->u_base = names.unmapped ? n_base : kNoMate, p->n_reads = last_n, p->u_lines = u_ctl;
-      p->pair_begin = names.unmapped ? pair_begin : nullptr;
-    } else if (names.unmapped) {
+      p->usrc = usrc, p->u_base = opt.unmapped ? n_base : kNoMate, p->n_reads = last_n, p->u_lines = u_ctl;
+      p->pair_begin = opt.unmapped ? pair_begin : nullptr;
+    } else if (opt.unmapped) {
       UlineParams u{};
       u.n_reads = last_n, u.n_base = n_base, u.paired = pair_order ? 1u : 0u;
       u.begin = pair_order ? pair_begin : rec_begin;
@@ -2774,7 +2776,7 @@ struct Tail::Impl {
       p->usrc = usrc, p->u_base = n_base, p->n_reads = last_n, p->u_lines = u_ctl;
       p->pair_begin = pair_begin;
     }
-    if (names.mapq) {
+    if (opt.mapq) {
       if (pair_order && !pair_mapq) {
         if (err) *err = "the records were paired without MAPQ (Tail::pair)";
         return FEM_ERR_STATE;
@@ -2800,24 +2802,23 @@ struct Tail::Impl {
     if (bad_name) TAIL_TRY(hipMemsetAsync(bad_name, 0, 4, stream));
     TAIL_TRY(span[kText].begin(stream));
     const dim3 len_grid(std::max<uint32_t>(1u, std::min<uint32_t>((nr + 256u) / 256u, (uint32_t)n_cu * 16u)));
-    const bool um = names.unmapped || report;
     if (bad_name)
-      hipLaunchKernelGGL(TEXT_KERNEL(bam_len_kernel, pair_order, um), len_grid, dim3(256), 0, stream, *p, last_n, bad_name);
+      hipLaunchKernelGGL(TEXT_KERNEL(bam_len_kernel, pair_order, um_kernels), len_grid, dim3(256), 0, stream, *p, last_n, bad_name);
     else
-      hipLaunchKernelGGL(TEXT_KERNEL(sam_len_kernel, pair_order, um), len_grid, dim3(256), 0, stream, *p);
+      hipLaunchKernelGGL(TEXT_KERNEL(sam_len_kernel, pair_order, um_kernels), len_grid, dim3(256), 0, stream, *p);
     TAIL_TRY(hipGetLastError());
     TAIL_TRY(scan(line_len.get(), line_off.get(), 0ull, r1, rocprim::plus<unsigned long long>(), stream));
     TAIL_TRY(hipMemcpyAsync(h_ctl + 2, ctl + 2, 4, hipMemcpyDeviceToHost, stream));
     return FEM_OK;
   }
   // after lines() and a wait for its stream: the number of lines (into p->n_records, which bounded it), n_unm
-  uint32_t counted(const SamInput &names, SamParams *p) {
+  uint32_t counted(const LineOptions &opt, SamParams *p) {
     if (filtered) {  // (what the filter kept, the unmapped reads' lines among them)
       const uint32_t n_lines = std::min(h_ctl[8], p->n_records);
-      n_unm = names.unmapped ? std::min(h_ctl[9], n_lines) : 0u;
+      n_unm = opt.unmapped ? std::min(h_ctl[9], n_lines) : 0u;
       n_filtered = n_base_last + n_unm - n_lines;
       p->n_records = n_lines;
-    } else if (names.unmapped) {
+    } else if (opt.unmapped) {
       const uint32_t n_lines = std::min(h_ctl[8], p->n_records);
       n_unm = n_lines - p->u_base;
       p->n_records = n_lines;
@@ -3114,8 +3115,8 @@ int Tail::wait_text() {
   return hipEventSynchronize(impl_->ev_text) == hipSuccess ? FEM_OK : FEM_ERR_HIP;
 }
 
-int Tail::sam(const TailInput &in, const SamInput &names, hipStream_t stream, int n_cu, SamOutput *out, std::string *err, bool wait,
-              TextGate *gate, bool paired) {
+int Tail::sam(const TailInput &in, const SamInput &names, const LineOptions &opt, hipStream_t stream, int n_cu, SamOutput *out,
+              std::string *err, bool wait, TextGate *gate) {
   if (!impl_ || !out) return FEM_ERR_STATE;
   Impl &m = *impl_;
   SamParams p{};
@@ -3127,19 +3128,19 @@ int Tail::sam(const TailInput &in, const SamInput &names, hipStream_t stream, in
     TAIL_TRY(hipMemsetAsync(m.qual_at, 0xFF, n_reads1 * 8, stream));
     p.qual_at = m.qual_at, p.qual_hole = 1u;
   }
-  int rc = m.lines(in, names, paired, nullptr, stream, n_cu, &p, err);
+  int rc = m.lines(in, names, opt, nullptr, stream, n_cu, &p, err);
   if (rc) return rc;
   unsigned long long *h_total = (unsigned long long *)(m.h_ctl + 6);
   TAIL_TRY(hipMemcpyAsync(h_total, m.line_off + p.n_records, 8, hipMemcpyDeviceToHost, stream));
   TAIL_TRY(hipStreamSynchronize(stream));
-  const uint32_t nr = m.counted(names, &p);
+  const uint32_t nr = m.counted(opt, &p);
   const uint64_t total = *h_total;
   TAIL_TRY(m.text.ensure(std::max<size_t>((size_t)total, 16)));
   TAIL_TRY(m.h_text.ensure(std::max<size_t>((size_t)total + total / 8, 1u << 20)));
   if (nr) {
     p.text = m.text;
     const uint32_t blocks = (nr + 255u) / 256u;  // a wave per 64 records
-    hipLaunchKernelGGL(TEXT_KERNEL(sam_write_kernel, paired, names.unmapped || m.filtered), dim3(blocks), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL(TEXT_KERNEL(sam_write_kernel, opt.paired, m.um_kernels), dim3(blocks), dim3(256), 0, stream, p);
     TAIL_TRY(hipGetLastError());
   }
   TAIL_TRY(m.span[kText].end(stream));
@@ -3150,8 +3151,8 @@ int Tail::sam(const TailInput &in, const SamInput &names, hipStream_t stream, in
   return FEM_OK;
 }
 
-int Tail::bam(const TailInput &in, const SamInput &names, int level, hipStream_t stream, int n_cu, BamOutput *out, std::string *err,
-              float *bgzf_ms, bool wait, TextGate *gate, bool paired) {
+int Tail::bam(const TailInput &in, const SamInput &names, const LineOptions &opt, int level, hipStream_t stream, int n_cu, BamOutput *out,
+              std::string *err, float *bgzf_ms, bool wait, TextGate *gate) {
   if (!impl_ || !out) return FEM_ERR_STATE;
   Impl &m = *impl_;
   if (!names.quals || names.qual_hole) {
@@ -3161,7 +3162,7 @@ int Tail::bam(const TailInput &in, const SamInput &names, int level, hipStream_t
   TAIL_TRY(m.bam_ctl.ensure(4));
   SamParams p{};
   uint32_t *bad_name = m.bam_ctl;
-  int rc = m.lines(in, names, paired, bad_name, stream, n_cu, &p, err);
+  int rc = m.lines(in, names, opt, bad_name, stream, n_cu, &p, err);
   if (rc) return rc;
   const uint32_t n_bound = p.n_records;
   // the record offsets come home with the total: the member cuts are made here
@@ -3172,12 +3173,12 @@ int Tail::bam(const TailInput &in, const SamInput &names, int level, hipStream_t
     if (err) *err = "the batch holds a read name over 254 characters: not writable as BAM (l_read_name is one byte)";
     return FEM_ERR_UNSUPPORTED;
   }
-  const uint32_t nr = m.counted(names, &p);
+  const uint32_t nr = m.counted(opt, &p);
   const uint64_t total = m.h_line_off[nr];
   TAIL_TRY(m.text.ensure(std::max<size_t>((size_t)total, 16)));
   if (nr) {
     p.text = m.text;
-    hipLaunchKernelGGL(TEXT_KERNEL(bam_write_kernel, paired, names.unmapped || m.filtered), dim3((nr + 3u) / 4u), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL(TEXT_KERNEL(bam_write_kernel, opt.paired, m.um_kernels), dim3((nr + 3u) / 4u), dim3(256), 0, stream, p);
     TAIL_TRY(hipGetLastError());
   }
   TAIL_TRY(m.span[kText].end(stream));
@@ -3193,7 +3194,7 @@ int Tail::bam(const TailInput &in, const SamInput &names, int level, hipStream_t
   return FEM_OK;
 }
 
-int Tail::pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::string *err, const RescueInput *rescue, bool mapq) {
+int Tail::pair(const LineOptions &opt, const RescueInput &rescue, hipStream_t stream, std::string *err) {
   if (!impl_) return FEM_ERR_STATE;
   Impl &m = *impl_;
   const uint32_t n = m.last_n, nr = m.last_nr, np = n / 2u;
@@ -3204,28 +3205,28 @@ int Tail::pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::
   m.n_resc = 0, m.n_resc_disc = 0, m.pair_mapq = false;
   m.not_run({kRescue, kPairing});
   const uint32_t *resc_before = nullptr;
-  if (rescue && np) {  // ---- mate rescue: the kept records behind run()'s, resc_before their exclusive scan over the pairs ----
-    const int32_t E = rescue->max_edits;
+  if (opt.rescues() && np) {  // ---- mate rescue: the kept records behind run()'s, resc_before their exclusive scan over the pairs ----
+    const int32_t E = opt.rescue_edits;
     TAIL_TRY(m.r_ctl.ensure(8));
     TAIL_TRY(m.h_r_ctl.ensure(8));
     TAIL_TRY(m.r_cand.ensure((size_t)np));
     TAIL_TRY(m.r_best.ensure((size_t)np));
-    TAIL_TRY(m.r_jobs.ensure((size_t)np * kRescueAnchors * (rescue->discordant ? 2u : 1u)));  // (both directions)
-    if (rescue->discordant) TAIL_TRY(m.r_disc.ensure((size_t)np));
+    TAIL_TRY(m.r_jobs.ensure((size_t)np * kRescueAnchors * (opt.rescue_discordant ? 2u : 1u)));  // (both directions)
+    if (opt.rescue_discordant) TAIL_TRY(m.r_disc.ensure((size_t)np));
     const uint32_t *h_tot = m.h_ctl;  // run() left its CIGAR and MD totals in h_ctl[4], h_ctl[5]
     RescueParams r{};
-    r.n_pairs = np, r.n_records = nr, r.E = E, r.min_insert = min_insert, r.max_insert = max_insert;
-    r.bases = rescue->bases, r.read_off = rescue->read_off, r.ref_raw = rescue->ref_raw, r.ref_bytes = rescue->ref_bytes;
-    r.seq_off = rescue->seq_off, r.seq_len = rescue->seq_len;
+    r.n_pairs = np, r.n_records = nr, r.E = E, r.min_insert = opt.min_insert, r.max_insert = opt.max_insert;
+    r.bases = rescue.bases, r.read_off = rescue.read_off, r.ref_raw = rescue.ref_raw, r.ref_bytes = rescue.ref_bytes;
+    r.seq_off = rescue.seq_off, r.seq_len = rescue.seq_len;
     r.ctl = m.r_ctl, r.cand_pair = m.r_cand, r.jobs = m.r_jobs;
     r.best = m.r_best;
     r.cig_total = h_tot[4], r.md_total = h_tot[5];
     m.bind_records(&r);
     TAIL_TRY(m.span[kRescue].begin(stream));
     TAIL_TRY(hipMemsetAsync(m.r_ctl, 0, 32, stream));
-    if (rescue->discordant) {  // the pairs with records on both sides that do not pair are candidates too
+    if (opt.rescue_discordant) {  // the pairs with records on both sides that do not pair are candidates too
       PairParams q{};
-      q.n_pairs = np, q.min_insert = min_insert, q.max_insert = max_insert;
+      q.n_pairs = np, q.min_insert = opt.min_insert, q.max_insert = opt.max_insert;
       m.bind_pairing(&q);
       hipLaunchKernelGGL(pair_probe_kernel, dim3((np + 255u) / 256u), dim3(256), 0, stream, q, m.r_disc.get());
       TAIL_TRY(hipGetLastError());
@@ -3240,7 +3241,7 @@ int Tail::pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::
     if (n_cand) {
       // first pass: the staging of a walk of E errors on canonical characters (<= 2E + 2 runs; MD <= 2E + 1 numbers of <= 4
       // digits and 3E characters); overflow pass: the longest walk, as trace_kernel's (every column an MD character)
-      r.max_len = std::max<uint32_t>(rescue->max_len, 1);
+      r.max_len = std::max<uint32_t>(rescue.max_len, 1);
       TracePlan plan;  // (trace_kernel's, at E)
       if (int rc = trace_plan(r.max_len, E, &plan, err)) return rc;
       const OverflowCaps o_cap = overflow_caps(r.max_len, E);
@@ -3313,7 +3314,7 @@ int Tail::pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::
   TAIL_TRY(m.mtid.ensure(lines));
   TAIL_TRY(m.mpos0.ensure(lines));
   TAIL_TRY(m.tlen.ensure(lines));
-  if (mapq) TAIL_TRY(m.lmq.ensure(lines));
+  if (opt.mapq) TAIL_TRY(m.lmq.ensure(lines));
   TAIL_TRY(m.pair_begin.ensure((size_t)n + 1));
   TAIL_TRY(m.pair_ctl.ensure(4));
   TAIL_TRY(m.h_pair_ctl.ensure(4));
@@ -3321,28 +3322,31 @@ int Tail::pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::
   TAIL_TRY(hipMemsetAsync(m.pair_ctl, 0, 16, stream));
   if (np) {
     PairParams q{};
-    q.n_pairs = np, q.min_insert = min_insert, q.max_insert = max_insert;
+    q.n_pairs = np, q.min_insert = opt.min_insert, q.max_insert = opt.max_insert;
     m.bind_pairing(&q);
     q.perm = m.perm, q.pflag = m.pflag, q.mtid = m.mtid, q.mpos0 = m.mpos0;
     q.tlen = m.tlen, q.pair_begin = m.pair_begin, q.n_proper = m.pair_ctl;
     q.resc_before = resc_before, q.resc_first = nr, q.s_read = m.s_read;
-    q.lmq = mapq ? m.lmq : nullptr;
-    hipLaunchKernelGGL(mapq ? pair_kernel<true> : pair_kernel<false>, dim3((np + 255u) / 256u), dim3(256), 0, stream, q);
+    q.lmq = opt.mapq ? m.lmq : nullptr;
+    hipLaunchKernelGGL(opt.mapq ? pair_kernel<true> : pair_kernel<false>, dim3((np + 255u) / 256u), dim3(256), 0, stream, q);
     TAIL_TRY(hipGetLastError());
   } else {
     TAIL_TRY(hipMemsetAsync(m.pair_begin, 0, 4, stream));
   }
   TAIL_TRY(m.span[kPairing].end(stream));
   TAIL_TRY(hipMemcpyAsync(m.h_pair_ctl, m.pair_ctl, 4, hipMemcpyDeviceToHost, stream));
-  m.paired = true, m.pair_mapq = mapq;
+  m.paired = true, m.pair_mapq = opt.mapq;
   return FEM_OK;
 }
 
-uint64_t Tail::n_rescued() const { return impl_ && impl_->paired ? impl_->n_resc : 0; }
-uint64_t Tail::n_rescued_discordant() const { return impl_ && impl_->paired ? impl_->n_resc_disc : 0; }
-uint64_t Tail::n_unmapped() const { return impl_ ? impl_->n_unm : 0; }
-uint64_t Tail::n_filtered() const { return impl_ ? impl_->n_filtered : 0; }
-uint64_t Tail::n_proper() const { return impl_ && impl_->paired && impl_->h_pair_ctl ? impl_->h_pair_ctl[0] : 0; }
+LineCounts Tail::counts() const {
+  LineCounts c;
+  if (!impl_) return c;
+  const Impl &m = *impl_;
+  if (m.paired) c.n_proper = m.h_pair_ctl ? m.h_pair_ctl[0] : 0, c.n_rescued = m.n_resc, c.n_rescued_discordant = m.n_resc_disc;
+  c.n_unmapped = m.n_unm, c.n_filtered = m.n_filtered;
+  return c;
+}
 
 int Tail::pair_fetch(hipStream_t stream, PairOutput *out, std::string *err) {
   if (!impl_ || !impl_->paired || !out) return FEM_ERR_STATE;

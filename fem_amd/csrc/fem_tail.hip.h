@@ -54,20 +54,13 @@ struct TailOutput {  // pinned host memory owned by the Tail object, valid until
 
 // ---- SAM text on the device: the records of the last run() rendered as the reference's output lines
 //      (generate_bam1_t + htslib's SAM writer, src/align.c:546-632, src/output_queue.c:93-116) ----
-struct SamInput {  // device pointers
+struct SamInput {  // device pointers (what the lines look like: LineOptions)
   const uint8_t *quals;          // quality characters, same offsets as the bases
   const uint8_t *names;          // read names, concatenated
   const uint64_t *name_off;      // n_reads + 1
   const uint8_t *ref_names;      // reference sequence names, concatenated
   const uint32_t *ref_name_off;  // n_seq + 1
   bool qual_hole;                // quals == nullptr and the QUAL field of a primary record is LEFT UNWRITTEN (the caller fills it: SamOutput::qual_at)
-  bool mapq = false;             // MAPQ from the hit strata (mapq_kernel; in pair mode pair() must have been asked for it too); else 255
-  bool unmapped = false;         // a line for every read without a record (fem_dev_set_unmapped; the kernels' kUnm instances)
-  int32_t strata = -1;           // the line filter (fem_dev_set_report; report_kernel): a slot's lines within this many edits of its best, -1: off
-  int32_t max_hits = -1;         // ... and at most this many lines per slot (>= 1), -1: off
-  const char *read_group = nullptr;  // HOST: the ID every line's RG:Z tag carries (fem_dev_set_tags), rg_len bytes; nullptr: no RG tag
-  uint32_t rg_len = 0;
-  bool hit_tags = false;         // NH:i and HI:i on every mapped line
 };
 struct SamOutput {  // pinned host memory owned by the Tail object, valid until its next sam()
   const char *text;
@@ -102,9 +95,8 @@ struct PairOutput {  // pinned host memory owned by the Tail object, valid until
   const char *r_md;
 };
 
-// Mate rescue (fem_dev_set_rescue): what pair() needs besides the records to search the mapped mate's insert window.
+// Mate rescue (LineOptions::rescue): what pair() needs besides the records to search the mapped mate's insert window.
 struct RescueInput {  // device pointers unless noted
-  int32_t max_edits;           // E, 0 .. 15
   const uint8_t *bases;        // the batch's read characters (both stagings leave them on the device)
   const uint64_t *read_off;
   uint32_t max_len;            // host: longest read of the batch
@@ -112,9 +104,34 @@ struct RescueInput {  // device pointers unless noted
   uint64_t ref_bytes;          // host: bytes in ref_raw, its slack included
   const uint64_t *seq_off;
   const uint32_t *seq_len;
-  // fem_dev_set_rescue_discordant: a pair with records on both sides and no concordant combination is a candidate too,
-  // searched from either mate's anchors (pair_probe_kernel in front of the rescue kernels)
-  bool discordant = false;
+};
+
+// What the lines of a slot's texts and BAM records look like: host values, one field per option of the C API's fem_dev_set_*.
+// pair() reads the pairing and rescue fields, sam() / bam() the others and `paired`.  A new output option is a field here.
+struct LineOptions {
+  bool paired = false;             // the lines in the order of the last pair() with its mate columns (the records of both stay on the device)
+  int32_t min_insert = 0, max_insert = 0;
+  bool rescue = false;             // mate rescue at rescue_edits edits (E, 0 .. 15), in pair mode
+  int32_t rescue_edits = 0;
+  // a pair with records on both sides and no concordant combination is a candidate too, searched from either mate's anchors
+  // (pair_probe_kernel in front of the rescue kernels)
+  bool rescue_discordant = false;
+  bool mapq = false;               // MAPQ from the hit strata (mapq_kernel; pair() leaves pair_kernel's bytes for it); else 255
+  bool unmapped = false;           // a line for every read without a record (the kernels' kUnm instances)
+  int32_t strata = -1;             // the line filter (report_kernel): a slot's lines within this many edits of its best, -1: off
+  int32_t max_hits = -1;           // ... and at most this many lines per slot (>= 1), -1: off
+  std::string read_group;          // the ID every line's RG:Z tag carries; empty: no RG tag
+  bool hit_tags = false;           // NH:i and HI:i on every mapped line
+  bool filters() const { return strata >= 0 || max_hits >= 1; }  // the line filter is on
+  bool rescues() const { return paired && rescue; }
+};
+// What the last pair() and the last sam() / bam() counted (Tail::counts).
+struct LineCounts {
+  uint64_t n_proper = 0;              // proper pairs
+  uint64_t n_rescued = 0;             // kept rescued records (0 without LineOptions::rescue)
+  uint64_t n_rescued_discordant = 0;  // ... those of pairs with records on both sides (0 without LineOptions::rescue_discordant)
+  uint64_t n_unmapped = 0;            // lines for unmapped reads (0 without LineOptions::unmapped)
+  uint64_t n_filtered = 0;            // lines the filter left out (0 without LineOptions::strata / max_hits)
 };
 
 // One text on its way home at a time (per GPU).  Two device-to-host copies queued in the copy engines take both of them, and
@@ -129,8 +146,8 @@ struct TextGate {
 
 // The timed stages of a batch's way out of the device.  Each runs between two events on its stream, recorded whether or not
 // anybody asks (Tail::stage_ms).  run(): kOrder, kTrace, kCompact.  pair(): kRescue when it rescues, kPairing.  sam() / bam():
-// kMapq with SamInput::mapq; kFilterIndex, the line index with the line filter, or else kUnmappedIndex, the one with
-// SamInput::unmapped alone; kText, the SAM text's or the BAM records' kernels.
+// kMapq with LineOptions::mapq; kFilterIndex, the line index with the line filter, or else kUnmappedIndex, the one with
+// LineOptions::unmapped alone; kText, the SAM text's or the BAM records' kernels.
 enum Stage { kOrder, kTrace, kCompact, kText, kPairing, kRescue, kMapq, kUnmappedIndex, kFilterIndex, kStages };
 
 class Tail {
@@ -150,31 +167,26 @@ class Tail {
   int reserve(uint32_t n_reads, uint32_t n_records, uint32_t max_len, int e, bool tiny, std::string *err);
   // ... and loads the kernels (a code object is loaded by its first launch otherwise) and wakes `stream`.
   int warm(hipStream_t stream, std::string *err);
-  // The records of the last run() as SAM lines, in record order.
+  // The records of the last run() as SAM lines, in record order; opt.paired: in the order of the last pair().
   // wait = false: returns once the copy of the text to the host has been queued; wait_text() (which may be called from
   // another thread) returns when it has arrived.
-  // paired = true: the lines in the order of the last pair() with its mate columns (the records of both stay on the device).
-  int sam(const TailInput &in, const SamInput &names, hipStream_t stream, int n_cu, SamOutput *out, std::string *err, bool wait = true,
-          TextGate *gate = nullptr, bool paired = false);
+  int sam(const TailInput &in, const SamInput &names, const LineOptions &opt, hipStream_t stream, int n_cu, SamOutput *out, std::string *err,
+          bool wait = true, TextGate *gate = nullptr);
   // The same lines as BAM records (names.quals must be set: no qual_hole), compressed at `level` (0 or 1) into BGZF members.
-  // bgzf_ms (optional) receives the BGZF kernels' device time (the record kernels' is stage kText's).  wait, gate, paired: as sam().
+  // bgzf_ms (optional) receives the BGZF kernels' device time (the record kernels' is stage kText's).  wait, gate: as sam().
   // FEM_ERR_UNSUPPORTED for a read name over 254 characters.
-  int bam(const TailInput &in, const SamInput &names, int level, hipStream_t stream, int n_cu, BamOutput *out, std::string *err,
-          float *bgzf_ms, bool wait = true, TextGate *gate = nullptr, bool paired = false);
+  int bam(const TailInput &in, const SamInput &names, const LineOptions &opt, int level, hipStream_t stream, int n_cu, BamOutput *out,
+          std::string *err, float *bgzf_ms, bool wait = true, TextGate *gate = nullptr);
   // Pairs the records of the last run() (pair_kernel): output order, FLAG, mate columns and TLEN of every line, the proper-pair
-  // count.  Asynchronous on `stream`; n_proper() is valid once the stream has been synchronised (sam() does).
-  // rescue (optional): mate rescue first (the rescue kernels), the kept rescued records appended behind run()'s; pair() then
-  // waits for the stream twice (the candidate count, the kept count).  RescueInput::discordant: pair_probe_kernel runs at
-  // their head, inside stage kRescue, and adds no wait.
-  // mapq: pair_kernel also writes each line's pairing byte (qp and whether the chosen record may keep its own MAPQ), which the
-  // next sam() / bam() with SamInput::mapq turns into the MAPQ of the mates' primary lines.
-  int pair(int32_t min_insert, int32_t max_insert, hipStream_t stream, std::string *err, const RescueInput *rescue = nullptr,
-           bool mapq = false);
-  uint64_t n_proper() const;
-  uint64_t n_rescued() const;   // kept rescued records of the last pair() (0 without rescue)
-  uint64_t n_rescued_discordant() const;  // ... those of pairs with records on both sides (0 without RescueInput::discordant)
-  uint64_t n_unmapped() const;  // lines for unmapped reads in the last sam() / bam() (0 without SamInput::unmapped)
-  uint64_t n_filtered() const;  // lines the filter left out of the last sam() / bam() (0 without SamInput::strata / max_hits)
+  // count.  Asynchronous on `stream`; counts().n_proper is valid once the stream has been synchronised (sam() does).
+  // opt.rescues(): mate rescue first (the rescue kernels, reading `rescue`), the kept rescued records appended behind run()'s;
+  // pair() then waits for the stream twice (the candidate count, the kept count).  LineOptions::rescue_discordant:
+  // pair_probe_kernel runs at their head, inside stage kRescue, and adds no wait.
+  // opt.mapq: pair_kernel also writes each line's pairing byte (qp and whether the chosen record may keep its own MAPQ), which the
+  // next sam() / bam() with LineOptions::mapq turns into the MAPQ of the mates' primary lines.
+  int pair(const LineOptions &opt, const RescueInput &rescue, hipStream_t stream, std::string *err);
+  // The counts of the last pair() (all 0 unless it ran since the last run()) and of the last sam() / bam().
+  LineCounts counts() const;
   // The device time of a stage, in ms.  Negative: the stage was not part of the last run() and of what followed it (pair(),
   // sam() or bam()), or its stream has not yet passed its end (a text that was not waited for).
   float stage_ms(Stage stage) const;
