@@ -345,8 +345,9 @@ int fem_dev_pair_count(fem_dev *h, int slot, uint64_t *n_proper);
 /* ---- mate rescue (new; opt-in: with it off every paired output stays byte for byte what it is without it) ----
  * fem_dev_set_rescue: the slot's read pairs are rescued at max_edits = E edits (0 <= E <= 15, else FEM_ERR_INVALID); NULL: off.
  *   It takes effect with pair mode (fem_dev_set_pairs); fetch time refuses max_insert - min_insert > 65536 (FEM_ERR_UNSUPPORTED).
- * Rule.  A pair is a candidate when exactly one mate, B (length L), has no record.  The anchors are those of the other mate's
- *   first FEM_RESCUE_ANCHORS records that do not carry 0x8000.  Per anchor a (sequence tid, pa = pos0, ea = end0, signed
+ * Rule.  A pair is a candidate when exactly one mate, B (length L), has no record.  A mate of length 0 is never searched (every
+ *   window would "hit" it at 0 edits with an empty CIGAR): such a pair stays as it is and B stays unmapped.  The anchors are those
+ *   of the other mate's first FEM_RESCUE_ANCHORS records that do not carry 0x8000.  Per anchor a (sequence tid, pa = pos0, ea = end0, signed
  *   arithmetic), the window of B's pos0 is
  *     anchor forward: B reverse-complemented, lo = max(pa, pa + I - L), hi = pa + X - L;
  *     anchor reverse: B forward,             lo = max(0, ea - X),         hi = min(pa, ea - I);      none when lo > hi

@@ -1,0 +1,471 @@
+"""Randomised differential run of the output-line options: pairing, mate rescue, --rescue-discordant, MAPQ, the unmapped reads'
+lines, --strata / --max-hits, the RG / NH / HI tags and BAM, all drawn together, against the composed plain-Python models
+(tests/pair_model, rescue_model, discordant_model, mapq_model, unmapped_model, report_model, tags_model, bam_model) on the
+oracle's single-end records.  include/fem_hip.h is the arbiter.
+
+Every trial is three functions: draw(rng) makes the world and the options, expected(trial) runs the models (both on the CPU:
+tests/test_fuzz_lines_model.py holds the drawn slice to coverage and sensitivity conditions), compare(dev, trial, want) runs the
+device.  One Device serves the whole run, so what a trial leaves behind in a slot meets the next trial's options.
+
+By the clock:  FUZZ_SECONDS=300 FUZZ_SEED=1 python tests/fuzz_lines.py ;  FUZZ_TRIAL=k re-runs trial k of the seed alone (a
+trial's random stream is default_rng([seed, k])).  Not collected by pytest; a bounded slice with fixed seeds runs under
+`pytest -m gpu` (tests/test_gpu_fuzz_lines.py)."""
+import gzip
+import itertools
+import os
+import pathlib
+import subprocess
+import sys
+import tempfile
+import time
+import types
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+from oracle import fem_oracle as fo
+from tests import bam_model as bm
+from tests import discordant_fixture as df
+from tests import discordant_model as dm
+from tests import pair_model as pm
+from tests import report_model as rp
+from tests import rescue_model as rm
+from tests import tags_model as tm
+from tests import unmapped_model as um
+from tests import util
+from tests.test_gpu_pairs import _write_fastq, make_pairs
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FEM = os.path.join(ROOT, "fem_amd", "csrc", "FEM")
+THREADS = 8
+COPIES = (6, 12, 40, 80)
+IUPAC = b"NNNNRYKMSWBDHVn"
+LETTERS = np.frombuffer(b"ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz", np.uint8)
+INSERT_LISTS = 16  # the records of a mate that draw() looks at for inserts that occur
+OPTIONS = ("paired", "e", "E", "L", "L2", "I", "X", "rescue", "discordant", "mapq", "unmapped", "strata", "max_hits", "rg", "hits",
+           "bam_level", "nowait", "packed", "quals_on_host", "slot", "copies", "n", "moved", "cli")
+
+
+def _printable(rng, n, lo=33):
+    return bytes(rng.integers(lo, 127, size=n).astype(np.uint8))
+
+
+def _qname(rng):
+    """1..254 bytes of [!-~], a letter at either end (a FASTQ header line and a SAM header line begin with @; a mate suffix
+    /1 /2 is cut off a name)."""
+    n = int(rng.integers(1, 255)) if rng.random() < 0.3 else int(rng.integers(1, 40))
+    s = bytearray(_printable(rng, n))
+    s[0] = LETTERS[rng.integers(0, len(LETTERS))]
+    s[-1] = LETTERS[rng.integers(0, len(LETTERS))]
+    return bytes(s).decode("latin-1")
+
+
+def occurring_inserts(se, n, I=0, X=1 << 30):
+    """The inserts of the concordant record combinations of every pair under (I, X), by default (0, 2^30):
+    pair_model.insert_of over each mate's first INSERT_LISTS records."""
+    out = []
+    for i in range(n):
+        a0, a1 = int(se.rec_off[i]), int(se.rec_off[i + 1])
+        b0, b1 = int(se.rec_off[n + i]), int(se.rec_off[n + i + 1])
+        for ja in range(a0, min(a1, a0 + INSERT_LISTS)):
+            for jb in range(b0, min(b1, b0 + INSERT_LISTS)):
+                ins = pm.insert_of(se, ja, jb, I, X)
+                if ins is not None:
+                    out.append(ins)
+    return out
+
+
+def anchor_pairs(rng, L, L2, e, E, X, n_copies=9):
+    """-> (a sequence, mate 1 reads, mate 2 reads): two pairs for the limit of rescue_model.ANCHORS.  Mate 1 of each is a segment
+    that stands n_copies times in the sequence, exactly and too far apart to share a window, so its records tie; mate 2's segment,
+    with e + 1 .. E substitutions (0 .. e where E <= e), stands beside one copy alone: the eighth for the first pair, any for the
+    second, the ninth included, which no rescue reaches."""
+    parts, r1, r2 = [util.rand_seq(rng, 500)], [], []
+    for beside in (7, int(rng.integers(0, n_copies))):
+        a, b = util.rand_seq(rng, L), util.rand_seq(rng, L2)
+        k = int(rng.integers(e + 1, E + 1)) if E > e else int(rng.integers(0, e + 1))
+        c = bytearray(b)
+        for x in rng.choice(np.arange(2, L2 - 2), k, replace=False):
+            c[int(x)] = ord("A") if c[int(x)] != ord("A") else ord("C")
+        gap = int(rng.integers(20, X - max(L, L2) + 1))
+        for j in range(n_copies):
+            parts += [a, util.rand_seq(rng, gap)]
+            parts += [bytes(c) if j == beside else util.rand_seq(rng, L2), util.rand_seq(rng, X + 300)]
+        r1.append(a)
+        r2.append(util.revcomp(b))
+    return b"".join(parts), r1, r2
+
+
+def draw(rng, force=None):
+    """World and options of one trial: a random 60 kbp sequence, two or three repeat-rich ones, the discordant fixture's decoy and
+    anchor_pairs' sequence; the fixture's pairs, anchor_pairs' and make_pairs', some mates made odd; the options, each drawn
+    on its own; the oracle's records; the insert range, in most paired trials with a bound on an insert that occurs.  force: values that a caller fixes instead of drawing them (e, copies, cli; paired, or
+    single_end: the share of single-end trials)."""
+    f = force or {}
+    t = types.SimpleNamespace()
+    t.cli = bool(f.get("cli", False))
+    e = int(rng.choice([0, 1, 2, 3, 4, 0, 1, 2, 3, 4, 5, 6, 7]))  # (a forced value takes the place of a drawn one: the stream goes on alike)
+    t.e = e = int(f.get("e", e))
+    lo = 37 + 12 * e
+    t.L = L = int(rng.integers(lo, 261))
+    t.L2 = L2 = L if rng.random() < 0.5 else int(rng.integers(lo, 261))
+    t.E = E = int(rng.integers(e + 1, 16)) if rng.random() < 0.75 else int(rng.integers(0, 16))
+    X = int(rng.integers(max(L, L2) + 60, 901))
+    t.copies = copies = int(f.get("copies", rng.choice(COPIES)))
+    # the world
+    main = [util.rand_seq(rng, 60_000)]
+    main += util.repeat_rich_reference(rng, n_seq=int(rng.integers(2, 4)), unit_len=300, n_units=int(rng.choice([3, 4, 6])),
+                                       copies=copies, spacer=200)
+    nd = int(rng.integers(16, 41))
+    seqs, r1, r2 = df.make_discordant_pairs(rng, main, nd, L, L2, e, E, X, n_sym=int(rng.integers(2, 7)),
+                                            decoy_copies=int(rng.integers(1, 3)), near_end=bool(rng.integers(0, 2)))
+    p1, p2 = make_pairs(rng, seqs, int(rng.integers(10, 41)), L, e, L2)
+    tied, a1, a2 = anchor_pairs(rng, L, L2, e, E, X)
+    seqs = seqs + [tied]
+    for a, b in zip(a1, a2):  # (somewhere among the others, either mate first)
+        at = int(rng.integers(0, len(r1) + 1))
+        a, b = (a, b) if rng.integers(0, 2) else (b, a)
+        r1.insert(at, a)
+        r2.insert(at, b)
+    r1, r2 = r1 + p1, r2 + p2
+    t.n = n = len(r1)
+    reads = r1 + r2
+    # mode, staging
+    t.paired = bool(f.get("paired", rng.random() >= f.get("single_end", 0.25)))
+    t.packed = bool(L == L2 and rng.random() < 0.4)
+    # odd reads: lower case (0x8000 records), N and IUPAC letters, random mates, reads of length 0
+    for r in rng.choice(2 * n, int(rng.integers(2, 5)), replace=False):
+        reads[r] = reads[r].lower()
+    for r in rng.choice(2 * n, int(rng.integers(2, 6)), replace=False):
+        s = bytearray(reads[r])
+        for x in rng.integers(0, len(s), int(rng.integers(1, 4))):
+            s[int(x)] = IUPAC[int(rng.integers(0, len(IUPAC)))]
+        reads[r] = bytes(s)
+    for r in rng.choice(2 * n, int(rng.integers(1, 4)), replace=False):
+        reads[r] = util.rand_seq(rng, len(reads[r]))
+    if not t.packed and not t.cli:
+        for r in rng.choice(2 * n, int(rng.integers(1, 3)), replace=False):
+            reads[r] = b""
+    if t.packed and 20 * sum(sum(c not in b"ACGT" for c in r) for r in reads) > 2 * n * L:
+        t.packed = False  # (a batch with more than one odd byte in sixteen goes as characters)
+    t.seqs, t.reads = seqs, reads
+    base = [_qname(rng) for _ in range(n)]
+    t.rnames = base + base
+    t.quals = [_printable(rng, len(r)).decode("latin-1") for r in reads]
+    t.names = ["chr%d%s" % (i, "_x" * int(rng.integers(0, 20))) for i in range(len(seqs))]
+    # the output options
+    t.rescue = bool(rng.random() >= 0.2)
+    t.discordant = bool(rng.integers(0, 2))
+    t.mapq = bool(rng.integers(0, 2))
+    t.unmapped = bool(rng.integers(0, 2))
+    t.strata = None if rng.random() < 0.4 else int(rng.integers(0, 4)) if rng.random() < 0.75 else int(rng.integers(0, 16))
+    u = rng.random()
+    t.max_hits = None if u < 0.4 else (1 << 31) - 1 if u < 0.5 else int(rng.integers(1, 7))
+    t.rg = None if rng.random() < 0.4 else _printable(rng, int(rng.integers(1, 256)) if rng.random() < 0.3 else int(rng.integers(1, 12)), 32)
+    if t.cli and t.rg is not None:  # (FEM map --rg reads the two characters \t as a tab)
+        t.rg = t.rg.replace(b"\\", b"/")
+    t.hits = bool(rng.integers(0, 2))
+    t.bam_level = int(rng.integers(0, 2))
+    t.nowait = bool(rng.integers(0, 2))
+    t.quals_on_host = bool(rng.random() < 0.3)
+    t.slot = int(rng.integers(0, 4))
+    # the oracle's single-end records: what the models start from, and the inserts that occur
+    t.ref = fo.Reference(seqs)
+    t.idx = fo.OracleIndex(t.ref, threads=THREADS)
+    t.se = fo.map_reads(t.ref, t.idx, fo.ReadBatch(reads), e=e, threads=THREADS)
+    # the insert range
+    I = int([0, 0, max(L, L2), rng.integers(0, X // 2)][int(rng.integers(0, 4))])
+    t.moved = None
+    if t.paired and rng.random() < 0.6:  # a bound onto an insert that occurs: ins == X, ins == I
+        ins = occurring_inserts(t.se, n)
+        near = [v for v in ins if v <= 2000] or ins
+        if near:
+            v = int(near[int(rng.integers(0, len(near)))])
+            if rng.integers(0, 2):
+                if v >= I and v - I <= 65536:
+                    X, t.moved = v, "X"
+            elif 0 < v <= X:
+                I, t.moved = v, "I"
+    t.I, t.X = I, X
+    assert 0 <= I <= X <= 1 << 30 and X - I <= 65536
+    return t
+
+
+def options(t):
+    return {k: getattr(t, k) for k in OPTIONS}
+
+
+def fingerprint(t):
+    """Everything draw() decided, in a form that compares."""
+    return (repr(options(t)), tuple(t.seqs), tuple(t.reads), tuple(t.rnames), tuple(t.quals), tuple(t.names))
+
+
+def rescued_lists(t, E=None, I=None, X=None):
+    """(the lists pairing sees, {read: its kept rescue}, {pair: every traced rescue}, {read: (kind, d)}) of a paired trial."""
+    E, I, X = t.E if E is None else E, t.I if I is None else I, t.X if X is None else X
+    memo = t.__dict__.setdefault("_rescued", {})
+    key = (E, I, X, rm.ANCHORS)
+    if key in memo:
+        return memo[key]
+    if t.rescue and t.discordant:
+        out = dm.rescue(t.se, t.n, t.reads, t.seqs, E, I, X)
+    elif t.rescue:
+        ext, kept, traced = rm.rescue(t.se, t.n, t.reads, t.seqs, E, I, X)
+        out = ext, kept, traced, {r: (1, 0 if r >= t.n else 1) for r in kept}
+    else:
+        out = t.se, {}, {}, {}
+    memo[key] = out
+    return out
+
+
+_KEEP = object()
+
+
+def expected(t, full=True, E=None, I=None, X=None, strata=_KEEP, max_hits=_KEEP, mapq_e=None):
+    """The models' answer: text, the five counts (proper, rescued, rescued discordant, unmapped, filtered; the pair counts None
+    single-end), and with `full` the fem_batch_pairs arrays and the BAM payload.  The keyword arguments replace one parameter of
+    the rule (tests/test_fuzz_lines_model.py: an off-by-one must show)."""
+    I, X = t.I if I is None else I, t.X if X is None else X
+    strata = t.strata if strata is _KEEP else strata
+    max_hits = t.max_hits if max_hits is _KEEP else max_hits
+    e = (t.e if mapq_e is None else mapq_e) if t.mapq else None
+    w = types.SimpleNamespace(pairs=None)
+    if t.paired:
+        ext, kept, traced, kinds = rescued_lists(t, E, I, X)
+        text, dropped = rp.paired(t.se, t.n, t.names, t.reads, t.rnames, t.quals, I, X, res=ext, rescued=set(kept), e=e,
+                                  unmapped=t.unmapped, strata=strata, max_hits=max_hits)
+        w.ext, w.kept, w.traced, w.kinds = ext, kept, traced, kinds
+        n_unm = len(um.unmapped_reads(ext, 2 * t.n)) if t.unmapped else 0
+        w.counts = (pm.expected(ext, t.n, I, X)[1], len(kept), sum(k == 2 for k, _ in kinds.values()), n_unm, dropped)
+        if full:
+            w.pairs = pm.pair_arrays(ext, t.n, I, X)
+    else:
+        text, dropped = rp.single_end(t.se, t.names, t.reads, t.rnames, t.quals, e=e, unmapped=t.unmapped, strata=strata,
+                                      max_hits=max_hits)
+        w.counts = (None, None, None, len(um.unmapped_reads(t.se, 2 * t.n)) if t.unmapped else 0, dropped)
+    w.plain, w.text = text, tm.apply(text, t.rg, t.hits)
+    if full:
+        w.bam = tm.bam_payload(w.text, [x.encode() for x in t.names])
+    return w
+
+
+# the slice of tests/test_gpu_fuzz_lines.py, which tests/test_fuzz_lines_model.py holds to its conditions:
+# id, seed, trials, force, the trials that also go through the command line
+SLICE = [("single-end-heavy", 11, 12, {"single_end": 0.6}, ()), ("copies-80", 12, 12, {"copies": 80}, ()), ("e-7", 13, 12, {"e": 7}, ()),
+         ("command-line", 14, 12, {}, (3,))]
+
+
+def trial_force(force, cli):
+    """draw()'s force of a trial: one that goes through the command line is paired and made for FASTQ files."""
+    return dict(force or {}, cli=True, paired=True) if cli else dict(force or {})
+
+
+def slice_trials():
+    """(seed, k, force) of every trial of SLICE."""
+    return [(seed, k, trial_force(force, k in cli)) for _, seed, trials, force, cli in SLICE for k in range(trials)]
+
+
+# ---- the device ----
+
+def _first_difference(got, want):
+    g, w = got.split(b"\n"), want.split(b"\n")
+    k = next((i for i, (a, b) in enumerate(zip(g, w)) if a != b), min(len(g), len(w)))
+    return "line %d of %d / %d: got %r want %r" % (k, len(g) - 1, len(w) - 1, g[k:k + 1], w[k:k + 1])
+
+
+def _counts(dev, t):
+    from fem_amd import FemError
+    out = []
+    for count in (dev.pair_count, dev.rescue_count, dev.rescue_discordant_count):
+        try:
+            out.append(count(slot=t.slot))
+        except FemError as err:  # single-end: the three pair counts refuse
+            if t.paired or "the slot is not in pair mode" not in str(err):
+                raise
+            out.append(None)
+    return tuple(out) + (dev.unmapped_count(slot=t.slot), dev.filtered_count(slot=t.slot))
+
+
+def set_options(dev, t, X=None):
+    """Every option of the trial's slot through its own setter, the ones that go off included."""
+    s = t.slot
+    dev.set_pairs(t.I, t.X if X is None else X, slot=s) if t.paired else dev.set_pairs(None, slot=s)
+    dev.set_rescue(t.E if t.rescue else None, slot=s)
+    dev.set_rescue_discordant(t.discordant, slot=s)
+    dev.set_mapq(t.mapq, slot=s)
+    dev.set_unmapped(t.unmapped, slot=s)
+    dev.set_report(strata=t.strata, max_hits=t.max_hits, slot=s)
+    dev.set_tags(slot=s, read_group=t.rg, hits=t.hits)
+
+
+def compare(dev, t, want, X=None):
+    """The device on the trial -> the list of differences (empty: everything compared is identical).  An error of the device layer
+    is raised, not listed.  X: the device's max_insert, if not the trial's (to show that a difference is seen)."""
+    from fem_amd import device
+    s, diffs = t.slot, []
+    dev.upload_reference(t.seqs)
+    dev.upload_reference_names(t.names)
+    dev.upload_index(12, 3, t.idx.lookup, t.idx.occ[:t.idx.n_occ])
+    set_options(dev, t, X)
+    batch = fo.ReadBatch(t.reads)
+    q = np.frombuffer("".join(t.quals).encode("latin-1"), np.uint8)
+    if t.packed:
+        hb, _ = dev.acquire_stage(2 * t.n, 2 * t.n * t.L, slot=s)
+        dev.commit_stage_packed(2 * t.n, t.L, device.pack_reads(batch.bases, 2 * t.n, t.L, hb), slot=s)
+    else:
+        dev.stage_reads(batch.bases, batch.off, slot=s)
+    if dev.stage_info(s)[1] != t.packed and t.packed:
+        diffs.append("staging: not packed")
+    dev.stage_text(q, t.rnames, slot=s, quals_on_host=t.quals_on_host)
+    dev.map_staged(e=t.e, slot=s)
+    hq = dict(quals=q, offsets=batch.off) if t.quals_on_host else {}
+    # the text, the counts behind it, the text again the other way
+    text, _, _, stats = dev.fetch_sam(slot=s, nowait=t.nowait, **hq)
+    if text != want.text:
+        diffs.append("fetch_sam: " + _first_difference(text, want.text))
+    got = _counts(dev, t)
+    if got != want.counts:
+        diffs.append("counts after the text: got %r want %r" % (got, want.counts))
+    again = dev.fetch_sam(slot=s, nowait=not t.nowait, **hq)[0]
+    if again != text:
+        diffs.append("fetch_sam, the other nowait: " + _first_difference(again, text))
+    # BAM at the drawn level (its qualities on the device)
+    if t.quals_on_host:
+        dev.stage_text(q, t.rnames, slot=s)
+    data = dev.fetch_bam(slot=s, level=t.bam_level, nowait=t.nowait)
+    members = [m[0] for m in bm.parse_bgzf(data[0], eof=False)] if data[0] else []
+    payload = b"".join(members)
+    if payload != want.bam:
+        ref_names = [x.encode() for x in t.names]
+        try:
+            where = _first_difference(bm.bam_payload_to_sam(payload, ref_names), bm.bam_payload_to_sam(want.bam, ref_names))
+        except Exception as err:  # (records that do not decode)
+            where = "undecodable: %r" % err
+        diffs.append("fetch_bam level %d: %s" % (t.bam_level, where))
+    if data[1] != len(payload):
+        diffs.append("fetch_bam: raw_len %d, %d bytes in the members" % (data[1], len(payload)))
+    if (gzip.decompress(data[0]) if data[0] else b"") != payload:
+        diffs.append("fetch_bam: gzip inflates to other bytes")
+    try:
+        for m in members:
+            bm.records(m)
+    except Exception:
+        diffs.append("fetch_bam: a record spans two members")
+    got = _counts(dev, t)
+    if got != want.counts:
+        diffs.append("counts after the BAM: got %r want %r" % (got, want.counts))
+    if dev.fetch_bam(slot=s, level=t.bam_level, nowait=not t.nowait)[0] != data[0]:
+        diffs.append("fetch_bam, the other nowait: other bytes")
+    # fem_batch_pairs; fem_batch_records and the stats keep their single-end meaning
+    if t.paired:
+        pairs = dev.fetch_pairs(slot=s)
+        for k, v in want.pairs.items():
+            g = getattr(pairs, k)
+            if not (g == v if k == "n_proper" else np.array_equal(g, v)):
+                diffs.append("fetch_pairs: %s differs" % k)
+                break
+    se, rec = t.se, dev.fetch_records(slot=s)
+    for k, g, v in (("rec_begin", rec.rec_begin, se.rec_off), ("flag", rec.flag & 0x7FFF, se.r_flag & 0x7FFF), ("pos0", rec.pos0, se.r_pos),
+                    ("tid", rec.tid, se.r_tid), ("nm", rec.nm, se.r_nm), ("cigar_off", rec.cigar_off, se.cig_off), ("cigar", rec.cigar, se.cig),
+                    ("md_off", rec.md_off, se.md_off), ("md", rec.md, se.md), ("stats", stats, se.stats), ("stats", rec.stats, se.stats)):
+        if not np.array_equal(g, v):
+            diffs.append("fetch_records: %s differs" % k)
+            break
+    return diffs
+
+
+# ---- FEM index + FEM map ----
+
+def _counters(t, want):
+    st = [int(x) for x in t.se.stats]
+    out = ["The number of read: %d" % st[0], "The number of mapped read: %d" % st[1],
+           "The number of candidate before additional q-gram filter: %d" % st[2], "The number of candidate: %d" % st[3],
+           "The number of mapping: %d" % st[4], "The number of proper pairs: %d" % want.counts[0]]
+    if t.rescue:
+        out.append("The number of rescued mates: %d" % want.counts[1])
+        if t.discordant:
+            out.append("The number of rescued discordant pairs: %d" % want.counts[2])
+    if t.unmapped:
+        out.append("The number of unmapped reads: %d" % want.counts[3])
+    if t.strata is not None or t.max_hits is not None:
+        out.append("The number of filtered lines: %d" % want.counts[4])
+    return out
+
+
+def compare_cli(t, want, rng, timeout=300):
+    """The paired trial through FEM index + FEM map with the drawn switches -> the list of differences."""
+    from tests.test_gpu_bam import _decode_bam_file
+    diffs = []
+    with tempfile.TemporaryDirectory() as tmp:
+        fa, idx_path, out = os.path.join(tmp, "ref.fa"), os.path.join(tmp, "ref.idx"), os.path.join(tmp, "out")
+        with open(fa, "wb") as fh:
+            fh.write(b"".join(b">" + nm.encode() + b" desc\n" + s + b"\n" for nm, s in zip(t.names, t.seqs)))
+        subprocess.run([FEM, "index", "12", "3", fa, idx_path], check=True, capture_output=True, timeout=timeout)
+        n = t.n
+        paths = [pathlib.Path(tmp) / "r1.fq", pathlib.Path(tmp) / "r2.fq"]
+        for m, suffix in ((0, "/1"), (1, "/2")):
+            _write_fastq(paths[m], t.reads[m * n:(m + 1) * n], [x + suffix for x in t.rnames[m * n:(m + 1) * n]],
+                         t.quals[m * n:(m + 1) * n], False)
+        args = ["-e", str(t.e), "-t", "4", "--ref", fa, "--index", idx_path, "--read1", str(paths[0]), "--read2", str(paths[1]),
+                "-o", out, "--batch", str(2 * int(rng.integers(1, max(2, n // 2)))), "-I", str(t.I), "-X", str(t.X)]
+        if t.rescue:
+            args += ["--rescue", str(t.E)] + (["--rescue-discordant"] if t.discordant else [])
+        args += (["--mapq"] if t.mapq else []) + (["--unmapped"] if t.unmapped else []) + (["--nh"] if t.hits else [])
+        args += ([] if t.strata is None else ["--strata", str(t.strata)]) + ([] if t.max_hits is None else ["--max-hits", str(t.max_hits)])
+        args += [] if t.rg is None else ["--rg", "@RG\tID:" + t.rg.decode("latin-1")]
+        args += ["--bam=%d" % t.bam_level] if t.bam else []
+        r = subprocess.run([FEM, "map"] + args, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout)
+        if r.returncode != 0:
+            return ["FEM map: exit status %d: %s" % (r.returncode, r.stderr.decode("latin-1")[-400:])]
+        data = _decode_bam_file(out) if t.bam else open(out, "rb").read()
+        lines = data.split(b"\n")
+        k = next((i for i, l in enumerate(lines) if not l.startswith(b"@")), len(lines))
+        body = b"\n".join(lines[k:])
+        if body != want.text:
+            diffs.append("FEM map%s: %s" % (" --bam" if t.bam else "", _first_difference(body, want.text)))
+        got = [l for l in r.stderr.decode("latin-1").splitlines() if l.startswith("The number of")]
+        if got != _counters(t, want):
+            diffs.append("FEM map: counters %r want %r" % (got, _counters(t, want)))
+    return diffs
+
+
+# ---- the run ----
+
+def run_trial(dev, seed, k, force=None, cli=False, log=print):
+    """Trial k of `seed` -> True if everything compared is identical."""
+    t = draw(np.random.default_rng([seed, k]), trial_force(force, cli))
+    want = expected(t)
+    diffs = compare(dev, t, want)
+    if cli:
+        rng = np.random.default_rng([seed, k, 1])
+        t.bam = bool(rng.integers(0, 2))
+        diffs += compare_cli(t, want, rng)
+    log("seed %d trial %d" % (seed, k), options(t), "lines %d" % want.text.count(b"\n"), "counts %r" % (want.counts,),
+        "ok" if not diffs else "MISMATCH: " + "; ".join(diffs))
+    return not diffs
+
+
+def run(seed, trials=None, seconds=None, log=print, force=None, cli_trials=None, only=None):
+    """`trials` trials of `seed` (0 .. trials - 1), or trials for `seconds`; only: that one trial alone -> (n_trials, bad).
+    force: draw()'s.  cli_trials: the trials that are paired and also go through the command line; by default every sixth trial
+    of a run by the clock (a rule on k alone, so that FUZZ_TRIAL meets the same trial).  A mismatch is logged and counted; an
+    error of the device layer ends the run: it is raised, and nothing more is started on the GPU."""
+    from fem_amd import Device
+    t_end = time.time() + seconds if seconds else None
+    n_trials = bad = 0
+    dev = Device(0)
+    for k in itertools.count() if only is None else [only]:
+        if only is None and (time.time() >= t_end if t_end else k >= trials):
+            break
+        cli = k in cli_trials if cli_trials is not None else bool(t_end) and k % 6 == 5
+        n_trials += 1
+        bad += not run_trial(dev, seed, k, force, cli, log)
+    dev.close()
+    return n_trials, bad
+
+
+if __name__ == "__main__":
+    only = os.environ.get("FUZZ_TRIAL")
+    n_trials, bad = run(int(os.environ.get("FUZZ_SEED", "1")), seconds=float(os.environ.get("FUZZ_SECONDS", "240")),
+                        only=None if only is None else int(only))
+    print("trials", n_trials, "bad", bad)
+    sys.exit(1 if bad else 0)

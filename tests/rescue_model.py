@@ -64,6 +64,8 @@ def rescue_pair(res, n_pairs, i, reads, seqs, E, I, X, ref=None):
     A, b_read = (range(a0, a1), n_pairs + i) if a1 > a0 else (range(b0, b1), i)
     read = reads[b_read]
     L = len(read)
+    if L == 0:  # a mate without a base is never searched: it stays unmapped
+        return None
     chosen = None
     for a, j in enumerate(list(A)[:ANCHORS]):
         fl = int(res.r_flag[j])

@@ -1,0 +1,21 @@
+"""A bounded slice of tests/fuzz_lines.py under `pytest -m gpu`: fixed seeds, twelve trials each, of the output-line options drawn
+together (pairing with I and X anywhere, an insert on either bound, mate rescue, --rescue-discordant, MAPQ, the unmapped reads'
+lines, --strata / --max-hits, RG / NH / HI, BAM, staging, slot, one trial through FEM index + FEM map) against the composed
+models: pair_kernel, pair_probe_kernel, mapq_kernel, report_kernel, the rescue kernels and the option branches of the sam_* /
+bam_* kernels (fem_tail.hip), and the LineOptions plumbing of fem_hip.hip, one handle per case.  What the slice reaches, and that
+it would see an off-by-one, is held without a GPU by tests/test_fuzz_lines_model.py.
+
+Wall time per case on the MI355X (the models on the host take most of it): single-end-heavy 1.2 s, copies-80 1.1 s, e-7 1.0 s,
+command-line 1.8 s."""
+import pytest
+
+from tests import fuzz_lines
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.mark.parametrize("name,seed,trials,force,cli", fuzz_lines.SLICE, ids=[c[0] for c in fuzz_lines.SLICE])
+def test_fuzz_slice(name, seed, trials, force, cli):
+    lines = []
+    n, bad = fuzz_lines.run(seed, trials=trials, force=force, cli_trials=cli, log=lambda *a: lines.append(" ".join(str(x) for x in a)))
+    assert n == trials and bad == 0, "\n".join(lines)

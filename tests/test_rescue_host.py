@@ -134,6 +134,14 @@ def test_no_rescue_when_both_mates_have_records():
     assert not kept and not traced
 
 
+def test_a_mate_of_length_0_is_not_searched():
+    s = _seq(7)
+    for anchor, b_first in (((0, 1000, 0, [(100, "M")]), False), ((16, 2000, 0, [(100, "M")]), True)):
+        ext, kept, traced = _case(s, [anchor], b"", b_first=b_first)
+        assert not kept and not traced
+        assert ext.rec_off.tolist() == ([0, 0, 1] if b_first else [0, 1, 1])  # the pair stays as it was
+
+
 def test_reverse_mate_pushed_past_x_is_dropped():
     s = _seq(6)
     assert s[1500:1501] == b"G"
