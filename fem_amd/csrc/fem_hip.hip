@@ -58,7 +58,7 @@ constexpr size_t kPackedFrontPad = 256;  // ... and verify_kernel_packed up to 1
 constexpr uint64_t kExpandAllShare = 8;  // a packed batch with more exceptions than one per this many reads is expanded whole at commit
 constexpr uint32_t kXcapSmall = 512, kFcap = 128, kCcap = 128;
 
-constexpr int kTimedKernels = 16;  // fem_dev_kernel_time ids: 0 seed (join), 1 verify, 2 generic seed, 3-5 tail, 6 pack_results_kernel (round 5; the count kernel of rounds 1-2 before), 7 SAM text, 8 seed selection, 9 pairing, 10 mate rescue, 11 BAM records, 12 BGZF, 13 MAPQ, 14 the line index with unmapped reads, 15 the line filter's line index; 3-5, 7, 9-11 and 13-15 are stages of the device tail (kTailStages)
+constexpr int kTimedKernels = 17;  // fem_dev_kernel_time ids: 0 seed (join), 1 verify, 2 generic seed, 3-5 tail, 6 pack_results_kernel (round 5; the count kernel of rounds 1-2 before), 7 SAM text, 8 seed selection, 9 pairing, 10 mate rescue, 11 BAM records, 12 BGZF, 13 MAPQ, 14 the line index with unmapped reads, 15 the line filter's line index, 16 the insert estimate; 3-5, 7, 9-11 and 13-15 are stages of the device tail (kTailStages), 16 is one too (fem_dev_estimate_insert counts it itself)
 struct TimedLaunch {
   int kernel;
   hipEvent_t start, stop;
@@ -2391,6 +2391,30 @@ int fem_dev_fetch_pairs(fem_dev *h, int slot, fem_batch_pairs *out) {
   out->mate_tid = po.mate_tid, out->mate_pos0 = po.mate_pos0, out->tlen = po.tlen;
   out->n_proper = po.n_proper;
   memcpy(out->stats, s.stats, sizeof s.stats);
+  return FEM_OK;
+}
+
+// The insert size range the slot's batch suggests (include/fem_hip.h: the rule): the records of fem_dev_fetch_records, then the
+// tail's two kernels over them.  Reads the records only: the slot's options, counts and whatever a later fetch makes stay.
+int fem_dev_estimate_insert(fem_dev *h, int slot, fem_insert_estimate *out) {
+  int rc = check_slot(h, slot);
+  if (rc) return rc;
+  if (!out) return fail(h, FEM_ERR_INVALID, "null result");
+  if (!h->slot[slot].opt.paired) return fail(h, FEM_ERR_STATE, "the slot is not in pair mode (fem_dev_set_pairs)");
+  fem_batch_records rec{};
+  if ((rc = fem_dev_fetch_records(h, slot, &rec))) return rc;
+  Slot &s = h->slot[slot];
+  if (s.n_reads & 1) return fail(h, FEM_ERR_INVALID, "a batch of read pairs holds an even number of reads");
+  femt::InsertEstimate e{};
+  std::string err;
+  if ((rc = s.tail->estimate_insert(s.stream, &e, &err))) return fail(h, rc, err);
+  if (h->timing) {
+    FEM_LOCK(h);
+    h->t_ms[16] += std::max(s.tail->stage_ms(femt::kInsert), 0.f), h->t_n[16] += 1;
+  }
+  out->n_pairs = e.n_pairs, out->n_unique = e.n_unique, out->n_informative = e.n_informative;
+  out->q25 = e.q25, out->q50 = e.q50, out->q75 = e.q75;
+  out->min_insert = e.min_insert, out->max_insert = e.max_insert, out->estimated = e.estimated ? 1 : 0;
   return FEM_OK;
 }
 

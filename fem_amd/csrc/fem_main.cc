@@ -7,6 +7,7 @@
 // per batch.  `--read2 STR` maps read pairs (record i of --read1 and of --read2 are the two mates of pair i), with -I / -X the
 // accepted insert size: the pairing and the paired SAM text on the device (fem_dev_set_pairs); `--rescue INT` adds mate rescue
 // at INT edits (fem_dev_set_rescue), `--rescue-discordant` also for pairs whose records do not pair (fem_dev_set_rescue_discordant).  `--mapq` writes mapping qualities made on the device (fem_dev_set_mapq) instead of 255.
+// `--infer-insert[=N]` learns -I / -X from the input's first N pairs on the device, before the run (fem_dev_estimate_insert).
 // `--unmapped` adds a line for every read without a mapping, made on the device (fem_dev_set_unmapped).
 // `--strata INT` / `--max-hits INT` leave out the lines of a read beyond its best strata / its first INT (fem_dev_set_report).
 // `--header` puts @HD in front of the @SQ lines and @PG behind them; `--rg LINE` adds the @RG line and RG:Z on every line, `--nh`
@@ -77,6 +78,7 @@ void usage_map() {
   fprintf(stderr, "        --read2  STR  Input read2 file: map read pairs (record i of both files is pair i)\n");
   fprintf(stderr, "        -I, --minins INT  minimum insert size of a proper pair [0]\n");
   fprintf(stderr, "        -X, --maxins INT  maximum insert size of a proper pair [500]\n");
+  fprintf(stderr, "        --infer-insert[=INT]  with --read2: learn -I / -X from the first INT (64-262144) [65536] pairs, on the GPU, before the run\n");
   fprintf(stderr, "        --rescue INT  with --read2: search a mate without records in its mate's insert window at INT (0-15) edits\n");
   fprintf(stderr, "        --rescue-discordant  with --rescue: also search the mates of a pair whose records do not pair\n");
   fprintf(stderr, "        --bam[=INT]   write BAM instead of SAM: BGZF level 1 (default) or 0 (uncompressed)\n");
@@ -294,6 +296,9 @@ int map_main(int argc, char **argv) {
   long long min_insert = 0, max_insert = 500;
   long long rescue_edits = 0;  // --rescue (mate rescue at this many edits, fem_dev_set_rescue)
   bool rescue_given = false;
+  // --infer-insert[=N]: the insert size range from the input's first N pairs (fem_dev_estimate_insert), -I / -X the fallback
+  bool infer_insert = false;
+  long long infer_pairs = 65536;
   bool rescue_discordant = false;  // --rescue-discordant (fem_dev_set_rescue_discordant)
   int bam_level = -1;  // --bam[=LEVEL]: BAM records and BGZF members made on the device (fem_dev_fetch_bam); -1: SAM
   bool unmapped = false;  // --unmapped: a line for every read without a mapping, made on the device (fem_dev_set_unmapped)
@@ -317,6 +322,7 @@ int map_main(int argc, char **argv) {
                                      {"read2", required_argument, nullptr, 'c'}, {"minins", required_argument, nullptr, 'I'},
                                      {"maxins", required_argument, nullptr, 'X'}, {"rescue", required_argument, nullptr, 'R'},
                                      {"rescue-discordant", no_argument, nullptr, 'D'},
+                                     {"infer-insert", optional_argument, nullptr, 'F'},
                                      {"bam", optional_argument, nullptr, 'Z'},  {"mapq", no_argument, nullptr, 'Q'},
                                      {"unmapped", no_argument, nullptr, 'U'},
                                      {"strata", required_argument, nullptr, 'S'}, {"max-hits", required_argument, nullptr, 'N'},
@@ -346,6 +352,14 @@ int map_main(int argc, char **argv) {
         bam_level = !optarg ? 1 : strcmp(optarg, "0") == 0 ? 0 : strcmp(optarg, "1") == 0 ? 1 : -2;  // (-2: refused below)
         break;
       case 'D': rescue_discordant = true; break;
+      case 'F':
+        infer_insert = true;
+        if (optarg) {
+          char *end = nullptr;
+          infer_pairs = strtoll(optarg, &end, 10);
+          if (!end || end == optarg || *end) infer_pairs = -1;  // (not a number: refused below)
+        }
+        break;
       case 'Q': mapq = true; break;
       case 'U': unmapped = true; break;
       case 'S': {
@@ -394,6 +408,8 @@ int map_main(int argc, char **argv) {
   else if (n_threads <= 0) bad = "Wrong number of threads.";
   else if (params.a < 0 || params.a > 2) bad = "Wrong number of additional q-grams.";
   else if (min_insert < 0 || max_insert < min_insert || max_insert > (1ll << 30)) bad = "Wrong insert size range.";
+  else if (infer_insert && !read2_path) bad = "--infer-insert needs read pairs (--read2).";
+  else if (infer_insert && (infer_pairs < 64 || infer_pairs > 262144)) bad = "Wrong number of pairs to infer from (64-262144).";
   else if (rescue_discordant && !rescue_given) bad = "--rescue-discordant needs --rescue.";
   else if (rescue_given && !read2_path) bad = "--rescue needs read pairs (--read2).";
   else if (rescue_given && (rescue_edits < 0 || rescue_edits > 15)) bad = "Wrong rescue error threshold (0-15).";
@@ -578,6 +594,58 @@ int map_main(int argc, char **argv) {
   }
   free(lookup), free(occ);
   fprintf(stderr, "Reference and index resident on %d GPU%s in %fs.\n", n_gpus, n_gpus > 1 ? "s" : "", real_time() - t_dev);
+
+  // --infer-insert: the insert size range from the input's first pairs, before anything is written and before the first batch
+  // is read: the sample is mapped single-end on the first device and its unique pairs say what the library's inserts are
+  // (fem_dev_estimate_insert).  The range then holds for the whole run, whatever --batch, -t and --gpus are; the main pass reads
+  // the input from its start and counts nothing of this.  Files that do not give as many records each, or a sample the reader
+  // cannot parse: no estimate, and the main pass reports the input as it does without the switch.
+  if (infer_insert) {
+    const double t_pre = real_time();
+    fem_seqset mate[2] = {};
+    bool sampled = true;
+    for (int m = 0; m < 2; ++m) {
+      fem_seqfile *f = fem_seqfile_open(m ? read2_path : read_path);
+      sampled = sampled && f && fem_seqfile_read(f, (uint64_t)infer_pairs, &mate[m]) == 0;
+      if (f) fem_seqfile_close(f);
+    }
+    sampled = sampled && mate[0].n == mate[1].n;
+    int rc = 0;
+    fem_insert_estimate est{};
+    est.q25 = est.q50 = est.q75 = -1;
+    if (sampled && mate[0].n) {  // mate 1's reads, then mate 2's, as one batch
+      const uint64_t np = mate[0].n, b1 = mate[0].off[np], b2 = mate[1].off[np];
+      std::vector<char> bases((size_t)(b1 + b2));
+      std::vector<uint64_t> off((size_t)(2 * np + 1));
+      if (b1) memcpy(bases.data(), mate[0].bases, (size_t)b1);
+      if (b2) memcpy(bases.data() + b1, mate[1].bases, (size_t)b2);
+      for (uint64_t i = 0; i <= np; ++i) off[(size_t)i] = mate[0].off[i], off[(size_t)(np + i)] = b1 + mate[1].off[i];
+      const fem_read_batch sample{bases.data(), off.data(), 2 * np};
+      fem_dev *h = devs[0];
+      rc = fem_dev_stage_reads(h, 0, &sample);
+      if (!rc) rc = fem_dev_map_staged(h, 0, &params);
+      if (!rc) rc = fem_dev_estimate_insert(h, 0, &est);
+      if (rc) dev_fail(h, "insert size estimate", rc);
+    }
+    for (fem_seqset &s : mate) fem_seqset_free(&s);
+    if (rc) return EXIT_FAILURE;
+    if (sampled && est.estimated) {
+      const fem_pair_params pp{est.min_insert, est.max_insert};
+      for (fem_dev *h : devs) {
+        int32_t ns = 4;
+        (void)fem_dev_limits(h, nullptr, &ns);
+        for (int sl = 0; sl < ns; ++sl)
+          if ((rc = fem_dev_set_pairs(h, sl, &pp))) return dev_fail(h, "insert size range", rc);
+      }
+      fprintf(stderr, "Inferred insert size range: %d-%d (quartiles %d %d %d, %lu informative of %lu pairs).\n", est.min_insert, est.max_insert,
+              est.q25, est.q50, est.q75, (unsigned long)est.n_informative, (unsigned long)est.n_pairs);
+    } else if (sampled) {
+      fprintf(stderr, "Insert size range not inferred (%lu informative of %lu pairs, %d needed): using %lld-%lld.\n",
+              (unsigned long)est.n_informative, (unsigned long)est.n_pairs, FEM_INSERT_MIN_PAIRS, min_insert, max_insert);
+    }
+    const char *st = getenv("FEM_STAGE_TIMES");
+    if (st && (st[0] == '1' || st[0] == '2')) fprintf(stderr, "[FEM] insert size pre-pass: %fs\n", real_time() - t_pre);
+  }
 
   const int out_fd = open(out_path, O_WRONLY | O_CREAT | O_TRUNC, 0666);
   if (out_fd < 0) {

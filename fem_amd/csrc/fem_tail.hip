@@ -2033,6 +2033,78 @@ __global__ void __launch_bounds__(256) pair_probe_kernel(PairParams p, uint8_t *
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// The insert size range the batch's own pairs suggest (fem_dev_estimate_insert).  A pair is unique when each
+// mate has exactly one record and neither carries 0x8000; a unique pair is informative when its two records are concordant
+// within 0 .. FEM_INSERT_MAX (the pairing rule's own statement: p.min_insert, p.max_insert are set to that, whatever the slot's
+// range is).  insert_sample_kernel: one lane per pair, one add into the histogram's bin of the insert; ctl[0] unique pairs,
+// ctl[1] informative ones.  insert_bounds_kernel (one block): the inserts in ascending order are v[0 .. n); q25 q50 q75 =
+// v[k (n - 1) / 4] to ctl[2 .. 4]; with n >= FEM_INSERT_MIN_PAIRS, ctl[7] = 1 and ctl[5], ctl[6] = max(0, q25 - 3 iqr),
+// q75 + 3 iqr (iqr = q75 - q25); else the three are 0.  n = 0: the quartiles are -1.
+// ---------------------------------------------------------------------------------------------------------
+constexpr uint32_t kInsertBins = FEM_INSERT_MAX + 1u;
+constexpr uint32_t kInsertCtl = 8;  // words behind the histogram
+
+__global__ void __launch_bounds__(256) insert_sample_kernel(PairParams p, uint32_t *hist, uint32_t *ctl) {
+  const uint32_t ln = threadIdx.x & 63u;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  bool unique = false, informative = false;
+  if (i < p.n_pairs) {
+    const uint32_t a0 = p.rec_begin[i], na = p.rec_begin[i + 1] - a0;
+    const uint32_t b0 = p.rec_begin[p.n_pairs + i], nb = p.rec_begin[p.n_pairs + i + 1] - b0;
+    if (na == 1u && nb == 1u) {
+      const MateRec ra = mate_rec(p, a0), rb = mate_rec(p, b0);
+      unique = !((ra.flag | rb.flag) & 0x8000u);
+      const int64_t ins = concordant(p, ra, rb);  // (-1 with 0x8000 on either)
+      informative = ins >= 0;
+      if (informative) atomicAdd(hist + (uint32_t)ins, 1u);  // (ins <= p.max_insert = FEM_INSERT_MAX)
+    }
+  }
+  const uint64_t unique_lanes = __ballot(unique), informative_lanes = __ballot(informative);
+  if (ln == 0 && unique_lanes) atomicAdd(ctl, (uint32_t)__builtin_popcountll(unique_lanes));
+  if (ln == 0 && informative_lanes) atomicAdd(ctl + 1, (uint32_t)__builtin_popcountll(informative_lanes));
+}
+
+__global__ void __launch_bounds__(256) insert_bounds_kernel(const uint32_t *hist, uint32_t *ctl) {
+  constexpr uint32_t kPerLane = kInsertBins / 256u;
+  static_assert(kPerLane * 256u == kInsertBins, "every lane sums as many bins");
+  __shared__ uint32_t incl[256];  // inclusive scan of the lanes' sums
+  __shared__ int32_t q[3];
+  const uint32_t t = threadIdx.x, first = t * kPerLane;
+  uint32_t mine = 0;
+  for (uint32_t b = 0; b < kPerLane; ++b) mine += hist[first + b];
+  incl[t] = mine;
+  __syncthreads();
+  for (uint32_t d = 1; d < 256u; d <<= 1) {
+    const uint32_t below = t >= d ? incl[t - d] : 0u;
+    __syncthreads();
+    incl[t] += below;
+    __syncthreads();
+  }
+  const uint32_t n = incl[255], before = incl[t] - mine;
+  if (t < 3u) q[t] = -1;
+  __syncthreads();
+  if (n && mine) {
+    for (uint32_t k = 1; k <= 3u; ++k) {
+      const uint32_t rank = (uint32_t)((uint64_t)k * (n - 1u) / 4u);  // v[rank]
+      if (rank < before || rank >= before + mine) continue;
+      uint32_t seen = before, b = 0;
+      while (seen + hist[first + b] <= rank) seen += hist[first + b], ++b;  // (ends inside the stretch: rank < before + mine)
+      q[k - 1u] = (int32_t)(first + b);
+    }
+  }
+  __syncthreads();
+  if (t == 0) {
+    const int32_t q25 = q[0], q75 = q[2], iqr = q75 - q25;
+    const bool estimated = n >= (uint32_t)FEM_INSERT_MIN_PAIRS;
+    const int32_t lo = q25 - 3 * iqr;
+    ctl[2] = (uint32_t)q[0], ctl[3] = (uint32_t)q[1], ctl[4] = (uint32_t)q75;
+    ctl[5] = estimated ? (uint32_t)(lo < 0 ? 0 : lo) : 0u;
+    ctl[6] = estimated ? (uint32_t)(q75 + 3 * iqr) : 0u;
+    ctl[7] = estimated ? 1u : 0u;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // MAPQ (fem_dev_set_mapq).  One lane per read: q_se from its records' NM (d1 the first record's, c1 records
 // at d1; d2 the least NM above d1 and c2 records at it, or e + 1 and 1 where there is none): 0 when c1 >= 2, else
 // Q(d2 - d1, c2).  A read with more than kMapqAlone records is taken by its whole wave after the lanes' own reads (repeats:
@@ -2573,6 +2645,11 @@ static hipError_t copy_home(PinBuf<T> &dst, const DevBuf<S> &src, size_t first, 
   return hipMemcpyAsync(dst.get(), src.get() + first, count * sizeof(T), hipMemcpyDeviceToHost, stream);
 }
 
+// The words of h_ctl, the pinned buffer the kernels' counters come home in: 0 .. 3 run()'s ctl (2: a text's asserted records,
+// 3: bam()'s name check), 4 5 run()'s CIGAR and MD totals, 6 7 a text's size, 8 9 a line index's counts, from kCtlInsert on
+// estimate_insert()'s kInsertCtl words.
+constexpr size_t kCtlInsert = 12, kCtlWords = kCtlInsert + kInsertCtl;
+
 struct Tail::Impl {
   DevBuf<uint32_t> rec_begin, queue, ctl, u_misc, s_misc, s_read, t_ops, o_ops, ovf, rec_list, src_slot, n_ops, n_md, tid, pos0, cigar_off, md_off, cigar;
   DevBuf<uint64_t> u_cand, s_cand;
@@ -2609,6 +2686,8 @@ struct Tail::Impl {
   PinBuf<uint16_t> h_r_flag;
   PinBuf<uint8_t> h_r_nm;
   PinBuf<char> h_r_md;
+  // the insert estimate (estimate_insert()): the histogram's kInsertBins bins, then the kInsertCtl words of its outcome
+  DevBuf<uint32_t> ins_hist;
   // BAM (bam()): the name check, the record offsets home (the member cuts), the compressor
   DevBuf<uint32_t> bam_ctl;
   PinBuf<uint64_t> h_line_off;
@@ -2698,7 +2777,7 @@ struct Tail::Impl {
     not_run({kText, kMapq, kUnmappedIndex, kFilterIndex});
     TAIL_TRY(line_len.ensure(r1));
     TAIL_TRY(line_off.ensure(r1));
-    TAIL_TRY(h_ctl.ensure(12));
+    TAIL_TRY(h_ctl.ensure(kCtlWords));
     size_t need = 16;
     TAIL_TRY(scan_need(&need, line_len.get(), line_off.get(), 0ull, r1, rocprim::plus<unsigned long long>()));
     if (opt.unmapped || report) {
@@ -2875,7 +2954,7 @@ int Tail::reserve(uint32_t n, uint32_t nr, uint32_t max_len_in, int e, bool tiny
   TAIL_TRY(m.rec_begin.ensure((size_t)n + 1));
   TAIL_TRY(m.queue.ensure(std::max<size_t>(n, 1)));
   TAIL_TRY(m.ctl.ensure(4));
-  TAIL_TRY(m.h_ctl.ensure(12));
+  TAIL_TRY(m.h_ctl.ensure(kCtlWords));
   const size_t r1 = (size_t)nr + 1;
   TAIL_TRY(m.u_cand.ensure(r1));
   TAIL_TRY(m.u_misc.ensure(r1));
@@ -2930,7 +3009,8 @@ int Tail::warm(hipStream_t stream, std::string *err) {
                            (const void *)sam_len_kernel<false, true>, (const void *)sam_write_kernel<false, true>,
                            (const void *)sam_len_kernel<true, true>, (const void *)sam_write_kernel<true, true>,
                            (const void *)rescue_jobs_kernel, (const void *)pair_probe_kernel,
-                           (const void *)rescue_search_kernel, (const void *)rescue_trace_kernel, (const void *)rescue_append_kernel};
+                           (const void *)rescue_search_kernel, (const void *)rescue_trace_kernel, (const void *)rescue_append_kernel,
+                           (const void *)insert_sample_kernel, (const void *)insert_bounds_kernel};
   for (const void *k : kernels) TAIL_TRY(hipFuncGetAttributes(&a, k));
   if (!m.scan_tmp || !m.rec_begin || !m.n_ops || !m.line_len) return FEM_OK;  // (nothing reserved: the scans load with the first batch)
   TAIL_TRY(hipMemsetAsync(m.n_ops, 0, 4, stream));
@@ -3336,6 +3416,39 @@ int Tail::pair(const LineOptions &opt, const RescueInput &rescue, hipStream_t st
   TAIL_TRY(m.span[kPairing].end(stream));
   TAIL_TRY(hipMemcpyAsync(m.h_pair_ctl, m.pair_ctl, 4, hipMemcpyDeviceToHost, stream));
   m.paired = true, m.pair_mapq = opt.mapq;
+  return FEM_OK;
+}
+
+int Tail::estimate_insert(hipStream_t stream, InsertEstimate *out, std::string *err) {
+  if (!impl_ || !out) return FEM_ERR_STATE;
+  Impl &m = *impl_;
+  const uint32_t n = m.last_n, np = n / 2u;
+  if (n & 1u) {
+    if (err) *err = "a paired batch holds an even number of reads";
+    return FEM_ERR_INVALID;
+  }
+  TAIL_TRY(m.ins_hist.ensure(kInsertBins + kInsertCtl));
+  TAIL_TRY(m.h_ctl.ensure(kCtlWords));
+  uint32_t *hist = m.ins_hist, *ctl = hist + kInsertBins;
+  m.not_run({kInsert});
+  TAIL_TRY(m.span[kInsert].begin(stream));
+  TAIL_TRY(hipMemsetAsync(hist, 0, (kInsertBins + kInsertCtl) * sizeof(uint32_t), stream));
+  if (np) {
+    PairParams q{};
+    q.n_pairs = np, q.min_insert = 0, q.max_insert = FEM_INSERT_MAX;
+    m.bind_pairing(&q);
+    hipLaunchKernelGGL(insert_sample_kernel, dim3((np + 255u) / 256u), dim3(256), 0, stream, q, hist, ctl);
+    TAIL_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(insert_bounds_kernel, dim3(1), dim3(256), 0, stream, (const uint32_t *)hist, ctl);
+  TAIL_TRY(hipGetLastError());
+  TAIL_TRY(m.span[kInsert].end(stream));
+  const uint32_t *h = m.h_ctl + kCtlInsert;
+  TAIL_TRY(hipMemcpyAsync(m.h_ctl + kCtlInsert, ctl, kInsertCtl * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  TAIL_TRY(hipStreamSynchronize(stream));
+  out->n_pairs = np, out->n_unique = h[0], out->n_informative = h[1];
+  out->q25 = (int32_t)h[2], out->q50 = (int32_t)h[3], out->q75 = (int32_t)h[4];
+  out->min_insert = (int32_t)h[5], out->max_insert = (int32_t)h[6], out->estimated = h[7] != 0;
   return FEM_OK;
 }
 

@@ -134,6 +134,14 @@ struct LineCounts {
   uint64_t n_filtered = 0;            // lines the filter left out (0 without LineOptions::strata / max_hits)
 };
 
+// What estimate_insert() learns from the unique pairs of the last run() (include/fem_hip.h, fem_dev_estimate_insert: the rule).
+struct InsertEstimate {
+  uint64_t n_pairs, n_unique, n_informative;
+  int32_t q25, q50, q75;           // -1 without an informative pair
+  int32_t min_insert, max_insert;  // 0 unless estimated
+  bool estimated;
+};
+
 // One text on its way home at a time (per GPU).  Two device-to-host copies queued in the copy engines take both of them, and
 // the next batch's reads wait for their copy in until every queued text is home (scratch/sdma_probe.hip: a 30 MB copy in
 // behind ONE 300 MB copy out is done after 0.6 ms, behind four after all four, 22 ms); FEM map's device then alternated
@@ -147,8 +155,8 @@ struct TextGate {
 // The timed stages of a batch's way out of the device.  Each runs between two events on its stream, recorded whether or not
 // anybody asks (Tail::stage_ms).  run(): kOrder, kTrace, kCompact.  pair(): kRescue when it rescues, kPairing.  sam() / bam():
 // kMapq with LineOptions::mapq; kFilterIndex, the line index with the line filter, or else kUnmappedIndex, the one with
-// LineOptions::unmapped alone; kText, the SAM text's or the BAM records' kernels.
-enum Stage { kOrder, kTrace, kCompact, kText, kPairing, kRescue, kMapq, kUnmappedIndex, kFilterIndex, kStages };
+// LineOptions::unmapped alone; kText, the SAM text's or the BAM records' kernels.  estimate_insert(): kInsert.
+enum Stage { kOrder, kTrace, kCompact, kText, kPairing, kRescue, kMapq, kUnmappedIndex, kFilterIndex, kInsert, kStages };
 
 class Tail {
  public:
@@ -185,6 +193,10 @@ class Tail {
   // opt.mapq: pair_kernel also writes each line's pairing byte (qp and whether the chosen record may keep its own MAPQ), which the
   // next sam() / bam() with LineOptions::mapq turns into the MAPQ of the mates' primary lines.
   int pair(const LineOptions &opt, const RescueInput &rescue, hipStream_t stream, std::string *err);
+  // The insert size range the records of the last run() suggest (insert_sample_kernel, insert_bounds_kernel): the pairs whose
+  // mates have one record each, their inserts' quartiles, the fence around them.  Runs on `stream` and waits for it.  Reads the
+  // records only: what pair() made, the slot's options and the counts stay as they are.
+  int estimate_insert(hipStream_t stream, InsertEstimate *out, std::string *err);
   // The counts of the last pair() (all 0 unless it ran since the last run()) and of the last sam() / bam().
   LineCounts counts() const;
   // The device time of a stage, in ms.  Negative: the stage was not part of the last run() and of what followed it (pair(),

@@ -19,7 +19,7 @@ ABI_SYMBOLS = [
     "fem_dev_h2d_bandwidth", "fem_dbg_live_bytes",
     "fem_device_numa", "fem_bind_thread_near_device",
     "fem_dev_allreduce_stats",
-    "fem_dev_set_pairs", "fem_dev_fetch_pairs", "fem_dev_pair_count",
+    "fem_dev_set_pairs", "fem_dev_fetch_pairs", "fem_dev_pair_count", "fem_dev_estimate_insert",
     "fem_dev_set_rescue", "fem_dev_rescue_count", "fem_dev_set_rescue_discordant", "fem_dev_rescue_discordant_count", "fem_dev_set_mapq",
     "fem_dev_set_unmapped", "fem_dev_unmapped_count",
     "fem_dev_set_report", "fem_dev_filtered_count", "fem_dev_set_tags",
@@ -70,6 +70,12 @@ class _BatchBam(C.Structure):
 
 class _PairParams(C.Structure):
     _fields_ = [("min_insert", C.c_int32), ("max_insert", C.c_int32)]
+
+
+class _InsertEstimate(C.Structure):
+    _fields_ = [("n_pairs", C.c_uint64), ("n_unique", C.c_uint64), ("n_informative", C.c_uint64),
+                ("q25", C.c_int32), ("q50", C.c_int32), ("q75", C.c_int32),
+                ("min_insert", C.c_int32), ("max_insert", C.c_int32), ("estimated", C.c_int32)]
 
 
 class _RescueParams(C.Structure):
@@ -160,6 +166,8 @@ def load_hip():
         L.fem_dev_set_pairs.argtypes = [vp, C.c_int, C.POINTER(_PairParams)]
         L.fem_dev_fetch_pairs.argtypes = [vp, C.c_int, C.POINTER(_BatchPairs)]
         L.fem_dev_pair_count.argtypes = [vp, C.c_int, C.POINTER(u64)]
+    if hasattr(L, "fem_dev_estimate_insert"):
+        L.fem_dev_estimate_insert.argtypes = [vp, C.c_int, C.POINTER(_InsertEstimate)]
     if hasattr(L, "fem_dev_set_rescue"):
         L.fem_dev_set_rescue.argtypes = [vp, C.c_int, C.POINTER(_RescueParams)]
         L.fem_dev_rescue_count.argtypes = [vp, C.c_int, C.POINTER(u64)]
@@ -364,6 +372,21 @@ class BatchPairs:
         self.mate_pos0 = _copy(r.mate_pos0, nr, np.uint32)
         self.tlen = _copy(r.tlen, nr, np.int32)
         self.stats = np.array(list(r.stats), dtype=np.uint64)
+
+
+class InsertEstimate:
+    """fem_insert_estimate: what a batch of read pairs says about the library's insert sizes (include/fem_hip.h: the rule)."""
+    FIELDS = ("n_pairs", "n_unique", "n_informative", "q25", "q50", "q75", "min_insert", "max_insert", "estimated")
+
+    def __init__(self, r):
+        for f in self.FIELDS:
+            setattr(self, f, int(getattr(r, f)))
+
+    def as_tuple(self):
+        return tuple(getattr(self, f) for f in self.FIELDS)
+
+    def __repr__(self):
+        return "InsertEstimate(%s)" % ", ".join("%s=%d" % (f, getattr(self, f)) for f in self.FIELDS)
 
 
 class Device:
@@ -601,6 +624,13 @@ class Device:
         r = _BatchPairs()
         self._check(self._L.fem_dev_fetch_pairs(self._h, slot, C.byref(r)))
         return BatchPairs(r)
+
+    def estimate_insert(self, slot=0):
+        """fem_dev_estimate_insert: the insert size range the slot's batch of read pairs suggests (InsertEstimate), from its
+        unique pairs, on the device; the slot's options and later fetches are untouched."""
+        r = _InsertEstimate()
+        self._check(self._L.fem_dev_estimate_insert(self._h, slot, C.byref(r)))
+        return InsertEstimate(r)
 
     def pair_count(self, slot=0):
         """fem_dev_pair_count: proper pairs of the slot's last paired text."""

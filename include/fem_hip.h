@@ -342,6 +342,32 @@ int fem_dev_fetch_pairs(fem_dev *h, int slot, fem_batch_pairs *out);
 /* Proper pairs of the slot's last paired SAM text (valid once fem_dev_fetch_sam[_nowait] has returned) or fem_dev_fetch_pairs. */
 int fem_dev_pair_count(fem_dev *h, int slot, uint64_t *n_proper);
 
+/* ---- the insert size range, learned from a batch (new; it changes nothing: a caller takes the range and sets it) ----
+ * fem_dev_estimate_insert: what the slot's batch of read pairs says about the library's insert sizes, from the single-end
+ *   records fem_dev_fetch_records makes (which it runs: sync + mapping tail), on the device.  FEM_ERR_STATE without pair mode,
+ *   FEM_ERR_INVALID for a null out or, at fetch time, an odd n_reads.  It needs no text stage and no reference names, changes
+ *   none of the slot's options and none of its counts: a fem_dev_fetch_sam, _bam or _pairs of the same batch afterwards gives
+ *   what it gives without the call.  The slot's own min_insert / max_insert play no part.
+ * Rule (integers throughout).  Over the pairs of the batch (read i and read n_reads/2 + i):
+ *   1. A pair is unique when each mate has exactly one record and neither record carries 0x8000.
+ *   2. A unique pair is informative when both records lie on one sequence on opposite strands, the forward one f starts at or
+ *      before the reverse one r (pos0(f) <= pos0(r)) and ins = end0(r) - pos0(f) <= FEM_INSERT_MAX (end0 = pos0 + the M and D
+ *      lengths of the CIGAR): the pairing rule above with the range 0 .. FEM_INSERT_MAX.
+ *   3. v[0..n) the informative inserts in ascending order: q25 = v[(n - 1) / 4], q50 = v[2 (n - 1) / 4], q75 = v[3 (n - 1) / 4]
+ *      (integer division); iqr = q75 - q25.  n == 0: the three are -1.
+ *   4. estimated = n >= FEM_INSERT_MIN_PAIRS; then min_insert = max(0, q25 - 3 iqr), max_insert = q75 + 3 iqr (the quartile
+ *      fence; max_insert - min_insert <= 65532, so fem_dev_set_rescue's window limit holds for a learned range).  Else both
+ *      are 0 and mean nothing. */
+#define FEM_INSERT_MAX 16383
+#define FEM_INSERT_MIN_PAIRS 64
+typedef struct {
+  uint64_t n_pairs, n_unique, n_informative;
+  int32_t q25, q50, q75;
+  int32_t min_insert, max_insert;
+  int32_t estimated;
+} fem_insert_estimate;
+int fem_dev_estimate_insert(fem_dev *h, int slot, fem_insert_estimate *out);
+
 /* ---- mate rescue (new; opt-in: with it off every paired output stays byte for byte what it is without it) ----
  * fem_dev_set_rescue: the slot's read pairs are rescued at max_edits = E edits (0 <= E <= 15, else FEM_ERR_INVALID); NULL: off.
  *   It takes effect with pair mode (fem_dev_set_pairs); fetch time refuses max_insert - min_insert > 65536 (FEM_ERR_UNSUPPORTED).
@@ -525,7 +551,9 @@ int fem_dev_index_info(const fem_dev *h, char *buf, uint64_t cap);
  * 14 = the line index kernels of a fem_dev_fetch_sam / fem_dev_fetch_bam with fem_dev_set_unmapped on (one entry per call;
  * the unmapped reads' lines themselves are written by the text and BAM record kernels: 7 and 11; none with a line filter set);
  * 15 = the line filter's line index kernels of a fem_dev_fetch_sam / fem_dev_fetch_bam with fem_dev_set_report on (one entry
- * per call; they make the unmapped reads' part of the index too, so 14 has no entry then). */
+ * per call; they make the unmapped reads' part of the index too, so 14 has no entry then);
+ * 16 = the insert sampling and bounds kernels of fem_dev_estimate_insert (one entry per call, the zeroing of the histogram
+ * included; its fem_dev_fetch_records counts 3, 4 and 5 as any other; no fetch of records, text or pairs counts here). */
 int fem_dev_set_timing(fem_dev *h, int on);
 int fem_dev_reset_timing(fem_dev *h);
 int fem_dev_kernel_time(fem_dev *h, int kernel, double *ms_total, uint64_t *launches);
