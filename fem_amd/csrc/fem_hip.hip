@@ -58,7 +58,7 @@ constexpr size_t kPackedFrontPad = 256;  // ... and verify_kernel_packed up to 1
 constexpr uint64_t kExpandAllShare = 8;  // a packed batch with more exceptions than one per this many reads is expanded whole at commit
 constexpr uint32_t kXcapSmall = 512, kFcap = 128, kCcap = 128;
 
-constexpr int kTimedKernels = 17;  // fem_dev_kernel_time ids: 0 seed (join), 1 verify, 2 generic seed, 3-5 tail, 6 pack_results_kernel (round 5; the count kernel of rounds 1-2 before), 7 SAM text, 8 seed selection, 9 pairing, 10 mate rescue, 11 BAM records, 12 BGZF, 13 MAPQ, 14 the line index with unmapped reads, 15 the line filter's line index, 16 the insert estimate; 3-5, 7, 9-11 and 13-15 are stages of the device tail (kTailStages), 16 is one too (fem_dev_estimate_insert counts it itself)
+constexpr int kTimedKernels = 18;  // fem_dev_kernel_time ids: 0 seed (join), 1 verify, 2 generic seed, 3-5 tail, 6 pack_results_kernel (round 5; the count kernel of rounds 1-2 before), 7 SAM text, 8 seed selection, 9 pairing, 10 mate rescue, 11 BAM records, 12 BGZF, 13 MAPQ, 14 the line index with unmapped reads, 15 the line filter's line index, 16 the insert estimate, 17 the mate tags' score kernel; 3-5, 7, 9-11, 13-15 and 17 are stages of the device tail (kTailStages), 16 is one too (fem_dev_estimate_insert counts it itself)
 struct TimedLaunch {
   int kernel;
   hipEvent_t start, stop;
@@ -2128,6 +2128,7 @@ static const TailStage kTailStages[] = {
     {femt::kMapq, 13, [](const femt::LineOptions &o) { return o.mapq; }},  // (its events precede the text's sizing, which sam() and bam() wait for)
     {femt::kUnmappedIndex, 14, [](const femt::LineOptions &o) { return o.unmapped && !o.filters(); }},  // (as do these)
     {femt::kFilterIndex, 15, [](const femt::LineOptions &o) { return o.filters(); }},  // (whose line index is the unmapped reads' too: no 14 then)
+    {femt::kMateScore, 17, [](const femt::LineOptions &o) { return o.mates(); }},  // (a text with mate tags has its qualities on the device: tail_records)
 };
 
 // Timing: counts the stages of the slot's last fetch once each, with their device time where the tail has one.  text_id: the
@@ -2153,6 +2154,8 @@ static int tail_records(fem_dev *h, int slot, const void *out, bool copy_records
   Slot &s = h->slot[slot];
   const bool text = !copy_records;
   if (text && !s.text_staged) return fail(h, FEM_ERR_STATE, "qualities and names of this batch were not committed (fem_dev_commit_text_stage)");
+  if (text && s.opt.mates() && s.host_quals)
+    return fail(h, FEM_ERR_INVALID, "mate tags (fem_dev_set_mate_tags) need the qualities on the device: ms:i is made from them (fem_dev_commit_text_stage, not _names_stage)");
   if (device_quals && s.host_quals) return fail(h, FEM_ERR_STATE, "BAM records need the qualities on the device (fem_dev_commit_text_stage, not _names_stage)");
   if (text && !h->d_ref_names) return fail(h, FEM_ERR_STATE, "reference names must be uploaded first (fem_dev_upload_reference_names)");
   s.prefetch_results = false;  // this caller takes records, not the per-candidate arrays
@@ -2318,6 +2321,10 @@ int fem_dev_set_mapq(fem_dev *h, int slot, int on) {
 }
 int fem_dev_set_unmapped(fem_dev *h, int slot, int on) {
   return with_slot(h, slot, [&](Slot &s) { return s.opt.unmapped = on != 0, (int)FEM_OK; });
+}
+
+int fem_dev_set_mate_tags(fem_dev *h, int slot, int on) {
+  return with_slot(h, slot, [&](Slot &s) { return s.opt.mate_tags = on != 0, (int)FEM_OK; });
 }
 
 int fem_dev_set_report(fem_dev *h, int slot, const fem_report_params *rp) {

@@ -12,6 +12,7 @@
 // `--strata INT` / `--max-hits INT` leave out the lines of a read beyond its best strata / its first INT (fem_dev_set_report).
 // `--header` puts @HD in front of the @SQ lines and @PG behind them; `--rg LINE` adds the @RG line and RG:Z on every line, `--nh`
 // NH:i and HI:i on every mapped line, both made on the device (fem_dev_set_tags).
+// `--mate-tags` adds MC:Z, MQ:i and ms:i to every line of a paired output, made on the device (fem_dev_set_mate_tags).
 #include <errno.h>
 #include <fcntl.h>
 #include <getopt.h>
@@ -90,6 +91,7 @@ void usage_map() {
   fprintf(stderr, "        --rg     STR  a whole @RG line, its fields separated by tabs or \\t ('@RG\\tID:x\\tSM:y'): written into the header\n");
   fprintf(stderr, "                      (implies --header), and every line gets RG:Z:<ID>\n");
   fprintf(stderr, "        --nh          write NH:i (the read's, or the mate's, lines in the output) and HI:i (which of them) on every mapped line\n");
+  fprintf(stderr, "        --mate-tags   with --read2: write MC:Z, MQ:i and ms:i (the other mate's CIGAR, MAPQ and quality score, as samtools fixmate -m) on every line\n");
   fprintf(stderr, "        -o       STR  Output SAM file \n\n");
 }
 
@@ -308,6 +310,7 @@ int map_main(int argc, char **argv) {
   bool header = false;  // --header: @HD in front of the @SQ lines, @PG behind them
   const char *rg_arg = nullptr;  // --rg: the @RG line (implies --header) and RG:Z on every line, made on the device (fem_dev_set_tags)
   bool hit_tags = false;         // --nh: NH:i and HI:i on every mapped line, made on the device (fem_dev_set_tags)
+  bool mate_tags = false;        // --mate-tags: MC:Z, MQ:i and ms:i on every line of a paired output, made on the device (fem_dev_set_mate_tags)
   fem_params params{12, 3, 2, 1};  // src/FEM_map.c:67-70: k and step are fixed, whatever the index header says
   int n_threads = 1, n_gpus = 1;
   // reads per batch: 250 k fills the pipeline soonest on small inputs; a batch costs three host round trips on its way through
@@ -327,7 +330,7 @@ int map_main(int argc, char **argv) {
                                      {"unmapped", no_argument, nullptr, 'U'},
                                      {"strata", required_argument, nullptr, 'S'}, {"max-hits", required_argument, nullptr, 'N'},
                                      {"header", no_argument, nullptr, 'H'},      {"rg", required_argument, nullptr, 'T'},
-                                     {"nh", no_argument, nullptr, 'n'},
+                                     {"nh", no_argument, nullptr, 'n'},          {"mate-tags", no_argument, nullptr, 'M'},
                                      {nullptr, 0, nullptr, 0}};
   int c, oi = 0;
   while ((c = getopt_long(argc, argv, short_opt, long_opt, &oi)) >= 0) {
@@ -335,6 +338,7 @@ int map_main(int argc, char **argv) {
       case 'H': header = true; break;
       case 'T': rg_arg = optarg, header = true; break;
       case 'n': hit_tags = true; break;
+      case 'M': mate_tags = true; break;
       case 'r': ref_path = optarg; break;
       case 'i': index_path = optarg; break;
       case 'b': read_path = optarg; break;
@@ -410,6 +414,7 @@ int map_main(int argc, char **argv) {
   else if (min_insert < 0 || max_insert < min_insert || max_insert > (1ll << 30)) bad = "Wrong insert size range.";
   else if (infer_insert && !read2_path) bad = "--infer-insert needs read pairs (--read2).";
   else if (infer_insert && (infer_pairs < 64 || infer_pairs > 262144)) bad = "Wrong number of pairs to infer from (64-262144).";
+  else if (mate_tags && !read2_path) bad = "--mate-tags needs --read2.";
   else if (rescue_discordant && !rescue_given) bad = "--rescue-discordant needs --rescue.";
   else if (rescue_given && !read2_path) bad = "--rescue needs read pairs (--read2).";
   else if (rescue_given && (rescue_edits < 0 || rescue_edits > 15)) bad = "Wrong rescue error threshold (0-15).";
@@ -434,6 +439,13 @@ int map_main(int argc, char **argv) {
     const char *x = getenv(v);
     if (bam && x && x[0] == '1') {
       fprintf(stderr, "--bam is not supported with %s=1: BAM records are made on the device, with the qualities there.\n", v);
+      exit(EXIT_FAILURE);
+    }
+  }
+  for (const char *v : {"FEM_HOST_TAIL", "FEM_HOST_FORMAT", "FEM_HOST_QUALS"}) {  // (nor can ms:i be: it is a sum over the mate's qualities)
+    const char *x = getenv(v);
+    if (mate_tags && x && x[0] == '1') {
+      fprintf(stderr, "--mate-tags is not supported with %s=1: the mate tags are made on the device, with the qualities there.\n", v);
       exit(EXIT_FAILURE);
     }
   }
@@ -504,7 +516,7 @@ int map_main(int argc, char **argv) {
   // to box (the run is bound by the link in one and by the cores in the other); from 24 threads on the qualities stay on the
   // host.  FEM_HOST_QUALS=1 / FEM_DEVICE_QUALS=1 decide it by hand.
   const char *dq = getenv("FEM_DEVICE_QUALS"), *hq = getenv("FEM_HOST_QUALS");
-  const bool host_quals = device_text && !bam && !(dq && dq[0] == '1') && ((hq && hq[0] == '1') || n_threads >= 24);
+  const bool host_quals = device_text && !bam && !mate_tags && !(dq && dq[0] == '1') && ((hq && hq[0] == '1') || n_threads >= 24);
   const bool splice = !host_tail && !device_text && !(spl && spl[0] == '0');
   // With the text on the device the link is what bounds the run: batches of equal-length reads then cross it at two bits per
   // base — the parser writes that form straight into the pinned staging (fem_seqfile_fill_packed ->
@@ -563,7 +575,8 @@ int map_main(int argc, char **argv) {
                                                                   // (--unmapped: a read of which nothing maps still has a line of its name, bases and qualities)
                                                                   // (--rg / --nh: the tags of a line, one line per read at the least)
                                                                   batch_bytes + batch_bytes / (unmapped ? 2 : 4) +
-                                                                      reads_cap0 * ((rg_arg ? 6 + strlen(rg_id) : 0) + (hit_tags ? 16 : 0)));
+                                                                      // (--mate-tags: MC of a few operations, MQ, ms)
+                                                                      reads_cap0 * ((rg_arg ? 6 + strlen(rg_id) : 0) + (hit_tags ? 16 : 0) + (mate_tags ? 16 + 9 + 12 : 0)));
           // (a read over the device's limit among the first records: no reservation, the staging of its batch names the read)
           if (!rc && device_text && res_reads && res_len <= max_read_len) rc = fem_dev_reserve_batch(devs[(size_t)g], sl, res_reads, res_reads + res_reads / 8, res_len, &params);
           if (!rc && mapq) rc = fem_dev_set_mapq(devs[(size_t)g], sl, 1);
@@ -579,6 +592,7 @@ int map_main(int argc, char **argv) {
           if (!rc && paired) {
             const fem_pair_params pp{(int32_t)min_insert, (int32_t)max_insert};
             rc = fem_dev_set_pairs(devs[(size_t)g], sl, &pp);
+            if (!rc && mate_tags) rc = fem_dev_set_mate_tags(devs[(size_t)g], sl, 1);
             if (!rc && rescue_given) {
               const fem_rescue_params rp{(int32_t)rescue_edits};
               rc = fem_dev_set_rescue(devs[(size_t)g], sl, &rp);

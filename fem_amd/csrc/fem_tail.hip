@@ -1146,6 +1146,10 @@ struct SamParams {
   uint32_t hit_tags;            // != 0: NH and HI
   const uint32_t *hit_begin;    // n_reads + 1, by slot: slot s has the lines [hit_begin[s], hit_begin[s + 1]) ...
   uint32_t hit_by_line;         // ... of the output (the line filter's scan), else of the records (pair mode: of pair_kernel's lines)
+  // the mate tags behind those (fem_dev_set_mate_tags; the kernels' kMate instances): MC:Z MQ:i ms:i
+  uint32_t mate_tags;           // != 0: the kMate instances run
+  const uint32_t *mate_begin;   // pair_kernel's pair_begin, with or without lines for unmapped reads (pair_begin above is theirs)
+  const uint32_t *mate_score;   // per read, mate_score_kernel's; nullptr: no qualities on the device, no ms
 };
 
 __device__ __forceinline__ uint32_t dec_digits(uint32_t v) {
@@ -1274,7 +1278,47 @@ __device__ __forceinline__ uint32_t bam_tags_len(const SamParams &p, bool mapped
   return (mapped && p.hit_tags ? 14u : 0u) + (p.rg_len ? 4u + p.rg_len : 0u);
 }
 
-// The line of an unmapped read: QNAME FLAG RNAME POS 0 * RNEXT PNEXT 0 SEQ QUAL, no tags but RG
+// ---- the mate tags (include/fem_hip.h, fem_dev_set_mate_tags): MC:Z MQ:i ms:i, the last fields of every line of a
+//      paired text ----
+// What the lines of read r say of the other mate.  has: it has a record; then the CIGAR words [c0, c0 + n_ops) and the MAPQ column of
+// its primary line, pair_kernel's first line of that slot (where placed_at looks, too).  has_ms: the batch has qualities on the device;
+// ms is mate_score_kernel's number of the other read, mapped or not.
+struct MateTags {
+  bool has, has_ms;
+  uint32_t c0, n_ops, mq, ms;
+};
+__device__ __forceinline__ MateTags mate_tags(const SamParams &p, uint32_t r) {
+  const uint32_t np = p.n_reads / 2u, o = pair_slot(p, r) ^ 1u, k0 = p.mate_begin[o];
+  MateTags m{p.mate_begin[o + 1] != k0, p.mate_score != nullptr, 0u, 0u, 0u, 0u};
+  if (m.has) {
+    const uint32_t rec0 = p.perm[k0];
+    m.c0 = p.cigar_off[rec0], m.n_ops = p.cigar_off[rec0 + 1] - m.c0;
+    m.mq = line_mapq<true>(p, k0, 0u, true);
+  }
+  if (m.has_ms) m.ms = p.mate_score[r < np ? r + np : r - np];
+  return m;
+}
+// The characters of CIGAR words [c0, c0 + n_ops) as SAM prints them, and their printing
+__device__ __forceinline__ uint32_t cigar_chars(const SamParams &p, uint32_t c0, uint32_t n_ops) {
+  uint32_t n = 0;
+  for (uint32_t c = c0; c < c0 + n_ops; ++c) n += dec_digits(p.cigar[c] >> 4) + 1u;
+  return n;
+}
+__device__ __forceinline__ uint8_t *put_cigar_op(uint8_t *q, uint32_t op) {
+  q = put_dec(q, op >> 4);
+  *q++ = (uint8_t)"MIDNSHP=XB"[op & 0xFu];
+  return q;
+}
+// SAM: "\tMC:Z:<cigar>" (cig: the CIGAR's characters; none for a primary line that prints *), "\tMQ:i:<n>", "\tms:i:<n>"
+__device__ __forceinline__ uint32_t mate_tags_len(const MateTags &m, uint32_t cig) {
+  return (m.has && m.n_ops ? 6u + cig : 0u) + (m.has ? 6u + dec_digits(m.mq) : 0u) + (m.has_ms ? 6u + dec_digits(m.ms) : 0u);
+}
+// BAM: MC as type Z (the characters and a NUL), MQ as type C, ms as type I
+__device__ __forceinline__ uint32_t bam_mate_tags_len(const MateTags &m, uint32_t cig) {
+  return (m.has && m.n_ops ? 4u + cig : 0u) + (m.has ? 4u : 0u) + (m.has_ms ? 7u : 0u);
+}
+
+// The line of an unmapped read: QNAME FLAG RNAME POS 0 * RNEXT PNEXT 0 SEQ QUAL, no tags but RG (and the mate tags behind it)
 __device__ __forceinline__ uint32_t unmapped_len(const SamParams &p, const Unmapped &u) {
   const uint32_t name_len = (uint32_t)(p.name_off[u.r + 1] - p.name_off[u.r]), L = (uint32_t)(p.read_off[u.r + 1] - p.read_off[u.r]);
   const uint32_t rname = u.t == kNoMate ? 1u : p.ref_name_off[u.t + 1] - p.ref_name_off[u.t], pos = dec_digits(u.pos0 + 1u);
@@ -1282,8 +1326,13 @@ __device__ __forceinline__ uint32_t unmapped_len(const SamParams &p, const Unmap
          rg_tag_len(p) + 1u;
 }
 
-template <bool kPair, bool kUnm = false>
+template <bool kPair, bool kUnm = false, bool kMate = false>
 __global__ void __launch_bounds__(256) sam_len_kernel(SamParams p) {
+  static_assert(kPair || !kMate, "mate tags are a paired text's");
+  auto mates = [&](uint32_t r) -> uint32_t {  // the mate tags of a line of read r
+    const MateTags m = mate_tags(p, r);
+    return mate_tags_len(m, cigar_chars(p, m.c0, m.n_ops));
+  };
   const uint32_t stride = gridDim.x * blockDim.x;
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i <= p.n_records; i += stride) {
     if (i == p.n_records || (kUnm && i >= p.u_lines[0])) {
@@ -1294,7 +1343,7 @@ __global__ void __launch_bounds__(256) sam_len_kernel(SamParams p) {
     if (kUnm) {
       j = p.usrc[i];
       if (j >= p.u_base) {
-        p.line_len[i] = unmapped_len(p, unmapped_line<kPair>(p, j - p.u_base));
+        p.line_len[i] = unmapped_len(p, unmapped_line<kPair>(p, j - p.u_base)) + (kMate ? mates(j - p.u_base) : 0u);
         continue;
       }
     }
@@ -1309,7 +1358,7 @@ __global__ void __launch_bounds__(256) sam_len_kernel(SamParams p) {
     const uint32_t seq_qual = primary ? seq_qual_len(p, L) : 3u;
     const uint32_t mate = kPair ? mate_cols_len(p, mate_cols<kUnm>(p, j, r), t) : 5u;
     const uint32_t mq = line_mapq<kPair>(p, j, r, primary);
-    const uint32_t tags = (p.hit_tags ? hit_tags_len(hit_tags<kPair>(p, i, j, r)) : 0u) + rg_tag_len(p);
+    const uint32_t tags = (p.hit_tags ? hit_tags_len(hit_tags<kPair>(p, i, j, r)) : 0u) + rg_tag_len(p) + (kMate ? mates(r) : 0u);
     p.line_len[i] = (unsigned long long)name_len + 1u + dec_digits(flag & 0x7FFFu) + 1u + rname_len + 1u + dec_digits(p.pos0[rec] + 1u) + 2u +
                     dec_digits(mq) + cig + 2u + mate + seq_qual + 6u + dec_digits(p.nm[rec]) + 6u + md_len + tags + 1u;
   }
@@ -1325,8 +1374,11 @@ __global__ void __launch_bounds__(256) sam_len_kernel(SamParams p) {
 // no CIGAR, no MD, no tags but RG.
 // The tags behind MD:Z (p.hit_tags, p.rg_len: the same in every lane): NH and HI are short fields; the ID is a long one, the same
 // bytes on every line, so each lane loads its bytes of it (up to four: 255 characters) once, in front of the records.
-template <bool kPair, bool kUnm = false>
+// kMate: MC, MQ and ms are three more short fields of the lane's own line, the other mate's first CIGAR operations in registers as
+// the line's own are.
+template <bool kPair, bool kUnm = false, bool kMate = false>
 __global__ void __launch_bounds__(256) sam_write_kernel(SamParams p) {
+  static_assert(kPair || !kMate, "mate tags are a paired text's");
   __shared__ uint8_t lut[256];
   lut[threadIdx.x] = kSamSeqLut[threadIdx.x];
   __syncthreads();
@@ -1394,7 +1446,25 @@ __global__ void __launch_bounds__(256) sam_write_kernel(SamParams p) {
   if (hits) ht = hit_tags<kPair>(p, j, src, r);
   const uint32_t o_hit = o_md + md_len;
   const uint32_t o_rg = o_hit + (hits ? hit_tags_len(ht) : 0u);
-  const uint32_t o_end = o_rg + rg_tag_len(p);
+  const uint32_t o_mate = o_rg + rg_tag_len(p);
+  MateTags mt{};
+  uint32_t mop_a = 0, mop_b = 0, mop_c = 0, mate_len = 0;
+  if (kMate) {
+    mt = mate_tags(p, r);
+    if (mt.n_ops > 0) mop_a = p.cigar[mt.c0];
+    if (mt.n_ops > 1) mop_b = p.cigar[mt.c0 + 1];
+    if (mt.n_ops > 2) mop_c = p.cigar[mt.c0 + 2];
+    uint32_t mcig = 0;
+    if (mt.n_ops <= 3u) {
+      if (mt.n_ops > 0) mcig += dec_digits(mop_a >> 4) + 1u;
+      if (mt.n_ops > 1) mcig += dec_digits(mop_b >> 4) + 1u;
+      if (mt.n_ops > 2) mcig += dec_digits(mop_c >> 4) + 1u;
+    } else {
+      mcig = cigar_chars(p, mt.c0, mt.n_ops);
+    }
+    mate_len = mate_tags_len(mt, mcig);
+  }
+  const uint32_t o_end = o_mate + mate_len;
   if (mine) {  // the short fields of the lane's own record
     uint8_t *w = p.text + at;
     w[name_len] = '\t';
@@ -1464,6 +1534,28 @@ __global__ void __launch_bounds__(256) sam_write_kernel(SamParams p) {
     if (p.rg_len) {
       q = w + o_rg;
       q[0] = '\t', q[1] = 'R', q[2] = 'G', q[3] = ':', q[4] = 'Z', q[5] = ':';
+    }
+    if (kMate) {
+      q = w + o_mate;
+      if (mt.has && mt.n_ops) {
+        q[0] = '\t', q[1] = 'M', q[2] = 'C', q[3] = ':', q[4] = 'Z', q[5] = ':';
+        q += 6;
+        if (mt.n_ops <= 3u) {
+          q = put_cigar_op(q, mop_a);
+          if (mt.n_ops > 1) q = put_cigar_op(q, mop_b);
+          if (mt.n_ops > 2) q = put_cigar_op(q, mop_c);
+        } else {
+          for (uint32_t c = mt.c0; c < mt.c0 + mt.n_ops; ++c) q = put_cigar_op(q, p.cigar[c]);
+        }
+      }
+      if (mt.has) {
+        q[0] = '\t', q[1] = 'M', q[2] = 'Q', q[3] = ':', q[4] = 'i', q[5] = ':';
+        q = put_dec(q + 6, mt.mq);
+      }
+      if (mt.has_ms) {
+        q[0] = '\t', q[1] = 'm', q[2] = 's', q[3] = ':', q[4] = 'i', q[5] = ':';
+        put_dec(q + 6, mt.ms);
+      }
     }
     w[o_end] = '\n';
   }
@@ -1567,8 +1659,13 @@ __device__ __forceinline__ uint32_t bam_reg2bin(uint32_t beg, uint32_t end) {  /
 }
 
 // Record sizes (block_size + 4); a read name over 254 characters in the batch sets *bad_name (l_read_name is a uint8).
-template <bool kPair, bool kUnm = false>
+template <bool kPair, bool kUnm = false, bool kMate = false>
 __global__ void __launch_bounds__(256) bam_len_kernel(SamParams p, uint32_t n_reads, uint32_t *bad_name) {
+  static_assert(kPair || !kMate, "mate tags are a paired text's");
+  auto mates = [&](uint32_t r) -> uint32_t {  // the mate tags of a record of read r
+    const MateTags m = mate_tags(p, r);
+    return bam_mate_tags_len(m, cigar_chars(p, m.c0, m.n_ops));
+  };
   const uint32_t stride = gridDim.x * blockDim.x;
   for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < n_reads; r += stride)
     if (p.name_off[r + 1] - p.name_off[r] > 254u) atomicOr(bad_name, 1u);
@@ -1582,7 +1679,8 @@ __global__ void __launch_bounds__(256) bam_len_kernel(SamParams p, uint32_t n_re
       j = p.usrc[i];
       if (j >= p.u_base) {  // an unmapped read: no CIGAR, SEQ and QUAL, no tags but RG
         const uint32_t r = j - p.u_base, L = (uint32_t)(p.read_off[r + 1] - p.read_off[r]);
-        p.line_len[i] = 36ull + (uint32_t)(p.name_off[r + 1] - p.name_off[r]) + 1u + (L + 1u) / 2u + L + bam_tags_len(p, false);
+        p.line_len[i] = 36ull + (uint32_t)(p.name_off[r + 1] - p.name_off[r]) + 1u + (L + 1u) / 2u + L + bam_tags_len(p, false) +
+                        (kMate ? mates(r) : 0u);
         continue;
       }
     }
@@ -1590,13 +1688,16 @@ __global__ void __launch_bounds__(256) bam_len_kernel(SamParams p, uint32_t n_re
     if (flag & 0x8000u) atomicAdd(p.asserted, 1u);
     const uint32_t n_ops = p.cigar_off[rec + 1] - p.cigar_off[rec], md_len = p.md_off[rec + 1] - p.md_off[rec];
     const uint32_t ls = primary ? L : 0u;
-    p.line_len[i] = 36ull + name_len + 1u + 4u * n_ops + (ls + 1u) / 2u + ls + 4u + 4u + md_len + bam_tags_len(p, true);
+    p.line_len[i] = 36ull + name_len + 1u + 4u * n_ops + (ls + 1u) / 2u + ls + 4u + 4u + md_len + bam_tags_len(p, true) + (kMate ? mates(r) : 0u);
   }
 }
 
-// One wave per record, a byte (or CIGAR word) per lane.
-template <bool kPair, bool kUnm = false>
+// One wave per record, a byte (or CIGAR word) per lane.  kMate: what the record says of the other mate is loaded in front of the
+// record's own bytes (four loads in a row: pair_begin, perm, cigar_off, cigar); the other mate's CIGAR as characters an operation
+// per lane, each lane's place the sum of the lengths in the lanes below it; MQ:C and ms:I a byte per lane.
+template <bool kPair, bool kUnm = false, bool kMate = false>
 __global__ void __launch_bounds__(256) bam_write_kernel(SamParams p) {
+  static_assert(kPair || !kMate, "mate tags are a paired text's");
   __shared__ uint8_t code4[256];  // read character -> 4-bit code of the letter the SAM text prints
   {
     const uint8_t ch = kSamSeqLut[threadIdx.x];
@@ -1639,6 +1740,12 @@ __global__ void __launch_bounds__(256) bam_write_kernel(SamParams p) {
       const MateCols mc = mate_cols<kUnm>(p, src, r);
       if (mc.mt != kNoMate) ntid = mc.mt, npos = mc.mp, tlen = (uint32_t)mc.tl;
     }
+  }
+  MateTags mt{};
+  uint32_t mop = 0;  // kMate: the other mate's CIGAR operation ln
+  if (kMate) {
+    mt = mate_tags(p, r);
+    if (ln < mt.n_ops) mop = p.cigar[mt.c0 + ln];
   }
   const uint64_t ro = p.read_off[r], no = p.name_off[r];
   const uint64_t at = p.line_off[j];
@@ -1689,7 +1796,62 @@ __global__ void __launch_bounds__(256) bam_write_kernel(SamParams p) {
     if (ln < 3u) x[ln] = (uint8_t)"RGZ"[ln];
     x += 3;
     for (uint32_t k = ln; k <= p.rg_len; k += 64u) x[k] = k < p.rg_len ? p.rg[k] : 0;
+    x += p.rg_len + 1u;
   }
+  if (kMate) {
+    if (mt.has && mt.n_ops) {
+      if (ln < 3u) x[ln] = (uint8_t)"MCZ"[ln];
+      uint8_t *y = x + 3;
+      uint32_t done = 0;  // characters of the operations in front of this round's
+      for (uint32_t cb = 0; cb < mt.n_ops; cb += 64u) {  // (a CIGAR of more than 64 operations goes round)
+        const uint32_t c = cb + ln, op = cb == 0 ? mop : c < mt.n_ops ? p.cigar[mt.c0 + c] : 0u;
+        const uint32_t len = c < mt.n_ops ? dec_digits(op >> 4) + 1u : 0u;
+        uint32_t end = len;
+        for (uint32_t o = 1; o < 64u; o <<= 1) {
+          const uint32_t below = __shfl_up(end, o);
+          if (ln >= o) end += below;
+        }
+        if (len) put_cigar_op(y + done + end - len, op);
+        done += __shfl(end, 63);
+      }
+      if (ln == 0) y[done] = 0;
+      x += 4u + done;
+    }
+    if (mt.has) {
+      if (ln < 4u) x[ln] = ln < 3u ? (uint8_t)"MQC"[ln] : (uint8_t)mt.mq;
+      x += 4;
+    }
+    if (mt.has_ms && ln < 7u) x[ln] = ln < 3u ? (uint8_t)"msI"[ln] : (uint8_t)(mt.ms >> (8u * (ln - 3u)));
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// ms:i of the mate tags (fem_dev_set_mate_tags): score[r] = the sum of b - 33 over read r's quality bytes b with
+// b - 33 >= 15.  One pass over the batch's qualities, 4 bytes written per read.  kScoreLanes lanes share a read, each taking 16
+// ALIGNED bytes per step (a read starts wherever the one before ended: the bytes of a chunk in front of the read's first and behind
+// its last are loaded and left out of the sum; a chunk that holds a byte of the array lies within its allocation).  Eight lanes
+// cover 128 bytes, which holds a 100-base read at any alignment in one step, and eight such reads fill a wave; a longer read
+// takes further steps.  The lanes' sums meet by shuffles within their group.
+// ---------------------------------------------------------------------------------------------------------
+constexpr uint32_t kScoreLanes = 8, kScoreChunk = 16;
+__global__ void __launch_bounds__(256) mate_score_kernel(const uint8_t *quals, const uint64_t *read_off, uint32_t n_reads, uint32_t *score) {
+  const uint32_t sub = threadIdx.x % kScoreLanes, r = blockIdx.x * (256u / kScoreLanes) + threadIdx.x / kScoreLanes;
+  const bool live = r < n_reads;  // (the lanes behind the last read run no step and add zero to nobody's sum)
+  const uintptr_t first = (uintptr_t)quals + (live ? read_off[r] : 0u), last = (uintptr_t)quals + (live ? read_off[r + 1] : 0u);
+  uint32_t sum = 0;
+  for (uintptr_t a = (first & ~(uintptr_t)(kScoreChunk - 1u)) + kScoreChunk * sub; a < last; a += kScoreChunk * kScoreLanes) {
+    const uint4 v = *(const uint4 *)a;
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    // the chunk's bytes [lo, hi) are the read's (a whole chunk inside it: 0, 16)
+    const uint32_t lo = a < first ? (uint32_t)(first - a) : 0u, hi = last - a < kScoreChunk ? (uint32_t)(last - a) : kScoreChunk;
+#pragma unroll
+    for (uint32_t k = 0; k < kScoreChunk; ++k) {
+      const uint32_t b = w[k / 4u] >> (8u * (k % 4u)) & 0xFFu;
+      if (k >= lo && k < hi && b >= 48u) sum += b - 33u;
+    }
+  }
+  for (uint32_t o = kScoreLanes / 2u; o; o >>= 1) sum += __shfl_xor(sum, o);
+  if (live && sub == 0) score[r] = sum;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2584,8 +2746,10 @@ __global__ void __launch_bounds__(256) rescue_append_kernel(RescueParams p) {
     }                                                                              \
   } while (0)
 
-// The <kPair, kUnm> instance of a text or BAM kernel (K: sam_len_kernel, sam_write_kernel, bam_len_kernel, bam_write_kernel)
-#define TEXT_KERNEL(K, pair, um) ((um) ? ((pair) ? K<true, true> : K<false, true>) : ((pair) ? K<true> : K<false>))
+// The <kPair, kUnm, kMate> instance of a text or BAM kernel (K: sam_len_kernel, sam_write_kernel, bam_len_kernel, bam_write_kernel)
+// (mate: its kMate form, which only paired texts have)
+#define TEXT_KERNEL(K, pair, um, mate) \
+  ((mate) ? ((um) ? K<true, true, true> : K<true, false, true>) : (um) ? ((pair) ? K<true, true> : K<false, true>) : ((pair) ? K<true> : K<false>))
 
 // A timed stage: what `stream` does between begin() and end().  A stage that starts where another one ends has no first
 // event of its own (follow()).  ran: it was recorded in the last call.
@@ -2675,6 +2839,8 @@ struct Tail::Impl {
   DevBuf<uint8_t> rg;
   PinBuf<uint8_t> h_rg;
   std::string rg_id;
+  // the mate tags (LineOptions::mate_tags): mate_score_kernel's number per read
+  DevBuf<uint32_t> m_score;
   PinBuf<uint32_t> h_perm, h_mtid, h_mpos0, h_pair_begin, h_pair_ctl;
   PinBuf<uint16_t> h_pflag;
   PinBuf<int32_t> h_tlen;
@@ -2760,6 +2926,8 @@ struct Tail::Impl {
   // above every source and pair_begin is nullptr (mate_cols), so that no line takes a shape it has not without the filter.
   // opt.read_group / opt.hit_tags (the tags behind MD:Z): the ID goes to the device when it is another than the last text's;
   // NH and HI read the slots' line ranges that are there already (hit_tags(), above): the filter's scan, or the index it began from.
+  // opt.mates() (the mate tags, the kernels' kMate instances): with qualities on the device mate_score_kernel runs in front of
+  // stage kText (stage kMateScore); without them the lines carry no ms.
   int lines(const TailInput &in, const SamInput &names, const LineOptions &opt, uint32_t *bad_name, hipStream_t stream, int n_cu,
             SamParams *p, std::string *err) {
     const bool pair_order = opt.paired, report = opt.filters();
@@ -2774,7 +2942,7 @@ struct Tail::Impl {
     }
     const uint32_t nr = n_base + (opt.unmapped ? last_n : 0u);
     const size_t r1 = (size_t)nr + 1, n1 = (size_t)last_n + 1;
-    not_run({kText, kMapq, kUnmappedIndex, kFilterIndex});
+    not_run({kText, kMapq, kUnmappedIndex, kFilterIndex, kMateScore});
     TAIL_TRY(line_len.ensure(r1));
     TAIL_TRY(line_off.ensure(r1));
     TAIL_TRY(h_ctl.ensure(kCtlWords));
@@ -2878,13 +3046,28 @@ struct Tail::Impl {
       }
       TAIL_TRY(span[kMapq].end(stream));
     }
+    if (opt.mates()) {
+      p->mate_tags = 1u, p->mate_begin = pair_begin;
+      if (names.quals) {
+        TAIL_TRY(m_score.ensure(std::max<size_t>(last_n, 1)));
+        TAIL_TRY(span[kMateScore].begin(stream));
+        if (last_n) {
+          const uint32_t per_block = 256u / kScoreLanes;
+          hipLaunchKernelGGL(mate_score_kernel, dim3((last_n + per_block - 1u) / per_block), dim3(256), 0, stream, names.quals, in.read_off, last_n,
+                             m_score.get());
+          TAIL_TRY(hipGetLastError());
+        }
+        TAIL_TRY(span[kMateScore].end(stream));
+        p->mate_score = m_score;
+      }
+    }
     if (bad_name) TAIL_TRY(hipMemsetAsync(bad_name, 0, 4, stream));
     TAIL_TRY(span[kText].begin(stream));
     const dim3 len_grid(std::max<uint32_t>(1u, std::min<uint32_t>((nr + 256u) / 256u, (uint32_t)n_cu * 16u)));
     if (bad_name)
-      hipLaunchKernelGGL(TEXT_KERNEL(bam_len_kernel, pair_order, um_kernels), len_grid, dim3(256), 0, stream, *p, last_n, bad_name);
+      hipLaunchKernelGGL(TEXT_KERNEL(bam_len_kernel, pair_order, um_kernels, opt.mates()), len_grid, dim3(256), 0, stream, *p, last_n, bad_name);
     else
-      hipLaunchKernelGGL(TEXT_KERNEL(sam_len_kernel, pair_order, um_kernels), len_grid, dim3(256), 0, stream, *p);
+      hipLaunchKernelGGL(TEXT_KERNEL(sam_len_kernel, pair_order, um_kernels, opt.mates()), len_grid, dim3(256), 0, stream, *p);
     TAIL_TRY(hipGetLastError());
     TAIL_TRY(scan(line_len.get(), line_off.get(), 0ull, r1, rocprim::plus<unsigned long long>(), stream));
     TAIL_TRY(hipMemcpyAsync(h_ctl + 2, ctl + 2, 4, hipMemcpyDeviceToHost, stream));
@@ -3010,7 +3193,10 @@ int Tail::warm(hipStream_t stream, std::string *err) {
                            (const void *)sam_len_kernel<true, true>, (const void *)sam_write_kernel<true, true>,
                            (const void *)rescue_jobs_kernel, (const void *)pair_probe_kernel,
                            (const void *)rescue_search_kernel, (const void *)rescue_trace_kernel, (const void *)rescue_append_kernel,
-                           (const void *)insert_sample_kernel, (const void *)insert_bounds_kernel};
+                           (const void *)insert_sample_kernel, (const void *)insert_bounds_kernel,
+                           (const void *)mate_score_kernel, (const void *)sam_len_kernel<true, false, true>,
+                           (const void *)sam_write_kernel<true, false, true>, (const void *)sam_len_kernel<true, true, true>,
+                           (const void *)sam_write_kernel<true, true, true>};
   for (const void *k : kernels) TAIL_TRY(hipFuncGetAttributes(&a, k));
   if (!m.scan_tmp || !m.rec_begin || !m.n_ops || !m.line_len) return FEM_OK;  // (nothing reserved: the scans load with the first batch)
   TAIL_TRY(hipMemsetAsync(m.n_ops, 0, 4, stream));
@@ -3220,7 +3406,7 @@ int Tail::sam(const TailInput &in, const SamInput &names, const LineOptions &opt
   if (nr) {
     p.text = m.text;
     const uint32_t blocks = (nr + 255u) / 256u;  // a wave per 64 records
-    hipLaunchKernelGGL(TEXT_KERNEL(sam_write_kernel, opt.paired, m.um_kernels), dim3(blocks), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL(TEXT_KERNEL(sam_write_kernel, opt.paired, m.um_kernels, opt.mates()), dim3(blocks), dim3(256), 0, stream, p);
     TAIL_TRY(hipGetLastError());
   }
   TAIL_TRY(m.span[kText].end(stream));
@@ -3258,7 +3444,7 @@ int Tail::bam(const TailInput &in, const SamInput &names, const LineOptions &opt
   TAIL_TRY(m.text.ensure(std::max<size_t>((size_t)total, 16)));
   if (nr) {
     p.text = m.text;
-    hipLaunchKernelGGL(TEXT_KERNEL(bam_write_kernel, opt.paired, m.um_kernels), dim3((nr + 3u) / 4u), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL(TEXT_KERNEL(bam_write_kernel, opt.paired, m.um_kernels, opt.mates()), dim3((nr + 3u) / 4u), dim3(256), 0, stream, p);
     TAIL_TRY(hipGetLastError());
   }
   TAIL_TRY(m.span[kText].end(stream));

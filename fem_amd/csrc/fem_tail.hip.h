@@ -122,8 +122,10 @@ struct LineOptions {
   int32_t max_hits = -1;           // ... and at most this many lines per slot (>= 1), -1: off
   std::string read_group;          // the ID every line's RG:Z tag carries; empty: no RG tag
   bool hit_tags = false;           // NH:i and HI:i on every mapped line
+  bool mate_tags = false;          // MC:Z MQ:i ms:i on every line of a paired text (mate_score_kernel; the kernels' kMate instances)
   bool filters() const { return strata >= 0 || max_hits >= 1; }  // the line filter is on
   bool rescues() const { return paired && rescue; }
+  bool mates() const { return paired && mate_tags; }
 };
 // What the last pair() and the last sam() / bam() counted (Tail::counts).
 struct LineCounts {
@@ -155,8 +157,9 @@ struct TextGate {
 // The timed stages of a batch's way out of the device.  Each runs between two events on its stream, recorded whether or not
 // anybody asks (Tail::stage_ms).  run(): kOrder, kTrace, kCompact.  pair(): kRescue when it rescues, kPairing.  sam() / bam():
 // kMapq with LineOptions::mapq; kFilterIndex, the line index with the line filter, or else kUnmappedIndex, the one with
-// LineOptions::unmapped alone; kText, the SAM text's or the BAM records' kernels.  estimate_insert(): kInsert.
-enum Stage { kOrder, kTrace, kCompact, kText, kPairing, kRescue, kMapq, kUnmappedIndex, kFilterIndex, kInsert, kStages };
+// LineOptions::unmapped alone; kMateScore, mate_score_kernel with LineOptions::mate_tags on a batch with device qualities;
+// kText, the SAM text's or the BAM records' kernels.  estimate_insert(): kInsert.
+enum Stage { kOrder, kTrace, kCompact, kText, kPairing, kRescue, kMapq, kUnmappedIndex, kFilterIndex, kInsert, kMateScore, kStages };
 
 class Tail {
  public:

@@ -22,7 +22,7 @@ ABI_SYMBOLS = [
     "fem_dev_set_pairs", "fem_dev_fetch_pairs", "fem_dev_pair_count", "fem_dev_estimate_insert",
     "fem_dev_set_rescue", "fem_dev_rescue_count", "fem_dev_set_rescue_discordant", "fem_dev_rescue_discordant_count", "fem_dev_set_mapq",
     "fem_dev_set_unmapped", "fem_dev_unmapped_count",
-    "fem_dev_set_report", "fem_dev_filtered_count", "fem_dev_set_tags",
+    "fem_dev_set_report", "fem_dev_filtered_count", "fem_dev_set_tags", "fem_dev_set_mate_tags",
     "fem_dev_fetch_bam", "fem_dev_fetch_bam_nowait", "fem_dev_bam_wait", "fem_dev_bgzf_compress",
 ]
 
@@ -184,6 +184,8 @@ def load_hip():
         L.fem_dev_filtered_count.argtypes = [vp, C.c_int, C.POINTER(u64)]
     if hasattr(L, "fem_dev_set_tags"):
         L.fem_dev_set_tags.argtypes = [vp, C.c_int, C.POINTER(_TagParams)]
+    if hasattr(L, "fem_dev_set_mate_tags"):
+        L.fem_dev_set_mate_tags.argtypes = [vp, C.c_int, C.c_int]
     if hasattr(L, "fem_dev_fetch_bam"):
         L.fem_dev_fetch_bam.argtypes = [vp, C.c_int, C.c_int, C.POINTER(_BatchBam)]
         L.fem_dev_fetch_bam_nowait.argtypes = [vp, C.c_int, C.c_int, C.POINTER(_BatchBam)]
@@ -687,6 +689,11 @@ class Device:
         rg = None if read_group is None else (read_group if isinstance(read_group, bytes) else read_group.encode("latin-1"))
         tp = _TagParams(rg, 1 if hits else 0)
         self._check(self._L.fem_dev_set_tags(self._h, slot, C.byref(tp)))
+
+    def set_mate_tags(self, on=True, slot=0):
+        """fem_dev_set_mate_tags: MC:Z, MQ:i and ms:i (the other mate's CIGAR, MAPQ and quality score) on every line of the slot's
+        paired SAM text and BAM records (False: none); the qualities must be on the device then."""
+        self._check(self._L.fem_dev_set_mate_tags(self._h, slot, 1 if on else 0))
 
     def filtered_count(self, slot=0):
         """fem_dev_filtered_count: lines the filter left out of the slot's last SAM text or BAM."""

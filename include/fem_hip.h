@@ -518,6 +518,33 @@ typedef struct {
 } fem_tag_params;
 int fem_dev_set_tags(fem_dev *h, int slot, const fem_tag_params *tp);
 
+/* ---- mate tags: MC:Z, MQ:i, ms:i (new; opt-in: what `samtools fixmate -m` would add in a pass of its own, here written with the
+ *      line) ----
+ * fem_dev_set_mate_tags: on != 0: every line of the slot's fem_dev_fetch_sam[_nowait] text and every record of its
+ *   fem_dev_fetch_bam[_nowait] IN PAIR MODE (fem_dev_set_pairs) carries the three tags below behind every field it has without
+ *   them; 0: none, every byte as before.  A single-end slot is unchanged by the setting.  fem_batch_records, fem_batch_pairs, the
+ *   stats, n_records and every count are unchanged (output text only).
+ *   ms is made from the qualities on the device: a fetch of a text or of BAM records with the setting on in pair mode and the
+ *   slot's qualities kept on the host (fem_dev_commit_names_stage) is FEM_ERR_INVALID.  (Leaving ms out silently would be worse.)
+ *   fem_dev_reserve_text: a line grows by up to 6 + the mate's CIGAR, 6 + 3 and 6 + 6 bytes.
+ * Rule.  A slot is one mate of a pair (slot 2i + m, as for fem_dev_set_report); its other mate is slot s ^ 1.  The other mate's
+ *   PRIMARY LINE is the first of its lines as the pairing made them: in a proper pair the chosen record, otherwise the first
+ *   single-end record, or the rescued one (where a line of an unmapped mate is placed, fem_dev_set_unmapped).  The primary line
+ *   is always in the output, whatever the line filter does.  Every line of a slot carries the same values, in this order:
+ *   MC:Z:<cigar>  iff the other mate has a record and its primary line's CIGAR column is not "*" (a primary record with 0x8000
+ *     prints "*": no MC then): that column, byte for byte.
+ *   MQ:i:<n>      iff the other mate has a record: what its primary line prints in its MAPQ column (255 without fem_dev_set_mapq).
+ *   ms:i:<n>      iff the batch has qualities on the device (where QUAL prints "*" for lack of them, there is no ms): the sum over
+ *     the other mate's quality bytes b of b - 33 where b - 33 >= 15; bytes below 48 add nothing; a read of length 0 gives 0.  The
+ *     other mate need not be mapped.  (As far as known what `samtools fixmate -m` computes; this rule is the specification.)
+ *   Field order on a mapped line: NM:i MD:Z [NH:i HI:i] [RG:Z] [MC:Z] [MQ:i] [ms:i]; on the line of an unmapped read
+ *   (fem_dev_set_unmapped): [RG:Z] [MC:Z MQ:i] [ms:i] behind QUAL, MC and MQ when its mate is mapped (the placed line), ms alone
+ *   for a pair of which nothing maps.  Secondary lines are tagged like the primary one, as RNEXT and PNEXT are.  The tags stand
+ *   behind QUAL, so qual_at of fem_dev_sam_quals is unchanged.
+ *   BAM: MC is type Z (the characters and a NUL), MQ type C (four bytes), ms type I (uint32, seven bytes whatever the value, as NH
+ *   and HI); block_size includes them. */
+int fem_dev_set_mate_tags(fem_dev *h, int slot, int on);
+
 /* Name of the seed + filter kernel fem_dev_map_staged would launch first for these parameters on the resident
  * index ("seed_join_kernel" — behind its "seed_select_kernel"; "seed_join_banked_kernel" where the reference's sequences
  * need more than one 32-bit coordinate space —, "seed_fast_kernel<hash>", "seed_fast_kernel<lean>" or
@@ -553,7 +580,9 @@ int fem_dev_index_info(const fem_dev *h, char *buf, uint64_t cap);
  * 15 = the line filter's line index kernels of a fem_dev_fetch_sam / fem_dev_fetch_bam with fem_dev_set_report on (one entry
  * per call; they make the unmapped reads' part of the index too, so 14 has no entry then);
  * 16 = the insert sampling and bounds kernels of fem_dev_estimate_insert (one entry per call, the zeroing of the histogram
- * included; its fem_dev_fetch_records counts 3, 4 and 5 as any other; no fetch of records, text or pairs counts here). */
+ * included; its fem_dev_fetch_records counts 3, 4 and 5 as any other; no fetch of records, text or pairs counts here);
+ * 17 = the score kernel (ms:i) of a paired fem_dev_fetch_sam / fem_dev_fetch_bam with fem_dev_set_mate_tags on (one entry per
+ * call; MC, MQ and ms themselves are written by the text and BAM record kernels: 7 and 11; none with the setting off). */
 int fem_dev_set_timing(fem_dev *h, int on);
 int fem_dev_reset_timing(fem_dev *h);
 int fem_dev_kernel_time(fem_dev *h, int kernel, double *ms_total, uint64_t *launches);
