@@ -2304,6 +2304,15 @@ int fem_dev_set_pairs(fem_dev *h, int slot, const fem_pair_params *pp) {
   });
 }
 
+int fem_dev_set_orientation(fem_dev *h, int slot, int orientation) {
+  return with_slot(h, slot, [&](Slot &s) {
+    if (orientation != FEM_ORIENT_FR && orientation != FEM_ORIENT_RF && orientation != FEM_ORIENT_FF)
+      return fail(h, FEM_ERR_INVALID, "orientation out of range (FEM_ORIENT_FR, FEM_ORIENT_RF or FEM_ORIENT_FF)");
+    s.opt.orientation = orientation;
+    return (int)FEM_OK;
+  });
+}
+
 int fem_dev_set_rescue(fem_dev *h, int slot, const fem_rescue_params *rp) {
   return with_slot(h, slot, [&](Slot &s) {
     if (!rp) return s.opt.rescue = false, (int)FEM_OK;
@@ -2401,9 +2410,16 @@ int fem_dev_fetch_pairs(fem_dev *h, int slot, fem_batch_pairs *out) {
   return FEM_OK;
 }
 
-// The insert size range the slot's batch suggests (include/fem_hip.h: the rule): the records of fem_dev_fetch_records, then the
-// tail's two kernels over them.  Reads the records only: the slot's options, counts and whatever a later fetch makes stay.
-int fem_dev_estimate_insert(fem_dev *h, int slot, fem_insert_estimate *out) {
+static void insert_estimate_out(const femt::InsertEstimate &e, fem_insert_estimate *out) {
+  out->n_pairs = e.n_pairs, out->n_unique = e.n_unique, out->n_informative = e.n_informative;
+  out->q25 = e.q25, out->q50 = e.q50, out->q75 = e.q75;
+  out->min_insert = e.min_insert, out->max_insert = e.max_insert, out->estimated = e.estimated ? 1 : 0;
+}
+
+// The insert size range the slot's batch suggests, under the slot's orientation or under all three (include/fem_hip.h: the
+// rules): the records of fem_dev_fetch_records, then `run`, the tail's two kernels over them.  Reads the records only: the
+// slot's options, counts and whatever a later fetch makes stay.
+static int estimate_with(fem_dev *h, int slot, const void *out, const std::function<int(Slot &, std::string *)> &run) {
   int rc = check_slot(h, slot);
   if (rc) return rc;
   if (!out) return fail(h, FEM_ERR_INVALID, "null result");
@@ -2412,16 +2428,28 @@ int fem_dev_estimate_insert(fem_dev *h, int slot, fem_insert_estimate *out) {
   if ((rc = fem_dev_fetch_records(h, slot, &rec))) return rc;
   Slot &s = h->slot[slot];
   if (s.n_reads & 1) return fail(h, FEM_ERR_INVALID, "a batch of read pairs holds an even number of reads");
-  femt::InsertEstimate e{};
   std::string err;
-  if ((rc = s.tail->estimate_insert(s.stream, &e, &err))) return fail(h, rc, err);
+  if ((rc = run(s, &err))) return fail(h, rc, err);
   if (h->timing) {
     FEM_LOCK(h);
     h->t_ms[16] += std::max(s.tail->stage_ms(femt::kInsert), 0.f), h->t_n[16] += 1;
   }
-  out->n_pairs = e.n_pairs, out->n_unique = e.n_unique, out->n_informative = e.n_informative;
-  out->q25 = e.q25, out->q50 = e.q50, out->q75 = e.q75;
-  out->min_insert = e.min_insert, out->max_insert = e.max_insert, out->estimated = e.estimated ? 1 : 0;
+  return FEM_OK;
+}
+
+int fem_dev_estimate_insert(fem_dev *h, int slot, fem_insert_estimate *out) {
+  femt::InsertEstimate e{};
+  const int rc = estimate_with(h, slot, out, [&](Slot &s, std::string *err) { return s.tail->estimate_insert(s.opt, s.stream, &e, err); });
+  if (!rc) insert_estimate_out(e, out);
+  return rc;
+}
+
+int fem_dev_estimate_library(fem_dev *h, int slot, fem_library_estimate *out) {
+  femt::LibraryEstimate e{};
+  const int rc = estimate_with(h, slot, out, [&](Slot &s, std::string *err) { return s.tail->estimate_library(s.stream, &e, err); });
+  if (rc) return rc;
+  for (int o = 0; o < 3; ++o) insert_estimate_out(e.by[o], &out->by[o]);
+  out->orientation = e.orientation;
   return FEM_OK;
 }
 

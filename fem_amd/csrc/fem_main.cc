@@ -12,6 +12,8 @@
 // `--strata INT` / `--max-hits INT` leave out the lines of a read beyond its best strata / its first INT (fem_dev_set_report).
 // `--header` puts @HD in front of the @SQ lines and @PG behind them; `--rg LINE` adds the @RG line and RG:Z on every line, `--nh`
 // NH:i and HI:i on every mapped line, both made on the device (fem_dev_set_tags).
+// `--orientation fr|rf|ff|auto` sets the library's orientation (fem_dev_set_orientation); `auto` learns it with the insert size
+// range, in --infer-insert's pre-pass (fem_dev_estimate_library).
 // `--mate-tags` adds MC:Z, MQ:i and ms:i to every line of a paired output, made on the device (fem_dev_set_mate_tags).
 #include <errno.h>
 #include <fcntl.h>
@@ -80,6 +82,7 @@ void usage_map() {
   fprintf(stderr, "        -I, --minins INT  minimum insert size of a proper pair [0]\n");
   fprintf(stderr, "        -X, --maxins INT  maximum insert size of a proper pair [500]\n");
   fprintf(stderr, "        --infer-insert[=INT]  with --read2: learn -I / -X from the first INT (64-262144) [65536] pairs, on the GPU, before the run\n");
+  fprintf(stderr, "        --orientation STR  with --read2: the library's orientation, fr, rf or ff [fr]; auto: learned with --infer-insert, on the GPU, before the run\n");
   fprintf(stderr, "        --rescue INT  with --read2: search a mate without records in its mate's insert window at INT (0-15) edits\n");
   fprintf(stderr, "        --rescue-discordant  with --rescue: also search the mates of a pair whose records do not pair\n");
   fprintf(stderr, "        --bam[=INT]   write BAM instead of SAM: BGZF level 1 (default) or 0 (uncompressed)\n");
@@ -301,6 +304,11 @@ int map_main(int argc, char **argv) {
   // --infer-insert[=N]: the insert size range from the input's first N pairs (fem_dev_estimate_insert), -I / -X the fallback
   bool infer_insert = false;
   long long infer_pairs = 65536;
+  // --orientation: FEM_ORIENT_FR / _RF / _FF (fem_dev_set_orientation); kOrientAuto: learned in --infer-insert's pre-pass
+  // (fem_dev_estimate_library); -1: another word, refused below
+  constexpr int kOrientAuto = 3;
+  int orientation = FEM_ORIENT_FR;
+  bool orientation_given = false;
   bool rescue_discordant = false;  // --rescue-discordant (fem_dev_set_rescue_discordant)
   int bam_level = -1;  // --bam[=LEVEL]: BAM records and BGZF members made on the device (fem_dev_fetch_bam); -1: SAM
   bool unmapped = false;  // --unmapped: a line for every read without a mapping, made on the device (fem_dev_set_unmapped)
@@ -326,6 +334,7 @@ int map_main(int argc, char **argv) {
                                      {"maxins", required_argument, nullptr, 'X'}, {"rescue", required_argument, nullptr, 'R'},
                                      {"rescue-discordant", no_argument, nullptr, 'D'},
                                      {"infer-insert", optional_argument, nullptr, 'F'},
+                                     {"orientation", required_argument, nullptr, 'O'},
                                      {"bam", optional_argument, nullptr, 'Z'},  {"mapq", no_argument, nullptr, 'Q'},
                                      {"unmapped", no_argument, nullptr, 'U'},
                                      {"strata", required_argument, nullptr, 'S'}, {"max-hits", required_argument, nullptr, 'N'},
@@ -363,6 +372,11 @@ int map_main(int argc, char **argv) {
           infer_pairs = strtoll(optarg, &end, 10);
           if (!end || end == optarg || *end) infer_pairs = -1;  // (not a number: refused below)
         }
+        break;
+      case 'O':
+        orientation = strcmp(optarg, "fr") == 0 ? FEM_ORIENT_FR : strcmp(optarg, "rf") == 0 ? FEM_ORIENT_RF : strcmp(optarg, "ff") == 0 ? FEM_ORIENT_FF
+                      : strcmp(optarg, "auto") == 0 ? kOrientAuto : -1;
+        orientation_given = true;
         break;
       case 'Q': mapq = true; break;
       case 'U': unmapped = true; break;
@@ -414,6 +428,9 @@ int map_main(int argc, char **argv) {
   else if (min_insert < 0 || max_insert < min_insert || max_insert > (1ll << 30)) bad = "Wrong insert size range.";
   else if (infer_insert && !read2_path) bad = "--infer-insert needs read pairs (--read2).";
   else if (infer_insert && (infer_pairs < 64 || infer_pairs > 262144)) bad = "Wrong number of pairs to infer from (64-262144).";
+  else if (orientation < 0) bad = "Wrong library orientation (fr, rf, ff or auto).";
+  else if (orientation_given && !read2_path) bad = "--orientation needs read pairs (--read2).";
+  else if (orientation == kOrientAuto && !infer_insert) bad = "--orientation auto needs --infer-insert.";
   else if (mate_tags && !read2_path) bad = "--mate-tags needs --read2.";
   else if (rescue_discordant && !rescue_given) bad = "--rescue-discordant needs --rescue.";
   else if (rescue_given && !read2_path) bad = "--rescue needs read pairs (--read2).";
@@ -592,6 +609,7 @@ int map_main(int argc, char **argv) {
           if (!rc && paired) {
             const fem_pair_params pp{(int32_t)min_insert, (int32_t)max_insert};
             rc = fem_dev_set_pairs(devs[(size_t)g], sl, &pp);
+            if (!rc && orientation_given && orientation != kOrientAuto) rc = fem_dev_set_orientation(devs[(size_t)g], sl, orientation);
             if (!rc && mate_tags) rc = fem_dev_set_mate_tags(devs[(size_t)g], sl, 1);
             if (!rc && rescue_given) {
               const fem_rescue_params rp{(int32_t)rescue_edits};
@@ -614,7 +632,12 @@ int map_main(int argc, char **argv) {
   // (fem_dev_estimate_insert).  The range then holds for the whole run, whatever --batch, -t and --gpus are; the main pass reads
   // the input from its start and counts nothing of this.  Files that do not give as many records each, or a sample the reader
   // cannot parse: no estimate, and the main pass reports the input as it does without the switch.
+  // --orientation auto: the same sample says which orientation the library has, too (fem_dev_estimate_library): the one under
+  // which most of its unique pairs are informative; the range is then that orientation's.
   if (infer_insert) {
+    const bool learn_orientation = orientation == kOrientAuto;
+    fem_library_estimate lib{};
+    lib.orientation = -1;
     const double t_pre = real_time();
     fem_seqset mate[2] = {};
     bool sampled = true;
@@ -638,22 +661,38 @@ int map_main(int argc, char **argv) {
       fem_dev *h = devs[0];
       rc = fem_dev_stage_reads(h, 0, &sample);
       if (!rc) rc = fem_dev_map_staged(h, 0, &params);
-      if (!rc) rc = fem_dev_estimate_insert(h, 0, &est);
+      if (!rc) rc = learn_orientation ? fem_dev_estimate_library(h, 0, &lib) : fem_dev_estimate_insert(h, 0, &est);
       if (rc) dev_fail(h, "insert size estimate", rc);
     }
     for (fem_seqset &s : mate) fem_seqset_free(&s);
     if (rc) return EXIT_FAILURE;
+    if (learn_orientation) {
+      static const char *const kOrientName[3] = {"FR", "RF", "FF"};
+      const unsigned long a = (unsigned long)lib.by[0].n_informative, b = (unsigned long)lib.by[1].n_informative,
+                          c3 = (unsigned long)lib.by[2].n_informative, S = (unsigned long)lib.by[0].n_pairs;
+      if (sampled && lib.orientation >= 0) {
+        orientation = lib.orientation, est = lib.by[lib.orientation];
+        fprintf(stderr, "Inferred library orientation: %s (FR %lu, RF %lu, FF %lu informative of %lu pairs).\n", kOrientName[orientation], a, b, c3, S);
+      } else {
+        orientation = FEM_ORIENT_FR, est.estimated = 0;
+        if (sampled)
+          fprintf(stderr, "Library orientation not inferred (FR %lu, RF %lu, FF %lu informative of %lu pairs, %d needed): using FR, %lld-%lld.\n", a, b,
+                  c3, S, FEM_INSERT_MIN_PAIRS, min_insert, max_insert);
+      }
+    }
     if (sampled && est.estimated) {
       const fem_pair_params pp{est.min_insert, est.max_insert};
       for (fem_dev *h : devs) {
         int32_t ns = 4;
         (void)fem_dev_limits(h, nullptr, &ns);
-        for (int sl = 0; sl < ns; ++sl)
+        for (int sl = 0; sl < ns; ++sl) {
           if ((rc = fem_dev_set_pairs(h, sl, &pp))) return dev_fail(h, "insert size range", rc);
+          if (learn_orientation && (rc = fem_dev_set_orientation(h, sl, orientation))) return dev_fail(h, "library orientation", rc);
+        }
       }
       fprintf(stderr, "Inferred insert size range: %d-%d (quartiles %d %d %d, %lu informative of %lu pairs).\n", est.min_insert, est.max_insert,
               est.q25, est.q50, est.q75, (unsigned long)est.n_informative, (unsigned long)est.n_pairs);
-    } else if (sampled) {
+    } else if (sampled && !learn_orientation) {
       fprintf(stderr, "Insert size range not inferred (%lu informative of %lu pairs, %d needed): using %lld-%lld.\n",
               (unsigned long)est.n_informative, (unsigned long)est.n_pairs, FEM_INSERT_MIN_PAIRS, min_insert, max_insert);
     }

@@ -1929,6 +1929,9 @@ struct PairParams {
   // MAPQ (pair_kernel<true>): per line, 0 on every line but a mate's primary one, which gets kPairProper | qp for a proper pair
   // (| kPairOwn when the chosen record may keep its single-end MAPQ: not rescued, NM = d1 of its mate); mapq_kernel finishes it
   uint8_t *lmq;
+  // the library's orientation (fem_dev_set_orientation): 16 where the mate's strand is flipped, else 0; a
+  // record's virtual strand is its FLAG's 16 ^ its mate's flip, and the pairing rule reads that one
+  uint32_t flip1, flip2;
 };
 constexpr uint32_t kPairOwn = 0x80u, kPairProper = 0x40u;
 
@@ -1986,12 +1989,15 @@ __device__ __forceinline__ uint32_t pair_mq_byte(const PairParams &p, bool prope
 
 struct MateRec {
   uint32_t tid, pos0, flag, nm;
+  uint32_t v;  // the virtual strand: 16 = reverse
   uint64_t end0;
 };
 
-__device__ __forceinline__ MateRec mate_rec(const PairParams &p, uint32_t r) {
+// record r of a mate whose flip is `flip` (PairParams::flip1 or flip2)
+__device__ __forceinline__ MateRec mate_rec(const PairParams &p, uint32_t r, uint32_t flip) {
   MateRec m;
   m.tid = p.tid[r], m.pos0 = p.pos0[r], m.flag = p.flag[r], m.nm = p.nm[r];
+  m.v = (m.flag & 16u) ^ flip;
   uint64_t span = 0;
   for (uint32_t c = p.cigar_off[r], c1 = p.cigar_off[r + 1]; c < c1; ++c) {
     const uint32_t op = p.cigar[c];
@@ -2001,10 +2007,11 @@ __device__ __forceinline__ MateRec mate_rec(const PairParams &p, uint32_t r) {
   return m;
 }
 
-// the insert of a concordant combination, -1 otherwise (an insert is never negative: pos0(f) <= pos0(r) <= end0(r))
+// the insert of a concordant combination, -1 otherwise (an insert is never negative: pos0(f) <= pos0(r) <= end0(r)); forward
+// and reverse are the virtual strands
 __device__ __forceinline__ int64_t concordant(const PairParams &p, const MateRec &a, const MateRec &b) {
-  if (((a.flag | b.flag) & 0x8000u) || a.tid != b.tid || !((a.flag ^ b.flag) & 16u)) return -1;
-  const MateRec &f = (a.flag & 16u) ? b : a, &r = (a.flag & 16u) ? a : b;
+  if (((a.flag | b.flag) & 0x8000u) || a.tid != b.tid || a.v == b.v) return -1;
+  const MateRec &f = a.v ? b : a, &r = a.v ? a : b;
   if (f.pos0 > r.pos0) return -1;
   const int64_t ins = (int64_t)(r.end0 - f.pos0);
   return ins >= p.min_insert && ins <= p.max_insert ? ins : -1;
@@ -2035,7 +2042,7 @@ __device__ void write_pair(const PairParams &p, uint32_t a0, uint32_t na, uint32
     }
     const uint32_t k = ob + u;
     p.perm[k] = rec, p.pflag[k] = (uint16_t)nf, p.mtid[k] = mt, p.mpos0[k] = mp;
-    p.tlen[k] = proper && t == 0 ? (int32_t)((fl & 16u) ? -insert : insert) : 0;
+    p.tlen[k] = proper && t == 0 ? (int32_t)(((fl & 16u) ^ (m2 ? p.flip2 : p.flip1)) ? -insert : insert) : 0;
     if (kMapq) p.lmq[k] = (uint8_t)(t ? 0u : m2 ? mq_b : mq_a);
   }
 }
@@ -2078,10 +2085,10 @@ __global__ void __launch_bounds__(256) pair_kernel(PairParams p) {
     int64_t ins = -1;
     Strata st;
     for (uint32_t a = 0; a < na; ++a) {
-      const MateRec ra = mate_rec(p, a0 + a);
+      const MateRec ra = mate_rec(p, a0 + a, p.flip1);
       if (ra.flag & 0x8000u) continue;
       for (uint32_t b = 0; b < nb; ++b) {
-        const MateRec rb = mate_rec(p, b0 + b);
+        const MateRec rb = mate_rec(p, b0 + b, p.flip2);
         const int64_t x = concordant(p, ra, rb);
         if (x >= 0 && ra.nm + rb.nm < best) best = ra.nm + rb.nm, ca = a, cb = b, ins = x;
         if (kMapq && x >= 0) st.add(ra.nm + rb.nm);
@@ -2108,14 +2115,15 @@ __global__ void __launch_bounds__(256) pair_kernel(PairParams p) {
     const uint32_t LA = NA + (RESC == 1u ? OWN_N : 0u), LB = NB + (RESC == 2u ? OWN_N : 0u);
     const bool lanes_on_a = NA >= NB;
     const uint32_t n_long = lanes_on_a ? NA : NB, n_short = lanes_on_a ? NB : NA;
+    const uint32_t flip_long = lanes_on_a ? p.flip1 : p.flip2, flip_short = lanes_on_a ? p.flip2 : p.flip1;
     uint64_t key = kNoKey;
     uint32_t key_b = 0xFFFFFFFFu;
     Strata st;
     for (uint32_t u = ln; u < n_long; u += 64u) {
-      const MateRec ru = mate_rec(p, (lanes_on_a ? A0 : B0) + u);
+      const MateRec ru = mate_rec(p, (lanes_on_a ? A0 : B0) + u, flip_long);
       if (ru.flag & 0x8000u) continue;
       for (uint32_t v = 0; v < n_short; ++v) {
-        const MateRec rv = mate_rec(p, (lanes_on_a ? B0 : A0) + v);
+        const MateRec rv = mate_rec(p, (lanes_on_a ? B0 : A0) + v, flip_short);
         if (concordant(p, ru, rv) < 0) continue;
         const uint32_t a = lanes_on_a ? u : v, b = lanes_on_a ? v : u;
         const uint64_t k = (uint64_t)(ru.nm + rv.nm) << 32 | a;
@@ -2135,7 +2143,7 @@ __global__ void __launch_bounds__(256) pair_kernel(PairParams p) {
     }
     const bool proper = kmin != kNoKey;
     const uint32_t ca = proper ? (uint32_t)kmin : 0u, cb = proper ? bmin : 0u;
-    const int64_t ins = proper ? concordant(p, mate_rec(p, A0 + ca), mate_rec(p, B0 + cb)) : -1;
+    const int64_t ins = proper ? concordant(p, mate_rec(p, A0 + ca, p.flip1), mate_rec(p, B0 + cb, p.flip2)) : -1;
     if (kMapq) {
       const uint32_t qp = pair_qp(wave_strata(st));
       write_pair<true>(p, A0, LA, B0, LB, OB, proper, ca, cb, ins, ln, 64u, RESC, OWN0, pair_mq_byte(p, proper, qp, A0, ca, RESC == 1),
@@ -2166,9 +2174,9 @@ __global__ void __launch_bounds__(256) pair_probe_kernel(PairParams p, uint8_t *
   bool found = false;
   if (both && !big) {
     for (uint32_t a = 0; a < na && !found; ++a) {
-      const MateRec ra = mate_rec(p, a0 + a);
+      const MateRec ra = mate_rec(p, a0 + a, p.flip1);
       if (ra.flag & 0x8000u) continue;
-      for (uint32_t b = 0; b < nb && !found; ++b) found = concordant(p, ra, mate_rec(p, b0 + b)) >= 0;
+      for (uint32_t b = 0; b < nb && !found; ++b) found = concordant(p, ra, mate_rec(p, b0 + b, p.flip2)) >= 0;
     }
   }
   uint64_t todo = __ballot(big);
@@ -2178,14 +2186,15 @@ __global__ void __launch_bounds__(256) pair_probe_kernel(PairParams p, uint8_t *
     const uint32_t A0 = wave_bcast(a0, src), NA = wave_bcast(na, src), B0 = wave_bcast(b0, src), NB = wave_bcast(nb, src);
     const bool lanes_on_a = NA >= NB;
     const uint32_t long0 = lanes_on_a ? A0 : B0, n_long = lanes_on_a ? NA : NB, short0 = lanes_on_a ? B0 : A0, n_short = lanes_on_a ? NB : NA;
+    const uint32_t flip_long = lanes_on_a ? p.flip1 : p.flip2, flip_short = lanes_on_a ? p.flip2 : p.flip1;
     bool any = false;
     for (uint32_t u0 = 0; u0 < n_long && !any; u0 += 64u) {
       const uint32_t u = u0 + ln;
       bool hit = false;
       if (u < n_long) {
-        const MateRec ru = mate_rec(p, long0 + u);
+        const MateRec ru = mate_rec(p, long0 + u, flip_long);
         if (!(ru.flag & 0x8000u))
-          for (uint32_t v = 0; v < n_short && !hit; ++v) hit = concordant(p, ru, mate_rec(p, short0 + v)) >= 0;
+          for (uint32_t v = 0; v < n_short && !hit; ++v) hit = concordant(p, ru, mate_rec(p, short0 + v, flip_short)) >= 0;
       }
       any = __ballot(hit) != 0;
     }
@@ -2214,7 +2223,7 @@ __global__ void __launch_bounds__(256) insert_sample_kernel(PairParams p, uint32
     const uint32_t a0 = p.rec_begin[i], na = p.rec_begin[i + 1] - a0;
     const uint32_t b0 = p.rec_begin[p.n_pairs + i], nb = p.rec_begin[p.n_pairs + i + 1] - b0;
     if (na == 1u && nb == 1u) {
-      const MateRec ra = mate_rec(p, a0), rb = mate_rec(p, b0);
+      const MateRec ra = mate_rec(p, a0, p.flip1), rb = mate_rec(p, b0, p.flip2);
       unique = !((ra.flag | rb.flag) & 0x8000u);
       const int64_t ins = concordant(p, ra, rb);  // (-1 with 0x8000 on either)
       informative = ins >= 0;
@@ -2226,7 +2235,46 @@ __global__ void __launch_bounds__(256) insert_sample_kernel(PairParams p, uint32
   if (ln == 0 && informative_lanes) atomicAdd(ctl + 1, (uint32_t)__builtin_popcountll(informative_lanes));
 }
 
+// The library estimate (fem_dev_estimate_library): the same sample under the three orientations in one pass.
+// hist: three histograms, FR RF FF, then their three control blocks.  One lane per pair reads its two records once and asks
+// the pairing rule under each orientation's flips: a unique pair on opposite strands can be informative under FR and under RF
+// (under both at equal pos0), one on the same strand under FF alone, so it adds to at most two histograms.  The unique pairs
+// are counted into all three blocks.
+constexpr uint32_t kOrientations = 3;
+__device__ __forceinline__ uint32_t orient_flip1(uint32_t o) { return o == FEM_ORIENT_RF ? 16u : 0u; }
+__device__ __forceinline__ uint32_t orient_flip2(uint32_t o) { return o == FEM_ORIENT_FR ? 0u : 16u; }
+
+__global__ void __launch_bounds__(256) library_sample_kernel(PairParams p, uint32_t *hist, uint32_t *ctl) {
+  const uint32_t ln = threadIdx.x & 63u;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  bool unique = false;
+  int64_t ins[kOrientations] = {-1, -1, -1};
+  if (i < p.n_pairs) {
+    const uint32_t a0 = p.rec_begin[i], na = p.rec_begin[i + 1] - a0;
+    const uint32_t b0 = p.rec_begin[p.n_pairs + i], nb = p.rec_begin[p.n_pairs + i + 1] - b0;
+    if (na == 1u && nb == 1u) {
+      MateRec ra = mate_rec(p, a0, 0u), rb = mate_rec(p, b0, 0u);
+      unique = !((ra.flag | rb.flag) & 0x8000u);
+#pragma unroll
+      for (uint32_t o = 0; o < kOrientations; ++o) {
+        ra.v = (ra.flag & 16u) ^ orient_flip1(o), rb.v = (rb.flag & 16u) ^ orient_flip2(o);
+        ins[o] = concordant(p, ra, rb);
+        if (ins[o] >= 0) atomicAdd(hist + o * kInsertBins + (uint32_t)ins[o], 1u);  // (ins <= p.max_insert = FEM_INSERT_MAX)
+      }
+    }
+  }
+  const uint64_t unique_lanes = __ballot(unique);
+#pragma unroll
+  for (uint32_t o = 0; o < kOrientations; ++o) {
+    const uint64_t informative_lanes = __ballot(ins[o] >= 0);
+    if (ln == 0 && unique_lanes) atomicAdd(ctl + o * kInsertCtl, (uint32_t)__builtin_popcountll(unique_lanes));
+    if (ln == 0 && informative_lanes) atomicAdd(ctl + o * kInsertCtl + 1, (uint32_t)__builtin_popcountll(informative_lanes));
+  }
+}
+
+// One block per histogram (fem_dev_estimate_insert: one; fem_dev_estimate_library: three, their control blocks behind them all)
 __global__ void __launch_bounds__(256) insert_bounds_kernel(const uint32_t *hist, uint32_t *ctl) {
+  hist += blockIdx.x * kInsertBins, ctl += blockIdx.x * kInsertCtl;
   constexpr uint32_t kPerLane = kInsertBins / 256u;
   static_assert(kPerLane * 256u == kInsertBins, "every lane sums as many bins");
   __shared__ uint32_t incl[256];  // inclusive scan of the lanes' sums
@@ -2492,41 +2540,45 @@ struct RescueParams {
   uint32_t *kept, *k_ops, *k_md; // per pair (n_pairs + 1): the kept record's 1, runs, MD characters (0 0 0 otherwise)
   const uint32_t *s_kept, *s_ops, *s_md;  // their exclusive scans
   uint32_t cig_total, md_total;  // run()'s CIGAR runs and MD characters
+  uint32_t flip1, flip2;         // the library's orientation, as PairParams's
 };
 
-// pair i's candidate view in direction d: the anchors' mate (A: mate 1 for d = 0, mate 2 for d = 1) and the searched mate (B)
+// pair i's candidate view in direction d: the anchors' mate (A: mate 1 for d = 0, mate 2 for d = 1) and the searched mate (B),
+// and the two mates' flips
 struct RescuePair {
-  uint32_t a0, na, b_read;
+  uint32_t a0, na, b_read, flip_a, flip_b;
 };
 __device__ __forceinline__ RescuePair rescue_pair(const RescueParams &p, uint32_t i, uint32_t d) {
   const uint32_t a_read = d ? p.n_pairs + i : i;
   RescuePair r;
   r.a0 = p.rec_begin[a_read], r.na = p.rec_begin[a_read + 1] - r.a0, r.b_read = d ? i : p.n_pairs + i;
+  r.flip_a = d ? p.flip2 : p.flip1, r.flip_b = d ? p.flip1 : p.flip2;
   return r;
 }
 constexpr unsigned long long kBestDir = 1ull << 35;  // the direction's bit of RescueParams::best
 
-// an anchor's window of B's pos0 ([lo, hi], empty when lo > hi) and the strand B is searched on
+// an anchor's window of B's pos0 ([lo, hi], empty when lo > hi) and the strand B is searched on (flip_b: B's mate's flip)
 struct RescueWindow {
   int64_t lo, hi;
-  uint32_t tid, rc;  // rc: B reverse-complemented (the anchor is forward)
+  uint32_t tid, rc;  // rc: B reverse-complemented (the anchor is virtually forward, or B's mate is flipped, not both)
 };
-__device__ __forceinline__ RescueWindow rescue_window(const RescueParams &p, const MateRec &an, int64_t L) {
+__device__ __forceinline__ RescueWindow rescue_window(const RescueParams &p, const MateRec &an, int64_t L, uint32_t flip_b) {
   RescueWindow w;
   w.tid = an.tid;
   const int64_t pa = an.pos0, ea = (int64_t)an.end0;
-  if (!(an.flag & 16u)) {
+  if (!an.v) {
     w.rc = 1u, w.lo = pa + p.min_insert - L > pa ? pa + p.min_insert - L : pa, w.hi = pa + p.max_insert - L;
   } else {
     w.rc = 0u, w.lo = ea - p.max_insert > 0 ? ea - p.max_insert : 0, w.hi = ea - p.min_insert < pa ? ea - p.min_insert : pa;
   }
+  w.rc ^= flip_b >> 4;
   return w;
 }
 
-__device__ __forceinline__ MateRec rescue_rec(const RescueParams &p, uint32_t r) {
+__device__ __forceinline__ MateRec rescue_rec(const RescueParams &p, uint32_t r, uint32_t flip) {
   PairParams q{};
   q.tid = p.tid, q.pos0 = p.pos0, q.flag = p.flag, q.nm = p.nm, q.cigar_off = p.cigar_off, q.cigar = p.cigar;
-  return mate_rec(q, r);
+  return mate_rec(q, r, flip);
 }
 
 // character j of B as searched: the read itself, or fo_revcomp's reverse complement (ACGT complemented in upper case, anything else N)
@@ -2608,10 +2660,10 @@ __global__ void __launch_bounds__(256) rescue_search_kernel(RescueParams p) {
   for (uint32_t job = blockIdx.x * kResWaves + wv; job < n_jobs; job += gridDim.x * kResWaves) {
     const uint32_t k = p.jobs[job] >> 4, d = p.jobs[job] >> 3 & 1u, a = p.jobs[job] & 7u;
     const RescuePair rp = rescue_pair(p, p.cand_pair[k], d);
-    const MateRec an = rescue_rec(p, rp.a0 + a);
+    const MateRec an = rescue_rec(p, rp.a0 + a, rp.flip_a);
     const uint64_t off = p.read_off[rp.b_read];
     const int64_t L = (int64_t)(p.read_off[rp.b_read + 1] - off);
-    const RescueWindow w = rescue_window(p, an, L);
+    const RescueWindow w = rescue_window(p, an, L, rp.flip_b);
     if (w.lo > w.hi || L == 0) continue;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // (the previous job's reads of tc are done)
     __builtin_amdgcn_wave_barrier();
@@ -2665,11 +2717,11 @@ __global__ void __launch_bounds__(64) rescue_trace_kernel(RescueParams p) {
     if (best == ~0ull) continue;
     const uint32_t i = p.cand_pair[k], a = (uint32_t)(best >> 32) & 7u, pos = (uint32_t)best;
     const RescuePair rp = rescue_pair(p, i, best & kBestDir ? 1u : 0u);
-    const MateRec an = rescue_rec(p, rp.a0 + a);
+    const MateRec an = rescue_rec(p, rp.a0 + a, rp.flip_a);
     const int ed = (int)(best >> 36) - (int)an.nm;
     const uint64_t off = p.read_off[rp.b_read];
     const int L = (int)(p.read_off[rp.b_read + 1] - off);
-    const RescueWindow w = rescue_window(p, an, L);
+    const RescueWindow w = rescue_window(p, an, L, rp.flip_b);
     const int64_t W = 2 * E + 1;
     const int64_t c = w.lo + ((int64_t)pos - w.lo) / W * W;  // the tile the hit came from (tiles are disjoint in pos0)
     const int end = (int)((int64_t)pos - c) + L - 1;
@@ -2698,7 +2750,7 @@ __global__ void __launch_bounds__(64) rescue_trace_kernel(RescueParams p) {
     }
     if (start < 0) continue;
     MateRec rs;
-    rs.tid = w.tid, rs.pos0 = (uint32_t)(c + start), rs.flag = w.rc ? 16u : 0u, rs.nm = (uint32_t)ed;
+    rs.tid = w.tid, rs.pos0 = (uint32_t)(c + start), rs.flag = w.rc ? 16u : 0u, rs.v = rs.flag ^ rp.flip_b, rs.nm = (uint32_t)ed;
     uint64_t span = 0;
     for (uint32_t u = 0; u < st.n_ops; ++u)
       if ((st.ops[u] & 0xFu) == kOpM || (st.ops[u] & 0xFu) == kOpD) span += st.ops[u] >> 4;
@@ -2811,8 +2863,8 @@ static hipError_t copy_home(PinBuf<T> &dst, const DevBuf<S> &src, size_t first, 
 
 // The words of h_ctl, the pinned buffer the kernels' counters come home in: 0 .. 3 run()'s ctl (2: a text's asserted records,
 // 3: bam()'s name check), 4 5 run()'s CIGAR and MD totals, 6 7 a text's size, 8 9 a line index's counts, from kCtlInsert on
-// estimate_insert()'s kInsertCtl words.
-constexpr size_t kCtlInsert = 12, kCtlWords = kCtlInsert + kInsertCtl;
+// estimate_insert()'s kInsertCtl words (estimate_library(): three times as many).
+constexpr size_t kCtlInsert = 12, kCtlWords = kCtlInsert + 3 * kInsertCtl;
 
 struct Tail::Impl {
   DevBuf<uint32_t> rec_begin, queue, ctl, u_misc, s_misc, s_read, t_ops, o_ops, ovf, rec_list, src_slot, n_ops, n_md, tid, pos0, cigar_off, md_off, cigar;
@@ -3193,7 +3245,7 @@ int Tail::warm(hipStream_t stream, std::string *err) {
                            (const void *)sam_len_kernel<true, true>, (const void *)sam_write_kernel<true, true>,
                            (const void *)rescue_jobs_kernel, (const void *)pair_probe_kernel,
                            (const void *)rescue_search_kernel, (const void *)rescue_trace_kernel, (const void *)rescue_append_kernel,
-                           (const void *)insert_sample_kernel, (const void *)insert_bounds_kernel,
+                           (const void *)insert_sample_kernel, (const void *)library_sample_kernel, (const void *)insert_bounds_kernel,
                            (const void *)mate_score_kernel, (const void *)sam_len_kernel<true, false, true>,
                            (const void *)sam_write_kernel<true, false, true>, (const void *)sam_len_kernel<true, true, true>,
                            (const void *)sam_write_kernel<true, true, true>};
@@ -3487,12 +3539,14 @@ int Tail::pair(const LineOptions &opt, const RescueInput &rescue, hipStream_t st
     r.ctl = m.r_ctl, r.cand_pair = m.r_cand, r.jobs = m.r_jobs;
     r.best = m.r_best;
     r.cig_total = h_tot[4], r.md_total = h_tot[5];
+    r.flip1 = opt.flip1(), r.flip2 = opt.flip2();
     m.bind_records(&r);
     TAIL_TRY(m.span[kRescue].begin(stream));
     TAIL_TRY(hipMemsetAsync(m.r_ctl, 0, 32, stream));
     if (opt.rescue_discordant) {  // the pairs with records on both sides that do not pair are candidates too
       PairParams q{};
       q.n_pairs = np, q.min_insert = opt.min_insert, q.max_insert = opt.max_insert;
+      q.flip1 = opt.flip1(), q.flip2 = opt.flip2();
       m.bind_pairing(&q);
       hipLaunchKernelGGL(pair_probe_kernel, dim3((np + 255u) / 256u), dim3(256), 0, stream, q, m.r_disc.get());
       TAIL_TRY(hipGetLastError());
@@ -3589,6 +3643,7 @@ int Tail::pair(const LineOptions &opt, const RescueInput &rescue, hipStream_t st
   if (np) {
     PairParams q{};
     q.n_pairs = np, q.min_insert = opt.min_insert, q.max_insert = opt.max_insert;
+    q.flip1 = opt.flip1(), q.flip2 = opt.flip2();
     m.bind_pairing(&q);
     q.perm = m.perm, q.pflag = m.pflag, q.mtid = m.mtid, q.mpos0 = m.mpos0;
     q.tlen = m.tlen, q.pair_begin = m.pair_begin, q.n_proper = m.pair_ctl;
@@ -3605,7 +3660,15 @@ int Tail::pair(const LineOptions &opt, const RescueInput &rescue, hipStream_t st
   return FEM_OK;
 }
 
-int Tail::estimate_insert(hipStream_t stream, InsertEstimate *out, std::string *err) {
+// The estimate a control block holds (insert_bounds_kernel's words, at home)
+static void insert_estimate_of(const uint32_t *h, uint32_t np, InsertEstimate *out) {
+  out->n_pairs = np, out->n_unique = h[0], out->n_informative = h[1];
+  out->q25 = (int32_t)h[2], out->q50 = (int32_t)h[3], out->q75 = (int32_t)h[4];
+  out->min_insert = (int32_t)h[5], out->max_insert = (int32_t)h[6], out->estimated = h[7] != 0;
+}
+
+// n_hist = 1: estimate_insert() under the orientation of `opt`; kOrientations: estimate_library(), all three side by side
+int Tail::estimate(const LineOptions *opt, uint32_t n_hist, hipStream_t stream, InsertEstimate *out, std::string *err) {
   if (!impl_ || !out) return FEM_ERR_STATE;
   Impl &m = *impl_;
   const uint32_t n = m.last_n, np = n / 2u;
@@ -3613,28 +3676,43 @@ int Tail::estimate_insert(hipStream_t stream, InsertEstimate *out, std::string *
     if (err) *err = "a paired batch holds an even number of reads";
     return FEM_ERR_INVALID;
   }
-  TAIL_TRY(m.ins_hist.ensure(kInsertBins + kInsertCtl));
+  const size_t words = (size_t)n_hist * (kInsertBins + kInsertCtl);
+  TAIL_TRY(m.ins_hist.ensure(words));
   TAIL_TRY(m.h_ctl.ensure(kCtlWords));
-  uint32_t *hist = m.ins_hist, *ctl = hist + kInsertBins;
+  uint32_t *hist = m.ins_hist, *ctl = hist + (size_t)n_hist * kInsertBins;
   m.not_run({kInsert});
   TAIL_TRY(m.span[kInsert].begin(stream));
-  TAIL_TRY(hipMemsetAsync(hist, 0, (kInsertBins + kInsertCtl) * sizeof(uint32_t), stream));
+  TAIL_TRY(hipMemsetAsync(hist, 0, words * sizeof(uint32_t), stream));
   if (np) {
     PairParams q{};
     q.n_pairs = np, q.min_insert = 0, q.max_insert = FEM_INSERT_MAX;
+    if (opt) q.flip1 = opt->flip1(), q.flip2 = opt->flip2();
     m.bind_pairing(&q);
-    hipLaunchKernelGGL(insert_sample_kernel, dim3((np + 255u) / 256u), dim3(256), 0, stream, q, hist, ctl);
+    hipLaunchKernelGGL(opt ? insert_sample_kernel : library_sample_kernel, dim3((np + 255u) / 256u), dim3(256), 0, stream, q, hist, ctl);
     TAIL_TRY(hipGetLastError());
   }
-  hipLaunchKernelGGL(insert_bounds_kernel, dim3(1), dim3(256), 0, stream, (const uint32_t *)hist, ctl);
+  hipLaunchKernelGGL(insert_bounds_kernel, dim3(n_hist), dim3(256), 0, stream, (const uint32_t *)hist, ctl);
   TAIL_TRY(hipGetLastError());
   TAIL_TRY(m.span[kInsert].end(stream));
   const uint32_t *h = m.h_ctl + kCtlInsert;
-  TAIL_TRY(hipMemcpyAsync(m.h_ctl + kCtlInsert, ctl, kInsertCtl * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  TAIL_TRY(hipMemcpyAsync(m.h_ctl + kCtlInsert, ctl, (size_t)n_hist * kInsertCtl * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
   TAIL_TRY(hipStreamSynchronize(stream));
-  out->n_pairs = np, out->n_unique = h[0], out->n_informative = h[1];
-  out->q25 = (int32_t)h[2], out->q50 = (int32_t)h[3], out->q75 = (int32_t)h[4];
-  out->min_insert = (int32_t)h[5], out->max_insert = (int32_t)h[6], out->estimated = h[7] != 0;
+  for (uint32_t o = 0; o < n_hist; ++o) insert_estimate_of(h + o * kInsertCtl, np, out + o);
+  return FEM_OK;
+}
+
+int Tail::estimate_insert(const LineOptions &opt, hipStream_t stream, InsertEstimate *out, std::string *err) {
+  return estimate(&opt, 1, stream, out, err);
+}
+
+int Tail::estimate_library(hipStream_t stream, LibraryEstimate *out, std::string *err) {
+  if (!out) return FEM_ERR_STATE;
+  if (int rc = estimate(nullptr, kOrientations, stream, out->by, err)) return rc;
+  // the choice, from the 24 control words: the most informative pairs among the estimated ones, ties in the order FR RF FF
+  out->orientation = -1;
+  for (uint32_t o = 0; o < kOrientations; ++o)
+    if (out->by[o].estimated && (out->orientation < 0 || out->by[o].n_informative > out->by[out->orientation].n_informative))
+      out->orientation = (int32_t)o;
   return FEM_OK;
 }
 

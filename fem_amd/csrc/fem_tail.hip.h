@@ -111,6 +111,7 @@ struct RescueInput {  // device pointers unless noted
 struct LineOptions {
   bool paired = false;             // the lines in the order of the last pair() with its mate columns (the records of both stay on the device)
   int32_t min_insert = 0, max_insert = 0;
+  int32_t orientation = 0;         // FEM_ORIENT_FR / _RF / _FF: which mates' strands the pairing rule reads flipped (in pair mode)
   bool rescue = false;             // mate rescue at rescue_edits edits (E, 0 .. 15), in pair mode
   int32_t rescue_edits = 0;
   // a pair with records on both sides and no concordant combination is a candidate too, searched from either mate's anchors
@@ -126,6 +127,9 @@ struct LineOptions {
   bool filters() const { return strata >= 0 || max_hits >= 1; }  // the line filter is on
   bool rescues() const { return paired && rescue; }
   bool mates() const { return paired && mate_tags; }
+  // the mates' flips as the kernels take them: 16 where the mate's strand is flipped (FR 0 0, RF 16 16, FF 0 16)
+  uint32_t flip1() const { return orientation == 1 ? 16u : 0u; }
+  uint32_t flip2() const { return orientation == 0 ? 0u : 16u; }
 };
 // What the last pair() and the last sam() / bam() counted (Tail::counts).
 struct LineCounts {
@@ -143,6 +147,11 @@ struct InsertEstimate {
   int32_t min_insert, max_insert;  // 0 unless estimated
   bool estimated;
 };
+// What estimate_library() learns: the estimate under each orientation (FR, RF, FF) and the chosen one, -1 for none.
+struct LibraryEstimate {
+  InsertEstimate by[3];
+  int32_t orientation;
+};
 
 // One text on its way home at a time (per GPU).  Two device-to-host copies queued in the copy engines take both of them, and
 // the next batch's reads wait for their copy in until every queued text is home (scratch/sdma_probe.hip: a 30 MB copy in
@@ -158,7 +167,7 @@ struct TextGate {
 // anybody asks (Tail::stage_ms).  run(): kOrder, kTrace, kCompact.  pair(): kRescue when it rescues, kPairing.  sam() / bam():
 // kMapq with LineOptions::mapq; kFilterIndex, the line index with the line filter, or else kUnmappedIndex, the one with
 // LineOptions::unmapped alone; kMateScore, mate_score_kernel with LineOptions::mate_tags on a batch with device qualities;
-// kText, the SAM text's or the BAM records' kernels.  estimate_insert(): kInsert.
+// kText, the SAM text's or the BAM records' kernels.  estimate_insert() and estimate_library(): kInsert.
 enum Stage { kOrder, kTrace, kCompact, kText, kPairing, kRescue, kMapq, kUnmappedIndex, kFilterIndex, kInsert, kMateScore, kStages };
 
 class Tail {
@@ -199,7 +208,11 @@ class Tail {
   // The insert size range the records of the last run() suggest (insert_sample_kernel, insert_bounds_kernel): the pairs whose
   // mates have one record each, their inserts' quartiles, the fence around them.  Runs on `stream` and waits for it.  Reads the
   // records only: what pair() made, the slot's options and the counts stay as they are.
-  int estimate_insert(hipStream_t stream, InsertEstimate *out, std::string *err);
+  // "Informative" follows opt.orientation.
+  int estimate_insert(const LineOptions &opt, hipStream_t stream, InsertEstimate *out, std::string *err);
+  // The same under the three orientations in one pass (library_sample_kernel, insert_bounds_kernel with a block each), and the
+  // choice: the orientation with the most informative pairs among the estimated ones, ties in the order FR RF FF, -1 for none.
+  int estimate_library(hipStream_t stream, LibraryEstimate *out, std::string *err);
   // The counts of the last pair() (all 0 unless it ran since the last run()) and of the last sam() / bam().
   LineCounts counts() const;
   // The device time of a stage, in ms.  Negative: the stage was not part of the last run() and of what followed it (pair(),
@@ -213,6 +226,7 @@ class Tail {
   struct Impl;
   std::unique_ptr<Impl> impl_;
   int impl(Impl **m);  // the state, made on first use; FEM_ERR_NOMEM
+  int estimate(const LineOptions *opt, uint32_t n_hist, hipStream_t stream, InsertEstimate *out, std::string *err);
 };
 
 }  // namespace femt

@@ -20,6 +20,7 @@ ABI_SYMBOLS = [
     "fem_device_numa", "fem_bind_thread_near_device",
     "fem_dev_allreduce_stats",
     "fem_dev_set_pairs", "fem_dev_fetch_pairs", "fem_dev_pair_count", "fem_dev_estimate_insert",
+    "fem_dev_set_orientation", "fem_dev_estimate_library",
     "fem_dev_set_rescue", "fem_dev_rescue_count", "fem_dev_set_rescue_discordant", "fem_dev_rescue_discordant_count", "fem_dev_set_mapq",
     "fem_dev_set_unmapped", "fem_dev_unmapped_count",
     "fem_dev_set_report", "fem_dev_filtered_count", "fem_dev_set_tags", "fem_dev_set_mate_tags",
@@ -76,6 +77,10 @@ class _InsertEstimate(C.Structure):
     _fields_ = [("n_pairs", C.c_uint64), ("n_unique", C.c_uint64), ("n_informative", C.c_uint64),
                 ("q25", C.c_int32), ("q50", C.c_int32), ("q75", C.c_int32),
                 ("min_insert", C.c_int32), ("max_insert", C.c_int32), ("estimated", C.c_int32)]
+
+
+class _LibraryEstimate(C.Structure):
+    _fields_ = [("by", _InsertEstimate * 3), ("orientation", C.c_int32)]
 
 
 class _RescueParams(C.Structure):
@@ -168,6 +173,9 @@ def load_hip():
         L.fem_dev_pair_count.argtypes = [vp, C.c_int, C.POINTER(u64)]
     if hasattr(L, "fem_dev_estimate_insert"):
         L.fem_dev_estimate_insert.argtypes = [vp, C.c_int, C.POINTER(_InsertEstimate)]
+    if hasattr(L, "fem_dev_set_orientation"):
+        L.fem_dev_set_orientation.argtypes = [vp, C.c_int, C.c_int]
+        L.fem_dev_estimate_library.argtypes = [vp, C.c_int, C.POINTER(_LibraryEstimate)]
     if hasattr(L, "fem_dev_set_rescue"):
         L.fem_dev_set_rescue.argtypes = [vp, C.c_int, C.POINTER(_RescueParams)]
         L.fem_dev_rescue_count.argtypes = [vp, C.c_int, C.POINTER(u64)]
@@ -389,6 +397,21 @@ class InsertEstimate:
 
     def __repr__(self):
         return "InsertEstimate(%s)" % ", ".join("%s=%d" % (f, getattr(self, f)) for f in self.FIELDS)
+
+
+ORIENTATIONS = ("fr", "rf", "ff")  # FEM_ORIENT_FR, _RF, _FF
+
+
+class LibraryEstimate:
+    """fem_library_estimate: the insert estimate under each orientation (.by: three InsertEstimate, FR RF FF) and the chosen
+    orientation (.orientation: 0, 1, 2, or -1 when no orientation has enough informative pairs)."""
+
+    def __init__(self, r):
+        self.by = tuple(InsertEstimate(r.by[o]) for o in range(3))
+        self.orientation = int(r.orientation)
+
+    def __repr__(self):
+        return "LibraryEstimate(orientation=%d, by=%r)" % (self.orientation, self.by)
 
 
 class Device:
@@ -633,6 +656,21 @@ class Device:
         r = _InsertEstimate()
         self._check(self._L.fem_dev_estimate_insert(self._h, slot, C.byref(r)))
         return InsertEstimate(r)
+
+    def set_orientation(self, orientation, slot=0):
+        """fem_dev_set_orientation: the library's orientation in pair mode: 0 / "fr" (the default), 1 / "rf", 2 / "ff"."""
+        if isinstance(orientation, str):
+            if orientation.lower() not in ORIENTATIONS:
+                raise FemError("fem_dev_set_orientation: not one of fr, rf, ff: %r" % orientation)
+            orientation = ORIENTATIONS.index(orientation.lower())
+        self._check(self._L.fem_dev_set_orientation(self._h, slot, int(orientation)))
+
+    def estimate_library(self, slot=0):
+        """fem_dev_estimate_library: estimate_insert under the three orientations in one pass over the slot's batch, and the
+        orientation with the most informative pairs (LibraryEstimate); the slot's options and later fetches are untouched."""
+        r = _LibraryEstimate()
+        self._check(self._L.fem_dev_estimate_library(self._h, slot, C.byref(r)))
+        return LibraryEstimate(r)
 
     def pair_count(self, slot=0):
         """fem_dev_pair_count: proper pairs of the slot's last paired text."""

@@ -368,6 +368,42 @@ typedef struct {
 } fem_insert_estimate;
 int fem_dev_estimate_insert(fem_dev *h, int slot, fem_insert_estimate *out);
 
+/* ---- the library's orientation (new; the default, FR, is every rule above as it stands) ----
+ * fem_dev_set_orientation: a slot option of its own, FEM_ERR_INVALID for anything but the three values.  It takes effect in pair
+ *   mode and stays through fem_dev_set_pairs calls, as the other fem_dev_set_* options do.
+ * Rule.  An orientation is a pair of flip bits (flip1, flip2) for mate 1 and mate 2:
+ *     FEM_ORIENT_FR  0 0  forward mate upstream, reverse mate downstream, facing each other
+ *     FEM_ORIENT_RF  1 1  the reverse-strand mate starts at or before the forward-strand one (the mates point away from each other)
+ *     FEM_ORIENT_FF  0 1  mate 1 forward upstream of mate 2 forward, or the whole fragment on the other strand: both reverse,
+ *                         mate 2 upstream of mate 1
+ *   The virtual strand of a record of mate m is its strand (FLAG & 16) XOR flip_m.  Every rule of pair mode is kept word for
+ *   word with "strand" read as "virtual strand":
+ *   Pairing.  (a, b) is concordant when neither carries 0x8000, both lie on one sequence, their virtual strands differ, the
+ *     virtually forward one f has pos0(f) <= pos0(r), and min_insert <= end0(r) - pos0(f) <= max_insert.  The choice (least NM
+ *     sum, ties to the smaller a, then b) is unchanged.  TLEN is +ins on f's primary line and -ins on r's: f is the leftmost
+ *     starting mate in all three orientations, at equal pos0 the virtually forward one.  FLAG 0x10 and 0x20, RNEXT and PNEXT
+ *     stay the real strands and places.  fem_dev_set_mapq's pair term counts the concordant combinations of this rule.
+ *   Rescue (fem_dev_set_rescue, fem_dev_set_rescue_discordant).  For an anchor of mate m_a and the searched mate m_b:
+ *     v = strand(anchor) XOR flip_{m_a}; the window is the rule's below with v for the anchor's strand; B is searched
+ *     reverse-complemented iff (v is forward) XOR flip_{m_b}; the traced record carries FLAG 16 iff B was reverse-complemented;
+ *     it is kept iff start >= 0 and it is concordant with its anchor by the rule above, on its real CIGAR span.  Tiles, the
+ *     key, the anchor limit, the order of the directions and of the appended records are untouched.
+ *   fem_dev_estimate_insert follows the slot's orientation: informative = concordant by the rule above within
+ *     0 .. FEM_INSERT_MAX.  A unique pair at equal pos0 on opposite strands is informative under FR and under RF.
+ * fem_dev_estimate_library: one pass over the batch, the three estimates side by side: by[O] is what fem_dev_estimate_insert
+ *   gives with orientation O set (n_pairs and n_unique are the same in all three).  orientation = the O with the most
+ *   informative pairs among those with estimated = 1, ties in the order FR, RF, FF; -1 when none reaches FEM_INSERT_MIN_PAIRS.
+ *   Preconditions, errors and the promise that the slot's options and counts stay as they are: fem_dev_estimate_insert's. */
+#define FEM_ORIENT_FR 0
+#define FEM_ORIENT_RF 1
+#define FEM_ORIENT_FF 2
+int fem_dev_set_orientation(fem_dev *h, int slot, int orientation);
+typedef struct {
+  fem_insert_estimate by[3];
+  int32_t orientation;
+} fem_library_estimate;
+int fem_dev_estimate_library(fem_dev *h, int slot, fem_library_estimate *out);
+
 /* ---- mate rescue (new; opt-in: with it off every paired output stays byte for byte what it is without it) ----
  * fem_dev_set_rescue: the slot's read pairs are rescued at max_edits = E edits (0 <= E <= 15, else FEM_ERR_INVALID); NULL: off.
  *   It takes effect with pair mode (fem_dev_set_pairs); fetch time refuses max_insert - min_insert > 65536 (FEM_ERR_UNSUPPORTED).
@@ -579,7 +615,7 @@ int fem_dev_index_info(const fem_dev *h, char *buf, uint64_t cap);
  * the unmapped reads' lines themselves are written by the text and BAM record kernels: 7 and 11; none with a line filter set);
  * 15 = the line filter's line index kernels of a fem_dev_fetch_sam / fem_dev_fetch_bam with fem_dev_set_report on (one entry
  * per call; they make the unmapped reads' part of the index too, so 14 has no entry then);
- * 16 = the insert sampling and bounds kernels of fem_dev_estimate_insert (one entry per call, the zeroing of the histogram
+ * 16 = the insert sampling and bounds kernels of fem_dev_estimate_insert or fem_dev_estimate_library (one entry per call, the zeroing of the histogram
  * included; its fem_dev_fetch_records counts 3, 4 and 5 as any other; no fetch of records, text or pairs counts here);
  * 17 = the score kernel (ms:i) of a paired fem_dev_fetch_sam / fem_dev_fetch_bam with fem_dev_set_mate_tags on (one entry per
  * call; MC, MQ and ms themselves are written by the text and BAM record kernels: 7 and 11; none with the setting off). */
