@@ -14,7 +14,6 @@ import gzip
 import itertools
 import os
 import pathlib
-import subprocess
 import sys
 import tempfile
 import time
@@ -32,10 +31,9 @@ from tests import rescue_model as rm
 from tests import tags_model as tm
 from tests import unmapped_model as um
 from tests import util
-from tests.test_gpu_pairs import _write_fastq, make_pairs
+from tests.cases import make_pairs, write_fastq
+from tests.harness import build_index, decode_bam_file, first_difference, run_fem
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FEM = os.path.join(ROOT, "fem_amd", "csrc", "FEM")
 THREADS = 8
 COPIES = (6, 12, 40, 80)
 IUPAC = b"NNNNRYKMSWBDHVn"
@@ -266,12 +264,6 @@ def slice_trials():
 
 # ---- the device ----
 
-def _first_difference(got, want):
-    g, w = got.split(b"\n"), want.split(b"\n")
-    k = next((i for i, (a, b) in enumerate(zip(g, w)) if a != b), min(len(g), len(w)))
-    return "line %d of %d / %d: got %r want %r" % (k, len(g) - 1, len(w) - 1, g[k:k + 1], w[k:k + 1])
-
-
 def _counts(dev, t):
     from fem_amd import FemError
     out = []
@@ -321,13 +313,13 @@ def compare(dev, t, want, X=None):
     # the text, the counts behind it, the text again the other way
     text, _, _, stats = dev.fetch_sam(slot=s, nowait=t.nowait, **hq)
     if text != want.text:
-        diffs.append("fetch_sam: " + _first_difference(text, want.text))
+        diffs.append("fetch_sam: " + first_difference(text, want.text))
     got = _counts(dev, t)
     if got != want.counts:
         diffs.append("counts after the text: got %r want %r" % (got, want.counts))
     again = dev.fetch_sam(slot=s, nowait=not t.nowait, **hq)[0]
     if again != text:
-        diffs.append("fetch_sam, the other nowait: " + _first_difference(again, text))
+        diffs.append("fetch_sam, the other nowait: " + first_difference(again, text))
     # BAM at the drawn level (its qualities on the device)
     if t.quals_on_host:
         dev.stage_text(q, t.rnames, slot=s)
@@ -337,7 +329,7 @@ def compare(dev, t, want, X=None):
     if payload != want.bam:
         ref_names = [x.encode() for x in t.names]
         try:
-            where = _first_difference(bm.bam_payload_to_sam(payload, ref_names), bm.bam_payload_to_sam(want.bam, ref_names))
+            where = first_difference(bm.bam_payload_to_sam(payload, ref_names), bm.bam_payload_to_sam(want.bam, ref_names))
         except Exception as err:  # (records that do not decode)
             where = "undecodable: %r" % err
         diffs.append("fetch_bam level %d: %s" % (t.bam_level, where))
@@ -393,17 +385,16 @@ def _counters(t, want):
 
 def compare_cli(t, want, rng, timeout=300):
     """The paired trial through FEM index + FEM map with the drawn switches -> the list of differences."""
-    from tests.test_gpu_bam import _decode_bam_file
     diffs = []
     with tempfile.TemporaryDirectory() as tmp:
         fa, idx_path, out = os.path.join(tmp, "ref.fa"), os.path.join(tmp, "ref.idx"), os.path.join(tmp, "out")
         with open(fa, "wb") as fh:
             fh.write(b"".join(b">" + nm.encode() + b" desc\n" + s + b"\n" for nm, s in zip(t.names, t.seqs)))
-        subprocess.run([FEM, "index", "12", "3", fa, idx_path], check=True, capture_output=True, timeout=timeout)
+        build_index(fa, idx_path)
         n = t.n
         paths = [pathlib.Path(tmp) / "r1.fq", pathlib.Path(tmp) / "r2.fq"]
         for m, suffix in ((0, "/1"), (1, "/2")):
-            _write_fastq(paths[m], t.reads[m * n:(m + 1) * n], [x + suffix for x in t.rnames[m * n:(m + 1) * n]],
+            write_fastq(paths[m], t.reads[m * n:(m + 1) * n], [x + suffix for x in t.rnames[m * n:(m + 1) * n]],
                          t.quals[m * n:(m + 1) * n], False)
         args = ["-e", str(t.e), "-t", "4", "--ref", fa, "--index", idx_path, "--read1", str(paths[0]), "--read2", str(paths[1]),
                 "-o", out, "--batch", str(2 * int(rng.integers(1, max(2, n // 2)))), "-I", str(t.I), "-X", str(t.X)]
@@ -413,15 +404,15 @@ def compare_cli(t, want, rng, timeout=300):
         args += ([] if t.strata is None else ["--strata", str(t.strata)]) + ([] if t.max_hits is None else ["--max-hits", str(t.max_hits)])
         args += [] if t.rg is None else ["--rg", "@RG\tID:" + t.rg.decode("latin-1")]
         args += ["--bam=%d" % t.bam_level] if t.bam else []
-        r = subprocess.run([FEM, "map"] + args, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout)
+        r = run_fem("map", *args, timeout=timeout)
         if r.returncode != 0:
             return ["FEM map: exit status %d: %s" % (r.returncode, r.stderr.decode("latin-1")[-400:])]
-        data = _decode_bam_file(out) if t.bam else open(out, "rb").read()
+        data = decode_bam_file(out) if t.bam else open(out, "rb").read()
         lines = data.split(b"\n")
         k = next((i for i, l in enumerate(lines) if not l.startswith(b"@")), len(lines))
         body = b"\n".join(lines[k:])
         if body != want.text:
-            diffs.append("FEM map%s: %s" % (" --bam" if t.bam else "", _first_difference(body, want.text)))
+            diffs.append("FEM map%s: %s" % (" --bam" if t.bam else "", first_difference(body, want.text)))
         got = [l for l in r.stderr.decode("latin-1").splitlines() if l.startswith("The number of")]
         if got != _counters(t, want):
             diffs.append("FEM map: counters %r want %r" % (got, _counters(t, want)))

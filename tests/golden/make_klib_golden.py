@@ -6,7 +6,7 @@ reference's sources are (`make -C oracle ref` builds the library from REF):
 
 The vectors are inputs + what the reference code returned for them; no reference source is stored.  klib_records.npz
 holds, for every input tests/test_ref_klib.py gives the reference, fingerprints of what those tests compare, recorded
-while they run against the library (test_ref_klib.input_key / file_key / StoredView / perm_fingerprint):
+while they run against the library (tests/cases.py: input_key / file_key / StoredView / perm_fingerprint):
     kseq_key[F, 8], last_rc[F], n_records[F], all_qual[F], names_seqs[F, 16], quals[F, 16]   per file
     sort_key[S, 8], perm[S, 16]                                                               per key array sorted"""
 import os
@@ -19,14 +19,14 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 from oracle import ref_klib  # noqa: E402
-from tests import test_ref_klib as T  # noqa: E402
+from tests import cases as T  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def main():
     out = {}
-    cases = [k for k in T._sort_cases() if len(k) <= 1000]
+    cases = [k for k in T.sort_cases() if len(k) <= 1000]
     for i, keys in enumerate(cases):
         _, perm = ref_klib.radix_sort(keys)
         out["keys_%d" % i], out["perm_%d" % i] = keys, perm
@@ -35,7 +35,7 @@ def main():
 
     out = {}
     rng = np.random.default_rng(4)
-    files = [T.HAND_MADE[k] for k in sorted(T.HAND_MADE)] + [T._random_file(rng) for _ in range(60)]
+    files = [T.HAND_MADE[k] for k in sorted(T.HAND_MADE)] + [T.random_file(rng) for _ in range(60)]
     with tempfile.TemporaryDirectory() as d:
         for i, data in enumerate(files):
             p = os.path.join(d, "f.fq")

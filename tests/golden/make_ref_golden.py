@@ -262,7 +262,7 @@ def reference_outcome(inp, e, a, stages=True):
 
 def oracle_outcome(inp, e, a, with_result=False):
     """The same outcome from the oracle (oracle/fem_oracle.c), under the same names."""
-    from tests.test_host import expected_sam
+    from tests.cases import expected_sam
     ref = fo.Reference(inp.seqs)
     idx = fo.OracleIndex(ref, K, STEP)
     res = fo.map_reads(ref, idx, fo.ReadBatch(inp.reads), e=e, a=a, k=K, step=STEP)

@@ -1,17 +1,10 @@
 """The C-ABI library loads without a GPU and exports every symbol include/fem_hip.h declares."""
 import ctypes
 import os
-import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def declared_symbols():
-    text = open(os.path.join(ROOT, "include", "fem_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(fem_[a-z0-9_]+)\s*\(", text)))
+from tests.cases import declared_symbols
 
 
 def test_header_and_binding_agree():

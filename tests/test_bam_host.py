@@ -9,7 +9,7 @@ import pytest
 
 from fem_amd import host
 from tests import bam_model as bm
-from tests.test_cli import run
+from tests.harness import run_fem
 
 REFS = [b"chr1", b"chrX_long_name"]
 
@@ -111,13 +111,13 @@ def zlib_raw(b):
 def test_cli_bam_usage_and_refusals():
     import __graft_entry__ as g
     g.build()
-    r = run("map", "-h")
+    r = run_fem("map", "-h")
     assert r.returncode == 0 and b"--bam" in r.stderr
     base = ("map", "--ref", "a", "--index", "b", "--read1", "c", "-o", "d")
     for bad in ("--bam=2", "--bam=x", "--bam=", "--bam=01"):
-        r = run(*(base + (bad,)))
+        r = run_fem(*(base + (bad,)))
         assert r.returncode == 1 and b"Wrong BAM compression level (0-1)." in r.stderr, bad
     for var in ("FEM_HOST_TAIL", "FEM_HOST_FORMAT", "FEM_HOST_QUALS"):
-        r = run(*(base + ("--bam",)), env={var: "1"})
+        r = run_fem(*(base + ("--bam",)), env={var: "1"})
         assert r.returncode == 1 and (b"--bam is not supported with %s=1" % var.encode()) in r.stderr, var
         assert b"Loaded index" not in r.stderr

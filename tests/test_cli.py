@@ -1,70 +1,37 @@
 """The drop-in command line (fem_amd/csrc/FEM): argument handling without a GPU, end-to-end `index` + `map` with one."""
-import gzip
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 from oracle import fem_oracle as fo
 from tests import util
-from tests.test_host import expected_sam
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FEM = os.path.join(ROOT, "fem_amd", "csrc", "FEM")
-
-
-def run(*args, env=None):
-    full = dict(os.environ, **env) if env else None
-    return subprocess.run([FEM] + list(args), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300, env=full)
+from tests.cases import expected_sam, write_case
+from tests.harness import run_fem
 
 
 def test_usage_and_argument_errors():
     import __graft_entry__ as g
     g.build()
-    r = run()
+    r = run_fem()
     assert r.returncode == 1 and b"Usage:   FEM <command>" in r.stderr           # src/FEM.c:24-28
-    r = run("frobnicate")
+    r = run_fem("frobnicate")
     assert r.returncode == 1 and b"unrecognized command" in r.stderr               # src/FEM.c:37-39
-    r = run("index", "12", "3")
+    r = run_fem("index", "12", "3")
     assert r.returncode == 1 and b"Usage: FEM index <window_size> <step_size> <reference> <output>" in r.stderr
     # k = 16 is refused from the arguments alone: before the reference is read and before a device is opened
     for k in ("16", "0"):
-        r = run("index", k, "3", "/nonexistent/ref.fa", "/nonexistent/out.idx")
+        r = run_fem("index", k, "3", "/nonexistent/ref.fa", "/nonexistent/out.idx")
         assert r.returncode == 1 and b"window_size must be 1..15 and step_size >= 1." in r.stderr
         assert b"Usage: FEM index" in r.stderr and b"fem_dev_open" not in r.stderr
-    r = run("map", "-h")
+    r = run_fem("map", "-h")
     assert r.returncode == 0 and b"--read1" in r.stderr                            # src/FEM_map.c:123-125
-    r = run("map", "-e", "9", "--ref", "a", "--index", "b", "--read1", "c", "-o", "d")
+    r = run_fem("map", "-e", "9", "--ref", "a", "--index", "b", "--read1", "c", "-o", "d")
     assert r.returncode == 1 and b"Wrong error threshold." in r.stderr             # src/FEM_map.c:30-33
-    r = run("map", "-e", "3", "--index", "b", "--read1", "c", "-o", "d")
+    r = run_fem("map", "-e", "3", "--index", "b", "--read1", "c", "-o", "d")
     assert r.returncode == 1 and b"Reference file path is required." in r.stderr
-    r = run("map", "-a", "3", "--ref", "a", "--index", "b", "--read1", "c", "-o", "d")
+    r = run_fem("map", "-a", "3", "--ref", "a", "--index", "b", "--read1", "c", "-o", "d")
     assert r.returncode == 1 and b"Wrong number of additional q-grams." in r.stderr
-    r = run("map", "-f", "x")
+    r = run_fem("map", "-f", "x")
     assert r.returncode == 1 and b"Wrong name of seeding algorithm!" in r.stderr   # src/FEM_map.c:113-117
-
-
-def write_case(tmp_path, seed, e, L, n_reads, gz):
-    rng = np.random.default_rng(seed)
-    seqs = util.repeat_rich_reference(rng, n_seq=3, unit_len=300, n_units=4, copies=40, spacer=200)
-    seqs.append(util.rand_seq(rng, 150_000))
-    names = ["chr%s" % c for c in "ABCD"]
-    reads = util.make_reads(rng, seqs, n_reads, L, e, n_rate=0.002)
-    rnames = ["read_%d" % i for i in range(n_reads)]
-    quals = ["".join(chr(33 + (7 * i + j) % 41) for j in range(L)) for i in range(n_reads)]
-    fa = tmp_path / "ref.fa"
-    with open(fa, "wb") as f:
-        for n, s in zip(names, seqs):
-            f.write(b">" + n.encode() + b" some description\n")
-            for i in range(0, len(s), 70):
-                f.write(s[i:i + 70] + b"\n")
-    fq = tmp_path / ("reads.fq.gz" if gz else "reads.fq")
-    op = gzip.open if gz else open
-    with op(fq, "wb") as f:
-        for n, r, q in zip(rnames, reads, quals):
-            f.write(b"@" + n.encode() + b" 1:N:0\n" + r + b"\n+\n" + q.encode() + b"\n")
-    return seqs, names, reads, rnames, quals, str(fa), str(fq)
 
 
 @pytest.mark.gpu
@@ -75,11 +42,11 @@ def test_index_and_map_end_to_end(tmp_path, e, L, gz, batch):
     idx = fo.OracleIndex(ref)
     want = fo.map_reads(ref, idx, fo.ReadBatch(reads), e=e)
     index_path, sam_path, oracle_index = str(tmp_path / "ref.idx"), str(tmp_path / "out.sam"), str(tmp_path / "o.idx")
-    r = run("index", "12", "3", fa, index_path)
+    r = run_fem("index", "12", "3", fa, index_path)
     assert r.returncode == 0, r.stderr.decode()
     idx.save(oracle_index)
     assert open(index_path, "rb").read() == open(oracle_index, "rb").read()  # byte-identical index file
-    r = run("map", "-e", str(e), "-t", "3", "--ref", fa, "--index", index_path, "--read1", fq, "-o", sam_path,
+    r = run_fem("map", "-e", str(e), "-t", "3", "--ref", fa, "--index", index_path, "--read1", fq, "-o", sam_path,
             "--batch", str(batch))
     assert r.returncode == 0, r.stderr.decode()
     text = open(sam_path).read()
@@ -88,7 +55,7 @@ def test_index_and_map_end_to_end(tmp_path, e, L, gz, batch):
     assert text[len(header):] == expected_sam(names, reads, rnames, quals, want)
     # the same run with the ordering / traceback / MD done by libfemhost instead of the device
     host_sam = str(tmp_path / "host.sam")
-    r2 = run("map", "-e", str(e), "-t", "3", "--ref", fa, "--index", index_path, "--read1", fq, "-o", host_sam,
+    r2 = run_fem("map", "-e", str(e), "-t", "3", "--ref", fa, "--index", index_path, "--read1", fq, "-o", host_sam,
              "--batch", str(batch), env={"FEM_HOST_TAIL": "1"})
     assert r2.returncode == 0, r2.stderr.decode()
     assert open(host_sam).read() == text
@@ -97,7 +64,7 @@ def test_index_and_map_end_to_end(tmp_path, e, L, gz, batch):
     # ... and with the device's text but the qualities kept on the host (the default from 24 threads on), packed and as characters
     for env in ({"FEM_HOST_FORMAT": "1"}, {"FEM_HOST_FORMAT": "1", "FEM_SPLICE": "0"}, {"FEM_PACK_BASES": "0"}, {"FEM_HOST_QUALS": "1"},
                 {"FEM_HOST_QUALS": "1", "FEM_PACK_BASES": "0"}):
-        r3 = run("map", "-e", str(e), "-t", "3", "--ref", fa, "--index", index_path, "--read1", fq, "-o", host_sam,
+        r3 = run_fem("map", "-e", str(e), "-t", "3", "--ref", fa, "--index", index_path, "--read1", fq, "-o", host_sam,
                  "--batch", str(batch), env=env)
         assert r3.returncode == 0, r3.stderr.decode()
         assert open(host_sam).read() == text, env
@@ -113,19 +80,19 @@ def test_map_fails_loudly_on_missing_or_truncated_reads(tmp_path):
     # the reference exits with EXIT_FAILURE in both cases (src/sequence_batch.c:33-35, 63-66): no statistics, no "Time:"
     seqs, names, reads, rnames, quals, fa, fq = write_case(tmp_path, 5, 3, 100, 300, False)
     index_path = str(tmp_path / "ref.idx")
-    assert run("index", "12", "3", fa, index_path).returncode == 0
-    r = run("map", "-e", "3", "-t", "2", "--ref", fa, "--index", index_path, "--read1", str(tmp_path / "nope.fq"), "-o",
+    assert run_fem("index", "12", "3", fa, index_path).returncode == 0
+    r = run_fem("map", "-e", "3", "-t", "2", "--ref", fa, "--index", index_path, "--read1", str(tmp_path / "nope.fq"), "-o",
             str(tmp_path / "a.sam"))
     assert r.returncode != 0 and b"Cannot find sequence file!" in r.stderr and b"Time:" not in r.stderr
     data = open(fq, "rb").read()
     cut = tmp_path / "cut.fq"
     cut.write_bytes(data[:len(data) - 37])  # ends inside a quality line
-    r = run("map", "-e", "3", "-t", "2", "--ref", fa, "--index", index_path, "--read1", str(cut), "-o", str(tmp_path / "b.sam"),
+    r = run_fem("map", "-e", "3", "-t", "2", "--ref", fa, "--index", index_path, "--read1", str(cut), "-o", str(tmp_path / "b.sam"),
             "--batch", "50")
     assert r.returncode != 0 and b"Didn't reach the end of sequence file" in r.stderr and b"Time:" not in r.stderr
-    r = run("map", "-e", "3", "-t", "2", "--ref", fa, "--index", index_path, "--read1", fq, "-o", "/nonexistent_dir/x.sam")
+    r = run_fem("map", "-e", "3", "-t", "2", "--ref", fa, "--index", index_path, "--read1", fq, "-o", "/nonexistent_dir/x.sam")
     assert r.returncode != 0 and b"Cannot open output file" in r.stderr
-    r = run("map", "-e", "3", "-t", "2", "--ref", fa, "--index", index_path, "--read1", fq, "-o", "/dev/full")
+    r = run_fem("map", "-e", "3", "-t", "2", "--ref", fa, "--index", index_path, "--read1", fq, "-o", "/dev/full")
     assert r.returncode != 0 and b"write error" in r.stderr
 
 
@@ -144,11 +111,11 @@ def test_map_on_several_gpus_gives_the_same_records_and_counters(tmp_path, share
         pytest.skip("needs two GPUs")
     seqs, names, reads, rnames, quals, fa, fq = write_case(tmp_path, 21, 3, 100, 900, False)
     index_path = str(tmp_path / "ref.idx")
-    assert run("index", "12", "3", fa, index_path).returncode == 0
+    assert run_fem("index", "12", "3", fa, index_path).returncode == 0
     outs = []
     for gpus in ("1", "3" if shared else "2"):
         sam = str(tmp_path / ("g%s.sam" % gpus))
-        r = run("map", "-e", "3", "-t", "4", "--gpus", gpus, "--ref", fa, "--index", index_path, "--read1", fq, "-o", sam,
+        r = run_fem("map", "-e", "3", "-t", "4", "--gpus", gpus, "--ref", fa, "--index", index_path, "--read1", fq, "-o", sam,
                 "--batch", "120", env={"FEM_TEST_SHARE_GPU": "1"} if shared else None)
         assert r.returncode == 0, r.stderr.decode()
         counters = [l for l in r.stderr.decode().splitlines() if l.startswith("The number of")]
@@ -209,11 +176,11 @@ def test_map_regrows_its_staging_for_unusual_records(tmp_path):
     idx = fo.OracleIndex(ref)
     want = fo.map_reads(ref, idx, fo.ReadBatch(reads), e=1)
     ix = str(tmp_path / "r.idx")
-    assert run("index", "12", "3", str(fa), ix).returncode == 0
+    assert run_fem("index", "12", "3", str(fa), ix).returncode == 0
     exp = "@SQ\tSN:chrL\tLN:%d\n" % len(seqs[0]) + expected_sam(["chrL"], reads, rnames, quals, want)
     for env in (None, {"FEM_HOST_FORMAT": "1"}, {"FEM_HOST_FORMAT": "1", "FEM_SPLICE": "0"}, {"FEM_PACK_BASES": "0"}, {"FEM_HOST_QUALS": "1"}):
         out = str(tmp_path / "o.sam")
-        r = run("map", "-e", "1", "-t", "4", "--ref", str(fa), "--index", ix, "--read1", str(fq), "-o", out, "--batch", "200", env=env)
+        r = run_fem("map", "-e", "1", "-t", "4", "--ref", str(fa), "--index", ix, "--read1", str(fq), "-o", out, "--batch", "200", env=env)
         assert r.returncode == 0, r.stderr.decode()
         assert open(out).read() == exp
     assert want.stats[1] > 300

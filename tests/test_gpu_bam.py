@@ -1,9 +1,5 @@
 """BAM output on the device: the BGZF compressor alone (fem_dev_bgzf_compress), fem_dev_fetch_bam against fem_dev_fetch_sam on
 the same batches through the model of tests/bam_model.py, and FEM map --bam end to end.  Needs a GPU: -m gpu."""
-import gzip
-import os
-import struct
-import subprocess
 import zlib
 
 import numpy as np
@@ -12,10 +8,8 @@ import pytest
 from oracle import fem_oracle as fo
 from tests import bam_model as bm
 from tests import util
-from tests.test_cli import FEM, write_case
-from tests.test_gpu_pairs import _write_fastq
-from tests.test_gpu_rescue import make_rescue_pairs
-from tests.test_gpu_sam import _case
+from tests.cases import make_rescue_pairs, write_case, write_fastq
+from tests.harness import bam_vs_sam, build_index, check_members, counters, decode_bam_file, open_device, open_sam_case, run_fem
 
 pytestmark = pytest.mark.gpu
 
@@ -45,15 +39,6 @@ def _compressor_inputs():
     }
 
 
-def _check_members(data, payload):
-    members = bm.parse_bgzf(data, eof=False)
-    assert gzip.decompress(data + bm.BGZF_EOF) == payload
-    assert b"".join(m[0] for m in members) == payload
-    for raw, size, _ in members:
-        assert size <= 18 + 5 + len(raw) + 8, "a member larger than its stored form"
-    return members
-
-
 @pytest.mark.parametrize("level", [0, 1])
 def test_compressor_alone(dev, level):
     for name, data in _compressor_inputs().items():
@@ -61,7 +46,7 @@ def test_compressor_alone(dev, level):
         if not data:
             assert out == b""
             continue
-        members = _check_members(out, data)
+        members = check_members(out, data)
         assert [len(m[0]) for m in members[:-1]] == [bm.MEMBER_INPUT] * (len(members) - 1), name
         if level == 0:
             assert all(m[2] == 0 for m in members), name
@@ -76,7 +61,7 @@ def test_compressor_ratio_against_zlib_level_1(dev):
     for profile in ("walk", "illumina"):
         payload = bm.sam_to_bam_payload(bm.synthetic_sam(rng, 4000, 100, profile), [b"chr1", b"chr2"])
         out = dev.bgzf_compress(payload, 1)
-        members = _check_members(out, payload)
+        members = check_members(out, payload)
         assert all(m[2] == 2 for m in members), profile  # dynamic Huffman blocks
         ref = 0
         for i in range(0, len(payload), bm.MEMBER_INPUT):
@@ -86,46 +71,18 @@ def test_compressor_ratio_against_zlib_level_1(dev):
         assert len(out) <= 1.08 * ref, (profile, len(out), ref)
 
 
-def _bam_vs_sam(dev, slot, ref_names, n_sam=None):
-    """fetch_sam and fetch_bam on the slot's staged batch: equal counters, level 0 == the model's encoding of the text, level 1
-    inflates to it, no record spans two members, nowait gives the same bytes.  Returns the SAM text."""
-    text, n_records, n_asserted, stats = dev.fetch_sam(slot=slot)
-    want = bm.sam_to_bam_payload(text, ref_names)
-    for level in (0, 1):
-        data, raw_len, n_blocks, n_rec_b, n_ass_b, stats_b = dev.fetch_bam(slot=slot, level=level)
-        assert (n_rec_b, n_ass_b) == (n_records, n_asserted) and np.array_equal(stats_b, stats)
-        assert raw_len == len(want)
-        members = _check_members(data, want) if want else []
-        assert data or not want
-        assert len(members) == n_blocks
-        if level == 0:
-            assert all(m[2] == 0 for m in members)
-        at = 0
-        for raw, _, _ in members:  # whole records in every member, packed greedily
-            bm.records(raw)
-            at += len(raw)
-            if at < len(want):
-                nxt = struct.unpack_from("<i", want, at)[0] + 4
-                assert len(raw) + nxt > bm.MEMBER_INPUT
-        again = dev.fetch_bam(slot=slot, level=level, nowait=True)
-        assert again[0] == data
-    if n_sam is not None:
-        assert bm.bam_payload_to_sam(want, ref_names) == text
-    return text
-
-
 @pytest.mark.parametrize("seed,e,L,n,repeats,odd", [(1, 3, 100, 1500, False, True), (2, 7, 150, 800, True, True),
                                                      (3, 2, 64, 3000, True, False), (4, 0, 36, 500, False, False),
                                                      (5, 7, 260, 700, False, True), (6, 4, 1024, 300, False, True)])
 def test_fetch_bam_equals_fetch_sam(seed, e, L, n, repeats, odd):
-    d, ref, idx, seqs, names, reads, rnames, quals = _case(seed, e, L, n, repeats, odd)
+    d, ref, idx, seqs, names, reads, rnames, quals = open_sam_case(seed, e, L, n, repeats, odd)
     try:
         batch = fo.ReadBatch(reads)
         q = np.frombuffer("".join(quals).encode(), np.uint8)
         d.stage_reads(batch.bases, batch.off, slot=1)
         d.stage_text(q, rnames, slot=1)
         d.map_staged(e=e, slot=1)
-        text = _bam_vs_sam(d, 1, [x.encode() for x in names], n_sam=True)
+        text = bam_vs_sam(d, 1, [x.encode() for x in names], n_sam=True)
         assert text.count(b"\n") > min(n // 2, 60) or L < 40
         # the qualities on the host: no BAM
         d.stage_text(q, rnames, slot=1, quals_on_host=True)
@@ -137,7 +94,7 @@ def test_fetch_bam_equals_fetch_sam(seed, e, L, n, repeats, odd):
 
 
 def test_reads_without_records_and_name_limits():
-    d, ref, idx, seqs, names, reads, rnames, quals = _case(11, 2, 100, 400, False, False)
+    d, ref, idx, seqs, names, reads, rnames, quals = open_sam_case(11, 2, 100, 400, False, False)
     try:
         rng = np.random.default_rng(3)
         junk = [util.rand_seq(rng, 100) for _ in range(50)]  # (random reads: no records)
@@ -151,7 +108,7 @@ def test_reads_without_records_and_name_limits():
             d.stage_text(q, rn, slot=0)
             d.map_staged(e=2, slot=0)
             if ok:
-                _bam_vs_sam(d, 0, [x.encode() for x in names], n_sam=True)
+                bam_vs_sam(d, 0, [x.encode() for x in names], n_sam=True)
             else:
                 from fem_amd import FemError
                 with pytest.raises(FemError, match="254"):
@@ -169,17 +126,11 @@ def test_reads_without_records_and_name_limits():
 
 @pytest.mark.parametrize("rescue", [None, 8])
 def test_paired_fetch_bam_equals_fetch_sam(rescue):
-    from fem_amd import Device
     rng = np.random.default_rng(21)
     seqs = [util.rand_seq(rng, 200_000), util.rand_seq(rng, 60_000)]
     names = ["chr%d" % i for i in range(len(seqs))]
-    ref = fo.Reference(seqs)
-    idx = fo.OracleIndex(ref)
-    d = Device(0)
+    d, ref, idx = open_device(seqs, names)
     try:
-        d.upload_reference(seqs)
-        d.upload_reference_names(names)
-        d.upload_index(12, 3, idx.lookup, idx.occ[:idx.n_occ])
         n = 600
         r1, r2 = make_rescue_pairs(rng, seqs, n, 100, 120, 2, 8, 500)
         reads = r1 + r2
@@ -190,7 +141,7 @@ def test_paired_fetch_bam_equals_fetch_sam(rescue):
         d.stage_reads(batch.bases, batch.off, slot=2)
         d.stage_text(q, ["p%d" % (i % n) for i in range(2 * n)], slot=2)
         d.map_staged(e=2, slot=2)
-        text = _bam_vs_sam(d, 2, [x.encode() for x in names], n_sam=True)
+        text = bam_vs_sam(d, 2, [x.encode() for x in names], n_sam=True)
         assert b"\t=\t" in text
         if rescue:
             assert d.rescue_count(slot=2) > 0
@@ -200,35 +151,15 @@ def test_paired_fetch_bam_equals_fetch_sam(rescue):
 
 # ---- FEM map --bam ----
 
-def _decode_bam_file(path):
-    raw = b"".join(m[0] for m in bm.parse_bgzf(open(path, "rb").read()))
-    assert raw[:4] == b"BAM\1"
-    (l_text,) = struct.unpack_from("<i", raw, 4)
-    text = raw[8:8 + l_text]
-    p = 8 + l_text
-    (n_ref,) = struct.unpack_from("<i", raw, p)
-    p += 4
-    names = []
-    for _ in range(n_ref):
-        (ln,) = struct.unpack_from("<i", raw, p)
-        names.append(raw[p + 4:p + 4 + ln - 1])
-        p += 8 + ln
-    return text + bm.bam_payload_to_sam(raw[p:], names)
-
-
-def _counters(err):
-    return [l for l in err.decode().splitlines() if l.startswith("The number of")]
-
-
 def _map(*args):
-    return subprocess.run([FEM, "map"] + list(args), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    return run_fem("map", *args)
 
 
 @pytest.mark.parametrize("gz", [False, True])
 def test_cli_bam_single_end(tmp_path, gz):
     seqs, names, reads, rnames, quals, fa, fq = write_case(tmp_path, 91, 3, 100, 3000, gz)
     index_path = str(tmp_path / "ref.idx")
-    assert subprocess.run([FEM, "index", "12", "3", fa, index_path], capture_output=True, timeout=600).returncode == 0
+    build_index(fa, index_path)
     sam = str(tmp_path / "out.sam")
     r = _map("-e", "3", "-t", "3", "--ref", fa, "--index", index_path, "--read1", fq, "-o", sam, "--batch", "1000")
     assert r.returncode == 0, r.stderr.decode()
@@ -237,8 +168,8 @@ def test_cli_bam_single_end(tmp_path, gz):
         out = str(tmp_path / "out.bam")
         rb = _map("-e", "3", "-t", "3", "--ref", fa, "--index", index_path, "--read1", fq, "-o", out, "--batch", "1000", flag)
         assert rb.returncode == 0, rb.stderr.decode()
-        assert _decode_bam_file(out) == want, flag
-        assert _counters(rb.stderr) == _counters(r.stderr)
+        assert decode_bam_file(out) == want, flag
+        assert counters(rb.stderr) == counters(r.stderr)
         data = open(out, "rb").read()
         assert data.endswith(bm.BGZF_EOF)
         if flag != "--bam=0":
@@ -251,15 +182,15 @@ def test_cli_bam_pairs_with_rescue(tmp_path):
     fa = tmp_path / "ref.fa"
     fa.write_bytes(b"".join(b">s%d desc\n%s\n" % (i, s) for i, s in enumerate(seqs)))
     idx_path = tmp_path / "ref.idx"
-    subprocess.run([FEM, "index", "12", "3", str(fa), str(idx_path)], check=True, capture_output=True, timeout=600)
+    build_index(fa, idx_path)
     n = 2000
     r1, r2 = make_rescue_pairs(rng, seqs, n, 100, 100, 2, 8, 500, frac=0.1)
     base = ["pair%d" % i for i in range(n)]
     q1 = ["".join(chr(33 + (7 * i + j) % 40) for j in range(len(r))) for i, r in enumerate(r1)]
     q2 = ["".join(chr(34 + (5 * i + j) % 40) for j in range(len(r))) for i, r in enumerate(r2)]
     p1, p2 = tmp_path / "r1.fq", tmp_path / "r2.fq"
-    _write_fastq(p1, r1, [b + "/1" for b in base], q1, False)
-    _write_fastq(p2, r2, [b + "/2" for b in base], q2, False)
+    write_fastq(p1, r1, [b + "/1" for b in base], q1, False)
+    write_fastq(p2, r2, [b + "/2" for b in base], q2, False)
     common = ["-e", "2", "-t", "4", "--ref", str(fa), "--index", str(idx_path), "--read1", str(p1), "--read2", str(p2),
               "--batch", "700", "--rescue", "8"]
     sam = str(tmp_path / "out.sam")
@@ -270,6 +201,6 @@ def test_cli_bam_pairs_with_rescue(tmp_path):
         out = str(tmp_path / "out.bam")
         rb = _map(*(common + ["-o", out, flag]))
         assert rb.returncode == 0, rb.stderr.decode()
-        assert _decode_bam_file(out) == want, flag
-        assert _counters(rb.stderr) == _counters(r.stderr)
-        assert any("rescued" in l for l in _counters(rb.stderr))
+        assert decode_bam_file(out) == want, flag
+        assert counters(rb.stderr) == counters(r.stderr)
+        assert any("rescued" in l for l in counters(rb.stderr))

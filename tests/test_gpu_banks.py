@@ -10,74 +10,24 @@ import pytest
 
 from oracle import fem_oracle as fo
 from tests import util
+from tests.cases import banked_reference
+from tests.harness import banked_compare, banked_device
 
 pytestmark = pytest.mark.gpu
-
-
-def _device(bank_bases, bank_seqs=None):
-    from fem_amd import Device
-    os.environ["FEM_FORCE_DENSE"] = "1"
-    os.environ["FEM_TEST_BANK_BASES"] = str(bank_bases)
-    if bank_seqs:
-        os.environ["FEM_TEST_BANK_SEQS"] = str(bank_seqs)
-    try:
-        return Device(0)
-    finally:
-        os.environ.pop("FEM_FORCE_DENSE")
-        os.environ.pop("FEM_TEST_BANK_BASES")
-        os.environ.pop("FEM_TEST_BANK_SEQS", None)
-
-
-def _reference(rng, n_seq, shared):
-    """Sequences that share repeat units (a list then has entries in several banks) between stretches of their own."""
-    units = [util.rand_seq(rng, 260) for _ in range(5)]
-    seqs = []
-    for s in range(n_seq):
-        parts = [util.rand_seq(rng, int(rng.integers(200, 1500)))]
-        for _ in range(int(rng.integers(18, 30))):
-            if shared and rng.random() < 0.6:
-                parts.append(util.mutate(rng, units[int(rng.integers(0, len(units)))], int(rng.integers(0, 3))))
-            parts.append(util.rand_seq(rng, int(rng.integers(300, 2500))))
-        if s % 3 == 1:
-            parts.append(b"N" * 40)
-            parts.append(util.rand_seq(rng, 900))
-        seqs.append(b"".join(parts))
-    return seqs
-
-
-def _compare(dev, seqs, reads, e, a, banked=True):
-    ref = fo.Reference(seqs)
-    idx = fo.OracleIndex(ref)
-    batch = fo.ReadBatch(reads)
-    want = fo.map_reads(ref, idx, batch, e=e, a=a)
-    dev.upload_reference(seqs)
-    dev.upload_index(12, 3, idx.lookup, idx.occ[:idx.n_occ])
-    assert dev.seed_kernel(e=e, a=a) == ("seed_join_banked_kernel" if banked else "seed_join_kernel")
-    got = dev.map_batch(batch.bases, batch.off, e=e, a=a)
-    off, cand, ed, end = got.per_strand()
-    assert np.array_equal(off, want.cand_off), "candidate counts per (read, strand)"
-    assert np.array_equal(cand, want.cands), "candidate locations"
-    assert np.array_equal(ed, want.v_ed), "edit distances / accept set"
-    assert np.array_equal(end[ed != 0xFF], want.v_end[want.v_ed != 0xFF]), "end offsets"
-    assert np.array_equal(got.stats, want.stats), (got.stats, want.stats)
-    rec = dev.fetch_records()  # the tail works on (sequence, position): nothing of the banks is left in it
-    assert np.array_equal(rec.rec_begin, want.rec_off) and np.array_equal(rec.tid, want.r_tid) and np.array_equal(rec.pos0, want.r_pos)
-    assert np.array_equal(rec.cigar, want.cig) and np.array_equal(rec.md, want.md)
-    return want
 
 
 @pytest.mark.parametrize("e,a,L,bank_bases,n_seq", [(3, 1, 100, 110_000, 7), (7, 1, 150, 130_000, 9), (2, 2, 80, 90_000, 6),
                                                      (0, 1, 60, 110_000, 5), (5, 1, 120, 1_000_000, 4)])
 def test_banked_reference_equals_oracle(e, a, L, bank_bases, n_seq):
     rng = np.random.default_rng(5200 + 10 * e + a)
-    seqs = _reference(rng, n_seq, shared=True)
+    seqs = banked_reference(rng, n_seq, shared=True)
     reads = util.make_reads(rng, seqs, 900, L, e, n_rate=0.002)
     # reads at the very start and end of every sequence: the first and last sequences of a bank, the remapped entries
     for s in seqs:
         reads += [s[:L], s[-L:], fo.revcomp(s[:L]), fo.revcomp(s[-L:]), s[3:3 + L], s[-L - 5:-5]]
-    dev = _device(bank_bases)
+    dev = banked_device(bank_bases)
     try:
-        want = _compare(dev, seqs, reads, e, a, banked=bank_bases < 1_000_000)
+        want = banked_compare(dev, seqs, reads, e, a, banked=bank_bases < 1_000_000)
     finally:
         dev.close()
     assert want.stats[1] > 0.7 * 900
@@ -96,15 +46,15 @@ def test_banks_cut_by_the_number_of_sequences():
     # within its bank); FEM_TEST_BANK_SEQS = 2 cuts seven sequences into banks of 2 + 2 + 2 + 1.  Reads at every
     # sequence's first bases take that path.
     rng = np.random.default_rng(77)
-    seqs = _reference(rng, 7, shared=True)
+    seqs = banked_reference(rng, 7, shared=True)
     L, e = 100, 3
     reads = util.make_reads(rng, seqs, 600, L, e, n_rate=0.002)
     for s in seqs:
         for at in (0, 1, 2, 5, 30, 200, 900, 1020, 1030):
             reads += [s[at:at + L], fo.revcomp(s[at:at + L])]
-    dev = _device(10_000_000, bank_seqs=2)
+    dev = banked_device(10_000_000, bank_seqs=2)
     try:
-        _compare(dev, seqs, reads, e, 1)
+        banked_compare(dev, seqs, reads, e, 1)
     finally:
         dev.close()
 
@@ -114,13 +64,13 @@ def test_more_banks_than_the_join_takes_falls_back():
     # tables and the 64-bit form runs — same results
     from fem_amd import Device
     rng = np.random.default_rng(61)
-    seqs = _reference(rng, 9, shared=True)
+    seqs = banked_reference(rng, 9, shared=True)
     reads = util.make_reads(rng, seqs, 400, 100, 3, n_rate=0.0)
     ref = fo.Reference(seqs)
     idx = fo.OracleIndex(ref)
     batch = fo.ReadBatch(reads)
     want = fo.map_reads(ref, idx, batch, e=3, a=1)
-    dev = _device(30_000)
+    dev = banked_device(30_000)
     try:
         dev.upload_reference(seqs)
         dev.upload_index(12, 3, idx.lookup, idx.occ[:idx.n_occ])
@@ -172,8 +122,8 @@ def test_a_higher_bank_whose_part_of_u_is_dropped_whole():
         seqs_sets.append([a_seq, b_seq])
         reads.append([core, fo.revcomp(core), util.mutate(rng, core, 1)[:L].ljust(L, b"C"), core[:L - 1] + b"G"])
     for seqs, rds in zip(seqs_sets, reads):
-        dev = _device(len(seqs[0]) + 2048 + 100)  # bank 0 = sequence A, bank 1 = sequence B
+        dev = banked_device(len(seqs[0]) + 2048 + 100)  # bank 0 = sequence A, bank 1 = sequence B
         try:
-            _compare(dev, seqs, rds + util.make_reads(rng, seqs, 60, L, e), e, 1)
+            banked_compare(dev, seqs, rds + util.make_reads(rng, seqs, 60, L, e), e, 1)
         finally:
             dev.close()

@@ -14,10 +14,8 @@ from tests import pair_model as pm
 from tests import rescue_model as rm
 from tests import unmapped_model as um
 from tests import util
-from tests.test_gpu_bam import _check_members
-from tests.test_gpu_parity import assert_same
-from tests.test_gpu_rescue import make_rescue_pairs
-from tests.test_gpu_tail import assert_same_records
+from tests.cases import make_rescue_pairs
+from tests.harness import assert_same, assert_same_records, check_members
 
 pytestmark = pytest.mark.gpu
 
@@ -110,13 +108,13 @@ def test_every_buffer_is_freed_once_and_a_regrow_loses_nothing(world, tiny):
         assert dev.rescue_count(slot=slot) == len(f["kept"])
         data, raw_len, n_blocks, n_rec_b, _, stats_b = dev.fetch_bam(slot=slot, level=1)
         payload = bm.sam_to_bam_payload(text, [x.encode() for x in w["names"]])
-        assert raw_len == len(payload) and len(_check_members(data, payload)) == n_blocks
+        assert raw_len == len(payload) and len(check_members(data, payload)) == n_blocks
         assert n_rec_b == n_records and np.array_equal(stats_b, stats)
         pairs = dev.fetch_pairs(slot=slot)
         for k, v in pm.pair_arrays(f["withr"], N_PAIRS, I, X).items():
             assert pairs.n_proper == v if k == "n_proper" else np.array_equal(getattr(pairs, k), v), k
         blob = bytes(np.random.default_rng(5).integers(65, 70, 100_000, dtype=np.uint8))
-        _check_members(dev.bgzf_compress(blob, 1), blob)
+        check_members(dev.bgzf_compress(blob, 1), blob)
         held = live_bytes()
         assert held[0] > base[0] and held[1] > base[1]
         # twice the reads in the same slot: every per-batch buffer regrows while it holds the first batch's sizes

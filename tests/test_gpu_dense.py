@@ -5,41 +5,25 @@ BASELINE configs C3-C5 (3 Gbp, ~60 entries per 12-mer bucket) run seed_select_ke
 for bit with the oracle on references large enough that the library picks them unprompted
 (reference path: src/filter.c:80-131,146-223).  Needs a GPU: -m gpu.
 """
-import os
-
 import numpy as np
 import pytest
 
 from oracle import fem_oracle as fo
+from tests.harness import assert_same, banked_device, dense_setup, device_with_env
 
 pytestmark = pytest.mark.gpu
 
 
-def _setup(seed, seq_lens):
-    from fem_amd import Device, host
-    for k in ("FEM_FORCE_GENERIC", "FEM_FORCE_HASH", "FEM_FORCE_DENSE", "FEM_NO_DENSE", "FEM_TEST_TINY_BUFFERS"):
-        assert os.environ.get(k, "0") == "0", k
-    text, off, lens = host.synth_reference(seed, seq_lens, threads=8)
-    seqs = [text[int(o):int(o) + int(l)] for o, l in zip(off, lens)]
-    ref = fo.Reference([s.tobytes() for s in seqs])
-    idx = fo.OracleIndex(ref)
-    dev = Device(0)
-    dev.upload_reference(seqs)
-    n, lookup, occ = dev.build_index(12, 3)  # also checks the device index build at this size, byte for byte
-    assert n == idx.n_occ and np.array_equal(lookup, idx.lookup) and np.array_equal(occ, idx.occ[:n])
-    return dict(text=text, off=off, lens=lens, ref=ref, idx=idx, dev=dev)
-
-
 @pytest.fixture(scope="module")
 def mid():  # 3 x 25 Mbp: 25 M entries in 16.8 M buckets -> seed_fast_kernel<R, true>
-    d = _setup(71, [25_000_000] * 3)
+    d = dense_setup(71, [25_000_000] * 3)
     yield d
     d["dev"].close()
 
 
 @pytest.fixture(scope="module")
 def dense():  # 3 x 72 Mbp: 72 M entries, 4.3 per bucket -> seed_select_kernel<R> + seed_join_kernel<R>
-    d = _setup(72, [72_000_000] * 3)
+    d = dense_setup(72, [72_000_000] * 3)
     yield d
     d["dev"].close()
 
@@ -54,12 +38,7 @@ def _compare(d, seed, n_reads, L, e, a=1, extra=()):
     d["dev"].reset_timing()
     got = d["dev"].map_batch(batch.bases, batch.off, e=e, a=a)
     d["dev"].set_timing(False)
-    off, cand, ed, end = got.per_strand()
-    assert np.array_equal(off, want.cand_off), "candidate counts per (read, strand)"
-    assert np.array_equal(cand, want.cands), "candidate locations"
-    assert np.array_equal(ed, want.v_ed), "edit distances / accept set"
-    assert np.array_equal(end[ed != 0xFF], want.v_end[want.v_ed != 0xFF]), "end offsets"
-    assert np.array_equal(got.stats, want.stats), (got.stats, want.stats)
+    assert_same(want, got)
     assert want.stats[1] > 0.9 * n_reads
     return got
 
@@ -102,7 +81,6 @@ def test_dense_form_a2(dense):
 def test_dense_form_declines_what_its_32_bit_coordinates_cannot_hold():
     # more than 2^18 sequences: the remapped near-start entries (seq << 10 | pos) do not fit; the library must fall back to
     # the 64-bit hash-join form even when asked for the dense one, with identical results
-    from fem_amd import Device
     from tests import util
     rng = np.random.default_rng(262)
     n_seq = (1 << 18) + 5
@@ -113,11 +91,7 @@ def test_dense_form_declines_what_its_32_bit_coordinates_cannot_hold():
     ref = fo.Reference(seqs)
     idx = fo.OracleIndex(ref)
     want = fo.map_reads(ref, idx, fo.ReadBatch(reads), e=3, stages=fo.STAGE_SEED | fo.STAGE_VERIFY)
-    os.environ["FEM_FORCE_DENSE"] = "1"
-    try:
-        dev = Device(0)
-    finally:
-        os.environ.pop("FEM_FORCE_DENSE")
+    dev = device_with_env(FEM_FORCE_DENSE=1)
     try:
         dev.upload_reference(seqs)
         dev.upload_index(12, 3, idx.lookup, idx.occ[:idx.n_occ])
@@ -213,21 +187,13 @@ def test_overlapped_pipeline_with_records_on_a_dense_index_equals_the_oracle(den
 def test_overlapped_pipeline_on_a_forced_dense_index(banked):
     # a small repeat-rich reference through the dense kernels (FEM_FORCE_DENSE=1), whole and cut into banks
     # (FEM_TEST_BANK_BASES): long lists, reads the join hands to the generic kernel, many candidates per strand
-    from fem_amd import Device
     from tests import util
     rng = np.random.default_rng(515 + banked)
     seqs = util.repeat_rich_reference(rng, n_seq=4, unit_len=300, n_units=10, copies=30)
     bank_bases = int(0.6 * sum(len(s) + 2048 for s in seqs)) if banked else 0  # two banks of two sequences
     ref = fo.Reference(seqs)
     idx = fo.OracleIndex(ref)
-    os.environ["FEM_FORCE_DENSE"] = "1"
-    if bank_bases:
-        os.environ["FEM_TEST_BANK_BASES"] = str(bank_bases)
-    try:
-        dev = Device(0)
-    finally:
-        os.environ.pop("FEM_FORCE_DENSE")
-        os.environ.pop("FEM_TEST_BANK_BASES", None)
+    dev = banked_device(bank_bases) if bank_bases else device_with_env(FEM_FORCE_DENSE=1)
     try:
         dev.upload_reference(seqs)
         dev.upload_index(12, 3, idx.lookup, idx.occ[:idx.n_occ])
@@ -251,7 +217,7 @@ def test_a_batch_that_meets_an_idle_device_is_mapped_in_parts_with_the_same_resu
     """launch_batch (fem_hip.hip): a batch committed to an idle device is copied, selected and joined in two parts (the
     pipeline's fill).  Same batch, same slot: in parts (idle device, the default), whole (FEM_NO_PARTS handle), in four
     parts (FEM_PARTS=4) — candidates, verification and counters must be identical; the dense index says what it runs on."""
-    from fem_amd import Device, host
+    from fem_amd import host
     d = dense
     assert "dense: 32-bit occurrence table, compact" in d["dev"].index_info() and "1 bank" in d["dev"].index_info()
     n, L, e = 300_000, 100, 3
@@ -267,12 +233,7 @@ def test_a_batch_that_meets_an_idle_device_is_mapped_in_parts_with_the_same_resu
     assert np.array_equal(in_parts.stats, got.stats)
     seqs = [d["text"][int(o):int(o) + int(l)] for o, l in zip(d["off"], d["lens"])]
     for env in ({"FEM_NO_PARTS": "1"}, {"FEM_PARTS": "4", "FEM_FORCE_DENSE": "1"}):  # (the second: the padded strided table)
-        os.environ.update(env)
-        try:
-            other = Device(0)
-        finally:
-            for k in env:
-                os.environ.pop(k)
+        other = device_with_env(**env)
         try:
             other.upload_reference(seqs)
             other.build_index(12, 3, fetch=False)

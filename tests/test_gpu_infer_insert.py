@@ -1,27 +1,23 @@
 """The insert size estimate on the device (fem_dev_estimate_insert: insert_sample_kernel + insert_bounds_kernel, fem_tail.hip) and
 FEM map --infer-insert against the plain-Python model of tests/insert_model.py on the oracle's single-end records of the same
 reads.  Needs a GPU: -m gpu."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 from oracle import fem_oracle as fo
 from tests import insert_model as im
 from tests import util
-from tests.test_gpu_pairs import _setup, _write_fastq, make_pairs
+from tests.cases import make_pairs, write_fastq
+from tests.harness import build_index, open_reference, run_fem
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FEM = os.path.join(ROOT, "fem_amd", "csrc", "FEM")
 E = 3
 
 
 class Case:
     def __init__(self, seed, repeats):
-        self.rng, self.dev, self.ref, self.idx, self.seqs, self.names = _setup(seed, repeats)
+        self.rng, self.dev, self.ref, self.idx, self.seqs, self.names = open_reference(seed, repeats, 50_000, 7)
 
     def model(self, reads, e=E):
         """(the oracle's records, the model's estimate) of a batch of pairs (mate 1's reads, then mate 2's)."""
@@ -258,8 +254,8 @@ def _fastq(tmp, tag, r1, r2):
     q1 = ["".join(chr(33 + (7 * i + j) % 40) for j in range(len(r))) for i, r in enumerate(r1)]
     q2 = ["".join(chr(34 + (5 * i + j) % 40) for j in range(len(r))) for i, r in enumerate(r2)]
     p1, p2 = tmp / (tag + "_1.fq"), tmp / (tag + "_2.fq")
-    _write_fastq(p1, r1, [b + "/1" for b in base], q1, False)
-    _write_fastq(p2, r2, [b + "/2" for b in base], q2, False)
+    write_fastq(p1, r1, [b + "/1" for b in base], q1, False)
+    write_fastq(p2, r2, [b + "/2" for b in base], q2, False)
     return p1, p2
 
 
@@ -271,7 +267,7 @@ def cli(tmp_path_factory):
     fa = tmp / "ref.fa"
     fa.write_bytes(b"".join(b">s%d desc\n%s\n" % (i, s) for i, s in enumerate(seqs)))
     idx_path = tmp / "ref.idx"
-    subprocess.run([FEM, "index", "12", "3", str(fa), str(idx_path)], check=True, capture_output=True, timeout=600)
+    build_index(fa, idx_path)
     ref = fo.Reference(seqs)
     return dict(tmp=tmp, rng=rng, seqs=seqs, fa=fa, idx=idx_path, ref=ref, oidx=fo.OracleIndex(ref))
 
@@ -282,9 +278,8 @@ def _model(cli, r1, r2):
 
 
 def _map(cli, p1, p2, out, *extra, env=None):
-    r = subprocess.run([FEM, "map", "-e", str(E), "-t", "4", "--ref", str(cli["fa"]), "--index", str(cli["idx"]), "--read1", str(p1),
-                        "--read2", str(p2), "-o", str(out)] + list(extra), capture_output=True, text=True,
-                       env=dict(os.environ, **(env or {})), timeout=900)
+    r = run_fem("map", "-e", E, "-t", "4", "--ref", cli["fa"], "--index", cli["idx"], "--read1", p1, "--read2", p2, "-o", out, *extra,
+                env=env, text=True)
     assert r.returncode == 0, r.stderr
     return r.stderr.splitlines(), out.read_bytes()
 

@@ -12,7 +12,7 @@ One reference of four sequences, about 300 kbp, whose second sequence crosses 2^
 GAP positions in front of every sequence) — in the first bank, so also where the reference is cut into banks of two sequences:
   * COPIES: a unit of 400 bases three times, the third with a 1-base, a 2-base and a 3-base deletion 130 bases apart (partners 1-3
     apart: the same or the neighbouring slot), the second across the 2^18 boundary; reads at every start offset.
-  * SOLO regions as in test_gpu_join_units.py (whose helpers this file uses), lists of exactly 40 and 64 entries: the true place
+  * SOLO regions as in test_gpu_join_units.py (their helpers: tests/cases.py, tests/harness.py), lists of exactly 40 and 64 entries: the true place
     sits in different lanes from list to list, the unit stays in the plain body.  Everywhere else lists have one entry: lane 0.
   * whole units of 60 bases in 32 and 40 copies: two agreeing lists flag 64 or 80 values, three more — as many as a group's array
     takes, or beyond: the read stays or goes to the generic kernel.
@@ -24,8 +24,9 @@ import numpy as np
 import pytest
 
 from oracle import fem_oracle as fo
-from tests import test_gpu_join_units as ju
 from tests import util
+from tests.cases import SOLO_LEN, SOLO_SLOTS, lone_copies, over_home
+from tests.harness import JOIN_FORMS, JoinWorld, join_check
 
 pytestmark = pytest.mark.gpu
 
@@ -40,7 +41,7 @@ WHOLE = (32, 40)                           # copies of the two whole units of 60
 WHOLE_LEN = 60
 NEAR_GROUPS = (2, 3, 5, 8)                 # near-copies per group
 NEAR_LEN = 150
-FORMS = ju.FORMS
+FORMS = JOIN_FORMS
 CASES = [(100, 3, 1), (100, 2, 1), (100, 4, 1), (150, 7, 1)]  # (L, e, a)
 
 
@@ -76,12 +77,12 @@ def _build_reference():
     third = bytearray(unit)
     for at, n in reversed(DELS):
         del third[at:at + n]
-    regions = [util.rand_seq(rng, ju.SOLO_LEN) for _ in SOLO]
+    regions = [util.rand_seq(rng, SOLO_LEN) for _ in SOLO]
     whole = [util.rand_seq(rng, WHOLE_LEN) for _ in WHOLE]
     near = [util.rand_seq(rng, NEAR_LEN) for _ in NEAR_GROUPS]
     lone_plan = [[] for _ in SEQ_LEN]      # per sequence: (class, slot) of the 12-mers that stand alone there
     for c, n in enumerate(SOLO):
-        for j in range(ju.SOLO_SLOTS):
+        for j in range(SOLO_SLOTS):
             for sq in rng.integers(0, len(SEQ_LEN), n - SOLO_HOMES):
                 lone_plan[int(sq)].append((c, j))
     whole_plan = [[] for _ in SEQ_LEN]
@@ -98,7 +99,7 @@ def _build_reference():
             copies["unit"].append((sq, lay.put(unit, 300), "plain"))
             copies["unit"].append((sq, lay.put(bytes(third), 900), "deletions"))
         lone = [lone_plan[sq][int(j)] for j in rng.permutation(len(lone_plan[sq]))]
-        lay.put(ju._lone_copies(rng, regions, lone), 60)
+        lay.put(lone_copies(rng, regions, lone), 60)
         for i in [whole_plan[sq][int(j)] for j in rng.permutation(len(whole_plan[sq]))]:
             copies["whole"][i].append((sq, lay.put(whole[i], int(rng.integers(10, 60)) * 3)))
         for c in range(len(SOLO)):
@@ -122,7 +123,7 @@ def _build_reference():
     return seqs, copies
 
 
-class _World(ju._World):
+class _World(JoinWorld):
     def __init__(self):
         self.seqs, self.copies = _build_reference()
         assert tuple(len(s) for s in self.seqs) == SEQ_LEN and sum(SEQ_LEN) > PERIOD and sum(SEQ_LEN) < 320_000
@@ -139,7 +140,7 @@ class _World(ju._World):
         freq = np.diff(self.idx.lookup.astype(np.int64))
         assert np.count_nonzero(freq == 1) > 0.9 * np.count_nonzero(freq)
         for n in SOLO:
-            assert np.count_nonzero(freq == n) >= ju.SOLO_SLOTS, (n, np.count_nonzero(freq == n))
+            assert np.count_nonzero(freq == n) >= SOLO_SLOTS, (n, np.count_nonzero(freq == n))
         for n in WHOLE:
             assert np.count_nonzero(freq == n) >= WHOLE_LEN // 3 - 4, (n, np.count_nonzero(freq == n))
         for c in range(len(SOLO)):
@@ -210,7 +211,7 @@ def test_every_bit_position_of_a_slot_and_the_word_edges(world, L, e, a, form):
         assert near_edge.min() >= 1, (s, near_edge)
     per_strand = np.diff(want.cand_off.astype(np.int64))
     assert np.count_nonzero(per_strand >= 2) > 0.5 * batch.n, "reads over the copies have a candidate in each"
-    ju._check(world, form, batch, want, e, a)
+    join_check(world, form, batch, want, e, a)
 
 
 def _over(rng, w, sq, pos, n, L, e):
@@ -237,7 +238,7 @@ def _lanes_batch(w, seed, L, e):
     for c in range(len(SOLO)):
         for sq, pos in w.copies["home"][c]:
             for _ in range(60):
-                r = ju._over_home(rng, w, c, sq, pos, L, e)
+                r = over_home(rng, w, c, sq, pos, L, e)
                 reads.append(util.revcomp(r) if rng.random() < 0.5 else r)
                 cls.append(c)
     return reads, (first, np.array(cls))
@@ -269,4 +270,4 @@ def test_flagged_lanes_capacity_and_survivor_order(world, L, e, a, form):
     assert np.count_nonzero((per_strand >= 2) & (per_strand <= 8)) >= 200, np.bincount(per_strand.ravel())[:10]
     for k in (2, 3, 5, 8):
         assert np.count_nonzero(per_strand == k) >= 10, (k, np.bincount(per_strand.ravel())[:10])
-    ju._check(world, form, batch, want, e, a)
+    join_check(world, form, batch, want, e, a)

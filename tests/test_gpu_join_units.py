@@ -16,13 +16,13 @@ entries, while the lists agree at the three regions only — few flagged values,
 its full body.  Which reads do that is asserted from the oracle (selected frequencies, candidates per strand) before anything
 runs on the GPU.
 Needs a GPU: -m gpu."""
-import os
-
 import numpy as np
 import pytest
 
 from oracle import fem_oracle as fo
 from tests import util
+from tests.cases import SOLO_LEN, SOLO_SLOTS, lone_copies, over_home
+from tests.harness import JOIN_FORMS, JoinWorld, join_check
 
 pytestmark = pytest.mark.gpu
 
@@ -31,27 +31,7 @@ COUNTS = (60, 64, 65, 100, 128, 129)       # copies of units 0..5: lists of exac
 NEAR = (0, 1, 3, 17, 1000, 1023, 1024)     # starts of the near-start unit's copies (one sequence each, in turn)
 N_SEQ = 4
 SOLO = (64, 65, 100, 128)                  # entries of every 12-mer's list in the solo regions of class 0..3
-SOLO_SLOTS = 14                            # indexed 12-mers of a solo region: offsets 0, 3, .. 39 -> 51 bases
-SOLO_LEN = 3 * (SOLO_SLOTS - 1) + 12
 SOLO_HOMES = 3                             # places where a region stands whole (the other entries: the 12-mer alone)
-FORMS = {"padded": {}, "compact": {"FEM_NO_STRIDED": "1"},
-         "banked": {"FEM_TEST_BANK_BASES": "10000000", "FEM_TEST_BANK_SEQS": "2"}}
-
-
-def _lone_copies(rng, regions, which):
-    """The 12-mers (class, slot) of `which`, each alone: three bases between one and the next, chosen so that none of the four
-    indexed 12-mers across the joint is a 12-mer of a region again (the lists stay exactly as long as planned).  Twelve random
-    bases in front and behind, joined the same way."""
-    planted = {r[3 * j:3 * j + 12] for r in regions for j in range(SOLO_SLOTS)}
-    mers = [util.rand_seq(rng, 12)] + [regions[c][3 * j:3 * j + 12] for c, j in which] + [util.rand_seq(rng, 12)]
-    out = bytearray(mers[0])
-    for nxt in mers[1:]:
-        while True:
-            joint = bytes(out[-12:]) + util.rand_seq(rng, 3) + nxt
-            if not any(joint[o:o + 12] in planted for o in (3, 6, 9, 12)):
-                break
-        out += joint[12:]
-    return bytes(out)
 
 
 def _build_reference():
@@ -107,7 +87,7 @@ def _build_reference():
         for at in sorted(head):
             out += util.rand_seq(rng, at - len(out))
             if isinstance(head[at], list):
-                out += _lone_copies(rng, regions, head[at])
+                out += lone_copies(rng, regions, head[at])
                 continue
             out += head[at]
             copies["near" if head[at] is near_unit else 3].append((s, at))
@@ -125,7 +105,7 @@ def _build_reference():
         # the region's again (the lists stay exactly as long as planned), then this sequence's whole regions between flanks
         out += util.rand_seq(rng, (-len(out)) % 3)
         lone = [lone_plan[s][int(j)] for j in rng.permutation(len(lone_plan[s]))]
-        out += _lone_copies(rng, regions, lone)
+        out += lone_copies(rng, regions, lone)
         for c in range(len(SOLO)):
             for _ in range(home_plan[s][c]):
                 out += util.rand_seq(rng, 72)
@@ -182,7 +162,7 @@ def _solo_lists(w):
                     assert np.count_nonzero((lst[64:] & np.uint64(0xFFFFFFFF)) < np.uint64(1024)) == 1, (c, j)
 
 
-class _World:
+class _World(JoinWorld):
     def __init__(self):
         self.seqs, self.copies = _build_reference()
         assert len(self.copies["mirrored"]) == SOLO_HOMES * (len(SOLO) - 1)
@@ -196,28 +176,6 @@ class _World:
         _list_classes(self.idx)
         _solo_lists(self)
         self.devices, self.wanted = {}, {}
-
-    def device(self, form):
-        if form not in self.devices:
-            from fem_amd import Device
-            env = dict(FORMS[form], FEM_FORCE_DENSE="1")
-            os.environ.update(env)
-            try:
-                dev = Device(0)
-            finally:
-                for k in env:
-                    os.environ.pop(k)
-            dev.upload_reference(self.seqs)
-            dev.upload_index(12, 3, self.idx.lookup, self.idx.occ[:self.idx.n_occ])
-            info = dev.index_info()
-            assert ("strided with pads" in info) == (form == "padded"), info
-            assert ("2 banks" in info) == (form == "banked"), info
-            self.devices[form] = dev
-        return self.devices[form]
-
-    def close(self):
-        for dev in self.devices.values():
-            dev.close()
 
 
 @pytest.fixture(scope="module")
@@ -250,30 +208,6 @@ def _reads(w, seed, L, e, n_random=1400):
     return reads
 
 
-def _check(w, form, batch, want, e, a):
-    dev = w.device(form)
-    assert dev.seed_kernel(e=e, a=a) == ("seed_join_banked_kernel" if form == "banked" else "seed_join_kernel")
-    got = dev.map_batch(batch.bases, batch.off, e=e, a=a)
-    off, cand, ed, end = got.per_strand()
-    assert np.array_equal(off, want.cand_off), "candidate counts per (read, strand)"
-    assert np.array_equal(cand, want.cands), "candidate locations"
-    assert np.array_equal(ed, want.v_ed), "edit distances / accept set"
-    assert np.array_equal(end[ed != 0xFF], want.v_end[want.v_ed != 0xFF]), "end offsets"
-    assert np.array_equal(got.stats, want.stats), (got.stats, want.stats)
-
-
-def _over_home(rng, w, c, sq, pos, L, e):
-    """A read of L bases that holds the whole solo region at (sq, pos), with 0..e edits in what lies before and behind the region
-    (an edit inside it takes four of its seeds away, a gap the seed selection steps into: such reads say nothing here)."""
-    s = w.seqs[sq]
-    before = int(rng.integers(0, L - SOLO_LEN + 1))
-    k = int(rng.integers(0, e + 1))
-    k_left = int(rng.integers(0, k + 1)) if before >= 3 else 0
-    left = util.mutate(rng, s[pos - before - e:pos], k_left)[-before:] if before else b""
-    right = util.mutate(rng, s[pos + SOLO_LEN:pos + SOLO_LEN + L], k - k_left)
-    return (left + s[pos:pos + SOLO_LEN] + right)[:L]
-
-
 def _solo_reads(w, seed, L, e, n_per_home=60):
     """-> reads over the whole solo regions (either strand), the class of each"""
     rng = np.random.default_rng(seed)
@@ -281,7 +215,7 @@ def _solo_reads(w, seed, L, e, n_per_home=60):
     for c in range(len(SOLO)):
         for sq, pos in w.copies[("home", c)]:
             for _ in range(n_per_home):
-                r = _over_home(rng, w, c, sq, pos, L, e)
+                r = over_home(rng, w, c, sq, pos, L, e)
                 reads.append(util.revcomp(r) if rng.random() < 0.5 else r)
                 cls.append(c)
     return reads, np.array(cls)
@@ -321,7 +255,7 @@ def _want(w, key, make, e, a):
     return w.wanted[key]
 
 
-@pytest.mark.parametrize("form", list(FORMS))
+@pytest.mark.parametrize("form", list(JOIN_FORMS))
 @pytest.mark.parametrize("e,a,L", CASES)
 def test_lists_on_both_sides_of_the_split_equal_the_oracle(world, e, a, L, form):
     batch, want, (first, cls) = _want(world, (e, a, L), lambda: _main_batch(world, e, a, L), e, a)
@@ -340,7 +274,7 @@ def test_lists_on_both_sides_of_the_split_equal_the_oracle(world, e, a, L, form)
     # ... and on the other side of the boundary: lists of exactly 64 entries, kept by the join too (plain body)
     short, _ = _finished_in_the_full_body(want, cls, first, long_classes=(0,))
     assert short[0] >= (0.8 if R >= 5 else 0.2) * drawn, short
-    _check(world, form, batch, want, e, a)
+    join_check(world, form, batch, want, e, a)
 
 
 def _two_bodies_in_one_read(w, seed, L=100, e=3):
@@ -351,13 +285,13 @@ def _two_bodies_in_one_read(w, seed, L=100, e=3):
     reads, cls = [], []
     for n in range(1000):
         c, sq, pos = w.copies["mirrored"][n % len(w.copies["mirrored"])]
-        r = _over_home(rng, w, c, sq, pos, L, e)
+        r = over_home(rng, w, c, sq, pos, L, e)
         reads += [r, util.revcomp(r)]
         cls += [c, c]
     return reads, (0, np.array(cls))
 
 
-@pytest.mark.parametrize("form", list(FORMS))
+@pytest.mark.parametrize("form", list(JOIN_FORMS))
 def test_a_unit_of_one_body_after_a_unit_of_the_other(world, form):
     # state must not leak from unit to unit: the bitmap clean, nothing left of a second chunk or of the survivors' masks
     e, a = 3, 1
@@ -370,4 +304,4 @@ def test_a_unit_of_one_body_after_a_unit_of_the_other(world, form):
     both = ok & (pre.min(axis=1) < 65) & (pre.min(axis=1) >= 2) & (per_strand.min(axis=1) >= 1)
     full_first = both & (pre[:, 0] > pre[:, 1])
     assert np.count_nonzero(full_first) >= 0.3 * batch.n and np.count_nonzero(both & ~full_first) >= 0.3 * batch.n, (np.count_nonzero(full_first), np.count_nonzero(both))
-    _check(world, form, batch, want, e, a)
+    join_check(world, form, batch, want, e, a)

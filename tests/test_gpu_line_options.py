@@ -1,55 +1,20 @@
 """A slot's output options together (fem_dev_set_pairs, _rescue, _rescue_discordant, _mapq, _unmapped, _report, _tags: one
 femt::LineOptions per slot, fem_hip.hip) and its counters (one femt::LineCounts): every option on and off again on one handle
 and one slot, against a fresh handle with the same options and against the Python models.  Needs a GPU: -m gpu."""
-import functools
-
 import numpy as np
 import pytest
 
 from fem_amd.device import FemError
-from oracle import fem_oracle as fo
-from tests import discordant_fixture as df
-from tests import discordant_model as dm
 from tests import pair_model as pm
 from tests import report_model as rp
 from tests import tags_model as tm
-from tests import unmapped_model as um
-from tests import util
-from tests.test_gpu_rescue import _run
+from tests.cases import I, LINE_E, LINE_RESCUE_E, MAX_HITS, RG, STRATA, X
+from tests.cases import line_options_case as case
+from tests.harness import fetch_sam, open_device, pairing_on
 
 pytestmark = pytest.mark.gpu
 
-K_PAIR_ALONE = 32  # fem_tail.hip: pairs with more combinations are their wave's
-e, E, I, X, L = 2, 8, 0, 500, 100
-STRATA, MAX_HITS, RG = 1, 3, b"grp1"
-
-
-@functools.lru_cache(maxsize=None)
-def case():
-    """46 pairs on a repeat-rich reference: discordant pairs, pairs with one heavy mate, plain ones, two that keep a mate
-    (both mates) without a record; the oracle's single-end records and the models' results."""
-    rng = np.random.default_rng(7)
-    main = [util.rand_seq(rng, 60_000)] + util.repeat_rich_reference(rng, n_seq=3, unit_len=300, n_units=4, copies=50, spacer=200)
-    seqs, r1, r2 = df.make_discordant_pairs(rng, main, 44, L, L, e, E, X, n_sym=4, decoy_copies=2)
-    r1 += [r1[2], util.rand_seq(rng, L)]
-    r2 += [util.rand_seq(rng, L), util.rand_seq(rng, L)]
-    n, reads = len(r1), r1 + r2
-    names = ["chr%d" % i for i in range(len(seqs))]
-    rnames = ["p%d" % i for i in range(n)] * 2
-    quals = ["".join(chr(33 + (11 * i + j) % 60) for j in range(len(r))) for i, r in enumerate(reads)]
-    ref = fo.Reference(seqs)
-    idx = fo.OracleIndex(ref)
-    want = fo.map_reads(ref, idx, fo.ReadBatch(reads), e=e, threads=8)
-    ext, kept, _, kinds = dm.rescue(want, n, reads, seqs, E, I, X)
-    c = dict(seqs=seqs, names=names, reads=reads, rnames=rnames, quals=quals, idx=idx, want=want, ext=ext, kept=kept, n=n)
-    c["n_kind2"] = sum(k == 2 for k, _ in kinds.values())
-    c["n_proper"] = pm.expected(ext, n, I, X)[1]
-    c["n_unmapped"] = len(um.unmapped_reads(ext, 2 * n))
-    # the fixture does its job: both kinds of rescue, reads that stay unmapped, proper pairs, a pair for pair_kernel's wave path
-    cnt = np.diff(want.rec_off.astype(np.int64))
-    assert c["n_kind2"] >= 1 and len(kept) > c["n_kind2"] and c["n_unmapped"] >= 2 and c["n_proper"] >= 1
-    assert any(cnt[i] * cnt[n + i] > K_PAIR_ALONE for i in range(n))
-    return c
+e, E = LINE_E, LINE_RESCUE_E
 
 
 def _model_text(c, strata=None, max_hits=None, tags=False):
@@ -60,20 +25,11 @@ def _model_text(c, strata=None, max_hits=None, tags=False):
 
 
 def _device(c):
-    from fem_amd import Device
-    dev = Device(0)
-    dev.upload_reference(c["seqs"])
-    dev.upload_reference_names(c["names"])
-    dev.upload_index(12, 3, c["idx"].lookup, c["idx"].occ[:c["idx"].n_occ])
-    return dev
+    return open_device(c["seqs"], c["names"], c["idx"])[0]
 
 
 def _pairing_on(dev):
-    dev.set_pairs(I, X)
-    dev.set_rescue(E)
-    dev.set_rescue_discordant(True)
-    dev.set_mapq(True)
-    dev.set_unmapped(True)
+    pairing_on(dev, I, X, E)
 
 
 def _all_on(dev):
@@ -83,7 +39,7 @@ def _all_on(dev):
 
 
 def _sam(dev, c):
-    return _run(dev, c["reads"], c["rnames"], c["quals"], e, 0)[0]
+    return fetch_sam(dev, c["reads"], c["rnames"], c["quals"], e, 0)[0]
 
 
 def _counts(dev):

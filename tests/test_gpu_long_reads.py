@@ -4,42 +4,24 @@ dense selection with its take masks of one, two and four words and its hand-off 
 the tail with MD strings beyond the first pass's staging, the SAM kernels, the packed transfer, read pairs with mates that
 overlap, contain one another and dovetail, the limits of the C ABI and `FEM map` end to end.  Each case asserts that its
 fixture reaches the path it is named for.  Needs a GPU: -m gpu."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 from oracle import fem_oracle as fo
 from tests import pair_model as pm
 from tests import util
-from tests.test_host import expected_sam
+from tests.cases import banked_reference, expected_sam, make_pairs
+from tests.harness import assert_same, assert_same_records, banked_compare, banked_device, build_index, dense_setup
+from tests.harness import device_with_env, fetch_sam, open_reference, run_fem
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FEM = os.path.join(ROOT, "fem_amd", "csrc", "FEM")
 MAX_LEN = 1024
 THREADS = 16
 BLOCK = 16            # reads per block of seed_fast_kernel (femk::kReadBlock)
 LEAN_CHARS = 16 * 256  # a block of the lean form holds at most this many characters when the batch has a read over 256
 MD_CAP = 32           # first-pass MD staging per record of the tail (fem_tail.hip: kMdCap)
 ODD = b"RYKM=.-*"     # characters outside ACGTN, as test_gpu_sam.py uses them
-
-
-def _device(**env):
-    """A handle opened with these environment switches set; the environment is restored afterwards."""
-    from fem_amd import Device
-    was = {k: os.environ.get(k) for k in env}
-    os.environ.update({k: str(v) for k, v in env.items()})
-    try:
-        return Device(0)
-    finally:
-        for k, v in was.items():
-            if v is None:
-                os.environ.pop(k)
-            else:
-                os.environ[k] = v
 
 
 def widest(L, R):
@@ -63,25 +45,6 @@ def _damage(rng, reads, lower_every=9, odd_every=7, n_run_every=11):
     return out
 
 
-def assert_same(got, want):
-    off, cand, ed, end = got.per_strand()
-    assert np.array_equal(off, want.cand_off), "candidate counts per (read, strand)"
-    assert np.array_equal(cand, want.cands), "candidate locations"
-    assert np.array_equal(ed, want.v_ed), "edit distances / accept set"
-    assert np.array_equal(end[ed != 0xFF], want.v_end[want.v_ed != 0xFF]), "end offsets"
-    assert np.array_equal(got.stats, want.stats), (got.stats, want.stats)
-
-
-def assert_same_records(rec, want):
-    assert np.array_equal(rec.rec_begin, want.rec_off), "records per read"
-    assert np.array_equal(rec.flag, want.r_flag), "FLAG"
-    assert np.array_equal(rec.tid, want.r_tid) and np.array_equal(rec.pos0, want.r_pos), "RNAME / POS"
-    assert np.array_equal(rec.nm, want.r_nm), "NM"
-    assert np.array_equal(rec.cigar_off, want.cig_off) and np.array_equal(rec.cigar, want.cig), "CIGAR"
-    assert np.array_equal(rec.md_off, want.md_off) and np.array_equal(rec.md, want.md), "MD"
-    assert np.array_equal(rec.stats, want.stats)
-
-
 def _sam_fields(text):
     """SAM lines split into fields, SEQ (which goes through the 4-bit BAM round trip) aside."""
     return [l.split("\t")[:9] + l.split("\t")[10:] for l in text.splitlines()]
@@ -99,7 +62,7 @@ def sparse():
     names = ["chr%d_%s" % (i, "x" * (40 * i)) for i in range(len(seqs))]
     ref = fo.Reference(seqs)
     idx = fo.OracleIndex(ref, threads=THREADS)
-    devs = {"default": _device(FEM_TEST_TINY_BUFFERS=0), "tiny-staging": _device(FEM_TEST_TINY_BUFFERS=1)}
+    devs = {"default": device_with_env(FEM_TEST_TINY_BUFFERS=0), "tiny-staging": device_with_env(FEM_TEST_TINY_BUFFERS=1)}
     for d in devs.values():
         d.upload_reference(seqs)
         d.upload_reference_names(names)
@@ -126,10 +89,10 @@ def _full_compare(s, reads, e, a, slot=0):
         dev.stage_reads(batch.bases, batch.off, slot=slot)
         dev.stage_text(q, rnames, slot=slot)
         dev.map_staged(e=e, a=a, slot=slot)
-        assert_same(dev.fetch(slot=slot), want)
-        assert_same(dev.fetch_packed(slot=slot), want)
+        assert_same(want, dev.fetch(slot=slot))
+        assert_same(want, dev.fetch_packed(slot=slot))
         rec = dev.fetch_records(slot=slot)
-        assert_same_records(rec, want)
+        assert_same_records(want, rec)
         text, n_records, n_asserted, stats = dev.fetch_sam(slot=slot)
         assert np.array_equal(stats, want.stats) and n_records == int(want.rec_off[-1]), name
         host_text, host_asserted = host.records_sam(s["tref"], rnames, batch.bases, batch.off, q, rec, threads=4, parts=True)
@@ -254,13 +217,13 @@ def test_packed_long_reads_three_ways(sparse, L, e):
     dev.commit_stage_packed(n, L, n_exc, slot=3)
     assert dev.stage_info(3)[1]
     dev.map_staged(e=e, slot=3)
-    assert_same(dev.fetch(slot=3), want)
-    assert_same_records(dev.fetch_records(slot=3), want)
+    assert_same(want, dev.fetch(slot=3))
+    assert_same_records(want, dev.fetch_records(slot=3))
     dev.stage_reads(batch.bases, batch.off, slot=2)
     assert dev.stage_info(2)[1], "a uniform batch with few exceptions crosses the link packed"
     dev.map_staged(e=e, slot=2)
-    assert_same(dev.fetch(slot=2), want)
-    assert_same_records(dev.fetch_records(slot=2), want)
+    assert_same(want, dev.fetch(slot=2))
+    assert_same_records(want, dev.fetch_records(slot=2))
     assert want.stats[1] > n // 4
 
 
@@ -300,8 +263,8 @@ def test_the_abi_takes_1024_and_refuses_1025(sparse):
 
     def check(slot):
         dev.map_staged(e=3, slot=slot)
-        assert_same(dev.fetch(slot=slot), want)
-        assert_same_records(dev.fetch_records(slot=slot), want)
+        assert_same(want, dev.fetch(slot=slot))
+        assert_same_records(want, dev.fetch_records(slot=slot))
 
     dev.stage_reads(good.bases, good.off, slot=0)
     check(0)
@@ -324,16 +287,14 @@ def test_the_abi_takes_1024_and_refuses_1025(sparse):
 # ---------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def dense():
-    from tests.test_gpu_dense import _setup
-    d = _setup(72, [72_000_000] * 3)
+    d = dense_setup(72, [72_000_000] * 3)
     yield d
     d["dev"].close()
 
 
 @pytest.fixture(scope="module")
 def mid():
-    from tests.test_gpu_dense import _setup
-    d = _setup(71, [25_000_000] * 3)
+    d = dense_setup(71, [25_000_000] * 3)
     yield d
     d["dev"].close()
 
@@ -366,9 +327,9 @@ def _dev_compare(d, reads, e, a, records):
     dev = d["dev"]
     dev.stage_reads(batch.bases, batch.off, slot=1)
     dev.map_staged(e=e, a=a, slot=1)
-    assert_same(dev.fetch(slot=1), want)
+    assert_same(want, dev.fetch(slot=1))
     if records:
-        assert_same_records(dev.fetch_records(slot=1), want)
+        assert_same_records(want, dev.fetch_records(slot=1))
     return want
 
 
@@ -414,16 +375,15 @@ def test_hash_join_form_on_long_reads(mid, e, a, L, n):
 # d. a reference in banks
 # ---------------------------------------------------------------------------------------------------------------------
 def test_banked_reference_with_long_reads():
-    from tests.test_gpu_banks import _compare, _device as banked_device, _reference
     rng = np.random.default_rng(3800)
-    seqs = _reference(rng, 7, shared=True)
+    seqs = banked_reference(rng, 7, shared=True)
     L, e = 800, 3
     reads = util.make_reads(rng, seqs, 200, L, e, n_rate=0.002)
     for s in seqs:
         reads += [s[:L], s[-L:], fo.revcomp(s[:L]), fo.revcomp(s[-L:]), s[3:3 + L], s[-L - 5:-5]]
     dev = banked_device(110_000)
     try:
-        want = _compare(dev, seqs, reads, e, 1)
+        want = banked_compare(dev, seqs, reads, e, 1)
         assert want.stats[1] > len(reads) // 4
     finally:
         dev.close()
@@ -458,8 +418,7 @@ def _placed_pairs(rng, seqs, n, L1, L2, e, max_edits=1):
 
 @pytest.mark.parametrize("L1,L2,n,X", [(250, 250, 300, 800), (300, 300, 300, 2000), (600, 1024, 160, 2000)])
 def test_long_mates_equal_the_pair_model(L1, L2, n, X):
-    from tests.test_gpu_pairs import _run, _setup as pair_setup, make_pairs
-    rng, dev, ref, idx, seqs, names = pair_setup(3900 + L1, False)
+    rng, dev, ref, idx, seqs, names = open_reference(3900 + L1, False, 50_000, 7)
     try:
         e = 3
         if L2 <= 300:
@@ -476,7 +435,7 @@ def test_long_mates_equal_the_pair_model(L1, L2, n, X):
         quals = ["".join(chr(33 + (11 * i + j) % 60) for j in range(len(r))) for i, r in enumerate(reads)]
         want = fo.map_reads(ref, idx, fo.ReadBatch(reads), e=e, threads=THREADS)
         dev.set_pairs(0, X, slot=1)
-        text, n_records, _, stats = _run(dev, reads, rnames, quals, e, slot=1)
+        text, n_records, _, stats = fetch_sam(dev, reads, rnames, quals, e, slot=1)
         assert np.array_equal(stats, want.stats) and n_records == int(want.rec_off[-1])
         exp = pm.sam_lines(want, n, names, reads, rnames, quals, 0, X)
         assert _sam_fields(text.decode("latin-1")) == _sam_fields(exp)
@@ -526,16 +485,16 @@ def cli_ref(tmp_path_factory):
     fa = tmp / "ref.fa"
     fa.write_bytes(b"".join(b">s%d desc\n%s\n" % (i, s) for i, s in enumerate(seqs)))
     ix = tmp / "ref.idx"
-    subprocess.run([FEM, "index", "12", "3", str(fa), str(ix)], check=True, capture_output=True, timeout=600)
+    build_index(fa, ix)
     ref = fo.Reference(seqs)
     return dict(rng=rng, seqs=seqs, fa=fa, ix=ix, ref=ref, idx=fo.OracleIndex(ref))
 
 
 def _fem_map(c, fq, out, *extra, read2=None, env=None):
-    args = [FEM, "map", "-e", "3", "-t", "4", "--ref", str(c["fa"]), "--index", str(c["ix"]), "--read1", str(fq), "-o", str(out)]
+    args = ["map", "-e", "3", "-t", "4", "--ref", c["fa"], "--index", c["ix"], "--read1", fq, "-o", out]
     if read2:
-        args += ["--read2", str(read2), "-X", "2000"]
-    return subprocess.run(args + list(extra), capture_output=True, text=True, timeout=900, env=dict(os.environ, **(env or {})))
+        args += ["--read2", read2, "-X", "2000"]
+    return run_fem(*args, *extra, env=env, text=True)
 
 
 def _batch_forms(stderr):

@@ -1,8 +1,5 @@
 """Mapping qualities on the device (fem_dev_set_mapq: mapq_kernel and pair_kernel<true> in front of the text kernels,
 fem_tail.hip) against the plain-Python rule of tests/mapq_model.py on the oracle's records.  Needs a GPU: -m gpu."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
@@ -10,25 +7,11 @@ from oracle import fem_oracle as fo
 from tests import mapq_model as mq
 from tests import rescue_model as rm
 from tests import util
-from tests.test_gpu_bam import _bam_vs_sam, _decode_bam_file
-from tests.test_gpu_pairs import _write_fastq, make_pairs
-from tests.test_gpu_rescue import make_rescue_pairs
+from tests.cases import make_pairs, make_rescue_pairs, write_fastq
+from tests.harness import bam_vs_sam, build_index, decode_bam_file, open_device, run_fem
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FEM = os.path.join(ROOT, "fem_amd", "csrc", "FEM")
-
-
-def _device(seqs, names):
-    from fem_amd import Device
-    ref = fo.Reference(seqs)
-    idx = fo.OracleIndex(ref)
-    dev = Device(0)
-    dev.upload_reference(seqs)
-    dev.upload_reference_names(names)
-    dev.upload_index(12, 3, idx.lookup, idx.occ[:idx.n_occ])
-    return dev, ref, idx
 
 
 def _stage(dev, reads, rnames, quals, e, slot, quals_on_host=False):
@@ -70,7 +53,7 @@ def test_single_end_equals_the_model(seed, e, L, n, repeats):
     reads = util.make_reads(rng, seqs, n, L, e, n_rate=0.003)
     rnames = ["read_%d_%s" % (i, "n" * (130 if i % 3 == 0 else i % 20)) for i in range(n)]  # names over 128 characters
     quals = ["".join(chr(33 + (11 * i + j) % 60) for j in range(len(r))) for i, r in enumerate(reads)]
-    dev, ref, idx = _device(seqs, names)
+    dev, ref, idx = open_device(seqs, names)
     try:
         res = fo.map_reads(ref, idx, fo.ReadBatch(reads), e=e, threads=8)
         want = mq.single_end(res, e)
@@ -82,7 +65,7 @@ def test_single_end_equals_the_model(seed, e, L, n, repeats):
         assert _sam(dev, reads, rnames, quals, e, 1, quals_on_host=True) == on
         # BAM at both levels: the model's encoding of the MAPQ text
         _stage(dev, reads, rnames, quals, e, 1)
-        _bam_vs_sam(dev, 1, [x.encode() for x in names], n_sam=True)
+        bam_vs_sam(dev, 1, [x.encode() for x in names], n_sam=True)
         # off again: the bytes of a slot that never had it
         assert _sam(dev, reads, rnames, quals, e, 1, mapq=False) == off
     finally:
@@ -107,7 +90,7 @@ def test_pairs_equal_the_model(seed, e, L, n, repeats):
     base = ["p%d_%s" % (i, "n" * (i % 140)) for i in range(n)]
     rnames = base + base
     quals = ["".join(chr(33 + (11 * i + j) % 60) for j in range(len(r))) for i, r in enumerate(reads)]
-    dev, ref, idx = _device(seqs, names)
+    dev, ref, idx = open_device(seqs, names)
     try:
         res = fo.map_reads(ref, idx, fo.ReadBatch(reads), e=e, threads=8)
         I, X = 0, 500
@@ -118,7 +101,7 @@ def test_pairs_equal_the_model(seed, e, L, n, repeats):
         _check(on, off, want)
         assert _sam(dev, reads, rnames, quals, e, 1, quals_on_host=True) == on
         _stage(dev, reads, rnames, quals, e, 1)
-        _bam_vs_sam(dev, 1, [x.encode() for x in names], n_sam=True)
+        bam_vs_sam(dev, 1, [x.encode() for x in names], n_sam=True)
         if repeats:  # pairs beyond kPairAlone combinations: pair_kernel's wave path
             counts = np.diff(res.rec_off.astype(np.int64))
             assert int((counts[:n] * counts[n:]).max()) > 32
@@ -135,7 +118,7 @@ def test_rescued_pairs_equal_the_model(seed, repeats):
     reads = r1 + r2
     rnames = ["q%d" % i for i in range(n)] * 2
     quals = ["".join(chr(35 + (7 * i + j) % 50) for j in range(len(r))) for i, r in enumerate(reads)]
-    dev, ref, idx = _device(seqs, names)
+    dev, ref, idx = open_device(seqs, names)
     try:
         res = fo.map_reads(ref, idx, fo.ReadBatch(reads), e=e, threads=8)
         withr, kept, _ = rm.rescue(res, n, reads, seqs, E, I, X)
@@ -146,7 +129,7 @@ def test_rescued_pairs_equal_the_model(seed, repeats):
         on = _sam(dev, reads, rnames, quals, e, 2, mapq=True)
         _check(on, off, mq.paired(res, n, e, I, X, res=withr, rescued=set(kept)))
         _stage(dev, reads, rnames, quals, e, 2)
-        _bam_vs_sam(dev, 2, [x.encode() for x in names], n_sam=True)
+        bam_vs_sam(dev, 2, [x.encode() for x in names], n_sam=True)
     finally:
         dev.close()
 
@@ -186,7 +169,7 @@ def test_thousands_of_records_per_mate():
     reads = r1 + r2
     rnames = ["q%d" % i for i in range(200)] * 2
     quals = ["I" * len(r) for r in reads]
-    dev, ref, idx = _device(seqs, names)
+    dev, ref, idx = open_device(seqs, names)
     try:
         res = fo.map_reads(ref, idx, fo.ReadBatch(reads), e=3, threads=8)
         assert np.diff(res.rec_off.astype(np.int64))[7] >= 1000
@@ -218,7 +201,7 @@ def test_by_construction():
     rng = np.random.default_rng(5)
     seqs = _built_reference(rng)
     s = seqs[0]
-    dev, ref, idx = _device(seqs, ["chrT"])
+    dev, ref, idx = open_device(seqs, ["chrT"])
     try:
         inside = [s[x:x + 100] for x in (20_100, 20_700, 21_300)]
         unique = [s[x:x + 100] for x in (5_000, 40_000, 80_000)] + [util.revcomp(s[90_000:90_100])]
@@ -246,7 +229,7 @@ def test_kernel_time_ids():
     reads = util.make_reads(rng, seqs, 300, 100, 3)
     rn = ["r%d" % i for i in range(300)]
     quals = ["I" * 100] * 300
-    dev, ref, idx = _device(seqs, ["c"])
+    dev, ref, idx = open_device(seqs, ["c"])
     try:
         dev.set_timing(True)
         for on, pairs in ((False, False), (True, False), (True, True)):
@@ -278,8 +261,7 @@ def _acgt_reference(rng):
 
 
 def _map(*args, env=None):
-    e = dict(os.environ, **(env or {}))
-    return subprocess.run([FEM, "map"] + list(args), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, env=e)
+    return run_fem("map", *args, env=env)
 
 
 def _body(data):
@@ -292,7 +274,7 @@ def test_cli(tmp_path):
     fa = tmp_path / "ref.fa"
     fa.write_bytes(b"".join(b">s%d\n%s\n" % (i, s) for i, s in enumerate(seqs)))
     idx_path = str(tmp_path / "ref.idx")
-    subprocess.run([FEM, "index", "12", "3", str(fa), idx_path], check=True, capture_output=True, timeout=600)
+    build_index(fa, idx_path)
     n = 2000
     se = util.make_reads(rng, seqs, n, 100, 3)
     r1, r2 = make_pairs(rng, seqs, n, 100, 3)
@@ -301,7 +283,7 @@ def test_cli(tmp_path):
     files = {}
     for key, reads, suffix in (("se", se, ""), ("r1", r1, "/1"), ("r2", r2, "/2"), ("x1", x1, "/1"), ("x2", x2, "/2")):
         files[key] = tmp_path / (key + ".fq")
-        _write_fastq(files[key], reads, ["r%d%s" % (i, suffix) for i in range(n)], q, False)
+        write_fastq(files[key], reads, ["r%d%s" % (i, suffix) for i in range(n)], q, False)
     common = ["-e", "3", "-t", "4", "--ref", str(fa), "--index", idx_path, "--batch", "700"]
     share = {"FEM_TESTING": "1", "FEM_TEST_SHARE_GPU": "1"}
     cases = [("se", ["--read1", str(files["se"])], False, True, None),
@@ -330,4 +312,4 @@ def test_cli(tmp_path):
     out = str(tmp_path / "on.bam")
     r = _map(*(common + ["--read1", str(files["r1"]), "--read2", str(files["r2"]), "-o", out, "--mapq", "--bam"]))
     assert r.returncode == 0, r.stderr.decode()
-    assert _decode_bam_file(out) == open(str(tmp_path / "pairs.on.sam"), "rb").read()
+    assert decode_bam_file(out) == open(str(tmp_path / "pairs.on.sam"), "rb").read()

@@ -9,9 +9,7 @@ Two cases of the issue's list cannot be built and are replaced by their nearest 
   * reads given without qualities: the C API has no such batch (fem_dev_commit_text_stage sends them, fem_dev_commit_names_stage
     keeps them on the host, which the option refuses); the tail's rule for it (no ms) is the model's test_no_qualities_no_ms."""
 import functools
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -21,17 +19,11 @@ from oracle import fem_oracle as fo
 from tests import bam_model as bm
 from tests import mate_tags_model as mt
 from tests import tags_model as tm
-from tests import test_gpu_line_options as lo
 from tests import util
-from tests.test_gpu_bam import _decode_bam_file
-from tests.test_gpu_pairs import _write_fastq, make_pairs
-from tests.test_gpu_rescue import _run
-from tests.test_gpu_unmapped import _map, _same
+from tests.cases import I, LINE_E, LINE_RESCUE_E, MAX_HITS, RG, STRATA, X, line_options_case, make_pairs, write_fastq
+from tests.harness import build_index, decode_bam_file, fetch_sam, open_device, pairing_on, run_fem, same_text
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FEM = os.path.join(ROOT, "fem_amd", "csrc", "FEM")
 
 
 def _rand_quals(rng, reads):
@@ -47,6 +39,10 @@ def _case(seqs, r1, r2, e, rng, names=None):
                 quals=_rand_quals(rng, reads), e=e, n=len(r1), idx=fo.OracleIndex(ref), ref=ref)
 
 
+def _device(c):
+    return open_device(c["seqs"], c["names"], c["idx"])[0]
+
+
 def _payload(dev, slot, level):
     data = dev.fetch_bam(slot=slot, level=level)
     return b"".join(m[0] for m in bm.parse_bgzf(data[0], eof=False)) if data[0] else b"", data[1]
@@ -55,13 +51,13 @@ def _payload(dev, slot, level):
 def _check(dev, c, slot=0, level=0):
     """The slot's text and BAM records with mate tags == the model on the same handle's text without them -> (off, on)."""
     dev.set_mate_tags(False, slot=slot)
-    off = _run(dev, c["reads"], c["rnames"], c["quals"], c["e"], slot)[0]
+    off = fetch_sam(dev, c["reads"], c["rnames"], c["quals"], c["e"], slot)[0]
     assert mt.strip(off) == (off, [(None, None, None)] * off.count(b"\n"))
     bam_off = _payload(dev, slot, level)[0]
     dev.set_mate_tags(True, slot=slot)
-    on = _run(dev, c["reads"], c["rnames"], c["quals"], c["e"], slot)[0]
+    on = fetch_sam(dev, c["reads"], c["rnames"], c["quals"], c["e"], slot)[0]
     want = mt.apply(off, c["n"], c["quals"])
-    _same(on, want)
+    same_text(on, want)
     assert mt.strip(on)[0] == off  # every byte in front of the tags is what it is without them
     names = [x.encode() for x in c["names"]]
     payload, raw_len = _payload(dev, slot, level)
@@ -85,18 +81,18 @@ def _tag(line, tag):
     return None
 
 
-# ---- the repeat-rich case of tests/test_gpu_line_options.py: every option together ----
+# ---- the repeat-rich case of tests/test_gpu_line_options.py (tests/cases.py): every option together ----
 
 @pytest.mark.parametrize("variant", ["plain", "filter+rg+nh", "no mapq"])
 def test_every_option_together(variant):
-    c = dict(lo.case(), e=lo.e)
-    dev = lo._device(c)
+    c = dict(line_options_case(), e=LINE_E)
+    dev = _device(c)
     try:
-        lo._pairing_on(dev)
+        pairing_on(dev, I, X, LINE_RESCUE_E)
         if variant == "filter+rg+nh":
-            unfiltered = lo._sam(dev, c)
-            dev.set_report(strata=lo.STRATA, max_hits=lo.MAX_HITS)
-            dev.set_tags(read_group=lo.RG, hits=True)
+            unfiltered = fetch_sam(dev, c["reads"], c["rnames"], c["quals"], LINE_E, 0)[0]
+            dev.set_report(strata=STRATA, max_hits=MAX_HITS)
+            dev.set_tags(read_group=RG, hits=True)
         if variant == "no mapq":
             dev.set_mapq(False)
         off, on = _check(dev, c, level=1)
@@ -168,7 +164,7 @@ def indel_case():
 
 def test_mate_cigars_short_path_boundary_and_loop():
     c = indel_case()
-    dev = lo._device(c)
+    dev = _device(c)
     try:
         dev.set_pairs(0, 500)
         dev.set_rescue(12)
@@ -190,7 +186,7 @@ def test_mates_on_different_sequences():
     r1 = [seqs[i % 3][500 + 90 * i:500 + 90 * i + L] for i in range(30)]
     r2 = [util.revcomp(seqs[(i + 1 + i % 2) % 3][700 + 80 * i:700 + 80 * i + L - i % 3]) for i in range(30)]
     c = _case(seqs, r1, r2, 2, rng, names=["first", "second_" + "n" * 70, "3"])
-    dev = lo._device(c)
+    dev = _device(c)
     try:
         dev.set_pairs(0, 500)
         dev.set_mapq(True)
@@ -206,7 +202,7 @@ def test_a_mate_whose_primary_line_prints_no_cigar():
     rng = np.random.default_rng(907)
     n = len(a["reads"]) // 2
     c = dict(a, n=n, rnames=["a%d" % (i % n) for i in range(2 * n)], quals=_rand_quals(rng, a["reads"]))
-    dev = lo._device(c)
+    dev = _device(c)
     try:
         dev.set_pairs(0, 100_000)
         for mapq in (False, True):
@@ -257,7 +253,7 @@ def lengths_case():
 def test_scores_of_every_length_and_pairs_across_waves():
     c = lengths_case()
     n = c["n"]
-    dev = lo._device(c)
+    dev = _device(c)
     try:
         dev.set_pairs(0, 500)
         off, on = _check(dev, c)
@@ -282,13 +278,13 @@ def test_scores_of_every_length_and_pairs_across_waves():
 
 def test_on_then_off_again_is_a_fresh_handle_and_the_kernel_times():
     c = lengths_case()
-    dev, fresh = lo._device(c), lo._device(c)
+    dev, fresh = _device(c), _device(c)
     try:
         for d in (dev, fresh):
             d.set_pairs(0, 500)
             d.set_unmapped(True)
             d.set_timing(True)
-        run = lambda d: (_run(d, c["reads"], c["rnames"], c["quals"], c["e"], 0)[0], d.fetch_bam(level=0)[0])  # noqa: E731
+        run = lambda d: (fetch_sam(d, c["reads"], c["rnames"], c["quals"], c["e"], 0)[0], d.fetch_bam(level=0)[0])  # noqa: E731
         counts = lambda d: [d.kernel_time(k)[1] for k in range(17)]  # noqa: E731
         dev.set_mate_tags(True)
         dev.reset_timing()
@@ -308,19 +304,19 @@ def test_on_then_off_again_is_a_fresh_handle_and_the_kernel_times():
         # the qualities kept on the host with the option on: refused, text and BAM; off again: served
         dev.set_mate_tags(True)
         with pytest.raises(FemError, match=r"^invalid argument: mate tags \(fem_dev_set_mate_tags\)"):
-            _run(dev, c["reads"], c["rnames"], c["quals"], c["e"], 0, quals_on_host=True)
+            fetch_sam(dev, c["reads"], c["rnames"], c["quals"], c["e"], 0, quals_on_host=True)
         with pytest.raises(FemError, match=r"^invalid argument: mate tags \(fem_dev_set_mate_tags\)"):
             dev.fetch_bam()
         dev.set_mate_tags(False)
-        assert _run(dev, c["reads"], c["rnames"], c["quals"], c["e"], 0, quals_on_host=True)[0] == off[0]
+        assert fetch_sam(dev, c["reads"], c["rnames"], c["quals"], c["e"], 0, quals_on_host=True)[0] == off[0]
         # a single-end slot is unchanged by the setting, wherever its qualities are
         dev.set_pairs(None)
         fresh.set_pairs(None)
-        single = _run(fresh, c["reads"], c["rnames"], c["quals"], c["e"], 0)[0]
+        single = fetch_sam(fresh, c["reads"], c["rnames"], c["quals"], c["e"], 0)[0]
         dev.set_mate_tags(True)
         dev.reset_timing()
-        assert _run(dev, c["reads"], c["rnames"], c["quals"], c["e"], 0)[0] == single
-        assert _run(dev, c["reads"], c["rnames"], c["quals"], c["e"], 0, quals_on_host=True)[0] == single
+        assert fetch_sam(dev, c["reads"], c["rnames"], c["quals"], c["e"], 0)[0] == single
+        assert fetch_sam(dev, c["reads"], c["rnames"], c["quals"], c["e"], 0, quals_on_host=True)[0] == single
         assert dev.kernel_time(17) == (0.0, 0)
     finally:
         dev.close()
@@ -341,7 +337,7 @@ def test_cli(tmp_path):
     fa = tmp_path / "ref.fa"
     fa.write_bytes(b"".join(b">s%d desc\n%s\n" % (i, s) for i, s in enumerate(seqs)))
     idx_path = str(tmp_path / "ref.idx")
-    subprocess.run([FEM, "index", "12", "3", str(fa), idx_path], check=True, capture_output=True, timeout=600)
+    build_index(fa, idx_path)
     n, e = 400, 2
     x1, x2 = make_pairs(rng, seqs, n, 100, e)
     for i in range(n):
@@ -354,16 +350,16 @@ def test_cli(tmp_path):
     q2 = ["".join(chr(33 + (5 * i + 11 * j + 1) % 94) for j in range(100)) for i in range(n)]
     rn = ["m%d" % i for i in range(n)]
     p1, p2 = tmp_path / "x1.fq", tmp_path / "x2.fq"
-    _write_fastq(p1, x1, rn, q1, False)
-    _write_fastq(p2, x2, rn, q2, False)
+    write_fastq(p1, x1, rn, q1, False)
+    write_fastq(p2, x2, rn, q2, False)
     out = str(tmp_path / "out")
     common = ["-e", str(e), "-t", "4", "--ref", str(fa), "--index", idx_path, "--read1", str(p1), "--read2", str(p2), "--unmapped", "--mapq",
               "--rescue", "8", "--nh", "-o", out]
 
     def body(*args, bam=False, env=None):
-        r = _map(*(common + list(args)), env=env)
+        r = run_fem("map", *(common + list(args)), env=env)
         assert r.returncode == 0, r.stderr.decode()
-        got = _decode_bam_file(out) if bam else open(out, "rb").read()
+        got = decode_bam_file(out) if bam else open(out, "rb").read()
         return _in_batch_order(b"".join(l + b"\n" for l in got.splitlines() if not l.startswith(b"@")))
 
     plain = body("--batch", "150")
@@ -372,14 +368,14 @@ def test_cli(tmp_path):
     shapes = [l for l in want.splitlines()]
     assert any(_flags(l) & 4 and _tag(l, b"MC") for l in shapes) and any(_flags(l) & 4 and not _tag(l, b"MQ") for l in shapes)
     assert any(_flags(l) & 0x100 and _tag(l, b"MC") for l in shapes)
-    _same(body("--batch", "150", "--mate-tags"), want)
-    _same(body("--batch", "64", "--mate-tags"), want)  # small batches: the same bytes
-    _same(body("--batch", "7", "--mate-tags", "--gpus", "1"), want)
-    _same(body("--batch", "150", "--mate-tags", "--bam", bam=True), want)
+    same_text(body("--batch", "150", "--mate-tags"), want)
+    same_text(body("--batch", "64", "--mate-tags"), want)  # small batches: the same bytes
+    same_text(body("--batch", "7", "--mate-tags", "--gpus", "1"), want)
+    same_text(body("--batch", "150", "--mate-tags", "--bam", bam=True), want)
     assert body("--batch", "150", "--bam", bam=True) == plain
     # with the read group's tag, the line filter, discordant rescue and a learned insert range, on two workers
     more = ["--batch", "150", "--rg", "@RG\\tID:lane.1", "--strata", "1", "--rescue-discordant", "--infer-insert=256"]
     plain2 = body(*more)
     assert plain2 != plain and b"\tRG:Z:lane.1\n" in plain2
     share = {"FEM_TESTING": "1", "FEM_TEST_SHARE_GPU": "1"}  # (--gpus 2: two workers on the one GPU)
-    _same(body(*(more + ["--mate-tags", "--gpus", "2"]), env=share), mt.apply(plain2, n, q1 + q2))
+    same_text(body(*(more + ["--mate-tags", "--gpus", "2"]), env=share), mt.apply(plain2, n, q1 + q2))

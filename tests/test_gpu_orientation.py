@@ -5,9 +5,7 @@ model of tests/orient_model.py on the oracle's single-end records of the same re
 Fixtures are made from FR fragments by the inverse of the model's reduction: FF is (mate 1, revcomp(mate 2)), RF is
 (revcomp(mate 1), revcomp(mate 2)); the FR builders swap the mates half the time.  Reads are upper-case A C G T N."""
 import functools
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -22,13 +20,11 @@ from tests import pair_model as pm
 from tests import report_model as rp
 from tests import tags_model as tm
 from tests import util
-from tests.test_gpu_pairs import _counters, _same_pairs, _write_fastq, make_pairs
-from tests.test_gpu_rescue import _run
+from tests.cases import make_pairs, write_fastq
+from tests.harness import build_index, counters, fetch_sam, open_device, run_fem, same_pairs
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FEM = os.path.join(ROOT, "fem_amd", "csrc", "FEM")
 K_PAIR_ALONE = 32  # fem_tail.hip: a pair with more combinations is its wave's
 I, X = 0, 500
 
@@ -39,12 +35,7 @@ def oriented(r1, r2, orient):
 
 
 def _device(c):
-    from fem_amd import Device
-    dev = Device(0)
-    dev.upload_reference(c["seqs"])
-    dev.upload_reference_names(c["names"])
-    dev.upload_index(12, 3, c["idx"].lookup, c["idx"].occ[:c["idx"].n_occ])
-    return dev
+    return open_device(c["seqs"], c["names"], c["idx"])[0]
 
 
 def _case(seqs, reads, e, n):
@@ -81,7 +72,7 @@ def pair_case(orient, repeats, L2=None):
 
 
 def _sam(dev, c, slot):
-    return _run(dev, c["reads"], c["rnames"], c["quals"], c["e"], slot)[0]
+    return fetch_sam(dev, c["reads"], c["rnames"], c["quals"], c["e"], slot)[0]
 
 
 @pytest.mark.parametrize("orient,repeats,L2", [(om.RF, False, None), (om.FF, False, None), (om.RF, False, 75), (om.FF, False, 75),
@@ -104,7 +95,7 @@ def test_paired_text_and_arrays_equal_the_model(orient, repeats, L2):
             exp = om.paired_text(want, n, c["names"], c["reads"], c["rnames"], c["quals"], I, X, orient, e=c["e"] if mapq else None)
             assert text == exp
             assert dev.pair_count(slot=1) == n_proper
-            _same_pairs(dev.fetch_pairs(slot=1), om.pair_arrays(want, n, I, X, orient))
+            same_pairs(dev.fetch_pairs(slot=1), om.pair_arrays(want, n, I, X, orient))
         dev.set_mapq(False, slot=1)
         text = _sam(dev, c, 1)
         assert [int(l.split(b"\t")[1]) for l in text.splitlines()] == [l[2] & 0x7FFF for l in lines]  # the rule, stated directly
@@ -182,7 +173,7 @@ def test_rescued_records_counts_and_text_equal_the_model(orient, discordant):
         assert dev.pair_count(slot=1) == n_proper and dev.rescue_count(slot=1) == len(kept)
         assert dev.rescue_discordant_count(slot=1) == n_kind2
         got = dev.fetch_pairs(slot=1)
-        _same_pairs(got, om.pair_arrays(want, n, I, X, orient, ext=ext))
+        same_pairs(got, om.pair_arrays(want, n, I, X, orient, ext=ext))
         # the rescued records themselves: the lines of the kept reads that are no single-end record of theirs
         by_line = {}
         for k in range(len(got.flag)):
@@ -323,18 +314,17 @@ def cli_case():
 
 
 def _map(tmp_path, out, *extra):
-    return subprocess.run([FEM, "map", "-e", "3", "-t", "4", "--ref", str(tmp_path / "ref.fa"), "--index", str(tmp_path / "ref.idx"),
-                           "--read1", str(tmp_path / "r1.fq"), "--read2", str(tmp_path / "r2.fq"), "-o", str(out)] + list(extra),
-                          capture_output=True, text=True, timeout=600)
+    return run_fem("map", "-e", "3", "-t", "4", "--ref", tmp_path / "ref.fa", "--index", tmp_path / "ref.idx",
+                   "--read1", tmp_path / "r1.fq", "--read2", tmp_path / "r2.fq", "-o", out, *extra, text=True)
 
 
 def test_cli_orientation_ff_and_auto(tmp_path):
     c = cli_case()
     n, want = c["n"], c["want"]
     (tmp_path / "ref.fa").write_bytes(b"".join(b">s%d desc\n%s\n" % (i, s) for i, s in enumerate(c["seqs"])))
-    subprocess.run([FEM, "index", "12", "3", str(tmp_path / "ref.fa"), str(tmp_path / "ref.idx")], check=True, capture_output=True, timeout=600)
-    _write_fastq(tmp_path / "r1.fq", c["reads"][:n], [b + "/1" for b in c["base"]], c["quals"][:n], False)
-    _write_fastq(tmp_path / "r2.fq", c["reads"][n:], [b + "/2" for b in c["base"]], c["quals"][n:], False)
+    build_index(tmp_path / "ref.fa", tmp_path / "ref.idx")
+    write_fastq(tmp_path / "r1.fq", c["reads"][:n], [b + "/1" for b in c["base"]], c["quals"][:n], False)
+    write_fastq(tmp_path / "r2.fq", c["reads"][n:], [b + "/2" for b in c["base"]], c["quals"][n:], False)
     header = "".join("@SQ\tSN:s%d\tLN:%d\n" % (i, len(s)) for i, s in enumerate(c["seqs"]))
 
     def model(lo, hi):
@@ -347,7 +337,7 @@ def test_cli_orientation_ff_and_auto(tmp_path):
     assert r.returncode == 0, r.stderr
     exp, n_proper = model(0, 500)
     assert out.read_text(encoding="latin-1") == exp and n_proper > n // 5
-    assert _counters(r.stderr)[-1] == "The number of proper pairs: %d" % n_proper
+    assert counters(r.stderr)[-1] == "The number of proper pairs: %d" % n_proper
     assert "Inferred" not in r.stderr
     # --orientation auto --infer-insert=256: the orientation line names FF, the range line follows it
     auto = tmp_path / "auto.sam"
@@ -366,7 +356,7 @@ def test_cli_orientation_ff_and_auto(tmp_path):
     assert (lo, hi) == (lib["by"][om.FF]["min_insert"], lib["by"][om.FF]["max_insert"])
     exp, n_proper = model(lo, hi)
     assert auto.read_text(encoding="latin-1") == exp
-    assert _counters(r.stderr)[-1] == "The number of proper pairs: %d" % n_proper
+    assert counters(r.stderr)[-1] == "The number of proper pairs: %d" % n_proper
     # ... and the output is that of --orientation ff -I LO -X HI, whatever the batch size
     whole = tmp_path / "auto_whole.sam"
     r = _map(tmp_path, whole, "--orientation", "auto", "--infer-insert=256")

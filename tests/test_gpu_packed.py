@@ -10,20 +10,16 @@ import pytest
 
 from oracle import fem_oracle as fo
 from tests import util
+from tests.harness import open_device
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def setup():
-    from fem_amd import Device
     rng = np.random.default_rng(4242)
     seqs = [util.rand_seq(rng, 300_000), util.rand_seq(rng, 50_000)]
-    ref = fo.Reference(seqs)
-    idx = fo.OracleIndex(ref)
-    dev = Device(0)
-    dev.upload_reference(seqs)
-    dev.upload_index(12, 3, idx.lookup, idx.occ[:idx.n_occ])
+    dev, ref, idx = open_device(seqs, None)
     yield rng, seqs, ref, idx, dev
     dev.close()
 

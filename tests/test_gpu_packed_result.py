@@ -2,26 +2,18 @@
 one offset per 256 strands, the candidates without padding — must say what fem_dev_fetch says, on every kernel path, for
 strands with 255 candidates and more (big[]), and once the slot packs and sends home behind its kernels (the second batch
 of a slot on).  Needs a GPU: -m gpu."""
-import os
-
 import numpy as np
 import pytest
 
 from oracle import fem_oracle as fo
 from tests import util
+from tests.harness import device_with_env
 
 pytestmark = pytest.mark.gpu
 
 
 def _device(env):
-    from fem_amd import Device
-    for k in env:
-        os.environ[k] = "1"
-    try:
-        return Device(0)
-    finally:
-        for k in env:
-            os.environ.pop(k)
+    return device_with_env(**dict.fromkeys(env, "1"))
 
 
 def _same(packed, plain, want=None):

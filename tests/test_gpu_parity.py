@@ -4,6 +4,7 @@ import pytest
 
 from oracle import fem_oracle as fo
 from tests import util
+from tests.harness import assert_same
 
 pytestmark = pytest.mark.gpu
 
@@ -50,15 +51,6 @@ def run_both(dev, seqs, reads, e, a=1, build_on_device=False):
         dev.upload_index(12, 3, idx.lookup, idx.occ[:idx.n_occ])
     got = dev.map_batch(batch.bases, batch.off, e=e, a=a)
     return want, got
-
-
-def assert_same(want, got):
-    off, cand, ed, end = got.per_strand()
-    assert np.array_equal(off, want.cand_off), "candidate counts per (read, strand)"
-    assert np.array_equal(cand, want.cands), "candidate locations"
-    assert np.array_equal(ed, want.v_ed), "edit distances / accept set"
-    assert np.array_equal(end[ed != 0xFF], want.v_end[want.v_ed != 0xFF]), "end offsets"
-    assert np.array_equal(got.stats, want.stats), (got.stats, want.stats)
 
 
 def test_config1_random_reference(dev):

@@ -11,18 +11,16 @@ the same files and, where oracle/_ref is built, against the live build).  Each f
 and through the command line (`FEM index` + `FEM map` on the fixture's files).  Everything is compared with the recorded
 values of the reference, not with the oracle.  Needs a GPU: -m gpu."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests.golden import make_ref_golden as mg
+from tests.harness import run_fem
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.dirname(os.path.abspath(mg.__file__))
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FEM = os.path.join(ROOT, "fem_amd", "csrc", "FEM")
 
 
 def open_device(dense):
@@ -41,7 +39,7 @@ def index_file_bytes(k, step, lookup, occ):
 
 
 class Recorded:
-    """A fixture's records under the names oracle.fem_oracle.MapResult gives them (what tests.test_host.expected_sam reads)."""
+    """A fixture's records under the names oracle.fem_oracle.MapResult gives them (what tests.cases.expected_sam reads)."""
 
     def __init__(self, z):
         for key in mg.RECORD_KEYS:
@@ -56,7 +54,7 @@ class Recorded:
 
 def recorded_sam_body(inp, want):
     """The alignment lines of the reference's SAM file, rebuilt from the recorded fields; checked against the file's digest."""
-    from tests.test_host import expected_sam
+    from tests.cases import expected_sam
     body = expected_sam(inp.names, inp.reads, inp.rnames, inp.quals, Recorded(want))
     header = "".join("@SQ\tSN:%s\tLN:%d\n" % (n, len(s)) for n, s in zip(inp.names, inp.seqs))
     assert np.array_equal(mg.sha((header + body).encode()), want["sam_sha256"])
@@ -168,11 +166,10 @@ def test_command_line_writes_the_references_files(tmp_path, name):
     header, body = recorded_sam_body(inp, want)
     fa, fq = inp.write(str(tmp_path))
     ix, sam = str(tmp_path / "ref.idx"), str(tmp_path / "out.sam")
-    r = subprocess.run([FEM, "index", str(mg.K), str(mg.STEP), fa, ix], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    r = run_fem("index", mg.K, mg.STEP, fa, ix)
     assert r.returncode == 0, r.stderr.decode()
     assert np.array_equal(mg.sha(open(ix, "rb").read()), want["index_sha256"])  # the SHA-256 of `FEM_ref index`'s file
-    r = subprocess.run([FEM, "map", "-e", str(case["e"]), "-a", str(case["a"]), "-t", "2", "--ref", fa, "--index", ix, "--read1", fq,
-                        "-o", sam], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    r = run_fem("map", "-e", case["e"], "-a", case["a"], "-t", "2", "--ref", fa, "--index", ix, "--read1", fq, "-o", sam)
     assert r.returncode == 0, r.stderr.decode()
     lines, theirs = open(sam).read().splitlines(), (header + body).splitlines()
     assert len(lines) == len(theirs)

@@ -1,92 +1,16 @@
 """Mate rescue on the device (fem_dev_set_rescue: the rescue kernels of fem_tail.hip in front of pair_kernel) against the
 plain-Python model of tests/rescue_model.py on the oracle's single-end records.  Needs a GPU: -m gpu."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-from fem_amd import device
 from oracle import fem_oracle as fo
 from tests import pair_model as pm
 from tests import rescue_model as rm
 from tests import util
-from tests.test_gpu_pairs import _counters, _same_pairs, _write_fastq
+from tests.cases import make_rescue_pairs, write_fastq
+from tests.harness import build_index, counters, fetch_sam, open_device, open_reference, run_fem, same_pairs
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FEM = os.path.join(ROOT, "fem_amd", "csrc", "FEM")
-
-
-def make_rescue_pairs(rng, seqs, n, L, L2, e, E, X, frac=0.4, near_end=False):
-    """n read pairs from fragments of max(L, L2)..X bp (mate 1 forward, mate 2 the reverse complement of the fragment's end,
-    mates swapped half the time).  0..e edits per mate; in `frac` of the pairs one mate carries e + 1 .. E edits instead
-    (substitutions and indels), which single-end mapping at e misses.  near_end: some fragments at a sequence's ends."""
-    lens = np.array([len(s) for s in seqs], np.int64)
-    ok = np.nonzero(lens > X + 200)[0]
-    r1, r2 = [], []
-
-    def fit(s, ln):
-        return s[:ln] if len(s) >= ln else s + util.rand_seq(rng, ln - len(s))
-
-    for i in range(n):
-        si = int(ok[rng.integers(0, len(ok))])
-        frag = int(rng.integers(max(L, L2) + 20, X + 1))
-        if near_end and i % 5 == 0:
-            st = int(rng.integers(0, 3)) if i % 10 == 0 else int(lens[si]) - frag - int(rng.integers(0, 3))
-        else:
-            st = int(rng.integers(0, lens[si] - frag))
-        f = seqs[si][st:st + frag]
-        a, b = f[:L], util.revcomp(f[frag - L2:])
-        heavy = rng.random() < frac
-        ka = int(rng.integers(0, e + 1))
-        kb = int(rng.integers(e + 1, E + 1)) if heavy and E > e else int(rng.integers(0, e + 1))
-        a, b = fit(util.mutate(rng, a, ka), L), fit(util.mutate(rng, b, kb), L2)
-        if rng.random() < 0.5:
-            a, b = b, a
-        r1.append(a)
-        r2.append(b)
-    return r1, r2
-
-
-def _setup(seed, repeats):
-    from fem_amd import Device
-    rng = np.random.default_rng(seed)
-    if repeats:
-        seqs = util.repeat_rich_reference(rng, n_seq=3, unit_len=300, n_units=4, copies=50, spacer=200)
-        seqs.append(util.rand_seq(rng, 120_000))
-    else:
-        seqs = [util.rand_seq(rng, 200_000), util.rand_seq(rng, 60_000)]
-    names = ["chr%d" % i for i in range(len(seqs))]
-    ref = fo.Reference(seqs)
-    idx = fo.OracleIndex(ref)
-    dev = Device(0)
-    dev.upload_reference(seqs)
-    dev.upload_reference_names(names)
-    dev.upload_index(12, 3, idx.lookup, idx.occ[:idx.n_occ])
-    return rng, dev, ref, idx, seqs, names
-
-
-def _run(dev, reads, rnames, quals, e, slot, quals_on_host=False, packed=False):
-    batch = fo.ReadBatch(reads)
-    q = np.frombuffer("".join(quals).encode("latin-1"), np.uint8)
-    if packed:  # the 2-bit form through the staging (fem_dev_commit_stage_packed)
-        n, L = len(reads), len(reads[0])
-        hb, _ = dev.acquire_stage(n, n * L, slot=slot)
-        n_exc = device.pack_reads(batch.bases, n, L, hb)
-        dev.commit_stage_packed(n, L, n_exc, slot=slot)
-    else:
-        dev.stage_reads(batch.bases, batch.off, slot=slot)
-    if packed:
-        assert dev.stage_info(slot)[1]
-    elif len(set(len(r) for r in reads)) > 1:
-        assert not dev.stage_info(slot)[1]  # (mates of unequal lengths: as characters)
-    dev.stage_text(q, rnames, slot=slot, quals_on_host=quals_on_host)
-    dev.map_staged(e=e, slot=slot)
-    if quals_on_host:
-        return dev.fetch_sam(slot=slot, quals=q, offsets=batch.off)
-    return dev.fetch_sam(slot=slot)
 
 
 def _has_indel(rec):
@@ -107,7 +31,7 @@ CASES = [
 
 @pytest.mark.parametrize("seed,e,E,L,L2,n,repeats,X,qhost,near_end,packed", CASES)
 def test_rescued_text_equals_the_model(seed, e, E, L, L2, n, repeats, X, qhost, near_end, packed):
-    rng, dev, ref, idx, seqs, names = _setup(seed, repeats)
+    rng, dev, ref, idx, seqs, names = open_reference(seed, repeats)
     try:
         r1, r2 = make_rescue_pairs(rng, seqs, n, L, L2, e, E, X, near_end=near_end)
         reads = r1 + r2
@@ -127,23 +51,23 @@ def test_rescued_text_equals_the_model(seed, e, E, L, L2, n, repeats, X, qhost, 
         dev.set_rescue(E, slot=1)
         dev.set_timing(True)
         dev.reset_timing()
-        text, n_records, _, stats = _run(dev, reads, rnames, quals, e, 1, qhost, packed)
+        text, n_records, _, stats = fetch_sam(dev, reads, rnames, quals, e, 1, qhost, packed)
         assert np.array_equal(stats, want.stats) and n_records == int(want.rec_off[-1])  # single-end meaning kept
         exp = pm.sam_lines(ext, n, names, reads, rnames, quals, I, X)
         assert text.decode("latin-1") == exp
         _, n_proper = pm.expected(ext, n, I, X)
         assert dev.pair_count(slot=1) == n_proper and dev.rescue_count(slot=1) == len(kept)
         assert dev.kernel_time(10)[1] >= 1
-        _same_pairs(dev.fetch_pairs(slot=1), pm.pair_arrays(ext, n, I, X))
+        same_pairs(dev.fetch_pairs(slot=1), pm.pair_arrays(ext, n, I, X))
         assert dev.rescue_count(slot=1) == len(kept)
         rec = dev.fetch_records(slot=1)  # single-end records untouched
         assert rec.n_records == int(want.rec_off[-1])
         if seed == 21:
             # rescue off again: byte-identical to a slot that never had it
             dev.set_rescue(None, slot=1)
-            text_off, _, _, _ = _run(dev, reads, rnames, quals, e, 1, qhost, packed)
+            text_off, _, _, _ = fetch_sam(dev, reads, rnames, quals, e, 1, qhost, packed)
             dev.set_pairs(I, X, slot=0)
-            text_0, _, _, _ = _run(dev, reads, rnames, quals, e, 0, qhost, packed)
+            text_0, _, _, _ = fetch_sam(dev, reads, rnames, quals, e, 0, qhost, packed)
             assert text_off == text_0 and text_off.decode("latin-1") == pm.sam_lines(want, n, names, reads, rnames, quals, I, X)
             assert dev.rescue_count(slot=1) == 0
             # rescue on, no candidate pair (both mates mapped everywhere): unchanged text
@@ -153,8 +77,8 @@ def test_rescued_text_equals_the_model(seed, e, E, L, L2, n, repeats, X, qhost, 
             sq = [quals[i] for i in both] + [quals[n + i] for i in both]
             sn = ["p%d" % i for i in both] * 2
             dev.set_rescue(E, slot=1)
-            t_on, _, _, _ = _run(dev, sub, sn, sq, e, 1)
-            t_off, _, _, _ = _run(dev, sub, sn, sq, e, 0)
+            t_on, _, _, _ = fetch_sam(dev, sub, sn, sq, e, 1)
+            t_off, _, _, _ = fetch_sam(dev, sub, sn, sq, e, 0)
             assert t_on == t_off and dev.rescue_count(slot=1) == 0
     finally:
         dev.close()
@@ -164,18 +88,12 @@ def test_rescued_text_equals_the_model(seed, e, E, L, L2, n, repeats, X, qhost, 
 def test_soft_masked_reference_and_lower_case_reads(seed, E, L):
     """Lower-case characters on either side: the search compares codes, the traceback and MD characters, so a rescued mate's
     MD can hold every column — more than the first traceback pass stages; the overflow pass takes those records."""
-    from fem_amd import Device
     rng = np.random.default_rng(seed)
     s0 = util.rand_seq(rng, 200_000)
     seqs = [s0[:20_000] + s0[20_000:140_000].lower() + s0[140_000:], util.rand_seq(rng, 60_000)]
     names = ["chr0", "chr1"]
-    ref = fo.Reference(seqs)
-    idx = fo.OracleIndex(ref)
-    dev = Device(0)
+    dev, ref, idx = open_device(seqs, names)
     try:
-        dev.upload_reference(seqs)
-        dev.upload_reference_names(names)
-        dev.upload_index(12, 3, idx.lookup, idx.occ[:idx.n_occ])
         e, n, X = 2, 400, 600
         r1, r2 = make_rescue_pairs(rng, seqs, n, L, L, e, E, X)
         reads = [r.lower() if i % 3 == 0 else r.upper() for i, r in enumerate(r1 + r2)]
@@ -187,18 +105,18 @@ def test_soft_masked_reference_and_lower_case_reads(seed, E, L):
         assert len(long_md) >= 2 and len(kept) > len(long_md)  # both traceback passes
         dev.set_pairs(0, X)
         dev.set_rescue(E)
-        text, _, _, _ = _run(dev, reads, rnames, quals, e, 0)
+        text, _, _, _ = fetch_sam(dev, reads, rnames, quals, e, 0)
         assert text.decode("latin-1") == pm.sam_lines(ext, n, names, reads, rnames, quals, 0, X)
         _, n_proper = pm.expected(ext, n, 0, X)
         assert dev.pair_count() == n_proper and dev.rescue_count() == len(kept)
-        _same_pairs(dev.fetch_pairs(), pm.pair_arrays(ext, n, 0, X))
+        same_pairs(dev.fetch_pairs(), pm.pair_arrays(ext, n, 0, X))
     finally:
         dev.close()
 
 
 def test_refusals():
     from fem_amd import FemError
-    rng, dev, ref, idx, seqs, names = _setup(28, False)
+    rng, dev, ref, idx, seqs, names = open_reference(28, False)
     try:
         for bad in (-1, 16):
             with pytest.raises(FemError):
@@ -210,9 +128,9 @@ def test_refusals():
         dev.set_pairs(100, 100 + 65537)
         dev.set_rescue(8)
         with pytest.raises(FemError):
-            _run(dev, reads, rnames, quals, 2, 0, packed=True)
+            fetch_sam(dev, reads, rnames, quals, 2, 0, packed=True)
         dev.set_pairs(100, 100 + 65536)  # the widest window rescue searches
-        text, _, _, _ = _run(dev, reads, rnames, quals, 2, 0, packed=True)
+        text, _, _, _ = fetch_sam(dev, reads, rnames, quals, 2, 0, packed=True)
         want = fo.map_reads(ref, idx, fo.ReadBatch(reads), e=2)
         ext, kept, _ = rm.rescue(want, 20, reads, seqs, 8, 100, 100 + 65536)
         assert text.decode("latin-1") == pm.sam_lines(ext, 20, names, reads, rnames, quals, 100, 100 + 65536)
@@ -223,8 +141,8 @@ def test_refusals():
 # ---- FEM map --rescue ----
 
 def _map(fa, idx_path, p1, p2, out, *extra):
-    return subprocess.run([FEM, "map", "-e", "2", "-t", "4", "--ref", str(fa), "--index", str(idx_path), "--read1", str(p1),
-                           "--read2", str(p2), "-o", str(out)] + list(extra), capture_output=True, text=True, timeout=900)
+    return run_fem("map", "-e", "2", "-t", "4", "--ref", fa, "--index", idx_path, "--read1", p1, "--read2", p2, "-o", out, *extra,
+                   text=True)
 
 
 @pytest.mark.parametrize("gz", [False, True])
@@ -234,7 +152,7 @@ def test_cli_rescue_equals_the_model(tmp_path, gz):
     fa = tmp_path / "ref.fa"
     fa.write_bytes(b"".join(b">s%d desc\n%s\n" % (i, s) for i, s in enumerate(seqs)))
     idx_path = tmp_path / "ref.idx"
-    subprocess.run([FEM, "index", "12", "3", str(fa), str(idx_path)], check=True, capture_output=True, timeout=600)
+    build_index(fa, idx_path)
     n = 2000
     r1, r2 = make_rescue_pairs(rng, seqs, n, 100, 100, 2, 8, 500, frac=0.1)
     base = ["pair%d" % i for i in range(n)]
@@ -242,8 +160,8 @@ def test_cli_rescue_equals_the_model(tmp_path, gz):
     q2 = ["".join(chr(34 + (5 * i + j) % 40) for j in range(len(r))) for i, r in enumerate(r2)]
     ext_ = ".fq.gz" if gz else ".fq"
     p1, p2 = tmp_path / ("r1" + ext_), tmp_path / ("r2" + ext_)
-    _write_fastq(p1, r1, [b + "/1" for b in base], q1, gz)
-    _write_fastq(p2, r2, [b + "/2" for b in base], q2, gz)
+    write_fastq(p1, r1, [b + "/1" for b in base], q1, gz)
+    write_fastq(p2, r2, [b + "/2" for b in base], q2, gz)
     ref = fo.Reference(seqs)
     want = fo.map_reads(ref, fo.OracleIndex(ref), fo.ReadBatch(r1 + r2), e=2, threads=4)
     ext, kept, _ = rm.rescue(want, n, r1 + r2, seqs, 8, 0, 500)
@@ -254,7 +172,7 @@ def test_cli_rescue_equals_the_model(tmp_path, gz):
     assert r.returncode == 0, r.stderr
     assert out.read_text(encoding="latin-1") == header + pm.sam_lines(ext, n, ["s0", "s1"], r1 + r2, base + base, q1 + q2, 0, 500)
     _, n_proper = pm.expected(ext, n, 0, 500)
-    assert _counters(r.stderr)[-2:] == ["The number of proper pairs: %d" % n_proper, "The number of rescued mates: %d" % len(kept)]
+    assert counters(r.stderr)[-2:] == ["The number of proper pairs: %d" % n_proper, "The number of rescued mates: %d" % len(kept)]
     # without the flag: the output of a paired run, no rescue line
     out0 = tmp_path / "out0.sam"
     r = _map(fa, idx_path, p1, p2, out0, "--batch", "700")
@@ -267,7 +185,7 @@ def test_fetch_timing_counts():
     """With timing on, every fetch advances the launch counts of exactly its kernel-time ids (include/fem_hip.h), by one
     each: fetch_records 3-5; fetch_sam 3-5 and 7 when it waits; fetch_bam 3-5, 11 and 12; a text of read pairs also 9, and
     10 with mate rescue."""
-    rng, dev, ref, idx, seqs, names = _setup(28, False)
+    rng, dev, ref, idx, seqs, names = open_reference(28, False)
     try:
         n, e = 150, 2
         r1, r2 = make_rescue_pairs(rng, seqs, n, 100, 100, e, 8, 500)
@@ -303,7 +221,7 @@ def test_fetch_timing_counts_with_every_stage():
     """A paired slot with rescue, MAPQ and lines for unmapped reads, over all sixteen ids: with the line filter a waiting
     fetch_sam counts 3-5, 7, 9, 10, 13 and 15 (the filter's line index is the unmapped reads' too: no 14); without the
     filter a fetch_bam that does not wait counts 3-5, 9-14."""
-    rng, dev, ref, idx, seqs, names = _setup(28, False)
+    rng, dev, ref, idx, seqs, names = open_reference(28, False)
     try:
         n, e = 150, 2
         r1, r2 = make_rescue_pairs(rng, seqs, n, 100, 100, e, 8, 500)

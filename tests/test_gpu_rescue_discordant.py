@@ -6,8 +6,6 @@ Every case first asserts on the model's result that its fixture does its job (te
 cases cannot reach the general figures (20 kept, 5 per mate): the 1000 bp case has 40 pairs in all and states its own, and
 at E = e single-end mapping has already written nearly every hit the windows hold, so that case asks nothing of its fixture."""
 import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -21,13 +19,11 @@ from tests import report_model as rp
 from tests import rescue_model as rm
 from tests import tags_model as tm
 from tests import util
-from tests.test_gpu_pairs import _counters, _same_pairs, _write_fastq
-from tests.test_gpu_rescue import _run
+from tests.cases import write_fastq
+from tests.harness import build_index, counters, fetch_sam, open_device, run_fem, same_pairs
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FEM = os.path.join(ROOT, "fem_amd", "csrc", "FEM")
 K_PAIR_ALONE = 32  # fem_tail.hip: pairs with more combinations are their wave's
 I = 0
 
@@ -58,12 +54,7 @@ def case(seed, e, E, L, L2, n, X, repeats=False, near_end=False, lower=False, n_
 
 
 def _device(c):
-    from fem_amd import Device
-    dev = Device(0)
-    dev.upload_reference(c["seqs"])
-    dev.upload_reference_names(c["names"])
-    dev.upload_index(12, 3, c["idx"].lookup, c["idx"].occ[:c["idx"].n_occ])
-    return dev
+    return open_device(c["seqs"], c["names"], c["idx"])[0]
 
 
 def _on(dev, c, slot, discordant=True):
@@ -79,13 +70,13 @@ def _n_kind2(c):
 def _check(dev, c, slot, qhost=False, packed=False):
     """The slot's text, counts and arrays equal the model's."""
     n, X = c["n"], c["X"]
-    text, n_records, _, stats = _run(dev, c["reads"], c["rnames"], c["quals"], c["e"], slot, qhost, packed)
+    text, n_records, _, stats = fetch_sam(dev, c["reads"], c["rnames"], c["quals"], c["e"], slot, qhost, packed)
     assert np.array_equal(stats, c["want"].stats) and n_records == int(c["want"].rec_off[-1])  # single-end meaning kept
     assert text.decode("latin-1") == pm.sam_lines(c["ext"], n, c["names"], c["reads"], c["rnames"], c["quals"], I, X)
     _, n_proper = pm.expected(c["ext"], n, I, X)
     assert dev.pair_count(slot=slot) == n_proper and dev.rescue_count(slot=slot) == len(c["kept"])
     assert dev.rescue_discordant_count(slot=slot) == _n_kind2(c)
-    _same_pairs(dev.fetch_pairs(slot=slot), pm.pair_arrays(c["ext"], n, I, X))
+    same_pairs(dev.fetch_pairs(slot=slot), pm.pair_arrays(c["ext"], n, I, X))
     assert dev.rescue_count(slot=slot) == len(c["kept"]) and dev.rescue_discordant_count(slot=slot) == _n_kind2(c)
     return text
 
@@ -115,13 +106,13 @@ def test_switch_off_again_is_rescue_alone():
     dev = _device(c)
     try:
         _on(dev, c, 1)
-        on = _run(dev, c["reads"], c["rnames"], c["quals"], c["e"], 1, packed=True)[0]
+        on = fetch_sam(dev, c["reads"], c["rnames"], c["quals"], c["e"], 1, packed=True)[0]
         dev.set_rescue_discordant(False, slot=1)
-        off = _run(dev, c["reads"], c["rnames"], c["quals"], c["e"], 1, packed=True)[0]
+        off = fetch_sam(dev, c["reads"], c["rnames"], c["quals"], c["e"], 1, packed=True)[0]
         assert dev.rescue_discordant_count(slot=1) == 0
         dev.set_pairs(I, X, slot=0)
         dev.set_rescue(c["E"], slot=0)  # a slot that only ever had set_rescue
-        plain = _run(dev, c["reads"], c["rnames"], c["quals"], c["e"], 0, packed=True)[0]
+        plain = fetch_sam(dev, c["reads"], c["rnames"], c["quals"], c["e"], 0, packed=True)[0]
         ext1, kept1, _ = rm.rescue(c["want"], n, c["reads"], c["seqs"], c["E"], I, X)
         assert off == plain and on != off
         assert off.decode("latin-1") == pm.sam_lines(ext1, n, c["names"], c["reads"], c["rnames"], c["quals"], I, X)
@@ -129,7 +120,7 @@ def test_switch_off_again_is_rescue_alone():
         # the switch without rescue: a paired text, nothing rescued
         dev.set_rescue(None, slot=1)
         dev.set_rescue_discordant(True, slot=1)
-        bare = _run(dev, c["reads"], c["rnames"], c["quals"], c["e"], 1, packed=True)[0]
+        bare = fetch_sam(dev, c["reads"], c["rnames"], c["quals"], c["e"], 1, packed=True)[0]
         assert bare.decode("latin-1") == pm.sam_lines(c["want"], n, c["names"], c["reads"], c["rnames"], c["quals"], I, X)
         assert dev.rescue_count(slot=1) == 0 and dev.rescue_discordant_count(slot=1) == 0
     finally:
@@ -150,8 +141,8 @@ def test_switch_on_a_batch_without_discordant_pairs():
     try:
         _on(dev, c, 1)
         _on(dev, c, 0, discordant=False)
-        t_on = _run(dev, sub, sn, sq, c["e"], 1)[0]
-        t_off = _run(dev, sub, sn, sq, c["e"], 0)[0]
+        t_on = fetch_sam(dev, sub, sn, sq, c["e"], 1)[0]
+        t_off = fetch_sam(dev, sub, sn, sq, c["e"], 0)[0]
         assert t_on == t_off and dev.rescue_count(slot=1) == dev.rescue_count(slot=0) > 0
         assert dev.rescue_discordant_count(slot=1) == 0
     finally:
@@ -209,7 +200,7 @@ def test_with_mapq_unmapped_filter_and_tags():
         dev.set_unmapped(True)
         dev.set_report(strata=1, max_hits=3)
         dev.set_tags(read_group=b"grp1", hits=True)
-        text = _run(dev, c["reads"], c["rnames"], c["quals"], e, 0, packed=True)[0]
+        text = fetch_sam(dev, c["reads"], c["rnames"], c["quals"], e, 0, packed=True)[0]
         assert text.splitlines() == want.splitlines()
         assert dev.filtered_count() == dropped and dev.rescue_discordant_count() == _n_kind2(c)
         # a rescued mate with own records: its first line is the rescued record with MAPQ <= 40, its own lines follow with 0
@@ -226,14 +217,14 @@ def test_with_mapq_unmapped_filter_and_tags():
         dev.set_report()
         whole = tm.apply(rp.paired(c["want"], n, c["names"], c["reads"], c["rnames"], c["quals"], I, X, res=c["ext"],
                                    rescued=set(c["kept"]), e=e)[0], b"grp1", True)
-        assert _run(dev, c["reads"], c["rnames"], c["quals"], e, 0, packed=True)[0].splitlines() == whole.splitlines()
+        assert fetch_sam(dev, c["reads"], c["rnames"], c["quals"], e, 0, packed=True)[0].splitlines() == whole.splitlines()
         assert len(whole.splitlines()) == len(want.splitlines()) + dropped
         # one line per mate: of a rescued mate with own records the rescued record stays, the own ones go
         dev.set_report(strata=0, max_hits=1)
         one, gone = rp.paired(c["want"], n, c["names"], c["reads"], c["rnames"], c["quals"], I, X, res=c["ext"], rescued=set(c["kept"]),
                               e=e, strata=0, max_hits=1)
         assert gone >= _n_kind2(c)
-        assert _run(dev, c["reads"], c["rnames"], c["quals"], e, 0, packed=True)[0].splitlines() == tm.apply(one, b"grp1", True).splitlines()
+        assert fetch_sam(dev, c["reads"], c["rnames"], c["quals"], e, 0, packed=True)[0].splitlines() == tm.apply(one, b"grp1", True).splitlines()
         assert dev.filtered_count() == gone
     finally:
         dev.close()
@@ -242,8 +233,8 @@ def test_with_mapq_unmapped_filter_and_tags():
 # ---- FEM map --rescue-discordant ----
 
 def _map(fa, idx_path, p1, p2, out, *extra):
-    return subprocess.run([FEM, "map", "-e", "2", "-t", "4", "--ref", str(fa), "--index", str(idx_path), "--read1", str(p1),
-                           "--read2", str(p2), "-o", str(out)] + list(extra), capture_output=True, text=True, timeout=900)
+    return run_fem("map", "-e", "2", "-t", "4", "--ref", fa, "--index", idx_path, "--read1", p1, "--read2", p2, "-o", out, *extra,
+                   text=True)
 
 
 @pytest.mark.parametrize("gz", [False, True])
@@ -253,20 +244,20 @@ def test_cli_equals_the_model(tmp_path, gz):
     fa = tmp_path / "ref.fa"
     fa.write_bytes(b"".join(b">%s desc\n%s\n" % (nm.encode(), s) for nm, s in zip(c["names"], seqs)))
     idx_path = tmp_path / "ref.idx"
-    subprocess.run([FEM, "index", "12", "3", str(fa), str(idx_path)], check=True, capture_output=True, timeout=600)
+    build_index(fa, idx_path)
     r1, r2, q1, q2 = c["reads"][:n], c["reads"][n:], c["quals"][:n], c["quals"][n:]
     base = c["rnames"][:n]
     ext_ = ".fq.gz" if gz else ".fq"
     p1, p2 = tmp_path / ("r1" + ext_), tmp_path / ("r2" + ext_)
-    _write_fastq(p1, r1, [b + "/1" for b in base], q1, gz)
-    _write_fastq(p2, r2, [b + "/2" for b in base], q2, gz)
+    write_fastq(p1, r1, [b + "/1" for b in base], q1, gz)
+    write_fastq(p2, r2, [b + "/2" for b in base], q2, gz)
     header = "".join("@SQ\tSN:%s\tLN:%d\n" % (nm, len(s)) for nm, s in zip(c["names"], seqs))
     out = tmp_path / "out.sam"
     r = _map(fa, idx_path, p1, p2, out, "--batch", "700", "--rescue", "8", "--rescue-discordant")
     assert r.returncode == 0, r.stderr
     assert out.read_text(encoding="latin-1") == header + pm.sam_lines(c["ext"], n, c["names"], c["reads"], c["rnames"], c["quals"], I, 500)
     _, n_proper = pm.expected(c["ext"], n, I, 500)
-    assert _counters(r.stderr)[-3:] == ["The number of proper pairs: %d" % n_proper, "The number of rescued mates: %d" % len(c["kept"]),
+    assert counters(r.stderr)[-3:] == ["The number of proper pairs: %d" % n_proper, "The number of rescued mates: %d" % len(c["kept"]),
                                         "The number of rescued discordant pairs: %d" % _n_kind2(c)]
     # without the flag: --rescue 8 alone, no such line
     ext1, kept1, _ = rm.rescue(c["want"], n, c["reads"], seqs, 8, I, 500)
@@ -274,4 +265,4 @@ def test_cli_equals_the_model(tmp_path, gz):
     r = _map(fa, idx_path, p1, p2, out1, "--batch", "700", "--rescue", "8")
     assert r.returncode == 0, r.stderr
     assert out1.read_text(encoding="latin-1") == header + pm.sam_lines(ext1, n, c["names"], c["reads"], c["rnames"], c["quals"], I, 500)
-    assert "discordant" not in r.stderr and _counters(r.stderr)[-1] == "The number of rescued mates: %d" % len(kept1)
+    assert "discordant" not in r.stderr and counters(r.stderr)[-1] == "The number of rescued mates: %d" % len(kept1)

@@ -6,43 +6,17 @@ import pytest
 
 from fem_amd import host
 from oracle import fem_oracle as fo
-from tests import util
-from tests.test_host import expected_sam
+from tests.cases import expected_sam
+from tests.harness import open_sam_case
 
 pytestmark = pytest.mark.gpu
-
-
-def _case(seed, e, L, n_reads, repeats, odd):
-    from fem_amd import Device
-    rng = np.random.default_rng(seed)
-    if repeats:
-        seqs = util.repeat_rich_reference(rng, n_seq=3, unit_len=300, n_units=4, copies=50, spacer=200)
-        seqs.append(util.rand_seq(rng, 120_000))
-    else:
-        seqs = [util.rand_seq(rng, 200_000), util.rand_seq(rng, 50_000)]
-    long_fields = L > 200  # names, reference names and MD strings beyond one and two bytes per lane of sam_write_kernel
-    names = ["chr%d_%s" % (i, "x" * (i * (70 if long_fields else 7))) for i in range(len(seqs))]
-    reads = util.make_reads(rng, seqs, n_reads, L, e, n_rate=0.003)
-    if odd:
-        reads[3] = reads[3].lower()
-        reads[5] = reads[5][:L // 2] + b"RYKM=.-*"[:min(8, L - L // 2)] + reads[5][L // 2 + 8:]
-        reads[7] = reads[7][:L - 17]  # a different length
-    rnames = ["read_%d/%s" % (i, "n" * (i % (150 if long_fields else 40))) for i in range(len(reads))]
-    quals = ["".join(chr(33 + (11 * i + j) % 60) for j in range(len(r))) for i, r in enumerate(reads)]
-    ref = fo.Reference(seqs)
-    idx = fo.OracleIndex(ref)
-    dev = Device(0)
-    dev.upload_reference(seqs)
-    dev.upload_reference_names(names)
-    dev.upload_index(12, 3, idx.lookup, idx.occ[:idx.n_occ])
-    return dev, ref, idx, seqs, names, reads, rnames, quals
 
 
 @pytest.mark.parametrize("seed,e,L,n,repeats,odd", [(1, 3, 100, 1500, False, True), (2, 7, 150, 800, True, True),
                                                      (3, 2, 64, 3000, True, False), (4, 0, 36, 500, False, False),
                                                      (5, 7, 260, 700, False, True)])
 def test_device_sam_text_equals_host_text_and_oracle_text(seed, e, L, n, repeats, odd):
-    dev, ref, idx, seqs, names, reads, rnames, quals = _case(seed, e, L, n, repeats, odd)
+    dev, ref, idx, seqs, names, reads, rnames, quals = open_sam_case(seed, e, L, n, repeats, odd)
     try:
         batch = fo.ReadBatch(reads)
         want = fo.map_reads(ref, idx, batch, e=e)
@@ -78,7 +52,7 @@ def test_device_sam_text_equals_host_text_and_oracle_text(seed, e, L, n, repeats
 
 def test_fetch_sam_needs_its_inputs():
     from fem_amd import FemError
-    dev, ref, idx, seqs, names, reads, rnames, quals = _case(9, 3, 100, 50, False, False)
+    dev, ref, idx, seqs, names, reads, rnames, quals = open_sam_case(9, 3, 100, 50, False, False)
     try:
         batch = fo.ReadBatch(reads)
         dev.stage_reads(batch.bases, batch.off)

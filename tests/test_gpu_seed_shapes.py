@@ -4,7 +4,7 @@ its DP forms and both of its list paths, its shape gate, the fast kernels over a
 mapping's, packed staging and the tail at another k, and `FEM index K S` / `FEM map` over such files — each against the
 oracle, array for array or byte for byte.  k = 16, which has no defined meaning, is refused.
 
-The reference, the reads and the edits are those of tests/test_gpu_verify_packed.py.  Needs a GPU: -m gpu."""
+The reference, the reads and the edits are those of tests/test_gpu_verify_packed.py (tests/cases.py).  Needs a GPU: -m gpu."""
 import os
 
 import numpy as np
@@ -12,10 +12,8 @@ import pytest
 
 from oracle import fem_oracle as fo
 from tests import util
-from tests.test_cli import run, write_case
-from tests.test_gpu_tail import assert_same_records
-from tests.test_gpu_verify_packed import _reads, _reference, _run_packed
-from tests.test_host import expected_sam
+from tests.cases import expected_sam, packed_reads, packed_reference, write_case
+from tests.harness import assert_same_records, device_with_env, run_fem, run_packed
 
 pytestmark = pytest.mark.gpu
 
@@ -66,7 +64,7 @@ def _dpp_form(L, k, step, e, a):
 class _World:
     def __init__(self):
         rng = np.random.default_rng(20260117)
-        self.seqs, self.places = _reference(rng)
+        self.seqs, self.places = packed_reference(rng)
         self.ref = fo.Reference(self.seqs)
         self.idx = {}
         self.devs = {}
@@ -85,14 +83,8 @@ class _World:
         """A handle with the reference and its (k, step) index: built on the device or the oracle's, uploaded."""
         key = (k, step, force_hash)
         if key not in self.devs:
-            from fem_amd import Device
             assert os.environ.get("FEM_FORCE_HASH", "0") == "0"
-            if force_hash:
-                os.environ["FEM_FORCE_HASH"] = "1"
-            try:
-                d = Device(0)
-            finally:
-                os.environ.pop("FEM_FORCE_HASH", None)
+            d = device_with_env(**({"FEM_FORCE_HASH": "1"} if force_hash else {}))
             d.upload_reference(self.seqs)
             if built:
                 d.build_index(k, step, fetch=False)
@@ -113,7 +105,7 @@ class _World:
         """(reads, the oracle's seeding and verification) of CASES[i], made once."""
         if i not in self.cases:
             k, step, L, e, a = CASES[i]
-            reads = _reads(np.random.default_rng(8000 + i), self.seqs, self.places, N_READS, L, e)
+            reads = packed_reads(np.random.default_rng(8000 + i), self.seqs, self.places, N_READS, L, e)
             self.cases[i] = (reads, _oracle(self, reads, k, step, e, a))
         return self.cases[i]
 
@@ -253,7 +245,7 @@ def test_the_shape_gate_at_13_5_closes_at_150_bases_and_opens_at_151(world):
     dev = world.dev(k, step, built=True)
     assert dev.seed_kernel(e, a, k, step) == "seed_filter_kernel"
     for L in (150, 151):
-        reads = _reads(np.random.default_rng(7100 + L), world.seqs, world.places, N_READS, L, e)
+        reads = packed_reads(np.random.default_rng(7100 + L), world.seqs, world.places, N_READS, L, e)
         want = _oracle(world, reads, k, step, e, a)
         got = _map(dev, reads, k, step, e, a)
         _assert_equal(got, want)
@@ -271,7 +263,7 @@ def test_a_batch_of_reads_on_both_sides_of_the_gate(world):
     lengths = [k - 1, k, gate - 1, gate, 100, 257]  # (the layout is sized from the longest)
     reads = []
     for L in lengths:
-        reads += _reads(rng, world.seqs, world.places, 67, L, e)
+        reads += packed_reads(rng, world.seqs, world.places, 67, L, e)
     reads = [reads[int(j)] for j in rng.permutation(len(reads))]
     want = _oracle(world, reads, k, step, e, a)
     dev = world.dev(k, step)
@@ -288,7 +280,7 @@ def test_a_batch_of_reads_on_both_sides_of_the_gate(world):
 @pytest.mark.parametrize("s,force_hash", [(1, False), (2, False), (4, False), (6, False), (17, False), (1, True)])
 def test_mapping_at_12_3_over_an_index_of_another_step(world, s, force_hash):
     L, e = 100, 3
-    reads = _reads(np.random.default_rng(7300), world.seqs, world.places, N_READS, L, e)
+    reads = packed_reads(np.random.default_rng(7300), world.seqs, world.places, N_READS, L, e)
     want = _oracle(world, reads, 12, 3, e, 1, index_step=s)
     base = _oracle(world, reads, 12, 3, e, 1)
     assert int(want.stats[3]) != int(base.stats[3]) and int(want.stats[4]) != int(base.stats[4]), "the step shows"
@@ -301,7 +293,7 @@ def test_mapping_at_12_3_over_an_index_of_another_step(world, s, force_hash):
 def test_map_staged_refuses_a_step_of_17_and_another_k(world):
     from fem_amd import FemError
     dev = world.dev(12, 17)
-    reads = _reads(np.random.default_rng(7300), world.seqs, world.places, 8, 100, 3)
+    reads = packed_reads(np.random.default_rng(7300), world.seqs, world.places, 8, 100, 3)
     batch = fo.ReadBatch(reads)
     dev.stage_reads(batch.bases, batch.off)
     with pytest.raises(FemError, match="out of range"):
@@ -316,7 +308,7 @@ def test_packed_staging_and_records_at_another_k(world, i):
     k, step, L, e, a = CASES[i]
     reads, want = world.case(i)
     dev = world.dev(k, step, built=i % 2 == 1)
-    off, cand, ed, end, stats = _run_packed(dev, reads, L, e, k, step)
+    off, cand, ed, end, stats = run_packed(dev, reads, L, e, k, step)
     _assert_equal((off, cand, ed, end, stats), want)
     rec = dev.fetch_records()
     full = _oracle(world, reads, k, step, e, a, stages=fo.STAGE_SEED | fo.STAGE_VERIFY | fo.STAGE_ALIGN)
@@ -332,13 +324,13 @@ def test_cli_index_files_of_other_shapes_and_map_over_them(tmp_path, k, step, ba
     ref = fo.Reference(seqs)
     idx = fo.OracleIndex(ref, k, step)
     index_path, oracle_index, sam_path = str(tmp_path / "ref.idx"), str(tmp_path / "o.idx"), str(tmp_path / "out.sam")
-    r = run("index", str(k), str(step), fa, index_path)
+    r = run_fem("index", str(k), str(step), fa, index_path)
     assert r.returncode == 0, r.stderr.decode()
     idx.save(oracle_index)
     assert open(index_path, "rb").read() == open(oracle_index, "rb").read()
     if k == 11:
         return
-    r = run("map", "-e", str(e), "-t", "3", "--ref", fa, "--index", index_path, "--read1", fq, "-o", sam_path,
+    r = run_fem("map", "-e", str(e), "-t", "3", "--ref", fa, "--index", index_path, "--read1", fq, "-o", sam_path,
             *(["--batch", batch] if batch else []))
     if k != 12:
         assert r.returncode != 0 and b"Index was built with k=8" in r.stderr
@@ -368,7 +360,7 @@ def test_the_device_refuses_a_seed_length_of_16_and_of_0(world):
         with pytest.raises(FemError, match=r"k must be 1\.\.15 and step >= 1"):
             dev.build_index(k, 3, fetch=False)
     dev = world.dev(12, 4)
-    batch = fo.ReadBatch(_reads(np.random.default_rng(1), world.seqs, world.places, 4, 100, 3))
+    batch = fo.ReadBatch(packed_reads(np.random.default_rng(1), world.seqs, world.places, 4, 100, 3))
     dev.stage_reads(batch.bases, batch.off)
     with pytest.raises(FemError, match=r"out of range \(k 1\.\.15"):
         dev.map_staged(e=3, a=1, k=16, step=4)

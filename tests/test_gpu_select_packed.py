@@ -16,7 +16,8 @@ import pytest
 
 from oracle import fem_oracle as fo
 from tests import util
-from tests.packed_batches import exceptions as _exceptions, reads as _reads, reference as _reference
+from tests.cases import packed_exceptions, packed_reads, packed_reference
+from tests.harness import device_with_env
 
 pytestmark = pytest.mark.gpu
 
@@ -32,7 +33,7 @@ N_READS = 600
 class _World:
     def __init__(self):
         rng = np.random.default_rng(20261019)
-        self.seqs, self.places = _reference(rng)
+        self.seqs, self.places = packed_reference(rng)
         x = util.rand_seq(rng, HALF)
         self.pal_at = len(self.seqs[3]) + 500
         self.seqs[3] = self.seqs[3] + util.rand_seq(rng, 500) + x + util.revcomp(x) + util.rand_seq(rng, 500)
@@ -45,28 +46,20 @@ class _World:
         """A handle with the index; chars: under FEM_SELECT_CHARS=1; dense: FEM_FORCE_DENSE=1; banked: two banks of two."""
         key = (chars, dense, banked)
         if key not in self.devs:
-            from fem_amd import Device
             switches = {"FEM_SELECT_CHARS": chars, "FEM_FORCE_DENSE": dense, "FEM_TEST_BANK_SEQS": banked}
             for name in switches:
                 assert os.environ.get(name, "0") == "0", name
-            for name, on in switches.items():
-                if on:
-                    os.environ[name] = "2" if name == "FEM_TEST_BANK_SEQS" else "1"
-            try:
-                d = Device(0)
-            finally:
-                for name in switches:
-                    os.environ.pop(name, None)
+            d = device_with_env(**{name: "2" if name == "FEM_TEST_BANK_SEQS" else "1" for name, on in switches.items() if on})
             d.upload_reference(self.seqs)
             d.upload_index(K, STEP, self.idx.lookup, self.idx.occ[:self.idx.n_occ])
             self.devs[key] = d
         return self.devs[key]
 
     def reads(self, rng, n, L, e):
-        """Read 0 from inside the palindrome (accepted on both strands, whatever n), the rest from tests.packed_batches."""
+        """Read 0 from inside the palindrome (accepted on both strands, whatever n), the rest from tests.cases.packed_reads."""
         at = self.pal_at + HALF - L // 2 if L <= 2 * HALF else self.pal_at
         first = self.seqs[3][at:at + L]
-        return [first] + (_reads(rng, self.seqs, self.places, n - 1, L, e) if n > 1 else [])
+        return [first] + (packed_reads(rng, self.seqs, self.places, n - 1, L, e) if n > 1 else [])
 
     def close(self):
         for d in self.devs.values():
@@ -142,10 +135,10 @@ def _check(world, reads, L, e, want=None, banked=False):
 def _some_exceptions(rng, reads, share=0.03):
     """About 3 % of the reads with N, n, a lower-case base or R at the first, a middle and the last base; a small batch gets
     one such read at least."""
-    odd, kind = _exceptions(rng, reads, share)
+    odd, kind = packed_exceptions(rng, reads, share)
     if not np.any(kind) and len(reads) > 1:
         i = int(rng.integers(1, len(reads)))
-        odd[i:i + 1] = _exceptions(rng, reads[i:i + 1], 1.0)[0]
+        odd[i:i + 1] = packed_exceptions(rng, reads[i:i + 1], 1.0)[0]
     return odd
 
 
@@ -187,7 +180,7 @@ def test_batch_sizes_around_sub_blocks_and_blocks(world, L, n):
 def test_a_batch_in_which_every_read_is_marked(world):
     L, e = 103, 3
     rng = np.random.default_rng(5)
-    odd, kind = _exceptions(rng, world.reads(rng, 500, L, e), 1.0)
+    odd, kind = packed_exceptions(rng, world.reads(rng, 500, L, e), 1.0)
     assert np.all(kind > 0) and np.any(kind == 1) and np.any(kind == 2)
     _check(world, odd, L, e)
 

@@ -8,20 +8,16 @@ import pytest
 
 from oracle import fem_oracle as fo
 from tests import util
+from tests.harness import open_device
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def setup():
-    from fem_amd import Device
     rng = np.random.default_rng(90)
     seqs = [util.rand_seq(rng, 250_000), util.rand_seq(rng, 40_000)]
-    ref = fo.Reference(seqs)
-    idx = fo.OracleIndex(ref)
-    dev = Device(0)
-    dev.upload_reference(seqs)
-    dev.upload_index(12, 3, idx.lookup, idx.occ[:idx.n_occ])
+    dev, ref, idx = open_device(seqs, None)
     yield rng, seqs, ref, idx, dev
     dev.close()
 
@@ -197,11 +193,8 @@ def test_two_handles_from_two_threads(setup):
     # handles are independent (include/fem_hip.h): two of them on one GPU, each driven by its own host thread through the
     # copying entry point (own staging threads, own streams), give what one gives
     import threading
-    from fem_amd import Device
     rng, seqs, ref, idx, dev = setup
-    other = Device(0)
-    other.upload_reference(seqs)
-    other.upload_index(12, 3, idx.lookup, idx.occ[:idx.n_occ])
+    other = open_device(seqs, None, idx)[0]
     batches = [fo.ReadBatch(util.make_reads(rng, seqs, 20_000, 100, 3)) for _ in range(2)]
     wants = [fo.map_reads(ref, idx, b, e=3, stages=fo.STAGE_SEED | fo.STAGE_VERIFY) for b in batches]
     errors = []

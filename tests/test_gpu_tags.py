@@ -1,11 +1,10 @@
 """RG:Z, NH:i and HI:i on the device (fem_dev_set_tags: the tag parts of the text and BAM record kernels, fem_tail.hip) and the
 header of FEM map --header / --rg against the plain-Python rule of tests/tags_model.py, applied to what the other models expect
-of the same batch without tags.  Needs a GPU: -m gpu.  (hits_case is also run without one, by tests/test_tags_model.py.)"""
+of the same batch without tags.  Needs a GPU: -m gpu."""
 import ctypes
 import functools
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,15 +15,13 @@ from tests import report_model as rp
 from tests import tags_model as tm
 from tests import unmapped_model as um
 from tests import util
-from tests.test_gpu_bam import _decode_bam_file
-from tests.test_gpu_pairs import _write_fastq, make_pairs
-from tests.test_gpu_report import I, X, PAIR_CASES, SINGLE_CASES, _reference, _set, _want, pair_case, single_case
-from tests.test_gpu_unmapped import _device, _map, _quals, _sam, _same, _stage
+from tests.cases import I, X, hits_case, make_pairs, quals, report_want, write_fastq
+from tests.cases import REPORT_PAIR_CASES as PAIR_CASES, REPORT_SINGLE_CASES as SINGLE_CASES
+from tests.cases import report_pair_case as pair_case, report_single_case as single_case
+from tests.harness import FEM, ROOT, build_index, decode_bam_file, fetch_sam, open_device, run_fem, same_text, set_line_filter
+from tests.harness import stage_and_map
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FEM = os.path.join(ROOT, "fem_amd", "csrc", "FEM")
 
 # ID lengths: one byte, a wave's width and the bytes around it, the longest
 IDS = {k: bytes(33 + (7 * i + k) % 94 for i in range(k)) for k in (1, 63, 64, 65, 255)}
@@ -32,6 +29,18 @@ IDS[6] = b"lane 1"
 
 
 # ---- the device's text and BAM against the model ----
+
+def _device(c):
+    return open_device(c["seqs"], c["names"], c["idx"])[0]
+
+
+def _stage(dev, c, slot, quals_on_host=False):
+    return stage_and_map(dev, c["reads"], c["rnames"], c["quals"], c["e"], slot, quals_on_host)
+
+
+def _sam(dev, c, slot, quals_on_host=False):
+    return fetch_sam(dev, c["reads"], c["rnames"], c["quals"], c["e"], slot, quals_on_host)
+
 
 def _bam(dev, slot, ref_names, text):
     """fetch_bam of the slot's staged batch at both levels: the model's records of `text`, which decode to it."""
@@ -49,10 +58,10 @@ def _check(dev, c, slot, model, rg, hits, quals_on_host=False):
     dev.set_tags(slot=slot, read_group=rg, hits=hits)
     want = tm.apply(model, rg, hits)
     got = _sam(dev, c, slot)[0]
-    _same(got, want)
+    same_text(got, want)
     _bam(dev, slot, [x.encode() for x in c["names"]], want)
     if quals_on_host:  # qual_at still finds every QUAL field: the tags stand behind it
-        _same(_sam(dev, c, slot, quals_on_host=True)[0], want)
+        same_text(_sam(dev, c, slot, quals_on_host=True)[0], want)
     return got
 
 
@@ -75,7 +84,7 @@ def unique_case(n, lost=False):
     res = fo.map_reads(ref, idx, fo.ReadBatch(reads), e=3, threads=4)
     counts = np.diff(res.rec_off.astype(np.int64))
     assert all(int(k) == (0 if lost and i % 3 == 1 else 1) for i, k in enumerate(counts)), counts
-    return dict(seqs=[UNIQUE_SEQ], names=["uniq"], reads=reads, rnames=rnames, quals=_quals(reads), e=3, idx=idx, res=res)
+    return dict(seqs=[UNIQUE_SEQ], names=["uniq"], reads=reads, rnames=rnames, quals=quals(reads), e=3, idx=idx, res=res)
 
 
 @pytest.fixture(scope="module")
@@ -90,7 +99,7 @@ def test_wave_boundaries(unique_dev, n, k):
     dev = unique_dev
     for lost in (False, True):
         c = unique_case(n, lost)
-        _set(dev, 0, False, lost, None, None)
+        set_line_filter(dev, 0, False, lost, None, None)
         model = um.single_end(c["res"], c["names"], c["reads"], c["rnames"], c["quals"])
         if not lost:
             model = um.without_unmapped(model)[0]
@@ -103,30 +112,13 @@ def test_wave_boundaries(unique_dev, n, k):
 @pytest.mark.parametrize("k", sorted(IDS))
 def test_id_lengths(unique_dev, k):
     dev, c = unique_dev, unique_case(65)
-    _set(dev, 0, False, False, None, None)
+    set_line_filter(dev, 0, False, False, None, None)
     model = um.without_unmapped(um.single_end(c["res"], c["names"], c["reads"], c["rnames"], c["quals"]))[0]
     for hits in (False, True):
         _check(dev, c, 0, model, IDS[k], hits)
 
 
 # ---- hit counts: slots of 130 lines among slots of 1 and 2 ----
-
-@functools.lru_cache(maxsize=None)
-def hits_case():
-    rng = np.random.default_rng(310)
-    L = 100
-    seqs, names, units, _, _ = _reference(rng, L, copies=(130, 2))
-    seqs, names = seqs[2:4], names[2:4]  # the random sequence and the one with the units
-    (u130, _), (u2, _) = units
-    reads = [u130[o:o + L] for o in rng.integers(0, 61, 5)] + [u2[o:o + L] for o in rng.integers(0, 61, 4)]
-    reads += util.make_reads(rng, seqs[:1], 7, L, 0)
-    reads = [reads[i] for i in rng.permutation(len(reads))]
-    ref = fo.Reference(seqs)
-    idx = fo.OracleIndex(ref)
-    res = fo.map_reads(ref, idx, fo.ReadBatch(reads), e=3, threads=4)
-    return dict(seqs=seqs, names=names, reads=reads, rnames=["h%d" % i for i in range(len(reads))], quals=_quals(reads), e=3, idx=idx,
-                res=res)
-
 
 @pytest.mark.parametrize("strata,max_hits", [(None, None), (0, None), (None, 1), (None, 33), (None, 100)])
 def test_hit_counts(strata, max_hits):
@@ -136,7 +128,7 @@ def test_hit_counts(strata, max_hits):
     kept = 130 if max_hits is None else min(130, max_hits)  # NH is what is in the text, not what was found
     dev = _device(c)
     try:
-        _set(dev, 0, False, False, strata, max_hits)
+        set_line_filter(dev, 0, False, False, strata, max_hits)
         got = _check(dev, c, 0, model, IDS[6], True)
         for hi in sorted({1, 9, 10, 32, 33, 64, 65, 99, 100, 130, kept}):
             assert got.count(b"\tNH:i:%d\tHI:i:%d\t" % (kept, hi)) == ((16 if kept == 1 else 5) if hi <= kept else 0), hi
@@ -147,7 +139,7 @@ def test_hit_counts(strata, max_hits):
         dev.close()
 
 
-# ---- every line shape: the cases of tests/test_gpu_report.py, a sampled matrix of the switches ----
+# ---- every line shape: the --strata / --max-hits cases of tests/cases.py, a sampled matrix of the switches ----
 
 # case, paired, mapq, unmapped, ID length (None: no RG), NH / HI, (S, N) of the line filter
 MATRIX = [
@@ -187,7 +179,7 @@ def _shapes(text, paired):
 def test_every_line_shape(row):
     case, paired, mapq, unmapped, k, hits, flt = MATRIX[row]
     c = pair_case(*case) if paired else single_case(*case)
-    model = rp.apply(_want(case, paired, mapq, unmapped), *flt)[0]
+    model = rp.apply(report_want(case, paired, mapq, unmapped), *flt)[0]
     shapes = _shapes(model, paired)
     assert {"primary", "secondary"} <= shapes
     if unmapped:
@@ -198,7 +190,7 @@ def test_every_line_shape(row):
             dev.set_pairs(I, X, slot=1)
             if c["E"] is not None:
                 dev.set_rescue(c["E"], slot=1)
-        _set(dev, 1, mapq, unmapped, *flt)
+        set_line_filter(dev, 1, mapq, unmapped, *flt)
         got = _check(dev, c, 1, model, None if k is None else IDS[k], hits, quals_on_host=hits and k is not None)
         if paired and c["E"] is not None and hits:  # a rescued mate's record is its slot's only line
             assert dev.rescue_count(slot=1) == len(c["kept"]) >= 20
@@ -227,7 +219,7 @@ def test_asserted_records(paired):
             assert sum(1 for l in plain.split(b"\n")[:-1] if l.split(b"\t")[5] == b"*" and not int(l.split(b"\t")[1]) & 4) == n_asserted
             for flt in ((None, None), (0, None), (None, 2)):
                 model = rp.apply(plain, *flt)[0]
-                _set(dev, 1, False, unmapped, *flt)
+                set_line_filter(dev, 1, False, unmapped, *flt)
                 got = _check(dev, c, 1, model, IDS[6], True, quals_on_host=True)
                 _check(dev, c, 1, model, None, True)
                 # the 0x8000 lines: MD:Z: empty, then NH and HI; a slot's count includes them, and they have a place of their own
@@ -250,7 +242,7 @@ def test_nothing_maps_and_an_empty_batch():
     c = dict(seqs=[util.rand_seq(rng, 5000)], names=["tiny"], e=3)
     c["reads"] = [util.rand_seq(rng, int(rng.integers(30, 160))) for _ in range(200)]
     c["rnames"] = ["x%d" % i for i in range(200)]
-    c["quals"] = _quals(c["reads"])
+    c["quals"] = quals(c["reads"])
     ref = fo.Reference(c["seqs"])
     c["idx"] = fo.OracleIndex(ref)
     res = fo.map_reads(ref, c["idx"], fo.ReadBatch(c["reads"]), e=3, threads=4)
@@ -336,7 +328,7 @@ def test_cli(tmp_path):
     fa = tmp_path / "ref.fa"
     fa.write_bytes(b"".join(b">s%d desc\n%s\n" % (i, s) for i, s in enumerate(seqs)))
     idx_path = str(tmp_path / "ref.idx")
-    subprocess.run([FEM, "index", "12", "3", str(fa), idx_path], check=True, capture_output=True, timeout=600)
+    build_index(fa, idx_path)
     sq = "".join("@SQ\tSN:%s\tLN:%d\n" % (nm, len(s)) for nm, s in zip(names, seqs)).encode()
     n, e = 400, 3
     se = util.make_reads(rng, seqs, n, 100, e)
@@ -354,7 +346,7 @@ def test_cli(tmp_path):
     files = {}
     for key, reads, suffix in (("se", se, ""), ("x1", x1, "/1"), ("x2", x2, "/2")):
         files[key] = tmp_path / (key + ".fq")
-        _write_fastq(files[key], reads, [x + suffix for x in rn], q, False)
+        write_fastq(files[key], reads, [x + suffix for x in rn], q, False)
     ref = fo.Reference(seqs)
     idx = fo.OracleIndex(ref)
     res = fo.map_reads(ref, idx, fo.ReadBatch(se), e=e, threads=8)
@@ -374,9 +366,9 @@ def test_cli(tmp_path):
     ]
     for args, bam, rg_arg, hits, plain, hd in runs:
         args = common + args + ["-o", out]
-        r = _map(*args, env={"FEM_TESTING": "1", "FEM_TEST_SHARE_GPU": "1"})  # (--gpus 2: two workers on the one GPU)
+        r = run_fem("map", *args, env={"FEM_TESTING": "1", "FEM_TEST_SHARE_GPU": "1"})  # (--gpus 2: two workers on the one GPU)
         assert r.returncode == 0, r.stderr.decode()
-        got = _decode_bam_file(out) if bam else open(out, "rb").read()
+        got = decode_bam_file(out) if bam else open(out, "rb").read()
         header, body = _split_header(got)
         rg = None if rg_arg is None else re.search(r"ID:([^\t]+)", tm.rg_line(rg_arg).decode()).group(1).encode()
         if hd:

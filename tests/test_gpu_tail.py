@@ -4,6 +4,7 @@ import pytest
 
 from oracle import fem_oracle as fo
 from tests import util
+from tests.harness import assert_same_records
 
 pytestmark = pytest.mark.gpu
 
@@ -32,19 +33,6 @@ def run_both(dev, seqs, reads, e, a=1):
     dev.map_staged(e=e, a=a)
     got = dev.fetch_records()
     return want, got
-
-
-def assert_same_records(want, got):
-    assert np.array_equal(got.rec_begin, want.rec_off), "records per read"
-    assert np.array_equal(got.flag, want.r_flag), "FLAG"
-    assert np.array_equal(got.tid, want.r_tid), "reference id"
-    assert np.array_equal(got.pos0, want.r_pos), "POS"
-    assert np.array_equal(got.nm, want.r_nm), "NM"
-    assert np.array_equal(got.cigar_off, want.cig_off), "CIGAR lengths"
-    assert np.array_equal(got.cigar, want.cig), "CIGAR"
-    assert np.array_equal(got.md_off, want.md_off), "MD lengths"
-    assert np.array_equal(got.md, want.md), "MD"
-    assert np.array_equal(got.stats, want.stats)
 
 
 @pytest.mark.parametrize("e,L,repeat", [(3, 100, True), (7, 150, True), (2, 80, False), (1, 64, True), (5, 125, True),

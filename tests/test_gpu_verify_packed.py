@@ -15,12 +15,10 @@ import numpy as np
 import pytest
 
 from oracle import fem_oracle as fo
-from tests import util
+from tests.cases import UNIT, UNIT_COPIES, packed_exceptions, packed_reads, packed_reference
+from tests.harness import device_with_env, run_packed
 
 pytestmark = pytest.mark.gpu
-
-UNIT, UNIT_COPIES = 300, 12
-LONG_UNIT = 1500
 
 # (L, e): every length with one e of {0, 1, 3, 7}; a = 1 throughout
 CASES = [(12, 0), (15, 1), (16, 0), (17, 0), (31, 1), (32, 3), (33, 0), (63, 7), (64, 3), (65, 1), (66, 7), (67, 3),
@@ -41,101 +39,10 @@ def _index_of(L, e):
     raise AssertionError("no index for L = %d, e = %d" % (L, e))
 
 
-def _clustered(rng, s, cluster, period):
-    """A near-copy: `cluster` consecutive substitutions every `period` bases — a read over it is beyond e edits where a
-    cluster of e + 2 falls inside it, and still shares whole seeds with the original between the clusters."""
-    s = bytearray(s)
-    for at in range(int(rng.integers(3, period)), len(s) - cluster, period):
-        for i in range(at, at + cluster):
-            s[i] = util.ACGT[(np.searchsorted(util.ACGT, s[i]) + 1 + rng.integers(0, 3)) % 4]
-    return bytes(s)
-
-
-def _reference(rng):
-    """Four sequences of 20-60 kbp: a 300-base unit in 12 copies, three near-copies of it, a 1500-base unit twice with three
-    near-copies (decoys for reads longer than the short unit), a 60-base repeat five times."""
-    unit, long_unit, short = util.rand_seq(rng, UNIT), util.rand_seq(rng, LONG_UNIT), util.rand_seq(rng, 60)
-    near = [(2, 14), (5, 30), (9, 45)]  # clusters of e + 2 for e = 0, 3, 7 (e = 1: two clusters of the first)
-    pieces = [unit] * UNIT_COPIES + [_clustered(rng, unit, c, p) for c, p in near]
-    pieces += [long_unit] * 2 + [_clustered(rng, long_unit, c, p) for c, p in near] + [short] * 5
-    order = rng.permutation(len(pieces))
-    seqs, places = [], []  # places: (sequence, offset, length) of the exact copies of the two units
-    lens = [20_000, 35_000, 45_000, 60_000]
-    per_seq = [[] for _ in lens]
-    for j, pi in enumerate(order):
-        per_seq[j % len(lens)].append(int(pi))
-    for si, total in enumerate(lens):
-        parts, used = [], 0
-        gap = (total - sum(len(pieces[pi]) for pi in per_seq[si])) // (len(per_seq[si]) + 1)
-        for pi in per_seq[si]:
-            parts.append(util.rand_seq(rng, gap))
-            used += gap
-            if pi < UNIT_COPIES or len(pieces) - 5 - 3 - 2 <= pi < len(pieces) - 5 - 3:
-                places.append((si, used, len(pieces[pi])))
-            parts.append(pieces[pi])
-            used += len(pieces[pi])
-        parts.append(util.rand_seq(rng, total - used))
-        seqs.append(b"".join(parts))
-    return seqs, places
-
-
-def _edit(rng, s, n_err, L):
-    """n_err edits (substitutions, insertions, deletions) anywhere — the first and last three bases included."""
-    s = bytearray(s)
-    for _ in range(n_err):
-        u = rng.random()
-        pos = int(rng.integers(0, 3)) if u < 0.2 else L - 1 - int(rng.integers(0, 3)) if u < 0.4 else int(rng.integers(0, L))
-        r = rng.random()
-        if r < 0.6:
-            s[pos] = util.ACGT[(np.searchsorted(util.ACGT, s[pos]) + 1 + rng.integers(0, 3)) % 4]
-        elif r < 0.8:
-            s.insert(pos, int(util.ACGT[rng.integers(0, 4)]))
-        else:
-            del s[pos]
-    return bytes(s[:L])
-
-
-def _reads(rng, seqs, places, n, L, e):
-    """Half of the reads from inside the planted units (many candidates, decoys among them), half from anywhere; both
-    strands; 0..e edits.  Reads 0 and n - 1 are exact and on the reverse strand: they load at the packed buffer's edges."""
-    fit = [p for p in places if p[2] >= L + e]
-    out = []
-    for i in range(n):
-        if fit and rng.random() < 0.5:
-            si, at, ln = fit[int(rng.integers(0, len(fit)))]
-            start = at + int(rng.integers(0, ln - (L + e) + 1))
-        else:
-            si = int(rng.integers(0, len(seqs)))
-            start = int(rng.integers(0, len(seqs[si]) - (L + e) - 1))
-        w = seqs[si][start:start + L + e]
-        edge = i == 0 or i == n - 1
-        r = w[:L] if edge else _edit(rng, w, int(rng.integers(0, e + 1)), L)
-        out.append(util.revcomp(r) if edge or rng.random() < 0.5 else r)
-    return out
-
-
-def _exceptions(rng, reads, share):
-    """A share of the reads carries one to three of N, n, a lower-case base and R, at the first, a middle and the last base.
-    Returns the reads and, per read, 0 (untouched), 1 (lower-case bases only: same outcome as in upper case) or 2."""
-    out, kind = [], np.zeros(len(reads), np.int8)
-    for i, r in enumerate(reads):
-        if rng.random() < share:
-            r = bytearray(r)
-            L = len(r)
-            lower_only = rng.random() < 0.4
-            places = [0, L // 2, L - 1]
-            for at in [places[int(j)] for j in rng.permutation(3)[:int(rng.integers(1, 4))]]:
-                r[at] = r[at] | 0x20 if lower_only else int(rng.choice([ord("N"), ord("n"), r[at] | 0x20, ord("R")]))
-            kind[i] = 1 if lower_only else 2
-            r = bytes(r)
-        out.append(r)
-    return out, kind
-
-
 class _World:
     def __init__(self):
         rng = np.random.default_rng(20260117)
-        self.seqs, self.places = _reference(rng)
+        self.seqs, self.places = packed_reference(rng)
         self.ref = fo.Reference(self.seqs)
         self.idx = {}
         self.devs = {}
@@ -149,18 +56,10 @@ class _World:
         """A handle with the (k, step) index of the reference; chars: under FEM_VERIFY_CHARS=1; dense: FEM_FORCE_DENSE=1."""
         key = (k, step, chars, dense)
         if key not in self.devs:
-            from fem_amd import Device
             switches = {"FEM_VERIFY_CHARS": chars, "FEM_FORCE_DENSE": dense}
             for name in switches:
                 assert os.environ.get(name, "0") == "0", name
-            for name, on in switches.items():
-                if on:
-                    os.environ[name] = "1"
-            try:
-                d = Device(0)
-            finally:
-                for name in switches:
-                    os.environ.pop(name, None)
+            d = device_with_env(**{name: "1" for name, on in switches.items() if on})
             idx = self.index(k, step)
             d.upload_reference(self.seqs)
             d.upload_index(k, step, idx.lookup, idx.occ[:idx.n_occ])
@@ -200,28 +99,14 @@ def _assert_mix(want, n):
     assert _strand_has(want, 0, 1) and _strand_has(want, n - 1, 1), "reads 0 and n - 1 accepted on the reverse strand"
 
 
-def _run_packed(dev, reads, L, e, k, step):
-    from fem_amd import device
-    n = len(reads)
-    bases = np.frombuffer(b"".join(reads), np.uint8)
-    hb, _ = dev.acquire_stage(n, n * L)
-    n_exc = device.pack_reads(bases, n, L, hb)
-    assert n_exc == sum(sum(1 for c in r if c not in b"ACGT") for r in reads)
-    dev.commit_stage_packed(n, L, n_exc)
-    assert dev.stage_info()[1]
-    dev.map_staged(e=e, k=k, step=step)
-    got = dev.fetch()
-    return got.per_strand() + (got.stats,)
-
-
 def _check(world, reads, L, e, want=None, dense=False):
     k, step = _index_of(L, e)
     want = want or _oracle(world, reads, e, k, step)
-    off, cand, ed, end, stats = _run_packed(world.dev(k, step, False, dense), reads, L, e, k, step)
+    off, cand, ed, end, stats = run_packed(world.dev(k, step, False, dense), reads, L, e, k, step)
     assert np.array_equal(off, want.cand_off) and np.array_equal(cand, want.cands)
     assert np.array_equal(ed, want.v_ed)
     assert np.array_equal(end[ed != 255], want.v_end[want.v_ed != 255])
-    off_c, cand_c, ed_c, end_c, stats_c = _run_packed(world.dev(k, step, True, dense), reads, L, e, k, step)
+    off_c, cand_c, ed_c, end_c, stats_c = run_packed(world.dev(k, step, True, dense), reads, L, e, k, step)
     assert np.array_equal(off, off_c) and np.array_equal(cand, cand_c)
     assert np.array_equal(ed, ed_c) and np.array_equal(end, end_c)
     assert np.array_equal(stats, stats_c) and len(stats) == 5
@@ -233,12 +118,12 @@ def _check(world, reads, L, e, want=None, dense=False):
 def test_every_boundary_length_against_the_oracle_and_the_character_kernel(world, L, e):
     rng = np.random.default_rng(1000 * L + e)
     k, step = _index_of(L, e)
-    reads = _reads(rng, world.seqs, world.places, N_READS, L, e)
+    reads = packed_reads(rng, world.seqs, world.places, N_READS, L, e)
     want = _oracle(world, reads, e, k, step)
     _assert_mix(want, N_READS)
     _check(world, reads, L, e, want)
     # the same batch with about 3 % of its reads carrying other characters: their lanes take the characters
-    odd, kind = _exceptions(rng, reads, 0.03)
+    odd, kind = packed_exceptions(rng, reads, 0.03)
     assert np.any(kind == 1) and np.any(kind == 2)
     _check(world, odd, L, e)
 
@@ -249,20 +134,20 @@ def test_small_batches_load_at_the_buffers_edges(world, L, n):
     e = SWEEP[L]
     rng = np.random.default_rng(77 * L + n)
     k, step = _index_of(L, e)
-    reads = _reads(rng, world.seqs, world.places, n, L, e)
+    reads = packed_reads(rng, world.seqs, world.places, n, L, e)
     want = _oracle(world, reads, e, k, step)
     # read 0 (nothing but padding in front of its codes) and read n - 1 (nothing but slack behind) on the reverse strand
     assert _strand_has(want, 0, 1) and _strand_has(want, n - 1, 1)
     _check(world, reads, L, e, want)
-    odd, _ = _exceptions(rng, reads, 0.03 if n > 1 else 0.0)
+    odd, _ = packed_exceptions(rng, reads, 0.03 if n > 1 else 0.0)
     _check(world, odd, L, e)
 
 
 def test_a_batch_in_which_every_read_is_an_exception(world):
     L, e = 100, 3
     rng = np.random.default_rng(5)
-    reads = _reads(rng, world.seqs, world.places, 1500, L, e)
-    odd, kind = _exceptions(rng, reads, 1.0)
+    reads = packed_reads(rng, world.seqs, world.places, 1500, L, e)
+    odd, kind = packed_exceptions(rng, reads, 1.0)
     assert np.all(kind > 0) and np.any(kind == 1) and np.any(kind == 2)
     off, cand, ed, end = _check(world, odd, L, e)  # (a read with N or R: what the oracle gives)
     # a read whose only odd characters are lower-case bases gives what its upper-case form gives
@@ -281,7 +166,7 @@ def test_groups_of_eight_inside_the_twelve_copy_unit(world, L, e):
     rng = np.random.default_rng(800 + L)
     units = [p for p in world.places if p[2] == UNIT]
     assert len(units) == UNIT_COPIES
-    reads = _reads(rng, world.seqs, units, 600, L, e) + _reads(rng, world.seqs, [], 600, L, e)
+    reads = packed_reads(rng, world.seqs, units, 600, L, e) + packed_reads(rng, world.seqs, [], 600, L, e)
     n = len(reads)
     assert _index_of(L, e) == (12, 3)
     want = _oracle(world, reads, e, 12, 3)
@@ -296,13 +181,13 @@ def test_dense_and_sparse_index_paths(world, dense):
     # the verification is shared; the order of the candidate slots differs
     L, e = 100, 3
     rng = np.random.default_rng(31 + dense)
-    reads = _reads(rng, world.seqs, world.places, 3000, L, e)
+    reads = packed_reads(rng, world.seqs, world.places, 3000, L, e)
     want = _oracle(world, reads, e, 12, 3)
     _assert_mix(want, len(reads))
     d = world.dev(12, 3, False, dense)
     assert (d.seed_kernel(e=e) == "seed_join_kernel") == dense
     _check(world, reads, L, e, want, dense=dense)
-    odd, _ = _exceptions(rng, reads, 0.03)
+    odd, _ = packed_exceptions(rng, reads, 0.03)
     _check(world, odd, L, e, dense=dense)
 
 
@@ -316,9 +201,9 @@ def test_mixed_lengths_staged_as_characters(world):
     e, per_len = 1, 200
     k, step = _index_of(min(MIXED_LENGTHS), e)
     rng = np.random.default_rng(4242)
-    reads = [r for L in MIXED_LENGTHS for r in _reads(rng, world.seqs, world.places, per_len, L, e)]
+    reads = [r for L in MIXED_LENGTHS for r in packed_reads(rng, world.seqs, world.places, per_len, L, e)]
     reads = [reads[int(j)] for j in rng.permutation(len(reads))]
-    reads, kind = _exceptions(rng, reads, 0.03)
+    reads, kind = packed_exceptions(rng, reads, 0.03)
     assert np.any(kind == 1) and np.any(kind == 2)
     want = _oracle(world, reads, e, k, step)
     strand = np.repeat(np.arange(2 * len(reads)) & 1, np.diff(want.cand_off.astype(np.int64)))

@@ -8,6 +8,7 @@ import pytest
 from fem_amd import host
 from oracle import fem_oracle as fo
 from tests import util
+from tests.cases import bgzf, expected_sam
 
 
 def oracle_case(seed, e, a=1, L=100, n_reads=250, repeat=True):
@@ -51,21 +52,6 @@ def test_tail_records_equal_oracle(e, L, repeat):
     if repeat and e >= 3:
         assert per_read.max() > 64, "fixture must exercise klib's radix path (>64 mappings of one read)"
     assert np.any((res.cig & 0xF) == 1) and np.any((res.cig & 0xF) == 2), "fixture must contain I and D"
-
-
-def expected_sam(seqs_names, reads, names, quals, res):
-    """SAM v1 text for the oracle's records (field rules of src/align.c:546-632, src/map.c:50-55)."""
-    lines = []
-    for r in range(len(reads)):
-        lo, hi = int(res.rec_off[r]), int(res.rec_off[r + 1])
-        for j in range(lo, hi):
-            primary = j == lo
-            lines.append("\t".join([
-                names[r], str(int(res.r_flag[j])), seqs_names[int(res.r_tid[j])], str(int(res.r_pos[j]) + 1), "255",
-                res.cigar_str(j), "*", "0", "0",
-                reads[r].decode().upper() if primary else "*", quals[r] if primary else "*",
-                "NM:i:%d" % int(res.r_nm[j]), "MD:Z:" + res.md_str(j)]))
-    return "".join(l + "\n" for l in lines)
 
 
 def test_sam_text_follows_the_record_rules():
@@ -343,21 +329,6 @@ def test_gzip_input_is_parsed_window_by_window(tmp_path):
         host.read_planned_batches(str(cut), 100_000, threads=2)
 
 
-def _bgzf(data, block=65280, level=1, eof_block=True):
-    """bgzip's format (SAM specification 4.1): gzip members with the 'BC' extra subfield, one per <= 64 KiB of input."""
-    import struct
-    import zlib
-    out = []
-    for at in list(range(0, len(data), block)) + ([None] if eof_block else []):
-        chunk = b"" if at is None else data[at:at + block]
-        c = zlib.compressobj(level, zlib.DEFLATED, -15)
-        payload = c.compress(chunk) + c.flush()
-        bsize = 18 + len(payload) + 8
-        out.append(b"\x1f\x8b\x08\x04" + b"\x00" * 4 + b"\x00\xff" + struct.pack("<H", 6) + b"BC" + struct.pack("<HH", 2, bsize - 1)
-                   + payload + struct.pack("<II", zlib.crc32(chunk) & 0xFFFFFFFF, len(chunk)))
-    return b"".join(out)
-
-
 def test_bgzf_input_is_inflated_block_parallel(tmp_path):
     # bgzip-compressed FASTQ / FASTA: the blocks of a window are inflated by all threads (fem_host.cc: bgzf_*), the window
     # goes through the multi-threaded parser; the sequential reader (references, multi-line records) reads block by block
@@ -376,7 +347,7 @@ def test_bgzf_input_is_inflated_block_parallel(tmp_path):
     assert whole.n == n
     for block, name in ((65280, "b.fq.gz"), (777, "small_blocks.fq.gz")):
         p = tmp_path / name
-        p.write_bytes(_bgzf(text, block=block))
+        p.write_bytes(bgzf(text, block=block))
         assert gzip.decompress(p.read_bytes()) == text  # (it is a valid multi-member gzip file)
         for approx, threads in ((100_000, 4), (1 << 21, 8), (0, 3)):
             parts = host.read_planned_batches(str(p), approx, threads=threads)
@@ -390,14 +361,14 @@ def test_bgzf_input_is_inflated_block_parallel(tmp_path):
     fa = b"".join(b">chr%d d\n" % i + b"\n".join(util.rand_seq(rng, 200_000)[j:j + 60] for j in range(0, 200_000, 60)) + b"\n" for i in range(3))
     fp, fz = tmp_path / "r.fa", tmp_path / "r.fa.gz"
     fp.write_bytes(fa)
-    fz.write_bytes(_bgzf(fa))
+    fz.write_bytes(bgzf(fa))
     a, b = host.read_sequences(str(fp)), host.read_sequences(str(fz))
     assert a.n == b.n == 3 and a.bases.tobytes() == b.bases.tobytes() and a.names_raw.tobytes() == b.names_raw.tobytes()
     # switch to the sequential reader in the middle (multi-line record), without the end-of-file block
     mixed = b"".join(recs[:4000]) + b"@ml x\nACGT\nACG\n+\nIIII\nIII\n" + b"".join(recs[4000:])
     mp, mz = tmp_path / "m.fq", tmp_path / "m.fq.gz"
     mp.write_bytes(mixed)
-    mz.write_bytes(_bgzf(mixed, block=5000, eof_block=False))
+    mz.write_bytes(bgzf(mixed, block=5000, eof_block=False))
     ref = host.read_sequences(str(mp))
     parts = host.read_planned_batches(str(mz), 120_000, threads=4)
     assert sum(q.n for q in parts) == ref.n == n + 1
@@ -434,7 +405,7 @@ def test_sequential_reads_then_batches_on_one_handle(tmp_path, kind):
         with gzip.open(str(p), "wb", compresslevel=1) as f:
             f.write(text)
     elif kind == "bgzf":
-        p.write_bytes(_bgzf(text))
+        p.write_bytes(bgzf(text))
     else:
         p.write_bytes(text)
     L = host.lib()

@@ -1,12 +1,10 @@
 """FEM map --infer-insert, the parts that need no GPU: the usage text, the refusals (given before any file is opened), the ABI's
 new symbol."""
 import os
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FEM = os.path.join(ROOT, "fem_amd", "csrc", "FEM")
+from tests.harness import ROOT, run_fem
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -16,7 +14,7 @@ def built():
 
 
 def run(*args):
-    return subprocess.run([FEM] + list(args), capture_output=True, text=True, timeout=120)
+    return run_fem(*args, text=True)
 
 
 def _map(tmp_path, *extra, read2=True):
@@ -61,7 +59,7 @@ def test_the_insert_range_is_still_checked(tmp_path):
 
 def test_the_library_exports_the_new_symbol():
     from fem_amd.device import ABI_SYMBOLS
-    from tests.test_abi import declared_symbols
+    from tests.cases import declared_symbols
     assert "fem_dev_estimate_insert" in set(ABI_SYMBOLS) & set(declared_symbols())
     hdr = open(os.path.join(ROOT, "include", "fem_hip.h")).read()
     assert "#define FEM_INSERT_MAX 16383" in hdr and "#define FEM_INSERT_MIN_PAIRS 64" in hdr

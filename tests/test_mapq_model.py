@@ -1,12 +1,7 @@
 """The MAPQ rule of FEM map --mapq (tests/mapq_model.py) on hand-built records, and the option's CPU-side handling."""
-import os
-import subprocess
-
 from tests import mapq_model as mq
 from tests import pair_model as pm
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FEM = os.path.join(ROOT, "fem_amd", "csrc", "FEM")
+from tests.harness import run_fem
 
 
 def rec(nm, pos=1000, flag=0, tid=0, L=100):
@@ -100,8 +95,7 @@ def test_from_sam_agrees_with_the_records():
 
 
 def _fem(*args, env=None):
-    full = dict(os.environ, **(env or {}))
-    return subprocess.run([FEM] + list(args), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300, env=full)
+    return run_fem(*args, env=env)
 
 
 def test_cli_lists_and_refuses_mapq(tmp_path):

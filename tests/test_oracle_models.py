@@ -15,39 +15,10 @@ import pytest
 
 from oracle import fem_oracle as fo
 from tests import util
-
-CODE = {65: 0, 97: 0, 67: 1, 99: 1, 71: 2, 103: 2, 84: 3, 116: 3}
-
-
-def code(c):
-    return CODE.get(c, 4)
+from tests.cases import banded_dp, code
 
 
 # ---------------------------------------------------------------- Myers vs banded DP
-def banded_dp(e, pattern, text):
-    """Edit distance of `text` against pattern[i+j], j in [0,2e] per column i; free start, free end, strict band."""
-    INF = 10 ** 6
-    L = len(text)
-    prev = [0] * (2 * e + 1)
-    score_path = 0
-    for i in range(L):
-        cur = [INF] * (2 * e + 1)
-        for j in range(2 * e + 1):
-            d = prev[j] + (0 if code(text[i]) == code(pattern[i + j]) else 1)
-            h = prev[j + 1] + 1 if j + 1 <= 2 * e else INF
-            v = cur[j - 1] + 1 if j >= 1 else INF
-            cur[j] = min(d, h, v)
-        prev = cur
-        score_path = cur[0]
-        if score_path > 3 * e:
-            return e + 1, None
-    best, end = prev[0], L - 1
-    for j in range(1, 2 * e + 1):
-        if prev[j] < best:
-            best, end = prev[j], L - 1 + j
-    return best, end
-
-
 @pytest.mark.parametrize("e", [0, 1, 2, 3, 5, 7])
 def test_myers32_equals_banded_dp(e):
     rng = np.random.default_rng(100 + e)

@@ -1,12 +1,10 @@
 """FEM map --orientation, the parts that need no GPU: the usage text, the three refusals (given before any file is opened), the
 ABI's two new symbols."""
 import os
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FEM = os.path.join(ROOT, "fem_amd", "csrc", "FEM")
+from tests.harness import ROOT, run_fem
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -16,7 +14,7 @@ def built():
 
 
 def run(*args):
-    return subprocess.run([FEM] + list(args), capture_output=True, text=True, timeout=120)
+    return run_fem(*args, text=True)
 
 
 def _map(tmp_path, *extra, read2=True):
@@ -64,7 +62,7 @@ def test_the_switch_is_accepted(tmp_path, extra):
 
 def test_the_library_exports_the_new_symbols():
     from fem_amd.device import ABI_SYMBOLS, hip_library_path
-    from tests.test_abi import declared_symbols
+    from tests.cases import declared_symbols
     import ctypes
     new = {"fem_dev_set_orientation", "fem_dev_estimate_library"}
     assert new <= set(ABI_SYMBOLS) & set(declared_symbols())

@@ -1,8 +1,6 @@
 """Paired-end mapping, the parts that need no GPU: FEM map's new options and their checks, the record-count reader that cuts
 the second read file (fem_seqfile_plan_count), and the output rules of tests/pair_model.py on hand-built record lists."""
 import gzip
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -10,10 +8,9 @@ import pytest
 from fem_amd import host
 from tests import pair_model as pm
 from tests import util
-from tests.test_host import _bgzf
+from tests.cases import bgzf
+from tests.harness import run_fem
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FEM = os.path.join(ROOT, "fem_amd", "csrc", "FEM")
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -23,7 +20,7 @@ def built():
 
 
 def run(*args):
-    return subprocess.run([FEM] + list(args), capture_output=True, text=True, timeout=120)
+    return run_fem(*args, text=True)
 
 
 def test_usage_lists_the_pair_options():
@@ -57,7 +54,7 @@ def _fastq(tmp_path, n):
     with gzip.open(str(gz), "wb", compresslevel=1) as f:
         f.write(data)
     bg = tmp_path / "r.fq.bgz.gz"
-    bg.write_bytes(_bgzf(data))
+    bg.write_bytes(bgzf(data))
     return plain, gz, bg
 
 

@@ -12,9 +12,7 @@ tests/golden/klib_records.npz holds, for every input these tests give it (keyed 
 fingerprints of what they compare: the loader's view of a file's records, the sort's permutation.  The vectors of
 tests/golden/klib_kseq.npz and klib_sort.npz are compared in full.  All are made by tests/golden/make_klib_golden.py."""
 import gzip
-import hashlib
 import os
-import struct
 
 import numpy as np
 import pytest
@@ -22,50 +20,11 @@ import pytest
 from fem_amd import host
 from oracle import fem_oracle as fo
 from oracle import ref_klib
+from tests.cases import HAND_MADE, StoredView, file_key, input_key, loader_view, perm_fingerprint, random_file, sort_cases, view_fingerprints
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 RECORDS = os.path.join(GOLDEN, "klib_records.npz")
 _stored = {}
-
-
-def input_key(kind, data):
-    return hashlib.sha1(kind + b"\0" + data).digest()[:8]
-
-
-def file_key(path):
-    data = open(path, "rb").read()
-    return input_key(b"gz", gzip.decompress(data)) if data[:2] == b"\x1f\x8b" else input_key(b"raw", data)
-
-
-def fingerprint(fields):
-    """SHA-1 (first 16 bytes) of a sequence of byte strings, each with its length; None is told apart from b""."""
-    h = hashlib.sha1()
-    for f in fields:
-        h.update(struct.pack("<q", -1 if f is None else len(f)))
-        h.update(f or b"")
-    return h.digest()[:16]
-
-
-def view_fingerprints(records):
-    """(names and sequences, qualities) of (name, sequence, quality) records: what same_records compares."""
-    return (fingerprint([x for r in records for x in (r[0], r[1])]), fingerprint([r[2] for r in records]))
-
-
-class StoredView:
-    """The loader's view of kseq_read's records (loader_view) of a file, as klib_records.npz holds it: how many records,
-    whether all have qualities, and the fingerprints of view_fingerprints."""
-
-    def __init__(self, n, all_qual, names_seqs, quals):
-        self.n, self.all_qual, self.names_seqs, self.quals = n, all_qual, names_seqs, quals
-
-    def __len__(self):
-        return self.n
-
-    @classmethod
-    def of(cls, view):
-        ns, q = view_fingerprints([(r[0], r[2], r[3]) for r in view])
-        all_qual = all(r[3] is not None for r in view)
-        return cls(len(view), all_qual, ns, q if all_qual and view else bytes(16))  # (qualities compared only then)
 
 
 def stored():
@@ -77,10 +36,6 @@ def stored():
                                                           g["quals"], g["last_rc"])}
         _stored["sort"] = {k.tobytes(): f.tobytes() for k, f in zip(g["sort_key"], g["perm"])}
     return _stored
-
-
-def perm_fingerprint(perm):
-    return fingerprint([np.ascontiguousarray(perm, dtype="<u4").tobytes()])
 
 
 def ref_view(path):
@@ -104,12 +59,6 @@ def same_sort(keys, got_k, got_perm):
     assert want is not None, "no stored radix sort result for these %d keys" % len(keys)
     assert np.array_equal(keys[got_perm.astype(np.int64)], got_k)
     assert perm_fingerprint(got_perm) == want, "order among equal keys"
-
-
-def loader_view(records, last_rc):
-    """What load_batch_of_sequences_into_sequence_batch keeps (src/sequence_batch.c:47-66): zero-length records are
-    skipped; a return value other than -1 at the end is "Didn't reach the end of sequence file" -> exit."""
-    return [r for r in records if len(r[2]) > 0], last_rc != -1
 
 
 def ours_sequential(path):
@@ -147,30 +96,6 @@ def same_records(ref, mine, quals=True):
             assert qual == q2
 
 
-HAND_MADE = {
-    "four_line": b"@r1 first comment\nACGT\n+\nIIII\n@r2\tTAB comment\nGGCC\n+r2\n!!!!\n",
-    "crlf": b"@r1 c\r\nACGT\r\n+\r\nIIII\r\n@r2\r\nGG\r\n+\r\nJJ\r\n",
-    "multi_line": b"@a\nACGT\nACG\n+\nIIII\nIII\n@b x\nTTTT\n+\nJJJJ\n",
-    "fasta": b">s1 desc\nACGTACGT\nACGT\n>s2\nGG\n\n>s3\nTTTT",
-    "mixed": b">f\nACGT\n@q\nGGGG\n+\nIIII\n>g\nCC\n",
-    "at_plus_quals": b"@r1\nACGT\n+\n@+@+\n@r2\nACGT\n+\n+@+@\n@r3\nAC\n+\n@@\n",
-    "blank_lines": b"\n\n@r1\nACGT\n+\nIIII\n\n\n@r2\nGG\n+\nII\n\n",
-    "leading_junk": b"junk line\nmore junk\n@r1\nACGT\n+\nIIII\n",
-    "no_final_newline": b"@r1\nACGT\n+\nIIII\n@r2\nGG\n+\nII",
-    "zero_length": b"@e1\n\n+\n\n@r1\nACGT\n+\nIIII\n@e2\n\n+\n\n",
-    "truncated_qual": b"@r1\nACGT\n+\nIIII\n@r2\nACGT\n+\nII\n",
-    "missing_qual_at_eof": b"@r1\nACGT\n+\nIIII\n@r2\nACGT\n+\n",
-    "header_only": b"@r1\n",
-    "empty": b"",
-    "only_newlines": b"\n\n\n",
-    "lower_and_n": b"@r1\nacgtNNnn\n+\nIIIIIIII\n",
-    "long_name": b"@" + b"n" * 300 + b" " + b"c" * 500 + b"\nACGT\n+\nIIII\n",
-    "qual_longer": b"@r1\nACGT\n+\nIIIIII\n@r2\nGG\n+\nII\n",
-    "plus_in_seq_line": b"@r1\nAC+GT\n+\nIIIII\n",
-    "gt_in_fastq": b"@r1\nACGT\n+\nIIII\n>f1\nACGT\n@r2\nGG\n+\nII\n",
-}
-
-
 @pytest.mark.parametrize("name", sorted(HAND_MADE))
 def test_readers_follow_kseq_on_hand_made_files(tmp_path, name):
     data = HAND_MADE[name]
@@ -190,48 +115,11 @@ def test_readers_follow_kseq_on_hand_made_files(tmp_path, name):
                 same_records(ref, mine)
 
 
-def _random_file(rng):
-    """FASTQ-like text with the irregularities kseq tolerates, then a few random byte edits."""
-    out = []
-    for i in range(int(rng.integers(1, 40))):
-        ln = int(rng.integers(0, 70))
-        seq = bytes(rng.choice(list(b"ACGTNacgt"), size=ln).astype(np.uint8))
-        qual = bytes(rng.integers(33, 75, size=ln).astype(np.uint8))
-        kind = rng.random()
-        name = b"r%d" % i + (b" comment %d" % i if rng.random() < 0.5 else b"")
-        eol = b"\r\n" if rng.random() < 0.1 else b"\n"
-        if kind < 0.7:
-            rec = b"@" + name + eol + seq + eol + b"+" + eol + qual + eol
-        elif kind < 0.8 and ln > 4:  # multi-line
-            h = ln // 2
-            rec = b"@" + name + eol + seq[:h] + eol + seq[h:] + eol + b"+" + eol + qual[:h] + eol + qual[h:] + eol
-        elif kind < 0.9:
-            rec = b">" + name + eol + seq + eol
-        else:
-            rec = b"@" + name + eol + seq + eol + b"+" + name + eol + qual + eol + b"\n"
-        out.append(rec)
-    data = bytearray(b"".join(out))
-    for _ in range(int(rng.integers(0, 3))):  # damage: delete, insert or change a byte
-        if not data:
-            break
-        at = int(rng.integers(0, len(data)))
-        op = rng.random()
-        if op < 0.4:
-            del data[at]
-        elif op < 0.7:
-            data.insert(at, int(rng.choice(list(b"@+>\nAI "))))
-        else:
-            data[at] = int(rng.choice(list(b"@+>\nAI ")))
-    if rng.random() < 0.3 and data:
-        data = data[:int(rng.integers(1, len(data) + 1))]  # cut off
-    return bytes(data)
-
-
 def test_readers_follow_kseq_on_random_damaged_files(tmp_path):
     rng = np.random.default_rng(2024)
     n_fatal = n_ok = 0
     for case in range(1500):
-        data = _random_file(rng)
+        data = random_file(rng)
         p = str(tmp_path / ("f%d.fq" % case))
         with open(p, "wb") as f:
             f.write(data)
@@ -249,19 +137,6 @@ def test_readers_follow_kseq_on_random_damaged_files(tmp_path):
     assert n_fatal > 300 and n_ok > 300
 
 
-def _sort_cases():
-    rng = np.random.default_rng(77)
-    cases = []
-    for n in [0, 1, 2, 5, 63, 64, 65, 66, 100, 128, 129, 200, 257, 448, 1000, 5000]:
-        for ties in (2, 8, 1 << 40):
-            # MappingSortKey: edit distance << 60 | direction << 59 | position (src/align.c:53); few distinct values = many ties
-            ed = rng.integers(0, 8, size=n).astype(np.uint64) << np.uint64(60)
-            direction = rng.integers(0, 2, size=n).astype(np.uint64) << np.uint64(59)
-            pos = rng.integers(0, ties, size=n).astype(np.uint64) * np.uint64(3 if ties < 100 else 1)
-            cases.append(ed | direction | pos)
-    return cases
-
-
 def _oracle_sort(keys):
     k = keys.copy()
     perm = np.zeros(len(k), np.uint32)
@@ -271,7 +146,7 @@ def _oracle_sort(keys):
 
 def test_mapping_order_follows_the_reference_radix_sort():
     n_tied = 0
-    for keys in _sort_cases():
+    for keys in sort_cases():
         got_k, got_perm = _oracle_sort(keys)
         same_sort(keys, got_k, got_perm)
         n_tied += len(keys) - len(np.unique(keys))

@@ -1,16 +1,13 @@
 """The model of the line filter (tests/report_model.py) on hand-built records: every row of the rule of include/fem_hip.h
-(fem_dev_set_report) at least once; on the oracle, without a GPU, that the generators of tests/test_gpu_report.py give what
+(fem_dev_set_report) at least once; on the oracle, without a GPU, that the case generators of tests/cases.py give what
 their cases need; and the argument errors of FEM map --strata / --max-hits."""
-import os
-import subprocess
-
+from tests import cases
 from tests import pair_model as pm
 from tests import report_model as rp
 from tests import unmapped_model as um
+from tests.harness import run_fem
 
 SEQS = ["chrA", "chrB"]
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FEM = os.path.join(ROOT, "fem_amd", "csrc", "FEM")
 
 
 def _rec(pos, nm, flag=0):
@@ -100,24 +97,20 @@ def test_pair_rows():
 # ---- the generators of the GPU cases meet their bounds (oracle and rescue model, no GPU) ----
 
 def test_generated_single_end_cases():
-    from tests import test_gpu_report as gr
-    for case in gr.SINGLE_CASES:
-        gr.check_single_case(gr.single_case(*case))
+    for case in cases.REPORT_SINGLE_CASES:
+        cases.check_report_single_case(cases.report_single_case(*case))
 
 
 def test_generated_pair_cases():
-    from tests import test_gpu_report as gr
-    assert any(c[4] is None for c in gr.PAIR_CASES) and any(c[4] is not None for c in gr.PAIR_CASES)
-    for case in gr.PAIR_CASES:
-        gr.check_pair_case(gr.pair_case(*case))
+    assert any(c[4] is None for c in cases.REPORT_PAIR_CASES) and any(c[4] is not None for c in cases.REPORT_PAIR_CASES)
+    for case in cases.REPORT_PAIR_CASES:
+        cases.check_report_pair_case(cases.report_pair_case(*case))
 
 
 # ---- FEM map --strata / --max-hits: the argument errors ----
 
 def _run(*args, env=None):
-    full = dict(os.environ, **env) if env else None
-    return subprocess.run([FEM, "map", "--ref", "a", "--index", "b", "--read1", "c", "-o", "d"] + list(args), stdout=subprocess.PIPE,
-                          stderr=subprocess.PIPE, timeout=300, env=full)
+    return run_fem("map", "--ref", "a", "--index", "b", "--read1", "c", "-o", "d", *args, env=env)
 
 
 def test_cli_argument_errors():

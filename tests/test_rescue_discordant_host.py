@@ -1,11 +1,8 @@
 """FEM map --rescue-discordant, the parts that need no GPU: the usage text, the refusal, the ABI's new symbols."""
-import os
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FEM = os.path.join(ROOT, "fem_amd", "csrc", "FEM")
+from tests.harness import run_fem
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -15,7 +12,7 @@ def built():
 
 
 def run(*args):
-    return subprocess.run([FEM] + list(args), capture_output=True, text=True, timeout=120)
+    return run_fem(*args, text=True)
 
 
 def test_usage_lists_rescue_discordant():
@@ -39,5 +36,5 @@ def test_with_rescue_the_switch_is_accepted(tmp_path):
 
 def test_the_library_exports_the_new_symbols():
     from fem_amd.device import ABI_SYMBOLS
-    from tests.test_abi import declared_symbols
+    from tests.cases import declared_symbols
     assert {"fem_dev_set_rescue_discordant", "fem_dev_rescue_discordant_count"} <= set(ABI_SYMBOLS) & set(declared_symbols())

@@ -1,8 +1,5 @@
 """Mate rescue, the parts that need no GPU: the oracle's banded Myers and traceback at the rescue's edit bounds (8..15)
 against the Python matrix models, the rule of tests/rescue_model.py on hand-built cases, and FEM map's --rescue checks."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
@@ -10,11 +7,8 @@ from oracle import fem_oracle as fo
 from tests import pair_model as pm
 from tests import rescue_model as rm
 from tests import util
-from tests.test_oracle_models import banded_dp
-from tests.test_traceback_model import Asserted, model_align
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FEM = os.path.join(ROOT, "fem_amd", "csrc", "FEM")
+from tests.cases import Asserted, banded_dp, model_align
+from tests.harness import run_fem
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -173,7 +167,7 @@ def test_lower_case_window_gives_an_md_of_every_column():
 # ---- FEM map --rescue ----
 
 def run(*args):
-    return subprocess.run([FEM] + list(args), capture_output=True, text=True, timeout=120)
+    return run_fem(*args, text=True)
 
 
 def test_usage_lists_rescue():

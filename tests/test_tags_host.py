@@ -8,7 +8,7 @@ import pytest
 from fem_amd import host
 from tests import bam_model as bm
 from tests import tags_model as tm
-from tests.test_cli import run
+from tests.harness import run_fem
 
 NAMES, LENS = ["chr1", "c2_" + "n" * 70, "x"], [1000, 123456, (1 << 31) - 1]
 
@@ -93,19 +93,19 @@ def test_the_validator_refuses(arg, why):
 def test_cli_usage_and_refusals():
     import __graft_entry__ as g
     g.build()
-    r = run("map", "-h")
+    r = run_fem("map", "-h")
     assert r.returncode == 0 and all(x in r.stderr for x in (b"--header", b"--rg", b"--nh"))
-    r = run("map", "--rg", "RG\\tID:x")
+    r = run_fem("map", "--rg", "RG\\tID:x")
     assert r.returncode != 0 and b"does not begin with @RG" in r.stderr
     base = ("map", "--ref", "a", "--index", "b", "--read1", "c", "-o", "d")
     for arg, why in (("@RG\\tSM:x", b"has no ID"), ("@RG\\tID:x\\tID:y", b"tag ID occurs twice"), ("@RG\tID:x\ny", b"contains a newline")):
-        r = run(*(base + ("--rg", arg)))
+        r = run_fem(*(base + ("--rg", arg)))
         assert r.returncode != 0 and why in r.stderr and b"Loaded index" not in r.stderr
     for var in ("FEM_HOST_TAIL", "FEM_HOST_FORMAT"):
         for sw in (("--rg", "@RG\\tID:x"), ("--nh",)):
-            r = run(*(base + sw), env={var: "1"})
+            r = run_fem(*(base + sw), env={var: "1"})
             assert r.returncode == 1 and (b"--rg and --nh are not supported with %s=1" % var.encode()) in r.stderr, (var, sw)
             assert b"Loaded index" not in r.stderr
         # --header alone is host text: not refused (the run then ends at the reference file that is not there)
-        r = run(*(base + ("--header",)), env={var: "1"})
+        r = run_fem(*(base + ("--header",)), env={var: "1"})
         assert b"not supported" not in r.stderr

@@ -1,11 +1,12 @@
-"""The model of the RG / NH / HI tags (tests/tags_model.py) on hand-written texts, and the case of tests/test_gpu_tags.py
-that has to hold slots of the sizes at which the kernels take another path.  No GPU."""
+"""The model of the RG / NH / HI tags (tests/tags_model.py) on hand-written texts, and the hit-count case of tests/cases.py (run by
+tests/test_gpu_tags.py), which has to hold slots of the sizes at which the kernels take another path.  No GPU."""
 import struct
 
 import numpy as np
 import pytest
 
 from tests import bam_model as bm
+from tests import cases
 from tests import tags_model as tm
 
 REFS = [b"chr1", b"chr2"]
@@ -114,8 +115,7 @@ def test_the_asserted_case_has_the_records_it_is_for():
 
 
 def test_the_hit_count_case_has_the_slots_it_is_for():
-    from tests.test_gpu_tags import hits_case
-    c = hits_case()
+    c = cases.hits_case()
     counts = np.diff(c["res"].rec_off.astype(np.int64))
     assert set(counts.tolist()) == {1, 2, 130} and min(np.count_nonzero(counts == k) for k in (1, 2, 130)) >= 4
     order = [int(k) for k in counts]

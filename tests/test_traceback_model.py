@@ -16,154 +16,7 @@ import pytest
 
 from oracle import fem_oracle as fo
 from tests import util
-
-CODE = {65: 0, 97: 0, 67: 1, 99: 1, 71: 2, 103: 2, 84: 3, 116: 3}
-
-
-def code(c):
-    return CODE.get(c, 4)  # src/utils.h:72
-
-
-def banded_matrix(e, pattern, text):
-    """D[t][j], t in 0..L-1, j in 0..2e, and the column before the first (all zero: free start)."""
-    INF = 10 ** 6
-    W = 2 * e + 1
-    prev = [0] * W
-    cols = []
-    for t in range(len(text)):
-        cur = [INF] * W
-        for j in range(W):
-            diag = prev[j] + (0 if code(text[t]) == code(pattern[t + j]) else 1)
-            left = prev[j + 1] + 1 if j + 1 < W else INF  # (t-1, q) with q below the previous column's band
-            up = cur[j - 1] + 1 if j >= 1 else INF
-            cur[j] = min(diag, left, up)
-        cols.append(cur)
-        prev = cur
-    return cols
-
-
-def bits(e, cols, t, j):
-    """(D0, HP) of cell (t, j) as the walk reads them."""
-    W = 2 * e + 1
-    prev = cols[t - 1] if t > 0 else [0] * W
-    d0 = cols[t][j] == prev[j]
-    left = prev[j + 1] if j + 1 < W else prev[j] + 1  # below the band the vertical step costs one (VP's high bits are set)
-    hp = cols[t][j] - left == 1
-    return d0, hp
-
-
-class Asserted(Exception):
-    pass
-
-
-def model_align(e, pattern, text, ed, end):
-    """-> (start, [(op, len)] left to right, md string); Asserted where the reference would trip an assert."""
-    L = len(text)
-    start = end - L + 1
-    if start < 0:
-        raise Asserted("start")
-    if all(text[i] == pattern[start + i] for i in range(L)):  # raw characters (src/align.c:289-300)
-        cigar = [("M", L)]
-        return start, cigar, model_md(pattern, text, start, cigar)
-    cols = banded_matrix(e, pattern, text)
-    bit, t, p = end - L + 1, L - 1, end
-    nerr = 0
-    d0, hp = bits(e, cols, t, bit)
-    if d0 and pattern[p] == text[t]:
-        t, p, pre, n = t - 1, p - 1, "M", 1
-    elif not d0:
-        if pattern[p] == text[t]:
-            raise Asserted("mismatch on equal characters")
-        t, p, nerr, pre, n = t - 1, p - 1, nerr + 1, "S", 1
-    elif d0 and hp:
-        t, bit, nerr, pre, n, start = t - 1, bit + 1, nerr + 1, "S", 1, start + 1
-    else:
-        raise Asserted("deletion first")
-    ops = []
-    while t >= 0 and nerr != ed:
-        if bit < 0 or bit > 2 * e:
-            raise Asserted("off the band")
-        d0, hp = bits(e, cols, t, bit)
-        if d0 and pattern[p] == text[t]:
-            t, p = t - 1, p - 1
-            if pre != "M":
-                ops.append((pre, n))
-                pre, n = "M", 1
-            else:
-                n += 1
-        elif not d0:
-            if pattern[p] == text[t]:
-                raise Asserted("mismatch on equal characters")
-            t, p, nerr = t - 1, p - 1, nerr + 1
-            if pre == "S":
-                n += 1
-            elif pre != "M":
-                ops.append((pre, n))
-                pre, n = "M", 1
-            else:
-                n += 1
-        elif d0 and hp:
-            t, bit, nerr, start = t - 1, bit + 1, nerr + 1, start + 1
-            if pre == "S":
-                n += 1
-            elif pre != "I":
-                ops.append((pre, n))
-                pre, n = "I", 1
-            else:
-                n += 1
-        else:
-            bit, p, nerr, start = bit - 1, p - 1, nerr + 1, start - 1
-            if pre != "D":
-                ops.append((pre, n))
-                pre, n = "D", 1
-            else:
-                n += 1
-    if t >= 0:
-        if pre != "M":
-            ops.append((pre, n))
-            ops.append(("M", t + 1))
-        else:
-            ops.append(("M", n + t + 1))
-    else:
-        ops.append((pre, n))
-    if ops[0][0] == "S":
-        if len(ops) < 2:
-            raise Asserted("only the pseudo-run")
-        ops[1] = (ops[1][0], ops[1][1] + ops[0][1])
-        ops = ops[1:]
-    if any(op == "S" for op, _ in ops):
-        raise Asserted("S inside")
-    cigar = ops[::-1]
-    if start < 0:
-        raise Asserted("start")
-    return start, cigar, model_md(pattern, text, start, cigar)
-
-
-def model_md(pattern, text, start, cigar):
-    out, run, rp, tp = [], 0, start, 0
-    for op, n in cigar:
-        if op == "M":
-            for _ in range(n):
-                if pattern[rp] == text[tp]:
-                    run += 1
-                else:
-                    if run:
-                        out.append(str(run))
-                        run = 0
-                    out.append(chr(pattern[rp]))
-                rp, tp = rp + 1, tp + 1
-        elif op == "I":
-            tp += n
-        else:
-            if run:
-                out.append(str(run))
-                run = 0
-            out.append("^" + pattern[rp:rp + n].decode("latin-1"))
-            rp += n
-    if run:
-        out.append(str(run))
-    return "".join(out)
-
+from tests.cases import Asserted, code, model_align
 
 def path_cost(pattern, text, start, cigar):
     """Edits the CIGAR spends (on base codes) and the reference position behind its last base."""

@@ -1,7 +1,8 @@
 """The model of the lines for unmapped reads (tests/unmapped_model.py) on hand-built records: every row of the rule of
-include/fem_hip.h (fem_dev_set_unmapped) at least once, and — on the oracle, without a GPU — that the generators of
-tests/test_gpu_unmapped.py give what their cases need."""
+include/fem_hip.h (fem_dev_set_unmapped) at least once, and — on the oracle, without a GPU — that the case generators of
+tests/cases.py (run by tests/test_gpu_unmapped.py) give what their cases need."""
 from tests import bam_model as bm
+from tests import cases
 from tests import pair_model as pm
 from tests import unmapped_model as um
 
@@ -104,14 +105,12 @@ def test_a_rescued_mate_is_mapped():
 # ---- the generators of the GPU cases meet their bounds (oracle and rescue model, no GPU) ----
 
 def test_generated_single_end_cases():
-    from tests import test_gpu_unmapped as gu
-    for case in gu.SINGLE_CASES:
-        c = gu.single_case(*case)
-        gu.check_single_case(c)
+    for case in cases.UNMAPPED_SINGLE_CASES:
+        c = cases.unmapped_single_case(*case)
+        cases.check_unmapped_single_case(c)
 
 
 def test_generated_pair_cases():
-    from tests import test_gpu_unmapped as gu
-    for case in gu.PAIR_CASES:
-        c = gu.pair_case(*case)
-        gu.check_pair_case(c)
+    for case in cases.UNMAPPED_PAIR_CASES:
+        c = cases.unmapped_pair_case(*case)
+        cases.check_unmapped_pair_case(c)
