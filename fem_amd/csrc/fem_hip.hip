@@ -2156,6 +2156,8 @@ static int tail_records(fem_dev *h, int slot, const void *out, bool copy_records
   if (text && !s.text_staged) return fail(h, FEM_ERR_STATE, "qualities and names of this batch were not committed (fem_dev_commit_text_stage)");
   if (text && s.opt.mates() && s.host_quals)
     return fail(h, FEM_ERR_INVALID, "mate tags (fem_dev_set_mate_tags) need the qualities on the device: ms:i is made from them (fem_dev_commit_text_stage, not _names_stage)");
+  if (text && s.opt.sam_seq && s.host_quals)
+    return fail(h, FEM_ERR_INVALID, "SEQ and QUAL in SAM order (fem_dev_set_sam_seq) need the qualities on the device: QUAL is reversed where it is written (fem_dev_commit_text_stage, not _names_stage)");
   if (device_quals && s.host_quals) return fail(h, FEM_ERR_STATE, "BAM records need the qualities on the device (fem_dev_commit_text_stage, not _names_stage)");
   if (text && !h->d_ref_names) return fail(h, FEM_ERR_STATE, "reference names must be uploaded first (fem_dev_upload_reference_names)");
   s.prefetch_results = false;  // this caller takes records, not the per-candidate arrays
@@ -2334,6 +2336,10 @@ int fem_dev_set_unmapped(fem_dev *h, int slot, int on) {
 
 int fem_dev_set_mate_tags(fem_dev *h, int slot, int on) {
   return with_slot(h, slot, [&](Slot &s) { return s.opt.mate_tags = on != 0, (int)FEM_OK; });
+}
+
+int fem_dev_set_sam_seq(fem_dev *h, int slot, int on) {
+  return with_slot(h, slot, [&](Slot &s) { return s.opt.sam_seq = on != 0, (int)FEM_OK; });
 }
 
 int fem_dev_set_report(fem_dev *h, int slot, const fem_report_params *rp) {

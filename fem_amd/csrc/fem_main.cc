@@ -15,6 +15,8 @@
 // `--orientation fr|rf|ff|auto` sets the library's orientation (fem_dev_set_orientation); `auto` learns it with the insert size
 // range, in --infer-insert's pre-pass (fem_dev_estimate_library).
 // `--mate-tags` adds MC:Z, MQ:i and ms:i to every line of a paired output, made on the device (fem_dev_set_mate_tags).
+// `--sam-seq` prints SEQ reverse-complemented and QUAL reversed on the reverse-strand lines that carry them, as the SAM
+// specification orders them, made on the device (fem_dev_set_sam_seq).
 #include <errno.h>
 #include <fcntl.h>
 #include <getopt.h>
@@ -95,6 +97,7 @@ void usage_map() {
   fprintf(stderr, "                      (implies --header), and every line gets RG:Z:<ID>\n");
   fprintf(stderr, "        --nh          write NH:i (the read's, or the mate's, lines in the output) and HI:i (which of them) on every mapped line\n");
   fprintf(stderr, "        --mate-tags   with --read2: write MC:Z, MQ:i and ms:i (the other mate's CIGAR, MAPQ and quality score, as samtools fixmate -m) on every line\n");
+  fprintf(stderr, "        --sam-seq     write SEQ reverse-complemented and QUAL reversed on reverse-strand lines (FLAG 0x10), as the SAM specification orders them\n");
   fprintf(stderr, "        -o       STR  Output SAM file \n\n");
 }
 
@@ -319,6 +322,7 @@ int map_main(int argc, char **argv) {
   const char *rg_arg = nullptr;  // --rg: the @RG line (implies --header) and RG:Z on every line, made on the device (fem_dev_set_tags)
   bool hit_tags = false;         // --nh: NH:i and HI:i on every mapped line, made on the device (fem_dev_set_tags)
   bool mate_tags = false;        // --mate-tags: MC:Z, MQ:i and ms:i on every line of a paired output, made on the device (fem_dev_set_mate_tags)
+  bool sam_seq = false;          // --sam-seq: SEQ and QUAL of the lines with 0x10 in the reference's direction, made on the device (fem_dev_set_sam_seq)
   fem_params params{12, 3, 2, 1};  // src/FEM_map.c:67-70: k and step are fixed, whatever the index header says
   int n_threads = 1, n_gpus = 1;
   // reads per batch: 250 k fills the pipeline soonest on small inputs; a batch costs three host round trips on its way through
@@ -340,6 +344,7 @@ int map_main(int argc, char **argv) {
                                      {"strata", required_argument, nullptr, 'S'}, {"max-hits", required_argument, nullptr, 'N'},
                                      {"header", no_argument, nullptr, 'H'},      {"rg", required_argument, nullptr, 'T'},
                                      {"nh", no_argument, nullptr, 'n'},          {"mate-tags", no_argument, nullptr, 'M'},
+                                     {"sam-seq", no_argument, nullptr, 'q'},
                                      {nullptr, 0, nullptr, 0}};
   int c, oi = 0;
   while ((c = getopt_long(argc, argv, short_opt, long_opt, &oi)) >= 0) {
@@ -348,6 +353,7 @@ int map_main(int argc, char **argv) {
       case 'T': rg_arg = optarg, header = true; break;
       case 'n': hit_tags = true; break;
       case 'M': mate_tags = true; break;
+      case 'q': sam_seq = true; break;
       case 'r': ref_path = optarg; break;
       case 'i': index_path = optarg; break;
       case 'b': read_path = optarg; break;
@@ -466,6 +472,13 @@ int map_main(int argc, char **argv) {
       exit(EXIT_FAILURE);
     }
   }
+  for (const char *v : {"FEM_HOST_TAIL", "FEM_HOST_FORMAT", "FEM_HOST_QUALS"}) {  // (nor QUAL reversed: the host would fill it in forward)
+    const char *x = getenv(v);
+    if (sam_seq && x && x[0] == '1') {
+      fprintf(stderr, "--sam-seq is not supported with %s=1: SEQ and QUAL are turned on the device, with the qualities there.\n", v);
+      exit(EXIT_FAILURE);
+    }
+  }
   for (const char *v : {"FEM_HOST_TAIL", "FEM_HOST_FORMAT"}) {  // (the host formatter has no MAPQ path)
     const char *x = getenv(v);
     if (mapq && x && x[0] == '1') {
@@ -533,7 +546,7 @@ int map_main(int argc, char **argv) {
   // to box (the run is bound by the link in one and by the cores in the other); from 24 threads on the qualities stay on the
   // host.  FEM_HOST_QUALS=1 / FEM_DEVICE_QUALS=1 decide it by hand.
   const char *dq = getenv("FEM_DEVICE_QUALS"), *hq = getenv("FEM_HOST_QUALS");
-  const bool host_quals = device_text && !bam && !mate_tags && !(dq && dq[0] == '1') && ((hq && hq[0] == '1') || n_threads >= 24);
+  const bool host_quals = device_text && !bam && !mate_tags && !sam_seq && !(dq && dq[0] == '1') && ((hq && hq[0] == '1') || n_threads >= 24);
   const bool splice = !host_tail && !device_text && !(spl && spl[0] == '0');
   // With the text on the device the link is what bounds the run: batches of equal-length reads then cross it at two bits per
   // base — the parser writes that form straight into the pinned staging (fem_seqfile_fill_packed ->
@@ -606,6 +619,7 @@ int map_main(int argc, char **argv) {
             const fem_tag_params tp{rg_arg ? rg_id : nullptr, hit_tags ? 1 : 0};
             rc = fem_dev_set_tags(devs[(size_t)g], sl, &tp);
           }
+          if (!rc && sam_seq) rc = fem_dev_set_sam_seq(devs[(size_t)g], sl, 1);
           if (!rc && paired) {
             const fem_pair_params pp{(int32_t)min_insert, (int32_t)max_insert};
             rc = fem_dev_set_pairs(devs[(size_t)g], sl, &pp);

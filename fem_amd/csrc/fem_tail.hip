@@ -1095,6 +1095,7 @@ using PinBuf = femb::Buf<T, femb::Mem::Pinned, femb::Grow::Quarter>;
 // them: QNAME FLAG RNAME POS 255 CIGAR * 0 0 SEQ QUAL NM:i MD:Z.  SEQ is the read as it came (src/align.c:79) through
 // the 4-bit round trip of the BAM record (seq_nt16_table / seq_nt16_str: IUPAC letters upper-cased, anything else N);
 // only a read's first record carries SEQ and QUAL (src/align.c:83-88).  Same bytes as fem_records_sam (fem_host.cc).
+// SamParams::sam_seq (fem_dev_set_sam_seq, opt-in) turns SEQ and QUAL of the lines with 0x10 as the SAM specification has them.
 // ---------------------------------------------------------------------------------------------------------
 __device__ const uint8_t kSamSeqLut[256] = {
     78, 78, 78, 78, 78, 78, 78, 78, 78, 78, 78, 78, 78, 78, 78, 78, 78, 78, 78, 78, 78, 78, 78, 78, 78, 78, 78, 78, 78, 78, 78, 78,
@@ -1150,7 +1151,19 @@ struct SamParams {
   uint32_t mate_tags;           // != 0: the kMate instances run
   const uint32_t *mate_begin;   // pair_kernel's pair_begin, with or without lines for unmapped reads (pair_begin above is theirs)
   const uint32_t *mate_score;   // per read, mate_score_kernel's; nullptr: no qualities on the device, no ms
+  // SEQ and QUAL as SAM orders them (fem_dev_set_sam_seq): a line whose FLAG as written has 0x10 and that carries
+  // SEQ prints the read's reverse complement and its qualities reversed (the write kernels alone: no length changes)
+  uint32_t sam_seq;             // != 0: on
 };
+
+// The complement of the letter kSamSeqLut prints: =ACMGRSVTWYHKDBN -> =TGKCYSBAWRDMHVN, the 4-bit BAM code with its bits reversed
+__device__ __forceinline__ uint8_t sam_seq_complement(uint8_t ch) {
+  const char *abc = "=ACMGRSVTWYHKDBN", *cba = "=TGKCYSBAWRDMHVN";
+  uint8_t c = 'N';
+  for (uint32_t k = 0; k < 16u; ++k)
+    if ((uint8_t)abc[k] == ch) c = (uint8_t)cba[k];
+  return c;
+}
 
 __device__ __forceinline__ uint32_t dec_digits(uint32_t v) {
   return v < 10u ? 1u : v < 100u ? 2u : v < 1000u ? 3u : v < 10000u ? 4u : v < 100000u ? 5u : v < 1000000u ? 6u
@@ -1376,11 +1389,14 @@ __global__ void __launch_bounds__(256) sam_len_kernel(SamParams p) {
 // bytes on every line, so each lane loads its bytes of it (up to four: 255 characters) once, in front of the records.
 // kMate: MC, MQ and ms are three more short fields of the lane's own line, the other mate's first CIGAR operations in registers as
 // the line's own are.
+// p.sam_seq (the same in every lane): whether a record's SEQ and QUAL are turned travels with its other numbers (Rec::rev); a
+// turned record loads base and quality L - 1 - k where the others load k and prints through the table's second half.
 template <bool kPair, bool kUnm = false, bool kMate = false>
 __global__ void __launch_bounds__(256) sam_write_kernel(SamParams p) {
   static_assert(kPair || !kMate, "mate tags are a paired text's");
-  __shared__ uint8_t lut[256];
+  __shared__ uint8_t lut[512];  // the letter a read character prints; from 256 on that letter's complement (p.sam_seq)
   lut[threadIdx.x] = kSamSeqLut[threadIdx.x];
+  if (p.sam_seq) lut[256u + threadIdx.x] = sam_seq_complement(kSamSeqLut[threadIdx.x]);
   __syncthreads();
   const uint32_t ln = threadIdx.x & 63u;
   const uint32_t j0 = ((blockIdx.x * blockDim.x + threadIdx.x) >> 6) * 64u;
@@ -1563,10 +1579,12 @@ __global__ void __launch_bounds__(256) sam_write_kernel(SamParams p) {
   const uint32_t at_lo = (uint32_t)at, at_hi = (uint32_t)(at >> 32), no_lo = (uint32_t)no, no_hi = (uint32_t)(no >> 32);
   const uint32_t ro_lo = (uint32_t)ro, ro_hi = (uint32_t)(ro >> 32);
   const uint32_t L_seq = seq ? L : 0u;  // (no SEQ / QUAL bytes on a read's further records)
+  // p.sam_seq: a line with 0x10 takes base and quality L - 1 - k where the others take k (an unmapped read's line has no 0x10)
+  const uint32_t rev = p.sam_seq && (flag & 16u) ? 1u : 0u;
   struct Rec {
     uint8_t *w;
     const uint8_t *name, *rname, *md, *bases, *quals;
-    uint32_t name_len, rname_len, md_len, L, o_rname, o_md, o_seq, o_id;
+    uint32_t name_len, rname_len, md_len, L, o_rname, o_md, o_seq, o_id, rev;
   };
   uint8_t id[4] = {0, 0, 0, 0};  // the lane's bytes of the read group's ID
   if (p.rg_len) {
@@ -1584,6 +1602,7 @@ __global__ void __launch_bounds__(256) sam_write_kernel(SamParams p) {
     x.name_len = rl(name_len, i), x.rname_len = rl(rname_len, i), x.md_len = rl(md_len, i), x.L = rl(L_seq, i);
     x.o_rname = rl(o_rname, i), x.o_md = rl(o_md, i), x.o_seq = rl(o_seq, i);
     x.o_id = p.rg_len ? rl(o_rg, i) + 6u : 0u;
+    x.rev = p.sam_seq ? rl(rev, i) : 0u;
     return x;
   };
   struct Bytes {
@@ -1595,11 +1614,12 @@ __global__ void __launch_bounds__(256) sam_write_kernel(SamParams p) {
     if (ln < x.name_len) b.n = x.name[ln];
     if (ln < x.rname_len) b.rn = x.rname[ln];
     if (ln < x.md_len) b.m = x.md[ln];
-    if (ln < x.L) b.sA = x.bases[ln];
-    if (k1 < x.L) b.sB = x.bases[k1];
+    const uint32_t kA = x.rev ? x.L - 1u - ln : ln, kB = x.rev ? x.L - 1u - k1 : k1;  // (read only where ln, k1 < L)
+    if (ln < x.L) b.sA = x.bases[kA];
+    if (k1 < x.L) b.sB = x.bases[kB];
     if (x.quals) {
-      if (ln < x.L) b.qA = x.quals[ln];
-      if (k1 < x.L) b.qB = x.quals[k1];
+      if (ln < x.L) b.qA = x.quals[kA];
+      if (k1 < x.L) b.qB = x.quals[kB];
     }
     return b;
   };
@@ -1608,8 +1628,9 @@ __global__ void __launch_bounds__(256) sam_write_kernel(SamParams p) {
     if (ln < x.name_len) x.w[ln] = b.n;
     if (ln < x.rname_len) w_rname[ln] = b.rn;
     if (ln < x.md_len) w_md[ln] = b.m;
-    if (ln < x.L) w_seq[ln] = lut[b.sA];
-    if (k1 < x.L) w_seq[k1] = lut[b.sB];
+    const uint8_t *tab = lut + (x.rev << 8);
+    if (ln < x.L) w_seq[ln] = tab[b.sA];
+    if (k1 < x.L) w_seq[k1] = tab[b.sB];
     if (x.quals) {
       if (ln < x.L) w_seq[x.L + 1u + ln] = b.qA;
       if (k1 < x.L) w_seq[x.L + 1u + k1] = b.qB;
@@ -1620,8 +1641,9 @@ __global__ void __launch_bounds__(256) sam_write_kernel(SamParams p) {
     for (uint32_t k = k1; k < x.rname_len; k += 64u) w_rname[k] = x.rname[k];
     for (uint32_t k = k1; k < x.md_len; k += 64u) w_md[k] = x.md[k];
     for (uint32_t k = ln + 128u; k < x.L; k += 64u) {
-      w_seq[k] = lut[x.bases[k]];
-      if (x.quals) w_seq[x.L + 1u + k] = x.quals[k];
+      const uint32_t from = x.rev ? x.L - 1u - k : k;
+      w_seq[k] = tab[x.bases[from]];
+      if (x.quals) w_seq[x.L + 1u + k] = x.quals[from];
     }
     if (p.rg_len) {
       uint8_t *w_id = x.w + x.o_id;
@@ -1698,7 +1720,7 @@ __global__ void __launch_bounds__(256) bam_len_kernel(SamParams p, uint32_t n_re
 template <bool kPair, bool kUnm = false, bool kMate = false>
 __global__ void __launch_bounds__(256) bam_write_kernel(SamParams p) {
   static_assert(kPair || !kMate, "mate tags are a paired text's");
-  __shared__ uint8_t code4[256];  // read character -> 4-bit code of the letter the SAM text prints
+  __shared__ uint8_t code4[512];  // read character -> 4-bit code of the letter the SAM text prints; from 256 on of its complement
   {
     const uint8_t ch = kSamSeqLut[threadIdx.x];
     const char *abc = "=ACMGRSVTWYHKDBN";
@@ -1706,6 +1728,7 @@ __global__ void __launch_bounds__(256) bam_write_kernel(SamParams p) {
     for (uint8_t k = 0; k < 16; ++k)
       if ((uint8_t)abc[k] == ch) c = k;
     code4[threadIdx.x] = c;
+    if (p.sam_seq) code4[256u + threadIdx.x] = (uint8_t)(__builtin_bitreverse32(c) >> 28);  // (the complement: the code's bits reversed)
   }
   __syncthreads();
   const uint32_t ln = threadIdx.x & 63u;
@@ -1769,13 +1792,27 @@ __global__ void __launch_bounds__(256) bam_write_kernel(SamParams p) {
   x += 4u * n_ops;
   const uint8_t *bases = p.bases + ro;
   const uint32_t sb = (ls + 1u) / 2u;
-  for (uint32_t k = ln; k < sb; k += 64u) {
-    const uint32_t hi = code4[bases[2u * k]], lo = 2u * k + 1u < ls ? code4[bases[2u * k + 1u]] : 0u;
-    x[k] = (uint8_t)(hi << 4 | lo);
-  }
-  x += sb;
+  // p.sam_seq: a record with 0x10 holds the reversed read, position i of it base ls - 1 - i complemented; byte k the positions 2k
+  // and 2k + 1 as ever, so with an odd ls the last byte's high nibble is base 0 and its low nibble stays 0
+  // (the whole wave takes one side: a forward record runs the loops it ran before there was an option)
   const uint8_t *quals = p.quals ? p.quals + ro : nullptr;
-  for (uint32_t k = ln; k < ls; k += 64u) x[k] = quals ? (uint8_t)(quals[k] - 33u) : (uint8_t)0xFF;
+  if (p.sam_seq && (fl & 16u) && !(kUnm && unm)) {
+    const uint8_t *tab = code4 + 256;
+    const uint32_t last = ls - 1u;
+    for (uint32_t k = ln; k < sb; k += 64u) {
+      const uint32_t hi = tab[bases[last - 2u * k]], lo = 2u * k + 1u < ls ? tab[bases[last - 2u * k - 1u]] : 0u;
+      x[k] = (uint8_t)(hi << 4 | lo);
+    }
+    x += sb;
+    for (uint32_t k = ln; k < ls; k += 64u) x[k] = quals ? (uint8_t)(quals[last - k] - 33u) : (uint8_t)0xFF;
+  } else {
+    for (uint32_t k = ln; k < sb; k += 64u) {
+      const uint32_t hi = code4[bases[2u * k]], lo = 2u * k + 1u < ls ? code4[bases[2u * k + 1u]] : 0u;
+      x[k] = (uint8_t)(hi << 4 | lo);
+    }
+    x += sb;
+    for (uint32_t k = ln; k < ls; k += 64u) x[k] = quals ? (uint8_t)(quals[k] - 33u) : (uint8_t)0xFF;
+  }
   x += ls;
   if (!(kUnm && unm)) {
     if (ln == 0) x[0] = 'N', x[1] = 'M', x[2] = 'C', x[3] = (uint8_t)nm, x[4] = 'M', x[5] = 'D', x[6] = 'Z';
@@ -3098,6 +3135,7 @@ struct Tail::Impl {
       }
       TAIL_TRY(span[kMapq].end(stream));
     }
+    p->sam_seq = opt.sam_seq ? 1u : 0u;
     if (opt.mates()) {
       p->mate_tags = 1u, p->mate_begin = pair_begin;
       if (names.quals) {

@@ -124,6 +124,7 @@ struct LineOptions {
   std::string read_group;          // the ID every line's RG:Z tag carries; empty: no RG tag
   bool hit_tags = false;           // NH:i and HI:i on every mapped line
   bool mate_tags = false;          // MC:Z MQ:i ms:i on every line of a paired text (mate_score_kernel; the kernels' kMate instances)
+  bool sam_seq = false;            // SEQ reverse-complemented and QUAL reversed on the lines with 0x10 that carry them (the write kernels)
   bool filters() const { return strata >= 0 || max_hits >= 1; }  // the line filter is on
   bool rescues() const { return paired && rescue; }
   bool mates() const { return paired && mate_tags; }

@@ -23,7 +23,7 @@ ABI_SYMBOLS = [
     "fem_dev_set_orientation", "fem_dev_estimate_library",
     "fem_dev_set_rescue", "fem_dev_rescue_count", "fem_dev_set_rescue_discordant", "fem_dev_rescue_discordant_count", "fem_dev_set_mapq",
     "fem_dev_set_unmapped", "fem_dev_unmapped_count",
-    "fem_dev_set_report", "fem_dev_filtered_count", "fem_dev_set_tags", "fem_dev_set_mate_tags",
+    "fem_dev_set_report", "fem_dev_filtered_count", "fem_dev_set_tags", "fem_dev_set_mate_tags", "fem_dev_set_sam_seq",
     "fem_dev_fetch_bam", "fem_dev_fetch_bam_nowait", "fem_dev_bam_wait", "fem_dev_bgzf_compress",
 ]
 
@@ -194,6 +194,8 @@ def load_hip():
         L.fem_dev_set_tags.argtypes = [vp, C.c_int, C.POINTER(_TagParams)]
     if hasattr(L, "fem_dev_set_mate_tags"):
         L.fem_dev_set_mate_tags.argtypes = [vp, C.c_int, C.c_int]
+    if hasattr(L, "fem_dev_set_sam_seq"):
+        L.fem_dev_set_sam_seq.argtypes = [vp, C.c_int, C.c_int]
     if hasattr(L, "fem_dev_fetch_bam"):
         L.fem_dev_fetch_bam.argtypes = [vp, C.c_int, C.c_int, C.POINTER(_BatchBam)]
         L.fem_dev_fetch_bam_nowait.argtypes = [vp, C.c_int, C.c_int, C.POINTER(_BatchBam)]
@@ -732,6 +734,12 @@ class Device:
         """fem_dev_set_mate_tags: MC:Z, MQ:i and ms:i (the other mate's CIGAR, MAPQ and quality score) on every line of the slot's
         paired SAM text and BAM records (False: none); the qualities must be on the device then."""
         self._check(self._L.fem_dev_set_mate_tags(self._h, slot, 1 if on else 0))
+
+    def set_sam_seq(self, on=True, slot=0):
+        """fem_dev_set_sam_seq: SEQ reverse-complemented and QUAL reversed on the lines and BAM records of the slot's output whose
+        FLAG has 0x10 and that carry them, as the SAM specification orders them (False: every read as sequenced, the reference's
+        output); the qualities must be on the device then."""
+        self._check(self._L.fem_dev_set_sam_seq(self._h, slot, 1 if on else 0))
 
     def filtered_count(self, slot=0):
         """fem_dev_filtered_count: lines the filter left out of the slot's last SAM text or BAM."""

@@ -581,6 +581,31 @@ int fem_dev_set_tags(fem_dev *h, int slot, const fem_tag_params *tp);
  *   and HI); block_size includes them. */
 int fem_dev_set_mate_tags(fem_dev *h, int slot, int on);
 
+/* ---- SEQ and QUAL as SAM orders them (new; opt-in: the reference prints every read as it came from the sequencer, src/align.c:79,
+ *      also on lines with FLAG 0x10, and so does every output without it) ----
+ * fem_dev_set_sam_seq: on != 0: the lines of the slot's fem_dev_fetch_sam[_nowait] text and the records of its
+ *   fem_dev_fetch_bam[_nowait] that the rule below names print the read in the reference's direction, as POS, CIGAR, NM and MD of
+ *   the same line already are; 0: every byte as before.  Per slot and sticky, as the other options.  fem_batch_records and
+ *   fem_batch_pairs carry no SEQ and are unchanged, as are the stats, n_records and every count (output text only).
+ *   QUAL is reversed where it is written, on the device: a fetch of a text with the setting on and the slot's qualities kept on the
+ *   host (fem_dev_commit_names_stage, where the caller fills the QUAL holes forward) is FEM_ERR_INVALID.  Both ways of staging the
+ *   bases serve it (characters, and the 2-bit packed transfer).
+ * Rule.  A line or record changes only if its FLAG AS WRITTEN has 0x10 and it carries SEQ: a read's primary line in single-end
+ *   output; a line without 0x100 in paired output, rescued mates' lines included.  A record with 0x8000 follows the same rule by
+ *   its 0x10 bit.  On such a line, L being the read's length:
+ *   SEQ   character i is the complement of character L - 1 - i of what is printed without the setting, that is, after the letter
+ *     table of the 4-bit round trip (IUPAC letters upper-cased, anything else N).  The complement maps the sixteen letters
+ *     =ACMGRSVTWYHKDBN to =TGKCYSBAWRDMHVN: the 4-bit BAM code with its bits reversed (htslib's table).  So a -> A -> T and
+ *     . -> N -> N.
+ *   QUAL  byte i is byte L - 1 - i.  A QUAL printed as * stays *.
+ *   BAM   the same letters as 4-bit codes packed from the reversed order: byte k holds positions 2k and 2k + 1 of the reversed
+ *     read, the low nibble of the last byte of an odd L is 0; qual - 33 is reversed (0xFF stays 0xFF); l_seq, block_size and bin
+ *     are unchanged.
+ *   Nothing else changes: no line or record changes its length, no offset, count or counter changes, no forward-strand line, no
+ *   secondary line (* and *), no line of an unmapped read, placed or not (it has no 0x10, whatever 0x20 says, and stays as
+ *   sequenced), no tag (ms:i is a sum).  FLAG 0x10 is the real strand under every fem_dev_set_orientation. */
+int fem_dev_set_sam_seq(fem_dev *h, int slot, int on);
+
 /* Name of the seed + filter kernel fem_dev_map_staged would launch first for these parameters on the resident
  * index ("seed_join_kernel" — behind its "seed_select_kernel"; "seed_join_banked_kernel" where the reference's sequences
  * need more than one 32-bit coordinate space —, "seed_fast_kernel<hash>", "seed_fast_kernel<lean>" or
