@@ -58,7 +58,7 @@ constexpr size_t kPackedFrontPad = 256;  // ... and verify_kernel_packed up to 1
 constexpr uint64_t kExpandAllShare = 8;  // a packed batch with more exceptions than one per this many reads is expanded whole at commit
 constexpr uint32_t kXcapSmall = 512, kFcap = 128, kCcap = 128;
 
-constexpr int kTimedKernels = 18;  // fem_dev_kernel_time ids: 0 seed (join), 1 verify, 2 generic seed, 3-5 tail, 6 pack_results_kernel (round 5; the count kernel of rounds 1-2 before), 7 SAM text, 8 seed selection, 9 pairing, 10 mate rescue, 11 BAM records, 12 BGZF, 13 MAPQ, 14 the line index with unmapped reads, 15 the line filter's line index, 16 the insert estimate, 17 the mate tags' score kernel; 3-5, 7, 9-11, 13-15 and 17 are stages of the device tail (kTailStages), 16 is one too (fem_dev_estimate_insert counts it itself)
+constexpr int kTimedKernels = 19;  // fem_dev_kernel_time ids: 0 seed (join), 1 verify, 2 generic seed, 3-5 tail, 6 pack_results_kernel (round 5; the count kernel of rounds 1-2 before), 7 SAM text, 8 seed selection, 9 pairing, 10 mate rescue, 11 BAM records, 12 BGZF, 13 MAPQ, 14 the line index with unmapped reads, 15 the line filter's line index, 16 the insert estimate, 17 the mate tags' score kernel, 18 the fold index (XA:Z); 3-5, 7, 9-11, 13-15, 17 and 18 are stages of the device tail (kTailStages), 16 is one too (fem_dev_estimate_insert counts it itself)
 struct TimedLaunch {
   int kernel;
   hipEvent_t start, stop;
@@ -2126,9 +2126,10 @@ static const TailStage kTailStages[] = {
     {femt::kPairing, 9, [](const femt::LineOptions &o) { return o.paired; }},
     {femt::kRescue, 10, [](const femt::LineOptions &o) { return o.rescues(); }},
     {femt::kMapq, 13, [](const femt::LineOptions &o) { return o.mapq; }},  // (its events precede the text's sizing, which sam() and bam() wait for)
-    {femt::kUnmappedIndex, 14, [](const femt::LineOptions &o) { return o.unmapped && !o.filters(); }},  // (as do these)
+    {femt::kUnmappedIndex, 14, [](const femt::LineOptions &o) { return o.unmapped && !o.filters() && !o.folds(); }},  // (as do these)
     {femt::kFilterIndex, 15, [](const femt::LineOptions &o) { return o.filters(); }},  // (whose line index is the unmapped reads' too: no 14 then)
     {femt::kMateScore, 17, [](const femt::LineOptions &o) { return o.mates(); }},  // (a text with mate tags has its qualities on the device: tail_records)
+    {femt::kXaIndex, 18, [](const femt::LineOptions &o) { return o.folds(); }},  // (the line index it reads is made inside it where no filter is set: no 14, no 15 then)
 };
 
 // Timing: counts the stages of the slot's last fetch once each, with their device time where the tail has one.  text_id: the
@@ -2341,6 +2342,15 @@ int fem_dev_set_mate_tags(fem_dev *h, int slot, int on) {
 int fem_dev_set_sam_seq(fem_dev *h, int slot, int on) {
   return with_slot(h, slot, [&](Slot &s) { return s.opt.sam_seq = on != 0, (int)FEM_OK; });
 }
+
+int fem_dev_set_xa(fem_dev *h, int slot, int32_t max_entries) {
+  return with_slot(h, slot, [&](Slot &s) {
+    if (max_entries < 0) return fail(h, FEM_ERR_INVALID, "XA entry limit out of range (max_entries >= 1, or 0 for off)");
+    s.opt.xa_entries = max_entries;
+    return (int)FEM_OK;
+  });
+}
+int fem_dev_xa_count(fem_dev *h, int slot, uint64_t *n) { return line_count(h, slot, n, &femt::LineCounts::n_xa, false); }
 
 int fem_dev_set_report(fem_dev *h, int slot, const fem_report_params *rp) {
   return with_slot(h, slot, [&](Slot &s) {

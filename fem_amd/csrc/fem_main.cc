@@ -17,6 +17,8 @@
 // `--mate-tags` adds MC:Z, MQ:i and ms:i to every line of a paired output, made on the device (fem_dev_set_mate_tags).
 // `--sam-seq` prints SEQ reverse-complemented and QUAL reversed on the reverse-strand lines that carry them, as the SAM
 // specification orders them, made on the device (fem_dev_set_sam_seq).
+// `--xa[=N]` folds the secondary lines of a read (of a mate) into an XA:Z field on its primary line, at most N of them and
+// FEM_XA_MAX_BYTES bytes per line, made on the device (fem_dev_set_xa).
 #include <errno.h>
 #include <fcntl.h>
 #include <getopt.h>
@@ -97,6 +99,7 @@ void usage_map() {
   fprintf(stderr, "                      (implies --header), and every line gets RG:Z:<ID>\n");
   fprintf(stderr, "        --nh          write NH:i (the read's, or the mate's, lines in the output) and HI:i (which of them) on every mapped line\n");
   fprintf(stderr, "        --mate-tags   with --read2: write MC:Z, MQ:i and ms:i (the other mate's CIGAR, MAPQ and quality score, as samtools fixmate -m) on every line\n");
+  fprintf(stderr, "        --xa[=N]      fold a read's secondary lines into XA:Z:(rname,+-pos,CIGAR,NM;)* on its primary line, at most N (1-1000000; default: all that fit %d bytes); the rest stay lines\n", FEM_XA_MAX_BYTES);
   fprintf(stderr, "        --sam-seq     write SEQ reverse-complemented and QUAL reversed on reverse-strand lines (FLAG 0x10), as the SAM specification orders them\n");
   fprintf(stderr, "        -o       STR  Output SAM file \n\n");
 }
@@ -277,6 +280,7 @@ struct BatchBuf {  // everything about the batch that sits in one (GPU, slot) pa
   uint64_t n_rescued_discordant = 0;        // --rescue-discordant: those of pairs whose records did not pair
   uint64_t n_unmapped = 0;                  // --unmapped: lines for unmapped reads of the batch
   uint64_t n_filtered = 0;                  // --strata / --max-hits: lines left out of the batch's text
+  uint64_t n_xa = 0;                        // --xa: lines folded into XA:Z entries in the batch's text
   fem_batch_result res{};                   // per-candidate outcome (FEM_HOST_TAIL=1)
   double t_submit = 0;
   double t_slot = 0, t_filled = 0, t_submitted = 0, t_retired = 0, t_text = 0;  // FEM_STAGE_TIMES=2: the batch's way through the stages
@@ -323,6 +327,8 @@ int map_main(int argc, char **argv) {
   bool hit_tags = false;         // --nh: NH:i and HI:i on every mapped line, made on the device (fem_dev_set_tags)
   bool mate_tags = false;        // --mate-tags: MC:Z, MQ:i and ms:i on every line of a paired output, made on the device (fem_dev_set_mate_tags)
   bool sam_seq = false;          // --sam-seq: SEQ and QUAL of the lines with 0x10 in the reference's direction, made on the device (fem_dev_set_sam_seq)
+  long long xa_entries = 0;      // --xa[=N]: secondary lines folded into XA:Z on the primary line, made on the device (fem_dev_set_xa); 0: off
+  bool xa_given = false;
   fem_params params{12, 3, 2, 1};  // src/FEM_map.c:67-70: k and step are fixed, whatever the index header says
   int n_threads = 1, n_gpus = 1;
   // reads per batch: 250 k fills the pipeline soonest on small inputs; a batch costs three host round trips on its way through
@@ -345,6 +351,7 @@ int map_main(int argc, char **argv) {
                                      {"header", no_argument, nullptr, 'H'},      {"rg", required_argument, nullptr, 'T'},
                                      {"nh", no_argument, nullptr, 'n'},          {"mate-tags", no_argument, nullptr, 'M'},
                                      {"sam-seq", no_argument, nullptr, 'q'},
+                                     {"xa", optional_argument, nullptr, 'x'},
                                      {nullptr, 0, nullptr, 0}};
   int c, oi = 0;
   while ((c = getopt_long(argc, argv, short_opt, long_opt, &oi)) >= 0) {
@@ -354,6 +361,14 @@ int map_main(int argc, char **argv) {
       case 'n': hit_tags = true; break;
       case 'M': mate_tags = true; break;
       case 'q': sam_seq = true; break;
+      case 'x':
+        xa_given = true, xa_entries = 0x7FFFFFFFll;  // (alone: the byte budget bounds the folding)
+        if (optarg) {
+          char *end = nullptr;
+          xa_entries = strtoll(optarg, &end, 10);
+          if (!end || end == optarg || *end) xa_entries = -1;  // (not a number: refused below)
+        }
+        break;
       case 'r': ref_path = optarg; break;
       case 'i': index_path = optarg; break;
       case 'b': read_path = optarg; break;
@@ -445,6 +460,7 @@ int map_main(int argc, char **argv) {
   else if (bam_level == -2) bad = "Wrong BAM compression level (0-1).";
   else if (strata_given && (strata < 0 || strata > 15)) bad = "Wrong number of strata (0-15).";
   else if (max_hits_given && (max_hits < 1 || max_hits > 0x7FFFFFFFll)) bad = "Wrong hit limit (>= 1).";
+  else if (xa_given && xa_entries != 0x7FFFFFFFll && (xa_entries < 1 || xa_entries > 1000000)) bad = "Wrong number of --xa entries (1-1000000).";
   else if (!ref_path) bad = "Reference file path is required.";
   else if (!index_path) bad = "Index file path is required.";
   else if (!read_path) bad = "Read file path is required.";
@@ -491,6 +507,10 @@ int map_main(int argc, char **argv) {
     }
     if ((rg_arg || hit_tags) && x && x[0] == '1') {  // (nor tags)
       fprintf(stderr, "--rg and --nh are not supported with %s=1: the tags are made on the device, with its SAM text or BAM.\n", v);
+      exit(EXIT_FAILURE);
+    }
+    if (xa_given && x && x[0] == '1') {  // (nor XA:Z: the folding acts on the device's lines; FEM_HOST_QUALS=1 is served, XA stands behind QUAL)
+      fprintf(stderr, "--xa is not supported with %s=1: the secondary lines are folded on the device, with its SAM text or BAM.\n", v);
       exit(EXIT_FAILURE);
     }
     if ((strata_given || max_hits_given) && x && x[0] == '1') {  // (nor a line filter)
@@ -620,6 +640,7 @@ int map_main(int argc, char **argv) {
             rc = fem_dev_set_tags(devs[(size_t)g], sl, &tp);
           }
           if (!rc && sam_seq) rc = fem_dev_set_sam_seq(devs[(size_t)g], sl, 1);
+          if (!rc && xa_given) rc = fem_dev_set_xa(devs[(size_t)g], sl, (int32_t)xa_entries);
           if (!rc && paired) {
             const fem_pair_params pp{(int32_t)min_insert, (int32_t)max_insert};
             rc = fem_dev_set_pairs(devs[(size_t)g], sl, &pp);
@@ -813,7 +834,7 @@ int map_main(int argc, char **argv) {
   std::vector<TextOut> texts(3);
   for (TextOut &t : texts) text_free_q.push(&t);
   std::vector<uint64_t> per_gpu((size_t)n_gpus * 5, 0), per_gpu_proper((size_t)n_gpus, 0),
-      per_gpu_rescued((size_t)n_gpus, 0), per_gpu_rescued_disc((size_t)n_gpus, 0), per_gpu_unmapped((size_t)n_gpus, 0), per_gpu_filtered((size_t)n_gpus, 0);
+      per_gpu_rescued((size_t)n_gpus, 0), per_gpu_rescued_disc((size_t)n_gpus, 0), per_gpu_unmapped((size_t)n_gpus, 0), per_gpu_filtered((size_t)n_gpus, 0), per_gpu_xa((size_t)n_gpus, 0);
 
   // ---- writer (src/output_queue.c:60-91) ----
   std::thread writer([&] {
@@ -973,6 +994,7 @@ int map_main(int argc, char **argv) {
         if (!rc && rescue_discordant) rc = fem_dev_rescue_discordant_count(h, b->slot, &b->n_rescued_discordant);
         if (!rc && unmapped) rc = fem_dev_unmapped_count(h, b->slot, &b->n_unmapped);
         if (!rc && report) rc = fem_dev_filtered_count(h, b->slot, &b->n_filtered);
+        if (!rc && xa_given) rc = fem_dev_xa_count(h, b->slot, &b->n_xa);
         const double waited = real_time() - t0;
         b->t_retired = t0 + waited;
         double placing = 0;
@@ -1012,6 +1034,7 @@ int map_main(int argc, char **argv) {
           if (paired) per_gpu_rescued_disc[(size_t)g] += b->n_rescued_discordant;
           per_gpu_unmapped[(size_t)g] += b->n_unmapped;
           per_gpu_filtered[(size_t)g] += b->n_filtered;
+          per_gpu_xa[(size_t)g] += b->n_xa;
           if (device_text) {
             n_asserted += b->sam.n_asserted;
             write_q.push(WriteItem{nullptr, b});
@@ -1360,6 +1383,11 @@ int map_main(int argc, char **argv) {
     uint64_t n_filtered = 0;
     for (uint64_t x : per_gpu_filtered) n_filtered += x;
     fprintf(stderr, "The number of filtered lines: %lu\n", (unsigned long)n_filtered);
+  }
+  if (xa_given) {
+    uint64_t n_xa = 0;
+    for (uint64_t x : per_gpu_xa) n_xa += x;
+    fprintf(stderr, "The number of XA entries: %lu\n", (unsigned long)n_xa);
   }
   fprintf(stderr, "Time: %fs\n", t_mapping);
   return 0;

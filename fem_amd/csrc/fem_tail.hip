@@ -1154,6 +1154,9 @@ struct SamParams {
   // SEQ and QUAL as SAM orders them (fem_dev_set_sam_seq): a line whose FLAG as written has 0x10 and that carries
   // SEQ prints the read's reverse complement and its qualities reversed (the write kernels alone: no length changes)
   uint32_t sam_seq;             // != 0: on
+  // secondary lines folded into XA:Z (fem_dev_set_xa; nullptr: off; the kUnm instances alone read them).  By slot:
+  // slot s's first line after folding is line xa_begin[s] and carries xa_n[s] entries of xa_bytes[s] bytes (both 0: no tag)
+  const uint32_t *xa_begin, *xa_n, *xa_bytes;
 };
 
 // The complement of the letter kSamSeqLut prints: =ACMGRSVTWYHKDBN -> =TGKCYSBAWRDMHVN, the 4-bit BAM code with its bits reversed
@@ -1278,10 +1281,18 @@ __device__ __forceinline__ uint32_t seq_qual_len(const SamParams &p, uint32_t L)
 struct HitTags {
   uint32_t nh, hi;
 };
-template <bool kPair>
+// kUnm with folding (p.xa_n): the numbers are those of the index before folding.  A folded line is still a reported hit, and the folded
+// ones are the slot's lines 2 .. xa_n + 1, so the slot's count and the place of every line behind its first grow by xa_n.
+template <bool kPair, bool kUnm = false>
 __device__ __forceinline__ HitTags hit_tags(const SamParams &p, uint32_t line, uint32_t src, uint32_t r) {
   const uint32_t s = kPair ? pair_slot(p, r) : r, b = p.hit_begin[s];
-  return {p.hit_begin[s + 1] - b, (p.hit_by_line ? line : src) - b + 1u};
+  HitTags h{p.hit_begin[s + 1] - b, (p.hit_by_line ? line : src) - b + 1u};
+  if (kUnm && p.xa_n) {
+    const uint32_t x = p.xa_n[s];
+    h.nh += x;
+    if (h.hi > 1u) h.hi += x;
+  }
+  return h;
 }
 // SAM: "\tNH:i:<n>\tHI:i:<i>" and "\tRG:Z:<ID>"
 __device__ __forceinline__ uint32_t hit_tags_len(const HitTags &h) { return 12u + dec_digits(h.nh) + dec_digits(h.hi); }
@@ -1290,6 +1301,18 @@ __device__ __forceinline__ uint32_t rg_tag_len(const SamParams &p) { return p.rg
 __device__ __forceinline__ uint32_t bam_tags_len(const SamParams &p, bool mapped) {
   return (mapped && p.hit_tags ? 14u : 0u) + (p.rg_len ? 4u + p.rg_len : 0u);
 }
+
+// ---- XA:Z (include/fem_hip.h, fem_dev_set_xa): the last field of a folding slot's first line ----
+// The bytes of the entries that output line `line`, a line of read r, carries: its slot's where the line is the slot's first, else 0
+template <bool kPair>
+__device__ __forceinline__ uint32_t xa_bytes_at(const SamParams &p, uint32_t line, uint32_t r) {
+  if (!p.xa_n) return 0u;
+  const uint32_t s = kPair ? pair_slot(p, r) : r;
+  return p.xa_begin[s] == line ? p.xa_bytes[s] : 0u;
+}
+// SAM: "\tXA:Z:" and the entries; BAM: 'X' 'A' 'Z', the entries and a NUL
+__device__ __forceinline__ uint32_t sam_xa_len(uint32_t entry_bytes) { return entry_bytes ? 6u + entry_bytes : 0u; }
+__device__ __forceinline__ uint32_t bam_xa_len(uint32_t entry_bytes) { return entry_bytes ? 4u + entry_bytes : 0u; }
 
 // ---- the mate tags (include/fem_hip.h, fem_dev_set_mate_tags): MC:Z MQ:i ms:i, the last fields of every line of a
 //      paired text ----
@@ -1371,7 +1394,8 @@ __global__ void __launch_bounds__(256) sam_len_kernel(SamParams p) {
     const uint32_t seq_qual = primary ? seq_qual_len(p, L) : 3u;
     const uint32_t mate = kPair ? mate_cols_len(p, mate_cols<kUnm>(p, j, r), t) : 5u;
     const uint32_t mq = line_mapq<kPair>(p, j, r, primary);
-    const uint32_t tags = (p.hit_tags ? hit_tags_len(hit_tags<kPair>(p, i, j, r)) : 0u) + rg_tag_len(p) + (kMate ? mates(r) : 0u);
+    const uint32_t tags = (p.hit_tags ? hit_tags_len(hit_tags<kPair, kUnm>(p, i, j, r)) : 0u) + rg_tag_len(p) + (kMate ? mates(r) : 0u) +
+                          (kUnm ? sam_xa_len(xa_bytes_at<kPair>(p, i, r)) : 0u);
     p.line_len[i] = (unsigned long long)name_len + 1u + dec_digits(flag & 0x7FFFu) + 1u + rname_len + 1u + dec_digits(p.pos0[rec] + 1u) + 2u +
                     dec_digits(mq) + cig + 2u + mate + seq_qual + 6u + dec_digits(p.nm[rec]) + 6u + md_len + tags + 1u;
   }
@@ -1459,7 +1483,7 @@ __global__ void __launch_bounds__(256) sam_write_kernel(SamParams p) {
   const uint32_t o_md = kUnm && unm ? o_tags : o_nm + dec_digits(nm) + 6u;
   const bool hits = p.hit_tags && !(kUnm && unm);
   HitTags ht{};
-  if (hits) ht = hit_tags<kPair>(p, j, src, r);
+  if (hits) ht = hit_tags<kPair, kUnm>(p, j, src, r);
   const uint32_t o_hit = o_md + md_len;
   const uint32_t o_rg = o_hit + (hits ? hit_tags_len(ht) : 0u);
   const uint32_t o_mate = o_rg + rg_tag_len(p);
@@ -1480,7 +1504,8 @@ __global__ void __launch_bounds__(256) sam_write_kernel(SamParams p) {
     }
     mate_len = mate_tags_len(mt, mcig);
   }
-  const uint32_t o_end = o_mate + mate_len;
+  // (the room of a folding slot's XA:Z lies in front of the newline: xa_write_kernel fills it)
+  const uint32_t o_end = o_mate + mate_len + (kUnm && !unm ? sam_xa_len(xa_bytes_at<kPair>(p, j, r)) : 0u);
   if (mine) {  // the short fields of the lane's own record
     uint8_t *w = p.text + at;
     w[name_len] = '\t';
@@ -1710,7 +1735,8 @@ __global__ void __launch_bounds__(256) bam_len_kernel(SamParams p, uint32_t n_re
     if (flag & 0x8000u) atomicAdd(p.asserted, 1u);
     const uint32_t n_ops = p.cigar_off[rec + 1] - p.cigar_off[rec], md_len = p.md_off[rec + 1] - p.md_off[rec];
     const uint32_t ls = primary ? L : 0u;
-    p.line_len[i] = 36ull + name_len + 1u + 4u * n_ops + (ls + 1u) / 2u + ls + 4u + 4u + md_len + bam_tags_len(p, true) + (kMate ? mates(r) : 0u);
+    p.line_len[i] = 36ull + name_len + 1u + 4u * n_ops + (ls + 1u) / 2u + ls + 4u + 4u + md_len + bam_tags_len(p, true) + (kMate ? mates(r) : 0u) +
+                    (kUnm ? bam_xa_len(xa_bytes_at<kPair>(p, i, r)) : 0u);
   }
 }
 
@@ -1821,7 +1847,7 @@ __global__ void __launch_bounds__(256) bam_write_kernel(SamParams p) {
     for (uint32_t k = ln; k <= md_len; k += 64u) x[k] = k < md_len ? md[k] : 0;
     x += md_len + 1u;
     if (p.hit_tags) {  // NH:I HI:I, lane k byte k of the fourteen
-      const HitTags ht = hit_tags<kPair>(p, j, src, r);
+      const HitTags ht = hit_tags<kPair, kUnm>(p, j, src, r);
       if (ln < 14u) {
         const uint32_t b = ln < 7u ? ln : ln - 7u, v = ln < 7u ? ht.nh : ht.hi;
         x[ln] = b < 3u ? (uint8_t)(ln < 7u ? "NHI" : "HII")[b] : (uint8_t)(v >> (8u * (b - 3u)));
@@ -2524,6 +2550,173 @@ __global__ void __launch_bounds__(256) report_kernel(ReportParams p) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Secondary lines folded into XA:Z (fem_dev_set_xa).  Behind report_kernel's index (which runs with both of its
+// tests off where the line filter is off): slot s has the lines usrc[begin[s] .. begin[s + 1]), the first one its primary line or
+// an unmapped read's.  The entry of line t >= 1 is <RNAME>,<+-><POS>,<CIGAR>,<NM>; with the bytes its line prints; f = the
+// largest f <= min(c - 1, N) whose entries 1 .. f have at most FEM_XA_MAX_BYTES bytes together.  The lengths' running sum grows
+// with t, so f is the number of lines t <= N whose sum fits, with no sequential stop.
+// xa_index_kernel<false>: per slot the lines that stay (c - f), f, whether it folds, and the entries' bytes; an exclusive scan of
+// the three counts (rocPRIM, one pass); xa_index_kernel<true>: the lines that stay into the new index, the folded ones in slot
+// order into xsrc, the folding slots into a list, 0x8000 among the folded records into the text's count of them.
+// A slot of up to kReportAlone lines is its lane's; a larger one is taken by the whole wave after the lanes' own, 64 lines per
+// step: a scan of the lengths by shuffles, the sum so far carried from step to step (the same in every lane).
+// xa_write_kernel: a wave per folding slot (from the list), lane i entry i of 64 per step at the sum of the lengths in front of it.
+// ---------------------------------------------------------------------------------------------------------
+struct XaParams {
+  uint32_t n_reads;
+  uint32_t max_entries;      // N
+  const uint32_t *begin;     // n_reads + 1, by slot: report_kernel's scan
+  const uint32_t *usrc;      // report_kernel's index
+  uint32_t *cnt;             // 3 (n_reads + 1): the lines that stay, the entries, 1 for a folding slot (the last of each zero)
+  uint32_t *bytes;           // n_reads + 1: the entries' bytes
+  const uint32_t *scan;      // 3 (n_reads + 1): the exclusive scans of cnt's parts
+  uint32_t *usrc_out;        // the index after folding
+  uint32_t *xsrc;            // the folded lines' sources, slot s's from scan[n1 + s] on
+  uint32_t *xlist;           // the folding slots
+  uint32_t *n_lines;         // [0] the lines after folding, [2] the entries, [3] the folding slots
+};
+
+// An entry's source as the line kernels resolve a line's: the record, and the FLAG as written (0x8000 kept)
+struct XaSource {
+  uint32_t rec, flag;
+};
+__device__ __forceinline__ XaSource xa_source(const SamParams &p, uint32_t src) {
+  const uint32_t rec = p.perm ? p.perm[src] : src;
+  return {rec, p.perm ? p.pflag[src] : p.flag[rec]};
+}
+__device__ __forceinline__ uint32_t xa_entry_len(const SamParams &p, uint32_t src) {
+  const uint32_t rec = p.perm ? p.perm[src] : src, t = p.tid[rec];
+  const uint32_t c0 = p.cigar_off[rec], n_ops = p.cigar_off[rec + 1] - c0;
+  return p.ref_name_off[t + 1] - p.ref_name_off[t] + dec_digits(p.pos0[rec] + 1u) + (n_ops ? cigar_chars(p, c0, n_ops) : 1u) + dec_digits(p.nm[rec]) + 5u;
+}
+// The inclusive sum of v over the lanes up to this one
+__device__ __forceinline__ uint32_t wave_scan32(uint32_t v, uint32_t ln) {
+  for (uint32_t o = 1; o < 64u; o <<= 1) {
+    const uint32_t below = __shfl_up(v, o);
+    if (ln >= o) v += below;
+  }
+  return v;
+}
+
+template <bool kWrite>
+__global__ void __launch_bounds__(256) xa_index_kernel(SamParams p, XaParams x) {
+  constexpr uint32_t kOver = FEM_XA_MAX_BYTES + 1u;  // (a length or a sum above the budget counts as this: no sum leaves 32 bits)
+  const uint32_t ln = threadIdx.x & 63u, n1 = x.n_reads + 1u;
+  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = s < x.n_reads;
+  uint32_t b0 = 0, c = 0, f = 0, bytes = 0, at = 0, xat = 0;
+  if (live) b0 = x.begin[s], c = x.begin[s + 1] - b0;
+  if (kWrite && live) f = x.cnt[n1 + s], at = x.scan[s], xat = x.scan[n1 + s];
+  if (kWrite && s == 0) x.n_lines[0] = x.scan[x.n_reads], x.n_lines[2] = x.scan[n1 + x.n_reads], x.n_lines[3] = x.scan[2u * n1 + x.n_reads];
+  const bool big = c > kReportAlone;
+  if (live && !big && c) {
+    if (kWrite) {
+      x.usrc_out[at] = x.usrc[b0];
+      for (uint32_t t = 1; t < c; ++t) {
+        const uint32_t src = x.usrc[b0 + t];
+        if (t <= f) {
+          x.xsrc[xat + t - 1u] = src;
+          if (xa_source(p, src).flag & 0x8000u) atomicAdd(p.asserted, 1u);
+        } else {
+          x.usrc_out[at + t - f] = src;
+        }
+      }
+    } else {
+      for (uint32_t t = 1; t < c && t <= x.max_entries; ++t) {
+        const uint32_t len = xa_entry_len(p, x.usrc[b0 + t]);
+        if (len > FEM_XA_MAX_BYTES - bytes) break;
+        bytes += len, ++f;
+      }
+    }
+  }
+  uint64_t todo = __ballot(big);
+  while (todo) {
+    const uint32_t from = (uint32_t)__builtin_ctzll(todo);
+    todo &= todo - 1u;
+    const uint32_t B0 = wave_bcast(b0, from), C = wave_bcast(c, from);
+    if (kWrite) {
+      const uint32_t F = wave_bcast(f, from), AT = wave_bcast(at, from), XAT = wave_bcast(xat, from);
+      for (uint32_t t = ln; t < C; t += 64u) {
+        const uint32_t src = x.usrc[B0 + t];
+        if (t >= 1u && t <= F) {
+          x.xsrc[XAT + t - 1u] = src;
+          if (xa_source(p, src).flag & 0x8000u) atomicAdd(p.asserted, 1u);
+        } else {
+          x.usrc_out[AT + (t ? t - F : 0u)] = src;
+        }
+      }
+    } else {
+      uint32_t F = 0, sum = 0;  // (the same in every lane)
+      for (uint32_t t0 = 1; t0 < C; t0 += 64u) {
+        const uint32_t t = t0 + ln;
+        const bool in = t < C && t <= x.max_entries;
+        uint32_t len = in ? xa_entry_len(p, x.usrc[B0 + t]) : kOver;
+        len = len < kOver ? len : kOver;
+        const uint32_t upto = sum + wave_scan32(len, ln);  // (at most 65 kOver)
+        const uint32_t n_ok = (uint32_t)__builtin_popcountll(__ballot(in && upto <= FEM_XA_MAX_BYTES));  // (the lanes 0 .. n_ok - 1: the sums grow)
+        if (n_ok) sum = wave_bcast(upto, n_ok - 1u);
+        F += n_ok;
+        if (n_ok < 64u) break;
+      }
+      if (ln == from) f = F, bytes = sum;
+    }
+  }
+  if (kWrite) {
+    if (live && f) x.xlist[x.scan[2u * n1 + s]] = s;
+    return;
+  }
+  if (s <= x.n_reads) {
+    x.cnt[s] = c - f, x.cnt[n1 + s] = f, x.cnt[2u * n1 + s] = f ? 1u : 0u;
+    x.bytes[s] = bytes;
+  }
+}
+
+// kBam: the tag as a BAM aux field ('X' 'A' 'Z', the entries, a NUL) at the record's end; else "\tXA:Z:" and the entries in front of
+// the line's newline.  line_off: the text's, from the scan of the lengths that took the tag into account (sam_xa_len, bam_xa_len).
+template <bool kBam>
+__global__ void __launch_bounds__(256) xa_write_kernel(SamParams p, XaParams x, uint32_t n_slots) {
+  const uint32_t ln = threadIdx.x & 63u, n1 = x.n_reads + 1u;
+  const uint32_t w = blockIdx.x * 4u + (threadIdx.x >> 6);
+  if (w >= n_slots) return;
+  const uint32_t s = x.xlist[w], f = x.cnt[n1 + s], xat = x.scan[n1 + s], bytes = x.bytes[s];
+  uint8_t *tag = p.text + p.line_off[x.scan[s] + 1u] - 1u - bytes;  // the first entry's first byte (behind it: the newline, or the NUL)
+  if (kBam) {
+    if (ln < 3u) tag[(int)ln - 3] = (uint8_t)"XAZ"[ln];
+    if (ln == 3u) tag[bytes] = 0;
+  } else {
+    if (ln < 6u) tag[(int)ln - 6] = (uint8_t)"\tXA:Z:"[ln];
+  }
+  uint32_t done = 0;  // bytes of the entries in front of this step's (the same in every lane)
+  for (uint32_t i0 = 0; i0 < f; i0 += 64u) {
+    const uint32_t i = i0 + ln;
+    const bool in = i < f;
+    uint32_t len = 0, rec = 0, flag = 0, t = 0, c0 = 0, n_ops = 0;
+    if (in) {
+      const uint32_t src = x.xsrc[xat + i];
+      const XaSource e = xa_source(p, src);
+      rec = e.rec, flag = e.flag, t = p.tid[rec];
+      c0 = p.cigar_off[rec], n_ops = p.cigar_off[rec + 1] - c0;
+      len = xa_entry_len(p, src);
+    }
+    const uint32_t upto = wave_scan32(len, ln);
+    if (in) {
+      uint8_t *q = tag + done + upto - len;
+      for (uint32_t k = p.ref_name_off[t]; k < p.ref_name_off[t + 1]; ++k) *q++ = p.ref_names[k];
+      *q++ = ',';
+      *q++ = (flag & 16u) ? '-' : '+';
+      q = put_dec(q, p.pos0[rec] + 1u);
+      *q++ = ',';
+      if (!n_ops) *q++ = '*';
+      for (uint32_t k = c0; k < c0 + n_ops; ++k) q = put_cigar_op(q, p.cigar[k]);
+      *q++ = ',';
+      q = put_dec(q, p.nm[rec]);
+      *q = ';';
+    }
+    done += wave_bcast(upto, 63u);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // Mate rescue (include/fem_hip.h).  A pair where exactly one mate (B) has no record: its other mate's first
 // kRescueAnchors records without 0x8000 are the anchors, and B's pos0 is searched in each anchor's insert window at E edits:
 // tiles c = lo + j (2E + 1), each the banded Myers of fo_banded_ed32 over ref[c, c + L + 2E) (first strict minimum, the same
@@ -2899,7 +3092,7 @@ static hipError_t copy_home(PinBuf<T> &dst, const DevBuf<S> &src, size_t first, 
 }
 
 // The words of h_ctl, the pinned buffer the kernels' counters come home in: 0 .. 3 run()'s ctl (2: a text's asserted records,
-// 3: bam()'s name check), 4 5 run()'s CIGAR and MD totals, 6 7 a text's size, 8 9 a line index's counts, from kCtlInsert on
+// 3: bam()'s name check), 4 5 run()'s CIGAR and MD totals, 6 7 a text's size, 8 9 a line index's counts, 10 11 the fold index's (entries, folding slots), from kCtlInsert on
 // estimate_insert()'s kInsertCtl words (estimate_library(): three times as many).
 constexpr size_t kCtlInsert = 12, kCtlWords = kCtlInsert + 3 * kInsertCtl;
 
@@ -2924,6 +3117,11 @@ struct Tail::Impl {
   // lines for unmapped reads (LineOptions::unmapped): the marks, their scan, each line's source, the line count
   // (the line filter, LineOptions::strata / max_hits, uses the same four: its counts, their scan, the sources, the line count)
   DevBuf<uint32_t> u_cnt, u_before, usrc, u_ctl;
+  // XA:Z (LineOptions::xa_entries): the slots' three counts and their scans, the entries' bytes, the index after folding, the folded
+  // lines' sources, the folding slots; what the last text's write kernel takes of them
+  DevBuf<uint32_t> x_cnt, x_scan, x_bytes, x_usrc, x_src, x_list;
+  DevBuf<uint8_t> x_scan_tmp;
+  XaParams xa{};
   // the RG tag (LineOptions::read_group): the ID on the device, the pinned copy it came from, and what that holds
   DevBuf<uint8_t> rg;
   PinBuf<uint8_t> h_rg;
@@ -2958,6 +3156,8 @@ struct Tail::Impl {
   uint32_t n_unm = 0;                // lines for unmapped reads in the last text
   uint32_t n_base_last = 0;          // the lines the last text had before the filter and without the unmapped reads'
   uint32_t n_filtered = 0;           // lines the filter left out of the last text
+  bool folded = false;               // the last text went through the fold index (LineOptions::xa_entries)
+  uint32_t n_xa = 0, n_xa_slots = 0; // lines folded into XA:Z entries in the last text, and the slots that carry them
   Span span[kStages];                // (Tail::stage_ms)
   femb::Event ev_text;               // the SAM text has arrived in h_text
 
@@ -2990,6 +3190,16 @@ struct Tail::Impl {
     if (e == hipSuccess) e = r_scan_tmp.ensure(need);
     return e != hipSuccess ? e : scan(lens, offs, zero, p1, TriplePlus(), stream, &r_scan_tmp);
   }
+  // XA:Z: (lines that stay, entries, folding slots) of n1 slots, the three parts of x_cnt, into those of x_scan
+  hipError_t scan_folds(size_t n1, hipStream_t stream) {
+    auto lens = rocprim::make_zip_iterator(rocprim::make_tuple(x_cnt.get(), x_cnt + n1, x_cnt + 2 * n1));
+    auto offs = rocprim::make_zip_iterator(rocprim::make_tuple(x_scan.get(), x_scan + n1, x_scan + 2 * n1));
+    const auto zero = rocprim::make_tuple(0u, 0u, 0u);
+    size_t need = 16;
+    hipError_t e = scan_need(&need, lens, offs, zero, n1, TriplePlus());
+    if (e == hipSuccess) e = x_scan_tmp.ensure(need);
+    return e != hipSuccess ? e : scan(lens, offs, zero, n1, TriplePlus(), stream, &x_scan_tmp);
+  }
   // The records as pair_kernel reads them ...
   template <class P>
   void bind_pairing(P *p) const {
@@ -3019,7 +3229,8 @@ struct Tail::Impl {
   // stage kText (stage kMateScore); without them the lines carry no ms.
   int lines(const TailInput &in, const SamInput &names, const LineOptions &opt, uint32_t *bad_name, hipStream_t stream, int n_cu,
             SamParams *p, std::string *err) {
-    const bool pair_order = opt.paired, report = opt.filters();
+    // (folding reads report_kernel's index: without the line filter that kernel runs with both of its tests off and keeps every line)
+    const bool pair_order = opt.paired, fold = opt.folds(), report = opt.filters() || fold;
     if (pair_order && !paired) {
       if (err) *err = "the records were not paired (Tail::pair)";
       return FEM_ERR_STATE;
@@ -3031,7 +3242,7 @@ struct Tail::Impl {
     }
     const uint32_t nr = n_base + (opt.unmapped ? last_n : 0u);
     const size_t r1 = (size_t)nr + 1, n1 = (size_t)last_n + 1;
-    not_run({kText, kMapq, kUnmappedIndex, kFilterIndex, kMateScore});
+    not_run({kText, kMapq, kUnmappedIndex, kFilterIndex, kMateScore, kXaIndex});
     TAIL_TRY(line_len.ensure(r1));
     TAIL_TRY(line_off.ensure(r1));
     TAIL_TRY(h_ctl.ensure(kCtlWords));
@@ -3074,6 +3285,7 @@ struct Tail::Impl {
     }
     n_unm = 0;
     filtered = report, um_kernels = opt.unmapped || report, n_filtered = 0, n_base_last = n_base;
+    folded = fold, n_xa = n_xa_slots = 0;
     if (report) {
       ReportParams f{};
       f.n_reads = last_n, f.n_base = n_base, f.begin = pair_order ? pair_begin : rec_begin;
@@ -3082,17 +3294,38 @@ struct Tail::Impl {
       f.unmapped = opt.unmapped ? 1u : 0u;
       f.cnt = u_cnt, f.before = u_before, f.usrc = usrc, f.n_lines = u_ctl;
       const dim3 grid((last_n + 256u) / 256u);
-      TAIL_TRY(span[kFilterIndex].begin(stream));
+      Span &index = opt.filters() ? span[kFilterIndex] : span[kXaIndex];
+      TAIL_TRY(index.begin(stream));
       TAIL_TRY(hipMemsetAsync(u_ctl, 0, 8, stream));
       hipLaunchKernelGGL(report_kernel<false>, grid, dim3(256), 0, stream, f);
       TAIL_TRY(hipGetLastError());
       TAIL_TRY(scan(u_cnt.get(), u_before.get(), 0u, n1, rocprim::plus<uint32_t>(), stream));
       hipLaunchKernelGGL(report_kernel<true>, grid, dim3(256), 0, stream, f);
       TAIL_TRY(hipGetLastError());
-      TAIL_TRY(span[kFilterIndex].end(stream));
-      TAIL_TRY(hipMemcpyAsync(h_ctl + 8, u_ctl, 8, hipMemcpyDeviceToHost, stream));
+      if (opt.filters()) TAIL_TRY(index.end(stream));
       p->usrc = usrc, p->u_base = opt.unmapped ? n_base : kNoMate, p->n_reads = last_n, p->u_lines = u_ctl;
       p->pair_begin = opt.unmapped ? pair_begin : nullptr;
+      if (fold) {  // (the entries read the records' arrays alone: *p holds what xa_index_kernel needs by now)
+        TAIL_TRY(x_cnt.ensure(3 * n1));
+        TAIL_TRY(x_scan.ensure(3 * n1));
+        TAIL_TRY(x_bytes.ensure(n1));
+        TAIL_TRY(x_usrc.ensure(std::max<size_t>(nr, 1)));
+        TAIL_TRY(x_src.ensure(std::max<size_t>(nr, 1)));
+        TAIL_TRY(x_list.ensure(n1));
+        xa = XaParams{};
+        xa.n_reads = last_n, xa.max_entries = (uint32_t)opt.xa_entries, xa.begin = u_before, xa.usrc = usrc;
+        xa.cnt = x_cnt, xa.bytes = x_bytes, xa.scan = x_scan, xa.usrc_out = x_usrc, xa.xsrc = x_src, xa.xlist = x_list, xa.n_lines = u_ctl;
+        if (opt.filters()) span[kXaIndex].follow(span[kFilterIndex]);
+        hipLaunchKernelGGL(xa_index_kernel<false>, grid, dim3(256), 0, stream, *p, xa);
+        TAIL_TRY(hipGetLastError());
+        TAIL_TRY(scan_folds(n1, stream));
+        hipLaunchKernelGGL(xa_index_kernel<true>, grid, dim3(256), 0, stream, *p, xa);
+        TAIL_TRY(hipGetLastError());
+        TAIL_TRY(span[kXaIndex].end(stream));
+        p->usrc = x_usrc, p->xa_begin = x_scan, p->xa_n = x_cnt + n1, p->xa_bytes = x_bytes;
+        if (opt.hit_tags) p->hit_begin = x_scan;
+      }
+      TAIL_TRY(hipMemcpyAsync(h_ctl + 8, u_ctl, fold ? 16 : 8, hipMemcpyDeviceToHost, stream));
     } else if (opt.unmapped) {
       UlineParams u{};
       u.n_reads = last_n, u.n_base = n_base, u.paired = pair_order ? 1u : 0u;
@@ -3168,7 +3401,8 @@ struct Tail::Impl {
     if (filtered) {  // (what the filter kept, the unmapped reads' lines among them)
       const uint32_t n_lines = std::min(h_ctl[8], p->n_records);
       n_unm = opt.unmapped ? std::min(h_ctl[9], n_lines) : 0u;
-      n_filtered = n_base_last + n_unm - n_lines;
+      if (folded) n_xa = std::min(h_ctl[10], n_base_last), n_xa_slots = std::min(h_ctl[11], std::min(n_xa, n_lines));
+      n_filtered = n_base_last + n_unm - n_lines - n_xa;
       p->n_records = n_lines;
     } else if (opt.unmapped) {
       const uint32_t n_lines = std::min(h_ctl[8], p->n_records);
@@ -3286,7 +3520,8 @@ int Tail::warm(hipStream_t stream, std::string *err) {
                            (const void *)insert_sample_kernel, (const void *)library_sample_kernel, (const void *)insert_bounds_kernel,
                            (const void *)mate_score_kernel, (const void *)sam_len_kernel<true, false, true>,
                            (const void *)sam_write_kernel<true, false, true>, (const void *)sam_len_kernel<true, true, true>,
-                           (const void *)sam_write_kernel<true, true, true>};
+                           (const void *)sam_write_kernel<true, true, true>, (const void *)xa_index_kernel<false>,
+                           (const void *)xa_index_kernel<true>, (const void *)xa_write_kernel<false>, (const void *)xa_write_kernel<true>};
   for (const void *k : kernels) TAIL_TRY(hipFuncGetAttributes(&a, k));
   if (!m.scan_tmp || !m.rec_begin || !m.n_ops || !m.line_len) return FEM_OK;  // (nothing reserved: the scans load with the first batch)
   TAIL_TRY(hipMemsetAsync(m.n_ops, 0, 4, stream));
@@ -3498,6 +3733,10 @@ int Tail::sam(const TailInput &in, const SamInput &names, const LineOptions &opt
     const uint32_t blocks = (nr + 255u) / 256u;  // a wave per 64 records
     hipLaunchKernelGGL(TEXT_KERNEL(sam_write_kernel, opt.paired, m.um_kernels, opt.mates()), dim3(blocks), dim3(256), 0, stream, p);
     TAIL_TRY(hipGetLastError());
+    if (m.n_xa_slots) {
+      hipLaunchKernelGGL(xa_write_kernel<false>, dim3((m.n_xa_slots + 3u) / 4u), dim3(256), 0, stream, p, m.xa, m.n_xa_slots);
+      TAIL_TRY(hipGetLastError());
+    }
   }
   TAIL_TRY(m.span[kText].end(stream));
   rc = m.send_home(m.text, (size_t)total, m.h_qual_at, m.qual_at, hole ? n_reads1 * 8 : 0, stream, wait, gate, err);
@@ -3536,6 +3775,10 @@ int Tail::bam(const TailInput &in, const SamInput &names, const LineOptions &opt
     p.text = m.text;
     hipLaunchKernelGGL(TEXT_KERNEL(bam_write_kernel, opt.paired, m.um_kernels, opt.mates()), dim3((nr + 3u) / 4u), dim3(256), 0, stream, p);
     TAIL_TRY(hipGetLastError());
+    if (m.n_xa_slots) {
+      hipLaunchKernelGGL(xa_write_kernel<true>, dim3((m.n_xa_slots + 3u) / 4u), dim3(256), 0, stream, p, m.xa, m.n_xa_slots);
+      TAIL_TRY(hipGetLastError());
+    }
   }
   TAIL_TRY(m.span[kText].end(stream));
   femz::bgzf_cut(m.h_line_off, nr, total, &m.cuts);
@@ -3759,7 +4002,7 @@ LineCounts Tail::counts() const {
   if (!impl_) return c;
   const Impl &m = *impl_;
   if (m.paired) c.n_proper = m.h_pair_ctl ? m.h_pair_ctl[0] : 0, c.n_rescued = m.n_resc, c.n_rescued_discordant = m.n_resc_disc;
-  c.n_unmapped = m.n_unm, c.n_filtered = m.n_filtered;
+  c.n_unmapped = m.n_unm, c.n_filtered = m.n_filtered, c.n_xa = m.n_xa;
   return c;
 }
 

@@ -125,7 +125,9 @@ struct LineOptions {
   bool hit_tags = false;           // NH:i and HI:i on every mapped line
   bool mate_tags = false;          // MC:Z MQ:i ms:i on every line of a paired text (mate_score_kernel; the kernels' kMate instances)
   bool sam_seq = false;            // SEQ reverse-complemented and QUAL reversed on the lines with 0x10 that carry them (the write kernels)
+  int32_t xa_entries = 0;          // secondary lines folded into XA:Z on the slot's first line, at most this many per slot; 0: off (xa_index_kernel, xa_write_kernel)
   bool filters() const { return strata >= 0 || max_hits >= 1; }  // the line filter is on
+  bool folds() const { return xa_entries > 0; }
   bool rescues() const { return paired && rescue; }
   bool mates() const { return paired && mate_tags; }
   // the mates' flips as the kernels take them: 16 where the mate's strand is flipped (FR 0 0, RF 16 16, FF 0 16)
@@ -139,6 +141,7 @@ struct LineCounts {
   uint64_t n_rescued_discordant = 0;  // ... those of pairs with records on both sides (0 without LineOptions::rescue_discordant)
   uint64_t n_unmapped = 0;            // lines for unmapped reads (0 without LineOptions::unmapped)
   uint64_t n_filtered = 0;            // lines the filter left out (0 without LineOptions::strata / max_hits)
+  uint64_t n_xa = 0;                  // lines folded into XA:Z entries (0 without LineOptions::xa_entries)
 };
 
 // What estimate_insert() learns from the unique pairs of the last run() (include/fem_hip.h, fem_dev_estimate_insert: the rule).
@@ -168,8 +171,10 @@ struct TextGate {
 // anybody asks (Tail::stage_ms).  run(): kOrder, kTrace, kCompact.  pair(): kRescue when it rescues, kPairing.  sam() / bam():
 // kMapq with LineOptions::mapq; kFilterIndex, the line index with the line filter, or else kUnmappedIndex, the one with
 // LineOptions::unmapped alone; kMateScore, mate_score_kernel with LineOptions::mate_tags on a batch with device qualities;
-// kText, the SAM text's or the BAM records' kernels.  estimate_insert() and estimate_library(): kInsert.
-enum Stage { kOrder, kTrace, kCompact, kText, kPairing, kRescue, kMapq, kUnmappedIndex, kFilterIndex, kInsert, kMateScore, kStages };
+// kText, the SAM text's or the BAM records' kernels (xa_write_kernel among them); kXaIndex with LineOptions::xa_entries, the fold index
+// behind the line index (and the line index itself where the line filter is off: report_kernel with nothing to leave out).
+// estimate_insert() and estimate_library(): kInsert.
+enum Stage { kOrder, kTrace, kCompact, kText, kPairing, kRescue, kMapq, kUnmappedIndex, kFilterIndex, kInsert, kMateScore, kXaIndex, kStages };
 
 class Tail {
  public:

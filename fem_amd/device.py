@@ -24,6 +24,7 @@ ABI_SYMBOLS = [
     "fem_dev_set_rescue", "fem_dev_rescue_count", "fem_dev_set_rescue_discordant", "fem_dev_rescue_discordant_count", "fem_dev_set_mapq",
     "fem_dev_set_unmapped", "fem_dev_unmapped_count",
     "fem_dev_set_report", "fem_dev_filtered_count", "fem_dev_set_tags", "fem_dev_set_mate_tags", "fem_dev_set_sam_seq",
+    "fem_dev_set_xa", "fem_dev_xa_count",
     "fem_dev_fetch_bam", "fem_dev_fetch_bam_nowait", "fem_dev_bam_wait", "fem_dev_bgzf_compress",
 ]
 
@@ -196,6 +197,9 @@ def load_hip():
         L.fem_dev_set_mate_tags.argtypes = [vp, C.c_int, C.c_int]
     if hasattr(L, "fem_dev_set_sam_seq"):
         L.fem_dev_set_sam_seq.argtypes = [vp, C.c_int, C.c_int]
+    if hasattr(L, "fem_dev_set_xa"):
+        L.fem_dev_set_xa.argtypes = [vp, C.c_int, C.c_int32]
+        L.fem_dev_xa_count.argtypes = [vp, C.c_int, C.POINTER(u64)]
     if hasattr(L, "fem_dev_fetch_bam"):
         L.fem_dev_fetch_bam.argtypes = [vp, C.c_int, C.c_int, C.POINTER(_BatchBam)]
         L.fem_dev_fetch_bam_nowait.argtypes = [vp, C.c_int, C.c_int, C.POINTER(_BatchBam)]
@@ -740,6 +744,19 @@ class Device:
         FLAG has 0x10 and that carry them, as the SAM specification orders them (False: every read as sequenced, the reference's
         output); the qualities must be on the device then."""
         self._check(self._L.fem_dev_set_sam_seq(self._h, slot, 1 if on else 0))
+
+    XA_ALL = 2**31 - 1  # set_xa: no entry limit, the byte budget (FEM_XA_MAX_BYTES) alone bounds a slot's folding
+
+    def set_xa(self, max_entries=XA_ALL, slot=0):
+        """fem_dev_set_xa: the secondary lines of every slot of the slot's SAM text and BAM records folded into an XA:Z field on the
+        slot's primary line, at most max_entries of them and FEM_XA_MAX_BYTES bytes per line (0: off, a line per mapping)."""
+        self._check(self._L.fem_dev_set_xa(self._h, slot, max_entries))
+
+    def xa_count(self, slot=0):
+        """fem_dev_xa_count: lines folded into XA:Z entries in the slot's last SAM text or BAM."""
+        n = C.c_uint64()
+        self._check(self._L.fem_dev_xa_count(self._h, slot, C.byref(n)))
+        return int(n.value)
 
     def filtered_count(self, slot=0):
         """fem_dev_filtered_count: lines the filter left out of the slot's last SAM text or BAM."""

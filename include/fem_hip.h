@@ -264,7 +264,8 @@ int fem_dev_commit_text_stage(fem_dev *h, int slot, uint64_t n_reads, uint64_t n
 int fem_dev_commit_names_stage(fem_dev *h, int slot, uint64_t n_reads, uint64_t n_name_bytes);
 int fem_dev_sam_quals(fem_dev *h, int slot, const uint64_t **qual_at, uint64_t *n_reads);
 /* Optional: device and pinned buffers of the slot for batches of this shape and `text_bytes` of SAM text, allocated now
- * (pinning host memory costs ~0.25 ms per MB; otherwise the first batch of every slot pays for it). */
+ * (pinning host memory costs ~0.25 ms per MB; otherwise the first batch of every slot pays for it).  With fem_dev_set_xa a primary
+ * line grows by up to 6 + FEM_XA_MAX_BYTES bytes while the secondary lines it stands for go: the text as a whole gets no larger. */
 int fem_dev_reserve_text(fem_dev *h, int slot, uint64_t n_reads, uint64_t n_bases, uint64_t n_name_bytes, uint64_t text_bytes);
 /* Optional, after the index is resident: everything else a batch of up to n_reads reads of up to max_len characters with up
  * to n_records mappings allocates in this slot on its way through fem_dev_map_staged and fem_dev_fetch_records /
@@ -606,6 +607,45 @@ int fem_dev_set_mate_tags(fem_dev *h, int slot, int on);
  *   sequenced), no tag (ms:i is a sum).  FLAG 0x10 is the real strand under every fem_dev_set_orientation. */
 int fem_dev_set_sam_seq(fem_dev *h, int slot, int on);
 
+/* ---- secondary hits folded into XA:Z on the primary line (new; opt-in: the reference writes a line of its own for every mapping,
+ *      and so does every output without it) ----
+ * fem_dev_set_xa: max_entries N: 0 is off, every byte as before; 1 .. 2^31 - 1 is on with at most N entries per slot; a negative
+ *   value is FEM_ERR_INVALID.  Per slot and sticky, as the other options.  It applies to the slot's fem_dev_fetch_sam[_nowait] text
+ *   and fem_dev_fetch_bam[_nowait] records, single-end and in pair mode, with both ways of staging the bases and with the qualities
+ *   on the device or kept on the host (fem_dev_commit_names_stage: XA stands behind QUAL and needs no quality).  It adds no refusal.
+ *   fem_dev_reserve_text: a primary line grows by up to 6 + FEM_XA_MAX_BYTES bytes (and the secondary lines it stands for go).
+ * Rule.  Folding acts on LINES, after everything else has been decided: the single-end order, rescue, pairing, MAPQ, the lines of
+ *   unmapped reads, the line filter, and every other tag.  A slot is a read single-end, or one mate of a pair (the slot of
+ *   fem_dev_set_report).  Its lines in output order are l_0 .. l_{c-1}; l_0 is the primary line, the only line of the slot without
+ *   FLAG 0x100; an unmapped read's line is a slot with c = 1.
+ *   Entry.  The entry of a secondary line l_t is <RNAME>,<s><POS>,<CIGAR>,<NM>; where RNAME, POS and CIGAR are the bytes of those
+ *     columns as l_t prints them (a record with 0x8000 prints * for CIGAR), <s> is - if l_t's FLAG as written has 0x10, else +
+ *     (the real strand under every fem_dev_set_orientation), and <NM> is the digits of its NM:i.  len_t is the entry's byte count.
+ *   How many fold.  With B = FEM_XA_MAX_BYTES, f is the largest f <= min(c - 1, N) with len_1 + .. + len_f <= B.  The folded lines
+ *     are always the prefix l_1 .. l_f of the secondary lines.
+ *   f = 0: the slot's lines are byte for byte as without the option (so a slot of one line never carries XA).
+ *   f >= 1: l_1 .. l_f are not written; l_0 is written byte for byte as without the option plus one last field, a tab, XA:Z: and the
+ *     f entries in order; l_{f+1} .. l_{c-1} are written byte for byte as without the option.
+ *   Field order on a mapped line: NM:i MD:Z [NH:i HI:i] [RG:Z] [MC:Z] [MQ:i] [ms:i] [XA:Z].  XA carries no MD: that is the format.
+ *   Unchanged: every byte in front of XA; the values of NH / HI on every line that stays (a folded hit is still a reported hit, so
+ *     a line keeps the numbers it has without the option); MAPQ, the mate columns, SEQ and QUAL, hence qual_at of
+ *     fem_dev_sam_quals; the order of everything that stays; fem_batch_records, fem_batch_pairs and the five stats; the proper,
+ *     rescued, unmapped and filtered counts; n_asserted (a folded 0x8000 record is still counted); n_records, which counts the
+ *     mapping records that are in the output as a line OR AS AN ENTRY and so equals the value without the option.
+ *   BAM: the primary record carries aux XA of type Z (the same characters and a NUL) as its last aux field; block_size includes it;
+ *     bin, l_seq and the rest are unchanged; folded records are absent.  B keeps a record far below the 65 280 bytes at which
+ *     fem_dev_fetch_bam cuts BGZF members of whole records.
+ * fem_dev_xa_count: the entries (folded lines) of the slot's last text or BAM (valid once the fetch has returned); 0 with the
+ *   option off. */
+/* The byte budget of one XA value.  The worst-case BAM record with it, for the device's longest read (L = 1024, e = 7): fixed part
+ * 36 + name <= 255 + CIGAR words (a few dozen bytes for an ordinary alignment; the traceback's bound of 2 L + 2 e + 8 operations
+ * would be 8344) + SEQ 512 + QUAL 1024 + NM 4 + MD 3 + (<= a few hundred characters for <= 7 edits) + 1 + the existing tags (NH HI
+ * 14, RG <= 259, MC a few dozen, MQ 4, ms 7) + XA 4 + FEM_XA_MAX_BYTES: on the order of 12 KB, and below 50 KB even with every term
+ * at its formal bound, so always below the 65 280 bytes of a BGZF member's input. */
+#define FEM_XA_MAX_BYTES 8192
+int fem_dev_set_xa(fem_dev *h, int slot, int32_t max_entries);
+int fem_dev_xa_count(fem_dev *h, int slot, uint64_t *n_entries);
+
 /* Name of the seed + filter kernel fem_dev_map_staged would launch first for these parameters on the resident
  * index ("seed_join_kernel" — behind its "seed_select_kernel"; "seed_join_banked_kernel" where the reference's sequences
  * need more than one 32-bit coordinate space —, "seed_fast_kernel<hash>", "seed_fast_kernel<lean>" or
@@ -643,7 +683,10 @@ int fem_dev_index_info(const fem_dev *h, char *buf, uint64_t cap);
  * 16 = the insert sampling and bounds kernels of fem_dev_estimate_insert or fem_dev_estimate_library (one entry per call, the zeroing of the histogram
  * included; its fem_dev_fetch_records counts 3, 4 and 5 as any other; no fetch of records, text or pairs counts here);
  * 17 = the score kernel (ms:i) of a paired fem_dev_fetch_sam / fem_dev_fetch_bam with fem_dev_set_mate_tags on (one entry per
- * call; MC, MQ and ms themselves are written by the text and BAM record kernels: 7 and 11; none with the setting off). */
+ * call; MC, MQ and ms themselves are written by the text and BAM record kernels: 7 and 11; none with the setting off);
+ * 18 = the fold index kernels (XA:Z) of a fem_dev_fetch_sam / fem_dev_fetch_bam with fem_dev_set_xa on (one entry per call; where no
+ * line filter is set the line index they read is made inside this id, and 14 has no entry; the entries' bytes themselves are
+ * written under 7 and 11; none with the option off). */
 int fem_dev_set_timing(fem_dev *h, int on);
 int fem_dev_reset_timing(fem_dev *h);
 int fem_dev_kernel_time(fem_dev *h, int kernel, double *ms_total, uint64_t *launches);
