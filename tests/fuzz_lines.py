@@ -1,7 +1,16 @@
 """Randomised differential run of the output-line options: pairing, mate rescue, --rescue-discordant, MAPQ, the unmapped reads'
-lines, --strata / --max-hits, the RG / NH / HI tags and BAM, all drawn together, against the composed plain-Python models
-(tests/pair_model, rescue_model, discordant_model, mapq_model, unmapped_model, report_model, tags_model, bam_model) on the
-oracle's single-end records.  include/fem_hip.h is the arbiter.
+lines, --strata / --max-hits, the RG / NH / HI tags, the library's orientation (FR, RF, FF), --mate-tags, --sam-seq, --xa (its
+entry limit and its byte budget, with long reference names), the two library estimates and BAM, all drawn together, against the
+composed plain-Python models (tests/pair_model, rescue_model, discordant_model, mapq_model, unmapped_model, report_model,
+orient_model, tags_model, mate_tags_model, sam_seq_model, xa_model, bam_model) on the oracle's single-end records.
+include/fem_hip.h is the arbiter, and expected() composes the models in the order it states.
+
+A paired trial's reads are an FR world's, turned with orient_model.virtual_reads before the oracle maps them, so the fixtures
+and the moved insert bound mean under RF and FF what they mean under FR.  The mates an orientation turns hold upper-case
+A C G T N only (the domain of orient_model.revcomp; the header defines no more): lower-case reads and the other IUPAC letters
+go into every mate under FR, into mate 1 under FF, into none under RF, and into every read single-end, where nothing is turned
+and the orientation, set all the same, must change nothing.  --infer-insert and --orientation auto stay with their own tests:
+their sample is a file's head, not a trial's batch.
 
 Every trial is three functions: draw(rng) makes the world and the options, expected(trial) runs the models (both on the CPU:
 tests/test_fuzz_lines_model.py holds the drawn slice to coverage and sensitivity conditions), compare(dev, trial, want) runs the
@@ -14,6 +23,7 @@ import gzip
 import itertools
 import os
 import pathlib
+import struct
 import sys
 import tempfile
 import time
@@ -24,12 +34,16 @@ import numpy as np
 from oracle import fem_oracle as fo
 from tests import bam_model as bm
 from tests import discordant_fixture as df
-from tests import discordant_model as dm
+from tests import insert_model as im
+from tests import mate_tags_model as mt
+from tests import orient_model as om
 from tests import pair_model as pm
 from tests import report_model as rp
 from tests import rescue_model as rm
+from tests import sam_seq_model as ss
 from tests import tags_model as tm
 from tests import unmapped_model as um
+from tests import xa_model as xm
 from tests import util
 from tests.cases import make_pairs, write_fastq
 from tests.harness import build_index, decode_bam_file, first_difference, run_fem
@@ -39,8 +53,11 @@ COPIES = (6, 12, 40, 80)
 IUPAC = b"NNNNRYKMSWBDHVn"
 LETTERS = np.frombuffer(b"ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz", np.uint8)
 INSERT_LISTS = 16  # the records of a mate that draw() looks at for inserts that occur
+XA_LIMITS = (1, 2, 3, 31, 32, 33, 63, 64, 65, xm.ALL)  # a lane's slot and its last line, a wave's first, one step, two, no limit
+LONG_NAME = (150, 241)  # the letters behind chr<i>_ of a long reference name: some forty entries fill FEM_XA_MAX_BYTES
 OPTIONS = ("paired", "e", "E", "L", "L2", "I", "X", "rescue", "discordant", "mapq", "unmapped", "strata", "max_hits", "rg", "hits",
-           "bam_level", "nowait", "packed", "quals_on_host", "slot", "copies", "n", "moved", "cli")
+           "bam_level", "nowait", "packed", "quals_on_host", "slot", "copies", "n", "moved", "cli", "orientation", "mate_tags", "sam_seq",
+           "xa", "estimate", "long_names", "xa_moved")
 
 
 def _printable(rng, n, lo=33):
@@ -96,10 +113,14 @@ def anchor_pairs(rng, L, L2, e, E, X, n_copies=9):
 def draw(rng, force=None):
     """World and options of one trial: a random 60 kbp sequence, two or three repeat-rich ones, the discordant fixture's decoy and
     anchor_pairs' sequence; the fixture's pairs, anchor_pairs' and make_pairs', some mates made odd; the options, each drawn
-    on its own; the oracle's records; the insert range, in most paired trials with a bound on an insert that occurs.  force: values that a caller fixes instead of drawing them (e, copies, cli; paired, or
-    single_end: the share of single-end trials)."""
+    on its own; the oracle's records; the insert range, in most paired trials with a bound on an insert that occurs; the XA
+    limit, from the ladder or from a slot that occurs, and with long reference names a name's length moved onto the byte budget
+    (xa_moved).  force: values that a caller fixes instead of drawing them (e, copies, cli, orientation, long_names, strata,
+    max_hits, xa: the ladder's value; paired, or single_end: the share of single-end trials)."""
     f = force or {}
     t = types.SimpleNamespace()
+    o = rng.spawn(1)[0]  # the newer options draw from a child stream, so the older ones and the FR world stay what they were
+    t.orientation = int(f.get("orientation", o.integers(0, 3)))
     t.cli = bool(f.get("cli", False))
     e = int(rng.choice([0, 1, 2, 3, 4, 0, 1, 2, 3, 4, 5, 6, 7]))  # (a forced value takes the place of a drawn one: the stream goes on alike)
     t.e = e = int(f.get("e", e))
@@ -130,13 +151,17 @@ def draw(rng, force=None):
     # mode, staging
     t.paired = bool(f.get("paired", rng.random() >= f.get("single_end", 0.25)))
     t.packed = bool(L == L2 and rng.random() < 0.4)
-    # odd reads: lower case (0x8000 records), N and IUPAC letters, random mates, reads of length 0
+    # odd reads: lower case (0x8000 records), N and IUPAC letters, random mates, reads of length 0.  The mates that a paired
+    # trial's orientation flips keep to upper-case A C G T N (orient_model.revcomp's domain): the same draws, the letter left out
+    flips = om.FLIPS[t.orientation] if t.paired else (0, 0)
     for r in rng.choice(2 * n, int(rng.integers(2, 5)), replace=False):
-        reads[r] = reads[r].lower()
+        if not flips[int(r >= n)]:
+            reads[r] = reads[r].lower()
     for r in rng.choice(2 * n, int(rng.integers(2, 6)), replace=False):
         s = bytearray(reads[r])
         for x in rng.integers(0, len(s), int(rng.integers(1, 4))):
-            s[int(x)] = IUPAC[int(rng.integers(0, len(IUPAC)))]
+            c = IUPAC[int(rng.integers(0, len(IUPAC)))]
+            s[int(x)] = c if not flips[int(r >= n)] else ord("N")
         reads[r] = bytes(s)
     for r in rng.choice(2 * n, int(rng.integers(1, 4)), replace=False):
         reads[r] = util.rand_seq(rng, len(reads[r]))
@@ -145,11 +170,16 @@ def draw(rng, force=None):
             reads[r] = b""
     if t.packed and 20 * sum(sum(c not in b"ACGT" for c in r) for r in reads) > 2 * n * L:
         t.packed = False  # (a batch with more than one odd byte in sixteen goes as characters)
+    if t.paired:  # so far the FR world's reads; the library's are those turned (single-end nothing reads the orientation: no read is)
+        reads = om.virtual_reads(reads, n, t.orientation)
     t.seqs, t.reads = seqs, reads
     base = [_qname(rng) for _ in range(n)]
     t.rnames = base + base
     t.quals = [_printable(rng, len(r)).decode("latin-1") for r in reads]
     t.names = ["chr%d%s" % (i, "_x" * int(rng.integers(0, 20))) for i in range(len(seqs))]
+    t.long_names = bool(f.get("long_names", o.random() < 0.3))
+    if t.long_names:  # (as xa_model.long_names: the byte budget then stops a slot's folding at these repeat sizes)
+        t.names = ["chr%d_%s" % (i, chr(97 + i % 26) * int(o.integers(*LONG_NAME))) for i in range(len(seqs))]
     # the output options
     t.rescue = bool(rng.random() >= 0.2)
     t.discordant = bool(rng.integers(0, 2))
@@ -158,6 +188,7 @@ def draw(rng, force=None):
     t.strata = None if rng.random() < 0.4 else int(rng.integers(0, 4)) if rng.random() < 0.75 else int(rng.integers(0, 16))
     u = rng.random()
     t.max_hits = None if u < 0.4 else (1 << 31) - 1 if u < 0.5 else int(rng.integers(1, 7))
+    t.strata, t.max_hits = f.get("strata", t.strata), f.get("max_hits", t.max_hits)
     t.rg = None if rng.random() < 0.4 else _printable(rng, int(rng.integers(1, 256)) if rng.random() < 0.3 else int(rng.integers(1, 12)), 32)
     if t.cli and t.rg is not None:  # (FEM map --rg reads the two characters \t as a tab)
         t.rg = t.rg.replace(b"\\", b"/")
@@ -166,6 +197,9 @@ def draw(rng, force=None):
     t.nowait = bool(rng.integers(0, 2))
     t.quals_on_host = bool(rng.random() < 0.3)
     t.slot = int(rng.integers(0, 4))
+    t.mate_tags = bool(o.integers(0, 2))
+    t.sam_seq = bool(o.integers(0, 2))
+    t.estimate = [None, None, None, "first", "last"][int(o.integers(0, 5))]  # estimate_insert / _library: before the text, behind the BAM
     # the oracle's single-end records: what the models start from, and the inserts that occur
     t.ref = fo.Reference(seqs)
     t.idx = fo.OracleIndex(t.ref, threads=THREADS)
@@ -174,7 +208,7 @@ def draw(rng, force=None):
     I = int([0, 0, max(L, L2), rng.integers(0, X // 2)][int(rng.integers(0, 4))])
     t.moved = None
     if t.paired and rng.random() < 0.6:  # a bound onto an insert that occurs: ins == X, ins == I
-        ins = occurring_inserts(t.se, n)
+        ins = occurring_inserts(om.virtual(t.se, n, t.orientation), n)
         near = [v for v in ins if v <= 2000] or ins
         if near:
             v = int(near[int(rng.integers(0, len(near)))])
@@ -185,7 +219,43 @@ def draw(rng, force=None):
                 I, t.moved = v, "I"
     t.I, t.X = I, X
     assert 0 <= I <= X <= 1 << 30 and X - I <= 65536
+    # XA: off, a limit of the ladder, or c - 1 of a slot that occurs, and that - 1 and + 1; with long names, in most trials one
+    # name's length moved so that a prefix of some slot's entries has FEM_XA_MAX_BYTES bytes exactly, or one more
+    t.xa = t.xa_moved = None
+    u, v = o.random(), o.random()
+    if u >= 0.25:
+        t.xa = int(f.get("xa", XA_LIMITS[int(o.integers(0, len(XA_LIMITS)))]))
+        seq = expected(t, full=False).seq  # (the text in front of the folding; the models' work is kept for the trial's own call)
+        sizes = sorted({len(s) - 1 for s in xm.slots(seq) if len(s) > 1})  # (each size once: the large slots are few)
+        if u >= 0.7 and sizes:
+            t.xa = max(1, sizes[int(o.integers(0, len(sizes)))] + int(o.integers(-1, 2)))
+        if t.long_names and v < 0.8:
+            target = xm.MAX_BYTES + int(o.integers(0, 2))
+            moves = budget_moves(seq, t.names, target)
+            if moves:
+                k, length, f = moves[int(o.integers(0, len(moves)))]
+                t.names[k] = "chr%d_" % k + t.names[k][-1] * (length - len("chr%d_" % k))
+                t.xa_moved = "B" if target == xm.MAX_BYTES else "B+1"
+                if t.xa < f:
+                    t.xa = xm.ALL
     return t
+
+
+def budget_moves(seq, names, target):
+    """Where one reference name's length can go so that a prefix of a slot's XA entries has `target` bytes: [(the name's index, its
+    new length, the prefix's entries)] over the slots of `seq`, the text in front of the folding.  An entry's length is its RNAME's
+    plus what the other columns take, so the first f entries, c of them on name k, reach the target iff c divides what is missing."""
+    raw, out = [x.encode() for x in names], []
+    for slot in xm.slots(seq):
+        lens = [len(xm.entry(l)) for l in slot[1:]]
+        on = [l.split(b"\t", 3)[2] for l in slot[1:]]
+        for name in sorted(set(on)):
+            k, total, c = raw.index(name), 0, 0
+            for f in range(1, len(lens) + 1):
+                total, c = total + lens[f - 1], c + (on[f - 1] == name)
+                if c and (target - total) % c == 0 and 8 <= len(name) + (target - total) // c <= 254:
+                    out.append((k, len(name) + (target - total) // c, f))
+    return out
 
 
 def options(t):
@@ -197,20 +267,19 @@ def fingerprint(t):
     return (repr(options(t)), tuple(t.seqs), tuple(t.reads), tuple(t.rnames), tuple(t.quals), tuple(t.names))
 
 
-def rescued_lists(t, E=None, I=None, X=None):
-    """(the lists pairing sees, {read: its kept rescue}, {pair: every traced rescue}, {read: (kind, d)}) of a paired trial."""
+def rescued_lists(t, E=None, I=None, X=None, orientation=None):
+    """(the virtual lists pairing sees, {read: its kept rescue}, {pair: every traced rescue}, {read: (kind, d)}) of a paired trial
+    (orient_model.rescued: the rescue models on the virtual batch; under FR that is the batch itself)."""
     E, I, X = t.E if E is None else E, t.I if I is None else I, t.X if X is None else X
+    orientation = t.orientation if orientation is None else orientation
     memo = t.__dict__.setdefault("_rescued", {})
-    key = (E, I, X, rm.ANCHORS)
+    key = (E, I, X, orientation, rm.ANCHORS)
     if key in memo:
         return memo[key]
-    if t.rescue and t.discordant:
-        out = dm.rescue(t.se, t.n, t.reads, t.seqs, E, I, X)
-    elif t.rescue:
-        ext, kept, traced = rm.rescue(t.se, t.n, t.reads, t.seqs, E, I, X)
-        out = ext, kept, traced, {r: (1, 0 if r >= t.n else 1) for r in kept}
+    if t.rescue:
+        out = om.rescued(t.se, t.n, t.reads, t.seqs, E, I, X, orientation, t.discordant)
     else:
-        out = t.se, {}, {}, {}
+        out = om.virtual(t.se, t.n, orientation), {}, {}, {}
     memo[key] = out
     return out
 
@@ -218,38 +287,79 @@ def rescued_lists(t, E=None, I=None, X=None):
 _KEEP = object()
 
 
-def expected(t, full=True, E=None, I=None, X=None, strata=_KEEP, max_hits=_KEEP, mapq_e=None):
-    """The models' answer: text, the five counts (proper, rescued, rescued discordant, unmapped, filtered; the pair counts None
-    single-end), and with `full` the fem_batch_pairs arrays and the BAM payload.  The keyword arguments replace one parameter of
-    the rule (tests/test_fuzz_lines_model.py: an off-by-one must show)."""
+def lines_behind(t, w, xa=_KEEP, xa_bytes=xm.MAX_BYTES):
+    """The stages behind w.plain, in the header's order, into w: tagged (RG, NH, HI), mated (MC, MQ, ms; pair mode only), seq (SEQ
+    and QUAL as SAM orders them), text (XA folded at `xa` entries and `xa_bytes` bytes) and n_xa, its entries."""
+    xa = t.xa if xa is _KEEP else xa
+    w.tagged = tm.apply(w.plain, t.rg, t.hits)
+    w.mated = mt.apply(w.tagged, t.n, t.quals) if t.paired and t.mate_tags else w.tagged
+    w.seq = ss.apply(w.mated) if t.sam_seq else w.mated
+    w.text, w.n_xa = (w.seq, 0) if xa is None else xm.apply(w.seq, xa, xa_bytes)
+    return w
+
+
+def expected(t, full=True, E=None, I=None, X=None, strata=_KEEP, max_hits=_KEEP, mapq_e=None, orientation=None):
+    """The models' answer, composed in the order include/fem_hip.h states: the oracle's records, virtual under the orientation,
+    through the rescue models; pairing, MAPQ, the unmapped reads' lines and the filter (report_model: w.virtual); the real strands
+    (orient_model.real_text: w.plain); then lines_behind's stages.  w.counts: proper, rescued, rescued discordant, unmapped,
+    filtered (the pair counts None single-end) and the XA entries.  With `full` also the fem_batch_pairs arrays, the BAM payload
+    and, where the trial asks for them, the two estimates.  The keyword arguments replace one parameter of the rule
+    (tests/test_fuzz_lines_model.py: an off-by-one must show).  The stages up to w.plain are kept per trial and parameter set."""
     I, X = t.I if I is None else I, t.X if X is None else X
     strata = t.strata if strata is _KEEP else strata
     max_hits = t.max_hits if max_hits is _KEEP else max_hits
+    orientation = t.orientation if orientation is None else orientation
     e = (t.e if mapq_e is None else mapq_e) if t.mapq else None
-    w = types.SimpleNamespace(pairs=None)
-    if t.paired:
-        ext, kept, traced, kinds = rescued_lists(t, E, I, X)
-        text, dropped = rp.paired(t.se, t.n, t.names, t.reads, t.rnames, t.quals, I, X, res=ext, rescued=set(kept), e=e,
-                                  unmapped=t.unmapped, strata=strata, max_hits=max_hits)
-        w.ext, w.kept, w.traced, w.kinds = ext, kept, traced, kinds
-        n_unm = len(um.unmapped_reads(ext, 2 * t.n)) if t.unmapped else 0
-        w.counts = (pm.expected(ext, t.n, I, X)[1], len(kept), sum(k == 2 for k, _ in kinds.values()), n_unm, dropped)
-        if full:
-            w.pairs = pm.pair_arrays(ext, t.n, I, X)
+    memo = t.__dict__.setdefault("_plain", {})
+    key = (E, I, X, strata, max_hits, e, orientation, tuple(t.names), rm.ANCHORS)
+    if key in memo:
+        w = types.SimpleNamespace(**memo[key])
     else:
-        text, dropped = rp.single_end(t.se, t.names, t.reads, t.rnames, t.quals, e=e, unmapped=t.unmapped, strata=strata,
-                                      max_hits=max_hits)
-        w.counts = (None, None, None, len(um.unmapped_reads(t.se, 2 * t.n)) if t.unmapped else 0, dropped)
-    w.plain, w.text = text, tm.apply(text, t.rg, t.hits)
+        w = types.SimpleNamespace(pairs=None)
+        if t.paired:
+            ext, kept, traced, kinds = rescued_lists(t, E, I, X, orientation)
+            w.virtual, dropped = rp.paired(om.virtual(t.se, t.n, orientation), t.n, t.names, t.reads, t.rnames, t.quals, I, X, res=ext,
+                                           rescued=set(kept), e=e, unmapped=t.unmapped, strata=strata, max_hits=max_hits)
+            w.plain = om.real_text(w.virtual, orientation)
+            w.ext, w.kept, w.traced, w.kinds = ext, kept, traced, kinds
+            n_unm = len(um.unmapped_reads(ext, 2 * t.n)) if t.unmapped else 0
+            w.five = (pm.expected(ext, t.n, I, X)[1], len(kept), sum(k == 2 for k, _ in kinds.values()), n_unm, dropped)
+        else:
+            w.plain, dropped = rp.single_end(t.se, t.names, t.reads, t.rnames, t.quals, e=e, unmapped=t.unmapped, strata=strata,
+                                             max_hits=max_hits)
+            w.five = (None, None, None, len(um.unmapped_reads(t.se, 2 * t.n)) if t.unmapped else 0, dropped)
+        memo[key] = dict(w.__dict__)
+    lines_behind(t, w)
+    w.counts = w.five + (w.n_xa,)
     if full:
-        w.bam = tm.bam_payload(w.text, [x.encode() for x in t.names])
+        if t.paired:
+            w.pairs = om.pair_arrays(t.se, t.n, I, X, orientation, ext=w.ext)
+            if t.estimate:
+                w.library, w.insert = om.library_estimate(t.se, t.n), om.estimate(t.se, t.n, orientation)
+        w.bam = bam_payload(w.text, [x.encode() for x in t.names])
     return w
+
+
+def bam_payload(text, ref_names):
+    """The BAM records of a text with every tag: mate_tags_model's record of each line without XA (tags_model's behind
+    bam_model's, MC MQ ms behind those), and XA of type Z as the last aux field."""
+    bare, xa = [], []
+    for l in text.splitlines():
+        v = xm.xa_of(l)
+        xa.append(v)
+        bare.append((l if v is None else l[:len(l) - len(v) - 6]) + b"\n")
+    out = []
+    for rec, v in zip(bm.records(mt.bam_payload(b"".join(bare), ref_names)), xa):
+        extra = b"" if v is None else b"XAZ" + v + b"\0"
+        out.append(struct.pack("<i", len(rec) - 4 + len(extra)) + rec[4:] + extra)
+    return b"".join(out)
 
 
 # the slice of tests/test_gpu_fuzz_lines.py, which tests/test_fuzz_lines_model.py holds to its conditions:
 # id, seed, trials, force, the trials that also go through the command line
-SLICE = [("single-end-heavy", 11, 12, {"single_end": 0.6}, ()), ("copies-80", 12, 12, {"copies": 80}, ()), ("e-7", 13, 12, {"e": 7}, ()),
-         ("command-line", 14, 12, {}, (3,))]
+SLICE = [("single-end-heavy", 18, 12, {"single_end": 0.6}, ()), ("copies-80", 15, 12, {"copies": 80}, ()), ("e-7", 25, 12, {"e": 7}, ()),
+         ("command-line", 21, 12, {}, (3,)), ("long-names", 24, 12, {"long_names": True, "copies": 80}, ()),
+         ("xa-deep", 16, 12, {"copies": 200, "strata": None, "max_hits": None, "xa": xm.ALL}, ())]
 
 
 def trial_force(force, cli):
@@ -274,7 +384,7 @@ def _counts(dev, t):
             if t.paired or "the slot is not in pair mode" not in str(err):
                 raise
             out.append(None)
-    return tuple(out) + (dev.unmapped_count(slot=t.slot), dev.filtered_count(slot=t.slot))
+    return tuple(out) + (dev.unmapped_count(slot=t.slot), dev.filtered_count(slot=t.slot), dev.xa_count(slot=t.slot))
 
 
 def set_options(dev, t, X=None):
@@ -287,12 +397,27 @@ def set_options(dev, t, X=None):
     dev.set_unmapped(t.unmapped, slot=s)
     dev.set_report(strata=t.strata, max_hits=t.max_hits, slot=s)
     dev.set_tags(slot=s, read_group=t.rg, hits=t.hits)
+    dev.set_orientation(t.orientation, slot=s)  # (single-end too: it must change nothing there, nor must the mate tags)
+    dev.set_mate_tags(t.mate_tags, slot=s)
+    dev.set_sam_seq(t.sam_seq, slot=s)
+    dev.set_xa(0 if t.xa is None else t.xa, slot=s)
+
+
+def _estimates(dev, t, want, when, diffs):
+    """estimate_insert and estimate_library of the trial's slot against the models."""
+    got = dev.estimate_insert(slot=t.slot).as_tuple()
+    if got != im.as_tuple(want.insert):
+        diffs.append("estimate_insert %s: got %r want %r" % (when, got, im.as_tuple(want.insert)))
+    lib = dev.estimate_library(slot=t.slot)
+    got, model = ([e.as_tuple() for e in lib.by], lib.orientation), ([im.as_tuple(e) for e in want.library["by"]], want.library["orientation"])
+    if got != model:
+        diffs.append("estimate_library %s: got %r want %r" % (when, got, model))
 
 
 def compare(dev, t, want, X=None):
     """The device on the trial -> the list of differences (empty: everything compared is identical).  An error of the device layer
     is raised, not listed.  X: the device's max_insert, if not the trial's (to show that a difference is seen)."""
-    from fem_amd import device
+    from fem_amd import FemError, device
     s, diffs = t.slot, []
     dev.upload_reference(t.seqs)
     dev.upload_reference_names(t.names)
@@ -309,7 +434,20 @@ def compare(dev, t, want, X=None):
         diffs.append("staging: not packed")
     dev.stage_text(q, t.rnames, slot=s, quals_on_host=t.quals_on_host)
     dev.map_staged(e=t.e, slot=s)
-    hq = dict(quals=q, offsets=batch.off) if t.quals_on_host else {}
+    on_host = t.quals_on_host
+    hq = dict(quals=q, offsets=batch.off) if on_host else {}
+    if t.estimate == "first" and t.paired:  # (the header's promise: what is fetched afterwards is what it is without the calls)
+        _estimates(dev, t, want, "before the text", diffs)
+    # QUAL reversed and ms:i are made from the qualities on the device: with them on the host the text is refused, and only there
+    if on_host and (t.sam_seq or (t.paired and t.mate_tags)):
+        try:
+            dev.fetch_sam(slot=s, nowait=t.nowait, **hq)
+            diffs.append("fetch_sam: a text with the qualities on the host")
+        except FemError as err:
+            if "qualities" not in str(err):
+                raise
+        dev.stage_text(q, t.rnames, slot=s)
+        on_host, hq = False, {}
     # the text, the counts behind it, the text again the other way
     text, _, _, stats = dev.fetch_sam(slot=s, nowait=t.nowait, **hq)
     if text != want.text:
@@ -320,8 +458,10 @@ def compare(dev, t, want, X=None):
     again = dev.fetch_sam(slot=s, nowait=not t.nowait, **hq)[0]
     if again != text:
         diffs.append("fetch_sam, the other nowait: " + first_difference(again, text))
+    if dev.xa_count(slot=s) != want.counts[5]:
+        diffs.append("xa_count after the text, the other nowait: got %d want %d" % (dev.xa_count(slot=s), want.counts[5]))
     # BAM at the drawn level (its qualities on the device)
-    if t.quals_on_host:
+    if on_host:
         dev.stage_text(q, t.rnames, slot=s)
     data = dev.fetch_bam(slot=s, level=t.bam_level, nowait=t.nowait)
     members = [m[0] for m in bm.parse_bgzf(data[0], eof=False)] if data[0] else []
@@ -347,6 +487,14 @@ def compare(dev, t, want, X=None):
         diffs.append("counts after the BAM: got %r want %r" % (got, want.counts))
     if dev.fetch_bam(slot=s, level=t.bam_level, nowait=not t.nowait)[0] != data[0]:
         diffs.append("fetch_bam, the other nowait: other bytes")
+    if dev.xa_count(slot=s) != want.counts[5]:
+        diffs.append("xa_count after the BAM, the other nowait: got %d want %d" % (dev.xa_count(slot=s), want.counts[5]))
+    if t.estimate == "last" and t.paired:  # ... and behind the BAM: the text, the BAM and the counts after them are as before
+        _estimates(dev, t, want, "behind the BAM", diffs)
+        if dev.fetch_sam(slot=s, nowait=t.nowait)[0] != text or _counts(dev, t) != want.counts:
+            diffs.append("behind the estimates: another text or other counts")
+        if dev.fetch_bam(slot=s, level=t.bam_level, nowait=t.nowait)[0] != data[0] or _counts(dev, t) != want.counts:
+            diffs.append("behind the estimates: another BAM or other counts")
     # fem_batch_pairs; fem_batch_records and the stats keep their single-end meaning
     if t.paired:
         pairs = dev.fetch_pairs(slot=s)
@@ -380,6 +528,8 @@ def _counters(t, want):
         out.append("The number of unmapped reads: %d" % want.counts[3])
     if t.strata is not None or t.max_hits is not None:
         out.append("The number of filtered lines: %d" % want.counts[4])
+    if t.xa is not None:
+        out.append("The number of XA entries: %d" % want.counts[5])
     return out
 
 
@@ -403,6 +553,8 @@ def compare_cli(t, want, rng, timeout=300):
         args += (["--mapq"] if t.mapq else []) + (["--unmapped"] if t.unmapped else []) + (["--nh"] if t.hits else [])
         args += ([] if t.strata is None else ["--strata", str(t.strata)]) + ([] if t.max_hits is None else ["--max-hits", str(t.max_hits)])
         args += [] if t.rg is None else ["--rg", "@RG\tID:" + t.rg.decode("latin-1")]
+        args += ["--orientation", om.NAMES[t.orientation]] + (["--mate-tags"] if t.mate_tags else []) + (["--sam-seq"] if t.sam_seq else [])
+        args += [] if t.xa is None else ["--xa"] if t.xa == xm.ALL else ["--xa=%d" % t.xa]
         args += ["--bam=%d" % t.bam_level] if t.bam else []
         r = run_fem("map", *args, timeout=timeout)
         if r.returncode != 0:

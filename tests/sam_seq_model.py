@@ -229,7 +229,9 @@ DRAWS_PER_CASE = 5
 
 
 def draws(k):
-    """The option sets drawn for DRAW_CASES[k]: a subset of the line options each; pair mode only for a case of pairs."""
+    """The option sets drawn for DRAW_CASES[k]: a subset of the line options each; pair mode only for a case of pairs.  They are
+    compared with the device's own text with the option off, which the line fuzzer (tests/fuzz_lines.py) now ties to the oracle
+    under drawn options."""
     rng = np.random.default_rng(620 + k)
     paired_case = DRAW_CASES[k][1].endswith("pair_case")
     out = []

@@ -1,12 +1,15 @@
 """A bounded slice of tests/fuzz_lines.py under `pytest -m gpu`: fixed seeds, twelve trials each, of the output-line options drawn
 together (pairing with I and X anywhere, an insert on either bound, mate rescue, --rescue-discordant, MAPQ, the unmapped reads'
-lines, --strata / --max-hits, RG / NH / HI, BAM, staging, slot, one trial through FEM index + FEM map) against the composed
-models: pair_kernel, pair_probe_kernel, mapq_kernel, report_kernel, the rescue kernels and the option branches of the sam_* /
-bam_* kernels (fem_tail.hip), and the LineOptions plumbing of fem_hip.hip, one handle per case.  What the slice reaches, and that
-it would see an off-by-one, is held without a GPU by tests/test_fuzz_lines_model.py.
+lines, --strata / --max-hits, RG / NH / HI, the orientation FR / RF / FF with the reads turned to match, --mate-tags, --sam-seq,
+--xa with its entry limit on a slot's size and its byte budget met exactly under long reference names, the refusal of host
+qualities, estimate_insert / estimate_library before the text or behind the BAM, BAM, staging, slot, one trial through
+FEM index + FEM map) against the composed models: pair_kernel, pair_probe_kernel, mapq_kernel, report_kernel, the rescue
+kernels, xa_index_kernel / xa_write_kernel and the option branches of the sam_* / bam_* kernels (fem_tail.hip), and the
+LineOptions plumbing of fem_hip.hip, one handle per case.  What the slice reaches, and that it would see an off-by-one or a
+strand read from the wrong world, is held without a GPU by tests/test_fuzz_lines_model.py.
 
-Wall time per case on the MI355X (the models on the host take most of it): single-end-heavy 1.2 s, copies-80 1.1 s, e-7 1.0 s,
-command-line 1.8 s."""
+Wall time per case on the MI355X (the models on the host take most of it): single-end-heavy 1.4 s, copies-80 1.4 s, e-7 1.2 s,
+command-line 1.7 s, long-names 1.3 s, xa-deep (200 copies: slots of more than 64 and more than 128 lines) 1.4 s."""
 import pytest
 
 from tests import fuzz_lines
