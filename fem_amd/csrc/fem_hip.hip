@@ -3,7 +3,9 @@
 // kernels in fem_kernels.hip.h and fem_verify.hip.h.  No CPU fallback: every entry point needs a GPU.
 #include "../../include/fem_hip.h"
 
+#include <cstring>  // before rocprim: its headers use memcpy unqualified
 #include <hip/hip_runtime.h>
+#include <rocprim/rocprim.hpp>
 #include <rccl/rccl.h>
 #include <sched.h>
 #if defined(__x86_64__)
@@ -35,6 +37,7 @@
 #include "fem_seed_join.hip.h"
 #include "fem_tail.hip.h"
 #include "fem_bgzf.hip.h"
+#include "fem_trim.hip.h"
 
 namespace {
 
@@ -58,7 +61,7 @@ constexpr size_t kPackedFrontPad = 256;  // ... and verify_kernel_packed up to 1
 constexpr uint64_t kExpandAllShare = 8;  // a packed batch with more exceptions than one per this many reads is expanded whole at commit
 constexpr uint32_t kXcapSmall = 512, kFcap = 128, kCcap = 128;
 
-constexpr int kTimedKernels = 19;  // fem_dev_kernel_time ids: 0 seed (join), 1 verify, 2 generic seed, 3-5 tail, 6 pack_results_kernel (round 5; the count kernel of rounds 1-2 before), 7 SAM text, 8 seed selection, 9 pairing, 10 mate rescue, 11 BAM records, 12 BGZF, 13 MAPQ, 14 the line index with unmapped reads, 15 the line filter's line index, 16 the insert estimate, 17 the mate tags' score kernel, 18 the fold index (XA:Z); 3-5, 7, 9-11, 13-15, 17 and 18 are stages of the device tail (kTailStages), 16 is one too (fem_dev_estimate_insert counts it itself)
+constexpr int kTimedKernels = 20;  // fem_dev_kernel_time ids: 19 the trim stage (fem_dev_set_trim: clip points, scan, gather); else 0 seed (join), 1 verify, 2 generic seed, 3-5 tail, 6 pack_results_kernel (round 5; the count kernel of rounds 1-2 before), 7 SAM text, 8 seed selection, 9 pairing, 10 mate rescue, 11 BAM records, 12 BGZF, 13 MAPQ, 14 the line index with unmapped reads, 15 the line filter's line index, 16 the insert estimate, 17 the mate tags' score kernel, 18 the fold index (XA:Z); 3-5, 7, 9-11, 13-15, 17 and 18 are stages of the device tail (kTailStages), 16 is one too (fem_dev_estimate_insert counts it itself)
 struct TimedLaunch {
   int kernel;
   hipEvent_t start, stop;
@@ -171,6 +174,21 @@ struct Slot {
   std::vector<uint32_t> pr_tid, pr_pos0, pr_cigar_off, pr_cigar, pr_md_off;
   std::vector<uint8_t> pr_nm;
   std::vector<char> pr_md;
+  // read trimming (fem_dev_set_trim): the setting, what the slot's mapped batch was trimmed by (read at fem_dev_map_staged), and
+  // that batch's clip points, kept lengths and MAPPING VIEW: the kept parts' characters and offsets, which the mapping kernels,
+  // the traceback and the rescue read in place of bases() / d_off (those stay the whole reads, for SEQ and QUAL of the text)
+  fem_trim_params trim{0, 0, 0}, trim_batch{0, 0, 0};
+  bool trimmed = false;
+  StageBuf<uint8_t> d_map_bases_alloc;  // laid out as d_bases_alloc
+  StageBuf<uint64_t> d_map_off, d_keep;
+  StageBuf<uint16_t> d_clip5, d_clip3;
+  Buf<unsigned long long> d_trim_ctr;
+  Buf<uint8_t> d_trim_scan_tmp;
+  PinStageBuf<uint16_t> h_clip5, h_clip3;
+  PinBuf<unsigned long long> h_trim_ctr;
+  bool clips_home = false;
+  const uint8_t *map_bases() const { return trimmed ? d_map_bases_alloc + 16 : bases(); }
+  const uint64_t *map_off() const { return trimmed ? d_map_off.get() : d_off.get(); }
 };
 
 // ctr[4] | arena_ctr[2] | stats[4] | pack cursor[2]
@@ -790,8 +808,8 @@ int launch_batch(fem_dev *h, Slot &s) {
     sp.packed = s.packed(), sp.exc_bits = s.d_exc_bits, sp.bpr = s.packed_bpr, sp.len = s.max_len;
     s.select_packed = s.n_reads != 0;
   }
-  sp.bases = s.bases();
-  sp.read_off = s.d_off;
+  sp.bases = s.map_bases();
+  sp.read_off = s.map_off();
   sp.n_reads = (uint32_t)s.n_reads;
   sp.read_begin = 0;
   sp.lookup = h->d_lookup;
@@ -832,7 +850,7 @@ int launch_batch(fem_dev *h, Slot &s) {
     const bool overlap = split_dense && !h->no_overlap;
     if (!overlap && h->have_kernels_done) HIP_TRY(h, hipStreamWaitEvent(s.stream, h->ev_kernels_done, 0));
     femk::VerifyParams vp{};
-    vp.bases = s.bases(), vp.read_off = s.d_off;
+    vp.bases = s.map_bases(), vp.read_off = s.map_off();
     vp.planes = h->d_planes, vp.seq_off = h->d_seq_off;
     vp.cand = s.d_cand, vp.cand_meta = s.d_meta;
     vp.ctr = d_ctr, vp.cand_cap = s.cand_cap, vp.e = p.e;
@@ -1280,6 +1298,52 @@ int enqueue_packed(fem_dev *h, Slot &s, uint64_t n, uint32_t len, uint64_t n_exc
   return FEM_OK;
 }
 
+bool trim_on(const fem_trim_params &t) { return t.trim5 > 0 || t.trim3 > 0 || t.qual > 0; }
+
+// The trim stage of the batch fem_dev_map_staged is about to map, on the slot's stream in front of the selection: the slot's
+// setting becomes the batch's, trim_clip_kernel makes the clip points and kept lengths, their scan the mapping view's offsets,
+// trim_gather_kernel its characters; the two counters go home behind them.  With trimming off it launches nothing.
+int enqueue_trim(fem_dev *h, Slot &s) {
+  s.trim_batch = s.trim, s.trimmed = false, s.clips_home = false;
+  if (!trim_on(s.trim_batch)) return FEM_OK;
+  if (s.sent_packed) return fail(h, FEM_ERR_UNSUPPORTED, "trimming (fem_dev_set_trim) reads a batch staged as characters, not a packed one (fem_dev_commit_stage_packed)");
+  if (s.trim_batch.qual > 0 && (!s.text_staged || s.host_quals))
+    return fail(h, FEM_ERR_STATE, "quality trimming (fem_dev_set_trim) needs the batch's qualities on the device before it is mapped (fem_dev_commit_text_stage)");
+  const size_t n = (size_t)s.n_reads;
+  HIP_TRY(h, s.d_map_bases_alloc.ensure(kFrontPad + (size_t)s.n_bases + 64));
+  HIP_TRY(h, s.d_map_off.ensure(n + 1));
+  HIP_TRY(h, s.d_keep.ensure(n + 1));
+  HIP_TRY(h, s.d_clip5.ensure(std::max<size_t>(n, 1)));
+  HIP_TRY(h, s.d_clip3.ensure(std::max<size_t>(n, 1)));
+  HIP_TRY(h, s.d_trim_ctr.ensure(2));
+  HIP_TRY(h, s.h_trim_ctr.ensure(2));
+  size_t scan_bytes = 0;
+  HIP_TRY(h, rocprim::exclusive_scan(nullptr, scan_bytes, s.d_keep.get(), s.d_map_off.get(), (uint64_t)0, n + 1, rocprim::plus<uint64_t>(), s.stream.s));
+  HIP_TRY(h, s.d_trim_scan_tmp.ensure(std::max<size_t>(scan_bytes, 16)));
+  scan_bytes = s.d_trim_scan_tmp.size();
+  if (s.trim_batch.qual > 0) HIP_TRY(h, hipStreamWaitEvent(s.stream, s.ev_text_staged, 0));  // (the qualities came on the slot's text stream)
+  HIP_TRY(h, hipMemsetAsync(s.d_trim_ctr, 0, 2 * sizeof(unsigned long long), s.stream));
+  femtr::TrimParams tp{};
+  tp.quals = s.trim_batch.qual > 0 ? s.d_quals.get() : nullptr, tp.read_off = s.d_off, tp.n_reads = (uint32_t)n;
+  tp.trim5 = s.trim_batch.trim5, tp.trim3 = s.trim_batch.trim3, tp.qual = s.trim_batch.qual;
+  tp.clip5 = s.d_clip5, tp.clip3 = s.d_clip3, tp.keep = s.d_keep, tp.ctr = s.d_trim_ctr;
+  const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 3) / 4, (uint64_t)h->n_cu * 8u));  // (four reads per block)
+  hipError_t scan_rc = hipSuccess;
+  // (kernel id 19: the three steps of the stage as one entry)
+  const int rc = timed_launch(h, s, 19, s.stream, true, [&] {
+    hipLaunchKernelGGL(femtr::trim_clip_kernel, dim3(grid), dim3(256), 0, s.stream, tp);
+    scan_rc = rocprim::exclusive_scan(s.d_trim_scan_tmp.get(), scan_bytes, s.d_keep.get(), s.d_map_off.get(), (uint64_t)0, n + 1, rocprim::plus<uint64_t>(), s.stream.s);
+    if (n && scan_rc == hipSuccess)
+      hipLaunchKernelGGL(femtr::trim_gather_kernel, dim3(grid), dim3(256), 0, s.stream, (const uint8_t *)s.bases(), (const uint64_t *)s.d_off.get(),
+                         (const uint16_t *)s.d_clip5.get(), (const uint64_t *)s.d_map_off.get(), (uint32_t)n, s.d_map_bases_alloc + kFrontPad);
+  });
+  HIP_TRY(h, scan_rc);
+  if (rc) return rc;
+  HIP_TRY(h, hipMemcpyAsync(s.h_trim_ctr, s.d_trim_ctr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
+  s.trimmed = true;
+  return FEM_OK;
+}
+
 unsigned stage_threads(uint64_t n_reads) {
   unsigned want = 12;  // (measured on the GPU box's 16-core share: 8 -> 12 threads still gains, 16 does not)
   if (const char *e = getenv("FEM_STAGE_THREADS")) want = (unsigned)std::max(1, atoi(e));
@@ -1669,7 +1733,8 @@ int fem_dev_stage_reads(fem_dev *h, int slot, const fem_read_batch *reads) {
   // ---- reads of one length: two bits per base cross the link instead of eight ----
   // (test hook, read per batch on purpose: tests/test_gpu_packed.py switches it between two batches of one handle; one
   // getenv per batch of >= 10^4 reads is not measurable)
-  const bool no_pack = testing_switch("FEM_NO_PACK");
+  // (a slot with trimming set stages its batches as characters: the trim stage reads and gathers them)
+  const bool no_pack = testing_switch("FEM_NO_PACK") || trim_on(h->slot[slot].trim);
   if (n && min_len == max_len && max_len > 0 && n_bases < 0xFFFFFFF0ull && !no_pack) {
     const uint32_t len = max_len, bpr = (len + 3u) / 4u;
     const uint64_t code_bytes = (n * bpr + 7u) & ~7ull;
@@ -1749,6 +1814,7 @@ int fem_dev_map_staged(fem_dev *h, int slot, const fem_params *p) {
   HIP_TRY(h, hipSetDevice(h->device));
   s.params = *p;
   if ((rc = ensure_outputs(h, s))) return rc;
+  if ((rc = enqueue_trim(h, s))) return rc;
   return launch_batch(h, s);
 }
 
@@ -2086,7 +2152,7 @@ static int pair_records(fem_dev *h, Slot &s, const femt::LineOptions &opt, hipSt
   if (s.n_reads & 1) return fail(h, FEM_ERR_INVALID, "a batch of read pairs holds an even number of reads");
   if (opt.rescues() && (int64_t)opt.max_insert - opt.min_insert > 65536)
     return fail(h, FEM_ERR_UNSUPPORTED, "mate rescue searches insert windows of at most 65536 (max_insert - min_insert)");
-  const femt::RescueInput ri{s.bases(), s.d_off, s.max_len, h->d_ref_raw, h->ref_bytes + 64, h->d_seq_off, h->d_seq_len};
+  const femt::RescueInput ri{s.map_bases(), s.map_off(), s.max_len, h->d_ref_raw, h->ref_bytes + 64, h->d_seq_off, h->d_seq_len};
   std::string err;
   const int rc = s.tail->pair(opt, ri, stream, &err);
   return rc ? fail(h, rc, err) : FEM_OK;
@@ -2095,7 +2161,8 @@ static int pair_records(fem_dev *h, Slot &s, const femt::LineOptions &opt, hipSt
 // What the device tail reads of the slot's batch and of the index.
 static femt::TailInput tail_input(const fem_dev *h, const Slot &s) {
   femt::TailInput in{};
-  in.bases = s.bases(), in.read_off = s.d_off, in.n_reads = (uint32_t)s.n_reads, in.max_len = s.max_len;
+  in.bases = s.map_bases(), in.read_off = s.map_off(), in.n_reads = (uint32_t)s.n_reads, in.max_len = s.max_len;
+  if (s.trimmed) in.text_bases = s.bases(), in.text_read_off = s.d_off, in.clip5 = s.d_clip5, in.clip3 = s.d_clip3;
   in.ref_raw = h->d_ref_raw, in.ref_bytes = h->ref_bytes + 64, in.seq_off = h->d_seq_off;
   in.planes = h->d_planes;
   if (s.sent_packed) in.packed = s.packed(), in.packed_bpr = s.packed_bpr, in.exc_bits = s.d_exc_bits;
@@ -2159,6 +2226,8 @@ static int tail_records(fem_dev *h, int slot, const void *out, bool copy_records
     return fail(h, FEM_ERR_INVALID, "mate tags (fem_dev_set_mate_tags) need the qualities on the device: ms:i is made from them (fem_dev_commit_text_stage, not _names_stage)");
   if (text && s.opt.sam_seq && s.host_quals)
     return fail(h, FEM_ERR_INVALID, "SEQ and QUAL in SAM order (fem_dev_set_sam_seq) need the qualities on the device: QUAL is reversed where it is written (fem_dev_commit_text_stage, not _names_stage)");
+  if (text && s.trimmed && s.host_quals)
+    return fail(h, FEM_ERR_INVALID, "a trimmed batch (fem_dev_set_trim) prints its whole QUAL from the device (fem_dev_commit_text_stage, not _names_stage)");
   if (device_quals && s.host_quals) return fail(h, FEM_ERR_STATE, "BAM records need the qualities on the device (fem_dev_commit_text_stage, not _names_stage)");
   if (text && !h->d_ref_names) return fail(h, FEM_ERR_STATE, "reference names must be uploaded first (fem_dev_upload_reference_names)");
   s.prefetch_results = false;  // this caller takes records, not the per-candidate arrays
@@ -2473,6 +2542,47 @@ int fem_dev_map_batch_submit(fem_dev *h, int slot, const fem_params *p, const fe
   int rc = fem_dev_stage_reads(h, slot, reads);
   if (rc) return rc;
   return fem_dev_map_staged(h, slot, p);
+}
+
+int fem_dev_set_trim(fem_dev *h, int slot, const fem_trim_params *tp) {
+  return with_slot(h, slot, [&](Slot &s) {
+    const fem_trim_params t = tp ? *tp : fem_trim_params{0, 0, 0};
+    if (t.trim5 < 0 || t.trim5 > 1024 || t.trim3 < 0 || t.trim3 > 1024 || t.qual < 0 || t.qual > 93)
+      return fail(h, FEM_ERR_INVALID, "trim out of range (trim5 and trim3 0..1024, qual 0 or 1..93)");
+    s.trim = t;
+    return (int)FEM_OK;
+  });
+}
+
+int fem_dev_fetch_trim(fem_dev *h, int slot, const uint16_t **clip5, const uint16_t **clip3, uint64_t *n_reads) {
+  int rc = fem_dev_sync(h, slot);
+  if (rc) return rc;
+  Slot &s = h->slot[slot];
+  if (!s.trimmed) return fail(h, FEM_ERR_STATE, "the slot's batch was mapped without trimming (fem_dev_set_trim)");
+  if (!s.clips_home) {
+    const size_t n = (size_t)s.n_reads;
+    HIP_TRY(h, s.h_clip5.ensure(std::max<size_t>(n, 1)));
+    HIP_TRY(h, s.h_clip3.ensure(std::max<size_t>(n, 1)));
+    if (n) {
+      HIP_TRY(h, hipMemcpyAsync(s.h_clip5, s.d_clip5, n * sizeof(uint16_t), hipMemcpyDeviceToHost, s.stream));
+      HIP_TRY(h, hipMemcpyAsync(s.h_clip3, s.d_clip3, n * sizeof(uint16_t), hipMemcpyDeviceToHost, s.stream));
+      HIP_TRY(h, hipStreamSynchronize(s.stream));
+    }
+    s.clips_home = true;
+  }
+  if (clip5) *clip5 = s.h_clip5;
+  if (clip3) *clip3 = s.h_clip3;
+  if (n_reads) *n_reads = s.n_reads;
+  return FEM_OK;
+}
+
+int fem_dev_trim_count(fem_dev *h, int slot, uint64_t *n_reads_trimmed, uint64_t *n_bases_trimmed) {
+  int rc = fem_dev_sync(h, slot);
+  if (rc) return rc;
+  const Slot &s = h->slot[slot];
+  if (n_reads_trimmed) *n_reads_trimmed = s.trimmed ? s.h_trim_ctr[0] : 0;
+  if (n_bases_trimmed) *n_bases_trimmed = s.trimmed ? s.h_trim_ctr[1] : 0;
+  return FEM_OK;
 }
 
 int fem_dev_map_batch_wait(fem_dev *h, int slot, fem_batch_result *out) { return fem_dev_fetch(h, slot, out); }

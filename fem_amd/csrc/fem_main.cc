@@ -17,6 +17,8 @@
 // `--mate-tags` adds MC:Z, MQ:i and ms:i to every line of a paired output, made on the device (fem_dev_set_mate_tags).
 // `--sam-seq` prints SEQ reverse-complemented and QUAL reversed on the reverse-strand lines that carry them, as the SAM
 // specification orders them, made on the device (fem_dev_set_sam_seq).
+// `--trim5 N`, `--trim3 N`, `--trim-qual Q` trim every read on the device before it is mapped (fixed counts off its ends, its
+// 3' end by quality: the running-sum rule of include/fem_hip.h) and print what was cut as soft clips (fem_dev_set_trim).
 // `--xa[=N]` folds the secondary lines of a read (of a mate) into an XA:Z field on its primary line, at most N of them and
 // FEM_XA_MAX_BYTES bytes per line, made on the device (fem_dev_set_xa).
 #include <errno.h>
@@ -100,6 +102,9 @@ void usage_map() {
   fprintf(stderr, "        --nh          write NH:i (the read's, or the mate's, lines in the output) and HI:i (which of them) on every mapped line\n");
   fprintf(stderr, "        --mate-tags   with --read2: write MC:Z, MQ:i and ms:i (the other mate's CIGAR, MAPQ and quality score, as samtools fixmate -m) on every line\n");
   fprintf(stderr, "        --xa[=N]      fold a read's secondary lines into XA:Z:(rname,+-pos,CIGAR,NM;)* on its primary line, at most N (1-1000000; default: all that fit %d bytes); the rest stay lines\n", FEM_XA_MAX_BYTES);
+  fprintf(stderr, "        --trim5 INT   trim INT (0-1024) bases off the 5' end of every read before mapping, on the GPU; printed as soft clips\n");
+  fprintf(stderr, "        --trim3 INT   trim INT (0-1024) bases off the 3' end of every read before mapping, on the GPU; printed as soft clips\n");
+  fprintf(stderr, "        --trim-qual INT  trim the 3' end of every read by quality INT (1-93) before mapping, on the GPU, keeping %d bases at the least; printed as soft clips\n", FEM_TRIM_MIN_KEEP);
   fprintf(stderr, "        --sam-seq     write SEQ reverse-complemented and QUAL reversed on reverse-strand lines (FLAG 0x10), as the SAM specification orders them\n");
   fprintf(stderr, "        -o       STR  Output SAM file \n\n");
 }
@@ -281,6 +286,7 @@ struct BatchBuf {  // everything about the batch that sits in one (GPU, slot) pa
   uint64_t n_unmapped = 0;                  // --unmapped: lines for unmapped reads of the batch
   uint64_t n_filtered = 0;                  // --strata / --max-hits: lines left out of the batch's text
   uint64_t n_xa = 0;                        // --xa: lines folded into XA:Z entries in the batch's text
+  uint64_t n_trimmed = 0, n_trimmed_bases = 0;  // --trim5 / --trim3 / --trim-qual: reads of the batch that were trimmed, and the bases cut
   fem_batch_result res{};                   // per-candidate outcome (FEM_HOST_TAIL=1)
   double t_submit = 0;
   double t_slot = 0, t_filled = 0, t_submitted = 0, t_retired = 0, t_text = 0;  // FEM_STAGE_TIMES=2: the batch's way through the stages
@@ -329,6 +335,9 @@ int map_main(int argc, char **argv) {
   bool sam_seq = false;          // --sam-seq: SEQ and QUAL of the lines with 0x10 in the reference's direction, made on the device (fem_dev_set_sam_seq)
   long long xa_entries = 0;      // --xa[=N]: secondary lines folded into XA:Z on the primary line, made on the device (fem_dev_set_xa); 0: off
   bool xa_given = false;
+  // --trim5 / --trim3 / --trim-qual: every read trimmed on the device before it is mapped, the cut bases soft clips (fem_dev_set_trim)
+  long long trim5 = 0, trim3 = 0, trim_qual = 0;
+  bool trim_given = false;
   fem_params params{12, 3, 2, 1};  // src/FEM_map.c:67-70: k and step are fixed, whatever the index header says
   int n_threads = 1, n_gpus = 1;
   // reads per batch: 250 k fills the pipeline soonest on small inputs; a batch costs three host round trips on its way through
@@ -352,6 +361,9 @@ int map_main(int argc, char **argv) {
                                      {"nh", no_argument, nullptr, 'n'},          {"mate-tags", no_argument, nullptr, 'M'},
                                      {"sam-seq", no_argument, nullptr, 'q'},
                                      {"xa", optional_argument, nullptr, 'x'},
+                                     {"trim5", required_argument, nullptr, '5'},
+                                     {"trim3", required_argument, nullptr, '3'},
+                                     {"trim-qual", required_argument, nullptr, 'm'},
                                      {nullptr, 0, nullptr, 0}};
   int c, oi = 0;
   while ((c = getopt_long(argc, argv, short_opt, long_opt, &oi)) >= 0) {
@@ -369,6 +381,17 @@ int map_main(int argc, char **argv) {
           if (!end || end == optarg || *end) xa_entries = -1;  // (not a number: refused below)
         }
         break;
+      case '5':
+      case '3':
+      case 'm': {
+        char *end = nullptr;
+        long long v = strtoll(optarg, &end, 10);
+        if (!end || end == optarg || *end) v = -1;  // (not a number: refused below)
+        (c == '5' ? trim5 : c == '3' ? trim3 : trim_qual) = v;
+        if (c == 'm' && v == 0) trim_qual = -1;  // (--trim-qual 0 is no quality: refused)
+        trim_given = true;
+        break;
+      }
       case 'r': ref_path = optarg; break;
       case 'i': index_path = optarg; break;
       case 'b': read_path = optarg; break;
@@ -461,6 +484,8 @@ int map_main(int argc, char **argv) {
   else if (strata_given && (strata < 0 || strata > 15)) bad = "Wrong number of strata (0-15).";
   else if (max_hits_given && (max_hits < 1 || max_hits > 0x7FFFFFFFll)) bad = "Wrong hit limit (>= 1).";
   else if (xa_given && xa_entries != 0x7FFFFFFFll && (xa_entries < 1 || xa_entries > 1000000)) bad = "Wrong number of --xa entries (1-1000000).";
+  else if (trim5 < 0 || trim5 > 1024 || trim3 < 0 || trim3 > 1024) bad = "Wrong number of bases to trim (0-1024).";
+  else if (trim_qual < 0 || trim_qual > 93) bad = "Wrong trimming quality (1-93).";
   else if (!ref_path) bad = "Reference file path is required.";
   else if (!index_path) bad = "Index file path is required.";
   else if (!read_path) bad = "Read file path is required.";
@@ -492,6 +517,13 @@ int map_main(int argc, char **argv) {
     const char *x = getenv(v);
     if (sam_seq && x && x[0] == '1') {
       fprintf(stderr, "--sam-seq is not supported with %s=1: SEQ and QUAL are turned on the device, with the qualities there.\n", v);
+      exit(EXIT_FAILURE);
+    }
+  }
+  for (const char *v : {"FEM_HOST_TAIL", "FEM_HOST_FORMAT", "FEM_HOST_QUALS"}) {  // (nor the whole read around its kept part: clips, SEQ and QUAL are the device's)
+    const char *x = getenv(v);
+    if (trim_given && x && x[0] == '1') {
+      fprintf(stderr, "--trim5, --trim3 and --trim-qual are not supported with %s=1: the reads are trimmed and their soft clips written on the device, with the qualities there.\n", v);
       exit(EXIT_FAILURE);
     }
   }
@@ -566,13 +598,13 @@ int map_main(int argc, char **argv) {
   // to box (the run is bound by the link in one and by the cores in the other); from 24 threads on the qualities stay on the
   // host.  FEM_HOST_QUALS=1 / FEM_DEVICE_QUALS=1 decide it by hand.
   const char *dq = getenv("FEM_DEVICE_QUALS"), *hq = getenv("FEM_HOST_QUALS");
-  const bool host_quals = device_text && !bam && !mate_tags && !sam_seq && !(dq && dq[0] == '1') && ((hq && hq[0] == '1') || n_threads >= 24);
+  const bool host_quals = device_text && !bam && !mate_tags && !sam_seq && !trim_given && !(dq && dq[0] == '1') && ((hq && hq[0] == '1') || n_threads >= 24);
   const bool splice = !host_tail && !device_text && !(spl && spl[0] == '0');
   // With the text on the device the link is what bounds the run: batches of equal-length reads then cross it at two bits per
   // base — the parser writes that form straight into the pinned staging (fem_seqfile_fill_packed ->
   // fem_dev_commit_stage_packed: no host work per base beyond the parse itself) (FEM_PACK_BASES=0: always as characters).
   const char *pk = getenv("FEM_PACK_BASES");
-  const bool pack_bases = !host_tail && !paired && !(pk && pk[0] == '0');
+  const bool pack_bases = !host_tail && !paired && !trim_given && !(pk && pk[0] == '0');  // (a trimmed batch goes as characters: the trim stage reads them)
   if (!batch_given) {
     struct stat st;
     if (stat(read_path, &st) == 0 && st.st_size >= (off_t)(1ll << 30)) batch_reads = 1000000;  // (plain FASTQ of >= ~4 M reads)
@@ -626,7 +658,9 @@ int map_main(int argc, char **argv) {
                                                                   // (--rg / --nh: the tags of a line, one line per read at the least)
                                                                   batch_bytes + batch_bytes / (unmapped ? 2 : 4) +
                                                                       // (--mate-tags: MC of a few operations, MQ, ms)
-                                                                      reads_cap0 * ((rg_arg ? 6 + strlen(rg_id) : 0) + (hit_tags ? 16 : 0) + (mate_tags ? 16 + 9 + 12 : 0)));
+                                                                      reads_cap0 * ((rg_arg ? 6 + strlen(rg_id) : 0) + (hit_tags ? 16 : 0) + (mate_tags ? 16 + 9 + 12 : 0) +
+                                                                                    // (trimming: two S operations on a line's CIGAR and on its MC; the clipped letters are part of the read's already)
+                                                                                    (trim_given ? 10 + (mate_tags ? 10 : 0) : 0)));
           // (a read over the device's limit among the first records: no reservation, the staging of its batch names the read)
           if (!rc && device_text && res_reads && res_len <= max_read_len) rc = fem_dev_reserve_batch(devs[(size_t)g], sl, res_reads, res_reads + res_reads / 8, res_len, &params);
           if (!rc && mapq) rc = fem_dev_set_mapq(devs[(size_t)g], sl, 1);
@@ -641,6 +675,10 @@ int map_main(int argc, char **argv) {
           }
           if (!rc && sam_seq) rc = fem_dev_set_sam_seq(devs[(size_t)g], sl, 1);
           if (!rc && xa_given) rc = fem_dev_set_xa(devs[(size_t)g], sl, (int32_t)xa_entries);
+          if (!rc && trim_given) {
+            const fem_trim_params tp{(int32_t)trim5, (int32_t)trim3, (int32_t)trim_qual};
+            rc = fem_dev_set_trim(devs[(size_t)g], sl, &tp);
+          }
           if (!rc && paired) {
             const fem_pair_params pp{(int32_t)min_insert, (int32_t)max_insert};
             rc = fem_dev_set_pairs(devs[(size_t)g], sl, &pp);
@@ -694,9 +732,21 @@ int map_main(int argc, char **argv) {
       for (uint64_t i = 0; i <= np; ++i) off[(size_t)i] = mate[0].off[i], off[(size_t)(np + i)] = b1 + mate[1].off[i];
       const fem_read_batch sample{bases.data(), off.data(), 2 * np};
       fem_dev *h = devs[0];
-      rc = fem_dev_stage_reads(h, 0, &sample);
-      if (!rc) rc = fem_dev_map_staged(h, 0, &params);
-      if (!rc) rc = learn_orientation ? fem_dev_estimate_library(h, 0, &lib) : fem_dev_estimate_insert(h, 0, &est);
+      rc = fem_dev_stage_reads(h, 0, &sample);  // (slot 0 carries the run's trimming: the sample is trimmed as the run's reads will be)
+      if (!rc && trim_qual > 0) {  // ... by its qualities, which go to the device in front of the mapping then; the names are not needed: empty ones
+        char *pq = nullptr, *pn = nullptr;
+        uint64_t *pno = nullptr;
+        sampled = mate[0].quals && mate[1].quals;
+        rc = !sampled ? FEM_OK : fem_dev_acquire_text_stage(h, 0, 2 * np, b1 + b2, 0, &pq, &pn, &pno);
+        if (!rc && sampled) {
+          if (b1) memcpy(pq, mate[0].quals, (size_t)b1);
+          if (b2) memcpy(pq + b1, mate[1].quals, (size_t)b2);
+          memset(pno, 0, (size_t)(2 * np + 1) * sizeof(uint64_t));
+          rc = fem_dev_commit_text_stage(h, 0, 2 * np, 0);
+        }
+      }
+      if (!rc && sampled) rc = fem_dev_map_staged(h, 0, &params);
+      if (!rc && sampled) rc = learn_orientation ? fem_dev_estimate_library(h, 0, &lib) : fem_dev_estimate_insert(h, 0, &est);
       if (rc) dev_fail(h, "insert size estimate", rc);
     }
     for (fem_seqset &s : mate) fem_seqset_free(&s);
@@ -834,7 +884,8 @@ int map_main(int argc, char **argv) {
   std::vector<TextOut> texts(3);
   for (TextOut &t : texts) text_free_q.push(&t);
   std::vector<uint64_t> per_gpu((size_t)n_gpus * 5, 0), per_gpu_proper((size_t)n_gpus, 0),
-      per_gpu_rescued((size_t)n_gpus, 0), per_gpu_rescued_disc((size_t)n_gpus, 0), per_gpu_unmapped((size_t)n_gpus, 0), per_gpu_filtered((size_t)n_gpus, 0), per_gpu_xa((size_t)n_gpus, 0);
+      per_gpu_rescued((size_t)n_gpus, 0), per_gpu_rescued_disc((size_t)n_gpus, 0), per_gpu_unmapped((size_t)n_gpus, 0), per_gpu_filtered((size_t)n_gpus, 0), per_gpu_xa((size_t)n_gpus, 0),
+      per_gpu_trimmed((size_t)n_gpus, 0), per_gpu_trimmed_bases((size_t)n_gpus, 0);
 
   // ---- writer (src/output_queue.c:60-91) ----
   std::thread writer([&] {
@@ -995,6 +1046,7 @@ int map_main(int argc, char **argv) {
         if (!rc && unmapped) rc = fem_dev_unmapped_count(h, b->slot, &b->n_unmapped);
         if (!rc && report) rc = fem_dev_filtered_count(h, b->slot, &b->n_filtered);
         if (!rc && xa_given) rc = fem_dev_xa_count(h, b->slot, &b->n_xa);
+        if (!rc && trim_given) rc = fem_dev_trim_count(h, b->slot, &b->n_trimmed, &b->n_trimmed_bases);
         const double waited = real_time() - t0;
         b->t_retired = t0 + waited;
         double placing = 0;
@@ -1035,6 +1087,7 @@ int map_main(int argc, char **argv) {
           per_gpu_unmapped[(size_t)g] += b->n_unmapped;
           per_gpu_filtered[(size_t)g] += b->n_filtered;
           per_gpu_xa[(size_t)g] += b->n_xa;
+          per_gpu_trimmed[(size_t)g] += b->n_trimmed, per_gpu_trimmed_bases[(size_t)g] += b->n_trimmed_bases;
           if (device_text) {
             n_asserted += b->sam.n_asserted;
             write_q.push(WriteItem{nullptr, b});
@@ -1078,11 +1131,13 @@ int map_main(int argc, char **argv) {
                      ? fem_dev_commit_stage_uniform(h, b->slot, b->shape.n_reads, b->shape.max_len)
                      : fem_dev_commit_stage(h, b->slot, b->shape.n_reads, b->shape.max_len);
         const double t_c1 = real_time();
+        // (--trim-qual reads the qualities in front of the mapping: on this path alone the text stage is committed first)
+        if (!rc && trim_given) rc = fem_dev_commit_text_stage(h, b->slot, b->shape.n_reads, b->shape.n_name_bytes);
         if (!rc) rc = fem_dev_map_staged(h, b->slot, &params);
         const double t_c2 = real_time();
         // (qualities and names behind the mapping's launches: the call that hands the link 140 MB can wait for room in the copy
         //  engine's queue, 8-10 ms now and then, and the kernels need none of it)
-        if (!rc && device_text)
+        if (!rc && device_text && !trim_given)
           rc = host_quals ? fem_dev_commit_names_stage(h, b->slot, b->shape.n_reads, b->shape.n_name_bytes)
                           : fem_dev_commit_text_stage(h, b->slot, b->shape.n_reads, b->shape.n_name_bytes);
         if (batch_times && real_time() - b->t_submit > 1e-3)
@@ -1388,6 +1443,13 @@ int map_main(int argc, char **argv) {
     uint64_t n_xa = 0;
     for (uint64_t x : per_gpu_xa) n_xa += x;
     fprintf(stderr, "The number of XA entries: %lu\n", (unsigned long)n_xa);
+  }
+  if (trim_given) {
+    uint64_t n_trimmed = 0, n_trimmed_bases = 0;
+    for (uint64_t x : per_gpu_trimmed) n_trimmed += x;
+    for (uint64_t x : per_gpu_trimmed_bases) n_trimmed_bases += x;
+    fprintf(stderr, "The number of trimmed reads: %lu\n", (unsigned long)n_trimmed);
+    fprintf(stderr, "The number of trimmed bases: %lu\n", (unsigned long)n_trimmed_bases);
   }
   fprintf(stderr, "Time: %fs\n", t_mapping);
   return 0;

@@ -3091,6 +3091,49 @@ static hipError_t copy_home(PinBuf<T> &dst, const DevBuf<S> &src, size_t first, 
   return hipMemcpyAsync(dst.get(), src.get() + first, count * sizeof(T), hipMemcpyDeviceToHost, stream);
 }
 
+// ---- soft clips of a trimmed batch (include/fem_hip.h, fem_dev_set_trim) ----
+// The records' CIGAR words once more with the clips of their reads as S operations (op 4) around them, in arrays of their own
+// that the text side reads in place of cigar_off / cigar: a record without FLAG 16 gets its read's clip5 in front and clip3
+// behind, one with it clip3 in front and clip5 behind (the CIGAR runs in the reference's direction), for counts > 0 only; a
+// record without operations (0x8000: it prints *) keeps none.  The records themselves (fem_batch_records, fem_batch_pairs, the
+// pairing, the spans) stay as they are.
+struct ClipParams {
+  uint32_t n_records;
+  const uint32_t *s_read;
+  const uint16_t *flag;
+  const uint32_t *cigar_off, *cigar;
+  const uint16_t *clip5, *clip3;
+  uint32_t *c_ops, *c_off, *c_cigar;  // c_ops, c_off: n_records + 1
+};
+__device__ __forceinline__ uint2 clip_sides(const ClipParams &p, uint32_t rec) {
+  const uint32_t r = p.s_read[rec], c5 = p.clip5[r], c3 = p.clip3[r];
+  return (p.flag[rec] & 16u) ? make_uint2(c3, c5) : make_uint2(c5, c3);
+}
+__global__ void __launch_bounds__(256) clip_count_kernel(ClipParams p) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > p.n_records) return;
+  uint32_t n = 0;
+  if (i < p.n_records) {
+    n = p.cigar_off[i + 1] - p.cigar_off[i];
+    if (n) {
+      const uint2 c = clip_sides(p, i);
+      n += (c.x ? 1u : 0u) + (c.y ? 1u : 0u);
+    }
+  }
+  p.c_ops[i] = n;
+}
+__global__ void __launch_bounds__(256) clip_write_kernel(ClipParams p) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= p.n_records) return;
+  const uint32_t c0 = p.cigar_off[i], c1 = p.cigar_off[i + 1];
+  if (c1 == c0) return;
+  const uint2 c = clip_sides(p, i);
+  uint32_t *w = p.c_cigar + p.c_off[i];
+  if (c.x) *w++ = (c.x << 4) | 4u;
+  for (uint32_t k = c0; k < c1; ++k) *w++ = p.cigar[k];
+  if (c.y) *w++ = (c.y << 4) | 4u;
+}
+
 // The words of h_ctl, the pinned buffer the kernels' counters come home in: 0 .. 3 run()'s ctl (2: a text's asserted records,
 // 3: bam()'s name check), 4 5 run()'s CIGAR and MD totals, 6 7 a text's size, 8 9 a line index's counts, 10 11 the fold index's (entries, folding slots), from kCtlInsert on
 // estimate_insert()'s kInsertCtl words (estimate_library(): three times as many).
@@ -3128,6 +3171,8 @@ struct Tail::Impl {
   std::string rg_id;
   // the mate tags (LineOptions::mate_tags): mate_score_kernel's number per read
   DevBuf<uint32_t> m_score;
+  // a trimmed batch (TailInput::clip5): the records' CIGARs with their S operations, for the text side
+  DevBuf<uint32_t> c_ops, c_off, c_cigar;
   PinBuf<uint32_t> h_perm, h_mtid, h_mpos0, h_pair_begin, h_pair_ctl;
   PinBuf<uint16_t> h_pflag;
   PinBuf<int32_t> h_tlen;
@@ -3259,6 +3304,27 @@ struct Tail::Impl {
     bind_records(p);
     p->n_records = nr;
     p->bases = in.bases, p->read_off = in.read_off;
+    const uint64_t *text_off = in.read_off;  // the offsets SEQ, QUAL and ms:i go by
+    if (in.clip5) {  // a trimmed batch: the whole reads' letters, the CIGARs with the clips (in front of everything that reads them)
+      const size_t b1 = (size_t)n_base + 1;
+      TAIL_TRY(c_ops.ensure(b1));
+      TAIL_TRY(c_off.ensure(b1));
+      TAIL_TRY(c_cigar.ensure(cigar.size() + 2 * (size_t)n_base + 1));
+      size_t clip_need = 16;
+      TAIL_TRY(scan_need(&clip_need, c_ops.get(), c_off.get(), 0u, b1, rocprim::plus<uint32_t>()));
+      if (clip_need > need) TAIL_TRY(scan_tmp.ensure(clip_need));
+      ClipParams c{};
+      c.n_records = n_base, c.s_read = s_read, c.flag = flag, c.cigar_off = cigar_off, c.cigar = cigar;
+      c.clip5 = in.clip5, c.clip3 = in.clip3, c.c_ops = c_ops, c.c_off = c_off, c.c_cigar = c_cigar;
+      const dim3 clip_grid((n_base + 256u) / 256u);
+      hipLaunchKernelGGL(clip_count_kernel, clip_grid, dim3(256), 0, stream, c);
+      TAIL_TRY(hipGetLastError());
+      TAIL_TRY(scan(c_ops.get(), c_off.get(), 0u, b1, rocprim::plus<uint32_t>(), stream));
+      hipLaunchKernelGGL(clip_write_kernel, clip_grid, dim3(256), 0, stream, c);
+      TAIL_TRY(hipGetLastError());
+      p->cigar_off = c_off, p->cigar = c_cigar;
+      p->bases = in.text_bases, p->read_off = text_off = in.text_read_off;
+    }
     p->quals = names.quals, p->names = names.names, p->name_off = names.name_off, p->ref_names = names.ref_names, p->ref_name_off = names.ref_name_off;
     p->line_len = line_len, p->line_off = line_off;
     p->asserted = ctl + 2;  // (ctl[2] is zero after a successful run())
@@ -3376,7 +3442,7 @@ struct Tail::Impl {
         TAIL_TRY(span[kMateScore].begin(stream));
         if (last_n) {
           const uint32_t per_block = 256u / kScoreLanes;
-          hipLaunchKernelGGL(mate_score_kernel, dim3((last_n + per_block - 1u) / per_block), dim3(256), 0, stream, names.quals, in.read_off, last_n,
+          hipLaunchKernelGGL(mate_score_kernel, dim3((last_n + per_block - 1u) / per_block), dim3(256), 0, stream, names.quals, text_off, last_n,
                              m_score.get());
           TAIL_TRY(hipGetLastError());
         }

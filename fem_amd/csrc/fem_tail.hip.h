@@ -37,6 +37,12 @@ struct TailInput {  // device pointers unless noted
   const uint32_t *n_map;       // n_reads: accepted candidates of each read
   int32_t e;
   uint64_t n_records;          // host: total accepted candidates (the "number of mapping" counter)
+  // a trimmed batch (fem_dev_set_trim): bases / read_off above are the kept parts, the mapping view, and these the whole reads
+  // and each read's clipped bases at its 5' and 3' end.  sam() and bam() print SEQ, QUAL and ms:i from the whole reads and the
+  // CIGARs with the clips as S operations around them (clip_count_kernel, clip_write_kernel).  nullptr: not trimmed.
+  const uint8_t *text_bases;
+  const uint64_t *text_read_off;
+  const uint16_t *clip5, *clip3;
 };
 
 struct TailOutput {  // pinned host memory owned by the Tail object, valid until its next run

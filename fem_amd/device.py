@@ -25,6 +25,7 @@ ABI_SYMBOLS = [
     "fem_dev_set_unmapped", "fem_dev_unmapped_count",
     "fem_dev_set_report", "fem_dev_filtered_count", "fem_dev_set_tags", "fem_dev_set_mate_tags", "fem_dev_set_sam_seq",
     "fem_dev_set_xa", "fem_dev_xa_count",
+    "fem_dev_set_trim", "fem_dev_fetch_trim", "fem_dev_trim_count",
     "fem_dev_fetch_bam", "fem_dev_fetch_bam_nowait", "fem_dev_bam_wait", "fem_dev_bgzf_compress",
 ]
 
@@ -90,6 +91,10 @@ class _RescueParams(C.Structure):
 
 class _ReportParams(C.Structure):
     _fields_ = [("strata", C.c_int32), ("max_hits", C.c_int32)]
+
+
+class _TrimParams(C.Structure):
+    _fields_ = [("trim5", C.c_int32), ("trim3", C.c_int32), ("qual", C.c_int32)]
 
 
 class _TagParams(C.Structure):
@@ -200,6 +205,10 @@ def load_hip():
     if hasattr(L, "fem_dev_set_xa"):
         L.fem_dev_set_xa.argtypes = [vp, C.c_int, C.c_int32]
         L.fem_dev_xa_count.argtypes = [vp, C.c_int, C.POINTER(u64)]
+    if hasattr(L, "fem_dev_set_trim"):
+        L.fem_dev_set_trim.argtypes = [vp, C.c_int, C.POINTER(_TrimParams)]
+        L.fem_dev_fetch_trim.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
+        L.fem_dev_trim_count.argtypes = [vp, C.c_int, C.POINTER(u64), C.POINTER(u64)]
     if hasattr(L, "fem_dev_fetch_bam"):
         L.fem_dev_fetch_bam.argtypes = [vp, C.c_int, C.c_int, C.POINTER(_BatchBam)]
         L.fem_dev_fetch_bam_nowait.argtypes = [vp, C.c_int, C.c_int, C.POINTER(_BatchBam)]
@@ -757,6 +766,25 @@ class Device:
         n = C.c_uint64()
         self._check(self._L.fem_dev_xa_count(self._h, slot, C.byref(n)))
         return int(n.value)
+
+    def set_trim(self, trim5=0, trim3=0, qual=0, slot=0):
+        """fem_dev_set_trim: the slot's batches are trimmed on the device from the next fem_dev_map_staged on: trim5 / trim3 bases
+        (0..1024) off the reads' ends, the 3' end by quality at qual (1..93; 0: off); all 0: off.  The SAM text and BAM records
+        print the clipped bases as soft clips."""
+        tp = _TrimParams(int(trim5), int(trim3), int(qual))
+        self._check(self._L.fem_dev_set_trim(self._h, slot, C.byref(tp)))
+
+    def fetch_trim(self, slot=0):
+        """fem_dev_fetch_trim: (clip5, clip3) of the slot's trimmed batch, read for read (uint16 arrays)."""
+        p5, p3, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        self._check(self._L.fem_dev_fetch_trim(self._h, slot, C.byref(p5), C.byref(p3), C.byref(n)))
+        return _copy(p5.value, n.value, np.uint16), _copy(p3.value, n.value, np.uint16)
+
+    def trim_count(self, slot=0):
+        """fem_dev_trim_count: (reads the slot's batch had trimmed, bases trimmed off them)."""
+        nr, nb = C.c_uint64(), C.c_uint64()
+        self._check(self._L.fem_dev_trim_count(self._h, slot, C.byref(nr), C.byref(nb)))
+        return int(nr.value), int(nb.value)
 
     def filtered_count(self, slot=0):
         """fem_dev_filtered_count: lines the filter left out of the slot's last SAM text or BAM."""

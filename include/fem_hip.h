@@ -646,6 +646,50 @@ int fem_dev_set_sam_seq(fem_dev *h, int slot, int on);
 int fem_dev_set_xa(fem_dev *h, int slot, int32_t max_entries);
 int fem_dev_xa_count(fem_dev *h, int slot, uint64_t *n_entries);
 
+/* ---- read trimming: soft clips made on the device (new; opt-in: the reference maps every read end to end as given, and so does
+ *      every batch without it) ----
+ * fem_dev_set_trim: trim5, trim3: 0 .. 1024 bases cut from the 5' and the 3' end of every read; qual: 0 is off, 1 .. 93 trims the 3'
+ *   end by quality.  tp == NULL or all three 0: off, every byte of every output as before and no kernel more.  Out-of-range values
+ *   are FEM_ERR_INVALID and leave the setting as it was.  Per slot and sticky, as the other options; in pair mode each mate is
+ *   trimmed on its own by the same setting.  The setting is READ AT fem_dev_map_staged / fem_dev_map_batch_submit and holds for
+ *   that batch through all of its fetches: a fem_dev_set_trim between map and fetch acts on the next batch.
+ * Rule (integers throughout; it is the specification).  For a read of length L with quality bytes b[0 .. L):
+ *   1. Fixed trims: c5 = min(trim5, L), c3f = min(trim3, L - c5).  The rest has L' = L - c5 - c3f bases, q[p] = (int)b[c5 + p] - 33.
+ *   2. Quality trim, only with Q = qual >= 1 and L' > K = FEM_TRIM_MIN_KEEP; otherwise cut = L'.  s = 0, best = 0, cut = L'; for
+ *      l = L' - 1 down to K: s += Q - q[l]; if s < 0 stop; if s > best (strictly) best = s, cut = l.  (The running-sum rule of
+ *      `bwa aln -q`; it never keeps fewer than K bases, and among equal sums it takes the largest l: the least cut.)
+ *      The same in parallel form: S[l] the suffix sum of Q - q over [l, L'); stop the largest l >= K with S[l] < 0, K - 1 if none;
+ *      cut the largest l in (stop, L') with S[l] the maximum over that range if that maximum is > 0, else L'.
+ *   3. c3 = c3f + (L' - cut).  The kept part is bases [c5, L - c3).
+ * The as-if property.  Every result of the batch is what the library gives for the batch of the kept parts staged as characters:
+ *   fem_dev_fetch, _fetch_packed, _fetch_stats, _fetch_records, _fetch_pairs, _estimate_insert, _estimate_library, every counter,
+ *   MAPQ, NH / HI, pairing, TLEN, both rescues, the line filter.  fem_batch_records and fem_batch_pairs carry no S operations: the
+ *   clips are output text only, as MAPQ and the tags are.  The text and the BAM records are that batch's with these differences:
+ *   CIGAR  a line whose CIGAR column is not * gets <n>S in front of and behind its operations, for n > 0 only: c5 in front and c3
+ *     behind without FLAG 0x10, c3 in front and c5 behind with it (the CIGAR runs in the reference's direction).  POS, NM, MD, TLEN
+ *     and the BAM bin ignore the clips.
+ *   MC:Z and XA:Z carry "the bytes the line would have printed", so the clips too; XA's byte budget counts them.
+ *   SEQ and QUAL, where a line carries them, are the whole read as given: L letters (BAM l_seq = L); with fem_dev_set_sam_seq on a
+ *     0x10 line the whole read turned.  A read whose kept part is empty is unmapped and prints its whole read, not *.
+ *   ms:i sums the other mate's whole quality string, the QUAL that is printed.
+ * Staging.  With qual > 0 the batch's qualities must have been committed with fem_dev_commit_text_stage BEFORE fem_dev_map_staged
+ *   (the trim stage waits for their copy): otherwise, and after fem_dev_commit_names_stage, FEM_ERR_STATE; so fem_dev_map_batch_submit
+ *   with qual > 0 is FEM_ERR_STATE.  With any trimming on, a text or BAM fetch of a batch whose qualities stayed on the host is
+ *   FEM_ERR_INVALID.  fem_dev_stage_reads on a slot with trimming set stages equal-length reads as characters, not packed;
+ *   fem_dev_commit_stage_packed followed by a map with trimming on is FEM_ERR_UNSUPPORTED.
+ *   fem_dev_reserve_text: a line grows by up to 2 x 5 bytes of CIGAR (MC and XA entries likewise) and by the clipped letters twice.
+ * fem_dev_fetch_trim: sync + the clip points c5 and c3 of the slot's batch, read for read (pinned memory of the slot, valid until
+ *   the slot is mapped again); FEM_ERR_STATE for a batch mapped without trimming.
+ * fem_dev_trim_count: sync + the reads with c5 + c3 > 0 and the sum of c5 + c3 over the batch; both 0 without trimming. */
+#define FEM_TRIM_MIN_KEEP 35
+typedef struct {
+  int32_t trim5, trim3; /* 0 .. 1024 */
+  int32_t qual;         /* 0: off, 1 .. 93 */
+} fem_trim_params;
+int fem_dev_set_trim(fem_dev *h, int slot, const fem_trim_params *tp);
+int fem_dev_fetch_trim(fem_dev *h, int slot, const uint16_t **clip5, const uint16_t **clip3, uint64_t *n_reads);
+int fem_dev_trim_count(fem_dev *h, int slot, uint64_t *n_reads_trimmed, uint64_t *n_bases_trimmed);
+
 /* Name of the seed + filter kernel fem_dev_map_staged would launch first for these parameters on the resident
  * index ("seed_join_kernel" — behind its "seed_select_kernel"; "seed_join_banked_kernel" where the reference's sequences
  * need more than one 32-bit coordinate space —, "seed_fast_kernel<hash>", "seed_fast_kernel<lean>" or
@@ -686,7 +730,9 @@ int fem_dev_index_info(const fem_dev *h, char *buf, uint64_t cap);
  * call; MC, MQ and ms themselves are written by the text and BAM record kernels: 7 and 11; none with the setting off);
  * 18 = the fold index kernels (XA:Z) of a fem_dev_fetch_sam / fem_dev_fetch_bam with fem_dev_set_xa on (one entry per call; where no
  * line filter is set the line index they read is made inside this id, and 14 has no entry; the entries' bytes themselves are
- * written under 7 and 11; none with the option off). */
+ * written under 7 and 11; none with the option off);
+ * of fem_dev_map_staged: 19 = the trim stage of a batch mapped with fem_dev_set_trim on (one entry per batch: trim_clip_kernel, the
+ * scan of the kept lengths, trim_gather_kernel; none with trimming off). */
 int fem_dev_set_timing(fem_dev *h, int on);
 int fem_dev_reset_timing(fem_dev *h);
 int fem_dev_kernel_time(fem_dev *h, int kernel, double *ms_total, uint64_t *launches);
