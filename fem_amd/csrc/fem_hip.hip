@@ -38,6 +38,7 @@
 #include "fem_tail.hip.h"
 #include "fem_bgzf.hip.h"
 #include "fem_trim.hip.h"
+#include "fem_adapter.hip.h"
 
 namespace {
 
@@ -61,7 +62,7 @@ constexpr size_t kPackedFrontPad = 256;  // ... and verify_kernel_packed up to 1
 constexpr uint64_t kExpandAllShare = 8;  // a packed batch with more exceptions than one per this many reads is expanded whole at commit
 constexpr uint32_t kXcapSmall = 512, kFcap = 128, kCcap = 128;
 
-constexpr int kTimedKernels = 20;  // fem_dev_kernel_time ids: 19 the trim stage (fem_dev_set_trim: clip points, scan, gather); else 0 seed (join), 1 verify, 2 generic seed, 3-5 tail, 6 pack_results_kernel (round 5; the count kernel of rounds 1-2 before), 7 SAM text, 8 seed selection, 9 pairing, 10 mate rescue, 11 BAM records, 12 BGZF, 13 MAPQ, 14 the line index with unmapped reads, 15 the line filter's line index, 16 the insert estimate, 17 the mate tags' score kernel, 18 the fold index (XA:Z); 3-5, 7, 9-11, 13-15, 17 and 18 are stages of the device tail (kTailStages), 16 is one too (fem_dev_estimate_insert counts it itself)
+constexpr int kTimedKernels = 20;  // fem_dev_kernel_time ids: 19 the trim stage (fem_dev_set_trim, fem_dev_set_adapter: adapter match, clip points, scan, gather); else 0 seed (join), 1 verify, 2 generic seed, 3-5 tail, 6 pack_results_kernel (round 5; the count kernel of rounds 1-2 before), 7 SAM text, 8 seed selection, 9 pairing, 10 mate rescue, 11 BAM records, 12 BGZF, 13 MAPQ, 14 the line index with unmapped reads, 15 the line filter's line index, 16 the insert estimate, 17 the mate tags' score kernel, 18 the fold index (XA:Z); 3-5, 7, 9-11, 13-15, 17 and 18 are stages of the device tail (kTailStages), 16 is one too (fem_dev_estimate_insert counts it itself)
 struct TimedLaunch {
   int kernel;
   hipEvent_t start, stop;
@@ -187,6 +188,18 @@ struct Slot {
   PinStageBuf<uint16_t> h_clip5, h_clip3;
   PinBuf<unsigned long long> h_trim_ctr;
   bool clips_home = false;
+  // 3' adapter matching (fem_dev_set_adapter): the setting as the kernel takes it, what the slot's mapped batch was matched by,
+  // and that batch's cuts a3 with the two counters.  A batch matched against an adapter is a trimmed batch (trimmed is set).
+  struct Adapter {
+    bool on = false;
+    uint64_t occ[2][4] = {};
+    int32_t len[2] = {0, 0}, min_overlap = 0, err_pct = 0;
+  } adapter, adapter_batch;
+  StageBuf<uint16_t> d_adapt3;
+  Buf<unsigned long long> d_adapter_ctr;
+  PinStageBuf<uint16_t> h_adapt3;
+  PinBuf<unsigned long long> h_adapter_ctr;
+  bool adapt3_home = false;
   const uint8_t *map_bases() const { return trimmed ? d_map_bases_alloc + 16 : bases(); }
   const uint64_t *map_off() const { return trimmed ? d_map_off.get() : d_off.get(); }
 };
@@ -1302,11 +1315,16 @@ bool trim_on(const fem_trim_params &t) { return t.trim5 > 0 || t.trim3 > 0 || t.
 
 // The trim stage of the batch fem_dev_map_staged is about to map, on the slot's stream in front of the selection: the slot's
 // setting becomes the batch's, trim_clip_kernel makes the clip points and kept lengths, their scan the mapping view's offsets,
-// trim_gather_kernel its characters; the two counters go home behind them.  With trimming off it launches nothing.
+// trim_gather_kernel its characters; the two counters go home behind them.  With an adapter set (fem_dev_set_adapter)
+// adapter_match_kernel runs first and hands trim_clip_kernel its cuts; that alone makes the batch a trimmed one.  With trimming
+// off and no adapter it launches nothing.
 int enqueue_trim(fem_dev *h, Slot &s) {
-  s.trim_batch = s.trim, s.trimmed = false, s.clips_home = false;
-  if (!trim_on(s.trim_batch)) return FEM_OK;
-  if (s.sent_packed) return fail(h, FEM_ERR_UNSUPPORTED, "trimming (fem_dev_set_trim) reads a batch staged as characters, not a packed one (fem_dev_commit_stage_packed)");
+  s.trim_batch = s.trim, s.adapter_batch = s.adapter, s.trimmed = false, s.clips_home = false, s.adapt3_home = false;
+  const bool adapter = s.adapter_batch.on;
+  if (!trim_on(s.trim_batch) && !adapter) return FEM_OK;
+  if (s.sent_packed)
+    return fail(h, FEM_ERR_UNSUPPORTED, adapter ? "trimming (fem_dev_set_trim, fem_dev_set_adapter) reads a batch staged as characters, not a packed one (fem_dev_commit_stage_packed)"
+                                                : "trimming (fem_dev_set_trim) reads a batch staged as characters, not a packed one (fem_dev_commit_stage_packed)");
   if (s.trim_batch.qual > 0 && (!s.text_staged || s.host_quals))
     return fail(h, FEM_ERR_STATE, "quality trimming (fem_dev_set_trim) needs the batch's qualities on the device before it is mapped (fem_dev_commit_text_stage)");
   const size_t n = (size_t)s.n_reads;
@@ -1317,6 +1335,11 @@ int enqueue_trim(fem_dev *h, Slot &s) {
   HIP_TRY(h, s.d_clip3.ensure(std::max<size_t>(n, 1)));
   HIP_TRY(h, s.d_trim_ctr.ensure(2));
   HIP_TRY(h, s.h_trim_ctr.ensure(2));
+  if (adapter) {
+    HIP_TRY(h, s.d_adapt3.ensure(std::max<size_t>(n, 1)));
+    HIP_TRY(h, s.d_adapter_ctr.ensure(2));
+    HIP_TRY(h, s.h_adapter_ctr.ensure(2));
+  }
   size_t scan_bytes = 0;
   HIP_TRY(h, rocprim::exclusive_scan(nullptr, scan_bytes, s.d_keep.get(), s.d_map_off.get(), (uint64_t)0, n + 1, rocprim::plus<uint64_t>(), s.stream.s));
   HIP_TRY(h, s.d_trim_scan_tmp.ensure(std::max<size_t>(scan_bytes, 16)));
@@ -1327,10 +1350,23 @@ int enqueue_trim(fem_dev *h, Slot &s) {
   tp.quals = s.trim_batch.qual > 0 ? s.d_quals.get() : nullptr, tp.read_off = s.d_off, tp.n_reads = (uint32_t)n;
   tp.trim5 = s.trim_batch.trim5, tp.trim3 = s.trim_batch.trim3, tp.qual = s.trim_batch.qual;
   tp.clip5 = s.d_clip5, tp.clip3 = s.d_clip3, tp.keep = s.d_keep, tp.ctr = s.d_trim_ctr;
+  tp.adapt3 = adapter ? s.d_adapt3.get() : nullptr;
+  femad::AdapterParams ap{};
+  if (adapter) {
+    HIP_TRY(h, hipMemsetAsync(s.d_adapter_ctr, 0, 2 * sizeof(unsigned long long), s.stream));
+    ap.bases = s.bases(), ap.read_off = s.d_off, ap.n_reads = (uint32_t)n;
+    ap.second_begin = s.opt.paired ? (uint32_t)(n / 2) : (uint32_t)n;  // (pair mode: the second half are the mates 2)
+    ap.trim5 = s.trim_batch.trim5, ap.trim3 = s.trim_batch.trim3;
+    ap.min_overlap = s.adapter_batch.min_overlap, ap.err_pct = s.adapter_batch.err_pct;
+    memcpy(ap.occ, s.adapter_batch.occ, sizeof ap.occ);
+    ap.len[0] = s.adapter_batch.len[0], ap.len[1] = s.adapter_batch.len[1];
+    ap.adapt3 = s.d_adapt3, ap.ctr = s.d_adapter_ctr;
+  }
   const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 3) / 4, (uint64_t)h->n_cu * 8u));  // (four reads per block)
   hipError_t scan_rc = hipSuccess;
-  // (kernel id 19: the three steps of the stage as one entry)
+  // (kernel id 19: the steps of the stage as one entry)
   const int rc = timed_launch(h, s, 19, s.stream, true, [&] {
+    if (adapter) hipLaunchKernelGGL(femad::adapter_match_kernel, dim3(grid), dim3(256), 0, s.stream, ap);
     hipLaunchKernelGGL(femtr::trim_clip_kernel, dim3(grid), dim3(256), 0, s.stream, tp);
     scan_rc = rocprim::exclusive_scan(s.d_trim_scan_tmp.get(), scan_bytes, s.d_keep.get(), s.d_map_off.get(), (uint64_t)0, n + 1, rocprim::plus<uint64_t>(), s.stream.s);
     if (n && scan_rc == hipSuccess)
@@ -1340,6 +1376,7 @@ int enqueue_trim(fem_dev *h, Slot &s) {
   HIP_TRY(h, scan_rc);
   if (rc) return rc;
   HIP_TRY(h, hipMemcpyAsync(s.h_trim_ctr, s.d_trim_ctr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
+  if (adapter) HIP_TRY(h, hipMemcpyAsync(s.h_adapter_ctr, s.d_adapter_ctr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
   s.trimmed = true;
   return FEM_OK;
 }
@@ -1733,8 +1770,8 @@ int fem_dev_stage_reads(fem_dev *h, int slot, const fem_read_batch *reads) {
   // ---- reads of one length: two bits per base cross the link instead of eight ----
   // (test hook, read per batch on purpose: tests/test_gpu_packed.py switches it between two batches of one handle; one
   // getenv per batch of >= 10^4 reads is not measurable)
-  // (a slot with trimming set stages its batches as characters: the trim stage reads and gathers them)
-  const bool no_pack = testing_switch("FEM_NO_PACK") || trim_on(h->slot[slot].trim);
+  // (a slot with trimming or an adapter set stages its batches as characters: the trim stage reads and gathers them)
+  const bool no_pack = testing_switch("FEM_NO_PACK") || trim_on(h->slot[slot].trim) || h->slot[slot].adapter.on;
   if (n && min_len == max_len && max_len > 0 && n_bases < 0xFFFFFFF0ull && !no_pack) {
     const uint32_t len = max_len, bpr = (len + 3u) / 4u;
     const uint64_t code_bytes = (n * bpr + 7u) & ~7ull;
@@ -2582,6 +2619,60 @@ int fem_dev_trim_count(fem_dev *h, int slot, uint64_t *n_reads_trimmed, uint64_t
   const Slot &s = h->slot[slot];
   if (n_reads_trimmed) *n_reads_trimmed = s.trimmed ? s.h_trim_ctr[0] : 0;
   if (n_bases_trimmed) *n_bases_trimmed = s.trimmed ? s.h_trim_ctr[1] : 0;
+  return FEM_OK;
+}
+
+int fem_dev_set_adapter(fem_dev *h, int slot, const fem_adapter_params *ap) {
+  return with_slot(h, slot, [&](Slot &s) {
+    Slot::Adapter a;
+    if (!ap || !ap->seq1) return s.adapter = a, (int)FEM_OK;
+    const char *seq[2] = {ap->seq1, ap->seq2 ? ap->seq2 : ap->seq1};
+    for (int k = 0; k < 2; ++k) {
+      const size_t m = strnlen(seq[k], 65);
+      if (m < 4 || m > 64) return fail(h, FEM_ERR_INVALID, "adapter out of range (4 to 64 letters of ACGT)");
+      for (size_t j = 0; j < m; ++j) {
+        static const char letters[] = "ACGT";
+        const char *at = strchr(letters, seq[k][j] & ~0x20);  // (lower case is accepted)
+        if (!at || !*at) return fail(h, FEM_ERR_INVALID, "adapter out of range (4 to 64 letters of ACGT)");
+        a.occ[k][at - letters] |= 1ull << j;
+      }
+      a.len[k] = (int32_t)m;
+    }
+    if (ap->min_overlap < 1 || ap->min_overlap > std::min(a.len[0], a.len[1]))
+      return fail(h, FEM_ERR_INVALID, "adapter overlap out of range (1 to the adapter's length, the shorter one's of two)");
+    if (ap->err_pct < 0 || ap->err_pct > 30) return fail(h, FEM_ERR_INVALID, "adapter error percentage out of range (0 to 30)");
+    a.on = true, a.min_overlap = ap->min_overlap, a.err_pct = ap->err_pct;
+    s.adapter = a;
+    return (int)FEM_OK;
+  });
+}
+
+int fem_dev_fetch_adapter(fem_dev *h, int slot, const uint16_t **adapt3, uint64_t *n_reads) {
+  int rc = fem_dev_sync(h, slot);
+  if (rc) return rc;
+  Slot &s = h->slot[slot];
+  if (!s.trimmed || !s.adapter_batch.on) return fail(h, FEM_ERR_STATE, "the slot's batch was mapped without an adapter (fem_dev_set_adapter)");
+  if (!s.adapt3_home) {
+    const size_t n = (size_t)s.n_reads;
+    HIP_TRY(h, s.h_adapt3.ensure(std::max<size_t>(n, 1)));
+    if (n) {
+      HIP_TRY(h, hipMemcpyAsync(s.h_adapt3, s.d_adapt3, n * sizeof(uint16_t), hipMemcpyDeviceToHost, s.stream));
+      HIP_TRY(h, hipStreamSynchronize(s.stream));
+    }
+    s.adapt3_home = true;
+  }
+  if (adapt3) *adapt3 = s.h_adapt3;
+  if (n_reads) *n_reads = s.n_reads;
+  return FEM_OK;
+}
+
+int fem_dev_adapter_count(fem_dev *h, int slot, uint64_t *n_reads_cut, uint64_t *n_bases_cut) {
+  int rc = fem_dev_sync(h, slot);
+  if (rc) return rc;
+  const Slot &s = h->slot[slot];
+  const bool on = s.trimmed && s.adapter_batch.on;
+  if (n_reads_cut) *n_reads_cut = on ? s.h_adapter_ctr[0] : 0;
+  if (n_bases_cut) *n_bases_cut = on ? s.h_adapter_ctr[1] : 0;
   return FEM_OK;
 }
 

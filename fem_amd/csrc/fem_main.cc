@@ -19,6 +19,8 @@
 // specification orders them, made on the device (fem_dev_set_sam_seq).
 // `--trim5 N`, `--trim3 N`, `--trim-qual Q` trim every read on the device before it is mapped (fixed counts off its ends, its
 // 3' end by quality: the running-sum rule of include/fem_hip.h) and print what was cut as soft clips (fem_dev_set_trim).
+// `--adapter SEQ` (`--adapter2 SEQ` for mate 2, `--adapter-overlap INT`, `--adapter-err INT`) has the 3' adapter of read-through
+// reads matched and cut on the device in front of the quality trim, printed as soft clips as well (fem_dev_set_adapter).
 // `--xa[=N]` folds the secondary lines of a read (of a mate) into an XA:Z field on its primary line, at most N of them and
 // FEM_XA_MAX_BYTES bytes per line, made on the device (fem_dev_set_xa).
 #include <errno.h>
@@ -63,6 +65,12 @@ double cpu_time() {
   return r.ru_utime.tv_sec + r.ru_stime.tv_sec + 1e-6 * (r.ru_utime.tv_usec + r.ru_stime.tv_usec);
 }
 
+// --adapter / --adapter2: 4 to 64 letters of ACGT, either case
+bool adapter_ok(const char *a) {
+  const size_t m = strlen(a);
+  return m >= 4 && m <= 64 && strspn(a, "ACGTacgt") == m;
+}
+
 void usage_main() {
   fprintf(stderr, "\nProgram: FEM (Fast and Efficient short read Mapper), MI355X build\n");
   fprintf(stderr, "Version: %s\n\n", FEM_VERSION);
@@ -105,6 +113,10 @@ void usage_map() {
   fprintf(stderr, "        --trim5 INT   trim INT (0-1024) bases off the 5' end of every read before mapping, on the GPU; printed as soft clips\n");
   fprintf(stderr, "        --trim3 INT   trim INT (0-1024) bases off the 3' end of every read before mapping, on the GPU; printed as soft clips\n");
   fprintf(stderr, "        --trim-qual INT  trim the 3' end of every read by quality INT (1-93) before mapping, on the GPU, keeping %d bases at the least; printed as soft clips\n", FEM_TRIM_MIN_KEEP);
+  fprintf(stderr, "        --adapter STR  cut the 3' adapter STR (4-64 letters of ACGT) and what follows it off every read before mapping, on the GPU, in front of --trim-qual; printed as soft clips\n");
+  fprintf(stderr, "        --adapter2 STR  with --read2: the adapter of the second mates (default: that of --adapter)\n");
+  fprintf(stderr, "        --adapter-overlap INT  the least number of adapter bases at a read's end that count as a match (1 to the adapter's length) [5]\n");
+  fprintf(stderr, "        --adapter-err INT  mismatches allowed in an adapter match, per cent of the overlap (0-30) [10]\n");
   fprintf(stderr, "        --sam-seq     write SEQ reverse-complemented and QUAL reversed on reverse-strand lines (FLAG 0x10), as the SAM specification orders them\n");
   fprintf(stderr, "        -o       STR  Output SAM file \n\n");
 }
@@ -286,6 +298,7 @@ struct BatchBuf {  // everything about the batch that sits in one (GPU, slot) pa
   uint64_t n_unmapped = 0;                  // --unmapped: lines for unmapped reads of the batch
   uint64_t n_filtered = 0;                  // --strata / --max-hits: lines left out of the batch's text
   uint64_t n_xa = 0;                        // --xa: lines folded into XA:Z entries in the batch's text
+  uint64_t n_adapter = 0, n_adapter_bases = 0;  // --adapter: reads of the batch with an adapter cut, and the bases cut
   uint64_t n_trimmed = 0, n_trimmed_bases = 0;  // --trim5 / --trim3 / --trim-qual: reads of the batch that were trimmed, and the bases cut
   fem_batch_result res{};                   // per-candidate outcome (FEM_HOST_TAIL=1)
   double t_submit = 0;
@@ -338,6 +351,10 @@ int map_main(int argc, char **argv) {
   // --trim5 / --trim3 / --trim-qual: every read trimmed on the device before it is mapped, the cut bases soft clips (fem_dev_set_trim)
   long long trim5 = 0, trim3 = 0, trim_qual = 0;
   bool trim_given = false;
+  // --adapter / --adapter2 / --adapter-overlap / --adapter-err: the 3' adapter matched and cut on the device (fem_dev_set_adapter)
+  const char *adapter1 = nullptr, *adapter2 = nullptr;
+  long long adapter_overlap = 5, adapter_err = 10;
+  bool adapter_overlap_given = false, adapter_err_given = false;
   fem_params params{12, 3, 2, 1};  // src/FEM_map.c:67-70: k and step are fixed, whatever the index header says
   int n_threads = 1, n_gpus = 1;
   // reads per batch: 250 k fills the pipeline soonest on small inputs; a batch costs three host round trips on its way through
@@ -364,6 +381,10 @@ int map_main(int argc, char **argv) {
                                      {"trim5", required_argument, nullptr, '5'},
                                      {"trim3", required_argument, nullptr, '3'},
                                      {"trim-qual", required_argument, nullptr, 'm'},
+                                     {"adapter", required_argument, nullptr, 1001},
+                                     {"adapter2", required_argument, nullptr, 1002},
+                                     {"adapter-overlap", required_argument, nullptr, 1003},
+                                     {"adapter-err", required_argument, nullptr, 1004},
                                      {nullptr, 0, nullptr, 0}};
   int c, oi = 0;
   while ((c = getopt_long(argc, argv, short_opt, long_opt, &oi)) >= 0) {
@@ -390,6 +411,17 @@ int map_main(int argc, char **argv) {
         (c == '5' ? trim5 : c == '3' ? trim3 : trim_qual) = v;
         if (c == 'm' && v == 0) trim_qual = -1;  // (--trim-qual 0 is no quality: refused)
         trim_given = true;
+        break;
+      }
+      case 1001: adapter1 = optarg; break;
+      case 1002: adapter2 = optarg; break;
+      case 1003:
+      case 1004: {
+        char *end = nullptr;
+        long long v = strtoll(optarg, &end, 10);
+        if (!end || end == optarg || *end) v = -1;  // (not a number: refused below)
+        (c == 1003 ? adapter_overlap : adapter_err) = v;
+        (c == 1003 ? adapter_overlap_given : adapter_err_given) = true;
         break;
       }
       case 'r': ref_path = optarg; break;
@@ -486,6 +518,12 @@ int map_main(int argc, char **argv) {
   else if (xa_given && xa_entries != 0x7FFFFFFFll && (xa_entries < 1 || xa_entries > 1000000)) bad = "Wrong number of --xa entries (1-1000000).";
   else if (trim5 < 0 || trim5 > 1024 || trim3 < 0 || trim3 > 1024) bad = "Wrong number of bases to trim (0-1024).";
   else if (trim_qual < 0 || trim_qual > 93) bad = "Wrong trimming quality (1-93).";
+  else if (!adapter1 && (adapter2 || adapter_overlap_given || adapter_err_given)) bad = "--adapter2, --adapter-overlap and --adapter-err need --adapter.";
+  else if (adapter2 && !read2_path) bad = "--adapter2 needs --read2.";
+  else if ((adapter1 && !adapter_ok(adapter1)) || (adapter2 && !adapter_ok(adapter2))) bad = "Wrong adapter sequence (4-64 letters of ACGT).";
+  else if (adapter1 && (adapter_overlap < 1 || adapter_overlap > (long long)std::min(strlen(adapter1), strlen(adapter2 ? adapter2 : adapter1))))
+    bad = "Wrong adapter overlap (1 to the adapter's length).";
+  else if (adapter1 && (adapter_err < 0 || adapter_err > 30)) bad = "Wrong adapter error percentage (0-30).";
   else if (!ref_path) bad = "Reference file path is required.";
   else if (!index_path) bad = "Index file path is required.";
   else if (!read_path) bad = "Read file path is required.";
@@ -527,6 +565,15 @@ int map_main(int argc, char **argv) {
       exit(EXIT_FAILURE);
     }
   }
+  for (const char *v : {"FEM_HOST_TAIL", "FEM_HOST_FORMAT", "FEM_HOST_QUALS"}) {  // (the adapter's cut is a soft clip as any other)
+    const char *x = getenv(v);
+    if (adapter1 && x && x[0] == '1') {
+      fprintf(stderr, "--adapter is not supported with %s=1: the adapter is cut and the soft clips written on the device, with the qualities there.\n", v);
+      exit(EXIT_FAILURE);
+    }
+  }
+  // what --trim5 / --trim3 / --trim-qual steer, --adapter steers too: a batch with either is a trimmed batch on the device
+  const bool clip_given = trim_given || adapter1 != nullptr;
   for (const char *v : {"FEM_HOST_TAIL", "FEM_HOST_FORMAT"}) {  // (the host formatter has no MAPQ path)
     const char *x = getenv(v);
     if (mapq && x && x[0] == '1') {
@@ -598,13 +645,13 @@ int map_main(int argc, char **argv) {
   // to box (the run is bound by the link in one and by the cores in the other); from 24 threads on the qualities stay on the
   // host.  FEM_HOST_QUALS=1 / FEM_DEVICE_QUALS=1 decide it by hand.
   const char *dq = getenv("FEM_DEVICE_QUALS"), *hq = getenv("FEM_HOST_QUALS");
-  const bool host_quals = device_text && !bam && !mate_tags && !sam_seq && !trim_given && !(dq && dq[0] == '1') && ((hq && hq[0] == '1') || n_threads >= 24);
+  const bool host_quals = device_text && !bam && !mate_tags && !sam_seq && !clip_given && !(dq && dq[0] == '1') && ((hq && hq[0] == '1') || n_threads >= 24);
   const bool splice = !host_tail && !device_text && !(spl && spl[0] == '0');
   // With the text on the device the link is what bounds the run: batches of equal-length reads then cross it at two bits per
   // base — the parser writes that form straight into the pinned staging (fem_seqfile_fill_packed ->
   // fem_dev_commit_stage_packed: no host work per base beyond the parse itself) (FEM_PACK_BASES=0: always as characters).
   const char *pk = getenv("FEM_PACK_BASES");
-  const bool pack_bases = !host_tail && !paired && !trim_given && !(pk && pk[0] == '0');  // (a trimmed batch goes as characters: the trim stage reads them)
+  const bool pack_bases = !host_tail && !paired && !clip_given && !(pk && pk[0] == '0');  // (a trimmed batch goes as characters: the trim stage reads them)
   if (!batch_given) {
     struct stat st;
     if (stat(read_path, &st) == 0 && st.st_size >= (off_t)(1ll << 30)) batch_reads = 1000000;  // (plain FASTQ of >= ~4 M reads)
@@ -660,7 +707,7 @@ int map_main(int argc, char **argv) {
                                                                       // (--mate-tags: MC of a few operations, MQ, ms)
                                                                       reads_cap0 * ((rg_arg ? 6 + strlen(rg_id) : 0) + (hit_tags ? 16 : 0) + (mate_tags ? 16 + 9 + 12 : 0) +
                                                                                     // (trimming: two S operations on a line's CIGAR and on its MC; the clipped letters are part of the read's already)
-                                                                                    (trim_given ? 10 + (mate_tags ? 10 : 0) : 0)));
+                                                                                    (clip_given ? 10 + (mate_tags ? 10 : 0) : 0)));
           // (a read over the device's limit among the first records: no reservation, the staging of its batch names the read)
           if (!rc && device_text && res_reads && res_len <= max_read_len) rc = fem_dev_reserve_batch(devs[(size_t)g], sl, res_reads, res_reads + res_reads / 8, res_len, &params);
           if (!rc && mapq) rc = fem_dev_set_mapq(devs[(size_t)g], sl, 1);
@@ -678,6 +725,10 @@ int map_main(int argc, char **argv) {
           if (!rc && trim_given) {
             const fem_trim_params tp{(int32_t)trim5, (int32_t)trim3, (int32_t)trim_qual};
             rc = fem_dev_set_trim(devs[(size_t)g], sl, &tp);
+          }
+          if (!rc && adapter1) {
+            const fem_adapter_params ap{adapter1, adapter2, (int32_t)adapter_overlap, (int32_t)adapter_err};
+            rc = fem_dev_set_adapter(devs[(size_t)g], sl, &ap);
           }
           if (!rc && paired) {
             const fem_pair_params pp{(int32_t)min_insert, (int32_t)max_insert};
@@ -885,7 +936,8 @@ int map_main(int argc, char **argv) {
   for (TextOut &t : texts) text_free_q.push(&t);
   std::vector<uint64_t> per_gpu((size_t)n_gpus * 5, 0), per_gpu_proper((size_t)n_gpus, 0),
       per_gpu_rescued((size_t)n_gpus, 0), per_gpu_rescued_disc((size_t)n_gpus, 0), per_gpu_unmapped((size_t)n_gpus, 0), per_gpu_filtered((size_t)n_gpus, 0), per_gpu_xa((size_t)n_gpus, 0),
-      per_gpu_trimmed((size_t)n_gpus, 0), per_gpu_trimmed_bases((size_t)n_gpus, 0);
+      per_gpu_trimmed((size_t)n_gpus, 0), per_gpu_trimmed_bases((size_t)n_gpus, 0),
+      per_gpu_adapter((size_t)n_gpus, 0), per_gpu_adapter_bases((size_t)n_gpus, 0);
 
   // ---- writer (src/output_queue.c:60-91) ----
   std::thread writer([&] {
@@ -1046,7 +1098,8 @@ int map_main(int argc, char **argv) {
         if (!rc && unmapped) rc = fem_dev_unmapped_count(h, b->slot, &b->n_unmapped);
         if (!rc && report) rc = fem_dev_filtered_count(h, b->slot, &b->n_filtered);
         if (!rc && xa_given) rc = fem_dev_xa_count(h, b->slot, &b->n_xa);
-        if (!rc && trim_given) rc = fem_dev_trim_count(h, b->slot, &b->n_trimmed, &b->n_trimmed_bases);
+        if (!rc && clip_given) rc = fem_dev_trim_count(h, b->slot, &b->n_trimmed, &b->n_trimmed_bases);
+        if (!rc && adapter1) rc = fem_dev_adapter_count(h, b->slot, &b->n_adapter, &b->n_adapter_bases);
         const double waited = real_time() - t0;
         b->t_retired = t0 + waited;
         double placing = 0;
@@ -1088,6 +1141,7 @@ int map_main(int argc, char **argv) {
           per_gpu_filtered[(size_t)g] += b->n_filtered;
           per_gpu_xa[(size_t)g] += b->n_xa;
           per_gpu_trimmed[(size_t)g] += b->n_trimmed, per_gpu_trimmed_bases[(size_t)g] += b->n_trimmed_bases;
+          per_gpu_adapter[(size_t)g] += b->n_adapter, per_gpu_adapter_bases[(size_t)g] += b->n_adapter_bases;
           if (device_text) {
             n_asserted += b->sam.n_asserted;
             write_q.push(WriteItem{nullptr, b});
@@ -1444,12 +1498,19 @@ int map_main(int argc, char **argv) {
     for (uint64_t x : per_gpu_xa) n_xa += x;
     fprintf(stderr, "The number of XA entries: %lu\n", (unsigned long)n_xa);
   }
-  if (trim_given) {
+  if (clip_given) {
     uint64_t n_trimmed = 0, n_trimmed_bases = 0;
     for (uint64_t x : per_gpu_trimmed) n_trimmed += x;
     for (uint64_t x : per_gpu_trimmed_bases) n_trimmed_bases += x;
     fprintf(stderr, "The number of trimmed reads: %lu\n", (unsigned long)n_trimmed);
     fprintf(stderr, "The number of trimmed bases: %lu\n", (unsigned long)n_trimmed_bases);
+  }
+  if (adapter1) {
+    uint64_t n_adapter = 0, n_adapter_bases = 0;
+    for (uint64_t x : per_gpu_adapter) n_adapter += x;
+    for (uint64_t x : per_gpu_adapter_bases) n_adapter_bases += x;
+    fprintf(stderr, "The number of reads with adapter: %lu\n", (unsigned long)n_adapter);
+    fprintf(stderr, "The number of adapter bases: %lu\n", (unsigned long)n_adapter_bases);
   }
   fprintf(stderr, "Time: %fs\n", t_mapping);
   return 0;

@@ -26,6 +26,7 @@ ABI_SYMBOLS = [
     "fem_dev_set_report", "fem_dev_filtered_count", "fem_dev_set_tags", "fem_dev_set_mate_tags", "fem_dev_set_sam_seq",
     "fem_dev_set_xa", "fem_dev_xa_count",
     "fem_dev_set_trim", "fem_dev_fetch_trim", "fem_dev_trim_count",
+    "fem_dev_set_adapter", "fem_dev_fetch_adapter", "fem_dev_adapter_count",
     "fem_dev_fetch_bam", "fem_dev_fetch_bam_nowait", "fem_dev_bam_wait", "fem_dev_bgzf_compress",
 ]
 
@@ -95,6 +96,10 @@ class _ReportParams(C.Structure):
 
 class _TrimParams(C.Structure):
     _fields_ = [("trim5", C.c_int32), ("trim3", C.c_int32), ("qual", C.c_int32)]
+
+
+class _AdapterParams(C.Structure):
+    _fields_ = [("seq1", C.c_char_p), ("seq2", C.c_char_p), ("min_overlap", C.c_int32), ("err_pct", C.c_int32)]
 
 
 class _TagParams(C.Structure):
@@ -209,6 +214,10 @@ def load_hip():
         L.fem_dev_set_trim.argtypes = [vp, C.c_int, C.POINTER(_TrimParams)]
         L.fem_dev_fetch_trim.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
         L.fem_dev_trim_count.argtypes = [vp, C.c_int, C.POINTER(u64), C.POINTER(u64)]
+    if hasattr(L, "fem_dev_set_adapter"):
+        L.fem_dev_set_adapter.argtypes = [vp, C.c_int, C.POINTER(_AdapterParams)]
+        L.fem_dev_fetch_adapter.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(u64)]
+        L.fem_dev_adapter_count.argtypes = [vp, C.c_int, C.POINTER(u64), C.POINTER(u64)]
     if hasattr(L, "fem_dev_fetch_bam"):
         L.fem_dev_fetch_bam.argtypes = [vp, C.c_int, C.c_int, C.POINTER(_BatchBam)]
         L.fem_dev_fetch_bam_nowait.argtypes = [vp, C.c_int, C.c_int, C.POINTER(_BatchBam)]
@@ -784,6 +793,29 @@ class Device:
         """fem_dev_trim_count: (reads the slot's batch had trimmed, bases trimmed off them)."""
         nr, nb = C.c_uint64(), C.c_uint64()
         self._check(self._L.fem_dev_trim_count(self._h, slot, C.byref(nr), C.byref(nb)))
+        return int(nr.value), int(nb.value)
+
+    def set_adapter(self, seq1=None, seq2=None, min_overlap=5, err_pct=10, slot=0):
+        """fem_dev_set_adapter: the slot's batches have the 3' adapter seq1 (mate 2 in pair mode: seq2, default seq1; 4..64 letters
+        of ACGT) matched and cut on the device from the next fem_dev_map_staged on, at an overlap of min_overlap bases at the least
+        and err_pct (0..30) per cent of mismatches at the most; seq1 None: off.  The cut bases are printed as soft clips."""
+        if seq1 is None:
+            self._check(self._L.fem_dev_set_adapter(self._h, slot, None))
+            return
+        enc = lambda x: x.encode("latin-1") if isinstance(x, str) else x  # noqa: E731
+        ap = _AdapterParams(enc(seq1), enc(seq2), int(min_overlap), int(err_pct))
+        self._check(self._L.fem_dev_set_adapter(self._h, slot, C.byref(ap)))
+
+    def fetch_adapter(self, slot=0):
+        """fem_dev_fetch_adapter: the adapter cuts a3 of the slot's batch, read for read (a uint16 array)."""
+        pa, n = C.c_void_p(), C.c_uint64()
+        self._check(self._L.fem_dev_fetch_adapter(self._h, slot, C.byref(pa), C.byref(n)))
+        return _copy(pa.value, n.value, np.uint16)
+
+    def adapter_count(self, slot=0):
+        """fem_dev_adapter_count: (reads of the slot's batch with an adapter cut, bases cut off them)."""
+        nr, nb = C.c_uint64(), C.c_uint64()
+        self._check(self._L.fem_dev_adapter_count(self._h, slot, C.byref(nr), C.byref(nb)))
         return int(nr.value), int(nb.value)
 
     def filtered_count(self, slot=0):

@@ -690,6 +690,38 @@ int fem_dev_set_trim(fem_dev *h, int slot, const fem_trim_params *tp);
 int fem_dev_fetch_trim(fem_dev *h, int slot, const uint16_t **clip5, const uint16_t **clip3, uint64_t *n_reads);
 int fem_dev_trim_count(fem_dev *h, int slot, uint64_t *n_reads_trimmed, uint64_t *n_bases_trimmed);
 
+/* ---- 3' adapter read-through: matched and clipped on the device (new; opt-in, as trimming is) ----
+ * When a fragment is shorter than the read the sequencer runs into the adapter, and the read as given maps nowhere at -e edits.
+ * fem_dev_set_adapter: seq1 the adapter of the reads (of mate 1 in pair mode), seq2 that of mate 2 (NULL: seq1 for both): 4 .. 64
+ *   letters of ACGT each, lower case accepted and upper-cased; min_overlap O: 1 .. the adapter's length (the shorter one's of two);
+ *   err_pct E: 0 .. 30.  ap == NULL or seq1 == NULL: off, every byte of every output as before and no kernel more.  The strings are
+ *   copied.  Out-of-range values are FEM_ERR_INVALID and leave the setting as it was.  Per slot and sticky; READ AT fem_dev_map_staged
+ *   as fem_dev_set_trim is, with the slot's pair mode (fem_dev_set_pairs) as it is then: in pair mode reads i and n_reads / 2 + i are
+ *   the mates, the reads of the second half are matched against seq2, the rest against seq1.
+ * Rule (integers throughout; it is the specification).  For a read of length L, A its adapter of m letters:
+ *   1. Fixed trims as above: c5, c3f, L' = L - c5 - c3f, x[p] = base[c5 + p].
+ *   2. Adapter match.  For p = 0 .. L' - 1: o = min(m, L' - p); mm = the number of j < o with upper(x[p + j]) != A[j], where a read
+ *      byte that is not one of ACGTacgt mismatches every letter.  p matches when o >= O and mm * 100 <= o * E.  a3 = L' - p for the
+ *      LEAST matching p, 0 when none matches.  Hamming distance only; no floor: a read that is all adapter (p = 0) keeps nothing, as
+ *      a read used up by the fixed trims does.
+ *   3. The quality trim above runs on what is left: its L' is L' - a3 (so it acts only when that is above FEM_TRIM_MIN_KEEP), and
+ *      c3 = c3f + a3 + (what the quality rule cuts).
+ *   Everything else is trimming as above: the kept part [c5, L - c3) is the mapping view, the as-if property holds, the text and BAM
+ *   carry S around every printed CIGAR and SEQ and QUAL of the whole read.  "Adapter set" counts as trimming on for the staging
+ *   rules above: a packed batch is FEM_ERR_UNSUPPORTED, fem_dev_stage_reads stages as characters, a text or BAM fetch with the
+ *   qualities on the host is FEM_ERR_INVALID.  The match itself reads no qualities: only qual > 0 needs them before the map.
+ *   fem_dev_fetch_trim and fem_dev_trim_count keep their meaning: c3 and the sums include a3; with the adapter alone they work.
+ * fem_dev_fetch_adapter: sync + a3 of the slot's batch, read for read (pinned memory of the slot, valid until the slot is mapped
+ *   again); FEM_ERR_STATE for a batch mapped without an adapter.
+ * fem_dev_adapter_count: sync + the reads with a3 > 0 and the sum of a3 over the batch; both 0 without an adapter. */
+typedef struct {
+  const char *seq1, *seq2;      /* 4 .. 64 letters of ACGT; seq2 NULL: seq1 */
+  int32_t min_overlap, err_pct; /* 1 .. the adapter's length; 0 .. 30 */
+} fem_adapter_params;
+int fem_dev_set_adapter(fem_dev *h, int slot, const fem_adapter_params *ap);
+int fem_dev_fetch_adapter(fem_dev *h, int slot, const uint16_t **adapt3, uint64_t *n_reads);
+int fem_dev_adapter_count(fem_dev *h, int slot, uint64_t *n_reads, uint64_t *n_bases);
+
 /* Name of the seed + filter kernel fem_dev_map_staged would launch first for these parameters on the resident
  * index ("seed_join_kernel" — behind its "seed_select_kernel"; "seed_join_banked_kernel" where the reference's sequences
  * need more than one 32-bit coordinate space —, "seed_fast_kernel<hash>", "seed_fast_kernel<lean>" or
@@ -731,7 +763,8 @@ int fem_dev_index_info(const fem_dev *h, char *buf, uint64_t cap);
  * 18 = the fold index kernels (XA:Z) of a fem_dev_fetch_sam / fem_dev_fetch_bam with fem_dev_set_xa on (one entry per call; where no
  * line filter is set the line index they read is made inside this id, and 14 has no entry; the entries' bytes themselves are
  * written under 7 and 11; none with the option off);
- * of fem_dev_map_staged: 19 = the trim stage of a batch mapped with fem_dev_set_trim on (one entry per batch: trim_clip_kernel, the
+ * of fem_dev_map_staged: 19 = the trim stage of a batch mapped with fem_dev_set_trim or fem_dev_set_adapter on (one entry per batch:
+ * adapter_match_kernel where an adapter is set, trim_clip_kernel, the
  * scan of the kept lengths, trim_gather_kernel; none with trimming off). */
 int fem_dev_set_timing(fem_dev *h, int on);
 int fem_dev_reset_timing(fem_dev *h);
