@@ -39,6 +39,7 @@
 #include "fem_bgzf.hip.h"
 #include "fem_trim.hip.h"
 #include "fem_adapter.hip.h"
+#include "fem_overlap.hip.h"
 
 namespace {
 
@@ -62,7 +63,7 @@ constexpr size_t kPackedFrontPad = 256;  // ... and verify_kernel_packed up to 1
 constexpr uint64_t kExpandAllShare = 8;  // a packed batch with more exceptions than one per this many reads is expanded whole at commit
 constexpr uint32_t kXcapSmall = 512, kFcap = 128, kCcap = 128;
 
-constexpr int kTimedKernels = 20;  // fem_dev_kernel_time ids: 19 the trim stage (fem_dev_set_trim, fem_dev_set_adapter: adapter match, clip points, scan, gather); else 0 seed (join), 1 verify, 2 generic seed, 3-5 tail, 6 pack_results_kernel (round 5; the count kernel of rounds 1-2 before), 7 SAM text, 8 seed selection, 9 pairing, 10 mate rescue, 11 BAM records, 12 BGZF, 13 MAPQ, 14 the line index with unmapped reads, 15 the line filter's line index, 16 the insert estimate, 17 the mate tags' score kernel, 18 the fold index (XA:Z); 3-5, 7, 9-11, 13-15, 17 and 18 are stages of the device tail (kTailStages), 16 is one too (fem_dev_estimate_insert counts it itself)
+constexpr int kTimedKernels = 20;  // fem_dev_kernel_time ids: 19 the trim stage (fem_dev_set_trim, fem_dev_set_adapter, fem_dev_set_pair_overlap: adapter_match_kernel, pair_overlap_kernel, clip points, scan, gather); else 0 seed (join), 1 verify, 2 generic seed, 3-5 tail, 6 pack_results_kernel (round 5; the count kernel of rounds 1-2 before), 7 SAM text, 8 seed selection, 9 pairing, 10 mate rescue, 11 BAM records, 12 BGZF, 13 MAPQ, 14 the line index with unmapped reads, 15 the line filter's line index, 16 the insert estimate, 17 the mate tags' score kernel, 18 the fold index (XA:Z); 3-5, 7, 9-11, 13-15, 17 and 18 are stages of the device tail (kTailStages), 16 is one too (fem_dev_estimate_insert counts it itself)
 struct TimedLaunch {
   int kernel;
   hipEvent_t start, stop;
@@ -200,6 +201,17 @@ struct Slot {
   PinStageBuf<uint16_t> h_adapt3;
   PinBuf<unsigned long long> h_adapter_ctr;
   bool adapt3_home = false;
+  // Read-through from the mates' overlap (fem_dev_set_pair_overlap): the setting, what the slot's mapped batch was matched by, and
+  // that batch's cuts v3 with the two counters.  A batch matched this way is a trimmed batch as well.
+  struct PairOverlap {
+    bool on = false;
+    int32_t min_overlap = 0, err_pct = 0;
+  } pair_overlap, pair_overlap_batch;
+  StageBuf<uint16_t> d_over3;
+  Buf<unsigned long long> d_overlap_ctr;
+  PinStageBuf<uint16_t> h_over3;
+  PinBuf<unsigned long long> h_overlap_ctr;
+  bool over3_home = false;
   const uint8_t *map_bases() const { return trimmed ? d_map_bases_alloc + 16 : bases(); }
   const uint64_t *map_off() const { return trimmed ? d_map_off.get() : d_off.get(); }
 };
@@ -1316,14 +1328,18 @@ bool trim_on(const fem_trim_params &t) { return t.trim5 > 0 || t.trim3 > 0 || t.
 // The trim stage of the batch fem_dev_map_staged is about to map, on the slot's stream in front of the selection: the slot's
 // setting becomes the batch's, trim_clip_kernel makes the clip points and kept lengths, their scan the mapping view's offsets,
 // trim_gather_kernel its characters; the two counters go home behind them.  With an adapter set (fem_dev_set_adapter)
-// adapter_match_kernel runs first and hands trim_clip_kernel its cuts; that alone makes the batch a trimmed one.  With trimming
-// off and no adapter it launches nothing.
+// adapter_match_kernel runs first and hands trim_clip_kernel its cuts; that alone makes the batch a trimmed one.  With the
+// mates' overlap set (fem_dev_set_pair_overlap) pair_overlap_kernel does the same beside it, and trim_clip_kernel takes the
+// larger cut of the two.  With trimming off, no adapter and no overlap it launches nothing.
 int enqueue_trim(fem_dev *h, Slot &s) {
-  s.trim_batch = s.trim, s.adapter_batch = s.adapter, s.trimmed = false, s.clips_home = false, s.adapt3_home = false;
-  const bool adapter = s.adapter_batch.on;
-  if (!trim_on(s.trim_batch) && !adapter) return FEM_OK;
+  s.trim_batch = s.trim, s.adapter_batch = s.adapter, s.pair_overlap_batch = s.pair_overlap;
+  s.trimmed = false, s.clips_home = false, s.adapt3_home = false, s.over3_home = false;
+  const bool adapter = s.adapter_batch.on, overlap = s.pair_overlap_batch.on;
+  if (!trim_on(s.trim_batch) && !adapter && !overlap) return FEM_OK;
+  if (overlap && !s.opt.paired) return fail(h, FEM_ERR_STATE, "the mates' overlap (fem_dev_set_pair_overlap) needs the slot in pair mode (fem_dev_set_pairs)");
   if (s.sent_packed)
-    return fail(h, FEM_ERR_UNSUPPORTED, adapter ? "trimming (fem_dev_set_trim, fem_dev_set_adapter) reads a batch staged as characters, not a packed one (fem_dev_commit_stage_packed)"
+    return fail(h, FEM_ERR_UNSUPPORTED, overlap ? "trimming (fem_dev_set_trim, fem_dev_set_adapter, fem_dev_set_pair_overlap) reads a batch staged as characters, not a packed one (fem_dev_commit_stage_packed)"
+                                        : adapter ? "trimming (fem_dev_set_trim, fem_dev_set_adapter) reads a batch staged as characters, not a packed one (fem_dev_commit_stage_packed)"
                                                 : "trimming (fem_dev_set_trim) reads a batch staged as characters, not a packed one (fem_dev_commit_stage_packed)");
   if (s.trim_batch.qual > 0 && (!s.text_staged || s.host_quals))
     return fail(h, FEM_ERR_STATE, "quality trimming (fem_dev_set_trim) needs the batch's qualities on the device before it is mapped (fem_dev_commit_text_stage)");
@@ -1339,6 +1355,11 @@ int enqueue_trim(fem_dev *h, Slot &s) {
     HIP_TRY(h, s.d_adapt3.ensure(std::max<size_t>(n, 1)));
     HIP_TRY(h, s.d_adapter_ctr.ensure(2));
     HIP_TRY(h, s.h_adapter_ctr.ensure(2));
+  }
+  if (overlap) {
+    HIP_TRY(h, s.d_over3.ensure(std::max<size_t>(n, 1)));
+    HIP_TRY(h, s.d_overlap_ctr.ensure(2));
+    HIP_TRY(h, s.h_overlap_ctr.ensure(2));
   }
   size_t scan_bytes = 0;
   HIP_TRY(h, rocprim::exclusive_scan(nullptr, scan_bytes, s.d_keep.get(), s.d_map_off.get(), (uint64_t)0, n + 1, rocprim::plus<uint64_t>(), s.stream.s));
@@ -1362,11 +1383,22 @@ int enqueue_trim(fem_dev *h, Slot &s) {
     ap.len[0] = s.adapter_batch.len[0], ap.len[1] = s.adapter_batch.len[1];
     ap.adapt3 = s.d_adapt3, ap.ctr = s.d_adapter_ctr;
   }
+  tp.over3 = overlap ? s.d_over3.get() : nullptr;
+  femov::OverlapParams vp{};
+  if (overlap) {
+    HIP_TRY(h, hipMemsetAsync(s.d_overlap_ctr, 0, 2 * sizeof(unsigned long long), s.stream));
+    vp.bases = s.bases(), vp.read_off = s.d_off, vp.n_reads = (uint32_t)n;
+    vp.trim5 = s.trim_batch.trim5, vp.trim3 = s.trim_batch.trim3;
+    vp.min_overlap = s.pair_overlap_batch.min_overlap, vp.err_pct = s.pair_overlap_batch.err_pct;
+    vp.over3 = s.d_over3, vp.ctr = s.d_overlap_ctr;
+  }
+  const uint32_t grid_pairs = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n / 2 + femov::kWaves - 1) / femov::kWaves, (uint64_t)h->n_cu * 8u));  // (a pair per wave)
   const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 3) / 4, (uint64_t)h->n_cu * 8u));  // (four reads per block)
   hipError_t scan_rc = hipSuccess;
   // (kernel id 19: the steps of the stage as one entry)
   const int rc = timed_launch(h, s, 19, s.stream, true, [&] {
     if (adapter) hipLaunchKernelGGL(femad::adapter_match_kernel, dim3(grid), dim3(256), 0, s.stream, ap);
+    if (overlap) hipLaunchKernelGGL(femov::pair_overlap_kernel, dim3(grid_pairs), dim3(64 * femov::kWaves), 0, s.stream, vp);
     hipLaunchKernelGGL(femtr::trim_clip_kernel, dim3(grid), dim3(256), 0, s.stream, tp);
     scan_rc = rocprim::exclusive_scan(s.d_trim_scan_tmp.get(), scan_bytes, s.d_keep.get(), s.d_map_off.get(), (uint64_t)0, n + 1, rocprim::plus<uint64_t>(), s.stream.s);
     if (n && scan_rc == hipSuccess)
@@ -1377,6 +1409,7 @@ int enqueue_trim(fem_dev *h, Slot &s) {
   if (rc) return rc;
   HIP_TRY(h, hipMemcpyAsync(s.h_trim_ctr, s.d_trim_ctr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
   if (adapter) HIP_TRY(h, hipMemcpyAsync(s.h_adapter_ctr, s.d_adapter_ctr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
+  if (overlap) HIP_TRY(h, hipMemcpyAsync(s.h_overlap_ctr, s.d_overlap_ctr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
   s.trimmed = true;
   return FEM_OK;
 }
@@ -1770,8 +1803,8 @@ int fem_dev_stage_reads(fem_dev *h, int slot, const fem_read_batch *reads) {
   // ---- reads of one length: two bits per base cross the link instead of eight ----
   // (test hook, read per batch on purpose: tests/test_gpu_packed.py switches it between two batches of one handle; one
   // getenv per batch of >= 10^4 reads is not measurable)
-  // (a slot with trimming or an adapter set stages its batches as characters: the trim stage reads and gathers them)
-  const bool no_pack = testing_switch("FEM_NO_PACK") || trim_on(h->slot[slot].trim) || h->slot[slot].adapter.on;
+  // (a slot with trimming, an adapter or the mates' overlap set stages its batches as characters: the trim stage reads and gathers them)
+  const bool no_pack = testing_switch("FEM_NO_PACK") || trim_on(h->slot[slot].trim) || h->slot[slot].adapter.on || h->slot[slot].pair_overlap.on;
   if (n && min_len == max_len && max_len > 0 && n_bases < 0xFFFFFFF0ull && !no_pack) {
     const uint32_t len = max_len, bpr = (len + 3u) / 4u;
     const uint64_t code_bytes = (n * bpr + 7u) & ~7ull;
@@ -2673,6 +2706,47 @@ int fem_dev_adapter_count(fem_dev *h, int slot, uint64_t *n_reads_cut, uint64_t 
   const bool on = s.trimmed && s.adapter_batch.on;
   if (n_reads_cut) *n_reads_cut = on ? s.h_adapter_ctr[0] : 0;
   if (n_bases_cut) *n_bases_cut = on ? s.h_adapter_ctr[1] : 0;
+  return FEM_OK;
+}
+
+int fem_dev_set_pair_overlap(fem_dev *h, int slot, const fem_pair_overlap_params *vp) {
+  return with_slot(h, slot, [&](Slot &s) {
+    Slot::PairOverlap v;
+    if (!vp) return s.pair_overlap = v, (int)FEM_OK;
+    if (vp->min_overlap < 8 || vp->min_overlap > 1024) return fail(h, FEM_ERR_INVALID, "pair overlap out of range (8 to 1024)");
+    if (vp->err_pct < 0 || vp->err_pct > 30) return fail(h, FEM_ERR_INVALID, "pair overlap error percentage out of range (0 to 30)");
+    v.on = true, v.min_overlap = vp->min_overlap, v.err_pct = vp->err_pct;
+    s.pair_overlap = v;
+    return (int)FEM_OK;
+  });
+}
+
+int fem_dev_fetch_pair_overlap(fem_dev *h, int slot, const uint16_t **over3, uint64_t *n_reads) {
+  int rc = fem_dev_sync(h, slot);
+  if (rc) return rc;
+  Slot &s = h->slot[slot];
+  if (!s.trimmed || !s.pair_overlap_batch.on) return fail(h, FEM_ERR_STATE, "the slot's batch was mapped without the mates' overlap (fem_dev_set_pair_overlap)");
+  if (!s.over3_home) {
+    const size_t n = (size_t)s.n_reads;
+    HIP_TRY(h, s.h_over3.ensure(std::max<size_t>(n, 1)));
+    if (n) {
+      HIP_TRY(h, hipMemcpyAsync(s.h_over3, s.d_over3, n * sizeof(uint16_t), hipMemcpyDeviceToHost, s.stream));
+      HIP_TRY(h, hipStreamSynchronize(s.stream));
+    }
+    s.over3_home = true;
+  }
+  if (over3) *over3 = s.h_over3;
+  if (n_reads) *n_reads = s.n_reads;
+  return FEM_OK;
+}
+
+int fem_dev_pair_overlap_count(fem_dev *h, int slot, uint64_t *n_pairs_cut, uint64_t *n_bases_cut) {
+  int rc = fem_dev_sync(h, slot);
+  if (rc) return rc;
+  const Slot &s = h->slot[slot];
+  const bool on = s.trimmed && s.pair_overlap_batch.on;
+  if (n_pairs_cut) *n_pairs_cut = on ? s.h_overlap_ctr[0] : 0;
+  if (n_bases_cut) *n_bases_cut = on ? s.h_overlap_ctr[1] : 0;
   return FEM_OK;
 }
 

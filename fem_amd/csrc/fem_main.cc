@@ -21,6 +21,8 @@
 // 3' end by quality: the running-sum rule of include/fem_hip.h) and print what was cut as soft clips (fem_dev_set_trim).
 // `--adapter SEQ` (`--adapter2 SEQ` for mate 2, `--adapter-overlap INT`, `--adapter-err INT`) has the 3' adapter of read-through
 // reads matched and cut on the device in front of the quality trim, printed as soft clips as well (fem_dev_set_adapter).
+// `--trim-overlap` (`--trim-overlap-min INT`, `--trim-overlap-err INT`) finds the read-through of a pair from the overlap of its
+// mates, with no adapter given, and cuts both mates at the fragment's end on the device (fem_dev_set_pair_overlap).
 // `--xa[=N]` folds the secondary lines of a read (of a mate) into an XA:Z field on its primary line, at most N of them and
 // FEM_XA_MAX_BYTES bytes per line, made on the device (fem_dev_set_xa).
 #include <errno.h>
@@ -117,6 +119,9 @@ void usage_map() {
   fprintf(stderr, "        --adapter2 STR  with --read2: the adapter of the second mates (default: that of --adapter)\n");
   fprintf(stderr, "        --adapter-overlap INT  the least number of adapter bases at a read's end that count as a match (1 to the adapter's length) [5]\n");
   fprintf(stderr, "        --adapter-err INT  mismatches allowed in an adapter match, per cent of the overlap (0-30) [10]\n");
+  fprintf(stderr, "        --trim-overlap  with --read2: where the mates of a pair overlap as a fragment shorter than the reads does, cut both at the fragment's end before mapping, on the GPU; no adapter needed; printed as soft clips\n");
+  fprintf(stderr, "        --trim-overlap-min INT  the least number of overlapping bases that count as a match (8-1024) [20]\n");
+  fprintf(stderr, "        --trim-overlap-err INT  mismatches allowed in the overlap, per cent of it (0-30) [10]\n");
   fprintf(stderr, "        --sam-seq     write SEQ reverse-complemented and QUAL reversed on reverse-strand lines (FLAG 0x10), as the SAM specification orders them\n");
   fprintf(stderr, "        -o       STR  Output SAM file \n\n");
 }
@@ -299,6 +304,7 @@ struct BatchBuf {  // everything about the batch that sits in one (GPU, slot) pa
   uint64_t n_filtered = 0;                  // --strata / --max-hits: lines left out of the batch's text
   uint64_t n_xa = 0;                        // --xa: lines folded into XA:Z entries in the batch's text
   uint64_t n_adapter = 0, n_adapter_bases = 0;  // --adapter: reads of the batch with an adapter cut, and the bases cut
+  uint64_t n_overlap = 0, n_overlap_bases = 0;  // --trim-overlap: pairs of the batch with an overlap cut, and the bases cut
   uint64_t n_trimmed = 0, n_trimmed_bases = 0;  // --trim5 / --trim3 / --trim-qual: reads of the batch that were trimmed, and the bases cut
   fem_batch_result res{};                   // per-candidate outcome (FEM_HOST_TAIL=1)
   double t_submit = 0;
@@ -355,6 +361,9 @@ int map_main(int argc, char **argv) {
   const char *adapter1 = nullptr, *adapter2 = nullptr;
   long long adapter_overlap = 5, adapter_err = 10;
   bool adapter_overlap_given = false, adapter_err_given = false;
+  // --trim-overlap / --trim-overlap-min / --trim-overlap-err: read-through found from the mates' overlap (fem_dev_set_pair_overlap)
+  bool trim_overlap = false, trim_overlap_min_given = false, trim_overlap_err_given = false;
+  long long trim_overlap_min = 20, trim_overlap_err = 10;
   fem_params params{12, 3, 2, 1};  // src/FEM_map.c:67-70: k and step are fixed, whatever the index header says
   int n_threads = 1, n_gpus = 1;
   // reads per batch: 250 k fills the pipeline soonest on small inputs; a batch costs three host round trips on its way through
@@ -385,6 +394,9 @@ int map_main(int argc, char **argv) {
                                      {"adapter2", required_argument, nullptr, 1002},
                                      {"adapter-overlap", required_argument, nullptr, 1003},
                                      {"adapter-err", required_argument, nullptr, 1004},
+                                     {"trim-overlap", no_argument, nullptr, 1005},
+                                     {"trim-overlap-min", required_argument, nullptr, 1006},
+                                     {"trim-overlap-err", required_argument, nullptr, 1007},
                                      {nullptr, 0, nullptr, 0}};
   int c, oi = 0;
   while ((c = getopt_long(argc, argv, short_opt, long_opt, &oi)) >= 0) {
@@ -422,6 +434,16 @@ int map_main(int argc, char **argv) {
         if (!end || end == optarg || *end) v = -1;  // (not a number: refused below)
         (c == 1003 ? adapter_overlap : adapter_err) = v;
         (c == 1003 ? adapter_overlap_given : adapter_err_given) = true;
+        break;
+      }
+      case 1005: trim_overlap = true; break;
+      case 1006:
+      case 1007: {
+        char *end = nullptr;
+        long long v = strtoll(optarg, &end, 10);
+        if (!end || end == optarg || *end) v = -1;  // (not a number: refused below)
+        (c == 1006 ? trim_overlap_min : trim_overlap_err) = v;
+        (c == 1006 ? trim_overlap_min_given : trim_overlap_err_given) = true;
         break;
       }
       case 'r': ref_path = optarg; break;
@@ -524,6 +546,10 @@ int map_main(int argc, char **argv) {
   else if (adapter1 && (adapter_overlap < 1 || adapter_overlap > (long long)std::min(strlen(adapter1), strlen(adapter2 ? adapter2 : adapter1))))
     bad = "Wrong adapter overlap (1 to the adapter's length).";
   else if (adapter1 && (adapter_err < 0 || adapter_err > 30)) bad = "Wrong adapter error percentage (0-30).";
+  else if (!trim_overlap && (trim_overlap_min_given || trim_overlap_err_given)) bad = "--trim-overlap-min and --trim-overlap-err need --trim-overlap.";
+  else if (trim_overlap && !read2_path) bad = "--trim-overlap needs read pairs (--read2).";
+  else if (trim_overlap && (trim_overlap_min < 8 || trim_overlap_min > 1024)) bad = "Wrong overlap of the mates (8-1024).";
+  else if (trim_overlap && (trim_overlap_err < 0 || trim_overlap_err > 30)) bad = "Wrong overlap error percentage (0-30).";
   else if (!ref_path) bad = "Reference file path is required.";
   else if (!index_path) bad = "Index file path is required.";
   else if (!read_path) bad = "Read file path is required.";
@@ -572,8 +598,15 @@ int map_main(int argc, char **argv) {
       exit(EXIT_FAILURE);
     }
   }
-  // what --trim5 / --trim3 / --trim-qual steer, --adapter steers too: a batch with either is a trimmed batch on the device
-  const bool clip_given = trim_given || adapter1 != nullptr;
+  for (const char *v : {"FEM_HOST_TAIL", "FEM_HOST_FORMAT", "FEM_HOST_QUALS"}) {  // (and so is the overlap's)
+    const char *x = getenv(v);
+    if (trim_overlap && x && x[0] == '1') {
+      fprintf(stderr, "--trim-overlap is not supported with %s=1: the mates are cut and the soft clips written on the device, with the qualities there.\n", v);
+      exit(EXIT_FAILURE);
+    }
+  }
+  // what --trim5 / --trim3 / --trim-qual steer, --adapter and --trim-overlap steer too: a batch with any is a trimmed batch on the device
+  const bool clip_given = trim_given || adapter1 != nullptr || trim_overlap;
   for (const char *v : {"FEM_HOST_TAIL", "FEM_HOST_FORMAT"}) {  // (the host formatter has no MAPQ path)
     const char *x = getenv(v);
     if (mapq && x && x[0] == '1') {
@@ -729,6 +762,10 @@ int map_main(int argc, char **argv) {
           if (!rc && adapter1) {
             const fem_adapter_params ap{adapter1, adapter2, (int32_t)adapter_overlap, (int32_t)adapter_err};
             rc = fem_dev_set_adapter(devs[(size_t)g], sl, &ap);
+          }
+          if (!rc && trim_overlap) {
+            const fem_pair_overlap_params vp{(int32_t)trim_overlap_min, (int32_t)trim_overlap_err};
+            rc = fem_dev_set_pair_overlap(devs[(size_t)g], sl, &vp);
           }
           if (!rc && paired) {
             const fem_pair_params pp{(int32_t)min_insert, (int32_t)max_insert};
@@ -937,7 +974,8 @@ int map_main(int argc, char **argv) {
   std::vector<uint64_t> per_gpu((size_t)n_gpus * 5, 0), per_gpu_proper((size_t)n_gpus, 0),
       per_gpu_rescued((size_t)n_gpus, 0), per_gpu_rescued_disc((size_t)n_gpus, 0), per_gpu_unmapped((size_t)n_gpus, 0), per_gpu_filtered((size_t)n_gpus, 0), per_gpu_xa((size_t)n_gpus, 0),
       per_gpu_trimmed((size_t)n_gpus, 0), per_gpu_trimmed_bases((size_t)n_gpus, 0),
-      per_gpu_adapter((size_t)n_gpus, 0), per_gpu_adapter_bases((size_t)n_gpus, 0);
+      per_gpu_adapter((size_t)n_gpus, 0), per_gpu_adapter_bases((size_t)n_gpus, 0),
+      per_gpu_overlap((size_t)n_gpus, 0), per_gpu_overlap_bases((size_t)n_gpus, 0);
 
   // ---- writer (src/output_queue.c:60-91) ----
   std::thread writer([&] {
@@ -1100,6 +1138,7 @@ int map_main(int argc, char **argv) {
         if (!rc && xa_given) rc = fem_dev_xa_count(h, b->slot, &b->n_xa);
         if (!rc && clip_given) rc = fem_dev_trim_count(h, b->slot, &b->n_trimmed, &b->n_trimmed_bases);
         if (!rc && adapter1) rc = fem_dev_adapter_count(h, b->slot, &b->n_adapter, &b->n_adapter_bases);
+        if (!rc && trim_overlap) rc = fem_dev_pair_overlap_count(h, b->slot, &b->n_overlap, &b->n_overlap_bases);
         const double waited = real_time() - t0;
         b->t_retired = t0 + waited;
         double placing = 0;
@@ -1142,6 +1181,7 @@ int map_main(int argc, char **argv) {
           per_gpu_xa[(size_t)g] += b->n_xa;
           per_gpu_trimmed[(size_t)g] += b->n_trimmed, per_gpu_trimmed_bases[(size_t)g] += b->n_trimmed_bases;
           per_gpu_adapter[(size_t)g] += b->n_adapter, per_gpu_adapter_bases[(size_t)g] += b->n_adapter_bases;
+          per_gpu_overlap[(size_t)g] += b->n_overlap, per_gpu_overlap_bases[(size_t)g] += b->n_overlap_bases;
           if (device_text) {
             n_asserted += b->sam.n_asserted;
             write_q.push(WriteItem{nullptr, b});
@@ -1511,6 +1551,13 @@ int map_main(int argc, char **argv) {
     for (uint64_t x : per_gpu_adapter_bases) n_adapter_bases += x;
     fprintf(stderr, "The number of reads with adapter: %lu\n", (unsigned long)n_adapter);
     fprintf(stderr, "The number of adapter bases: %lu\n", (unsigned long)n_adapter_bases);
+  }
+  if (trim_overlap) {
+    uint64_t n_overlap = 0, n_overlap_bases = 0;
+    for (uint64_t x : per_gpu_overlap) n_overlap += x;
+    for (uint64_t x : per_gpu_overlap_bases) n_overlap_bases += x;
+    fprintf(stderr, "The number of pairs with overlap cut: %lu\n", (unsigned long)n_overlap);
+    fprintf(stderr, "The number of overlap bases: %lu\n", (unsigned long)n_overlap_bases);
   }
   fprintf(stderr, "Time: %fs\n", t_mapping);
   return 0;

@@ -14,6 +14,7 @@ struct TrimParams {
   const uint8_t *quals;      // quality bytes, same offsets as the bases; read only with qual > 0
   const uint64_t *read_off;  // n_reads + 1: the whole-read view's offsets
   const uint16_t *adapt3;    // n_reads: bases the adapter match takes off the 3' end behind the fixed trims (fem_adapter.hip.h); nullptr: none
+  const uint16_t *over3;     // n_reads: the same from the mates' overlap (fem_overlap.hip.h); nullptr: none.  The larger of the two is taken
   uint32_t n_reads;
   int32_t trim5, trim3, qual;
   uint16_t *clip5, *clip3;   // n_reads
@@ -21,8 +22,8 @@ struct TrimParams {
   unsigned long long *ctr;   // [0] reads with c5 + c3 > 0, [1] the sum of c5 + c3
 };
 
-// One wave per read.  The fixed trims are arithmetic; the adapter's cut comes off what they leave, and the quality trim runs on the
-// rest.  The quality trim is the running-sum rule of the header, run from the 3'
+// One wave per read.  The fixed trims are arithmetic; the adapter's cut, or the overlap's where that is the larger, comes off what
+// they leave, and the quality trim runs on the rest.  The quality trim is the running-sum rule of the header, run from the 3'
 // end in chunks of 64 positions, lane 0 the 3'-most: s = carry + the wave's inclusive scan of Q - q; the ballot of s < 0 gives
 // the stop, the lanes in front of it are the rule's range, and a max-reduce over (s, lane) finds that range's maximum with
 // the least lane, which is the largest l.  A later chunk (smaller l) replaces the cut only with a strictly larger sum, so
@@ -38,7 +39,8 @@ __global__ void __launch_bounds__(256) trim_clip_kernel(TrimParams p) {
     const int L = (int)(p.read_off[r + 1] - off);
     const int c5 = p.trim5 < L ? p.trim5 : L;
     const int c3f = p.trim3 < L - c5 ? p.trim3 : L - c5;
-    const int a3 = p.adapt3 ? (int)p.adapt3[r] : 0;
+    const int v3 = p.over3 ? (int)p.over3[r] : 0;
+    const int a3 = p.adapt3 && (int)p.adapt3[r] > v3 ? (int)p.adapt3[r] : v3;  // (both are measured from the same end of the same L')
     const int Lp = L - c5 - c3f - a3;
     int cut = Lp;
     if (p.qual > 0 && Lp > kMinKeep) {

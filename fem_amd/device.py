@@ -27,6 +27,7 @@ ABI_SYMBOLS = [
     "fem_dev_set_xa", "fem_dev_xa_count",
     "fem_dev_set_trim", "fem_dev_fetch_trim", "fem_dev_trim_count",
     "fem_dev_set_adapter", "fem_dev_fetch_adapter", "fem_dev_adapter_count",
+    "fem_dev_set_pair_overlap", "fem_dev_fetch_pair_overlap", "fem_dev_pair_overlap_count",
     "fem_dev_fetch_bam", "fem_dev_fetch_bam_nowait", "fem_dev_bam_wait", "fem_dev_bgzf_compress",
 ]
 
@@ -100,6 +101,10 @@ class _TrimParams(C.Structure):
 
 class _AdapterParams(C.Structure):
     _fields_ = [("seq1", C.c_char_p), ("seq2", C.c_char_p), ("min_overlap", C.c_int32), ("err_pct", C.c_int32)]
+
+
+class _PairOverlapParams(C.Structure):
+    _fields_ = [("min_overlap", C.c_int32), ("err_pct", C.c_int32)]
 
 
 class _TagParams(C.Structure):
@@ -218,6 +223,10 @@ def load_hip():
         L.fem_dev_set_adapter.argtypes = [vp, C.c_int, C.POINTER(_AdapterParams)]
         L.fem_dev_fetch_adapter.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(u64)]
         L.fem_dev_adapter_count.argtypes = [vp, C.c_int, C.POINTER(u64), C.POINTER(u64)]
+    if hasattr(L, "fem_dev_set_pair_overlap"):
+        L.fem_dev_set_pair_overlap.argtypes = [vp, C.c_int, C.POINTER(_PairOverlapParams)]
+        L.fem_dev_fetch_pair_overlap.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(u64)]
+        L.fem_dev_pair_overlap_count.argtypes = [vp, C.c_int, C.POINTER(u64), C.POINTER(u64)]
     if hasattr(L, "fem_dev_fetch_bam"):
         L.fem_dev_fetch_bam.argtypes = [vp, C.c_int, C.c_int, C.POINTER(_BatchBam)]
         L.fem_dev_fetch_bam_nowait.argtypes = [vp, C.c_int, C.c_int, C.POINTER(_BatchBam)]
@@ -816,6 +825,29 @@ class Device:
         """fem_dev_adapter_count: (reads of the slot's batch with an adapter cut, bases cut off them)."""
         nr, nb = C.c_uint64(), C.c_uint64()
         self._check(self._L.fem_dev_adapter_count(self._h, slot, C.byref(nr), C.byref(nb)))
+        return int(nr.value), int(nb.value)
+
+    def set_pair_overlap(self, min_overlap=20, err_pct=10, slot=0):
+        """fem_dev_set_pair_overlap: in pair mode the slot's batches have the read-through of both mates found from their overlap
+        and cut on the device from the next fem_dev_map_staged on: the largest fragment length at which mate 1 is the reverse
+        complement of mate 2 over min_overlap (8..1024) bases at the least with err_pct (0..30) per cent of mismatches at the most;
+        min_overlap None: off.  The cut bases are printed as soft clips."""
+        if min_overlap is None:
+            self._check(self._L.fem_dev_set_pair_overlap(self._h, slot, None))
+            return
+        vp = _PairOverlapParams(int(min_overlap), int(err_pct))
+        self._check(self._L.fem_dev_set_pair_overlap(self._h, slot, C.byref(vp)))
+
+    def fetch_pair_overlap(self, slot=0):
+        """fem_dev_fetch_pair_overlap: the overlap cuts v3 of the slot's batch, read for read (a uint16 array)."""
+        pv, n = C.c_void_p(), C.c_uint64()
+        self._check(self._L.fem_dev_fetch_pair_overlap(self._h, slot, C.byref(pv), C.byref(n)))
+        return _copy(pv.value, n.value, np.uint16)
+
+    def pair_overlap_count(self, slot=0):
+        """fem_dev_pair_overlap_count: (pairs of the slot's batch with an overlap cut, bases cut off both mates)."""
+        nr, nb = C.c_uint64(), C.c_uint64()
+        self._check(self._L.fem_dev_pair_overlap_count(self._h, slot, C.byref(nr), C.byref(nb)))
         return int(nr.value), int(nb.value)
 
     def filtered_count(self, slot=0):

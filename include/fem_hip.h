@@ -722,6 +722,43 @@ int fem_dev_set_adapter(fem_dev *h, int slot, const fem_adapter_params *ap);
 int fem_dev_fetch_adapter(fem_dev *h, int slot, const uint16_t **adapt3, uint64_t *n_reads);
 int fem_dev_adapter_count(fem_dev *h, int slot, uint64_t *n_reads, uint64_t *n_bases);
 
+/* ---- read-through found from the mates' overlap: no adapter sequence needed (new; opt-in, pair mode only) ----
+ * When a fragment is shorter than the reads BOTH mates read through it, and mate 1 is the reverse complement of mate 2 over the
+ * whole fragment.  That overlap gives the fragment's length, and so the cut of both mates, from 1 read-through base on.
+ * fem_dev_set_pair_overlap: min_overlap O: 8 .. 1024; err_pct E: 0 .. 30.  vp == NULL: off, every byte of every output as before and
+ *   no kernel more.  Out-of-range values are FEM_ERR_INVALID and leave the setting as it was.  Per slot and sticky; READ AT
+ *   fem_dev_map_staged as fem_dev_set_trim is; a set between map and fetch acts on the next batch.  A batch mapped with it on while
+ *   the slot is not in pair mode (fem_dev_set_pairs) is FEM_ERR_STATE.
+ * Rule (integers throughout; it is the specification).  Reads i and n_reads / 2 + i of a batch are the mates of pair i.
+ *   1. Fixed trims as above on each mate: c5, c3f, L1', L2'; x[j] = the base of mate 1 at c5 + j, y[j] the same for mate 2.
+ *   2. Base classes: up(b) is the upper-case letter for ACGTacgt and 0 for every other byte, comp the complement on letters.  A
+ *      position whose up is 0 matches nothing, in either mate, also when both mates have such a byte at aligned places.
+ *   3. The window of a candidate fragment length f, 1 <= f < max(L1', L2'): mate 1 covers the fragment's positions [0, min(f, L1')),
+ *      mate 2 covers [max(0, f - L2'), f); their common part is lo = max(0, f - L2'), hi = min(f, L1'), o = hi - lo.
+ *   4. The test: mm = the number of j in [lo, hi) for which up(x[j]) is 0, up(y[f - 1 - j]) is 0, or
+ *      up(x[j]) != comp(up(y[f - 1 - j])).  f matches when o >= O and mm * 100 <= o * E.  Hamming distance only; the qualities are
+ *      not looked at.
+ *   5. The pair's fragment length F is the LARGEST matching f (the least cut: in a tandem repeat several f match), 0 when none does.
+ *   6. The cuts: v3 of mate k = max(0, Lk' - F) when F > 0, else 0.  As f < max(L1', L2') a matching pair cuts at least one base of
+ *      at least one mate; as F >= O every mate keeps min(Lk', O) bases at the least: the rule makes no empty read.
+ *   7. Composition: the adapter's a3 (fem_dev_set_adapter, where set as well) and v3 are measured from the same end of the same L';
+ *      the 3' cut behind the fixed trims is max(a3, v3).  The quality trim runs on what that leaves exactly as it runs behind a3
+ *      alone, and everything after that is trimming as above: the mapping view and the as-if property, the soft clips in CIGAR,
+ *      MC:Z and XA:Z, the insert estimate sampling the reads as the run trims them.
+ *   8. The overlap is the sequencer's geometry, not the library's: the rule is the same under every fem_dev_set_orientation.
+ *   "Overlap set" counts as trimming on for the staging rules above: a packed batch is FEM_ERR_UNSUPPORTED, fem_dev_stage_reads
+ *   stages as characters.  It needs no qualities.  fem_dev_fetch_adapter and fem_dev_adapter_count keep their meaning, the
+ *   adapter's own matches; c3 and the sums of fem_dev_fetch_trim / fem_dev_trim_count include the composed cut, every cut base once.
+ * fem_dev_fetch_pair_overlap: sync + v3 of the slot's batch, read for read (pinned memory of the slot, valid until the slot is
+ *   mapped again); FEM_ERR_STATE for a batch mapped without the setting.
+ * fem_dev_pair_overlap_count: sync + the pairs with F > 0 and the sum of v3 over both mates; both 0 without the setting. */
+typedef struct {
+  int32_t min_overlap, err_pct; /* 8 .. 1024; 0 .. 30 */
+} fem_pair_overlap_params;
+int fem_dev_set_pair_overlap(fem_dev *h, int slot, const fem_pair_overlap_params *vp);
+int fem_dev_fetch_pair_overlap(fem_dev *h, int slot, const uint16_t **over3, uint64_t *n_reads);
+int fem_dev_pair_overlap_count(fem_dev *h, int slot, uint64_t *n_pairs, uint64_t *n_bases);
+
 /* Name of the seed + filter kernel fem_dev_map_staged would launch first for these parameters on the resident
  * index ("seed_join_kernel" — behind its "seed_select_kernel"; "seed_join_banked_kernel" where the reference's sequences
  * need more than one 32-bit coordinate space —, "seed_fast_kernel<hash>", "seed_fast_kernel<lean>" or
@@ -763,8 +800,8 @@ int fem_dev_index_info(const fem_dev *h, char *buf, uint64_t cap);
  * 18 = the fold index kernels (XA:Z) of a fem_dev_fetch_sam / fem_dev_fetch_bam with fem_dev_set_xa on (one entry per call; where no
  * line filter is set the line index they read is made inside this id, and 14 has no entry; the entries' bytes themselves are
  * written under 7 and 11; none with the option off);
- * of fem_dev_map_staged: 19 = the trim stage of a batch mapped with fem_dev_set_trim or fem_dev_set_adapter on (one entry per batch:
- * adapter_match_kernel where an adapter is set, trim_clip_kernel, the
+ * of fem_dev_map_staged: 19 = the trim stage of a batch mapped with fem_dev_set_trim, fem_dev_set_adapter or fem_dev_set_pair_overlap on (one
+ * entry per batch: adapter_match_kernel where an adapter is set, pair_overlap_kernel where the mates' overlap is, trim_clip_kernel, the
  * scan of the kept lengths, trim_gather_kernel; none with trimming off). */
 int fem_dev_set_timing(fem_dev *h, int on);
 int fem_dev_reset_timing(fem_dev *h);
