@@ -40,6 +40,7 @@
 #include "fem_trim.hip.h"
 #include "fem_adapter.hip.h"
 #include "fem_overlap.hip.h"
+#include "fem_coverage.h"
 
 namespace {
 
@@ -163,6 +164,7 @@ struct Slot {
   // state of the last launch
   fem_params params{};
   bool mapped = false, synced = false;
+  bool covered = false;  // the slot's mapped batch has been added to the coverage track (its first text or BAM fetch does that)
   uint64_t stats[5] = {0, 0, 0, 0, 0};
   uint32_t n_cand = 0;
   std::vector<TimedLaunch> pending;
@@ -335,6 +337,16 @@ struct fem_dev {
   uint32_t n_seq = 0;
   std::vector<uint64_t> seq_off;
   std::vector<uint32_t> seq_len;
+  // the coverage track (fem_dev_set_coverage): the setting, the windows' layout (host and device) and the bins, which every slot's
+  // first text of a batch adds to (Slot::covered) and which stay until the setting changes
+  struct Coverage {
+    bool on = false;
+    fem_coverage_params set{0, 0, 0};
+    uint64_t n_bins = 0;
+    std::vector<uint64_t> bin_off;  // n_seq + 1
+    Buf<uint64_t> d_bin_off;
+    Buf<unsigned long long> d_bins;
+  } coverage;
   Slot slot[kSlots];
   bool timing = false;
   int verify_blocks_per_cu = 0;  // resident 256-thread blocks of verify_kernel per CU (queried once)
@@ -1058,6 +1070,7 @@ int launch_batch(fem_dev *h, Slot &s) {
   }
   s.mapped = true;
   s.synced = false;
+  s.covered = false;
   return FEM_OK;
 }
 
@@ -1574,7 +1587,9 @@ int fem_dev_upload_reference(fem_dev *h, uint32_t n_seq, const char *const *seq,
   auto drop_reference = [&]() {
     h->d_ref_raw.release(), h->d_seq_off.release(), h->d_seq_len.release(), h->d_planes.release();
     h->ref_bytes = 0, h->n_seq = 0;
+    h->coverage = fem_dev::Coverage{};  // (the track's windows were the old reference's: off)
   };
+  if (h->coverage.on) HIP_TRY(h, hipDeviceSynchronize());  // (a text that was not waited for may still be adding to the bins that go)
   drop_reference();
   // 64 bytes of slack so that 4-byte window reads at the very end stay inside the allocation
   HIP_TRY(h, h->d_ref_raw.ensure(total + 128));
@@ -2338,6 +2353,21 @@ static int text_done(fem_dev *h, int slot, const TailFront &f, const char *tag, 
   return FEM_OK;
 }
 
+// The coverage field of a text's or BAM fetch's options (fem_dev_set_coverage, rule 4): the first one of the slot's batch carries
+// the track and so adds the batch's lines; every other one, and every one with the option off, carries none.  The batch counts
+// as added (text_covered, behind sam() / bam() whether or not they succeeded) once coverage_kernel has been queued for it: a fetch
+// that failed in front of the kernel leaves the batch to the next one, one that failed behind it is not added twice.
+static femt::LineOptions::Coverage text_coverage(fem_dev *h, Slot &s) {
+  femt::LineOptions::Coverage c{};
+  if (!h->coverage.on || s.covered) return c;
+  c.window = h->coverage.set.window, c.all_hits = h->coverage.set.all_hits != 0, c.min_mapq = h->coverage.set.min_mapq;
+  c.n_seq = h->n_seq, c.bin_off = h->coverage.d_bin_off, c.seq_len = h->d_seq_len, c.bins = h->coverage.d_bins;
+  return c;
+}
+static void text_covered(Slot &s) {
+  if (s.opt.covers() && s.tail->coverage_queued()) s.covered = true;
+}
+
 int fem_dev_fetch_records(fem_dev *h, int slot, fem_batch_records *out) {
   TailFront f{};
   int rc = tail_records(h, slot, out, true, false, &f);
@@ -2356,7 +2386,9 @@ static int fetch_sam(fem_dev *h, int slot, fem_batch_sam *out, bool wait) {
   Slot &s = h->slot[slot];
   femt::SamOutput text{};
   std::string err;
+  s.opt.coverage = text_coverage(h, s);
   rc = s.tail->sam(f.in, sam_input(h, s), s.opt, f.stream, h->n_cu, &text, &err, wait, &h->text_gate);
+  text_covered(s);
   if (rc) return fail(h, rc, err);
   if ((rc = text_done(h, slot, f, "fetch_sam", wait ? 7 : -1))) return rc;
   s.qual_at = text.qual_at;
@@ -2376,7 +2408,9 @@ static int fetch_bam(fem_dev *h, int slot, int level, fem_batch_bam *out, bool w
   femt::BamOutput bam{};
   float ms_bgzf = 0.f;
   std::string err;
+  s.opt.coverage = text_coverage(h, s);
   rc = s.tail->bam(f.in, sam_input(h, s), s.opt, level, f.stream, h->n_cu, &bam, &err, h->timing ? &ms_bgzf : nullptr, wait, &h->text_gate);
+  text_covered(s);
   if (rc) return fail(h, rc, err);
   if ((rc = text_done(h, slot, f, "fetch_bam", 11))) return rc;  // (bam() has waited for its records' stage: the compressor does)
   if (h->timing) {
@@ -2490,6 +2524,81 @@ int fem_dev_set_xa(fem_dev *h, int slot, int32_t max_entries) {
   });
 }
 int fem_dev_xa_count(fem_dev *h, int slot, uint64_t *n) { return line_count(h, slot, n, &femt::LineCounts::n_xa, false); }
+
+// ---- the coverage track: bins of the handle, added to by every slot's texts (Tail::lines, coverage_kernel) ----
+// Waits for everything the slots have queued: a text that was not waited for may still be adding.
+static int coverage_quiet(fem_dev *h) {
+  HIP_TRY(h, hipSetDevice(h->device));
+  for (Slot &s : h->slot) {
+    if (s.stream) HIP_TRY(h, hipStreamSynchronize(s.stream));
+    if (s.out_stream) HIP_TRY(h, hipStreamSynchronize(s.out_stream));
+  }
+  return FEM_OK;
+}
+
+int fem_dev_set_coverage(fem_dev *h, const fem_coverage_params *cp) {
+  if (!h) return FEM_ERR_INVALID;
+  FEM_LOCK(h);
+  if (int rc = coverage_quiet(h)) return rc;
+  if (!cp) {
+    h->coverage = fem_dev::Coverage{};
+    return FEM_OK;
+  }
+  if (!h->d_ref_raw || !h->n_seq) return fail(h, FEM_ERR_STATE, "the reference must be uploaded first (fem_dev_upload_reference)");
+  if (cp->window < 1 || cp->window > femc::kMaxWindow) return fail(h, FEM_ERR_INVALID, "coverage window out of range (1 .. 1000000)");
+  if (cp->all_hits != 0 && cp->all_hits != 1) return fail(h, FEM_ERR_INVALID, "coverage all_hits out of range (0 or 1)");
+  if (cp->min_mapq < 0 || cp->min_mapq > 60) return fail(h, FEM_ERR_INVALID, "coverage min_mapq out of range (0 .. 60)");
+  std::vector<uint64_t> bin_off((size_t)h->n_seq + 1);
+  uint64_t n_bins = 0;
+  if (femc::layout(h->n_seq, h->seq_len.data(), cp->window, bin_off.data(), &n_bins) != 0)
+    return fail(h, FEM_ERR_INVALID, "more than 2^29 coverage windows (" + std::to_string(n_bins) + "); the least window that fits is " +
+                                        std::to_string(femc::min_window(h->n_seq, h->seq_len.data())));
+  // (in buffers of their own first: a failure leaves the setting, and the track, as they were)
+  Buf<uint64_t> d_bin_off;
+  Buf<unsigned long long> d_bins;
+  HIP_TRY(h, d_bin_off.ensure(bin_off.size()));
+  HIP_TRY(h, d_bins.ensure(std::max<uint64_t>(n_bins, 1)));
+  HIP_TRY(h, hipMemcpy(d_bin_off, bin_off.data(), bin_off.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+  HIP_TRY(h, hipMemset(d_bins, 0, std::max<uint64_t>(n_bins, 1) * sizeof(unsigned long long)));
+  HIP_TRY(h, hipDeviceSynchronize());  // (the slots' streams do not wait for the null stream's)
+  fem_dev::Coverage &c = h->coverage;
+  c.on = true, c.set = *cp, c.n_bins = n_bins, c.bin_off = std::move(bin_off);
+  c.d_bin_off = std::move(d_bin_off), c.d_bins = std::move(d_bins);
+  return FEM_OK;
+}
+
+int fem_dev_coverage_layout(const fem_dev *h, uint64_t *n_bins, uint64_t *bin_off) {
+  if (!h) return FEM_ERR_INVALID;
+  if (!h->coverage.on) return FEM_ERR_STATE;
+  if (n_bins) *n_bins = h->coverage.n_bins;
+  if (bin_off) std::copy(h->coverage.bin_off.begin(), h->coverage.bin_off.end(), bin_off);
+  return FEM_OK;
+}
+
+int fem_dev_fetch_coverage(fem_dev *h, uint64_t *bins, uint64_t cap) {
+  if (!h) return FEM_ERR_INVALID;
+  FEM_LOCK(h);
+  if (!h->coverage.on) return fail(h, FEM_ERR_STATE, "the coverage track is off (fem_dev_set_coverage)");
+  if (cap < h->coverage.n_bins || (!bins && h->coverage.n_bins)) return fail(h, FEM_ERR_INVALID, "room for fewer bins than the track has (fem_dev_coverage_layout)");
+  if (int rc = coverage_quiet(h)) return rc;
+  if (h->coverage.n_bins) HIP_TRY(h, hipMemcpy(bins, h->coverage.d_bins, h->coverage.n_bins * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return FEM_OK;
+}
+
+int fem_dev_reset_coverage(fem_dev *h) {
+  if (!h) return FEM_ERR_INVALID;
+  FEM_LOCK(h);
+  if (!h->coverage.on) return fail(h, FEM_ERR_STATE, "the coverage track is off (fem_dev_set_coverage)");
+  if (int rc = coverage_quiet(h)) return rc;
+  HIP_TRY(h, hipMemset(h->coverage.d_bins, 0, std::max<uint64_t>(h->coverage.n_bins, 1) * sizeof(unsigned long long)));
+  HIP_TRY(h, hipDeviceSynchronize());
+  return FEM_OK;
+}
+
+int fem_dbg_stage_ms(fem_dev *h, int slot, int stage, float *ms) {
+  if (!ms || stage < 0 || stage >= femt::kStages) return FEM_ERR_INVALID;
+  return with_slot(h, slot, [&](Slot &s) { return *ms = s.tail ? s.tail->stage_ms((femt::Stage)stage) : -1.f, (int)FEM_OK; });
+}
 
 int fem_dev_set_report(fem_dev *h, int slot, const fem_report_params *rp) {
   return with_slot(h, slot, [&](Slot &s) {

@@ -1,6 +1,7 @@
 // fem_host.cc — host side of the drop-in (see fem_host.h).  C++17, OpenMP for the per-read loops.
 #include "fem_host.h"
 #include "fem_pack.h"
+#include "fem_coverage.h"
 
 #include <fcntl.h>
 #include <omp.h>
@@ -2202,6 +2203,55 @@ int fem_records_sam_refs(const fem_tail_ref *ref, const fem_read_refs *reads, co
     return f;
   };
   return records_sam_parts_impl(ref, reads->n, read_of, rv, n_threads, buf, cap, parts, n_asserted);
+}
+
+// ------------------------------------------------------------------------------------------------
+// coverage track (`FEM map --coverage`): the window arithmetic (fem_coverage.h) and the BED text
+// ------------------------------------------------------------------------------------------------
+int fem_coverage_layout(uint32_t n_seq, const uint32_t *seq_len, int32_t window, uint64_t *bin_off, uint64_t *n_bins) {
+  return femc::layout(n_seq, seq_len, window, bin_off, n_bins);
+}
+int32_t fem_coverage_min_window(uint32_t n_seq, const uint32_t *seq_len) { return seq_len || !n_seq ? femc::min_window(n_seq, seq_len) : 0; }
+
+int fem_coverage_write(FILE *out, uint32_t n_seq, const char *names, const uint64_t *name_off, const uint32_t *seq_len, int32_t window,
+                       const uint64_t *bins, uint64_t *total) {
+  uint64_t n_bins = 0;
+  if (!out || (n_seq && (!names || !name_off)) || femc::layout(n_seq, seq_len, window, nullptr, &n_bins) != 0 || (n_bins && !bins)) return -1;
+  auto put_u64 = [](char *w, uint64_t v) {
+    char tmp[20];
+    int n = 0;
+    do tmp[n++] = (char)('0' + v % 10u), v /= 10u; while (v);
+    while (n) *w++ = tmp[--n];
+    return w;
+  };
+  std::vector<char> buf(1 << 16);
+  size_t used = 0;
+  uint64_t k = 0, sum = 0;
+  for (uint32_t t = 0; t < n_seq; ++t) {
+    const size_t name_len = (size_t)(name_off[t + 1] - name_off[t]);
+    if (buf.size() < 2 * (name_len + 128)) buf.resize(2 * (name_len + 128));
+    for (uint64_t start = 0; start < seq_len[t]; start += (uint32_t)window, ++k) {
+      if (used + name_len + 128 > buf.size()) {
+        if (fwrite(buf.data(), 1, used, out) != used) return -3;
+        used = 0;
+      }
+      const uint64_t end = std::min<uint64_t>(start + (uint32_t)window, seq_len[t]), len = end - start, bases = bins[k];
+      const uint64_t h = (bases * 100u + len / 2u) / len;
+      char *w = buf.data() + used;
+      memcpy(w, names + name_off[t], name_len);
+      w += name_len;
+      *w++ = '\t', w = put_u64(w, start);
+      *w++ = '\t', w = put_u64(w, end);
+      *w++ = '\t', w = put_u64(w, bases);
+      *w++ = '\t', w = put_u64(w, h / 100u);
+      *w++ = '.', *w++ = (char)('0' + h % 100u / 10u), *w++ = (char)('0' + h % 10u), *w++ = '\n';
+      used = (size_t)(w - buf.data());
+      sum += bases;
+    }
+  }
+  if (used && fwrite(buf.data(), 1, used, out) != used) return -3;
+  if (total) *total = sum;
+  return 0;
 }
 
 // ------------------------------------------------------------------------------------------------

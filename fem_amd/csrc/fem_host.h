@@ -15,6 +15,7 @@
 
 #include <stddef.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -200,6 +201,22 @@ int fem_parse_read_group(const char *arg, char **line, char *id, char *msg, uint
  * null argument or a field that would end behind text_len. */
 int fem_sam_fill_quals(char *text, uint64_t text_len, const uint64_t *qual_at, uint64_t n_reads, const char *quals, const uint64_t *off,
                        uint32_t read_len, int n_threads);
+
+/* ---------------- coverage track (`FEM map --coverage`; include/fem_hip.h, fem_dev_set_coverage: the rule) ---------------- */
+/* The windows of a reference: a sequence of n bases has ceil(n / window) of them, the last one ending at n; bin_off[t] = the windows
+ * of the sequences in front of t (n_seq + 1 entries, or NULL), *n_bins their total, set whenever the arguments are in range.
+ * Arithmetic only, no allocation; fem_dev_set_coverage lays its bins out by the same code (fem_coverage.h).
+ * 0; -1: a null argument or a window outside 1 .. 1 000 000; -2: more than 2^29 windows. */
+int fem_coverage_layout(uint32_t n_seq, const uint32_t *seq_len, int32_t window, uint64_t *bin_off, uint64_t *n_bins);
+/* The least window at which fem_coverage_layout accepts these sequences; 0: none does. */
+int32_t fem_coverage_min_window(uint32_t n_seq, const uint32_t *seq_len);
+/* The track as BED text: for every window of every sequence, in the order of the sequences and then by position, the line
+ * RNAME \t start \t end \t bases \t mean \n with start and end 0-based and half-open, bases = bins[k] and mean the depth with two
+ * decimals in integers: h = (bases * 100 + len / 2) / len with len = end - start, printed as h / 100, '.', two digits of h % 100.
+ * names / name_off as in fem_tail_ref.  *total (optional): the sum of the bins.  0; -1: a bad argument (as
+ * fem_coverage_layout's -1 and -2); -3: the write failed. */
+int fem_coverage_write(FILE *out, uint32_t n_seq, const char *names, const uint64_t *name_off, const uint32_t *seq_len, int32_t window,
+                       const uint64_t *bins, uint64_t *total);
 
 /* ---------------- synthetic data ---------------- */
 /* iid uniform A/C/G/T; sequence i is a pure function of (seed, i). */

@@ -25,6 +25,9 @@
 // mates, with no adapter given, and cuts both mates at the fragment's end on the device (fem_dev_set_pair_overlap).
 // `--xa[=N]` folds the secondary lines of a read (of a mate) into an XA:Z field on its primary line, at most N of them and
 // FEM_XA_MAX_BYTES bytes per line, made on the device (fem_dev_set_xa).
+// `--coverage FILE` (`--coverage-window INT`, `--coverage-all`, `--coverage-mapq INT`) writes the windowed depth of the output's
+// lines as BED text: summed on the device over the whole run, one array per GPU, added up and written here at the end
+// (fem_dev_set_coverage, fem_coverage_write).
 #include <errno.h>
 #include <fcntl.h>
 #include <getopt.h>
@@ -122,6 +125,10 @@ void usage_map() {
   fprintf(stderr, "        --trim-overlap  with --read2: where the mates of a pair overlap as a fragment shorter than the reads does, cut both at the fragment's end before mapping, on the GPU; no adapter needed; printed as soft clips\n");
   fprintf(stderr, "        --trim-overlap-min INT  the least number of overlapping bases that count as a match (8-1024) [20]\n");
   fprintf(stderr, "        --trim-overlap-err INT  mismatches allowed in the overlap, per cent of it (0-30) [10]\n");
+  fprintf(stderr, "        --coverage FILE  write the windowed depth of the output's lines to FILE as BED (name, start, end, covered bases, mean depth), summed on the GPU\n");
+  fprintf(stderr, "        --coverage-window INT  the window (1-1000000) [1000]\n");
+  fprintf(stderr, "        --coverage-all  count every hit that is in the output (secondary lines and XA entries too), not the primary lines alone\n");
+  fprintf(stderr, "        --coverage-mapq INT  with --mapq: count the lines whose MAPQ is INT (1-60) at the least\n");
   fprintf(stderr, "        --sam-seq     write SEQ reverse-complemented and QUAL reversed on reverse-strand lines (FLAG 0x10), as the SAM specification orders them\n");
   fprintf(stderr, "        -o       STR  Output SAM file \n\n");
 }
@@ -364,6 +371,11 @@ int map_main(int argc, char **argv) {
   // --trim-overlap / --trim-overlap-min / --trim-overlap-err: read-through found from the mates' overlap (fem_dev_set_pair_overlap)
   bool trim_overlap = false, trim_overlap_min_given = false, trim_overlap_err_given = false;
   long long trim_overlap_min = 20, trim_overlap_err = 10;
+  // --coverage FILE / --coverage-window / --coverage-all / --coverage-mapq: windowed depth of the output lines, summed on the device
+  // over the whole run and written as BED text at its end (fem_dev_set_coverage, fem_coverage_write)
+  const char *coverage_path = nullptr;
+  long long coverage_window = 1000, coverage_mapq = 0;
+  bool coverage_window_given = false, coverage_all = false, coverage_mapq_given = false;
   fem_params params{12, 3, 2, 1};  // src/FEM_map.c:67-70: k and step are fixed, whatever the index header says
   int n_threads = 1, n_gpus = 1;
   // reads per batch: 250 k fills the pipeline soonest on small inputs; a batch costs three host round trips on its way through
@@ -397,6 +409,10 @@ int map_main(int argc, char **argv) {
                                      {"trim-overlap", no_argument, nullptr, 1005},
                                      {"trim-overlap-min", required_argument, nullptr, 1006},
                                      {"trim-overlap-err", required_argument, nullptr, 1007},
+                                     {"coverage", required_argument, nullptr, 1008},
+                                     {"coverage-window", required_argument, nullptr, 1009},
+                                     {"coverage-all", no_argument, nullptr, 1010},
+                                     {"coverage-mapq", required_argument, nullptr, 1011},
                                      {nullptr, 0, nullptr, 0}};
   int c, oi = 0;
   while ((c = getopt_long(argc, argv, short_opt, long_opt, &oi)) >= 0) {
@@ -444,6 +460,17 @@ int map_main(int argc, char **argv) {
         if (!end || end == optarg || *end) v = -1;  // (not a number: refused below)
         (c == 1006 ? trim_overlap_min : trim_overlap_err) = v;
         (c == 1006 ? trim_overlap_min_given : trim_overlap_err_given) = true;
+        break;
+      }
+      case 1008: coverage_path = optarg; break;
+      case 1010: coverage_all = true; break;
+      case 1009:
+      case 1011: {
+        char *end = nullptr;
+        long long v = strtoll(optarg, &end, 10);
+        if (!end || end == optarg || *end) v = -1;  // (not a number: refused below)
+        (c == 1009 ? coverage_window : coverage_mapq) = v;
+        (c == 1009 ? coverage_window_given : coverage_mapq_given) = true;
         break;
       }
       case 'r': ref_path = optarg; break;
@@ -550,6 +577,10 @@ int map_main(int argc, char **argv) {
   else if (trim_overlap && !read2_path) bad = "--trim-overlap needs read pairs (--read2).";
   else if (trim_overlap && (trim_overlap_min < 8 || trim_overlap_min > 1024)) bad = "Wrong overlap of the mates (8-1024).";
   else if (trim_overlap && (trim_overlap_err < 0 || trim_overlap_err > 30)) bad = "Wrong overlap error percentage (0-30).";
+  else if (!coverage_path && (coverage_window_given || coverage_all || coverage_mapq_given)) bad = "--coverage-window, --coverage-all and --coverage-mapq need --coverage.";
+  else if (coverage_path && (coverage_window < 1 || coverage_window > 1000000)) bad = "Wrong coverage window (1-1000000).";
+  else if (coverage_mapq_given && (coverage_mapq < 1 || coverage_mapq > 60)) bad = "Wrong coverage MAPQ threshold (1-60).";
+  else if (coverage_mapq_given && !mapq) bad = "--coverage-mapq needs --mapq.";
   else if (!ref_path) bad = "Reference file path is required.";
   else if (!index_path) bad = "Index file path is required.";
   else if (!read_path) bad = "Read file path is required.";
@@ -625,6 +656,10 @@ int map_main(int argc, char **argv) {
       fprintf(stderr, "--xa is not supported with %s=1: the secondary lines are folded on the device, with its SAM text or BAM.\n", v);
       exit(EXIT_FAILURE);
     }
+    if (coverage_path && x && x[0] == '1') {  // (nor a coverage track: it is summed from the device's lines)
+      fprintf(stderr, "--coverage is not supported with %s=1: the coverage track is summed on the device, from the lines of its SAM text or BAM.\n", v);
+      exit(EXIT_FAILURE);
+    }
     if ((strata_given || max_hits_given) && x && x[0] == '1') {  // (nor a line filter)
       fprintf(stderr, "--strata and --max-hits are not supported with %s=1: the lines are filtered on the device, with its SAM text or BAM.\n", v);
       exit(EXIT_FAILURE);
@@ -639,6 +674,19 @@ int map_main(int argc, char **argv) {
   if (n_gpus == 1 || share_gpu) (void)fem_bind_thread_near_device(0);
   Reference ref;
   if (!ref.load(ref_path)) exit(EXIT_FAILURE);
+  // --coverage: the track's windows, from the sequences' lengths alone, before the index is read and before any device is opened
+  std::vector<uint64_t> coverage_off;
+  uint64_t coverage_bins = 0;
+  if (coverage_path) {
+    coverage_off.resize((size_t)ref.view.n_seq + 1);
+    if (fem_coverage_layout(ref.view.n_seq, ref.view.len, (int32_t)coverage_window, coverage_off.data(), &coverage_bins) != 0) {
+      const int32_t least = fem_coverage_min_window(ref.view.n_seq, ref.view.len);
+      if (least) fprintf(stderr, "--coverage-window %lld gives %lu windows on this reference, more than 2^29; the least window that fits is %d.\n",
+                         coverage_window, (unsigned long)coverage_bins, least);
+      else fprintf(stderr, "--coverage: this reference has more than 2^29 windows at every window up to 1000000.\n");
+      exit(EXIT_FAILURE);
+    }
+  }
   double t_idx = real_time();
   int32_t ik = 0, istep = 0;
   uint32_t *lookup = nullptr;
@@ -871,6 +919,13 @@ int map_main(int argc, char **argv) {
     }
     const char *st = getenv("FEM_STAGE_TIMES");
     if (st && (st[0] == '1' || st[0] == '2')) fprintf(stderr, "[FEM] insert size pre-pass: %fs\n", real_time() - t_pre);
+  }
+  // --coverage: every device keeps a track of its own from here on (behind the sample pass, which adds nothing to it); the host
+  // sums them at the end
+  if (coverage_path) {
+    const fem_coverage_params cp{(int32_t)coverage_window, coverage_all ? 1 : 0, (int32_t)coverage_mapq};
+    for (fem_dev *h : devs)
+      if (int rc = fem_dev_set_coverage(h, &cp)) return dev_fail(h, "coverage track", rc);
   }
 
   const int out_fd = open(out_path, O_WRONLY | O_CREAT | O_TRUNC, 0666);
@@ -1497,6 +1552,22 @@ int map_main(int argc, char **argv) {
   }
   uint64_t totals[5];
   for (int i = 0; i < 5; ++i) totals[i] = per_gpu[(size_t)i];
+  // --coverage: the devices' tracks home, summed, and the file (inside the timed phase: it is part of what the switch costs)
+  uint64_t n_covered = 0;
+  if (coverage_path && !exit_code) {
+    std::vector<uint64_t> bins((size_t)coverage_bins, 0), part(n_gpus > 1 ? (size_t)coverage_bins : 0);
+    for (int g = 0; g < n_gpus && !exit_code; ++g) {
+      uint64_t *to = g ? part.data() : bins.data();
+      if (int rc = fem_dev_fetch_coverage(devs[(size_t)g], to, coverage_bins)) exit_code = dev_fail(devs[(size_t)g], "coverage track", rc);
+      if (g && !exit_code)
+        for (size_t k = 0; k < bins.size(); ++k) bins[k] += part[k];
+    }
+    if (!exit_code) {
+      FILE *cf = fopen(coverage_path, "w");
+      const int wrc = cf ? fem_coverage_write(cf, ref.view.n_seq, ref.view.names, ref.view.name_off, ref.view.len, (int32_t)coverage_window, bins.data(), &n_covered) : -3;
+      if ((!cf || wrc || fclose(cf) != 0) && !exit_code.exchange(EXIT_FAILURE)) fprintf(stderr, "[FEM] write error on %s\n", coverage_path);
+    }
+  }
   const double t_mapping = real_time() - t_start;  // (the reference's timer stops after the counter reduction, src/FEM_map.c:219)
   for (TextOut &t : texts) free(t.buf);
   if (read_file) fem_seqfile_close(read_file);
@@ -1559,6 +1630,7 @@ int map_main(int argc, char **argv) {
     fprintf(stderr, "The number of pairs with overlap cut: %lu\n", (unsigned long)n_overlap);
     fprintf(stderr, "The number of overlap bases: %lu\n", (unsigned long)n_overlap_bases);
   }
+  if (coverage_path) fprintf(stderr, "The number of covered bases: %lu\n", (unsigned long)n_covered);
   fprintf(stderr, "Time: %fs\n", t_mapping);
   return 0;
 }

@@ -2716,6 +2716,9 @@ __global__ void __launch_bounds__(256) xa_write_kernel(SamParams p, XaParams x, 
   }
 }
 
+// ---- the coverage track (fem_dev_set_coverage): coverage_kernel ----
+#include "fem_coverage.hip.h"
+
 // ---------------------------------------------------------------------------------------------------------
 // Mate rescue (include/fem_hip.h).  A pair where exactly one mate (B) has no record: its other mate's first
 // kRescueAnchors records without 0x8000 are the anchors, and B's pos0 is searched in each anchor's insert window at E edits:
@@ -3201,6 +3204,7 @@ struct Tail::Impl {
   uint32_t n_unm = 0;                // lines for unmapped reads in the last text
   uint32_t n_base_last = 0;          // the lines the last text had before the filter and without the unmapped reads'
   uint32_t n_filtered = 0;           // lines the filter left out of the last text
+  bool cov_queued = false;           // coverage_kernel has been queued since the last run() (LineOptions::coverage)
   bool folded = false;               // the last text went through the fold index (LineOptions::xa_entries)
   uint32_t n_xa = 0, n_xa_slots = 0; // lines folded into XA:Z entries in the last text, and the slots that carry them
   Span span[kStages];                // (Tail::stage_ms)
@@ -3287,7 +3291,7 @@ struct Tail::Impl {
     }
     const uint32_t nr = n_base + (opt.unmapped ? last_n : 0u);
     const size_t r1 = (size_t)nr + 1, n1 = (size_t)last_n + 1;
-    not_run({kText, kMapq, kUnmappedIndex, kFilterIndex, kMateScore, kXaIndex});
+    not_run({kText, kMapq, kUnmappedIndex, kFilterIndex, kMateScore, kXaIndex, kCoverage});
     TAIL_TRY(line_len.ensure(r1));
     TAIL_TRY(line_off.ensure(r1));
     TAIL_TRY(h_ctl.ensure(kCtlWords));
@@ -3434,6 +3438,27 @@ struct Tail::Impl {
       }
       TAIL_TRY(span[kMapq].end(stream));
     }
+    if (opt.covers()) {  // behind the MAPQ kernel, whose column it reads, and over the index as it was before folding
+      const LineOptions::Coverage &cv = opt.coverage;
+      CoverageParams c{};
+      c.window = (uint32_t)cv.window, c.all_hits = cv.all_hits ? 1u : 0u, c.min_mapq = (uint32_t)cv.min_mapq, c.n_seq = cv.n_seq;
+      c.bin_off = cv.bin_off, c.seq_len = cv.seq_len, c.bins = cv.bins;
+      SamParams q = *p;
+      c.n_lines = um_kernels ? nr : n_base;
+      if (report) q.usrc = usrc, c.n_lines_at = u_before + last_n;  // (u_ctl[0] is the count after folding where the text folds)
+      else if (opt.unmapped) c.n_lines_at = u_ctl;
+      TAIL_TRY(span[kCoverage].begin(stream));
+      if (c.n_lines) {
+        const dim3 grid((c.n_lines + 255u) / 256u);
+        if (um_kernels)
+          hipLaunchKernelGGL((pair_order ? coverage_kernel<true, true> : coverage_kernel<false, true>), grid, dim3(256), 0, stream, q, c);
+        else
+          hipLaunchKernelGGL((pair_order ? coverage_kernel<true, false> : coverage_kernel<false, false>), grid, dim3(256), 0, stream, q, c);
+        TAIL_TRY(hipGetLastError());
+      }
+      cov_queued = true;  // (a batch without lines is added too: nothing)
+      TAIL_TRY(span[kCoverage].end(stream));
+    }
     p->sam_seq = opt.sam_seq ? 1u : 0u;
     if (opt.mates()) {
       p->mate_tags = 1u, p->mate_begin = pair_begin;
@@ -3511,6 +3536,8 @@ int Tail::impl(Impl **m) {
   *m = impl_.get();
   return impl_ ? FEM_OK : FEM_ERR_NOMEM;
 }
+
+bool Tail::coverage_queued() const { return impl_ && impl_->cov_queued; }
 
 float Tail::stage_ms(Stage stage) const { return impl_ ? impl_->span[stage].ms() : -1.f; }
 
@@ -3607,6 +3634,7 @@ int Tail::run(const TailInput &in, hipStream_t stream, int n_cu, bool tiny, Tail
   Impl *mp;
   if (int rc = impl(&mp)) return rc;
   Impl &m = *mp;
+  m.cov_queued = false;
   if (in.n_records > 0xFFFFFFF0ull) {
     if (err) *err = "more than 2^32 mappings in one batch; split the batch";
     return FEM_ERR_UNSUPPORTED;

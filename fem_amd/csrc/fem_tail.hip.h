@@ -131,9 +131,21 @@ struct LineOptions {
   bool hit_tags = false;           // NH:i and HI:i on every mapped line
   bool mate_tags = false;          // MC:Z MQ:i ms:i on every line of a paired text (mate_score_kernel; the kernels' kMate instances)
   bool sam_seq = false;            // SEQ reverse-complemented and QUAL reversed on the lines with 0x10 that carry them (the write kernels)
+  // the coverage track (fem_dev_set_coverage): this text's lines are added to the handle's bins (coverage_kernel).
+  // Set by the caller for the first text of a batch alone; window 0: off
+  struct Coverage {
+    int32_t window = 0;            // W
+    bool all_hits = false;         // lines with 0x100 count too (folded ones among them)
+    int32_t min_mapq = 0;          // a line counts from this MAPQ column on
+    uint32_t n_seq = 0;
+    const uint64_t *bin_off = nullptr;   // device: n_seq + 1
+    const uint32_t *seq_len = nullptr;   // device: n_seq
+    unsigned long long *bins = nullptr;  // device: the handle's array
+  } coverage;
   int32_t xa_entries = 0;          // secondary lines folded into XA:Z on the slot's first line, at most this many per slot; 0: off (xa_index_kernel, xa_write_kernel)
   bool filters() const { return strata >= 0 || max_hits >= 1; }  // the line filter is on
   bool folds() const { return xa_entries > 0; }
+  bool covers() const { return coverage.window > 0; }
   bool rescues() const { return paired && rescue; }
   bool mates() const { return paired && mate_tags; }
   // the mates' flips as the kernels take them: 16 where the mate's strand is flipped (FR 0 0, RF 16 16, FF 0 16)
@@ -179,8 +191,9 @@ struct TextGate {
 // LineOptions::unmapped alone; kMateScore, mate_score_kernel with LineOptions::mate_tags on a batch with device qualities;
 // kText, the SAM text's or the BAM records' kernels (xa_write_kernel among them); kXaIndex with LineOptions::xa_entries, the fold index
 // behind the line index (and the line index itself where the line filter is off: report_kernel with nothing to leave out).
-// estimate_insert() and estimate_library(): kInsert.
-enum Stage { kOrder, kTrace, kCompact, kText, kPairing, kRescue, kMapq, kUnmappedIndex, kFilterIndex, kInsert, kMateScore, kXaIndex, kStages };
+// kCoverage with LineOptions::coverage, coverage_kernel behind the line index and the MAPQ kernel.
+// estimate_insert() and estimate_library(): kInsert.  (The numbers are those of fem_dbg_stage_ms, include/fem_hip.h: new stages at the end.)
+enum Stage { kOrder, kTrace, kCompact, kText, kPairing, kRescue, kMapq, kUnmappedIndex, kFilterIndex, kInsert, kMateScore, kXaIndex, kCoverage, kStages };
 
 class Tail {
  public:
@@ -230,6 +243,9 @@ class Tail {
   // The device time of a stage, in ms.  Negative: the stage was not part of the last run() and of what followed it (pair(),
   // sam() or bam()), or its stream has not yet passed its end (a text that was not waited for).
   float stage_ms(Stage stage) const;
+  // coverage_kernel has been queued since the last run() (a sam() / bam() with LineOptions::coverage got that far, whether or not
+  // it succeeded afterwards): the batch's lines are in the track, or on their way there.
+  bool coverage_queued() const;
   // The arrays of the last pair() to the host (waits for `stream`).
   int pair_fetch(hipStream_t stream, PairOutput *out, std::string *err);
   int wait_text();

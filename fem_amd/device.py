@@ -28,6 +28,7 @@ ABI_SYMBOLS = [
     "fem_dev_set_trim", "fem_dev_fetch_trim", "fem_dev_trim_count",
     "fem_dev_set_adapter", "fem_dev_fetch_adapter", "fem_dev_adapter_count",
     "fem_dev_set_pair_overlap", "fem_dev_fetch_pair_overlap", "fem_dev_pair_overlap_count",
+    "fem_dev_set_coverage", "fem_dev_coverage_layout", "fem_dev_fetch_coverage", "fem_dev_reset_coverage", "fem_dbg_stage_ms",
     "fem_dev_fetch_bam", "fem_dev_fetch_bam_nowait", "fem_dev_bam_wait", "fem_dev_bgzf_compress",
 ]
 
@@ -105,6 +106,15 @@ class _AdapterParams(C.Structure):
 
 class _PairOverlapParams(C.Structure):
     _fields_ = [("min_overlap", C.c_int32), ("err_pct", C.c_int32)]
+
+
+class _CoverageParams(C.Structure):
+    _fields_ = [("window", C.c_int32), ("all_hits", C.c_int32), ("min_mapq", C.c_int32)]
+
+
+#: fem_dbg_stage_ms stages (include/fem_hip.h)
+STAGE_TEXT = 3
+STAGE_COVERAGE = 12
 
 
 class _TagParams(C.Structure):
@@ -232,6 +242,12 @@ def load_hip():
         L.fem_dev_fetch_bam_nowait.argtypes = [vp, C.c_int, C.c_int, C.POINTER(_BatchBam)]
         L.fem_dev_bam_wait.argtypes = [vp, C.c_int]
         L.fem_dev_bgzf_compress.argtypes = [vp, vp, u64, C.c_int, vp, u64, C.POINTER(u64)]
+    if hasattr(L, "fem_dev_set_coverage"):
+        L.fem_dev_set_coverage.argtypes = [vp, C.POINTER(_CoverageParams)]
+        L.fem_dev_coverage_layout.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
+        L.fem_dev_fetch_coverage.argtypes = [vp, C.POINTER(u64), u64]
+        L.fem_dev_reset_coverage.argtypes = [vp]
+        L.fem_dbg_stage_ms.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_float)]
     if hasattr(L, "fem_dbg_live_bytes"):
         L.fem_dbg_live_bytes.argtypes = [C.POINTER(u64), C.POINTER(u64)]
     L.fem_device_numa.argtypes = [C.c_int, C.POINTER(C.c_int32), C.c_char_p, u64]
@@ -495,6 +511,7 @@ class Device:
         ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
         lens = np.array([len(a) for a in arrs], dtype=np.uint32)
         self._check(self._L.fem_dev_upload_reference(self._h, len(arrs), ptrs, lens.ctypes.data))
+        self._n_seq = len(arrs)  # (coverage_layout sizes bin_off by it)
 
     def build_index(self, k=12, step=3, fetch=True):
         n = C.c_uint64()
@@ -784,6 +801,40 @@ class Device:
         n = C.c_uint64()
         self._check(self._L.fem_dev_xa_count(self._h, slot, C.byref(n)))
         return int(n.value)
+
+    def set_coverage(self, window=1000, all_hits=False, min_mapq=0):
+        """fem_dev_set_coverage: the handle keeps a coverage track of windows of `window` bases from now on, which the first text
+        or BAM fetch of every mapped batch adds to; window=None: off.  Setting it again zeroes the track."""
+        if window is None:
+            return self._check(self._L.fem_dev_set_coverage(self._h, None))
+        cp = _CoverageParams(int(window), int(all_hits), int(min_mapq))
+        self._check(self._L.fem_dev_set_coverage(self._h, C.byref(cp)))
+
+    def coverage_layout(self):
+        """fem_dev_coverage_layout: (n_bins, bin_off with n_seq + 1 entries)."""
+        n = C.c_uint64()
+        self._check(self._L.fem_dev_coverage_layout(self._h, C.byref(n), None))
+        off = np.zeros(self._n_seq + 1, np.uint64)
+        self._check(self._L.fem_dev_coverage_layout(self._h, C.byref(n), off.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return int(n.value), off
+
+    def fetch_coverage(self, cap=None):
+        """fem_dev_fetch_coverage: the track's bins (uint64), after everything the slots have queued; cap: the room offered."""
+        n = C.c_uint64()
+        self._check(self._L.fem_dev_coverage_layout(self._h, C.byref(n), None))
+        cap = int(n.value) if cap is None else int(cap)
+        bins = np.zeros(max(cap, 1), np.uint64)
+        self._check(self._L.fem_dev_fetch_coverage(self._h, bins.ctypes.data_as(C.POINTER(C.c_uint64)), cap))
+        return bins[: int(n.value)]
+
+    def reset_coverage(self):
+        self._check(self._L.fem_dev_reset_coverage(self._h))
+
+    def stage_ms(self, stage, slot=0):
+        """fem_dbg_stage_ms: device time of one stage of the slot's last fetch (STAGE_TEXT, STAGE_COVERAGE); negative: it did not run."""
+        ms = C.c_float()
+        self._check(self._L.fem_dbg_stage_ms(self._h, slot, int(stage), C.byref(ms)))
+        return float(ms.value)
 
     def set_trim(self, trim5=0, trim3=0, qual=0, slot=0):
         """fem_dev_set_trim: the slot's batches are trimmed on the device from the next fem_dev_map_staged on: trim5 / trim3 bases

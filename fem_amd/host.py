@@ -93,6 +93,10 @@ def lib():
         L.fem_synth_reads_packed.argtypes = [u64, vp, vp, vp, C.c_uint32, u64, u64, C.c_uint32, i32, vp, C.c_int]
         L.fem_synth_write_fastq.argtypes = [C.c_char_p, vp, C.c_uint32, u64, u64]
         L.fem_synth_write_fasta.argtypes = [C.c_char_p, vp, vp, vp, C.c_uint32]
+        L.fem_coverage_layout.argtypes = [C.c_uint32, vp, i32, vp, C.POINTER(u64)]
+        L.fem_coverage_min_window.argtypes = [C.c_uint32, vp]
+        L.fem_coverage_min_window.restype = i32
+        L.fem_coverage_write.argtypes = [vp, C.c_uint32, vp, vp, vp, i32, vp, C.POINTER(u64)]
         L.free = C.CDLL(None).free
         L.free.argtypes = [vp]
         _LIB = L
@@ -614,3 +618,42 @@ def tail_sam(e, ref, names, read_bases, read_off, quals, cand_begin, cand_count,
     text = _copy(p.value, n.value, np.uint8).tobytes().decode()
     lib().free(p)
     return text
+
+
+# ------------------------------------------------------------------------------------------ coverage track
+def coverage_layout(seq_lens, window):
+    """fem_coverage_layout: (rc, n_bins, bin_off with n_seq + 1 entries).  rc 0, -1 (bad argument) or -2 (more than 2^29 windows);
+    n_bins is the windows' number whenever rc is not -1.  Arithmetic only: nothing of the sequences' size is allocated."""
+    lens = np.ascontiguousarray(seq_lens, np.uint32)
+    off = np.zeros(len(lens) + 1, np.uint64)
+    n = C.c_uint64()
+    rc = lib().fem_coverage_layout(len(lens), lens.ctypes.data, int(window), off.ctypes.data, C.byref(n))
+    return rc, int(n.value), off
+
+
+def coverage_min_window(seq_lens):
+    """fem_coverage_min_window: the least window fem_coverage_layout accepts for these sequences, 0 for none."""
+    lens = np.ascontiguousarray(seq_lens, np.uint32)
+    return int(lib().fem_coverage_min_window(len(lens), lens.ctypes.data))
+
+
+def coverage_write(path, names, seq_lens, window, bins):
+    """fem_coverage_write into the file `path` (through the C library's fopen): returns the sum of the bins."""
+    lens = np.ascontiguousarray(seq_lens, np.uint32)
+    raw = [n.encode() if isinstance(n, str) else bytes(n) for n in names]
+    name_off = np.zeros(len(raw) + 1, np.uint64)
+    name_off[1:] = np.cumsum([len(r) for r in raw])
+    nm = np.frombuffer(b"".join(raw) + b"\0", np.uint8).copy()
+    b = np.ascontiguousarray(bins, np.uint64)
+    libc = C.CDLL(None)
+    libc.fopen.restype = C.c_void_p
+    libc.fopen.argtypes = [C.c_char_p, C.c_char_p]
+    libc.fclose.argtypes = [C.c_void_p]
+    f = libc.fopen(os.fsencode(path), b"w")
+    if not f:
+        raise RuntimeError("cannot open %s" % path)
+    total = C.c_uint64()
+    rc = lib().fem_coverage_write(f, len(raw), nm.ctypes.data, name_off.ctypes.data, lens.ctypes.data, int(window), b.ctypes.data, C.byref(total))
+    if libc.fclose(f) != 0 or rc != 0:
+        raise RuntimeError("fem_coverage_write failed (%d)" % rc)
+    return int(total.value)

@@ -759,6 +759,49 @@ int fem_dev_set_pair_overlap(fem_dev *h, int slot, const fem_pair_overlap_params
 int fem_dev_fetch_pair_overlap(fem_dev *h, int slot, const uint16_t **over3, uint64_t *n_reads);
 int fem_dev_pair_overlap_count(fem_dev *h, int slot, uint64_t *n_pairs, uint64_t *n_bases);
 
+/* ---- the coverage track: windowed depth of the output lines, summed on the device over the whole run (new; opt-in: the reference
+ *      knows no coverage, and every output without it is byte for byte as before with no kernel more) ----
+ * The first output that is accumulated across batches and not rendered per batch: the array belongs to the HANDLE, not to a slot.
+ * fem_dev_set_coverage: window W: 1 .. 1 000 000; all_hits: 0 or 1; min_mapq: 0 .. 60.  cp == NULL turns the track off and frees its
+ *   array.  It needs the reference on the device (fem_dev_upload_reference), else FEM_ERR_STATE; out-of-range values, or a reference
+ *   with more than 2^29 windows at W (the message names the least W that fits), are FEM_ERR_INVALID and leave the setting and the
+ *   array as they were.  Setting it again, with the same values or others, zeroes the array.  A new fem_dev_upload_reference waits for the device
+ *   and turns it off (as for the reference itself, the caller has no fetch in flight on another thread then).  It never touches a line: the texts and BAM records are byte for byte those without it.
+ * Rule (integers throughout; it is the specification).  Coverage is a property of LINES.  It is taken after everything else about
+ *   the batch's lines has been decided: the single-end order, rescue, pairing, MAPQ, the lines of unmapped reads, the line filter.
+ *   1. Lines that count.  A line counts when its FLAG as written has neither 0x4 nor 0x100, its CIGAR column does not print * (so
+ *      a record with 0x8000 never counts), and its MAPQ column as printed is >= min_mapq (without fem_dev_set_mapq the column is
+ *      255: every line passes).  With all_hits lines with 0x100 count too, each judged by its own MAPQ column, and so do the lines
+ *      that fem_dev_set_xa folds into entries: a folded hit is still a reported hit, as for NH / HI and n_records, and is judged
+ *      as the line it would have been.  Folding therefore never changes the track.  Lines the filter (fem_dev_set_report) left
+ *      out never count.
+ *   2. Span.  A counting line covers [pos0, pos0 + s) of its sequence, s = the summed lengths of the M and D operations of the
+ *      record's CIGAR words.  The soft clips of a trimmed batch are output text only and do not enter; an insertion covers
+ *      nothing; a deletion counts as covered (the whole-span rule of `mosdepth -x`).  A span is cut at its sequence's end (no line
+ *      the mapper makes reaches past it).
+ *   3. Windows.  A sequence of n bases has ceil(n / W) windows, the last one ending at n.  bin_off[t] = the sum over the sequences
+ *      before t of ceil(len / W); base p of sequence t falls in bin bin_off[t] + p / W.  Each counting line adds, to every bin its
+ *      span meets, the number of bases they share.  The bins are 64-bit.
+ *   4. Accumulation.  The first text or BAM fetch of a mapped batch (fem_dev_fetch_sam[_nowait], fem_dev_fetch_bam[_nowait]) adds
+ *      that batch's lines, exactly once, with the slot's options as they are at that fetch.  Further fetches of the same batch add
+ *      nothing; a batch that is mapped but never fetched as text or BAM (fem_dev_fetch_records, _fetch_pairs, the estimates) adds
+ *      nothing.  Integer adds commute: the result does not depend on the number of slots, the batch size or the fetch order.
+ * fem_dev_coverage_layout: the number of bins and bin_off (n_seq + 1 entries; either pointer may be NULL); FEM_ERR_STATE with the
+ *   track off.  The arithmetic is fem_coverage_layout's (fem_host.h).
+ * fem_dev_fetch_coverage: waits for every slot's streams (a text fetched with _nowait is complete once its wait has returned, and
+ *   also here) and copies the bins to `bins`; cap < n_bins is FEM_ERR_INVALID, the track off FEM_ERR_STATE.  The caller has no
+ *   fetch in flight on another thread while it, fem_dev_set_coverage or fem_dev_reset_coverage runs.
+ * fem_dev_reset_coverage: zeroes the array; FEM_ERR_STATE with the track off. */
+typedef struct {
+  int32_t window;   /* 1 .. 1 000 000 */
+  int32_t all_hits; /* 0: primary lines only; 1: every hit that is in the output */
+  int32_t min_mapq; /* 0 .. 60 */
+} fem_coverage_params;
+int fem_dev_set_coverage(fem_dev *h, const fem_coverage_params *cp);
+int fem_dev_coverage_layout(const fem_dev *h, uint64_t *n_bins, uint64_t *bin_off /* n_seq + 1, or NULL */);
+int fem_dev_fetch_coverage(fem_dev *h, uint64_t *bins, uint64_t cap);
+int fem_dev_reset_coverage(fem_dev *h);
+
 /* Name of the seed + filter kernel fem_dev_map_staged would launch first for these parameters on the resident
  * index ("seed_join_kernel" — behind its "seed_select_kernel"; "seed_join_banked_kernel" where the reference's sequences
  * need more than one 32-bit coordinate space —, "seed_fast_kernel<hash>", "seed_fast_kernel<lean>" or
@@ -814,6 +857,14 @@ int fem_dev_h2d_bandwidth(fem_dev *h, uint64_t bytes, int iters, double *gb_per_
  * over every handle of the process (either pointer may be null).  Needs no handle; back at its earlier value once a
  * handle is closed. */
 int fem_dbg_live_bytes(uint64_t *device_bytes, uint64_t *pinned_bytes);
+/* Debug: the device time in ms of one stage of the slot's LAST fetch of records, text or BAM, whether or not timing is on.
+ * Negative: the stage was not part of that fetch, the slot has fetched none, or the stream has not yet passed the stage's end (a
+ * text that was not waited for).  Stages: 0 order, 1 traceback, 2 compaction, 3 the text's or BAM records' kernels, 4 pairing,
+ * 5 rescue, 6 MAPQ, 7 the unmapped reads' line index, 8 the line filter's, 9 the insert estimate, 10 the mate score, 11 the fold
+ * index, 12 coverage_kernel (fem_dev_set_coverage). */
+#define FEM_STAGE_TEXT 3
+#define FEM_STAGE_COVERAGE 12
+int fem_dbg_stage_ms(fem_dev *h, int slot, int stage, float *ms);
 
 /* ---- host placement (new; the reference leaves its threads to the scheduler, src/FEM_map.c:172-198) ---- */
 /* NUMA node of the host memory GPU `device` is attached to (-1 if the system does not say) and that node's CPUs
