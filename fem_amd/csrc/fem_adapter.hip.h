@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fem_trim.hip.h"
+
 namespace femad {
 
 struct AdapterParams {
@@ -46,12 +48,9 @@ __global__ void __launch_bounds__(256) adapter_match_kernel(AdapterParams p) {
   uint32_t n_cut = 0;
   unsigned long long n_bases = 0;
   for (uint32_t r = wave; r < p.n_reads; r += n_waves) {
-    const uint64_t off = p.read_off[r];
-    const int L = (int)(p.read_off[r + 1] - off);
-    const int c5 = p.trim5 < L ? p.trim5 : L;
-    const int c3f = p.trim3 < L - c5 ? p.trim3 : L - c5;
-    const int Lp = L - c5 - c3f;
-    const uint8_t *x = p.bases + off + c5;
+    const femtr::Window w = femtr::fixed_window(p.read_off + r, p.trim5, p.trim3);
+    const int Lp = w.Lp;
+    const uint8_t *x = p.bases + w.off + w.c5;
     const int which = r >= p.second_begin ? 1 : 0;
     const int m = p.len[which];
     const unsigned long long a0 = p.occ[which][0], a1 = p.occ[which][1], a2 = p.occ[which][2], a3w = p.occ[which][3];
@@ -79,10 +78,7 @@ __global__ void __launch_bounds__(256) adapter_match_kernel(AdapterParams p) {
     if (ln == 0) p.adapt3[r] = (uint16_t)a3;
     if (a3 > 0) ++n_cut, n_bases += (unsigned long long)a3;
   }
-  if (ln == 0 && n_cut) {  // once per wave
-    atomicAdd(p.ctr, (unsigned long long)n_cut);
-    atomicAdd(p.ctr + 1, n_bases);
-  }
+  femtr::add_wave_counts(p.ctr, ln, n_cut, n_bases);
 }
 
 }  // namespace femad

@@ -72,6 +72,61 @@ struct TimedLaunch {
 };
 constexpr int kMaxParts = 4;
 
+// The trim stage in front of the selection (enqueue_trim) has CUT PRODUCERS: a kernel each that writes a
+// uint16 cut per read and two counters.  A kind is a row here (its setter and what a batch mapped without it lacks, as the
+// refusals word them), a Cuts in the slot and a member of PrepSettings.  kTrim is the stage's last step, which takes the others'
+// cuts in and makes the batch's clip points: it has two arrays (clip5, clip3) and runs for every trimmed batch.
+enum CutKind { kTrim, kAdapter, kOverlap, kCutKinds };
+constexpr struct {
+  const char *setter, *what;
+} kCutRows[kCutKinds] = {{"fem_dev_set_trim", "trimming"}, {"fem_dev_set_adapter", "an adapter"}, {"fem_dev_set_pair_overlap", "the mates' overlap"}};
+
+// What the three setters made of a slot's trim stage
+struct PrepSettings {
+  fem_trim_params trim{0, 0, 0};
+  struct Adapter {  // as the kernel takes it
+    bool on = false;
+    uint64_t occ[2][4] = {};
+    int32_t len[2] = {0, 0}, min_overlap = 0, err_pct = 0;
+  } adapter;
+  struct PairOverlap {
+    bool on = false;
+    int32_t min_overlap = 0, err_pct = 0;
+  } overlap;
+  // a batch mapped under these settings is a TRIMMED batch: staged as characters, with clip points and a mapping view
+  bool any() const { return trim.trim5 > 0 || trim.trim3 > 0 || trim.qual > 0 || adapter.on || overlap.on; }
+  bool has(int kind) const { return kind == kAdapter ? adapter.on : kind == kOverlap ? overlap.on : any(); }
+};
+
+// A producer's cuts of the slot's mapped batch and its two counters: on the device, the counters pinned on the host behind the
+// stage, the arrays from the batch's first fetch on.
+struct Cuts {
+  int n_arrays = 1;
+  StageBuf<uint16_t> d[2];
+  PinStageBuf<uint16_t> h[2];
+  Buf<unsigned long long> d_ctr;
+  PinBuf<unsigned long long> h_ctr;
+  bool home = false;  // h holds the mapped batch's cuts
+  hipError_t size(size_t n) {
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < n_arrays && e == hipSuccess; ++k) e = d[k].ensure(std::max<size_t>(n, 1));
+    if (e == hipSuccess) e = d_ctr.ensure(2);
+    return e == hipSuccess ? h_ctr.ensure(2) : e;
+  }
+  hipError_t zero_counts(hipStream_t st) { return hipMemsetAsync(d_ctr, 0, 2 * sizeof(unsigned long long), st); }
+  hipError_t counts_home(hipStream_t st) { return hipMemcpyAsync(h_ctr, d_ctr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st); }
+  // the arrays of n reads in h, copied once per batch (the host waits for the stream)
+  hipError_t fetch(size_t n, hipStream_t st) {
+    if (home) return hipSuccess;
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < n_arrays && e == hipSuccess; ++k) e = h[k].ensure(std::max<size_t>(n, 1));
+    for (int k = 0; k < n_arrays && n && e == hipSuccess; ++k) e = hipMemcpyAsync(h[k], d[k], n * sizeof(uint16_t), hipMemcpyDeviceToHost, st);
+    if (n && e == hipSuccess) e = hipStreamSynchronize(st);
+    home = e == hipSuccess;
+    return e;
+  }
+};
+
 struct Slot {
   Stream stream;
   // inputs
@@ -178,44 +233,20 @@ struct Slot {
   std::vector<uint32_t> pr_tid, pr_pos0, pr_cigar_off, pr_cigar, pr_md_off;
   std::vector<uint8_t> pr_nm;
   std::vector<char> pr_md;
-  // read trimming (fem_dev_set_trim): the setting, what the slot's mapped batch was trimmed by (read at fem_dev_map_staged), and
-  // that batch's clip points, kept lengths and MAPPING VIEW: the kept parts' characters and offsets, which the mapping kernels,
-  // the traceback and the rescue read in place of bases() / d_off (those stay the whole reads, for SEQ and QUAL of the text)
-  fem_trim_params trim{0, 0, 0}, trim_batch{0, 0, 0};
-  bool trimmed = false;
-  StageBuf<uint8_t> d_map_bases_alloc;  // laid out as d_bases_alloc
-  StageBuf<uint64_t> d_map_off, d_keep;
-  StageBuf<uint16_t> d_clip5, d_clip3;
-  Buf<unsigned long long> d_trim_ctr;
-  Buf<uint8_t> d_trim_scan_tmp;
-  PinStageBuf<uint16_t> h_clip5, h_clip3;
-  PinBuf<unsigned long long> h_trim_ctr;
-  bool clips_home = false;
-  // 3' adapter matching (fem_dev_set_adapter): the setting as the kernel takes it, what the slot's mapped batch was matched by,
-  // and that batch's cuts a3 with the two counters.  A batch matched against an adapter is a trimmed batch (trimmed is set).
-  struct Adapter {
-    bool on = false;
-    uint64_t occ[2][4] = {};
-    int32_t len[2] = {0, 0}, min_overlap = 0, err_pct = 0;
-  } adapter, adapter_batch;
-  StageBuf<uint16_t> d_adapt3;
-  Buf<unsigned long long> d_adapter_ctr;
-  PinStageBuf<uint16_t> h_adapt3;
-  PinBuf<unsigned long long> h_adapter_ctr;
-  bool adapt3_home = false;
-  // Read-through from the mates' overlap (fem_dev_set_pair_overlap): the setting, what the slot's mapped batch was matched by, and
-  // that batch's cuts v3 with the two counters.  A batch matched this way is a trimmed batch as well.
-  struct PairOverlap {
-    bool on = false;
-    int32_t min_overlap = 0, err_pct = 0;
-  } pair_overlap, pair_overlap_batch;
-  StageBuf<uint16_t> d_over3;
-  Buf<unsigned long long> d_overlap_ctr;
-  PinStageBuf<uint16_t> h_over3;
-  PinBuf<unsigned long long> h_overlap_ctr;
-  bool over3_home = false;
-  const uint8_t *map_bases() const { return trimmed ? d_map_bases_alloc + 16 : bases(); }
-  const uint64_t *map_off() const { return trimmed ? d_map_off.get() : d_off.get(); }
+  // The trim stage (enqueue_trim): what fem_dev_set_trim, fem_dev_set_adapter and fem_dev_set_pair_overlap wrote, what the slot's
+  // mapped batch was made with (taken at fem_dev_map_staged), that batch's cuts and counters per producer (cuts[kTrim]: the clip
+  // points clip5 and clip3), and its MAPPING VIEW: the kept parts' characters and offsets, which the mapping kernels, the
+  // traceback and the rescue read in place of bases() / d_off (those stay the whole reads, for SEQ and QUAL of the text)
+  PrepSettings prep, prep_batch;
+  Cuts cuts[kCutKinds] = {{2}, {}, {}};
+  struct MapView {
+    bool trimmed = false;              // the mapped batch is a trimmed batch: it has this view and clip points
+    StageBuf<uint8_t> d_bases_alloc;   // laid out as the slot's d_bases_alloc
+    StageBuf<uint64_t> d_off, d_keep;  // the kept lengths and their scan
+    Buf<uint8_t> d_scan_tmp;
+  } view;
+  const uint8_t *map_bases() const { return view.trimmed ? view.d_bases_alloc + 16 : bases(); }
+  const uint64_t *map_off() const { return view.trimmed ? view.d_off.get() : d_off.get(); }
 };
 
 // ctr[4] | arena_ctr[2] | stats[4] | pack cursor[2]
@@ -1336,74 +1367,64 @@ int enqueue_packed(fem_dev *h, Slot &s, uint64_t n, uint32_t len, uint64_t n_exc
   return FEM_OK;
 }
 
-bool trim_on(const fem_trim_params &t) { return t.trim5 > 0 || t.trim3 > 0 || t.qual > 0; }
-
 // The trim stage of the batch fem_dev_map_staged is about to map, on the slot's stream in front of the selection: the slot's
-// setting becomes the batch's, trim_clip_kernel makes the clip points and kept lengths, their scan the mapping view's offsets,
-// trim_gather_kernel its characters; the two counters go home behind them.  With an adapter set (fem_dev_set_adapter)
-// adapter_match_kernel runs first and hands trim_clip_kernel its cuts; that alone makes the batch a trimmed one.  With the
-// mates' overlap set (fem_dev_set_pair_overlap) pair_overlap_kernel does the same beside it, and trim_clip_kernel takes the
-// larger cut of the two.  With trimming off, no adapter and no overlap it launches nothing.
+// settings become the batch's; the cut producers that are on run first (adapter_match_kernel, pair_overlap_kernel) and hand
+// trim_clip_kernel their cuts, of which it takes the larger; it makes the clip points and kept lengths, their scan the mapping
+// view's offsets, trim_gather_kernel its characters; every producer's two counters go home behind them.  Any one setting makes
+// the batch a trimmed one.  With nothing set it launches nothing.
 int enqueue_trim(fem_dev *h, Slot &s) {
-  s.trim_batch = s.trim, s.adapter_batch = s.adapter, s.pair_overlap_batch = s.pair_overlap;
-  s.trimmed = false, s.clips_home = false, s.adapt3_home = false, s.over3_home = false;
-  const bool adapter = s.adapter_batch.on, overlap = s.pair_overlap_batch.on;
-  if (!trim_on(s.trim_batch) && !adapter && !overlap) return FEM_OK;
+  const PrepSettings &b = s.prep_batch = s.prep;
+  s.view.trimmed = false;
+  for (Cuts &c : s.cuts) c.home = false;
+  if (!b.any()) return FEM_OK;
+  const bool adapter = b.adapter.on, overlap = b.overlap.on;
   if (overlap && !s.opt.paired) return fail(h, FEM_ERR_STATE, "the mates' overlap (fem_dev_set_pair_overlap) needs the slot in pair mode (fem_dev_set_pairs)");
-  if (s.sent_packed)
-    return fail(h, FEM_ERR_UNSUPPORTED, overlap ? "trimming (fem_dev_set_trim, fem_dev_set_adapter, fem_dev_set_pair_overlap) reads a batch staged as characters, not a packed one (fem_dev_commit_stage_packed)"
-                                        : adapter ? "trimming (fem_dev_set_trim, fem_dev_set_adapter) reads a batch staged as characters, not a packed one (fem_dev_commit_stage_packed)"
-                                                : "trimming (fem_dev_set_trim) reads a batch staged as characters, not a packed one (fem_dev_commit_stage_packed)");
-  if (s.trim_batch.qual > 0 && (!s.text_staged || s.host_quals))
+  if (s.sent_packed) {
+    // (the setters are named in the table's order up to the last one that is on)
+    int last = kTrim;
+    for (int k = 0; k < kCutKinds; ++k)
+      if (b.has(k)) last = k;
+    std::string setters;
+    for (int k = 0; k <= last; ++k) setters += (k ? ", " : "") + std::string(kCutRows[k].setter);
+    return fail(h, FEM_ERR_UNSUPPORTED, "trimming (" + setters + ") reads a batch staged as characters, not a packed one (fem_dev_commit_stage_packed)");
+  }
+  if (b.trim.qual > 0 && (!s.text_staged || s.host_quals))
     return fail(h, FEM_ERR_STATE, "quality trimming (fem_dev_set_trim) needs the batch's qualities on the device before it is mapped (fem_dev_commit_text_stage)");
   const size_t n = (size_t)s.n_reads;
-  HIP_TRY(h, s.d_map_bases_alloc.ensure(kFrontPad + (size_t)s.n_bases + 64));
-  HIP_TRY(h, s.d_map_off.ensure(n + 1));
-  HIP_TRY(h, s.d_keep.ensure(n + 1));
-  HIP_TRY(h, s.d_clip5.ensure(std::max<size_t>(n, 1)));
-  HIP_TRY(h, s.d_clip3.ensure(std::max<size_t>(n, 1)));
-  HIP_TRY(h, s.d_trim_ctr.ensure(2));
-  HIP_TRY(h, s.h_trim_ctr.ensure(2));
-  if (adapter) {
-    HIP_TRY(h, s.d_adapt3.ensure(std::max<size_t>(n, 1)));
-    HIP_TRY(h, s.d_adapter_ctr.ensure(2));
-    HIP_TRY(h, s.h_adapter_ctr.ensure(2));
-  }
-  if (overlap) {
-    HIP_TRY(h, s.d_over3.ensure(std::max<size_t>(n, 1)));
-    HIP_TRY(h, s.d_overlap_ctr.ensure(2));
-    HIP_TRY(h, s.h_overlap_ctr.ensure(2));
-  }
+  Cuts &clips = s.cuts[kTrim], &adapt3 = s.cuts[kAdapter], &over3 = s.cuts[kOverlap];
+  HIP_TRY(h, s.view.d_bases_alloc.ensure(kFrontPad + (size_t)s.n_bases + 64));
+  HIP_TRY(h, s.view.d_off.ensure(n + 1));
+  HIP_TRY(h, s.view.d_keep.ensure(n + 1));
+  for (int k = 0; k < kCutKinds; ++k)
+    if (b.has(k)) HIP_TRY(h, s.cuts[k].size(n));
   size_t scan_bytes = 0;
-  HIP_TRY(h, rocprim::exclusive_scan(nullptr, scan_bytes, s.d_keep.get(), s.d_map_off.get(), (uint64_t)0, n + 1, rocprim::plus<uint64_t>(), s.stream.s));
-  HIP_TRY(h, s.d_trim_scan_tmp.ensure(std::max<size_t>(scan_bytes, 16)));
-  scan_bytes = s.d_trim_scan_tmp.size();
-  if (s.trim_batch.qual > 0) HIP_TRY(h, hipStreamWaitEvent(s.stream, s.ev_text_staged, 0));  // (the qualities came on the slot's text stream)
-  HIP_TRY(h, hipMemsetAsync(s.d_trim_ctr, 0, 2 * sizeof(unsigned long long), s.stream));
+  HIP_TRY(h, rocprim::exclusive_scan(nullptr, scan_bytes, s.view.d_keep.get(), s.view.d_off.get(), (uint64_t)0, n + 1, rocprim::plus<uint64_t>(), s.stream.s));
+  HIP_TRY(h, s.view.d_scan_tmp.ensure(std::max<size_t>(scan_bytes, 16)));
+  scan_bytes = s.view.d_scan_tmp.size();
+  if (b.trim.qual > 0) HIP_TRY(h, hipStreamWaitEvent(s.stream, s.ev_text_staged, 0));  // (the qualities came on the slot's text stream)
+  for (int k = 0; k < kCutKinds; ++k)
+    if (b.has(k)) HIP_TRY(h, s.cuts[k].zero_counts(s.stream));
   femtr::TrimParams tp{};
-  tp.quals = s.trim_batch.qual > 0 ? s.d_quals.get() : nullptr, tp.read_off = s.d_off, tp.n_reads = (uint32_t)n;
-  tp.trim5 = s.trim_batch.trim5, tp.trim3 = s.trim_batch.trim3, tp.qual = s.trim_batch.qual;
-  tp.clip5 = s.d_clip5, tp.clip3 = s.d_clip3, tp.keep = s.d_keep, tp.ctr = s.d_trim_ctr;
-  tp.adapt3 = adapter ? s.d_adapt3.get() : nullptr;
+  tp.quals = b.trim.qual > 0 ? s.d_quals.get() : nullptr, tp.read_off = s.d_off, tp.n_reads = (uint32_t)n;
+  tp.trim5 = b.trim.trim5, tp.trim3 = b.trim.trim3, tp.qual = b.trim.qual;
+  tp.clip5 = clips.d[0], tp.clip3 = clips.d[1], tp.keep = s.view.d_keep, tp.ctr = clips.d_ctr;
+  tp.adapt3 = adapter ? adapt3.d[0].get() : nullptr, tp.over3 = overlap ? over3.d[0].get() : nullptr;
   femad::AdapterParams ap{};
   if (adapter) {
-    HIP_TRY(h, hipMemsetAsync(s.d_adapter_ctr, 0, 2 * sizeof(unsigned long long), s.stream));
     ap.bases = s.bases(), ap.read_off = s.d_off, ap.n_reads = (uint32_t)n;
     ap.second_begin = s.opt.paired ? (uint32_t)(n / 2) : (uint32_t)n;  // (pair mode: the second half are the mates 2)
-    ap.trim5 = s.trim_batch.trim5, ap.trim3 = s.trim_batch.trim3;
-    ap.min_overlap = s.adapter_batch.min_overlap, ap.err_pct = s.adapter_batch.err_pct;
-    memcpy(ap.occ, s.adapter_batch.occ, sizeof ap.occ);
-    ap.len[0] = s.adapter_batch.len[0], ap.len[1] = s.adapter_batch.len[1];
-    ap.adapt3 = s.d_adapt3, ap.ctr = s.d_adapter_ctr;
+    ap.trim5 = b.trim.trim5, ap.trim3 = b.trim.trim3;
+    ap.min_overlap = b.adapter.min_overlap, ap.err_pct = b.adapter.err_pct;
+    memcpy(ap.occ, b.adapter.occ, sizeof ap.occ);
+    ap.len[0] = b.adapter.len[0], ap.len[1] = b.adapter.len[1];
+    ap.adapt3 = adapt3.d[0], ap.ctr = adapt3.d_ctr;
   }
-  tp.over3 = overlap ? s.d_over3.get() : nullptr;
   femov::OverlapParams vp{};
   if (overlap) {
-    HIP_TRY(h, hipMemsetAsync(s.d_overlap_ctr, 0, 2 * sizeof(unsigned long long), s.stream));
     vp.bases = s.bases(), vp.read_off = s.d_off, vp.n_reads = (uint32_t)n;
-    vp.trim5 = s.trim_batch.trim5, vp.trim3 = s.trim_batch.trim3;
-    vp.min_overlap = s.pair_overlap_batch.min_overlap, vp.err_pct = s.pair_overlap_batch.err_pct;
-    vp.over3 = s.d_over3, vp.ctr = s.d_overlap_ctr;
+    vp.trim5 = b.trim.trim5, vp.trim3 = b.trim.trim3;
+    vp.min_overlap = b.overlap.min_overlap, vp.err_pct = b.overlap.err_pct;
+    vp.over3 = over3.d[0], vp.ctr = over3.d_ctr;
   }
   const uint32_t grid_pairs = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n / 2 + femov::kWaves - 1) / femov::kWaves, (uint64_t)h->n_cu * 8u));  // (a pair per wave)
   const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 3) / 4, (uint64_t)h->n_cu * 8u));  // (four reads per block)
@@ -1413,17 +1434,42 @@ int enqueue_trim(fem_dev *h, Slot &s) {
     if (adapter) hipLaunchKernelGGL(femad::adapter_match_kernel, dim3(grid), dim3(256), 0, s.stream, ap);
     if (overlap) hipLaunchKernelGGL(femov::pair_overlap_kernel, dim3(grid_pairs), dim3(64 * femov::kWaves), 0, s.stream, vp);
     hipLaunchKernelGGL(femtr::trim_clip_kernel, dim3(grid), dim3(256), 0, s.stream, tp);
-    scan_rc = rocprim::exclusive_scan(s.d_trim_scan_tmp.get(), scan_bytes, s.d_keep.get(), s.d_map_off.get(), (uint64_t)0, n + 1, rocprim::plus<uint64_t>(), s.stream.s);
+    scan_rc = rocprim::exclusive_scan(s.view.d_scan_tmp.get(), scan_bytes, s.view.d_keep.get(), s.view.d_off.get(), (uint64_t)0, n + 1, rocprim::plus<uint64_t>(), s.stream.s);
     if (n && scan_rc == hipSuccess)
       hipLaunchKernelGGL(femtr::trim_gather_kernel, dim3(grid), dim3(256), 0, s.stream, (const uint8_t *)s.bases(), (const uint64_t *)s.d_off.get(),
-                         (const uint16_t *)s.d_clip5.get(), (const uint64_t *)s.d_map_off.get(), (uint32_t)n, s.d_map_bases_alloc + kFrontPad);
+                         (const uint16_t *)clips.d[0].get(), (const uint64_t *)s.view.d_off.get(), (uint32_t)n, s.view.d_bases_alloc + kFrontPad);
   });
   HIP_TRY(h, scan_rc);
   if (rc) return rc;
-  HIP_TRY(h, hipMemcpyAsync(s.h_trim_ctr, s.d_trim_ctr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
-  if (adapter) HIP_TRY(h, hipMemcpyAsync(s.h_adapter_ctr, s.d_adapter_ctr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
-  if (overlap) HIP_TRY(h, hipMemcpyAsync(s.h_overlap_ctr, s.d_overlap_ctr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
-  s.trimmed = true;
+  for (int k = 0; k < kCutKinds; ++k)
+    if (b.has(k)) HIP_TRY(h, s.cuts[k].counts_home(s.stream));
+  s.view.trimmed = true;
+  return FEM_OK;
+}
+
+// fem_dev_fetch_trim, _adapter, _pair_overlap: a producer's cuts of the slot's mapped batch, copied home at the batch's first fetch
+int fetch_cuts(fem_dev *h, int slot, int kind, const uint16_t **first, const uint16_t **second, uint64_t *n_reads) {
+  int rc = fem_dev_sync(h, slot);
+  if (rc) return rc;
+  Slot &s = h->slot[slot];
+  if (!s.view.trimmed || !s.prep_batch.has(kind))
+    return fail(h, FEM_ERR_STATE, std::string("the slot's batch was mapped without ") + kCutRows[kind].what + " (" + kCutRows[kind].setter + ")");
+  Cuts &c = s.cuts[kind];
+  HIP_TRY(h, c.fetch((size_t)s.n_reads, s.stream));
+  if (first) *first = c.h[0];
+  if (second) *second = c.h[1];
+  if (n_reads) *n_reads = s.n_reads;
+  return FEM_OK;
+}
+
+// fem_dev_trim_count, _adapter_count, _pair_overlap_count: its two counters, 0 when the batch was mapped without it
+int cut_counts(fem_dev *h, int slot, int kind, uint64_t *n_cut, uint64_t *n_bases) {
+  int rc = fem_dev_sync(h, slot);
+  if (rc) return rc;
+  const Slot &s = h->slot[slot];
+  const bool on = s.view.trimmed && s.prep_batch.has(kind);
+  if (n_cut) *n_cut = on ? s.cuts[kind].h_ctr[0] : 0;
+  if (n_bases) *n_bases = on ? s.cuts[kind].h_ctr[1] : 0;
   return FEM_OK;
 }
 
@@ -1819,7 +1865,7 @@ int fem_dev_stage_reads(fem_dev *h, int slot, const fem_read_batch *reads) {
   // (test hook, read per batch on purpose: tests/test_gpu_packed.py switches it between two batches of one handle; one
   // getenv per batch of >= 10^4 reads is not measurable)
   // (a slot with trimming, an adapter or the mates' overlap set stages its batches as characters: the trim stage reads and gathers them)
-  const bool no_pack = testing_switch("FEM_NO_PACK") || trim_on(h->slot[slot].trim) || h->slot[slot].adapter.on || h->slot[slot].pair_overlap.on;
+  const bool no_pack = testing_switch("FEM_NO_PACK") || h->slot[slot].prep.any();
   if (n && min_len == max_len && max_len > 0 && n_bases < 0xFFFFFFF0ull && !no_pack) {
     const uint32_t len = max_len, bpr = (len + 3u) / 4u;
     const uint64_t code_bytes = (n * bpr + 7u) & ~7ull;
@@ -2247,7 +2293,7 @@ static int pair_records(fem_dev *h, Slot &s, const femt::LineOptions &opt, hipSt
 static femt::TailInput tail_input(const fem_dev *h, const Slot &s) {
   femt::TailInput in{};
   in.bases = s.map_bases(), in.read_off = s.map_off(), in.n_reads = (uint32_t)s.n_reads, in.max_len = s.max_len;
-  if (s.trimmed) in.text_bases = s.bases(), in.text_read_off = s.d_off, in.clip5 = s.d_clip5, in.clip3 = s.d_clip3;
+  if (s.view.trimmed) in.text_bases = s.bases(), in.text_read_off = s.d_off, in.clip5 = s.cuts[kTrim].d[0], in.clip3 = s.cuts[kTrim].d[1];
   in.ref_raw = h->d_ref_raw, in.ref_bytes = h->ref_bytes + 64, in.seq_off = h->d_seq_off;
   in.planes = h->d_planes;
   if (s.sent_packed) in.packed = s.packed(), in.packed_bpr = s.packed_bpr, in.exc_bits = s.d_exc_bits;
@@ -2311,7 +2357,7 @@ static int tail_records(fem_dev *h, int slot, const void *out, bool copy_records
     return fail(h, FEM_ERR_INVALID, "mate tags (fem_dev_set_mate_tags) need the qualities on the device: ms:i is made from them (fem_dev_commit_text_stage, not _names_stage)");
   if (text && s.opt.sam_seq && s.host_quals)
     return fail(h, FEM_ERR_INVALID, "SEQ and QUAL in SAM order (fem_dev_set_sam_seq) need the qualities on the device: QUAL is reversed where it is written (fem_dev_commit_text_stage, not _names_stage)");
-  if (text && s.trimmed && s.host_quals)
+  if (text && s.view.trimmed && s.host_quals)
     return fail(h, FEM_ERR_INVALID, "a trimmed batch (fem_dev_set_trim) prints its whole QUAL from the device (fem_dev_commit_text_stage, not _names_stage)");
   if (device_quals && s.host_quals) return fail(h, FEM_ERR_STATE, "BAM records need the qualities on the device (fem_dev_commit_text_stage, not _names_stage)");
   if (text && !h->d_ref_names) return fail(h, FEM_ERR_STATE, "reference names must be uploaded first (fem_dev_upload_reference_names)");
@@ -2728,46 +2774,23 @@ int fem_dev_set_trim(fem_dev *h, int slot, const fem_trim_params *tp) {
     const fem_trim_params t = tp ? *tp : fem_trim_params{0, 0, 0};
     if (t.trim5 < 0 || t.trim5 > 1024 || t.trim3 < 0 || t.trim3 > 1024 || t.qual < 0 || t.qual > 93)
       return fail(h, FEM_ERR_INVALID, "trim out of range (trim5 and trim3 0..1024, qual 0 or 1..93)");
-    s.trim = t;
+    s.prep.trim = t;
     return (int)FEM_OK;
   });
 }
 
 int fem_dev_fetch_trim(fem_dev *h, int slot, const uint16_t **clip5, const uint16_t **clip3, uint64_t *n_reads) {
-  int rc = fem_dev_sync(h, slot);
-  if (rc) return rc;
-  Slot &s = h->slot[slot];
-  if (!s.trimmed) return fail(h, FEM_ERR_STATE, "the slot's batch was mapped without trimming (fem_dev_set_trim)");
-  if (!s.clips_home) {
-    const size_t n = (size_t)s.n_reads;
-    HIP_TRY(h, s.h_clip5.ensure(std::max<size_t>(n, 1)));
-    HIP_TRY(h, s.h_clip3.ensure(std::max<size_t>(n, 1)));
-    if (n) {
-      HIP_TRY(h, hipMemcpyAsync(s.h_clip5, s.d_clip5, n * sizeof(uint16_t), hipMemcpyDeviceToHost, s.stream));
-      HIP_TRY(h, hipMemcpyAsync(s.h_clip3, s.d_clip3, n * sizeof(uint16_t), hipMemcpyDeviceToHost, s.stream));
-      HIP_TRY(h, hipStreamSynchronize(s.stream));
-    }
-    s.clips_home = true;
-  }
-  if (clip5) *clip5 = s.h_clip5;
-  if (clip3) *clip3 = s.h_clip3;
-  if (n_reads) *n_reads = s.n_reads;
-  return FEM_OK;
+  return fetch_cuts(h, slot, kTrim, clip5, clip3, n_reads);
 }
 
 int fem_dev_trim_count(fem_dev *h, int slot, uint64_t *n_reads_trimmed, uint64_t *n_bases_trimmed) {
-  int rc = fem_dev_sync(h, slot);
-  if (rc) return rc;
-  const Slot &s = h->slot[slot];
-  if (n_reads_trimmed) *n_reads_trimmed = s.trimmed ? s.h_trim_ctr[0] : 0;
-  if (n_bases_trimmed) *n_bases_trimmed = s.trimmed ? s.h_trim_ctr[1] : 0;
-  return FEM_OK;
+  return cut_counts(h, slot, kTrim, n_reads_trimmed, n_bases_trimmed);
 }
 
 int fem_dev_set_adapter(fem_dev *h, int slot, const fem_adapter_params *ap) {
   return with_slot(h, slot, [&](Slot &s) {
-    Slot::Adapter a;
-    if (!ap || !ap->seq1) return s.adapter = a, (int)FEM_OK;
+    PrepSettings::Adapter a;
+    if (!ap || !ap->seq1) return s.prep.adapter = a, (int)FEM_OK;
     const char *seq[2] = {ap->seq1, ap->seq2 ? ap->seq2 : ap->seq1};
     for (int k = 0; k < 2; ++k) {
       const size_t m = strnlen(seq[k], 65);
@@ -2784,79 +2807,37 @@ int fem_dev_set_adapter(fem_dev *h, int slot, const fem_adapter_params *ap) {
       return fail(h, FEM_ERR_INVALID, "adapter overlap out of range (1 to the adapter's length, the shorter one's of two)");
     if (ap->err_pct < 0 || ap->err_pct > 30) return fail(h, FEM_ERR_INVALID, "adapter error percentage out of range (0 to 30)");
     a.on = true, a.min_overlap = ap->min_overlap, a.err_pct = ap->err_pct;
-    s.adapter = a;
+    s.prep.adapter = a;
     return (int)FEM_OK;
   });
 }
 
 int fem_dev_fetch_adapter(fem_dev *h, int slot, const uint16_t **adapt3, uint64_t *n_reads) {
-  int rc = fem_dev_sync(h, slot);
-  if (rc) return rc;
-  Slot &s = h->slot[slot];
-  if (!s.trimmed || !s.adapter_batch.on) return fail(h, FEM_ERR_STATE, "the slot's batch was mapped without an adapter (fem_dev_set_adapter)");
-  if (!s.adapt3_home) {
-    const size_t n = (size_t)s.n_reads;
-    HIP_TRY(h, s.h_adapt3.ensure(std::max<size_t>(n, 1)));
-    if (n) {
-      HIP_TRY(h, hipMemcpyAsync(s.h_adapt3, s.d_adapt3, n * sizeof(uint16_t), hipMemcpyDeviceToHost, s.stream));
-      HIP_TRY(h, hipStreamSynchronize(s.stream));
-    }
-    s.adapt3_home = true;
-  }
-  if (adapt3) *adapt3 = s.h_adapt3;
-  if (n_reads) *n_reads = s.n_reads;
-  return FEM_OK;
+  return fetch_cuts(h, slot, kAdapter, adapt3, nullptr, n_reads);
 }
 
 int fem_dev_adapter_count(fem_dev *h, int slot, uint64_t *n_reads_cut, uint64_t *n_bases_cut) {
-  int rc = fem_dev_sync(h, slot);
-  if (rc) return rc;
-  const Slot &s = h->slot[slot];
-  const bool on = s.trimmed && s.adapter_batch.on;
-  if (n_reads_cut) *n_reads_cut = on ? s.h_adapter_ctr[0] : 0;
-  if (n_bases_cut) *n_bases_cut = on ? s.h_adapter_ctr[1] : 0;
-  return FEM_OK;
+  return cut_counts(h, slot, kAdapter, n_reads_cut, n_bases_cut);
 }
 
 int fem_dev_set_pair_overlap(fem_dev *h, int slot, const fem_pair_overlap_params *vp) {
   return with_slot(h, slot, [&](Slot &s) {
-    Slot::PairOverlap v;
-    if (!vp) return s.pair_overlap = v, (int)FEM_OK;
+    PrepSettings::PairOverlap v;
+    if (!vp) return s.prep.overlap = v, (int)FEM_OK;
     if (vp->min_overlap < 8 || vp->min_overlap > 1024) return fail(h, FEM_ERR_INVALID, "pair overlap out of range (8 to 1024)");
     if (vp->err_pct < 0 || vp->err_pct > 30) return fail(h, FEM_ERR_INVALID, "pair overlap error percentage out of range (0 to 30)");
     v.on = true, v.min_overlap = vp->min_overlap, v.err_pct = vp->err_pct;
-    s.pair_overlap = v;
+    s.prep.overlap = v;
     return (int)FEM_OK;
   });
 }
 
 int fem_dev_fetch_pair_overlap(fem_dev *h, int slot, const uint16_t **over3, uint64_t *n_reads) {
-  int rc = fem_dev_sync(h, slot);
-  if (rc) return rc;
-  Slot &s = h->slot[slot];
-  if (!s.trimmed || !s.pair_overlap_batch.on) return fail(h, FEM_ERR_STATE, "the slot's batch was mapped without the mates' overlap (fem_dev_set_pair_overlap)");
-  if (!s.over3_home) {
-    const size_t n = (size_t)s.n_reads;
-    HIP_TRY(h, s.h_over3.ensure(std::max<size_t>(n, 1)));
-    if (n) {
-      HIP_TRY(h, hipMemcpyAsync(s.h_over3, s.d_over3, n * sizeof(uint16_t), hipMemcpyDeviceToHost, s.stream));
-      HIP_TRY(h, hipStreamSynchronize(s.stream));
-    }
-    s.over3_home = true;
-  }
-  if (over3) *over3 = s.h_over3;
-  if (n_reads) *n_reads = s.n_reads;
-  return FEM_OK;
+  return fetch_cuts(h, slot, kOverlap, over3, nullptr, n_reads);
 }
 
 int fem_dev_pair_overlap_count(fem_dev *h, int slot, uint64_t *n_pairs_cut, uint64_t *n_bases_cut) {
-  int rc = fem_dev_sync(h, slot);
-  if (rc) return rc;
-  const Slot &s = h->slot[slot];
-  const bool on = s.trimmed && s.pair_overlap_batch.on;
-  if (n_pairs_cut) *n_pairs_cut = on ? s.h_overlap_ctr[0] : 0;
-  if (n_bases_cut) *n_bases_cut = on ? s.h_overlap_ctr[1] : 0;
-  return FEM_OK;
+  return cut_counts(h, slot, kOverlap, n_pairs_cut, n_bases_cut);
 }
 
 int fem_dev_map_batch_wait(fem_dev *h, int slot, fem_batch_result *out) { return fem_dev_fetch(h, slot, out); }

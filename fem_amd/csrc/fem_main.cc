@@ -285,6 +285,8 @@ struct Growable {  // a reusable host array: only ever grows
   ~Growable() { free(p); }
 };
 
+constexpr int kCutKinds = 3;  // what cuts reads on the device in front of the mapping: the trims, --adapter, --trim-overlap (cut_kinds in map_main)
+
 struct BatchBuf {  // everything about the batch that sits in one (GPU, slot) pair
   uint64_t seq = 0;  // submission number on its GPU: results are handed on in this order
   int gpu = 0, slot = 0;
@@ -310,9 +312,7 @@ struct BatchBuf {  // everything about the batch that sits in one (GPU, slot) pa
   uint64_t n_unmapped = 0;                  // --unmapped: lines for unmapped reads of the batch
   uint64_t n_filtered = 0;                  // --strata / --max-hits: lines left out of the batch's text
   uint64_t n_xa = 0;                        // --xa: lines folded into XA:Z entries in the batch's text
-  uint64_t n_adapter = 0, n_adapter_bases = 0;  // --adapter: reads of the batch with an adapter cut, and the bases cut
-  uint64_t n_overlap = 0, n_overlap_bases = 0;  // --trim-overlap: pairs of the batch with an overlap cut, and the bases cut
-  uint64_t n_trimmed = 0, n_trimmed_bases = 0;  // --trim5 / --trim3 / --trim-qual: reads of the batch that were trimmed, and the bases cut
+  uint64_t n_cut[kCutKinds][2] = {};            // per cut kind: reads (--trim-overlap: pairs) of the batch with a cut, and the bases cut
   fem_batch_result res{};                   // per-candidate outcome (FEM_HOST_TAIL=1)
   double t_submit = 0;
   double t_slot = 0, t_filled = 0, t_submitted = 0, t_retired = 0, t_text = 0;  // FEM_STAGE_TIMES=2: the batch's way through the stages
@@ -615,29 +615,33 @@ int map_main(int argc, char **argv) {
       exit(EXIT_FAILURE);
     }
   }
-  for (const char *v : {"FEM_HOST_TAIL", "FEM_HOST_FORMAT", "FEM_HOST_QUALS"}) {  // (nor the whole read around its kept part: clips, SEQ and QUAL are the device's)
-    const char *x = getenv(v);
-    if (trim_given && x && x[0] == '1') {
-      fprintf(stderr, "--trim5, --trim3 and --trim-qual are not supported with %s=1: the reads are trimmed and their soft clips written on the device, with the qualities there.\n", v);
-      exit(EXIT_FAILURE);
-    }
-  }
-  for (const char *v : {"FEM_HOST_TAIL", "FEM_HOST_FORMAT", "FEM_HOST_QUALS"}) {  // (the adapter's cut is a soft clip as any other)
-    const char *x = getenv(v);
-    if (adapter1 && x && x[0] == '1') {
-      fprintf(stderr, "--adapter is not supported with %s=1: the adapter is cut and the soft clips written on the device, with the qualities there.\n", v);
-      exit(EXIT_FAILURE);
-    }
-  }
-  for (const char *v : {"FEM_HOST_TAIL", "FEM_HOST_FORMAT", "FEM_HOST_QUALS"}) {  // (and so is the overlap's)
-    const char *x = getenv(v);
-    if (trim_overlap && x && x[0] == '1') {
-      fprintf(stderr, "--trim-overlap is not supported with %s=1: the mates are cut and the soft clips written on the device, with the qualities there.\n", v);
-      exit(EXIT_FAILURE);
-    }
-  }
   // what --trim5 / --trim3 / --trim-qual steer, --adapter and --trim-overlap steer too: a batch with any is a trimmed batch on the device
   const bool clip_given = trim_given || adapter1 != nullptr || trim_overlap;
+  // The cut kinds of the device's trim stage, a row each: whether its options were given, whether its counters
+  // are read (the trimmed reads and bases are those of every kind), its count call, its refusal and its two lines on stderr.
+  const struct {
+    bool given, counted;
+    int (*count)(fem_dev *, int, uint64_t *, uint64_t *);
+    const char *refusal, *line[2];
+  } cut_kinds[kCutKinds] = {
+      {trim_given, clip_given, fem_dev_trim_count,
+       "--trim5, --trim3 and --trim-qual are not supported with %s=1: the reads are trimmed and their soft clips written on the device, with the qualities there.\n",
+       {"The number of trimmed reads", "The number of trimmed bases"}},
+      {adapter1 != nullptr, adapter1 != nullptr, fem_dev_adapter_count,
+       "--adapter is not supported with %s=1: the adapter is cut and the soft clips written on the device, with the qualities there.\n",
+       {"The number of reads with adapter", "The number of adapter bases"}},
+      {trim_overlap, trim_overlap, fem_dev_pair_overlap_count,
+       "--trim-overlap is not supported with %s=1: the mates are cut and the soft clips written on the device, with the qualities there.\n",
+       {"The number of pairs with overlap cut", "The number of overlap bases"}}};
+  for (const auto &kind : cut_kinds) {  // (nor the whole read around its kept part: clips, SEQ and QUAL are the device's)
+    for (const char *v : {"FEM_HOST_TAIL", "FEM_HOST_FORMAT", "FEM_HOST_QUALS"}) {
+      const char *x = getenv(v);
+      if (kind.given && x && x[0] == '1') {
+        fprintf(stderr, kind.refusal, v);
+        exit(EXIT_FAILURE);
+      }
+    }
+  }
   for (const char *v : {"FEM_HOST_TAIL", "FEM_HOST_FORMAT"}) {  // (the host formatter has no MAPQ path)
     const char *x = getenv(v);
     if (mapq && x && x[0] == '1') {
@@ -1028,9 +1032,7 @@ int map_main(int argc, char **argv) {
   for (TextOut &t : texts) text_free_q.push(&t);
   std::vector<uint64_t> per_gpu((size_t)n_gpus * 5, 0), per_gpu_proper((size_t)n_gpus, 0),
       per_gpu_rescued((size_t)n_gpus, 0), per_gpu_rescued_disc((size_t)n_gpus, 0), per_gpu_unmapped((size_t)n_gpus, 0), per_gpu_filtered((size_t)n_gpus, 0), per_gpu_xa((size_t)n_gpus, 0),
-      per_gpu_trimmed((size_t)n_gpus, 0), per_gpu_trimmed_bases((size_t)n_gpus, 0),
-      per_gpu_adapter((size_t)n_gpus, 0), per_gpu_adapter_bases((size_t)n_gpus, 0),
-      per_gpu_overlap((size_t)n_gpus, 0), per_gpu_overlap_bases((size_t)n_gpus, 0);
+      per_gpu_cut((size_t)n_gpus * kCutKinds * 2, 0);
 
   // ---- writer (src/output_queue.c:60-91) ----
   std::thread writer([&] {
@@ -1191,9 +1193,8 @@ int map_main(int argc, char **argv) {
         if (!rc && unmapped) rc = fem_dev_unmapped_count(h, b->slot, &b->n_unmapped);
         if (!rc && report) rc = fem_dev_filtered_count(h, b->slot, &b->n_filtered);
         if (!rc && xa_given) rc = fem_dev_xa_count(h, b->slot, &b->n_xa);
-        if (!rc && clip_given) rc = fem_dev_trim_count(h, b->slot, &b->n_trimmed, &b->n_trimmed_bases);
-        if (!rc && adapter1) rc = fem_dev_adapter_count(h, b->slot, &b->n_adapter, &b->n_adapter_bases);
-        if (!rc && trim_overlap) rc = fem_dev_pair_overlap_count(h, b->slot, &b->n_overlap, &b->n_overlap_bases);
+        for (int k = 0; k < kCutKinds; ++k)
+          if (!rc && cut_kinds[k].counted) rc = cut_kinds[k].count(h, b->slot, &b->n_cut[k][0], &b->n_cut[k][1]);
         const double waited = real_time() - t0;
         b->t_retired = t0 + waited;
         double placing = 0;
@@ -1234,9 +1235,7 @@ int map_main(int argc, char **argv) {
           per_gpu_unmapped[(size_t)g] += b->n_unmapped;
           per_gpu_filtered[(size_t)g] += b->n_filtered;
           per_gpu_xa[(size_t)g] += b->n_xa;
-          per_gpu_trimmed[(size_t)g] += b->n_trimmed, per_gpu_trimmed_bases[(size_t)g] += b->n_trimmed_bases;
-          per_gpu_adapter[(size_t)g] += b->n_adapter, per_gpu_adapter_bases[(size_t)g] += b->n_adapter_bases;
-          per_gpu_overlap[(size_t)g] += b->n_overlap, per_gpu_overlap_bases[(size_t)g] += b->n_overlap_bases;
+          for (int i = 0; i < kCutKinds * 2; ++i) per_gpu_cut[(size_t)g * kCutKinds * 2 + (size_t)i] += b->n_cut[i / 2][i % 2];
           if (device_text) {
             n_asserted += b->sam.n_asserted;
             write_q.push(WriteItem{nullptr, b});
@@ -1609,26 +1608,12 @@ int map_main(int argc, char **argv) {
     for (uint64_t x : per_gpu_xa) n_xa += x;
     fprintf(stderr, "The number of XA entries: %lu\n", (unsigned long)n_xa);
   }
-  if (clip_given) {
-    uint64_t n_trimmed = 0, n_trimmed_bases = 0;
-    for (uint64_t x : per_gpu_trimmed) n_trimmed += x;
-    for (uint64_t x : per_gpu_trimmed_bases) n_trimmed_bases += x;
-    fprintf(stderr, "The number of trimmed reads: %lu\n", (unsigned long)n_trimmed);
-    fprintf(stderr, "The number of trimmed bases: %lu\n", (unsigned long)n_trimmed_bases);
-  }
-  if (adapter1) {
-    uint64_t n_adapter = 0, n_adapter_bases = 0;
-    for (uint64_t x : per_gpu_adapter) n_adapter += x;
-    for (uint64_t x : per_gpu_adapter_bases) n_adapter_bases += x;
-    fprintf(stderr, "The number of reads with adapter: %lu\n", (unsigned long)n_adapter);
-    fprintf(stderr, "The number of adapter bases: %lu\n", (unsigned long)n_adapter_bases);
-  }
-  if (trim_overlap) {
-    uint64_t n_overlap = 0, n_overlap_bases = 0;
-    for (uint64_t x : per_gpu_overlap) n_overlap += x;
-    for (uint64_t x : per_gpu_overlap_bases) n_overlap_bases += x;
-    fprintf(stderr, "The number of pairs with overlap cut: %lu\n", (unsigned long)n_overlap);
-    fprintf(stderr, "The number of overlap bases: %lu\n", (unsigned long)n_overlap_bases);
+  for (int k = 0; k < kCutKinds; ++k) {
+    for (int j = 0; j < 2 && cut_kinds[k].counted; ++j) {
+      uint64_t sum = 0;
+      for (int g = 0; g < n_gpus; ++g) sum += per_gpu_cut[((size_t)g * kCutKinds + (size_t)k) * 2 + (size_t)j];
+      fprintf(stderr, "%s: %lu\n", cut_kinds[k].line[j], (unsigned long)sum);
+    }
   }
   if (coverage_path) fprintf(stderr, "The number of covered bases: %lu\n", (unsigned long)n_covered);
   fprintf(stderr, "Time: %fs\n", t_mapping);

@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fem_trim.hip.h"
+
 namespace femov {
 
 constexpr int kWords = 16;  // 64-bit words of a bit plane: reads are <= 1024 bases on the device
@@ -81,12 +83,8 @@ __global__ void __launch_bounds__(64 * kWaves) pair_overlap_kernel(OverlapParams
     int Lp[2];
     const uint8_t *at[2];
     for (int k = 0; k < 2; ++k) {
-      const uint32_t r = k ? n_pairs + i : i;
-      const uint64_t off = p.read_off[r];
-      const int L = (int)(p.read_off[r + 1] - off);
-      const int c5 = p.trim5 < L ? p.trim5 : L;
-      const int c3f = p.trim3 < L - c5 ? p.trim3 : L - c5;
-      Lp[k] = L - c5 - c3f, at[k] = p.bases + off + c5;
+      const femtr::Window w = femtr::fixed_window(p.read_off + (k ? n_pairs + i : i), p.trim5, p.trim3);
+      Lp[k] = w.Lp, at[k] = p.bases + w.off + w.c5;
     }
     const int L1 = Lp[0], L2 = Lp[1];
     const int nx = L1 < 64 * kWords ? (L1 + 63) >> 6 : kWords, nz = L2 < 64 * kWords ? (L2 + 63) >> 6 : kWords;
@@ -119,10 +117,7 @@ __global__ void __launch_bounds__(64 * kWaves) pair_overlap_kernel(OverlapParams
     if (ln == 0) p.over3[i] = (uint16_t)v1, p.over3[n_pairs + i] = (uint16_t)v2;
     if (F > 0) ++n_cut, n_bases += (unsigned long long)(v1 + v2);
   }
-  if (ln == 0 && n_cut) {  // once per wave
-    atomicAdd(p.ctr, (unsigned long long)n_cut);
-    atomicAdd(p.ctr + 1, n_bases);
-  }
+  femtr::add_wave_counts(p.ctr, ln, n_cut, n_bases);
 }
 
 }  // namespace femov

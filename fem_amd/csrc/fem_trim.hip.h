@@ -22,6 +22,28 @@ struct TrimParams {
   unsigned long long *ctr;   // [0] reads with c5 + c3 > 0, [1] the sum of c5 + c3
 };
 
+// A read behind the fixed trims, as every kernel of the trim stage sees it: where the read starts, its length L, the fixed
+// counts c5 and c3f as the read's length bounds them, and what they leave, L' = L - c5 - c3f.
+struct Window {
+  uint64_t off;
+  int L, c5, c3f, Lp;
+};
+__device__ __forceinline__ Window fixed_window(const uint64_t *at, int trim5, int trim3) {  // at: the read's entry of the offsets
+  const uint64_t off = at[0];
+  const int L = (int)(at[1] - off);
+  const int c5 = trim5 < L ? trim5 : L;
+  const int c3f = trim3 < L - c5 ? trim3 : L - c5;
+  return {off, L, c5, c3f, L - c5 - c3f};
+}
+
+// What a wave counted over its reads, added to a producer's two counters once per wave.
+__device__ __forceinline__ void add_wave_counts(unsigned long long *ctr, uint32_t ln, uint32_t n, unsigned long long n_bases) {
+  if (ln == 0 && n) {
+    atomicAdd(ctr, (unsigned long long)n);
+    atomicAdd(ctr + 1, n_bases);
+  }
+}
+
 // One wave per read.  The fixed trims are arithmetic; the adapter's cut, or the overlap's where that is the larger, comes off what
 // they leave, and the quality trim runs on the rest.  The quality trim is the running-sum rule of the header, run from the 3'
 // end in chunks of 64 positions, lane 0 the 3'-most: s = carry + the wave's inclusive scan of Q - q; the ballot of s < 0 gives
@@ -35,16 +57,14 @@ __global__ void __launch_bounds__(256) trim_clip_kernel(TrimParams p) {
   uint32_t n_trimmed = 0;
   unsigned long long n_bases = 0;
   for (uint32_t r = wave; r < p.n_reads; r += n_waves) {
-    const uint64_t off = p.read_off[r];
-    const int L = (int)(p.read_off[r + 1] - off);
-    const int c5 = p.trim5 < L ? p.trim5 : L;
-    const int c3f = p.trim3 < L - c5 ? p.trim3 : L - c5;
+    const Window w = fixed_window(p.read_off + r, p.trim5, p.trim3);
+    const int c5 = w.c5, c3f = w.c3f;
     const int v3 = p.over3 ? (int)p.over3[r] : 0;
     const int a3 = p.adapt3 && (int)p.adapt3[r] > v3 ? (int)p.adapt3[r] : v3;  // (both are measured from the same end of the same L')
-    const int Lp = L - c5 - c3f - a3;
+    const int Lp = w.L - c5 - c3f - a3;  // (the window's L' less the larger cut)
     int cut = Lp;
     if (p.qual > 0 && Lp > kMinKeep) {
-      const uint8_t *q = p.quals + off + c5;
+      const uint8_t *q = p.quals + w.off + c5;
       int carry = 0, best = 0;
       for (int hi = Lp; hi > kMinKeep; hi -= 64) {  // positions [max(hi - 64, K), hi), lane ln at hi - 1 - ln
         const int l = hi - 1 - (int)ln;
@@ -71,14 +91,11 @@ __global__ void __launch_bounds__(256) trim_clip_kernel(TrimParams p) {
     const int c3 = c3f + a3 + (Lp - cut);
     if (ln == 0) {
       p.clip5[r] = (uint16_t)c5, p.clip3[r] = (uint16_t)c3;
-      p.keep[r] = (uint64_t)(L - c5 - c3);
+      p.keep[r] = (uint64_t)(w.L - c5 - c3);
     }
     if (c5 + c3 > 0) ++n_trimmed, n_bases += (unsigned long long)(c5 + c3);
   }
-  if (ln == 0 && n_trimmed) {  // once per wave
-    atomicAdd(p.ctr, (unsigned long long)n_trimmed);
-    atomicAdd(p.ctr + 1, n_bases);
-  }
+  add_wave_counts(p.ctr, ln, n_trimmed, n_bases);
 }
 
 // The kept bytes of every read into the mapping view: a wave per read, the lanes along its bytes.

@@ -225,18 +225,11 @@ def load_hip():
     if hasattr(L, "fem_dev_set_xa"):
         L.fem_dev_set_xa.argtypes = [vp, C.c_int, C.c_int32]
         L.fem_dev_xa_count.argtypes = [vp, C.c_int, C.POINTER(u64)]
-    if hasattr(L, "fem_dev_set_trim"):
-        L.fem_dev_set_trim.argtypes = [vp, C.c_int, C.POINTER(_TrimParams)]
-        L.fem_dev_fetch_trim.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
-        L.fem_dev_trim_count.argtypes = [vp, C.c_int, C.POINTER(u64), C.POINTER(u64)]
-    if hasattr(L, "fem_dev_set_adapter"):
-        L.fem_dev_set_adapter.argtypes = [vp, C.c_int, C.POINTER(_AdapterParams)]
-        L.fem_dev_fetch_adapter.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(u64)]
-        L.fem_dev_adapter_count.argtypes = [vp, C.c_int, C.POINTER(u64), C.POINTER(u64)]
-    if hasattr(L, "fem_dev_set_pair_overlap"):
-        L.fem_dev_set_pair_overlap.argtypes = [vp, C.c_int, C.POINTER(_PairOverlapParams)]
-        L.fem_dev_fetch_pair_overlap.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(u64)]
-        L.fem_dev_pair_overlap_count.argtypes = [vp, C.c_int, C.POINTER(u64), C.POINTER(u64)]
+    for name, params, n_arrays in (("trim", _TrimParams, 2), ("adapter", _AdapterParams, 1), ("pair_overlap", _PairOverlapParams, 1)):
+        if hasattr(L, "fem_dev_set_" + name):
+            getattr(L, "fem_dev_set_" + name).argtypes = [vp, C.c_int, C.POINTER(params)]
+            getattr(L, "fem_dev_fetch_" + name).argtypes = [vp, C.c_int] + [C.POINTER(vp)] * n_arrays + [C.POINTER(u64)]
+            getattr(L, "fem_dev_%s_count" % name).argtypes = [vp, C.c_int, C.POINTER(u64), C.POINTER(u64)]
     if hasattr(L, "fem_dev_fetch_bam"):
         L.fem_dev_fetch_bam.argtypes = [vp, C.c_int, C.c_int, C.POINTER(_BatchBam)]
         L.fem_dev_fetch_bam_nowait.argtypes = [vp, C.c_int, C.c_int, C.POINTER(_BatchBam)]
@@ -836,6 +829,18 @@ class Device:
         self._check(self._L.fem_dbg_stage_ms(self._h, slot, int(stage), C.byref(ms)))
         return float(ms.value)
 
+    def _fetch_cuts(self, fn, slot, n_arrays=1):
+        """A cut producer's fetch (fem_dev_fetch_trim, _adapter, _pair_overlap): its uint16 arrays, read for read."""
+        ptrs, n = [C.c_void_p() for _ in range(n_arrays)], C.c_uint64()
+        self._check(fn(self._h, slot, *[C.byref(p) for p in ptrs], C.byref(n)))
+        return [_copy(p.value, n.value, np.uint16) for p in ptrs]
+
+    def _cut_counts(self, fn, slot):
+        """A cut producer's two counters (fem_dev_trim_count, _adapter_count, _pair_overlap_count)."""
+        n_cut, n_bases = C.c_uint64(), C.c_uint64()
+        self._check(fn(self._h, slot, C.byref(n_cut), C.byref(n_bases)))
+        return int(n_cut.value), int(n_bases.value)
+
     def set_trim(self, trim5=0, trim3=0, qual=0, slot=0):
         """fem_dev_set_trim: the slot's batches are trimmed on the device from the next fem_dev_map_staged on: trim5 / trim3 bases
         (0..1024) off the reads' ends, the 3' end by quality at qual (1..93; 0: off); all 0: off.  The SAM text and BAM records
@@ -845,15 +850,11 @@ class Device:
 
     def fetch_trim(self, slot=0):
         """fem_dev_fetch_trim: (clip5, clip3) of the slot's trimmed batch, read for read (uint16 arrays)."""
-        p5, p3, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
-        self._check(self._L.fem_dev_fetch_trim(self._h, slot, C.byref(p5), C.byref(p3), C.byref(n)))
-        return _copy(p5.value, n.value, np.uint16), _copy(p3.value, n.value, np.uint16)
+        return tuple(self._fetch_cuts(self._L.fem_dev_fetch_trim, slot, 2))
 
     def trim_count(self, slot=0):
         """fem_dev_trim_count: (reads the slot's batch had trimmed, bases trimmed off them)."""
-        nr, nb = C.c_uint64(), C.c_uint64()
-        self._check(self._L.fem_dev_trim_count(self._h, slot, C.byref(nr), C.byref(nb)))
-        return int(nr.value), int(nb.value)
+        return self._cut_counts(self._L.fem_dev_trim_count, slot)
 
     def set_adapter(self, seq1=None, seq2=None, min_overlap=5, err_pct=10, slot=0):
         """fem_dev_set_adapter: the slot's batches have the 3' adapter seq1 (mate 2 in pair mode: seq2, default seq1; 4..64 letters
@@ -868,15 +869,11 @@ class Device:
 
     def fetch_adapter(self, slot=0):
         """fem_dev_fetch_adapter: the adapter cuts a3 of the slot's batch, read for read (a uint16 array)."""
-        pa, n = C.c_void_p(), C.c_uint64()
-        self._check(self._L.fem_dev_fetch_adapter(self._h, slot, C.byref(pa), C.byref(n)))
-        return _copy(pa.value, n.value, np.uint16)
+        return self._fetch_cuts(self._L.fem_dev_fetch_adapter, slot)[0]
 
     def adapter_count(self, slot=0):
         """fem_dev_adapter_count: (reads of the slot's batch with an adapter cut, bases cut off them)."""
-        nr, nb = C.c_uint64(), C.c_uint64()
-        self._check(self._L.fem_dev_adapter_count(self._h, slot, C.byref(nr), C.byref(nb)))
-        return int(nr.value), int(nb.value)
+        return self._cut_counts(self._L.fem_dev_adapter_count, slot)
 
     def set_pair_overlap(self, min_overlap=20, err_pct=10, slot=0):
         """fem_dev_set_pair_overlap: in pair mode the slot's batches have the read-through of both mates found from their overlap
@@ -891,15 +888,11 @@ class Device:
 
     def fetch_pair_overlap(self, slot=0):
         """fem_dev_fetch_pair_overlap: the overlap cuts v3 of the slot's batch, read for read (a uint16 array)."""
-        pv, n = C.c_void_p(), C.c_uint64()
-        self._check(self._L.fem_dev_fetch_pair_overlap(self._h, slot, C.byref(pv), C.byref(n)))
-        return _copy(pv.value, n.value, np.uint16)
+        return self._fetch_cuts(self._L.fem_dev_fetch_pair_overlap, slot)[0]
 
     def pair_overlap_count(self, slot=0):
         """fem_dev_pair_overlap_count: (pairs of the slot's batch with an overlap cut, bases cut off both mates)."""
-        nr, nb = C.c_uint64(), C.c_uint64()
-        self._check(self._L.fem_dev_pair_overlap_count(self._h, slot, C.byref(nr), C.byref(nb)))
-        return int(nr.value), int(nb.value)
+        return self._cut_counts(self._L.fem_dev_pair_overlap_count, slot)
 
     def filtered_count(self, slot=0):
         """fem_dev_filtered_count: lines the filter left out of the slot's last SAM text or BAM."""

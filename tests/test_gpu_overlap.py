@@ -126,6 +126,24 @@ def test_adapter_and_overlap_together_take_the_larger_cut(small_dev):
     assert [int(a) for a in small_dev.fetch_adapter()] == a3 and small_dev.adapter_count() == am.counts(a3)  # the adapter's own matches
 
 
+def test_fetches_repeat_and_end_with_their_batch(small_dev):
+    """Every producer's cuts come home once per batch: a second fetch gives what the first gave, and the slot's next batch, the
+    same pairs in reverse order, gives its own."""
+    p = am.pairs_case()
+    n, names2, seen = p["n"], p["rnames"] + p["rnames"], []
+    for pairs in (list(range(n)), list(range(n - 1, -1, -1))):
+        pick = pairs + [n + i for i in pairs]
+        reads, quals = [p["reads"][i] for i in pick], [p["quals"][i] for i in pick]
+        _map(small_dev, reads, [names2[i] for i in pick], quals, 2, adapter=A1, adapter2=A2, trim=(2, 3, 20))
+        cl, v3, a3 = m.batch_clips(reads, quals, 2, 3, 20, A=A1, A2=A2)
+        assert m.counts(v3)[0] > 100 and am.counts(a3)[0] > 100 and all(c5 == 2 and c3 >= 3 for c5, c3 in cl)
+        for _ in range(2):
+            _check_cuts(small_dev, cl, v3)
+            assert [int(a) for a in small_dev.fetch_adapter()] == a3 and small_dev.adapter_count() == am.counts(a3)
+        seen.append((cl, v3, a3))
+    assert all(a != b for a, b in zip(*seen))  # an array left over from the first batch would not pass for the second's
+
+
 # ---- 2. as-if on the arrays and in the text: the pairs case ----
 
 @functools.lru_cache(maxsize=None)
