@@ -184,3 +184,124 @@ def test_map_regrows_its_staging_for_unusual_records(tmp_path):
         assert r.returncode == 0, r.stderr.decode()
         assert open(out).read() == exp
     assert want.stats[1] > 300
+
+
+# ---- FEM map's argument checks, message by message: which refusal comes first, from the command line and the environment alone ----
+
+_NO = "/nonexistent/"
+_REQ = {"--ref": _NO + "a.fa", "--index": _NO + "a.idx", "--read1": _NO + "r.fq", "-o": _NO + "o.sam"}
+_R2 = ["--read2", _NO + "r2.fq"]
+_COV = ["--coverage", _NO + "c.bed"]
+_DEV_TEXT = ", with its SAM text or BAM."
+_DEV_QUAL = ", with the qualities there."
+_PASSED = "Cannot find sequence file!"  # every argument check passed: the reference file is the first thing opened
+_HOST_ROWS = [  # the options the host-side paths refuse, in the order they are looked at: arguments, message, refused by FEM_HOST_QUALS=1 too
+    (["--bam"], "--bam is not supported with %s=1: BAM records are made on the device" + _DEV_QUAL, True),
+    (_R2 + ["--mate-tags"], "--mate-tags is not supported with %s=1: the mate tags are made on the device" + _DEV_QUAL, True),
+    (["--sam-seq"], "--sam-seq is not supported with %s=1: SEQ and QUAL are turned on the device" + _DEV_QUAL, True),
+    (["--trim3", "2"], "--trim5, --trim3 and --trim-qual are not supported with %s=1: the reads are trimmed and their soft clips written on the device" + _DEV_QUAL, True),
+    (["--adapter", "ACGTAC"], "--adapter is not supported with %s=1: the adapter is cut and the soft clips written on the device" + _DEV_QUAL, True),
+    (_R2 + ["--trim-overlap"], "--trim-overlap is not supported with %s=1: the mates are cut and the soft clips written on the device" + _DEV_QUAL, True),
+    (["--mapq"], "--mapq is not supported with %s=1: mapping qualities are made on the device" + _DEV_TEXT, False),
+    (["--unmapped"], "--unmapped is not supported with %s=1: the lines of unmapped reads are made on the device" + _DEV_TEXT, False),
+    (["--nh"], "--rg and --nh are not supported with %s=1: the tags are made on the device" + _DEV_TEXT, False),
+    (["--xa"], "--xa is not supported with %s=1: the secondary lines are folded on the device" + _DEV_TEXT, False),
+    (_COV, "--coverage is not supported with %s=1: the coverage track is summed on the device, from the lines of its SAM text or BAM.", False),
+    (["--max-hits", "3"], "--strata and --max-hits are not supported with %s=1: the lines are filtered on the device" + _DEV_TEXT, False),
+]
+_TAIL, _FORMAT, _QUALS = {"FEM_HOST_TAIL": "1"}, {"FEM_HOST_FORMAT": "1"}, {"FEM_HOST_QUALS": "1"}
+_REFUSALS = [  # (arguments, required arguments left out, environment, the first line on stderr)
+    # refusals that nothing else pins
+    (["-t", "0"], (), None, "Wrong number of threads."),
+    (["--mate-tags"], (), None, "--mate-tags needs --read2."),
+    (["--coverage-window", "5"], (), None, "--coverage-window, --coverage-all and --coverage-mapq need --coverage."),
+    (_COV + ["--coverage-window", "0"], (), None, "Wrong coverage window (1-1000000)."),
+    (_COV + ["--coverage-mapq", "61", "--mapq"], (), None, "Wrong coverage MAPQ threshold (1-60)."),
+    (_COV + ["--coverage-mapq", "5"], (), None, "--coverage-mapq needs --mapq."),
+    ([], ("--index",), None, "Index file path is required."),
+    ([], ("--read1",), None, "Read file path is required."),
+    ([], ("-o",), None, "Output file path is required."),
+    (["--gpus", "0"], (), None, "Wrong number of GPUs."),
+    (["--gpus", "65"], (), None, "Wrong number of GPUs."),
+    (["--batch", "0"], (), None, "Wrong batch size."),
+    # two faults each: the check that stands earlier in the chain speaks
+    (["--mate-tags", "--trim5", "2000"], (), None, "--mate-tags needs --read2."),
+    (["--trim5", "2000", "--gpus", "99"], (), None, "Wrong number of bases to trim (0-1024)."),
+    (["--strata", "x", "--max-hits", "0"], (), None, "Wrong number of strata (0-15)."),
+    (["-e", "9", "-t", "0"], (), None, "Wrong error threshold."),
+    (["-t", "0", "-a", "3"], (), None, "Wrong number of threads."),
+    (["-a", "3", "-I", "5", "-X", "2"], (), None, "Wrong number of additional q-grams."),
+    (["-I", "5", "-X", "2", "--infer-insert"], (), None, "Wrong insert size range."),
+    (["--infer-insert", "--orientation", "xx"], (), None, "--infer-insert needs read pairs (--read2)."),
+    (_R2 + ["--infer-insert=5", "--orientation", "xx"], (), None, "Wrong number of pairs to infer from (64-262144)."),
+    (["--orientation", "xx", "--mate-tags"], (), None, "Wrong library orientation (fr, rf, ff or auto)."),
+    (["--orientation", "rf", "--mate-tags"], (), None, "--orientation needs read pairs (--read2)."),
+    (_R2 + ["--orientation", "auto", "--rescue-discordant"], (), None, "--orientation auto needs --infer-insert."),
+    (["--rescue-discordant", "--bam=5"], (), None, "--rescue-discordant needs --rescue."),
+    (["--rescue", "3", "--rescue-discordant", "--bam=5"], (), None, "--rescue needs read pairs (--read2)."),
+    (_R2 + ["--rescue", "16", "-X", "100000"], (), None, "Wrong rescue error threshold (0-15)."),
+    (_R2 + ["--rescue", "3", "-X", "100000", "--bam=5"], (), None, "--rescue searches insert size ranges of at most 65536."),
+    (["--bam=5", "--strata", "16"], (), None, "Wrong BAM compression level (0-1)."),
+    (["--max-hits", "0", "--xa=0"], (), None, "Wrong hit limit (>= 1)."),
+    (["--xa=0", "--trim3", "2000"], (), None, "Wrong number of --xa entries (1-1000000)."),
+    (["--trim3", "2000", "--trim-qual", "0"], (), None, "Wrong number of bases to trim (0-1024)."),
+    (["--trim-qual", "0", "--adapter2", "ACGT"], (), None, "Wrong trimming quality (1-93)."),
+    (["--adapter-err", "5", "--adapter", "AC"], (), None, "Wrong adapter sequence (4-64 letters of ACGT)."),
+    (["--adapter2", "ACGT", "--trim-overlap-min", "9"], (), None, "--adapter2, --adapter-overlap and --adapter-err need --adapter."),
+    (["--adapter", "AC", "--adapter2", "ACGT"], (), None, "--adapter2 needs --read2."),
+    (["--adapter", "ACGTAC", "--adapter-overlap", "7", "--adapter-err", "31"], (), None, "Wrong adapter overlap (1 to the adapter's length)."),
+    (["--adapter", "ACGTAC", "--adapter-err", "31", "--trim-overlap-min", "9"], (), None, "Wrong adapter error percentage (0-30)."),
+    (["--trim-overlap-min", "9", "--coverage-all"], (), None, "--trim-overlap-min and --trim-overlap-err need --trim-overlap."),
+    (["--trim-overlap", "--trim-overlap-min", "2"], (), None, "--trim-overlap needs read pairs (--read2)."),
+    (_R2 + ["--trim-overlap", "--trim-overlap-min", "2", "--trim-overlap-err", "40"], (), None, "Wrong overlap of the mates (8-1024)."),
+    (_R2 + ["--trim-overlap", "--trim-overlap-err", "40", "--coverage-all"], (), None, "Wrong overlap error percentage (0-30)."),
+    (["--coverage-all", "--gpus", "0"], (), None, "--coverage-window, --coverage-all and --coverage-mapq need --coverage."),
+    (_COV + ["--coverage-window", "0", "--coverage-mapq", "99"], (), None, "Wrong coverage window (1-1000000)."),
+    (_COV + ["--coverage-mapq", "99"], (), None, "Wrong coverage MAPQ threshold (1-60)."),
+    (_COV + ["--coverage-mapq", "5"], ("--ref",), None, "--coverage-mapq needs --mapq."),
+    ([], ("--ref", "--index"), None, "Reference file path is required."),
+    ([], ("--index", "--read1"), None, "Index file path is required."),
+    ([], ("--read1", "-o"), None, "Read file path is required."),
+    (["--gpus", "0"], ("-o",), None, "Output file path is required."),
+    (["--gpus", "0", "--batch", "0"], (), None, "Wrong number of GPUs."),
+    (["--rg", "bogus", "-e", "9"], (), None, "Wrong --rg line: the read group line does not begin with @RG and a tab."),
+    (["-e", "9"], (), _FORMAT, "Wrong error threshold."),  # (the argument checks stand in front of the environment's)
+    # a value that is no number: the option's own range message
+    (_COV + ["--coverage-window", "x"], (), None, "Wrong coverage window (1-1000000)."),
+    (_COV + ["--mapq", "--coverage-mapq", "x"], (), None, "Wrong coverage MAPQ threshold (1-60)."),
+    (["--strata", "x"], (), None, "Wrong number of strata (0-15)."),
+    (["--max-hits", "x"], (), None, "Wrong hit limit (>= 1)."),
+    (["--xa=x"], (), None, "Wrong number of --xa entries (1-1000000)."),
+    (_R2 + ["--rescue", "x"], (), None, "Wrong rescue error threshold (0-15)."),
+    (_R2 + ["--infer-insert=x"], (), None, "Wrong number of pairs to infer from (64-262144)."),
+    (["--trim5", "x"], (), None, "Wrong number of bases to trim (0-1024)."),
+    (["--trim3", "2x"], (), None, "Wrong number of bases to trim (0-1024)."),
+    (["--trim-qual", "x"], (), None, "Wrong trimming quality (1-93)."),
+    (["--adapter", "ACGTAC", "--adapter-overlap", "x"], (), None, "Wrong adapter overlap (1 to the adapter's length)."),
+    (["--adapter", "ACGTAC", "--adapter-err", "x"], (), None, "Wrong adapter error percentage (0-30)."),
+    (_R2 + ["--trim-overlap", "--trim-overlap-min", "x"], (), None, "Wrong overlap of the mates (8-1024)."),
+    (_R2 + ["--trim-overlap", "--trim-overlap-err", "x"], (), None, "Wrong overlap error percentage (0-30)."),
+    # the host-side paths: the first option in the table's order speaks, of the first variable that is set
+    (["--unmapped", "--mapq"], (), dict(_TAIL, **_FORMAT), _HOST_ROWS[6][1] % "FEM_HOST_TAIL"),
+    (["--xa", "--strata", "1", "--bam"], (), _FORMAT, _HOST_ROWS[0][1] % "FEM_HOST_FORMAT"),
+    (["--coverage-all", "--sam-seq"] + _COV, (), dict(_FORMAT, **_QUALS), _HOST_ROWS[2][1] % "FEM_HOST_FORMAT"),
+    (["--max-hits", "3", "--xa", "--nh"], (), _TAIL, _HOST_ROWS[8][1] % "FEM_HOST_TAIL"),
+    (["--rg", "@RG\\tID:x"], (), _FORMAT, _HOST_ROWS[8][1] % "FEM_HOST_FORMAT"),
+    (["--strata", "1"], (), _TAIL, _HOST_ROWS[11][1] % "FEM_HOST_TAIL"),
+    (["--trim-qual", "20", "--adapter", "ACGTAC"], (), _QUALS, _HOST_ROWS[3][1] % "FEM_HOST_QUALS"),
+    (_R2 + ["--trim-overlap", "--adapter", "ACGTAC", "--mapq"], (), _TAIL, _HOST_ROWS[4][1] % "FEM_HOST_TAIL"),
+    (_R2, (), _FORMAT, _PASSED),  # (--read2 on the host-side paths is refused behind the reference and the index, not here)
+]
+# ... and every row of it: refused under FEM_HOST_FORMAT=1; under FEM_HOST_QUALS=1 refused where the qualities are needed on the
+# device, and served (the argument checks passed) where they are not
+_REFUSALS += [(args, (), _FORMAT, msg % "FEM_HOST_FORMAT") for args, msg, _ in _HOST_ROWS if "--read2" not in args]
+_REFUSALS += [(args, (), _QUALS, msg % "FEM_HOST_QUALS" if quals else _PASSED) for args, msg, quals in _HOST_ROWS]
+
+
+@pytest.mark.parametrize("args,without,env,first_line", _REFUSALS)
+def test_map_refusals_in_order(args, without, env, first_line):
+    required = [w for k, v in _REQ.items() if k not in without for w in (k, v)]
+    # (FEM_NUMA_BIND=0: a command line that passes the checks asks for no device's NUMA node on its way to the reference file)
+    r = run_fem("map", *required, *args, env=dict(env or {}, FEM_NUMA_BIND="0"), text=True)
+    assert r.returncode == 1
+    assert r.stderr.splitlines()[0] == first_line
