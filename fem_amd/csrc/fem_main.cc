@@ -820,6 +820,11 @@ int open_devices(const MapOptions &o, const Reference &ref, const Index &ix, con
     if (up_rc[(size_t)g]) return dev_fail((*devs)[(size_t)g], "device setup (mapping runs on the GPU; no CPU path)", up_rc[(size_t)g]);
   free(ix.lookup), free(ix.occ);
   fprintf(stderr, "Reference and index resident on %d GPU%s in %fs.\n", o.n_gpus, o.n_gpus > 1 ? "s" : "", real_time() - t_dev);
+  if (env_var("FEM_TESTING").c == '1') {  // (a test that steers the kernel choice through the environment reads here what ran)
+    char info[512] = "";
+    (void)fem_dev_index_info((*devs)[0], info, sizeof info);
+    fprintf(stderr, "Seed kernel: %s (index: %s).\n", fem_dev_seed_kernel((*devs)[0], &o.params), info);
+  }
   return 0;
 }
 

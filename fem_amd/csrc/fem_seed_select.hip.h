@@ -162,6 +162,35 @@ __device__ __forceinline__ PackedArgs packed_args() {
   return {a->packed, a->bases, a->exc_bits, a->bpr, a->len};
 }
 
+// The place word of the frequency loop (seed_select_kernel): what a lane keeps of a round between its loads and their use.
+//   bits 0..3 the read's place in the sub-block | 4..13 its first seed j | 14..23 the read's seeds S | 24 "seed j + 1 too" | 25 active
+// S is the unsigned r_len - (k - 1): for a read of fewer than k - 1 bases it wraps to 0xFFFFFFF5.., and shifted by 14 its bits
+// would land on both flags — a lane that is not active would go on and store a thousand elements behind its read's row, in
+// other reads' frequencies and in the next wave's LDS.  So S goes into the word of an active lane only (act implies
+// 1 <= S <= kSelMaxPlaceS); the asserts below hold the layout to that.
+constexpr uint32_t kPlaceTwo = 1u << 24, kPlaceAct = 1u << 25;
+constexpr uint32_t kSelMaxPlaceS = 1024u - (uint32_t)(kK - 1);  // seeds of the longest read the device path takes (1024 bases)
+constexpr __host__ __device__ uint32_t place_pack(uint32_t read, uint32_t j, uint32_t S, bool two, bool act) {
+  return read | (j << 4) | (act ? (S << 14) | kPlaceAct : 0u) | (two ? kPlaceTwo : 0u);
+}
+constexpr __host__ __device__ uint32_t place_read(uint32_t w) { return w & 15u; }
+constexpr __host__ __device__ uint32_t place_first(uint32_t w) { return (w >> 4) & 1023u; }
+constexpr __host__ __device__ uint32_t place_seeds(uint32_t w) { return (w >> 14) & 1023u; }
+constexpr bool place_idle_is_clean() {  // lengths 0 .. k - 2: the wrapped S, every place, the largest j a lane computes
+  for (uint32_t len = 0; len + 1u < (uint32_t)kK; ++len)
+    for (uint32_t read = 0; read < kReadBlock; ++read)
+      if (place_pack(read, kSelMaxPlaceS - 1u, len - (uint32_t)(kK - 1), false, false) & (kPlaceAct | kPlaceTwo)) return false;
+  return true;
+}
+static_assert(place_idle_is_clean(), "a lane that is not active must carry neither flag, whatever its read's length");
+static_assert(kReadBlock - 1u <= 15u && kSelMaxPlaceS == 1013u, "the fields are 4, 10 and 10 bits wide");
+static_assert(place_read(place_pack(15u, 1012u, 1013u, true, true)) == 15u && place_first(place_pack(15u, 1012u, 1013u, true, true)) == 1012u &&
+                  place_seeds(place_pack(15u, 1012u, 1013u, true, true)) == 1013u,
+              "the fields round-trip at their largest values");
+static_assert((place_pack(15u, 1012u, 1013u, true, true) >> 24) == 3u && (place_pack(15u, 1012u, 1013u, false, true) >> 24) == 2u &&
+                  (place_pack(0u, 0u, 1u, false, true) >> 24) == 2u,
+              "the flags are the lane's own");
+
 #ifndef FEM_SELECT_WAVES
 #define FEM_SELECT_WAVES 6
 #endif
@@ -348,9 +377,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FEM_SE
         const uint32_t magic = 0xFFFFFFFFu / SPp + 1u;   // w / SPp = umulhi(w, magic) for w * SPp < 2^32
         const uint32_t total = cnt * SPp;
         constexpr int U = FEM_SELECT_UNROLL;
-        constexpr uint32_t kActBit = 1u << 25, kTwoBit = 1u << 24;
-        // U rounds of loads are issued before the first one is used; a round's place (read | first seed << 4 | S << 14 | flags)
-        // waits in one register.  The kernel shares the chip with seed_join_kernel: it is built to be small.
+        // U rounds of loads are issued before the first one is used; a round's place (place_pack above) waits in one register.
+        // The kernel shares the chip with seed_join_kernel: it is built to be small.
         for (uint32_t w0 = 0; w0 < total; w0 += (uint32_t)(U * kWave)) {
           uint32_t d0[U], d1[U], where[U];
 #pragma unroll
@@ -369,13 +397,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FEM_SE
             const uint32_t at0 = ((hf0 & (kX11 - 1u)) << 2) | (hf0 >> 22), at1 = (win >> 6) & kHashMask;
             d0[u] = p.freq11[act ? at0 : 0u];
             d1[u] = p.freq11[two ? at1 : 0u];
-            where[u] = i_c | (j << 4) | (S << 14) | (two ? kTwoBit : 0u) | (act ? kActBit : 0u);
+            where[u] = place_pack(i_c, j, S, two, act);
           }
 #pragma unroll
           for (int u = 0; u < U; ++u) {
-            if (where[u] & kActBit) {
-              const uint32_t i = where[u] & 15u, j = (where[u] >> 4) & 1023u, S = (where[u] >> 14) & 1023u;
-              const bool two = (where[u] & kTwoBit) != 0u;
+            if (where[u] & kPlaceAct) {
+              const uint32_t i = place_read(where[u]), j = place_first(where[u]), S = place_seeds(where[u]);
+              const bool two = (where[u] & kPlaceTwo) != 0u;
               // bytes: f(seed j), f(its reverse complement), f(seed j + 1), f(its reverse complement)
               uint32_t x = (d0[u] & 0x0000FFFFu) | (d1[u] & 0xFFFF0000u);
               if (!two) x &= 0x0000FFFFu;

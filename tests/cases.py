@@ -630,6 +630,89 @@ def banked_reference(rng, n_seq, shared):
     return seqs
 
 
+# ---- ragged batches with reads too short to seed (tests/test_gpu_dense_short_reads.py; the draw of tests/fuzz_gpu.py) ----
+
+# (e, longest read): seed_select_kernel works on sub-blocks of 13, 8, 5, 5 and 2 reads at these (make_layout_select, fem_hip.hip)
+SHORT_PARAMS = [(0, 64), (3, 100), (3, 150), (7, 150), (2, 300)]
+SHORT_N = 17 * 16 * 2  # read r short iff r % 17 == 0: the short read visits every place of the 16-read block, twice
+TOO_SHORT = 14         # lengths below this (0..13) have at most two 12-mers: the draw of tests/fuzz_gpu.py
+
+
+def short_lengths(e):
+    """No base, one, the last length whose unsigned L - (k - 1) wraps, the first that does not, one and two seeds, and one base
+    under the shape gate of src/filter.c:5-7 at a = 1 (L - 11 - 2 >= 12 (e + 2): 37 + 12 e bases)."""
+    return (0, 1, 10, 11, 12, 13, 36 + 12 * e)
+
+
+@functools.lru_cache(maxsize=None)
+def short_reads_reference():
+    """A random sequence of 200 kbp with three units of 400 bases planted four times each (0..2 edits a copy), and a second
+    sequence of ~21 kbp that holds each unit again: reads inside a unit have several hits, in both sequences (both banks).
+    -> seqs, names, ref, idx."""
+    rng = np.random.default_rng(1700)
+    units = [util.rand_seq(rng, 400) for _ in range(3)]
+    main, second = [], []
+    for i in range(12):
+        main += [util.rand_seq(rng, 16_266), util.mutate(rng, units[i % 3], int(rng.integers(0, 3)))]
+    for u in units:
+        second += [util.rand_seq(rng, 5_000), u]
+    seqs = [b"".join(main), b"".join(second + [util.rand_seq(rng, 5_000)])]
+    ref = fo.Reference(seqs)
+    return seqs, ["chr0", "chr1"], ref, fo.OracleIndex(ref)
+
+
+def every_17th_short(e, n=SHORT_N):
+    ls = short_lengths(e)
+    return {r: ls[(r // 17) % len(ls)] for r in range(0, n, 17)}
+
+
+@functools.lru_cache(maxsize=None)
+def short_reads_batch(seed, e, L, n=SHORT_N, short=None):
+    """n reads: read r has short[r] bases where r is in `short` (a tuple of (read, length) pairs; None: every_17th_short), else
+    L - 0..L/8 bases with 0..e edits, a third of them from inside the planted units; the first long read has exactly L bases (the
+    kernels' layout follows the longest read).  Short reads are prefixes of reads that would map.  The oracle's result of the
+    batch and of the batch without its short reads.  -> dict."""
+    seqs, names, ref, idx = short_reads_reference()
+    short = every_17th_short(e, n) if short is None else dict(short)
+    rng = np.random.default_rng(seed)
+    unit_at = [i * (16_266 + 400) + 16_266 for i in range(12)]  # (where the units start, but for the indels of earlier copies)
+    reads, first_long = [], True
+    for r in range(n):
+        ln = short[r] if r in short else L if first_long else L - int(rng.integers(0, L // 8 + 1))
+        first_long = first_long and r in short
+        if r not in short and r % 3 == 0 and ln + e + 2 < 380:
+            at = unit_at[int(rng.integers(0, 12))] + int(rng.integers(10, 380 - ln - e))
+            read = util.mutate(rng, seqs[0][at:at + ln + e], int(rng.integers(0, e + 1)))[:ln]
+            read = read + util.rand_seq(rng, ln - len(read))
+            read = util.revcomp(read) if rng.random() < 0.5 else read
+        else:
+            read = util.make_reads(rng, seqs, 1, max(ln, 1), e if r not in short else 0)[0][:ln]
+        assert len(read) == ln
+        reads.append(read)
+    long_reads = [x for r, x in enumerate(reads) if r not in short]
+    want = fo.map_reads(ref, idx, fo.ReadBatch(reads), e=e, threads=8)
+    want_long = fo.map_reads(ref, idx, fo.ReadBatch(long_reads), e=e, threads=8) if long_reads else None
+    return dict(reads=reads, short=sorted(short), e=e, L=L, want=want, want_long=want_long, rnames=["s%d" % r for r in range(n)],
+                quals=quals(reads))
+
+
+def per_read(res, n):
+    """The oracle's result read by read: (candidates, edit distances and end offsets of both strands; FLAG, sequence, POS, NM,
+    CIGAR and MD of its records), as bytes — what test_gpu_dense_short_reads.py compares between a batch and its long reads."""
+    out = []
+    for r in range(n):
+        c0, c1 = int(res.cand_off[2 * r]), int(res.cand_off[2 * r + 2])
+        mid = int(res.cand_off[2 * r + 1]) - c0
+        ok = res.v_ed[c0:c1] != 0xFF
+        j0, j1 = int(res.rec_off[r]), int(res.rec_off[r + 1])
+        g0, g1, m0, m1 = int(res.cig_off[j0]), int(res.cig_off[j1]), int(res.md_off[j0]), int(res.md_off[j1])
+        out.append((mid, res.cands[c0:c1].tobytes(), res.v_ed[c0:c1].tobytes(), res.v_end[c0:c1][ok].tobytes(),
+                    res.r_flag[j0:j1].tobytes(), res.r_tid[j0:j1].tobytes(), res.r_pos[j0:j1].tobytes(), res.r_nm[j0:j1].tobytes(),
+                    (res.cig_off[j0 + 1:j1 + 1] - res.cig_off[j0]).tobytes(), res.cig[g0:g1].tobytes(),
+                    (res.md_off[j0 + 1:j1 + 1] - res.md_off[j0]).tobytes(), res.md[m0:m1].tobytes()))
+    return out
+
+
 # ---- solo regions of the join tests (tests/test_gpu_join_units.py, test_gpu_join_flags.py) ----
 
 SOLO_SLOTS = 14                            # indexed 12-mers of a solo region: offsets 0, 3, .. 39 -> 51 bases

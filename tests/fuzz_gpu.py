@@ -28,14 +28,29 @@ def reference(rng, kind, threads=16):
     return seqs
 
 
-def trial(rng, dev, ref, idx, tref, seqs, kind, threads=16, max_reads=15000, log=print):
-    """One random batch through oracle and device; True if everything compared is identical."""
+TOO_SHORT = 14  # reads of 0..13 bases: none, one or two 12-mers, and below k - 1 = 11 the lengths whose seed count would be negative
+
+
+def draw(rng, seqs, kind, max_reads=15000):
+    """One trial's draws, all of them, in the order the generator has always made them: parameters, reads, the slot and — where
+    records and text are compared (full) — qualities, names and how the text is fetched.  Needs no device: a slice's trials can
+    be listed on the CPU."""
     e = int(rng.integers(0, 8)); a = int(rng.choice([1, 1, 1, 2]))
     L = int(rng.integers(30, 301)); n = int(rng.integers(500, min(6000, max_reads) if kind == "repeat" else max_reads))
     reads = util.make_reads(rng, seqs, n, L, min(e + 2, 9), n_rate=float(rng.choice([0, 0, 0.002, 0.02])))
+    n_short, n_drawn = 0, n * L
     if rng.random() < 0.4:  # mixed lengths
         for j in range(0, n, 3):
             reads[j] = reads[j][:int(rng.integers(max(1, L // 3), L + 1))]
+        # ... a tenth of the shortened reads with 0..13 bases: reads without a seed among reads with many.  From a child stream,
+        # and with the draws below sized as before it (n_drawn; the reads of random letters keep their lengths), so that every
+        # other draw of a seed is what it was without these
+        n_drawn = sum(len(r) for r in reads)
+        child = rng.spawn(1)[0]
+        for j in range(0, n, 3):
+            if j % 97 and child.random() < 0.1:
+                reads[j] = reads[j][:int(child.integers(0, TOO_SHORT))]
+                n_short += 1
     if rng.random() < 0.3:
         for j in range(0, n, 11):
             reads[j] = reads[j].lower()
@@ -43,12 +58,26 @@ def trial(rng, dev, ref, idx, tref, seqs, kind, threads=16, max_reads=15000, log
         reads[j] = util.rand_seq(rng, len(reads[j]))
     b = fo.ReadBatch(reads)
     full = kind != "dense" and n < 8000
-    want = fo.map_reads(ref, idx, b, e=e, a=a, threads=threads, stages=(fo.STAGE_SEED | fo.STAGE_VERIFY | (fo.STAGE_ALIGN if full else 0)))
-    slot = int(rng.integers(0, 4))
-    dev.stage_reads(b.bases, b.off, slot=slot)
+    d = dict(e=e, a=a, L=L, n=n, reads=reads, batch=b, full=full, n_short=n_short, slot=int(rng.integers(0, 4)))
     if full:  # qualities and names for the device's SAM text
-        quals = rng.integers(33, 100, size=len(b.bases)).astype(np.uint8)
-        rnames = ["q%d_%s" % (j, "z" * int(rng.integers(0, 70))) for j in range(n)]
+        pad = len(b.bases) - int(b.off[-1])  # (the batch's bytes behind the last read have always been drawn for too)
+        d["quals"] = rng.integers(33, 100, size=n_drawn + pad).astype(np.uint8)[:len(b.bases)]
+        d["rnames"] = ["q%d_%s" % (j, "z" * int(rng.integers(0, 70))) for j in range(n)]
+        d["nowait"] = bool(rng.integers(0, 2))
+        d["host_quals"] = bool(rng.integers(0, 2))  # ... and with the qualities kept on the host
+        if d["host_quals"]:
+            d["nowait_host"] = bool(rng.integers(0, 2))
+    return d
+
+
+def trial(rng, dev, ref, idx, tref, seqs, kind, threads=16, max_reads=15000, log=print):
+    """One random batch through oracle and device; True if everything compared is identical."""
+    d = draw(rng, seqs, kind, max_reads)
+    e, a, L, n, b, full, slot = d["e"], d["a"], d["L"], d["n"], d["batch"], d["full"], d["slot"]
+    want = fo.map_reads(ref, idx, b, e=e, a=a, threads=threads, stages=(fo.STAGE_SEED | fo.STAGE_VERIFY | (fo.STAGE_ALIGN if full else 0)))
+    dev.stage_reads(b.bases, b.off, slot=slot)
+    if full:
+        quals, rnames = d["quals"], d["rnames"]
         dev.stage_text(quals, rnames, slot=slot)
     dev.map_staged(e=e, a=a, slot=slot)
     got = dev.fetch(slot=slot)
@@ -61,16 +90,25 @@ def trial(rng, dev, ref, idx, tref, seqs, kind, threads=16, max_reads=15000, log
               and np.array_equal(rec.nm, want.r_nm) and np.array_equal(rec.cigar_off, want.cig_off) and np.array_equal(rec.cigar, want.cig)
               and np.array_equal(rec.md_off, want.md_off) and np.array_equal(rec.md, want.md))
     if ok and full:  # the text rendered on the device against the host formatter on the same records
-        text, n_rec, n_assert, st = dev.fetch_sam(slot=slot, nowait=bool(rng.integers(0, 2)))
+        text, n_rec, n_assert, st = dev.fetch_sam(slot=slot, nowait=d["nowait"])
         host_text, host_assert = host.records_sam(tref, rnames, b.bases, b.off, quals, rec, threads=4, parts=True)
         ok = text.decode("latin-1") == host_text and n_assert == host_assert and n_rec == rec.n_records
-        if ok and rng.integers(0, 2):  # ... and with the qualities kept on the host (the device leaves their field open): the same bytes
+        if ok and d["host_quals"]:  # ... and with the qualities kept on the host (the device leaves their field open): the same bytes
             dev.stage_text(quals, rnames, slot=slot, quals_on_host=True)
-            text_h, n_rec_h, _, _ = dev.fetch_sam(slot=slot, nowait=bool(rng.integers(0, 2)), quals=quals, offsets=b.off)
+            text_h, n_rec_h, _, _ = dev.fetch_sam(slot=slot, nowait=d["nowait_host"], quals=quals, offsets=b.off)
             ok = text_h == text and n_rec_h == n_rec
-    log(kind, dict(e=e, a=a, L=L, n=n, packed=dev.stage_info(slot)[1], full=full, kernel=dev.seed_kernel(e=e, a=a)), "ok" if ok else "MISMATCH",
+    log(kind, dict(e=e, a=a, L=L, n=n, short=d["n_short"], packed=dev.stage_info(slot)[1], full=full, kernel=dev.seed_kernel(e=e, a=a)), "ok" if ok else "MISMATCH",
         [int(x) for x in got.stats], flush=True)
     return ok
+
+
+def draws(seed, kinds, trials_per_kind, threads=16, max_reads=15000):
+    """(kind, draw) of every trial that run(seed, kinds, trials_per_kind=..) makes while nothing mismatches — without a device."""
+    rng = np.random.default_rng(seed)
+    for kind in kinds:
+        seqs = reference(rng, kind, threads)
+        for _ in range(trials_per_kind[kind] if isinstance(trials_per_kind, dict) else trials_per_kind):
+            yield kind, draw(rng, seqs, kind, max_reads)
 
 
 def run(seed, kinds=KINDS, seconds=None, trials_per_kind=None, threads=16, max_reads=15000, log=print):

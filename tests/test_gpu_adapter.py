@@ -126,19 +126,15 @@ def test_mate_2_is_matched_against_its_own_adapter(small_dev):
 # ---- 3. as-if on the arrays ----
 
 @functools.lru_cache(maxsize=None)
-def _oracle_kept(no_empty=False):
+def _oracle_kept():
     c = m.readthrough_case()
     reads, quals, cl, a3 = m.kept(c["reads"], c["quals"], 0, 0, 0, c["adapter"])
-    if no_empty:  # (a read of length 0 in a ragged batch makes the dense-index kernels lose neighbours' candidates: DESIGN.md §4.6n)
-        keep = [i for i, r in enumerate(reads) if len(r) > 0]
-        c = dict(c, reads=[c["reads"][i] for i in keep], quals=[c["quals"][i] for i in keep], rnames=[c["rnames"][i] for i in keep])
-        reads, quals, cl, a3 = [reads[i] for i in keep], [quals[i] for i in keep], [cl[i] for i in keep], [a3[i] for i in keep]
     return c, reads, quals, cl, a3, fo.map_reads(c["ref"], c["idx"], fo.ReadBatch(reads), e=c["e"], threads=8)
 
 
 @pytest.mark.parametrize("dense", [False, True], ids=["sparse", "dense"])
 def test_arrays_are_those_of_the_kept_parts(dense):
-    c, kept_reads, kept_quals, cl, a3, want = _oracle_kept(dense)
+    c, kept_reads, kept_quals, cl, a3, want = _oracle_kept()
     assert len(set(len(r) for r in c["reads"])) == 1 and len(set(len(r) for r in kept_reads)) > 40
     dev = device_with_env(FEM_FORCE_DENSE=1) if dense else open_device(c["seqs"], c["names"], c["idx"])[0]
     try:

@@ -78,21 +78,14 @@ def test_clip_points_of_tiny_batches(small_dev, n):
 
 # ---- 2. as-if on the arrays ----
 
-@functools.lru_cache(maxsize=None)
-def _case(name, no_empty=False):
-    """A case of the model; no_empty: without the reads whose kept part is empty.  (A read of length 0 in a ragged batch makes the
-    dense-index kernels lose candidates of the reads beside it now and then, with trimming or without it, before this option as
-    after it: DESIGN.md §4.6n.  The sparse runs keep such reads.)"""
-    c = getattr(m, name)()
-    if no_empty:
-        keep = [i for i, (r, (a, b)) in enumerate(zip(c["reads"], _kept(c)[2])) if len(r) - a - b > 0]
-        c = dict(c, reads=[c["reads"][i] for i in keep], quals=[c["quals"][i] for i in keep], rnames=[c["rnames"][i] for i in keep])
-    return c
+def _case(name):
+    """A case of the model, on both index forms as it is: with the reads whose kept part is empty."""
+    return getattr(m, name)()
 
 
 @functools.lru_cache(maxsize=None)
-def _oracle_kept(name, no_empty=False):
-    c = _case(name, no_empty)
+def _oracle_kept(name):
+    c = _case(name)
     reads, quals, cl = _kept(c)
     return reads, quals, cl, fo.map_reads(c["ref"], c["idx"], fo.ReadBatch(reads), e=c["e"], threads=8)
 
@@ -100,9 +93,11 @@ def _oracle_kept(name, no_empty=False):
 @pytest.mark.parametrize("dense", [False, True], ids=["sparse", "dense"])
 @pytest.mark.parametrize("name", ["tails_case", "ragged_case"])
 def test_arrays_are_those_of_the_kept_parts(name, dense):
-    c = _case(name, dense)
-    kept_reads, kept_quals, cl, want = _oracle_kept(name, dense)
-    assert min(len(r) for r in kept_reads) == (0 if name == "ragged_case" and not dense else 28 if name == "ragged_case" else 80)
+    c = _case(name)
+    kept_reads, kept_quals, cl, want = _oracle_kept(name)
+    assert min(len(r) for r in kept_reads) == (0 if name == "ragged_case" else 80)
+    if name == "ragged_case":  # a read of no bases, and one the fixed trims use up: on the dense index too
+        assert len(c["reads"][7]) == 0 and len(c["reads"][11]) == 6 and len(kept_reads[7]) == len(kept_reads[11]) == 0
     assert (len(set(len(r) for r in c["reads"])) == 1) == (name == "tails_case")  # equal lengths through stage_reads, and ragged
     dev = device_with_env(FEM_FORCE_DENSE=1) if dense else open_device(c["seqs"], c["names"], c["idx"])[0]
     try:
