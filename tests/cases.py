@@ -1047,3 +1047,129 @@ def sort_cases():
             pos = rng.integers(0, ties, size=n).astype(np.uint64) * np.uint64(3 if ties < 100 else 1)
             cases.append(ed | direction | pos)
     return cases
+
+
+# ---- read pairs that a cut makes mappable (tests/fuzz_lines.py) ----
+
+CUT_PROFILES = ("good", "illumina", "walk", "plateau")  # the profiles of trim_model.profile_quals with printable bytes alone
+
+
+def long_tail(e):
+    """How many foreign bases on a read's 3' end keep the read as given from mapping at e edits.  A random base matches the
+    reference with probability 1/4, so a tail of 8 bases stays within e >= 6 edits in most reads and within e = 2 in four of a
+    thousand; 2e + 8 random bases have more than e mismatches in all but about 1e-4 of the reads at every e of 0 .. 7.  So
+    cut_pairs makes no tail of 8 .. 2e + 7 bases: every made tail of 8 bases or more has this many."""
+    return 2 * e + 8
+
+
+def _subst(rng, s, k, lo=0, hi=None):
+    """s with k substitutions at distinct places of [lo, hi)."""
+    s = bytearray(s)
+    hi = len(s) if hi is None else hi
+    if hi > lo and k > 0:
+        for p in rng.choice(hi - lo, min(k, hi - lo), replace=False):
+            s[lo + int(p)] = b"ACGT"[(b"ACGT".index(bytes([s[lo + int(p)]])) + 1 + int(rng.integers(0, 3))) % 4]
+    return bytes(s)
+
+
+def cut_pairs(rng, seqs, L, L2, e, flips=(0, 0), t5=0, t3=0, Q=0, A=None, A2=None, aO=5, aE=10, vO=None, vE=10, n=5):
+    """Pairs that map only once they are cut, as the device is given them (mate 1 of L bases, mate 2 of L2): upper-case A C G T.
+    Q > 0: n pairs with bad-quality tails (a reference segment, then 5 + 9k random bases under trim_model's "tail" profile).
+    A: n pairs with adapter read-through (a segment, then a prefix of A, for mate 2 of A2, with a mismatch or two within aE).
+    Those two kinds are pairs of an FR fragment of 150..500 bases, their flipped mates (flips: orient_model.FLIPS of the library)
+    reverse-complemented first, so that the kept parts pair under the library's orientation.  One more pair with an adapter has a
+    mate 1 that is all adapter behind its t5 bases: the match at p = 0, which keeps nothing.
+    A or vO: pairs of a fragment of f < max(L, L2) bases, mate 1 the fragment, mate 2 its reverse complement, each read through
+    into its adapter (where there is one) and random bases: the sequencer's geometry, whatever the library; f = max(L, L2) - 1 and
+    f = vO among them, the others with 37 + 12e <= f; no f at which a mate reads 8 .. long_tail(e) - 1 bases through.
+    vO: two pairs of such a fragment inside a tandem repeat, where several f match.
+    The bodies carry 0..e substitutions; a tail is short (below 8 bases) or has long_tail(e) bases at the least, and where the
+    read is long enough for it, it leaves 37 + 12e bases behind the fixed trims t5 and t3.
+    -> dict(r1, r2, q1, q2: the mates and their quality strings; tails: per pair the foreign bases at (mate 1's, mate 2's) 3' end;
+    seq: the sequence with the tandem repeat, to be added to the reference, or None)."""
+    from tests import trim_model as trm
+    main, lo, top, far = seqs[0], 37 + 12 * e, max(L, L2), long_tail(e)
+    out = dict(r1=[], r2=[], q1=[], q2=[], tails=[], seq=None)
+
+    def good(ln):
+        return trm.profile_quals(rng, CUT_PROFILES[int(rng.integers(0, len(CUT_PROFILES)))], ln, int(rng.integers(0, 4))).decode("latin-1")
+
+    def add(a, b, qa, qb, ta, tb):
+        assert len(a) == len(qa) == L and len(b) == len(qb) == L2
+        out["r1"].append(a), out["r2"].append(b), out["q1"].append(qa), out["q2"].append(qb), out["tails"].append((ta, tb))
+
+    def fr_pair():
+        frag = int(rng.integers(max(150, top), 501))
+        st = int(rng.integers(0, len(main) - frag))
+        f = main[st:st + frag] if rng.integers(0, 2) else util.revcomp(main[st:st + frag])
+        a, b = f[:L], util.revcomp(f[frag - L2:])
+        return (util.revcomp(a) if flips[0] else a), (util.revcomp(b) if flips[1] else b)
+
+    def tail_length(ln):
+        t = int(rng.integers(1, 8)) if rng.random() < 0.25 else far + int(rng.integers(0, 30))
+        room = ln - lo - t5 - t3  # (the longest tail whose read still maps)
+        return max(1, min(t, ln - 1, room if room >= far or t < 8 else t))
+
+    for _ in range(n if Q > 0 else 0):
+        mates, which = [], int(rng.integers(0, 3))  # the tail on mate 1, on mate 2, on both
+        for m, body in enumerate(fr_pair()):
+            ln = len(body)
+            if which != 1 - m:
+                k = 0 if rng.random() < 0.25 else -(-(far - 5) // 9) + int(rng.integers(0, 3))
+                t = min(ln, 5 + 9 * k)
+                body = _subst(rng, body[:ln - t], int(rng.integers(0, e + 1))) + util.rand_seq(rng, t)
+                mates.append((body, trm.profile_quals(rng, "tail", ln, k).decode("latin-1"), t))
+            else:
+                mates.append((body, good(ln), 0))
+        add(mates[0][0], mates[1][0], mates[0][1], mates[1][1], mates[0][2], mates[1][2])
+    for _ in range(n if A else 0):
+        mates, which = [], int(rng.integers(0, 3))
+        for m, body in enumerate(fr_pair()):
+            ln, ad = len(body), (A2 or A) if m else A
+            t = tail_length(ln) if which != 1 - m else 0
+            if t:
+                o = min(t, len(ad))
+                body = _subst(rng, body[:ln - t], int(rng.integers(0, e + 1))) + (ad + util.rand_seq(rng, ln))[:t]
+                body = _subst(rng, body, min(int(rng.integers(0, 3)), o * aE // 100), ln - t, ln - t + o)
+            mates.append((body, good(ln), t))
+        add(mates[0][0], mates[1][0], mates[0][1], mates[1][1], mates[0][2], mates[1][2])
+    if A:
+        add((util.rand_seq(rng, t5) + A + util.rand_seq(rng, L))[:L], fr_pair()[1], good(L), good(L2), 0, 0)
+
+    def through(fragment, k_body):
+        f = len(fragment)
+        fragment = _subst(rng, fragment, k_body)
+        a = (fragment + (A or b"") + util.rand_seq(rng, L))[:L]
+        b = (util.revcomp(fragment) + (A2 or A or b"") + util.rand_seq(rng, L2))[:L2]
+        o = min(f, L) - max(0, f - L2)
+        if vO is not None and o > 0:  # mate 1 against mate 2, within the mapping's e and the overlap's vE: in half of the pairs on it
+            most = o * vE // 100
+            k = most if most <= e - k_body and rng.integers(0, 2) else min(int(rng.integers(0, 3)), most, e - k_body)
+            a = _subst(rng, a, k, max(0, f - L2), min(f, L))
+        add(a, b, good(L), good(L2), max(0, L - f), max(0, L2 - f))
+
+    def clear(f):
+        """No mate of a fragment of f bases reads 8 .. long_tail(e) - 1 bases through it: such a read may or may not map as given."""
+        return not any(8 <= ln - f < far for ln in (L, L2))
+
+    if A or vO is not None:
+        fs = [top - 1] + ([vO] if vO is not None and 1 <= vO < top else [])
+        allowed = [f for f in range(lo, top) if clear(f)]
+        fs += [int(allowed[int(rng.integers(0, len(allowed)))]) for _ in range(n)] if allowed else []
+        fs += [top - t for t in (far, far + 1) if lo <= top - t]  # (the shortest read-through that keeps the read as given from mapping)
+        for f in fs:
+            if not clear(f):
+                continue
+            st = int(rng.integers(0, len(main) - f))
+            fragment = main[st:st + f] if rng.integers(0, 2) else util.revcomp(main[st:st + f])
+            through(fragment, int(rng.integers(0, e // 2 + 1)))
+    if vO is not None:
+        unit = util.rand_seq(rng, int(rng.choice([2, 3, 5, 7, 13])))
+        repeat = (unit * 300)[:600]
+        out["seq"] = util.rand_seq(rng, 300) + repeat + util.rand_seq(rng, 300)
+        allowed = [f for f in range(min(lo, top - 1), top) if clear(f)]  # (top - 1 is among them: a tail of one base, or none)
+        for _ in range(2):
+            f = int(allowed[int(rng.integers(0, len(allowed)))])
+            st = int(rng.integers(0, len(repeat) - f))
+            through(repeat[st:st + f], 0)
+    return out

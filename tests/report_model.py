@@ -64,9 +64,24 @@ def apply(text, strata=None, max_hits=None):
     return b"".join(out), dropped
 
 
-def single_end(res, seq_names, reads, names, quals, e=None, unmapped=True, strata=None, max_hits=None):
+def _with_reads(make, names):
+    """make(names) -> (text, dropped), with the read of every line: the text is made under the reads' numbers for names, which
+    only column 1 prints, and the names are put back -> (text, dropped, [the read of each line])."""
+    text, dropped = make(["%d" % r for r in range(len(names))])
+    out, line_reads = [], []
+    for l in text.split(b"\n"):
+        if l:
+            r, rest = l.split(b"\t", 1)
+            line_reads.append(int(r))
+            out.append(names[int(r)].encode("latin-1") + b"\t" + rest + b"\n")
+    return b"".join(out), dropped, line_reads
+
+
+def single_end(res, seq_names, reads, names, quals, e=None, unmapped=True, strata=None, max_hits=None, with_reads=False):
     """The filtered single-end text from the oracle's records -> (text, dropped).  e: with MAPQ at -e e; unmapped: with the
-    unmapped reads' lines."""
+    unmapped reads' lines; with_reads: -> (text, dropped, the read of each line), for names that repeat."""
+    if with_reads:
+        return _with_reads(lambda nm: single_end(res, seq_names, reads, nm, quals, e, unmapped, strata, max_hits), names)
     text = um.single_end(res, seq_names, reads, names, quals, e=e)
     if not unmapped:
         text = um.without_unmapped(text)[0]
@@ -74,8 +89,11 @@ def single_end(res, seq_names, reads, names, quals, e=None, unmapped=True, strat
 
 
 def paired(se, n_pairs, seq_names, reads, names, quals, min_insert=0, max_insert=500, res=None, rescued=(), e=None, unmapped=True,
-           strata=None, max_hits=None):
-    """The filtered paired text -> (text, dropped); the arguments of unmapped_model.paired, and `unmapped` as above."""
+           strata=None, max_hits=None, with_reads=False):
+    """The filtered paired text -> (text, dropped); the arguments of unmapped_model.paired, and `unmapped` and `with_reads` as above."""
+    if with_reads:
+        return _with_reads(lambda nm: paired(se, n_pairs, seq_names, reads, nm, quals, min_insert, max_insert, res, rescued, e, unmapped,
+                                             strata, max_hits), names)
     text = um.paired(se, n_pairs, seq_names, reads, names, quals, min_insert, max_insert, res=res, rescued=rescued, e=e)
     if not unmapped:
         text = um.without_unmapped(text, True)[0]

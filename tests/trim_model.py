@@ -98,27 +98,27 @@ def ms_score(qual):
     return sum(b - 33 for b in _bytes(qual) if b - 33 >= MS_MIN_QUAL)
 
 
-def apply(text, reads, quals, cl, rnames, paired=False, sam_seq=False):
+def apply(text, reads, quals, cl, rnames, paired=False, sam_seq=False, line_reads=None):
     """The SAM text (bytes, no header) of the trimmed batch from the text of the batch of the kept parts.  reads, quals: the whole
     reads; cl: their clips; rnames: the batch's read names, unique (pairs: the names of the n / 2 pairs; read i and n / 2 + i are
-    the mates, told apart by 0x40 / 0x80)."""
+    the mates, told apart by 0x40 / 0x80).  line_reads: the read of every line, from the stage that made the lines
+    (report_model, with_reads); the names may then repeat and are not looked at."""
     n = len(reads)
-    index = {_bytes(nm): i for i, nm in enumerate(rnames)}
-    assert len(index) == len(rnames)
     half = n // 2
-
-    def read_of(f):
-        return index[f[0]] + (half if paired and int(f[1]) & 0x80 else 0)
-
     lines = [l.split(b"\t") for l in text.split(b"\n") if l]
+    if line_reads is None:
+        index = {_bytes(nm): i for i, nm in enumerate(rnames)}
+        assert len(index) == len(rnames)
+        line_reads = [index[f[0]] + (half if paired and int(f[1]) & 0x80 else 0) for f in lines]
+    assert len(line_reads) == len(lines)
     primary_rev = {}  # read -> its primary line's strand, for the MC of the other mate's lines
-    for f in lines:
+    for f, r in zip(lines, line_reads):
         flag = int(f[1])
         if not flag & 0x104:
-            primary_rev.setdefault(read_of(f), bool(flag & 16))
+            primary_rev.setdefault(r, bool(flag & 16))
     out = []
-    for f in lines:
-        flag, r = int(f[1]), read_of(f)
+    for f, r in zip(lines, line_reads):
+        flag = int(f[1])
         c5, c3 = cl[r]
         rev = bool(flag & 16)
         f[5] = clip_cigar(f[5], c5, c3, rev)
