@@ -176,7 +176,7 @@ struct Slot {
   uint32_t part_begin[kMaxParts + 1] = {0, 0, 0, 0, 0};
   Event ev_part[kMaxParts], ev_sel[kMaxParts];
   Event ev_zeroed;
-  Event ev_results, ev_home;  // the batch's results are final on the device / have arrived on the host
+  Event ev_results;  // the batch's results are final on the device
   // outputs on the device
   // (arrays that share a capacity are allocated together, femb::alloc_all: all of them hold it or none holds anything)
   Buf<uint64_t> d_cand;
@@ -185,9 +185,9 @@ struct Slot {
   Buf<int16_t> d_end;
   uint32_t cand_cap = 0;  // published once all four exist
   Buf<uint32_t> d_begin, d_count, d_nmap;  // 2, 2 and 1 entries per read
-  // counters: ctr[4] (u32) | arena_ctr[2] (u64) | stats[4] (u64)
+  // counters, flags and work cursors (CtlBlock)
   Buf<uint8_t> d_ctl;
-  PinBuf<uint8_t> h_ctl;  // pinned mirror
+  PinBuf<uint8_t> h_ctl;  // pinned mirror of its head
   Buf<uint64_t> d_arena;
   uint64_t arena_cap = 0;
   Buf<uint32_t> d_slow;  // reads the fast seed kernel leaves to the generic one
@@ -249,14 +249,31 @@ struct Slot {
   const uint64_t *map_off() const { return view.trimmed ? view.d_off.get() : d_off.get(); }
 };
 
-// ctr[4] | arena_ctr[2] | stats[4] | pack cursor[2]
-constexpr size_t kCtlPackCursor = 4 * sizeof(uint32_t) + 2 * sizeof(uint64_t) + 4 * sizeof(uint64_t);  // pack_results_kernel: packed candidates, big[] entries
-constexpr size_t kCtlBytes = kCtlPackCursor + 2 * sizeof(uint32_t);
+// A slot's control block as it lies in d_ctl (kCtlAlloc bytes, zeroed whole in front of every launch of a batch); its first
+// kCtlBytes go home into h_ctl behind the batch's kernels.  The kernels get plain pointers to its members.
+struct CtlBlock {
+  uint32_t ctr[4];
+  unsigned long long arena_ctr[2];
+  unsigned long long stats[4];
+  uint32_t pack_cursor[2];  // pack_results_kernel: packed candidates, big[] entries
+  // ... and, in cache lines of their own behind them, the work cursors: a pair per part of a batch mapped in parts
+  struct Work {
+    alignas(64) uint32_t select;  // seed_select_kernel; part 0's is seed_fast_kernel's too
+    alignas(64) uint32_t join;    // seed_join_kernel
+  } work[kMaxParts];
+};
+constexpr size_t kCtlPackCursor = offsetof(CtlBlock, pack_cursor);
+constexpr size_t kCtlBytes = kCtlPackCursor + sizeof(CtlBlock::pack_cursor);
 constexpr uint32_t kBigCap = 4096;  // strands with 255 candidates and more that a packed result lists (beyond: fetch the plain form)
-// ... and, in a cache line of its own behind them, the work cursor of seed_fast_kernel
-constexpr size_t kCtlWorkCursor = 128, kCtlWorkCursor2 = 192, kCtlPartStride = 128, kCtlAlloc = 1024;  // (seed_select_kernel / seed_join_kernel; one pair per part)
+constexpr size_t kCtlWorkCursor = offsetof(CtlBlock, work), kCtlWorkCursor2 = kCtlWorkCursor + offsetof(CtlBlock::Work, join);
+constexpr size_t kCtlPartStride = sizeof(CtlBlock::Work), kCtlAlloc = 1024;
 static_assert(kCtlWorkCursor2 + (kMaxParts - 1) * kCtlPartStride + 64 <= kCtlAlloc, "control block layout");
 static_assert(kCtlBytes <= kCtlWorkCursor, "control block layout");
+static_assert(offsetof(CtlBlock, arena_ctr) == 16 && offsetof(CtlBlock, stats) == 32 && kCtlPackCursor == 64 && kCtlBytes == 72, "control block layout");
+static_assert(kCtlWorkCursor == 128 && kCtlWorkCursor2 == 192 && kCtlPartStride == 128 && sizeof(CtlBlock) <= kCtlAlloc, "control block layout");
+// (the device's block: for the addresses of its members only, the host never reads through it; the mirror: its first kCtlBytes)
+CtlBlock *ctl_of(const Slot &s) { return (CtlBlock *)s.d_ctl.get(); }
+const CtlBlock *ctl_home(const Slot &s) { return (const CtlBlock *)s.h_ctl.get(); }
 
 }  // namespace
 
@@ -341,8 +358,6 @@ struct fem_dev {
   Buf<uint64_t> d_occ;
   uint64_t n_occ = 0;
   int32_t k = 0, step = 0;
-  uint64_t fast_occ_key = ~0ull;  // seed_fast_kernel residency, cached per (R, form, LDS bytes)
-  int fast_occ_blocks = 0;
   Buf<uint32_t> d_summary;  // bucket summaries (femk::SeedParams::summary), built for sparse indexes only
   // dense indexes: occurrence table in 32-bit global coordinates + its sequence tables (fem_seed_dense.hip.h)
   Buf<uint32_t> d_occ32, d_goff, d_blkseq;
@@ -356,8 +371,6 @@ struct fem_dev {
   Buf<uint32_t> d_bank_lo;  // [n_banks - 1][n_buckets]: where each further bank's part of a bucket's list starts
   uint64_t bank_limit = 0;        // FEM_TEST_BANK_BASES: coordinates per bank (tests: banks on small references); 0 = kDenseLimit
   uint32_t bank_seqs = 0;         // FEM_TEST_BANK_SEQS: sequences per bank (tests); 0 = kDenseMaxSeq
-  int select_occ_blocks = 0, join_occ_blocks = 0;
-  uint64_t select_occ_key = ~0ull, join_occ_key = ~0ull;
   // reference
   // bit q of the codes, one bit per base (verify_kernel's windows); [3]: the uploaded character is not one of "ACGTN"
   Buf<uint8_t> d_planes;  // femk::plane_window
@@ -380,8 +393,9 @@ struct fem_dev {
   } coverage;
   Slot slot[kSlots];
   bool timing = false;
-  int verify_blocks_per_cu = 0;  // resident 256-thread blocks of verify_kernel per CU (queried once)
-  int verify_packed_blocks_per_cu = 0;  // ... and of verify_kernel_packed
+  // blocks of a kernel that a CU holds at a time, as the runtime answered once per (kernel, block threads, LDS bytes): resident_blocks
+  struct Residency { const void *kernel; uint32_t threads, lds; int blocks; };
+  std::vector<Residency> residency;
   double t_ms[kTimedKernels] = {};
   uint64_t t_n[kTimedKernels] = {};
   bool force_generic = false;  // FEM_FORCE_GENERIC=1: skip the fast seed kernel (test hook)
@@ -594,6 +608,28 @@ femk::SeedLayout make_layout_join(const fem_params &p, bool banked, bool padded 
   return l;
 }
 
+// The handle has the 32-bit occurrence table and the 11-mer frequencies of a dense index (refresh_dense)
+bool has_dense_tables(const fem_dev *h) { return h->d_occ32 && h->d_freq11; }
+
+// Which seed kernels map a batch of given parameters on this handle: seed_filter_kernel over every read (generic), or, in
+// front of it, seed_fast_kernel in one of its two forms, or seed_select_kernel and seed_join_kernel on one of the three forms
+// of a dense index's table.  launch_batch, fem_dev_seed_kernel and fem_dev_reserve_batch all follow this one decision.
+struct SeedPath {
+  enum Kind { kGeneric, kFastLean, kFastHash, kDenseCompact, kDenseBanked, kDenseStrided } kind;
+  int R;  // e + 1 + a, the seeds selected per phase group
+  bool dense() const { return kind >= kDenseCompact; }
+  bool fast() const { return kind == kFastLean || kind == kFastHash; }
+  bool banked() const { return kind == kDenseBanked; }
+};
+SeedPath seed_path(const fem_dev *h, const fem_params &p) {
+  const int R = p.e + 1 + p.a;
+  // the fast and the dense kernels are compiled for one seed length and step and for R up to kMaxR
+  if (!(p.k == femk::kK && p.step == femk::kStep && R >= 1 && R <= femk::kMaxR && !h->force_generic)) return {SeedPath::kGeneric, R};
+  if (has_dense_tables(h)) return {h->n_banks > 1 ? SeedPath::kDenseBanked : h->list_shift ? SeedPath::kDenseStrided : SeedPath::kDenseCompact, R};
+  // long occurrence lists: the hash-join form of the fast kernel; short ones: lists in lanes only
+  return {h->force_hash || (double)h->n_occ > (double)h->n_lookup ? SeedPath::kFastHash : SeedPath::kFastLean, R};
+}
+
 typedef void (*SeedKernel)(femk::SeedParams);
 template <size_t... I>
 SeedKernel select_kernel_of(int R, bool banked, bool packed, std::index_sequence<I...>) {
@@ -612,8 +648,9 @@ SeedKernel fast_kernel_of(int R, bool hash, std::index_sequence<I...>) {
 SeedKernel select_kernel(int R, bool banked, bool packed) { return select_kernel_of(R, banked, packed, std::make_index_sequence<femk::kMaxR>{}); }
 // (`hash`: the hash-join form for long occurrence lists; otherwise the lean one, lists in lanes only)
 SeedKernel fast_kernel(int R, bool hash) { return fast_kernel_of(R, hash, std::make_index_sequence<femk::kMaxR>{}); }
-// which = 0: the compact table, 1: references in banks (compact, cut at bank_lo), 2: the strided table with its pads
-SeedKernel join_kernel(int R, int which) {
+// (the dense kinds in SeedPath's order: the compact table, references in banks (compact, cut at bank_lo), the strided table with its pads)
+SeedKernel join_kernel(SeedPath path) {
+  const int R = path.R, which = path.kind - SeedPath::kDenseCompact;
   static const SeedKernel k[3][femk::kMaxR] = {
       {femk::seed_join_kernel_r1, femk::seed_join_kernel_r2, femk::seed_join_kernel_r3, femk::seed_join_kernel_r4, femk::seed_join_kernel_r5,
        femk::seed_join_kernel_r6, femk::seed_join_kernel_r7, femk::seed_join_kernel_r8, femk::seed_join_kernel_r9, femk::seed_join_kernel_r10},
@@ -626,32 +663,30 @@ SeedKernel join_kernel(int R, int which) {
   return k[which][std::min(std::max(R, 1), femk::kMaxR) - 1];
 }
 
-// blocks of `kernel` one CU holds at a time (registers and LDS both count); 0 = unknown
-int blocks_per_cu(const void *kernel, int block, uint32_t lds) {
-  int nb = 0;
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, block, lds) == hipSuccess ? nb : 0;
+// Blocks of `kernel` one CU holds at a time, `threads` to a block with `lds` bytes (registers and LDS both count): the runtime
+// is asked once per such triple and handle (under the handle's lock, as every launch).  Where it does not say: what the LDS
+// alone allows, and four blocks of a kernel without LDS (the verification's 256-thread blocks).
+uint64_t resident_blocks(fem_dev *h, const void *kernel, uint32_t threads, uint32_t lds) {
+  auto at = std::find_if(h->residency.begin(), h->residency.end(), [&](const fem_dev::Residency &r) { return r.kernel == kernel && r.threads == threads && r.lds == lds; });
+  if (at == h->residency.end()) {
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, (int)threads, lds) != hipSuccess) nb = 0;
+    at = h->residency.insert(at, {kernel, threads, lds, nb});
+  }
+  return at->blocks > 0 ? (uint64_t)at->blocks : lds ? std::max<uint64_t>(1, 160u * 1024u / lds) : 4;
 }
-// vector registers per lane of seed_join_kernel<R> / seed_select_kernel<R>
+// vector registers per lane of the path's seed_join_kernel<R> / seed_select_kernel<R>
 // (handles of several GPUs launch from their own threads: the cache is atomic; every thread would store the same value)
-uint32_t kernel_regs(int R, bool join, int which = 0, bool packed = false) {
+uint32_t kernel_regs(SeedPath path, bool join, bool packed = false) {
   static std::atomic<uint32_t> cache[3][3][femk::kMaxR + 1] = {};
-  std::atomic<uint32_t> &slot = cache[which][join ? 1 : packed ? 2 : 0][std::min(std::max(R, 1), femk::kMaxR)];
+  std::atomic<uint32_t> &slot = cache[join ? path.kind - SeedPath::kDenseCompact : path.banked()][join ? 1 : packed ? 2 : 0][std::min(std::max(path.R, 1), femk::kMaxR)];
   uint32_t c = slot.load(std::memory_order_relaxed);
   if (c) return c;
   hipFuncAttributes a{};
-  const void *f = join ? (const void *)join_kernel(R, which) : (const void *)select_kernel(R, which == 1, packed);
+  const void *f = join ? (const void *)join_kernel(path) : (const void *)select_kernel(path.R, path.banked(), packed);
   c = hipFuncGetAttributes(&a, f) == hipSuccess && a.numRegs > 0 ? (uint32_t)a.numRegs : 128u;
   slot.store(c, std::memory_order_relaxed);
   return c;
-}
-void launch_select(int R, bool banked, dim3 grid, dim3 block, uint32_t lds, hipStream_t st, const femk::SeedParams &sp) {
-  hipLaunchKernelGGL(select_kernel(R, banked, sp.packed != nullptr), grid, block, lds, st, sp);
-}
-void launch_join(int R, int which, dim3 grid, dim3 block, uint32_t lds, hipStream_t st, const femk::SeedParams &sp) {
-  hipLaunchKernelGGL(join_kernel(R, which), grid, block, lds, st, sp);
-}
-void launch_fast(int R, bool hash, dim3 grid, dim3 block, uint32_t lds, hipStream_t st, const femk::SeedParams &sp) {
-  hipLaunchKernelGGL(fast_kernel(R, hash), grid, block, lds, st, sp);
 }
 
 // (timeline only) events around a copy on `st`
@@ -752,22 +787,15 @@ bool device_idle(fem_dev *h) {
   return (!h->have_kernels_done || hipEventQuery(h->ev_kernels_done) == hipSuccess) &&
          (!h->have_select_done || hipEventQuery(h->ev_select_done) == hipSuccess);
 }
-constexpr uint64_t kPartMinReads = 1u << 16;  // a part is at least this many reads
-
-// The stream a slot's results go home on: its own.  (Tried: one stream for every slot's results behind an event of the slot's
-// stream — consistent 0.63 ms per 32 MB where a slot's own stream takes 0.6 to 1.5 beside the next batch's H2D copy, but the
-// calls that enqueue the copies then kept the host until the batch's kernels were through: 326 -> 284 Mreads/s.  Ten streams
-// timed one by one all copy at 54 GB/s: the slow copies are the link shared with the other direction, not a slow engine.)
-hipStream_t d2h_begin(fem_dev *h, Slot &s) {
-  (void)h;
-  return s.stream;
-}
-// ... and the slot's stream (what fem_dev_sync waits for) continues behind them.
-int d2h_end(fem_dev *h, Slot &s, hipStream_t st) {
-  if (st == s.stream) return FEM_OK;
-  HIP_TRY(h, hipEventRecord(s.ev_home, st));
-  HIP_TRY(h, hipStreamWaitEvent(s.stream, s.ev_home, 0));
-  return FEM_OK;
+// The parts of a batch of n reads, reads [part_begin[q], part_begin[q + 1]): more than one only where the batch meets an idle
+// device (and `allowed`: what the caller knows does not speak against it) — a part is at least kPartMinReads reads and begins
+// at a multiple of 64.  The copy (enqueue_packed) and the kernels (plan_batch) are split by this one rule.
+constexpr uint64_t kPartMinReads = 1u << 16;
+int plan_parts(fem_dev *h, uint64_t n, bool allowed, uint32_t part_begin[kMaxParts + 1]) {
+  int parts = 1;
+  if (allowed && !h->no_parts && !h->no_overlap && n >= 2 * kPartMinReads && device_idle(h)) parts = (int)std::min<uint64_t>((uint64_t)h->max_parts, n / kPartMinReads);
+  for (int q = 0; q <= parts; ++q) part_begin[q] = q == parts ? (uint32_t)n : (uint32_t)((n * q / parts) & ~63ull);
+  return parts;
 }
 
 // `launch` on `st`, between two events when the handle times its kernels (id: fem_dev_kernel_time; counts = false: a further
@@ -803,305 +831,280 @@ int enqueue_pack(fem_dev *h, Slot &s, bool kernel, bool send_home) {
   if (kernel) {
     femk::PackParams pp{};
     pp.cand_begin = s.d_begin, pp.cand_count = s.d_count, pp.cand = s.d_cand, pp.ed = s.d_ed, pp.end = s.d_end;
-    pp.ctr = (const uint32_t *)s.d_ctl.get(), pp.n_strands = (uint32_t)n2;
+    pp.ctr = ctl_of(s)->ctr, pp.n_strands = (uint32_t)n2;
     pp.count8 = s.d_count8, pp.seg_begin = s.d_seg, pp.pcand = s.d_pcand, pp.ped = s.d_ped, pp.pend = s.d_pend, pp.pcap = (uint32_t)s.d_pcand.size();
-    pp.cursor = (uint32_t *)(s.d_ctl + kCtlPackCursor), pp.big = s.d_big, pp.big_cap = kBigCap;
+    pp.cursor = ctl_of(s)->pack_cursor, pp.big = s.d_big, pp.big_cap = kBigCap;
     const uint32_t grid = (uint32_t)std::max<size_t>(1, (n_seg + femk::kPackSegs - 1) / femk::kPackSegs);  // (a block per sixteen segments)
     // (kernel id 6: pack_results_kernel)
     if ((rc = timed_launch(h, s, 6, s.stream, true, [&] { hipLaunchKernelGGL(femk::pack_results_kernel, dim3(grid), dim3(256), 0, s.stream, pp); }))) return rc;
     s.packed_enqueued = true;
   }
-  if (send_home) {
-    hipStream_t st = d2h_begin(h, s);
-    {
-      Span span(h, s, 21, st);
-      HIP_TRY(h, hipMemcpyAsync(s.h_count8, s.d_count8, n2, hipMemcpyDeviceToHost, st));
-      HIP_TRY(h, hipMemcpyAsync(s.h_seg, s.d_seg, n_seg * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-      s.packed_per_read_home = true;
-      const size_t guess = std::min<size_t>({(size_t)(s.last_n_packed + s.last_n_packed / 32 + 1024), s.h_pcand.size(), s.d_pcand.size()});
-      if (s.last_n_packed && s.h_pcand && guess) {
-        HIP_TRY(h, hipMemcpyAsync(s.h_pcand, s.d_pcand, guess * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(h, hipMemcpyAsync(s.h_ped, s.d_ped, guess * sizeof(uint8_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(h, hipMemcpyAsync(s.h_pend, s.d_pend, guess * sizeof(int16_t), hipMemcpyDeviceToHost, st));
-        s.packed_home = guess;
-      }
+  if (send_home) {  // (on the slot's own stream: see enqueue_prefetch)
+    Span span(h, s, 21, s.stream);
+    HIP_TRY(h, hipMemcpyAsync(s.h_count8, s.d_count8, n2, hipMemcpyDeviceToHost, s.stream));
+    HIP_TRY(h, hipMemcpyAsync(s.h_seg, s.d_seg, n_seg * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream));
+    s.packed_per_read_home = true;
+    const size_t guess = std::min<size_t>({(size_t)(s.last_n_packed + s.last_n_packed / 32 + 1024), s.h_pcand.size(), s.d_pcand.size()});
+    if (s.last_n_packed && s.h_pcand && guess) {
+      HIP_TRY(h, hipMemcpyAsync(s.h_pcand, s.d_pcand, guess * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream));
+      HIP_TRY(h, hipMemcpyAsync(s.h_ped, s.d_ped, guess * sizeof(uint8_t), hipMemcpyDeviceToHost, s.stream));
+      HIP_TRY(h, hipMemcpyAsync(s.h_pend, s.d_pend, guess * sizeof(int16_t), hipMemcpyDeviceToHost, s.stream));
+      s.packed_home = guess;
     }
-    if ((rc = d2h_end(h, s, st))) return rc;
   }
   return FEM_OK;
 }
 
 int ensure_chars(fem_dev *h, Slot &s);
 
-// Enqueue the two kernels of one batch on the slot's stream (asynchronous).
-int launch_batch(fem_dev *h, Slot &s) {
-  const fem_params &p = s.params;
-  uint32_t *d_ctr = (uint32_t *)s.d_ctl.get();
-  unsigned long long *d_arena_ctr = (unsigned long long *)(s.d_ctl + 4 * sizeof(uint32_t));
-  unsigned long long *d_stats = (unsigned long long *)(s.d_ctl + 4 * sizeof(uint32_t) + 2 * sizeof(uint64_t));
-  // A batch that meets an IDLE device (the start of a job) is mapped in parts on a dense index — see below; its counters are
-  // then zeroed on the side stream, ahead of the slot's stream, which may still be busy with the rest of the batch's copy.
-  int parts = 1;
-  uint32_t part_begin[kMaxParts + 1] = {0, 0, 0, 0, 0};
-  const bool copied_in_parts = s.parts > 1;
-  {
-    const int R_ = p.e + 1 + p.a;
-    const bool dense_overlap = !h->force_generic && p.k == femk::kK && p.step == femk::kStep && R_ >= 1 && R_ <= femk::kMaxR && h->d_occ32 &&
-                               h->d_freq11 && !h->no_overlap;
-    if (dense_overlap && !h->no_parts && s.n_reads >= 2 * kPartMinReads && (copied_in_parts || device_idle(h))) {
-      parts = copied_in_parts ? s.parts : (int)std::min<uint64_t>((uint64_t)h->max_parts, s.n_reads / kPartMinReads);
-      for (int q = 0; q <= parts; ++q)
-        part_begin[q] = copied_in_parts ? s.part_begin[q] : q == parts ? (uint32_t)s.n_reads : (uint32_t)((s.n_reads * q / parts) & ~63ull);
-    }
-    s.parts = 1;  // (consumed: the slot's batch mapped again starts from the device's state then)
+// One kernel of a batch as it will be launched (plan_batch): a wave's LDS carve-up, the waves of a block — four at most, as many
+// as `lds_budget` bytes hold of the layout —, the block's dynamic LDS (`extra`: what it has besides the waves' regions) and the
+// grid: as many blocks as the reads want at `reads_per_wave` a wave, at most `max_grid`, what the device holds at a time (the
+// planner's).  A grid-stride kernel (no layout, 256 threads) gets exactly max_grid.
+struct KernelShape {
+  femk::SeedLayout lay{};
+  uint32_t wpb = 4, lds = 0, reads_per_block = 0;
+  uint64_t max_grid = 1;
+  KernelShape() = default;
+  KernelShape(const femk::SeedLayout &l, uint32_t lds_budget, uint32_t reads_per_wave, uint32_t extra = 0)
+      : lay(l), wpb(std::min<uint32_t>(4u, std::max<uint32_t>(1u, lds_budget / l.wave_bytes))), lds(wpb * l.wave_bytes + extra), reads_per_block(reads_per_wave * wpb) {}
+  dim3 block() const { return dim3(64u * wpb); }
+  dim3 grid(uint64_t n_reads) const {
+    const uint64_t wanted = reads_per_block ? (n_reads + reads_per_block - 1) / reads_per_block : max_grid;
+    return dim3((uint32_t)std::max<uint64_t>(1, std::min(wanted, max_grid)));
   }
-  if (parts > 1) {
-    if (h->have_select_done) HIP_TRY(h, hipStreamWaitEvent(h->side_stream, h->ev_select_done, 0));
-    HIP_TRY(h, hipMemsetAsync(s.d_ctl, 0, kCtlAlloc, h->side_stream));
-  } else {
-    HIP_TRY(h, hipMemsetAsync(s.d_ctl, 0, kCtlAlloc, s.stream));
-  }
+};
+typedef void (*VerifyKernel)(femk::VerifyParams);
+VerifyKernel verify_kernel_of(bool packed) { return packed ? femk::verify_kernel_packed : femk::verify_kernel; }
 
-  const int R_all = p.e + 1 + p.a;
-  const bool dense_kernels = !h->force_generic && p.k == femk::kK && p.step == femk::kStep && R_all >= 1 && R_all <= femk::kMaxR && h->d_occ32 && h->d_freq11;
+struct BatchPlan {
+  SeedPath path{};
+  int parts = 1;                  // > 1: mapped in parts, reads [part_begin[q], part_begin[q + 1]) (Slot::parts)
+  uint32_t part_begin[kMaxParts + 1] = {};
+  bool copied_in_parts = false;   // ... the parts it was copied in (enqueue_packed): ev_part[q] says that part q has arrived
+  bool overlap = false;           // dense path: the selection runs beside the previous batch's join (fem_dev::ev_select_done)
+  bool need_chars = false;        // a kernel reads the whole batch's characters (ensure_chars)
+  bool select_packed = false, verify_packed = false;  // the seed kernels / the verification read the batch's 2-bit codes
+  KernelShape select, join, fast, generic, verify;    // (select and join or fast as the path has them; the other two always)
+};
+
+// What the slot's staged batch will launch under s.params: every decision, every query of the runtime and every refusal.
+// Queues nothing and changes nothing in the slot.
+int plan_batch(fem_dev *h, const Slot &s, BatchPlan &pl) {
+  const fem_params &p = s.params;
+  const SeedPath path = pl.path = seed_path(h, p);
+  pl.overlap = path.dense() && !h->no_overlap;
+  // A batch that meets an IDLE device (the start of a job) is mapped in parts on a dense index: those of its copy where it
+  // was copied in parts (enqueue_packed), else (an exception kept the copy whole, or the batch is mapped again) cut here.
+  pl.copied_in_parts = s.parts > 1 && path.dense();
+  pl.parts = pl.copied_in_parts ? s.parts : plan_parts(h, s.n_reads, path.dense(), pl.part_begin);
+  if (pl.copied_in_parts) std::copy(s.part_begin, s.part_begin + kMaxParts + 1, pl.part_begin);
   // Who reads a whole batch's characters gets them made first (ensure_chars): seed_fast_kernel, the generic kernel over all
   // reads, verify_kernel.  The dense kernels read a packed batch's codes, and characters of its marked reads only.
-  if (s.n_reads && (!dense_kernels || h->verify_chars)) {
-    int rc = ensure_chars(h, s);
-    if (rc) return rc;
+  pl.need_chars = s.n_reads && (!path.dense() || h->verify_chars);
+  pl.select_packed = s.sent_packed && !h->select_chars && path.dense();
+  // A batch that came packed (equal-length reads, codes in d_packed_alloc) is verified straight from its 2-bit codes; every
+  // other one — mixed lengths, FEM_NO_PACK, the zero-copy character forms — from its characters.
+  pl.verify_packed = s.sent_packed && !h->verify_chars;
+  const uint32_t max_len = std::max<uint32_t>(s.max_len, (uint32_t)p.k);
+  pl.generic = KernelShape(make_layout(p, max_len), 64u * 1024u, 1);
+  if (pl.generic.lay.wave_bytes > 64u * 1024u) return fail(h, FEM_ERR_UNSUPPORTED, "read too long for the device path");
+  const uint32_t generic_waves_per_cu = std::min<uint32_t>(32u, (160u * 1024u / pl.generic.lds) * pl.generic.wpb);
+  pl.generic.max_grid = (uint64_t)h->n_cu * std::max<uint32_t>(1u, generic_waves_per_cu / pl.generic.wpb) * 4;
+  if (s.n_reads == 0) return FEM_OK;
+  // grid-stride kernel: exactly the blocks that are resident together, or the ones that start late set the makespan
+  pl.verify.max_grid = (uint64_t)h->n_cu * resident_blocks(h, (const void *)verify_kernel_of(pl.verify_packed), 256, 0);
+  if (path.dense()) {
+    pl.select = KernelShape(make_layout_select(p, max_len, pl.select_packed), 64u * 1024u, femk::kReadBlock);
+    if (pl.select.lay.wave_bytes > 64u * 1024u) return fail(h, FEM_ERR_UNSUPPORTED, "read too long for the device path");
+    pl.join = KernelShape(make_layout_join(p, path.banked(), path.kind == SeedPath::kDenseStrided), 60u * 1024u, femk::kReadBlock, 64u * 8u);
+    pl.join.lay.picked = pl.join.wpb * pl.join.lay.wave_bytes;  // the block's sequence table, behind the waves' regions
+    const KernelShape &ks = pl.select, &kj = pl.join;
+    // (3.3 ms per 2.5 M reads of C3 with one block per CU as with five: sectors per second, not waves)
+    const uint64_t per_cu_s = pl.overlap ? 1 : resident_blocks(h, (const void *)select_kernel(path.R, path.banked(), pl.select_packed), 64u * ks.wpb, ks.lds);
+    uint64_t per_cu_j = resident_blocks(h, (const void *)join_kernel(path), 64u * kj.wpb, kj.lds);
+    if (pl.overlap) {
+      // leave one block of the next batch's seed_select_kernel room on every CU: registers (512 per lane and SIMD,
+      // handed out in eights), LDS (160 KB) and wave slots (8 per SIMD) of both kernels together
+      const uint32_t vj = (kernel_regs(path, true) + 7u) & ~7u, vs = (kernel_regs(path, false, pl.select_packed) + 7u) & ~7u;
+      const uint32_t wj = 64u * kj.wpb / 256u ? 64u * kj.wpb / 256u : 1u, ws = 64u * ks.wpb / 256u ? 64u * ks.wpb / 256u : 1u;  // waves per SIMD and block
+      const uint32_t lj = (kj.lds + 511u) & ~511u, ls = (ks.lds + 511u) & ~511u;  // (LDS is handed out in pieces of 512 bytes)
+      while (per_cu_j > 1 && (per_cu_j * wj * vj + ws * vs > 512u || per_cu_j * lj + ls > 160u * 1024u || per_cu_j * wj + ws > 8u)) --per_cu_j;
+    }
+    pl.select.max_grid = (uint64_t)h->n_cu * per_cu_s, pl.join.max_grid = (uint64_t)h->n_cu * per_cu_j;
+  } else if (path.fast()) {
+    const bool hash = path.kind == SeedPath::kFastHash;
+    pl.fast = KernelShape(make_layout_fast(p, max_len, hash), 64u * 1024u, femk::kReadBlock);
+    // The kernel's waves pull blocks of reads from a cursor: the grid is exactly what is resident at a time
+    // (registers included).  (With a fixed stride per wave the same grid took 6.9 ms against 6.2 at six times as
+    // many waves: the CUs do not all run at the same pace.  Every wave pads its last chunk of candidate slots, so
+    // extra waves cost the verify kernel lanes.)  FEM_GRID_MULT overrides the multiple (measurement only).
+    static const uint64_t mult = testing_switch("FEM_TESTING") && getenv("FEM_GRID_MULT") ? (uint64_t)std::max(1, atoi(getenv("FEM_GRID_MULT"))) : 1;
+    pl.fast.max_grid = (uint64_t)h->n_cu * resident_blocks(h, (const void *)fast_kernel(path.R, hash), 64u * pl.fast.wpb, pl.fast.lds) * mult;
   }
+  return FEM_OK;
+}
+
+// What every seed kernel of the batch takes, with the generic kernel's layout (the dense kernels' tables: enqueue_dense)
+femk::SeedParams seed_params(const fem_dev *h, const Slot &s, const BatchPlan &pl) {
+  const fem_params &p = s.params;
+  CtlBlock *ctl = ctl_of(s);
   femk::SeedParams sp{};
-  s.select_packed = false;
-  if (s.sent_packed && !h->select_chars && dense_kernels) {
-    sp.packed = s.packed(), sp.exc_bits = s.d_exc_bits, sp.bpr = s.packed_bpr, sp.len = s.max_len;
-    s.select_packed = s.n_reads != 0;
-  }
-  sp.bases = s.map_bases();
-  sp.read_off = s.map_off();
-  sp.n_reads = (uint32_t)s.n_reads;
-  sp.read_begin = 0;
-  sp.lookup = h->d_lookup;
-  sp.occ = h->d_occ;
-  sp.inf32 = (uint32_t)h->n_occ;
-  sp.seq_len = h->d_seq_len;
-  sp.e = p.e, sp.a = p.a, sp.R = p.e + 1 + p.a, sp.k = p.k, sp.step = p.step;
+  if (pl.select_packed) sp.packed = s.packed(), sp.exc_bits = s.d_exc_bits, sp.bpr = s.packed_bpr, sp.len = s.max_len;
+  sp.bases = s.map_bases(), sp.read_off = s.map_off(), sp.n_reads = (uint32_t)s.n_reads;
+  sp.lookup = h->d_lookup, sp.occ = h->d_occ, sp.inf32 = (uint32_t)h->n_occ, sp.summary = h->d_summary;
+  sp.seq_len = h->d_seq_len, sp.n_seq = h->n_seq;
+  sp.e = p.e, sp.a = p.a, sp.R = pl.path.R, sp.k = p.k, sp.step = p.step;
   sp.lg = p.k / p.step + (p.k % p.step ? 1 : 0);
   sp.cand = s.d_cand, sp.cand_meta = s.d_meta, sp.cand_cap = s.cand_cap;
   sp.cand_begin = s.d_begin, sp.cand_count = s.d_count;
-  sp.ctr = d_ctr;
-  sp.work_cursor = (uint32_t *)(s.d_ctl + kCtlWorkCursor);
-  sp.stats = d_stats;
-  sp.arena = s.d_arena, sp.arena_cap = s.arena_cap, sp.arena_ctr = d_arena_ctr;
-  sp.lay = make_layout(p, std::max<uint32_t>(s.max_len, (uint32_t)p.k));
+  sp.ctr = ctl->ctr, sp.stats = ctl->stats, sp.work_cursor = &ctl->work[0].select;
+  sp.arena = s.d_arena, sp.arena_cap = s.arena_cap, sp.arena_ctr = ctl->arena_ctr;
+  sp.slow_queue = s.d_slow, sp.slow_cap = s.slow_cap;  // (work_queue: enqueue_generic)
+  sp.lay = pl.generic.lay;
+  return sp;
+}
 
-  sp.n_seq = h->n_seq;
-  sp.summary = h->d_summary;
-  sp.slow_queue = s.d_slow, sp.slow_cap = s.slow_cap;
-  sp.work_queue = nullptr;
-  const int R = p.e + 1 + p.a;
-  const bool use_fast = !h->force_generic && p.k == femk::kK && p.step == femk::kStep && R >= 1 && R <= femk::kMaxR;
+femk::VerifyParams verify_params(const fem_dev *h, const Slot &s, const BatchPlan &pl) {
+  CtlBlock *ctl = ctl_of(s);
+  femk::VerifyParams vp{};
+  vp.bases = s.map_bases(), vp.read_off = s.map_off();
+  vp.planes = h->d_planes, vp.seq_off = h->d_seq_off;
+  vp.cand = s.d_cand, vp.cand_meta = s.d_meta;
+  vp.ctr = ctl->ctr, vp.cand_cap = s.cand_cap, vp.e = s.params.e;
+  vp.ed = s.d_ed, vp.end = s.d_end;
+  vp.n_map = s.d_nmap, vp.stats = ctl->stats;
+  if (pl.verify_packed) vp.packed = s.packed(), vp.exc_bits = s.d_exc_bits, vp.bpr = s.packed_bpr, vp.len = s.max_len;
+  return vp;
+}
 
-  auto shape = [&](const femk::SeedLayout &lay, uint32_t *wpb_out, uint32_t *lds_out, uint32_t *grid_out) {
-    uint32_t wpb = std::min<uint32_t>(4u, std::max<uint32_t>(1u, (64u * 1024u) / lay.wave_bytes));
-    uint32_t lds_bytes = wpb * lay.wave_bytes;
-    uint32_t waves_per_cu = std::min<uint32_t>(32u, (160u * 1024u / lds_bytes) * wpb);
-    uint64_t blocks_wanted = (s.n_reads + wpb - 1) / wpb;
-    uint64_t blocks_resident = (uint64_t)h->n_cu * std::max<uint32_t>(1u, waves_per_cu / wpb);
-    *wpb_out = wpb, *lds_out = lds_bytes;
-    *grid_out = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(blocks_wanted, blocks_resident * 4));
-  };
-  if (sp.lay.wave_bytes > 64u * 1024u) return fail(h, FEM_ERR_UNSUPPORTED, "read too long for the device path");
-
-  if (s.n_reads) {
-    int rc;
-    const bool split_dense = use_fast && h->d_occ32 && h->d_freq11;
-    const bool overlap = split_dense && !h->no_overlap;
-    if (!overlap && h->have_kernels_done) HIP_TRY(h, hipStreamWaitEvent(s.stream, h->ev_kernels_done, 0));
-    femk::VerifyParams vp{};
-    vp.bases = s.map_bases(), vp.read_off = s.map_off();
-    vp.planes = h->d_planes, vp.seq_off = h->d_seq_off;
-    vp.cand = s.d_cand, vp.cand_meta = s.d_meta;
-    vp.ctr = d_ctr, vp.cand_cap = s.cand_cap, vp.e = p.e;
-    vp.ed = s.d_ed, vp.end = s.d_end;
-    vp.n_map = s.d_nmap, vp.stats = d_stats;
-    HIP_TRY(h, hipMemsetAsync(s.d_nmap, 0, (size_t)s.n_reads * sizeof(uint32_t), s.stream));
-    // grid-stride kernel: exactly the blocks that are resident together, or the ones that start late set the makespan
-    // A batch that came packed (equal-length reads, codes in d_packed_alloc) is verified straight from its 2-bit codes; every
-    // other one — mixed lengths, FEM_NO_PACK, the zero-copy character forms — from its characters.
-    const bool verify_packed = s.sent_packed && !h->verify_chars;
-    if (verify_packed) vp.packed = s.packed(), vp.exc_bits = s.d_exc_bits, vp.bpr = s.packed_bpr, vp.len = s.max_len;
-    void (*const verify)(femk::VerifyParams) = verify_packed ? femk::verify_kernel_packed : femk::verify_kernel;
-    int &v_per_cu = verify_packed ? h->verify_packed_blocks_per_cu : h->verify_blocks_per_cu;
-    if (v_per_cu == 0) {
-      const int nb = blocks_per_cu((const void *)verify, 256, 0);
-      v_per_cu = nb > 0 ? nb : 4;
-    }
-    const uint32_t vgrid = (uint32_t)h->n_cu * (uint32_t)v_per_cu;
-    if (split_dense) {
-      // dense index: seed selection for blocks of reads (fem_seed_select.hip.h), then the bitmap join on 32-bit
-      // coordinates, a wave per read (fem_seed_dense.hip.h)
-      const uint32_t max_len = std::max<uint32_t>(s.max_len, (uint32_t)p.k);
-      const bool banked = h->n_banks > 1;
-      const size_t want_sel = (size_t)s.n_reads * 6u * (size_t)R * h->n_banks;
-      HIP_TRY(h, s.d_sel.ensure(want_sel));
-      HIP_TRY(h, s.d_sel_hdr.ensure((size_t)s.n_reads));
-      femk::SeedParams fp = sp;
-      fp.occ32 = h->d_occ32, fp.list_shift = h->list_shift, fp.goff = h->d_goff, fp.blkseq = h->d_blkseq;
-      fp.freq11 = h->d_freq11, fp.sel = s.d_sel, fp.sel_hdr = s.d_sel_hdr;
-      fp.n_banks = h->n_banks, fp.bank_lo = h->d_bank_lo, fp.n_buckets = (uint32_t)(h->n_lookup - 1);
-      fp.blk_stride = (femk::kDenseRemap >> femk::kDenseBlkShift) + 1u;
-      for (uint32_t b = 0; b <= femk::kDenseMaxBanks; ++b) fp.bank_first[b] = h->bank_first[b];
-      // A batch committed to an idle device (enqueue_packed: s.parts > 1) is mapped in parts: part q's selection on the side
-      // stream as soon as its characters are in HBM, its join on the slot's stream behind its selection — beside the selection
-      // of part q + 1.  Any other batch is one part, selection and join on the slot's stream as before.
-      uint32_t select_lds = 0, select_threads = 256;
-      fp.lay = make_layout_select(p, max_len, fp.packed != nullptr);
-      if (fp.lay.wave_bytes > 64u * 1024u) return fail(h, FEM_ERR_UNSUPPORTED, "read too long for the device path");
-      const femk::SeedLayout lay_select = fp.lay;
-      femk::SeedLayout lay_join = make_layout_join(p, banked, !banked && h->list_shift != 0);
-      const uint32_t wpb_s = std::min<uint32_t>(4u, std::max<uint32_t>(1u, (64u * 1024u) / lay_select.wave_bytes));
-      const uint32_t wpb_j = std::min<uint32_t>(4u, std::max<uint32_t>(1u, (60u * 1024u) / lay_join.wave_bytes));
-      lay_join.picked = wpb_j * lay_join.wave_bytes;
-      const uint32_t lds_j = wpb_j * lay_join.wave_bytes + 64u * 8u;
-      const int which = banked ? 1 : h->list_shift ? 2 : 0;  // (join_kernel)
-      uint64_t per_cu_s, per_cu_j;
-      {
-        const uint32_t lds_bytes = wpb_s * lay_select.wave_bytes;
-        const uint64_t key = ((uint64_t)(fp.packed != nullptr) << 49) | ((uint64_t)banked << 48) | ((uint64_t)R << 40) | lds_bytes;
-        if (h->select_occ_key != key)
-          h->select_occ_key = key, h->select_occ_blocks = blocks_per_cu((const void *)select_kernel(R, banked, fp.packed != nullptr), (int)(64u * wpb_s), lds_bytes);
-        per_cu_s = h->select_occ_blocks > 0 ? (uint64_t)h->select_occ_blocks : std::max<uint64_t>(1, 160u * 1024u / lds_bytes);
-        if (overlap) per_cu_s = 1;  // (3.3 ms per 2.5 M reads of C3 with one block per CU as with five: sectors per second, not waves)
-        select_lds = lds_bytes, select_threads = 64u * wpb_s;
-      }
-      {
-        const uint64_t key = ((uint64_t)which << 48) | ((uint64_t)R << 40) | lds_j;
-        if (h->join_occ_key != key) h->join_occ_key = key, h->join_occ_blocks = blocks_per_cu((const void *)join_kernel(R, which), (int)(64u * wpb_j), lds_j);
-        per_cu_j = h->join_occ_blocks > 0 ? (uint64_t)h->join_occ_blocks : std::max<uint64_t>(1, 160u * 1024u / lds_j);
-        if (overlap) {
-          // leave one block of the next batch's seed_select_kernel room on every CU: registers (512 per lane and SIMD,
-          // handed out in eights), LDS (160 KB) and wave slots (8 per SIMD) of both kernels together
-          const uint32_t vj = (kernel_regs(R, true, which) + 7u) & ~7u, vs = (kernel_regs(R, false, banked ? 1 : 0, fp.packed != nullptr) + 7u) & ~7u;
-          const uint32_t wj = 64u * wpb_j / 256u ? 64u * wpb_j / 256u : 1u, ws = select_threads / 256u ? select_threads / 256u : 1u;  // waves per SIMD and block
-          const uint32_t lj = (lds_j + 511u) & ~511u, ls = (select_lds + 511u) & ~511u;  // (LDS is handed out in pieces of 512 bytes)
-          while (per_cu_j > 1 && (per_cu_j * wj * vj + ws * vs > 512u || per_cu_j * lj + ls > 160u * 1024u || per_cu_j * wj + ws > 8u)) --per_cu_j;
-        }
-      }
-      if (parts > 1 && !copied_in_parts) {  // (the copy went whole, on the slot's stream: the side stream starts behind it)
-        HIP_TRY(h, hipEventRecord(s.ev_zeroed, s.stream));
-        HIP_TRY(h, hipStreamWaitEvent(h->side_stream, s.ev_zeroed, 0));
-      }
-      for (int q = 0; q < parts; ++q) {
-        const uint32_t r_lo = parts > 1 ? part_begin[q] : 0u, r_hi = parts > 1 ? part_begin[q + 1] : (uint32_t)s.n_reads;
-        const uint64_t blocks_of_reads = ((uint64_t)(r_hi - r_lo) + femk::kReadBlock - 1) / femk::kReadBlock;
-        fp.read_begin = r_lo, fp.n_reads = r_hi;
-        hipStream_t st_sel = parts > 1 ? h->side_stream : s.stream;
-        {
-          fp.lay = lay_select;
-          if (parts > 1) {
-            if (copied_in_parts) HIP_TRY(h, hipStreamWaitEvent(st_sel, s.ev_part[q], 0));
-          } else if (overlap && h->have_select_done) {
-            HIP_TRY(h, hipStreamWaitEvent(s.stream, h->ev_select_done, 0));
-          }
-          const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((blocks_of_reads + wpb_s - 1) / wpb_s, (uint64_t)h->n_cu * per_cu_s));
-          fp.work_cursor = (uint32_t *)(s.d_ctl + kCtlWorkCursor + (size_t)q * kCtlPartStride);
-          rc = timed_launch(h, s, 8, st_sel, q == 0, [&] { launch_select(R, banked, dim3(grid), dim3(64u * wpb_s), select_lds, st_sel, fp); });
-          if (rc) return rc;
-          if (parts > 1) {
-            HIP_TRY(h, hipEventRecord(s.ev_sel[q], st_sel));
-            HIP_TRY(h, hipStreamWaitEvent(s.stream, s.ev_sel[q], 0));
-          }
-          if (overlap && q + 1 == parts) {
-            HIP_TRY(h, hipEventRecord(h->ev_select_done, st_sel));
-            h->have_select_done = true;
-          }
-          if (overlap && q == 0 && h->have_kernels_done) HIP_TRY(h, hipStreamWaitEvent(s.stream, h->ev_kernels_done, 0));
-        }
-        {
-          fp.lay = lay_join;
-          const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((blocks_of_reads + wpb_j - 1) / wpb_j, (uint64_t)h->n_cu * per_cu_j));
-          fp.work_cursor = (uint32_t *)(s.d_ctl + kCtlWorkCursor2 + (size_t)q * kCtlPartStride);
-          rc = timed_launch(h, s, 0, s.stream, q == 0, [&] { launch_join(R, which, dim3(grid), dim3(64u * wpb_j), lds_j, s.stream, fp); });
-          if (rc) return rc;
-        }
-      }
-      sp.work_queue = s.d_slow;  // the generic kernel finishes what the two queued
-    } else if (use_fast) {
-      femk::SeedParams fp = sp;
-      // long occurrence lists (dense index): the hash-join form of the kernel; short ones: lists in lanes only
-      const bool hash = h->force_hash || (double)h->n_occ > (double)h->n_lookup;
-      fp.lay = make_layout_fast(p, std::max<uint32_t>(s.max_len, (uint32_t)p.k), hash);
-      uint32_t wpb, lds_bytes, grid;
-      shape(fp.lay, &wpb, &lds_bytes, &grid);
-      {
-        // The kernel's waves pull blocks of reads from a cursor: the grid is exactly what is resident at a time
-        // (registers included).  (With a fixed stride per wave the same grid took 6.9 ms against 6.2 at six times as
-        // many waves: the CUs do not all run at the same pace.  Every wave pads its last chunk of candidate slots, so
-        // extra waves cost the verify kernel lanes.)  FEM_GRID_MULT overrides the multiple (measurement only).
-        const uint64_t key = ((uint64_t)R << 40) | ((uint64_t)hash << 32) | lds_bytes;
-        if (h->fast_occ_key != key) h->fast_occ_key = key, h->fast_occ_blocks = blocks_per_cu((const void *)fast_kernel((int)R, hash), (int)(64u * wpb), lds_bytes);
-        static const uint64_t mult = testing_switch("FEM_TESTING") && getenv("FEM_GRID_MULT") ? (uint64_t)std::max(1, atoi(getenv("FEM_GRID_MULT"))) : 1;
-        const uint64_t per_cu = h->fast_occ_blocks > 0 ? (uint64_t)h->fast_occ_blocks : std::max<uint64_t>(1, 160u * 1024u / lds_bytes);
-        const uint64_t wanted = (s.n_reads + (uint64_t)femk::kReadBlock * wpb - 1) / ((uint64_t)femk::kReadBlock * wpb);
-        grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(wanted, (uint64_t)h->n_cu * per_cu * mult));
-      }
-      auto launch_range = [&](uint32_t lo, uint32_t hi) {
-        femk::SeedParams q = fp;
-        q.read_begin = lo, q.n_reads = hi;
-        dim3 g(grid), b(64u * wpb);
-        launch_fast((int)R, hash, g, b, lds_bytes, s.stream, q);
-      };
-      rc = timed_launch(h, s, 0, s.stream, true, [&] { launch_range(0, (uint32_t)s.n_reads); });
-      if (rc) return rc;
-      sp.work_queue = s.d_slow;  // the generic kernel finishes what the fast one queued
-    }
-    {
-      uint32_t wpb, lds_bytes, grid;
-      shape(sp.lay, &wpb, &lds_bytes, &grid);
-      rc = timed_launch(h, s, 2, s.stream, true, [&] { hipLaunchKernelGGL(femk::seed_filter_kernel, dim3(grid), dim3(64u * wpb), lds_bytes, s.stream, sp); });
-      if (rc) return rc;
-    }
-    rc = timed_launch(h, s, 1, s.stream, true, [&] { hipLaunchKernelGGL(verify, dim3(vgrid), dim3(256), 0, s.stream, vp); });
-    if (rc) return rc;
-    s.packed_enqueued = false, s.packed_home = 0, s.packed_per_read_home = false;
-    // (the packing inside the chain of the batches' kernels, 0.07 ms: beside the next batch's join — three kernels starting at
-    //  once — it cost that join 0.6 ms; on a sparse index, where nothing runs beside the seed kernel, it goes behind the chain)
-    if (s.want_packed && split_dense && (rc = enqueue_pack(h, s, true, false))) return rc;
-    HIP_TRY(h, hipEventRecord(h->ev_kernels_done, s.stream));
-    h->have_kernels_done = true;
-    if (s.want_packed && (rc = enqueue_pack(h, s, !split_dense, true))) return rc;
-  } else {
-    s.packed_enqueued = false, s.packed_home = 0, s.packed_per_read_home = false;
+// Dense index: seed selection for blocks of reads (fem_seed_select.hip.h), then the bitmap join on 32-bit coordinates, a wave
+// per read (fem_seed_dense.hip.h).  A batch mapped in parts: part q's selection on the side stream as soon as its characters
+// are in HBM, its join on the slot's stream behind its selection — beside the selection of part q + 1.  Any other batch is one
+// part, selection and join on the slot's stream as before.
+int enqueue_dense(fem_dev *h, Slot &s, const BatchPlan &pl, femk::SeedParams fp) {
+  const SeedPath path = pl.path;
+  const int parts = pl.parts;
+  int rc;
+  HIP_TRY(h, s.d_sel.ensure((size_t)s.n_reads * 6u * (size_t)path.R * h->n_banks));
+  HIP_TRY(h, s.d_sel_hdr.ensure((size_t)s.n_reads));
+  fp.occ32 = h->d_occ32, fp.list_shift = h->list_shift, fp.goff = h->d_goff, fp.blkseq = h->d_blkseq;
+  fp.freq11 = h->d_freq11, fp.sel = s.d_sel, fp.sel_hdr = s.d_sel_hdr;
+  fp.n_banks = h->n_banks, fp.bank_lo = h->d_bank_lo, fp.n_buckets = (uint32_t)(h->n_lookup - 1);
+  fp.blk_stride = (femk::kDenseRemap >> femk::kDenseBlkShift) + 1u;
+  for (uint32_t b = 0; b <= femk::kDenseMaxBanks; ++b) fp.bank_first[b] = h->bank_first[b];
+  if (parts > 1 && !pl.copied_in_parts) {  // (the copy went whole, on the slot's stream: the side stream starts behind it)
+    HIP_TRY(h, hipEventRecord(s.ev_zeroed, s.stream));
+    HIP_TRY(h, hipStreamWaitEvent(h->side_stream, s.ev_zeroed, 0));
   }
-  HIP_TRY(h, hipMemcpyAsync(s.h_ctl, s.d_ctl, kCtlBytes, hipMemcpyDeviceToHost, s.stream));
+  hipStream_t st_sel = parts > 1 ? h->side_stream : s.stream;
+  for (int q = 0; q < parts; ++q) {
+    const uint32_t n_part = pl.part_begin[q + 1] - pl.part_begin[q];
+    fp.read_begin = pl.part_begin[q], fp.n_reads = pl.part_begin[q + 1];
+    CtlBlock::Work *cursors = &ctl_of(s)->work[q];
+    if (parts > 1) {
+      if (pl.copied_in_parts) HIP_TRY(h, hipStreamWaitEvent(st_sel, s.ev_part[q], 0));
+    } else if (pl.overlap && h->have_select_done) {
+      HIP_TRY(h, hipStreamWaitEvent(s.stream, h->ev_select_done, 0));
+    }
+    fp.lay = pl.select.lay, fp.work_cursor = &cursors->select;
+    const SeedKernel select = select_kernel(path.R, path.banked(), pl.select_packed);
+    if ((rc = timed_launch(h, s, 8, st_sel, q == 0, [&] { hipLaunchKernelGGL(select, pl.select.grid(n_part), pl.select.block(), pl.select.lds, st_sel, fp); }))) return rc;
+    if (parts > 1) {
+      HIP_TRY(h, hipEventRecord(s.ev_sel[q], st_sel));
+      HIP_TRY(h, hipStreamWaitEvent(s.stream, s.ev_sel[q], 0));
+    }
+    if (pl.overlap && q + 1 == parts) {
+      HIP_TRY(h, hipEventRecord(h->ev_select_done, st_sel));
+      h->have_select_done = true;
+    }
+    if (pl.overlap && q == 0 && h->have_kernels_done) HIP_TRY(h, hipStreamWaitEvent(s.stream, h->ev_kernels_done, 0));
+    fp.lay = pl.join.lay, fp.work_cursor = &cursors->join;
+    if ((rc = timed_launch(h, s, 0, s.stream, q == 0, [&] { hipLaunchKernelGGL(join_kernel(path), pl.join.grid(n_part), pl.join.block(), pl.join.lds, s.stream, fp); }))) return rc;
+  }
+  return FEM_OK;
+}
+
+// Sparse index: seed_fast_kernel over the whole batch, in the form the path names
+int enqueue_fast(fem_dev *h, Slot &s, const BatchPlan &pl, femk::SeedParams fp) {
+  const KernelShape &k = pl.fast;
+  const SeedKernel fast = fast_kernel(pl.path.R, pl.path.kind == SeedPath::kFastHash);
+  fp.lay = k.lay;
+  return timed_launch(h, s, 0, s.stream, true, [&] { hipLaunchKernelGGL(fast, k.grid(s.n_reads), k.block(), k.lds, s.stream, fp); });
+}
+// seed_filter_kernel: over every read on the generic path; behind the fast or the dense kernels it finishes what they queued
+int enqueue_generic(fem_dev *h, Slot &s, const BatchPlan &pl, femk::SeedParams sp) {
+  const KernelShape &k = pl.generic;
+  if (pl.path.kind != SeedPath::kGeneric) sp.work_queue = s.d_slow;
+  return timed_launch(h, s, 2, s.stream, true, [&] { hipLaunchKernelGGL(femk::seed_filter_kernel, k.grid(s.n_reads), k.block(), k.lds, s.stream, sp); });
+}
+int enqueue_verify(fem_dev *h, Slot &s, const BatchPlan &pl) {
+  const femk::VerifyParams vp = verify_params(h, s, pl);
+  const VerifyKernel verify = verify_kernel_of(pl.verify_packed);
+  return timed_launch(h, s, 1, s.stream, true, [&] { hipLaunchKernelGGL(verify, pl.verify.grid(s.n_reads), pl.verify.block(), 0, s.stream, vp); });
+}
+
+// fem_dev_fetch callers get the per-read arrays sent home behind the kernels, and the per-candidate arrays up to what the slot's
+// previous batch needed (Slot::prefetch_results) — on the slot's own stream.  (Tried: one stream for every slot's results
+// behind an event of the slot's stream — consistent 0.63 ms per 32 MB where a slot's own stream takes 0.6 to 1.5 beside the next
+// batch's H2D copy, but the calls that enqueue the copies then kept the host until the batch's kernels were through: 326 -> 284
+// Mreads/s.  Ten streams timed one by one all copy at 54 GB/s: the slow copies are the link shared with the other direction,
+// not a slow engine.)
+int enqueue_prefetch(fem_dev *h, Slot &s) {
   s.prefetched_reads2 = 0, s.prefetched_cand = 0;
   static const bool no_prefetch = testing_switch("FEM_NO_PREFETCH");
   // (only behind fem_dev_stage_reads, whose caller packs the next batch in the meantime; a caller of the zero-copy form is
   // idle until it fetches, and the extra traffic next to its four-times-larger H2D cost 5 % there)
-  if (s.prefetch_results && !s.want_packed && s.staged_by_copy && !no_prefetch) {
-    hipStream_t st = d2h_begin(h, s);
-    {
-      Span span(h, s, 21, st);
-      const size_t n2 = (size_t)s.n_reads * 2;
-      if (n2 && s.h_begin && n2 <= s.h_begin.size()) {
-        HIP_TRY(h, hipMemcpyAsync(s.h_begin, s.d_begin, n2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(h, hipMemcpyAsync(s.h_count, s.d_count, n2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        s.prefetched_reads2 = n2;
-      }
-      const size_t guess = std::min<size_t>({(size_t)(s.last_n_cand + s.last_n_cand / 32 + 1024), s.h_cand.size(), (size_t)s.cand_cap});
-      if (s.last_n_cand && s.h_cand && guess) {
-        HIP_TRY(h, hipMemcpyAsync(s.h_cand, s.d_cand, guess * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(h, hipMemcpyAsync(s.h_ed, s.d_ed, guess * sizeof(uint8_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(h, hipMemcpyAsync(s.h_end, s.d_end, guess * sizeof(int16_t), hipMemcpyDeviceToHost, st));
-        s.prefetched_cand = guess;
-      }
-    }
-    int rc2 = d2h_end(h, s, st);
-    if (rc2) return rc2;
+  if (!s.prefetch_results || s.want_packed || !s.staged_by_copy || no_prefetch) return FEM_OK;
+  Span span(h, s, 21, s.stream);
+  const size_t n2 = (size_t)s.n_reads * 2;
+  if (n2 && s.h_begin && n2 <= s.h_begin.size()) {
+    HIP_TRY(h, hipMemcpyAsync(s.h_begin, s.d_begin, n2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream));
+    HIP_TRY(h, hipMemcpyAsync(s.h_count, s.d_count, n2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream));
+    s.prefetched_reads2 = n2;
   }
-  s.mapped = true;
-  s.synced = false;
-  s.covered = false;
+  const size_t guess = std::min<size_t>({(size_t)(s.last_n_cand + s.last_n_cand / 32 + 1024), s.h_cand.size(), (size_t)s.cand_cap});
+  if (s.last_n_cand && s.h_cand && guess) {
+    HIP_TRY(h, hipMemcpyAsync(s.h_cand, s.d_cand, guess * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream));
+    HIP_TRY(h, hipMemcpyAsync(s.h_ed, s.d_ed, guess * sizeof(uint8_t), hipMemcpyDeviceToHost, s.stream));
+    HIP_TRY(h, hipMemcpyAsync(s.h_end, s.d_end, guess * sizeof(int16_t), hipMemcpyDeviceToHost, s.stream));
+    s.prefetched_cand = guess;
+  }
+  return FEM_OK;
+}
+
+// Enqueue one batch (asynchronous): its kernels as plan_batch has them — the path's seed kernels, the generic kernel, the
+// verification — on the slot's stream (a batch mapped in parts: its selections on the side stream), and behind them what
+// goes home.  Different batches' kernels are chained by the handle's events (fem_dev::ev_kernels_done, ev_select_done).
+int launch_batch(fem_dev *h, Slot &s) {
+  int rc;
+  BatchPlan pl;
+  if ((rc = plan_batch(h, s, pl))) return rc;
+  s.parts = 1;  // (consumed: the slot's batch mapped again starts from the device's state then)
+  // (a batch mapped in parts: zeroed on the side stream, ahead of the slot's stream, which may still be busy with the rest of its copy)
+  if (pl.parts > 1 && h->have_select_done) HIP_TRY(h, hipStreamWaitEvent(h->side_stream, h->ev_select_done, 0));
+  HIP_TRY(h, hipMemsetAsync(s.d_ctl, 0, kCtlAlloc, pl.parts > 1 ? h->side_stream.s : s.stream.s));
+  if (pl.need_chars && (rc = ensure_chars(h, s))) return rc;
+  s.select_packed = pl.select_packed && s.n_reads != 0;
+  s.packed_enqueued = false, s.packed_home = 0, s.packed_per_read_home = false;
+  if (s.n_reads) {
+    const bool dense = pl.path.dense();
+    const femk::SeedParams sp = seed_params(h, s, pl);
+    if (!pl.overlap && h->have_kernels_done) HIP_TRY(h, hipStreamWaitEvent(s.stream, h->ev_kernels_done, 0));
+    HIP_TRY(h, hipMemsetAsync(s.d_nmap, 0, (size_t)s.n_reads * sizeof(uint32_t), s.stream));  // (the verification counts into it)
+    if ((rc = dense ? enqueue_dense(h, s, pl, sp) : pl.path.fast() ? enqueue_fast(h, s, pl, sp) : FEM_OK)) return rc;
+    if ((rc = enqueue_generic(h, s, pl, sp))) return rc;
+    if ((rc = enqueue_verify(h, s, pl))) return rc;
+    // (the packing inside the chain of the batches' kernels, 0.07 ms: beside the next batch's join — three kernels starting at
+    //  once — it cost that join 0.6 ms; on a sparse index, where nothing runs beside the seed kernel, it goes behind the chain)
+    if (s.want_packed && dense && (rc = enqueue_pack(h, s, true, false))) return rc;
+    HIP_TRY(h, hipEventRecord(h->ev_kernels_done, s.stream));
+    h->have_kernels_done = true;
+    if (s.want_packed && (rc = enqueue_pack(h, s, !dense, true))) return rc;
+  }
+  HIP_TRY(h, hipMemcpyAsync(s.h_ctl, s.d_ctl, kCtlBytes, hipMemcpyDeviceToHost, s.stream));
+  if ((rc = enqueue_prefetch(h, s))) return rc;
+  s.mapped = true, s.synced = false, s.covered = false;
   return FEM_OK;
 }
 
@@ -1315,17 +1318,14 @@ int enqueue_packed(fem_dev *h, Slot &s, uint64_t n, uint32_t len, uint64_t n_exc
   HIP_TRY(h, s.d_exc_bits.ensure((size_t)n / 32 + 2));
   // parts: only where nothing is pending on the device (the start of a job), for batches without exceptions (their scatter
   // follows the whole batch) and of some size
-  s.parts = 1;
-  if (!h->no_parts && !h->no_overlap && n_exc == 0 && n >= 2 * kPartMinReads && device_idle(h))
-    s.parts = (int)std::min<uint64_t>((uint64_t)h->max_parts, n / kPartMinReads);
-  for (int q = 0; q <= s.parts; ++q) s.part_begin[q] = q == s.parts ? (uint32_t)n : (uint32_t)((n * q / s.parts) & ~63ull);
+  s.parts = plan_parts(h, n, n_exc == 0, s.part_begin);
   HIP_TRY(h, hipMemsetAsync(s.d_exc_bits, 0, ((size_t)n / 32 + 1) * sizeof(uint32_t), s.stream));
   // The characters are made here only where the selection is to read them (FEM_SELECT_CHARS) or where more than one read in
   // kExpandAllShare may be marked: expanding read by read then moves about as much as expanding the batch, less well.
   const bool at_commit = h->select_chars || n_exc * kExpandAllShare > n;
   // (a handle without the dense tables will ask for the characters when the batch is mapped: its offset table, which depends on
   //  nothing the copy brings, is still written here, in front of the copy — behind it it cost C2 6 us per step)
-  const bool offs_at_commit = at_commit || !(h->d_occ32 && h->d_freq11);
+  const bool offs_at_commit = at_commit || !has_dense_tables(h);
   if (offs_at_commit)
     hipLaunchKernelGGL(femk::uniform_offsets_kernel, dim3((uint32_t)std::min<uint64_t>((n + 256) / 256, (uint64_t)h->n_cu * 8u)), dim3(256), 0,
                        s.stream, s.d_off, n, len);
@@ -1534,7 +1534,7 @@ int fem_dev_open(int device, fem_dev **out) {
   for (int i = 0; ok_ev && i < kSlots; ++i) {
     Slot &sl = h->slot[i];
     ok_ev = sl.ev_zeroed.create(hipEventDisableTiming) == hipSuccess && sl.ev_results.create(hipEventDisableTiming) == hipSuccess &&
-            sl.ev_home.create(hipEventDisableTiming) == hipSuccess && sl.ev_chars.create(hipEventDisableTiming) == hipSuccess;
+            sl.ev_chars.create(hipEventDisableTiming) == hipSuccess;
     for (int q = 0; ok_ev && q < kMaxParts; ++q)
       ok_ev = sl.ev_part[q].create(hipEventDisableTiming) == hipSuccess && sl.ev_sel[q].create(hipEventDisableTiming) == hipSuccess;
   }
@@ -1960,37 +1960,35 @@ int fem_dev_sync(fem_dev *h, int slot) {
     HIP_TRY(h, hipStreamSynchronize(s.stream));  // (without the handle's lock: other slots' calls go on meanwhile)
     FEM_LOCK(h);
     drain_timing(h, s);
-    const uint32_t *ctr = (const uint32_t *)s.h_ctl.get();
-    const uint64_t *arena_ctr = (const uint64_t *)(s.h_ctl + 4 * sizeof(uint32_t));
-    const uint64_t *st = (const uint64_t *)(s.h_ctl + 4 * sizeof(uint32_t) + 2 * sizeof(uint64_t));
-    uint32_t flags = ctr[1];
+    const CtlBlock *ctl = ctl_home(s);
+    uint32_t flags = ctl->ctr[1];
     if (flags & femk::kFlagTooLarge)
       return fail(h, FEM_ERR_UNSUPPORTED, "a read selects more than 2^31 occurrence entries in one seed group");
     if (flags == 0) {
-      s.n_cand = ctr[0];
-      s.n_packed = ((const uint32_t *)(s.h_ctl + kCtlPackCursor))[0], s.n_big = ((const uint32_t *)(s.h_ctl + kCtlPackCursor))[1];
+      s.n_cand = ctl->ctr[0];
+      s.n_packed = ctl->pack_cursor[0], s.n_big = ctl->pack_cursor[1];
       s.stats[0] = s.n_reads;
-      s.stats[1] = st[3];
-      s.stats[2] = st[0];
-      s.stats[3] = st[1];
-      s.stats[4] = st[2];
+      s.stats[1] = ctl->stats[3];
+      s.stats[2] = ctl->stats[0];
+      s.stats[3] = ctl->stats[1];
+      s.stats[4] = ctl->stats[2];
       s.synced = true;
       return FEM_OK;
     }
     // scratch too small: grow exactly what was asked for and run the batch again
     if (flags & femk::kFlagCandOverflow) {
-      uint64_t want = (uint64_t)ctr[0] + ctr[0] / 8 + 1024;
+      uint64_t want = (uint64_t)ctl->ctr[0] + ctl->ctr[0] / 8 + 1024;
       if ((rc = grow_candidates(h, s, std::min<uint64_t>(want, 0xFFFFFFF0ull)))) return rc;
     }
     if (flags & femk::kFlagQueueOverflow) {
-      uint64_t want = (uint64_t)ctr[2] + ctr[2] / 8 + 4096;
+      uint64_t want = (uint64_t)ctl->ctr[2] + ctl->ctr[2] / 8 + 4096;
       s.d_slow.release();
       s.slow_cap = 0;
       if (s.d_slow.ensure(want) != hipSuccess) return fail(h, FEM_ERR_NOMEM, "slow-read queue does not fit in device memory");
       s.slow_cap = (uint32_t)std::min<uint64_t>(want, 0xFFFFFFF0ull);
     }
     if (flags & femk::kFlagArenaOverflow) {
-      uint64_t want = arena_ctr[1] + arena_ctr[1] / 8 + 1024;
+      uint64_t want = ctl->arena_ctr[1] + ctl->arena_ctr[1] / 8 + 1024;
       s.d_arena.release();
       if (s.d_arena.ensure(want) != hipSuccess) {
         s.arena_cap = 0;
@@ -2058,7 +2056,7 @@ int fem_dev_fetch_packed(fem_dev *h, int slot, fem_batch_packed *out) {
     if ((rc = enqueue_pack(h, s, true, false))) return rc;
     HIP_TRY(h, hipMemcpyAsync(s.h_ctl, s.d_ctl, kCtlBytes, hipMemcpyDeviceToHost, s.stream));
     HIP_TRY(h, hipStreamSynchronize(s.stream));
-    s.n_packed = ((const uint32_t *)(s.h_ctl + kCtlPackCursor))[0], s.n_big = ((const uint32_t *)(s.h_ctl + kCtlPackCursor))[1];
+    s.n_packed = ctl_home(s)->pack_cursor[0], s.n_big = ctl_home(s)->pack_cursor[1];
   }
   if (s.n_big > kBigCap) return fail(h, FEM_ERR_UNSUPPORTED, "more strands with 255 candidates and more than a packed result lists: use fem_dev_fetch");
   const size_t np = s.n_reads ? s.n_packed : 0;
@@ -2189,9 +2187,8 @@ int fem_dev_reserve_batch(fem_dev *h, int slot, uint64_t n_reads, uint64_t n_rec
   HIP_TRY(h, s.d_bases_alloc.ensure(kFrontPad + (size_t)n_bases + 64));
   HIP_TRY(h, s.d_off.ensure((size_t)n_reads + 1));
   HIP_TRY(h, s.d_exc_bits.ensure((size_t)n_reads / 32 + 2));
-  if (h->d_occ32 && h->d_freq11 && p->k == 12 && p->step == 3) {  // dense index: the selection's hand-over to the join
-    const size_t R = (size_t)(p->e + 1 + p->a);
-    HIP_TRY(h, s.d_sel.ensure((size_t)n_reads * 6u * R * h->n_banks));
+  if (const SeedPath path = seed_path(h, *p); path.dense()) {  // the selection's hand-over to the join
+    HIP_TRY(h, s.d_sel.ensure((size_t)n_reads * 6u * (size_t)path.R * h->n_banks));
     HIP_TRY(h, s.d_sel_hdr.ensure((size_t)n_reads));
   }
   // the mapping tail and the SAM text's bookkeeping
@@ -2848,7 +2845,7 @@ int fem_dev_index_info(const fem_dev *h, char *buf, uint64_t cap) {
   std::string s;
   if (!h->d_lookup) {
     s = "no index";
-  } else if (h->d_occ32 && h->d_freq11) {
+  } else if (has_dense_tables(h)) {
     s = "dense: 32-bit occurrence table, ";
     s += h->list_shift ? "strided with pads (" + std::to_string(((n_buckets + femk::kDensePadBuckets) << h->list_shift) * 4 >> 20) + " MiB)"
                        : "compact (" + std::to_string(h->n_occ * 4 >> 20) + " MiB)";
@@ -2865,11 +2862,9 @@ int fem_dev_index_info(const fem_dev *h, char *buf, uint64_t cap) {
 
 const char *fem_dev_seed_kernel(const fem_dev *h, const fem_params *p) {
   if (!h || !params_ok(p)) return "";
-  const int R = p->e + 1 + p->a;
-  const bool use_fast = !h->force_generic && p->k == femk::kK && p->step == femk::kStep && R >= 1 && R <= femk::kMaxR;
-  if (!use_fast) return "seed_filter_kernel";
-  if (h->d_occ32 && h->d_freq11) return h->n_banks > 1 ? "seed_join_banked_kernel" : "seed_join_kernel";
-  return (h->force_hash || (double)h->n_occ > (double)h->n_lookup) ? "seed_fast_kernel<hash>" : "seed_fast_kernel<lean>";
+  // (by SeedPath::Kind; the strided table's kernel goes by the compact one's name)
+  static const char *const names[] = {"seed_filter_kernel", "seed_fast_kernel<lean>", "seed_fast_kernel<hash>", "seed_join_kernel", "seed_join_banked_kernel", "seed_join_kernel"};
+  return names[seed_path(h, *p).kind];
 }
 
 int fem_dev_set_timing(fem_dev *h, int on) {

@@ -3,10 +3,13 @@ counters, a handle with reference, names and index uploaded, "stage reads and te
 comparisons of the device's arrays, texts and BAM with what tests/cases.py and the models expect.  Functions take explicit
 arguments; a test module that keeps its case in a dict wraps them in a line of its own.  No test module imports another: what
 two of them share lives here or in tests/cases.py."""
+import contextlib
 import gzip
 import os
 import struct
 import subprocess
+import sys
+import tempfile
 
 import numpy as np
 
@@ -61,6 +64,25 @@ def device_with_env(**env):
                 os.environ.pop(k)
             else:
                 os.environ[k] = v
+
+
+@contextlib.contextmanager
+def library_stderr():
+    """What the library writes to stderr inside the block (C stdio on file descriptor 2: the FEM_TIMELINE lines) -> a list
+    that holds the text once the block has ended."""
+    out = []
+    sys.stderr.flush()
+    saved = os.dup(2)
+    with tempfile.TemporaryFile() as f:
+        os.dup2(f.fileno(), 2)
+        try:
+            yield out
+        finally:
+            sys.stderr.flush()
+            os.dup2(saved, 2)
+            os.close(saved)
+            f.seek(0)
+            out.append(f.read().decode())
 
 
 def open_device(seqs, names, idx=None, k=12, step=3):
