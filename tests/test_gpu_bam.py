@@ -7,6 +7,7 @@ import pytest
 
 from oracle import fem_oracle as fo
 from tests import bam_model as bm
+from tests import deflate_model as dm
 from tests import util
 from tests.cases import make_rescue_pairs, write_case, write_fastq
 from tests.harness import bam_vs_sam, build_index, check_members, counters, decode_bam_file, open_device, open_sam_case, run_fem
@@ -32,6 +33,9 @@ def _compressor_inputs():
         "65280": bytes(rng.integers(0, 4, 65280, dtype=np.uint8) + 65),
         "65281": bytes(rng.integers(0, 4, 65281, dtype=np.uint8) + 65),
         "zeros": bytes(200_000), "random": rng.bytes(150_000),
+        "far32768": dm.far_match(32768), "far32767": dm.far_match(32767),
+        # random letters with a period of 32768 and of 32769: three members each, cut off the period, that compress by their
+        # 2-bit codes; of 64 three-letter words the latest occurrences are a few bytes back, so they say nothing of the window
         "dist32768": (period * 5)[:150_000], "dist32769": (period2 * 5)[:150_000],
         "runs258": b"".join(bytes([int(c)]) * int(n) for c, n in zip(rng.integers(0, 256, 2000), rng.integers(250, 600, 2000))),
         "illumina": bm.sam_to_bam_payload(bm.synthetic_sam(rng, 1500, 100, "illumina"), [b"chr1", b"chr2"]),
@@ -52,8 +56,8 @@ def test_compressor_alone(dev, level):
             assert all(m[2] == 0 for m in members), name
         elif name in ("zeros", "runs258", "dist32768", "illumina", "walk"):
             assert len(out) < len(data) // 2 if name != "walk" else len(out) < len(data), name
-        if level == 1 and name in ("dist32768",):  # matches at distance 32768 are found; 32769 is out of the window
-            assert len(out) < 0.5 * len(dev.bgzf_compress(data, 0))
+        if level == 1 and name in ("far32768", "far32767"):  # a 258-byte copy at the far end of the window is found
+            assert (258, int(name[3:])) in dm.inflate(out, 18)[0][0].tokens, name
 
 
 def test_compressor_ratio_against_zlib_level_1(dev):
